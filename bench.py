@@ -13,10 +13,18 @@ per evaluation, ell = 0,2,4,6), with the seeded dense synthetic distortion matri
 region.  With N ranks each rank evaluates its own B walkers per step (weak scaling) and the chi2
 vectors are exchanged with ONE all-gather per step (RCCL over xGMI).
 
-Rank 0 prints one JSON line.  Extra objects:
+Rank 0 prints one JSON line.  A plain run sets up, warms up (clock ramp + the W warm-up steps), times the K steps and
+prints `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload's `config`; nothing else.
+`--dump-outputs DIR` writes what the timed path returned in its last step (DIR/chi2.npy: the chi2 vector, float64; with
+N > 1 ranks the gathered vector of all ranks, rank-major).  The same arguments give the same inputs in every run.
+
+`--full` adds everything else the benchmark measures (with `--core-only`: the calibration pass and the sections that come
+from the timed steps' own events, no side sections):
   roofline      the distortion-matrix step (the kernel SURVEY.md section 8d prices: fp64 MFMA at B = 256), timed live
                 with HIP events over the timed steps; roofline_other_kernels: the other heavy kernels, among them
                 the P(k,mu) stage (fp64 vector ALU), from the calibration pass
+  single_lane, regions, exact_mu_loop, other_paths, metals, monte_carlo_fits, single_point, distortion_csr
+                the other legs (each function says what it measures)
   distortion    the B = 1 distortion-matrix product of configs[1] (2500^2 fp64): GB/s vs HBM
   cpu_baseline  the CPU oracle (NumPy restatement of the reference) timed on this host
 """
@@ -497,12 +505,14 @@ def launch_ranks(args):
         s.bind(('127.0.0.1', 0))
         port = s.getsockname()[1]
     procs = []
+    # (the ranks run in the repository: a relative --dump-outputs is made the caller's, the last occurrence being the one argparse keeps)
+    argv = sys.argv[1:] + (['--dump-outputs', str(Path(args.dump_outputs).resolve())] if args.dump_outputs else [])
     for r in range(args.gpus):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(0 if args.ranks_share_gpu else r), WORLD_SIZE=str(args.gpus),
                    LOCAL_WORLD_SIZE=str(args.gpus), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
         env.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')       # the host driver only supports dmabuf IPC (RCCL needs it)
         env.setdefault('OMP_NUM_THREADS', '1')
-        procs.append(subprocess.Popen([sys.executable, str(Path(__file__).resolve())] + sys.argv[1:], env=env, cwd=str(REPO),
+        procs.append(subprocess.Popen([sys.executable, str(Path(__file__).resolve())] + argv, env=env, cwd=str(REPO),
                                       stdout=subprocess.PIPE if r == 0 else sys.stderr, stderr=sys.stderr))
     # rank 0's stdout is drained by a reader thread while the ranks are polled: the other ranks sit in the final barrier until rank
     # 0 has written its line, and a line larger than the pipe's buffer (64 KB; it is ~15 KB today and grows) must not block it
@@ -552,8 +562,14 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--ramp-steps', type=int, default=150, help='untimed steps before the calibration pass (clock ramp); half as many again before the W warm-up steps')
     ap.add_argument('--event-stride', type=int, default=2, help='HIP-event pairs around every n-th launch of the roofline kernel in the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline figure: calibration pass, roofline, one-lane and repeated regions, the '
+                         'other paths, the side sections and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the chi2 vector of the last timed step to DIR/chi2.npy (float64)')
     ap.add_argument('--core-only', action='store_true',
-                    help='calibration + warm-up + timed steps only (the command the rocprofv3 summaries in profiles/ use)')
+                    help='calibration + warm-up + timed steps only (the command the rocprofv3 summaries in profiles/ use): the '
+                         'measurements of --full that come from the timed steps, without the side sections')
     ap.add_argument('--no-static-metals', action='store_true', help='keep every metal pair on its own pipeline')
     ap.add_argument('--force-dist', action='store_true', help='run the collective path even with one rank')
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
@@ -568,6 +584,10 @@ def main():
         ap.error('--ranks-share-gpu needs --dist-backend gloo (RCCL refuses two ranks on one device)')
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(launch_ranks(args))
+    # a plain run measures the headline figure only; `measure`: the per-kernel events and the regions around the timed steps
+    # (--full, --core-only), `extras`: the side sections and the CPU baseline (--full)
+    measure = args.full or args.core_only
+    extras = args.full and not args.core_only
 
     # stdout carries the one JSON line and nothing else: whatever libraries print there (RCCL's version banner when a
     # communicator is first used, for one) goes to stderr until the line is written
@@ -591,12 +611,21 @@ def main():
     # others wait on the lock - not in a barrier
     import fcntl
     import __graft_entry__ as entry
-    with open(REPO / 'vega_amd' / '.build.lock', 'w') as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            entry.build()
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+    try:
+        lock = open(REPO / 'vega_amd' / '.build.lock', 'w')
+    except OSError:
+        # a tree this process may not write to (built beforehand by its owner): it can compile nothing into it either, so
+        # build() only loads and checks the library that is there
+        lock = None
+    if lock is None:
+        entry.build()
+    else:
+        with lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            try:
+                entry.build()
+            finally:
+                fcntl.flock(lock, fcntl.LOCK_UN)
 
     B = args.batch
     prob = build_problem(args.workload)
@@ -608,7 +637,7 @@ def main():
     # the CPU baseline runs first, on rank 0 of the N = 1 run, before this process touches the GPU
     cpu = cpu_idx = cpu_vals = general_vals = None
     general_theta = synthetic.walkers(low.theta0, low.names, B, varied=VARIED + GENERAL_EXTRA, seed=synthetic.SEED + 555)
-    if rank == 0 and world == 1 and not args.core_only and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and extras and not args.no_cpu_baseline:
         cpu, cpu_idx, cpu_vals, general_vals = cpu_baseline(args.workload, low.names, host_theta,
                                                             extra_theta=general_theta[:16])
 
@@ -737,23 +766,24 @@ def main():
     for i in range(max(args.warmup, 3) * L + args.ramp_steps):
         step(i)
     sync_all()
-    eng.set_profiling(True)         # (every class timed: the engine keeps one batch in flight - uncontended kernel durations)
-    for i in range(3):
-        step(i)
-    eng.sync()
-    eng.timings(reset=True)
-    for i in range(5):
-        step(i)
-    eng.sync()
-    breakdown = eng.timings(reset=True)
-    dominant = max((k for k, v in breakdown.items() if v[1]), key=lambda k: breakdown[k][0])
-    # SURVEY.md section 8d prices the roofline on the distortion-matrix step; the class with the largest total is timed too
-    # ... which chi2-only steps run as the quadratic-form product (one half-triangle MFMA product per item in place
-    # of the distortion and C^-1 products, include/vegamx.h: vmx_set_quadratic_form)
-    roof_class = next((k for k in ('quadratic_form_product', 'distortion_product') if breakdown.get(k, (0, 0))[1]), dominant)
-    # ... and around every second launch of it: with K = 20 steps on two lanes that is still five live samples of the
-    # roofline kernel inside the timed region, at half the perturbation
-    eng.set_profiling_classes(sorted({roof_class, dominant}), stride=args.event_stride)
+    if measure:
+        eng.set_profiling(True)         # (every class timed: the engine keeps one batch in flight - uncontended kernel durations)
+        for i in range(3):
+            step(i)
+        eng.sync()
+        eng.timings(reset=True)
+        for i in range(5):
+            step(i)
+        eng.sync()
+        breakdown = eng.timings(reset=True)
+        dominant = max((k for k, v in breakdown.items() if v[1]), key=lambda k: breakdown[k][0])
+        # SURVEY.md section 8d prices the roofline on the distortion-matrix step; the class with the largest total is timed too
+        # ... which chi2-only steps run as the quadratic-form product (one half-triangle MFMA product per item in place
+        # of the distortion and C^-1 products, include/vegamx.h: vmx_set_quadratic_form)
+        roof_class = next((k for k in ('quadratic_form_product', 'distortion_product') if breakdown.get(k, (0, 0))[1]), dominant)
+        # ... and around every second launch of it: with K = 20 steps on two lanes that is still five live samples of the
+        # roofline kernel inside the timed region, at half the perturbation
+        eng.set_profiling_classes(sorted({roof_class, dominant}), stride=args.event_stride)
 
     # (the calibration pass idles the queue between its event pairs: ramp again, until two consecutive 20-step blocks agree
     # to 1 % - the clocks have settled -, at most `ramp_steps` blocks; then the W warm-up steps of the contract)
@@ -776,7 +806,8 @@ def main():
         step(i)
     sync_all()
     torch.cuda.synchronize()
-    eng.timings(reset=True)
+    if measure:
+        eng.timings(reset=True)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -791,12 +822,18 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     gather_clock['on'] = False
-    timings = eng.timings(reset=True)
-    eng.set_profiling(False)
+    timings = {}
+    if measure:
+        timings = eng.timings(reset=True)
+        eng.set_profiling(False)
+    # what the timed path handed its caller in the last step, kept before any later step reuses the buffers: the chi2
+    # vector (with N > 1 ranks the gathered one, every rank's block in rank order)
+    last_slot = (args.steps - 1) % nslot
+    last_chi2 = (gathered[last_slot] if use_dist else chi2_bufs[last_slot]).cpu().numpy().copy() if args.dump_outputs else None
 
     single_lane = None
     single_timings = None
-    if L > 1:
+    if measure and L > 1:
         # (with N > 1 ranks every rank runs this section too: the steps carry the collective, so the ranks stay in step)
         # the same steps with ONE batch in flight (vmx_set_lanes(1)): what a caller gets whose next batch depends on this one's
         # chi2.  With two lanes (`value`) consecutive batches overlap: one lane's launch tails and small kernels are filled
@@ -825,11 +862,11 @@ def main():
             step(i)
         sync_all()
 
-    pk_state = engines[0].debug_read(4, 0, 5)       # live wavenumbers, node-rule tiles and table level of the timed steps
+    pk_state = engines[0].debug_read(4, 0, 5) if measure else None     # live wavenumbers, node-rule tiles, table level of the timed steps
     # the same K steps a few more times: `value` above is ONE region of K steps (the contract); the spread between regions
     # of a few milliseconds each is reported beside it
     regions = None
-    if not use_dist:
+    if measure and not use_dist:
         rates = []
         for _ in range(5):
             sync_all()
@@ -856,7 +893,7 @@ def main():
         return B * reps / (time.perf_counter() - t0)
 
     other_paths = None
-    if not use_dist and not args.core_only:
+    if extras and not use_dist:
         # The other ways through the same engine, same workload, same B (none of them is `value`):
         #   general_walkers  walkers that also differ in Arinyo / smoothing / peak-broadening parameters (no tables)
         #   full_chain       the model is asked for (compute_model_batch): distortion + C^-1 products instead of Q'
@@ -897,7 +934,7 @@ def main():
         other_paths['host_entry'] = entry
 
     exact_mu = None
-    if not use_dist and not args.core_only:
+    if extras and not use_dist:
         # the same steps with the reference's 1000-point mu loop itself instead of the node rule that reproduces its sums
         # (include/vegamx.h: vmx_set_mu_quadrature) - reported beside `value`, and the two must agree
         ref_chi2 = chi2_bufs[(args.steps - 1) % nslot].clone()
@@ -980,115 +1017,117 @@ def main():
     if rank == 0:
         total_evals = B * args.steps * world
         value = total_evals / elapsed
-        kernels = {k: {'ms_per_launch': v[0] / v[1], 'launches_per_step': v[1] // 5, 'ms_per_step': v[0] / 5}
-                   for k, v in breakdown.items() if v[1]}
-        live = {k: {'ms_per_launch': timings[k][0] / timings[k][1], 'launches': timings[k][1]}
-                for k in {roof_class, dominant}}
-        n_items = len(prob.items)
-
-        def roofline_for(kclass, ms_per_launch):
-            if kclass == 'pk_multipoles':
-                # (k, mu) points the stage evaluates per walker and item: the live wavenumbers of the step (blocks whose
-                # every value underflows are skipped) x the mu nodes of each - 178 where the node rule applies, 1000 above
-                k_live, k_node_max, n_nodes, k_rule, level = pk_state
-                points = float(np.where(np.arange(int(k_live)) < k_rule, n_nodes, 1000).sum())
-                per_point = FLOPS_PER_POINT_TAB2 if level >= 2 else FLOPS_PER_POINT
-                flops = 0.0
-                for item in prob.items.values():
-                    kind = 'auto' if item.tracer1.name == item.tracer2.name else 'cross'
-                    flops += B * points * per_point[kind]          # one paired pass per item
-                bound, peak, reach = 'valu-fp64', FP64_VALU_PEAK_TF, FP64_VALU_MEASURED_TF
-            elif kclass == 'quadratic_form_product':
-                # x'^T Q' x' in half form: nq^2 flops per walker and item, nq = n_model + additive post-distortion coefficients
-                nqs = []
-                for it in prob.items.values():
-                    na = sum(len(range(t.r1[0], t.r1[1] + 1, t.r1[2])) * len(range(t.r2[0], t.r2[1] + 1, t.r2[2]))
-                             for t in it.broadband if t.pos == 'post' and t.kind == 'add')
-                    nqs.append(it.model_grid.size + na)
-                flops = float(sum(n * n for n in nqs)) * B
-                if kernels[kclass]['launches_per_step'] > 1:
-                    flops /= len(nqs)
-                bound, peak, reach = 'mfma', FP64_MFMA_PEAK_TF, FP64_MFMA_4X4X4_MEASURED_TF
-            elif kclass in ('distortion_product', 'invcov_product'):
-                # (the FFTLog product is left out: its launch skips the operator rows and columns outside the batch's live
-                # ranges, so a flop count of the full operator would overstate it)
-                if kclass == 'distortion_product':
-                    shapes = [(it.dist_grid.size, it.model_grid.size) for it in prob.items.values()]
-                elif kclass == 'invcov_product':
-                    shapes = [(it.data_size, it.data_size) for it in prob.items.values()]
-                else:
-                    shapes = [(816, 814)] * 4
-                n_vec = B * (4 * n_items // 2 if kclass == 'fftlog_spline_product' else 1)
-                flops = sum(2.0 * m * n * n_vec for m, n in shapes)
-                if kclass == 'invcov_product':
-                    flops /= 2.0            # the half (lower-triangular) form of the symmetric inverse covariance
-                # the FFTLog launch covers all ell and, for B > 8, one launch covers every item's product
-                if kclass != 'fftlog_spline_product' and kernels[kclass]['launches_per_step'] > 1:
-                    flops /= len(shapes)
-                bound, peak = 'mfma', FP64_MFMA_PEAK_TF
-                reach = FP64_MFMA_4X4X4_MEASURED_TF if kclass == 'distortion_product' else FP64_MFMA_MEASURED_TF
-            else:
-                return None
-            tf = flops / (ms_per_launch * 1e-3) / 1e12
-            return {'kernel': kclass, 'bound': bound, 'achieved': tf, 'peak': peak, 'unit': 'TFLOP/s',
-                    'frac': tf / peak, 'traffic': None, 'algorithmic_flops_per_launch': flops,
-                    'ms_per_launch': ms_per_launch, 'instruction_issue_ceiling': reach,
-                    'frac_of_issue_ceiling': tf / reach}
-
-        # The roofline kernel is timed live (HIP events on its stream) in BOTH timed regions.  With two batches in flight a
-        # launch shares the chip with the other lane's kernels, so its duration there says what the lanes do to each other, not
-        # what the kernel reaches: `roofline` is the one-batch-in-flight region (`single_lane`: the same K steps, same events),
-        # `roofline.two_lane_region` the same launch inside the region `value` is measured on.
-        live2 = None
-        if single_timings is not None and single_timings[roof_class][1]:
-            live2 = live
-            live = {k: {'ms_per_launch': single_timings[k][0] / single_timings[k][1], 'launches': single_timings[k][1]}
+        roofline = roofline_other = kernels = None
+        if measure:
+            kernels = {k: {'ms_per_launch': v[0] / v[1], 'launches_per_step': v[1] // 5, 'ms_per_step': v[0] / 5}
+                       for k, v in breakdown.items() if v[1]}
+            live = {k: {'ms_per_launch': timings[k][0] / timings[k][1], 'launches': timings[k][1]}
                     for k in {roof_class, dominant}}
-        roofline = roofline_for(roof_class, live[roof_class]['ms_per_launch'])
-        # HBM bytes per launch come from separate rocprofv3 --pmc passes of `bench.py --core-only` (a counter pass
-        # cannot run inside this process): the committed summary of the latest collection is attached when present
-        traffic_file = latest_profile('bench_core_traffic.json')
-        traffic = json.loads(traffic_file.read_text())['kernels'] if traffic_file is not None else {}
-        if roofline is not None and roof_class in traffic and args.workload == 'joint' and B == 256:
-            roofline['traffic'] = traffic[roof_class]['hbm_bytes_per_launch']
-            roofline['traffic_unit'] = f'bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, profiles/{traffic_file.name})'
-            roofline['algorithmic_bytes_per_launch'] = traffic[roof_class]['algorithmic_bytes_per_launch']
-            roofline['traffic_over_algorithmic'] = roofline['traffic'] / roofline['algorithmic_bytes_per_launch']
-            # the counter passes belong to the kernel as it was when they were collected: their launch duration travels with
-            # them, and a live duration that has moved away from it says the file is due for a refresh
-            collected_us = traffic[roof_class].get('avg_us_kernel_trace_run')
-            if collected_us:
-                roofline['traffic_collected_at_us_per_launch'] = collected_us
-                roofline['traffic_stale'] = bool(abs(live[roof_class]['ms_per_launch'] * 1e3 / collected_us - 1.0) > 0.1)
-        if roofline is not None:
-            roofline['launches_timed'] = live[roof_class]['launches']
-            roofline['timing'] = 'HIP events on the launch stream, over the timed region'
-            if live2 is not None:
-                roofline['timing'] = (f'HIP events on the launch stream over the {args.steps} timed steps of the one-batch-in-flight '
-                                      'region (`single_lane`); `two_lane_region`: the same events inside the region `value` '
-                                      'is measured on (every second launch of lane 0), where the other lane\'s kernels share the chip')
-                r2 = roofline_for(roof_class, live2[roof_class]['ms_per_launch'])
-                roofline['two_lane_region'] = {k: r2[k] for k in ('achieved', 'frac', 'ms_per_launch', 'frac_of_issue_ceiling')}
-                roofline['two_lane_region']['launches_timed'] = live2[roof_class]['launches']
-                roofline['calibration_pass'] = {k: roofline_for(roof_class, kernels[roof_class]['ms_per_launch'])[k]
-                                                for k in ('achieved', 'frac', 'ms_per_launch')}
-        roofline_other = []
-        for k, v in kernels.items():
-            if k == roof_class:
-                continue
-            timed = k in live
-            r = roofline_for(k, live[k]['ms_per_launch'] if timed else v['ms_per_launch'])
-            if r is not None:
-                r['timing'] = 'HIP events over the timed region' if timed else 'calibration pass'
-                r['largest_total_time'] = k == dominant
-                roofline_other.append(r)
-        extras = not args.core_only and world == 1        # the side sections and the CPU baseline belong to the N = 1 run
-        distortion = distortion_microbench(eng, torch) if extras else None
-        single = single_point_latency(local_rank) if extras else None
-        dist_csr = distortion_csr(local_rank) if extras else None
-        mc_fits = monte_carlo_fits(prob, local_rank) if extras and args.workload == 'joint' else None
-        metals = metals_throughput(local_rank) if extras and args.workload == 'joint' else None
-        if other_paths is not None and extras and args.workload == 'joint':
+            n_items = len(prob.items)
+
+            def roofline_for(kclass, ms_per_launch):
+                if kclass == 'pk_multipoles':
+                    # (k, mu) points the stage evaluates per walker and item: the live wavenumbers of the step (blocks whose
+                    # every value underflows are skipped) x the mu nodes of each - 178 where the node rule applies, 1000 above
+                    k_live, k_node_max, n_nodes, k_rule, level = pk_state
+                    points = float(np.where(np.arange(int(k_live)) < k_rule, n_nodes, 1000).sum())
+                    per_point = FLOPS_PER_POINT_TAB2 if level >= 2 else FLOPS_PER_POINT
+                    flops = 0.0
+                    for item in prob.items.values():
+                        kind = 'auto' if item.tracer1.name == item.tracer2.name else 'cross'
+                        flops += B * points * per_point[kind]          # one paired pass per item
+                    bound, peak, reach = 'valu-fp64', FP64_VALU_PEAK_TF, FP64_VALU_MEASURED_TF
+                elif kclass == 'quadratic_form_product':
+                    # x'^T Q' x' in half form: nq^2 flops per walker and item, nq = n_model + additive post-distortion coefficients
+                    nqs = []
+                    for it in prob.items.values():
+                        na = sum(len(range(t.r1[0], t.r1[1] + 1, t.r1[2])) * len(range(t.r2[0], t.r2[1] + 1, t.r2[2]))
+                                 for t in it.broadband if t.pos == 'post' and t.kind == 'add')
+                        nqs.append(it.model_grid.size + na)
+                    flops = float(sum(n * n for n in nqs)) * B
+                    if kernels[kclass]['launches_per_step'] > 1:
+                        flops /= len(nqs)
+                    bound, peak, reach = 'mfma', FP64_MFMA_PEAK_TF, FP64_MFMA_4X4X4_MEASURED_TF
+                elif kclass in ('distortion_product', 'invcov_product'):
+                    # (the FFTLog product is left out: its launch skips the operator rows and columns outside the batch's live
+                    # ranges, so a flop count of the full operator would overstate it)
+                    if kclass == 'distortion_product':
+                        shapes = [(it.dist_grid.size, it.model_grid.size) for it in prob.items.values()]
+                    elif kclass == 'invcov_product':
+                        shapes = [(it.data_size, it.data_size) for it in prob.items.values()]
+                    else:
+                        shapes = [(816, 814)] * 4
+                    n_vec = B * (4 * n_items // 2 if kclass == 'fftlog_spline_product' else 1)
+                    flops = sum(2.0 * m * n * n_vec for m, n in shapes)
+                    if kclass == 'invcov_product':
+                        flops /= 2.0            # the half (lower-triangular) form of the symmetric inverse covariance
+                    # the FFTLog launch covers all ell and, for B > 8, one launch covers every item's product
+                    if kclass != 'fftlog_spline_product' and kernels[kclass]['launches_per_step'] > 1:
+                        flops /= len(shapes)
+                    bound, peak = 'mfma', FP64_MFMA_PEAK_TF
+                    reach = FP64_MFMA_4X4X4_MEASURED_TF if kclass == 'distortion_product' else FP64_MFMA_MEASURED_TF
+                else:
+                    return None
+                tf = flops / (ms_per_launch * 1e-3) / 1e12
+                return {'kernel': kclass, 'bound': bound, 'achieved': tf, 'peak': peak, 'unit': 'TFLOP/s',
+                        'frac': tf / peak, 'traffic': None, 'algorithmic_flops_per_launch': flops,
+                        'ms_per_launch': ms_per_launch, 'instruction_issue_ceiling': reach,
+                        'frac_of_issue_ceiling': tf / reach}
+
+            # The roofline kernel is timed live (HIP events on its stream) in BOTH timed regions.  With two batches in flight a
+            # launch shares the chip with the other lane's kernels, so its duration there says what the lanes do to each other, not
+            # what the kernel reaches: `roofline` is the one-batch-in-flight region (`single_lane`: the same K steps, same events),
+            # `roofline.two_lane_region` the same launch inside the region `value` is measured on.
+            live2 = None
+            if single_timings is not None and single_timings[roof_class][1]:
+                live2 = live
+                live = {k: {'ms_per_launch': single_timings[k][0] / single_timings[k][1], 'launches': single_timings[k][1]}
+                        for k in {roof_class, dominant}}
+            roofline = roofline_for(roof_class, live[roof_class]['ms_per_launch'])
+            # HBM bytes per launch come from separate rocprofv3 --pmc passes of `bench.py --core-only` (a counter pass
+            # cannot run inside this process): the committed summary of the latest collection is attached when present
+            traffic_file = latest_profile('bench_core_traffic.json')
+            traffic = json.loads(traffic_file.read_text())['kernels'] if traffic_file is not None else {}
+            if roofline is not None and roof_class in traffic and args.workload == 'joint' and B == 256:
+                roofline['traffic'] = traffic[roof_class]['hbm_bytes_per_launch']
+                roofline['traffic_unit'] = f'bytes per launch (FETCH_SIZE x 2 + WRITE_SIZE, profiles/{traffic_file.name})'
+                roofline['algorithmic_bytes_per_launch'] = traffic[roof_class]['algorithmic_bytes_per_launch']
+                roofline['traffic_over_algorithmic'] = roofline['traffic'] / roofline['algorithmic_bytes_per_launch']
+                # the counter passes belong to the kernel as it was when they were collected: their launch duration travels with
+                # them, and a live duration that has moved away from it says the file is due for a refresh
+                collected_us = traffic[roof_class].get('avg_us_kernel_trace_run')
+                if collected_us:
+                    roofline['traffic_collected_at_us_per_launch'] = collected_us
+                    roofline['traffic_stale'] = bool(abs(live[roof_class]['ms_per_launch'] * 1e3 / collected_us - 1.0) > 0.1)
+            if roofline is not None:
+                roofline['launches_timed'] = live[roof_class]['launches']
+                roofline['timing'] = 'HIP events on the launch stream, over the timed region'
+                if live2 is not None:
+                    roofline['timing'] = (f'HIP events on the launch stream over the {args.steps} timed steps of the one-batch-in-flight '
+                                          'region (`single_lane`); `two_lane_region`: the same events inside the region `value` '
+                                          'is measured on (every second launch of lane 0), where the other lane\'s kernels share the chip')
+                    r2 = roofline_for(roof_class, live2[roof_class]['ms_per_launch'])
+                    roofline['two_lane_region'] = {k: r2[k] for k in ('achieved', 'frac', 'ms_per_launch', 'frac_of_issue_ceiling')}
+                    roofline['two_lane_region']['launches_timed'] = live2[roof_class]['launches']
+                    roofline['calibration_pass'] = {k: roofline_for(roof_class, kernels[roof_class]['ms_per_launch'])[k]
+                                                    for k in ('achieved', 'frac', 'ms_per_launch')}
+            roofline_other = []
+            for k, v in kernels.items():
+                if k == roof_class:
+                    continue
+                timed = k in live
+                r = roofline_for(k, live[k]['ms_per_launch'] if timed else v['ms_per_launch'])
+                if r is not None:
+                    r['timing'] = 'HIP events over the timed region' if timed else 'calibration pass'
+                    r['largest_total_time'] = k == dominant
+                    roofline_other.append(r)
+        side = extras and world == 1        # the side sections and the CPU baseline belong to the N = 1 run
+        distortion = distortion_microbench(eng, torch) if side else None
+        single = single_point_latency(local_rank) if side else None
+        dist_csr = distortion_csr(local_rank) if side else None
+        mc_fits = monte_carlo_fits(prob, local_rank) if side and args.workload == 'joint' else None
+        metals = metals_throughput(local_rank) if side and args.workload == 'joint' else None
+        if other_paths is not None and side and args.workload == 'joint':
             other_paths['coefmod2'] = coefmod_throughput(local_rank)
         if cpu is not None:
             got = vega.chi2_batch(host_theta[cpu_idx])
@@ -1110,13 +1149,20 @@ def main():
                        'varied_parameters': [v for v in VARIED if v in eng.low.slot],
                        'collective': communicator if use_dist else 'none',
                        'cpu_affinity': affinity,
-                       'steady_state': f'untimed before the timed region: {args.ramp_steps} ramp steps, a calibration pass, 20-step '
-                                       f'blocks until two agree to 1 % (clock ramp), then the {args.warmup} warm-up steps - '
-                                       '`value` is a warmed steady state'},
-            'roofline': roofline, 'roofline_other_kernels': roofline_other, 'distortion': distortion, 'distortion_csr': dist_csr, 'single_point': single, 'metals': metals, 'monte_carlo_fits': mc_fits, 'single_lane': single_lane, 'exact_mu_loop': exact_mu, 'regions': regions, 'other_paths': other_paths, 'cpu_baseline': cpu,
-            'pk_stage': dict(zip(('k_live', 'k_node_max', 'mu_nodes', 'k_on_node_rule', 'table_level'), [float(v) for v in pk_state])),
-            'kernels': kernels, 'kernels_note': 'calibration pass before the timed region, event pairs around every kernel',
+                       'steady_state': f'untimed before the timed region: {args.ramp_steps} ramp steps, '
+                                       f'{"a calibration pass, " if measure else ""}20-step blocks until two agree to 1 % (clock '
+                                       f'ramp), then the {args.warmup} warm-up steps - `value` is a warmed steady state'},
         }
+        if measure:
+            out.update({
+                'roofline': roofline, 'roofline_other_kernels': roofline_other, 'distortion': distortion, 'distortion_csr': dist_csr, 'single_point': single, 'metals': metals, 'monte_carlo_fits': mc_fits, 'single_lane': single_lane, 'exact_mu_loop': exact_mu, 'regions': regions, 'other_paths': other_paths, 'cpu_baseline': cpu,
+                'pk_stage': dict(zip(('k_live', 'k_node_max', 'mu_nodes', 'k_on_node_rule', 'table_level'), [float(v) for v in pk_state])),
+                'kernels': kernels, 'kernels_note': 'calibration pass before the timed region, event pairs around every kernel',
+            })
+        if args.dump_outputs:
+            dump = Path(args.dump_outputs)
+            dump.mkdir(parents=True, exist_ok=True)
+            np.save(dump / 'chi2.npy', np.asarray(last_chi2, dtype=np.float64))
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if use_dist:

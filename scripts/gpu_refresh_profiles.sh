@@ -1,7 +1,7 @@
 #!/bin/bash
 # Refresh of profiles/ (run through gpurun from the repo root; every pass appends to gpurun_out/refresh/log.txt; then
 # `python3 scripts/install_profiles.py rNN` copies the summaries into profiles/ under the round's names):
-#   rNN_bench_full.json                      plain `python3 bench.py --steps 20 --warmup 5` (what the driver runs)
+#   rNN_bench_full.json                      `python3 bench.py --full --steps 20 --warmup 5` (every section of the line)
 #   rNN_bench_core.json + _kernel_stats.csv  `bench.py --core-only --lanes 1` under rocprofv3 --kernel-trace --stats
 #   rNN_quad_pmc.json                        SQ counter passes of the same command (MFMA busy / MOPS, VALU, waits)
 #   rNN_bench_core_traffic.json              FETCH_SIZE / WRITE_SIZE passes of the same command
@@ -13,7 +13,7 @@ O=$R/gpurun_out/refresh
 rm -rf $O && mkdir -p $O
 log() { echo "[$(date +%T)] $*" | tee -a $O/log.txt; }
 log "full bench"
-python3 bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
 log "kernel stats (core, one lane)"
 cd /tmp && export TMPDIR=/tmp
 CORE="$R/bench.py --core-only --lanes 1 --steps 20 --warmup 5"

@@ -1,12 +1,11 @@
 """Every FITS file this package writes, checked by a validator written from the FITS standard (tests/fits_standard.py) and not
 from the package's own reader - 2880-byte blocks, 80-column cards, the mandatory keywords in their order and fixed format,
 TFORMn / TDIMn / NAXIS1 consistency, HIERARCH cards, big-endian payload, zero fill - and decoded independently: the columns the
-validator reads are the arrays that were written, and what `fitslite` reads.  The reverse too, in the build container: the
-package's reader on the files astropy wrote for the reference (tests/data, vega/models) against the validator's own decoding of
-them and against the committed .npz bundles.  Layouts being matched: reference vega/output.py:37-349, :442-520,
-vega/data.py:285-473."""
+validator reads are the arrays that were written, and what `fitslite` reads.  The reverse too: the package's reader on the files
+astropy wrote for the reference (its tests/data and vega/models, kept byte for byte under tests/golden/astropy_written) against
+the validator's own decoding of them and against the committed .npz bundles.  Layouts being matched: reference
+vega/output.py:37-349, :442-520, vega/data.py:285-473."""
 import gzip
-from pathlib import Path
 from types import SimpleNamespace
 
 import numpy as np
@@ -15,7 +14,8 @@ import pytest
 from conftest import GOLDEN, load_problem
 from fits_standard import FitsError, check_file
 
-REFERENCE = Path('/root/reference')
+# the reference's FITS files as astropy / picca wrote them, in the reference's layout (its tests/data, vega/models/<model>)
+ASTROPY_WRITTEN = GOLDEN / 'astropy_written'
 
 
 def _same(a, b):
@@ -187,12 +187,12 @@ def test_the_validator_rejects_what_the_standard_forbids(tmp_path):
     damaged(lambda b: b.__setitem__(slice(hier + 8, hier + 9), b'_'))                   # HIERARCH without its blank
 
 
-@pytest.mark.skipif(not (REFERENCE / 'tests' / 'data').is_dir(), reason='the reference tree exists in the build container only')
 def test_the_package_reader_on_files_astropy_wrote():
     """fitslite on the FITS files of the reference tree (written by astropy / picca) against the validator's independent decoding
     of the same bytes, and against the committed .npz bundles the tests run on."""
     from vega_amd.tables import read_tables
-    files = sorted(list((REFERENCE / 'tests' / 'data').glob('*.fits*')) + list((REFERENCE / 'vega' / 'models').glob('*/*.fits*')))
+    files = sorted(list((ASTROPY_WRITTEN / 'tests' / 'data').glob('*.fits*')) +
+                   list((ASTROPY_WRITTEN / 'vega' / 'models').glob('*/*.fits*')))
     assert len(files) >= 12
     for path in files:
         std = _against_fitslite(path)
@@ -204,7 +204,7 @@ def test_the_package_reader_on_files_astropy_wrote():
         bundle = GOLDEN / 'inputs' / f'{stem}.npz'
         if not bundle.is_file():
             continue
-        std = [h for h in check_file(REFERENCE / rel)[1:] if h['columns']]
+        std = [h for h in check_file(ASTROPY_WRITTEN / rel)[1:] if h['columns']]
         for table, h in zip(read_tables(bundle), std):
             for name in table.names:
                 assert _same(table.data[name], h['columns'][name]), (stem, name)
