@@ -152,7 +152,8 @@ typedef struct {
 
 const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
- * 7 vmx_fit_stats): lets a foreign binding verify its struct layout at load time. */
+ * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats): lets a foreign binding verify its
+ * struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -417,6 +418,48 @@ typedef struct {
 } vmx_fit_stats;
 int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, const double* theta0, const int32_t* mock_row,
                    const vmx_fit_options* opt, vmx_fit_result* results, vmx_fit_stats* stats);
+/* Posterior sampling where the walkers live: the affine-invariant ensemble sampler (Goodman & Weare 2010, emcee's stretch move
+ * with randomize_split = False), every decision pinned in vega_amd/csrc/vmx_ensemble.h.  The reference samples through
+ * PolyChord / pocoMC (bin/run_vega_mpi.py), which call log_lik one point at a time; here a half-step is one small kernel that
+ * decides the half just evaluated, records chain rows when due and proposes the next half, then the engine's chain over the W/2
+ * proposal rows in chunks of `chunk` (two lanes alternate when the quadratic form serves them).  The host enqueues the whole
+ * segment and synchronises once, at the end.
+ *   spec      n_params = the engine's; n sampled columns col[n] with their box [lo, hi] (finite, lo < hi); the stretch scale a > 1;
+ *             log_norm (lnL = log_norm - 0.5 chi2, chi2 with the Gaussian priors); seed / stream (the Philox key; stream 0 for
+ *             now, reserved for a rank); theta_fixed[n_params], the row that supplies the columns not sampled
+ *   W         walkers, even and >= 2 n
+ *   x, lnL, accepted   [W][n], [W], [W] host: the walkers' state, read at entry and written back at exit
+ *   step0     global index of the first step (the random stream and the chain's thinning count from the start of the run: a run
+ *             cut into calls gives the same chain)
+ *   thin      a chain row after every step s with (s + 1) % thin == 0: chain [rows][W][n], chain_lnL [rows][W] (host, NULL: not
+ *             kept), rows = (step0 + n_steps) / thin - step0 / thin
+ *   opt       const_hint (-1: derived - a column varies when it is sampled), chunk (rows per engine call, 0: max_batch), lanes
+ *             (0: 2); NULL: -1, 0, 0
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): W odd or < 2 n, a column out of range or repeated, a
+ * non-finite limit or lo >= hi, a <= 1, thin < 1, a start walker outside the box or with a non-finite lnL.  A HIP failure later
+ * returns -2 and leaves the engine usable. */
+#define VMX_ENS_MAXN 64
+typedef struct {
+    int32_t n_params, n;
+    const int32_t* col; const double* lo; const double* hi;
+    double a, log_norm;
+    uint64_t seed, stream;
+    const double* theta_fixed;
+} vmx_ensemble_spec;
+typedef struct { int32_t const_hint, chunk, lanes, reserved; } vmx_ensemble_options;
+typedef struct {
+    int64_t steps, proposals, accepted, rejected_outside_box, rejected_failed_model, engine_calls;
+    double seconds, seconds_enqueuing;
+    int64_t host_synchronisations;
+    int32_t const_hint, lanes;          /* what the call ran with */
+} vmx_ensemble_stats;
+int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
+                     int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
+                     const vmx_ensemble_options* opt, vmx_ensemble_stats* stats);
+/* The table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns varies[n_params] != 0 allow - what
+ * vmx_fit_migrad and vmx_ensemble_run derive when they are given const_hint = -1; a caller that evaluates such batches itself
+ * sets it with vmx_set_constant_nl_hint. */
+int vmx_derived_const_hint(vmx_engine* e, const int32_t* varies);
 /* direct_pk (vega_interface.py:208-248 -> model.py:188-207): while set, every item's model is its smooth pipeline
  * (no peak component, no metals with the default no-metal-decomp; additive broadband terms enter once) evaluated with
  * the linear spectrum pk[b][nk] of walker b (host pointer, e.g. the output of a Boltzmann code per parameter point)

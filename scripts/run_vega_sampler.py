@@ -1,0 +1,31 @@
+#!/usr/bin/env python
+"""Sample the posterior of a main config on one GPU: the reference's ``bin/run_vega_mpi.py`` for one process with
+``[control] run_sampler = True`` and ``sampler = Ensemble`` (settings in ``[Ensemble]``: path, name, walkers, steps, seed, a,
+thin, init, init_scale, driver).  Writes ``<path>/<name>.txt`` and ``<path>/<name>.paramnames`` (getdist's plain-text chain).
+
+    python scripts/run_vega_sampler.py main.ini
+"""
+import argparse
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+if str(REPO) not in sys.path:
+    sys.path.insert(0, str(REPO))
+
+
+def main():
+    pars = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                                   description='Run the ensemble sampler of vega_amd on one GPU.')
+    pars.add_argument('config', type=str, help='Main config file')
+    pars.add_argument('--search-dir', action='append', default=[], help='extra directories to look for input files in')
+    pars.add_argument('--max-batch', type=int, default=256, help="the engine's batch size (walkers per chain launch)")
+    args = pars.parse_args()
+    from vega_amd import run_vega_sampler
+    sampler = run_vega_sampler(args.config, search_dirs=args.search_dir, max_batch=args.max_batch)
+    print(f'acceptance fraction {sampler.acceptance_fraction.mean():.3f}, {sampler.stats["proposals"]} proposals in '
+          f'{sampler.stats["seconds"]:.2f} s ({sampler.driver} driver)')
+
+
+if __name__ == '__main__':
+    main()

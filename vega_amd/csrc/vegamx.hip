@@ -6,6 +6,7 @@
 // vmx_device.h on the engine stream.
 #include "vmx_device.h"
 #include "vmx_fit.h"
+#include "vmx_ensemble.h"
 
 #include <atomic>
 #include <cmath>
@@ -166,6 +167,85 @@ struct FitWorkspace {
 template <typename T>
 static int ensure(DevBuf<T>& b, size_t count) { return b.n >= count && b.p ? 0 : b.alloc(count, false); }
 
+// Ensemble sampling (vmx_ensemble_run): the walkers' state, the proposals of a half and the chain record, grown on demand
+struct EnsWorkspace {
+    DevBuf<double> x, lnl, prop, factor, theta, chi2, fixed, lo, hi, chain, chain_lnl;
+    DevBuf<int64_t> acc, n_box, n_fail;
+    DevBuf<int32_t> inside, status, col;
+    hipEvent_t ev_prop = nullptr, ev_lane = nullptr;
+    ~EnsWorkspace() {
+        if (ev_prop) (void)hipEventDestroy(ev_prop);
+        if (ev_lane) (void)hipEventDestroy(ev_lane);
+    }
+};
+
+struct EnsDev {
+    double* x; double* lnl; int64_t* acc; int64_t* n_box; int64_t* n_fail;      // [W][n], [W], [W] x 3
+    double* prop; double* factor; int32_t* inside;                              // the active half's proposals [H][n], [H], [H]
+    double* theta; const double* chi2; const int32_t* status;                   // the engine's rows [H][P] and its answers [H]
+    const double* fixed; const int32_t* col; const double* lo; const double* hi;
+    double* chain; double* chain_lnl;                                           // [rows][W][n], [rows][W] (nullptr: not kept)
+    int32_t W, n, P, thin;
+    double a, log_norm;
+    uint64_t seed, stream;
+    int64_t step0;
+};
+
+// One half-step of the sampler in one work-group (partners read the half decided just before, a grid-wide dependency):
+// decide the proposals of half h_dec at step s_dec (s_dec < 0: none), record the chain row when step s_dec is complete and due,
+// then propose half h_prop at step s_prop (s_prop < 0: none) and write the engine's rows.  Every expression: vmx_ensemble.h.
+constexpr int ENS_THREADS = 1024;
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
+{
+    const int H = D.W / 2, n = D.n;
+    if (s_dec >= 0) {
+        for (int k = threadIdx.x; k < H; k += blockDim.x) {
+            const int w = h_dec * H + k;
+            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, D.stream);
+            const double c2 = D.chi2[k];
+            const bool inside = D.inside[k] != 0, ok = vmx_ens::model_ok(D.status[k], c2);
+            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
+            if (vmx_ens::accept(inside, ok, D.factor[k], lnl_new, D.lnl[w], b.w[2])) {
+                for (int d = 0; d < n; ++d) D.x[(size_t)w * n + d] = D.prop[(size_t)k * n + d];
+                D.lnl[w] = lnl_new;
+                D.acc[w] += 1;
+            } else if (!inside) D.n_box[w] += 1;
+            else if (!ok) D.n_fail[w] += 1;
+        }
+        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
+            __syncthreads();
+            const int64_t r = (s_dec + 1) / D.thin - D.step0 / D.thin - 1;
+            if (D.chain)
+                for (int q = threadIdx.x; q < D.W * n; q += blockDim.x) D.chain[(size_t)r * D.W * n + q] = D.x[q];
+            if (D.chain_lnl)
+                for (int q = threadIdx.x; q < D.W; q += blockDim.x) D.chain_lnl[(size_t)r * D.W + q] = D.lnl[q];
+        }
+    }
+    if (s_prop < 0) return;
+    __syncthreads();            // (the partners of the next half are the walkers just decided)
+    for (int k = threadIdx.x; k < H; k += blockDim.x) {
+        const int w = h_prop * H + k;
+        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, D.stream);
+        const int64_t j = vmx_ens::partner(b.w[0], H);
+        const double* c = D.x + (size_t)((1 - h_prop) * H + j) * n;
+        const double* s = D.x + (size_t)w * n;
+        const double z = vmx_ens::stretch_z(D.a, b.w[1]);
+        double* y = D.prop + (size_t)k * n;
+        bool in = true;
+        for (int d = 0; d < n; ++d) {
+            const double v = vmx_ens::propose(c[d], s[d], z);
+            y[d] = v;
+            in = in && v >= D.lo[d] && v <= D.hi[d];
+        }
+        D.factor[k] = vmx_ens::log_factor(n, z);
+        D.inside[k] = in ? 1 : 0;
+        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
+        double* row = D.theta + (size_t)k * D.P;
+        for (int p = 0; p < D.P; ++p) row[p] = D.fixed[p];
+        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
+    }
+}
+
 }  // namespace
 
 struct vmx_engine {
@@ -185,6 +265,8 @@ struct vmx_engine {
     hipStream_t last_stream = nullptr;      // the stream the last vmx_eval_device ran on
     const int32_t* call_mock = nullptr;     // per-call mock rows of the walkers (device pointer; vmx_eval_device_mocks, vmx_fit_migrad)
     FitWorkspace* fitws = nullptr;
+    EnsWorkspace* ensws = nullptr;
+    hipEvent_t lane_wait = nullptr;         // vmx_ensemble_run: the rows of the second lane's calls are complete at this event
 
     int nk = 0, nkp = 0, n_mu = 0;
     int n_rows = 0, n_extra = 0, mu_lo = 0, mu_hi = 0;     // node rule of the mu sums (vmx_set_mu_quadrature)
@@ -339,6 +421,7 @@ struct vmx_engine {
         for (auto& q : cinv_lists) delete q.second;
         for (void* p : host_allocs) (void)hipHostFree(p);
         delete fitws;
+        delete ensws;
         if (pin_theta) (void)hipHostFree(pin_theta);
         if (pin_chi2) (void)hipHostFree(pin_chi2);
         if (pin_status) (void)hipHostFree(pin_status);
@@ -689,6 +772,9 @@ int vmx_struct_size(int32_t which)
         case 5: return (int)sizeof(vmx_fit_options);
         case 6: return (int)sizeof(vmx_fit_result);
         case 7: return (int)sizeof(vmx_fit_stats);
+        case 8: return (int)sizeof(vmx_ensemble_spec);
+        case 9: return (int)sizeof(vmx_ensemble_options);
+        case 10: return (int)sizeof(vmx_ensemble_stats);
         default: return -1;
     }
 }
@@ -3034,7 +3120,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
-    L->fitws = nullptr; L->call_mock = nullptr;
+    L->fitws = nullptr; L->ensws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
     L->graphs.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
     L->pin_theta = nullptr; L->pin_chi2 = nullptr; L->pin_status = nullptr; L->pin_done = nullptr; L->pin_part = nullptr;
@@ -3134,6 +3220,7 @@ static int eval_device_impl(vmx_engine* e, const double* d_theta, int32_t B, dou
         if (quad_ready(L, &lq, B)) return -2;       // (its work lists: the tensors are the borrowed ones)
         if (!lq) return fail(-2, "the second lane cannot take the quadratic form");
         const int tab = (B >= 16 && L->n_xtab > 0) ? L->const_hint : 0;
+        if (e->lane_wait) HIP_OK(hipStreamWaitEvent(L->stream, e->lane_wait, 0));
         MockScope scope(L, d_mock);
         if (run_chain(L, B, tab, false, d_theta, d_chi2, d_status, true)) return -2;
         e->last_stream = L->stream;
@@ -3187,6 +3274,24 @@ static_assert(sizeof(vmx_fit_stage) == sizeof(vmx_migrad::StageSpec) && sizeof(v
               "include/vegamx.h and vmx_migrad.h describe the same fit");
 static_assert(VMX_FIT_MAXN == vmx_migrad::MAXN && VMX_FIT_MAX_STAGES == vmx_migrad::MAX_STAGES, "fit limits");
 
+// the table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns `varies` allow, as vmx_eval derives
+// it from host walkers
+static int derived_const_hint(const vmx_engine* e, const std::vector<char>& varies)
+{
+    int hint = e->n_xtab > 0 ? (e->no_tab2 ? 1 : 2) : 0;
+    for (int slot : e->const_slots) if (varies[slot]) hint = 0;
+    for (int slot : e->const_slots2) if (hint == 2 && varies[slot]) hint = 1;
+    return hint;
+}
+
+int vmx_derived_const_hint(vmx_engine* e, const int32_t* varies)
+{
+    REQUIRE(e && e->finalized && varies, "vmx_derived_const_hint");
+    std::vector<char> v(e->n_params, 0);
+    for (int c = 0; c < e->n_params; ++c) v[c] = varies[c] != 0;
+    return derived_const_hint(e, v);
+}
+
 int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, const double* theta0, const int32_t* mock_row,
                    const vmx_fit_options* opt, vmx_fit_result* results, vmx_fit_stats* stats)
 {
@@ -3233,17 +3338,14 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     int hint = opt ? opt->const_hint : -1;
     REQUIRE(hint >= -1 && hint <= 2, "vmx_fit_migrad: const_hint -1 (derive it), 0, 1 or 2");
     if (hint < 0) {
-        // the table level the rows of a round allow (vmx_set_constant_nl_hint), as vmx_eval derives it from host walkers: a column
-        // varies when a stage frees it or the fits' rows differ in it
+        // a column varies when a stage frees it or the fits' rows differ in it
         std::vector<char> varies(e->n_params, 0);
         for (int s = 0; s < spec->n_stages; ++s)
             for (int i = 0; i < spec->stage[s].n; ++i) varies[spec->stage[s].col[i]] = 1;
         for (int f = 1; f < n_fits; ++f)
             for (int c = 0; c < e->n_params; ++c)
                 if (theta0[(size_t)f * e->n_params + c] != theta0[c]) varies[c] = 1;
-        hint = e->n_xtab > 0 ? (e->no_tab2 ? 1 : 2) : 0;
-        for (int slot : e->const_slots) if (varies[slot]) hint = 0;
-        for (int slot : e->const_slots2) if (hint == 2 && varies[slot]) hint = 1;
+        hint = derived_const_hint(e, varies);
     }
     HIP_OK(hipSetDevice(e->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -3450,6 +3552,142 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     S.seconds_host_waiting = wait_s;
     S.gpu_idle_seconds_between_rounds = idle_ms * 1e-3;
     if (stats) *stats = S;
+    return 0;
+}
+
+// ---- posterior sampling where the walkers live (vmx_ensemble.h)
+int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
+                     int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
+                     const vmx_ensemble_options* opt, vmx_ensemble_stats* stats)
+{
+    REQUIRE(e && e->finalized && spec && x && lnL && accepted, "vmx_ensemble_run");
+    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
+            "vmx_ensemble_run: parameter columns, limits and the fixed row");
+    const int n = spec->n, P = e->n_params;
+    REQUIRE(n >= 1 && n <= VMX_ENS_MAXN, "vmx_ensemble_run: 1 .. 64 sampled columns");
+    REQUIRE(W >= 2 * n && W % 2 == 0, "vmx_ensemble_run: an even number of walkers, at least twice the sampled columns");
+    std::vector<char> varies(P, 0);
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_ensemble_run: parameter column");
+        REQUIRE(!varies[spec->col[i]], "vmx_ensemble_run: a column is listed twice");
+        varies[spec->col[i]] = 1;
+        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_ensemble_run: limits");
+    }
+    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), "vmx_ensemble_run: the stretch scale a must exceed 1");
+    REQUIRE(std::isfinite(spec->log_norm), "vmx_ensemble_run: log_norm");
+    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, "vmx_ensemble_run: thin >= 1, n_steps >= 0, step0 >= 0");
+    for (int w = 0; w < W; ++w) {
+        REQUIRE(std::isfinite(lnL[w]), "vmx_ensemble_run: a start walker has a non-finite lnL");
+        for (int i = 0; i < n; ++i) {
+            const double v = x[(size_t)w * n + i];
+            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], "vmx_ensemble_run: a start walker lies outside the box");
+        }
+    }
+    int hint = opt ? opt->const_hint : -1;
+    REQUIRE(hint >= -1 && hint <= 2, "vmx_ensemble_run: const_hint -1 (derive it), 0, 1 or 2");
+    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_ensemble_run: chunk, lanes");
+    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
+    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
+    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    const int H = W / 2;
+    const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->ensws) e->ensws = new EnsWorkspace();
+    EnsWorkspace& S = *e->ensws;
+    if (ensure(S.x, (size_t)W * n) || ensure(S.lnl, W) || ensure(S.acc, W) || ensure(S.n_box, W) || ensure(S.n_fail, W) ||
+        ensure(S.prop, (size_t)H * n) || ensure(S.factor, H) || ensure(S.inside, H) || ensure(S.theta, (size_t)H * P) ||
+        ensure(S.chi2, H) || ensure(S.status, H) || ensure(S.fixed, P) || ensure(S.col, n) || ensure(S.lo, n) || ensure(S.hi, n))
+        return -2;
+    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * W * n)) return -2;
+    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * W)) return -2;
+    if (!S.ev_prop) {
+        HIP_OK(hipEventCreateWithFlags(&S.ev_prop, hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
+    }
+    hipStream_t st = e->stream;
+    HIP_OK(hipMemcpyAsync(S.x.p, x, (size_t)W * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.acc.p, accepted, (size_t)W * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(S.n_box.p, 0, (size_t)W * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.n_fail.p, 0, (size_t)W * sizeof(int64_t), st));
+    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.col.p, spec->col, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+
+    EnsDev D{};
+    D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p; D.n_box = S.n_box.p; D.n_fail = S.n_fail.p;
+    D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
+    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
+    D.fixed = S.fixed.p; D.col = S.col.p; D.lo = S.lo.p; D.hi = S.hi.p;
+    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
+    D.seed = spec->seed; D.stream = spec->stream; D.step0 = step0;
+
+    // the engine as the sampler's likelihood: chi2-only device evaluations of the half's rows, eager launches, two lanes when the
+    // quadratic form serves them; the table level the sampled columns allow.  The second lane's stream waits for the rows at
+    // lane_wait, the next decision waits for the lane.
+    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
+    const bool saved_ring = e->ring_allowed;
+    e->const_hint = hint;
+    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
+    e->lane_calls = 0;
+    struct Restore {
+        vmx_engine* e; int hint, lanes; bool ring;
+        ~Restore() { wait_lane(e); e->lane_wait = nullptr; e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
+    } restore{e, saved_hint, saved_lanes, saved_ring};
+
+    vmx_ensemble_stats R{};
+    R.const_hint = hint;
+    R.lanes = e->n_lanes;
+    const auto t_loop = std::chrono::steady_clock::now();
+    const int64_t halves = 2 * (int64_t)n_steps;
+    if (halves > 0) hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, (int64_t)-1, 0, step0, 0);
+    HIP_OK(hipGetLastError());
+    for (int64_t q = 0; q < halves; ++q) {
+        const int64_t s = step0 + q / 2;
+        const int h = (int)(q % 2);
+        HIP_OK(hipEventRecord(S.ev_prop, st));
+        e->lane_wait = S.ev_prop;
+        hipStream_t lane_stream = nullptr;
+        for (int off = 0; off < H; off += chunk) {
+            const int B = std::min(chunk, H - off);
+            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
+            if (e->last_stream != st) lane_stream = e->last_stream;
+            R.engine_calls += 1;
+        }
+        if (lane_stream) {      // (the decision reads every chunk's chi2)
+            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
+            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
+        }
+        const int64_t nq = q + 1;
+        hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, s, h,
+                           nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
+        HIP_OK(hipGetLastError());
+    }
+    e->lane_wait = nullptr;
+    std::vector<int64_t> acc0(accepted, accepted + W), box(W), failed(W);
+    HIP_OK(hipMemcpyAsync(x, S.x.p, (size_t)W * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(accepted, S.acc.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(box.data(), S.n_box.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(failed.data(), S.n_fail.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * W * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * W * sizeof(double), hipMemcpyDeviceToHost, st));
+    R.seconds_enqueuing = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
+    HIP_OK(hipStreamSynchronize(st));       // (the call's only wait: the segment is enqueued as a whole)
+    R.host_synchronisations = 1;
+    R.steps = n_steps;
+    R.proposals = (int64_t)n_steps * W;
+    for (int w = 0; w < W; ++w) {
+        R.accepted += accepted[w] - acc0[w];
+        R.rejected_outside_box += box[w];
+        R.rejected_failed_model += failed[w];
+    }
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
     return 0;
 }
 

@@ -115,6 +115,26 @@ class FitStats(C.Structure):
                 ('seconds_enqueuing_rounds', C.c_double), ('seconds_enqueuing_calls', C.c_double)]
 
 
+VMX_ENS_MAXN = 64
+
+
+class EnsembleSpec(C.Structure):
+    _fields_ = [('n_params', C.c_int32), ('n', C.c_int32), ('col', C.POINTER(C.c_int32)), ('lo', C.POINTER(C.c_double)),
+                ('hi', C.POINTER(C.c_double)), ('a', C.c_double), ('log_norm', C.c_double), ('seed', C.c_uint64),
+                ('stream', C.c_uint64), ('theta_fixed', C.POINTER(C.c_double))]
+
+
+class EnsembleOptions(C.Structure):
+    _fields_ = [('const_hint', C.c_int32), ('chunk', C.c_int32), ('lanes', C.c_int32), ('reserved', C.c_int32)]
+
+
+class EnsembleStats(C.Structure):
+    _fields_ = [('steps', C.c_int64), ('proposals', C.c_int64), ('accepted', C.c_int64), ('rejected_outside_box', C.c_int64),
+                ('rejected_failed_model', C.c_int64), ('engine_calls', C.c_int64), ('seconds', C.c_double),
+                ('seconds_enqueuing', C.c_double), ('host_synchronisations', C.c_int64), ('const_hint', C.c_int32),
+                ('lanes', C.c_int32)]
+
+
 FIT_BATCH_BINS = ('1', '2..4', '5..16', '17..64', '65..256', '257..1024', '1025..4096', '4097..')
 
 
@@ -185,6 +205,9 @@ def load_library():
     lib.vmx_eval_device_mocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.vmx_fit_migrad.argtypes = [C.c_void_p, C.POINTER(FitSpec), C.c_int32, dptr, iptr, C.POINTER(FitOptions),
                                    C.POINTER(FitResultArrays), C.POINTER(FitStats)]
+    lib.vmx_ensemble_run.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, dptr, dptr, C.POINTER(C.c_int64), C.c_int64,
+                                     C.c_int32, C.c_int32, dptr, dptr, C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats)]
+    lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
     lib.vmx_set_constant_nl_hint.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_direct_pk.argtypes = [C.c_void_p, dptr, C.c_int32, C.c_int32]
     lib.vmx_set_linear_spectra.argtypes = [C.c_void_p, dptr, dptr, dptr, C.c_int32]
@@ -216,7 +239,8 @@ def load_library():
     lib.vmx_set_profiling_mask.argtypes = [C.c_void_p, C.c_uint32]
     lib.vmx_get_timings.argtypes = [C.c_void_p, dptr, C.POINTER(C.c_int64), C.c_int32]
     lib.vmx_struct_size.argtypes = [C.c_int32]
-    for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats)):
+    for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
+                                    EnsembleSpec, EnsembleOptions, EnsembleStats)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -229,7 +253,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -505,6 +529,7 @@ class Engine:
         self.max_batch = int(max_batch)
         self._small_io = None
         self.lanes = 1
+        self.nl_hint = 0                # (the level of set_constant_nl_hint, 0 until it is called)
         self._h = C.c_void_p()
         self._gk = {}
         self.device = int(device)
@@ -952,11 +977,47 @@ class Engine:
         info['evaluations_by_batch'] = dict(zip(FIT_BATCH_BINS, list(stats.evaluations_by_batch)))
         return outs, info
 
+    def ensemble_run(self, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin=1, a=2.0, log_norm=0.0, seed=0,
+                     stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
+        """``n_steps`` steps of the ensemble sampler on the device (include/vegamx.h: vmx_ensemble_run): ``cols`` the sampled
+        parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``x`` [W, n] / ``lnl`` [W] / ``accepted``
+        int64 [W] the walkers' state (updated in place), ``step0`` the global index of the first step.  Returns (chain [rows, W, n],
+        chain_lnl [rows, W], statistics), rows = (step0 + n_steps) // thin - step0 // thin."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
+        for arr, dtype in ((x, np.float64), (lnl, np.float64), (accepted, np.int64)):
+            if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous):
+                raise ValueError('x, lnl, accepted: C-contiguous float64 / float64 / int64 arrays (updated in place)')
+        W = x.shape[0]
+        if x.shape != (W, cols.size) or lnl.shape != (W,) or accepted.shape != (W,) or theta_fixed.shape != (self.n_params,):
+            raise ValueError('x [W, n], lnl [W], accepted [W], theta_fixed [n_params]')
+        step0, n_steps, thin = int(step0), int(n_steps), int(thin)
+        rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
+        chain = np.empty((rows, W, cols.size)) if keep_chain else None
+        chain_lnl = np.empty((rows, W)) if keep_chain else None
+        spec = EnsembleSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), float(a), float(log_norm), int(seed), int(stream),
+                            _dp(theta_fixed))
+        opt = EnsembleOptions(int(const_hint), int(chunk), int(lanes), 0)
+        stats = EnsembleStats()
+        self._check(self.lib.vmx_ensemble_run(self._h, C.byref(spec), W, _dp(x), _dp(lnl),
+                                              accepted.ctypes.data_as(C.POINTER(C.c_int64)), step0, n_steps, thin,
+                                              _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None,
+                                              C.byref(opt), C.byref(stats)))
+        return chain, chain_lnl, {name: getattr(stats, name) for name, _ in EnsembleStats._fields_}
+
+    def derived_const_hint(self, cols):
+        """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:
+        vmx_derived_const_hint): 0, 1 (Arinyo parameters shared) or 2 (and the Gaussian-factor parameters)."""
+        varies = np.zeros(self.n_params, dtype=np.int32)
+        varies[np.asarray(cols, dtype=int)] = 1
+        return self._check(self.lib.vmx_derived_const_hint(self._h, _ip(varies)))
+
     def set_constant_nl_hint(self, on=True, gaussian=False):
         """For ``eval_device``: the caller asserts that the Arinyo parameters - with ``gaussian`` also the smoothing,
         peak-broadening and Gaussian velocity-dispersion parameters - are identical for all walkers of a batch
         (violations are flagged per walker, never silently wrong)."""
         self._check(self.lib.vmx_set_constant_nl_hint(self._h, 0 if not on else 2 if gaussian else 1))
+        self.nl_hint = 0 if not on else 2 if gaussian else 1
 
     def stream_handle(self):
         """hipStream_t of the engine as an integer (for ``torch.cuda.ExternalStream``)."""

@@ -1,0 +1,490 @@
+"""Posterior sampling: the affine-invariant ensemble sampler (Goodman & Weare 2010, emcee's stretch move with
+randomize_split=False), run where the walkers are.
+
+The reference samples through PolyChord / pocoMC (bin/run_vega_mpi.py: ``[control] run_sampler = True``), which call
+``log_lik`` one point at a time.  Here W walkers advance half an ensemble at a time: the ``device`` driver runs the whole walker
+loop on the GPU (include/vegamx.h: vmx_ensemble_run - one small kernel per half-step, the engine's chain over the half's rows,
+one host synchronisation per call); the ``python`` driver is the readable restatement of the same algorithm in NumPy over
+``VegaInterface.chi2_batch_device``.  Both follow vega_amd/csrc/vmx_ensemble.h decision for decision, so that they produce the
+same chain bit for bit.  The random stream is NumPy's Philox4x64-10 (one block per walker-in-half, step and half).
+"""
+import configparser
+import math
+import os
+from pathlib import Path
+
+import numpy as np
+
+# ------------------------------------------------------------------ the algorithm (vmx_ensemble.h) in NumPy
+_PHILOX_M = (np.uint64(0xD2E7470EE14C6C93), np.uint64(0xCA5A826395121157))
+_PHILOX_W = (np.uint64(0x9E3779B97F4A7C15), np.uint64(0xBB67AE8584CAA73B))
+_M32 = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+def _mulhilo(a, b):
+    """(high, low) 64-bit words of the 128-bit products a * b (uint64 arrays)."""
+    a_lo, a_hi, b_lo, b_hi = a & _M32, a >> _S32, b & _M32, b >> _S32
+    ll, lh, hl, hh = a_lo * b_lo, a_lo * b_hi, a_hi * b_lo, a_hi * b_hi
+    mid = (ll >> _S32) + (lh & _M32) + (hl & _M32)
+    return hh + (lh >> _S32) + (hl >> _S32) + (mid >> _S32), a * b
+
+
+def philox4x64_10(counter, key):
+    """Random123 Philox4x64-10 of counters [..., 4] (word 0 least significant) under the key (k0, k1): blocks [..., 4] uint64.
+    Equal to ``np.random.Philox(key=[k0, k1], counter=(c - 1) mod 2**256).random_raw(4)`` for the counter c."""
+    c = np.array(counter, dtype=np.uint64)
+    c0, c1, c2, c3 = (c[..., i].copy() for i in range(4))
+    shape = c0.shape
+    k0 = np.full(shape, key[0], dtype=np.uint64)
+    k1 = np.full(shape, key[1], dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        for r in range(10):
+            if r > 0:
+                k0 += _PHILOX_W[0]
+                k1 += _PHILOX_W[1]
+            hi0, lo0 = _mulhilo(np.full(shape, _PHILOX_M[0]), c0)
+            hi1, lo1 = _mulhilo(np.full(shape, _PHILOX_M[1]), c2)
+            c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+    return np.stack([c0, c1, c2, c3], axis=-1)
+
+
+def step_blocks(half, step, h, seed, stream=0):
+    """The blocks of walkers-in-half 0 .. half-1 at global step ``step``, half ``h``: [half, 4] uint64."""
+    ctr = np.zeros((half, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(half, dtype=np.uint64)
+    ctr[:, 1] = np.uint64(step)
+    ctr[:, 2] = np.uint64(h)
+    return philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def u01(x):
+    return (np.asarray(x, dtype=np.uint64) >> np.uint64(11)).astype(np.float64) * 2.0**-53
+
+
+def partner(x0, half):
+    return ((np.asarray(x0, dtype=np.uint64) >> _S32) * np.uint64(half)) >> _S32
+
+
+def stretch_z(a, x1):
+    t = (a - 1.0) * u01(x1)
+    t = t + 1.0
+    z = t * t
+    return z / a
+
+
+def propose(c, s, z):
+    """Rows of the proposal: c the partners' positions [k, n], s the walkers' own [k, n], z [k]."""
+    d = (c - s) * z[:, None]
+    return c - d
+
+
+def _log(v):
+    # the C library's log, as the header compiled for the host calls it (np.log may take another implementation)
+    return np.array([math.log(float(t)) if t > 0 else -math.inf for t in np.atleast_1d(v)])
+
+
+def log_factor(n, z):
+    return float(n - 1) * _log(z)
+
+
+def log_lik(log_norm, chi2):
+    return log_norm - 0.5 * np.asarray(chi2, dtype=np.float64)
+
+
+def model_ok(status, chi2):
+    return (np.asarray(status) == 0) & (np.asarray(chi2) < 1e99)
+
+
+def accept(inside, ok, factor, lnl_new, lnl_old, x2):
+    lhs = (factor + lnl_new) - lnl_old
+    with np.errstate(invalid='ignore'):
+        return np.asarray(inside, dtype=bool) & np.asarray(ok, dtype=bool) & (lhs > _log(u01(x2)))
+
+
+def half_step_proposals(x, h, step, a, seed, stream, lo, hi):
+    """Proposals of half ``h`` at ``step`` for the walkers ``x`` [W, n]: (y [W/2, n], inside [W/2], factor [W/2], blocks)."""
+    W, n = x.shape
+    H = W // 2
+    b = step_blocks(H, step, h, seed, stream)
+    j = partner(b[:, 0], H).astype(np.int64)
+    c = x[(1 - h) * H + j]
+    s = x[h * H:(h + 1) * H]
+    z = stretch_z(a, b[:, 1])
+    y = propose(c, s, z)
+    with np.errstate(invalid='ignore'):
+        inside = np.all((y >= lo) & (y <= hi), axis=1)
+    return y, inside, log_factor(n, z), b
+
+
+def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate):
+    """``n_steps`` steps of the sampler in NumPy from the state ``x`` [W, n], ``lnl`` [W], ``accepted`` [W] (updated in place).
+    ``evaluate(rows, h)`` -> (chi2 [W/2], status [W/2]) for the half's rows [W/2, n] (a proposal outside the box is replaced
+    by the walker's own position, as the device driver hands it to the engine).  Returns (chain [rows, W, n], chain_lnl, stats)."""
+    W, n = x.shape
+    H = W // 2
+    rows = (step0 + n_steps) // thin - step0 // thin
+    chain, chain_lnl = np.empty((rows, W, n)), np.empty((rows, W))
+    st = dict(steps=n_steps, proposals=n_steps * W, accepted=0, rejected_outside_box=0, rejected_failed_model=0)
+    for s in range(step0, step0 + n_steps):
+        for h in (0, 1):
+            y, inside, factor, b = half_step_proposals(x, h, s, a, seed, stream, lo, hi)
+            mine = slice(h * H, (h + 1) * H)
+            chi2, status = evaluate(np.where(inside[:, None], y, x[mine]), h)
+            ok = model_ok(status, chi2)
+            lnl_new = log_lik(log_norm, chi2)
+            acc = accept(inside, ok, factor, lnl_new, lnl[mine], b[:, 2])
+            x[mine][acc] = y[acc]
+            lnl[mine][acc] = lnl_new[acc]
+            accepted[mine] += acc
+            st['accepted'] += int(acc.sum())
+            st['rejected_outside_box'] += int((~inside).sum())
+            st['rejected_failed_model'] += int((inside & ~ok).sum())
+        if (s + 1) % thin == 0:
+            r = (s + 1) // thin - step0 // thin - 1
+            chain[r], chain_lnl[r] = x, lnl
+    return chain, chain_lnl, st
+
+
+def write_getdist(path, name, names, chain, chain_lnl):
+    """getdist's plain-text chain: ``name.txt`` (one row per sample: weight 1, -lnL, the parameters) and ``name.paramnames``
+    (one ``name label`` line per parameter, label = name).  ``chain`` [..., n], ``chain_lnl`` [...]."""
+    path = Path(path)
+    chain = np.asarray(chain, dtype=np.float64).reshape(-1, len(names))
+    lnl = np.asarray(chain_lnl, dtype=np.float64).reshape(-1)
+    np.savetxt(path / f'{name}.txt', np.column_stack([np.ones(lnl.size), -lnl, chain]), fmt='%.17g')
+    with open(path / f'{name}.paramnames', 'w') as f:
+        for nm in names:
+            f.write(f'{nm} {nm}\n')
+    return path / f'{name}.txt', path / f'{name}.paramnames'
+
+
+def autocorr_func_1d(x):
+    """Normalised autocorrelation function of a series by FFT (emcee.autocorr.function_1d)."""
+    x = np.asarray(x, dtype=np.float64)
+    n = 1
+    while n < len(x):
+        n <<= 1
+    f = np.fft.fft(x - np.mean(x), n=2 * n)
+    acf = np.fft.ifft(f * np.conjugate(f))[:len(x)].real
+    return acf / acf[0] if acf[0] != 0 else acf
+
+
+def integrated_time(chain, c=5):
+    """Integrated autocorrelation time per parameter of ``chain`` [steps, walkers, n] (or [steps] / [steps, walkers]): the
+    walker-averaged autocorrelation function, summed up to Sokal's automatic window M >= c tau (emcee.autocorr.integrated_time)."""
+    x = np.asarray(chain, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None, None]
+    elif x.ndim == 2:
+        x = x[:, :, None]
+    tau = np.empty(x.shape[2])
+    for d in range(x.shape[2]):
+        f = np.mean([autocorr_func_1d(x[:, k, d]) for k in range(x.shape[1])], axis=0)
+        taus = 2.0 * np.cumsum(f) - 1.0
+        m = np.arange(len(taus)) < c * taus
+        window = int(np.argmin(m)) if np.any(m) else len(taus) - 1
+        tau[d] = taus[window]
+    return tau
+
+
+# ------------------------------------------------------------------ the sampler
+class EnsembleSampler:
+    """W walkers over the sampled parameters of ``vega`` (``sample_params['limits']``: the ``[sample]`` section, or the
+    ``[monte carlo]`` one after ``initialize_monte_carlo``, as bin/run_vega_mpi.py picks them; ``sample_params`` overrides).
+
+    ``driver``: ``'device'`` (vmx_ensemble_run) or ``'python'`` (the NumPy restatement over ``chi2_batch_device``); an engine
+    group (one engine per transform setting, no single C handle) takes ``'python'``.  The choice is made when ``run`` knows the
+    engine - ``freeze_metals`` may replace it.  ``segment``: steps per call of the driver (the chain does not depend on it)."""
+
+    def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
+                 chunk=0, lanes=0, const_hint=-1):
+        if driver not in ('device', 'python'):
+            raise ValueError("driver: 'device' or 'python'")
+        self.vega = vega
+        sp = vega.sample_params if sample_params is None else sample_params
+        limits = dict(sp['limits'])
+        for lims in limits.values():
+            if lims is None or None in tuple(lims):
+                raise ValueError('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
+                                 ' just say par_name = True to use defaults.')
+        self.names = list(limits)
+        if not self.names:
+            raise ValueError('no sampled parameters')
+        unknown = [nm for nm in self.names if nm not in vega.param_names]
+        if unknown:
+            raise KeyError(f'unknown parameters {unknown}')
+        self.lo = np.array([float(limits[nm][0]) for nm in self.names])
+        self.hi = np.array([float(limits[nm][1]) for nm in self.names])
+        if not (np.all(np.isfinite(self.lo)) and np.all(np.isfinite(self.hi)) and np.all(self.lo < self.hi)):
+            raise ValueError('Sampler needs well defined prior limits: finite, lower < upper')
+        self.values = {nm: sp.get('values', {}).get(nm, vega.params.get(nm)) for nm in self.names}
+        self.errors = {nm: sp.get('errors', {}).get(nm) for nm in self.names}
+        self.n = len(self.names)
+        self.W = int(walkers)
+        if self.W % 2 or self.W < 2 * self.n:
+            raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
+        self.a, self.seed, self.stream = float(a), int(seed), int(stream)
+        if not self.a > 1.0:
+            raise ValueError('a: the stretch scale must exceed 1')
+        self.thin = int(thin)
+        if self.thin < 1:
+            raise ValueError('thin >= 1')
+        self.segment = max(1, int(segment))
+        self.driver_asked = driver
+        self.driver = None
+        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
+        self.cols = np.array([vega.param_names.index(nm) for nm in self.names], dtype=np.int32)
+        self.reset()
+
+    def reset(self):
+        self.x = self.lnl = None
+        self.accepted = np.zeros(self.W, dtype=np.int64)
+        self.step = 0
+        self._chain, self._chain_lnl = [], []
+        self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
+                          seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
+
+    # ---- start
+    def _start_positions(self, start, init_scale):
+        rng = np.random.default_rng(self.seed)
+        if isinstance(start, str) and start == 'prior':
+            return self.lo + (self.hi - self.lo) * rng.random((self.W, self.n))
+        if isinstance(start, str) and start == 'ball':
+            centre = np.array([float(self.values[nm]) for nm in self.names])
+            err = np.array([float(self.errors[nm]) if self.errors[nm] is not None else 0.01 * (h - l)
+                            for nm, l, h in zip(self.names, self.lo, self.hi)])
+            x = np.empty((self.W, self.n))
+            for w in range(self.W):
+                for _ in range(10000):
+                    p = centre + init_scale * err * rng.standard_normal(self.n)
+                    if np.all(p >= self.lo) and np.all(p <= self.hi):
+                        break
+                else:
+                    raise ValueError('start ball: no draw inside the box (configured values outside the limits?)')
+                x[w] = p
+            return x
+        x = np.array(start, dtype=np.float64)
+        if x.shape != (self.W, self.n):
+            raise ValueError(f'start: an array [{self.W}, {self.n}], "ball" or "prior"')
+        if not (np.all(x >= self.lo) and np.all(x <= self.hi)):
+            raise ValueError('start: every walker inside the box')
+        return x
+
+    def _fixed_row(self):
+        return np.asarray(self.vega._theta(None), dtype=np.float64).copy()
+
+    def _prepare(self, start, init_scale):
+        vega = self.vega
+        theta = self._fixed_row()
+        if self.x is None:
+            x0 = self._start_positions(start, init_scale)
+            theta_w = np.repeat(theta[None, :], self.W, axis=0)
+            theta_w[:, self.cols] = x0
+        else:
+            x0 = None
+            theta_w = theta[None, :]
+        vega.freeze_metals(theta_w[0])          # (fast_metals: the first walker plays the reference's first call)
+        pinned = set(int(c) for c in getattr(vega, '_pinned_slots', ()))
+        if pinned & set(int(c) for c in self.cols):
+            raise ValueError('frozen metal terms: ' + ', '.join(vega._pinned_names) + ' must keep the values they had '
+                             'when the terms were frozen (or be listed in [sample] beforehand)')
+        eng = vega.engine
+        is_single = hasattr(eng, 'ensemble_run')
+        self.driver = self.driver_asked if is_single else 'python'
+        if self.x is None:
+            chi2 = np.asarray(vega.chi2_batch(theta_w), dtype=np.float64)
+            self.x, self.lnl = x0, log_lik(self.log_norm(), chi2)
+            if not np.all(np.isfinite(self.lnl)):
+                raise ValueError('a start walker has a non-finite log-likelihood')
+        return theta
+
+    def log_norm(self):
+        return float(self.vega._log_norm())
+
+    # ---- run
+    def run(self, n_steps, start='ball', init_scale=1.0):
+        """Advance the ensemble by ``n_steps`` steps (the first call draws the start: ``'ball'`` - the configured values plus
+        init_scale x errors x N(0, 1), redrawn until inside the box - ``'prior'`` - uniform in the box - or an array [W, n]; both
+        draws from ``np.random.default_rng(seed)``).  Later calls continue the chain."""
+        theta = self._prepare(start, init_scale)
+        done = 0
+        while done < n_steps:
+            k = min(self.segment, n_steps - done)
+            if self.driver == 'device':
+                chain, chain_lnl, st = self._segment_device(theta, k)
+            else:
+                chain, chain_lnl, st = self._segment_python(theta, k)
+            self._chain.append(chain)
+            self._chain_lnl.append(chain_lnl)
+            for key in st:
+                if key in self.stats:
+                    self.stats[key] += st[key]
+            self.stats['calls'] += 1
+            self.step += k
+            done += k
+        return self
+
+    def _segment_device(self, theta, k):
+        self.vega._sync_monte_carlo()
+        chain, chain_lnl, st = self.vega.engine.ensemble_run(
+            self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.step, k, thin=self.thin, a=self.a,
+            log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint, chunk=self.chunk,
+            lanes=self.lanes)
+        return chain, chain_lnl, st
+
+    def _segment_python(self, theta, k):
+        """The readable restatement: proposals and decisions in NumPy, chi2 through ``chi2_batch_device`` in the device driver's
+        chunks, with its table level and lanes."""
+        import time
+        import torch
+        vega, eng = self.vega, self.vega.engine
+        t0 = time.perf_counter()
+        H = self.W // 2
+        log_norm = self.log_norm()
+        single = hasattr(eng, 'ensemble_run')
+        chunk = max(1, min(self.chunk if self.chunk > 0 else eng.max_batch, eng.max_batch))
+        hint = self.const_hint
+        if hint < 0:
+            hint = eng.derived_const_hint(self.cols) if single else 0
+        saved_hint, saved_lanes = getattr(eng, 'nl_hint', 0), getattr(eng, 'lanes', 1)
+        want_lanes = min(self.lanes if self.lanes > 0 else 2, 2)
+        device = torch.device('cuda', getattr(eng, 'device', 0))
+        calls = [0]
+
+        def evaluate(rows_x, h):
+            rows_t = np.repeat(theta[None, :], H, axis=0)
+            rows_t[:, self.cols] = rows_x
+            t_dev = torch.from_numpy(rows_t).to(device)
+            chi2 = np.empty(H)
+            for off in range(0, H, chunk):
+                chi2[off:off + chunk] = vega.chi2_batch_device(t_dev[off:off + chunk].contiguous()).cpu().numpy()
+                calls[0] += 1
+            # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+            return chi2, np.zeros(H, dtype=np.int32)
+
+        try:
+            eng.set_constant_nl_hint(hint > 0, hint >= 2)
+            if single and want_lanes > saved_lanes:
+                eng.set_lanes(want_lanes)
+            chain, chain_lnl, st = python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed,
+                                                self.stream, self.lo, self.hi, log_norm, evaluate)
+        finally:
+            eng.set_constant_nl_hint(saved_hint > 0, saved_hint >= 2)
+            if single and getattr(eng, 'lanes', 1) != saved_lanes:
+                eng.set_lanes(saved_lanes)
+        st['engine_calls'] = calls[0]
+        st['host_synchronisations'] = calls[0]
+        st['seconds'] = time.perf_counter() - t0
+        return chain, chain_lnl, st
+
+    # ---- results
+    def _stack(self, parts, discard, thin, flat):
+        if parts:
+            arr = np.concatenate(parts)
+        else:
+            arr = np.empty((0, self.W) + ((self.n,) if parts is self._chain else ()))
+        arr = arr[int(discard)::int(thin)]
+        return arr.reshape((-1,) + arr.shape[2:]) if flat else arr
+
+    def get_chain(self, discard=0, thin=1, flat=False):
+        """Recorded positions [rows, W, n] (rows = steps / thin of the sampler), ``discard`` / ``thin`` in recorded rows;
+        ``flat``: [rows W, n]."""
+        return self._stack(self._chain, discard, thin, flat)
+
+    def get_log_lik(self, discard=0, thin=1, flat=False):
+        return self._stack(self._chain_lnl, discard, thin, flat)
+
+    @property
+    def acceptance_fraction(self):
+        return self.accepted / max(self.step, 1)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5):
+        """Integrated autocorrelation time per parameter in recorded rows (emcee's estimator: :func:`integrated_time`)."""
+        return integrated_time(self.get_chain(discard=discard, thin=thin), c=c)
+
+    def write(self, path, name):
+        """getdist's plain-text chain of the recorded rows (:func:`write_getdist`): ``name.txt`` and ``name.paramnames``."""
+        return write_getdist(path, name, self.names, self.get_chain(flat=True), self.get_log_lik(flat=True))
+
+
+# ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
+_ENSEMBLE_DEFAULTS = dict(name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
+                          driver='device')
+
+
+def sampler_settings(main_config, sample_params):
+    """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
+    (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
+    parameters: {path, name, walkers, steps, seed, a, thin, init, init_scale, driver}."""
+    control = main_config['control'] if 'control' in main_config else {}
+    run = control.getboolean('run_sampler', False) if hasattr(control, 'getboolean') else False
+    if not run:
+        raise ValueError('Warning: You called the sampler without asking for it. Add "run_sampler = True" to the "[control]" '
+                         'section.')
+    sampler = control.get('sampler', None)
+    if sampler in ('Polychord', 'PocoMC'):
+        raise NotImplementedError(f'sampler = {sampler}: nested sampling is not available here; use sampler = Ensemble')
+    if sampler != 'Ensemble':
+        raise ValueError('Sampler not recognized. Please use Ensemble.')
+    if 'Ensemble' not in main_config:
+        raise RuntimeError('run_sampler called, but no sampler config found')
+    sec = main_config['Ensemble']
+    limits = sample_params['limits']
+    for lims in limits.values():
+        if lims is None or None in tuple(lims):
+            raise ValueError('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
+                             ' just say par_name = True to use defaults.')
+    if 'path' not in sec:
+        raise ValueError('[Ensemble] needs a path')
+    path = Path(os.path.expandvars(sec.get('path')))
+    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
+                           "running.")
+    out = dict(_ENSEMBLE_DEFAULTS, path=path)
+    out['name'] = sec.get('name', out['name'])
+    out['walkers'] = sec.getint('walkers', max(2 * len(limits), 32) + (max(2 * len(limits), 32) % 2))
+    out['steps'] = sec.getint('steps', out['steps'])
+    out['seed'] = sec.getint('seed', out['seed'])
+    out['a'] = sec.getfloat('a', out['a'])
+    out['thin'] = sec.getint('thin', out['thin'])
+    out['init'] = sec.get('init', out['init'])
+    out['init_scale'] = sec.getfloat('init_scale', out['init_scale'])
+    out['driver'] = sec.get('driver', out['driver'])
+    if out['init'] not in ('ball', 'prior'):
+        raise ValueError("[Ensemble] init: 'ball' or 'prior'")
+    if out['driver'] not in ('device', 'python'):
+        raise ValueError("[Ensemble] driver: 'device' or 'python'")
+    if out['walkers'] % 2 or out['walkers'] < 2 * len(limits):
+        raise ValueError(f'[Ensemble] walkers: an even number, at least twice the {len(limits)} sampled parameters')
+    if out['steps'] < 1 or out['thin'] < 1:
+        raise ValueError('[Ensemble] steps and thin must be positive')
+    if not out['a'] > 1.0:
+        raise ValueError('[Ensemble] a: the stretch scale must exceed 1')
+    return out
+
+
+def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwargs):
+    """bin/run_vega_mpi.py for one process: initialise, compute the model once, switch to the Monte-Carlo mock when asked,
+    require ``run_sampler = True`` and ``sampler = Ensemble``, run the ``[Ensemble]`` settings, write the getdist chain.
+    Returns the sampler."""
+    from .interface import VegaInterface
+    print_func('Initializing Vega')
+    vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
+    sample_params = vega.sample_params
+    _ = vega.compute_model(run_init=False)
+    print_func('Finished initializing Vega')
+    control = vega.main_config['control'] if 'control' in vega.main_config else configparser.ConfigParser()['DEFAULT']
+    run_montecarlo = control.getboolean('run_montecarlo', False)
+    if run_montecarlo and vega.mc_config is not None:
+        vega.initialize_monte_carlo(print_func=print_func)
+        sample_params = vega.mc_config['sample']
+    elif run_montecarlo:
+        raise ValueError('You asked to run over a Monte Carlo simulation, but no "[monte carlo]" section provided.')
+    cfg = sampler_settings(vega.main_config, sample_params)
+    print_func('Running the ensemble sampler')
+    sampler = EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
+                              sample_params=sample_params)
+    sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
+    sampler.write(cfg['path'], cfg['name'])
+    print_func('Finished running sampler')
+    return sampler

@@ -109,6 +109,16 @@ class VegaInterface:
         from .output import Output
         self.output = Output(self.main_config['output'] if self.main_config is not None and 'output' in self.main_config
                              else None, self.problem.items)
+        # the sampler switch (reference vega_interface.py:186-195), read but never checked here: configs carry `sampler = True`
+        # without asking for a run; run_vega_sampler checks the settings when it is asked to sample
+        self.run_sampler, self.sampler = False, None
+        if self.main_config is not None and 'control' in self.main_config:
+            control = self.main_config['control']
+            try:
+                self.run_sampler = control.getboolean('run_sampler', False)
+            except ValueError:
+                self.run_sampler = False
+            self.sampler = control.get('sampler', None)
         self.bestfit = self.minimizer = None
         self.bestfit_model = self.bestfit_corr_stats = None
         self.chisq = self.reduced_chisq = self.p_value = self.total_data_size = None
