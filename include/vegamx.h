@@ -11,6 +11,10 @@
  * (vega/broadband_poly.py:74-198), the distortion-matrix product (vega/model.py:143-144)
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
+ * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
+ * an ensemble MCMC sampler (vmx_ensemble_run) and a nested sampler with the evidence (vmx_nested_run), the counterparts of
+ * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
+ *
  * The reference is pure Python and has no FFI of its own; the binding a maintainer adds is the
  * ctypes layer shown in INTEGRATION.md (vega_amd/engine.py is that binding).
  *
@@ -152,8 +156,8 @@ typedef struct {
 
 const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
- * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats): lets a foreign binding verify its
- * struct layout at load time. */
+ * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
+ * 13 vmx_nested_stats): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -456,6 +460,54 @@ typedef struct {
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
                      int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats);
+/* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
+ * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
+ * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice
+ * steps from a random survivor under lnL > L*; the end points replace the dead.  One small kernel heads the iteration
+ * (k_ns_iteration); then rounds: k_ns_advance gives every thread the answer to its last request, advances its state machine and
+ * compacts the next requests into the engine's rows, the host reads the row count (one mapped word) and enqueues the engine's
+ * chain over the rows in chunks of `chunk` (two lanes alternate when the quadratic form serves them).  When no thread asks any
+ * more the same kernel has written the live and the newly dead lnL beside the word, and `stop` decides whether to go on.
+ *   spec      n_params = the engine's; n sampled columns col[n] with their box [lo, hi] (finite, lo < hi: the uniform prior);
+ *             nlive live points, K threads, num_repeats slice steps per thread; log_norm (lnL = log_norm - 0.5 chi2); seed /
+ *             stream (the Philox key); theta_fixed[n_params], the row that supplies the columns not sampled
+ *   live_u, live_lnl   [nlive][n] in the unit cube, [nlive] host: the run's state, read at entry (unless opt->draw_live) and
+ *             written back at exit; *iteration the global index of the next iteration, advanced by the iterations done (a run
+ *             cut into calls is the same run)
+ *   dead_u, dead_lnl, dead_nlive   [n_iterations K][n], [n_iterations K], [n_iterations K] host: the deaths of this call in
+ *             order, each with the live count at its death (nlive - j for the j-th of an iteration); stats->iterations K rows
+ *             are written
+ *   opt       const_hint (-1: derived - a column varies when it is sampled), chunk (rows per engine call, 0: max_batch), lanes
+ *             (0: 2), draw_live (nonzero: *iteration must be 0; the live points are drawn from the Philox blocks (i, 0, j, 2) and
+ *             evaluated first), stop (called after every iteration with the iterations done in the run, the K newly dead lnL and
+ *             the live lnL; nonzero ends the call; NULL: all n_iterations run), user (handed to stop); NULL: -1, 0, 0, 0, NULL
+ *   stats     host_waits = rounds + iterations + 1 (the copy back) + 1 with draw_live
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): n outside 1 .. 32, nlive outside n + 2 .. 4096, K
+ * outside 1 .. nlive - n - 1, num_repeats < 1, a column out of range or repeated, a non-finite limit or lo >= hi, a live point
+ * outside the cube or with a NaN lnL (without draw_live).  A HIP failure later returns -2 and leaves the engine usable. */
+#define VMX_NS_MAXN 32
+#define VMX_NS_MAX_LIVE 4096
+typedef struct {
+    int32_t n_params, n;
+    const int32_t* col; const double* lo; const double* hi;
+    int32_t nlive, K, num_repeats, reserved;
+    double log_norm;
+    uint64_t seed, stream;
+    const double* theta_fixed;
+} vmx_nested_spec;
+typedef int32_t (*vmx_nested_stop)(void* user, int64_t iterations, const double* dead_lnl, const double* live_lnl);
+typedef struct {
+    int32_t const_hint, chunk, lanes, draw_live;
+    vmx_nested_stop stop; void* user;
+} vmx_nested_options;
+typedef struct {
+    int64_t iterations, rounds, rows, rows_own_position, engine_calls, host_waits;
+    double seconds, seconds_enqueuing;
+    int32_t const_hint, lanes;          /* what the call ran with */
+} vmx_nested_stats;
+int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                   int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                   const vmx_nested_options* opt, vmx_nested_stats* stats);
 /* The table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns varies[n_params] != 0 allow - what
  * vmx_fit_migrad and vmx_ensemble_run derive when they are given const_hint = -1; a caller that evaluates such batches itself
  * sets it with vmx_set_constant_nl_hint. */
@@ -507,7 +559,7 @@ int vmx_get_mu_nodes(vmx_engine* e, double* mu, double* w, int32_t capacity);
  * alternate between the engine's own per-batch workspace and a second one - a clone that BORROWS every static tensor
  * (matrices, tables, operators; no copy) and owns its workspace, its per-batch tables and its stream - so that two
  * independent batches are in flight and the kernels of one fill the partly idle first / last block rounds of the other's
- * (an ensemble sampler's half-ensembles, Monte-Carlo realisations, nested-sampling threads; the reference's
+ * (an ensemble sampler's half-ensembles, Monte-Carlo realisations, the nested sampler's threads: vmx_nested_run; the reference's
  * bin/run_vega_mc_mpi.py:54-65 gives every rank such independent work).  Per batch the arithmetic, and therefore every bit
  * of chi2, is that of one lane.  A call returns once its kernels are enqueued, as before; vmx_sync waits for both lanes;
  * vmx_last_stream is the stream of the last vmx_eval_device (to order a consumer after it with an event; vmx_stream stays

@@ -3,6 +3,7 @@ from .interface import VegaInterface  # noqa: F401
 from .setup import Grid as Coordinates  # noqa: F401  (reference vega/coordinates.py: the grids a caller hands to a model-only correlation)
 from .errors import VegaModelError, VegaBoundsError, VegaArinyoError  # noqa: F401
 from .ensemble import EnsembleSampler, run_vega_sampler  # noqa: F401  (posterior sampling: bin/run_vega_mpi.py for one process)
+from .nested import NestedSampler  # noqa: F401  (evidence and a weighted posterior: sampler = Nested)
 
 
 def run_vega(config_path, search_dirs=(), print_func=print, **engine_args):

@@ -7,6 +7,7 @@
 #include "vmx_device.h"
 #include "vmx_fit.h"
 #include "vmx_ensemble.h"
+#include "vmx_nested.h"
 
 #include <atomic>
 #include <cmath>
@@ -246,6 +247,178 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_de
     }
 }
 
+// Nested sampling (vmx_nested_run): live points, the threads' state machines, the rows of a round and the dead record
+struct NsWorkspace {
+    DevBuf<double> live_u, live_lnl, mean, cov, chol, lstar, dead_u, dead_lnl, theta, chi2, fixed, lo, hi;
+    DevBuf<double> th;                  // [K] vmx_ns::Thread
+    DevBuf<int32_t> rank, surv, killed, slot, dead_n, status, inv;
+    DevBuf<int64_t> counters;
+    int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round
+    double* pin_lnl = nullptr; double* dpin_lnl = nullptr;           // ... and, when an iteration ends, live lnL [nlive] + dead lnL [K]
+    size_t pin_lnl_n = 0;
+    hipEvent_t ev_lane = nullptr;
+    ~NsWorkspace() {
+        if (pin_word) (void)hipHostFree(pin_word);
+        if (pin_lnl) (void)hipHostFree(pin_lnl);
+        if (ev_lane) (void)hipEventDestroy(ev_lane);
+    }
+};
+
+struct NsDev {
+    double* live_u; double* live_lnl;                       // [nlive][n], [nlive]
+    int32_t* rank; int32_t* surv; int32_t* killed;          // [nlive], [nlive - K], [K]
+    double* mean; double* cov; double* chol; double* lstar; // [n], [n][n], [n][n], [1]
+    vmx_ns::Thread* th; int32_t* slot;                      // [K]: the machines, and the row of each one's last request (-1: none)
+    double* dead_u; double* dead_lnl; int32_t* dead_n;      // the call's record [iterations][K] ([n])
+    double* theta; const double* chi2; const int32_t* status;       // the engine's rows and its answers
+    const double* fixed; const int32_t* inv; const double* lo; const double* hi;    // inv[p]: sampled index of column p, or -1
+    int32_t* host_word; double* host_lnl; int64_t* counters;        // counters[0]: rows that were a thread's own position
+    int32_t nlive, K, n, P, num_repeats;
+    double log_norm;
+    uint64_t seed, stream;
+};
+
+constexpr int NS_THREADS = 1024;
+
+// the initial live points: u from the Philox blocks (i, 0, j, 2), and their rows for the engine
+__global__ __launch_bounds__(NS_THREADS) void k_ns_draw_live(NsDev D)
+{
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) vmx_ns::draw_live(i, D.n, D.seed, D.stream, D.live_u + (size_t)i * D.n);
+    __syncthreads();
+    for (int q = threadIdx.x; q < D.nlive * D.P; q += blockDim.x) {
+        const int i = q / D.P, p = q % D.P, d = D.inv[p];
+        D.theta[q] = d < 0 ? D.fixed[p] : vmx_ns::map_cube(D.lo[d], D.hi[d], D.live_u[(size_t)i * D.n + d]);
+    }
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_live_lnl(NsDev D)
+{
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.live_lnl[i] = vmx_ns::lnl_of(D.status[i], D.chi2[i], D.log_norm);
+}
+
+// The head of iteration `it` (record row `rec` of this call) in one work-group: rank the live points by counting, append the K
+// deaths to the record, the survivors' mean and covariance (one lane per entry), the factor (one lane: n <= 32), L*, and every
+// thread at its start.  Every expression: vmx_nested.h.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it, int64_t rec)
+{
+    __shared__ double s_lnl[vmx_ns::MAX_LIVE];
+    __shared__ int32_t s_rank[vmx_ns::MAX_LIVE];
+    const int nlive = D.nlive, K = D.K, n = D.n, m = nlive - K;
+    for (int i = threadIdx.x; i < nlive; i += blockDim.x) s_lnl[i] = D.live_lnl[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < nlive; i += blockDim.x) {
+        const int r = vmx_ns::rank_of(i, s_lnl, nlive);
+        s_rank[i] = r;
+        D.rank[i] = r;
+        if (r < K) {
+            D.killed[r] = i;
+            const size_t row = (size_t)rec * K + r;
+            for (int d = 0; d < n; ++d) D.dead_u[row * n + d] = D.live_u[(size_t)i * n + d];
+            D.dead_lnl[row] = s_lnl[i];
+            D.dead_n[row] = nlive - r;
+            if (r == K - 1) *D.lstar = s_lnl[i];
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nlive; i += blockDim.x) {
+        if (s_rank[i] < K) continue;
+        int pos = 0;
+        for (int j = 0; j < i; ++j) pos += s_rank[j] >= K ? 1 : 0;
+        D.surv[pos] = i;
+    }
+    for (int a = threadIdx.x; a < n; a += blockDim.x) D.mean[a] = vmx_ns::mean_entry(a, D.live_u, s_rank, nlive, K, n);
+    __syncthreads();
+    for (int q = threadIdx.x; q < n * n; q += blockDim.x) {
+        const int a = q / n, b = q % n;
+        if (b > a) continue;
+        const double c = vmx_ns::cov_entry(a, b, D.live_u, s_rank, D.mean, nlive, K, n);
+        D.cov[a * n + b] = c;
+        D.cov[b * n + a] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) (void)vmx_ns::whiten(n, D.cov, D.chol);
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        const int i = D.surv[vmx_ns::start_choice(k, it, m, D.seed, D.stream)];
+        vmx_ns::start(D.th[k], n, D.live_u + (size_t)i * n, s_lnl[i]);
+        D.slot[k] = -1;
+    }
+}
+
+// One answer for every thread that asked, in one work-group: lane by lane (contiguous threads per lane, so that the compaction
+// keeps their order) read chi2 / status of the thread's row, advance its machine, then scan the requests of the threads still
+// running and emit their rows (the fixed row with the sampled columns mapped out of the cube) and the row count to the host's
+// word.  When nothing is asked for the iteration is over: the end points take the killed points' slots, and the live and the
+// newly dead lnL go to the host beside the word.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, int64_t rec)
+{
+    __shared__ int32_t s_scan[NS_THREADS];
+    __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
+    const int K = D.K, n = D.n, P = D.P;
+    const int per = (K + NS_THREADS - 1) / NS_THREADS;
+    const int k0 = threadIdx.x * per;
+    vmx_ns::Iteration I{D.chol, *D.lstar, it, D.seed, D.stream, n, D.num_repeats};
+    int mine = 0;
+    uint32_t asks = 0;
+    for (int j = 0; j < per; ++j) {
+        const int k = k0 + j;
+        if (k >= K) break;
+        vmx_ns::Thread& T = D.th[k];
+        if (T.state == vmx_ns::S_DONE) continue;
+        const int row = D.slot[k];
+        const double answer = row >= 0 ? vmx_ns::lnl_of(D.status[row], D.chi2[row], D.log_norm) : -INFINITY;
+        if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
+    }
+    s_scan[threadIdx.x] = mine;
+    __syncthreads();
+    for (int step = 1; step < NS_THREADS; step <<= 1) {
+        const int v = threadIdx.x >= step ? s_scan[threadIdx.x - step] : 0;
+        __syncthreads();
+        s_scan[threadIdx.x] += v;
+        __syncthreads();
+    }
+    const int total = s_scan[NS_THREADS - 1];
+    int row = s_scan[threadIdx.x] - mine;
+    int own = 0;
+    for (int j = 0; j < per; ++j) {
+        const int k = k0 + j;
+        if (k >= K) break;
+        if (asks & (1u << j)) {
+            D.slot[k] = row;
+            s_row_thread[row] = k;
+            own += D.th[k].inside ? 0 : 1;
+            row += 1;
+        } else D.slot[k] = -1;
+    }
+    if (own) atomicAdd((unsigned long long*)D.counters, (unsigned long long)own);
+    __syncthreads();
+    // (a lane keeps its column: what the column needs is read once, the rows go round the waves)
+    for (int p = threadIdx.x % 64; p < P; p += 64) {
+        const int d = D.inv[p];
+        const double fixed = D.fixed[p], lo = d < 0 ? 0.0 : D.lo[d], hi = d < 0 ? 0.0 : D.hi[d];
+#pragma unroll 4
+        for (int r = threadIdx.x / 64; r < total; r += NS_THREADS / 64) {
+            double v = fixed;
+            if (d >= 0) {
+                const vmx_ns::Thread& T = D.th[s_row_thread[r]];
+                v = vmx_ns::map_cube(lo, hi, T.inside ? T.y[d] : T.x[d]);
+            }
+            D.theta[(size_t)r * P + p] = v;
+        }
+    }
+    if (total == 0) {
+        for (int k = threadIdx.x; k < K; k += blockDim.x) {
+            const int i = D.killed[k];
+            const vmx_ns::Thread& T = D.th[k];
+            for (int d = 0; d < n; ++d) D.live_u[(size_t)i * n + d] = T.x[d];
+            D.live_lnl[i] = T.lnl;
+            D.host_lnl[D.nlive + k] = D.dead_lnl[(size_t)rec * K + k];
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.host_lnl[i] = D.live_lnl[i];
+    }
+    if (threadIdx.x == 0) *D.host_word = total;
+}
+
 }  // namespace
 
 struct vmx_engine {
@@ -266,6 +439,7 @@ struct vmx_engine {
     const int32_t* call_mock = nullptr;     // per-call mock rows of the walkers (device pointer; vmx_eval_device_mocks, vmx_fit_migrad)
     FitWorkspace* fitws = nullptr;
     EnsWorkspace* ensws = nullptr;
+    NsWorkspace* nsws = nullptr;
     hipEvent_t lane_wait = nullptr;         // vmx_ensemble_run: the rows of the second lane's calls are complete at this event
 
     int nk = 0, nkp = 0, n_mu = 0;
@@ -422,6 +596,7 @@ struct vmx_engine {
         for (void* p : host_allocs) (void)hipHostFree(p);
         delete fitws;
         delete ensws;
+        delete nsws;
         if (pin_theta) (void)hipHostFree(pin_theta);
         if (pin_chi2) (void)hipHostFree(pin_chi2);
         if (pin_status) (void)hipHostFree(pin_status);
@@ -775,6 +950,9 @@ int vmx_struct_size(int32_t which)
         case 8: return (int)sizeof(vmx_ensemble_spec);
         case 9: return (int)sizeof(vmx_ensemble_options);
         case 10: return (int)sizeof(vmx_ensemble_stats);
+        case 11: return (int)sizeof(vmx_nested_spec);
+        case 12: return (int)sizeof(vmx_nested_options);
+        case 13: return (int)sizeof(vmx_nested_stats);
         default: return -1;
     }
 }
@@ -3120,7 +3298,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
-    L->fitws = nullptr; L->ensws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
+    L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
     L->graphs.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
     L->pin_theta = nullptr; L->pin_chi2 = nullptr; L->pin_status = nullptr; L->pin_done = nullptr; L->pin_part = nullptr;
@@ -3686,6 +3864,177 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
         R.rejected_outside_box += box[w];
         R.rejected_failed_model += failed[w];
     }
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// ---- evidence where the live points live (vmx_nested.h)
+static_assert(VMX_NS_MAXN == vmx_ns::MAXN && VMX_NS_MAX_LIVE == vmx_ns::MAX_LIVE, "nested sampling limits");
+
+int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                   int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                   const vmx_nested_options* opt, vmx_nested_stats* stats)
+{
+    REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration, "vmx_nested_run");
+    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
+            "vmx_nested_run: parameter columns, limits and the fixed row");
+    const int n = spec->n, P = e->n_params, nlive = spec->nlive, K = spec->K;
+    REQUIRE(n >= 1 && n <= VMX_NS_MAXN, "vmx_nested_run: 1 .. 32 sampled columns");
+    REQUIRE(nlive >= n + 2 && nlive <= VMX_NS_MAX_LIVE, "vmx_nested_run: n + 2 .. 4096 live points");
+    REQUIRE(K >= 1 && K <= nlive - n - 1, "vmx_nested_run: 1 .. nlive - n - 1 threads");
+    REQUIRE(spec->num_repeats >= 1, "vmx_nested_run: num_repeats >= 1");
+    std::vector<char> varies(P, 0);
+    std::vector<int32_t> inv(P, -1);
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_nested_run: parameter column");
+        REQUIRE(!varies[spec->col[i]], "vmx_nested_run: a column is listed twice");
+        varies[spec->col[i]] = 1;
+        inv[spec->col[i]] = i;
+        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_nested_run: limits");
+    }
+    REQUIRE(std::isfinite(spec->log_norm), "vmx_nested_run: log_norm");
+    REQUIRE(n_iterations >= 0 && *iteration >= 0, "vmx_nested_run: n_iterations >= 0, iteration >= 0");
+    REQUIRE(n_iterations == 0 || (dead_u && dead_lnl && dead_nlive), "vmx_nested_run: the dead record");
+    const bool draw = opt && opt->draw_live != 0;
+    REQUIRE(!draw || *iteration == 0, "vmx_nested_run: live points are drawn at iteration 0");
+    if (!draw)
+        for (int i = 0; i < nlive; ++i) {
+            REQUIRE(!std::isnan(live_lnl[i]), "vmx_nested_run: a live point has a NaN lnL");
+            for (int d = 0; d < n; ++d) {
+                const double v = live_u[(size_t)i * n + d];
+                REQUIRE(v >= 0.0 && v <= 1.0, "vmx_nested_run: a live point lies outside the unit cube");
+            }
+        }
+    int hint = opt ? opt->const_hint : -1;
+    REQUIRE(hint >= -1 && hint <= 2, "vmx_nested_run: const_hint -1 (derive it), 0, 1 or 2");
+    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_nested_run: chunk, lanes");
+    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
+    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
+    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    const size_t cap = (size_t)std::max(nlive, K), rec_rows = (size_t)std::max(n_iterations, 1) * K;
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->nsws) e->nsws = new NsWorkspace();
+    NsWorkspace& S = *e->nsws;
+    if (ensure(S.live_u, (size_t)nlive * n) || ensure(S.live_lnl, nlive) || ensure(S.rank, nlive) || ensure(S.surv, nlive) ||
+        ensure(S.killed, K) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) || ensure(S.lstar, 1) ||
+        ensure(S.th, (size_t)K * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, K) || ensure(S.dead_u, rec_rows * n) ||
+        ensure(S.dead_lnl, rec_rows) || ensure(S.dead_n, rec_rows) || ensure(S.theta, cap * P) || ensure(S.chi2, cap) ||
+        ensure(S.status, cap) || ensure(S.fixed, P) || ensure(S.inv, P) || ensure(S.lo, n) || ensure(S.hi, n) || ensure(S.counters, 1))
+        return -2;
+    if (!S.pin_word) {
+        HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_word, S.pin_word, 0));
+        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
+    }
+    if (S.pin_lnl_n < (size_t)nlive + K) {
+        if (S.pin_lnl) { (void)hipHostFree(S.pin_lnl); S.pin_lnl = nullptr; S.pin_lnl_n = 0; }
+        HIP_OK(hipHostMalloc((void**)&S.pin_lnl, ((size_t)nlive + K) * sizeof(double), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_lnl, S.pin_lnl, 0));
+        S.pin_lnl_n = (size_t)nlive + K;
+    }
+    hipStream_t st = e->stream;
+    if (!draw) {
+        HIP_OK(hipMemcpyAsync(S.live_u.p, live_u, (size_t)nlive * n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.live_lnl.p, live_lnl, (size_t)nlive * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemsetAsync(S.counters.p, 0, sizeof(int64_t), st));
+    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.inv.p, inv.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+
+    NsDev D{};
+    D.live_u = S.live_u.p; D.live_lnl = S.live_lnl.p; D.rank = S.rank.p; D.surv = S.surv.p; D.killed = S.killed.p;
+    D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.lstar = S.lstar.p;
+    D.th = (vmx_ns::Thread*)S.th.p; D.slot = S.slot.p;
+    D.dead_u = S.dead_u.p; D.dead_lnl = S.dead_lnl.p; D.dead_n = S.dead_n.p;
+    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
+    D.fixed = S.fixed.p; D.inv = S.inv.p; D.lo = S.lo.p; D.hi = S.hi.p;
+    D.host_word = S.dpin_word; D.host_lnl = S.dpin_lnl; D.counters = S.counters.p;
+    D.nlive = nlive; D.K = K; D.n = n; D.P = P; D.num_repeats = spec->num_repeats;
+    D.log_norm = spec->log_norm; D.seed = spec->seed; D.stream = spec->stream;
+
+    // the engine as the sampler's likelihood: chi2-only device evaluations of the round's rows, eager launches, two lanes when the
+    // quadratic form serves them; the table level the sampled columns allow
+    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
+    const bool saved_ring = e->ring_allowed;
+    e->const_hint = hint;
+    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
+    e->lane_calls = 0;
+    struct Restore {
+        vmx_engine* e; int hint, lanes; bool ring;
+        ~Restore() { wait_lane(e); e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
+    } restore{e, saved_hint, saved_lanes, saved_ring};
+
+    vmx_nested_stats R{};
+    R.const_hint = hint;
+    R.lanes = e->n_lanes;
+    double enqueue_s = 0.0;
+    // the engine's chain over the first `total` rows; the stream then waits for the second lane
+    auto evaluate = [&](int total) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipStream_t lane_stream = nullptr;
+        for (int off = 0; off < total; off += chunk) {
+            const int B = std::min(chunk, total - off);
+            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
+            if (e->last_stream != st) lane_stream = e->last_stream;
+            R.engine_calls += 1;
+        }
+        if (lane_stream) {      // (the next kernel reads every chunk's chi2)
+            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
+            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
+        }
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    };
+    if (draw) {
+        hipLaunchKernelGGL(k_ns_draw_live, dim3(1), dim3(NS_THREADS), 0, st, D);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st));       // (the second lane reads the rows)
+        R.host_waits += 1;
+        R.rows += nlive;
+        if (evaluate(nlive)) return -2;
+        hipLaunchKernelGGL(k_ns_live_lnl, dim3(1), dim3(NS_THREADS), 0, st, D);
+        HIP_OK(hipGetLastError());
+    }
+    int done = 0;
+    while (done < n_iterations) {
+        const int64_t it = *iteration + done;
+        hipLaunchKernelGGL(k_ns_iteration, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
+        for (;;) {
+            hipLaunchKernelGGL(k_ns_advance, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipStreamSynchronize(st));   // (the round's only wait: the row count, one mapped word)
+            R.host_waits += 1;
+            const int total = S.pin_word[0];
+            if (total <= 0) break;
+            if ((size_t)total > cap) return fail(-2, "vmx_nested_run: a round asked for more rows than its buffers hold");
+            R.rounds += 1;
+            R.rows += total;
+            if (evaluate(total)) return -2;
+        }
+        done += 1;
+        std::memcpy(live_lnl, S.pin_lnl, (size_t)nlive * sizeof(double));
+        if (opt && opt->stop && opt->stop(opt->user, *iteration + done, S.pin_lnl + nlive, live_lnl)) break;
+    }
+    HIP_OK(hipMemcpyAsync(live_u, S.live_u.p, (size_t)nlive * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(live_lnl, S.live_lnl.p, (size_t)nlive * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (done > 0) {
+        HIP_OK(hipMemcpyAsync(dead_u, S.dead_u.p, (size_t)done * K * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(dead_lnl, S.dead_lnl.p, (size_t)done * K * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(dead_nlive, S.dead_n.p, (size_t)done * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    int64_t own = 0;
+    HIP_OK(hipMemcpyAsync(&own, S.counters.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    R.host_waits += 1;
+    *iteration += done;
+    R.iterations = done;
+    R.rows_own_position = own;
+    R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;
     return 0;

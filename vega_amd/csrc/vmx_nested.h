@@ -1,0 +1,275 @@
+// Nested sampling by slice sampling in the whitened unit cube, pinned decision for decision.
+//
+// The loop runs where the live points are (vmx_nested_run, vegamx.hip: k_ns_iteration kills, whitens and starts the threads,
+// k_ns_advance moves every thread's state machine by one likelihood answer and compacts the next requests);
+// vega_amd/nested.py restates every expression below in NumPy (the `python` driver) and tests/helpers/nested_driver.cpp compiles
+// this header with g++ so that tests/test_nested_host.py can hold the two against each other bit for bit.  No HIP type, no heap.
+//
+//   cube             the sampler works in u in [0, 1]^n; a physical parameter is lo + (hi - lo) u (map_cube), a uniform prior over
+//                    the limits.  lnL = log_norm - 0.5 chi2 (vmx_ens::log_lik); a failed model (!vmx_ens::model_ok) has
+//                    lnL = -inf and satisfies no constraint.
+//   random numbers   vmx_ens::philox4x64_10 keyed (seed, stream).  Thread k at iteration t reads the blocks with counter
+//                    (k, t, j, 1), j = 0, 1, 2 ... in the order it needs them (j: the thread's own draw index, so its stream
+//                    depends on nothing but its own history); initial live point i reads (i, 0, j, 2), coordinate c from word
+//                    c % 4 of block j = c / 4.  A uniform double from a word: vmx_ens::u01.
+//   one iteration    nlive live points, K threads (1 <= K, nlive - K >= n + 1):
+//     kill           rank_i = #{j : lnL_j < lnL_i, or lnL_j == lnL_i and j < i}; the points of rank 0 .. K-1 die in that order,
+//                    death j recorded with the live count nlive - j; L* = lnL of rank K-1.
+//     whiten         m = nlive - K survivors, sums over them in live-index order, one accumulator per entry:
+//                    mean_a = (sum u_a) / m, cov_ab = (sum (u_a - mean_a)(u_b - mean_b)) / (m - 1), C its lower Cholesky factor
+//                    (row by row, see cholesky); a pivot that is not positive makes the iteration use diag(sqrt(cov_aa)).
+//     start          thread k copies survivor number vmx_ens::partner(word 0 of block 0, m) (survivors counted in live-index
+//                    order); its draws go on at block 1.
+//     slice steps    num_repeats times, under lnL > L* and inside the cube:
+//                    direction  n + 1 words q = 0 .. n from the next n / 4 + 1 blocks (word q % 4 of block q / 4): g_q = 2 u - 1,
+//                               d = C g / |g|; the last word is r.
+//                    bracket    [L, R] = [-(r w), (1 - r) w] in units of d, w = 2.
+//                    step out   L -= w while x + L d is acceptable, then R += w likewise (at most MAX_STEP_OUT times each).
+//                    shrink     t = L + (R - L) u (word 0 of the next block); x + t d acceptable: the step ends there; otherwise
+//                               the end on t's side moves to t (after MAX_SHRINK rejections the step ends where it began).
+//                    a point outside the cube is unacceptable without an evaluation: the thread's request is then its own position
+//                    and the answer is ignored.
+//     replace        the K end points and their lnL take the killed points' slots, thread k the slot of rank k.
+//
+// Thread is a resumable state machine: advance(state, lnL of my last request) -> next request | done.  Every expression is the
+// separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are correctly rounded.
+#pragma once
+#include "vmx_ensemble.h"
+
+namespace vmx_ns {
+
+constexpr int MAXN = 32;
+constexpr int MAX_LIVE = 4096;
+constexpr int MAX_STEP_OUT = 32;
+constexpr int MAX_SHRINK = 64;
+constexpr double WIDTH = 2.0;
+enum State : int32_t { S_NEXT = 0, S_LEFT = 1, S_RIGHT = 2, S_SHRINK = 3, S_DONE = 4 };
+
+struct Thread {
+    double x[MAXN], d[MAXN], y[MAXN];       // position, direction, the point asked for (x + t d)
+    double lnl, L, R, t;
+    int64_t draw;                           // next block index of this thread in this iteration
+    int32_t state, repeat, n_out, n_shrink, inside, reserved;
+};
+
+// what every thread of an iteration shares
+struct Iteration {
+    const double* C;                        // [n][n] lower factor
+    double lstar;
+    int64_t iteration;
+    uint64_t seed, stream;
+    int32_t n, num_repeats;
+};
+
+VMX_HD inline vmx_ens::Block thread_block(int64_t k, int64_t t, int64_t j, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::philox4x64_10((uint64_t)k, (uint64_t)t, (uint64_t)j, 1, seed, stream);
+}
+
+VMX_HD inline vmx_ens::Block live_block(int64_t i, int64_t j, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::philox4x64_10((uint64_t)i, 0, (uint64_t)j, 2, seed, stream);
+}
+
+// initial live point i: u[n]
+VMX_HD inline void draw_live(int64_t i, int n, uint64_t seed, uint64_t stream, double* u)
+{
+    for (int c = 0; c < n; c += 4) {
+        const vmx_ens::Block b = live_block(i, c / 4, seed, stream);
+        for (int q = 0; q < 4 && c + q < n; ++q) u[c + q] = vmx_ens::u01(b.w[q]);
+    }
+}
+
+VMX_HD inline double map_cube(double lo, double hi, double u)
+{
+    VMX_NO_CONTRACT
+    const double w = hi - lo;
+    const double p = w * u;
+    return lo + p;
+}
+
+VMX_HD inline double lnl_of(int32_t status, double chi2, double log_norm)
+{
+    return vmx_ens::model_ok(status, chi2) ? vmx_ens::log_lik(log_norm, chi2) : -INFINITY;
+}
+
+// ---- kill
+VMX_HD inline int rank_of(int i, const double* lnl, int nlive)
+{
+    const double v = lnl[i];
+    int r = 0;
+    for (int j = 0; j < nlive; ++j) r += (lnl[j] < v || (lnl[j] == v && j < i)) ? 1 : 0;
+    return r;
+}
+
+// ---- whiten (rank[i] >= K: a survivor)
+VMX_HD inline double mean_entry(int a, const double* u, const int32_t* rank, int nlive, int K, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    for (int i = 0; i < nlive; ++i)
+        if (rank[i] >= K) acc = acc + u[(size_t)i * n + a];
+    return acc / (double)(nlive - K);
+}
+
+VMX_HD inline double cov_entry(int a, int b, const double* u, const int32_t* rank, const double* mean, int nlive, int K, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    const double ma = mean[a], mb = mean[b];
+    for (int i = 0; i < nlive; ++i) {
+        if (rank[i] < K) continue;
+        const double da = u[(size_t)i * n + a] - ma;
+        const double db = u[(size_t)i * n + b] - mb;
+        const double p = da * db;
+        acc = acc + p;
+    }
+    return acc / (double)(nlive - K - 1);
+}
+
+// lower Cholesky factor of cov [n][n] (its lower triangle is read) into C [n][n], column by column; false: a pivot was not positive
+VMX_HD inline bool cholesky(int n, const double* cov, double* C)
+{
+    VMX_NO_CONTRACT
+    for (int i = 0; i < n * n; ++i) C[i] = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double s = cov[j * n + j];
+        for (int k = 0; k < j; ++k) {
+            const double p = C[j * n + k] * C[j * n + k];
+            s = s - p;
+        }
+        if (!(s > 0.0)) return false;
+        const double piv = sqrt(s);
+        C[j * n + j] = piv;
+        for (int i = j + 1; i < n; ++i) {
+            double t = cov[i * n + j];
+            for (int k = 0; k < j; ++k) {
+                const double p = C[i * n + k] * C[j * n + k];
+                t = t - p;
+            }
+            C[i * n + j] = t / piv;
+        }
+    }
+    return true;
+}
+
+// the factor an iteration uses; true: the Cholesky factor, false: the diagonal of standard deviations
+VMX_HD inline bool whiten(int n, const double* cov, double* C)
+{
+    if (cholesky(n, cov, C)) return true;
+    for (int i = 0; i < n * n; ++i) C[i] = 0.0;
+    for (int a = 0; a < n; ++a) C[a * n + a] = cov[a * n + a] > 0.0 ? sqrt(cov[a * n + a]) : 0.0;
+    return false;
+}
+
+// ---- the thread
+// survivor number (in live-index order) that thread k of iteration t starts from
+VMX_HD inline int64_t start_choice(int64_t k, int64_t t, int64_t m, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::partner(thread_block(k, t, 0, seed, stream).w[0], m);
+}
+
+VMX_HD inline void start(Thread& T, int n, const double* u, double lnl)
+{
+    for (int i = 0; i < n; ++i) { T.x[i] = u[i]; T.y[i] = u[i]; T.d[i] = 0.0; }
+    T.lnl = lnl; T.L = 0.0; T.R = 0.0; T.t = 0.0;
+    T.draw = 1;
+    T.state = S_NEXT; T.repeat = 0; T.n_out = 0; T.n_shrink = 0; T.inside = 1; T.reserved = 0;
+}
+
+// y = x + t d, and whether it lies in the cube
+VMX_HD inline void trial(Thread& T, int n)
+{
+    VMX_NO_CONTRACT
+    bool in = true;
+    for (int i = 0; i < n; ++i) {
+        const double p = T.t * T.d[i];
+        const double v = T.x[i] + p;
+        T.y[i] = v;
+        in = in && v >= 0.0 && v <= 1.0;
+    }
+    T.inside = in ? 1 : 0;
+}
+
+VMX_HD inline void new_direction(Thread& T, const Iteration& I, int64_t k)
+{
+    VMX_NO_CONTRACT
+    const int n = I.n;
+    double g[MAXN];
+    double r = 0.0;
+    for (int q = 0; q <= n; q += 4) {
+        const vmx_ens::Block b = thread_block(k, I.iteration, T.draw + q / 4, I.seed, I.stream);
+        for (int w = 0; w < 4 && q + w <= n; ++w) {
+            const double u = vmx_ens::u01(b.w[w]);
+            if (q + w < n) { const double two = 2.0 * u; g[q + w] = two - 1.0; }
+            else r = u;
+        }
+    }
+    T.draw += n / 4 + 1;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) { const double p = g[i] * g[i]; s = s + p; }
+    double nrm = sqrt(s);
+    if (!(nrm > 0.0)) { g[0] = 1.0; nrm = 1.0; }
+    for (int i = 0; i < n; ++i) g[i] = g[i] / nrm;
+    for (int i = 0; i < n; ++i) {
+        double acc = 0.0;
+        for (int j = 0; j <= i; ++j) { const double p = I.C[i * n + j] * g[j]; acc = acc + p; }
+        T.d[i] = acc;
+    }
+    const double rw = r * WIDTH;
+    T.L = -rw;
+    const double q1 = 1.0 - r;
+    T.R = q1 * WIDTH;
+}
+
+VMX_HD inline void draw_trial(Thread& T, const Iteration& I, int64_t k)
+{
+    VMX_NO_CONTRACT
+    const double u = vmx_ens::u01(thread_block(k, I.iteration, T.draw, I.seed, I.stream).w[0]);
+    T.draw += 1;
+    const double wid = T.R - T.L;
+    const double p = wid * u;
+    T.t = T.L + p;
+    trial(T, I.n);
+}
+
+// `answer`: lnL of the thread's last request (ignored in S_NEXT, and whenever that request lay outside the cube).
+// true: T.y / T.inside hold the next request (the thread asks for T.inside ? T.y : T.x); false: the thread is done, T.x / T.lnl
+// are its end point.
+VMX_HD inline bool advance(Thread& T, const Iteration& I, int64_t k, double answer)
+{
+    VMX_NO_CONTRACT
+    const bool ok = T.inside != 0 && answer > I.lstar;
+    if (T.state == S_LEFT) {
+        if (ok && T.n_out < MAX_STEP_OUT) { T.L = T.L - WIDTH; T.n_out += 1; T.t = T.L; trial(T, I.n); return true; }
+        T.state = S_RIGHT; T.n_out = 0; T.t = T.R; trial(T, I.n);
+        return true;
+    }
+    if (T.state == S_RIGHT) {
+        if (ok && T.n_out < MAX_STEP_OUT) { T.R = T.R + WIDTH; T.n_out += 1; T.t = T.R; trial(T, I.n); return true; }
+        T.state = S_SHRINK; T.n_shrink = 0;
+        draw_trial(T, I, k);
+        return true;
+    }
+    if (T.state == S_SHRINK) {
+        if (ok) {
+            for (int i = 0; i < I.n; ++i) T.x[i] = T.y[i];
+            T.lnl = answer; T.repeat += 1; T.state = S_NEXT;
+        } else {
+            if (T.t < 0.0) T.L = T.t; else T.R = T.t;
+            T.n_shrink += 1;
+            if (T.n_shrink < MAX_SHRINK) { draw_trial(T, I, k); return true; }
+            T.repeat += 1; T.state = S_NEXT;
+        }
+    }
+    if (T.state == S_NEXT) {
+        if (T.repeat >= I.num_repeats) { T.state = S_DONE; T.inside = 1; return false; }
+        new_direction(T, I, k);
+        T.state = S_LEFT; T.n_out = 0; T.t = T.L;
+        trial(T, I.n);
+        return true;
+    }
+    return false;
+}
+
+}  // namespace vmx_ns

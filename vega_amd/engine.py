@@ -135,6 +135,29 @@ class EnsembleStats(C.Structure):
                 ('lanes', C.c_int32)]
 
 
+VMX_NS_MAXN = 32
+VMX_NS_MAX_LIVE = 4096
+NESTED_STOP = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+class NestedSpec(C.Structure):
+    _fields_ = [('n_params', C.c_int32), ('n', C.c_int32), ('col', C.POINTER(C.c_int32)), ('lo', C.POINTER(C.c_double)),
+                ('hi', C.POINTER(C.c_double)), ('nlive', C.c_int32), ('K', C.c_int32), ('num_repeats', C.c_int32),
+                ('reserved', C.c_int32), ('log_norm', C.c_double), ('seed', C.c_uint64), ('stream', C.c_uint64),
+                ('theta_fixed', C.POINTER(C.c_double))]
+
+
+class NestedOptions(C.Structure):
+    _fields_ = [('const_hint', C.c_int32), ('chunk', C.c_int32), ('lanes', C.c_int32), ('draw_live', C.c_int32),
+                ('stop', NESTED_STOP), ('user', C.c_void_p)]
+
+
+class NestedStats(C.Structure):
+    _fields_ = [('iterations', C.c_int64), ('rounds', C.c_int64), ('rows', C.c_int64), ('rows_own_position', C.c_int64),
+                ('engine_calls', C.c_int64), ('host_waits', C.c_int64), ('seconds', C.c_double), ('seconds_enqueuing', C.c_double),
+                ('const_hint', C.c_int32), ('lanes', C.c_int32)]
+
+
 FIT_BATCH_BINS = ('1', '2..4', '5..16', '17..64', '65..256', '257..1024', '1025..4096', '4097..')
 
 
@@ -207,6 +230,8 @@ def load_library():
                                    C.POINTER(FitResultArrays), C.POINTER(FitStats)]
     lib.vmx_ensemble_run.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, dptr, dptr, C.POINTER(C.c_int64), C.c_int64,
                                      C.c_int32, C.c_int32, dptr, dptr, C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats)]
+    lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
+                                   C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
     lib.vmx_set_constant_nl_hint.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_direct_pk.argtypes = [C.c_void_p, dptr, C.c_int32, C.c_int32]
@@ -240,7 +265,7 @@ def load_library():
     lib.vmx_get_timings.argtypes = [C.c_void_p, dptr, C.POINTER(C.c_int64), C.c_int32]
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
-                                    EnsembleSpec, EnsembleOptions, EnsembleStats)):
+                                    EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -253,7 +278,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1004,6 +1029,46 @@ class Engine:
                                               _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None,
                                               C.byref(opt), C.byref(stats)))
         return chain, chain_lnl, {name: getattr(stats, name) for name, _ in EnsembleStats._fields_}
+
+    def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
+                   seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):
+        """Up to ``n_iterations`` iterations of the nested sampler on the device (include/vegamx.h: vmx_nested_run): ``cols`` the
+        sampled parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``live_u`` [nlive, n] in the unit
+        cube / ``live_lnl`` [nlive] the run's state (updated in place; drawn first with ``draw_live``), ``iteration`` the global
+        index of the next iteration.  ``stop(iterations, dead_lnl [K], live_lnl [nlive])`` is asked after every iteration; a true
+        answer ends the call.  Returns (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K], iteration + m, statistics) for the m
+        iterations done."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
+        for arr in (live_u, live_lnl):
+            if not (isinstance(arr, np.ndarray) and arr.dtype == np.float64 and arr.flags.c_contiguous):
+                raise ValueError('live_u, live_lnl: C-contiguous float64 arrays (updated in place)')
+        nlive, K, n_iterations = live_u.shape[0], int(threads), max(0, int(n_iterations))
+        if live_u.shape != (nlive, cols.size) or live_lnl.shape != (nlive,) or theta_fixed.shape != (self.n_params,):
+            raise ValueError('live_u [nlive, n], live_lnl [nlive], theta_fixed [n_params]')
+        rows = n_iterations * max(K, 0)
+        dead_u, dead_lnl, dead_n = np.empty((rows, cols.size)), np.empty(rows), np.empty(rows, dtype=np.int32)
+        spec = NestedSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), nlive, K, int(num_repeats), 0, float(log_norm),
+                          int(seed), int(stream), _dp(theta_fixed))
+        raised = []
+
+        def _stop(_user, iterations, p_dead, p_live):
+            try:
+                return 1 if stop(int(iterations), np.ctypeslib.as_array(p_dead, (K,)), np.ctypeslib.as_array(p_live, (nlive,))) else 0
+            except BaseException as exc:        # (an exception cannot cross the C frames: end the call, raise it afterwards)
+                raised.append(exc)
+                return 1
+
+        callback = NESTED_STOP(_stop) if stop is not None else NESTED_STOP()
+        opt = NestedOptions(int(const_hint), int(chunk), int(lanes), 1 if draw_live else 0, callback, None)
+        stats = NestedStats()
+        it = C.c_int64(int(iteration))
+        self._check(self.lib.vmx_nested_run(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
+                                            _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats)))
+        if raised:
+            raise raised[0]
+        m = int(stats.iterations) * K
+        return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), {name: getattr(stats, name) for name, _ in NestedStats._fields_}
 
     def derived_const_hint(self, cols):
         """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:

@@ -146,13 +146,15 @@ def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi
     return chain, chain_lnl, st
 
 
-def write_getdist(path, name, names, chain, chain_lnl):
+def write_getdist(path, name, names, chain, chain_lnl, weights=None):
     """getdist's plain-text chain: ``name.txt`` (one row per sample: weight 1, -lnL, the parameters) and ``name.paramnames``
-    (one ``name label`` line per parameter, label = name).  ``chain`` [..., n], ``chain_lnl`` [...]."""
+    (one ``name label`` line per parameter, label = name).  ``chain`` [..., n], ``chain_lnl`` [...]; ``weights`` [...]: a
+    weighted chain (a nested sampler's), the first column then holds them."""
     path = Path(path)
     chain = np.asarray(chain, dtype=np.float64).reshape(-1, len(names))
     lnl = np.asarray(chain_lnl, dtype=np.float64).reshape(-1)
-    np.savetxt(path / f'{name}.txt', np.column_stack([np.ones(lnl.size), -lnl, chain]), fmt='%.17g')
+    first = np.ones(lnl.size) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
+    np.savetxt(path / f'{name}.txt', np.column_stack([first, -lnl, chain]), fmt='%.17g')
     with open(path / f'{name}.paramnames', 'w') as f:
         for nm in names:
             f.write(f'{nm} {nm}\n')
@@ -188,6 +190,99 @@ def integrated_time(chain, c=5):
     return tau
 
 
+# ------------------------------------------------------------------ what every sampler here sets up the same way
+_NO_LIMITS = ('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
+              ' just say par_name = True to use defaults.')
+
+
+class SampledBox:
+    """The sampled parameters of ``vega`` with their box: ``sample_params['limits']`` (the ``[sample]`` section, or the
+    ``[monte carlo]`` one after ``initialize_monte_carlo``, as bin/run_vega_mpi.py picks them), checked as the reference checks
+    them.  names, lo, hi, values, errors, n, cols (the engine's columns)."""
+
+    def __init__(self, vega, sample_params=None):
+        sp = vega.sample_params if sample_params is None else sample_params
+        limits = dict(sp['limits'])
+        for lims in limits.values():
+            if lims is None or None in tuple(lims):
+                raise ValueError(_NO_LIMITS)
+        self.names = list(limits)
+        if not self.names:
+            raise ValueError('no sampled parameters')
+        unknown = [nm for nm in self.names if nm not in vega.param_names]
+        if unknown:
+            raise KeyError(f'unknown parameters {unknown}')
+        self.lo = np.array([float(limits[nm][0]) for nm in self.names])
+        self.hi = np.array([float(limits[nm][1]) for nm in self.names])
+        if not (np.all(np.isfinite(self.lo)) and np.all(np.isfinite(self.hi)) and np.all(self.lo < self.hi)):
+            raise ValueError('Sampler needs well defined prior limits: finite, lower < upper')
+        self.values = {nm: sp.get('values', {}).get(nm, vega.params.get(nm)) for nm in self.names}
+        self.errors = {nm: sp.get('errors', {}).get(nm) for nm in self.names}
+        self.n = len(self.names)
+        self.cols = np.array([vega.param_names.index(nm) for nm in self.names], dtype=np.int32)
+
+
+def freeze_and_pick_driver(vega, first_row, cols, driver_asked, device_method):
+    """Before the first likelihood: ``freeze_metals`` on ``first_row`` (fast_metals: it plays the reference's first call; the
+    engine may be replaced), the sampled columns must not be pinned by it, and the driver the engine allows - an engine group
+    (one engine per transform setting, no single C handle, hence no ``device_method``) takes ``'python'``."""
+    vega.freeze_metals(first_row)
+    pinned = set(int(c) for c in getattr(vega, '_pinned_slots', ()))
+    if pinned & set(int(c) for c in cols):
+        raise ValueError('frozen metal terms: ' + ', '.join(vega._pinned_names) + ' must keep the values they had '
+                         'when the terms were frozen (or be listed in [sample] beforehand)')
+    return driver_asked if hasattr(vega.engine, device_method) else 'python'
+
+
+class EngineRows:
+    """The engine as a ``python`` driver's likelihood, set up as the device drivers set it up: inside the ``with`` block
+    ``chi2(theta_rows)`` evaluates host rows [R, n_params] through ``chi2_batch_device`` in chunks of ``chunk`` (0: max_batch)
+    with the table level the sampled columns ``cols`` allow (``const_hint`` -1) and two lanes; both are restored on exit.
+    ``calls`` counts the engine calls."""
+
+    def __init__(self, vega, cols, chunk=0, lanes=0, const_hint=-1):
+        self.vega, self.eng = vega, vega.engine
+        eng = self.eng
+        self.single = hasattr(eng, 'ensemble_run')
+        self.chunk = max(1, min(chunk if chunk > 0 else eng.max_batch, eng.max_batch))
+        self.hint = const_hint
+        if self.hint < 0:
+            self.hint = eng.derived_const_hint(cols) if self.single else 0
+        self.want_lanes = min(lanes if lanes > 0 else 2, 2)
+        self.calls = 0
+
+    def __enter__(self):
+        import torch
+        eng = self.eng
+        self.saved_hint, self.saved_lanes = getattr(eng, 'nl_hint', 0), getattr(eng, 'lanes', 1)
+        self.device = torch.device('cuda', getattr(eng, 'device', 0))
+        try:
+            eng.set_constant_nl_hint(self.hint > 0, self.hint >= 2)
+            if self.single and self.want_lanes > self.saved_lanes:
+                eng.set_lanes(self.want_lanes)
+        except BaseException:
+            self.__exit__(None, None, None)
+            raise
+        return self
+
+    def __exit__(self, *exc):
+        eng = self.eng
+        eng.set_constant_nl_hint(self.saved_hint > 0, self.saved_hint >= 2)
+        if self.single and getattr(eng, 'lanes', 1) != self.saved_lanes:
+            eng.set_lanes(self.saved_lanes)
+        return False
+
+    def chi2(self, theta_rows):
+        import torch
+        t_dev = torch.from_numpy(np.ascontiguousarray(theta_rows)).to(self.device)
+        R = theta_rows.shape[0]
+        chi2 = np.empty(R)
+        for off in range(0, R, self.chunk):
+            chi2[off:off + self.chunk] = self.vega.chi2_batch_device(t_dev[off:off + self.chunk].contiguous()).cpu().numpy()
+            self.calls += 1
+        return chi2
+
+
 # ------------------------------------------------------------------ the sampler
 class EnsembleSampler:
     """W walkers over the sampled parameters of ``vega`` (``sample_params['limits']``: the ``[sample]`` section, or the
@@ -202,25 +297,8 @@ class EnsembleSampler:
         if driver not in ('device', 'python'):
             raise ValueError("driver: 'device' or 'python'")
         self.vega = vega
-        sp = vega.sample_params if sample_params is None else sample_params
-        limits = dict(sp['limits'])
-        for lims in limits.values():
-            if lims is None or None in tuple(lims):
-                raise ValueError('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
-                                 ' just say par_name = True to use defaults.')
-        self.names = list(limits)
-        if not self.names:
-            raise ValueError('no sampled parameters')
-        unknown = [nm for nm in self.names if nm not in vega.param_names]
-        if unknown:
-            raise KeyError(f'unknown parameters {unknown}')
-        self.lo = np.array([float(limits[nm][0]) for nm in self.names])
-        self.hi = np.array([float(limits[nm][1]) for nm in self.names])
-        if not (np.all(np.isfinite(self.lo)) and np.all(np.isfinite(self.hi)) and np.all(self.lo < self.hi)):
-            raise ValueError('Sampler needs well defined prior limits: finite, lower < upper')
-        self.values = {nm: sp.get('values', {}).get(nm, vega.params.get(nm)) for nm in self.names}
-        self.errors = {nm: sp.get('errors', {}).get(nm) for nm in self.names}
-        self.n = len(self.names)
+        box = SampledBox(vega, sample_params)
+        self.names, self.lo, self.hi, self.values, self.errors, self.n = box.names, box.lo, box.hi, box.values, box.errors, box.n
         self.W = int(walkers)
         if self.W % 2 or self.W < 2 * self.n:
             raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
@@ -234,7 +312,7 @@ class EnsembleSampler:
         self.driver_asked = driver
         self.driver = None
         self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
-        self.cols = np.array([vega.param_names.index(nm) for nm in self.names], dtype=np.int32)
+        self.cols = box.cols
         self.reset()
 
     def reset(self):
@@ -284,14 +362,7 @@ class EnsembleSampler:
         else:
             x0 = None
             theta_w = theta[None, :]
-        vega.freeze_metals(theta_w[0])          # (fast_metals: the first walker plays the reference's first call)
-        pinned = set(int(c) for c in getattr(vega, '_pinned_slots', ()))
-        if pinned & set(int(c) for c in self.cols):
-            raise ValueError('frozen metal terms: ' + ', '.join(vega._pinned_names) + ' must keep the values they had '
-                             'when the terms were frozen (or be listed in [sample] beforehand)')
-        eng = vega.engine
-        is_single = hasattr(eng, 'ensemble_run')
-        self.driver = self.driver_asked if is_single else 'python'
+        self.driver = freeze_and_pick_driver(vega, theta_w[0], self.cols, self.driver_asked, 'ensemble_run')
         if self.x is None:
             chi2 = np.asarray(vega.chi2_batch(theta_w), dtype=np.float64)
             self.x, self.lnl = x0, log_lik(self.log_norm(), chi2)
@@ -337,44 +408,20 @@ class EnsembleSampler:
         """The readable restatement: proposals and decisions in NumPy, chi2 through ``chi2_batch_device`` in the device driver's
         chunks, with its table level and lanes."""
         import time
-        import torch
-        vega, eng = self.vega, self.vega.engine
         t0 = time.perf_counter()
         H = self.W // 2
         log_norm = self.log_norm()
-        single = hasattr(eng, 'ensemble_run')
-        chunk = max(1, min(self.chunk if self.chunk > 0 else eng.max_batch, eng.max_batch))
-        hint = self.const_hint
-        if hint < 0:
-            hint = eng.derived_const_hint(self.cols) if single else 0
-        saved_hint, saved_lanes = getattr(eng, 'nl_hint', 0), getattr(eng, 'lanes', 1)
-        want_lanes = min(self.lanes if self.lanes > 0 else 2, 2)
-        device = torch.device('cuda', getattr(eng, 'device', 0))
-        calls = [0]
+        with EngineRows(self.vega, self.cols, self.chunk, self.lanes, self.const_hint) as rows:
+            def evaluate(rows_x, h):
+                rows_t = np.repeat(theta[None, :], H, axis=0)
+                rows_t[:, self.cols] = rows_x
+                # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+                return rows.chi2(rows_t), np.zeros(H, dtype=np.int32)
 
-        def evaluate(rows_x, h):
-            rows_t = np.repeat(theta[None, :], H, axis=0)
-            rows_t[:, self.cols] = rows_x
-            t_dev = torch.from_numpy(rows_t).to(device)
-            chi2 = np.empty(H)
-            for off in range(0, H, chunk):
-                chi2[off:off + chunk] = vega.chi2_batch_device(t_dev[off:off + chunk].contiguous()).cpu().numpy()
-                calls[0] += 1
-            # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
-            return chi2, np.zeros(H, dtype=np.int32)
-
-        try:
-            eng.set_constant_nl_hint(hint > 0, hint >= 2)
-            if single and want_lanes > saved_lanes:
-                eng.set_lanes(want_lanes)
             chain, chain_lnl, st = python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed,
                                                 self.stream, self.lo, self.hi, log_norm, evaluate)
-        finally:
-            eng.set_constant_nl_hint(saved_hint > 0, saved_hint >= 2)
-            if single and getattr(eng, 'lanes', 1) != saved_lanes:
-                eng.set_lanes(saved_lanes)
-        st['engine_calls'] = calls[0]
-        st['host_synchronisations'] = calls[0]
+        st['engine_calls'] = rows.calls
+        st['host_synchronisations'] = rows.calls
         st['seconds'] = time.perf_counter() - t0
         return chain, chain_lnl, st
 
@@ -409,14 +456,15 @@ class EnsembleSampler:
 
 
 # ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
-_ENSEMBLE_DEFAULTS = dict(name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
+_ENSEMBLE_DEFAULTS = dict(sampler='Ensemble', name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
                           driver='device')
 
 
 def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
-    parameters: {path, name, walkers, steps, seed, a, thin, init, init_scale, driver}."""
+    parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver}; with ``sampler = Nested`` the
+    ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
     run = control.getboolean('run_sampler', False) if hasattr(control, 'getboolean') else False
     if not run:
@@ -424,17 +472,20 @@ def sampler_settings(main_config, sample_params):
                          'section.')
     sampler = control.get('sampler', None)
     if sampler in ('Polychord', 'PocoMC'):
-        raise NotImplementedError(f'sampler = {sampler}: nested sampling is not available here; use sampler = Ensemble')
+        raise NotImplementedError(f'sampler = {sampler}: that library is not available here; use sampler = Nested (evidence and a '
+                                  'weighted posterior) or sampler = Ensemble')
+    if sampler == 'Nested':
+        from .nested import nested_settings
+        return nested_settings(main_config, sample_params)
     if sampler != 'Ensemble':
-        raise ValueError('Sampler not recognized. Please use Ensemble.')
+        raise ValueError('Sampler not recognized. Please use Nested or Ensemble.')
     if 'Ensemble' not in main_config:
         raise RuntimeError('run_sampler called, but no sampler config found')
     sec = main_config['Ensemble']
     limits = sample_params['limits']
     for lims in limits.values():
         if lims is None or None in tuple(lims):
-            raise ValueError('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
-                             ' just say par_name = True to use defaults.')
+            raise ValueError(_NO_LIMITS)
     if 'path' not in sec:
         raise ValueError('[Ensemble] needs a path')
     path = Path(os.path.expandvars(sec.get('path')))
@@ -465,8 +516,8 @@ def sampler_settings(main_config, sample_params):
 
 def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwargs):
     """bin/run_vega_mpi.py for one process: initialise, compute the model once, switch to the Monte-Carlo mock when asked,
-    require ``run_sampler = True`` and ``sampler = Ensemble``, run the ``[Ensemble]`` settings, write the getdist chain.
-    Returns the sampler."""
+    require ``run_sampler = True`` and ``sampler = Ensemble`` or ``Nested``, run the ``[Ensemble]`` / ``[Nested]`` settings, write
+    the getdist chain (a nested run also ``name.stats`` with the evidence).  Returns the sampler."""
     from .interface import VegaInterface
     print_func('Initializing Vega')
     vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
@@ -481,10 +532,20 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwarg
     elif run_montecarlo:
         raise ValueError('You asked to run over a Monte Carlo simulation, but no "[monte carlo]" section provided.')
     cfg = sampler_settings(vega.main_config, sample_params)
-    print_func('Running the ensemble sampler')
-    sampler = EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
-                              sample_params=sample_params)
-    sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
+    if cfg['sampler'] == 'Nested':
+        from .nested import NestedSampler
+        print_func('Running the nested sampler')
+        sampler = NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
+                                precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
+                                max_iterations=cfg['max_iterations'], sample_params=sample_params)
+        sampler.run()
+        log_z, err = sampler.log_evidence()
+        print_func(f'log(Z) = {log_z} +- {err}')
+    else:
+        print_func('Running the ensemble sampler')
+        sampler = EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
+                                  sample_params=sample_params)
+        sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
     sampler.write(cfg['path'], cfg['name'])
     print_func('Finished running sampler')
     return sampler

@@ -1,0 +1,583 @@
+"""Evidence and a weighted posterior: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube, run where the
+live points are.
+
+The reference samples through PolyChord (bin/run_vega_mpi.py: ``[control] run_sampler = True``, ``sampler = Polychord``) and
+takes away ``log Z +- err`` with a weighted posterior.  Here an iteration kills the K live points of lowest lnL, whitens with the
+survivors' covariance, and lets K threads each walk ``num_repeats`` slice steps from a random survivor under the hard constraint
+lnL > L*; the K end points replace the dead.  Every thread asks for one likelihood at a time, so a round is one batch of at most K
+rows for the engine.  The ``device`` driver keeps live points, threads and bookkeeping on the GPU (include/vegamx.h:
+vmx_nested_run); the ``python`` driver is the readable restatement in NumPy over ``VegaInterface.chi2_batch_device``.  Both follow
+vega_amd/csrc/vmx_nested.h decision for decision, so that they produce the same dead record bit for bit.  Evidence, information
+and termination are computed here, on the host, from the dead record - one code for both drivers.
+
+What is not here: clustering of separated modes (whitening uses one covariance), ``boost_posterior``, resume files, the
+marginalised coefficients as derived parameters, pocoMC.
+"""
+import math
+import time
+from pathlib import Path
+
+import numpy as np
+
+from . import ensemble as E
+
+MAXN = 32
+MAX_LIVE = 4096
+MAX_STEP_OUT = 32
+MAX_SHRINK = 64
+WIDTH = 2.0
+S_NEXT, S_LEFT, S_RIGHT, S_SHRINK, S_DONE = range(5)
+
+
+# ------------------------------------------------------------------ the algorithm (vmx_nested.h) in NumPy
+def _blocks(k, t, j, last, seed, stream):
+    """Philox blocks of the counters (k, t, j, last) (k, j arrays of one shape): [..., 4] uint64."""
+    k = np.asarray(k, dtype=np.uint64)
+    ctr = np.zeros(k.shape + (4,), dtype=np.uint64)
+    ctr[..., 0] = k
+    ctr[..., 1] = np.uint64(t)
+    ctr[..., 2] = np.asarray(j, dtype=np.uint64)
+    ctr[..., 3] = np.uint64(last)
+    return E.philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def thread_blocks(k, t, j, seed, stream=0):
+    return _blocks(k, t, j, 1, seed, stream)
+
+
+def draw_live(nlive, n, seed, stream=0):
+    """The initial live points [nlive, n] in the unit cube: coordinate c of point i from word c % 4 of block (i, 0, c / 4, 2)."""
+    nb = (n + 3) // 4
+    i = np.repeat(np.arange(nlive)[:, None], nb, axis=1)
+    j = np.repeat(np.arange(nb)[None, :], nlive, axis=0)
+    return E.u01(_blocks(i, 0, j, 2, seed, stream).reshape(nlive, nb * 4)[:, :n])
+
+
+def map_cube(lo, hi, u):
+    w = hi - lo
+    p = w * u
+    return lo + p
+
+
+def lnl_of(status, chi2, log_norm):
+    chi2 = np.asarray(chi2, dtype=np.float64)
+    with np.errstate(invalid='ignore'):
+        return np.where(E.model_ok(status, chi2), E.log_lik(log_norm, chi2), -np.inf)
+
+
+def rank_live(lnl):
+    """rank_i = #{j : lnL_j < lnL_i, or lnL_j == lnL_i and j < i}."""
+    order = np.argsort(lnl, kind='stable')
+    rank = np.empty(len(lnl), dtype=np.int32)
+    rank[order] = np.arange(len(lnl), dtype=np.int32)
+    return rank
+
+
+def _sum_in_order(terms):
+    """Sum over axis 0 with one accumulator per entry, in order, from 0.0 (np.sum would add pairwise)."""
+    return np.add.accumulate(np.concatenate([np.zeros((1,) + terms.shape[1:]), terms]), axis=0)[-1]
+
+
+def mean_cov(u_surv):
+    m = u_surv.shape[0]
+    mean = _sum_in_order(u_surv) / float(m)
+    dev = u_surv - mean
+    cov = _sum_in_order(dev[:, :, None] * dev[:, None, :]) / float(m - 1)
+    return mean, cov
+
+
+def cholesky(cov):
+    """The lower factor column by column as vmx_ns::cholesky computes it, or None when a pivot is not positive."""
+    n = cov.shape[0]
+    C = np.zeros((n, n))
+    for j in range(n):
+        s = cov[j, j]
+        for k in range(j):
+            s = s - C[j, k] * C[j, k]
+        if not s > 0.0:
+            return None
+        piv = np.sqrt(s)
+        C[j, j] = piv
+        if j + 1 < n:
+            t = cov[j + 1:, j].copy()
+            for k in range(j):
+                t = t - C[j + 1:, k] * C[j, k]
+            C[j + 1:, j] = t / piv
+    return C
+
+
+def whiten(cov):
+    """(the factor an iteration uses, whether it is the Cholesky factor)."""
+    C = cholesky(cov)
+    if C is not None:
+        return C, True
+    d = np.diag(cov)
+    return np.diag(np.where(d > 0.0, np.sqrt(np.where(d > 0.0, d, 0.0)), 0.0)), False
+
+
+def iteration_head(live_u, live_lnl, K, t, seed, stream=0):
+    """Kill, whiten and choose the starts of iteration ``t``: dict(rank, killed [K] in order of death, lstar, surv (live indices
+    of the survivors in order), mean, cov, C, cholesky, start [K] (live index each thread starts from))."""
+    nlive = live_u.shape[0]
+    rank = rank_live(live_lnl)
+    killed = np.empty(K, dtype=np.int64)
+    dying = np.flatnonzero(rank < K)
+    killed[rank[dying]] = dying
+    surv = np.flatnonzero(rank >= K)
+    mean, cov = mean_cov(live_u[surv])
+    C, ok = whiten(cov)
+    ks = np.arange(K)
+    choice = E.partner(thread_blocks(ks, t, np.zeros(K, dtype=np.int64), seed, stream)[:, 0], nlive - K).astype(np.int64)
+    return dict(rank=rank, killed=killed, lstar=live_lnl[killed[K - 1]], surv=surv, mean=mean, cov=cov, C=C, cholesky=ok,
+                start=surv[choice])
+
+
+class Threads:
+    """The K state machines of an iteration (vmx_ns::Thread as arrays)."""
+
+    def __init__(self, u, lnl, C, lstar, t, num_repeats, seed, stream=0):
+        K, n = u.shape
+        self.K, self.n = K, n
+        self.x, self.y, self.d = u.copy(), u.copy(), np.zeros((K, n))
+        self.lnl = np.array(lnl, dtype=np.float64)
+        self.L, self.R, self.t = np.zeros(K), np.zeros(K), np.zeros(K)
+        self.draw = np.ones(K, dtype=np.int64)
+        self.state = np.full(K, S_NEXT, dtype=np.int32)
+        self.repeat, self.n_out, self.n_shrink = (np.zeros(K, dtype=np.int32) for _ in range(3))
+        self.inside = np.ones(K, dtype=bool)
+        self.C, self.lstar, self.iteration, self.num_repeats, self.seed, self.stream = C, lstar, t, num_repeats, seed, stream
+
+    def _trial(self, ix):
+        if ix.size == 0:
+            return
+        p = self.t[ix, None] * self.d[ix]
+        v = self.x[ix] + p
+        self.y[ix] = v
+        self.inside[ix] = np.all((v >= 0.0) & (v <= 1.0), axis=1)
+
+    def _new_direction(self, ix):
+        n, nb = self.n, self.n // 4 + 1
+        j = self.draw[ix][:, None] + np.arange(nb)[None, :]
+        k = np.repeat(ix[:, None], nb, axis=1)
+        u = E.u01(thread_blocks(k, self.iteration, j, self.seed, self.stream).reshape(ix.size, nb * 4)[:, :n + 1])
+        self.draw[ix] += nb
+        two = 2.0 * u[:, :n]
+        g = two - 1.0
+        r = u[:, n]
+        s = np.zeros(ix.size)
+        for i in range(n):
+            s = s + g[:, i] * g[:, i]
+        nrm = np.sqrt(s)
+        bad = ~(nrm > 0.0)
+        g[bad, 0] = 1.0
+        nrm[bad] = 1.0
+        g = g / nrm[:, None]
+        d = np.zeros((ix.size, n))
+        for jj in range(n):         # (d_i accumulates C_ij g_j in the order j = 0 .. i)
+            d[:, jj:] = d[:, jj:] + self.C[jj:, jj][None, :] * g[:, jj][:, None]
+        self.d[ix] = d
+        rw = r * WIDTH
+        self.L[ix] = -rw
+        q1 = 1.0 - r
+        self.R[ix] = q1 * WIDTH
+
+    def _draw_trial(self, ix):
+        if ix.size == 0:
+            return
+        u = E.u01(thread_blocks(ix, self.iteration, self.draw[ix], self.seed, self.stream)[:, 0])
+        self.draw[ix] += 1
+        wid = self.R[ix] - self.L[ix]
+        p = wid * u
+        self.t[ix] = self.L[ix] + p
+        self._trial(ix)
+
+    def advance(self, answer):
+        """vmx_ns::advance of every thread with the lnL ``answer`` [K] of its last request: the mask of threads that ask again
+        (their request: ``requests``)."""
+        was = self.state.copy()
+        with np.errstate(invalid='ignore'):
+            ok = self.inside & (answer > self.lstar)
+        more = ok & (self.n_out < MAX_STEP_OUT)
+        a = np.flatnonzero((was == S_LEFT) & more)
+        b = np.flatnonzero((was == S_LEFT) & ~more)
+        self.L[a] = self.L[a] - WIDTH
+        self.n_out[a] += 1
+        self.t[a] = self.L[a]
+        self.state[b] = S_RIGHT
+        self.n_out[b] = 0
+        self.t[b] = self.R[b]
+        a2 = np.flatnonzero((was == S_RIGHT) & more)
+        b2 = np.flatnonzero((was == S_RIGHT) & ~more)
+        self.R[a2] = self.R[a2] + WIDTH
+        self.n_out[a2] += 1
+        self.t[a2] = self.R[a2]
+        self._trial(np.concatenate([a, b, a2]))
+        self.state[b2] = S_SHRINK
+        self.n_shrink[b2] = 0
+        acc = np.flatnonzero((was == S_SHRINK) & ok)
+        self.x[acc] = self.y[acc]
+        self.lnl[acc] = answer[acc]
+        rej = (was == S_SHRINK) & ~ok
+        neg = np.flatnonzero(rej & (self.t < 0.0))
+        pos = np.flatnonzero(rej & ~(self.t < 0.0))
+        self.L[neg] = self.t[neg]
+        self.R[pos] = self.t[pos]
+        self.n_shrink[rej] += 1
+        again = np.flatnonzero(rej & (self.n_shrink < MAX_SHRINK))
+        gave_up = np.flatnonzero(rej & ~(self.n_shrink < MAX_SHRINK))
+        ended = np.concatenate([acc, gave_up])
+        self.repeat[ended] += 1
+        self.state[ended] = S_NEXT
+        self._draw_trial(np.sort(np.concatenate([b2, again])))
+        nxt = self.state == S_NEXT
+        fin = np.flatnonzero(nxt & (self.repeat >= self.num_repeats))
+        self.state[fin] = S_DONE
+        self.inside[fin] = True
+        go = np.flatnonzero(nxt & (self.repeat < self.num_repeats))
+        if go.size:
+            self._new_direction(go)
+            self.state[go] = S_LEFT
+            self.n_out[go] = 0
+            self.t[go] = self.L[go]
+            self._trial(go)
+        return (was != S_DONE) & (self.state != S_DONE)
+
+    def requests(self, asks):
+        """Rows [R, n] in the cube the asking threads want evaluated (a thread whose point left the cube asks for its own
+        position), and how many of them are such."""
+        ks = np.flatnonzero(asks)
+        return ks, np.where(self.inside[ks, None], self.y[ks], self.x[ks]), int((~self.inside[ks]).sum())
+
+
+def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, stream, evaluate, stop=None):
+    """Up to ``n_iterations`` iterations in NumPy from the state ``live_u`` [nlive, n], ``live_lnl`` [nlive] (updated in place).
+    ``evaluate(rows_u)`` -> lnL [R] of rows in the cube (-inf: a failed model).  ``stop(iterations, dead_lnl, live_lnl)`` as for
+    the device driver.  Returns (dead_u, dead_lnl, dead_nlive, iteration, stats)."""
+    nlive, n = live_u.shape
+    dead_u, dead_lnl, dead_n = [], [], []
+    st = dict(iterations=0, rounds=0, rows=0, rows_own_position=0)
+    for _ in range(n_iterations):
+        head = iteration_head(live_u, live_lnl, K, iteration, seed, stream)
+        killed = head['killed']
+        dead_u.append(live_u[killed].copy())
+        dead_lnl.append(live_lnl[killed].copy())
+        dead_n.append(nlive - np.arange(K, dtype=np.int32))
+        T = Threads(live_u[head['start']], live_lnl[head['start']], head['C'], head['lstar'], iteration, num_repeats, seed, stream)
+        answer = np.full(K, -np.inf)
+        asks = T.advance(answer)
+        while asks.any():
+            ks, rows, own = T.requests(asks)
+            answer = np.full(K, -np.inf)
+            answer[ks] = evaluate(rows)
+            st['rounds'] += 1
+            st['rows'] += ks.size
+            st['rows_own_position'] += own
+            asks = T.advance(answer)
+        live_u[killed] = T.x
+        live_lnl[killed] = T.lnl
+        iteration += 1
+        st['iterations'] += 1
+        if stop is not None and stop(iteration, dead_lnl[-1], live_lnl):
+            break
+    if not dead_u:
+        return np.empty((0, n)), np.empty(0), np.empty(0, dtype=np.int32), iteration, st
+    return np.concatenate(dead_u), np.concatenate(dead_lnl), np.concatenate(dead_n), iteration, st
+
+
+# ------------------------------------------------------------------ evidence (host, both drivers)
+def _logsumexp(a):
+    a = np.asarray(a, dtype=np.float64)
+    if a.size == 0:
+        return -np.inf
+    m = np.max(a)
+    if not np.isfinite(m):
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(a - m))))
+
+
+def log_weights(dead_lnl, dead_nlive, live_lnl):
+    """log(L_i w_i) of the dead points followed by the live ones: log X_i = log X_{i-1} - 1 / n_i, w_i = X_{i-1} - X_i, the live
+    points X_end / nlive each."""
+    dead_nlive = np.asarray(dead_nlive, dtype=np.float64)
+    log_x = -np.cumsum(1.0 / dead_nlive)
+    log_x_before = np.concatenate([[0.0], log_x[:-1]])
+    log_w = log_x_before + np.log1p(-np.exp(-1.0 / dead_nlive))
+    log_x_end = log_x[-1] if log_x.size else 0.0
+    log_w_live = np.full(len(live_lnl), log_x_end - math.log(len(live_lnl)))
+    return np.concatenate([np.asarray(dead_lnl) + log_w, np.asarray(live_lnl) + log_w_live])
+
+
+def evidence(dead_lnl, dead_nlive, live_lnl):
+    """(log Z, H, posterior weights p_i summing to 1) over the dead points followed by the live ones."""
+    lw = log_weights(dead_lnl, dead_nlive, live_lnl)
+    log_z = _logsumexp(lw)
+    lnl = np.concatenate([np.asarray(dead_lnl, dtype=np.float64), np.asarray(live_lnl, dtype=np.float64)])
+    with np.errstate(invalid='ignore'):
+        p = np.exp(lw - log_z) if np.isfinite(log_z) else np.zeros(lw.size)
+    p = np.where(np.isfinite(p), p, 0.0)
+    used = p > 0.0
+    info = float(np.sum(p[used] * (lnl[used] - log_z))) if np.any(used) else 0.0
+    return log_z, info, p
+
+
+class NestedRun:
+    """A nested-sampling run over ``loglike(rows_u [R, n]) -> lnL [R]`` in the unit cube (-inf: a failed model), NumPy driver: the
+    live points, the dead record, termination and the evidence.  :class:`NestedSampler` puts the engine behind it."""
+
+    def __init__(self, loglike, n, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, stream=0,
+                 max_iterations=None, max_batch=None):
+        self.loglike = loglike
+        self.n = int(n)
+        self.num_live = int(num_live) if num_live is not None else 25 * self.n
+        self.num_repeats = int(num_repeats) if num_repeats is not None else 5 * self.n
+        if threads is None:
+            top = self.num_live // 2 if max_batch is None else min(self.num_live // 2, int(max_batch))
+            threads = max(1, min(top // 64 * 64 if top >= 64 else 1, self.num_live - self.n - 1))
+        self.threads = int(threads)
+        self.precision = float(precision)
+        self.seed, self.stream = int(seed), int(stream)
+        self.max_iterations = None if max_iterations is None else int(max_iterations)
+        if not 1 <= self.n <= MAXN:
+            raise ValueError(f'1 .. {MAXN} sampled parameters')
+        if not self.n + 2 <= self.num_live <= MAX_LIVE:
+            raise ValueError(f'num_live: {self.n + 2} .. {MAX_LIVE} for {self.n} sampled parameters')
+        if not 1 <= self.threads <= self.num_live - self.n - 1:
+            raise ValueError(f'threads: 1 .. num_live - n - 1 = {self.num_live - self.n - 1}')
+        if self.num_repeats < 1:
+            raise ValueError('num_repeats >= 1')
+        if not self.precision > 0.0:
+            raise ValueError('precision > 0')
+        if self.max_iterations is not None and self.max_iterations < 1:
+            raise ValueError('max_iterations >= 1')
+        self.reset()
+
+    def reset(self):
+        self.live_u = self.live_lnl = None
+        self.iteration = 0
+        self.terminated = False
+        self._to_termination = True
+        self._dead_u, self._dead_lnl, self._dead_n = [], [], []
+        self._log_x, self._log_z_dead = 0.0, -np.inf
+        self.stats = dict(iterations=0, rounds=0, rows=0, rows_own_position=0, engine_calls=0, host_waits=0, seconds=0.0,
+                          seconds_enqueuing=0.0, calls=0)
+
+    # ---- termination (PolyChord's precision_criterion), asked after every iteration by either driver
+    def _stop(self, iterations, dead_lnl, live_lnl):
+        nlive = self.num_live
+        with np.errstate(invalid='ignore', divide='ignore'):
+            for j, lnl in enumerate(np.asarray(dead_lnl, dtype=np.float64)):
+                n_j = float(nlive - j)
+                self._log_z_dead = float(np.logaddexp(self._log_z_dead, lnl + self._log_x + math.log1p(-math.exp(-1.0 / n_j))))
+                self._log_x -= 1.0 / n_j
+            log_z_live = self._log_x + _logsumexp(live_lnl) - math.log(nlive)
+            done = bool(log_z_live - np.logaddexp(self._log_z_dead, log_z_live) < math.log(self.precision))
+        if self.max_iterations is not None and iterations >= self.max_iterations:
+            done = True
+        self.terminated = done
+        return done and self._to_termination      # (iterations asked for by number are all run)
+
+    # ---- drivers
+    def _draw(self):
+        self.live_u = np.ascontiguousarray(draw_live(self.num_live, self.n, self.seed, self.stream))
+        self.live_lnl = np.ascontiguousarray(self._evaluate(self.live_u), dtype=np.float64)
+        self.stats['rows'] += self.num_live
+
+    def _evaluate(self, rows_u):
+        return np.asarray(self.loglike(rows_u), dtype=np.float64)
+
+    def _advance(self, n_iterations):
+        """One call of the driver: (dead_u, dead_lnl, dead_nlive, statistics)."""
+        if self.live_u is None:
+            self._draw()
+        du, dl, dn, self.iteration, st = python_iterations(self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
+                                                           self.num_repeats, self.seed, self.stream, self._evaluate, self._stop)
+        return du, dl, dn, st
+
+    def run(self, iterations=None):
+        """To termination (``iterations`` None: the precision criterion or ``max_iterations``), or exactly ``iterations`` more
+        iterations, whatever the criterion says (``terminated`` still reports it); the run does not depend on how it is cut."""
+        t0 = time.perf_counter()
+        self._to_termination = iterations is None
+        per_call = max(1, 65536 // self.threads)        # (the dead record of a call is allocated up front)
+        if iterations is None:
+            left = self.max_iterations - self.iteration if self.max_iterations is not None else per_call
+            call = min(max(0, left), per_call) if not self.terminated else 0
+        else:
+            call = int(iterations)
+        while call > 0:
+            du, dl, dn, st = self._advance(call)
+            self._dead_u.append(du)
+            self._dead_lnl.append(dl)
+            self._dead_n.append(dn)
+            for key, val in st.items():
+                if key in self.stats and key != 'seconds':
+                    self.stats[key] += val
+            self.stats['calls'] += 1
+            if iterations is not None or self.terminated or st['iterations'] == 0:
+                break
+            if self.max_iterations is not None:
+                call = min(per_call, self.max_iterations - self.iteration)
+        self.stats['seconds'] += time.perf_counter() - t0
+        return self
+
+    # ---- results
+    def dead(self):
+        """The dead record: (u [N, n], lnL [N], live count [N])."""
+        if not self._dead_u:
+            return np.empty((0, self.n)), np.empty(0), np.empty(0, dtype=np.int32)
+        return np.concatenate(self._dead_u), np.concatenate(self._dead_lnl), np.concatenate(self._dead_n)
+
+    def _evidence(self):
+        if self.live_u is None:
+            raise ValueError('nothing has run yet')
+        _, dl, dn = self.dead()
+        return evidence(dl, dn, self.live_lnl)
+
+    def log_evidence(self):
+        """(log Z, its error sqrt(H / num_live))."""
+        log_z, info, _ = self._evidence()
+        return log_z, math.sqrt(max(info, 0.0) / self.num_live)
+
+    def information(self):
+        return self._evidence()[1]
+
+    def to_physical(self, u):
+        return u
+
+    def samples(self):
+        """(points [N, n], lnL [N], weights [N] summing to 1): the dead points in order of death, then the live points."""
+        du, dl, _ = self.dead()
+        p = self._evidence()[2]
+        return self.to_physical(np.concatenate([du, self.live_u])), np.concatenate([dl, self.live_lnl]), p / p.sum()
+
+    def equal_weighted(self, rng=None):
+        """Points of equal weight: each sample kept with probability weight / max weight.  (points [M, n], lnL [M])."""
+        rng = np.random.default_rng(rng)
+        pts, lnl, w = self.samples()
+        keep = rng.random(w.size) < w / w.max()
+        return pts[keep], lnl[keep]
+
+
+# ------------------------------------------------------------------ the sampler over the engine
+class NestedSampler(NestedRun):
+    """Nested sampling of ``vega`` over its sampled parameters (``sample_params['limits']`` as for
+    :class:`vega_amd.ensemble.EnsembleSampler`), a uniform prior over the limits.
+
+    Defaults as the reference's PolyChord interface: ``num_live`` 25 n, ``num_repeats`` 5 n; ``threads`` the largest multiple of 64
+    not above min(num_live / 2, vega's max_batch), at least 1.  ``driver``: ``'device'`` (vmx_nested_run) or ``'python'`` (the NumPy
+    restatement over ``chi2_batch_device``); an engine group takes ``'python'``."""
+
+    def __init__(self, vega, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, driver='device',
+                 sample_params=None, stream=0, chunk=0, lanes=0, const_hint=-1, max_iterations=None):
+        if driver not in ('device', 'python'):
+            raise ValueError("driver: 'device' or 'python'")
+        self.vega = vega
+        box = E.SampledBox(vega, sample_params)
+        self.names, self.lo, self.hi, self.cols = box.names, box.lo, box.hi, box.cols
+        self.driver_asked = driver
+        self.driver = None
+        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
+        self._rows = None
+        super().__init__(None, box.n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
+                         stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
+
+    def log_norm(self):
+        return float(self.vega._log_norm())
+
+    def to_physical(self, u):
+        return map_cube(self.lo, self.hi, np.asarray(u, dtype=np.float64))
+
+    def _evaluate(self, rows_u):
+        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
+        rows_t[:, self.cols] = map_cube(self.lo, self.hi, rows_u)
+        # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+        return lnl_of(0, self._rows.chi2(rows_t), self.log_norm())
+
+    def _advance(self, n_iterations):
+        vega = self.vega
+        self._theta = np.asarray(vega._theta(None), dtype=np.float64).copy()
+        if self.driver is None:
+            first = self._theta.copy()
+            first[self.cols] = map_cube(self.lo, self.hi, draw_live(1, self.n, self.seed, self.stream)[0])
+            self.driver = E.freeze_and_pick_driver(vega, first, self.cols, self.driver_asked, 'nested_run')
+        if self.driver == 'python':
+            with E.EngineRows(vega, self.cols, self.chunk, self.lanes, self.const_hint) as self._rows:
+                du, dl, dn, st = super()._advance(n_iterations)
+            st['engine_calls'] = st['host_waits'] = self._rows.calls
+            self._rows = None
+            return du, dl, dn, st
+        vega._sync_monte_carlo()
+        draw = self.live_u is None
+        if draw:
+            self.live_u, self.live_lnl = np.zeros((self.num_live, self.n)), np.zeros(self.num_live)
+        du, dl, dn, self.iteration, st = vega.engine.nested_run(
+            self.cols, self.lo, self.hi, self._theta, self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
+            self.num_repeats, log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint,
+            chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop)
+        return du, dl, dn, st
+
+    def write(self, path, name):
+        """getdist's weighted chain ``name.txt`` (weight / max weight, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
+        ``name.paramnames`` and ``name.stats``."""
+        return write_run(self, path, name, self.names)
+
+
+def nested_settings(main_config, sample_params):
+    """The ``[Nested]`` settings of a main config with ``sampler = Nested`` (called by
+    :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
+    precision, seed, threads, driver, max_iterations}.  ``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
+    mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default."""
+    import os
+    if 'Nested' not in main_config:
+        raise RuntimeError('run_sampler called, but no sampler config found')
+    sec = main_config['Nested']
+    limits = sample_params['limits']
+    for lims in limits.values():
+        if lims is None or None in tuple(lims):
+            raise ValueError(E._NO_LIMITS)
+    if 'path' not in sec:
+        raise ValueError('[Nested] needs a path')
+    path = Path(os.path.expandvars(sec.get('path')))
+    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
+                           "running.")
+    n = len(limits)
+    out = dict(sampler='Nested', path=path, name=sec.get('name', 'nested'), num_live=sec.getint('num_live', 25 * n),
+               num_repeats=sec.getint('num_repeats', 5 * n), precision=sec.getfloat('precision', 0.001),
+               seed=sec.getint('seed', 0), threads=sec.getint('threads', None), driver=sec.get('driver', 'device'),
+               max_iterations=sec.getint('max_iterations', None))
+    if out['driver'] not in ('device', 'python'):
+        raise ValueError("[Nested] driver: 'device' or 'python'")
+    if not n + 2 <= out['num_live'] <= MAX_LIVE:
+        raise ValueError(f'[Nested] num_live: {n + 2} .. {MAX_LIVE} for {n} sampled parameters')
+    if out['threads'] is not None and not 1 <= out['threads'] <= out['num_live'] - n - 1:
+        raise ValueError(f'[Nested] threads: 1 .. num_live - n - 1 = {out["num_live"] - n - 1}')
+    if out['num_repeats'] < 1:
+        raise ValueError('[Nested] num_repeats must be positive')
+    if not out['precision'] > 0.0:
+        raise ValueError('[Nested] precision must be positive')
+    if out['max_iterations'] is not None and out['max_iterations'] < 1:
+        raise ValueError('[Nested] max_iterations must be positive')
+    return out
+
+
+def write_run(run, path, name, names):
+    """The three files of a finished :class:`NestedRun`: (txt, paramnames, stats)."""
+    pts, lnl, w = run.samples()
+    txt, pn = E.write_getdist(path, name, names, pts, lnl, weights=w / w.max())
+    log_z, err = run.log_evidence()
+    stats = Path(path) / f'{name}.stats'
+    with open(stats, 'w') as f:
+        f.write(f'log(Z) = {log_z!r}\nlog(Z) error = {err!r}\nH = {run.information()!r}\n')
+        f.write(f'dead points = {sum(len(d) for d in run._dead_lnl)}\nlikelihood evaluations = {run.stats["rows"]}\n')
+        f.write(f'iterations = {run.iteration}\nseed = {run.seed}\nnum_live = {run.num_live}\nnum_repeats = {run.num_repeats}\n')
+        f.write(f'threads = {run.threads}\n')
+    return txt, pn, stats
+
+
+def read_stats(path):
+    """``name.stats`` back as a dict (floats for the evidence lines, ints for the counts)."""
+    out = {}
+    for line in Path(path).read_text().splitlines():
+        key, _, val = line.partition(' = ')
+        out[key] = float(val) if key in ('log(Z)', 'log(Z) error', 'H') else int(val)
+    return out
