@@ -12,7 +12,8 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run) and a nested sampler with the evidence (vmx_nested_run), the counterparts of
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run) and a tempered SMC sampler (vmx_smc_run), both
+ * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
  * The reference is pure Python and has no FFI of its own; the binding a maintainer adds is the
@@ -157,7 +158,7 @@ typedef struct {
 const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
- * 13 vmx_nested_stats): lets a foreign binding verify its struct layout at load time. */
+ * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -508,6 +509,53 @@ typedef struct {
 int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                    int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
                    const vmx_nested_options* opt, vmx_nested_stats* stats);
+/* Evidence and an equal-weight posterior where the particles live: tempered sequential Monte Carlo (the scheme of pocoMC, the
+ * reference's second sampler in bin/run_vega_mpi.py, without its normalising flow), every decision pinned in
+ * vega_amd/csrc/vmx_smc.h.  N particles walk from the prior (beta = 0) to the posterior (beta = 1); a stage picks the next beta by
+ * bisection on the effective sample size of the importance weights, resamples systematically, whitens with the particles'
+ * covariance (k_smc_stage: one work-group, once per stage) and moves all particles by `sweeps` Metropolis sweeps under L^beta:
+ * k_smc_move decides the sweep just evaluated, adapts the proposal scale and writes the N rows of the next one, then the
+ * engine's chain runs over them in chunks of `chunk` (two lanes alternate when the quadratic form serves them).  A whole stage is
+ * enqueued at once; the host waits once per stage, on a mapped word that carries beta.
+ *   spec      n_params = the engine's; n sampled columns col[n] with their box [lo, hi] (finite, lo < hi: the uniform prior);
+ *             N particles, sweeps per stage, 0 < ess < 1 (the ladder keeps ESS >= ess N); log_norm (lnL = log_norm - 0.5 chi2);
+ *             seed / stream (the Philox key); theta_fixed[n_params], the row that supplies the columns not sampled
+ *   u, lnl    [N][n] in the unit cube, [N] host: the particles, read at entry (unless opt->draw) and written back at exit;
+ *             *stage the global index of the next stage, *beta its starting inverse temperature, *scale the proposal scale -
+ *             all advanced by the call (a run cut into calls is the same run).  *beta >= 1: nothing is left to do.
+ *   n_stages  at most so many stages; the call ends after the stage that reaches beta = 1
+ *   rec, rec_lnl, rec_anc   [n_stages][VMX_SMC_REC], [n_stages][N], [n_stages][N] host: per stage beta_{t-1}, beta_t, ESS(beta_t),
+ *             accepted moves, the scale after the stage, 1 if the factor is the Cholesky factor (0: the diagonal fallback), rows
+ *             that were a particle's own position, moves rejected by a failed model; the lnL before reweighting; the ancestors.
+ *             stats->stages rows are written
+ *   opt       const_hint (-1: derived - a column varies when it is sampled), chunk (rows per engine call, 0: max_batch), lanes
+ *             (0: 2), draw (nonzero: *stage must be 0; the particles are drawn from the Philox blocks (i, 0, j, 5), evaluated, and
+ *             *beta = 0, *scale = 2.38 sqrt(3 / n)); NULL: -1, 0, 0, 0
+ *   stats     host_waits = stages + 1 (the copy back) + 1 with draw (the start: how many particles have a finite lnL)
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): n outside 1 .. 32, N outside max(2 n + 2, 8) .. 4096,
+ * ess outside (0, 1), sweeps < 1, a column out of range or repeated, a non-finite limit or lo >= hi, and without draw a particle
+ * outside the cube or with a NaN lnL, no particle with a finite lnL, beta outside [0, 1], a scale that is not positive.  A HIP
+ * failure later returns -2 and leaves the engine usable; so does a run that cannot go on (every start particle failed, or fewer
+ * than ess N particles carry weight so that beta cannot advance) - the caller's arrays are then left as they were. */
+#define VMX_SMC_MAX_PARTICLES 4096
+#define VMX_SMC_REC 8
+typedef struct {
+    int32_t n_params, n;
+    const int32_t* col; const double* lo; const double* hi;
+    int32_t N, sweeps;
+    double ess, log_norm;
+    uint64_t seed, stream;
+    const double* theta_fixed;
+} vmx_smc_spec;
+typedef struct { int32_t const_hint, chunk, lanes, draw; } vmx_smc_options;
+typedef struct {
+    int64_t stages, sweeps, rows, rows_own_position, accepted, rejected_failed_model, engine_calls, host_waits;
+    double seconds, seconds_enqueuing;
+    int32_t const_hint, lanes;          /* what the call ran with */
+} vmx_smc_stats;
+int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
+                vmx_smc_stats* stats);
 /* The table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns varies[n_params] != 0 allow - what
  * vmx_fit_migrad and vmx_ensemble_run derive when they are given const_hint = -1; a caller that evaluates such batches itself
  * sets it with vmx_set_constant_nl_hint. */

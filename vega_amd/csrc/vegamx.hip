@@ -8,6 +8,7 @@
 #include "vmx_fit.h"
 #include "vmx_ensemble.h"
 #include "vmx_nested.h"
+#include "vmx_smc.h"
 
 #include <atomic>
 #include <cmath>
@@ -419,6 +420,273 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
     if (threadIdx.x == 0) *D.host_word = total;
 }
 
+// Tempered SMC (vmx_smc_run): the particles, their proposals, the weights of a stage, the rows of a sweep and the stage record
+struct SmcWorkspace {
+    DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, theta, chi2, fixed, lo, hi, rec, rec_lnl;
+    DevBuf<int32_t> inside, status, inv, zero, rec_anc;
+    DevBuf<int64_t> counters;
+    double* pin = nullptr; double* dpin = nullptr;          // mapped host memory: beta, accepted, scale of the stage; the start's count
+    hipEvent_t ev_prop = nullptr, ev_lane = nullptr;
+    ~SmcWorkspace() {
+        if (pin) (void)hipHostFree(pin);
+        if (ev_prop) (void)hipEventDestroy(ev_prop);
+        if (ev_lane) (void)hipEventDestroy(ev_lane);
+    }
+};
+
+struct SmcDev {
+    double* u; double* lnl; double* u2; double* lnl2;               // [N][n], [N], and where the resampled copies are gathered
+    double* w; double* cum;                                         // [N] weights at beta_t, their cumulative sums
+    const int32_t* zero;                                            // [N] zeros: every particle is a "survivor" for vmx_ns::cov_entry
+    double* mean; double* cov; double* chol;                        // [n], [n][n], [n][n]
+    double* state;                                                  // [0] beta, [1] scale
+    double* prop; double* uacc; int32_t* inside;                    // the sweep's proposals [N][n], deciding uniforms [N], in the cube [N]
+    double* theta; const double* chi2; const int32_t* status;       // the engine's rows [N][P] and its answers
+    const double* fixed; const int32_t* inv; const double* lo; const double* hi;    // inv[p]: sampled index of column p, or -1
+    double* rec; double* rec_lnl; int32_t* rec_anc;                 // the call's record [stages][VMX_SMC_REC], [stages][N], [stages][N]
+    int64_t* counters;                                              // the stage's accepted, own-position rows, failed models
+    double* host;                                                   // mapped: [0] beta_t, [1] accepted, [2] scale, [3] finite start lnL
+    int32_t N, n, P, sweeps;
+    double ess, log_norm;
+    uint64_t seed, stream;
+};
+
+constexpr int SMC_THREADS = vmx_smc::LANES;
+constexpr int SMC_PER = vmx_smc::MAX_PARTICLES / SMC_THREADS;
+
+// the rows of the engine: the fixed row with the sampled columns mapped out of the cube, from the proposal where it lies inside
+// and from the particle's own position elsewhere (a lane keeps its column, the rows go round the waves)
+__device__ inline void smc_write_rows(const SmcDev& D, bool proposals)
+{
+    const int n = D.n, P = D.P;
+    for (int p = threadIdx.x % 64; p < P; p += 64) {
+        const int d = D.inv[p];
+        const double fixed = D.fixed[p], lo = d < 0 ? 0.0 : D.lo[d], hi = d < 0 ? 0.0 : D.hi[d];
+#pragma unroll 4
+        for (int r = threadIdx.x / 64; r < D.N; r += SMC_THREADS / 64) {
+            double v = fixed;
+            if (d >= 0) v = vmx_ns::map_cube(lo, hi, proposals && D.inside[r] ? D.prop[(size_t)r * n + d] : D.u[(size_t)r * n + d]);
+            D.theta[(size_t)r * P + p] = v;
+        }
+    }
+}
+
+// the start particles: u from the Philox blocks (i, 0, j, 5), beta = 0, the start scale, and their rows for the engine
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcDev D)
+{
+    for (int i = threadIdx.x; i < D.N; i += blockDim.x) vmx_smc::draw_start(i, D.n, D.seed, D.stream, D.u + (size_t)i * D.n);
+    if (threadIdx.x == 0) { D.state[0] = 0.0; D.state[1] = vmx_smc::start_scale(D.n); }
+    __syncthreads();
+    smc_write_rows(D, false);
+}
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcDev D)
+{
+    __shared__ int s_finite;
+    if (threadIdx.x == 0) s_finite = 0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < D.N; i += blockDim.x) {
+        const double v = vmx_ns::lnl_of(D.status[i], D.chi2[i], D.log_norm);
+        D.lnl[i] = v;
+        if (v > -INFINITY) atomicAdd(&s_finite, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) D.host[3] = (double)s_finite;
+}
+
+// S1 and S2 of the weights at dbeta by vmx_smc.h's stride-halving tree: lane t holds the entries t, t + 1024 .. of the padded array
+// (the tree's first levels add exactly those), the levels below 1024 run in shared memory
+__device__ inline void smc_sums(double dbeta, const double (&d)[SMC_PER], int J, int W, double* s_a, double* s_b, double& s1, double& s2)
+{
+    VMX_NO_CONTRACT
+    double a[SMC_PER], b[SMC_PER];
+#pragma unroll
+    for (int j = 0; j < SMC_PER; ++j) {
+        const double w = j < J ? vmx_smc::weight(dbeta, d[j]) : 0.0;
+        a[j] = w;
+        b[j] = vmx_smc::square(w);
+    }
+#pragma unroll
+    for (int s = SMC_PER / 2; s >= 1; s /= 2) {
+        if (s < J) {
+#pragma unroll
+            for (int j = 0; j < s; ++j) { a[j] = a[j] + a[j + s]; b[j] = b[j] + b[j + s]; }
+        }
+    }
+    __syncthreads();            // (the sums of the call before have been read)
+    s_a[threadIdx.x] = a[0];
+    s_b[threadIdx.x] = b[0];
+    __syncthreads();
+    for (int s = W / 2; s >= 1; s /= 2) {
+        if ((int)threadIdx.x < s) {
+            s_a[threadIdx.x] = s_a[threadIdx.x] + s_a[threadIdx.x + s];
+            s_b[threadIdx.x] = s_b[threadIdx.x] + s_b[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    s1 = s_a[0];
+    s2 = s_b[0];
+}
+
+// The head of stage `stage` (record row `rec` of this call) in one work-group: the next beta by bisection on the effective sample
+// size (every sum in the fixed order of vmx_smc.h), the record, the cumulative weights, the ancestors, the gather, the particles'
+// mean and covariance (one lane per entry) and the factor (one lane: n <= 32).  beta_t goes to D.state[0]; NaN: no particle has a
+// finite lnL.
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcDev D, int64_t stage, int64_t rec)
+{
+    VMX_NO_CONTRACT
+    __shared__ double s_a[SMC_THREADS], s_b[SMC_THREADS];
+    const int N = D.N, n = D.n, tid = threadIdx.x;
+    const int M = vmx_smc::pad_pow2(N), J = M > SMC_THREADS ? M / SMC_THREADS : 1, W = M < SMC_THREADS ? M : SMC_THREADS;
+    const double beta_prev = D.state[0];
+    double d[SMC_PER];
+    double top = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < SMC_PER; ++j) {
+        const int i = tid + j * SMC_THREADS;
+        d[j] = j < J && i < N ? D.lnl[i] : -INFINITY;
+        if (j < J && i < N) D.rec_lnl[(size_t)rec * N + i] = d[j];
+        top = fmax(top, d[j]);
+    }
+    s_a[tid] = top;
+    __syncthreads();
+    for (int s = SMC_THREADS / 2; s >= 1; s /= 2) {
+        if (tid < s) s_a[tid] = fmax(s_a[tid], s_a[tid + s]);
+        __syncthreads();
+    }
+    top = s_a[0];
+    if (top == -INFINITY) {
+        if (tid == 0) { D.state[0] = NAN; D.host[0] = NAN; }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < SMC_PER; ++j) d[j] = d[j] - top;       // (-inf stays -inf: weight 0, as the padding)
+
+    const double target = D.ess * (double)N;
+    double s1, s2, beta = 1.0;
+    smc_sums(1.0 - beta_prev, d, J, W, s_a, s_b, s1, s2);
+    if (!(vmx_smc::ess_of(s1, s2) >= target)) {
+        double lo = beta_prev, hi = 1.0;
+        for (int it = 0; it < vmx_smc::BISECTIONS; ++it) {
+            const double mid = vmx_smc::midpoint(lo, hi);
+            smc_sums(mid - beta_prev, d, J, W, s_a, s_b, s1, s2);
+            if (vmx_smc::ess_of(s1, s2) >= target) lo = mid; else hi = mid;
+        }
+        beta = lo;
+        smc_sums(beta - beta_prev, d, J, W, s_a, s_b, s1, s2);
+    }
+    const double dbeta = beta - beta_prev;
+#pragma unroll
+    for (int j = 0; j < SMC_PER; ++j) {
+        const int i = tid + j * SMC_THREADS;
+        if (j < J && i < N) D.w[i] = vmx_smc::weight(dbeta, d[j]);
+    }
+    if (tid == 0) {
+        double* r = D.rec + (size_t)rec * VMX_SMC_REC;
+        r[0] = beta_prev; r[1] = beta; r[2] = vmx_smc::ess_of(s1, s2);
+        D.state[0] = beta;
+        D.counters[0] = 0; D.counters[1] = 0; D.counters[2] = 0;
+    }
+    __syncthreads();
+
+    // cumulative weights: lane j sums its segment, the totals are scanned, every entry takes the scanned total before its segment
+    const int L = vmx_smc::segment_length(N);
+    s_a[tid] = vmx_smc::segment_sums(tid, D.w, s1, N, D.cum);
+    __syncthreads();
+    for (int step = 1; step < SMC_THREADS; step <<= 1) {
+        const double v = tid >= step ? s_a[tid] + s_a[tid - step] : s_a[tid];
+        __syncthreads();
+        s_a[tid] = v;
+        __syncthreads();
+    }
+    const double pre = tid > 0 ? s_a[tid - 1] : 0.0;
+    for (int i = tid * L; i < (tid + 1) * L && i < N; ++i) D.cum[i] = i == N - 1 ? 1.0 : pre + D.cum[i];
+    __syncthreads();
+
+    const double v = vmx_smc::resample_uniform(stage, D.seed, D.stream);
+    for (int i = tid; i < N; i += SMC_THREADS) {
+        const int a = vmx_smc::ancestor(D.cum, N, vmx_smc::position(v, i, N));
+        D.rec_anc[(size_t)rec * N + i] = a;
+        for (int c = 0; c < n; ++c) D.u2[(size_t)i * n + c] = D.u[(size_t)a * n + c];
+        D.lnl2[i] = D.lnl[a];
+    }
+    __syncthreads();
+    for (int q = tid; q < N * n; q += SMC_THREADS) D.u[q] = D.u2[q];
+    for (int i = tid; i < N; i += SMC_THREADS) D.lnl[i] = D.lnl2[i];
+    __syncthreads();
+
+    for (int a = tid; a < n; a += SMC_THREADS) D.mean[a] = vmx_ns::mean_entry(a, D.u, D.zero, N, 0, n);
+    __syncthreads();
+    for (int q = tid; q < n * n; q += SMC_THREADS) {
+        const int a = q / n, b = q % n;
+        if (b > a) continue;
+        const double c = vmx_ns::cov_entry(a, b, D.u, D.zero, D.mean, N, 0, n);
+        D.cov[a * n + b] = c;
+        D.cov[b * n + a] = c;
+    }
+    __syncthreads();
+    if (tid == 0) D.rec[(size_t)rec * VMX_SMC_REC + 5] = vmx_ns::whiten(n, D.cov, D.chol) ? 1.0 : 0.0;
+}
+
+// One sweep boundary in one work-group (the acceptance count steers the scale of every particle's next proposal): decide sweep
+// s_dec of the stage from chi2 / status of each particle's row (s_dec < 0: none), adapt the scale, then propose sweep s_prop
+// (s_prop < 0: none - the stage is over: its counts go to the record and beta, acceptance and scale to the host's words) and
+// write the N rows of the engine.  Every expression: vmx_smc.h.
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stage, int s_dec, int s_prop, int64_t rec)
+{
+    __shared__ int s_cnt[3];
+    __shared__ double s_C[vmx_smc::MAXN * vmx_smc::MAXN];
+    __shared__ double s_scale;
+    const int N = D.N, n = D.n, tid = threadIdx.x;
+    if (isnan(D.state[0])) return;          // (no particle had a finite lnL: the host ends the run)
+    if (s_dec >= 0) {
+        if (tid < 3) s_cnt[tid] = 0;
+        __syncthreads();
+        const double beta = D.state[0];
+        int acc = 0, own = 0, failed = 0;
+        for (int i = tid; i < N; i += SMC_THREADS) {
+            const double c2 = D.chi2[i];
+            const bool inside = D.inside[i] != 0, ok = vmx_ens::model_ok(D.status[i], c2);
+            const double lnl_new = vmx_ns::lnl_of(D.status[i], c2, D.log_norm);
+            if (vmx_smc::accept(inside, ok, beta, lnl_new, D.lnl[i], D.uacc[i])) {
+                for (int c = 0; c < n; ++c) D.u[(size_t)i * n + c] = D.prop[(size_t)i * n + c];
+                D.lnl[i] = lnl_new;
+                acc += 1;
+            } else if (!inside) own += 1;
+            else if (!ok) failed += 1;
+        }
+        if (acc) atomicAdd(&s_cnt[0], acc);
+        if (own) atomicAdd(&s_cnt[1], own);
+        if (failed) atomicAdd(&s_cnt[2], failed);
+        __syncthreads();
+        if (tid == 0) {
+            const double scale = vmx_smc::adapt(D.state[1], s_cnt[0], N);
+            D.state[1] = scale;
+            for (int q = 0; q < 3; ++q) D.counters[q] += s_cnt[q];
+            if (s_prop < 0) {
+                double* r = D.rec + (size_t)rec * VMX_SMC_REC;
+                r[3] = (double)D.counters[0]; r[4] = scale; r[6] = (double)D.counters[1]; r[7] = (double)D.counters[2];
+                D.host[1] = r[3]; D.host[2] = scale; D.host[0] = beta;
+            }
+        }
+    }
+    if (s_prop < 0) return;
+    __syncthreads();
+    for (int q = tid; q < n * n; q += SMC_THREADS) s_C[q] = D.chol[q];
+    if (tid == 0) s_scale = D.state[1];
+    __syncthreads();
+    const double scale = s_scale;
+    for (int i = tid; i < N; i += SMC_THREADS) {
+        double ua = 0.0;
+        const bool in = vmx_smc::propose(i, stage, s_prop, n, s_C, scale, D.u + (size_t)i * n, D.seed, D.stream,
+                                         D.prop + (size_t)i * n, ua);
+        D.uacc[i] = ua;
+        D.inside[i] = in ? 1 : 0;
+    }
+    __syncthreads();
+    smc_write_rows(D, true);
+}
+
 }  // namespace
 
 struct vmx_engine {
@@ -440,6 +708,7 @@ struct vmx_engine {
     FitWorkspace* fitws = nullptr;
     EnsWorkspace* ensws = nullptr;
     NsWorkspace* nsws = nullptr;
+    SmcWorkspace* smcws = nullptr;
     hipEvent_t lane_wait = nullptr;         // vmx_ensemble_run: the rows of the second lane's calls are complete at this event
 
     int nk = 0, nkp = 0, n_mu = 0;
@@ -597,6 +866,7 @@ struct vmx_engine {
         delete fitws;
         delete ensws;
         delete nsws;
+        delete smcws;
         if (pin_theta) (void)hipHostFree(pin_theta);
         if (pin_chi2) (void)hipHostFree(pin_chi2);
         if (pin_status) (void)hipHostFree(pin_status);
@@ -953,6 +1223,9 @@ int vmx_struct_size(int32_t which)
         case 11: return (int)sizeof(vmx_nested_spec);
         case 12: return (int)sizeof(vmx_nested_options);
         case 13: return (int)sizeof(vmx_nested_stats);
+        case 14: return (int)sizeof(vmx_smc_spec);
+        case 15: return (int)sizeof(vmx_smc_options);
+        case 16: return (int)sizeof(vmx_smc_stats);
         default: return -1;
     }
 }
@@ -3298,7 +3571,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
-    L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
+    L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
     L->graphs.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
     L->pin_theta = nullptr; L->pin_chi2 = nullptr; L->pin_status = nullptr; L->pin_done = nullptr; L->pin_part = nullptr;
@@ -4034,6 +4307,199 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
     *iteration += done;
     R.iterations = done;
     R.rows_own_position = own;
+    R.seconds_enqueuing = enqueue_s;
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// ---- evidence where the particles live (vmx_smc.h)
+static_assert(VMX_SMC_MAX_PARTICLES == vmx_smc::MAX_PARTICLES && VMX_NS_MAXN == vmx_smc::MAXN, "SMC limits");
+
+int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
+                vmx_smc_stats* stats)
+{
+    REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale, "vmx_smc_run");
+    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
+            "vmx_smc_run: parameter columns, limits and the fixed row");
+    const int n = spec->n, P = e->n_params, N = spec->N, sweeps = spec->sweeps;
+    REQUIRE(n >= 1 && n <= VMX_NS_MAXN, "vmx_smc_run: 1 .. 32 sampled columns");
+    REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, "vmx_smc_run: max(2 n + 2, 8) .. 4096 particles");
+    REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, "vmx_smc_run: 0 < ess < 1");
+    REQUIRE(sweeps >= 1, "vmx_smc_run: sweeps >= 1");
+    std::vector<char> varies(P, 0);
+    std::vector<int32_t> inv(P, -1);
+    for (int i = 0; i < n; ++i) {
+        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_smc_run: parameter column");
+        REQUIRE(!varies[spec->col[i]], "vmx_smc_run: a column is listed twice");
+        varies[spec->col[i]] = 1;
+        inv[spec->col[i]] = i;
+        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_smc_run: limits");
+    }
+    REQUIRE(std::isfinite(spec->log_norm), "vmx_smc_run: log_norm");
+    REQUIRE(n_stages >= 0 && *stage >= 0 && *stage < ((int64_t)1 << 31), "vmx_smc_run: n_stages >= 0, 0 <= stage < 2^31");
+    REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), "vmx_smc_run: the stage record");
+    const bool draw = opt && opt->draw != 0;
+    REQUIRE(!draw || *stage == 0, "vmx_smc_run: particles are drawn at stage 0");
+    if (!draw) {
+        REQUIRE(*beta >= 0.0 && *beta <= 1.0, "vmx_smc_run: beta in [0, 1]");
+        REQUIRE(*scale > 0.0 && std::isfinite(*scale), "vmx_smc_run: a positive scale");
+        bool any = false;
+        for (int i = 0; i < N; ++i) {
+            REQUIRE(!std::isnan(lnl[i]), "vmx_smc_run: a particle has a NaN lnL");
+            any = any || lnl[i] > -INFINITY;
+            for (int d = 0; d < n; ++d) {
+                const double v = u[(size_t)i * n + d];
+                REQUIRE(v >= 0.0 && v <= 1.0, "vmx_smc_run: a particle lies outside the unit cube");
+            }
+        }
+        REQUIRE(any, "vmx_smc_run: no particle has a finite lnL");
+    }
+    int hint = opt ? opt->const_hint : -1;
+    REQUIRE(hint >= -1 && hint <= 2, "vmx_smc_run: const_hint -1 (derive it), 0, 1 or 2");
+    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_smc_run: chunk, lanes");
+    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
+    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
+    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    const size_t rec_rows = (size_t)std::max(n_stages, 1);
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->smcws) e->smcws = new SmcWorkspace();
+    SmcWorkspace& S = *e->smcws;
+    if (ensure(S.u, (size_t)N * n) || ensure(S.lnl, N) || ensure(S.u2, (size_t)N * n) || ensure(S.lnl2, N) || ensure(S.w, N) ||
+        ensure(S.cum, N) || ensure(S.zero, N) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) ||
+        ensure(S.state, 2) || ensure(S.prop, (size_t)N * n) || ensure(S.uacc, N) || ensure(S.inside, N) || ensure(S.theta, (size_t)N * P) ||
+        ensure(S.chi2, N) || ensure(S.status, N) || ensure(S.fixed, P) || ensure(S.inv, P) || ensure(S.lo, n) || ensure(S.hi, n) ||
+        ensure(S.rec, rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * N) || ensure(S.rec_anc, rec_rows * N) ||
+        ensure(S.counters, 3))
+        return -2;
+    if (!S.pin) {
+        HIP_OK(hipHostMalloc((void**)&S.pin, 4 * sizeof(double), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin, S.pin, 0));
+        HIP_OK(hipEventCreateWithFlags(&S.ev_prop, hipEventDisableTiming));
+        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
+    }
+    hipStream_t st = e->stream;
+    const double state0[2] = {*beta, *scale};
+    if (!draw) {
+        HIP_OK(hipMemcpyAsync(S.u.p, u, (size_t)N * n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.lnl.p, lnl, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.state.p, state0, sizeof state0, hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemsetAsync(S.zero.p, 0, (size_t)N * sizeof(int32_t), st));
+    HIP_OK(hipMemsetAsync(S.counters.p, 0, 3 * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.rec.p, 0, rec_rows * VMX_SMC_REC * sizeof(double), st));
+    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.inv.p, inv.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+
+    SmcDev D{};
+    D.u = S.u.p; D.lnl = S.lnl.p; D.u2 = S.u2.p; D.lnl2 = S.lnl2.p; D.w = S.w.p; D.cum = S.cum.p; D.zero = S.zero.p;
+    D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.state = S.state.p;
+    D.prop = S.prop.p; D.uacc = S.uacc.p; D.inside = S.inside.p;
+    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
+    D.fixed = S.fixed.p; D.inv = S.inv.p; D.lo = S.lo.p; D.hi = S.hi.p;
+    D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.dpin;
+    D.N = N; D.n = n; D.P = P; D.sweeps = sweeps; D.ess = spec->ess; D.log_norm = spec->log_norm;
+    D.seed = spec->seed; D.stream = spec->stream;
+
+    // the engine as the sampler's likelihood: chi2-only device evaluations of the sweep's rows, eager launches, two lanes when the
+    // quadratic form serves them; the table level the sampled columns allow.  The second lane's stream waits for the rows at
+    // lane_wait, the next decision waits for the lane.
+    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
+    const bool saved_ring = e->ring_allowed;
+    e->const_hint = hint;
+    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
+    e->lane_calls = 0;
+    struct Restore {
+        vmx_engine* e; int hint, lanes; bool ring;
+        ~Restore() { wait_lane(e); e->lane_wait = nullptr; e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
+    } restore{e, saved_hint, saved_lanes, saved_ring};
+
+    vmx_smc_stats R{};
+    R.const_hint = hint;
+    R.lanes = e->n_lanes;
+    double enqueue_s = 0.0;
+    // the engine's chain over the N rows just written; the stream then waits for the second lane
+    auto evaluate = [&]() -> int {
+        HIP_OK(hipEventRecord(S.ev_prop, st));
+        e->lane_wait = S.ev_prop;
+        hipStream_t lane_stream = nullptr;
+        for (int off = 0; off < N; off += chunk) {
+            const int B = std::min(chunk, N - off);
+            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
+            if (e->last_stream != st) lane_stream = e->last_stream;
+            R.engine_calls += 1;
+        }
+        if (lane_stream) {      // (the next kernel reads every chunk's chi2)
+            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
+            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
+        }
+        R.rows += N;
+        return 0;
+    };
+    double b_now = *beta, scale_now = *scale;
+    if (draw) {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_smc_start, dim3(1), dim3(SMC_THREADS), 0, st, D);
+        HIP_OK(hipGetLastError());
+        if (evaluate()) return -2;
+        hipLaunchKernelGGL(k_smc_start_lnl, dim3(1), dim3(SMC_THREADS), 0, st, D);
+        HIP_OK(hipGetLastError());
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the start's wait: how many particles have a finite lnL)
+        R.host_waits += 1;
+        if (!(S.pin[3] > 0.0)) return fail(-2, "vmx_smc_run: no start particle has a finite lnL");
+        b_now = 0.0;
+        scale_now = vmx_smc::start_scale(n);
+    }
+    int done = 0;
+    while (done < n_stages && b_now < 1.0) {
+        const int64_t t = *stage + done;
+        const auto t0 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_smc_stage, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)done);
+        hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, -1, 0, (int64_t)done);
+        HIP_OK(hipGetLastError());
+        for (int s = 0; s < sweeps; ++s) {
+            if (evaluate()) return -2;
+            hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, s, s + 1 < sweeps ? s + 1 : -1, (int64_t)done);
+            HIP_OK(hipGetLastError());
+        }
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the stage's only wait: beta, acceptance and scale, three mapped words)
+        R.host_waits += 1;
+        const double b = S.pin[0];
+        if (std::isnan(b)) return fail(-2, "vmx_smc_run: no particle has a finite lnL");
+        if (!(b > b_now)) return fail(-2, "vmx_smc_run: the temperature ladder cannot advance: fewer than ess N particles carry weight");
+        b_now = b;
+        scale_now = S.pin[2];
+        R.accepted += (int64_t)S.pin[1];
+        done += 1;
+    }
+    e->lane_wait = nullptr;
+    std::vector<double> rec_host((size_t)std::max(done, 1) * VMX_SMC_REC);
+    HIP_OK(hipMemcpyAsync(u, S.u.p, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(lnl, S.lnl.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (done > 0) {
+        HIP_OK(hipMemcpyAsync(rec_host.data(), S.rec.p, (size_t)done * VMX_SMC_REC * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(rec_lnl, S.rec_lnl.p, (size_t)done * N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(rec_anc, S.rec_anc.p, (size_t)done * N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    R.host_waits += 1;
+    for (int k = 0; k < done; ++k) {
+        R.rows_own_position += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 6];
+        R.rejected_failed_model += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 7];
+    }
+    if (done > 0) std::memcpy(rec, rec_host.data(), (size_t)done * VMX_SMC_REC * sizeof(double));
+    *stage += done;
+    *beta = b_now;
+    *scale = scale_now;
+    R.stages = done;
+    R.sweeps = (int64_t)done * sweeps;
     R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;

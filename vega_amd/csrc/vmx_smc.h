@@ -1,0 +1,307 @@
+// Tempered sequential Monte Carlo (the scheme of pocoMC without its normalising flow), pinned decision for decision.
+//
+// N particles walk from the prior (beta = 0) to the posterior (beta = 1) along a ladder of inverse temperatures chosen by the
+// effective sample size; every stage reweights, resamples, whitens and moves all particles by `sweeps` Metropolis sweeps under
+// L^beta.  The loop runs where the particles are (vmx_smc_run, vegamx.hip: k_smc_stage once per stage, k_smc_move once per
+// sweep); vega_amd/smc.py restates every expression below in NumPy (the `python` driver) and tests/helpers/smc_driver.cpp compiles
+// this header with g++ so that tests/test_smc_host.py can hold the two against each other bit for bit.  No HIP type, no heap.
+//
+//   cube             particles live in u in [0, 1]^n (vmx_ns::map_cube: a uniform prior over the limits); lnL = log_norm - 0.5 chi2,
+//                    -inf for a failed model (vmx_ns::lnl_of).  Target of stage t: L^beta_t inside the cube.
+//   random numbers   vmx_ens::philox4x64_10 keyed (seed, stream), a uniform double from a word by vmx_ens::u01.  Counters (word 0
+//                    first):  start particle i      (i, 0, j, 5)                    coordinate c: word c % 4 of block j = c / 4
+//                             resampling of stage t (0, t, 0, 4)                    word 0 is v
+//                             particle i, stage t, sweep s  (i, t 2^32 + s, j, 3)   words q = 0 .. n from blocks j = q / 4, word q % 4:
+//                                                                                   g_q = 2 u - 1 for q < n, word n decides
+//                    A particle's stream depends on nothing but (i, t, s).  Stages count from 0 over the whole run.
+//   exp              pexp below: range reduction by k = floor(x / ln 2 + 1/2) with a two-word ln 2, a degree-13 Horner polynomial
+//                    in the remainder, a power of two - separately rounded operations only, so that NumPy restates it bit for
+//                    bit.  Nothing that decides calls the C library.
+//   a stage t        given beta_{t-1} and lnL_i:
+//     weights        d_i = lnL_i - max_j lnL_j;  w_i(beta) = pexp((beta - beta_{t-1}) d_i), 0 where lnL_i = -inf.
+//     sums           S1 = sum w_i and S2 = sum w_i^2 by the stride-halving tree over the array padded with zeros to M, the power
+//                    of two >= N: for s = M/2, M/4 .. 1: a_i = a_i + a_{i+s} (i < s); the sum is a_0.  ESS = S1 S1 / S2.
+//     next beta      1 if ESS(1) >= ess N; otherwise [lo, hi] = [beta_{t-1}, 1] halved BISECTIONS times at mid = 0.5 (lo + hi),
+//                    lo = mid where ESS(mid) >= ess N, hi = mid elsewhere; beta_t = lo.  No finite lnL at all, or beta_t =
+//                    beta_{t-1} (fewer than ess N particles carry weight): the run ends with an error.
+//     cumulative     q_i = w_i(beta_t) / S1.  Segments of L = ceil(N / LANES) consecutive particles, LANES of them (the last ones
+//                    empty): r_i the running sum inside the segment from 0.0, T_j its total; the T_j scanned inclusively in
+//                    log2 LANES rounds (step = 1, 2, 4 ..: T_j = T_j + T_{j-step} for j >= step, from the values of the round
+//                    before); c_i = P_j + r_i with P_j the scanned total of segment j - 1 (0.0 for j = 0); c_{N-1} = 1.
+//     resample       position p_i = (v + i) / N; ancestor a_i by the bisection  lo = 0, hi = N - 1; while lo < hi: mid =
+//                    (lo + hi) / 2; c_mid > p_i ? hi = mid : lo = mid + 1.  Particle i becomes a copy of particle a_i.
+//     precondition   mean, covariance and factor C of the resampled particles: vmx_ns::mean_entry / cov_entry over all of them
+//                    (K = 0), vmx_ns::whiten with its diagonal fallback.
+//     sweeps         s = 0 .. sweeps - 1: z_a = sum_{j <= a} C_aj g_j (in that order), y_a = u_a + scale z_a.  Outside the cube:
+//                    rejected without an evaluation (the engine's row is the particle's own position).  Inside: accepted iff the
+//                    model is ok and (D = beta_t (lnL_y - lnL_u) >= 0 or u01(word n) < pexp(D)).  After the sweep, with a =
+//                    accepted / N: scale = 0.8 scale if a < 0.15, 1.25 scale if a > 0.35.
+//   start            beta = 0, scale = 2.38 sqrt(3 / n); the scale carries over from stage to stage.  After the sweeps of the stage
+//                    with beta_t = 1 the particles are the posterior sample, weight 1 / N each.
+//
+// Every expression is the separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are
+// correctly rounded.  The evidence is computed from the stage record by host Python (vega_amd/smc.py: evidence).
+#pragma once
+#include <cstring>
+
+#include "vmx_nested.h"
+
+namespace vmx_smc {
+
+constexpr int MAXN = vmx_ns::MAXN;
+constexpr int MAX_PARTICLES = 4096;
+constexpr int BISECTIONS = 60;
+constexpr int LANES = 1024;                 // segments of the cumulative sum: the lanes of the work-group that computes it
+constexpr uint64_t DOMAIN_MOVE = 3, DOMAIN_RESAMPLE = 4, DOMAIN_START = 5;
+
+// ---- exp
+constexpr double INV_LN2 = 1.44269504088896338700e+00;
+constexpr double LN2_HI = 6.93147180369123816490e-01;      // (the upper 32 bits of ln 2: k LN2_HI is exact for |k| < 2^20)
+constexpr double LN2_LO = 1.90821492927058770002e-10;
+
+VMX_HD inline double pow2(int k)            // 2^k, -1022 <= k <= 1023
+{
+    const uint64_t b = (uint64_t)(k + 1023) << 52;
+    double d;
+    memcpy(&d, &b, sizeof d);
+    return d;
+}
+
+VMX_HD inline double horner(double p, double r, double c)
+{
+    VMX_NO_CONTRACT
+    const double m = p * r;
+    return m + c;
+}
+
+VMX_HD inline double pexp(double x)
+{
+    VMX_NO_CONTRACT
+    if (x != x) return x;
+    if (x > 709.0) return INFINITY;         // (no caller asks for a positive argument)
+    if (x < -745.2) return 0.0;
+    const double s = x * INV_LN2;
+    const double kf = floor(s + 0.5);
+    const double h = kf * LN2_HI;
+    double r = x - h;
+    const double l = kf * LN2_LO;
+    r = r - l;
+    double p = 1.0 / 6227020800.0;
+    p = horner(p, r, 1.0 / 479001600.0);
+    p = horner(p, r, 1.0 / 39916800.0);
+    p = horner(p, r, 1.0 / 3628800.0);
+    p = horner(p, r, 1.0 / 362880.0);
+    p = horner(p, r, 1.0 / 40320.0);
+    p = horner(p, r, 1.0 / 5040.0);
+    p = horner(p, r, 1.0 / 720.0);
+    p = horner(p, r, 1.0 / 120.0);
+    p = horner(p, r, 1.0 / 24.0);
+    p = horner(p, r, 1.0 / 6.0);
+    p = horner(p, r, 0.5);
+    p = horner(p, r, 1.0);
+    p = horner(p, r, 1.0);
+    const int k = (int)kf;
+    if (k >= -1022) return p * pow2(k);
+    const double q = p * pow2(k + 1000);    // (exact; the product below rounds once, into the subnormals)
+    return q * 0x1.0p-1000;
+}
+
+// ---- random numbers
+VMX_HD inline vmx_ens::Block move_block(int64_t i, int64_t stage, int64_t sweep, int64_t j, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::philox4x64_10((uint64_t)i, ((uint64_t)stage << 32) + (uint64_t)sweep, (uint64_t)j, DOMAIN_MOVE, seed, stream);
+}
+
+VMX_HD inline double resample_uniform(int64_t stage, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::u01(vmx_ens::philox4x64_10(0, (uint64_t)stage, 0, DOMAIN_RESAMPLE, seed, stream).w[0]);
+}
+
+// start particle i: u[n]
+VMX_HD inline void draw_start(int64_t i, int n, uint64_t seed, uint64_t stream, double* u)
+{
+    for (int c = 0; c < n; c += 4) {
+        const vmx_ens::Block b = vmx_ens::philox4x64_10((uint64_t)i, 0, (uint64_t)(c / 4), DOMAIN_START, seed, stream);
+        for (int q = 0; q < 4 && c + q < n; ++q) u[c + q] = vmx_ens::u01(b.w[q]);
+    }
+}
+
+VMX_HD inline double start_scale(int n)
+{
+    VMX_NO_CONTRACT
+    const double t = 3.0 / (double)n;
+    return 2.38 * sqrt(t);
+}
+
+// ---- weights and their sums
+VMX_HD inline int pad_pow2(int N) { int M = 1; while (M < N) M <<= 1; return M; }
+
+VMX_HD inline double weight(double dbeta, double d)
+{
+    VMX_NO_CONTRACT
+    if (d == -INFINITY) return 0.0;
+    return pexp(dbeta * d);
+}
+
+VMX_HD inline double square(double w) { VMX_NO_CONTRACT return w * w; }
+
+VMX_HD inline double ess_of(double s1, double s2)
+{
+    VMX_NO_CONTRACT
+    const double t = s1 * s1;
+    return t / s2;
+}
+
+VMX_HD inline double midpoint(double lo, double hi)
+{
+    VMX_NO_CONTRACT
+    const double s = lo + hi;
+    return 0.5 * s;
+}
+
+// the stride-halving tree over a[M] (destroyed), M a power of two
+inline double tree_sum(double* a, int M)
+{
+    VMX_NO_CONTRACT
+    for (int s = M / 2; s >= 1; s /= 2)
+        for (int i = 0; i < s; ++i) a[i] = a[i] + a[i + s];
+    return a[0];
+}
+
+// S1, S2 of the weights at beta_prev + dbeta; d[N], scratch[2 M]
+inline void weight_sums(double dbeta, const double* d, int N, double* scratch, double& s1, double& s2)
+{
+    const int M = pad_pow2(N);
+    double* a = scratch;
+    double* b = scratch + M;
+    for (int i = 0; i < M; ++i) {
+        const double w = i < N ? weight(dbeta, d[i]) : 0.0;
+        a[i] = w;
+        b[i] = square(w);
+    }
+    s1 = tree_sum(a, M);
+    s2 = tree_sum(b, M);
+}
+
+// beta_t from beta_{t-1}; ess_out = ESS(beta_t), s1_out = S1(beta_t).  NaN: no particle has a finite lnL (d is then unusable).
+inline double next_beta(double beta_prev, const double* d, int N, double target, double* scratch, double& ess_out, double& s1_out)
+{
+    VMX_NO_CONTRACT
+    double s1, s2;
+    double beta = 1.0;
+    weight_sums(1.0 - beta_prev, d, N, scratch, s1, s2);
+    if (!(ess_of(s1, s2) >= target)) {
+        double lo = beta_prev, hi = 1.0;
+        for (int it = 0; it < BISECTIONS; ++it) {
+            const double mid = midpoint(lo, hi);
+            weight_sums(mid - beta_prev, d, N, scratch, s1, s2);
+            if (ess_of(s1, s2) >= target) lo = mid; else hi = mid;
+        }
+        beta = lo;
+        weight_sums(beta - beta_prev, d, N, scratch, s1, s2);
+    }
+    ess_out = ess_of(s1, s2);
+    s1_out = s1;
+    return beta;
+}
+
+// ---- cumulative weights and ancestors
+VMX_HD inline int segment_length(int N) { return (N + LANES - 1) / LANES; }
+
+// running sum of segment j: c[i] = r_i for its particles, returns the total
+VMX_HD inline double segment_sums(int j, const double* w, double s1, int N, double* c)
+{
+    VMX_NO_CONTRACT
+    const int L = segment_length(N);
+    double r = 0.0;
+    for (int i = j * L; i < (j + 1) * L && i < N; ++i) {
+        const double q = w[i] / s1;
+        r = r + q;
+        c[i] = r;
+    }
+    return r;
+}
+
+// c[N] from w[N]; totals[2 LANES] scratch
+inline void cumulative(const double* w, double s1, int N, double* totals, double* c)
+{
+    VMX_NO_CONTRACT
+    double* t = totals;
+    double* t2 = totals + LANES;
+    for (int j = 0; j < LANES; ++j) t[j] = segment_sums(j, w, s1, N, c);
+    for (int step = 1; step < LANES; step <<= 1) {
+        for (int j = 0; j < LANES; ++j) t2[j] = j >= step ? t[j] + t[j - step] : t[j];
+        for (int j = 0; j < LANES; ++j) t[j] = t2[j];
+    }
+    const int L = segment_length(N);
+    for (int i = 0; i < N; ++i) {
+        const int j = i / L;
+        const double pre = j > 0 ? t[j - 1] : 0.0;
+        c[i] = pre + c[i];
+    }
+    c[N - 1] = 1.0;
+}
+
+VMX_HD inline double position(double v, int i, int N)
+{
+    VMX_NO_CONTRACT
+    const double s = v + (double)i;
+    return s / (double)N;
+}
+
+VMX_HD inline int ancestor(const double* c, int N, double p)
+{
+    int lo = 0, hi = N - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (c[mid] > p) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+// ---- a sweep
+// the proposal of particle i at (stage, sweep) from u[n] into y[n] (no overlap); ua: the uniform that decides.  true: y in the cube
+VMX_HD inline bool propose(int64_t i, int64_t stage, int64_t sweep, int n, const double* C, double scale, const double* u,
+                           uint64_t seed, uint64_t stream, double* y, double& ua)
+{
+    VMX_NO_CONTRACT
+    for (int q = 0; q <= n; q += 4) {       // (y holds g first)
+        const vmx_ens::Block b = move_block(i, stage, sweep, q / 4, seed, stream);
+        for (int w = 0; w < 4 && q + w <= n; ++w) {
+            const double x = vmx_ens::u01(b.w[w]);
+            if (q + w < n) { const double two = 2.0 * x; y[q + w] = two - 1.0; }
+            else ua = x;
+        }
+    }
+    bool in = true;
+    for (int a = n - 1; a >= 0; --a) {      // (z_a reads g_0 .. g_a: from the last row up, each slot is free when it is written)
+        double acc = 0.0;
+        for (int j = 0; j <= a; ++j) { const double p = C[a * n + j] * y[j]; acc = acc + p; }
+        const double step = scale * acc;
+        const double v = u[a] + step;
+        y[a] = v;
+        in = in && v >= 0.0 && v <= 1.0;
+    }
+    return in;
+}
+
+VMX_HD inline bool accept(bool inside, bool ok, double beta, double lnl_new, double lnl_old, double ua)
+{
+    VMX_NO_CONTRACT
+    if (!inside || !ok) return false;
+    const double dl = lnl_new - lnl_old;
+    const double delta = beta * dl;
+    if (delta >= 0.0) return true;
+    return ua < pexp(delta);
+}
+
+VMX_HD inline double adapt(double scale, int64_t accepted, int N)
+{
+    VMX_NO_CONTRACT
+    const double a = (double)accepted / (double)N;
+    if (a < 0.15) return scale * 0.8;
+    if (a > 0.35) return scale * 1.25;
+    return scale;
+}
+
+}  // namespace vmx_smc

@@ -158,6 +158,27 @@ class NestedStats(C.Structure):
                 ('const_hint', C.c_int32), ('lanes', C.c_int32)]
 
 
+VMX_SMC_MAX_PARTICLES = 4096
+VMX_SMC_REC = 8
+
+
+class SmcSpec(C.Structure):
+    _fields_ = [('n_params', C.c_int32), ('n', C.c_int32), ('col', C.POINTER(C.c_int32)), ('lo', C.POINTER(C.c_double)),
+                ('hi', C.POINTER(C.c_double)), ('N', C.c_int32), ('sweeps', C.c_int32), ('ess', C.c_double),
+                ('log_norm', C.c_double), ('seed', C.c_uint64), ('stream', C.c_uint64), ('theta_fixed', C.POINTER(C.c_double))]
+
+
+class SmcOptions(C.Structure):
+    _fields_ = [('const_hint', C.c_int32), ('chunk', C.c_int32), ('lanes', C.c_int32), ('draw', C.c_int32)]
+
+
+class SmcStats(C.Structure):
+    _fields_ = [('stages', C.c_int64), ('sweeps', C.c_int64), ('rows', C.c_int64), ('rows_own_position', C.c_int64),
+                ('accepted', C.c_int64), ('rejected_failed_model', C.c_int64), ('engine_calls', C.c_int64),
+                ('host_waits', C.c_int64), ('seconds', C.c_double), ('seconds_enqueuing', C.c_double), ('const_hint', C.c_int32),
+                ('lanes', C.c_int32)]
+
+
 FIT_BATCH_BINS = ('1', '2..4', '5..16', '17..64', '65..256', '257..1024', '1025..4096', '4097..')
 
 
@@ -232,6 +253,8 @@ def load_library():
                                      C.c_int32, C.c_int32, dptr, dptr, C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
+    lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
+                                iptr, C.POINTER(SmcOptions), C.POINTER(SmcStats)]
     lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
     lib.vmx_set_constant_nl_hint.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_direct_pk.argtypes = [C.c_void_p, dptr, C.c_int32, C.c_int32]
@@ -265,7 +288,8 @@ def load_library():
     lib.vmx_get_timings.argtypes = [C.c_void_p, dptr, C.POINTER(C.c_int64), C.c_int32]
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
-                                    EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats)):
+                                    EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
+                                    SmcSpec, SmcOptions, SmcStats)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -278,7 +302,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1069,6 +1093,35 @@ class Engine:
             raise raised[0]
         m = int(stats.iterations) * K
         return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), {name: getattr(stats, name) for name, _ in NestedStats._fields_}
+
+    def smc_run(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, n_stages, ess, sweeps, log_norm=0.0, seed=0, stream=0,
+                const_hint=-1, chunk=0, lanes=0, draw=False):
+        """Up to ``n_stages`` stages of the tempered SMC sampler on the device (include/vegamx.h: vmx_smc_run): ``cols`` the sampled
+        parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``u`` [N, n] in the unit cube / ``lnl``
+        [N] the particles (updated in place; drawn first with ``draw``), ``stage`` the global index of the next stage, ``beta`` and
+        ``scale`` its inverse temperature and proposal scale.  Returns (record: one dict per stage done with beta_prev, beta, ess,
+        lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale afterwards; statistics)."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
+        for arr in (u, lnl):
+            if not (isinstance(arr, np.ndarray) and arr.dtype == np.float64 and arr.flags.c_contiguous):
+                raise ValueError('u, lnl: C-contiguous float64 arrays (updated in place)')
+        N, n_stages = u.shape[0], max(0, int(n_stages))
+        if u.shape != (N, cols.size) or lnl.shape != (N,) or theta_fixed.shape != (self.n_params,):
+            raise ValueError('u [N, n], lnl [N], theta_fixed [n_params]')
+        rec, rec_lnl = np.zeros((n_stages, VMX_SMC_REC)), np.empty((n_stages, N))
+        rec_anc = np.empty((n_stages, N), dtype=np.int32)
+        spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
+                       int(stream), _dp(theta_fixed))
+        opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
+        stats = SmcStats()
+        st, b, sc = C.c_int64(int(stage)), C.c_double(float(beta)), C.c_double(float(scale))
+        self._check(self.lib.vmx_smc_run(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc), n_stages,
+                                         _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(opt), C.byref(stats)))
+        record = [dict(beta_prev=float(rec[k, 0]), beta=float(rec[k, 1]), ess=float(rec[k, 2]), lnl=rec_lnl[k].copy(),
+                       anc=rec_anc[k].copy(), accepted=int(rec[k, 3]), scale=float(rec[k, 4]), cholesky=bool(rec[k, 5]))
+                  for k in range(int(stats.stages))]
+        return record, int(st.value), float(b.value), float(sc.value), {name: getattr(stats, name) for name, _ in SmcStats._fields_}
 
     def derived_const_hint(self, cols):
         """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:

@@ -464,7 +464,8 @@ def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
     parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver}; with ``sampler = Nested`` the
-    ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`)."""
+    ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones
+    (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
     run = control.getboolean('run_sampler', False) if hasattr(control, 'getboolean') else False
     if not run:
@@ -477,6 +478,9 @@ def sampler_settings(main_config, sample_params):
     if sampler == 'Nested':
         from .nested import nested_settings
         return nested_settings(main_config, sample_params)
+    if sampler == 'SMC':
+        from .smc import smc_settings
+        return smc_settings(main_config, sample_params)
     if sampler != 'Ensemble':
         raise ValueError('Sampler not recognized. Please use Nested or Ensemble.')
     if 'Ensemble' not in main_config:
@@ -516,8 +520,9 @@ def sampler_settings(main_config, sample_params):
 
 def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwargs):
     """bin/run_vega_mpi.py for one process: initialise, compute the model once, switch to the Monte-Carlo mock when asked,
-    require ``run_sampler = True`` and ``sampler = Ensemble`` or ``Nested``, run the ``[Ensemble]`` / ``[Nested]`` settings, write
-    the getdist chain (a nested run also ``name.stats`` with the evidence).  Returns the sampler."""
+    require ``run_sampler = True`` and ``sampler = Ensemble``, ``Nested`` or ``SMC``, run the ``[Ensemble]`` / ``[Nested]`` /
+    ``[SMC]`` settings, write the getdist chain (a nested or SMC run also ``name.stats`` with the evidence).  Returns the
+    sampler."""
     from .interface import VegaInterface
     print_func('Initializing Vega')
     vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
@@ -538,6 +543,14 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwarg
         sampler = NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
                                 precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
                                 max_iterations=cfg['max_iterations'], sample_params=sample_params)
+        sampler.run()
+        log_z, err = sampler.log_evidence()
+        print_func(f'log(Z) = {log_z} +- {err}')
+    elif cfg['sampler'] == 'SMC':
+        from .smc import SMCSampler
+        print_func('Running the SMC sampler')
+        sampler = SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],
+                             driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params)
         sampler.run()
         log_z, err = sampler.log_evidence()
         print_func(f'log(Z) = {log_z} +- {err}')

@@ -11,7 +11,7 @@ vega_amd/csrc/vmx_nested.h decision for decision, so that they produce the same 
 and termination are computed here, on the host, from the dead record - one code for both drivers.
 
 What is not here: clustering of separated modes (whitening uses one covariance), ``boost_posterior``, resume files, the
-marginalised coefficients as derived parameters, pocoMC.
+marginalised coefficients as derived parameters.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
 """
 import math
 import time

@@ -1,0 +1,557 @@
+"""Evidence and an equal-weight posterior by tempered sequential Monte Carlo (the scheme of pocoMC, without its normalising flow),
+run where the particles are.
+
+The reference's second sampler is pocoMC (bin/run_vega_mpi.py: ``[control] run_sampler = True``, ``sampler = PocoMC``).  Here N
+particles start from the prior and walk a ladder of inverse temperatures 0 = beta_0 < beta_1 < ... = 1 chosen so that the effective
+sample size of the importance weights stays at ``ess`` N; every stage reweights, resamples (systematic), whitens with the
+particles' covariance and moves all particles by ``sweeps`` Metropolis sweeps under L^beta.  A sweep is one batch of N rows for the
+engine.  The ``device`` driver keeps particles and bookkeeping on the GPU (include/vegamx.h: vmx_smc_run); the ``python`` driver is
+the readable restatement in NumPy over ``VegaInterface.chi2_batch_device``.  Both follow vega_amd/csrc/vmx_smc.h decision for
+decision - its own ``exp`` included - so that they produce the same particles and ancestors bit for bit.  The evidence is computed
+here, on the host, from the stage record - one code for both drivers.
+
+``log Z = sum_t log mean_i w_i(beta_t)`` with ``w_i = L_i^(beta_t - beta_{t-1})``; its error ``sqrt(sum_t (N / ESS_t - 1) / N)``
+is the delta-method figure for independent particles: it ignores the correlation the moves leave behind (few sweeps make the
+particles of a stage more alike than independent draws would be, and the seed-to-seed scatter then exceeds it; see
+:func:`evidence`).
+
+What is not here: pocoMC's flow-based preconditioning, ``dynamic`` particle counts, ``n_total`` top-ups at beta = 1, state files.
+"""
+import math
+import time
+from pathlib import Path
+
+import numpy as np
+
+from . import ensemble as E
+from . import nested as NS
+
+MAXN = 32
+MAX_PARTICLES = 4096
+BISECTIONS = 60
+LANES = 1024
+DOMAIN_MOVE, DOMAIN_RESAMPLE, DOMAIN_START = 3, 4, 5
+
+INV_LN2 = 1.44269504088896338700e+00
+LN2_HI = 6.93147180369123816490e-01
+LN2_LO = 1.90821492927058770002e-10
+_EXP_COEF = (1.0 / 479001600.0, 1.0 / 39916800.0, 1.0 / 3628800.0, 1.0 / 362880.0, 1.0 / 40320.0, 1.0 / 5040.0, 1.0 / 720.0,
+             1.0 / 120.0, 1.0 / 24.0, 1.0 / 6.0, 0.5, 1.0, 1.0)
+
+
+# ------------------------------------------------------------------ the algorithm (vmx_smc.h) in NumPy
+def _pow2(k):
+    return ((np.asarray(k, dtype=np.int64) + 1023).astype(np.uint64) << np.uint64(52)).view(np.float64)
+
+
+def pexp(x):
+    """vmx_smc::pexp: exp from separately rounded operations, the same bits as the header gives."""
+    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    nan, big, small = np.isnan(x), x > 709.0, x < -745.2
+    xs = np.where(nan | big | small, 0.0, x)
+    s = xs * INV_LN2
+    kf = np.floor(s + 0.5)
+    h = kf * LN2_HI
+    r = xs - h
+    low = kf * LN2_LO
+    r = r - low
+    p = np.full(x.shape, 1.0 / 6227020800.0)
+    for c in _EXP_COEF:
+        m = p * r
+        p = m + c
+    k = kf.astype(np.int64)
+    deep = k < -1022
+    q = p * _pow2(np.where(deep, k + 1000, k))
+    out = np.where(deep, q * 2.0**-1000, q)
+    out = np.where(small, 0.0, np.where(big, np.inf, out))
+    return np.where(nan, x, out)
+
+
+def _blocks(c0, c1, c2, c3, seed, stream):
+    c0 = np.asarray(c0, dtype=np.uint64)
+    ctr = np.zeros(c0.shape + (4,), dtype=np.uint64)
+    ctr[..., 0] = c0
+    ctr[..., 1] = np.asarray(c1, dtype=np.uint64)
+    ctr[..., 2] = np.asarray(c2, dtype=np.uint64)
+    ctr[..., 3] = np.uint64(c3)
+    return E.philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def move_blocks(i, stage, sweep, j, seed, stream=0):
+    """Blocks of particle ``i`` at (stage, sweep), block index ``j``: counter (i, stage 2^32 + sweep, j, 3)."""
+    return _blocks(i, (int(stage) << 32) + int(sweep), j, DOMAIN_MOVE, seed, stream)
+
+
+def resample_uniform(stage, seed, stream=0):
+    return float(E.u01(_blocks(np.zeros(1), int(stage), 0, DOMAIN_RESAMPLE, seed, stream)[0, 0]))
+
+
+def draw_start(N, n, seed, stream=0):
+    """The start particles [N, n]: coordinate c of particle i from word c % 4 of block (i, 0, c / 4, 5)."""
+    nb = (n + 3) // 4
+    i = np.repeat(np.arange(N)[:, None], nb, axis=1)
+    j = np.repeat(np.arange(nb)[None, :], N, axis=0)
+    return E.u01(_blocks(i, 0, j, DOMAIN_START, seed, stream).reshape(N, nb * 4)[:, :n])
+
+
+def start_scale(n):
+    t = 3.0 / float(n)
+    return 2.38 * math.sqrt(t)
+
+
+def pad_pow2(N):
+    M = 1
+    while M < N:
+        M <<= 1
+    return M
+
+
+def weights(dbeta, d):
+    d = np.asarray(d, dtype=np.float64)
+    dead = np.isneginf(d)
+    return np.where(dead, 0.0, pexp(np.float64(dbeta) * np.where(dead, 0.0, d)))
+
+
+def tree_sum(a):
+    """The stride-halving tree over ``a`` padded with zeros to a power of two."""
+    M = pad_pow2(a.size)
+    a = np.concatenate([a, np.zeros(M - a.size)])
+    s = M // 2
+    while s >= 1:
+        a = a[:s] + a[s:2 * s]
+        s //= 2
+    return float(a[0])
+
+
+def weight_sums(dbeta, d):
+    w = weights(dbeta, d)
+    return tree_sum(w), tree_sum(w * w)
+
+
+def ess_of(s1, s2):
+    t = np.float64(s1) * np.float64(s1)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return float(t / np.float64(s2))
+
+
+def next_beta(beta_prev, d, target):
+    """(beta_t, ESS(beta_t), S1(beta_t)) from beta_{t-1} and d_i = lnL_i - max lnL."""
+    beta = 1.0
+    s1, s2 = weight_sums(1.0 - beta_prev, d)
+    if not ess_of(s1, s2) >= target:
+        lo, hi = float(beta_prev), 1.0
+        for _ in range(BISECTIONS):
+            mid = 0.5 * (lo + hi)
+            s1, s2 = weight_sums(mid - beta_prev, d)
+            if ess_of(s1, s2) >= target:
+                lo = mid
+            else:
+                hi = mid
+        beta = lo
+        s1, s2 = weight_sums(beta - beta_prev, d)
+    return beta, ess_of(s1, s2), s1
+
+
+def cumulative(w, s1):
+    """The cumulative normalised weights: per-segment running sums plus the scanned segment totals; the last entry is 1."""
+    N = w.size
+    L = (N + LANES - 1) // LANES
+    with np.errstate(invalid='ignore', divide='ignore'):
+        q = np.concatenate([w / np.float64(s1), np.zeros(L * LANES - N)]).reshape(LANES, L)
+    r = np.zeros((LANES, L))
+    acc = np.zeros(LANES)
+    for k in range(L):
+        acc = acc + q[:, k]
+        r[:, k] = acc
+    t = acc.copy()
+    step = 1
+    while step < LANES:
+        t = np.concatenate([t[:step], t[step:] + t[:-step]])
+        step <<= 1
+    pre = np.concatenate([[0.0], t[:-1]])
+    c = (pre[:, None] + r).reshape(-1)[:N].copy()
+    c[N - 1] = 1.0
+    return c
+
+
+def positions(v, N):
+    s = np.float64(v) + np.arange(N, dtype=np.float64)
+    return s / float(N)
+
+
+def ancestors(c, p):
+    N = c.size
+    lo = np.zeros(p.size, dtype=np.int64)
+    hi = np.full(p.size, N - 1, dtype=np.int64)
+    while np.any(lo < hi):
+        go = lo < hi
+        mid = (lo + hi) // 2
+        with np.errstate(invalid='ignore'):
+            right = c[mid] > p
+        hi = np.where(go & right, mid, hi)
+        lo = np.where(go & ~right, mid + 1, lo)
+    return lo.astype(np.int32)
+
+
+def stage_head(u, lnl, beta_prev, ess, stage, seed, stream=0):
+    """Reweight, resample and whiten for stage ``stage``: dict(beta, ess, s1, w, c, anc, u, lnl (resampled), mean, cov, C,
+    cholesky).  ``beta`` NaN: no particle has a finite lnL."""
+    N = u.shape[0]
+    top = np.max(lnl)
+    if top == -np.inf:
+        return dict(beta=math.nan)
+    with np.errstate(invalid='ignore'):
+        d = lnl - top
+    beta, ess_t, s1 = next_beta(beta_prev, d, np.float64(ess) * float(N))
+    w = weights(beta - beta_prev, d)
+    c = cumulative(w, s1)
+    anc = ancestors(c, positions(resample_uniform(stage, seed, stream), N))
+    u2, lnl2 = u[anc], lnl[anc]
+    mean, cov = NS.mean_cov(u2)
+    C, ok = NS.whiten(cov)
+    return dict(beta=beta, ess=ess_t, s1=s1, w=w, c=c, anc=anc, u=u2, lnl=lnl2, mean=mean, cov=cov, C=C, cholesky=ok)
+
+
+def propose(u, C, scale, stage, sweep, seed, stream=0):
+    """Proposals of every particle at (stage, sweep): (y [N, n], inside [N], the deciding uniforms [N])."""
+    N, n = u.shape
+    nb = n // 4 + 1
+    i = np.repeat(np.arange(N)[:, None], nb, axis=1)
+    j = np.repeat(np.arange(nb)[None, :], N, axis=0)
+    x = E.u01(move_blocks(i, stage, sweep, j, seed, stream).reshape(N, nb * 4)[:, :n + 1])
+    two = 2.0 * x[:, :n]
+    g = two - 1.0
+    z = np.zeros((N, n))
+    for jj in range(n):         # (z_a accumulates C_aj g_j in the order j = 0 .. a)
+        z[:, jj:] = z[:, jj:] + C[jj:, jj][None, :] * g[:, jj][:, None]
+    step = np.float64(scale) * z
+    y = u + step
+    return y, np.all((y >= 0.0) & (y <= 1.0), axis=1), x[:, n]
+
+
+def accept(inside, ok, beta, lnl_new, lnl_old, ua):
+    with np.errstate(invalid='ignore'):
+        dl = lnl_new - lnl_old
+        delta = np.float64(beta) * dl
+        up = delta >= 0.0
+        return inside & ok & (up | (ua < pexp(np.where(up | np.isnan(delta), 0.0, delta))))
+
+
+def adapt(scale, accepted, N):
+    a = float(accepted) / float(N)
+    if a < 0.15:
+        return scale * 0.8
+    if a > 0.35:
+        return scale * 1.25
+    return scale
+
+
+_REC_KEYS = ('beta_prev', 'beta', 'ess', 'accepted', 'scale', 'cholesky')
+
+
+def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, watch=None):
+    """Up to ``n_stages`` stages in NumPy from the state ``u`` [N, n], ``lnl`` [N] (updated in place), stopping after the stage
+    that reaches beta = 1.  ``evaluate(rows_u)`` -> lnL [N] of rows in the cube (-inf: a failed model).  ``watch(stage, sweep, u,
+    lnl, scale, accepted)`` is called after every sweep.  Returns (record: a list of dicts per stage with beta_prev, beta, ess,
+    lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale, stats)."""
+    N, n = u.shape
+    record = []
+    st = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0)
+    for _ in range(n_stages):
+        if beta >= 1.0:
+            break
+        head = stage_head(u, lnl, beta, ess, stage, seed, stream)
+        if math.isnan(head['beta']):
+            raise ValueError('SMC: no particle has a finite log-likelihood')
+        if not head['beta'] > beta:
+            raise ValueError('SMC: the temperature ladder cannot advance: fewer than ess N particles carry weight')
+        rec = dict(beta_prev=beta, beta=head['beta'], ess=head['ess'], lnl=lnl.copy(), anc=head['anc'], cholesky=head['cholesky'])
+        u[:], lnl[:] = head['u'], head['lnl']
+        beta = head['beta']
+        acc_stage = 0
+        for s in range(sweeps):
+            y, inside, ua = propose(u, head['C'], scale, stage, s, seed, stream)
+            lnl_new = np.asarray(evaluate(np.where(inside[:, None], y, u)), dtype=np.float64)
+            ok = lnl_new > -np.inf
+            acc = accept(inside, ok, beta, lnl_new, lnl, ua)
+            u[acc] = y[acc]
+            lnl[acc] = lnl_new[acc]
+            k = int(acc.sum())
+            scale = adapt(scale, k, N)
+            acc_stage += k
+            st['rows'] += N
+            st['rows_own_position'] += int((~inside).sum())
+            st['rejected_failed_model'] += int((inside & ~ok).sum())
+            if watch is not None:
+                watch(stage, s, u, lnl, scale, k)
+        st['sweeps'] += sweeps
+        st['accepted'] += acc_stage
+        st['stages'] += 1
+        rec.update(accepted=acc_stage, scale=scale)
+        record.append(rec)
+        stage += 1
+    return record, stage, beta, scale, st
+
+
+# ------------------------------------------------------------------ evidence (host, both drivers)
+def evidence(record, N):
+    """(log Z, err) from the stage record: ``log Z = sum_t [log mean_i w_i(beta_t) + (beta_t - beta_{t-1}) max lnL]`` with
+    ``w_i(beta_t) = exp((beta_t - beta_{t-1})(lnL_i - max lnL))``, through a log-sum-exp; ``err = sqrt(sum_t (N / ESS_t - 1) /
+    N)``.  The error is the delta-method variance of a mean of N independent weights, stage by stage (relative variance of the
+    mean weight = (N / ESS - 1) / N); resampling noise and the correlation between particles that share an ancestor and have
+    not moved apart are not in it.  With the default 4 n sweeps the seed-to-seed scatter was measured at about 1.0 - 1.2 times
+    this figure (tests/test_smc_host.py), with half as many sweeps about 1.5 times."""
+    log_z, var = 0.0, 0.0
+    for rec in record:
+        db = rec['beta'] - rec['beta_prev']
+        with np.errstate(invalid='ignore'):
+            log_z += NS._logsumexp(db * np.asarray(rec['lnl'], dtype=np.float64)) - math.log(N)
+        var += (N / rec['ess'] - 1.0) / N
+    return log_z, math.sqrt(max(var, 0.0))
+
+
+class SMCRun:
+    """A tempered SMC run over ``loglike(rows_u [R, n]) -> lnL [R]`` in the unit cube (-inf: a failed model), NumPy driver: the
+    particles, the stage record and the evidence.  :class:`SMCSampler` puts the engine behind it."""
+
+    def __init__(self, loglike, n, particles=1024, ess=0.5, sweeps=None, seed=0, stream=0, max_stages=None):
+        self.loglike = loglike
+        self.n = int(n)
+        self.particles = int(particles)
+        self.ess = float(ess)
+        self.sweeps = int(sweeps) if sweeps is not None else 4 * self.n
+        self.seed, self.stream = int(seed), int(stream)
+        self.max_stages = None if max_stages is None else int(max_stages)
+        if not 1 <= self.n <= MAXN:
+            raise ValueError(f'1 .. {MAXN} sampled parameters')
+        if not max(2 * self.n + 2, 8) <= self.particles <= MAX_PARTICLES:
+            raise ValueError(f'particles: {max(2 * self.n + 2, 8)} .. {MAX_PARTICLES} for {self.n} sampled parameters')
+        if not 0.0 < self.ess < 1.0:
+            raise ValueError('ess: between 0 and 1')
+        if self.sweeps < 1:
+            raise ValueError('sweeps >= 1')
+        if self.max_stages is not None and self.max_stages < 1:
+            raise ValueError('max_stages >= 1')
+        self.reset()
+
+    def reset(self):
+        self.u = self.lnl = None
+        self.stage = 0
+        self.beta = 0.0
+        self.scale = start_scale(self.n)
+        self.record = []
+        self.stats = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0, engine_calls=0,
+                          host_waits=0, seconds=0.0, seconds_enqueuing=0.0, calls=0)
+
+    @property
+    def finished(self):
+        return self.beta >= 1.0
+
+    @property
+    def stages(self):
+        """The ladder so far, one entry per stage: dict of arrays beta_prev, beta, ess, acceptance (accepted / (N sweeps)),
+        scale (after the stage)."""
+        rec = self.record
+        return dict(beta_prev=np.array([r['beta_prev'] for r in rec]), beta=np.array([r['beta'] for r in rec]),
+                    ess=np.array([r['ess'] for r in rec]),
+                    acceptance=np.array([r['accepted'] / (self.particles * self.sweeps) for r in rec]),
+                    scale=np.array([r['scale'] for r in rec]))
+
+    # ---- drivers
+    def _evaluate(self, rows_u):
+        return np.asarray(self.loglike(rows_u), dtype=np.float64)
+
+    def _draw(self):
+        self.u = np.ascontiguousarray(draw_start(self.particles, self.n, self.seed, self.stream))
+        self.lnl = np.ascontiguousarray(self._evaluate(self.u), dtype=np.float64)
+        self.stats['rows'] += self.particles
+        if np.any(np.isnan(self.lnl)):
+            raise ValueError('SMC: a start particle has a NaN log-likelihood')
+        if not np.any(self.lnl > -np.inf):
+            raise ValueError('SMC: no particle has a finite log-likelihood')
+
+    def _advance(self, n_stages):
+        """One call of the driver: (record, statistics)."""
+        if self.u is None:
+            self._draw()
+        rec, self.stage, self.beta, self.scale, st = python_stages(
+            self.u, self.lnl, self.stage, self.beta, self.scale, n_stages, self.ess, self.sweeps, self.seed, self.stream,
+            self._evaluate)
+        return rec, st
+
+    def run(self, stages=None):
+        """To beta = 1 (``stages`` None; ``max_stages`` bounds the run), or at most ``stages`` more stages; the run does not
+        depend on how it is cut."""
+        t0 = time.perf_counter()
+        if stages is None:
+            call = 1 << 20 if self.max_stages is None else max(0, self.max_stages - self.stage)
+        else:
+            call = int(stages)
+            if self.max_stages is not None:
+                call = min(call, max(0, self.max_stages - self.stage))
+        if call > 0 and not self.finished:
+            rec, st = self._advance(call)
+            self.record.extend(rec)
+            for key, val in st.items():
+                if key in ('lanes', 'const_hint'):      # (what the engine ran with)
+                    self.stats[key] = val
+                elif key in self.stats and key != 'seconds':
+                    self.stats[key] += val
+            self.stats['calls'] += 1
+        self.stats['seconds'] += time.perf_counter() - t0
+        return self
+
+    # ---- results
+    def log_evidence(self):
+        """(log Z, its delta-method error: :func:`evidence`) of the stages run so far (the evidence when ``finished``)."""
+        if self.u is None:
+            raise ValueError('nothing has run yet')
+        return evidence(self.record, self.particles)
+
+    def to_physical(self, u):
+        return u
+
+    def samples(self):
+        """(points [N, n], lnL [N], weights [N] = 1 / N): the particles - the posterior sample once ``finished``."""
+        if self.u is None:
+            raise ValueError('nothing has run yet')
+        return self.to_physical(self.u.copy()), self.lnl.copy(), np.full(self.particles, 1.0 / self.particles)
+
+
+# ------------------------------------------------------------------ the sampler over the engine
+_PER_CALL = 64          # stages per call of the device driver (its record is allocated up front)
+
+
+class SMCSampler(SMCRun):
+    """Tempered SMC of ``vega`` over its sampled parameters (``sample_params['limits']`` as for
+    :class:`vega_amd.ensemble.EnsembleSampler`), a uniform prior over the limits.  ``driver``: ``'device'`` (vmx_smc_run) or
+    ``'python'`` (the NumPy restatement over ``chi2_batch_device``); an engine group takes ``'python'``."""
+
+    def __init__(self, vega, particles=1024, ess=0.5, sweeps=None, seed=0, driver='device', chunk=0, sample_params=None, stream=0,
+                 lanes=0, const_hint=-1, max_stages=None):
+        if driver not in ('device', 'python'):
+            raise ValueError("driver: 'device' or 'python'")
+        self.vega = vega
+        box = E.SampledBox(vega, sample_params)
+        self.names, self.lo, self.hi, self.cols = box.names, box.lo, box.hi, box.cols
+        self.driver_asked = driver
+        self.driver = None
+        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
+        self._rows = None
+        super().__init__(None, box.n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, stream=stream, max_stages=max_stages)
+
+    def log_norm(self):
+        return float(self.vega._log_norm())
+
+    def to_physical(self, u):
+        return NS.map_cube(self.lo, self.hi, np.asarray(u, dtype=np.float64))
+
+    def _evaluate(self, rows_u):
+        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
+        rows_t[:, self.cols] = NS.map_cube(self.lo, self.hi, rows_u)
+        # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+        return NS.lnl_of(0, self._rows.chi2(rows_t), self.log_norm())
+
+    def _advance(self, n_stages):
+        vega = self.vega
+        self._theta = np.asarray(vega._theta(None), dtype=np.float64).copy()
+        if self.driver is None:
+            first = self._theta.copy()
+            first[self.cols] = NS.map_cube(self.lo, self.hi, draw_start(1, self.n, self.seed, self.stream)[0])
+            self.driver = E.freeze_and_pick_driver(vega, first, self.cols, self.driver_asked, 'smc_run')
+        if self.driver == 'python':
+            with E.EngineRows(vega, self.cols, self.chunk, self.lanes, self.const_hint) as self._rows:
+                try:
+                    rec, st = super()._advance(n_stages)
+                finally:
+                    calls, self._rows = self._rows.calls, None
+            st['engine_calls'] = st['host_waits'] = calls
+            return rec, st
+        vega._sync_monte_carlo()
+        draw = self.u is None
+        u = np.zeros((self.particles, self.n)) if draw else self.u
+        lnl = np.zeros(self.particles) if draw else self.lnl
+        record, total = [], None
+        while n_stages > 0 and (draw or self.beta < 1.0):
+            rec, self.stage, self.beta, self.scale, st = vega.engine.smc_run(
+                self.cols, self.lo, self.hi, self._theta, u, lnl, self.stage, self.beta, self.scale, min(n_stages, _PER_CALL),
+                self.ess, self.sweeps, log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint,
+                chunk=self.chunk, lanes=self.lanes, draw=draw)
+            self.u, self.lnl = u, lnl
+            draw = False
+            n_stages -= min(n_stages, _PER_CALL)
+            record.extend(rec)
+            if total is None:
+                total = dict(st)
+            else:
+                for key, val in st.items():
+                    if key not in ('const_hint', 'lanes'):
+                        total[key] += val
+        return record, total or {}
+
+    def write(self, path, name):
+        """getdist's chain ``name.txt`` (weight 1, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
+        ``name.paramnames`` and ``name.stats``."""
+        return write_run(self, path, name, self.names)
+
+
+def smc_settings(main_config, sample_params):
+    """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
+    has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}; ``sweeps`` None: 4 n."""
+    import os
+    if 'SMC' not in main_config:
+        raise RuntimeError('run_sampler called, but no sampler config found')
+    sec = main_config['SMC']
+    limits = sample_params['limits']
+    for lims in limits.values():
+        if lims is None or None in tuple(lims):
+            raise ValueError(E._NO_LIMITS)
+    if 'path' not in sec:
+        raise ValueError('[SMC] needs a path')
+    path = Path(os.path.expandvars(sec.get('path')))
+    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
+                           "running.")
+    n = len(limits)
+    out = dict(sampler='SMC', path=path, name=sec.get('name', 'smc'), particles=sec.getint('particles', 1024),
+               ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None), seed=sec.getint('seed', 0),
+               driver=sec.get('driver', 'device'), max_stages=sec.getint('max_stages', None))
+    if out['driver'] not in ('device', 'python'):
+        raise ValueError("[SMC] driver: 'device' or 'python'")
+    if not 1 <= n <= MAXN:
+        raise ValueError(f'[SMC] 1 .. {MAXN} sampled parameters')
+    if not max(2 * n + 2, 8) <= out['particles'] <= MAX_PARTICLES:
+        raise ValueError(f'[SMC] particles: {max(2 * n + 2, 8)} .. {MAX_PARTICLES} for {n} sampled parameters')
+    if not 0.0 < out['ess'] < 1.0:
+        raise ValueError('[SMC] ess: between 0 and 1')
+    if out['sweeps'] is not None and out['sweeps'] < 1:
+        raise ValueError('[SMC] sweeps must be positive')
+    if out['max_stages'] is not None and out['max_stages'] < 1:
+        raise ValueError('[SMC] max_stages must be positive')
+    return out
+
+
+def write_run(run, path, name, names):
+    """The three files of an :class:`SMCRun`: (txt, paramnames, stats)."""
+    pts, lnl, _ = run.samples()
+    txt, pn = E.write_getdist(path, name, names, pts, lnl)
+    log_z, err = run.log_evidence()
+    stats = Path(path) / f'{name}.stats'
+    with open(stats, 'w') as f:
+        f.write(f'log(Z) = {log_z!r}\nlog(Z) error = {err!r}\n')
+        f.write(f'stages = {run.stage}\nsweeps = {run.sweeps}\nlikelihood evaluations = {run.stats["rows"]}\n')
+        f.write(f'seed = {run.seed}\nparticles = {run.particles}\ness = {run.ess!r}\n')
+        f.write('beta = ' + ' '.join(repr(float(r['beta'])) for r in run.record) + '\n')
+    return txt, pn, stats
+
+
+def read_stats(path):
+    """``name.stats`` back as a dict (floats for the evidence lines and ``ess``, a list of floats for ``beta``, ints for the
+    counts)."""
+    out = {}
+    for line in Path(path).read_text().splitlines():
+        key, _, val = line.partition(' = ')
+        if key == 'beta':
+            out[key] = [float(v) for v in val.split()]
+        else:
+            out[key] = float(val) if key in ('log(Z)', 'log(Z) error', 'ess') else int(val)
+    return out
