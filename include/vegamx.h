@@ -581,6 +581,21 @@ int vmx_set_linear_spectra(vmx_engine* e, const double* pk_peak, const double* p
  * kernels and copies out [B][n_templates] (host pointer; synchronous). */
 int vmx_item_set_marg_matrix(vmx_engine* e, int32_t item, const double* m, int32_t n_templates, int32_t n_masked);
 int vmx_marg_coeff(vmx_engine* e, int32_t item, double* out, int32_t B);
+/* The same coefficients as derived columns of walkers that live in HBM - what a sampler stores beside every point
+ * (samplers/polychord.py:106-113).  The residual is linear in the dx = x' - x0' that the quadratic form of chi2 contracts
+ * (vmx_set_quadratic_form), so coeff = c0 - G dx with G = M S DM' [n_templates][nq] and c0 = M r0 per data vector / mock, folded
+ * once when the form's tensors are built and refreshed with them (data, mock pool, reference point).  The call runs the chain up
+ * to the walkers' vectors (table level of vmx_set_constant_nl_hint and the mock rows of vmx_set_mock_index honoured), then per item
+ * one skinny product (split-K slabs added in fixed order) and one kernel that writes d_out[b][offset(item) + i], row-major with
+ * leading dimension ld_out >= the total count; NaN in every column of a walker whose status is not 0.  No chi2, no model
+ * vector, no distortion product, no residual; enqueued on the engine's stream without host synchronisation or host copy
+ * (vmx_sync, vmx_stream).  Where the quadratic form does not apply (global covariance, multiplicative or non-polynomial
+ * post-distortion broadband, direct_pk, the form switched off) the same call takes the full chain and applies M to its
+ * residuals, still device to device.  d_status [B] may be NULL.  vmx_debug_read(what = 4)[8] reports the form the call took.
+ * vmx_marg_layout: the columns of `item` (offset, count; either may be NULL; count 0 for an item without a map), items in the
+ * order of vmx_add_item; returns the total number of columns (item = -1: only that). */
+int vmx_marg_coeff_device(vmx_engine* e, const double* d_theta, int32_t B, double* d_out, int32_t ld_out, int32_t* d_status);
+int vmx_marg_layout(vmx_engine* e, int32_t item, int32_t* offset, int32_t* count);
 
 /* The mu sums of the P(k,mu) stage.  The reference sums P(k,mu) L_ell(mu) over 1000 midpoints in mu
  * (power_spectrum.py:76-77, pktoxi.py:138).  node_rule != 0 (the default): for wavenumbers up to 24 / (largest bin size)

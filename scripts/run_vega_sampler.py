@@ -4,7 +4,8 @@
 thin, init, init_scale, driver) or ``sampler = Nested`` (``[Nested]``: path, name, num_live, num_repeats, precision, seed, threads,
 driver, max_iterations) or ``sampler = SMC`` (``[SMC]``: path, name, particles, ess, sweeps, seed, driver, max_stages).  Writes
 ``<path>/<name>.txt`` and ``<path>/<name>.paramnames`` (getdist's plain-text chain); a nested or SMC run also
-``<path>/<name>.stats`` with the evidence.
+``<path>/<name>.stats`` with the evidence.  ``derived = True`` in the sampler's section appends the marginalisation
+coefficients as derived parameters (``<corr>_marg_<i>``) to both files.
 
     python scripts/run_vega_sampler.py main.ini
 """

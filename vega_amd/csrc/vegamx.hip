@@ -130,6 +130,9 @@ struct ItemHost {
     // ... in its factored form (vmx_set_quadratic_form_kind): U with C^-1 = U^T U [n_masked][n_masked_pad], F = U S DM'
     // [n_masked][nq_pad], u0 = U r0 per data vector / mock [rows][n_masked_pad], slabs of F dx [slab_rows][n_masked_pad]
     DevBuf<double> q_u, q_f, q_u0, q_y;
+    // marginalisation coefficients folded into that form (vmx_marg_coeff_device): G = M S DM' [n_templates][nq_pad] (static),
+    // c0 = M r0 per data vector / mock [rows][pad(n_templates)], slabs of G dx (or of M . residual) [mg_rows][pad(n_templates)]
+    DevBuf<double> mg_g, mg_c0, mg_y;
     // mocks made on the device (vmx_item_set_mock_factor, vmx_fit_migrad with a mock stream): Cholesky factor [n_masked][pad] and
     // fiducial [pad]; the full C^-1 and the masked reference model of the quadratic form, kept for the per-wave linear terms;
     // per-wave scratch (draws, noise, residual rows, C^-1 rows)
@@ -825,6 +828,9 @@ struct vmx_engine {
     bool static_poly = true;         // vmx_set_static_poly
     int quad_kind = 0;               // vmx_set_quadratic_form_kind: 0 = the cheaper form, 1 = Q', 2 = factored
     bool quad_factored = false;      // the form the tensors were built for
+    struct MargReq { double* out; int64_t ld_out; int32_t* status; };
+    const MargReq* marg_req = nullptr;      // set while vmx_marg_coeff_device runs the chain: derived columns instead of chi2
+    int marg_slab_rows = 0;          // rows of the items' mg_y (K slabs of G dx)
     int last_form = 0;               // form of the last evaluation: 0 full chain, 1 Q', 2 factored (vmx_debug_read 4 [8])
     // VMX_TRACE_HOST: host-side phases of vmx_eval accumulated in nanoseconds (staging, enqueue, wait), printed at destroy
     bool trace_host = false; double host_ns[3] = {0, 0, 0}; int64_t host_calls = 0;
@@ -2735,6 +2741,8 @@ static int xi_sum_plan(vmx_engine* e)
     return 0;
 }
 
+static int marg_products(vmx_engine* e, const EngineDev& D, int B, bool folded);
+
 static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false, const double* d_theta = nullptr,
                      double* d_chi2 = nullptr, int32_t* d_status = nullptr, bool quad = false,
                      const double* theta_by_value = nullptr)
@@ -3028,6 +3036,14 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
             ScopedTimer t(e, KC_ASSEMBLE);
             hipLaunchKernelGGL(k_assemble_quad, dim3((max_nq + 255) / 256, B, (unsigned)e->items.size()), dim3(256), 0, e->cur, D);
         }
+        if (e->marg_req) {
+            // derived columns only (vmx_marg_coeff_device): G dx per item with templates instead of the form's own product
+            e->last_form = e->quad_factored ? 2 : 1;
+            if (marg_products(e, D, B, true)) return -2;
+            e->last_B = B;
+            e->last_full = false;
+            return 0;
+        }
         SlabInfo qs{};
         for (size_t q = 0; q < e->items.size(); ++q) qs.z[q] = 1;
         if (e->quad_factored) {
@@ -3320,6 +3336,42 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
     return 0;
 }
 
+// The products and the output kernel of vmx_marg_coeff_device for the B walkers run_chain has just taken up to their vectors:
+// folded = true: y = G dx from the quadratic form's dx (q_x), out = c0[mock(b)] - y; false: y = M . residual of the full chain.
+// Split-K slabs in fixed order; everything on the engine's stream, into buffers made outside (marg_workspace).
+static int marg_products(vmx_engine* e, const EngineDev& D, int B, bool folded)
+{
+    const vmx_engine::MargReq& r = *e->marg_req;
+    MargOutArgs A{};
+    int n = 0, off = 0;
+    e->cur = e->stream;
+    for (size_t q = 0; q < e->items.size(); ++q) {
+        ItemHost* it = e->items[q];
+        if (it->n_templates <= 0) continue;
+        const ItemDev& d = it->dev;
+        const int nt = it->n_templates, ldt = vmx_pad(nt);
+        MargOutItem& m = A.p[n++];
+        m.item = (int)q; m.n = nt; m.ld = ldt; m.off = off; m.y = it->mg_y.p;
+        off += nt;
+        if (folded) {
+            m.slabs = launch_product(e, KC_MATVEC, it->mg_g.p, d.nq_pad, 0, nt, d.nq_pad, it->q_x.p, d.nq_pad, 0, B,
+                                     it->mg_y.p, ldt, 0, 1, e->marg_slab_rows);
+            m.c0 = it->mg_c0.p;
+        } else {
+            m.slabs = launch_product(e, KC_MATVEC, it->marg.p, d.n_masked_pad, 0, nt, d.n_masked_pad, it->res.p, d.n_masked_pad, 0, B,
+                                     it->mg_y.p, ldt, 0, 1, e->marg_slab_rows);
+            m.c0 = nullptr;
+        }
+    }
+    A.out = r.out; A.ld_out = r.ld_out; A.status_out = r.status; A.finish = folded ? 1 : 0;
+    if (n > 0) {
+        ScopedTimer t(e, KC_POST);
+        hipLaunchKernelGGL(k_marg_out, dim3(B, n), dim3(256), 0, e->stream, D, A, B);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // run the chain for B walkers: replay a captured graph when one exists (or can be captured), else launch eagerly
 static int run_chain_cached(vmx_engine* e, int B, int tab_mode, bool zero_copy = false, bool quad = false)
 {
@@ -3356,6 +3408,18 @@ static int run_chain_cached(vmx_engine* e, int B, int tab_mode, bool zero_copy =
     HIP_OK(hipGraphLaunch(it->second, e->stream));
     e->last_B = B;
     e->last_full = !quad;
+    return 0;
+}
+
+// G = M X^T [n_templates][nq_pad] of an item with a marginalisation map, from the gathered X = (S DM')^T [nq][n_masked_pad] that
+// quad_build has just made for Q' / F (allocated once: static like them, and lanes hold views)
+static int marg_fold_matrix(vmx_engine* e, ItemHost* it, const double* X)
+{
+    if (it->n_templates <= 0) return 0;
+    const ItemDev& d = it->dev;
+    if (it->mg_g.p == nullptr && it->mg_g.alloc((size_t)it->n_templates * d.nq_pad, true)) return -2;
+    launch_product(e, KC_OTHER, X, d.n_masked_pad, 0, d.nq, d.n_masked_pad, it->marg.p, d.n_masked_pad, 0, it->n_templates,
+                   it->mg_g.p, d.nq_pad, 0, 1, it->n_templates);
     return 0;
 }
 
@@ -3478,6 +3542,7 @@ static int quad_build(vmx_engine* e)
             // F[m][j] = sum_i X[j][i] U[m][i]  (allocated once: captured graphs hold the pointer)
             if (it->q_f.p == nullptr && it->q_f.alloc((size_t)nm * nqp, true)) return -2;
             launch_product(e, KC_OTHER, X.p, nmp, 0, nq, nmp, it->q_u.p, nmp, 0, nm, it->q_f.p, nqp, 0, 1, nm);
+            if (marg_fold_matrix(e, it, X.p)) return -2;
             HIP_OK(hipStreamSynchronize(e->stream));        // X is released here
         }
         if (!e->quad_factored && (e->quad_mat_dirty || it->q_mat.p == nullptr)) {
@@ -3502,6 +3567,7 @@ static int quad_build(vmx_engine* e)
             launch_product(e, KC_OTHER, X.p, nmp, 0, nq, nmp, it->q_w.p, nmp, 0, nq, qfull.p, nqp, 0, 1, nq);
             if (it->q_mat.p == nullptr && it->q_mat.alloc((size_t)nq * nqp, true)) return -2;
             hipLaunchKernelGGL(k_half_from_full, dim3((nqp + 255) / 256, nq), dim3(256), 0, e->stream, it->q_mat.p, qfull.p, nq, nqp);
+            if (marg_fold_matrix(e, it, X.p)) return -2;
             HIP_OK(hipStreamSynchronize(e->stream));        // X / qfull are released here
         }
         // linear terms for the data vector and every mock of the pool
@@ -3527,6 +3593,12 @@ static int quad_build(vmx_engine* e)
             hipLaunchKernelGGL(k_rowdot, dim3(rows), dim3(256), 0, e->stream, it->q_c0.p, R0.p, T.p, nmp, nm);
         } else {
             hipLaunchKernelGGL(k_rowdot, dim3(rows), dim3(256), 0, e->stream, it->q_c0.p, R0.p, R0.p, nmp, nm);
+        }
+        if (it->n_templates > 0) {
+            // c0 = M r0 per data vector / mock, beside q_lin / q_c0 (reallocated only when the pool's size changed)
+            const int ldt = vmx_pad(it->n_templates);
+            if (it->mg_c0.n != (size_t)rows * ldt && it->mg_c0.alloc((size_t)rows * ldt, true)) return -2;
+            launch_product(e, KC_OTHER, it->marg.p, nmp, 0, it->n_templates, nmp, R0.p, nmp, 0, rows, it->mg_c0.p, ldt, 0, 1, rows);
         }
         it->q_rows = rows;
         if (it->q_x.n < (size_t)e->max_batch * nqp && it->q_x.alloc((size_t)e->max_batch * nqp, true)) return -2;
@@ -4599,6 +4671,64 @@ int vmx_marg_coeff(vmx_engine* e, int32_t item, double* out, int32_t B)
     HIP_OK(hipMemcpy2D(out, (size_t)it->n_templates * sizeof(double), it->marg_out.p, (size_t)ldo * sizeof(double),
                        (size_t)it->n_templates * sizeof(double), B, hipMemcpyDeviceToHost));
     return 0;
+}
+
+int vmx_marg_layout(vmx_engine* e, int32_t item, int32_t* offset, int32_t* count)
+{
+    REQUIRE(e && e->finalized, "vmx_marg_layout (after vmx_finalize)");
+    REQUIRE(item >= -1 && item < (int)e->items.size(), "item id");
+    int off = 0, total = 0;
+    for (int q = 0; q < (int)e->items.size(); ++q) {
+        if (q == item) off = total;
+        total += e->items[q]->n_templates;
+    }
+    if (item >= 0) {
+        if (offset) *offset = off;
+        if (count) *count = e->items[item]->n_templates;
+    }
+    return total;
+}
+
+int vmx_marg_coeff_device(vmx_engine* e, const double* d_theta, int32_t B, double* d_out, int32_t ld_out, int32_t* d_status)
+{
+    REQUIRE(e && e->finalized && d_theta && d_out, "vmx_marg_coeff_device");
+    REQUIRE(B > 0 && B <= e->max_batch, "batch exceeds max_batch");
+    int total = 0;
+    for (auto* it : e->items) total += it->n_templates;
+    REQUIRE(total > 0, "no marginalisation matrix was set for any item");
+    REQUIRE(ld_out >= total, "vmx_marg_coeff_device: ld_out holds fewer columns than vmx_marg_layout counts");
+    HIP_OK(hipSetDevice(e->device));
+    wait_lane(e);                       // (one lane: the request rides on the first lane's workspace)
+    e->host_key_valid = false;
+    bool quad = false;
+    if (quad_ready(e, &quad, B)) return -2;
+    // the slabs of the products: made at the first call, outside everything that is enqueued (the sizes never change)
+    if (e->marg_slab_rows == 0) e->marg_slab_rows = std::max(e->max_batch, std::min(8 * e->max_batch, 4096));
+    for (auto* it : e->items) {
+        const size_t need = (size_t)e->marg_slab_rows * vmx_pad(it->n_templates);
+        if (it->n_templates > 0 && it->mg_y.n < need) {
+            HIP_OK(hipStreamSynchronize(e->stream));
+            if (it->mg_y.alloc(need, true)) return -2;
+        }
+    }
+    e->last_stream = e->stream;
+    const vmx_engine::MargReq req{d_out, ld_out, d_status};
+    struct Scope { vmx_engine* x; Scope(vmx_engine* x_, const vmx_engine::MargReq* r) : x(x_) { x->marg_req = r; } ~Scope() { x->marg_req = nullptr; } };
+    Scope scope(e, &req);
+    const int tab = (B >= 16 && e->n_xtab > 0) ? e->const_hint : 0;
+    // eager launches: the first kernel reads the caller's walkers in place (behind a parameter transform: the engine's copy)
+    const double* src = d_theta;
+    if (!e->blind_scale.empty()) {
+        HIP_OK(hipMemcpyAsync(e->theta.p, d_theta, (size_t)B * e->n_params * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+        const int n = B * e->n_params;
+        hipLaunchKernelGGL(k_theta_affine, dim3((n + 255) / 256), dim3(256), 0, e->stream, e->theta.p, e->d_blind.p, e->n_params, n);
+        src = nullptr;
+    }
+    if (run_chain(e, B, tab, false, src, nullptr, nullptr, quad)) return -2;
+    if (quad) return 0;
+    // not served by the quadratic form (global covariance, multiplicative or non-polynomial post-distortion broadband, direct_pk,
+    // the form switched off): the full chain has left its residuals, M is applied to them as vmx_marg_coeff does
+    return marg_products(e, e->dev, B, false);
 }
 
 int vmx_get_mu_nodes(vmx_engine* e, double* mu, double* w, int32_t capacity)

@@ -37,6 +37,7 @@
 #define VMX_MAX_METALS 64
 #define VMX_MAX_QUAD_COEF 64 // additive post-distortion broadband coefficients the quadratic form of chi2 can carry
 #define VMX_MAX_GROUP 8      // independent products in one grouped launch (GemmGroup)
+#define VMX_MAX_MARG 16      // items of one k_marg_out launch (= the most items an engine takes)
 
 enum {
     S_BIAS1 = 0, S_BB1, S_BIAS2, S_BB2,
@@ -2367,6 +2368,41 @@ __global__ __launch_bounds__(256) void k_chi2_parts(EngineDev D, int B, const do
     if (b == 0) {
         D.k_live[2] = D.coef_win[0]; D.k_live[3] = D.coef_win[1]; D.coef_win[0] = 0x7fffffff; D.coef_win[1] = -1;
         xtab_key_store(D);
+    }
+}
+
+// Marginalisation coefficients as derived columns (vmx_marg_coeff_device).  The coefficients are the static map M of the residual,
+// and the residual is linear in the dx the quadratic form contracts: coeff = M (d - S DM' x') = c0 - G dx with G = M S DM'
+// [n_templates][nq_pad] and c0 = M r0 per data vector / mock, both folded at set-up (quad_build).  The product kernel leaves
+// y = G dx in K slabs; this kernel adds them in fixed order and writes c0[row(b)] - y into the caller's rows at the item's column
+// offset - NaN in every column of a walker whose status is not 0.  c0 = nullptr: the slabs hold M . residual of the full chain
+// itself (configurations the quadratic form does not serve) and are written as they are.  grid (B, items with templates).
+struct MargOutItem { const double* y; const double* c0; int32_t item, n, ld, off, slabs, pad; };
+struct MargOutArgs { MargOutItem p[VMX_MAX_MARG]; double* out; int64_t ld_out; int32_t* status_out; int32_t finish; };
+
+__global__ __launch_bounds__(256) void k_marg_out(EngineDev D, MargOutArgs A, int B)
+{
+    const int b = blockIdx.x;
+    const MargOutItem& m = A.p[blockIdx.y];
+    const ItemDev& it = D.items[m.item];
+    const int st = D.status[b];
+    const int mock = D.mock_index[b];
+    const int row = (mock >= 0 && it.mock_pool) ? 1 + mock : 0;
+    const double* c0 = m.c0 ? m.c0 + (size_t)row * m.ld : nullptr;
+    double* out = A.out + (size_t)b * A.ld_out + m.off;
+    for (int t = threadIdx.x; t < m.n; t += 256) {
+        double y = 0.0;
+        for (int s = 0; s < m.slabs; ++s) y += m.y[((size_t)s * B + b) * m.ld + t];       // fixed order
+        const double v = c0 ? c0[t] - y : y;
+        out[t] = st ? __longlong_as_double(0x7ff8000000000000ll) : v;
+    }
+    if (blockIdx.y == 0 && threadIdx.x == 0) {
+        if (A.status_out) A.status_out[b] = st;
+        // (no chi2 kernel closes this evaluation: the bookkeeping it does for the next one)
+        if (A.finish && b == 0) {
+            D.k_live[2] = D.coef_win[0]; D.k_live[3] = D.coef_win[1]; D.coef_win[0] = 0x7fffffff; D.coef_win[1] = -1;
+            xtab_key_store(D);
+        }
     }
 }
 

@@ -261,6 +261,8 @@ def load_library():
     lib.vmx_set_linear_spectra.argtypes = [C.c_void_p, dptr, dptr, dptr, C.c_int32]
     lib.vmx_item_set_marg_matrix.argtypes = [C.c_void_p, C.c_int32, dptr, C.c_int32, C.c_int32]
     lib.vmx_marg_coeff.argtypes = [C.c_void_p, C.c_int32, dptr, C.c_int32]
+    lib.vmx_marg_coeff_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.vmx_marg_layout.argtypes = [C.c_void_p, C.c_int32, iptr, iptr]
     lib.vmx_set_quadratic_form.argtypes = [C.c_void_p, dptr]
     lib.vmx_set_quadratic_form_kind.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_static_poly.argtypes = [C.c_void_p, C.c_int32]
@@ -302,7 +304,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1268,6 +1270,23 @@ class Engine:
         out = np.empty((B, nt))
         self._check(self.lib.vmx_marg_coeff(self._h, qi, _dp(out), B))
         return out
+
+    def marg_layout(self):
+        """{item name: (first column, count)} of the rows ``marg_coeff_device`` writes, and their total width - items in the
+        engine's order, those without templates left out (include/vegamx.h: vmx_marg_layout)."""
+        layout = {}
+        for qi, name in enumerate(self.item_names):
+            off, cnt = C.c_int32(0), C.c_int32(0)
+            total = self._check(self.lib.vmx_marg_layout(self._h, qi, C.byref(off), C.byref(cnt)))
+            if cnt.value > 0:
+                layout[name] = (off.value, cnt.value)
+        return layout, (total if self.item_names else 0)
+
+    def marg_coeff_device(self, d_theta_ptr, B, d_out_ptr, ld, d_status_ptr=None):
+        """Marginalisation-template coefficients of B walkers in device memory as rows of ``d_out_ptr`` [B][ld] (columns:
+        ``marg_layout``), NaN where a walker's model failed; enqueued on the engine's stream, nothing crosses PCIe
+        (include/vegamx.h: vmx_marg_coeff_device).  ``last_form()`` then tells which route served the call."""
+        self._check(self.lib.vmx_marg_coeff_device(self._h, d_theta_ptr, B, d_out_ptr, ld, d_status_ptr))
 
     def set_parameter_transform(self, scale=None, shift=None):
         """Parameter-level blinding: every walker becomes scale * theta + shift (per column) before the model and the

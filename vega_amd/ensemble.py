@@ -146,19 +146,84 @@ def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi
     return chain, chain_lnl, st
 
 
-def write_getdist(path, name, names, chain, chain_lnl, weights=None):
+def write_getdist(path, name, names, chain, chain_lnl, weights=None, derived=None, derived_names=None, derived_labels=None):
     """getdist's plain-text chain: ``name.txt`` (one row per sample: weight 1, -lnL, the parameters) and ``name.paramnames``
     (one ``name label`` line per parameter, label = name).  ``chain`` [..., n], ``chain_lnl`` [...]; ``weights`` [...]: a
-    weighted chain (a nested sampler's), the first column then holds them."""
+    weighted chain (a nested sampler's), the first column then holds them.  ``derived`` [..., m] with ``derived_names`` [m]
+    (``derived_labels`` [m], default the names): derived parameters, their columns after the sampled ones and their lines after
+    the sampled parameters' (the layout of the reference's PolyChord chains)."""
     path = Path(path)
     chain = np.asarray(chain, dtype=np.float64).reshape(-1, len(names))
     lnl = np.asarray(chain_lnl, dtype=np.float64).reshape(-1)
     first = np.ones(lnl.size) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
-    np.savetxt(path / f'{name}.txt', np.column_stack([first, -lnl, chain]), fmt='%.17g')
+    columns = [first, -lnl, chain]
+    lines = [(nm, nm) for nm in names]
+    if derived is not None:
+        if derived_names is None:
+            raise ValueError('derived columns need derived_names')
+        derived_names = list(derived_names)
+        labels = derived_names if derived_labels is None else list(derived_labels)
+        block = np.asarray(derived, dtype=np.float64).reshape(-1, len(derived_names))
+        if block.shape[0] != lnl.size or len(labels) != len(derived_names):
+            raise ValueError('derived: one row per sample, one name and one label per column')
+        columns.append(block)
+        lines += list(zip(derived_names, labels))
+    np.savetxt(path / f'{name}.txt', np.column_stack(columns), fmt='%.17g')
     with open(path / f'{name}.paramnames', 'w') as f:
-        for nm in names:
-            f.write(f'{nm} {nm}\n')
+        for nm, label in lines:
+            f.write(f'{nm} {label}\n')
     return path / f'{name}.txt', path / f'{name}.paramnames'
+
+
+def marg_derived_labels(counts):
+    """(names, labels) of the marginalisation coefficients as derived parameters for ``counts`` {correlation: coefficients}:
+    ``<corr>_marg_<i>`` with the label ``M_{\\rm <corr>}^{<i>}`` (reference vega/samplers/sampler_interface.py:82-89), the
+    correlations sorted by name (the stacking order of ``log_lik(..., return_marg_coeff=True)``, reference
+    vega/vega_interface.py:371-383), a correlation's coefficients in template order."""
+    names, labels = [], []
+    for corr in sorted(counts):
+        for i in range(int(counts[corr])):
+            names.append(f'{corr}_marg_{i}')
+            labels.append(f'M_{{\\rm {corr}}}^{{{i}}}')
+    return names, labels
+
+
+def parse_derived(section):
+    """``derived = True | False`` of a sampler's section (absent: False); anything else is refused."""
+    try:
+        return section.getboolean('derived', False)
+    except ValueError:
+        raise ValueError(f"[{section.name}] derived: True or False") from None
+
+
+def derived_rows(vega, cols, fixed_row, rows, chunk=0, lanes=0, const_hint=-1):
+    """The derived block [R, len(vega.derived_names())] of recorded sampler rows ``rows`` [R, n] (physical values of the columns
+    ``cols``; ``fixed_row`` supplies the others): one pass through ``marg_coeff_batch_device`` with the table level the run itself
+    used.  Evaluation is deterministic, so this is what recording at evaluation time would have stored; rows that repeat (a
+    walker that did not move) are evaluated once."""
+    import torch
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, len(cols))
+    m = len(vega.derived_names())
+    if m == 0 or rows.shape[0] == 0:
+        return np.empty((rows.shape[0], m))
+    uniq, inverse = np.unique(rows, axis=0, return_inverse=True)
+    theta = np.repeat(np.asarray(fixed_row, dtype=np.float64)[None, :], uniq.shape[0], axis=0)
+    theta[:, cols] = uniq
+    with EngineRows(vega, cols, chunk, lanes, const_hint) as er:
+        block = vega.marg_coeff_batch_device(torch.from_numpy(np.ascontiguousarray(theta)).to(er.device)).cpu().numpy()
+    return block[np.asarray(inverse).reshape(-1)]
+
+
+def derived_for_write(sampler, derived, print_func=print):
+    """The keyword arguments ``write_getdist`` takes for a sampler's ``write(..., derived=...)``: empty without the option, and
+    with it when no correlation has marginalisation templates (said through ``print_func``)."""
+    if not derived:
+        return {}
+    names = sampler.vega.derived_names()
+    if not names:
+        print_func('derived = True, but no correlation has marginalisation templates: writing the plain chain')
+        return {}
+    return dict(derived_names=names, derived_labels=sampler.vega.derived_labels())
 
 
 def autocorr_func_1d(x):
@@ -450,9 +515,22 @@ class EnsembleSampler:
         """Integrated autocorrelation time per parameter in recorded rows (emcee's estimator: :func:`integrated_time`)."""
         return integrated_time(self.get_chain(discard=discard, thin=thin), c=c)
 
-    def write(self, path, name):
-        """getdist's plain-text chain of the recorded rows (:func:`write_getdist`): ``name.txt`` and ``name.paramnames``."""
-        return write_getdist(path, name, self.names, self.get_chain(flat=True), self.get_log_lik(flat=True))
+    def get_derived(self, discard=0, thin=1, flat=False):
+        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the recorded rows,
+        [rows, W, m] like :meth:`get_chain` (``flat``: [rows W, m]) - a pass over the recorded rows after the run
+        (:func:`derived_rows`), the same block whichever driver ran."""
+        chain = self.get_chain(discard=discard, thin=thin)
+        block = derived_rows(self.vega, self.cols, self._fixed_row(), chain.reshape(-1, self.n), self.chunk, self.lanes,
+                             self.const_hint)
+        return block if flat else block.reshape(chain.shape[:2] + (block.shape[1],))
+
+    def write(self, path, name, derived=False, print_func=print):
+        """getdist's plain-text chain of the recorded rows (:func:`write_getdist`): ``name.txt`` and ``name.paramnames``;
+        ``derived``: with the derived parameters' columns and lines after the sampled ones."""
+        extra = derived_for_write(self, derived, print_func)
+        if extra:
+            extra['derived'] = self.get_derived(flat=True)
+        return write_getdist(path, name, self.names, self.get_chain(flat=True), self.get_log_lik(flat=True), **extra)
 
 
 # ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
@@ -463,7 +541,8 @@ _ENSEMBLE_DEFAULTS = dict(sampler='Ensemble', name='ensemble', walkers=None, ste
 def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
-    parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver}; with ``sampler = Nested`` the
+    parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver} and, when the section states it,
+    ``derived`` (True | False; absent means False: the chain files are what they were); with ``sampler = Nested`` the
     ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones
     (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
@@ -505,6 +584,8 @@ def sampler_settings(main_config, sample_params):
     out['init'] = sec.get('init', out['init'])
     out['init_scale'] = sec.getfloat('init_scale', out['init_scale'])
     out['driver'] = sec.get('driver', out['driver'])
+    if 'derived' in sec:
+        out['derived'] = parse_derived(sec)
     if out['init'] not in ('ball', 'prior'):
         raise ValueError("[Ensemble] init: 'ball' or 'prior'")
     if out['driver'] not in ('device', 'python'):
@@ -521,8 +602,8 @@ def sampler_settings(main_config, sample_params):
 def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwargs):
     """bin/run_vega_mpi.py for one process: initialise, compute the model once, switch to the Monte-Carlo mock when asked,
     require ``run_sampler = True`` and ``sampler = Ensemble``, ``Nested`` or ``SMC``, run the ``[Ensemble]`` / ``[Nested]`` /
-    ``[SMC]`` settings, write the getdist chain (a nested or SMC run also ``name.stats`` with the evidence).  Returns the
-    sampler."""
+    ``[SMC]`` settings, write the getdist chain (a nested or SMC run also ``name.stats`` with the evidence; with ``derived = True``
+    in the sampler's section the marginalisation coefficients as derived columns).  Returns the sampler."""
     from .interface import VegaInterface
     print_func('Initializing Vega')
     vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
@@ -559,6 +640,6 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwarg
         sampler = EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
                                   sample_params=sample_params)
         sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
-    sampler.write(cfg['path'], cfg['name'])
+    sampler.write(cfg['path'], cfg['name'], derived=cfg.get('derived', False), print_func=print_func)
     print_func('Finished running sampler')
     return sampler

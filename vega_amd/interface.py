@@ -536,6 +536,58 @@ class VegaInterface:
             current.wait_event(torch.cuda.ExternalStream(eng.last_stream_handle(), device=theta.device).record_event())
         return out
 
+    def derived_names(self):
+        """Names of the derived parameters a sampler run can store beside every point: ``<corr>_marg_<i>`` (reference
+        vega/samplers/sampler_interface.py:82-89), correlations sorted by name, a correlation's coefficients in template order
+        (the stacking of ``log_lik(..., return_marg_coeff=True)``, reference vega/vega_interface.py:371-383).  The count per
+        correlation is that of the returned vector, ``marg_diff2coeff.shape[0]``.  Empty without templates."""
+        return [f'{name}_marg_{i}' for name in sorted(self._marg_names)
+                for i in range(self.problem.items[name].marg_diff2coeff.shape[0])]
+
+    def derived_labels(self):
+        """LaTeX labels of :meth:`derived_names`, the reference's ``M_{\\rm <corr>}^{<i>}`` (sampler_interface.py:82-89)."""
+        from .ensemble import marg_derived_labels
+        return marg_derived_labels({name: self.problem.items[name].marg_diff2coeff.shape[0] for name in self._marg_names})[1]
+
+    def marg_coeff_batch_device(self, theta):
+        """The marginalisation coefficients of walkers that are already in HBM: ``theta`` as for :meth:`chi2_batch_device` ->
+        CUDA float64 tensor [n, len(derived_names())], columns in the order of :meth:`derived_names`, NaN in the rows of walkers
+        whose model failed.  Chunks of ``max_batch`` go through ``vmx_marg_coeff_device`` on the engine's stream, ordered after
+        the caller's current torch stream and before what it does next (events, no host synchronisation): the coefficients
+        come from the walker vectors of the chi2 path through the map folded at set-up, or, where the quadratic form does
+        not apply, from the full chain's residuals - one behaviour either way.  An engine group (mixed settings) has no
+        single handle and answers through its engines' host route."""
+        import torch
+        if not (theta.is_cuda and theta.dtype == torch.float64 and theta.dim() == 2 and theta.is_contiguous()
+                and theta.shape[1] == len(self.param_names)):
+            raise ValueError(f'theta: contiguous CUDA float64 tensor [n, {len(self.param_names)}]')
+        names = sorted(self._marg_names)
+        n = theta.shape[0]
+        if not names:
+            return torch.empty((n, 0), dtype=torch.float64, device=theta.device)
+        eng = self.engine
+        if not hasattr(eng, 'marg_coeff_device'):
+            coeff = self.chi2_batch(theta.cpu().numpy(), return_marg_coeff=True)[1]
+            return torch.from_numpy(np.hstack([coeff[name] for name in names])).to(theta.device)
+        if not self._metals_frozen:
+            self.freeze_metals(theta[0].cpu().numpy())
+        self._sync_monte_carlo()
+        layout, total = eng.marg_layout()
+        out = torch.empty((n, total), dtype=torch.float64, device=theta.device)
+        current = torch.cuda.current_stream(theta.device)
+        stream = torch.cuda.ExternalStream(eng.stream_handle(), device=theta.device)
+        stream.wait_event(current.record_event())
+        mb = eng.max_batch
+        for lo in range(0, n, mb):
+            hi = min(lo + mb, n)
+            eng.marg_coeff_device(theta[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr(), total)
+        current.wait_event(stream.record_event())
+        # the engine writes its items in their own order: the reference stacks the correlations sorted by name
+        cols = [c for name in names for c in range(layout[name][0], layout[name][0] + layout[name][1])]
+        if cols != list(range(total)):
+            out = out.index_select(1, torch.tensor(cols, dtype=torch.int64, device=theta.device))
+        return out
+
     def log_lik_batch(self, params_list):
         return self._log_norm() - 0.5 * self.chi2_batch(params_list)
 

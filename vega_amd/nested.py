@@ -516,16 +516,26 @@ class NestedSampler(NestedRun):
             chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop)
         return du, dl, dn, st
 
-    def write(self, path, name):
+    def derived(self):
+        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the rows of :meth:`samples`,
+        [N, m]: a pass over them after the run (:func:`vega_amd.ensemble.derived_rows`), the same block whichever driver ran."""
+        theta = np.asarray(self.vega._theta(None), dtype=np.float64)
+        return E.derived_rows(self.vega, self.cols, theta, self.samples()[0], self.chunk, self.lanes, self.const_hint)
+
+    def write(self, path, name, derived=False, print_func=print):
         """getdist's weighted chain ``name.txt`` (weight / max weight, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
-        ``name.paramnames`` and ``name.stats``."""
-        return write_run(self, path, name, self.names)
+        ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
+        ones."""
+        extra = E.derived_for_write(self, derived, print_func)
+        if extra:
+            extra['derived'] = self.derived()
+        return write_run(self, path, name, self.names, **extra)
 
 
 def nested_settings(main_config, sample_params):
     """The ``[Nested]`` settings of a main config with ``sampler = Nested`` (called by
     :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
-    precision, seed, threads, driver, max_iterations}.  ``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
+    precision, seed, threads, driver, max_iterations} and ``derived`` when the section states it.  ``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
     mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default."""
     import os
     if 'Nested' not in main_config:
@@ -545,6 +555,8 @@ def nested_settings(main_config, sample_params):
                num_repeats=sec.getint('num_repeats', 5 * n), precision=sec.getfloat('precision', 0.001),
                seed=sec.getint('seed', 0), threads=sec.getint('threads', None), driver=sec.get('driver', 'device'),
                max_iterations=sec.getint('max_iterations', None))
+    if 'derived' in sec:
+        out['derived'] = E.parse_derived(sec)
     if out['driver'] not in ('device', 'python'):
         raise ValueError("[Nested] driver: 'device' or 'python'")
     if not n + 2 <= out['num_live'] <= MAX_LIVE:
@@ -560,10 +572,11 @@ def nested_settings(main_config, sample_params):
     return out
 
 
-def write_run(run, path, name, names):
-    """The three files of a finished :class:`NestedRun`: (txt, paramnames, stats)."""
+def write_run(run, path, name, names, **derived):
+    """The three files of a finished :class:`NestedRun`: (txt, paramnames, stats); ``derived``: the derived-parameter arguments of
+    :func:`vega_amd.ensemble.write_getdist`."""
     pts, lnl, w = run.samples()
-    txt, pn = E.write_getdist(path, name, names, pts, lnl, weights=w / w.max())
+    txt, pn = E.write_getdist(path, name, names, pts, lnl, weights=w / w.max(), **derived)
     log_z, err = run.log_evidence()
     stats = Path(path) / f'{name}.stats'
     with open(stats, 'w') as f:

@@ -489,15 +489,26 @@ class SMCSampler(SMCRun):
                         total[key] += val
         return record, total or {}
 
-    def write(self, path, name):
+    def derived(self):
+        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the rows of :meth:`samples`,
+        [N, m]: a pass over them after the run (:func:`vega_amd.ensemble.derived_rows`), the same block whichever driver ran."""
+        theta = np.asarray(self.vega._theta(None), dtype=np.float64)
+        return E.derived_rows(self.vega, self.cols, theta, self.samples()[0], self.chunk, self.lanes, self.const_hint)
+
+    def write(self, path, name, derived=False, print_func=print):
         """getdist's chain ``name.txt`` (weight 1, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
-        ``name.paramnames`` and ``name.stats``."""
-        return write_run(self, path, name, self.names)
+        ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
+        ones."""
+        extra = E.derived_for_write(self, derived, print_func)
+        if extra:
+            extra['derived'] = self.derived()
+        return write_run(self, path, name, self.names, **extra)
 
 
 def smc_settings(main_config, sample_params):
     """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
-    has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}; ``sweeps`` None: 4 n."""
+    has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages} and ``derived`` when the section states it; ``sweeps``
+    None: 4 n."""
     import os
     if 'SMC' not in main_config:
         raise RuntimeError('run_sampler called, but no sampler config found')
@@ -515,6 +526,8 @@ def smc_settings(main_config, sample_params):
     out = dict(sampler='SMC', path=path, name=sec.get('name', 'smc'), particles=sec.getint('particles', 1024),
                ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None), seed=sec.getint('seed', 0),
                driver=sec.get('driver', 'device'), max_stages=sec.getint('max_stages', None))
+    if 'derived' in sec:
+        out['derived'] = E.parse_derived(sec)
     if out['driver'] not in ('device', 'python'):
         raise ValueError("[SMC] driver: 'device' or 'python'")
     if not 1 <= n <= MAXN:
@@ -530,10 +543,11 @@ def smc_settings(main_config, sample_params):
     return out
 
 
-def write_run(run, path, name, names):
-    """The three files of an :class:`SMCRun`: (txt, paramnames, stats)."""
+def write_run(run, path, name, names, **derived):
+    """The three files of an :class:`SMCRun`: (txt, paramnames, stats); ``derived``: the derived-parameter arguments of
+    :func:`vega_amd.ensemble.write_getdist`."""
     pts, lnl, _ = run.samples()
-    txt, pn = E.write_getdist(path, name, names, pts, lnl)
+    txt, pn = E.write_getdist(path, name, names, pts, lnl, **derived)
     log_z, err = run.log_evidence()
     stats = Path(path) / f'{name}.stats'
     with open(stats, 'w') as f:
