@@ -153,6 +153,22 @@ def write_getdist(path, name, names, chain, chain_lnl, weights=None, derived=Non
     (``derived_labels`` [m], default the names): derived parameters, their columns after the sampled ones and their lines after
     the sampled parameters' (the layout of the reference's PolyChord chains)."""
     path = Path(path)
+    table, lines = getdist_table(names, chain, chain_lnl, weights, derived, derived_names, derived_labels)
+    np.savetxt(path / f'{name}.txt', table, fmt='%.17g')
+    return path / f'{name}.txt', write_paramnames(path, name, lines)
+
+
+def write_paramnames(path, name, lines):
+    """``name.paramnames`` from (name, label) pairs."""
+    with open(Path(path) / f'{name}.paramnames', 'w') as f:
+        for nm, label in lines:
+            f.write(f'{nm} {label}\n')
+    return Path(path) / f'{name}.paramnames'
+
+
+def getdist_table(names, chain, chain_lnl, weights=None, derived=None, derived_names=None, derived_labels=None):
+    """(the rows of :func:`write_getdist`'s ``name.txt`` [samples, 2 + n (+ m)], the (name, label) pairs of its
+    ``name.paramnames``)."""
     chain = np.asarray(chain, dtype=np.float64).reshape(-1, len(names))
     lnl = np.asarray(chain_lnl, dtype=np.float64).reshape(-1)
     first = np.ones(lnl.size) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1)
@@ -168,11 +184,7 @@ def write_getdist(path, name, names, chain, chain_lnl, weights=None, derived=Non
             raise ValueError('derived: one row per sample, one name and one label per column')
         columns.append(block)
         lines += list(zip(derived_names, labels))
-    np.savetxt(path / f'{name}.txt', np.column_stack(columns), fmt='%.17g')
-    with open(path / f'{name}.paramnames', 'w') as f:
-        for nm, label in lines:
-            f.write(f'{nm} {label}\n')
-    return path / f'{name}.txt', path / f'{name}.paramnames'
+    return np.column_stack(columns), lines
 
 
 def marg_derived_labels(counts):
@@ -320,7 +332,8 @@ class EngineRows:
         import torch
         eng = self.eng
         self.saved_hint, self.saved_lanes = getattr(eng, 'nl_hint', 0), getattr(eng, 'lanes', 1)
-        self.device = torch.device('cuda', getattr(eng, 'device', 0))
+        own = getattr(eng, 'rows_device', None)          # (a stand-in engine without a GPU names where its rows live)
+        self.device = torch.device('cuda', getattr(eng, 'device', 0)) if own is None else torch.device(own)
         try:
             eng.set_constant_nl_hint(self.hint > 0, self.hint >= 2)
             if self.single and self.want_lanes > self.saved_lanes:
@@ -390,7 +403,8 @@ class EnsembleSampler:
 
     # ---- start
     def _start_positions(self, start, init_scale):
-        rng = np.random.default_rng(self.seed)
+        # (stream 0 draws what it always drew; another stream - a replica - starts from walkers of its own)
+        rng = np.random.default_rng(self.seed if self.stream == 0 else [self.seed, self.stream])
         if isinstance(start, str) and start == 'prior':
             return self.lo + (self.hi - self.lo) * rng.random((self.W, self.n))
         if isinstance(start, str) and start == 'ball':
@@ -442,7 +456,8 @@ class EnsembleSampler:
     def run(self, n_steps, start='ball', init_scale=1.0):
         """Advance the ensemble by ``n_steps`` steps (the first call draws the start: ``'ball'`` - the configured values plus
         init_scale x errors x N(0, 1), redrawn until inside the box - ``'prior'`` - uniform in the box - or an array [W, n]; both
-        draws from ``np.random.default_rng(seed)``).  Later calls continue the chain."""
+        draws from ``np.random.default_rng(seed)``, with a non-zero ``stream`` from ``default_rng([seed, stream])``).  Later
+        calls continue the chain."""
         theta = self._prepare(start, init_scale)
         done = 0
         while done < n_steps:
@@ -542,7 +557,8 @@ def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
     parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver} and, when the section states it,
-    ``derived`` (True | False; absent means False: the chain files are what they were); with ``sampler = Nested`` the
+    ``derived`` (True | False; absent means False: the chain files are what they were) and ``replicas`` (R >= 1 independent
+    copies on Philox streams 0 .. R - 1, merged afterwards: :mod:`vega_amd.replicas`); with ``sampler = Nested`` the
     ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones
     (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
@@ -586,6 +602,9 @@ def sampler_settings(main_config, sample_params):
     out['driver'] = sec.get('driver', out['driver'])
     if 'derived' in sec:
         out['derived'] = parse_derived(sec)
+    if 'replicas' in sec:
+        from .replicas import parse_replicas
+        out['replicas'] = parse_replicas(sec)
     if out['init'] not in ('ball', 'prior'):
         raise ValueError("[Ensemble] init: 'ball' or 'prior'")
     if out['driver'] not in ('device', 'python'):
@@ -599,14 +618,53 @@ def sampler_settings(main_config, sample_params):
     return out
 
 
-def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwargs):
-    """bin/run_vega_mpi.py for one process: initialise, compute the model once, switch to the Monte-Carlo mock when asked,
-    require ``run_sampler = True`` and ``sampler = Ensemble``, ``Nested`` or ``SMC``, run the ``[Ensemble]`` / ``[Nested]`` /
-    ``[SMC]`` settings, write the getdist chain (a nested or SMC run also ``name.stats`` with the evidence; with ``derived = True``
-    in the sampler's section the marginalisation coefficients as derived columns).  Returns the sampler."""
-    from .interface import VegaInterface
+def build_sampler(vega, cfg, sample_params, stream=0):
+    """The sampler the settings ``cfg`` (:func:`sampler_settings`) ask for, on the Philox stream ``stream``."""
+    if cfg['sampler'] == 'Nested':
+        from .nested import NestedSampler
+        return NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
+                             precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
+                             max_iterations=cfg['max_iterations'], sample_params=sample_params, stream=stream)
+    if cfg['sampler'] == 'SMC':
+        from .smc import SMCSampler
+        return SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],
+                          driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params, stream=stream)
+    return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
+                           sample_params=sample_params, stream=stream)
+
+
+def advance_sampler(sampler, cfg):
+    """Run a sampler of :func:`build_sampler` as its settings say: the ensemble its steps, the others to their end."""
+    if cfg['sampler'] in ('Nested', 'SMC'):
+        return sampler.run()
+    return sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
+
+
+def run_vega_sampler(config_path, search_dirs=(), print_func=print, rank=None, world_size=None, make_vega=None, **vega_kwargs):
+    """bin/run_vega_mpi.py: initialise, compute the model once, switch to the Monte-Carlo mock when asked, require
+    ``run_sampler = True`` and ``sampler = Ensemble``, ``Nested`` or ``SMC``, run the ``[Ensemble]`` / ``[Nested]`` / ``[SMC]``
+    settings, write the getdist chain (a nested or SMC run also ``name.stats`` with the evidence; with ``derived = True`` in the
+    sampler's section the marginalisation coefficients as derived columns).  Returns the sampler.
+
+    One process per GPU: ``rank`` / ``world_size`` (default: ``RANK`` / ``WORLD_SIZE`` / ``LOCAL_RANK`` of the environment, as
+    torchrun sets them; one process without them) share out the ``replicas = R`` of the sampler's section
+    (:mod:`vega_amd.replicas`); the device is ``LOCAL_RANK % torch.cuda.device_count()``, chosen before anything touches the GPU.
+    With R > 1 every rank returns a :class:`vega_amd.replicas.ReplicaRun` and rank 0 writes the merged files; without the key
+    (or with R = 1) the files are those of one plain run, written by rank 0, and the other ranks return None.
+    ``make_vega(config_path, device)`` may replace the interface (CPU tests of the body)."""
+    from . import replicas
+    rank, world, local_rank = replicas.ranks_from_environment(rank, world_size)
+    if world > 1 or 'LOCAL_RANK' in os.environ:
+        vega_kwargs.setdefault('device', replicas.device_of(local_rank))
+    group = replicas.Group(rank, world)
+    if rank > 0:
+        print_func = _silent
     print_func('Initializing Vega')
-    vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
+    if make_vega is None:
+        from .interface import VegaInterface
+        vega = VegaInterface(config_path, search_dirs=search_dirs, **vega_kwargs)
+    else:
+        vega = make_vega(config_path, vega_kwargs.get('device', 0))
     sample_params = vega.sample_params
     _ = vega.compute_model(run_init=False)
     print_func('Finished initializing Vega')
@@ -618,28 +676,25 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, **vega_kwarg
     elif run_montecarlo:
         raise ValueError('You asked to run over a Monte Carlo simulation, but no "[monte carlo]" section provided.')
     cfg = sampler_settings(vega.main_config, sample_params)
-    if cfg['sampler'] == 'Nested':
-        from .nested import NestedSampler
-        print_func('Running the nested sampler')
-        sampler = NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
-                                precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
-                                max_iterations=cfg['max_iterations'], sample_params=sample_params)
-        sampler.run()
-        log_z, err = sampler.log_evidence()
-        print_func(f'log(Z) = {log_z} +- {err}')
-    elif cfg['sampler'] == 'SMC':
-        from .smc import SMCSampler
-        print_func('Running the SMC sampler')
-        sampler = SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],
-                             driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params)
-        sampler.run()
-        log_z, err = sampler.log_evidence()
-        print_func(f'log(Z) = {log_z} +- {err}')
-    else:
-        print_func('Running the ensemble sampler')
-        sampler = EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
-                                  sample_params=sample_params)
-        sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
-    sampler.write(cfg['path'], cfg['name'], derived=cfg.get('derived', False), print_func=print_func)
+    kind = {'Nested': 'nested', 'SMC': 'SMC'}.get(cfg['sampler'], 'ensemble')
+    if cfg.get('replicas', 1) > 1:
+        print_func(f'Running {cfg["replicas"]} replicas of the {kind} sampler on {world} rank(s)')
+        out = replicas.run_replicas(vega, cfg, sample_params, group, print_func)
+        print_func(out.summary())
+        print_func('Finished running sampler')
+        return out
+    sampler = None
+    if rank == 0:           # (one run: the files of today, by the path of today)
+        print_func(f'Running the {kind} sampler')
+        sampler = advance_sampler(build_sampler(vega, cfg, sample_params), cfg)
+        if hasattr(sampler, 'log_evidence'):
+            log_z, err = sampler.log_evidence()
+            print_func(f'log(Z) = {log_z} +- {err}')
+        sampler.write(cfg['path'], cfg['name'], derived=cfg.get('derived', False), print_func=print_func)
+    group.barrier()
     print_func('Finished running sampler')
     return sampler
+
+
+def _silent(*args, **kwargs):
+    pass

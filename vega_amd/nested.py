@@ -535,7 +535,7 @@ class NestedSampler(NestedRun):
 def nested_settings(main_config, sample_params):
     """The ``[Nested]`` settings of a main config with ``sampler = Nested`` (called by
     :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
-    precision, seed, threads, driver, max_iterations} and ``derived`` when the section states it.  ``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
+    precision, seed, threads, driver, max_iterations}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them.``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
     mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default."""
     import os
     if 'Nested' not in main_config:
@@ -557,6 +557,9 @@ def nested_settings(main_config, sample_params):
                max_iterations=sec.getint('max_iterations', None))
     if 'derived' in sec:
         out['derived'] = E.parse_derived(sec)
+    if 'replicas' in sec:
+        from .replicas import parse_replicas
+        out['replicas'] = parse_replicas(sec)
     if out['driver'] not in ('device', 'python'):
         raise ValueError("[Nested] driver: 'device' or 'python'")
     if not n + 2 <= out['num_live'] <= MAX_LIVE:

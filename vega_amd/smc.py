@@ -507,7 +507,7 @@ class SMCSampler(SMCRun):
 
 def smc_settings(main_config, sample_params):
     """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
-    has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages} and ``derived`` when the section states it; ``sweeps``
+    has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them; ``sweeps``
     None: 4 n."""
     import os
     if 'SMC' not in main_config:
@@ -528,6 +528,9 @@ def smc_settings(main_config, sample_params):
                driver=sec.get('driver', 'device'), max_stages=sec.getint('max_stages', None))
     if 'derived' in sec:
         out['derived'] = E.parse_derived(sec)
+    if 'replicas' in sec:
+        from .replicas import parse_replicas
+        out['replicas'] = parse_replicas(sec)
     if out['driver'] not in ('device', 'python'):
         raise ValueError("[SMC] driver: 'device' or 'python'")
     if not 1 <= n <= MAXN:
