@@ -59,3 +59,41 @@ def test_two_lanes_equal_one_lane_bitwise(tag, batch):
     for a, b, c in zip(two, ref, one):
         assert torch.equal(a, b) and not torch.equal(a, c)
     vega.close()
+
+
+@pytest.mark.parametrize('kind', ['ensemble', 'smc'])
+def test_an_evaluation_of_a_main_lane_chunk_a_second_lane_chunk_and_a_ragged_tail(kind, monkeypatch):
+    """The shared evaluate of the device drivers where its three chunk kinds meet after a rows-ready event was published:
+    max_batch = 256, chunk = 64, two lanes, 160 rows per evaluation = 64 (main lane) + 64 (second lane) + 32 (below the 64-row
+    floor of two lanes: it waits for the lane and runs on the main stream).  The two drivers that publish the event: the
+    ensemble sampler (320 walkers, halves of 160, 3 steps) and SMC (160 particles, 3 sweeps, 1 stage)."""
+    import test_ensemble_gpu as TE
+    import test_smc_gpu as TS
+    from vega_amd import EnsembleSampler, SMCSampler, VegaInterface
+    vega = VegaInterface(None, problem=synth_joint_problem(), max_batch=256)
+    try:
+        sp = TE._sample_params(vega, TE.AUTO_SAMPLED)
+        if kind == 'ensemble':
+            whole = EnsembleSampler(vega, 320, seed=7, sample_params=sp, chunk=0, lanes=2).run(3)
+            seen = []       # (the sampler's own statistics do not carry the lanes: the engine's do)
+            run = vega.engine.ensemble_run
+            monkeypatch.setattr(vega.engine, 'ensemble_run', lambda *a, **k: seen.append(run(*a, **k)) or seen[-1])
+            dev, py = TE._pair(vega, 320, 3, sp, chunk=64, lanes=2)
+            TE._assert_same(dev, py)
+            assert [st['lanes'] for _, _, st in seen] == [2]
+            assert dev.stats['engine_calls'] == py.stats['engine_calls'] == 3 * (3 * 2)
+            assert whole.stats['engine_calls'] == 3 * 2
+            assert np.array_equal(dev.get_chain(), whole.get_chain()) and np.array_equal(dev.accepted, whole.accepted)
+            np.testing.assert_allclose(dev.get_log_lik(), whole.get_log_lik(), rtol=1e-12, atol=0)
+        else:
+            kw = dict(particles=160, sweeps=3, seed=3)
+            whole = SMCSampler(vega, sample_params=sp, chunk=0, lanes=2, **kw).run(stages=1)
+            dev, py = TS._pair(vega, sp, 1, chunk=64, lanes=2, **kw)
+            TS._assert_same(dev, py)
+            assert dev.stage == 1 and dev.stats['lanes'] == 2
+            assert dev.stats['engine_calls'] == py.stats['engine_calls'] == 3 * (1 + 3)
+            assert whole.stats['engine_calls'] == 1 + 3
+            assert np.array_equal(dev.u, whole.u) and dev.stage == whole.stage
+            np.testing.assert_allclose(dev.lnl, whole.lnl, rtol=1e-12, atol=0)
+    finally:
+        vega.close()

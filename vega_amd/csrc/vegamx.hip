@@ -161,34 +161,68 @@ struct FitWorkspace {
     DevBuf<int32_t> oflags[vmx_migrad::MAX_STAGES], oiter[vmx_migrad::MAX_STAGES];
     DevBuf<int64_t> onfcn[vmx_migrad::MAX_STAGES];
     int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round, fits still running
-    hipEvent_t ev_lane = nullptr;
     std::vector<hipEvent_t> ev_gap;                                   // pairs around the host's turn of a round (GPU idle time)
     ~FitWorkspace() {
         if (pin_word) (void)hipHostFree(pin_word);
-        if (ev_lane) (void)hipEventDestroy(ev_lane);
         for (auto& ev : ev_gap) (void)hipEventDestroy(ev);
     }
 };
 template <typename T>
 static int ensure(DevBuf<T>& b, size_t count) { return b.n >= count && b.p ? 0 : b.alloc(count, false); }
 
+// What the three samplers share: the engine's rows and its answers, the fixed row and the sampled box, grown on demand
+struct BoxDev {
+    double* theta; const double* chi2; const int32_t* status;                   // the engine's rows [rows][P] and its answers [rows]
+    const double* fixed; const int32_t* inv; const double* lo; const double* hi;    // inv[p]: sampled index of column p, or -1
+};
+struct BoxWorkspace {
+    DevBuf<double> theta, chi2, fixed, lo, hi;
+    DevBuf<int32_t> status, inv;
+    // room for `rows` rows of P columns; the fixed row, the box of the n sampled columns and their places go up on `st`
+    int upload(size_t rows, int P, int n, const double* h_fixed, const double* h_lo, const double* h_hi, const std::vector<int32_t>& h_inv,
+               hipStream_t st, BoxDev& D)
+    {
+        if (ensure(theta, rows * P) || ensure(chi2, rows) || ensure(status, rows) || ensure(fixed, P) || ensure(inv, P) || ensure(lo, n) ||
+            ensure(hi, n)) return -2;
+        HIP_OK(hipMemcpyAsync(fixed.p, h_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(inv.p, h_inv.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(lo.p, h_lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(hi.p, h_hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+        D = BoxDev{theta.p, chi2.p, status.p, fixed.p, inv.p, lo.p, hi.p};
+        return 0;
+    }
+};
+
+// The engine's rows out of the unit cube: the fixed row with the sampled columns mapped into the box, u(r, d) the cube coordinate
+// d of row r (a lane keeps its column: what the column needs is read once, the rows go round the waves)
+template <int THREADS, typename U>
+__device__ inline void write_cube_rows(const BoxDev& B, int P, int rows, U u)
+{
+    for (int p = threadIdx.x % 64; p < P; p += 64) {
+        const int d = B.inv[p];
+        const double fixed = B.fixed[p], lo = d < 0 ? 0.0 : B.lo[d], hi = d < 0 ? 0.0 : B.hi[d];
+#pragma unroll 4
+        for (int r = threadIdx.x / 64; r < rows; r += THREADS / 64) {
+            double v = fixed;
+            if (d >= 0) v = vmx_ns::map_cube(lo, hi, u(r, d));
+            B.theta[(size_t)r * P + p] = v;
+        }
+    }
+}
+
 // Ensemble sampling (vmx_ensemble_run): the walkers' state, the proposals of a half and the chain record, grown on demand
 struct EnsWorkspace {
-    DevBuf<double> x, lnl, prop, factor, theta, chi2, fixed, lo, hi, chain, chain_lnl;
+    BoxWorkspace box;
+    DevBuf<double> x, lnl, prop, factor, chain, chain_lnl;
     DevBuf<int64_t> acc, n_box, n_fail;
-    DevBuf<int32_t> inside, status, col;
-    hipEvent_t ev_prop = nullptr, ev_lane = nullptr;
-    ~EnsWorkspace() {
-        if (ev_prop) (void)hipEventDestroy(ev_prop);
-        if (ev_lane) (void)hipEventDestroy(ev_lane);
-    }
+    DevBuf<int32_t> inside, col;
 };
 
 struct EnsDev {
     double* x; double* lnl; int64_t* acc; int64_t* n_box; int64_t* n_fail;      // [W][n], [W], [W] x 3
     double* prop; double* factor; int32_t* inside;                              // the active half's proposals [H][n], [H], [H]
-    double* theta; const double* chi2; const int32_t* status;                   // the engine's rows [H][P] and its answers [H]
-    const double* fixed; const int32_t* col; const double* lo; const double* hi;
+    BoxDev box;                                                                 // rows [H][P]
+    const int32_t* col;                                                         // (a walker writes its own row: the sampled columns listed)
     double* chain; double* chain_lnl;                                           // [rows][W][n], [rows][W] (nullptr: not kept)
     int32_t W, n, P, thin;
     double a, log_norm;
@@ -207,8 +241,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_de
         for (int k = threadIdx.x; k < H; k += blockDim.x) {
             const int w = h_dec * H + k;
             const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, D.stream);
-            const double c2 = D.chi2[k];
-            const bool inside = D.inside[k] != 0, ok = vmx_ens::model_ok(D.status[k], c2);
+            const double c2 = D.box.chi2[k];
+            const bool inside = D.inside[k] != 0, ok = vmx_ens::model_ok(D.box.status[k], c2);
             const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
             if (vmx_ens::accept(inside, ok, D.factor[k], lnl_new, D.lnl[w], b.w[2])) {
                 for (int d = 0; d < n; ++d) D.x[(size_t)w * n + d] = D.prop[(size_t)k * n + d];
@@ -240,31 +274,30 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_de
         for (int d = 0; d < n; ++d) {
             const double v = vmx_ens::propose(c[d], s[d], z);
             y[d] = v;
-            in = in && v >= D.lo[d] && v <= D.hi[d];
+            in = in && v >= D.box.lo[d] && v <= D.box.hi[d];
         }
         D.factor[k] = vmx_ens::log_factor(n, z);
         D.inside[k] = in ? 1 : 0;
         // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
-        double* row = D.theta + (size_t)k * D.P;
-        for (int p = 0; p < D.P; ++p) row[p] = D.fixed[p];
+        double* row = D.box.theta + (size_t)k * D.P;
+        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
         for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
     }
 }
 
 // Nested sampling (vmx_nested_run): live points, the threads' state machines, the rows of a round and the dead record
 struct NsWorkspace {
-    DevBuf<double> live_u, live_lnl, mean, cov, chol, lstar, dead_u, dead_lnl, theta, chi2, fixed, lo, hi;
+    BoxWorkspace box;
+    DevBuf<double> live_u, live_lnl, mean, cov, chol, lstar, dead_u, dead_lnl;
     DevBuf<double> th;                  // [K] vmx_ns::Thread
-    DevBuf<int32_t> rank, surv, killed, slot, dead_n, status, inv;
+    DevBuf<int32_t> rank, surv, killed, slot, dead_n;
     DevBuf<int64_t> counters;
     int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round
     double* pin_lnl = nullptr; double* dpin_lnl = nullptr;           // ... and, when an iteration ends, live lnL [nlive] + dead lnL [K]
     size_t pin_lnl_n = 0;
-    hipEvent_t ev_lane = nullptr;
     ~NsWorkspace() {
         if (pin_word) (void)hipHostFree(pin_word);
         if (pin_lnl) (void)hipHostFree(pin_lnl);
-        if (ev_lane) (void)hipEventDestroy(ev_lane);
     }
 };
 
@@ -274,8 +307,7 @@ struct NsDev {
     double* mean; double* cov; double* chol; double* lstar; // [n], [n][n], [n][n], [1]
     vmx_ns::Thread* th; int32_t* slot;                      // [K]: the machines, and the row of each one's last request (-1: none)
     double* dead_u; double* dead_lnl; int32_t* dead_n;      // the call's record [iterations][K] ([n])
-    double* theta; const double* chi2; const int32_t* status;       // the engine's rows and its answers
-    const double* fixed; const int32_t* inv; const double* lo; const double* hi;    // inv[p]: sampled index of column p, or -1
+    BoxDev box;
     int32_t* host_word; double* host_lnl; int64_t* counters;        // counters[0]: rows that were a thread's own position
     int32_t nlive, K, n, P, num_repeats;
     double log_norm;
@@ -289,15 +321,12 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_draw_live(NsDev D)
 {
     for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) vmx_ns::draw_live(i, D.n, D.seed, D.stream, D.live_u + (size_t)i * D.n);
     __syncthreads();
-    for (int q = threadIdx.x; q < D.nlive * D.P; q += blockDim.x) {
-        const int i = q / D.P, p = q % D.P, d = D.inv[p];
-        D.theta[q] = d < 0 ? D.fixed[p] : vmx_ns::map_cube(D.lo[d], D.hi[d], D.live_u[(size_t)i * D.n + d]);
-    }
+    write_cube_rows<NS_THREADS>(D.box, D.P, D.nlive, [&](int r, int d) { return D.live_u[(size_t)r * D.n + d]; });
 }
 
 __global__ __launch_bounds__(NS_THREADS) void k_ns_live_lnl(NsDev D)
 {
-    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.live_lnl[i] = vmx_ns::lnl_of(D.status[i], D.chi2[i], D.log_norm);
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.live_lnl[i] = vmx_ns::lnl_of(D.box.status[i], D.box.chi2[i], D.log_norm);
 }
 
 // The head of iteration `it` (record row `rec` of this call) in one work-group: rank the live points by counting, append the K
@@ -369,7 +398,7 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
         vmx_ns::Thread& T = D.th[k];
         if (T.state == vmx_ns::S_DONE) continue;
         const int row = D.slot[k];
-        const double answer = row >= 0 ? vmx_ns::lnl_of(D.status[row], D.chi2[row], D.log_norm) : -INFINITY;
+        const double answer = row >= 0 ? vmx_ns::lnl_of(D.box.status[row], D.box.chi2[row], D.log_norm) : -INFINITY;
         if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
     }
     s_scan[threadIdx.x] = mine;
@@ -395,20 +424,10 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
     }
     if (own) atomicAdd((unsigned long long*)D.counters, (unsigned long long)own);
     __syncthreads();
-    // (a lane keeps its column: what the column needs is read once, the rows go round the waves)
-    for (int p = threadIdx.x % 64; p < P; p += 64) {
-        const int d = D.inv[p];
-        const double fixed = D.fixed[p], lo = d < 0 ? 0.0 : D.lo[d], hi = d < 0 ? 0.0 : D.hi[d];
-#pragma unroll 4
-        for (int r = threadIdx.x / 64; r < total; r += NS_THREADS / 64) {
-            double v = fixed;
-            if (d >= 0) {
-                const vmx_ns::Thread& T = D.th[s_row_thread[r]];
-                v = vmx_ns::map_cube(lo, hi, T.inside ? T.y[d] : T.x[d]);
-            }
-            D.theta[(size_t)r * P + p] = v;
-        }
-    }
+    write_cube_rows<NS_THREADS>(D.box, P, total, [&](int r, int d) {
+        const vmx_ns::Thread& T = D.th[s_row_thread[r]];
+        return T.inside ? T.y[d] : T.x[d];
+    });
     if (total == 0) {
         for (int k = threadIdx.x; k < K; k += blockDim.x) {
             const int i = D.killed[k];
@@ -425,16 +444,12 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
 
 // Tempered SMC (vmx_smc_run): the particles, their proposals, the weights of a stage, the rows of a sweep and the stage record
 struct SmcWorkspace {
-    DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, theta, chi2, fixed, lo, hi, rec, rec_lnl;
-    DevBuf<int32_t> inside, status, inv, zero, rec_anc;
+    BoxWorkspace box;
+    DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, rec, rec_lnl;
+    DevBuf<int32_t> inside, zero, rec_anc;
     DevBuf<int64_t> counters;
     double* pin = nullptr; double* dpin = nullptr;          // mapped host memory: beta, accepted, scale of the stage; the start's count
-    hipEvent_t ev_prop = nullptr, ev_lane = nullptr;
-    ~SmcWorkspace() {
-        if (pin) (void)hipHostFree(pin);
-        if (ev_prop) (void)hipEventDestroy(ev_prop);
-        if (ev_lane) (void)hipEventDestroy(ev_lane);
-    }
+    ~SmcWorkspace() { if (pin) (void)hipHostFree(pin); }
 };
 
 struct SmcDev {
@@ -444,8 +459,7 @@ struct SmcDev {
     double* mean; double* cov; double* chol;                        // [n], [n][n], [n][n]
     double* state;                                                  // [0] beta, [1] scale
     double* prop; double* uacc; int32_t* inside;                    // the sweep's proposals [N][n], deciding uniforms [N], in the cube [N]
-    double* theta; const double* chi2; const int32_t* status;       // the engine's rows [N][P] and its answers
-    const double* fixed; const int32_t* inv; const double* lo; const double* hi;    // inv[p]: sampled index of column p, or -1
+    BoxDev box;                                                     // rows [N][P]
     double* rec; double* rec_lnl; int32_t* rec_anc;                 // the call's record [stages][VMX_SMC_REC], [stages][N], [stages][N]
     int64_t* counters;                                              // the stage's accepted, own-position rows, failed models
     double* host;                                                   // mapped: [0] beta_t, [1] accepted, [2] scale, [3] finite start lnL
@@ -457,21 +471,13 @@ struct SmcDev {
 constexpr int SMC_THREADS = vmx_smc::LANES;
 constexpr int SMC_PER = vmx_smc::MAX_PARTICLES / SMC_THREADS;
 
-// the rows of the engine: the fixed row with the sampled columns mapped out of the cube, from the proposal where it lies inside
-// and from the particle's own position elsewhere (a lane keeps its column, the rows go round the waves)
+// the rows of the engine: from the proposal where it lies inside the cube and from the particle's own position elsewhere
 __device__ inline void smc_write_rows(const SmcDev& D, bool proposals)
 {
-    const int n = D.n, P = D.P;
-    for (int p = threadIdx.x % 64; p < P; p += 64) {
-        const int d = D.inv[p];
-        const double fixed = D.fixed[p], lo = d < 0 ? 0.0 : D.lo[d], hi = d < 0 ? 0.0 : D.hi[d];
-#pragma unroll 4
-        for (int r = threadIdx.x / 64; r < D.N; r += SMC_THREADS / 64) {
-            double v = fixed;
-            if (d >= 0) v = vmx_ns::map_cube(lo, hi, proposals && D.inside[r] ? D.prop[(size_t)r * n + d] : D.u[(size_t)r * n + d]);
-            D.theta[(size_t)r * P + p] = v;
-        }
-    }
+    const int n = D.n;
+    write_cube_rows<SMC_THREADS>(D.box, D.P, D.N, [&](int r, int d) {
+        return proposals && D.inside[r] ? D.prop[(size_t)r * n + d] : D.u[(size_t)r * n + d];
+    });
 }
 
 // the start particles: u from the Philox blocks (i, 0, j, 5), beta = 0, the start scale, and their rows for the engine
@@ -489,7 +495,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcDev D)
     if (threadIdx.x == 0) s_finite = 0;
     __syncthreads();
     for (int i = threadIdx.x; i < D.N; i += blockDim.x) {
-        const double v = vmx_ns::lnl_of(D.status[i], D.chi2[i], D.log_norm);
+        const double v = vmx_ns::lnl_of(D.box.status[i], D.box.chi2[i], D.log_norm);
         D.lnl[i] = v;
         if (v > -INFINITY) atomicAdd(&s_finite, 1);
     }
@@ -648,9 +654,9 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stag
         const double beta = D.state[0];
         int acc = 0, own = 0, failed = 0;
         for (int i = tid; i < N; i += SMC_THREADS) {
-            const double c2 = D.chi2[i];
-            const bool inside = D.inside[i] != 0, ok = vmx_ens::model_ok(D.status[i], c2);
-            const double lnl_new = vmx_ns::lnl_of(D.status[i], c2, D.log_norm);
+            const double c2 = D.box.chi2[i];
+            const bool inside = D.inside[i] != 0, ok = vmx_ens::model_ok(D.box.status[i], c2);
+            const double lnl_new = vmx_ns::lnl_of(D.box.status[i], c2, D.log_norm);
             if (vmx_smc::accept(inside, ok, beta, lnl_new, D.lnl[i], D.uacc[i])) {
                 for (int c = 0; c < n; ++c) D.u[(size_t)i * n + c] = D.prop[(size_t)i * n + c];
                 D.lnl[i] = lnl_new;
@@ -712,7 +718,10 @@ struct vmx_engine {
     EnsWorkspace* ensws = nullptr;
     NsWorkspace* nsws = nullptr;
     SmcWorkspace* smcws = nullptr;
-    hipEvent_t lane_wait = nullptr;         // vmx_ensemble_run: the rows of the second lane's calls are complete at this event
+    // a likelihood session (vmx_fit_migrad and the three samplers): lane_wait, when set, is the event at which the rows of the second
+    // lane's calls are complete (its stream waits for it); ev_rows is the session's event for that, ev_lane the one that joins the
+    // second lane back to `stream`.  Both are made on first use.
+    hipEvent_t lane_wait = nullptr, ev_rows = nullptr, ev_lane = nullptr;
 
     int nk = 0, nkp = 0, n_mu = 0;
     int n_rows = 0, n_extra = 0, mu_lo = 0, mu_hi = 0;     // node rule of the mu sums (vmx_set_mu_quadrature)
@@ -881,6 +890,8 @@ struct vmx_engine {
         for (auto& a : aux) (void)hipStreamDestroy(a);
         for (auto& ev : ev_join) (void)hipEventDestroy(ev);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_rows) (void)hipEventDestroy(ev_rows);
+        if (ev_lane) (void)hipEventDestroy(ev_lane);
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -3643,7 +3654,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
-    L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->call_mock = nullptr;
+    L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->ev_rows = nullptr; L->ev_lane = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
     L->graphs.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
     L->pin_theta = nullptr; L->pin_chi2 = nullptr; L->pin_status = nullptr; L->pin_done = nullptr; L->pin_part = nullptr;
@@ -3815,6 +3826,93 @@ int vmx_derived_const_hint(vmx_engine* e, const int32_t* varies)
     return derived_const_hint(e, v);
 }
 
+namespace {
+
+// The engine as one call's likelihood (vmx_fit_migrad and the three samplers): chi2-only device evaluations of a driver's rows,
+// eager launches, in chunks, two lanes when the quadratic form serves them, at the table level the caller states or the columns
+// that vary allow.  Open it once every argument has been checked; however the call ends, the engine is then as it was.
+struct LikelihoodSession {
+    vmx_engine* e;
+    int hint, chunk, lanes;                 // what the call runs with (the stats report them)
+    int saved_hint, saved_lanes;
+    bool saved_ring;
+    // the three option integers of a call (the samplers refuse a negative chunk or lanes, the fits read them as "default")
+    static int check(const std::string& fn, int hint, int chunk, int lanes, bool refuse_negative)
+    {
+        REQUIRE(hint >= -1 && hint <= 2, fn + ": const_hint -1 (derive it), 0, 1 or 2");
+        REQUIRE(!refuse_negative || (chunk >= 0 && lanes >= 0), fn + ": chunk, lanes");
+        return 0;
+    }
+    // hint -1: derived from `varies`; chunk <= 0: default_chunk; lanes <= 0: 2
+    LikelihoodSession(vmx_engine* e_, int hint_, int chunk_, int lanes_, int default_chunk, const std::vector<char>& varies)
+        : e(e_), hint(hint_ < 0 ? derived_const_hint(e_, varies) : hint_),
+          chunk(std::max(1, std::min(chunk_ > 0 ? chunk_ : default_chunk, e_->max_batch))),
+          saved_hint(e_->const_hint), saved_lanes(e_->n_lanes), saved_ring(e_->ring_allowed)
+    {
+        const int want = lanes_ > 0 ? std::min(lanes_, VMX_MAX_LANES) : 2;
+        e->const_hint = hint;
+        if (want > e->n_lanes) { e->n_lanes = want; e->ring_allowed = false; }
+        e->lane_calls = 0;
+        lanes = e->n_lanes;
+    }
+    LikelihoodSession(const LikelihoodSession&) = delete;
+    ~LikelihoodSession()
+    {
+        wait_lane(e);
+        e->lane_wait = nullptr;
+        e->const_hint = saved_hint; e->n_lanes = saved_lanes; e->ring_allowed = saved_ring; e->lane_calls = 0;
+        e->last_stream = e->stream;
+    }
+    // The engine's chain over the first `total` rows of `theta` into chi2 / status (mock: the rows' mocks, or nullptr); e->stream then
+    // waits for the second lane, so that the driver's next kernel reads every chunk's answer.  rows_from_kernel: a kernel on
+    // e->stream wrote the rows and the host has not waited since, so the second lane's stream waits for them at lane_wait;
+    // otherwise nothing is recorded and nothing waits unless the lane ran.  Returns the engine calls made, negative on failure.
+    int evaluate(const double* theta, int total, double* chi2, int32_t* status, const int32_t* mock, bool rows_from_kernel)
+    {
+        hipStream_t st = e->stream, lane_stream = nullptr;
+        if (rows_from_kernel) {
+            if (!e->ev_rows) HIP_OK(hipEventCreateWithFlags(&e->ev_rows, hipEventDisableTiming));
+            HIP_OK(hipEventRecord(e->ev_rows, st));
+            e->lane_wait = e->ev_rows;
+        }
+        int calls = 0;
+        for (int off = 0; off < total; off += chunk, ++calls) {
+            const int B = std::min(chunk, total - off);
+            if (eval_device_impl(e, theta + (size_t)off * e->n_params, B, chi2 + off, nullptr, status + off, mock ? mock + off : nullptr, true)) return -2;
+            if (e->last_stream != st) lane_stream = e->last_stream;
+        }
+        if (lane_stream) {
+            if (!e->ev_lane) HIP_OK(hipEventCreateWithFlags(&e->ev_lane, hipEventDisableTiming));
+            HIP_OK(hipEventRecord(e->ev_lane, lane_stream));
+            HIP_OK(hipStreamWaitEvent(st, e->ev_lane, 0));
+        }
+        return calls;
+    }
+};
+
+// The sampled box of the three samplers (fn: the caller, for the messages): n of the engine's columns, none twice, each with
+// finite limits lo < hi, beside the fixed row and a finite log_norm.  varies[p]: column p is sampled; inv[p]: as which, or -1.
+extern "C++" template <typename Spec>      // (the three specs start alike; this stretch of the file has C linkage)
+static int check_box(const std::string& fn, const vmx_engine* e, const Spec* spec, int max_n, std::vector<char>& varies, std::vector<int32_t>& inv)
+{
+    const int P = e->n_params;
+    REQUIRE(spec->n_params == P && spec->theta_fixed && spec->col && spec->lo && spec->hi, fn + ": parameter columns, limits and the fixed row");
+    REQUIRE(spec->n >= 1 && spec->n <= max_n, fn + ": 1 .. " + std::to_string(max_n) + " sampled columns");
+    varies.assign(P, 0);
+    inv.assign(P, -1);
+    for (int i = 0; i < spec->n; ++i) {
+        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, fn + ": parameter column");
+        REQUIRE(!varies[spec->col[i]], fn + ": a column is listed twice");
+        varies[spec->col[i]] = 1;
+        inv[spec->col[i]] = i;
+        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], fn + ": limits");
+    }
+    REQUIRE(std::isfinite(spec->log_norm), fn + ": log_norm");
+    return 0;
+}
+
+}  // namespace
+
 int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, const double* theta0, const int32_t* mock_row,
                    const vmx_fit_options* opt, vmx_fit_result* results, vmx_fit_stats* stats)
 {
@@ -3856,19 +3954,16 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     else if (mock_row)
         for (int f = 0; f < n_fits; ++f)
             for (auto* it : e->items) REQUIRE(mock_row[f] < 0 || mock_row[f] < it->n_mocks, "vmx_fit_migrad: mock row exceeds the pool");
-    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : 512, e->max_batch));
-    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
-    int hint = opt ? opt->const_hint : -1;
-    REQUIRE(hint >= -1 && hint <= 2, "vmx_fit_migrad: const_hint -1 (derive it), 0, 1 or 2");
-    if (hint < 0) {
+    const int opt_hint = opt ? opt->const_hint : -1;
+    if (LikelihoodSession::check("vmx_fit_migrad", opt_hint, 0, 0, false)) return -1;
+    std::vector<char> varies(e->n_params, 0);
+    if (opt_hint < 0) {
         // a column varies when a stage frees it or the fits' rows differ in it
-        std::vector<char> varies(e->n_params, 0);
         for (int s = 0; s < spec->n_stages; ++s)
             for (int i = 0; i < spec->stage[s].n; ++i) varies[spec->stage[s].col[i]] = 1;
         for (int f = 1; f < n_fits; ++f)
             for (int c = 0; c < e->n_params; ++c)
                 if (theta0[(size_t)f * e->n_params + c] != theta0[c]) varies[c] = 1;
-        hint = derived_const_hint(e, varies);
     }
     HIP_OK(hipSetDevice(e->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -3919,7 +4014,6 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     if (!W.pin_word) {
         HIP_OK(hipHostMalloc((void**)&W.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
         HIP_OK(hipHostGetDevicePointer((void**)&W.dpin_word, W.pin_word, 0));
-        HIP_OK(hipEventCreateWithFlags(&W.ev_lane, hipEventDisableTiming));
     }
     hipStream_t st = e->stream;
     HIP_OK(hipMemsetAsync(W.state.p, 0, (size_t)F * state_bytes, st));       // (all zeros = a fit at its start)
@@ -3936,16 +4030,9 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     D.count = W.count.p; D.offset = W.offset.p; D.done = W.done.p; D.theta = W.theta.p; D.mock = W.mock.p; D.chi2 = W.chi2.p;
     D.host_word = W.dpin_word; D.F = F; D.P = P; D.admitted = ms ? 0 : F;
 
-    // the engine as the fits' objective: chi2-only device evaluations of the round's rows, eager launches, two lanes when the
-    // quadratic form serves them; the table level the caller vouches for
-    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
-    const bool saved_ring = e->ring_allowed;
-    e->const_hint = hint;
-    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
-    struct Restore {
-        vmx_engine* e; int hint, lanes; bool ring;
-        ~Restore() { wait_lane(e); e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
-    } restore{e, saved_hint, saved_lanes, saved_ring};
+    // the engine as the fits' objective, the round's rows in chunks of 512 unless the caller says otherwise
+    LikelihoodSession L(e, opt_hint, opt ? opt->chunk : 0, opt ? opt->lanes : 0, 512, varies);
+    const int chunk = L.chunk;
 
     vmx_fit_stats S{};
     const size_t emit_lds = (size_t)((P + 1) & ~1) * sizeof(int32_t) + vmx_migrad::MAXN * sizeof(double);
@@ -4024,24 +4111,19 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
         gap_used += 2;
         S.rounds += 1;
         S.evaluations += total;
-        bool lane_used = false;
-        hipStream_t lane_stream = nullptr;
         const auto t_c0 = std::chrono::steady_clock::now();
+        // (the host has just waited for the stream: the rows are there for either lane)
+        const int calls = L.evaluate(W.theta.p, total, W.chi2.p, W.status.p, mock_row ? W.mock.p : nullptr, false);
+        if (calls < 0) return -2;
+        S.engine_calls += calls;
         for (int off = 0; off < total; off += chunk) {
             const int B = std::min(chunk, total - off);
-            if (eval_device_impl(e, W.theta.p + (size_t)off * P, B, W.chi2.p + off, nullptr, W.status.p + off, mock_row ? W.mock.p + off : nullptr, true)) return -2;
-            if (e->last_stream != st) { lane_used = true; lane_stream = e->last_stream; }
-            S.engine_calls += 1;
             int bin = 0;
             while (bin < 7 && B > (1 << (2 * bin))) ++bin;          // 1, 2..4, 5..16, 17..64, 65..256, 257..1024, 1025..4096, more
             S.calls_by_batch[bin] += 1;
             S.evaluations_by_batch[bin] += B;
         }
         S.seconds_enqueuing_calls += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_c0).count();
-        if (lane_used) {        // the next round's bookkeeping reads every chunk's chi2
-            HIP_OK(hipEventRecord(W.ev_lane, lane_stream));
-            HIP_OK(hipStreamWaitEvent(st, W.ev_lane, 0));
-        }
     }
     S.fits_unfinished = W.pin_word[1];
     S.seconds_waiting_for_draws = producer_wait_s;
@@ -4084,20 +4166,12 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats)
 {
     REQUIRE(e && e->finalized && spec && x && lnL && accepted, "vmx_ensemble_run");
-    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
-            "vmx_ensemble_run: parameter columns, limits and the fixed row");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box("vmx_ensemble_run", e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params;
-    REQUIRE(n >= 1 && n <= VMX_ENS_MAXN, "vmx_ensemble_run: 1 .. 64 sampled columns");
     REQUIRE(W >= 2 * n && W % 2 == 0, "vmx_ensemble_run: an even number of walkers, at least twice the sampled columns");
-    std::vector<char> varies(P, 0);
-    for (int i = 0; i < n; ++i) {
-        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_ensemble_run: parameter column");
-        REQUIRE(!varies[spec->col[i]], "vmx_ensemble_run: a column is listed twice");
-        varies[spec->col[i]] = 1;
-        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_ensemble_run: limits");
-    }
     REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), "vmx_ensemble_run: the stretch scale a must exceed 1");
-    REQUIRE(std::isfinite(spec->log_norm), "vmx_ensemble_run: log_norm");
     REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, "vmx_ensemble_run: thin >= 1, n_steps >= 0, step0 >= 0");
     for (int w = 0; w < W; ++w) {
         REQUIRE(std::isfinite(lnL[w]), "vmx_ensemble_run: a start walker has a non-finite lnL");
@@ -4106,12 +4180,7 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
             REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], "vmx_ensemble_run: a start walker lies outside the box");
         }
     }
-    int hint = opt ? opt->const_hint : -1;
-    REQUIRE(hint >= -1 && hint <= 2, "vmx_ensemble_run: const_hint -1 (derive it), 0, 1 or 2");
-    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_ensemble_run: chunk, lanes");
-    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
-    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
-    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    if (LikelihoodSession::check("vmx_ensemble_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const int H = W / 2;
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
 
@@ -4120,51 +4189,32 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
     if (!e->ensws) e->ensws = new EnsWorkspace();
     EnsWorkspace& S = *e->ensws;
     if (ensure(S.x, (size_t)W * n) || ensure(S.lnl, W) || ensure(S.acc, W) || ensure(S.n_box, W) || ensure(S.n_fail, W) ||
-        ensure(S.prop, (size_t)H * n) || ensure(S.factor, H) || ensure(S.inside, H) || ensure(S.theta, (size_t)H * P) ||
-        ensure(S.chi2, H) || ensure(S.status, H) || ensure(S.fixed, P) || ensure(S.col, n) || ensure(S.lo, n) || ensure(S.hi, n))
+        ensure(S.prop, (size_t)H * n) || ensure(S.factor, H) || ensure(S.inside, H) || ensure(S.col, n))
         return -2;
     if (chain && rows > 0 && ensure(S.chain, (size_t)rows * W * n)) return -2;
     if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * W)) return -2;
-    if (!S.ev_prop) {
-        HIP_OK(hipEventCreateWithFlags(&S.ev_prop, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
-    }
     hipStream_t st = e->stream;
+    EnsDev D{};
+    if (S.box.upload(H, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
     HIP_OK(hipMemcpyAsync(S.x.p, x, (size_t)W * n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(S.acc.p, accepted, (size_t)W * sizeof(int64_t), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemsetAsync(S.n_box.p, 0, (size_t)W * sizeof(int64_t), st));
     HIP_OK(hipMemsetAsync(S.n_fail.p, 0, (size_t)W * sizeof(int64_t), st));
-    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(S.col.p, spec->col, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
 
-    EnsDev D{};
     D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p; D.n_box = S.n_box.p; D.n_fail = S.n_fail.p;
     D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
-    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
-    D.fixed = S.fixed.p; D.col = S.col.p; D.lo = S.lo.p; D.hi = S.hi.p;
+    D.col = S.col.p;
     D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
     D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
     D.seed = spec->seed; D.stream = spec->stream; D.step0 = step0;
 
-    // the engine as the sampler's likelihood: chi2-only device evaluations of the half's rows, eager launches, two lanes when the
-    // quadratic form serves them; the table level the sampled columns allow.  The second lane's stream waits for the rows at
-    // lane_wait, the next decision waits for the lane.
-    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
-    const bool saved_ring = e->ring_allowed;
-    e->const_hint = hint;
-    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
-    e->lane_calls = 0;
-    struct Restore {
-        vmx_engine* e; int hint, lanes; bool ring;
-        ~Restore() { wait_lane(e); e->lane_wait = nullptr; e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
-    } restore{e, saved_hint, saved_lanes, saved_ring};
-
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
     vmx_ensemble_stats R{};
-    R.const_hint = hint;
-    R.lanes = e->n_lanes;
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
     const auto t_loop = std::chrono::steady_clock::now();
     const int64_t halves = 2 * (int64_t)n_steps;
     if (halves > 0) hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, (int64_t)-1, 0, step0, 0);
@@ -4172,25 +4222,14 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
     for (int64_t q = 0; q < halves; ++q) {
         const int64_t s = step0 + q / 2;
         const int h = (int)(q % 2);
-        HIP_OK(hipEventRecord(S.ev_prop, st));
-        e->lane_wait = S.ev_prop;
-        hipStream_t lane_stream = nullptr;
-        for (int off = 0; off < H; off += chunk) {
-            const int B = std::min(chunk, H - off);
-            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
-            if (e->last_stream != st) lane_stream = e->last_stream;
-            R.engine_calls += 1;
-        }
-        if (lane_stream) {      // (the decision reads every chunk's chi2)
-            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
-            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
-        }
+        const int calls = L.evaluate(S.box.theta.p, H, S.box.chi2.p, S.box.status.p, nullptr, true);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
         const int64_t nq = q + 1;
         hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, s, h,
                            nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
         HIP_OK(hipGetLastError());
     }
-    e->lane_wait = nullptr;
     std::vector<int64_t> acc0(accepted, accepted + W), box(W), failed(W);
     HIP_OK(hipMemcpyAsync(x, S.x.p, (size_t)W * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -4222,23 +4261,13 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
                    const vmx_nested_options* opt, vmx_nested_stats* stats)
 {
     REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration, "vmx_nested_run");
-    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
-            "vmx_nested_run: parameter columns, limits and the fixed row");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box("vmx_nested_run", e, spec, VMX_NS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params, nlive = spec->nlive, K = spec->K;
-    REQUIRE(n >= 1 && n <= VMX_NS_MAXN, "vmx_nested_run: 1 .. 32 sampled columns");
     REQUIRE(nlive >= n + 2 && nlive <= VMX_NS_MAX_LIVE, "vmx_nested_run: n + 2 .. 4096 live points");
     REQUIRE(K >= 1 && K <= nlive - n - 1, "vmx_nested_run: 1 .. nlive - n - 1 threads");
     REQUIRE(spec->num_repeats >= 1, "vmx_nested_run: num_repeats >= 1");
-    std::vector<char> varies(P, 0);
-    std::vector<int32_t> inv(P, -1);
-    for (int i = 0; i < n; ++i) {
-        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_nested_run: parameter column");
-        REQUIRE(!varies[spec->col[i]], "vmx_nested_run: a column is listed twice");
-        varies[spec->col[i]] = 1;
-        inv[spec->col[i]] = i;
-        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_nested_run: limits");
-    }
-    REQUIRE(std::isfinite(spec->log_norm), "vmx_nested_run: log_norm");
     REQUIRE(n_iterations >= 0 && *iteration >= 0, "vmx_nested_run: n_iterations >= 0, iteration >= 0");
     REQUIRE(n_iterations == 0 || (dead_u && dead_lnl && dead_nlive), "vmx_nested_run: the dead record");
     const bool draw = opt && opt->draw_live != 0;
@@ -4251,12 +4280,7 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
                 REQUIRE(v >= 0.0 && v <= 1.0, "vmx_nested_run: a live point lies outside the unit cube");
             }
         }
-    int hint = opt ? opt->const_hint : -1;
-    REQUIRE(hint >= -1 && hint <= 2, "vmx_nested_run: const_hint -1 (derive it), 0, 1 or 2");
-    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_nested_run: chunk, lanes");
-    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
-    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
-    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    if (LikelihoodSession::check("vmx_nested_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const size_t cap = (size_t)std::max(nlive, K), rec_rows = (size_t)std::max(n_iterations, 1) * K;
 
     HIP_OK(hipSetDevice(e->device));
@@ -4266,13 +4290,11 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
     if (ensure(S.live_u, (size_t)nlive * n) || ensure(S.live_lnl, nlive) || ensure(S.rank, nlive) || ensure(S.surv, nlive) ||
         ensure(S.killed, K) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) || ensure(S.lstar, 1) ||
         ensure(S.th, (size_t)K * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, K) || ensure(S.dead_u, rec_rows * n) ||
-        ensure(S.dead_lnl, rec_rows) || ensure(S.dead_n, rec_rows) || ensure(S.theta, cap * P) || ensure(S.chi2, cap) ||
-        ensure(S.status, cap) || ensure(S.fixed, P) || ensure(S.inv, P) || ensure(S.lo, n) || ensure(S.hi, n) || ensure(S.counters, 1))
+        ensure(S.dead_lnl, rec_rows) || ensure(S.dead_n, rec_rows) || ensure(S.counters, 1))
         return -2;
     if (!S.pin_word) {
         HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
         HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_word, S.pin_word, 0));
-        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
     }
     if (S.pin_lnl_n < (size_t)nlive + K) {
         if (S.pin_lnl) { (void)hipHostFree(S.pin_lnl); S.pin_lnl = nullptr; S.pin_lnl_n = 0; }
@@ -4286,52 +4308,28 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
         HIP_OK(hipMemcpyAsync(S.live_lnl.p, live_lnl, (size_t)nlive * sizeof(double), hipMemcpyHostToDevice, st));
     }
     HIP_OK(hipMemsetAsync(S.counters.p, 0, sizeof(int64_t), st));
-    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.inv.p, inv.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-
     NsDev D{};
+    if (S.box.upload(cap, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
     D.live_u = S.live_u.p; D.live_lnl = S.live_lnl.p; D.rank = S.rank.p; D.surv = S.surv.p; D.killed = S.killed.p;
     D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.lstar = S.lstar.p;
     D.th = (vmx_ns::Thread*)S.th.p; D.slot = S.slot.p;
     D.dead_u = S.dead_u.p; D.dead_lnl = S.dead_lnl.p; D.dead_n = S.dead_n.p;
-    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
-    D.fixed = S.fixed.p; D.inv = S.inv.p; D.lo = S.lo.p; D.hi = S.hi.p;
     D.host_word = S.dpin_word; D.host_lnl = S.dpin_lnl; D.counters = S.counters.p;
     D.nlive = nlive; D.K = K; D.n = n; D.P = P; D.num_repeats = spec->num_repeats;
     D.log_norm = spec->log_norm; D.seed = spec->seed; D.stream = spec->stream;
 
-    // the engine as the sampler's likelihood: chi2-only device evaluations of the round's rows, eager launches, two lanes when the
-    // quadratic form serves them; the table level the sampled columns allow
-    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
-    const bool saved_ring = e->ring_allowed;
-    e->const_hint = hint;
-    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
-    e->lane_calls = 0;
-    struct Restore {
-        vmx_engine* e; int hint, lanes; bool ring;
-        ~Restore() { wait_lane(e); e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
-    } restore{e, saved_hint, saved_lanes, saved_ring};
-
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
     vmx_nested_stats R{};
-    R.const_hint = hint;
-    R.lanes = e->n_lanes;
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
     double enqueue_s = 0.0;
-    // the engine's chain over the first `total` rows; the stream then waits for the second lane
+    // the first `total` rows (the host has waited for the kernel that wrote them: they are there for either lane)
     auto evaluate = [&](int total) -> int {
         const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t lane_stream = nullptr;
-        for (int off = 0; off < total; off += chunk) {
-            const int B = std::min(chunk, total - off);
-            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
-            if (e->last_stream != st) lane_stream = e->last_stream;
-            R.engine_calls += 1;
-        }
-        if (lane_stream) {      // (the next kernel reads every chunk's chi2)
-            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
-            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
-        }
+        const int calls = L.evaluate(S.box.theta.p, total, S.box.chi2.p, S.box.status.p, nullptr, false);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return 0;
     };
@@ -4393,23 +4391,13 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
                 vmx_smc_stats* stats)
 {
     REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale, "vmx_smc_run");
-    REQUIRE(spec->n_params == e->n_params && spec->theta_fixed && spec->col && spec->lo && spec->hi,
-            "vmx_smc_run: parameter columns, limits and the fixed row");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box("vmx_smc_run", e, spec, VMX_NS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params, N = spec->N, sweeps = spec->sweeps;
-    REQUIRE(n >= 1 && n <= VMX_NS_MAXN, "vmx_smc_run: 1 .. 32 sampled columns");
     REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, "vmx_smc_run: max(2 n + 2, 8) .. 4096 particles");
     REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, "vmx_smc_run: 0 < ess < 1");
     REQUIRE(sweeps >= 1, "vmx_smc_run: sweeps >= 1");
-    std::vector<char> varies(P, 0);
-    std::vector<int32_t> inv(P, -1);
-    for (int i = 0; i < n; ++i) {
-        REQUIRE(spec->col[i] >= 0 && spec->col[i] < P, "vmx_smc_run: parameter column");
-        REQUIRE(!varies[spec->col[i]], "vmx_smc_run: a column is listed twice");
-        varies[spec->col[i]] = 1;
-        inv[spec->col[i]] = i;
-        REQUIRE(std::isfinite(spec->lo[i]) && std::isfinite(spec->hi[i]) && spec->lo[i] < spec->hi[i], "vmx_smc_run: limits");
-    }
-    REQUIRE(std::isfinite(spec->log_norm), "vmx_smc_run: log_norm");
     REQUIRE(n_stages >= 0 && *stage >= 0 && *stage < ((int64_t)1 << 31), "vmx_smc_run: n_stages >= 0, 0 <= stage < 2^31");
     REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), "vmx_smc_run: the stage record");
     const bool draw = opt && opt->draw != 0;
@@ -4428,12 +4416,7 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
         }
         REQUIRE(any, "vmx_smc_run: no particle has a finite lnL");
     }
-    int hint = opt ? opt->const_hint : -1;
-    REQUIRE(hint >= -1 && hint <= 2, "vmx_smc_run: const_hint -1 (derive it), 0, 1 or 2");
-    REQUIRE(!opt || (opt->chunk >= 0 && opt->lanes >= 0), "vmx_smc_run: chunk, lanes");
-    if (hint < 0) hint = derived_const_hint(e, varies);          // (a column varies when it is sampled)
-    const int chunk = std::max(1, std::min(opt && opt->chunk > 0 ? opt->chunk : e->max_batch, e->max_batch));
-    const int want_lanes = opt && opt->lanes > 0 ? std::min(opt->lanes, VMX_MAX_LANES) : 2;
+    if (LikelihoodSession::check("vmx_smc_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const size_t rec_rows = (size_t)std::max(n_stages, 1);
 
     HIP_OK(hipSetDevice(e->device));
@@ -4442,16 +4425,13 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
     SmcWorkspace& S = *e->smcws;
     if (ensure(S.u, (size_t)N * n) || ensure(S.lnl, N) || ensure(S.u2, (size_t)N * n) || ensure(S.lnl2, N) || ensure(S.w, N) ||
         ensure(S.cum, N) || ensure(S.zero, N) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) ||
-        ensure(S.state, 2) || ensure(S.prop, (size_t)N * n) || ensure(S.uacc, N) || ensure(S.inside, N) || ensure(S.theta, (size_t)N * P) ||
-        ensure(S.chi2, N) || ensure(S.status, N) || ensure(S.fixed, P) || ensure(S.inv, P) || ensure(S.lo, n) || ensure(S.hi, n) ||
+        ensure(S.state, 2) || ensure(S.prop, (size_t)N * n) || ensure(S.uacc, N) || ensure(S.inside, N) ||
         ensure(S.rec, rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * N) || ensure(S.rec_anc, rec_rows * N) ||
         ensure(S.counters, 3))
         return -2;
     if (!S.pin) {
         HIP_OK(hipHostMalloc((void**)&S.pin, 4 * sizeof(double), hipHostMallocMapped));
         HIP_OK(hipHostGetDevicePointer((void**)&S.dpin, S.pin, 0));
-        HIP_OK(hipEventCreateWithFlags(&S.ev_prop, hipEventDisableTiming));
-        HIP_OK(hipEventCreateWithFlags(&S.ev_lane, hipEventDisableTiming));
     }
     hipStream_t st = e->stream;
     const double state0[2] = {*beta, *scale};
@@ -4463,53 +4443,26 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
     HIP_OK(hipMemsetAsync(S.zero.p, 0, (size_t)N * sizeof(int32_t), st));
     HIP_OK(hipMemsetAsync(S.counters.p, 0, 3 * sizeof(int64_t), st));
     HIP_OK(hipMemsetAsync(S.rec.p, 0, rec_rows * VMX_SMC_REC * sizeof(double), st));
-    HIP_OK(hipMemcpyAsync(S.fixed.p, spec->theta_fixed, (size_t)P * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.inv.p, inv.data(), (size_t)P * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.lo.p, spec->lo, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.hi.p, spec->hi, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-
     SmcDev D{};
+    if (S.box.upload(N, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
     D.u = S.u.p; D.lnl = S.lnl.p; D.u2 = S.u2.p; D.lnl2 = S.lnl2.p; D.w = S.w.p; D.cum = S.cum.p; D.zero = S.zero.p;
     D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.state = S.state.p;
     D.prop = S.prop.p; D.uacc = S.uacc.p; D.inside = S.inside.p;
-    D.theta = S.theta.p; D.chi2 = S.chi2.p; D.status = S.status.p;
-    D.fixed = S.fixed.p; D.inv = S.inv.p; D.lo = S.lo.p; D.hi = S.hi.p;
     D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.dpin;
     D.N = N; D.n = n; D.P = P; D.sweeps = sweeps; D.ess = spec->ess; D.log_norm = spec->log_norm;
     D.seed = spec->seed; D.stream = spec->stream;
 
-    // the engine as the sampler's likelihood: chi2-only device evaluations of the sweep's rows, eager launches, two lanes when the
-    // quadratic form serves them; the table level the sampled columns allow.  The second lane's stream waits for the rows at
-    // lane_wait, the next decision waits for the lane.
-    const int saved_hint = e->const_hint, saved_lanes = e->n_lanes;
-    const bool saved_ring = e->ring_allowed;
-    e->const_hint = hint;
-    if (want_lanes > e->n_lanes) { e->n_lanes = want_lanes; e->ring_allowed = false; }
-    e->lane_calls = 0;
-    struct Restore {
-        vmx_engine* e; int hint, lanes; bool ring;
-        ~Restore() { wait_lane(e); e->lane_wait = nullptr; e->const_hint = hint; e->n_lanes = lanes; e->ring_allowed = ring; e->lane_calls = 0; e->last_stream = e->stream; }
-    } restore{e, saved_hint, saved_lanes, saved_ring};
-
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
     vmx_smc_stats R{};
-    R.const_hint = hint;
-    R.lanes = e->n_lanes;
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
     double enqueue_s = 0.0;
-    // the engine's chain over the N rows just written; the stream then waits for the second lane
+    // the N rows a kernel has just written
     auto evaluate = [&]() -> int {
-        HIP_OK(hipEventRecord(S.ev_prop, st));
-        e->lane_wait = S.ev_prop;
-        hipStream_t lane_stream = nullptr;
-        for (int off = 0; off < N; off += chunk) {
-            const int B = std::min(chunk, N - off);
-            if (eval_device_impl(e, S.theta.p + (size_t)off * P, B, S.chi2.p + off, nullptr, S.status.p + off, nullptr, true)) return -2;
-            if (e->last_stream != st) lane_stream = e->last_stream;
-            R.engine_calls += 1;
-        }
-        if (lane_stream) {      // (the next kernel reads every chunk's chi2)
-            HIP_OK(hipEventRecord(S.ev_lane, lane_stream));
-            HIP_OK(hipStreamWaitEvent(st, S.ev_lane, 0));
-        }
+        const int calls = L.evaluate(S.box.theta.p, N, S.box.chi2.p, S.box.status.p, nullptr, true);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
         R.rows += N;
         return 0;
     };
@@ -4551,7 +4504,6 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
         R.accepted += (int64_t)S.pin[1];
         done += 1;
     }
-    e->lane_wait = nullptr;
     std::vector<double> rec_host((size_t)std::max(done, 1) * VMX_SMC_REC);
     HIP_OK(hipMemcpyAsync(u, S.u.p, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(lnl, S.lnl.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -194,6 +194,17 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _in_place(dtype, **arrays):
+    """The named arrays are what the library can update in place: C-contiguous NumPy arrays of ``dtype``."""
+    for name, arr in arrays.items():
+        if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous):
+            raise ValueError(f'{name}: a C-contiguous {np.dtype(dtype).name} array (updated in place)')
+
+
+def _stats_dict(stats):
+    return {name: getattr(stats, name) for name, _ in stats._fields_}
+
+
 def load_library():
     """Load libvegamx.so (built in-tree by ``__graft_entry__.build()``); no fallback."""
     global _lib
@@ -1028,20 +1039,29 @@ class Engine:
         info['evaluations_by_batch'] = dict(zip(FIT_BATCH_BINS, list(stats.evaluations_by_batch)))
         return outs, info
 
+    def _sampled_box(self, cols, lo, hi, theta_fixed, **state):
+        """What the three samplers' calls take alike: ``cols`` / ``lo`` / ``hi`` / ``theta_fixed`` as the library reads them, and the
+        check of the run's state, given by name: points [rows, n] and their lnL [rows], float64, updated in place.  Returns the four
+        arrays and rows."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
+        _in_place(np.float64, **state)
+        (pname, points), (lname, lnl) = state.items()
+        rows = points.shape[0]
+        if points.shape != (rows, cols.size) or lnl.shape != (rows,) or theta_fixed.shape != (self.n_params,):
+            raise ValueError(f'{pname} [rows, n], {lname} [rows], theta_fixed [n_params]')
+        return cols, lo, hi, theta_fixed, rows
+
     def ensemble_run(self, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin=1, a=2.0, log_norm=0.0, seed=0,
                      stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
         """``n_steps`` steps of the ensemble sampler on the device (include/vegamx.h: vmx_ensemble_run): ``cols`` the sampled
         parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``x`` [W, n] / ``lnl`` [W] / ``accepted``
         int64 [W] the walkers' state (updated in place), ``step0`` the global index of the first step.  Returns (chain [rows, W, n],
         chain_lnl [rows, W], statistics), rows = (step0 + n_steps) // thin - step0 // thin."""
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
-        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
-        for arr, dtype in ((x, np.float64), (lnl, np.float64), (accepted, np.int64)):
-            if not (isinstance(arr, np.ndarray) and arr.dtype == dtype and arr.flags.c_contiguous):
-                raise ValueError('x, lnl, accepted: C-contiguous float64 / float64 / int64 arrays (updated in place)')
-        W = x.shape[0]
-        if x.shape != (W, cols.size) or lnl.shape != (W,) or accepted.shape != (W,) or theta_fixed.shape != (self.n_params,):
-            raise ValueError('x [W, n], lnl [W], accepted [W], theta_fixed [n_params]')
+        cols, lo, hi, theta_fixed, W = self._sampled_box(cols, lo, hi, theta_fixed, x=x, lnl=lnl)
+        _in_place(np.int64, accepted=accepted)
+        if accepted.shape != (W,):
+            raise ValueError('accepted [W]')
         step0, n_steps, thin = int(step0), int(n_steps), int(thin)
         rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
         chain = np.empty((rows, W, cols.size)) if keep_chain else None
@@ -1054,7 +1074,7 @@ class Engine:
                                               accepted.ctypes.data_as(C.POINTER(C.c_int64)), step0, n_steps, thin,
                                               _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None,
                                               C.byref(opt), C.byref(stats)))
-        return chain, chain_lnl, {name: getattr(stats, name) for name, _ in EnsembleStats._fields_}
+        return chain, chain_lnl, _stats_dict(stats)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
                    seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):
@@ -1064,14 +1084,8 @@ class Engine:
         index of the next iteration.  ``stop(iterations, dead_lnl [K], live_lnl [nlive])`` is asked after every iteration; a true
         answer ends the call.  Returns (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K], iteration + m, statistics) for the m
         iterations done."""
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
-        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
-        for arr in (live_u, live_lnl):
-            if not (isinstance(arr, np.ndarray) and arr.dtype == np.float64 and arr.flags.c_contiguous):
-                raise ValueError('live_u, live_lnl: C-contiguous float64 arrays (updated in place)')
-        nlive, K, n_iterations = live_u.shape[0], int(threads), max(0, int(n_iterations))
-        if live_u.shape != (nlive, cols.size) or live_lnl.shape != (nlive,) or theta_fixed.shape != (self.n_params,):
-            raise ValueError('live_u [nlive, n], live_lnl [nlive], theta_fixed [n_params]')
+        cols, lo, hi, theta_fixed, nlive = self._sampled_box(cols, lo, hi, theta_fixed, live_u=live_u, live_lnl=live_lnl)
+        K, n_iterations = int(threads), max(0, int(n_iterations))
         rows = n_iterations * max(K, 0)
         dead_u, dead_lnl, dead_n = np.empty((rows, cols.size)), np.empty(rows), np.empty(rows, dtype=np.int32)
         spec = NestedSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), nlive, K, int(num_repeats), 0, float(log_norm),
@@ -1094,7 +1108,7 @@ class Engine:
         if raised:
             raise raised[0]
         m = int(stats.iterations) * K
-        return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), {name: getattr(stats, name) for name, _ in NestedStats._fields_}
+        return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), _stats_dict(stats)
 
     def smc_run(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, n_stages, ess, sweeps, log_norm=0.0, seed=0, stream=0,
                 const_hint=-1, chunk=0, lanes=0, draw=False):
@@ -1103,14 +1117,8 @@ class Engine:
         [N] the particles (updated in place; drawn first with ``draw``), ``stage`` the global index of the next stage, ``beta`` and
         ``scale`` its inverse temperature and proposal scale.  Returns (record: one dict per stage done with beta_prev, beta, ess,
         lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale afterwards; statistics)."""
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
-        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
-        for arr in (u, lnl):
-            if not (isinstance(arr, np.ndarray) and arr.dtype == np.float64 and arr.flags.c_contiguous):
-                raise ValueError('u, lnl: C-contiguous float64 arrays (updated in place)')
-        N, n_stages = u.shape[0], max(0, int(n_stages))
-        if u.shape != (N, cols.size) or lnl.shape != (N,) or theta_fixed.shape != (self.n_params,):
-            raise ValueError('u [N, n], lnl [N], theta_fixed [n_params]')
+        cols, lo, hi, theta_fixed, N = self._sampled_box(cols, lo, hi, theta_fixed, u=u, lnl=lnl)
+        n_stages = max(0, int(n_stages))
         rec, rec_lnl = np.zeros((n_stages, VMX_SMC_REC)), np.empty((n_stages, N))
         rec_anc = np.empty((n_stages, N), dtype=np.int32)
         spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
@@ -1123,7 +1131,7 @@ class Engine:
         record = [dict(beta_prev=float(rec[k, 0]), beta=float(rec[k, 1]), ess=float(rec[k, 2]), lnl=rec_lnl[k].copy(),
                        anc=rec_anc[k].copy(), accepted=int(rec[k, 3]), scale=float(rec[k, 4]), cholesky=bool(rec[k, 5]))
                   for k in range(int(stats.stages))]
-        return record, int(st.value), float(b.value), float(sc.value), {name: getattr(stats, name) for name, _ in SmcStats._fields_}
+        return record, int(st.value), float(b.value), float(sc.value), _stats_dict(stats)
 
     def derived_const_hint(self, cols):
         """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:

@@ -361,8 +361,83 @@ class EngineRows:
         return chi2
 
 
+class EngineSampler:
+    """What the samplers over ``vega`` hold and do alike (a mixin, set up by :meth:`_setup_engine`: the cube samplers' bases have
+    constructors of their own): the interface, the sampled box (names, lo, hi, values, errors, cols), the driver asked for and the
+    one picked when the first likelihood knows the engine, ``chunk`` / ``lanes`` / ``const_hint`` of the engine's calls."""
+
+    def _setup_engine(self, vega, sample_params, driver, chunk, lanes, const_hint):
+        """Returns the number of sampled parameters."""
+        if driver not in ('device', 'python'):
+            raise ValueError("driver: 'device' or 'python'")
+        self.vega = vega
+        box = SampledBox(vega, sample_params)
+        self.names, self.lo, self.hi, self.values, self.errors, self.cols = box.names, box.lo, box.hi, box.values, box.errors, box.cols
+        self.driver_asked, self.driver = driver, None
+        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
+        self._rows = None
+        return box.n
+
+    def log_norm(self):
+        return float(self.vega._log_norm())
+
+    def _fixed_row(self):
+        return np.asarray(self.vega._theta(None), dtype=np.float64).copy()
+
+    def _pick_driver(self, first_row, device_method):
+        self.driver = freeze_and_pick_driver(self.vega, first_row, self.cols, self.driver_asked, device_method)
+
+    def _engine_rows(self):
+        return EngineRows(self.vega, self.cols, self.chunk, self.lanes, self.const_hint)
+
+    def _derived_of(self, rows):
+        return derived_rows(self.vega, self.cols, self._fixed_row(), rows, self.chunk, self.lanes, self.const_hint)
+
+    def _write_extra(self, derived, print_func, block):
+        """The derived-parameter arguments of ``write_getdist`` for ``write(..., derived=...)``; ``block()`` computes the rows."""
+        extra = derived_for_write(self, derived, print_func)
+        if extra:
+            extra['derived'] = block()
+        return extra
+
+    # ---- the samplers in the unit cube (a uniform prior over the box)
+    def to_physical(self, u):
+        from .nested import map_cube
+        return map_cube(self.lo, self.hi, np.asarray(u, dtype=np.float64))
+
+    def _evaluate(self, rows_u):
+        from .nested import lnl_of
+        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
+        rows_t[:, self.cols] = self.to_physical(rows_u)
+        # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+        return lnl_of(0, self._rows.chi2(rows_t), self.log_norm())
+
+    def _begin_advance(self, first_u, device_method):
+        """The fixed row of this call; on the first one the driver (``first_u``: the first point the run evaluates)."""
+        self._theta = self._fixed_row()
+        if self.driver is None:
+            first = self._theta.copy()
+            first[self.cols] = self.to_physical(first_u())
+            self._pick_driver(first, device_method)
+
+    def _advance_python(self, advance, count):
+        """``advance(count)`` of the NumPy driver with the engine behind ``_evaluate``; its last result is the statistics."""
+        with self._engine_rows() as self._rows:
+            try:
+                out = advance(count)
+            finally:
+                calls, self._rows = self._rows.calls, None
+        out[-1]['engine_calls'] = out[-1]['host_waits'] = calls
+        return out
+
+    def derived(self):
+        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the rows of ``samples()``,
+        [N, m]: a pass over them after the run (:func:`derived_rows`), the same block whichever driver ran."""
+        return self._derived_of(self.samples()[0])
+
+
 # ------------------------------------------------------------------ the sampler
-class EnsembleSampler:
+class EnsembleSampler(EngineSampler):
     """W walkers over the sampled parameters of ``vega`` (``sample_params['limits']``: the ``[sample]`` section, or the
     ``[monte carlo]`` one after ``initialize_monte_carlo``, as bin/run_vega_mpi.py picks them; ``sample_params`` overrides).
 
@@ -372,11 +447,7 @@ class EnsembleSampler:
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
                  chunk=0, lanes=0, const_hint=-1):
-        if driver not in ('device', 'python'):
-            raise ValueError("driver: 'device' or 'python'")
-        self.vega = vega
-        box = SampledBox(vega, sample_params)
-        self.names, self.lo, self.hi, self.values, self.errors, self.n = box.names, box.lo, box.hi, box.values, box.errors, box.n
+        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         self.W = int(walkers)
         if self.W % 2 or self.W < 2 * self.n:
             raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
@@ -387,10 +458,6 @@ class EnsembleSampler:
         if self.thin < 1:
             raise ValueError('thin >= 1')
         self.segment = max(1, int(segment))
-        self.driver_asked = driver
-        self.driver = None
-        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
-        self.cols = box.cols
         self.reset()
 
     def reset(self):
@@ -428,9 +495,6 @@ class EnsembleSampler:
             raise ValueError('start: every walker inside the box')
         return x
 
-    def _fixed_row(self):
-        return np.asarray(self.vega._theta(None), dtype=np.float64).copy()
-
     def _prepare(self, start, init_scale):
         vega = self.vega
         theta = self._fixed_row()
@@ -441,16 +505,13 @@ class EnsembleSampler:
         else:
             x0 = None
             theta_w = theta[None, :]
-        self.driver = freeze_and_pick_driver(vega, theta_w[0], self.cols, self.driver_asked, 'ensemble_run')
+        self._pick_driver(theta_w[0], 'ensemble_run')
         if self.x is None:
             chi2 = np.asarray(vega.chi2_batch(theta_w), dtype=np.float64)
             self.x, self.lnl = x0, log_lik(self.log_norm(), chi2)
             if not np.all(np.isfinite(self.lnl)):
                 raise ValueError('a start walker has a non-finite log-likelihood')
         return theta
-
-    def log_norm(self):
-        return float(self.vega._log_norm())
 
     # ---- run
     def run(self, n_steps, start='ball', init_scale=1.0):
@@ -491,7 +552,7 @@ class EnsembleSampler:
         t0 = time.perf_counter()
         H = self.W // 2
         log_norm = self.log_norm()
-        with EngineRows(self.vega, self.cols, self.chunk, self.lanes, self.const_hint) as rows:
+        with self._engine_rows() as rows:
             def evaluate(rows_x, h):
                 rows_t = np.repeat(theta[None, :], H, axis=0)
                 rows_t[:, self.cols] = rows_x
@@ -535,22 +596,48 @@ class EnsembleSampler:
         [rows, W, m] like :meth:`get_chain` (``flat``: [rows W, m]) - a pass over the recorded rows after the run
         (:func:`derived_rows`), the same block whichever driver ran."""
         chain = self.get_chain(discard=discard, thin=thin)
-        block = derived_rows(self.vega, self.cols, self._fixed_row(), chain.reshape(-1, self.n), self.chunk, self.lanes,
-                             self.const_hint)
+        block = self._derived_of(chain.reshape(-1, self.n))
         return block if flat else block.reshape(chain.shape[:2] + (block.shape[1],))
 
     def write(self, path, name, derived=False, print_func=print):
         """getdist's plain-text chain of the recorded rows (:func:`write_getdist`): ``name.txt`` and ``name.paramnames``;
         ``derived``: with the derived parameters' columns and lines after the sampled ones."""
-        extra = derived_for_write(self, derived, print_func)
-        if extra:
-            extra['derived'] = self.get_derived(flat=True)
+        extra = self._write_extra(derived, print_func, lambda: self.get_derived(flat=True))
         return write_getdist(path, name, self.names, self.get_chain(flat=True), self.get_log_lik(flat=True), **extra)
 
 
 # ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
 _ENSEMBLE_DEFAULTS = dict(sampler='Ensemble', name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
                           driver='device')
+
+
+def section_settings(main_config, sample_params, section, **defaults):
+    """What the settings of every sampler's section share: the section must be there, every sampled parameter must have limits,
+    ``path`` is required, expanded and must exist; ``name`` and ``driver`` over ``defaults``, ``derived`` and ``replicas`` when
+    stated.  Returns (the section, the limits, the settings so far: ``defaults`` with sampler, path, name, driver)."""
+    if section not in main_config:
+        raise RuntimeError('run_sampler called, but no sampler config found')
+    sec = main_config[section]
+    limits = sample_params['limits']
+    for lims in limits.values():
+        if lims is None or None in tuple(lims):
+            raise ValueError(_NO_LIMITS)
+    if 'path' not in sec:
+        raise ValueError(f'[{section}] needs a path')
+    path = Path(os.path.expandvars(sec.get('path')))
+    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
+                           "running.")
+    out = dict(defaults, sampler=section, path=path)
+    out['name'] = sec.get('name', out['name'])
+    out['driver'] = sec.get('driver', 'device')
+    if 'derived' in sec:
+        out['derived'] = parse_derived(sec)
+    if 'replicas' in sec:
+        from .replicas import parse_replicas
+        out['replicas'] = parse_replicas(sec)
+    if out['driver'] not in ('device', 'python'):
+        raise ValueError(f"[{section}] driver: 'device' or 'python'")
+    return sec, limits, out
 
 
 def sampler_settings(main_config, sample_params):
@@ -578,20 +665,7 @@ def sampler_settings(main_config, sample_params):
         return smc_settings(main_config, sample_params)
     if sampler != 'Ensemble':
         raise ValueError('Sampler not recognized. Please use Nested or Ensemble.')
-    if 'Ensemble' not in main_config:
-        raise RuntimeError('run_sampler called, but no sampler config found')
-    sec = main_config['Ensemble']
-    limits = sample_params['limits']
-    for lims in limits.values():
-        if lims is None or None in tuple(lims):
-            raise ValueError(_NO_LIMITS)
-    if 'path' not in sec:
-        raise ValueError('[Ensemble] needs a path')
-    path = Path(os.path.expandvars(sec.get('path')))
-    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
-                           "running.")
-    out = dict(_ENSEMBLE_DEFAULTS, path=path)
-    out['name'] = sec.get('name', out['name'])
+    sec, limits, out = section_settings(main_config, sample_params, 'Ensemble', **_ENSEMBLE_DEFAULTS)
     out['walkers'] = sec.getint('walkers', max(2 * len(limits), 32) + (max(2 * len(limits), 32) % 2))
     out['steps'] = sec.getint('steps', out['steps'])
     out['seed'] = sec.getint('seed', out['seed'])
@@ -599,16 +673,8 @@ def sampler_settings(main_config, sample_params):
     out['thin'] = sec.getint('thin', out['thin'])
     out['init'] = sec.get('init', out['init'])
     out['init_scale'] = sec.getfloat('init_scale', out['init_scale'])
-    out['driver'] = sec.get('driver', out['driver'])
-    if 'derived' in sec:
-        out['derived'] = parse_derived(sec)
-    if 'replicas' in sec:
-        from .replicas import parse_replicas
-        out['replicas'] = parse_replicas(sec)
     if out['init'] not in ('ball', 'prior'):
         raise ValueError("[Ensemble] init: 'ball' or 'prior'")
-    if out['driver'] not in ('device', 'python'):
-        raise ValueError("[Ensemble] driver: 'device' or 'python'")
     if out['walkers'] % 2 or out['walkers'] < 2 * len(limits):
         raise ValueError(f'[Ensemble] walkers: an even number, at least twice the {len(limits)} sampled parameters')
     if out['steps'] < 1 or out['thin'] < 1:

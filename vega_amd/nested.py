@@ -459,7 +459,7 @@ class NestedRun:
 
 
 # ------------------------------------------------------------------ the sampler over the engine
-class NestedSampler(NestedRun):
+class NestedSampler(E.EngineSampler, NestedRun):
     """Nested sampling of ``vega`` over its sampled parameters (``sample_params['limits']`` as for
     :class:`vega_amd.ensemble.EnsembleSampler`), a uniform prior over the limits.
 
@@ -469,43 +469,15 @@ class NestedSampler(NestedRun):
 
     def __init__(self, vega, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, driver='device',
                  sample_params=None, stream=0, chunk=0, lanes=0, const_hint=-1, max_iterations=None):
-        if driver not in ('device', 'python'):
-            raise ValueError("driver: 'device' or 'python'")
-        self.vega = vega
-        box = E.SampledBox(vega, sample_params)
-        self.names, self.lo, self.hi, self.cols = box.names, box.lo, box.hi, box.cols
-        self.driver_asked = driver
-        self.driver = None
-        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
-        self._rows = None
-        super().__init__(None, box.n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
-                         stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
-
-    def log_norm(self):
-        return float(self.vega._log_norm())
-
-    def to_physical(self, u):
-        return map_cube(self.lo, self.hi, np.asarray(u, dtype=np.float64))
-
-    def _evaluate(self, rows_u):
-        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
-        rows_t[:, self.cols] = map_cube(self.lo, self.hi, rows_u)
-        # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
-        return lnl_of(0, self._rows.chi2(rows_t), self.log_norm())
+        n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        NestedRun.__init__(self, None, n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
+                           stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
 
     def _advance(self, n_iterations):
         vega = self.vega
-        self._theta = np.asarray(vega._theta(None), dtype=np.float64).copy()
-        if self.driver is None:
-            first = self._theta.copy()
-            first[self.cols] = map_cube(self.lo, self.hi, draw_live(1, self.n, self.seed, self.stream)[0])
-            self.driver = E.freeze_and_pick_driver(vega, first, self.cols, self.driver_asked, 'nested_run')
+        self._begin_advance(lambda: draw_live(1, self.n, self.seed, self.stream)[0], 'nested_run')
         if self.driver == 'python':
-            with E.EngineRows(vega, self.cols, self.chunk, self.lanes, self.const_hint) as self._rows:
-                du, dl, dn, st = super()._advance(n_iterations)
-            st['engine_calls'] = st['host_waits'] = self._rows.calls
-            self._rows = None
-            return du, dl, dn, st
+            return self._advance_python(super()._advance, n_iterations)
         vega._sync_monte_carlo()
         draw = self.live_u is None
         if draw:
@@ -516,20 +488,11 @@ class NestedSampler(NestedRun):
             chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop)
         return du, dl, dn, st
 
-    def derived(self):
-        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the rows of :meth:`samples`,
-        [N, m]: a pass over them after the run (:func:`vega_amd.ensemble.derived_rows`), the same block whichever driver ran."""
-        theta = np.asarray(self.vega._theta(None), dtype=np.float64)
-        return E.derived_rows(self.vega, self.cols, theta, self.samples()[0], self.chunk, self.lanes, self.const_hint)
-
     def write(self, path, name, derived=False, print_func=print):
         """getdist's weighted chain ``name.txt`` (weight / max weight, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
         ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
         ones."""
-        extra = E.derived_for_write(self, derived, print_func)
-        if extra:
-            extra['derived'] = self.derived()
-        return write_run(self, path, name, self.names, **extra)
+        return write_run(self, path, name, self.names, **self._write_extra(derived, print_func, self.derived))
 
 
 def nested_settings(main_config, sample_params):
@@ -537,31 +500,11 @@ def nested_settings(main_config, sample_params):
     :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
     precision, seed, threads, driver, max_iterations}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them.``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
     mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default."""
-    import os
-    if 'Nested' not in main_config:
-        raise RuntimeError('run_sampler called, but no sampler config found')
-    sec = main_config['Nested']
-    limits = sample_params['limits']
-    for lims in limits.values():
-        if lims is None or None in tuple(lims):
-            raise ValueError(E._NO_LIMITS)
-    if 'path' not in sec:
-        raise ValueError('[Nested] needs a path')
-    path = Path(os.path.expandvars(sec.get('path')))
-    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
-                           "running.")
+    sec, limits, out = E.section_settings(main_config, sample_params, 'Nested', name='nested')
     n = len(limits)
-    out = dict(sampler='Nested', path=path, name=sec.get('name', 'nested'), num_live=sec.getint('num_live', 25 * n),
-               num_repeats=sec.getint('num_repeats', 5 * n), precision=sec.getfloat('precision', 0.001),
-               seed=sec.getint('seed', 0), threads=sec.getint('threads', None), driver=sec.get('driver', 'device'),
+    out.update(num_live=sec.getint('num_live', 25 * n), num_repeats=sec.getint('num_repeats', 5 * n),
+               precision=sec.getfloat('precision', 0.001), seed=sec.getint('seed', 0), threads=sec.getint('threads', None),
                max_iterations=sec.getint('max_iterations', None))
-    if 'derived' in sec:
-        out['derived'] = E.parse_derived(sec)
-    if 'replicas' in sec:
-        from .replicas import parse_replicas
-        out['replicas'] = parse_replicas(sec)
-    if out['driver'] not in ('device', 'python'):
-        raise ValueError("[Nested] driver: 'device' or 'python'")
     if not n + 2 <= out['num_live'] <= MAX_LIVE:
         raise ValueError(f'[Nested] num_live: {n + 2} .. {MAX_LIVE} for {n} sampled parameters')
     if out['threads'] is not None and not 1 <= out['threads'] <= out['num_live'] - n - 1:

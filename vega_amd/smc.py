@@ -422,51 +422,21 @@ class SMCRun:
 _PER_CALL = 64          # stages per call of the device driver (its record is allocated up front)
 
 
-class SMCSampler(SMCRun):
+class SMCSampler(E.EngineSampler, SMCRun):
     """Tempered SMC of ``vega`` over its sampled parameters (``sample_params['limits']`` as for
     :class:`vega_amd.ensemble.EnsembleSampler`), a uniform prior over the limits.  ``driver``: ``'device'`` (vmx_smc_run) or
     ``'python'`` (the NumPy restatement over ``chi2_batch_device``); an engine group takes ``'python'``."""
 
     def __init__(self, vega, particles=1024, ess=0.5, sweeps=None, seed=0, driver='device', chunk=0, sample_params=None, stream=0,
                  lanes=0, const_hint=-1, max_stages=None):
-        if driver not in ('device', 'python'):
-            raise ValueError("driver: 'device' or 'python'")
-        self.vega = vega
-        box = E.SampledBox(vega, sample_params)
-        self.names, self.lo, self.hi, self.cols = box.names, box.lo, box.hi, box.cols
-        self.driver_asked = driver
-        self.driver = None
-        self.chunk, self.lanes, self.const_hint = int(chunk), int(lanes), int(const_hint)
-        self._rows = None
-        super().__init__(None, box.n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, stream=stream, max_stages=max_stages)
-
-    def log_norm(self):
-        return float(self.vega._log_norm())
-
-    def to_physical(self, u):
-        return NS.map_cube(self.lo, self.hi, np.asarray(u, dtype=np.float64))
-
-    def _evaluate(self, rows_u):
-        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
-        rows_t[:, self.cols] = NS.map_cube(self.lo, self.hi, rows_u)
-        # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
-        return NS.lnl_of(0, self._rows.chi2(rows_t), self.log_norm())
+        n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        SMCRun.__init__(self, None, n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, stream=stream, max_stages=max_stages)
 
     def _advance(self, n_stages):
         vega = self.vega
-        self._theta = np.asarray(vega._theta(None), dtype=np.float64).copy()
-        if self.driver is None:
-            first = self._theta.copy()
-            first[self.cols] = NS.map_cube(self.lo, self.hi, draw_start(1, self.n, self.seed, self.stream)[0])
-            self.driver = E.freeze_and_pick_driver(vega, first, self.cols, self.driver_asked, 'smc_run')
+        self._begin_advance(lambda: draw_start(1, self.n, self.seed, self.stream)[0], 'smc_run')
         if self.driver == 'python':
-            with E.EngineRows(vega, self.cols, self.chunk, self.lanes, self.const_hint) as self._rows:
-                try:
-                    rec, st = super()._advance(n_stages)
-                finally:
-                    calls, self._rows = self._rows.calls, None
-            st['engine_calls'] = st['host_waits'] = calls
-            return rec, st
+            return self._advance_python(super()._advance, n_stages)
         vega._sync_monte_carlo()
         draw = self.u is None
         u = np.zeros((self.particles, self.n)) if draw else self.u
@@ -489,50 +459,21 @@ class SMCSampler(SMCRun):
                         total[key] += val
         return record, total or {}
 
-    def derived(self):
-        """The derived parameters (``vega.derived_names()``: the marginalisation coefficients) of the rows of :meth:`samples`,
-        [N, m]: a pass over them after the run (:func:`vega_amd.ensemble.derived_rows`), the same block whichever driver ran."""
-        theta = np.asarray(self.vega._theta(None), dtype=np.float64)
-        return E.derived_rows(self.vega, self.cols, theta, self.samples()[0], self.chunk, self.lanes, self.const_hint)
-
     def write(self, path, name, derived=False, print_func=print):
         """getdist's chain ``name.txt`` (weight 1, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
         ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
         ones."""
-        extra = E.derived_for_write(self, derived, print_func)
-        if extra:
-            extra['derived'] = self.derived()
-        return write_run(self, path, name, self.names, **extra)
+        return write_run(self, path, name, self.names, **self._write_extra(derived, print_func, self.derived))
 
 
 def smc_settings(main_config, sample_params):
     """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
     has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them; ``sweeps``
     None: 4 n."""
-    import os
-    if 'SMC' not in main_config:
-        raise RuntimeError('run_sampler called, but no sampler config found')
-    sec = main_config['SMC']
-    limits = sample_params['limits']
-    for lims in limits.values():
-        if lims is None or None in tuple(lims):
-            raise ValueError(E._NO_LIMITS)
-    if 'path' not in sec:
-        raise ValueError('[SMC] needs a path')
-    path = Path(os.path.expandvars(sec.get('path')))
-    assert path.exists(), ("The sampler 'path' does not correspond to an existing folder. Create the output folder before "
-                           "running.")
+    sec, limits, out = E.section_settings(main_config, sample_params, 'SMC', name='smc')
     n = len(limits)
-    out = dict(sampler='SMC', path=path, name=sec.get('name', 'smc'), particles=sec.getint('particles', 1024),
-               ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None), seed=sec.getint('seed', 0),
-               driver=sec.get('driver', 'device'), max_stages=sec.getint('max_stages', None))
-    if 'derived' in sec:
-        out['derived'] = E.parse_derived(sec)
-    if 'replicas' in sec:
-        from .replicas import parse_replicas
-        out['replicas'] = parse_replicas(sec)
-    if out['driver'] not in ('device', 'python'):
-        raise ValueError("[SMC] driver: 'device' or 'python'")
+    out.update(particles=sec.getint('particles', 1024), ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None),
+               seed=sec.getint('seed', 0), max_stages=sec.getint('max_stages', None))
     if not 1 <= n <= MAXN:
         raise ValueError(f'[SMC] 1 .. {MAXN} sampled parameters')
     if not max(2 * n + 2, 8) <= out['particles'] <= MAX_PARTICLES:
