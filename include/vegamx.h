@@ -461,6 +461,34 @@ typedef struct {
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
                      int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats);
+/* E independent ensembles advanced together: a posterior for every Monte-Carlo mock, or the replicas of one run, as one device run.
+ * A run of W = 32 - 64 walkers hands the engine batches of 16 - 32 rows, far below what it is fast at; here the half-steps of all
+ * ensembles are decided by one kernel of E work-groups (k_ens_half_many: work-group e does for ensemble e exactly what the kernel
+ * of the single run does, nothing crosses ensembles) and their E W/2 proposal rows go through the engine as one stream of chunks
+ * of `chunk` on two lanes.  Ensemble e is by construction the chain the single run makes with spec->stream = streams[e] on the
+ * same data; its chi2 is evaluated in batches of another shape, so that its lnL may differ from the single run's in the last bits
+ * (E = 1 has the single run's batches and gives its chain bit for bit).
+ *   spec      as for the single run; spec->stream is not read
+ *   E, W      ensembles (>= 1) of W walkers each, W even and >= 2 n
+ *   streams   [E] the Philox stream of every ensemble (repeats allowed: equal streams on equal data give equal chains)
+ *   mock_row  [E] the row of the items' mock pools ensemble e is compared with, 0 <= row < n_mocks of every item's pool, repeats
+ *             allowed (the row of every engine row is written once per call, not per half-step); NULL: every ensemble reads the
+ *             installed data
+ *   x, lnL, accepted   [E][W][n], [E][W], [E][W] host: the walkers' state, read at entry and written back at exit
+ *   step0, n_steps, thin   as for the single run, shared by the ensembles
+ *   chain, chain_lnL       [E][rows][W][n], [E][rows][W] (host, NULL: not kept)
+ *   stats     the totals over the ensembles; per_ensemble [E][3] (NULL: not wanted): accepted, rejected outside the box, rejected
+ *             for a failed model, of this call
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever the single run refuses, for every ensemble;
+ * E < 1; streams NULL; a mock row that is negative or not below n_mocks; mock rows while an item has no pool; E W beyond the
+ * engine's int32 row count or a chain beyond size_t.  A HIP failure later returns -2 and leaves the engine usable. */
+int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W,
+                          const uint64_t* streams, const int32_t* mock_row,
+                          double* x, double* lnL, int64_t* accepted,
+                          int64_t step0, int32_t n_steps, int32_t thin,
+                          double* chain, double* chain_lnL,
+                          const vmx_ensemble_options* opt,
+                          vmx_ensemble_stats* stats, int64_t* per_ensemble);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

@@ -216,6 +216,8 @@ struct EnsWorkspace {
     DevBuf<double> x, lnl, prop, factor, chain, chain_lnl;
     DevBuf<int64_t> acc, n_box, n_fail;
     DevBuf<int32_t> inside, col;
+    DevBuf<int32_t> mock;               // vmx_ensemble_run_many: the mock row of every engine row [E H], written once per call
+    DevBuf<uint64_t> streams;           // and the ensembles' Philox streams [E]
 };
 
 struct EnsDev {
@@ -280,6 +282,81 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_de
         D.inside[k] = in ? 1 : 0;
         // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
         double* row = D.box.theta + (size_t)k * D.P;
+        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
+        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
+    }
+}
+
+// E independent ensembles, one work-group each (vmx_ensemble_run_many): block e does for ensemble e what k_ens_half does for its
+// one - the same expressions of vmx_ensemble.h in the same order, under the Philox stream streams[e].  Every per-ensemble array
+// of EnsDev has a leading E dimension here; the engine's rows of ensemble e are rows [e H, (e + 1) H) of the box workspace, so
+// that the E H proposal rows of a half-step are one stream of chunks for the engine.  Nothing crosses ensembles: no barrier beyond
+// __syncthreads().
+struct EnsManyDev {
+    EnsDev D;                       // (D.stream is not read)
+    const uint64_t* streams;        // [E]
+    int64_t rows;                   // chain rows of this call, per ensemble
+};
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_many(EnsManyDev M, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
+{
+    const EnsDev& D = M.D;
+    const int W = D.W, H = W / 2, n = D.n;
+    const size_t e = blockIdx.x;
+    const uint64_t stream = M.streams[e];
+    double* const x = D.x + e * W * n;
+    double* const lnl = D.lnl + e * W;
+    int64_t* const acc = D.acc + e * W;
+    int64_t* const n_box = D.n_box + e * W;
+    int64_t* const n_fail = D.n_fail + e * W;
+    double* const prop = D.prop + e * H * n;
+    double* const factor = D.factor + e * H;
+    int32_t* const inside_of = D.inside + e * H;
+    const double* const chi2 = D.box.chi2 + e * H;
+    const int32_t* const status = D.box.status + e * H;
+    double* const theta = D.box.theta + e * H * D.P;
+    if (s_dec >= 0) {
+        for (int k = threadIdx.x; k < H; k += blockDim.x) {
+            const int w = h_dec * H + k;
+            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, stream);
+            const double c2 = chi2[k];
+            const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
+            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
+            if (vmx_ens::accept(inside, ok, factor[k], lnl_new, lnl[w], b.w[2])) {
+                for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
+                lnl[w] = lnl_new;
+                acc[w] += 1;
+            } else if (!inside) n_box[w] += 1;
+            else if (!ok) n_fail[w] += 1;
+        }
+        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
+            __syncthreads();
+            const size_t r = e * M.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
+            if (D.chain)
+                for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
+            if (D.chain_lnl)
+                for (int q = threadIdx.x; q < W; q += blockDim.x) D.chain_lnl[r * W + q] = lnl[q];
+        }
+    }
+    if (s_prop < 0) return;
+    __syncthreads();            // (the partners of the next half are the walkers just decided)
+    for (int k = threadIdx.x; k < H; k += blockDim.x) {
+        const int w = h_prop * H + k;
+        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
+        const int64_t j = vmx_ens::partner(b.w[0], H);
+        const double* c = x + (size_t)((1 - h_prop) * H + j) * n;
+        const double* s = x + (size_t)w * n;
+        const double z = vmx_ens::stretch_z(D.a, b.w[1]);
+        double* y = prop + (size_t)k * n;
+        bool in = true;
+        for (int d = 0; d < n; ++d) {
+            const double v = vmx_ens::propose(c[d], s[d], z);
+            y[d] = v;
+            in = in && v >= D.box.lo[d] && v <= D.box.hi[d];
+        }
+        factor[k] = vmx_ens::log_factor(n, z);
+        inside_of[k] = in ? 1 : 0;
+        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
+        double* row = theta + (size_t)k * D.P;
         for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
         for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
     }
@@ -4247,6 +4324,134 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
         R.accepted += accepted[w] - acc0[w];
         R.rejected_outside_box += box[w];
         R.rejected_failed_model += failed[w];
+    }
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// E independent ensembles advanced together (k_ens_half_many): vmx_ensemble_run line for line, the E H proposal rows of a
+// half-step as one stream of chunks for the engine, every row with the mock of its ensemble
+int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                          const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                          int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
+                          vmx_ensemble_stats* stats, int64_t* per_ensemble)
+{
+    REQUIRE(e && e->finalized && spec && x && lnL && accepted, "vmx_ensemble_run_many");
+    REQUIRE(E >= 1, "vmx_ensemble_run_many: at least one ensemble");
+    REQUIRE(streams, "vmx_ensemble_run_many: a Philox stream for every ensemble");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box("vmx_ensemble_run_many", e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
+    const int n = spec->n, P = e->n_params;
+    REQUIRE(W >= 2 * n && W % 2 == 0, "vmx_ensemble_run_many: an even number of walkers, at least twice the sampled columns");
+    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), "vmx_ensemble_run_many: the stretch scale a must exceed 1");
+    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, "vmx_ensemble_run_many: thin >= 1, n_steps >= 0, step0 >= 0");
+    const int H = W / 2;
+    const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
+    // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
+    REQUIRE((int64_t)E * W <= INT32_MAX, "vmx_ensemble_run_many: E W exceeds the engine's row count");
+    const size_t EW = (size_t)E * W, per_row = (size_t)std::max(n, P) * sizeof(double);
+    REQUIRE(EW <= SIZE_MAX / per_row && (rows <= 0 || EW * per_row <= SIZE_MAX / (size_t)rows),
+            "vmx_ensemble_run_many: the chain is too large");
+    for (size_t w = 0; w < EW; ++w) {
+        REQUIRE(std::isfinite(lnL[w]), "vmx_ensemble_run_many: a start walker has a non-finite lnL");
+        for (int i = 0; i < n; ++i) {
+            const double v = x[w * n + i];
+            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], "vmx_ensemble_run_many: a start walker lies outside the box");
+        }
+    }
+    if (mock_row)
+        for (int q = 0; q < E; ++q)
+            for (auto* it : e->items) {
+                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, "vmx_ensemble_run_many: mock rows, but an item has no mock pool");
+                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, "vmx_ensemble_run_many: mock row outside the pool");
+            }
+    if (LikelihoodSession::check("vmx_ensemble_run_many", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    const int EH = E * H;
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->ensws) e->ensws = new EnsWorkspace();
+    EnsWorkspace& S = *e->ensws;
+    if (ensure(S.x, EW * n) || ensure(S.lnl, EW) || ensure(S.acc, EW) || ensure(S.n_box, EW) || ensure(S.n_fail, EW) ||
+        ensure(S.prop, (size_t)EH * n) || ensure(S.factor, EH) || ensure(S.inside, EH) || ensure(S.col, n) || ensure(S.streams, E) ||
+        (mock_row && ensure(S.mock, EH)))
+        return -2;
+    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
+    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
+    hipStream_t st = e->stream;
+    EnsManyDev M{};
+    EnsDev& D = M.D;
+    if (S.box.upload(EH, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
+    HIP_OK(hipMemcpyAsync(S.x.p, x, EW * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, EW * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.acc.p, accepted, EW * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(S.n_box.p, 0, EW * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.n_fail.p, 0, EW * sizeof(int64_t), st));
+    HIP_OK(hipMemcpyAsync(S.col.p, spec->col, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.streams.p, streams, (size_t)E * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    std::vector<int32_t> row_mock;          // (static for the call: row e H + k reads the mock of ensemble e)
+    if (mock_row) {
+        row_mock.resize(EH);
+        for (int q = 0; q < E; ++q) std::fill(row_mock.begin() + (size_t)q * H, row_mock.begin() + (size_t)(q + 1) * H, mock_row[q]);
+        HIP_OK(hipMemcpyAsync(S.mock.p, row_mock.data(), (size_t)EH * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    }
+    const int32_t* d_mock = mock_row ? S.mock.p : nullptr;
+
+    D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p; D.n_box = S.n_box.p; D.n_fail = S.n_fail.p;
+    D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
+    D.col = S.col.p;
+    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
+    D.seed = spec->seed; D.stream = 0; D.step0 = step0;
+    M.streams = S.streams.p; M.rows = rows;
+
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
+    vmx_ensemble_stats R{};
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
+    const auto t_loop = std::chrono::steady_clock::now();
+    const int64_t halves = 2 * (int64_t)n_steps;
+    const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
+    if (halves > 0) hipLaunchKernelGGL(k_ens_half_many, grid, block, 0, st, M, (int64_t)-1, 0, step0, 0);
+    HIP_OK(hipGetLastError());
+    for (int64_t q = 0; q < halves; ++q) {
+        const int64_t s = step0 + q / 2;
+        const int h = (int)(q % 2);
+        const int calls = L.evaluate(S.box.theta.p, EH, S.box.chi2.p, S.box.status.p, d_mock, true);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
+        const int64_t nq = q + 1;
+        hipLaunchKernelGGL(k_ens_half_many, grid, block, 0, st, M, s, h,
+                           nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
+        HIP_OK(hipGetLastError());
+    }
+    std::vector<int64_t> acc0(accepted, accepted + EW), box(EW), failed(EW);
+    HIP_OK(hipMemcpyAsync(x, S.x.p, EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, EW * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(box.data(), S.n_box.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(failed.data(), S.n_fail.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * EW * sizeof(double), hipMemcpyDeviceToHost, st));
+    R.seconds_enqueuing = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
+    HIP_OK(hipStreamSynchronize(st));       // (the call's only wait: the segment is enqueued as a whole)
+    R.host_synchronisations = 1;
+    R.steps = n_steps;
+    R.proposals = (int64_t)n_steps * (int64_t)EW;
+    for (int q = 0; q < E; ++q) {
+        int64_t took = 0, out = 0, bad = 0;
+        for (size_t w = (size_t)q * W; w < (size_t)(q + 1) * W; ++w) {
+            took += accepted[w] - acc0[w];
+            out += box[w];
+            bad += failed[w];
+        }
+        if (per_ensemble) { per_ensemble[3 * q] = took; per_ensemble[3 * q + 1] = out; per_ensemble[3 * q + 2] = bad; }
+        R.accepted += took;
+        R.rejected_outside_box += out;
+        R.rejected_failed_model += bad;
     }
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;

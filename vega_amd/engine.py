@@ -262,6 +262,9 @@ def load_library():
                                    C.POINTER(FitResultArrays), C.POINTER(FitStats)]
     lib.vmx_ensemble_run.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, dptr, dptr, C.POINTER(C.c_int64), C.c_int64,
                                      C.c_int32, C.c_int32, dptr, dptr, C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats)]
+    lib.vmx_ensemble_run_many.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, C.c_int32, C.POINTER(C.c_uint64), iptr, dptr,
+                                          dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, dptr, dptr,
+                                          C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
@@ -315,7 +318,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1075,6 +1078,44 @@ class Engine:
                                               _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None,
                                               C.byref(opt), C.byref(stats)))
         return chain, chain_lnl, _stats_dict(stats)
+
+    def ensemble_run_many(self, cols, lo, hi, theta_fixed, x, lnl, accepted, streams, step0, n_steps, mock_rows=None, thin=1, a=2.0,
+                          log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
+        """``n_steps`` steps of E independent ensembles in one device run (include/vegamx.h: vmx_ensemble_run_many): ``x`` [E, W, n]
+        / ``lnl`` [E, W] / ``accepted`` int64 [E, W] the walkers' state (updated in place), ``streams`` [E] the Philox stream of every
+        ensemble, ``mock_rows`` [E] the pool row every ensemble is compared with (None: the installed data); the rest as for
+        :meth:`ensemble_run`.  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], statistics); the statistics carry
+        ``per_ensemble`` int64 [E, 3]: accepted, rejected outside the box, rejected for a failed model."""
+        cols = np.ascontiguousarray(cols, dtype=np.int32)
+        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
+        _in_place(np.float64, x=x, lnl=lnl)
+        _in_place(np.int64, accepted=accepted)
+        if x.ndim != 3 or x.shape[2] != cols.size or lnl.shape != x.shape[:2] or accepted.shape != x.shape[:2] \
+                or theta_fixed.shape != (self.n_params,):
+            raise ValueError('x [E, W, n], lnl [E, W], accepted [E, W], theta_fixed [n_params]')
+        E, W = x.shape[:2]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if (streams is not None and streams.shape != (E,)) or (mock_rows is not None and mock_rows.shape != (E,)):
+            raise ValueError('streams [E], mock_rows [E]')
+        step0, n_steps, thin = int(step0), int(n_steps), int(thin)
+        rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
+        chain = np.empty((E, rows, W, cols.size)) if keep_chain else None
+        chain_lnl = np.empty((E, rows, W)) if keep_chain else None
+        per = np.zeros((E, 3), dtype=np.int64)
+        spec = EnsembleSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), float(a), float(log_norm), int(seed), 0,
+                            _dp(theta_fixed))
+        opt = EnsembleOptions(int(const_hint), int(chunk), int(lanes), 0)
+        stats = EnsembleStats()
+        i64 = C.POINTER(C.c_int64)
+        self._check(self.lib.vmx_ensemble_run_many(
+            self._h, C.byref(spec), E, W, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), _dp(x), _dp(lnl), accepted.ctypes.data_as(i64), step0, n_steps, thin,
+            _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None, C.byref(opt), C.byref(stats),
+            per.ctypes.data_as(i64)))
+        return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
                    seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):

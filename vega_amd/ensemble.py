@@ -146,6 +146,41 @@ def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi
     return chain, chain_lnl, st
 
 
+def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate):
+    """``n_steps`` steps of E independent ensembles advanced together, in NumPy: the state ``x`` [E, W, n], ``lnl`` [E, W],
+    ``accepted`` [E, W] (updated in place), ensemble e on the Philox stream ``streams[e]``.  Every half-step makes the decisions of
+    :func:`python_steps` per ensemble; only the likelihood is joined: ``evaluate(rows, h)`` -> (chi2 [E W/2], status [E W/2]) for
+    the E W/2 rows [E W/2, n] of the half, ensemble e's at [e W/2, (e + 1) W/2) - the rows the device driver hands the engine.
+    Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats, per_ensemble [E, 3]: accepted, rejected outside the box,
+    rejected for a failed model)."""
+    E, W, n = x.shape
+    H = W // 2
+    rows = (step0 + n_steps) // thin - step0 // thin
+    chain, chain_lnl = np.empty((E, rows, W, n)), np.empty((E, rows, W))
+    per = np.zeros((E, 3), dtype=np.int64)
+    for s in range(step0, step0 + n_steps):
+        for h in (0, 1):
+            mine = slice(h * H, (h + 1) * H)
+            props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi) for e in range(E)]
+            chi2, status = evaluate(np.concatenate([np.where(inside[:, None], y, x[e, mine])
+                                                    for e, (y, inside, _, _) in enumerate(props)]), h)
+            for e, (y, inside, factor, b) in enumerate(props):
+                c2, st_e = chi2[e * H:(e + 1) * H], status[e * H:(e + 1) * H]
+                ok = model_ok(st_e, c2)
+                lnl_new = log_lik(log_norm, c2)
+                acc = accept(inside, ok, factor, lnl_new, lnl[e, mine], b[:, 2])
+                x[e, mine][acc] = y[acc]
+                lnl[e, mine][acc] = lnl_new[acc]
+                accepted[e, mine] += acc
+                per[e] += (int(acc.sum()), int((~inside).sum()), int((inside & ~ok).sum()))
+        if (s + 1) % thin == 0:
+            r = (s + 1) // thin - step0 // thin - 1
+            chain[:, r], chain_lnl[:, r] = x, lnl
+    st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
+              rejected_failed_model=int(per[:, 2].sum()))
+    return chain, chain_lnl, st, per
+
+
 def write_getdist(path, name, names, chain, chain_lnl, weights=None, derived=None, derived_names=None, derived_labels=None):
     """getdist's plain-text chain: ``name.txt`` (one row per sample: weight 1, -lnL, the parameters) and ``name.paramnames``
     (one ``name label`` line per parameter, label = name).  ``chain`` [..., n], ``chain_lnl`` [...]; ``weights`` [...]: a
@@ -350,13 +385,21 @@ class EngineRows:
             eng.set_lanes(self.saved_lanes)
         return False
 
-    def chi2(self, theta_rows):
+    def chi2(self, theta_rows, mock_rows=None):
+        """``mock_rows`` [R] (None: the installed data): per row the row of the mock pools it is compared with."""
         import torch
         t_dev = torch.from_numpy(np.ascontiguousarray(theta_rows)).to(self.device)
         R = theta_rows.shape[0]
         chi2 = np.empty(R)
+        if mock_rows is None:
+            for off in range(0, R, self.chunk):
+                chi2[off:off + self.chunk] = self.vega.chi2_batch_device(t_dev[off:off + self.chunk].contiguous()).cpu().numpy()
+                self.calls += 1
+            return chi2
+        m_dev = torch.from_numpy(np.ascontiguousarray(mock_rows, dtype=np.int32)).to(self.device)
         for off in range(0, R, self.chunk):
-            chi2[off:off + self.chunk] = self.vega.chi2_batch_device(t_dev[off:off + self.chunk].contiguous()).cpu().numpy()
+            chi2[off:off + self.chunk] = self.vega.chi2_batch_device(t_dev[off:off + self.chunk].contiguous(),
+                                                                     mock_rows=m_dev[off:off + self.chunk].contiguous()).cpu().numpy()
             self.calls += 1
         return chi2
 
@@ -606,6 +649,194 @@ class EnsembleSampler(EngineSampler):
         return write_getdist(path, name, self.names, self.get_chain(flat=True), self.get_log_lik(flat=True), **extra)
 
 
+# ------------------------------------------------------------------ many ensembles in one run
+class EnsembleSet(EngineSampler):
+    """E independent ensembles of W walkers each over the sampled parameters of ``vega``, advanced together: the half-steps of all
+    ensembles are decided at once and their E W/2 proposal rows go through the engine as one stream of chunks (``'device'``:
+    vmx_ensemble_run_many, one work-group per ensemble; ``'python'``: :func:`python_steps_many` over ``chi2_batch_device``, cut
+    into the same chunks).  Ensemble e runs on the Philox stream ``streams[e]`` (default ``range(E)``) from the walkers
+    ``EnsembleSampler(..., seed=seed, stream=streams[e])`` draws, and is the chain that sampler makes - up to the last bits of lnL
+    where the engine's batches are shaped differently.  ``mock_rows`` [E]: the row of the installed mock
+    pools every ensemble is compared with - a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`);
+    None: every ensemble reads the data the interface has installed - replicas of one run.  An engine group takes ``'python'``."""
+
+    def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
+                 sample_params=None, chunk=0, lanes=0, const_hint=-1):
+        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        self.E, self.W = int(ensembles), int(walkers)
+        if self.E < 1:
+            raise ValueError('ensembles: at least one')
+        if self.W % 2 or self.W < 2 * self.n:
+            raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
+        self.streams = np.arange(self.E, dtype=np.uint64) if streams is None else np.array(streams, dtype=np.uint64)
+        self.mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
+        if self.streams.shape != (self.E,) or (self.mock_rows is not None and self.mock_rows.shape != (self.E,)):
+            raise ValueError(f'streams, mock_rows: one entry for each of the {self.E} ensembles')
+        if self.mock_rows is not None and np.any(self.mock_rows < 0):
+            raise ValueError('mock_rows: rows of the installed mock pools, none negative')
+        self.a, self.seed = float(a), int(seed)
+        if not self.a > 1.0:
+            raise ValueError('a: the stretch scale must exceed 1')
+        self.thin = int(thin)
+        if self.thin < 1:
+            raise ValueError('thin >= 1')
+        self.segment = max(1, int(segment))
+        self.reset()
+
+    def reset(self):
+        self.x = self.lnl = None
+        self.accepted = np.zeros((self.E, self.W), dtype=np.int64)
+        self.per_ensemble = np.zeros((self.E, 3), dtype=np.int64)
+        self.step = 0
+        self._chain, self._chain_lnl = [], []
+        self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
+                          seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
+
+    # ---- start
+    def _member_settings(self, e):
+        """An :class:`EnsembleSampler` with the settings of ensemble e (no state): what draws its start and reads its results."""
+        return EnsembleSampler(self.vega, self.W, a=self.a, seed=self.seed, thin=self.thin, driver=self.driver_asked,
+                               segment=self.segment, sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))),
+                                                                         values=self.values, errors=self.errors),
+                               stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint)
+
+    def _start_positions(self, start, init_scale):
+        if not isinstance(start, str):
+            start = np.array(start, dtype=np.float64)
+            if start.shape != (self.E, self.W, self.n):
+                raise ValueError(f'start: an array [{self.E}, {self.W}, {self.n}], "ball" or "prior"')
+        return np.stack([self._member_settings(e)._start_positions(start if isinstance(start, str) else start[e], init_scale)
+                         for e in range(self.E)])
+
+    def _start_chi2(self, theta_w):
+        """chi2 of the start walkers [E, W, n_params]: ensemble by ensemble through the host entry, as a single sampler evaluates
+        its start - against the ensemble's own mock when the set has mock rows."""
+        vega, eng = self.vega, self.vega.engine
+        if self.mock_rows is None:
+            return np.stack([np.asarray(vega.chi2_batch(theta_w[e]), dtype=np.float64) for e in range(self.E)])
+        try:
+            out = []
+            for e in range(self.E):
+                vega._sync_monte_carlo()
+                eng.set_mock_index(np.full(min(self.W, eng.max_batch), self.mock_rows[e], dtype=np.int32))
+                out.append(np.asarray(vega.chi2_batch(theta_w[e]), dtype=np.float64))
+        finally:
+            eng.set_mock_index(None)
+        return np.stack(out)
+
+    def _prepare(self, start, init_scale):
+        theta = self._fixed_row()
+        if self.x is None:
+            x0 = self._start_positions(start, init_scale)
+            theta_w = np.tile(theta, (self.E, self.W, 1))
+            theta_w[:, :, self.cols] = x0
+            first = theta_w[0, 0]
+        else:
+            x0, first = None, theta
+        self._pick_driver(first, 'ensemble_run_many')
+        if self.x is None:
+            self.x, self.lnl = x0, log_lik(self.log_norm(), self._start_chi2(theta_w))
+            if not np.all(np.isfinite(self.lnl)):
+                raise ValueError('a start walker has a non-finite log-likelihood')
+        return theta
+
+    # ---- run
+    def run(self, n_steps, start='ball', init_scale=1.0):
+        """Advance every ensemble by ``n_steps`` steps (the first call draws the starts: ``'ball'``, ``'prior'`` - ensemble e as
+        ``EnsembleSampler(seed, stream=streams[e])`` draws them - or an array [E, W, n]).  Later calls continue the chains."""
+        theta = self._prepare(start, init_scale)
+        done = 0
+        while done < n_steps:
+            k = min(self.segment, n_steps - done)
+            segment = self._segment_device if self.driver == 'device' else self._segment_python
+            chain, chain_lnl, st, per = segment(theta, k)
+            self._chain.append(chain)
+            self._chain_lnl.append(chain_lnl)
+            self.per_ensemble += per
+            for key in st:
+                if key in self.stats:
+                    self.stats[key] += st[key]
+            self.stats['calls'] += 1
+            self.step += k
+            done += k
+        return self
+
+    def _segment_device(self, theta, k):
+        self.vega._sync_monte_carlo()
+        chain, chain_lnl, st = self.vega.engine.ensemble_run_many(
+            self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.step, k,
+            mock_rows=self.mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(), seed=self.seed,
+            const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes)
+        return chain, chain_lnl, st, st.pop('per_ensemble')
+
+    def _segment_python(self, theta, k):
+        """The readable restatement: the decisions of :func:`python_steps` per ensemble, chi2 of the E W/2 rows of a half through
+        ``chi2_batch_device`` in the device driver's chunks, with its table level and lanes and every row's own mock."""
+        import time
+        t0 = time.perf_counter()
+        H = self.W // 2
+        row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, H)
+        with self._engine_rows() as rows:
+            def evaluate(rows_x, h):
+                rows_t = np.repeat(theta[None, :], self.E * H, axis=0)
+                rows_t[:, self.cols] = rows_x
+                # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+                return rows.chi2(rows_t, mock_rows=row_mock), np.zeros(self.E * H, dtype=np.int32)
+
+            chain, chain_lnl, st, per = python_steps_many(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a,
+                                                          self.seed, self.streams, self.lo, self.hi, self.log_norm(), evaluate)
+        st['engine_calls'] = rows.calls
+        st['host_synchronisations'] = rows.calls
+        st['seconds'] = time.perf_counter() - t0
+        return chain, chain_lnl, st, per
+
+    # ---- results
+    def _stack(self, parts, tail, discard, thin, flat):
+        arr = np.concatenate(parts, axis=1) if parts else np.empty((self.E, 0, self.W) + tail)
+        arr = arr[:, int(discard)::int(thin)]
+        return arr.reshape((self.E, -1) + arr.shape[3:]) if flat else arr
+
+    def get_chain(self, discard=0, thin=1, flat=False):
+        """Recorded positions [E, rows, W, n] (rows = steps / thin of the set), ``discard`` / ``thin`` in recorded rows; ``flat``:
+        [E, rows W, n]."""
+        return self._stack(self._chain, (self.n,), discard, thin, flat)
+
+    def get_log_lik(self, discard=0, thin=1, flat=False):
+        return self._stack(self._chain_lnl, (), discard, thin, flat)
+
+    @property
+    def acceptance_fraction(self):
+        return self.accepted / max(self.step, 1)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5):
+        """Integrated autocorrelation time per ensemble and parameter in recorded rows, [E, n] (:func:`integrated_time`)."""
+        chain = self.get_chain(discard=discard, thin=thin)
+        return np.array([integrated_time(chain[e], c=c) for e in range(self.E)])
+
+    def member(self, e):
+        """Ensemble ``e`` as a sampler that has run: :class:`EnsembleSampler`'s result methods (``get_chain``, ``get_log_lik``,
+        ``acceptance_fraction``, ``get_autocorr_time``, ``get_derived``, ``write``) over copies of its part of the set's state.
+        Read-only: it cannot be advanced."""
+        if not 0 <= int(e) < self.E:
+            raise IndexError(f'member: 0 .. {self.E - 1}')
+        e = int(e)
+        m = self._member_settings(e)
+        m.driver = self.driver
+        m.run = m.reset = _read_only
+        if self.x is not None:
+            m.x, m.lnl = self.x[e].copy(), self.lnl[e].copy()
+        m.accepted, m.step = self.accepted[e].copy(), self.step
+        m._chain[:] = [part[e] for part in self._chain]
+        m._chain_lnl[:] = [part[e] for part in self._chain_lnl]
+        took, out, bad = (int(v) for v in self.per_ensemble[e])
+        m.stats = dict(self.stats, proposals=self.step * self.W, accepted=took, rejected_outside_box=out, rejected_failed_model=bad)
+        return m
+
+
+def _read_only(*args, **kwargs):
+    raise RuntimeError('a member of an EnsembleSet is read-only: advance the set')
+
+
 # ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
 _ENSEMBLE_DEFAULTS = dict(sampler='Ensemble', name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
                           driver='device')
@@ -681,7 +912,32 @@ def sampler_settings(main_config, sample_params):
         raise ValueError('[Ensemble] steps and thin must be positive')
     if not out['a'] > 1.0:
         raise ValueError('[Ensemble] a: the stretch scale must exceed 1')
+    if 'mocks' in sec:
+        out['mocks'] = _parse_mocks(sec, main_config)
+    if 'together' in sec:
+        try:
+            out['together'] = sec.getboolean('together')
+        except ValueError:
+            raise ValueError('[Ensemble] together: True or False') from None
     return out
+
+
+def _parse_mocks(sec, main_config):
+    """``mocks = M`` of ``[Ensemble]``: a posterior for each of M Monte-Carlo mocks in one run; it needs the Monte-Carlo mode."""
+    try:
+        M = sec.getint('mocks')
+    except ValueError:
+        raise ValueError('[Ensemble] mocks: a whole number, at least 1') from None
+    if M < 1:
+        raise ValueError('[Ensemble] mocks: a whole number, at least 1')
+    control = main_config['control']
+    if not control.getboolean('run_montecarlo', False):
+        raise ValueError('[Ensemble] mocks needs "run_montecarlo = True" in the "[control]" section')
+    if 'monte carlo' not in main_config:
+        raise ValueError('[Ensemble] mocks needs a "[monte carlo]" section')
+    if 'replicas' in sec and sec.getint('replicas') > 1:
+        raise ValueError('[Ensemble] mocks and replicas > 1 do not combine: every mock has an ensemble of its own')
+    return M
 
 
 def build_sampler(vega, cfg, sample_params, stream=0):
@@ -743,6 +999,14 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, rank=None, w
         raise ValueError('You asked to run over a Monte Carlo simulation, but no "[monte carlo]" section provided.')
     cfg = sampler_settings(vega.main_config, sample_params)
     kind = {'Nested': 'nested', 'SMC': 'SMC'}.get(cfg['sampler'], 'ensemble')
+    if cfg.get('mocks'):
+        sampler = None
+        if rank == 0:
+            print_func(f'Sampling the posteriors of {cfg["mocks"]} Monte-Carlo mocks in one run')
+            sampler = _sample_config_mocks(vega, cfg, sample_params, control)
+        group.barrier()
+        print_func('Finished running sampler')
+        return sampler
     if cfg.get('replicas', 1) > 1:
         print_func(f'Running {cfg["replicas"]} replicas of the {kind} sampler on {world} rank(s)')
         out = replicas.run_replicas(vega, cfg, sample_params, group, print_func)
@@ -759,6 +1023,29 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, rank=None, w
         sampler.write(cfg['path'], cfg['name'], derived=cfg.get('derived', False), print_func=print_func)
     group.barrier()
     print_func('Finished running sampler')
+    return sampler
+
+
+def _sample_config_mocks(vega, cfg, sample_params, control):
+    """``[Ensemble] mocks = M``: M mocks around the Monte-Carlo fiducial with ``[control] mc_seed``, their posteriors as one
+    :class:`EnsembleSet` (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`); writes the getdist chains ``<name>_mock<m>.txt``
+    with one ``<name>.paramnames`` and the summary table ``mock_posteriors.fits``.  Returns the set."""
+    mc = vega.analysis
+    scale = None
+    if vega._use_global_cov and 'global_cov_rescale' in control:
+        scale = control.getfloat('global_cov_rescale')
+    mocks = mc.create_mocks(vega.mc_fiducial_model, cfg['mocks'], seed=control.getint('mc_seed', 0), scale=scale,
+                            forecast=control.getboolean('forecast', False))
+    if 'global' in mc.mc_mocks:
+        mocks = mc.mc_mocks['global']
+    sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],
+                              scale=scale, sample_params=sample_params, driver=cfg['driver'])
+    chain, lnl = sampler.get_chain(), sampler.get_log_lik()
+    for m in range(sampler.E):
+        table, lines = getdist_table(sampler.names, chain[m], lnl[m])
+        np.savetxt(Path(cfg['path']) / f'{cfg["name"]}_mock{m}.txt', table, fmt='%.17g')
+    write_paramnames(cfg['path'], cfg['name'], lines)
+    mc.write_mock_posteriors(cfg['path'])
     return sampler
 
 

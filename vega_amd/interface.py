@@ -502,12 +502,14 @@ class VegaInterface:
             res = res + (coeff,)
         return res if len(res) > 1 else res[0]
 
-    def chi2_batch_device(self, theta, out=None):
+    def chi2_batch_device(self, theta, out=None, mock_rows=None):
         """chi2 of walkers that are already in HBM: ``theta`` a CUDA float64 tensor [n, n_params] (column order
         ``self.param_names``) on the engine's device -> CUDA tensor [n].  Nothing crosses PCIe: chunks of ``max_batch``
         go through ``vmx_eval_device`` on the engine's stream, which is ordered after the caller's current torch stream
         and before whatever that stream does next (events, no host synchronisation).  Failed walkers carry the
-        reference's 1e100 sentinel.  Frozen-metal pins are the caller's contract here (no host copy to check)."""
+        reference's 1e100 sentinel.  Frozen-metal pins are the caller's contract here (no host copy to check).
+        ``mock_rows``: a CUDA int32 tensor [n], per walker the row of the installed mock pools it is compared with
+        (``Engine.eval_device_mocks``); None: the data every evaluation reads."""
         import torch
         if not (theta.is_cuda and theta.dtype == torch.float64 and theta.dim() == 2 and theta.is_contiguous()
                 and theta.shape[1] == len(self.param_names)):
@@ -525,13 +527,27 @@ class VegaInterface:
         else:
             torch.cuda.ExternalStream(eng.stream_handle(), device=theta.device).wait_event(current.record_event())
         mb = eng.max_batch
+        if mock_rows is not None and not (mock_rows.is_cuda and mock_rows.dtype == torch.int32 and mock_rows.shape == (n,)
+                                          and mock_rows.is_contiguous()):
+            raise ValueError('mock_rows: contiguous CUDA int32 tensor [n]')
         if hasattr(eng, 'eval_device_tensor'):      # (one engine per transform setting: engine_group.py)
-            for lo in range(0, n, mb):
-                eng.eval_device_tensor(theta[lo:lo + mb], out[lo:lo + mb])
+            if mock_rows is not None:
+                host_rows = mock_rows.cpu().numpy()
+            try:
+                for lo in range(0, n, mb):
+                    if mock_rows is not None:
+                        eng.set_mock_index(host_rows[lo:lo + mb])
+                    eng.eval_device_tensor(theta[lo:lo + mb], out[lo:lo + mb])
+            finally:
+                if mock_rows is not None:
+                    eng.set_mock_index(None)
             return out
         for lo in range(0, n, mb):
             hi = min(lo + mb, n)
-            eng.eval_device(theta[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr())
+            if mock_rows is None:
+                eng.eval_device(theta[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr())
+            else:
+                eng.eval_device_mocks(theta[lo:hi].data_ptr(), hi - lo, out[lo:hi].data_ptr(), mock_rows[lo:hi].data_ptr())
             # (with two lanes consecutive chunks run on alternating streams: the caller's stream waits for each)
             current.wait_event(torch.cuda.ExternalStream(eng.last_stream_handle(), device=theta.device).record_event())
         return out
@@ -851,6 +867,7 @@ class VegaInterface:
         from .montecarlo import MonteCarlo
         self.freeze_metals()
         fiducial_model = self.get_fiducial_for_monte_carlo(print_func)
+        self.mc_fiducial_model = fiducial_model         # (kept: more mocks around it later cost no second fit)
         control = self.main_config['control']
         if self.problem.mc_config is not None:
             self.sample_params = self.problem.mc_config['sample']       # "Reset the minimizer" (:523-525)

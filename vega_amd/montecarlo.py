@@ -468,6 +468,99 @@ class MonteCarlo:
         self.has_monte_carlo = True
         return res
 
+    def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
+                     sample_params=None, driver='device', keep_chains=True, fiducial_model=None):
+        """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
+        (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
+        only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
+        ``fiducial_model`` - default: the model at the current parameters - with ``seed`` and ``scale``), or passed in
+        (``mocks``: {correlation: [M, n_masked]}, or [M, sum n_masked] vectors of the global masked data); their pools go to the
+        engine as for the fits, with the rescaled inverse covariance while the run lasts.  ``sample_params``: default the
+        ``[monte carlo]`` section's; ``walkers``: default max(32, 2 n); ``burn``: steps dropped from the summaries, default a third.
+
+        Keeps ``mc_posteriors``: names, per mock ``mean`` / ``sd`` [M, n] and ``covariance`` [M, n, n] of the rows after ``burn``,
+        ``tau`` [M, n] (integrated autocorrelation times in recorded rows), ``acceptance`` [M], ``n_eff`` [M] (rows after burn x
+        walkers / the largest tau) and the run's settings; with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
+        ``mc_chain_lnl``.  Returns the set."""
+        from .ensemble import EnsembleSet, SampledBox
+        vega = self.vega
+        prob = vega.problem
+        if sample_params is None:
+            sample_params = prob.mc_config['sample'] if prob.mc_config is not None else vega.sample_params
+        vega.freeze_metals()            # (it may replace the engine: before the pools go to it)
+        if mocks is None:
+            if num_mocks is None:
+                raise ValueError('sample_mocks: num_mocks, or the mocks themselves')
+            if fiducial_model is None:
+                fiducial_model = vega.compute_model()
+            mocks = self.create_mocks(fiducial_model, int(num_mocks), seed=seed, scale=scale)
+        elif not isinstance(mocks, dict):
+            whole = np.ascontiguousarray(np.atleast_2d(np.asarray(mocks, dtype=float)))
+            self.mc_mocks = {'global': whole}
+            self.current_mc_mock = whole[-1]
+            mocks = split_global(prob, whole)
+        else:
+            self.mc_mocks = mocks
+        M = len(next(iter(mocks.values())))
+        if num_mocks is not None and int(num_mocks) != M:
+            raise ValueError(f'sample_mocks: num_mocks = {num_mocks}, but {M} mocks were passed')
+        n = SampledBox(vega, sample_params).n
+        walkers = max(32, 2 * n) if walkers is None else int(walkers)
+        steps, thin = int(steps), int(thin)
+        burn = steps // 3 if burn is None else int(burn)
+        if not 0 <= burn < steps:
+            raise ValueError('sample_mocks: 0 <= burn < steps')
+        eng = vega.engine
+        scales = item_scales(prob, scale)
+        rescaled = [name for name in mocks if scales[name] != 1. and prob.items[name].cov is not None and not vega._use_global_cov]
+        sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
+                              sample_params=sample_params)
+        try:
+            for name, pool in mocks.items():
+                eng.set_mock_pool(name, pool)
+            for name in rescaled:
+                # (marginalize-in-fit: chi2_matrix keeps the projector of the unscaled covariance, as in _fit_mocks)
+                eng.set_invcov(name, prob.items[name].chi2_matrix / scales[name])
+            sampler.run(steps)
+        finally:
+            for name in rescaled:
+                eng.set_invcov(name, prob.items[name].chi2_matrix)
+        first = burn // thin
+        post = sampler.get_chain(discard=first)
+        flat = post.reshape(M, -1, n)
+        tau = sampler.get_autocorr_time(discard=first)
+        self.mc_posteriors = dict(
+            names=list(sampler.names), mean=flat.mean(axis=1), sd=flat.std(axis=1, ddof=1),
+            covariance=np.array([np.atleast_2d(np.cov(rows.T)) for rows in flat]), tau=tau,
+            acceptance=sampler.acceptance_fraction.mean(axis=1), n_eff=flat.shape[1] / tau.max(axis=1),
+            steps=steps, burn=burn, thin=thin, walkers=walkers, seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+        self.mc_chains = sampler.get_chain() if keep_chains else None
+        self.mc_chain_lnl = sampler.get_log_lik() if keep_chains else None
+        return sampler
+
+    def write_mock_posteriors(self, directory, cpu_id=None, overwrite=True):
+        """`mock_posteriors[_<cpu_id>].fits` under ``directory``: one table ``POSTERIORS`` with one row per mock of
+        :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
+        ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  Returns the path."""
+        from pathlib import Path
+        from . import fitslite
+        post = getattr(self, 'mc_posteriors', None)
+        if post is None:
+            raise ValueError('No mock posteriors found. Run sample_mocks() first.')
+        names, n = post['names'], len(post['names'])
+        M = post['mean'].shape[0]
+        cols = []
+        for j, nm in enumerate(names):
+            cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]
+        cols += [('acceptance', 'D', post['acceptance']), ('n_eff', 'D', post['n_eff']),
+                 ('covariance', f'{n * n}D' if n > 1 else 'D', post['covariance'].reshape(M, n * n) if n > 1 else post['covariance'].reshape(M))]
+        header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
+        directory = Path(directory)
+        directory.mkdir(parents=True, exist_ok=True)
+        path = directory / ('mock_posteriors.fits' if cpu_id is None else f'mock_posteriors_{cpu_id}.fits')
+        fitslite.write_tables(str(path), [('POSTERIORS', cols, header)], overwrite=overwrite)
+        return path
+
     def write(self, directory, cpu_id=None, overwrite=False):
         """`monte_carlo[_<cpu_id>].fits` in the reference's layout (reference vega/output.py:442-520)."""
         from .output import write_monte_carlo

@@ -479,9 +479,19 @@ def run_replicas(vega, cfg, sample_params, group, print_func=print):
     lo, hi = shard_bounds(R, group.world, group.rank)
     t0 = time.perf_counter()
     samplers, records, work = [], [], 0
+    ready = []
+    if cfg.get('together', False) and cfg['sampler'] == 'Ensemble' and hi > lo:
+        # the rank's replicas as one set: their half-steps decided together, their rows one stream of full batches for the engine
+        both = E.EnsembleSet(vega, hi - lo, cfg['walkers'], streams=range(lo, hi), a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'],
+                             driver=cfg['driver'], sample_params=sample_params)
+        both.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
+        ready = [both.member(k) for k in range(hi - lo)]
     for r in range(lo, hi):
-        sampler = E.build_sampler(vega, cfg, sample_params, stream=r)
-        E.advance_sampler(sampler, cfg)
+        if ready:
+            sampler = ready[r - lo]
+        else:
+            sampler = E.build_sampler(vega, cfg, sample_params, stream=r)
+            E.advance_sampler(sampler, cfg)
         rec = record_of(sampler, cfg.get('derived', False), print_func)
         save_record(record_path(cfg['path'], cfg['name'], r), rec)
         samplers.append(sampler)
