@@ -158,7 +158,7 @@ typedef struct {
 const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
- * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats): lets a foreign binding verify its struct layout at load time. */
+ * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -537,6 +537,37 @@ typedef struct {
 int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                    int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
                    const vmx_nested_options* opt, vmx_nested_stats* stats);
+/* The same run with the survivors of every iteration split into clusters, every cluster whitened on its own and persistent ids
+ * (the reference's [Polychord] do_clustering; the rule, pinned: vega_amd/csrc/vmx_nested.h "clustering").  After the kill one launch
+ * of k_ns_knn (a grid over the survivors, the points streamed through LDS) lists every survivor's VMX_NS_KNN nearest others, one
+ * work-group (k_ns_cluster) turns the lists into components, at most VMX_NS_MAX_CLUSTERS clusters, ids, means and factors; every
+ * thread then walks with the factor of its start point's cluster and its end point inherits that cluster's id.  All arguments
+ * before `clusters` are those of vmx_nested_run, with its checks and its statistics.
+ *   clusters  flags: VMX_NS_CLUSTER to cluster; 0 runs exactly what vmx_nested_run runs and touches nothing else in the struct
+ *             live_cluster [nlive] host: the id of every live point (0: never labelled), read at entry, written back at exit
+ *             next_id      [1] host: the next unused id (a new run: 1), read at entry, written back at exit; with live_cluster
+ *                          it is part of the run's state, so that a run cut into calls stays the same run
+ *             dead_cluster [n_iterations K] host: beside dead_u / dead_lnl, the id every dead point held when it was killed
+ * Refused in addition (-1): clusters NULL, unknown flags; with VMX_NS_CLUSTER a missing array, next_id < 1 or so large that the
+ * call could overflow it, an id outside 0 .. next_id - 1. */
+#define VMX_NS_KNN 8
+#define VMX_NS_MAX_CLUSTERS 8
+#define VMX_NS_CLUSTER 1u
+typedef struct {
+    int32_t* live_cluster; int32_t* next_id; int32_t* dead_cluster;
+    uint32_t flags, reserved;
+} vmx_nested_clusters;
+int vmx_nested_run_clustered(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                             int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                             const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters);
+/* The clustering of one iteration on host arrays, the two kernels' unit-test entry: m points u[m][n] (finite) with previous ids
+ * prev_id[m] (0: none; all below *next_id) on `device`.  Writes ids[m] (every point's new id), *k_used (the neighbour level 3 .. 8
+ * the components were taken at), *n_clusters (1 .. VMX_NS_MAX_CLUSTERS), means [VMX_NS_MAX_CLUSTERS][n] and factors
+ * [VMX_NS_MAX_CLUSTERS][n][n] (the clusters in their order: size descending, then smallest member ascending; rows beyond
+ * *n_clusters are zero) and moves *next_id past the ids it handed out.  Refused (-1): n outside 1 .. 32, m outside 2 .. 4096, a
+ * coordinate that is not finite, an id outside 0 .. *next_id - 1.  A HIP failure returns -2. */
+int vmx_nested_cluster_points(int32_t device, const double* u, int32_t m, int32_t n, const int32_t* prev_id, int32_t* next_id,
+                              int32_t* ids, int32_t* k_used, int32_t* n_clusters, double* means, double* factors);
 /* Evidence and an equal-weight posterior where the particles live: tempered sequential Monte Carlo (the scheme of pocoMC, the
  * reference's second sampler in bin/run_vega_mpi.py, without its normalising flow), every decision pinned in
  * vega_amd/csrc/vmx_smc.h.  N particles walk from the prior (beta = 0) to the posterior (beta = 1); a stage picks the next beta by

@@ -369,6 +369,11 @@ struct NsWorkspace {
     DevBuf<double> th;                  // [K] vmx_ns::Thread
     DevBuf<int32_t> rank, surv, killed, slot, dead_n;
     DevBuf<int64_t> counters;
+    // clustering (vmx_nested_run_clustered): ids, the neighbour lists and link levels, the survivors' and the threads' clusters
+    DevBuf<int32_t> live_cluster, dead_cluster, nn, cslot, tslot, cl_id, cl_size, cl_info;
+    DevBuf<uint8_t> lev;
+    DevBuf<double> cl_mean, cl_cov, cl_chol;
+    int32_t info_host[4] = {0, 0, 0, 0};                             // what goes up into cl_info (it outlives the copy)
     int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round
     double* pin_lnl = nullptr; double* dpin_lnl = nullptr;           // ... and, when an iteration ends, live lnL [nlive] + dead lnL [K]
     size_t pin_lnl_n = 0;
@@ -376,6 +381,16 @@ struct NsWorkspace {
         if (pin_word) (void)hipHostFree(pin_word);
         if (pin_lnl) (void)hipHostFree(pin_lnl);
     }
+};
+
+// The clustering of m points (vmx_nested.h "clustering"): position p is row row_of(surv, p) of u and of ids
+struct NsClusterDev {
+    const double* u; const int32_t* surv;                   // [rows][n], [m] (nullptr: the rows themselves)
+    int32_t* ids;                                           // [rows]: the previous ids in, the new ones out
+    int32_t* nn; uint8_t* lev; int32_t* slot;               // [m][KNN] neighbours and their link levels, [m] the cluster of every point
+    int32_t* cl_id; int32_t* cl_size; int32_t* info;        // [MAX_CLUSTERS] x 2; info: the level used, the cluster count, next_id
+    double* mean; double* cov; double* chol;                // [MAX_CLUSTERS] x [n], [n][n], [n][n]
+    int32_t m, n;
 };
 
 struct NsDev {
@@ -391,7 +406,179 @@ struct NsDev {
     uint64_t seed, stream;
 };
 
+// what a run with clustering hands its kernels beside NsDev (the kernels of a run without it take NsDev alone, as they did):
+// cl.ids is live_cluster [nlive]; the record's ids [iterations][K]; the cluster of every thread's start [K]
+struct NsClusterRun {
+    NsClusterDev cl; int32_t* dead_cluster; int32_t* tslot;
+    int32_t phase;                                          // k_ns_iteration_clustered: 0 the kill, 1 (after the clustering) the starts
+};
+
 constexpr int NS_THREADS = 1024;
+constexpr int NS_KNN_THREADS = 256;
+
+// The KNN nearest others of every point, one point per lane with its coordinates in registers: the points stream through LDS in
+// tiles of NS_KNN_THREADS x NP doubles (NP >= n, the rest zeros, which add +0.0 to a sum that is never negative: the bits of
+// vmx_ns::dist2 over n).  Every lane reads the same tile entry at the same time - a broadcast, no bank conflict - and keeps its
+// sorted list by insertion; (d2, position) is a total order, so the lists do not depend on the tiling.
+template <int NP>
+__global__ __launch_bounds__(NS_KNN_THREADS) void k_ns_knn(NsClusterDev C)
+{
+    __shared__ double tile[NS_KNN_THREADS * NP];
+    const int m = C.m, n = C.n;
+    const int i = blockIdx.x * NS_KNN_THREADS + threadIdx.x;
+    double x[NP], d[vmx_ns::KNN];
+    int32_t p[vmx_ns::KNN];
+#pragma unroll
+    for (int a = 0; a < NP; ++a) x[a] = (i < m && a < n) ? C.u[(size_t)vmx_ns::row_of(C.surv, i) * n + a] : 0.0;
+#pragma unroll
+    for (int s = 0; s < vmx_ns::KNN; ++s) { d[s] = INFINITY; p[s] = vmx_ns::NO_NEIGHBOUR; }
+    for (int j0 = 0; j0 < m; j0 += NS_KNN_THREADS) {
+        const int count = min(NS_KNN_THREADS, m - j0);
+        __syncthreads();
+        for (int e = threadIdx.x; e < count * NP; e += NS_KNN_THREADS) {
+            const int j = e / NP, a = e % NP;
+            tile[e] = a < n ? C.u[(size_t)vmx_ns::row_of(C.surv, j0 + j) * n + a] : 0.0;
+        }
+        __syncthreads();
+        if (i >= m) continue;
+        for (int j = 0; j < count; ++j) {
+            const double d2 = vmx_ns::dist2(x, tile + j * NP, NP);
+            if (j0 + j != i) vmx_ns::nn_insert(d, p, d2, j0 + j);
+        }
+    }
+    if (i < m) {
+#pragma unroll
+        for (int s = 0; s < vmx_ns::KNN; ++s) C.nn[(size_t)i * vmx_ns::KNN + s] = p[s] == vmx_ns::NO_NEIGHBOUR ? -1 : p[s];
+    }
+}
+
+// Neighbour lists to factors in one work-group: link levels, min-label propagation with pointer jumping to its fixed point (which
+// no schedule changes; at most m sweeps per level, levels 2 .. KNN), sizes and the order of the sizeable components, the loose
+// points to their nearest clustered one, the ids, then mean and covariance with one lane per (cluster, entry) and the factor with
+// one lane per cluster.  Every decision: vmx_nested.h.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_cluster(NsClusterDev C)
+{
+    __shared__ int32_t s_lab[vmx_ns::MAX_LIVE];             // labels; later the previous ids
+    __shared__ int32_t s_size[vmx_ns::MAX_LIVE];            // component sizes; later every point's cluster
+    __shared__ int32_t s_slot0[vmx_ns::MAX_LIVE];           // the cluster of a point of a sizeable component, -1: loose
+    __shared__ int32_t s_flag, s_count, s_root[vmx_ns::MAX_CLUSTERS], s_csize[vmx_ns::MAX_CLUSTERS], s_cid[vmx_ns::MAX_CLUSTERS];
+    __shared__ unsigned long long s_best[vmx_ns::MAX_CLUSTERS];
+    constexpr int KNN = vmx_ns::KNN, MAXC = vmx_ns::MAX_CLUSTERS;
+    const int m = C.m, n = C.n, tid = threadIdx.x;
+    volatile int32_t* lab = s_lab;
+    for (int e = tid; e < m * KNN; e += NS_THREADS) C.lev[e] = (uint8_t)vmx_ns::link_level(C.nn, e / KNN, e % KNN);
+    for (int i = tid; i < m; i += NS_THREADS) s_lab[i] = i;
+    if (tid == 0) s_flag = 0;
+    __syncthreads();
+    int k = 2, before = 0;
+    for (;; ++k) {
+        for (int sweep = 0; sweep < m; ++sweep) {
+            bool changed = false;
+            for (int i = tid; i < m; i += NS_THREADS) {
+                const int32_t mine = lab[i];
+                int32_t l = mine;
+                for (int q = 0; q < k; ++q)
+                    if (C.lev[(size_t)i * KNN + q] <= k) l = min(l, lab[C.nn[(size_t)i * KNN + q]]);
+                l = min(l, lab[l]);
+                if (l < mine) { lab[i] = l; changed = true; }
+            }
+            if (changed) s_flag = 1;
+            __syncthreads();
+            const int again = s_flag;
+            __syncthreads();
+            if (tid == 0) s_flag = 0;
+            __syncthreads();
+            if (!again) break;
+        }
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+        int roots = 0;
+        for (int i = tid; i < m; i += NS_THREADS) roots += s_lab[i] == i ? 1 : 0;
+        if (roots) atomicAdd(&s_count, roots);
+        __syncthreads();
+        const int count = s_count;
+        __syncthreads();
+        if ((k >= 3 && count == before) || k == KNN) break;
+        before = count;
+    }
+    for (int i = tid; i < m; i += NS_THREADS) s_size[i] = 0;
+    if (tid < MAXC) { s_root[tid] = -1; s_csize[tid] = 0; s_cid[tid] = 0; s_best[tid] = 0; }
+    __syncthreads();
+    for (int i = tid; i < m; i += NS_THREADS) atomicAdd(&s_size[s_lab[i]], 1);
+    __syncthreads();
+    const int sizeable = 2 * n + 2;
+    for (int i = tid; i < m; i += NS_THREADS) {
+        if (s_lab[i] != i || s_size[i] < sizeable) continue;
+        int rank = 0;
+        for (int r = 0; r < m; ++r)
+            rank += (s_lab[r] == r && s_size[r] >= sizeable && (s_size[r] > s_size[i] || (s_size[r] == s_size[i] && r < i))) ? 1 : 0;
+        if (rank < MAXC) s_root[rank] = i;
+    }
+    __syncthreads();
+    int nc = 0;
+    for (int c = 0; c < MAXC; ++c) nc += s_root[c] >= 0 ? 1 : 0;
+    for (int i = tid; i < m; i += NS_THREADS) {
+        int32_t c0 = nc == 0 ? 0 : -1;
+        for (int c = 0; c < nc; ++c)
+            if (s_lab[i] == s_root[c]) c0 = c;
+        s_slot0[i] = c0;
+    }
+    if (nc == 0) nc = 1;
+    __syncthreads();
+    int32_t* s_slot = s_size;
+    int32_t* s_prev = s_lab;
+    for (int i = tid; i < m; i += NS_THREADS) {
+        int32_t c = s_slot0[i];
+        if (c < 0) {
+            const double* x = C.u + (size_t)vmx_ns::row_of(C.surv, i) * n;
+            double bd = INFINITY;
+            int32_t bp = vmx_ns::NO_NEIGHBOUR;
+            for (int j = 0; j < m; ++j) {
+                if (s_slot0[j] < 0) continue;
+                const double d2 = vmx_ns::dist2(x, C.u + (size_t)vmx_ns::row_of(C.surv, j) * n, n);
+                if (vmx_ns::nearer(d2, j, bd, bp)) { bd = d2; bp = j; }
+            }
+            c = s_slot0[bp];
+        }
+        s_slot[i] = c;
+        C.slot[i] = c;
+        s_prev[i] = C.ids[vmx_ns::row_of(C.surv, i)];
+        atomicAdd(&s_csize[c], 1);
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += NS_THREADS) {
+        const int32_t id = s_prev[i], c = s_slot[i];
+        if (id == 0) continue;
+        int32_t same = 0;
+        for (int j = 0; j < m; ++j) same += (s_slot[j] == c && s_prev[j] == id) ? 1 : 0;
+        atomicMax(&s_best[c], (unsigned long long)vmx_ns::id_key(same, id));
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint64_t best[MAXC];
+        int32_t ids[MAXC], next = C.info[2];
+        for (int c = 0; c < MAXC; ++c) { best[c] = s_best[c]; ids[c] = 0; }
+        vmx_ns::assign_ids(nc, best, &next, ids);
+        for (int c = 0; c < MAXC; ++c) { s_cid[c] = ids[c]; C.cl_id[c] = ids[c]; C.cl_size[c] = s_csize[c]; }
+        C.info[0] = k; C.info[1] = nc; C.info[2] = next;
+    }
+    __syncthreads();
+    for (int i = tid; i < m; i += NS_THREADS) C.ids[vmx_ns::row_of(C.surv, i)] = s_cid[s_slot[i]];
+    for (int e = tid; e < nc * n; e += NS_THREADS) {
+        const int c = e / n, a = e % n;
+        C.mean[e] = vmx_ns::cluster_mean_entry(a, C.u, C.surv, s_slot, m, c, s_csize[c], n);
+    }
+    __syncthreads();
+    for (int e = tid; e < nc * n * n; e += NS_THREADS) {
+        const int c = e / (n * n), a = e % (n * n) / n, b = e % n;
+        if (b > a) continue;
+        const double v = vmx_ns::cluster_cov_entry(a, b, C.u, C.surv, s_slot, C.mean + (size_t)c * n, m, c, s_csize[c], n);
+        C.cov[(size_t)c * n * n + a * n + b] = v;
+        C.cov[(size_t)c * n * n + b * n + a] = v;
+    }
+    __syncthreads();
+    if (tid < nc) (void)vmx_ns::whiten(n, C.cov + (size_t)tid * n * n, C.chol + (size_t)tid * n * n);
+}
 
 // the initial live points: u from the Philox blocks (i, 0, j, 2), and their rows for the engine
 __global__ __launch_bounds__(NS_THREADS) void k_ns_draw_live(NsDev D)
@@ -408,12 +595,27 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_live_lnl(NsDev D)
 
 // The head of iteration `it` (record row `rec` of this call) in one work-group: rank the live points by counting, append the K
 // deaths to the record, the survivors' mean and covariance (one lane per entry), the factor (one lane: n <= 32), L*, and every
-// thread at its start.  Every expression: vmx_nested.h.
-__global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it, int64_t rec)
+// thread at its start.  Every expression: vmx_nested.h.  CLUSTER (k_ns_iteration_clustered): two launches around k_ns_knn /
+// k_ns_cluster - X.phase 0 kills, records the ids the dead held and lists the survivors; X.phase 1 starts the threads and notes the
+// cluster of every start.  Without it (k_ns_iteration) X is not there and the code is what it was.
+template <bool CLUSTER>
+__device__ __forceinline__ void ns_iteration(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec)
 {
     __shared__ double s_lnl[vmx_ns::MAX_LIVE];
     __shared__ int32_t s_rank[vmx_ns::MAX_LIVE];
     const int nlive = D.nlive, K = D.K, n = D.n, m = nlive - K;
+    if constexpr (CLUSTER) {
+        if (X.phase == 1) {
+            for (int k = threadIdx.x; k < K; k += blockDim.x) {
+                const int64_t choice = vmx_ns::start_choice(k, it, m, D.seed, D.stream);
+                const int i = D.surv[choice];
+                vmx_ns::start(D.th[k], n, D.live_u + (size_t)i * n, D.live_lnl[i]);
+                D.slot[k] = -1;
+                X.tslot[k] = X.cl.slot[choice];
+            }
+            return;
+        }
+    }
     for (int i = threadIdx.x; i < nlive; i += blockDim.x) s_lnl[i] = D.live_lnl[i];
     __syncthreads();
     for (int i = threadIdx.x; i < nlive; i += blockDim.x) {
@@ -426,6 +628,7 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it
             for (int d = 0; d < n; ++d) D.dead_u[row * n + d] = D.live_u[(size_t)i * n + d];
             D.dead_lnl[row] = s_lnl[i];
             D.dead_n[row] = nlive - r;
+            if constexpr (CLUSTER) X.dead_cluster[row] = X.cl.ids[i];
             if (r == K - 1) *D.lstar = s_lnl[i];
         }
     }
@@ -436,6 +639,7 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it
         for (int j = 0; j < i; ++j) pos += s_rank[j] >= K ? 1 : 0;
         D.surv[pos] = i;
     }
+    if constexpr (CLUSTER) return;
     for (int a = threadIdx.x; a < n; a += blockDim.x) D.mean[a] = vmx_ns::mean_entry(a, D.live_u, s_rank, nlive, K, n);
     __syncthreads();
     for (int q = threadIdx.x; q < n * n; q += blockDim.x) {
@@ -454,12 +658,24 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it
     }
 }
 
+__global__ __launch_bounds__(NS_THREADS) void k_ns_iteration(NsDev D, int64_t it, int64_t rec)
+{
+    ns_iteration<false>(D, NsClusterRun{}, it, rec);
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_iteration_clustered(NsDev D, NsClusterRun X, int64_t it, int64_t rec)
+{
+    ns_iteration<true>(D, X, it, rec);
+}
+
 // One answer for every thread that asked, in one work-group: lane by lane (contiguous threads per lane, so that the compaction
 // keeps their order) read chi2 / status of the thread's row, advance its machine, then scan the requests of the threads still
 // running and emit their rows (the fixed row with the sampled columns mapped out of the cube) and the row count to the host's
 // word.  When nothing is asked for the iteration is over: the end points take the killed points' slots, and the live and the
-// newly dead lnL go to the host beside the word.
-__global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, int64_t rec)
+// newly dead lnL go to the host beside the word.  CLUSTER (k_ns_advance_clustered): every thread walks with the factor of its
+// start's cluster, and its end point inherits that cluster's id.
+template <bool CLUSTER>
+__device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec)
 {
     __shared__ int32_t s_scan[NS_THREADS];
     __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
@@ -476,6 +692,7 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
         if (T.state == vmx_ns::S_DONE) continue;
         const int row = D.slot[k];
         const double answer = row >= 0 ? vmx_ns::lnl_of(D.box.status[row], D.box.chi2[row], D.log_norm) : -INFINITY;
+        if constexpr (CLUSTER) I.C = X.cl.chol + (size_t)X.tslot[k] * n * n;
         if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
     }
     s_scan[threadIdx.x] = mine;
@@ -511,12 +728,23 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
             const vmx_ns::Thread& T = D.th[k];
             for (int d = 0; d < n; ++d) D.live_u[(size_t)i * n + d] = T.x[d];
             D.live_lnl[i] = T.lnl;
+            if constexpr (CLUSTER) X.cl.ids[i] = X.cl.cl_id[X.tslot[k]];
             D.host_lnl[D.nlive + k] = D.dead_lnl[(size_t)rec * K + k];
         }
         __syncthreads();
         for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.host_lnl[i] = D.live_lnl[i];
     }
     if (threadIdx.x == 0) *D.host_word = total;
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, int64_t rec)
+{
+    ns_advance<false>(D, NsClusterRun{}, it, rec);
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_advance_clustered(NsDev D, NsClusterRun X, int64_t it, int64_t rec)
+{
+    ns_advance<true>(D, X, it, rec);
 }
 
 // Tempered SMC (vmx_smc_run): the particles, their proposals, the weights of a stage, the rows of a sweep and the stage record
@@ -1320,6 +1548,7 @@ int vmx_struct_size(int32_t which)
         case 14: return (int)sizeof(vmx_smc_spec);
         case 15: return (int)sizeof(vmx_smc_options);
         case 16: return (int)sizeof(vmx_smc_stats);
+        case 17: return (int)sizeof(vmx_nested_clusters);
         default: return -1;
     }
 }
@@ -4461,31 +4690,117 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
 // ---- evidence where the live points live (vmx_nested.h)
 static_assert(VMX_NS_MAXN == vmx_ns::MAXN && VMX_NS_MAX_LIVE == vmx_ns::MAX_LIVE, "nested sampling limits");
 
+static_assert(VMX_NS_KNN == vmx_ns::KNN && VMX_NS_MAX_CLUSTERS == vmx_ns::MAX_CLUSTERS, "nested sampling clusters");
+
+// k_ns_knn for n coordinates (the tile's row is the next power of two) and k_ns_cluster, on `st`
+static int launch_clustering(const NsClusterDev& C, hipStream_t st)
+{
+    const dim3 grid((C.m + NS_KNN_THREADS - 1) / NS_KNN_THREADS), block(NS_KNN_THREADS);
+    if (C.n <= 1) hipLaunchKernelGGL(k_ns_knn<1>, grid, block, 0, st, C);
+    else if (C.n <= 2) hipLaunchKernelGGL(k_ns_knn<2>, grid, block, 0, st, C);
+    else if (C.n <= 4) hipLaunchKernelGGL(k_ns_knn<4>, grid, block, 0, st, C);
+    else if (C.n <= 8) hipLaunchKernelGGL(k_ns_knn<8>, grid, block, 0, st, C);
+    else if (C.n <= 16) hipLaunchKernelGGL(k_ns_knn<16>, grid, block, 0, st, C);
+    else hipLaunchKernelGGL(k_ns_knn<32>, grid, block, 0, st, C);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_ns_cluster, dim3(1), dim3(NS_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                      int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters);
+
 int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                    int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
                    const vmx_nested_options* opt, vmx_nested_stats* stats)
 {
-    REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration, "vmx_nested_run");
+    return nested_run("vmx_nested_run", e, spec, live_u, live_lnl, iteration, n_iterations, dead_u, dead_lnl, dead_nlive, opt, stats,
+                      nullptr);
+}
+
+int vmx_nested_run_clustered(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                             int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                             const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters)
+{
+    REQUIRE(clusters, "vmx_nested_run_clustered: the clusters");
+    REQUIRE((clusters->flags & ~(uint32_t)VMX_NS_CLUSTER) == 0, "vmx_nested_run_clustered: flags 0 or VMX_NS_CLUSTER");
+    return nested_run("vmx_nested_run_clustered", e, spec, live_u, live_lnl, iteration, n_iterations, dead_u, dead_lnl, dead_nlive, opt,
+                      stats, (clusters->flags & VMX_NS_CLUSTER) ? clusters : nullptr);
+}
+
+int vmx_nested_cluster_points(int32_t device, const double* u, int32_t m, int32_t n, const int32_t* prev_id, int32_t* next_id,
+                              int32_t* ids, int32_t* k_used, int32_t* n_clusters, double* means, double* factors)
+{
+    REQUIRE(u && prev_id && next_id && ids && k_used && n_clusters && means && factors, "vmx_nested_cluster_points");
+    REQUIRE(n >= 1 && n <= VMX_NS_MAXN, "vmx_nested_cluster_points: 1 .. 32 coordinates");
+    REQUIRE(m >= 2 && m <= VMX_NS_MAX_LIVE, "vmx_nested_cluster_points: 2 .. 4096 points");
+    REQUIRE(*next_id >= 1 && *next_id <= 0x7fffffff - VMX_NS_MAX_CLUSTERS, "vmx_nested_cluster_points: next_id >= 1");
+    for (int i = 0; i < m; ++i) REQUIRE(prev_id[i] >= 0 && prev_id[i] < *next_id, "vmx_nested_cluster_points: 0 <= prev_id < next_id");
+    for (size_t q = 0; q < (size_t)m * n; ++q) REQUIRE(std::isfinite(u[q]), "vmx_nested_cluster_points: a coordinate is not finite");
+    HIP_OK(hipSetDevice(device));
+    constexpr int MAXC = VMX_NS_MAX_CLUSTERS;
+    DevBuf<double> d_u, d_mean, d_cov, d_chol;
+    DevBuf<int32_t> d_ids, d_nn, d_slot, d_cid, d_csize, d_info;
+    DevBuf<uint8_t> d_lev;
+    if (d_u.alloc((size_t)m * n, false) || d_mean.alloc((size_t)MAXC * n) || d_cov.alloc((size_t)MAXC * n * n) ||
+        d_chol.alloc((size_t)MAXC * n * n) || d_ids.alloc(m, false) || d_nn.alloc((size_t)m * VMX_NS_KNN, false) ||
+        d_slot.alloc(m, false) || d_cid.alloc(MAXC) || d_csize.alloc(MAXC) || d_info.alloc(4) || d_lev.alloc((size_t)m * VMX_NS_KNN, false))
+        return -2;
+    hipStream_t st = nullptr;
+    const int32_t info_in[4] = {0, 0, *next_id, 0};
+    HIP_OK(hipMemcpyAsync(d_u.p, u, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_ids.p, prev_id, (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(d_info.p, info_in, sizeof(info_in), hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));       // (info_in leaves the stack)
+    const NsClusterDev C{d_u.p, nullptr, d_ids.p, d_nn.p, d_lev.p, d_slot.p, d_cid.p, d_csize.p, d_info.p, d_mean.p, d_cov.p, d_chol.p, m, n};
+    if (launch_clustering(C, st)) return -2;
+    int32_t info[4] = {0, 0, 0, 0};
+    HIP_OK(hipMemcpyAsync(info, d_info.p, sizeof(info), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(ids, d_ids.p, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(means, d_mean.p, (size_t)MAXC * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(factors, d_chol.p, (size_t)MAXC * n * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    *k_used = info[0]; *n_clusters = info[1]; *next_id = info[2];
+    return 0;
+}
+
+static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                      int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters)
+{
+    const std::string name(who);
+    REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration, name);
     std::vector<char> varies;
     std::vector<int32_t> inv;
-    if (check_box("vmx_nested_run", e, spec, VMX_NS_MAXN, varies, inv)) return -1;
+    if (check_box(name, e, spec, VMX_NS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params, nlive = spec->nlive, K = spec->K;
-    REQUIRE(nlive >= n + 2 && nlive <= VMX_NS_MAX_LIVE, "vmx_nested_run: n + 2 .. 4096 live points");
-    REQUIRE(K >= 1 && K <= nlive - n - 1, "vmx_nested_run: 1 .. nlive - n - 1 threads");
-    REQUIRE(spec->num_repeats >= 1, "vmx_nested_run: num_repeats >= 1");
-    REQUIRE(n_iterations >= 0 && *iteration >= 0, "vmx_nested_run: n_iterations >= 0, iteration >= 0");
-    REQUIRE(n_iterations == 0 || (dead_u && dead_lnl && dead_nlive), "vmx_nested_run: the dead record");
+    REQUIRE(nlive >= n + 2 && nlive <= VMX_NS_MAX_LIVE, name + ": n + 2 .. 4096 live points");
+    REQUIRE(K >= 1 && K <= nlive - n - 1, name + ": 1 .. nlive - n - 1 threads");
+    REQUIRE(spec->num_repeats >= 1, name + ": num_repeats >= 1");
+    REQUIRE(n_iterations >= 0 && *iteration >= 0, name + ": n_iterations >= 0, iteration >= 0");
+    REQUIRE(n_iterations == 0 || (dead_u && dead_lnl && dead_nlive), name + ": the dead record");
     const bool draw = opt && opt->draw_live != 0;
-    REQUIRE(!draw || *iteration == 0, "vmx_nested_run: live points are drawn at iteration 0");
+    const bool clustering = clusters != nullptr;
+    if (clustering) {
+        REQUIRE(clusters->live_cluster && clusters->next_id, name + ": live_cluster, next_id");
+        REQUIRE(n_iterations == 0 || clusters->dead_cluster, name + ": the dead record's ids");
+        REQUIRE(*clusters->next_id >= 1, name + ": next_id >= 1");
+        REQUIRE((int64_t)*clusters->next_id + (int64_t)n_iterations * VMX_NS_MAX_CLUSTERS < 0x7fffffff, name + ": next_id would overflow");
+        for (int i = 0; i < nlive; ++i)
+            REQUIRE(clusters->live_cluster[i] >= 0 && clusters->live_cluster[i] < *clusters->next_id, name + ": 0 <= live_cluster < next_id");
+    }
+    REQUIRE(!draw || *iteration == 0, name + ": live points are drawn at iteration 0");
     if (!draw)
         for (int i = 0; i < nlive; ++i) {
-            REQUIRE(!std::isnan(live_lnl[i]), "vmx_nested_run: a live point has a NaN lnL");
+            REQUIRE(!std::isnan(live_lnl[i]), name + ": a live point has a NaN lnL");
             for (int d = 0; d < n; ++d) {
                 const double v = live_u[(size_t)i * n + d];
-                REQUIRE(v >= 0.0 && v <= 1.0, "vmx_nested_run: a live point lies outside the unit cube");
+                REQUIRE(v >= 0.0 && v <= 1.0, name + ": a live point lies outside the unit cube");
             }
         }
-    if (LikelihoodSession::check("vmx_nested_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const size_t cap = (size_t)std::max(nlive, K), rec_rows = (size_t)std::max(n_iterations, 1) * K;
 
     HIP_OK(hipSetDevice(e->device));
@@ -4496,6 +4811,13 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
         ensure(S.killed, K) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) || ensure(S.lstar, 1) ||
         ensure(S.th, (size_t)K * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, K) || ensure(S.dead_u, rec_rows * n) ||
         ensure(S.dead_lnl, rec_rows) || ensure(S.dead_n, rec_rows) || ensure(S.counters, 1))
+        return -2;
+    const int m = nlive - K;
+    if (clustering &&
+        (ensure(S.live_cluster, nlive) || ensure(S.dead_cluster, rec_rows) || ensure(S.nn, (size_t)m * VMX_NS_KNN) ||
+         ensure(S.lev, (size_t)m * VMX_NS_KNN) || ensure(S.cslot, m) || ensure(S.tslot, K) || ensure(S.cl_id, VMX_NS_MAX_CLUSTERS) ||
+         ensure(S.cl_size, VMX_NS_MAX_CLUSTERS) || ensure(S.cl_info, 4) || ensure(S.cl_mean, (size_t)VMX_NS_MAX_CLUSTERS * n) ||
+         ensure(S.cl_cov, (size_t)VMX_NS_MAX_CLUSTERS * n * n) || ensure(S.cl_chol, (size_t)VMX_NS_MAX_CLUSTERS * n * n)))
         return -2;
     if (!S.pin_word) {
         HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
@@ -4522,6 +4844,16 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
     D.host_word = S.dpin_word; D.host_lnl = S.dpin_lnl; D.counters = S.counters.p;
     D.nlive = nlive; D.K = K; D.n = n; D.P = P; D.num_repeats = spec->num_repeats;
     D.log_norm = spec->log_norm; D.seed = spec->seed; D.stream = spec->stream;
+    NsClusterRun X{};
+    if (clustering) {
+        S.info_host[0] = S.info_host[1] = S.info_host[3] = 0;
+        S.info_host[2] = *clusters->next_id;
+        HIP_OK(hipMemcpyAsync(S.live_cluster.p, clusters->live_cluster, (size_t)nlive * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.cl_info.p, S.info_host, sizeof(S.info_host), hipMemcpyHostToDevice, st));
+        X.cl = NsClusterDev{S.live_u.p, S.surv.p, S.live_cluster.p, S.nn.p, S.lev.p, S.cslot.p, S.cl_id.p, S.cl_size.p, S.cl_info.p,
+                            S.cl_mean.p, S.cl_cov.p, S.cl_chol.p, m, n};
+        X.dead_cluster = S.dead_cluster.p; X.tslot = S.tslot.p;
+    }
 
     // the engine as the sampler's likelihood, at the table level the sampled columns allow
     LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
@@ -4551,15 +4883,23 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
     int done = 0;
     while (done < n_iterations) {
         const int64_t it = *iteration + done;
-        hipLaunchKernelGGL(k_ns_iteration, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
+        if (clustering) {
+            X.phase = 0;
+            hipLaunchKernelGGL(k_ns_iteration_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
+            HIP_OK(hipGetLastError());
+            if (launch_clustering(X.cl, st)) return -2;
+            X.phase = 1;
+            hipLaunchKernelGGL(k_ns_iteration_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
+        } else hipLaunchKernelGGL(k_ns_iteration, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
         for (;;) {
-            hipLaunchKernelGGL(k_ns_advance, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
+            if (clustering) hipLaunchKernelGGL(k_ns_advance_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
+            else hipLaunchKernelGGL(k_ns_advance, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
             HIP_OK(hipGetLastError());
             HIP_OK(hipStreamSynchronize(st));   // (the round's only wait: the row count, one mapped word)
             R.host_waits += 1;
             const int total = S.pin_word[0];
             if (total <= 0) break;
-            if ((size_t)total > cap) return fail(-2, "vmx_nested_run: a round asked for more rows than its buffers hold");
+            if ((size_t)total > cap) return fail(-2, name + ": a round asked for more rows than its buffers hold");
             R.rounds += 1;
             R.rows += total;
             if (evaluate(total)) return -2;
@@ -4575,11 +4915,19 @@ int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, d
         HIP_OK(hipMemcpyAsync(dead_lnl, S.dead_lnl.p, (size_t)done * K * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(dead_nlive, S.dead_n.p, (size_t)done * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
+    int32_t info_out[4] = {0, 0, 0, 0};
+    if (clustering) {
+        HIP_OK(hipMemcpyAsync(clusters->live_cluster, S.live_cluster.p, (size_t)nlive * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(info_out, S.cl_info.p, sizeof(info_out), hipMemcpyDeviceToHost, st));
+        if (done > 0)
+            HIP_OK(hipMemcpyAsync(clusters->dead_cluster, S.dead_cluster.p, (size_t)done * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
     int64_t own = 0;
     HIP_OK(hipMemcpyAsync(&own, S.counters.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     R.host_waits += 1;
     *iteration += done;
+    if (clustering) *clusters->next_id = info_out[2];
     R.iterations = done;
     R.rows_own_position = own;
     R.seconds_enqueuing = enqueue_s;

@@ -31,6 +31,26 @@
 //                    and the answer is ignored.
 //     replace        the K end points and their lnL take the killed points' slots, thread k the slot of rank k.
 //
+//   clustering       (optional: vmx_nested_run_clustered; off, everything above is what an iteration does) after the kill the m
+//                    survivors, numbered by position in live-index order, are split into clusters and every cluster is whitened
+//                    on its own:
+//     distances      d2(i, j) = sum_a (u_ia - u_ja)^2 from 0.0 over a = 0 .. n-1 (dist2); neighbours are ordered by (d2, position)
+//                    (nearer: duplicated live points occur, a slice step that gives up ends where it began); every survivor
+//                    keeps its KNN = 8 nearest others (m - 1 if that is fewer; -1 fills the list).
+//     components     at level k = 2 .. 8, i and j are linked when each is among the other's first k neighbours (link_level); c_k
+//                    counts the connected components.  The first k >= 3 with c_k = c_{k-1} is used, otherwise k = 8.  A
+//                    component's raw label is its smallest position.
+//     clusters       a component of at least 2 n + 2 points is sizeable; the sizeable ones in the order (size descending, raw
+//                    label ascending), at most MAX_CLUSTERS = 8, are the clusters; none: all survivors form one cluster.  Every
+//                    other survivor joins the cluster of its nearest clustered survivor by (d2, position).
+//     ids            live_cluster[nlive] (0: never labelled) and next_id (from 1) belong to the run's state.  The clusters in
+//                    their order each take the most frequent non-zero previous id among their members (attached ones included),
+//                    ties to the lowest id; none, or one an earlier cluster of this iteration took: next_id++.
+//     factors        mean and covariance per cluster over its members in live-index order, divisor size - 1
+//                    (cluster_mean_entry, cluster_cov_entry), then whiten, the diagonal fallback included.
+//     threads        thread k walks with the factor of its start point's cluster; its end point inherits that cluster's id.
+//     record         a death carries the id the point held when it was killed.
+//
 // Thread is a resumable state machine: advance(state, lnL of my last request) -> next request | done.  Every expression is the
 // separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are correctly rounded.
 #pragma once
@@ -270,6 +290,187 @@ VMX_HD inline bool advance(Thread& T, const Iteration& I, int64_t k, double answ
         return true;
     }
     return false;
+}
+
+// ---- clustering of the survivors (positions 0 .. m-1; `surv` maps a position to its row of u and of prev_id, nullptr: itself)
+constexpr int KNN = 8;
+constexpr int MAX_CLUSTERS = 8;
+constexpr int32_t NO_NEIGHBOUR = 0x7fffffff;
+
+VMX_HD inline int row_of(const int32_t* surv, int p) { return surv ? surv[p] : p; }
+
+VMX_HD inline double dist2(const double* a, const double* b, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    for (int c = 0; c < n; ++c) {
+        const double d = a[c] - b[c];
+        const double p = d * d;
+        acc = acc + p;
+    }
+    return acc;
+}
+
+VMX_HD inline bool nearer(double d, int32_t p, double d_than, int32_t p_than) { return d < d_than || (d == d_than && p < p_than); }
+
+// the sorted list (d[KNN], p[KNN]; empty places: +inf, NO_NEIGHBOUR) after the candidate (cd, cp) has been offered to it
+VMX_HD inline void nn_insert(double* d, int32_t* p, double cd, int32_t cp)
+{
+    if (!nearer(cd, cp, d[KNN - 1], p[KNN - 1])) return;
+    for (int s = 0; s < KNN; ++s) {
+        const bool in = nearer(cd, cp, d[s], p[s]);
+        const double kd = in ? cd : d[s], od = in ? d[s] : cd;
+        const int32_t kp = in ? cp : p[s], op = in ? p[s] : cp;
+        d[s] = kd; p[s] = kp; cd = od; cp = op;
+    }
+}
+
+// the neighbours of survivor i into out[KNN]
+VMX_HD inline void knn_of(int i, const double* u, const int32_t* surv, int m, int n, int32_t* out)
+{
+    double d[KNN];
+    int32_t p[KNN];
+    for (int s = 0; s < KNN; ++s) { d[s] = INFINITY; p[s] = NO_NEIGHBOUR; }
+    const double* x = u + (size_t)row_of(surv, i) * n;
+    for (int j = 0; j < m; ++j)
+        if (j != i) nn_insert(d, p, dist2(x, u + (size_t)row_of(surv, j) * n, n), j);
+    for (int s = 0; s < KNN; ++s) out[s] = p[s] == NO_NEIGHBOUR ? -1 : p[s];
+}
+
+// the smallest level k at which i and its q-th neighbour are linked (each among the other's first k); KNN + 1: at none
+VMX_HD inline int link_level(const int32_t* nn, int i, int q)
+{
+    const int j = nn[(size_t)i * KNN + q];
+    if (j < 0) return KNN + 1;
+    for (int r = 0; r < KNN; ++r)
+        if (nn[(size_t)j * KNN + r] == i) return (q > r ? q : r) + 1;
+    return KNN + 1;
+}
+
+// one sweep of min-label propagation over the links of level <= k; true: a label changed
+VMX_HD inline bool propagate(const int32_t* nn, int m, int k, int32_t* label)
+{
+    bool changed = false;
+    for (int i = 0; i < m; ++i)
+        for (int q = 0; q < k; ++q) {
+            if (link_level(nn, i, q) > k) continue;
+            const int32_t l = label[nn[(size_t)i * KNN + q]];
+            if (l < label[i]) { label[i] = l; changed = true; }
+        }
+    return changed;
+}
+
+// the key by which a cluster picks its id among its members' previous ones: more members first, then the lower id
+VMX_HD inline uint64_t id_key(int32_t count, int32_t id) { return ((uint64_t)(uint32_t)count << 32) | (uint32_t)(0x7fffffff - id); }
+VMX_HD inline int32_t id_of_key(uint64_t key) { return key ? 0x7fffffff - (int32_t)(uint32_t)(key & 0xffffffffu) : 0; }
+
+// the clusters' ids in their order from the best key of each (0: no member had an id)
+VMX_HD inline void assign_ids(int n_clusters, const uint64_t* best, int32_t* next_id, int32_t* cluster_id)
+{
+    for (int c = 0; c < n_clusters; ++c) {
+        int32_t id = id_of_key(best[c]);
+        for (int e = 0; e < c; ++e)
+            if (cluster_id[e] == id) id = 0;
+        if (id == 0) { id = *next_id; *next_id += 1; }
+        cluster_id[c] = id;
+    }
+}
+
+// Distances to ids, serially: nn [m][KNN], label / size / slot0 [m] are the caller's scratch; slot [m] the cluster of every
+// survivor (its place in the order), cluster_id / cluster_size [MAX_CLUSTERS], *k_used, *n_clusters; *next_id moves on.
+VMX_HD inline void cluster_points(const double* u, const int32_t* surv, int m, int n, const int32_t* prev_id, int32_t* next_id,
+                                  int32_t* nn, int32_t* label, int32_t* size, int32_t* slot0, int32_t* slot, int32_t* cluster_id,
+                                  int32_t* cluster_size, int32_t* k_used, int32_t* n_clusters)
+{
+    for (int i = 0; i < m; ++i) knn_of(i, u, surv, m, n, nn + (size_t)i * KNN);
+    for (int i = 0; i < m; ++i) label[i] = i;
+    int k = 2, before = 0;
+    for (;; ++k) {
+        for (int sweep = 0; sweep < m && propagate(nn, m, k, label); ++sweep) {}
+        int count = 0;
+        for (int i = 0; i < m; ++i) count += label[i] == i ? 1 : 0;
+        if ((k >= 3 && count == before) || k == KNN) break;
+        before = count;
+    }
+    *k_used = k;
+    for (int i = 0; i < m; ++i) size[i] = 0;
+    for (int i = 0; i < m; ++i) size[label[i]] += 1;
+    int nc = 0;
+    int32_t root[MAX_CLUSTERS];
+    for (; nc < MAX_CLUSTERS; ++nc) {
+        int best = -1;
+        for (int r = 0; r < m; ++r) {
+            if (label[r] != r || size[r] < 2 * n + 2) continue;
+            bool taken = false;
+            for (int e = 0; e < nc; ++e) taken = taken || root[e] == r;
+            if (!taken && (best < 0 || size[r] > size[best])) best = r;
+        }
+        if (best < 0) break;
+        root[nc] = best;
+    }
+    if (nc == 0) {
+        for (int i = 0; i < m; ++i) { slot0[i] = 0; slot[i] = 0; }
+        nc = 1;
+    } else {
+        for (int i = 0; i < m; ++i) {
+            slot0[i] = -1;
+            for (int c = 0; c < nc; ++c)
+                if (label[i] == root[c]) slot0[i] = c;
+        }
+        for (int i = 0; i < m; ++i) {
+            slot[i] = slot0[i];
+            if (slot0[i] >= 0) continue;
+            const double* x = u + (size_t)row_of(surv, i) * n;
+            double bd = INFINITY;
+            int32_t bp = NO_NEIGHBOUR;
+            for (int j = 0; j < m; ++j) {
+                if (slot0[j] < 0) continue;
+                const double d = dist2(x, u + (size_t)row_of(surv, j) * n, n);
+                if (nearer(d, j, bd, bp)) { bd = d; bp = j; }
+            }
+            slot[i] = slot0[bp];
+        }
+    }
+    *n_clusters = nc;
+    uint64_t best[MAX_CLUSTERS];
+    for (int c = 0; c < MAX_CLUSTERS; ++c) { cluster_size[c] = 0; cluster_id[c] = 0; best[c] = 0; }
+    for (int i = 0; i < m; ++i) {
+        cluster_size[slot[i]] += 1;
+        const int32_t id = prev_id[row_of(surv, i)];
+        if (id == 0) continue;
+        int32_t count = 0;
+        for (int j = 0; j < m; ++j) count += (slot[j] == slot[i] && prev_id[row_of(surv, j)] == id) ? 1 : 0;
+        const uint64_t key = id_key(count, id);
+        if (key > best[slot[i]]) best[slot[i]] = key;
+    }
+    assign_ids(nc, best, next_id, cluster_id);
+}
+
+// mean and covariance of cluster c (size members) over its members in order, one accumulator per entry
+VMX_HD inline double cluster_mean_entry(int a, const double* u, const int32_t* surv, const int32_t* slot, int m, int c, int size, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    for (int i = 0; i < m; ++i)
+        if (slot[i] == c) acc = acc + u[(size_t)row_of(surv, i) * n + a];
+    return acc / (double)size;
+}
+
+VMX_HD inline double cluster_cov_entry(int a, int b, const double* u, const int32_t* surv, const int32_t* slot, const double* mean,
+                                       int m, int c, int size, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    const double ma = mean[a], mb = mean[b];
+    for (int i = 0; i < m; ++i) {
+        if (slot[i] != c) continue;
+        const double* x = u + (size_t)row_of(surv, i) * n;
+        const double da = x[a] - ma;
+        const double db = x[b] - mb;
+        const double p = da * db;
+        acc = acc + p;
+    }
+    return acc / (double)(size - 1);
 }
 
 }  // namespace vmx_ns

@@ -158,6 +158,16 @@ class NestedStats(C.Structure):
                 ('const_hint', C.c_int32), ('lanes', C.c_int32)]
 
 
+VMX_NS_KNN = 8
+VMX_NS_MAX_CLUSTERS = 8
+VMX_NS_CLUSTER = 1
+
+
+class NestedClusters(C.Structure):
+    _fields_ = [('live_cluster', C.POINTER(C.c_int32)), ('next_id', C.POINTER(C.c_int32)), ('dead_cluster', C.POINTER(C.c_int32)),
+                ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
 VMX_SMC_MAX_PARTICLES = 4096
 VMX_SMC_REC = 8
 
@@ -267,6 +277,8 @@ def load_library():
                                           C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
+    lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
+    lib.vmx_nested_cluster_points.argtypes = [C.c_int32, dptr, C.c_int32, C.c_int32, iptr, iptr, iptr, iptr, iptr, dptr, dptr]
     lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
                                 iptr, C.POINTER(SmcOptions), C.POINTER(SmcStats)]
     lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
@@ -305,7 +317,7 @@ def load_library():
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
-                                    SmcSpec, SmcOptions, SmcStats)):
+                                    SmcSpec, SmcOptions, SmcStats, NestedClusters)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -313,12 +325,31 @@ def load_library():
     return lib
 
 
+def cluster_points(u, prev_id, next_id, device=0):
+    """The clustering of one nested-sampling iteration on the device (include/vegamx.h: vmx_nested_cluster_points): ``u`` [m, n],
+    ``prev_id`` [m].  dict(ids [m], k, n_clusters, next_id, mean [n_clusters, n], C [n_clusters, n, n]) - the entries of the same
+    names of :func:`vega_amd.nested.cluster_points`."""
+    lib = load_library()
+    u = np.ascontiguousarray(u, dtype=np.float64)
+    prev_id = np.ascontiguousarray(prev_id, dtype=np.int32)
+    if u.ndim != 2 or prev_id.shape != (u.shape[0],):
+        raise ValueError('u [m, n], prev_id [m]')
+    m, n = u.shape
+    ids = np.zeros(m, dtype=np.int32)
+    nxt, k, nc = (np.array([v], dtype=np.int32) for v in (int(next_id), 0, 0))
+    mean, fac = np.zeros((VMX_NS_MAX_CLUSTERS, n)), np.zeros((VMX_NS_MAX_CLUSTERS, n, n))
+    rc = lib.vmx_nested_cluster_points(int(device), _dp(u), m, n, _ip(prev_id), _ip(nxt), _ip(ids), _ip(k), _ip(nc), _dp(mean), _dp(fac))
+    if rc != 0:
+        raise EngineError(lib.vmx_last_error().decode())
+    return dict(ids=ids, k=int(k[0]), n_clusters=int(nc[0]), next_id=int(nxt[0]), mean=mean[:int(nc[0])], C=fac[:int(nc[0])])
+
+
 EXPORTED_SYMBOLS = [
     'vmx_last_error', 'vmx_struct_size', 'vmx_create', 'vmx_destroy', 'vmx_set_template', 'vmx_set_fftlog', 'vmx_set_fftlog_padding', 'vmx_set_spline_extrapolation', 'vmx_set_fvoigt_table', 'vmx_add_gk_table', 'vmx_add_gk_table_mock',
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1118,13 +1149,15 @@ class Engine:
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
-                   seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):
+                   seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, clusters=None, cluster_flags=None):
         """Up to ``n_iterations`` iterations of the nested sampler on the device (include/vegamx.h: vmx_nested_run): ``cols`` the
         sampled parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``live_u`` [nlive, n] in the unit
         cube / ``live_lnl`` [nlive] the run's state (updated in place; drawn first with ``draw_live``), ``iteration`` the global
         index of the next iteration.  ``stop(iterations, dead_lnl [K], live_lnl [nlive])`` is asked after every iteration; a true
         answer ends the call.  Returns (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K], iteration + m, statistics) for the m
-        iterations done."""
+        iterations done.  ``clusters`` (a :class:`vega_amd.nested.ClusterState`, updated in place, the ids of this call's dead
+        appended to its ``dead``): the run with clustering (vmx_nested_run_clustered); ``cluster_flags`` overrides the flags word
+        (0: the entry runs what vmx_nested_run runs)."""
         cols, lo, hi, theta_fixed, nlive = self._sampled_box(cols, lo, hi, theta_fixed, live_u=live_u, live_lnl=live_lnl)
         K, n_iterations = int(threads), max(0, int(n_iterations))
         rows = n_iterations * max(K, 0)
@@ -1144,12 +1177,29 @@ class Engine:
         opt = NestedOptions(int(const_hint), int(chunk), int(lanes), 1 if draw_live else 0, callback, None)
         stats = NestedStats()
         it = C.c_int64(int(iteration))
-        self._check(self.lib.vmx_nested_run(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
-                                            _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats)))
+        if clusters is None:
+            self._check(self.lib.vmx_nested_run(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
+                                                _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats)))
+        else:
+            if clusters.live_cluster.dtype != np.int32 or clusters.live_cluster.shape != (nlive,) or \
+                    not clusters.live_cluster.flags['C_CONTIGUOUS']:
+                raise ValueError('clusters.live_cluster: a contiguous int32 array [nlive]')
+            dead_c, next_id = np.zeros(rows, dtype=np.int32), C.c_int32(int(clusters.next_id))
+            flags = VMX_NS_CLUSTER if cluster_flags is None else int(cluster_flags)
+            cl = NestedClusters(_ip(clusters.live_cluster), C.pointer(next_id), _ip(dead_c), flags, 0)
+            self._check(self.lib.vmx_nested_run_clustered(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
+                                                          _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats),
+                                                          C.byref(cl)))
+            clusters.next_id = int(next_id.value)
+            clusters.dead.append(dead_c[:int(stats.iterations) * K])
         if raised:
             raise raised[0]
         m = int(stats.iterations) * K
         return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), _stats_dict(stats)
+
+    def nested_cluster_points(self, u, prev_id, next_id):
+        """:func:`cluster_points` of this engine's device."""
+        return cluster_points(u, prev_id, next_id, device=self.device)
 
     def smc_run(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, n_stages, ess, sweeps, log_norm=0.0, seed=0, stream=0,
                 const_hint=-1, chunk=0, lanes=0, draw=False):

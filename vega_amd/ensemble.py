@@ -946,7 +946,8 @@ def build_sampler(vega, cfg, sample_params, stream=0):
         from .nested import NestedSampler
         return NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
                              precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
-                             max_iterations=cfg['max_iterations'], sample_params=sample_params, stream=stream)
+                             max_iterations=cfg['max_iterations'], sample_params=sample_params, stream=stream,
+                             clustering=cfg.get('do_clustering', False), cluster_posteriors=cfg.get('cluster_posteriors', False))
     if cfg['sampler'] == 'SMC':
         from .smc import SMCSampler
         return SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],

@@ -10,8 +10,11 @@ vmx_nested_run); the ``python`` driver is the readable restatement in NumPy over
 vega_amd/csrc/vmx_nested.h decision for decision, so that they produce the same dead record bit for bit.  Evidence, information
 and termination are computed here, on the host, from the dead record - one code for both drivers.
 
-What is not here: clustering of separated modes (whitening uses one covariance), ``boost_posterior``, resume files, the
-marginalised coefficients as derived parameters.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
+``clustering`` (the reference's ``do_clustering``) splits the survivors of every iteration into clusters by mutual nearest
+neighbours, whitens each on its own and keeps persistent ids, so that separated modes get factors that fit them, local evidences
+(:meth:`NestedRun.clusters`) and chains of their own (``cluster_posteriors``).
+
+What is not here: ``boost_posterior``, resume files.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
 """
 import math
 import time
@@ -27,6 +30,8 @@ MAX_STEP_OUT = 32
 MAX_SHRINK = 64
 WIDTH = 2.0
 S_NEXT, S_LEFT, S_RIGHT, S_SHRINK, S_DONE = range(5)
+KNN = 8
+MAX_CLUSTERS = 8
 
 
 # ------------------------------------------------------------------ the algorithm (vmx_nested.h) in NumPy
@@ -115,25 +120,137 @@ def whiten(cov):
     return np.diag(np.where(d > 0.0, np.sqrt(np.where(d > 0.0, d, 0.0)), 0.0)), False
 
 
-def iteration_head(live_u, live_lnl, K, t, seed, stream=0):
+# ---- clustering of the survivors (vmx_nested.h: "clustering")
+def nearest_neighbours(u):
+    """(nn [m, KNN] int32: every point's nearest others by (d2, position), -1 where m - 1 < KNN; d2 [m, m] with +inf on the
+    diagonal), d2 accumulated coordinate by coordinate from 0.0."""
+    m, n = u.shape
+    d2 = np.zeros((m, m))
+    for a in range(n):
+        diff = u[:, None, a] - u[None, :, a]
+        d2 = d2 + diff * diff
+    d2[np.arange(m), np.arange(m)] = np.inf
+    kk = min(KNN, m - 1)
+    nn = np.full((m, KNN), -1, dtype=np.int32)
+    nn[:, :kk] = np.argsort(d2, axis=1, kind='stable')[:, :kk]
+    return nn, d2
+
+
+def link_levels(nn):
+    """[m, KNN]: the smallest k at which a point and its q-th neighbour are linked (each among the other's first k), KNN + 1: at
+    none."""
+    m = nn.shape[0]
+    there = nn >= 0
+    back = (nn[np.where(there, nn, 0)] == np.arange(m)[:, None, None]) & there[:, :, None]       # [m, q, r]: nn[nn[i, q], r] == i
+    r = np.argmax(back, axis=2)
+    return np.where(back.any(axis=2), np.maximum(np.arange(KNN)[None, :], r) + 1, KNN + 1)
+
+
+def components(nn, levels, k, label=None):
+    """The smallest position of every point's connected component under the links of level <= k (min-label propagation with
+    pointer jumping to its fixed point, which no schedule changes)."""
+    m = nn.shape[0]
+    i, q = np.nonzero(levels <= k)
+    j = nn[i, q]
+    label = np.arange(m) if label is None else label.copy()
+    while True:
+        new = label.copy()
+        np.minimum.at(new, i, label[j])
+        new = new[new]
+        if np.array_equal(new, label):
+            return label
+        label = new
+
+
+def cluster_points(u, prev_id, next_id):
+    """The clusters of the points ``u`` [m, n] with previous ids ``prev_id`` [m] (0: none): dict(nn, k (the level used), label
+    (raw), n_clusters, slot [m] (every point's cluster, by its place in the order), sizes, cluster_id [n_clusters], ids [m],
+    next_id, mean [n_clusters, n], cov, C [n_clusters, n, n], cholesky [n_clusters])."""
+    u = np.asarray(u, dtype=np.float64)
+    prev_id = np.asarray(prev_id, dtype=np.int32)
+    m, n = u.shape
+    nn, d2 = nearest_neighbours(u)
+    levels = link_levels(nn)
+    label, before, k = None, 0, 2
+    while True:
+        label = components(nn, levels, k, label)
+        count = int(np.sum(label == np.arange(m)))
+        if (k >= 3 and count == before) or k == KNN:
+            break
+        before, k = count, k + 1
+    roots, sizes = np.unique(label, return_counts=True)
+    big = sizes >= 2 * n + 2
+    roots, sizes = roots[big], sizes[big]
+    order = np.lexsort((roots, -sizes))[:MAX_CLUSTERS]
+    roots = roots[order]
+    if roots.size == 0:
+        slot = np.zeros(m, dtype=np.int32)
+        nc = 1
+    else:
+        nc = roots.size
+        slot = np.full(m, -1, dtype=np.int32)
+        for c, r in enumerate(roots):
+            slot[label == r] = c
+        loose, held = np.flatnonzero(slot < 0), np.flatnonzero(slot >= 0)
+        if loose.size:      # (argmin: the first of equal distances, the lowest position)
+            slot[loose] = slot[held[np.argmin(d2[np.ix_(loose, held)], axis=1)]]
+    cluster_id = np.zeros(nc, dtype=np.int32)
+    for c in range(nc):
+        had = prev_id[(slot == c) & (prev_id != 0)]
+        pick = 0
+        if had.size:
+            ids, counts = np.unique(had, return_counts=True)
+            pick = int(ids[np.argmax(counts)])
+        if pick == 0 or pick in cluster_id[:c]:
+            pick, next_id = next_id, next_id + 1
+        cluster_id[c] = pick
+    mean, cov, C, ok = np.zeros((nc, n)), np.zeros((nc, n, n)), np.zeros((nc, n, n)), np.zeros(nc, dtype=bool)
+    for c in range(nc):
+        mean[c], cov[c] = mean_cov(u[slot == c])
+        C[c], ok[c] = whiten(cov[c])
+    return dict(nn=nn, k=k, label=label, n_clusters=nc, slot=slot, sizes=np.bincount(slot, minlength=nc), cluster_id=cluster_id,
+                ids=cluster_id[slot], next_id=int(next_id), mean=mean, cov=cov, C=C, cholesky=ok)
+
+
+class ClusterState:
+    """What clustering adds to a run's state: ``live_cluster`` [nlive] int32 (0: never labelled), ``next_id``, and the ids of the
+    dead of every call (``dead``, one array per call)."""
+
+    def __init__(self, nlive):
+        self.live_cluster = np.zeros(nlive, dtype=np.int32)
+        self.next_id = 1
+        self.dead = []
+
+
+def iteration_head(live_u, live_lnl, K, t, seed, stream=0, clusters=None):
     """Kill, whiten and choose the starts of iteration ``t``: dict(rank, killed [K] in order of death, lstar, surv (live indices
-    of the survivors in order), mean, cov, C, cholesky, start [K] (live index each thread starts from))."""
+    of the survivors in order), mean, cov, C, cholesky, start [K] (live index each thread starts from)).  With ``clusters`` (a
+    :class:`ClusterState`, whose survivors' ids and ``next_id`` move on): mean, cov, C, cholesky per cluster, ``cluster``
+    (:func:`cluster_points` of the survivors), ``dead_cluster`` [K], ``start_slot`` [K] and ``C_thread`` [K, n, n]."""
     nlive = live_u.shape[0]
     rank = rank_live(live_lnl)
     killed = np.empty(K, dtype=np.int64)
     dying = np.flatnonzero(rank < K)
     killed[rank[dying]] = dying
     surv = np.flatnonzero(rank >= K)
-    mean, cov = mean_cov(live_u[surv])
-    C, ok = whiten(cov)
     ks = np.arange(K)
     choice = E.partner(thread_blocks(ks, t, np.zeros(K, dtype=np.int64), seed, stream)[:, 0], nlive - K).astype(np.int64)
+    if clusters is not None:
+        cl = cluster_points(live_u[surv], clusters.live_cluster[surv], clusters.next_id)
+        dead_cluster = clusters.live_cluster[killed].copy()
+        clusters.live_cluster[surv] = cl['ids']
+        clusters.next_id = cl['next_id']
+        return dict(rank=rank, killed=killed, lstar=live_lnl[killed[K - 1]], surv=surv, mean=cl['mean'], cov=cl['cov'], C=cl['C'],
+                    cholesky=cl['cholesky'], start=surv[choice], cluster=cl, dead_cluster=dead_cluster,
+                    start_slot=cl['slot'][choice], C_thread=cl['C'][cl['slot'][choice]])
+    mean, cov = mean_cov(live_u[surv])
+    C, ok = whiten(cov)
     return dict(rank=rank, killed=killed, lstar=live_lnl[killed[K - 1]], surv=surv, mean=mean, cov=cov, C=C, cholesky=ok,
                 start=surv[choice])
 
 
 class Threads:
-    """The K state machines of an iteration (vmx_ns::Thread as arrays)."""
+    """The K state machines of an iteration (vmx_ns::Thread as arrays); ``C`` [n, n], or [K, n, n]: a factor per thread."""
 
     def __init__(self, u, lnl, C, lstar, t, num_repeats, seed, stream=0):
         K, n = u.shape
@@ -174,7 +291,8 @@ class Threads:
         g = g / nrm[:, None]
         d = np.zeros((ix.size, n))
         for jj in range(n):         # (d_i accumulates C_ij g_j in the order j = 0 .. i)
-            d[:, jj:] = d[:, jj:] + self.C[jj:, jj][None, :] * g[:, jj][:, None]
+            col = self.C[jj:, jj][None, :] if self.C.ndim == 2 else self.C[ix][:, jj:, jj]
+            d[:, jj:] = d[:, jj:] + col * g[:, jj][:, None]
         self.d[ix] = d
         rw = r * WIDTH
         self.L[ix] = -rw
@@ -249,20 +367,24 @@ class Threads:
         return ks, np.where(self.inside[ks, None], self.y[ks], self.x[ks]), int((~self.inside[ks]).sum())
 
 
-def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, stream, evaluate, stop=None):
+def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, stream, evaluate, stop=None, clusters=None):
     """Up to ``n_iterations`` iterations in NumPy from the state ``live_u`` [nlive, n], ``live_lnl`` [nlive] (updated in place).
     ``evaluate(rows_u)`` -> lnL [R] of rows in the cube (-inf: a failed model).  ``stop(iterations, dead_lnl, live_lnl)`` as for
-    the device driver.  Returns (dead_u, dead_lnl, dead_nlive, iteration, stats)."""
+    the device driver.  ``clusters``: a :class:`ClusterState` turns clustering on (updated in place; the ids of this call's dead
+    are appended to its ``dead``).  Returns (dead_u, dead_lnl, dead_nlive, iteration, stats)."""
     nlive, n = live_u.shape
-    dead_u, dead_lnl, dead_n = [], [], []
+    dead_u, dead_lnl, dead_n, dead_c = [], [], [], []
     st = dict(iterations=0, rounds=0, rows=0, rows_own_position=0)
     for _ in range(n_iterations):
-        head = iteration_head(live_u, live_lnl, K, iteration, seed, stream)
+        head = iteration_head(live_u, live_lnl, K, iteration, seed, stream, clusters)
         killed = head['killed']
         dead_u.append(live_u[killed].copy())
         dead_lnl.append(live_lnl[killed].copy())
         dead_n.append(nlive - np.arange(K, dtype=np.int32))
-        T = Threads(live_u[head['start']], live_lnl[head['start']], head['C'], head['lstar'], iteration, num_repeats, seed, stream)
+        if clusters is not None:
+            dead_c.append(head['dead_cluster'])
+        T = Threads(live_u[head['start']], live_lnl[head['start']], head['C'] if clusters is None else head['C_thread'],
+                    head['lstar'], iteration, num_repeats, seed, stream)
         answer = np.full(K, -np.inf)
         asks = T.advance(answer)
         while asks.any():
@@ -275,10 +397,14 @@ def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats,
             asks = T.advance(answer)
         live_u[killed] = T.x
         live_lnl[killed] = T.lnl
+        if clusters is not None:
+            clusters.live_cluster[killed] = head['cluster']['cluster_id'][head['start_slot']]
         iteration += 1
         st['iterations'] += 1
         if stop is not None and stop(iteration, dead_lnl[-1], live_lnl):
             break
+    if clusters is not None:
+        clusters.dead.append(np.concatenate(dead_c) if dead_c else np.empty(0, dtype=np.int32))
     if not dead_u:
         return np.empty((0, n)), np.empty(0), np.empty(0, dtype=np.int32), iteration, st
     return np.concatenate(dead_u), np.concatenate(dead_lnl), np.concatenate(dead_n), iteration, st
@@ -322,11 +448,15 @@ def evidence(dead_lnl, dead_nlive, live_lnl):
 
 class NestedRun:
     """A nested-sampling run over ``loglike(rows_u [R, n]) -> lnL [R]`` in the unit cube (-inf: a failed model), NumPy driver: the
-    live points, the dead record, termination and the evidence.  :class:`NestedSampler` puts the engine behind it."""
+    live points, the dead record, termination and the evidence.  :class:`NestedSampler` puts the engine behind it.
+    ``clustering``: cluster the survivors of every iteration, whiten per cluster and keep ids (:meth:`clusters`)."""
 
     def __init__(self, loglike, n, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, stream=0,
-                 max_iterations=None, max_batch=None):
+                 max_iterations=None, max_batch=None, clustering=False):
         self.loglike = loglike
+        if not isinstance(clustering, (bool, np.bool_)):
+            raise ValueError('clustering: True or False')
+        self.clustering = bool(clustering)
         self.n = int(n)
         self.num_live = int(num_live) if num_live is not None else 25 * self.n
         self.num_repeats = int(num_repeats) if num_repeats is not None else 5 * self.n
@@ -358,6 +488,7 @@ class NestedRun:
         self._to_termination = True
         self._dead_u, self._dead_lnl, self._dead_n = [], [], []
         self._log_x, self._log_z_dead = 0.0, -np.inf
+        self.cluster_state = ClusterState(self.num_live) if self.clustering else None
         self.stats = dict(iterations=0, rounds=0, rows=0, rows_own_position=0, engine_calls=0, host_waits=0, seconds=0.0,
                           seconds_enqueuing=0.0, calls=0)
 
@@ -390,7 +521,8 @@ class NestedRun:
         if self.live_u is None:
             self._draw()
         du, dl, dn, self.iteration, st = python_iterations(self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
-                                                           self.num_repeats, self.seed, self.stream, self._evaluate, self._stop)
+                                                           self.num_repeats, self.seed, self.stream, self._evaluate, self._stop,
+                                                           clusters=self.cluster_state)
         return du, dl, dn, st
 
     def run(self, iterations=None):
@@ -444,11 +576,47 @@ class NestedRun:
     def to_physical(self, u):
         return u
 
-    def samples(self):
-        """(points [N, n], lnL [N], weights [N] summing to 1): the dead points in order of death, then the live points."""
+    def samples(self, cluster=None):
+        """(points [N, n], lnL [N], weights [N] summing to 1): the dead points in order of death, then the live points;
+        ``cluster``: those of one id of :meth:`clusters` only."""
         du, dl, _ = self.dead()
         p = self._evidence()[2]
-        return self.to_physical(np.concatenate([du, self.live_u])), np.concatenate([dl, self.live_lnl]), p / p.sum()
+        pts, lnl = self.to_physical(np.concatenate([du, self.live_u])), np.concatenate([dl, self.live_lnl])
+        if cluster is not None:
+            ids = self.cluster_ids()
+            if int(cluster) not in ids:
+                raise ValueError(f'no point carries the cluster id {cluster}')
+            keep = ids == int(cluster)
+            pts, lnl, p = pts[keep], lnl[keep], p[keep]
+        return pts, lnl, p / p.sum()
+
+    # ---- clusters
+    def cluster_ids(self):
+        """The id of every row of :meth:`samples`: what a dead point held when it was killed (0: never labelled), then the live
+        points' ids."""
+        if self.cluster_state is None:
+            raise ValueError('the run was not asked to cluster (clustering=True)')
+        if self.live_u is None:
+            raise ValueError('nothing has run yet')
+        return np.concatenate(self.cluster_state.dead + [self.cluster_state.live_cluster]).astype(np.int32)
+
+    def clusters(self):
+        """Per id in order of decreasing posterior mass, a dict: ``id``, ``log_z`` (the log-sum of L_i w_i over the dead and final
+        live points of that id, with the weights of :func:`log_weights`), ``mass`` (that local evidence over the whole),
+        ``n_dead``, ``n_live``."""
+        ids = self.cluster_ids()
+        _, dl, dn = self.dead()
+        lw = log_weights(dl, dn, self.live_lnl)
+        log_z = _logsumexp(lw)
+        out = []
+        for j in np.unique(ids):
+            lz = _logsumexp(lw[ids == j])
+            with np.errstate(invalid='ignore'):
+                mass = math.exp(lz - log_z) if np.isfinite(lz) and np.isfinite(log_z) else 0.0
+            out.append(dict(id=int(j), log_z=lz, mass=mass, n_dead=int(np.sum(ids[:dl.size] == j)),
+                            n_live=int(np.sum(ids[dl.size:] == j))))
+        out.sort(key=lambda c: (-c['mass'], c['id']))
+        return out
 
     def equal_weighted(self, rng=None):
         """Points of equal weight: each sample kept with probability weight / max weight.  (points [M, n], lnL [M])."""
@@ -468,10 +636,13 @@ class NestedSampler(E.EngineSampler, NestedRun):
     restatement over ``chi2_batch_device``); an engine group takes ``'python'``."""
 
     def __init__(self, vega, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, driver='device',
-                 sample_params=None, stream=0, chunk=0, lanes=0, const_hint=-1, max_iterations=None):
+                 sample_params=None, stream=0, chunk=0, lanes=0, const_hint=-1, max_iterations=None, clustering=False,
+                 cluster_posteriors=False):
         n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        self.cluster_posteriors = bool(cluster_posteriors)
         NestedRun.__init__(self, None, n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
-                           stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
+                           stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None),
+                           clustering=bool(clustering) or self.cluster_posteriors)
 
     def _advance(self, n_iterations):
         vega = self.vega
@@ -485,26 +656,38 @@ class NestedSampler(E.EngineSampler, NestedRun):
         du, dl, dn, self.iteration, st = vega.engine.nested_run(
             self.cols, self.lo, self.hi, self._theta, self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
             self.num_repeats, log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint,
-            chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop)
+            chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop, clusters=self.cluster_state)
         return du, dl, dn, st
 
     def write(self, path, name, derived=False, print_func=print):
         """getdist's weighted chain ``name.txt`` (weight / max weight, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
         ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
-        ones."""
-        return write_run(self, path, name, self.names, **self._write_extra(derived, print_func, self.derived))
+        ones.  A sampler built with ``cluster_posteriors`` also writes ``name_cluster_<j>.txt``, j = 1 ... in the order of
+        :meth:`clusters`, and their evidences and masses into ``name.stats``."""
+        return write_run(self, path, name, self.names, cluster_posteriors=self.cluster_posteriors,
+                         **self._write_extra(derived, print_func, self.derived))
 
 
 def nested_settings(main_config, sample_params):
     """The ``[Nested]`` settings of a main config with ``sampler = Nested`` (called by
     :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
     precision, seed, threads, driver, max_iterations}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them.``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
-    mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default."""
+    mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default.
+    ``do_clustering`` / ``cluster_posteriors`` (the reference's keys, both False when absent and then not in the settings;
+    ``cluster_posteriors`` implies ``do_clustering`` and is refused with ``replicas > 1``)."""
     sec, limits, out = E.section_settings(main_config, sample_params, 'Nested', name='nested')
     n = len(limits)
     out.update(num_live=sec.getint('num_live', 25 * n), num_repeats=sec.getint('num_repeats', 5 * n),
                precision=sec.getfloat('precision', 0.001), seed=sec.getint('seed', 0), threads=sec.getint('threads', None),
                max_iterations=sec.getint('max_iterations', None))
+    for key in ('do_clustering', 'cluster_posteriors'):         # (the reference's [Polychord] keys; absent: the settings of before)
+        if key in sec:
+            out[key] = sec.getboolean(key)
+    if out.get('cluster_posteriors'):
+        out['do_clustering'] = True
+        if out.get('replicas', 1) > 1:
+            raise ValueError('[Nested] cluster_posteriors and replicas > 1 do not combine: the cluster ids of different replicas '
+                             'are unrelated')
     if not n + 2 <= out['num_live'] <= MAX_LIVE:
         raise ValueError(f'[Nested] num_live: {n + 2} .. {MAX_LIVE} for {n} sampled parameters')
     if out['threads'] is not None and not 1 <= out['threads'] <= out['num_live'] - n - 1:
@@ -518,11 +701,24 @@ def nested_settings(main_config, sample_params):
     return out
 
 
-def write_run(run, path, name, names, **derived):
+def write_run(run, path, name, names, cluster_posteriors=False, **derived):
     """The three files of a finished :class:`NestedRun`: (txt, paramnames, stats); ``derived``: the derived-parameter arguments of
-    :func:`vega_amd.ensemble.write_getdist`."""
+    :func:`vega_amd.ensemble.write_getdist`.  ``cluster_posteriors`` (a run with clustering): also ``name_cluster_<j>.txt`` for
+    j = 1 ... in the order of ``run.clusters()``, the weighted chain of that id alone (with its own ``.paramnames``, so that
+    getdist reads it as a chain of its own), and per cluster the lines
+    ``log(Z_j)``, ``mass_j`` and ``id_j`` in ``name.stats``."""
     pts, lnl, w = run.samples()
     txt, pn = E.write_getdist(path, name, names, pts, lnl, weights=w / w.max(), **derived)
+    found = run.clusters() if cluster_posteriors else []
+    if found:
+        ids = run.cluster_ids()
+        block = derived.get('derived')
+        for j, c in enumerate(found, start=1):
+            keep = ids == c['id']
+            extra = dict(derived, derived=np.asarray(block)[keep]) if block is not None else derived
+            wj = w[keep]
+            top = wj.max() if wj.size and wj.max() > 0.0 else 1.0
+            E.write_getdist(path, f'{name}_cluster_{j}', names, pts[keep], lnl[keep], weights=wj / top, **extra)
     log_z, err = run.log_evidence()
     stats = Path(path) / f'{name}.stats'
     with open(stats, 'w') as f:
@@ -530,6 +726,8 @@ def write_run(run, path, name, names, **derived):
         f.write(f'dead points = {sum(len(d) for d in run._dead_lnl)}\nlikelihood evaluations = {run.stats["rows"]}\n')
         f.write(f'iterations = {run.iteration}\nseed = {run.seed}\nnum_live = {run.num_live}\nnum_repeats = {run.num_repeats}\n')
         f.write(f'threads = {run.threads}\n')
+        for j, c in enumerate(found, start=1):
+            f.write(f'log(Z_{j}) = {c["log_z"]!r}\nmass_{j} = {c["mass"]!r}\nid_{j} = {c["id"]}\n')
     return txt, pn, stats
 
 
@@ -538,5 +736,6 @@ def read_stats(path):
     out = {}
     for line in Path(path).read_text().splitlines():
         key, _, val = line.partition(' = ')
-        out[key] = float(val) if key in ('log(Z)', 'log(Z) error', 'H') else int(val)
+        real = key in ('log(Z)', 'log(Z) error', 'H') or key.startswith('log(Z_') or key.startswith('mass_')
+        out[key] = float(val) if real else int(val)
     return out

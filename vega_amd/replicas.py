@@ -10,7 +10,8 @@ Ranks take contiguous shares of ``range(R)`` (:func:`vega_amd.parallel.shard_bou
 own engine; every replica leaves one record ``<name>.replica<r>.npz``; after a barrier rank 0 reads the R records back and merges:
 
 * nested runs merge exactly into one run with the summed live count (:func:`merge_nested`; Skilling 2006, the rule nestcheck and
-  dyPolyChord use),
+  dyPolyChord use); replicas that cluster (``do_clustering``) number their clusters independently, so a record carries no
+  cluster ids and the merged run has none (``cluster_posteriors`` with ``replicas > 1`` is refused when the settings are read),
 * SMC evidences are unbiased, so they average (:func:`merge_smc`),
 * independent ensembles are kept apart and supply what one ensemble cannot, a between-chain convergence figure
   (:func:`gelman_rubin`).
