@@ -463,8 +463,8 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats);
 /* E independent ensembles advanced together: a posterior for every Monte-Carlo mock, or the replicas of one run, as one device run.
  * A run of W = 32 - 64 walkers hands the engine batches of 16 - 32 rows, far below what it is fast at; here the half-steps of all
- * ensembles are decided by one kernel of E work-groups (k_ens_half_many: work-group e does for ensemble e exactly what the kernel
- * of the single run does, nothing crosses ensembles) and their E W/2 proposal rows go through the engine as one stream of chunks
+ * ensembles are decided by one kernel of E work-groups (k_ens_half: work-group e owns ensemble e, nothing crosses ensembles; the
+ * single run is this routine with E = 1) and their E W/2 proposal rows go through the engine as one stream of chunks
  * of `chunk` on two lanes.  Ensemble e is by construction the chain the single run makes with spec->stream = streams[e] on the
  * same data; its chi2 is evaluated in batches of another shape, so that its lnL may differ from the single run's in the last bits
  * (E = 1 has the single run's batches and gives its chain bit for bit).

@@ -72,6 +72,18 @@ def test_drivers_agree_on_the_joint_problem_with_two_lanes():
         vega.close()
 
 
+@pytest.mark.parametrize('W, steps, calls_per_half', [(8, 10, 1), (2112, 3, 5)])
+def test_drivers_agree_at_both_ends_of_the_block_size(auto_vega, W, steps, calls_per_half):
+    """The block of the half-step kernel follows the half: H = 4, far below one wave, a block of 64; H = 1056, beyond the 1024
+    threads of a block, so the strided loop runs, its rows in 5 chunks of max_batch = 256."""
+    sp = _sample_params(auto_vega, AUTO_SAMPLED)
+    dev, py = _pair(auto_vega, W, steps, sp)
+    _assert_same(dev, py)
+    assert dev.get_chain().shape == (steps, W, 4)
+    assert 0 < dev.stats['accepted'] < dev.stats['proposals'] == steps * W
+    assert dev.stats['engine_calls'] == steps * 2 * calls_per_half and dev.stats['host_synchronisations'] == 1
+
+
 def test_chain_is_independent_of_the_cut(auto_vega):
     from vega_amd import EnsembleSampler
     sp = _sample_params(auto_vega, AUTO_SAMPLED)

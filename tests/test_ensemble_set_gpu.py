@@ -71,6 +71,8 @@ def _assert_same(dev, py):
 
 
 def test_one_ensemble_is_the_existing_sampler(auto_vega):
+    """One kernel and one host routine serve both: this holds the two exported entries (vmx_ensemble_run, vmx_ensemble_run_many
+    with E = 1) and the two Python classes over them to one chain."""
     from vega_amd import EnsembleSampler, EnsembleSet
     sp = _sample_params(auto_vega, AUTO_SAMPLED)
     both = EnsembleSet(auto_vega, 1, 64, streams=[3], seed=7, sample_params=sp).run(30)
@@ -83,6 +85,48 @@ def test_one_ensemble_is_the_existing_sampler(auto_vega):
     member = both.member(0)
     assert np.array_equal(member.get_chain(flat=True), one.get_chain(flat=True)) and member.stats['accepted'] == one.stats['accepted']
     assert np.array_equal(member.acceptance_fraction, one.acceptance_fraction)
+
+
+def _entry_state(vega):
+    """A start inside the box of two sampled columns, W = 8, with the lnL of its rows (log_norm = 0): (cols, lo, hi, theta_fixed,
+    x, lnl)."""
+    eng = vega.engine
+    cols = [eng.names.index('bias_eta_LYA'), eng.names.index('beta_LYA')]
+    lo, hi = np.array([-0.5, 0.5]), np.array([0.0, 3.0])
+    x = np.array([-0.2, 1.67]) + 0.01 * np.random.default_rng(2).standard_normal((8, 2))
+    assert np.all(x >= lo) and np.all(x <= hi)
+    theta = eng.low.theta0.copy()
+    rows = np.repeat(theta[None, :], 8, axis=0)
+    rows[:, cols] = x
+    return cols, lo, hi, theta, x, -0.5 * np.asarray(vega.chi2_batch(rows), dtype=np.float64)
+
+
+def test_the_two_entries_are_one_routine(auto_vega):
+    """ctypes level: `ensemble_run(stream=3)` and `ensemble_run_many(streams=[3])` from the same start, from a step0 that is no
+    multiple of thin - the same chain, state and counters bit for bit; the forwarder passes the stream on (stream 4 is another
+    chain); without the chain kept the final state is the same."""
+    eng = auto_vega.engine
+    cols, lo, hi, theta, x0, lnl0 = _entry_state(auto_vega)
+    kw = dict(step0=3, n_steps=8, thin=3)
+
+    def single(stream, **more):
+        x, lnl, acc = x0.copy(), lnl0.copy(), np.zeros(8, dtype=np.int64)
+        chain, chain_lnl, st = eng.ensemble_run(cols, lo, hi, theta, x, lnl, acc, stream=stream, **kw, **more)
+        return chain, chain_lnl, x, lnl, acc, st
+
+    chain, chain_lnl, x, lnl, acc, st = single(3)
+    xm, lnlm, accm = x0[None].copy(), lnl0[None].copy(), np.zeros((1, 8), dtype=np.int64)
+    chain_m, chain_lnl_m, st_m = eng.ensemble_run_many(cols, lo, hi, theta, xm, lnlm, accm, streams=[3], **kw)
+    # (steps 3 .. 10, thin 3: the rows after steps 6 and 9)
+    assert chain.shape == (2, 8, 2) and chain_m.shape == (1, 2, 8, 2) and chain_lnl_m.shape == (1, 2, 8)
+    assert np.array_equal(chain, chain_m[0]) and np.array_equal(chain_lnl, chain_lnl_m[0])
+    assert np.array_equal(x, xm[0]) and np.array_equal(lnl, lnlm[0]) and np.array_equal(acc, accm[0])
+    assert (st['accepted'], st['rejected_outside_box'], st['rejected_failed_model']) == tuple(st_m['per_ensemble'][0])
+    assert 0 < st['accepted'] == acc.sum() and st['proposals'] == st_m['proposals'] == 8 * 8
+    assert not np.array_equal(single(4)[0], chain)
+    none, none_lnl, x_k, lnl_k, acc_k, _ = single(3, keep_chain=False)
+    assert none is None and none_lnl is None
+    assert np.array_equal(x_k, x) and np.array_equal(lnl_k, lnl) and np.array_equal(acc_k, acc)
 
 
 def test_drivers_agree_on_shared_data(auto_vega):

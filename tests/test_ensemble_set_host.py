@@ -1,6 +1,7 @@
 """Many ensembles advanced together (vega_amd/ensemble.py: EnsembleSet, python_steps_many) on the CPU, without an engine: the set's
-NumPy restatement makes, for every ensemble, exactly the chain a single `python_steps` run makes on that ensemble's Philox stream
-and data - whole or cut into segments -, every member starts from the walkers the single sampler draws, the config keys
+NumPy restatement makes, for every ensemble, exactly the chain a single-ensemble loop kept here (`_reference_python_steps`) makes on
+that ensemble's Philox stream and data - whole or cut into segments -, `python_steps` (the set of one) makes that chain too, every
+member starts from the walkers the single sampler draws, the config keys
 ``[Ensemble] mocks`` / ``together`` parse and refuse as documented, and over a stand-in interface the ``python`` driver gives every
 ensemble its mock and ``together = True`` writes the records and merged files of the sequential path."""
 import configparser
@@ -36,9 +37,37 @@ def _starts(means, sd, lo, hi):
     return np.clip(means[:, None, :] + 0.3 * sd * rng.standard_normal((len(STREAMS), W, N)), lo, hi)
 
 
+def _reference_python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate):
+    """The single-ensemble loop as `python_steps` was written before it became the E = 1 case of `python_steps_many`: the
+    reference both are held to.  Same arguments, same returned triple."""
+    W, n = x.shape
+    H = W // 2
+    rows = (step0 + n_steps) // thin - step0 // thin
+    chain, chain_lnl = np.empty((rows, W, n)), np.empty((rows, W))
+    st = dict(steps=n_steps, proposals=n_steps * W, accepted=0, rejected_outside_box=0, rejected_failed_model=0)
+    for s in range(step0, step0 + n_steps):
+        for h in (0, 1):
+            y, inside, factor, b = E.half_step_proposals(x, h, s, a, seed, stream, lo, hi)
+            mine = slice(h * H, (h + 1) * H)
+            chi2, status = evaluate(np.where(inside[:, None], y, x[mine]), h)
+            ok = E.model_ok(status, chi2)
+            lnl_new = E.log_lik(log_norm, chi2)
+            acc = E.accept(inside, ok, factor, lnl_new, lnl[mine], b[:, 2])
+            x[mine][acc] = y[acc]
+            lnl[mine][acc] = lnl_new[acc]
+            accepted[mine] += acc
+            st['accepted'] += int(acc.sum())
+            st['rejected_outside_box'] += int((~inside).sum())
+            st['rejected_failed_model'] += int((inside & ~ok).sum())
+        if (s + 1) % thin == 0:
+            r = (s + 1) // thin - step0 // thin - 1
+            chain[r], chain_lnl[r] = x, lnl
+    return chain, chain_lnl, st
+
+
 @pytest.fixture(scope='module')
 def separate():
-    """Three separate `python_steps` runs: the reference, computed once."""
+    """Three separate `_reference_python_steps` runs: the reference, computed once."""
     means, icov, lo, hi, sd = _problem()
     x0 = _starts(means, sd, lo, hi)
     out = []
@@ -46,8 +75,9 @@ def separate():
         x = x0[e].copy()
         lnl = E.log_lik(LOG_NORM, _chi2(x, means[e], icov))
         acc = np.zeros(W, dtype=np.int64)
-        chain, chain_lnl, st = E.python_steps(x, lnl, acc, 0, STEPS, THIN, A, SEED, stream, lo, hi, LOG_NORM,
-                                              lambda rows, h, e=e: (_chi2(rows, means[e], icov), np.zeros(len(rows), dtype=np.int32)))
+        chain, chain_lnl, st = _reference_python_steps(
+            x, lnl, acc, 0, STEPS, THIN, A, SEED, stream, lo, hi, LOG_NORM,
+            lambda rows, h, e=e: (_chi2(rows, means[e], icov), np.zeros(len(rows), dtype=np.int32)))
         out.append((chain, chain_lnl, acc, x, lnl, st))
     return out
 
@@ -86,6 +116,35 @@ def test_the_set_restates_separate_runs(separate, segments):
     assert 0 < per[:, 0].sum() < STEPS * W * 3
     # (the ensembles are different chains: another stream, another mean)
     assert not np.array_equal(chain[0], chain[1]) and not np.array_equal(chain[1], chain[2])
+
+
+def test_python_steps_is_the_set_of_one():
+    """`python_steps` against the reference loop from a step0 that is no multiple of thin, on a non-zero stream: chain, lnL, the
+    state updated in place, the counters and the statistics, bit for bit; the rows `evaluate` sees are one half's."""
+    means, icov, lo, hi, sd = _problem()
+    step0, n_steps, thin, stream = 3, STEPS, 2, 5
+    start = _starts(means, sd, lo, hi)[1]
+    seen = []
+
+    def evaluate(rows, h):
+        seen.append((rows.shape, h))
+        return _chi2(rows, means[1], icov), np.zeros(len(rows), dtype=np.int32)
+
+    runs = []
+    for steps in (_reference_python_steps, E.python_steps):
+        x = start.copy()
+        lnl = E.log_lik(LOG_NORM, _chi2(x, means[1], icov))
+        acc = np.arange(W, dtype=np.int64)
+        chain, chain_lnl, st = steps(x, lnl, acc, step0, n_steps, thin, A, SEED, stream, lo, hi, LOG_NORM, evaluate)
+        runs.append((chain, chain_lnl, x, lnl, acc, st))
+    ref, new = runs
+    rows = (step0 + n_steps) // thin - step0 // thin
+    assert new[0].shape == (rows, W, N) and new[1].shape == (rows, W)
+    for got, want in zip(new[:5], ref[:5]):
+        assert got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got, want)
+    assert new[5] == ref[5] and list(new[5]) == list(ref[5])
+    assert 0 < ref[5]['accepted'] < n_steps * W and not np.array_equal(new[2], start)
+    assert seen[:2 * n_steps] == seen[2 * n_steps:] and set(shape for shape, _ in seen) == {(W // 2, N)}
 
 
 def _stand_in():

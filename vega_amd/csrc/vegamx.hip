@@ -210,99 +210,42 @@ __device__ inline void write_cube_rows(const BoxDev& B, int P, int rows, U u)
     }
 }
 
-// Ensemble sampling (vmx_ensemble_run): the walkers' state, the proposals of a half and the chain record, grown on demand
+// Ensemble sampling (vmx_ensemble_run, vmx_ensemble_run_many): the walkers' state of the E ensembles, the proposals of a half and
+// the chain record, grown on demand
 struct EnsWorkspace {
     BoxWorkspace box;
     DevBuf<double> x, lnl, prop, factor, chain, chain_lnl;
     DevBuf<int64_t> acc, n_box, n_fail;
     DevBuf<int32_t> inside, col;
-    DevBuf<int32_t> mock;               // vmx_ensemble_run_many: the mock row of every engine row [E H], written once per call
-    DevBuf<uint64_t> streams;           // and the ensembles' Philox streams [E]
+    DevBuf<int32_t> mock;               // the mock row of every engine row [E H], written once per call that names mocks
+    DevBuf<uint64_t> streams;           // the ensembles' Philox streams [E]
 };
 
 struct EnsDev {
-    double* x; double* lnl; int64_t* acc; int64_t* n_box; int64_t* n_fail;      // [W][n], [W], [W] x 3
-    double* prop; double* factor; int32_t* inside;                              // the active half's proposals [H][n], [H], [H]
-    BoxDev box;                                                                 // rows [H][P]
+    double* x; double* lnl; int64_t* acc; int64_t* n_box; int64_t* n_fail;      // [E][W][n], [E][W], [E][W] x 3
+    double* prop; double* factor; int32_t* inside;                              // the active half's proposals [E][H][n], [E][H] x 2
+    BoxDev box;                                                                 // rows [E H][P]: ensemble e's at [e H, (e + 1) H)
     const int32_t* col;                                                         // (a walker writes its own row: the sampled columns listed)
-    double* chain; double* chain_lnl;                                           // [rows][W][n], [rows][W] (nullptr: not kept)
+    double* chain; double* chain_lnl;                                           // [E][rows][W][n], [E][rows][W] (nullptr: not kept)
+    const uint64_t* streams;                                                    // [E]
+    int64_t rows;                                                               // chain rows of this call, per ensemble
     int32_t W, n, P, thin;
     double a, log_norm;
-    uint64_t seed, stream;
+    uint64_t seed;
     int64_t step0;
 };
 
-// One half-step of the sampler in one work-group (partners read the half decided just before, a grid-wide dependency):
-// decide the proposals of half h_dec at step s_dec (s_dec < 0: none), record the chain row when step s_dec is complete and due,
-// then propose half h_prop at step s_prop (s_prop < 0: none) and write the engine's rows.  Every expression: vmx_ensemble.h.
+// One half-step of the sampler, a grid of E work-groups: work-group e owns ensemble e (partners read the half decided just before,
+// a dependency across the whole ensemble; nothing crosses ensembles, so __syncthreads() is the only barrier) under the Philox
+// stream streams[e].  Decide the proposals of half h_dec at step s_dec (s_dec < 0: none), record the chain row when step s_dec is
+// complete and due, then propose half h_prop at step s_prop (s_prop < 0: none) and write the engine's rows, so that the E H
+// proposal rows of a half-step are one stream of chunks for the engine.  Every expression: vmx_ensemble.h.
 constexpr int ENS_THREADS = 1024;
 __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
 {
-    const int H = D.W / 2, n = D.n;
-    if (s_dec >= 0) {
-        for (int k = threadIdx.x; k < H; k += blockDim.x) {
-            const int w = h_dec * H + k;
-            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, D.stream);
-            const double c2 = D.box.chi2[k];
-            const bool inside = D.inside[k] != 0, ok = vmx_ens::model_ok(D.box.status[k], c2);
-            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
-            if (vmx_ens::accept(inside, ok, D.factor[k], lnl_new, D.lnl[w], b.w[2])) {
-                for (int d = 0; d < n; ++d) D.x[(size_t)w * n + d] = D.prop[(size_t)k * n + d];
-                D.lnl[w] = lnl_new;
-                D.acc[w] += 1;
-            } else if (!inside) D.n_box[w] += 1;
-            else if (!ok) D.n_fail[w] += 1;
-        }
-        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
-            __syncthreads();
-            const int64_t r = (s_dec + 1) / D.thin - D.step0 / D.thin - 1;
-            if (D.chain)
-                for (int q = threadIdx.x; q < D.W * n; q += blockDim.x) D.chain[(size_t)r * D.W * n + q] = D.x[q];
-            if (D.chain_lnl)
-                for (int q = threadIdx.x; q < D.W; q += blockDim.x) D.chain_lnl[(size_t)r * D.W + q] = D.lnl[q];
-        }
-    }
-    if (s_prop < 0) return;
-    __syncthreads();            // (the partners of the next half are the walkers just decided)
-    for (int k = threadIdx.x; k < H; k += blockDim.x) {
-        const int w = h_prop * H + k;
-        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, D.stream);
-        const int64_t j = vmx_ens::partner(b.w[0], H);
-        const double* c = D.x + (size_t)((1 - h_prop) * H + j) * n;
-        const double* s = D.x + (size_t)w * n;
-        const double z = vmx_ens::stretch_z(D.a, b.w[1]);
-        double* y = D.prop + (size_t)k * n;
-        bool in = true;
-        for (int d = 0; d < n; ++d) {
-            const double v = vmx_ens::propose(c[d], s[d], z);
-            y[d] = v;
-            in = in && v >= D.box.lo[d] && v <= D.box.hi[d];
-        }
-        D.factor[k] = vmx_ens::log_factor(n, z);
-        D.inside[k] = in ? 1 : 0;
-        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
-        double* row = D.box.theta + (size_t)k * D.P;
-        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
-        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
-    }
-}
-
-// E independent ensembles, one work-group each (vmx_ensemble_run_many): block e does for ensemble e what k_ens_half does for its
-// one - the same expressions of vmx_ensemble.h in the same order, under the Philox stream streams[e].  Every per-ensemble array
-// of EnsDev has a leading E dimension here; the engine's rows of ensemble e are rows [e H, (e + 1) H) of the box workspace, so
-// that the E H proposal rows of a half-step are one stream of chunks for the engine.  Nothing crosses ensembles: no barrier beyond
-// __syncthreads().
-struct EnsManyDev {
-    EnsDev D;                       // (D.stream is not read)
-    const uint64_t* streams;        // [E]
-    int64_t rows;                   // chain rows of this call, per ensemble
-};
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_many(EnsManyDev M, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
-{
-    const EnsDev& D = M.D;
     const int W = D.W, H = W / 2, n = D.n;
     const size_t e = blockIdx.x;
-    const uint64_t stream = M.streams[e];
+    const uint64_t stream = D.streams[e];
     double* const x = D.x + e * W * n;
     double* const lnl = D.lnl + e * W;
     int64_t* const acc = D.acc + e * W;
@@ -330,7 +273,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_many(EnsManyDev M, int
         }
         if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
             __syncthreads();
-            const size_t r = e * M.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
+            const size_t r = e * D.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
             if (D.chain)
                 for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
             if (D.chain_lnl)
@@ -4467,136 +4410,68 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
 }
 
 // ---- posterior sampling where the walkers live (vmx_ensemble.h)
+static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                        const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                        int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble);
+
+// One ensemble is the set of one, on the stream of its spec
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
                      int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats)
 {
-    REQUIRE(e && e->finalized && spec && x && lnL && accepted, "vmx_ensemble_run");
-    std::vector<char> varies;
-    std::vector<int32_t> inv;
-    if (check_box("vmx_ensemble_run", e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
-    const int n = spec->n, P = e->n_params;
-    REQUIRE(W >= 2 * n && W % 2 == 0, "vmx_ensemble_run: an even number of walkers, at least twice the sampled columns");
-    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), "vmx_ensemble_run: the stretch scale a must exceed 1");
-    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, "vmx_ensemble_run: thin >= 1, n_steps >= 0, step0 >= 0");
-    for (int w = 0; w < W; ++w) {
-        REQUIRE(std::isfinite(lnL[w]), "vmx_ensemble_run: a start walker has a non-finite lnL");
-        for (int i = 0; i < n; ++i) {
-            const double v = x[(size_t)w * n + i];
-            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], "vmx_ensemble_run: a start walker lies outside the box");
-        }
-    }
-    if (LikelihoodSession::check("vmx_ensemble_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
-    const int H = W / 2;
-    const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
-
-    HIP_OK(hipSetDevice(e->device));
-    const auto t_begin = std::chrono::steady_clock::now();
-    if (!e->ensws) e->ensws = new EnsWorkspace();
-    EnsWorkspace& S = *e->ensws;
-    if (ensure(S.x, (size_t)W * n) || ensure(S.lnl, W) || ensure(S.acc, W) || ensure(S.n_box, W) || ensure(S.n_fail, W) ||
-        ensure(S.prop, (size_t)H * n) || ensure(S.factor, H) || ensure(S.inside, H) || ensure(S.col, n))
-        return -2;
-    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * W * n)) return -2;
-    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * W)) return -2;
-    hipStream_t st = e->stream;
-    EnsDev D{};
-    if (S.box.upload(H, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
-    HIP_OK(hipMemcpyAsync(S.x.p, x, (size_t)W * n * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, (size_t)W * sizeof(double), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemcpyAsync(S.acc.p, accepted, (size_t)W * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    HIP_OK(hipMemsetAsync(S.n_box.p, 0, (size_t)W * sizeof(int64_t), st));
-    HIP_OK(hipMemsetAsync(S.n_fail.p, 0, (size_t)W * sizeof(int64_t), st));
-    HIP_OK(hipMemcpyAsync(S.col.p, spec->col, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-
-    D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p; D.n_box = S.n_box.p; D.n_fail = S.n_fail.p;
-    D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
-    D.col = S.col.p;
-    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
-    D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
-    D.seed = spec->seed; D.stream = spec->stream; D.step0 = step0;
-
-    // the engine as the sampler's likelihood, at the table level the sampled columns allow
-    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
-    vmx_ensemble_stats R{};
-    R.const_hint = L.hint;
-    R.lanes = L.lanes;
-    const auto t_loop = std::chrono::steady_clock::now();
-    const int64_t halves = 2 * (int64_t)n_steps;
-    if (halves > 0) hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, (int64_t)-1, 0, step0, 0);
-    HIP_OK(hipGetLastError());
-    for (int64_t q = 0; q < halves; ++q) {
-        const int64_t s = step0 + q / 2;
-        const int h = (int)(q % 2);
-        const int calls = L.evaluate(S.box.theta.p, H, S.box.chi2.p, S.box.status.p, nullptr, true);
-        if (calls < 0) return -2;
-        R.engine_calls += calls;
-        const int64_t nq = q + 1;
-        hipLaunchKernelGGL(k_ens_half, dim3(1), dim3(ENS_THREADS), 0, st, D, s, h,
-                           nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
-        HIP_OK(hipGetLastError());
-    }
-    std::vector<int64_t> acc0(accepted, accepted + W), box(W), failed(W);
-    HIP_OK(hipMemcpyAsync(x, S.x.p, (size_t)W * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, (size_t)W * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(accepted, S.acc.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(box.data(), S.n_box.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(failed.data(), S.n_fail.p, (size_t)W * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * W * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * W * sizeof(double), hipMemcpyDeviceToHost, st));
-    R.seconds_enqueuing = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
-    HIP_OK(hipStreamSynchronize(st));       // (the call's only wait: the segment is enqueued as a whole)
-    R.host_synchronisations = 1;
-    R.steps = n_steps;
-    R.proposals = (int64_t)n_steps * W;
-    for (int w = 0; w < W; ++w) {
-        R.accepted += accepted[w] - acc0[w];
-        R.rejected_outside_box += box[w];
-        R.rejected_failed_model += failed[w];
-    }
-    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    if (stats) *stats = R;
-    return 0;
+    REQUIRE(spec, "vmx_ensemble_run");
+    return ensemble_run("vmx_ensemble_run", e, spec, 1, W, &spec->stream, nullptr, x, lnL, accepted, step0, n_steps, thin, chain,
+                        chain_lnL, opt, stats, nullptr);
 }
 
-// E independent ensembles advanced together (k_ens_half_many): vmx_ensemble_run line for line, the E H proposal rows of a
-// half-step as one stream of chunks for the engine, every row with the mock of its ensemble
 int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                           const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                           int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
                           vmx_ensemble_stats* stats, int64_t* per_ensemble)
 {
-    REQUIRE(e && e->finalized && spec && x && lnL && accepted, "vmx_ensemble_run_many");
-    REQUIRE(E >= 1, "vmx_ensemble_run_many: at least one ensemble");
-    REQUIRE(streams, "vmx_ensemble_run_many: a Philox stream for every ensemble");
+    return ensemble_run("vmx_ensemble_run_many", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, chain,
+                        chain_lnL, opt, stats, per_ensemble);
+}
+
+// E independent ensembles advanced together (k_ens_half): the E H proposal rows of a half-step as one stream of chunks for the
+// engine, every row with the mock of its ensemble
+static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                        const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                        int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble)
+{
+    const std::string name(who);
+    REQUIRE(e && e->finalized && spec && x && lnL && accepted, name);
+    REQUIRE(E >= 1, name + ": at least one ensemble");
+    REQUIRE(streams, name + ": a Philox stream for every ensemble");
     std::vector<char> varies;
     std::vector<int32_t> inv;
-    if (check_box("vmx_ensemble_run_many", e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
+    if (check_box(name, e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params;
-    REQUIRE(W >= 2 * n && W % 2 == 0, "vmx_ensemble_run_many: an even number of walkers, at least twice the sampled columns");
-    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), "vmx_ensemble_run_many: the stretch scale a must exceed 1");
-    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, "vmx_ensemble_run_many: thin >= 1, n_steps >= 0, step0 >= 0");
+    REQUIRE(W >= 2 * n && W % 2 == 0, name + ": an even number of walkers, at least twice the sampled columns");
+    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), name + ": the stretch scale a must exceed 1");
+    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, name + ": thin >= 1, n_steps >= 0, step0 >= 0");
     const int H = W / 2;
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
     // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
-    REQUIRE((int64_t)E * W <= INT32_MAX, "vmx_ensemble_run_many: E W exceeds the engine's row count");
+    REQUIRE((int64_t)E * W <= INT32_MAX, name + ": E W exceeds the engine's row count");
     const size_t EW = (size_t)E * W, per_row = (size_t)std::max(n, P) * sizeof(double);
-    REQUIRE(EW <= SIZE_MAX / per_row && (rows <= 0 || EW * per_row <= SIZE_MAX / (size_t)rows),
-            "vmx_ensemble_run_many: the chain is too large");
+    REQUIRE(EW <= SIZE_MAX / per_row && (rows <= 0 || EW * per_row <= SIZE_MAX / (size_t)rows), name + ": the chain is too large");
     for (size_t w = 0; w < EW; ++w) {
-        REQUIRE(std::isfinite(lnL[w]), "vmx_ensemble_run_many: a start walker has a non-finite lnL");
+        REQUIRE(std::isfinite(lnL[w]), name + ": a start walker has a non-finite lnL");
         for (int i = 0; i < n; ++i) {
             const double v = x[w * n + i];
-            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], "vmx_ensemble_run_many: a start walker lies outside the box");
+            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], name + ": a start walker lies outside the box");
         }
     }
     if (mock_row)
         for (int q = 0; q < E; ++q)
             for (auto* it : e->items) {
-                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, "vmx_ensemble_run_many: mock rows, but an item has no mock pool");
-                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, "vmx_ensemble_run_many: mock row outside the pool");
+                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
+                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
             }
-    if (LikelihoodSession::check("vmx_ensemble_run_many", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const int EH = E * H;
 
     HIP_OK(hipSetDevice(e->device));
@@ -4610,8 +4485,7 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
     if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
     if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
     hipStream_t st = e->stream;
-    EnsManyDev M{};
-    EnsDev& D = M.D;
+    EnsDev D{};
     if (S.box.upload(EH, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
     HIP_OK(hipMemcpyAsync(S.x.p, x, EW * n * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, EW * sizeof(double), hipMemcpyHostToDevice, st));
@@ -4632,9 +4506,9 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
     D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
     D.col = S.col.p;
     D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.streams = S.streams.p; D.rows = rows;
     D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
-    D.seed = spec->seed; D.stream = 0; D.step0 = step0;
-    M.streams = S.streams.p; M.rows = rows;
+    D.seed = spec->seed; D.step0 = step0;
 
     // the engine as the sampler's likelihood, at the table level the sampled columns allow
     LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
@@ -4643,8 +4517,9 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
     R.lanes = L.lanes;
     const auto t_loop = std::chrono::steady_clock::now();
     const int64_t halves = 2 * (int64_t)n_steps;
+    // (every loop of the kernel strides by its block: the chain does not depend on this size)
     const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
-    if (halves > 0) hipLaunchKernelGGL(k_ens_half_many, grid, block, 0, st, M, (int64_t)-1, 0, step0, 0);
+    if (halves > 0) hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, (int64_t)-1, 0, step0, 0);
     HIP_OK(hipGetLastError());
     for (int64_t q = 0; q < halves; ++q) {
         const int64_t s = step0 + q / 2;
@@ -4653,7 +4528,7 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
         if (calls < 0) return -2;
         R.engine_calls += calls;
         const int64_t nq = q + 1;
-        hipLaunchKernelGGL(k_ens_half_many, grid, block, 0, st, M, s, h,
+        hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s, h,
                            nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
         HIP_OK(hipGetLastError());
     }

@@ -1086,28 +1086,37 @@ class Engine:
             raise ValueError(f'{pname} [rows, n], {lname} [rows], theta_fixed [n_params]')
         return cols, lo, hi, theta_fixed, rows
 
+    def _ensemble_arrays(self, ndim, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, *, a, log_norm,
+                         seed, stream, const_hint, chunk, lanes):
+        """What :meth:`ensemble_run` (``ndim`` 2: x [W, n]) and :meth:`ensemble_run_many` (3: x [E, W, n]) hand the library alike:
+        the box and the state checked as :meth:`_sampled_box` checks them, the chain [(E,) rows, W, n] with its lnL (None: not
+        kept), the spec, the call's arguments from ``x`` to the options, and the statistics; last, what the pointers borrow."""
+        _in_place(np.float64, x=x, lnl=lnl)
+        _in_place(np.int64, accepted=accepted)
+        if x.ndim != ndim or lnl.shape != x.shape[:-1] or accepted.shape != x.shape[:-1]:
+            raise ValueError('x [W, n], lnl [W], accepted [W]' if ndim == 2 else 'x [E, W, n], lnl [E, W], accepted [E, W]')
+        cols, lo, hi, theta_fixed, _ = self._sampled_box(cols, lo, hi, theta_fixed, x=x.reshape(-1, x.shape[-1]), lnl=lnl.reshape(-1))
+        step0, n_steps, thin = int(step0), int(n_steps), int(thin)
+        rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
+        chain = np.empty(x.shape[:-2] + (rows,) + x.shape[-2:]) if keep_chain else None
+        chain_lnl = np.empty(x.shape[:-2] + (rows, x.shape[-2])) if keep_chain else None
+        spec = EnsembleSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), float(a), float(log_norm), int(seed), int(stream),
+                            _dp(theta_fixed))
+        opt = EnsembleOptions(int(const_hint), int(chunk), int(lanes), 0)
+        args = (_dp(x), _dp(lnl), accepted.ctypes.data_as(C.POINTER(C.c_int64)), step0, n_steps, thin,
+                _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None, C.byref(opt))
+        return spec, args, chain, chain_lnl, EnsembleStats(), (cols, lo, hi, theta_fixed, opt)
+
     def ensemble_run(self, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin=1, a=2.0, log_norm=0.0, seed=0,
                      stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
         """``n_steps`` steps of the ensemble sampler on the device (include/vegamx.h: vmx_ensemble_run): ``cols`` the sampled
         parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``x`` [W, n] / ``lnl`` [W] / ``accepted``
         int64 [W] the walkers' state (updated in place), ``step0`` the global index of the first step.  Returns (chain [rows, W, n],
         chain_lnl [rows, W], statistics), rows = (step0 + n_steps) // thin - step0 // thin."""
-        cols, lo, hi, theta_fixed, W = self._sampled_box(cols, lo, hi, theta_fixed, x=x, lnl=lnl)
-        _in_place(np.int64, accepted=accepted)
-        if accepted.shape != (W,):
-            raise ValueError('accepted [W]')
-        step0, n_steps, thin = int(step0), int(n_steps), int(thin)
-        rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
-        chain = np.empty((rows, W, cols.size)) if keep_chain else None
-        chain_lnl = np.empty((rows, W)) if keep_chain else None
-        spec = EnsembleSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), float(a), float(log_norm), int(seed), int(stream),
-                            _dp(theta_fixed))
-        opt = EnsembleOptions(int(const_hint), int(chunk), int(lanes), 0)
-        stats = EnsembleStats()
-        self._check(self.lib.vmx_ensemble_run(self._h, C.byref(spec), W, _dp(x), _dp(lnl),
-                                              accepted.ctypes.data_as(C.POINTER(C.c_int64)), step0, n_steps, thin,
-                                              _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None,
-                                              C.byref(opt), C.byref(stats)))
+        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
+            2, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=a, log_norm=log_norm, seed=seed,
+            stream=stream, const_hint=const_hint, chunk=chunk, lanes=lanes)
+        self._check(self.lib.vmx_ensemble_run(self._h, C.byref(spec), x.shape[0], *args, C.byref(stats)))
         return chain, chain_lnl, _stats_dict(stats)
 
     def ensemble_run_many(self, cols, lo, hi, theta_fixed, x, lnl, accepted, streams, step0, n_steps, mock_rows=None, thin=1, a=2.0,
@@ -1117,13 +1126,9 @@ class Engine:
         ensemble, ``mock_rows`` [E] the pool row every ensemble is compared with (None: the installed data); the rest as for
         :meth:`ensemble_run`.  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], statistics); the statistics carry
         ``per_ensemble`` int64 [E, 3]: accepted, rejected outside the box, rejected for a failed model."""
-        cols = np.ascontiguousarray(cols, dtype=np.int32)
-        lo, hi, theta_fixed = _f64(lo), _f64(hi), _f64(theta_fixed)
-        _in_place(np.float64, x=x, lnl=lnl)
-        _in_place(np.int64, accepted=accepted)
-        if x.ndim != 3 or x.shape[2] != cols.size or lnl.shape != x.shape[:2] or accepted.shape != x.shape[:2] \
-                or theta_fixed.shape != (self.n_params,):
-            raise ValueError('x [E, W, n], lnl [E, W], accepted [E, W], theta_fixed [n_params]')
+        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
+            3, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=a, log_norm=log_norm, seed=seed,
+            stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
         E, W = x.shape[:2]
         if streams is not None:
             streams = np.ascontiguousarray(streams, dtype=np.uint64)
@@ -1131,21 +1136,10 @@ class Engine:
             mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
         if (streams is not None and streams.shape != (E,)) or (mock_rows is not None and mock_rows.shape != (E,)):
             raise ValueError('streams [E], mock_rows [E]')
-        step0, n_steps, thin = int(step0), int(n_steps), int(thin)
-        rows = max(0, (step0 + n_steps) // thin - step0 // thin) if thin >= 1 else 0
-        chain = np.empty((E, rows, W, cols.size)) if keep_chain else None
-        chain_lnl = np.empty((E, rows, W)) if keep_chain else None
         per = np.zeros((E, 3), dtype=np.int64)
-        spec = EnsembleSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), float(a), float(log_norm), int(seed), 0,
-                            _dp(theta_fixed))
-        opt = EnsembleOptions(int(const_hint), int(chunk), int(lanes), 0)
-        stats = EnsembleStats()
-        i64 = C.POINTER(C.c_int64)
         self._check(self.lib.vmx_ensemble_run_many(
             self._h, C.byref(spec), E, W, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), _dp(x), _dp(lnl), accepted.ctypes.data_as(i64), step0, n_steps, thin,
-            _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None, C.byref(opt), C.byref(stats),
-            per.ctypes.data_as(i64)))
+            None if mock_rows is None else _ip(mock_rows), *args, C.byref(stats), per.ctypes.data_as(C.POINTER(C.c_int64))))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,

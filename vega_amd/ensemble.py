@@ -117,42 +117,13 @@ def half_step_proposals(x, h, step, a, seed, stream, lo, hi):
     return y, inside, log_factor(n, z), b
 
 
-def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate):
-    """``n_steps`` steps of the sampler in NumPy from the state ``x`` [W, n], ``lnl`` [W], ``accepted`` [W] (updated in place).
-    ``evaluate(rows, h)`` -> (chi2 [W/2], status [W/2]) for the half's rows [W/2, n] (a proposal outside the box is replaced
-    by the walker's own position, as the device driver hands it to the engine).  Returns (chain [rows, W, n], chain_lnl, stats)."""
-    W, n = x.shape
-    H = W // 2
-    rows = (step0 + n_steps) // thin - step0 // thin
-    chain, chain_lnl = np.empty((rows, W, n)), np.empty((rows, W))
-    st = dict(steps=n_steps, proposals=n_steps * W, accepted=0, rejected_outside_box=0, rejected_failed_model=0)
-    for s in range(step0, step0 + n_steps):
-        for h in (0, 1):
-            y, inside, factor, b = half_step_proposals(x, h, s, a, seed, stream, lo, hi)
-            mine = slice(h * H, (h + 1) * H)
-            chi2, status = evaluate(np.where(inside[:, None], y, x[mine]), h)
-            ok = model_ok(status, chi2)
-            lnl_new = log_lik(log_norm, chi2)
-            acc = accept(inside, ok, factor, lnl_new, lnl[mine], b[:, 2])
-            x[mine][acc] = y[acc]
-            lnl[mine][acc] = lnl_new[acc]
-            accepted[mine] += acc
-            st['accepted'] += int(acc.sum())
-            st['rejected_outside_box'] += int((~inside).sum())
-            st['rejected_failed_model'] += int((inside & ~ok).sum())
-        if (s + 1) % thin == 0:
-            r = (s + 1) // thin - step0 // thin - 1
-            chain[r], chain_lnl[r] = x, lnl
-    return chain, chain_lnl, st
-
-
 def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate):
     """``n_steps`` steps of E independent ensembles advanced together, in NumPy: the state ``x`` [E, W, n], ``lnl`` [E, W],
-    ``accepted`` [E, W] (updated in place), ensemble e on the Philox stream ``streams[e]``.  Every half-step makes the decisions of
-    :func:`python_steps` per ensemble; only the likelihood is joined: ``evaluate(rows, h)`` -> (chi2 [E W/2], status [E W/2]) for
-    the E W/2 rows [E W/2, n] of the half, ensemble e's at [e W/2, (e + 1) W/2) - the rows the device driver hands the engine.
-    Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats, per_ensemble [E, 3]: accepted, rejected outside the box,
-    rejected for a failed model)."""
+    ``accepted`` [E, W] (updated in place), ensemble e on the Philox stream ``streams[e]``.  Every half-step is decided ensemble by
+    ensemble; only the likelihood is joined: ``evaluate(rows, h)`` -> (chi2 [E W/2], status [E W/2]) for the E W/2 rows
+    [E W/2, n] of the half, ensemble e's at [e W/2, (e + 1) W/2) - the rows the device driver hands the engine (a proposal outside
+    the box is replaced by the walker's own position).  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats,
+    per_ensemble [E, 3]: accepted, rejected outside the box, rejected for a failed model)."""
     E, W, n = x.shape
     H = W // 2
     rows = (step0 + n_steps) // thin - step0 // thin
@@ -179,6 +150,15 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
               rejected_failed_model=int(per[:, 2].sum()))
     return chain, chain_lnl, st, per
+
+
+def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate):
+    """``n_steps`` steps of one ensemble in NumPy - :func:`python_steps_many` with E = 1 - from the state ``x`` [W, n], ``lnl`` [W],
+    ``accepted`` [W] (updated in place); ``evaluate(rows, h)`` -> (chi2 [W/2], status [W/2]) for the half's rows [W/2, n].
+    Returns (chain [rows, W, n], chain_lnl [rows, W], stats)."""
+    chain, chain_lnl, st, _ = python_steps_many(x[None], lnl[None], accepted[None], step0, n_steps, thin, a, seed, [stream], lo, hi,
+                                                log_norm, evaluate)
+    return chain[0], chain_lnl[0], st
 
 
 def write_getdist(path, name, names, chain, chain_lnl, weights=None, derived=None, derived_names=None, derived_labels=None):
@@ -480,7 +460,80 @@ class EngineSampler:
 
 
 # ------------------------------------------------------------------ the sampler
-class EnsembleSampler(EngineSampler):
+class StretchSampler(EngineSampler):
+    """What :class:`EnsembleSampler` and :class:`EnsembleSet` do alike: the settings of the stretch move, the statistics, the loop
+    over segments and the python driver's engine.  ``_lead`` is the shape in front of the walkers: () or (E,).  A class supplies
+    ``_prepare``, ``_segment_device`` and ``_python_steps``; a segment returns (chain, chain_lnl, stats) and, for a set, the
+    per-ensemble counters."""
+    _lead = ()
+
+    def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint):
+        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        self.W = int(walkers)
+        if self.W % 2 or self.W < 2 * self.n:
+            raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
+        self.a, self.seed = float(a), int(seed)
+        if not self.a > 1.0:
+            raise ValueError('a: the stretch scale must exceed 1')
+        self.thin = int(thin)
+        if self.thin < 1:
+            raise ValueError('thin >= 1')
+        self.segment = max(1, int(segment))
+
+    def reset(self):
+        self.x = self.lnl = None
+        self.accepted = np.zeros(self._lead + (self.W,), dtype=np.int64)
+        self.step = 0
+        self._chain, self._chain_lnl = [], []
+        self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
+                          seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
+
+    def run(self, n_steps, start='ball', init_scale=1.0):
+        """Advance by ``n_steps`` steps.  The first call draws the start, as the class's ``_start_positions`` says: ``'ball'``,
+        ``'prior'`` or an array; later calls continue the chain."""
+        theta = self._prepare(start, init_scale)
+        done = 0
+        while done < n_steps:
+            k = min(self.segment, n_steps - done)
+            segment = self._segment_device if self.driver == 'device' else self._segment_python
+            chain, chain_lnl, st, *per = segment(theta, k)
+            self._chain.append(chain)
+            self._chain_lnl.append(chain_lnl)
+            if per:             # (a set's segment: the counters of every ensemble)
+                self.per_ensemble += per[0]
+            for key in st:
+                if key in self.stats:
+                    self.stats[key] += st[key]
+            self.stats['calls'] += 1
+            self.step += k
+            done += k
+        return self
+
+    def _segment_python(self, theta, k):
+        """The readable restatement: proposals and decisions in NumPy (``_python_steps``), chi2 of a half's rows through
+        ``chi2_batch_device`` in the device driver's chunks, with its table level and lanes and, where given, every row's mock."""
+        import time
+        t0 = time.perf_counter()
+        with self._engine_rows() as rows:
+            def chi2(rows_x, mock_rows=None):
+                rows_t = np.repeat(theta[None, :], rows_x.shape[0], axis=0)
+                rows_t[:, self.cols] = rows_x
+                # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
+                return rows.chi2(rows_t, mock_rows=mock_rows), np.zeros(rows_x.shape[0], dtype=np.int32)
+
+            out = self._python_steps(k, chi2)
+        st = out[2]
+        st['engine_calls'] = rows.calls
+        st['host_synchronisations'] = rows.calls
+        st['seconds'] = time.perf_counter() - t0
+        return out
+
+    @property
+    def acceptance_fraction(self):
+        return self.accepted / max(self.step, 1)
+
+
+class EnsembleSampler(StretchSampler):
     """W walkers over the sampled parameters of ``vega`` (``sample_params['limits']``: the ``[sample]`` section, or the
     ``[monte carlo]`` one after ``initialize_monte_carlo``, as bin/run_vega_mpi.py picks them; ``sample_params`` overrides).
 
@@ -490,29 +543,15 @@ class EnsembleSampler(EngineSampler):
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
                  chunk=0, lanes=0, const_hint=-1):
-        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
-        self.W = int(walkers)
-        if self.W % 2 or self.W < 2 * self.n:
-            raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
-        self.a, self.seed, self.stream = float(a), int(seed), int(stream)
-        if not self.a > 1.0:
-            raise ValueError('a: the stretch scale must exceed 1')
-        self.thin = int(thin)
-        if self.thin < 1:
-            raise ValueError('thin >= 1')
-        self.segment = max(1, int(segment))
+        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint)
+        self.stream = int(stream)
         self.reset()
-
-    def reset(self):
-        self.x = self.lnl = None
-        self.accepted = np.zeros(self.W, dtype=np.int64)
-        self.step = 0
-        self._chain, self._chain_lnl = [], []
-        self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
-                          seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
 
     # ---- start
     def _start_positions(self, start, init_scale):
+        """The start of ``run``'s first call: ``'ball'`` - the configured values plus init_scale x errors x N(0, 1), redrawn until
+        inside the box - ``'prior'`` - uniform in the box - or an array [W, n]; both draws from ``np.random.default_rng(seed)``,
+        with a non-zero ``stream`` from ``default_rng([seed, stream])``."""
         # (stream 0 draws what it always drew; another stream - a replica - starts from walkers of its own)
         rng = np.random.default_rng(self.seed if self.stream == 0 else [self.seed, self.stream])
         if isinstance(start, str) and start == 'prior':
@@ -557,29 +596,6 @@ class EnsembleSampler(EngineSampler):
         return theta
 
     # ---- run
-    def run(self, n_steps, start='ball', init_scale=1.0):
-        """Advance the ensemble by ``n_steps`` steps (the first call draws the start: ``'ball'`` - the configured values plus
-        init_scale x errors x N(0, 1), redrawn until inside the box - ``'prior'`` - uniform in the box - or an array [W, n]; both
-        draws from ``np.random.default_rng(seed)``, with a non-zero ``stream`` from ``default_rng([seed, stream])``).  Later
-        calls continue the chain."""
-        theta = self._prepare(start, init_scale)
-        done = 0
-        while done < n_steps:
-            k = min(self.segment, n_steps - done)
-            if self.driver == 'device':
-                chain, chain_lnl, st = self._segment_device(theta, k)
-            else:
-                chain, chain_lnl, st = self._segment_python(theta, k)
-            self._chain.append(chain)
-            self._chain_lnl.append(chain_lnl)
-            for key in st:
-                if key in self.stats:
-                    self.stats[key] += st[key]
-            self.stats['calls'] += 1
-            self.step += k
-            done += k
-        return self
-
     def _segment_device(self, theta, k):
         self.vega._sync_monte_carlo()
         chain, chain_lnl, st = self.vega.engine.ensemble_run(
@@ -588,26 +604,9 @@ class EnsembleSampler(EngineSampler):
             lanes=self.lanes)
         return chain, chain_lnl, st
 
-    def _segment_python(self, theta, k):
-        """The readable restatement: proposals and decisions in NumPy, chi2 through ``chi2_batch_device`` in the device driver's
-        chunks, with its table level and lanes."""
-        import time
-        t0 = time.perf_counter()
-        H = self.W // 2
-        log_norm = self.log_norm()
-        with self._engine_rows() as rows:
-            def evaluate(rows_x, h):
-                rows_t = np.repeat(theta[None, :], H, axis=0)
-                rows_t[:, self.cols] = rows_x
-                # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
-                return rows.chi2(rows_t), np.zeros(H, dtype=np.int32)
-
-            chain, chain_lnl, st = python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed,
-                                                self.stream, self.lo, self.hi, log_norm, evaluate)
-        st['engine_calls'] = rows.calls
-        st['host_synchronisations'] = rows.calls
-        st['seconds'] = time.perf_counter() - t0
-        return chain, chain_lnl, st
+    def _python_steps(self, k, chi2):
+        return python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.stream, self.lo,
+                            self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x))
 
     # ---- results
     def _stack(self, parts, discard, thin, flat):
@@ -625,10 +624,6 @@ class EnsembleSampler(EngineSampler):
 
     def get_log_lik(self, discard=0, thin=1, flat=False):
         return self._stack(self._chain_lnl, discard, thin, flat)
-
-    @property
-    def acceptance_fraction(self):
-        return self.accepted / max(self.step, 1)
 
     def get_autocorr_time(self, discard=0, thin=1, c=5):
         """Integrated autocorrelation time per parameter in recorded rows (emcee's estimator: :func:`integrated_time`)."""
@@ -650,7 +645,7 @@ class EnsembleSampler(EngineSampler):
 
 
 # ------------------------------------------------------------------ many ensembles in one run
-class EnsembleSet(EngineSampler):
+class EnsembleSet(StretchSampler):
     """E independent ensembles of W walkers each over the sampled parameters of ``vega``, advanced together: the half-steps of all
     ensembles are decided at once and their E W/2 proposal rows go through the engine as one stream of chunks (``'device'``:
     vmx_ensemble_run_many, one work-group per ensemble; ``'python'``: :func:`python_steps_many` over ``chi2_batch_device``, cut
@@ -662,35 +657,22 @@ class EnsembleSet(EngineSampler):
 
     def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
                  sample_params=None, chunk=0, lanes=0, const_hint=-1):
-        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
-        self.E, self.W = int(ensembles), int(walkers)
+        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint)
+        self.E = int(ensembles)
         if self.E < 1:
             raise ValueError('ensembles: at least one')
-        if self.W % 2 or self.W < 2 * self.n:
-            raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
+        self._lead = (self.E,)
         self.streams = np.arange(self.E, dtype=np.uint64) if streams is None else np.array(streams, dtype=np.uint64)
         self.mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
         if self.streams.shape != (self.E,) or (self.mock_rows is not None and self.mock_rows.shape != (self.E,)):
             raise ValueError(f'streams, mock_rows: one entry for each of the {self.E} ensembles')
         if self.mock_rows is not None and np.any(self.mock_rows < 0):
             raise ValueError('mock_rows: rows of the installed mock pools, none negative')
-        self.a, self.seed = float(a), int(seed)
-        if not self.a > 1.0:
-            raise ValueError('a: the stretch scale must exceed 1')
-        self.thin = int(thin)
-        if self.thin < 1:
-            raise ValueError('thin >= 1')
-        self.segment = max(1, int(segment))
         self.reset()
 
     def reset(self):
-        self.x = self.lnl = None
-        self.accepted = np.zeros((self.E, self.W), dtype=np.int64)
+        super().reset()
         self.per_ensemble = np.zeros((self.E, 3), dtype=np.int64)
-        self.step = 0
-        self._chain, self._chain_lnl = [], []
-        self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
-                          seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
 
     # ---- start
     def _member_settings(self, e):
@@ -701,6 +683,8 @@ class EnsembleSet(EngineSampler):
                                stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint)
 
     def _start_positions(self, start, init_scale):
+        """The starts of ``run``'s first call: ``'ball'``, ``'prior'`` - ensemble e as ``EnsembleSampler(seed, stream=streams[e])``
+        draws them - or an array [E, W, n]."""
         if not isinstance(start, str):
             start = np.array(start, dtype=np.float64)
             if start.shape != (self.E, self.W, self.n):
@@ -741,26 +725,6 @@ class EnsembleSet(EngineSampler):
         return theta
 
     # ---- run
-    def run(self, n_steps, start='ball', init_scale=1.0):
-        """Advance every ensemble by ``n_steps`` steps (the first call draws the starts: ``'ball'``, ``'prior'`` - ensemble e as
-        ``EnsembleSampler(seed, stream=streams[e])`` draws them - or an array [E, W, n]).  Later calls continue the chains."""
-        theta = self._prepare(start, init_scale)
-        done = 0
-        while done < n_steps:
-            k = min(self.segment, n_steps - done)
-            segment = self._segment_device if self.driver == 'device' else self._segment_python
-            chain, chain_lnl, st, per = segment(theta, k)
-            self._chain.append(chain)
-            self._chain_lnl.append(chain_lnl)
-            self.per_ensemble += per
-            for key in st:
-                if key in self.stats:
-                    self.stats[key] += st[key]
-            self.stats['calls'] += 1
-            self.step += k
-            done += k
-        return self
-
     def _segment_device(self, theta, k):
         self.vega._sync_monte_carlo()
         chain, chain_lnl, st = self.vega.engine.ensemble_run_many(
@@ -769,26 +733,10 @@ class EnsembleSet(EngineSampler):
             const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes)
         return chain, chain_lnl, st, st.pop('per_ensemble')
 
-    def _segment_python(self, theta, k):
-        """The readable restatement: the decisions of :func:`python_steps` per ensemble, chi2 of the E W/2 rows of a half through
-        ``chi2_batch_device`` in the device driver's chunks, with its table level and lanes and every row's own mock."""
-        import time
-        t0 = time.perf_counter()
-        H = self.W // 2
-        row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, H)
-        with self._engine_rows() as rows:
-            def evaluate(rows_x, h):
-                rows_t = np.repeat(theta[None, :], self.E * H, axis=0)
-                rows_t[:, self.cols] = rows_x
-                # (chi2_batch_device reports a failed model by the 1e100 sentinel alone)
-                return rows.chi2(rows_t, mock_rows=row_mock), np.zeros(self.E * H, dtype=np.int32)
-
-            chain, chain_lnl, st, per = python_steps_many(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a,
-                                                          self.seed, self.streams, self.lo, self.hi, self.log_norm(), evaluate)
-        st['engine_calls'] = rows.calls
-        st['host_synchronisations'] = rows.calls
-        st['seconds'] = time.perf_counter() - t0
-        return chain, chain_lnl, st, per
+    def _python_steps(self, k, chi2):
+        row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, self.W // 2)
+        return python_steps_many(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.streams, self.lo,
+                                 self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x, row_mock))
 
     # ---- results
     def _stack(self, parts, tail, discard, thin, flat):
@@ -803,10 +751,6 @@ class EnsembleSet(EngineSampler):
 
     def get_log_lik(self, discard=0, thin=1, flat=False):
         return self._stack(self._chain_lnl, (), discard, thin, flat)
-
-    @property
-    def acceptance_fraction(self):
-        return self.accepted / max(self.step, 1)
 
     def get_autocorr_time(self, discard=0, thin=1, c=5):
         """Integrated autocorrelation time per ensemble and parameter in recorded rows, [E, n] (:func:`integrated_time`)."""
