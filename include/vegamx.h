@@ -12,7 +12,7 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run) and a tempered SMC sampler (vmx_smc_run), both
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
  * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
@@ -615,6 +615,48 @@ typedef struct {
 int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
                 int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
                 vmx_smc_stats* stats);
+/* E independent SMC runs advanced together: log Z and an equal-weight posterior for every Monte-Carlo mock, or the replicas of one
+ * run, as one device run.  A run of N = 256 - 512 particles hands the engine one batch per sweep and stops the host once per
+ * stage; here every kernel of the single run is launched with one work-group per run still going (k_smc_set_start,
+ * k_smc_set_start_lnl, k_smc_set_stage, k_smc_set_move: work-group a owns run active[a], the same device functions as the single
+ * run's kernels, nothing crosses runs), the A N rows of a sweep go through the engine as one stream of chunks of `chunk` on two
+ * lanes, and the host waits once per stage round for the whole set.  Run e is by construction the run vmx_smc_run makes with
+ * spec->stream = streams[e] on the data of mock_row[e]; its chi2 is evaluated in batches of another shape, so that its lnL may
+ * differ from the single run's in the last bits (E = 1 has the single run's batches and gives it bit for bit).
+ *   spec      as for the single run; spec->stream is not read
+ *   E         runs (>= 1) of spec->N particles each
+ *   streams   [E] the Philox stream of every run (repeats allowed: equal streams on equal data give equal runs)
+ *   mock_row  [E] the row of the items' mock pools run e is compared with, 0 <= row < n_mocks of every item's pool, repeats
+ *             allowed (the kernel that opens a round writes the row of every engine row); NULL: every run reads the installed data
+ *   u, lnl    [E][N][n], [E][N] host: the particles, read at entry (unless opt->draw) and written back at exit
+ *   stage, beta, scale   [E] each: the runs' own state, as the single run's - runs may enter at different stages and
+ *             temperatures, Philox counters use the run's own stage index; a run with beta >= 1 at entry is left alone.  A set
+ *             cut into calls is the same set.
+ *   status    [E] out: 0 the run is still going (n_stages used up), 1 it has reached beta = 1, 2 no particle has a finite lnL, 3
+ *             its ladder cannot advance (fewer than ess N particles carry weight).  A run with status 2 or 3 does not fail the
+ *             call: its u / lnl / stage / beta / scale are left as they were at entry and its stages_done is 0.
+ *   n_stages  at most so many stage rounds; a round advances every run still going by one stage; after each round the runs with
+ *             status != 0 leave the active list (which stays in ascending run order) and the others' rows move up to A N
+ *             contiguous engine rows
+ *   rec, rec_lnl, rec_anc   [E][n_stages][VMX_SMC_REC], [E][n_stages][N], [E][n_stages][N] host: the record of every run as the
+ *             single run writes it; stages_done[e] rows of run e are written
+ *   stages_done   [E] out: the stages run e was advanced by
+ *   opt       as for the single run; draw applies to every run (every stage[e] must then be 0)
+ *   stats     the totals over the runs (stages: the sum of stages_done); host_waits = stage rounds + 1 (the copy back) + 1 with
+ *             draw.  per_run [E][4] (NULL: not wanted): accepted moves, rows that were a particle's own position, moves rejected
+ *             for a failed model (all three 0 for a failed run), rows evaluated
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever the single run refuses, for every run; E < 1;
+ * streams NULL; a mock row that is negative or not below n_mocks; mock rows while an item has no pool; E N beyond the engine's
+ * int32 row count or a record beyond size_t.  A HIP failure later returns -2 and leaves the engine usable. */
+int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E,
+                     const uint64_t* streams, const int32_t* mock_row,
+                     double* u, double* lnl,
+                     int64_t* stage, double* beta, double* scale,
+                     int32_t* status,
+                     int32_t n_stages,
+                     double* rec, double* rec_lnl, int32_t* rec_anc,
+                     int32_t* stages_done,
+                     const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run);
 /* The table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns varies[n_params] != 0 allow - what
  * vmx_fit_migrad and vmx_ensemble_run derive when they are given const_hint = -1; a caller that evaluates such batches itself
  * sets it with vmx_set_constant_nl_hint. */

@@ -4,7 +4,7 @@ from .setup import Grid as Coordinates  # noqa: F401  (reference vega/coordinate
 from .errors import VegaModelError, VegaBoundsError, VegaArinyoError  # noqa: F401
 from .ensemble import EnsembleSampler, EnsembleSet, run_vega_sampler  # noqa: F401  (posterior sampling: bin/run_vega_mpi.py for one process)
 from .nested import NestedSampler  # noqa: F401  (evidence and a weighted posterior: sampler = Nested)
-from .smc import SMCRun, SMCSampler  # noqa: F401  (evidence and an equal-weight posterior by tempered SMC: sampler = SMC)
+from .smc import SMCRun, SMCSampler, SMCSet  # noqa: F401  (evidence and an equal-weight posterior by tempered SMC: sampler = SMC)
 from .replicas import gelman_rubin, merge_ensemble, merge_nested, merge_smc  # noqa: F401  (replicas = R: one process per GPU)
 
 

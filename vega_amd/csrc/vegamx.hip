@@ -697,7 +697,17 @@ struct SmcWorkspace {
     DevBuf<int32_t> inside, zero, rec_anc;
     DevBuf<int64_t> counters;
     double* pin = nullptr; double* dpin = nullptr;          // mapped host memory: beta, accepted, scale of the stage; the start's count
-    ~SmcWorkspace() { if (pin) (void)hipHostFree(pin); }
+    // a set of runs (vmx_smc_run_many): the words [E][4] and the active list (pinned), the list, streams, stages and mocks on the device
+    double* set_pin = nullptr; double* set_dpin = nullptr; int32_t* set_active = nullptr; size_t set_runs = 0;
+    DevBuf<int32_t> active, mock_row, mock;
+    DevBuf<uint64_t> streams;
+    DevBuf<int64_t> stage0;
+    ~SmcWorkspace()
+    {
+        if (pin) (void)hipHostFree(pin);
+        if (set_pin) (void)hipHostFree(set_pin);
+        if (set_active) (void)hipHostFree(set_active);
+    }
 };
 
 struct SmcDev {
@@ -729,7 +739,7 @@ __device__ inline void smc_write_rows(const SmcDev& D, bool proposals)
 }
 
 // the start particles: u from the Philox blocks (i, 0, j, 5), beta = 0, the start scale, and their rows for the engine
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcDev D)
+__device__ __forceinline__ void smc_start(const SmcDev& D)
 {
     for (int i = threadIdx.x; i < D.N; i += blockDim.x) vmx_smc::draw_start(i, D.n, D.seed, D.stream, D.u + (size_t)i * D.n);
     if (threadIdx.x == 0) { D.state[0] = 0.0; D.state[1] = vmx_smc::start_scale(D.n); }
@@ -737,7 +747,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcDev D)
     smc_write_rows(D, false);
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcDev D)
+__device__ __forceinline__ void smc_start_lnl(const SmcDev& D)
 {
     __shared__ int s_finite;
     if (threadIdx.x == 0) s_finite = 0;
@@ -789,7 +799,7 @@ __device__ inline void smc_sums(double dbeta, const double (&d)[SMC_PER], int J,
 // size (every sum in the fixed order of vmx_smc.h), the record, the cumulative weights, the ancestors, the gather, the particles'
 // mean and covariance (one lane per entry) and the factor (one lane: n <= 32).  beta_t goes to D.state[0]; NaN: no particle has a
 // finite lnL.
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcDev D, int64_t stage, int64_t rec)
+__device__ __forceinline__ void smc_stage(const SmcDev& D, int64_t stage, int64_t rec)
 {
     VMX_NO_CONTRACT
     __shared__ double s_a[SMC_THREADS], s_b[SMC_THREADS];
@@ -889,7 +899,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcDev D, int64_t sta
 // s_dec of the stage from chi2 / status of each particle's row (s_dec < 0: none), adapt the scale, then propose sweep s_prop
 // (s_prop < 0: none - the stage is over: its counts go to the record and beta, acceptance and scale to the host's words) and
 // write the N rows of the engine.  Every expression: vmx_smc.h.
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stage, int s_dec, int s_prop, int64_t rec)
+__device__ __forceinline__ void smc_move(const SmcDev& D, int64_t stage, int s_dec, int s_prop, int64_t rec)
 {
     __shared__ int s_cnt[3];
     __shared__ double s_C[vmx_smc::MAXN * vmx_smc::MAXN];
@@ -942,6 +952,81 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stag
     }
     __syncthreads();
     smc_write_rows(D, true);
+}
+
+// the single run (vmx_smc_run): one work-group
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcDev D) { smc_start(D); }
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcDev D) { smc_start_lnl(D); }
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcDev D, int64_t stage, int64_t rec) { smc_stage(D, stage, rec); }
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stage, int s_dec, int s_prop, int64_t rec)
+{
+    smc_move(D, stage, s_dec, s_prop, rec);
+}
+
+// A set of runs (vmx_smc_run_many): work-group a of a launch owns run active[a] - the functions above over that run's part of
+// every array - and the engine rows a N .. (a + 1) N - 1; nothing crosses runs.  `run0` is the view of run 0 on the rows of slot
+// 0.  Every active run is at record row `round` of the call and at stage stage0[run] + round of its own count.
+struct SmcSetDev {
+    SmcDev run0;
+    const int32_t* active;              // [A] the runs still going, ascending
+    const uint64_t* streams;            // [E] Philox streams
+    const int64_t* stage0;              // [E] the runs' stage at entry
+    const int32_t* mock_row;            // [E] the pool row of every run, or nullptr
+    int32_t* mock;                      // [E N] the mock row of every engine row (the kernels that open a round write it)
+    int32_t rec_rows;                   // record rows per run
+};
+
+__device__ __forceinline__ SmcDev smc_view(const SmcSetDev& S, int& run)
+{
+    SmcDev D = S.run0;
+    const size_t a = blockIdx.x, r = (size_t)S.active[a], N = (size_t)D.N, n = (size_t)D.n;
+    run = (int)r;
+    D.u += r * N * n; D.lnl += r * N; D.u2 += r * N * n; D.lnl2 += r * N; D.w += r * N; D.cum += r * N;
+    D.mean += r * n; D.cov += r * n * n; D.chol += r * n * n; D.state += r * 2;
+    D.prop += r * N * n; D.uacc += r * N; D.inside += r * N;
+    D.box.theta += a * N * (size_t)D.P; D.box.chi2 += a * N; D.box.status += a * N;
+    D.rec += r * (size_t)S.rec_rows * VMX_SMC_REC; D.rec_lnl += r * (size_t)S.rec_rows * N; D.rec_anc += r * (size_t)S.rec_rows * N;
+    D.counters += r * 3; D.host += r * 4;
+    D.stream = S.streams[r];
+    return D;
+}
+
+// the mock of the engine rows of this work-group's slot
+__device__ __forceinline__ void smc_write_mock(const SmcSetDev& S, int run)
+{
+    if (!S.mock_row) return;
+    const int N = S.run0.N, m = S.mock_row[run];
+    for (int i = threadIdx.x; i < N; i += SMC_THREADS) S.mock[(size_t)blockIdx.x * N + i] = m;
+}
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_start(SmcSetDev S)
+{
+    int run;
+    const SmcDev D = smc_view(S, run);
+    smc_write_mock(S, run);
+    smc_start(D);
+}
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_start_lnl(SmcSetDev S)
+{
+    int run;
+    const SmcDev D = smc_view(S, run);
+    smc_start_lnl(D);
+}
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage(SmcSetDev S, int64_t round)
+{
+    int run;
+    const SmcDev D = smc_view(S, run);
+    smc_stage(D, S.stage0[run] + round, round);
+}
+
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_move(SmcSetDev S, int64_t round, int s_dec, int s_prop)
+{
+    int run;
+    const SmcDev D = smc_view(S, run);
+    if (s_dec < 0) smc_write_mock(S, run);
+    smc_move(D, S.stage0[run] + round, s_dec, s_prop, round);
 }
 
 }  // namespace
@@ -4952,6 +5037,220 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
     *scale = scale_now;
     R.stages = done;
     R.sweeps = (int64_t)done * sweeps;
+    R.seconds_enqueuing = enqueue_s;
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// E independent runs advanced together (k_smc_set_*): one host round per stage for every run still going, the A N rows of a sweep
+// as one stream of chunks for the engine, every row with the mock of its run
+int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
+                     double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status, int32_t n_stages,
+                     double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_options* opt,
+                     vmx_smc_stats* stats, int64_t* per_run)
+{
+    const std::string name("vmx_smc_run_many");
+    REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale && status && stages_done, name);
+    REQUIRE(E >= 1, name + ": at least one run");
+    REQUIRE(streams, name + ": a Philox stream for every run");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box(name, e, spec, VMX_NS_MAXN, varies, inv)) return -1;
+    const int n = spec->n, P = e->n_params, N = spec->N, sweeps = spec->sweeps;
+    REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, name + ": max(2 n + 2, 8) .. 4096 particles");
+    REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, name + ": 0 < ess < 1");
+    REQUIRE(sweeps >= 1, name + ": sweeps >= 1");
+    REQUIRE(n_stages >= 0, name + ": n_stages >= 0");
+    REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), name + ": the stage record");
+    // sizes: the engine's rows are counted in int32, the largest array (the record, or the rows themselves) in size_t
+    REQUIRE((int64_t)E * N <= INT32_MAX, name + ": E N exceeds the engine's row count");
+    const size_t EN = (size_t)E * N, rec_rows = (size_t)std::max(n_stages, 1);
+    const size_t per_row = (size_t)std::max(std::max(n, P), VMX_SMC_REC) * sizeof(double);
+    REQUIRE(EN <= SIZE_MAX / per_row && EN * per_row <= SIZE_MAX / rec_rows, name + ": the record is too large");
+    const bool draw = opt && opt->draw != 0;
+    for (int q = 0; q < E; ++q) {
+        REQUIRE(stage[q] >= 0 && stage[q] < ((int64_t)1 << 31), name + ": 0 <= stage < 2^31");
+        REQUIRE(!draw || stage[q] == 0, name + ": particles are drawn at stage 0");
+        if (draw) continue;
+        REQUIRE(beta[q] >= 0.0 && beta[q] <= 1.0, name + ": beta in [0, 1]");
+        REQUIRE(scale[q] > 0.0 && std::isfinite(scale[q]), name + ": a positive scale");
+        bool any = false;
+        for (size_t i = (size_t)q * N; i < (size_t)(q + 1) * N; ++i) {
+            REQUIRE(!std::isnan(lnl[i]), name + ": a particle has a NaN lnL");
+            any = any || lnl[i] > -INFINITY;
+            for (int d = 0; d < n; ++d) {
+                const double v = u[i * n + d];
+                REQUIRE(v >= 0.0 && v <= 1.0, name + ": a particle lies outside the unit cube");
+            }
+        }
+        REQUIRE(any, name + ": no particle has a finite lnL");
+    }
+    if (mock_row)
+        for (int q = 0; q < E; ++q)
+            for (auto* it : e->items) {
+                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
+                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
+            }
+    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->smcws) e->smcws = new SmcWorkspace();
+    SmcWorkspace& S = *e->smcws;
+    if (ensure(S.u, EN * n) || ensure(S.lnl, EN) || ensure(S.u2, EN * n) || ensure(S.lnl2, EN) || ensure(S.w, EN) || ensure(S.cum, EN) ||
+        ensure(S.zero, N) || ensure(S.mean, (size_t)E * n) || ensure(S.cov, (size_t)E * n * n) || ensure(S.chol, (size_t)E * n * n) ||
+        ensure(S.state, (size_t)E * 2) || ensure(S.prop, EN * n) || ensure(S.uacc, EN) || ensure(S.inside, EN) ||
+        ensure(S.rec, E * rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * EN) || ensure(S.rec_anc, rec_rows * EN) ||
+        ensure(S.counters, (size_t)E * 3) || ensure(S.active, E) || ensure(S.streams, E) || ensure(S.stage0, E) ||
+        (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, EN))))
+        return -2;
+    if (S.set_runs < (size_t)E) {
+        if (S.set_pin) { (void)hipHostFree(S.set_pin); S.set_pin = nullptr; }
+        if (S.set_active) { (void)hipHostFree(S.set_active); S.set_active = nullptr; }
+        S.set_runs = 0;
+        HIP_OK(hipHostMalloc((void**)&S.set_pin, (size_t)E * 4 * sizeof(double), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.set_dpin, S.set_pin, 0));
+        HIP_OK(hipHostMalloc((void**)&S.set_active, (size_t)E * sizeof(int32_t), hipHostMallocDefault));
+        S.set_runs = (size_t)E;
+    }
+    hipStream_t st = e->stream;
+    std::vector<double> state0((size_t)E * 2);
+    for (int q = 0; q < E; ++q) { state0[2 * q] = beta[q]; state0[2 * q + 1] = scale[q]; }
+    if (!draw) {
+        HIP_OK(hipMemcpyAsync(S.u.p, u, EN * n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.lnl.p, lnl, EN * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.state.p, state0.data(), state0.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemcpyAsync(S.streams.p, streams, (size_t)E * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.stage0.p, stage, (size_t)E * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (mock_row) HIP_OK(hipMemcpyAsync(S.mock_row.p, mock_row, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(S.zero.p, 0, (size_t)N * sizeof(int32_t), st));
+    HIP_OK(hipMemsetAsync(S.counters.p, 0, (size_t)E * 3 * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.rec.p, 0, E * rec_rows * VMX_SMC_REC * sizeof(double), st));
+    SmcSetDev X{};
+    SmcDev& D = X.run0;
+    if (S.box.upload(EN, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
+    D.u = S.u.p; D.lnl = S.lnl.p; D.u2 = S.u2.p; D.lnl2 = S.lnl2.p; D.w = S.w.p; D.cum = S.cum.p; D.zero = S.zero.p;
+    D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.state = S.state.p;
+    D.prop = S.prop.p; D.uacc = S.uacc.p; D.inside = S.inside.p;
+    D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.set_dpin;
+    D.N = N; D.n = n; D.P = P; D.sweeps = sweeps; D.ess = spec->ess; D.log_norm = spec->log_norm;
+    D.seed = spec->seed; D.stream = 0;
+    X.active = S.active.p; X.streams = S.streams.p; X.stage0 = S.stage0.p;
+    X.mock_row = mock_row ? S.mock_row.p : nullptr; X.mock = mock_row ? S.mock.p : nullptr;
+    X.rec_rows = (int32_t)rec_rows;
+    const int32_t* d_mock = mock_row ? S.mock.p : nullptr;
+
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
+    vmx_smc_stats R{};
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
+    double enqueue_s = 0.0;
+    std::vector<int64_t> rows_of(E, 0), accepted_of(E, 0);
+    std::vector<int32_t> done(E, 0);
+    std::vector<double> b_now(beta, beta + E), scale_now(scale, scale + E);
+    int32_t* active = S.set_active;
+    int A = vmx_smc::first_active(beta, E, draw, active, status);
+    // the list goes up on the stream: the host changes it only after it has waited for the stream
+    auto put_active = [&]() -> int {
+        if (A > 0) HIP_OK(hipMemcpyAsync(S.active.p, active, (size_t)A * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        return 0;
+    };
+    // the A N rows a launch has just written
+    auto evaluate = [&]() -> int {
+        const int calls = L.evaluate(S.box.theta.p, A * N, S.box.chi2.p, S.box.status.p, d_mock, true);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
+        R.rows += (int64_t)A * N;
+        for (int a = 0; a < A; ++a) rows_of[active[a]] += N;
+        return 0;
+    };
+    if (put_active()) return -2;
+    if (draw) {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_smc_set_start, dim3(A), dim3(SMC_THREADS), 0, st, X);
+        HIP_OK(hipGetLastError());
+        if (evaluate()) return -2;
+        hipLaunchKernelGGL(k_smc_set_start_lnl, dim3(A), dim3(SMC_THREADS), 0, st, X);
+        HIP_OK(hipGetLastError());
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the start's wait: how many particles of every run have a finite lnL)
+        R.host_waits += 1;
+        for (int a = 0; a < A; ++a) {
+            const int q = active[a];
+            status[q] = vmx_smc::start_status(S.set_pin[(size_t)q * 4 + 3]);
+            b_now[q] = 0.0;
+            scale_now[q] = vmx_smc::start_scale(n);
+        }
+        const int B = vmx_smc::compact_active(active, A, status);
+        if (B != A) { A = B; if (put_active()) return -2; }
+    }
+    int round = 0;
+    while (round < n_stages && A > 0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_smc_set_stage, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round);
+        hipLaunchKernelGGL(k_smc_set_move, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, -1, 0);
+        HIP_OK(hipGetLastError());
+        for (int s = 0; s < sweeps; ++s) {
+            if (evaluate()) return -2;
+            hipLaunchKernelGGL(k_smc_set_move, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, s, s + 1 < sweeps ? s + 1 : -1);
+            HIP_OK(hipGetLastError());
+        }
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the round's only wait: beta, acceptance and scale of every run, mapped words)
+        R.host_waits += 1;
+        for (int a = 0; a < A; ++a) {
+            const int q = active[a];
+            const double* word = S.set_pin + (size_t)q * 4;
+            status[q] = vmx_smc::run_status(b_now[q], word[0]);
+            if (status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK) continue;
+            b_now[q] = word[0];
+            scale_now[q] = word[2];
+            accepted_of[q] += (int64_t)word[1];
+            done[q] += 1;
+        }
+        const int B = vmx_smc::compact_active(active, A, status);
+        round += 1;
+        if (B != A) { A = B; if (put_active()) return -2; }
+    }
+    // the runs that ended by themselves or are still going come back; a failed run's arrays stay as they were at entry
+    std::vector<double> rec_host(E * rec_rows * VMX_SMC_REC, 0.0);
+    for (int q = 0; q < E; ++q) {
+        if (status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK) { done[q] = 0; continue; }
+        const size_t o = (size_t)q * N;
+        HIP_OK(hipMemcpyAsync(u + o * n, S.u.p + o * n, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(lnl + o, S.lnl.p + o, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (done[q] == 0) continue;
+        const size_t r = (size_t)q * rec_rows, h = (size_t)q * n_stages;
+        HIP_OK(hipMemcpyAsync(rec_lnl + h * N, S.rec_lnl.p + r * N, (size_t)done[q] * N * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(rec_anc + h * N, S.rec_anc.p + r * N, (size_t)done[q] * N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipMemcpyAsync(rec_host.data(), S.rec.p, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    R.host_waits += 1;
+    for (int q = 0; q < E; ++q) {
+        int64_t own = 0, bad = 0;
+        for (int k = 0; k < done[q]; ++k) {
+            const double* r = rec_host.data() + ((size_t)q * rec_rows + k) * VMX_SMC_REC;
+            own += (int64_t)r[6];
+            bad += (int64_t)r[7];
+        }
+        if (done[q] > 0)
+            std::memcpy(rec + (size_t)q * n_stages * VMX_SMC_REC, rec_host.data() + (size_t)q * rec_rows * VMX_SMC_REC,
+                        (size_t)done[q] * VMX_SMC_REC * sizeof(double));
+        const bool failed = status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK;
+        if (failed) accepted_of[q] = 0;
+        else { stage[q] += done[q]; beta[q] = b_now[q]; scale[q] = scale_now[q]; }
+        stages_done[q] = done[q];
+        if (per_run) { per_run[4 * q] = accepted_of[q]; per_run[4 * q + 1] = own; per_run[4 * q + 2] = bad; per_run[4 * q + 3] = rows_of[q]; }
+        R.accepted += accepted_of[q];
+        R.rows_own_position += own;
+        R.rejected_failed_model += bad;
+        R.stages += done[q];
+    }
+    R.sweeps = R.stages * sweeps;
     R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;

@@ -39,6 +39,9 @@
 //   start            beta = 0, scale = 2.38 sqrt(3 / n); the scale carries over from stage to stage.  After the sweeps of the stage
 //                    with beta_t = 1 the particles are the posterior sample, weight 1 / N each.
 //
+//   a set of runs   vmx_smc_run_many advances E such runs a stage per host round, one work-group per run; the status of a run and
+//                    the list of the runs still going are decided at the end of this header (tests/helpers/smc_set_driver.cpp).
+//
 // Every expression is the separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are
 // correctly rounded.  The evidence is computed from the stage record by host Python (vega_amd/smc.py: evidence).
 #pragma once
@@ -302,6 +305,45 @@ VMX_HD inline double adapt(double scale, int64_t accepted, int N)
     if (a < 0.15) return scale * 0.8;
     if (a > 0.35) return scale * 1.25;
     return scale;
+}
+
+// ---- a set of runs (vmx_smc_run_many): E independent runs advanced a stage per host round; nothing below crosses runs
+// A run's status: RUNNING while beta < 1 (also the status of a run whose call ran out of stages), FINISHED at beta = 1, NO_FINITE
+// when no particle has a finite lnL (the stage head reports beta = NaN), STUCK when the ladder cannot advance (beta_t =
+// beta_{t-1}).  The last two end the run without ending the set.
+constexpr int RUNNING = 0, FINISHED = 1, NO_FINITE = 2, STUCK = 3;
+
+// after a stage round: beta_before the run's beta at the head of the stage, beta_after the word its kernels handed back
+VMX_HD inline int run_status(double beta_before, double beta_after)
+{
+    if (beta_after != beta_after) return NO_FINITE;
+    if (!(beta_after > beta_before)) return STUCK;
+    return beta_after >= 1.0 ? FINISHED : RUNNING;
+}
+
+// after the start: `finite` of the N drawn particles have a finite lnL
+VMX_HD inline int start_status(double finite) { return finite > 0.0 ? RUNNING : NO_FINITE; }
+
+// the runs a call begins with, in ascending order: every run with draw, the runs with beta < 1 otherwise.  Returns their number;
+// status[e] = FINISHED for the others.
+VMX_HD inline int first_active(const double* beta, int E, bool draw, int32_t* active, int32_t* status)
+{
+    int A = 0;
+    for (int e = 0; e < E; ++e) {
+        status[e] = draw || beta[e] < 1.0 ? RUNNING : FINISHED;
+        if (status[e] == RUNNING) active[A++] = e;
+    }
+    return A;
+}
+
+// drop the runs that are no longer RUNNING; the rest keep their (ascending) order and move up: run active[a] owns the engine rows
+// a N .. (a + 1) N - 1 of the next round.  Returns the new number.
+VMX_HD inline int compact_active(int32_t* active, int A, const int32_t* status)
+{
+    int B = 0;
+    for (int a = 0; a < A; ++a)
+        if (status[active[a]] == RUNNING) active[B++] = active[a];
+    return B;
 }
 
 }  // namespace vmx_smc

@@ -281,6 +281,9 @@ def load_library():
     lib.vmx_nested_cluster_points.argtypes = [C.c_int32, dptr, C.c_int32, C.c_int32, iptr, iptr, iptr, iptr, iptr, dptr, dptr]
     lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
                                 iptr, C.POINTER(SmcOptions), C.POINTER(SmcStats)]
+    lib.vmx_smc_run_many.argtypes = [C.c_void_p, C.POINTER(SmcSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
+                                     C.POINTER(C.c_int64), dptr, dptr, iptr, C.c_int32, dptr, dptr, iptr, iptr, C.POINTER(SmcOptions),
+                                     C.POINTER(SmcStats), C.POINTER(C.c_int64)]
     lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
     lib.vmx_set_constant_nl_hint.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_direct_pk.argtypes = [C.c_void_p, dptr, C.c_int32, C.c_int32]
@@ -349,7 +352,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_smc_run', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1217,6 +1220,46 @@ class Engine:
                        anc=rec_anc[k].copy(), accepted=int(rec[k, 3]), scale=float(rec[k, 4]), cholesky=bool(rec[k, 5]))
                   for k in range(int(stats.stages))]
         return record, int(st.value), float(b.value), float(sc.value), _stats_dict(stats)
+
+    def smc_run_many(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, streams, n_stages, ess, sweeps, mock_rows=None,
+                     log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw=False):
+        """Up to ``n_stages`` stage rounds of E independent SMC runs in one device run (include/vegamx.h: vmx_smc_run_many): ``u``
+        [E, N, n] / ``lnl`` [E, N] the particles, ``stage`` int64 [E] / ``beta`` [E] / ``scale`` [E] the runs' own state (all updated
+        in place; a failed run's part is left as it was), ``streams`` [E] the Philox stream of every run, ``mock_rows`` [E] the pool
+        row every run is compared with (None: the installed data); the rest as for :meth:`smc_run`.  Returns (records: for every
+        run the list of stage dicts of the stages done, status int32 [E], stages_done int32 [E], statistics); the statistics
+        carry ``per_run`` int64 [E, 4]: accepted, rows that were a particle's own position, rejected for a failed model, rows
+        evaluated."""
+        _in_place(np.float64, u=u, lnl=lnl, beta=beta, scale=scale)
+        _in_place(np.int64, stage=stage)
+        if u.ndim != 3 or lnl.shape != u.shape[:2]:
+            raise ValueError('u [E, N, n], lnl [E, N]')
+        E, N = u.shape[:2]
+        cols, lo, hi, theta_fixed, _ = self._sampled_box(cols, lo, hi, theta_fixed, u=u.reshape(-1, u.shape[-1]), lnl=lnl.reshape(-1))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if stage.shape != (E,) or beta.shape != (E,) or scale.shape != (E,) or (streams is not None and streams.shape != (E,)) or \
+                (mock_rows is not None and mock_rows.shape != (E,)):
+            raise ValueError('stage [E], beta [E], scale [E], streams [E], mock_rows [E]')
+        n_stages = max(0, int(n_stages))
+        rec, rec_lnl = np.zeros((E, n_stages, VMX_SMC_REC)), np.empty((E, n_stages, N))
+        rec_anc = np.empty((E, n_stages, N), dtype=np.int32)
+        status, done, per = np.zeros(E, dtype=np.int32), np.zeros(E, dtype=np.int32), np.zeros((E, 4), dtype=np.int64)
+        spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
+                       0, _dp(theta_fixed))
+        opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
+        stats = SmcStats()
+        self._check(self.lib.vmx_smc_run_many(
+            self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), _dp(u), _dp(lnl), stage.ctypes.data_as(C.POINTER(C.c_int64)), _dp(beta),
+            _dp(scale), _ip(status), n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), _ip(done), C.byref(opt), C.byref(stats),
+            per.ctypes.data_as(C.POINTER(C.c_int64))))
+        records = [[dict(beta_prev=float(rec[e, k, 0]), beta=float(rec[e, k, 1]), ess=float(rec[e, k, 2]), lnl=rec_lnl[e, k].copy(),
+                         anc=rec_anc[e, k].copy(), accepted=int(rec[e, k, 3]), scale=float(rec[e, k, 4]),
+                         cholesky=bool(rec[e, k, 5])) for k in range(int(done[e]))] for e in range(E)]
+        return records, status, done, dict(_stats_dict(stats), per_run=per)
 
     def derived_const_hint(self, cols):
         """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:

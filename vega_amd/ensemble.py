@@ -866,21 +866,22 @@ def sampler_settings(main_config, sample_params):
     return out
 
 
-def _parse_mocks(sec, main_config):
-    """``mocks = M`` of ``[Ensemble]``: a posterior for each of M Monte-Carlo mocks in one run; it needs the Monte-Carlo mode."""
+def _parse_mocks(sec, main_config, section='Ensemble', own='an ensemble'):
+    """``mocks = M`` of ``[Ensemble]`` (or ``[SMC]``): a posterior for each of M Monte-Carlo mocks in one run; it needs the
+    Monte-Carlo mode."""
     try:
         M = sec.getint('mocks')
     except ValueError:
-        raise ValueError('[Ensemble] mocks: a whole number, at least 1') from None
+        raise ValueError(f'[{section}] mocks: a whole number, at least 1') from None
     if M < 1:
-        raise ValueError('[Ensemble] mocks: a whole number, at least 1')
+        raise ValueError(f'[{section}] mocks: a whole number, at least 1')
     control = main_config['control']
     if not control.getboolean('run_montecarlo', False):
-        raise ValueError('[Ensemble] mocks needs "run_montecarlo = True" in the "[control]" section')
+        raise ValueError(f'[{section}] mocks needs "run_montecarlo = True" in the "[control]" section')
     if 'monte carlo' not in main_config:
-        raise ValueError('[Ensemble] mocks needs a "[monte carlo]" section')
+        raise ValueError(f'[{section}] mocks needs a "[monte carlo]" section')
     if 'replicas' in sec and sec.getint('replicas') > 1:
-        raise ValueError('[Ensemble] mocks and replicas > 1 do not combine: every mock has an ensemble of its own')
+        raise ValueError(f'[{section}] mocks and replicas > 1 do not combine: every mock has {own} of its own')
     return M
 
 
@@ -974,7 +975,9 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, rank=None, w
 def _sample_config_mocks(vega, cfg, sample_params, control):
     """``[Ensemble] mocks = M``: M mocks around the Monte-Carlo fiducial with ``[control] mc_seed``, their posteriors as one
     :class:`EnsembleSet` (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`); writes the getdist chains ``<name>_mock<m>.txt``
-    with one ``<name>.paramnames`` and the summary table ``mock_posteriors.fits``.  Returns the set."""
+    with one ``<name>.paramnames`` and the summary table ``mock_posteriors.fits``.  ``[SMC] mocks = M``: the same mocks as one
+    :class:`vega_amd.smc.SMCSet`; every mock's three files ``<name>_mock<m>.txt`` / ``.paramnames`` / ``.stats`` (the evidence)
+    and the table.  Returns the set."""
     mc = vega.analysis
     scale = None
     if vega._use_global_cov and 'global_cov_rescale' in control:
@@ -983,6 +986,13 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
                             forecast=control.getboolean('forecast', False))
     if 'global' in mc.mc_mocks:
         mocks = mc.mc_mocks['global']
+    if cfg['sampler'] == 'SMC':
+        sampler = mc.sample_mocks(mocks=mocks, seed=cfg['seed'], scale=scale, sample_params=sample_params, driver=cfg['driver'],
+                                  sampler='smc', particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'])
+        for m in range(sampler.E):
+            sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')
+        mc.write_mock_posteriors(cfg['path'])
+        return sampler
     sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],
                               scale=scale, sample_params=sample_params, driver=cfg['driver'])
     chain, lnl = sampler.get_chain(), sampler.get_log_lik()

@@ -469,7 +469,8 @@ class MonteCarlo:
         return res
 
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
-                     sample_params=None, driver='device', keep_chains=True, fiducial_model=None):
+                     sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
+                     ess=0.5, sweeps=None):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -481,8 +482,17 @@ class MonteCarlo:
         Keeps ``mc_posteriors``: names, per mock ``mean`` / ``sd`` [M, n] and ``covariance`` [M, n, n] of the rows after ``burn``,
         ``tau`` [M, n] (integrated autocorrelation times in recorded rows), ``acceptance`` [M], ``n_eff`` [M] (rows after burn x
         walkers / the largest tau) and the run's settings; with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
-        ``mc_chain_lnl``.  Returns the set."""
+        ``mc_chain_lnl``.  Returns the set.
+
+        ``sampler='smc'``: the evidence and an equal-weight posterior of every mock instead, M tempered SMC runs advanced together
+        (:class:`vega_amd.smc.SMCSet`: run m on mock m and stream m, ``particles`` - default 1024 - ``ess`` and ``sweeps`` its
+        settings; ``walkers`` / ``steps`` / ``burn`` / ``thin`` are not read: every run ends by itself at beta = 1).  It keeps in
+        ``mc_posteriors``: names, ``mean`` / ``sd`` / ``covariance`` of the N samples, ``log_z``, ``log_z_err`` (NaN for a run that
+        failed), ``stages``, ``status`` (:class:`SMCSet`), ``acceptance`` and the settings; ``mc_chains`` holds the samples
+        [M, N, n] and ``mc_chain_lnl`` their lnL."""
         from .ensemble import EnsembleSet, SampledBox
+        if sampler not in ('ensemble', 'smc'):
+            raise ValueError("sample_mocks: sampler 'ensemble' or 'smc'")
         vega = self.vega
         prob = vega.problem
         if sample_params is None:
@@ -505,26 +515,49 @@ class MonteCarlo:
         if num_mocks is not None and int(num_mocks) != M:
             raise ValueError(f'sample_mocks: num_mocks = {num_mocks}, but {M} mocks were passed')
         n = SampledBox(vega, sample_params).n
-        walkers = max(32, 2 * n) if walkers is None else int(walkers)
-        steps, thin = int(steps), int(thin)
-        burn = steps // 3 if burn is None else int(burn)
-        if not 0 <= burn < steps:
-            raise ValueError('sample_mocks: 0 <= burn < steps')
+        smc = sampler == 'smc'
+        if not smc:
+            walkers = max(32, 2 * n) if walkers is None else int(walkers)
+            steps, thin = int(steps), int(thin)
+            burn = steps // 3 if burn is None else int(burn)
+            if not 0 <= burn < steps:
+                raise ValueError('sample_mocks: 0 <= burn < steps')
         eng = vega.engine
         scales = item_scales(prob, scale)
         rescaled = [name for name in mocks if scales[name] != 1. and prob.items[name].cov is not None and not vega._use_global_cov]
-        sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
-                              sample_params=sample_params)
+        if smc:
+            from .smc import SMCSet
+            sampler = SMCSet(vega, M, particles=1024 if particles is None else int(particles), mock_rows=np.arange(M), ess=ess,
+                             sweeps=sweeps, seed=seed, driver=driver, sample_params=sample_params)
+        else:
+            sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
+                                  sample_params=sample_params)
         try:
             for name, pool in mocks.items():
                 eng.set_mock_pool(name, pool)
             for name in rescaled:
                 # (marginalize-in-fit: chi2_matrix keeps the projector of the unscaled covariance, as in _fit_mocks)
                 eng.set_invcov(name, prob.items[name].chi2_matrix / scales[name])
-            sampler.run(steps)
+            if smc:
+                sampler.run()
+            else:
+                sampler.run(steps)
         finally:
             for name in rescaled:
                 eng.set_invcov(name, prob.items[name].chi2_matrix)
+        if smc:
+            pts, lnl, _ = sampler.samples()
+            log_z, err = sampler.log_evidence()
+            moved = np.maximum(sampler.stats['per_run'][:, 3] - sampler.particles, 1)       # (the rows of the sweeps)
+            self.mc_posteriors = dict(
+                sampler='smc', names=list(sampler.names), mean=pts.mean(axis=1), sd=pts.std(axis=1, ddof=1),
+                covariance=np.array([np.atleast_2d(np.cov(rows.T)) for rows in pts]), log_z=log_z, log_z_err=err,
+                stages=sampler.stage.copy(), status=sampler.status.copy(), acceptance=sampler.stats['per_run'][:, 0] / moved,
+                particles=sampler.particles, ess=sampler.ess, sweeps=sampler.sweeps, seed=int(seed), driver=sampler.driver,
+                stats=dict(sampler.stats))
+            self.mc_chains = pts if keep_chains else None
+            self.mc_chain_lnl = lnl if keep_chains else None
+            return sampler
         first = burn // thin
         post = sampler.get_chain(discard=first)
         flat = post.reshape(M, -1, n)
@@ -541,7 +574,10 @@ class MonteCarlo:
     def write_mock_posteriors(self, directory, cpu_id=None, overwrite=True):
         """`mock_posteriors[_<cpu_id>].fits` under ``directory``: one table ``POSTERIORS`` with one row per mock of
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
-        ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  Returns the path."""
+        ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  After
+        ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
+        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED``.  Returns the
+        path."""
         from pathlib import Path
         from . import fitslite
         post = getattr(self, 'mc_posteriors', None)
@@ -550,11 +586,19 @@ class MonteCarlo:
         names, n = post['names'], len(post['names'])
         M = post['mean'].shape[0]
         cols = []
-        for j, nm in enumerate(names):
-            cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]
-        cols += [('acceptance', 'D', post['acceptance']), ('n_eff', 'D', post['n_eff']),
-                 ('covariance', f'{n * n}D' if n > 1 else 'D', post['covariance'].reshape(M, n * n) if n > 1 else post['covariance'].reshape(M))]
-        header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
+        cov_col = ('covariance', f'{n * n}D' if n > 1 else 'D', post['covariance'].reshape(M, n * n) if n > 1 else post['covariance'].reshape(M))
+        if post.get('sampler') == 'smc':
+            for j, nm in enumerate(names):
+                cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j])]
+            cols += [('log_z', 'D', post['log_z']), ('log_z_err', 'D', post['log_z_err']),
+                     ('stages', 'K', np.asarray(post['stages'], dtype=np.int64)), ('status', 'K', np.asarray(post['status'], dtype=np.int64)),
+                     cov_col]
+            header = {'SAMPLER': 'SMC', 'PARTICLE': post['particles'], 'ESS': post['ess'], 'SWEEPS': post['sweeps'], 'SEED': post['seed']}
+        else:
+            for j, nm in enumerate(names):
+                cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]
+            cols += [('acceptance', 'D', post['acceptance']), ('n_eff', 'D', post['n_eff']), cov_col]
+            header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)
         path = directory / ('mock_posteriors.fits' if cpu_id is None else f'mock_posteriors_{cpu_id}.fits')

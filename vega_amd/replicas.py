@@ -487,6 +487,18 @@ def run_replicas(vega, cfg, sample_params, group, print_func=print):
                              driver=cfg['driver'], sample_params=sample_params)
         both.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
         ready = [both.member(k) for k in range(hi - lo)]
+    if cfg.get('together', False) and cfg['sampler'] == 'SMC' and hi > lo:
+        # the rank's replicas as one set: one host round per stage for all of them, their rows one stream of full batches
+        from .smc import SMCSet
+        both = SMCSet(vega, hi - lo, particles=cfg['particles'], streams=range(lo, hi), ess=cfg['ess'], sweeps=cfg['sweeps'],
+                      seed=cfg['seed'], driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params)
+        both.run()
+        for k in range(hi - lo):        # (a single run that cannot go on raises: so does the set)
+            if both.status[k] in (2, 3):
+                raise ValueError(f'SMC: replica {lo + k} cannot go on (status {int(both.status[k])}): '
+                                 + ('no particle has a finite log-likelihood' if both.status[k] == 2 else
+                                    'the temperature ladder cannot advance: fewer than ess N particles carry weight'))
+        ready = [both.member(k) for k in range(hi - lo)]
     for r in range(lo, hi):
         if ready:
             sampler = ready[r - lo]

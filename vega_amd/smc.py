@@ -293,6 +293,115 @@ def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, strea
     return record, stage, beta, scale, st
 
 
+# ------------------------------------------------------------------ a set of runs (vmx_smc.h: "a set of runs")
+RUNNING, FINISHED, NO_FINITE, STUCK = 0, 1, 2, 3
+
+
+def run_status(beta_before, beta_after):
+    """vmx_smc::run_status: what a stage round made of a run."""
+    if math.isnan(beta_after):
+        return NO_FINITE
+    if not beta_after > beta_before:
+        return STUCK
+    return FINISHED if beta_after >= 1.0 else RUNNING
+
+
+def first_active(beta, draw):
+    """vmx_smc::first_active: (the runs a call begins with, ascending; the status of every run)."""
+    status = np.where(draw | (np.asarray(beta) < 1.0), RUNNING, FINISHED).astype(np.int32)
+    return [int(e) for e in np.flatnonzero(status == RUNNING)], status
+
+
+def compact_active(active, status):
+    """vmx_smc::compact_active: the runs still going keep their order and move up."""
+    return [e for e in active if status[e] == RUNNING]
+
+
+def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, streams, evaluate, draw=False):
+    """Up to ``n_stages`` stage rounds of E runs in NumPy (vmx_smc_run_many restated): ``u`` [E, N, n], ``lnl`` [E, N], ``stage``
+    int64 [E], ``beta`` [E], ``scale`` [E] the runs' state, updated in place (a failed run's part is left as it was at entry),
+    ``streams`` [E].  A round advances every run still going by one stage (:func:`stage_head`, then ``sweeps`` times
+    :func:`propose` / :func:`accept` / :func:`adapt`, run by run); ``evaluate(rows_u [A N, n], runs [A])`` -> lnL [A N] takes the
+    rows of the A runs still going (ascending, run ``runs[a]`` owns rows a N .. (a + 1) N - 1) at once.  ``draw``: the particles are
+    drawn and evaluated first.  Returns (records: per run the list of stage dicts as :func:`python_stages` makes them, status
+    int32 [E]: 0 still going, 1 at beta = 1, 2 no particle with a finite lnL, 3 the ladder cannot advance; stages_done int32 [E];
+    statistics with ``per_run`` int64 [E, 4]: accepted, own-position rows, failed models, rows evaluated, and ``rounds``)."""
+    E, N, n = u.shape
+    entry = (u.copy(), lnl.copy(), stage.copy(), beta.copy(), scale.copy())
+    records = [[] for _ in range(E)]
+    per = np.zeros((E, 4), dtype=np.int64)
+    active, status = first_active(beta, bool(draw))
+    rounds = 0
+
+    def rows_of(parts):
+        per[active, 3] += N
+        return np.asarray(evaluate(np.concatenate(parts, axis=0), np.array(active, dtype=np.int64)), dtype=np.float64).reshape(len(active), N)
+
+    if draw and active:
+        for e in active:
+            u[e] = draw_start(N, n, seed, int(streams[e]))
+            beta[e], scale[e] = 0.0, start_scale(n)
+        first = rows_of([u[e] for e in active])
+        for a, e in enumerate(active):
+            lnl[e] = first[a]
+            status[e] = RUNNING if np.any(first[a] > -np.inf) else NO_FINITE
+        active = compact_active(active, status)
+    while rounds < n_stages and active:
+        heads = {}
+        for e in active:
+            head = stage_head(u[e], lnl[e], float(beta[e]), ess, int(stage[e]), seed, int(streams[e]))
+            heads[e] = head
+            if math.isnan(head['beta']):
+                continue
+            records[e].append(dict(beta_prev=float(beta[e]), beta=head['beta'], ess=head['ess'], lnl=lnl[e].copy(), anc=head['anc'],
+                                   cholesky=head['cholesky'], accepted=0, scale=float(scale[e])))
+            u[e], lnl[e] = head['u'], head['lnl']
+        own, bad = np.zeros(E, dtype=np.int64), np.zeros(E, dtype=np.int64)
+        for s in range(sweeps):
+            prop = {}
+            for e in active:            # (a run without a finite lnL sends its rows as they are: the device does the same)
+                if math.isnan(heads[e]['beta']):
+                    prop[e] = None
+                else:
+                    prop[e] = propose(u[e], heads[e]['C'], float(scale[e]), int(stage[e]), s, seed, int(streams[e]))
+            new = rows_of([u[e] if prop[e] is None else np.where(prop[e][1][:, None], prop[e][0], u[e]) for e in active])
+            for a, e in enumerate(active):
+                if prop[e] is None:
+                    continue
+                y, inside, ua = prop[e]
+                ok = new[a] > -np.inf
+                acc = accept(inside, ok, heads[e]['beta'], new[a], lnl[e], ua)
+                u[e][acc] = y[acc]
+                lnl[e][acc] = new[a][acc]
+                k = int(acc.sum())
+                scale[e] = adapt(float(scale[e]), k, N)
+                records[e][-1]['accepted'] += k
+                own[e] += int((~inside).sum())
+                bad[e] += int((inside & ~ok).sum())
+        for e in active:
+            status[e] = run_status(float(beta[e]), heads[e]['beta'])
+            if status[e] in (NO_FINITE, STUCK):
+                continue
+            records[e][-1]['scale'] = float(scale[e])
+            beta[e] = heads[e]['beta']
+            stage[e] += 1
+            per[e, 0] += records[e][-1]['accepted']
+            per[e, 1] += own[e]
+            per[e, 2] += bad[e]
+        active = compact_active(active, status)
+        rounds += 1
+    done = np.zeros(E, dtype=np.int32)
+    for e in range(E):
+        if status[e] in (NO_FINITE, STUCK):
+            u[e], lnl[e], stage[e], beta[e], scale[e] = (arr[e] for arr in entry)
+            records[e] = []
+            per[e, :3] = 0
+        done[e] = len(records[e])
+    st = dict(stages=int(done.sum()), sweeps=int(done.sum()) * sweeps, rows=int(per[:, 3].sum()), rows_own_position=int(per[:, 1].sum()),
+              accepted=int(per[:, 0].sum()), rejected_failed_model=int(per[:, 2].sum()), rounds=rounds, per_run=per)
+    return records, status, done, st
+
+
 # ------------------------------------------------------------------ evidence (host, both drivers)
 def evidence(record, N):
     """(log Z, err) from the stage record: ``log Z = sum_t [log mean_i w_i(beta_t) + (beta_t - beta_{t-1}) max lnL]`` with
@@ -466,10 +575,195 @@ class SMCSampler(E.EngineSampler, SMCRun):
         return write_run(self, path, name, self.names, **self._write_extra(derived, print_func, self.derived))
 
 
+class SMCSet(E.EngineSampler):
+    """E independent tempered SMC runs of N particles each over the sampled parameters of ``vega``, advanced together: one host
+    round per stage for every run still going, the A N rows of a sweep through the engine as one stream of chunks (``'device'``:
+    vmx_smc_run_many, one work-group per run; ``'python'``: :func:`python_stages_many` over ``chi2_batch_device``, cut into the
+    same chunks).  Run e is on the Philox stream ``streams[e]`` (default ``range(E)``) and is the run
+    ``SMCSampler(..., seed=seed, stream=streams[e])`` makes - up to the last bits of lnL where the engine's batches are shaped
+    differently.  ``mock_rows`` [E]: the row of the installed mock pools every run is compared with - log Z
+    and a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`); None: every run reads the data
+    the interface has installed - replicas of one run.  Every run ends on its own: at beta = 1 (``status`` 1), or because no
+    particle has a finite lnL (2) or its ladder cannot advance (3); the last two do not stop the others.  An engine group takes
+    ``'python'``."""
+
+    def __init__(self, vega, runs, particles=1024, streams=None, mock_rows=None, ess=0.5, sweeps=None, seed=0, driver='device',
+                 chunk=0, lanes=0, const_hint=-1, max_stages=None, sample_params=None):
+        self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        probe = SMCRun(None, self.n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, max_stages=max_stages)   # (its checks)
+        self.particles, self.ess, self.sweeps, self.seed, self.max_stages = probe.particles, probe.ess, probe.sweeps, probe.seed, probe.max_stages
+        self.E = int(runs)
+        if self.E < 1:
+            raise ValueError('runs: at least one')
+        self.streams = np.arange(self.E, dtype=np.uint64) if streams is None else np.array(streams, dtype=np.uint64)
+        self.mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
+        if self.streams.shape != (self.E,) or (self.mock_rows is not None and self.mock_rows.shape != (self.E,)):
+            raise ValueError(f'streams, mock_rows: one entry for each of the {self.E} runs')
+        if self.mock_rows is not None and np.any(self.mock_rows < 0):
+            raise ValueError('mock_rows: rows of the installed mock pools, none negative')
+        self.reset()
+
+    def reset(self):
+        self.u = self.lnl = None
+        self.stage = np.zeros(self.E, dtype=np.int64)
+        self.beta = np.zeros(self.E)
+        self.scale = np.full(self.E, start_scale(self.n))
+        self.status = np.zeros(self.E, dtype=np.int32)
+        self.record = [[] for _ in range(self.E)]
+        self.stats = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0, engine_calls=0,
+                          host_waits=0, seconds=0.0, seconds_enqueuing=0.0, calls=0, rounds=0,
+                          per_run=np.zeros((self.E, 4), dtype=np.int64))
+
+    @property
+    def finished(self):
+        """[E]: the run has reached beta = 1."""
+        return self.beta >= 1.0
+
+    # ---- drivers
+    def _advance(self, n_stages):
+        """Up to ``n_stages`` rounds of the runs still going, as a set of their own (the engine's rows are those of the runs still
+        going either way); returns the statistics."""
+        vega, N, n = self.vega, self.particles, self.n
+        self._begin_advance(lambda: draw_start(1, n, self.seed, int(self.streams[0]))[0], 'smc_run_many')
+        draw = self.u is None
+        if draw:
+            self.u, self.lnl = np.zeros((self.E, N, n)), np.zeros((self.E, N))
+        idx = np.flatnonzero(self.status == RUNNING)
+        u, lnl = np.ascontiguousarray(self.u[idx]), np.ascontiguousarray(self.lnl[idx])
+        stage, beta, scale = self.stage[idx].copy(), self.beta[idx].copy(), self.scale[idx].copy()
+        streams = self.streams[idx]
+        mocks = None if self.mock_rows is None else self.mock_rows[idx]
+        records, total = [[] for _ in idx], None
+        status = np.zeros(idx.size, dtype=np.int32)
+
+        def add(st):
+            nonlocal total
+            if total is None:
+                total = dict(st, per_run=st['per_run'].copy())
+                return
+            for key, val in st.items():
+                if key not in ('const_hint', 'lanes'):
+                    total[key] = total[key] + val
+
+        if self.driver == 'python':
+            log_norm = self.log_norm()
+
+            def evaluate(rows_u, runs):
+                rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
+                rows_t[:, self.cols] = self.to_physical(rows_u)
+                return NS.lnl_of(0, self._rows.chi2(rows_t, None if mocks is None else np.repeat(mocks[runs], N)), log_norm)
+
+            with self._engine_rows() as self._rows:
+                try:
+                    records, status, _, st = python_stages_many(u, lnl, stage, beta, scale, n_stages, self.ess, self.sweeps, self.seed,
+                                                                streams, evaluate, draw=draw)
+                finally:
+                    calls, self._rows = self._rows.calls, None
+            add(dict(st, engine_calls=calls, host_waits=calls))
+        else:
+            vega._sync_monte_carlo()
+            while True:
+                k = min(n_stages, _PER_CALL)
+                sub = np.flatnonzero(status == RUNNING)         # (a long run is cut into calls of _PER_CALL rounds)
+                if sub.size == 0 or (k == 0 and not draw):
+                    break
+                su, sl, ss, sb, sc = (np.ascontiguousarray(arr[sub]) for arr in (u, lnl, stage, beta, scale))
+                rec, stat, _, st = vega.engine.smc_run_many(
+                    self.cols, self.lo, self.hi, self._theta, su, sl, ss, sb, sc, streams[sub], k, self.ess, self.sweeps,
+                    mock_rows=None if mocks is None else mocks[sub], log_norm=self.log_norm(), seed=self.seed,
+                    const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw=draw)
+                u[sub], lnl[sub], stage[sub], beta[sub], scale[sub], status[sub] = su, sl, ss, sb, sc, stat
+                for a, e in enumerate(sub):
+                    records[e].extend(rec[a])
+                per = np.zeros((idx.size, 4), dtype=np.int64)
+                per[sub] = st['per_run']
+                add(dict(st, per_run=per, rounds=st['host_waits'] - 1 - (1 if draw else 0)))
+                draw = False
+                n_stages -= k
+        self.u[idx], self.lnl[idx], self.stage[idx], self.beta[idx], self.scale[idx], self.status[idx] = u, lnl, stage, beta, scale, status
+        for a, e in enumerate(idx):
+            self.record[e].extend(records[a])
+        if total is not None:
+            per = np.zeros((self.E, 4), dtype=np.int64)
+            per[idx] = total['per_run']
+            total['per_run'] = per
+        return total or {}
+
+    def run(self, stages=None):
+        """Every run to its end (``stages`` None; ``max_stages`` bounds the runs), or at most ``stages`` more rounds (0 on a new
+        set: the start particles alone); the set does not depend on how it is cut."""
+        t0 = time.perf_counter()
+        at = int(self.stage.max())
+        if stages is None:
+            call = 1 << 20 if self.max_stages is None else max(0, self.max_stages - at)
+        else:
+            call = int(stages)
+            if self.max_stages is not None:
+                call = min(call, max(0, self.max_stages - at))
+        going = (self.status == RUNNING) & (True if self.u is None else ~self.finished)
+        if (call > 0 or self.u is None) and np.any(going):        # (a first call of no stages draws and evaluates the start)
+            st = self._advance(max(call, 0))
+            for key, val in st.items():
+                if key in ('lanes', 'const_hint'):      # (what the engine ran with)
+                    self.stats[key] = val
+                elif key in self.stats and key != 'seconds':
+                    self.stats[key] = self.stats[key] + val
+            self.stats['calls'] += 1
+        self.stats['seconds'] += time.perf_counter() - t0
+        return self
+
+    # ---- results
+    def _ran(self):
+        if self.u is None:
+            raise ValueError('nothing has run yet')
+
+    def log_evidence(self):
+        """(log Z [E], its delta-method error [E]: :func:`evidence` of every run's record); NaN for a failed run."""
+        self._ran()
+        out = np.full((2, self.E), np.nan)
+        for e in range(self.E):
+            if self.status[e] not in (NO_FINITE, STUCK):
+                out[:, e] = evidence(self.record[e], self.particles)
+        return out[0], out[1]
+
+    def samples(self):
+        """(points [E, N, n], lnL [E, N], weights [E, N] = 1 / N): the particles of every run - its posterior sample once finished
+        (a failed run's are what it started from)."""
+        self._ran()
+        return self.to_physical(self.u.copy()), self.lnl.copy(), np.full((self.E, self.particles), 1.0 / self.particles)
+
+    def member(self, e):
+        """Run ``e`` as a sampler that has run: :class:`SMCSampler`'s result methods (``log_evidence``, ``samples``, ``stages``,
+        ``derived``, ``write``) over copies of its part of the set's state.  Read-only: it cannot be advanced."""
+        if not 0 <= int(e) < self.E:
+            raise IndexError(f'member: 0 .. {self.E - 1}')
+        e = int(e)
+        m = SMCSampler(self.vega, particles=self.particles, ess=self.ess, sweeps=self.sweeps, seed=self.seed, driver=self.driver_asked,
+                       chunk=self.chunk, sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))), values=self.values,
+                                                            errors=self.errors),
+                       stream=int(self.streams[e]), lanes=self.lanes, const_hint=self.const_hint, max_stages=self.max_stages)
+        m.driver = self.driver
+        m.run = m.reset = _read_only
+        if self.u is not None:
+            m.u, m.lnl = self.u[e].copy(), self.lnl[e].copy()
+        m.stage, m.beta, m.scale = int(self.stage[e]), float(self.beta[e]), float(self.scale[e])
+        m.record = list(self.record[e])
+        took, own, bad, rows = (int(v) for v in self.stats['per_run'][e])
+        m.stats = dict({k: v for k, v in self.stats.items() if k not in ('per_run', 'rounds')}, stages=len(m.record),
+                       sweeps=len(m.record) * self.sweeps, rows=rows, rows_own_position=own, accepted=took, rejected_failed_model=bad)
+        m.status = int(self.status[e])
+        return m
+
+
+def _read_only(*args, **kwargs):
+    raise RuntimeError('a member of an SMCSet is read-only: advance the set')
+
+
 def smc_settings(main_config, sample_params):
     """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
     has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them; ``sweeps``
-    None: 4 n."""
+    None: 4 n.  ``mocks = M``: log Z and a posterior for each of M Monte-Carlo mocks in one run (the conditions of ``[Ensemble]
+    mocks``); ``together = True`` with ``replicas``: a rank's replicas advance as one :class:`SMCSet`."""
     sec, limits, out = E.section_settings(main_config, sample_params, 'SMC', name='smc')
     n = len(limits)
     out.update(particles=sec.getint('particles', 1024), ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None),
@@ -484,6 +778,13 @@ def smc_settings(main_config, sample_params):
         raise ValueError('[SMC] sweeps must be positive')
     if out['max_stages'] is not None and out['max_stages'] < 1:
         raise ValueError('[SMC] max_stages must be positive')
+    if 'mocks' in sec:
+        out['mocks'] = E._parse_mocks(sec, main_config, 'SMC', 'an SMC run')
+    if 'together' in sec:
+        try:
+            out['together'] = sec.getboolean('together')
+        except ValueError:
+            raise ValueError('[SMC] together: True or False') from None
     return out
 
 
