@@ -706,7 +706,12 @@ int vmx_marg_layout(vmx_engine* e, int32_t item, int32_t* offset, int32_t* count
  * <= 1e-13 of the largest k^3 P_ell over the whole parameter box of vmx_set_mu_rule_box (tests/test_mu_quadrature.py: the
  * reference's prior limits and wider, corners included); larger wavenumbers, and the model options
  * that are not smooth in mu (exponential smoothing, Voigt / sinc HCD, McDonald), keep the plain loop.  node_rule = 0:
- * the 1000-point loop everywhere (VMX_EXACT_MU in the environment does the same).  Returns the setting in effect. */
+ * the 1000-point loop everywhere (VMX_EXACT_MU in the environment does the same).  Returns the setting in effect.
+ * Tiers: in the level-2 kernel (vmx_set_constant_nl_hint) a k tile whose largest wavenumber is at most 0.0058 / 0.11 h/Mpc
+ * takes a 42- / 82-node rule of the same generator (4 + 4 midpoints and one 16-point panel / 16 + 16 and one 32-point panel,
+ * the same stencils): there k^3 P_ell is orders of magnitude below its largest value, and each tier adds <= 1e-14 of that
+ * (vega_amd/mu_quadrature.py: TIERS, tests/test_mu_tiers.py).  The choice depends on the tile alone.  VMX_NO_MU_TIERS in the
+ * environment (read by vmx_set_template) keeps the main rule on every tile. */
 int vmx_set_mu_quadrature(vmx_engine* e, int32_t node_rule);
 /* Applicability guard of that rule (before vmx_finalize).  The rule is validated on a parameter box - the prior limits
  * of the reference's vega/parameters/default_values.txt for every parameter that shapes P(k,mu) other than polynomially,
@@ -774,7 +779,7 @@ void* vmx_stream(vmx_engine* e);
  * 2 = spline coefficients; 3 = metal correlation after its metal matrix [B][pad32(n_model)] (index = metal, in the
  * global order of vmx_item_add_metal).
  * 4 = {live wavenumbers of the P(k,mu) stage in the last evaluation, k up to which the mu node rule applies (0: off),
- * nodes per wavenumber of that rule, leading wavenumbers whose tiles took the rule in the last evaluation, table level of
+ * nodes per wavenumber of that rule (the mean over the wavenumbers on it, where k tiles took shorter tiers), leading wavenumbers whose tiles took the rule in the last evaluation, table level of
  * the last evaluation (vmx_set_constant_nl_hint), first and last spline-coefficient row the last evaluation's bins read,
  * walkers that left the mu rule's box since vmx_finalize, form of the last evaluation (vmx_set_quadratic_form_kind)}.
  * Returns the number of doubles written (<= capacity) or a negative error. */

@@ -1058,6 +1058,10 @@ struct vmx_engine {
 
     int nk = 0, nkp = 0, n_mu = 0;
     int n_rows = 0, n_extra = 0, mu_lo = 0, mu_hi = 0;     // node rule of the mu sums (vmx_set_mu_quadrature)
+    int mu_tiers = 1;                                      // VMX_NO_MU_TIERS: 1 - the main rule for every k tile of k_pk_tab2
+    vmx_plan::MuTierDesc mu_tier[vmx_plan::MU_TIERS] = {};
+    std::vector<uint16_t> zmap64, zmap16;                  // launch order and tiers of k_pk_tab2's k tiles (vmx_plan::plan_mu_tiles)
+    int last_tab2_kt = 0;                                  // tile width of the last k_pk_tab2 launch (0: none)
     DevBuf<double> node_w, mu_img, mu_img_w;
     std::vector<int32_t> rule_slot; std::vector<double> rule_lo, rule_hi;     // vmx_set_mu_rule_box
     DevBuf<int32_t> d_rule_slot; DevBuf<double> d_rule_lo, d_rule_hi;
@@ -1651,68 +1655,17 @@ int vmx_set_template(vmx_engine* e, int32_t nk, const double* k, const double* p
         // (round 3: 48 + 48 kept midpoints, two 32-point panels and ONE nine-point one-sided stencil per end that carries the
         // first, third and fifth derivative terms of the Euler-Maclaurin formula at once - 178 nodes, 7e-14 of the largest
         // k^3 M_n over the guard's whole parameter box; round 2's 96 + 96 + 84 with five-point stencils reached 1e-13)
-        const int lo = 48, hi = 48, panels = 2, ngl = 32, npts = 9;
-        const double h = 1.0 / n_mu, a = lo * h, b = (n_mu - hi) * h, eps = 1e-3;
-        std::vector<double> gx(ngl), gw(ngl);
-        for (int i = 0; i < ngl; ++i) {            // Gauss-Legendre nodes by Newton's iteration on P_ngl
-            double x = std::cos(M_PI * (i + 0.75) / (ngl + 0.5)), dp = 1.0;
-            for (int it = 0; it < 100; ++it) {
-                double p0 = 1.0, p1 = x;
-                for (int n = 2; n <= ngl; ++n) { const double p2 = ((2 * n - 1) * x * p1 - (n - 1) * p0) / n; p0 = p1; p1 = p2; }
-                dp = ngl * (x * p1 - p0) / (x * x - 1.0);
-                const double dx = p1 / dp;
-                x -= dx;
-                if (std::fabs(dx) < 1e-16) break;
-            }
-            gx[i] = x; gw[i] = 2.0 / ((1.0 - x * x) * dp * dp);
-        }
-        for (int pnl = 0; pnl < panels; ++pnl) {
-            const double pa = a + (b - a) * pnl / panels, pb = a + (b - a) * (pnl + 1) / panels;
-            for (int i = 0; i < ngl; ++i) { node_mu.push_back(0.5 * (pb - pa) * gx[i] + 0.5 * (pa + pb)); node_w.push_back(0.5 * (pb - pa) * gw[i] / h); }
-        }
-        // Finite-difference weights of the derivatives 0 .. 5 at x = 0 on the points 0, 1, .. npts - 1 (Fornberg's recursion):
-        // D^k f(x) ~ sum_i c[i][k] f(x + i e) / e^k
-        constexpr int MD = 5;
-        std::vector<std::vector<double>> c(npts, std::vector<double>(MD + 1, 0.0));
-        {
-            double c1 = 1.0, c4 = 0.0;
-            c[0][0] = 1.0;
-            for (int i = 1; i < npts; ++i) {
-                const int mn = std::min(i, MD);
-                double c2 = 1.0;
-                const double c5 = c4;
-                c4 = (double)i;
-                for (int j = 0; j < i; ++j) {
-                    const double c3 = (double)(i - j);
-                    c2 *= c3;
-                    if (j == i - 1) {
-                        for (int k = mn; k >= 1; --k) c[i][k] = c1 * (k * c[i - 1][k - 1] - c5 * c[i - 1][k]) / c2;
-                        c[i][0] = -c1 * c5 * c[i - 1][0] / c2;
-                    }
-                    for (int k = mn; k >= 1; --k) c[j][k] = (c4 * c[j][k] - k * c[j][k - 1]) / c3;
-                    c[j][0] = c4 * c[j][0] / c3;
-                }
-                c1 = c2;
-            }
-        }
-        // midpoint sum = (1/h) int - (h/24) [Df] + (7 h^3/5760) [D^3 f] - (31 h^5/967680) [D^5 f],  [g] = g(b) - g(a);
-        // backward stencil at b: D^k f(b) ~ -sum_i c[i][k] f(b - i e) / e^k for odd k
-        const double coef[3] = {-h / 24.0, 7.0 * h * h * h / 5760.0, -31.0 * h * h * h * h * h / 967680.0};
-        const int order[3] = {1, 3, 5};
-        for (int i = 0; i < npts; ++i) {
-            double wb = 0.0, wa = 0.0;
-            for (int q = 0; q < 3; ++q) {
-                const double scaled = c[i][order[q]] / std::pow(eps, order[q]);
-                wb += coef[q] * (-scaled);
-                wa += -coef[q] * scaled;
-            }
-            node_mu.push_back(b - i * eps); node_w.push_back(wb);
-            node_mu.push_back(a + i * eps); node_w.push_back(wa);
-        }
-        e->mu_lo = lo; e->mu_hi = hi;
+        // The generator and the tiers are vmx_plan.h's (mu_rule_extra, build_mu_tiers - run on the CPU by tests/test_mu_tiers.py).
+        // Behind the main rule's 82 extra nodes lie those of up to two shorter rules for the k tiles of k_pk_tab2 whose
+        // k^3 M_n carries no weight (+50: 16 + 16 kept midpoints, one 32-point panel; +34: 4 + 4 and one 16-point panel); the
+        // numbers and their validation: vega_amd/mu_quadrature.py TIERS, tests/test_mu_tiers.py.
+        e->mu_tiers = getenv("VMX_NO_MU_TIERS") ? 1 : vmx_plan::MU_TIERS;
+        vmx_plan::build_mu_tiers(n_mu, e->mu_tiers, node_mu, node_w, e->mu_tier);
+        e->mu_lo = e->mu_tier[0].lo; e->mu_hi = e->mu_tier[0].hi;
+        e->n_extra = e->mu_tier[0].x_cnt;
     }
-    e->n_extra = (int)node_mu.size();
-    e->n_rows = n_mu + e->n_extra;
+    // (n_extra: the main rule's nodes - what every kernel but k_pk_tab2 loops over; the tables hold all tiers' rows)
+    e->n_rows = n_mu + (int)node_mu.size();
     if (e->node_w.upload(node_w.data(), node_w.size())) return -2;
     const int n_rows = e->n_rows;
     std::vector<double> mu(n_rows), sq(n_rows), lnm(n_rows), wl(4 * (size_t)n_mu);
@@ -1732,14 +1685,21 @@ int vmx_set_template(vmx_engine* e, int32_t nk, const double* k, const double* p
     e->h_mu = mu;
     {
         // the LDS image of k_pk_tab2's node tables: {mu^2, mu^4} of the midpoints, {mu, mu^2, mu^4, w} of the extra nodes
-        std::vector<double> img(2 * (size_t)n_mu + 4 * (size_t)e->n_extra);
+        // (one image per tier, each of the main rule's size: a block copies the midpoints and its tier's nodes in one run)
+        const size_t img_size = 2 * (size_t)n_mu + 4 * (size_t)e->n_extra;
+        std::vector<double> img(img_size), img_t(img_size * vmx_plan::MU_TIERS, 0.0);
         for (int j = 0; j < n_mu; ++j) { const double m2 = mu[j] * mu[j]; img[2 * (size_t)j] = m2; img[2 * (size_t)j + 1] = m2 * m2; }
-        for (int j = 0; j < e->n_extra; ++j) {
-            const double m = mu[n_mu + j], m2 = m * m;
-            double* q = &img[2 * (size_t)n_mu + 4 * (size_t)j];
-            q[0] = m; q[1] = m2; q[2] = m2 * m2; q[3] = node_w[j];
+        for (int t = 0; t < vmx_plan::MU_TIERS; ++t) {
+            double* dst = &img_t[img_size * t];
+            std::copy(img.begin(), img.begin() + 2 * (size_t)n_mu, dst);
+            for (int j = 0; j < e->mu_tier[t].x_cnt; ++j) {
+                const int r = e->mu_tier[t].x_off + j;
+                const double m = mu[n_mu + r], m2 = m * m;
+                double* q = dst + 2 * (size_t)n_mu + 4 * (size_t)j;
+                q[0] = m; q[1] = m2; q[2] = m2 * m2; q[3] = node_w[r];
+            }
         }
-        if (e->mu_img.upload(img.data(), img.size())) return -2;
+        if (e->mu_img.upload(img_t.data(), img_t.size())) return -2;
         // ... and of k_pk_w's: the same midpoints, {mu^2, mu^4, mu^6, w} of the extra nodes
         for (int j = 0; j < e->n_extra; ++j) {
             const double m = mu[n_mu + j], m2 = m * m;
@@ -2668,6 +2628,10 @@ int vmx_finalize(vmx_engine* e, int32_t n_params, int32_t max_batch)
         e->k_node_max = 24.0 / size;
         if (getenv("VMX_EXACT_MU") || e->n_extra == 0) e->mu_nodes_on = false;
         D.k_node_max = e->mu_nodes_on ? e->k_node_max : 0.0;
+        // which k tile of k_pk_tab2 takes which tier, and the launch order of the tiles (vmx_plan.h)
+        for (int t = 0; t < vmx_plan::MU_TIERS; ++t) D.mu_tier[t] = e->mu_tier[t];
+        e->zmap64 = vmx_plan::plan_mu_tiles(e->h_k.data(), e->nk, 64, e->k_node_max, e->mu_tiers, VMX_TAB2_ZMAP);
+        e->zmap16 = vmx_plan::plan_mu_tiles(e->h_k.data(), e->nk, 16, e->k_node_max, e->mu_tiers, VMX_TAB2_ZMAP);
     }
     for (int sl : e->rule_slot) REQUIRE(sl < n_params, "mu-rule box slot exceeds n_params");
     if (!e->rule_slot.empty() && (e->d_rule_slot.upload(e->rule_slot.data(), e->rule_slot.size()) ||
@@ -3221,7 +3185,12 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
                 Tab2Args A{};
                 const int n = (int)std::min<size_t>(VMX_TAB2_GROUPS, e->tab2_groups.size() - first);
                 for (int q = 0; q < n; ++q) A.g[q] = e->tab2_groups[first + q];
-                if ((int64_t)B * e->n_xtab >= 24) {
+                const bool wide = (int64_t)B * e->n_xtab >= 24;
+                const std::vector<uint16_t>& zmap = wide ? e->zmap64 : e->zmap16;
+                A.n_z = (int32_t)zmap.size();           // (0: plain order, main rule)
+                std::copy(zmap.begin(), zmap.end(), A.zmap);
+                e->last_tab2_kt = wide ? 64 : 16;
+                if (wide) {
                     if (B >= 64)
                         hipLaunchKernelGGL((k_pk_tab2<64, 4, 2>), dim3((B + 1) / 2, n, (e->nk + 63) / 64), dim3(256), std::max(sh1, (size_t)4096 * sizeof(double)), e->stream, D, A, B);
                     else
@@ -5663,7 +5632,11 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (capacity < 3) { fail(-1, "invalid argument: capacity too small"); return -1; }
         int32_t live[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpy(live, e->k_live.p, 8 * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { fail(-2, "hipMemcpy"); return -2; }
-        out[0] = live[0]; out[1] = e->dev.k_node_max; out[2] = e->mu_lo + e->mu_hi + e->n_extra;
+        // (k_pk_tab2's tiles take the tier of their largest wavenumber: the mean over the wavenumbers on the rule)
+        const int kt = e->last_tab_level >= 2 ? e->last_tab2_kt : 0;
+        const bool tiered = kt > 0 && !(kt == 64 ? e->zmap64 : e->zmap16).empty();
+        out[0] = live[0]; out[1] = e->dev.k_node_max;
+        out[2] = vmx_plan::mu_mean_nodes(e->h_k.data(), e->nk, kt, live[1], tiered ? e->mu_tiers : 1, e->mu_tier);
         if (capacity >= 4) out[3] = live[1];
         if (capacity >= 5) out[4] = e->last_tab_level;
         if (capacity >= 7) { out[5] = live[2]; out[6] = live[3]; }

@@ -161,7 +161,8 @@ struct EngineDev {
     const double* pklin;        // [3][nkp]
     const double* delta2;       // [nkp]
     const double* mu;           // [n_mu]
-    const double* mu_img;       // [n_mu] {mu^2, mu^4}, [n_extra] {mu, mu^2, mu^4, w}: the LDS image of k_pk_tab2's node tables
+    const double* mu_img;       // [tiers] { [n_mu] {mu^2, mu^4}, [n_extra] {mu, mu^2, mu^4, w} }: the LDS images of k_pk_tab2's node tables
+    vmx_plan::MuTierDesc mu_tier[vmx_plan::MU_TIERS];      // k_pk_tab2's tiers of the node rule ([0]: the main rule; n_extra: its nodes)
     const double* mu_img_w;     // ... of k_pk_w's: [n_mu] {mu^2, mu^4}, [n_extra] {mu^2, mu^4, mu^6, w}
     const double* sq1mmu2;      // [n_mu] sqrt(1 - mu^2)
     const double* lnmu;         // [n_mu] ln(mu)
@@ -1427,7 +1428,11 @@ __global__ __launch_bounds__(256, GENERIC ? 1 : VMX_PK_WAVES) void k_pk_multipol
 struct Tab2Group { int32_t pipe, partner, xtab, cross, kind_s, kind_q, col_s, col_q, uvb, heii, lya1, lya2, damping_power, pad;
                    double damping_scale; };
 #define VMX_TAB2_GROUPS 8
-struct Tab2Args { Tab2Group g[VMX_TAB2_GROUPS]; };
+// zmap: the k tile (low 12 bits) and its tier of the node rule that grid index z takes - the longest blocks start first
+// (vmx_plan::plan_mu_tiles); n_z = 0: tile z, main rule
+#define VMX_TAB2_ZMAP 256
+struct Tab2Args { Tab2Group g[VMX_TAB2_GROUPS]; int32_t n_z, pad; uint16_t zmap[VMX_TAB2_ZMAP]; };
+static_assert(sizeof(EngineDev) + sizeof(Tab2Args) + 16 <= 4096, "kernel arguments of k_pk_tab2");
 
 // MODE: whose choice the mu rule is.  0: every walker of the block agrees (the common case: this instantiation is the
 // kernel's hot path) - the rule when all lie in its box, the reference's loop when none does.  A block whose walkers DISAGREE
@@ -1439,7 +1444,7 @@ struct Tab2Args { Tab2Group g[VMX_TAB2_GROUPS]; };
 #define VMX_TAB2_PF 4
 #endif
 template <int KT, int MS, int NW, bool CROSS, int MODE = 0>
-__device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group& G, int B)
+__device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group& G, int tile, int tr, int B)
 {
     extern __shared__ double smem[];
     constexpr int NT = KT * MS;
@@ -1449,7 +1454,8 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
     v4d* s_node = (v4d*)(smem + 2 * D.n_mu);
     const int p = G.pipe, pp = G.partner, xt = G.xtab;
     constexpr bool cross = CROSS;
-    const int tile = blockIdx.z;
+    // the tile's tier of the node rule: block-uniform, a function of the tile alone (never of the walkers)
+    const vmx_plan::MuTierDesc tier = D.mu_tier[tr];
     const unsigned long long t_start = D.pk_trace ? wall_clock64() : 0ull;
     const int kk = threadIdx.x % KT;
     const int ms = (KT == 64) ? __builtin_amdgcn_readfirstlane(threadIdx.x / KT) : (int)(threadIdx.x / KT);
@@ -1465,8 +1471,9 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
     // [n_mu] {mu^2, mu^4}, [n_extra] {mu, mu^2, mu^4, w} - the LDS layout below), the tile's and the walkers' values into
     // registers; then the block decides.
     {
-        const unsigned total = (2u * (unsigned)n_mu + 4u * (unsigned)D.n_extra) * 8u;           // bytes, a multiple of 16
-        const char* img = (const char*)D.mu_img;
+        // (the tier's image: the midpoints and its own extra nodes - a short tier copies less)
+        const unsigned total = (2u * (unsigned)n_mu + 4u * (unsigned)tier.x_cnt) * 8u;          // bytes, a multiple of 16
+        const char* img = (const char*)(D.mu_img + (size_t)tr * (2 * (size_t)n_mu + 4 * (size_t)D.n_extra));
         const unsigned wave_off = (threadIdx.x >> 6) * 1024u, lane_off = (threadIdx.x & 63) * 16u;
         for (unsigned c = 0; c < total; c += (unsigned)NT * 16u) {
             const unsigned off = c + wave_off;                  // (a wave's 64 x 16 bytes land contiguously at its LDS base)
@@ -1557,11 +1564,11 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
     if (MODE == 1) in_box = true;
     if (MODE == 2) in_box = false;
     if (threadIdx.x == 0) atomicMax(D.k_live, min((tile + 1) * KT, D.nk));
-    // the node rule (first mu_lo and last mu_hi midpoints plus the extra nodes) serves a tile whose wavenumbers are all
+    // the node rule (the tier's first lo and last hi midpoints plus its extra nodes) serves a tile whose wavenumbers are all
     // within its range or negligible (VMX_PK_NEGLIGIBLE) - and whose walkers lie in the box the rule is validated on
     const bool node_mode = D.n_extra > 0 && in_box && rule_ok;
     if (node_mode && threadIdx.x == 0) atomicMax(D.k_live + 1, min((tile + 1) * KT, D.nk));
-    const int lo_end = node_mode ? D.mu_lo : n_mu, hi_beg = node_mode ? n_mu - D.mu_hi : n_mu;
+    const int lo_end = node_mode ? tier.lo : n_mu, hi_beg = node_mode ? n_mu - tier.hi : n_mu;
     if (G.uvb || G.heii) {
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
@@ -1640,12 +1647,13 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
         if (node_mode) {
             // the extra nodes (rows n_mu + jj): not equally spaced, so the HCD factor is exponentiated directly; the table
             // entries run four nodes ahead as above
-            const double* tab = base + (size_t)n_mu * row;
+            // (rows n_mu + x_off + jj of the tables, entry jj of the tier's LDS image)
+            const double* tab = base + (size_t)(n_mu + tier.x_off) * row;
             double gw[VMX_TAB2_PF], hw[VMX_TAB2_PF];
 #pragma unroll
             for (int u = 0; u < VMX_TAB2_PF; ++u) { gw[u] = tab[u * stride]; hw[u] = tab[plane + u * stride]; }
             tab += VMX_TAB2_PF * stride;
-            const int steps = D.n_extra > ms ? (D.n_extra - ms + MS - 1) / MS : 0;
+            const int steps = tier.x_cnt > ms ? (tier.x_cnt - ms + MS - 1) / MS : 0;
 #define VMX_TAB2_XSTEP(GREG, HREG, JJ)                                                                                \
             {                                                                                                         \
                 const v4d nd = s_node[JJ];                                                                            \
@@ -1687,7 +1695,7 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
         }
     __syncthreads();
     if (D.pk_trace && threadIdx.x == 0) {
-        unsigned long long* tr = D.pk_trace + 4 * ((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+        unsigned long long* tr = D.pk_trace + 4 * ((size_t)(tile * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
         tr[0] = t_start; tr[1] = wall_clock64();
 #ifdef VMX_EXP_PK_PHASE
         tr[2] = t_setup; tr[3] = t_loop;
@@ -1721,11 +1729,11 @@ __device__ __forceinline__ void pk_tab2_body(const EngineDev& D, const Tab2Group
 // the two passes of a block whose walkers disagree on the rule (inlined: as a function of its own it would bring a stack,
 // i.e. scratch memory, to every launch of the kernel)
 template <int KT, int MS, int NW>
-__device__ __forceinline__ void pk_tab2_mixed(const EngineDev& D, const Tab2Group& G, int B)
+__device__ __forceinline__ void pk_tab2_mixed(const EngineDev& D, const Tab2Group& G, int tile, int tr, int B)
 {
-    if (G.cross) pk_tab2_body<KT, MS, NW, true, 1>(D, G, B); else pk_tab2_body<KT, MS, NW, false, 1>(D, G, B);
+    if (G.cross) pk_tab2_body<KT, MS, NW, true, 1>(D, G, tile, tr, B); else pk_tab2_body<KT, MS, NW, false, 1>(D, G, tile, tr, B);
     __syncthreads();        // (the reduction scratch of the first pass shares its LDS with the second pass's node tables)
-    if (G.cross) pk_tab2_body<KT, MS, NW, true, 2>(D, G, B); else pk_tab2_body<KT, MS, NW, false, 2>(D, G, B);
+    if (G.cross) pk_tab2_body<KT, MS, NW, true, 2>(D, G, tile, tr, B); else pk_tab2_body<KT, MS, NW, false, 2>(D, G, tile, tr, B);
 }
 
 // waves per SIMD the register allocation aims at (measured: three or four waves of the two-walker shape run the same)
@@ -1737,6 +1745,8 @@ template <int KT, int MS, int NW>
 __global__ __launch_bounds__(KT * MS, KT != 64 ? 4 : (NW == 1 ? VMX_TAB2_BLOCKS : VMX_TAB2_W2) * (4 / MS)) void k_pk_tab2(EngineDev D, Tab2Args A, int B)
 {
     const Tab2Group& G = A.g[blockIdx.y];
+    const int zz = A.n_z ? (int)A.zmap[blockIdx.z] : -1;                       // tile | tier << 12
+    const int tile = zz >= 0 ? zz & 0xfff : (int)blockIdx.z, tr = zz >= 0 ? zz >> 12 : 0;
     if constexpr (NW > 1) {
         // do the walkers of this block agree on the mu rule? (block-uniform: the flags are the prologue's, per walker)
         bool any_in = false, all_in = true;
@@ -1745,10 +1755,10 @@ __global__ __launch_bounds__(KT * MS, KT != 64 ? 4 : (NW == 1 ? VMX_TAB2_BLOCKS 
             const bool inside = D.scal[((size_t)b * D.n_pipe + G.pipe) * VMX_NS + S_NO_RULE] == 0.0;
             any_in = any_in || inside; all_in = all_in && inside;
         }
-        if (any_in && !all_in) { pk_tab2_mixed<KT, MS, NW>(D, G, B); return; }
+        if (any_in && !all_in) { pk_tab2_mixed<KT, MS, NW>(D, G, tile, tr, B); return; }
     }
-    if (G.cross) pk_tab2_body<KT, MS, NW, true>(D, G, B);
-    else pk_tab2_body<KT, MS, NW, false>(D, G, B);
+    if (G.cross) pk_tab2_body<KT, MS, NW, true>(D, G, tile, tr, B);
+    else pk_tab2_body<KT, MS, NW, false>(D, G, tile, tr, B);
 }
 
 // `fht_extrap` (reference pktoxi.py:41,141; mcfit's `_pad(extrap=True)`): behind the nk samples F of every P_ell row the

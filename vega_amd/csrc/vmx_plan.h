@@ -377,4 +377,143 @@ inline bool cholesky_lower(double* a, int n, int64_t ld)
     return true;
 }
 
+// ---- the mu node rules ------------------------------------------------------------------------------------------------
+// Extra nodes (mu, w) of a node rule of the mu sums: the nodes that replace the midpoints lo .. n_mu - hi - 1 of the
+// n_mu-point midpoint sum - `panels` Gauss-Legendre panels of `ngl` nodes over [a, b] = [lo, n_mu - hi] / n_mu, then per
+// point i of ONE one-sided `npts`-point stencil per end the two entries (b - i eps, a + i eps) that carry the first, third
+// and fifth derivative terms of the Euler-Maclaurin formula.  Appended to mu / w.  The NumPy restatement is
+// vega_amd/mu_quadrature.py: extra_nodes (the same sequence of operations).
+inline void mu_rule_extra(int n_mu, int lo, int hi, int panels, int ngl, int npts, double eps, std::vector<double>& node_mu, std::vector<double>& node_w)
+{
+    const double h = 1.0 / n_mu, a = lo * h, b = (n_mu - hi) * h;
+    std::vector<double> gx(ngl), gw(ngl);
+    for (int i = 0; i < ngl; ++i) {            // Gauss-Legendre nodes by Newton's iteration on P_ngl
+        double x = std::cos(M_PI * (i + 0.75) / (ngl + 0.5)), dp = 1.0;
+        for (int it = 0; it < 100; ++it) {
+            double p0 = 1.0, p1 = x;
+            for (int n = 2; n <= ngl; ++n) { const double p2 = ((2 * n - 1) * x * p1 - (n - 1) * p0) / n; p0 = p1; p1 = p2; }
+            dp = ngl * (x * p1 - p0) / (x * x - 1.0);
+            const double dx = p1 / dp;
+            x -= dx;
+            if (std::fabs(dx) < 1e-16) break;
+        }
+        gx[i] = x; gw[i] = 2.0 / ((1.0 - x * x) * dp * dp);
+    }
+    for (int pnl = 0; pnl < panels; ++pnl) {
+        const double pa = a + (b - a) * pnl / panels, pb = a + (b - a) * (pnl + 1) / panels;
+        for (int i = 0; i < ngl; ++i) { node_mu.push_back(0.5 * (pb - pa) * gx[i] + 0.5 * (pa + pb)); node_w.push_back(0.5 * (pb - pa) * gw[i] / h); }
+    }
+    // Finite-difference weights of the derivatives 0 .. 5 at x = 0 on the points 0, 1, .. npts - 1 (Fornberg's recursion):
+    // D^k f(x) ~ sum_i c[i][k] f(x + i e) / e^k
+    constexpr int MD = 5;
+    std::vector<std::vector<double>> c(npts, std::vector<double>(MD + 1, 0.0));
+    {
+        double c1 = 1.0, c4 = 0.0;
+        c[0][0] = 1.0;
+        for (int i = 1; i < npts; ++i) {
+            const int mn = std::min(i, MD);
+            double c2 = 1.0;
+            const double c5 = c4;
+            c4 = (double)i;
+            for (int j = 0; j < i; ++j) {
+                const double c3 = (double)(i - j);
+                c2 *= c3;
+                if (j == i - 1) {
+                    for (int k = mn; k >= 1; --k) c[i][k] = c1 * (k * c[i - 1][k - 1] - c5 * c[i - 1][k]) / c2;
+                    c[i][0] = -c1 * c5 * c[i - 1][0] / c2;
+                }
+                for (int k = mn; k >= 1; --k) c[j][k] = (c4 * c[j][k] - k * c[j][k - 1]) / c3;
+                c[j][0] = c4 * c[j][0] / c3;
+            }
+            c1 = c2;
+        }
+    }
+    // midpoint sum = (1/h) int - (h/24) [Df] + (7 h^3/5760) [D^3 f] - (31 h^5/967680) [D^5 f],  [g] = g(b) - g(a);
+    // backward stencil at b: D^k f(b) ~ -sum_i c[i][k] f(b - i e) / e^k for odd k
+    const double coef[3] = {-h / 24.0, 7.0 * h * h * h / 5760.0, -31.0 * h * h * h * h * h / 967680.0};
+    const int order[3] = {1, 3, 5};
+    for (int i = 0; i < npts; ++i) {
+        double wb = 0.0, wa = 0.0;
+        for (int q = 0; q < 3; ++q) {
+            const double scaled = c[i][order[q]] / std::pow(eps, order[q]);
+            wb += coef[q] * (-scaled);
+            wa += -coef[q] * scaled;
+        }
+        node_mu.push_back(b - i * eps); node_w.push_back(wb);
+        node_mu.push_back(a + i * eps); node_w.push_back(wa);
+    }
+}
+
+// The tiers of the rule (vega_amd/mu_quadrature.py: TIERS is the statement of these numbers, with the validation that
+// gave k_max - tests/test_mu_tiers.py).  Tier 0 is the main rule; a shorter tier serves a k tile whose largest wavenumber
+// is at most its k_max: there k^3 M_n is orders of magnitude below its maximum, which is what the rule's accuracy is
+// measured against, and the integrand is nearly a polynomial in mu^2.
+struct MuTierRule { int lo, hi, panels, ngl; double k_max; };
+constexpr int MU_TIERS = 3;
+constexpr int MU_STENCIL = 9;
+constexpr double MU_EPS = 1e-3;
+inline const MuTierRule* mu_tier_rules()
+{
+    static const MuTierRule rules[MU_TIERS] = {{48, 48, 2, 32, HUGE_VAL}, {16, 16, 1, 32, 0.11}, {4, 4, 1, 16, 0.0058}};
+    return rules;
+}
+
+// kept midpoints and extra nodes of a tier within the node list (rows n_mu + x_off .. n_mu + x_off + x_cnt - 1 of the tables)
+struct MuTierDesc { int32_t lo, hi, x_off, x_cnt; };
+
+// All tiers' extra nodes one behind the other (the main rule's first, unchanged); n_tiers = 1: the main rule alone.
+inline void build_mu_tiers(int n_mu, int n_tiers, std::vector<double>& node_mu, std::vector<double>& node_w, MuTierDesc* desc)
+{
+    const MuTierRule* rules = mu_tier_rules();
+    for (int t = 0; t < MU_TIERS; ++t) {
+        const MuTierRule& r = rules[t < n_tiers ? t : 0];
+        if (t < n_tiers) {
+            const int off = (int)node_mu.size();
+            mu_rule_extra(n_mu, r.lo, r.hi, r.panels, r.ngl, MU_STENCIL, MU_EPS, node_mu, node_w);
+            desc[t] = {r.lo, r.hi, off, (int)node_mu.size() - off};
+        } else desc[t] = desc[0];
+    }
+}
+
+// The cheapest tier whose k_max is at or above the tile's largest wavenumber (the tiers are ordered by falling k_max).
+inline int mu_tier_of(double k_tile_max, int n_tiers)
+{
+    const MuTierRule* rules = mu_tier_rules();
+    int tier = 0;
+    for (int t = 1; t < n_tiers && t < MU_TIERS; ++t) if (k_tile_max <= rules[t].k_max) tier = t;
+    return tier;
+}
+
+// Launch order of the k tiles of k_pk_tab2 (tile width kt over the nk wavenumbers k, ascending): zmap[z] = tile | tier << 12
+// for the z-th slowest grid index.  The longest blocks start first - main-rule tiles, then the shorter tiers, and last the
+// tiles that lie wholly above k_node_max (dead at these wavenumbers, or on the plain loop as before); ascending k within a
+// class.  Empty when the tiles do not fit the 12 bits or `cap` entries: the caller then launches in plain order, main rule.
+inline std::vector<uint16_t> plan_mu_tiles(const double* k, int nk, int kt, double k_node_max, int n_tiers, size_t cap)
+{
+    const int n_tiles = (nk + kt - 1) / kt;
+    std::vector<uint16_t> zmap;
+    if (n_tiles <= 0 || n_tiles > 4096 || (size_t)n_tiles > cap) return zmap;
+    std::vector<int> cls(n_tiles), tier(n_tiles);
+    for (int t = 0; t < n_tiles; ++t) {
+        tier[t] = mu_tier_of(k[std::min((t + 1) * kt, nk) - 1], n_tiers);
+        cls[t] = k[t * kt] > k_node_max ? MU_TIERS : tier[t];
+    }
+    for (int c = 0; c <= MU_TIERS; ++c)
+        for (int t = 0; t < n_tiles; ++t) if (cls[t] == c) zmap.push_back((uint16_t)(t | tier[t] << 12));
+    return zmap;
+}
+
+// mean number of nodes per wavenumber over the first k_on_rule wavenumbers (tiles of width kt on their tiers)
+inline double mu_mean_nodes(const double* k, int nk, int kt, int k_on_rule, int n_tiers, const MuTierDesc* desc)
+{
+    k_on_rule = std::min(k_on_rule, nk);
+    if (k_on_rule <= 0 || kt <= 0) return (double)(desc[0].lo + desc[0].hi + desc[0].x_cnt);
+    double sum = 0.0;
+    for (int i = 0; i < k_on_rule; ++i) {
+        const MuTierDesc& d = desc[mu_tier_of(k[std::min((i / kt + 1) * kt, nk) - 1], n_tiers)];
+        sum += d.lo + d.hi + d.x_cnt;
+    }
+    return sum / k_on_rule;
+}
+
 }  // namespace vmx_plan

@@ -13,7 +13,7 @@ model sit at the ends of the mu range), integrates the middle with ``panels`` Ga
 forms three derivative terms (the formula's next one is - (31 h^5 / 967680) [D^5 f]) with ONE one-sided nine-point
 finite-difference stencil per end - every piece is a fixed set of nodes
 with fixed weights: ``sum_j W_j mu_j^(2n) P(k, mu_j)`` over 48 + 48 + 82 nodes instead of 1000 (round 2: 96 + 96 + 84 with
-five-point stencils and two derivative terms).
+five-point stencils and two derivative terms).  Low-wavenumber k tiles of the level-2 kernel take shorter rules: TIERS.
 """
 import numpy as np
 
@@ -79,6 +79,44 @@ def node_rule(n_mu=N_MU, lo=LO, hi=HI, **kw):
     kept = np.concatenate([np.arange(lo), np.arange(n_mu - hi, n_mu)])
     mu_x, w_x = extra_nodes(n_mu, lo, hi, **kw)
     return np.concatenate([(kept + 0.5) / n_mu, mu_x]), np.concatenate([np.ones(kept.size), w_x])
+
+
+# ---- tiers --------------------------------------------------------------------------------------------------------------
+# The accuracy bar of the rule is a fraction of the LARGEST k^3 M_n over all wavenumbers (how a multipole enters xi).  On the
+# logarithmic FFTLog grid most k tiles of the level-2 P(k, mu) kernel (k_pk_tab2) lie where k^3 is orders of magnitude below
+# its maximum and the integrand is nearly a polynomial in mu^2: a shorter rule from the same generator serves them.  A tile
+# takes the cheapest tier whose ``k_max`` is at or above its largest wavenumber.  ``k_max`` [h/Mpc]: the tier adds at most 1e-14
+# of the largest k^3 M_n at every wavenumber up to it - 104 draws over the guard box, corners included, four moments, both
+# items of the joint fit, peak and smooth (tests/test_mu_tiers.py, which records the margins: the 82-node rule holds the bar
+# up to k = 0.188, the 42-node rule up to 0.0080).  The single statement of these numbers; the engine's copy is
+# vmx_plan::mu_tier_rules (csrc/vmx_plan.h).  The extra nodes of the shorter tiers follow the main rule's in the engine's
+# tables (+50, +34); their kept midpoints are rows the tables already have.
+TIERS = (
+    dict(lo=LO, hi=HI, panels=PANELS, n_gl=N_GL, k_max=np.inf),       # 178 nodes: the main rule
+    dict(lo=16, hi=16, panels=1, n_gl=32, k_max=0.11),                  # 82 nodes
+    dict(lo=4, hi=4, panels=1, n_gl=16, k_max=0.0058),                  # 42 nodes
+)
+
+
+def tier_of(k_tile_max, n_tiers=len(TIERS)):
+    """Index into TIERS of the rule a k tile with largest wavenumber ``k_tile_max`` takes."""
+    tier = 0
+    for t in range(1, n_tiers):
+        if k_tile_max <= TIERS[t]['k_max']:
+            tier = t
+    return tier
+
+
+def tier_rule(tier):
+    """(mu, w) of a tier's whole rule."""
+    return node_rule(**{key: val for key, val in TIERS[tier].items() if key != 'k_max'})
+
+
+def tiers_of_grid(k, tile):
+    """Per wavenumber of the ascending grid ``k``: the tier its ``tile``-wide k tile takes."""
+    k = np.asarray(k, dtype=float)
+    ends = np.minimum((np.arange(k.size) // tile + 1) * tile, k.size) - 1
+    return np.array([tier_of(k[e]) for e in ends])
 
 
 # ---- applicability guard ---------------------------------------------------------------------------------------------
