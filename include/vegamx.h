@@ -12,7 +12,7 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_many) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
  * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
@@ -158,7 +158,8 @@ typedef struct {
 const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
- * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters): lets a foreign binding verify its struct layout at load time. */
+ * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
+ * 18 vmx_nested_set_options): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -568,6 +569,56 @@ int vmx_nested_run_clustered(vmx_engine* e, const vmx_nested_spec* spec, double*
  * coordinate that is not finite, an id outside 0 .. *next_id - 1.  A HIP failure returns -2. */
 int vmx_nested_cluster_points(int32_t device, const double* u, int32_t m, int32_t n, const int32_t* prev_id, int32_t* next_id,
                               int32_t* ids, int32_t* k_used, int32_t* n_clusters, double* means, double* factors);
+/* E independent nested-sampling runs advanced together: log Z and a weighted posterior for every Monte-Carlo mock, or the replicas
+ * of one run, as one device run (the rule, pinned: vega_amd/csrc/vmx_nested.h "a set of runs").  A run of a few hundred live points
+ * hands the engine a fraction of a batch per round and stops the host every round; here a set round is at most three launches
+ * for the whole set - k_ns_set_head (one work-group per run whose iteration begins: k_ns_iteration's body), k_ns_set_advance (one
+ * per run still in the set: every thread takes the answer of the engine row it asked for and advances; the run counts its
+ * requests; a run that asks for nothing ends its iteration there) and k_ns_set_emit (the requests of all runs packed into the
+ * engine's rows [0, total) in ascending (run, thread) order, the offsets a sum of the counts in list order) - then one host wait,
+ * and the total rows go through the engine as one stream of chunks of `chunk` on two lanes.  Runs do not wait for each other's
+ * iterations: a run whose iteration ended in round r is headed in round r + 1.  Run e is by construction the run vmx_nested_run
+ * makes with spec->stream = streams[e] on the data of mock_row[e]; its chi2 is evaluated in batches of another shape, so that
+ * its lnL may differ from the single run's in the last bits (E = 1 has the single run's batches and gives it bit for bit).
+ * Clustering is not part of the set.
+ *   spec      as for the single run; spec->stream is not read
+ *   E         runs (>= 1) of spec->nlive live points and spec->K threads each
+ *   streams   [E] the Philox stream of every run (repeats allowed)
+ *   mock_row  [E] the row of the items' mock pools run e is compared with, 0 <= row < n_mocks of every item's pool, repeats
+ *             allowed; NULL: every run reads the installed data
+ *   live_u, live_lnl   [E][nlive][n], [E][nlive] host: the runs' state, read at entry (unless opt->draw_live), written back at exit
+ *   iteration [E] the global index of every run's next iteration (runs may enter at different ones), advanced by iterations_done
+ *   status    [E] out: 0 the run is still going (n_iterations used up), 1 its stop callback ended it, 2 with draw_live no live
+ *             point has a finite lnL - the run is never entered, its arrays are left as they were, its iterations_done is 0 and
+ *             the call does not fail
+ *   n_iterations   at most so many iterations per run in this call
+ *   dead_u, dead_lnl, dead_nlive   [E][n_iterations K][n], [E][n_iterations K] x 2 host: every run's deaths as the single run
+ *             records them; iterations_done[e] K rows of run e are written
+ *   iterations_done   [E] out
+ *   opt       vmx_nested_options with the stop callback of a set: stop(user, run, iterations, dead_lnl [K], live_lnl [nlive]) is
+ *             called after every iteration of every run with the iterations done in that run; nonzero ends that run alone.
+ *             draw_live applies to every run (every iteration[e] must then be 0).
+ *   stats     the totals over the runs; rounds: the set rounds; host_waits = set rounds + 1 (the copy back) + 1 with draw_live.
+ *             per_run [E][3] (NULL: not wanted): rows evaluated (the nlive drawn ones included), rows that were a thread's own
+ *             position, set rounds the run took part in
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever the single run refuses, for every run; E < 1;
+ * streams NULL; a mock row that is negative or not below n_mocks; mock rows while an item has no pool; E nlive beyond the
+ * engine's int32 row count or a record beyond size_t; draw_live with a non-zero iteration[e].  A HIP failure later returns -2
+ * and leaves the engine usable. */
+typedef int32_t (*vmx_nested_set_stop)(void* user, int32_t run, int64_t iterations, const double* dead_lnl, const double* live_lnl);
+typedef struct {
+    int32_t const_hint, chunk, lanes, draw_live;
+    vmx_nested_set_stop stop; void* user;
+} vmx_nested_set_options;
+int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E,
+                        const uint64_t* streams, const int32_t* mock_row,
+                        double* live_u, double* live_lnl,
+                        int64_t* iteration,
+                        int32_t* status,
+                        int32_t n_iterations,
+                        double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                        int32_t* iterations_done,
+                        const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run);
 /* Evidence and an equal-weight posterior where the particles live: tempered sequential Monte Carlo (the scheme of pocoMC, the
  * reference's second sampler in bin/run_vega_mpi.py, without its normalising flow), every decision pinned in
  * vega_amd/csrc/vmx_smc.h.  N particles walk from the prior (beta = 0) to the posterior (beta = 1); a stage picks the next beta by

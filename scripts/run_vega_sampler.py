@@ -11,7 +11,9 @@ coefficients as derived parameters (``<corr>_marg_<i>``) to both files.
 
 ``replicas = R`` in the sampler's section runs R independent copies (the same seed, Philox stream r) and merges them
 (vega_amd/replicas.py): nested runs into one run with the summed live count, SMC evidences into their mean, ensembles into
-``<name>_1.txt ... <name>_R.txt`` with R-hat in ``<name>.stats``.  The ranks share the replicas out in contiguous blocks and run
+``<name>_1.txt ... <name>_R.txt`` with R-hat in ``<name>.stats``.  ``together = True`` beside it (``[Ensemble]``, ``[SMC]``,
+``[Nested]``) advances a rank's replicas as one set in one device run; ``mocks = M`` in the sampler's section (Monte-Carlo mode)
+samples every one of M mocks in one run and writes ``<name>_mock<m>.*`` with ``mock_posteriors.fits``.  The ranks share the replicas out in contiguous blocks and run
 theirs one after the other; every replica leaves ``<name>.replica<r>.npz``; rank 0 merges.  Under torchrun (gloo carries two
 barriers and one gather of counts; there is no data-path collective):
 

@@ -194,9 +194,10 @@ struct BoxWorkspace {
 };
 
 // The engine's rows out of the unit cube: the fixed row with the sampled columns mapped into the box, u(r, d) the cube coordinate
-// d of row r (a lane keeps its column: what the column needs is read once, the rows go round the waves)
+// d of row r (a lane keeps its column: what the column needs is read once, the rows go round the waves); the rows land at the
+// engine's rows row0 .. row0 + rows - 1
 template <int THREADS, typename U>
-__device__ inline void write_cube_rows(const BoxDev& B, int P, int rows, U u)
+__device__ inline void write_cube_rows(const BoxDev& B, int P, size_t row0, int rows, U u)
 {
     for (int p = threadIdx.x % 64; p < P; p += 64) {
         const int d = B.inv[p];
@@ -205,9 +206,14 @@ __device__ inline void write_cube_rows(const BoxDev& B, int P, int rows, U u)
         for (int r = threadIdx.x / 64; r < rows; r += THREADS / 64) {
             double v = fixed;
             if (d >= 0) v = vmx_ns::map_cube(lo, hi, u(r, d));
-            B.theta[(size_t)r * P + p] = v;
+            B.theta[(row0 + (size_t)r) * P + p] = v;
         }
     }
+}
+template <int THREADS, typename U>
+__device__ inline void write_cube_rows(const BoxDev& B, int P, int rows, U u)
+{
+    write_cube_rows<THREADS>(B, P, (size_t)0, rows, u);
 }
 
 // Ensemble sampling (vmx_ensemble_run, vmx_ensemble_run_many): the walkers' state of the E ensembles, the proposals of a half and
@@ -320,9 +326,17 @@ struct NsWorkspace {
     int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round
     double* pin_lnl = nullptr; double* dpin_lnl = nullptr;           // ... and, when an iteration ends, live lnL [nlive] + dead lnL [K]
     size_t pin_lnl_n = 0;
+    // a set of runs (vmx_nested_run_many): the lists and the iterations done [3][E] (pinned, and on the device), the counts of the
+    // round per list entry and per run (mapped), streams, first iterations and mocks
+    DevBuf<int32_t> set_ctl, set_count, mock_row, mock;
+    DevBuf<uint64_t> streams;
+    DevBuf<int64_t> it0;
+    int32_t* set_host = nullptr; int32_t* pin_count = nullptr; int32_t* dpin_count = nullptr; size_t set_runs = 0;
     ~NsWorkspace() {
         if (pin_word) (void)hipHostFree(pin_word);
         if (pin_lnl) (void)hipHostFree(pin_lnl);
+        if (set_host) (void)hipHostFree(set_host);
+        if (pin_count) (void)hipHostFree(pin_count);
     }
 };
 
@@ -618,11 +632,9 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_iteration_clustered(NsDev D, 
 // newly dead lnL go to the host beside the word.  CLUSTER (k_ns_advance_clustered): every thread walks with the factor of its
 // start's cluster, and its end point inherits that cluster's id.
 template <bool CLUSTER>
-__device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec)
+__device__ __forceinline__ int ns_advance_threads(const NsDev& D, const NsClusterRun& X, int64_t it, int32_t* s_scan, int32_t* s_row_thread)
 {
-    __shared__ int32_t s_scan[NS_THREADS];
-    __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
-    const int K = D.K, n = D.n, P = D.P;
+    const int K = D.K, n = D.n;
     const int per = (K + NS_THREADS - 1) / NS_THREADS;
     const int k0 = threadIdx.x * per;
     vmx_ns::Iteration I{D.chol, *D.lstar, it, D.seed, D.stream, n, D.num_repeats};
@@ -654,29 +666,44 @@ __device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X
         if (k >= K) break;
         if (asks & (1u << j)) {
             D.slot[k] = row;
-            s_row_thread[row] = k;
+            if (s_row_thread) s_row_thread[row] = k;
             own += D.th[k].inside ? 0 : 1;
             row += 1;
         } else D.slot[k] = -1;
     }
     if (own) atomicAdd((unsigned long long*)D.counters, (unsigned long long)own);
     __syncthreads();
-    write_cube_rows<NS_THREADS>(D.box, P, total, [&](int r, int d) {
+    return total;
+}
+
+// the end of an iteration: the end points take the killed points' slots, the live and the newly dead lnL go to the host
+template <bool CLUSTER>
+__device__ __forceinline__ void ns_iteration_end(const NsDev& D, const NsClusterRun& X, int64_t rec)
+{
+    const int K = D.K, n = D.n;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        const int i = D.killed[k];
+        const vmx_ns::Thread& T = D.th[k];
+        for (int d = 0; d < n; ++d) D.live_u[(size_t)i * n + d] = T.x[d];
+        D.live_lnl[i] = T.lnl;
+        if constexpr (CLUSTER) X.cl.ids[i] = X.cl.cl_id[X.tslot[k]];
+        D.host_lnl[D.nlive + k] = D.dead_lnl[(size_t)rec * K + k];
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.host_lnl[i] = D.live_lnl[i];
+}
+
+template <bool CLUSTER>
+__device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec)
+{
+    __shared__ int32_t s_scan[NS_THREADS];
+    __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
+    const int total = ns_advance_threads<CLUSTER>(D, X, it, s_scan, s_row_thread);
+    write_cube_rows<NS_THREADS>(D.box, D.P, total, [&](int r, int d) {
         const vmx_ns::Thread& T = D.th[s_row_thread[r]];
         return T.inside ? T.y[d] : T.x[d];
     });
-    if (total == 0) {
-        for (int k = threadIdx.x; k < K; k += blockDim.x) {
-            const int i = D.killed[k];
-            const vmx_ns::Thread& T = D.th[k];
-            for (int d = 0; d < n; ++d) D.live_u[(size_t)i * n + d] = T.x[d];
-            D.live_lnl[i] = T.lnl;
-            if constexpr (CLUSTER) X.cl.ids[i] = X.cl.cl_id[X.tslot[k]];
-            D.host_lnl[D.nlive + k] = D.dead_lnl[(size_t)rec * K + k];
-        }
-        __syncthreads();
-        for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.host_lnl[i] = D.live_lnl[i];
-    }
+    if (total == 0) ns_iteration_end<CLUSTER>(D, X, rec);
     if (threadIdx.x == 0) *D.host_word = total;
 }
 
@@ -688,6 +715,123 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
 __global__ __launch_bounds__(NS_THREADS) void k_ns_advance_clustered(NsDev D, NsClusterRun X, int64_t it, int64_t rec)
 {
     ns_advance<true>(D, X, it, rec);
+}
+
+// A set of runs (vmx_nested_run_many; vmx_nested.h "a set of runs"): a work-group owns one run - the functions above over that
+// run's part of every array (`run0` is the view of run 0) under the stream streams[run] - and nothing crosses runs except the
+// row offsets: the engine's rows are shared, a thread's slot is its global row.  Run r is at record row done[r] of the call and
+// at iteration it0[r] + done[r] of its own count.
+struct NsSetDev {
+    NsDev run0;
+    const int32_t* active;              // [A] the runs not OUT, ascending
+    const int32_t* heading;             // [H] those of them whose iteration has to be headed
+    const int32_t* done;                // [E] iterations done in this call
+    const int64_t* it0;                 // [E] the runs' iteration at entry
+    const uint64_t* streams;            // [E] Philox streams
+    const int32_t* mock_row;            // [E] the pool row of every run, or nullptr
+    int32_t* mock;                      // the mock row of every engine row (k_ns_set_emit / k_ns_set_draw_live write it)
+    int32_t* count;                     // [A] the requests of run active[a] in this round
+    int32_t* host_count;                // [E] mapped: per run its requests of the round (the draw: whether a live lnL is finite)
+    int32_t rec_rows, A;                // record rows per run; the length of the active list
+};
+
+__device__ __forceinline__ NsDev ns_view(const NsSetDev& S, int run)
+{
+    NsDev D = S.run0;
+    const size_t r = (size_t)run, nlive = (size_t)D.nlive, K = (size_t)D.K, n = (size_t)D.n, rec = (size_t)S.rec_rows * K;
+    D.live_u += r * nlive * n; D.live_lnl += r * nlive; D.rank += r * nlive; D.surv += r * nlive; D.killed += r * K;
+    D.mean += r * n; D.cov += r * n * n; D.chol += r * n * n; D.lstar += r;
+    D.th += r * K; D.slot += r * K;
+    D.dead_u += r * rec * n; D.dead_lnl += r * rec; D.dead_n += r * rec;
+    D.host_lnl += r * (nlive + K); D.counters += r;
+    D.stream = S.streams[r];
+    return D;
+}
+
+// the initial live points of every active run, run active[a] at the engine's rows a nlive .. (a + 1) nlive - 1
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_draw_live(NsSetDev S)
+{
+    const int run = S.active[blockIdx.x];
+    const NsDev D = ns_view(S, run);
+    const size_t row0 = (size_t)blockIdx.x * D.nlive;
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) {
+        vmx_ns::draw_live(i, D.n, D.seed, D.stream, D.live_u + (size_t)i * D.n);
+        if (S.mock_row) S.mock[row0 + i] = S.mock_row[run];
+    }
+    __syncthreads();
+    write_cube_rows<NS_THREADS>(D.box, D.P, row0, D.nlive, [&](int r, int d) { return D.live_u[(size_t)r * D.n + d]; });
+}
+
+// ... their lnL, and to the host whether any of a run's is finite
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_live_lnl(NsSetDev S)
+{
+    const int run = S.active[blockIdx.x];
+    const NsDev D = ns_view(S, run);
+    const size_t row0 = (size_t)blockIdx.x * D.nlive;
+    int finite = 0;
+    for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) {
+        const double l = vmx_ns::lnl_of(D.box.status[row0 + i], D.box.chi2[row0 + i], D.log_norm);
+        D.live_lnl[i] = l;
+        finite |= l > -INFINITY ? 1 : 0;
+    }
+    const int any = __syncthreads_or(finite);
+    if (threadIdx.x == 0) S.host_count[run] = any ? 1 : 0;
+}
+
+// the head of the next iteration of every run of the heading list: k_ns_iteration's body on that run's view
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_head(NsSetDev S)
+{
+    const int run = S.heading[blockIdx.x];
+    const NsDev D = ns_view(S, run);
+    ns_iteration<false>(D, NsClusterRun{}, S.it0[run] + S.done[run], (int64_t)S.done[run]);
+}
+
+// One answer for every thread of every active run (k_ns_advance's body up to the rows): the threads' slots hold their place among
+// the run's own requests, count[a] the run's requests; a run that asks for nothing ends its iteration here.  Holds 4 KB of LDS.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_advance(NsSetDev S)
+{
+    __shared__ int32_t s_scan[NS_THREADS];
+    const int run = S.active[blockIdx.x];
+    const NsDev D = ns_view(S, run);
+    const int total = ns_advance_threads<false>(D, NsClusterRun{}, S.it0[run] + S.done[run], s_scan, nullptr);
+    if (total == 0) ns_iteration_end<false>(D, NsClusterRun{}, (int64_t)S.done[run]);
+    if (threadIdx.x == 0) S.count[blockIdx.x] = total;
+}
+
+// The packing: run active[a] owns the engine's rows offset[a] .. offset[a] + count[a] - 1, offset[a] the sum of the counts before
+// it in list order (vmx_ns::row_offsets), its requests in thread order.  Every slot becomes a global row, the rows and their
+// mocks are written, the run's count and (work-group 0) the total go to the host.  Holds 16 KB of LDS.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_emit(NsSetDev S)
+{
+    __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
+    const int a = blockIdx.x, run = S.active[a];
+    const NsDev D = ns_view(S, run);
+    int offset = 0;
+    for (int b = 0; b < a; ++b) offset += S.count[b];
+    const int cnt = S.count[a];
+    for (int k = threadIdx.x; k < D.K; k += blockDim.x) {
+        const int local = D.slot[k];
+        if (local < 0) continue;
+        s_row_thread[local] = k;
+        D.slot[k] = offset + local;
+    }
+    __syncthreads();
+    write_cube_rows<NS_THREADS>(D.box, D.P, (size_t)offset, cnt, [&](int r, int d) {
+        const vmx_ns::Thread& T = D.th[s_row_thread[r]];
+        return T.inside ? T.y[d] : T.x[d];
+    });
+    if (S.mock_row) {
+        const int m = S.mock_row[run];
+        for (int i = threadIdx.x; i < cnt; i += blockDim.x) S.mock[offset + i] = m;
+    }
+    if (threadIdx.x == 0) {
+        S.host_count[run] = cnt;
+        if (a == 0) {
+            int total = 0;
+            for (int b = 0; b < S.A; ++b) total += S.count[b];
+            *D.host_word = total;
+        }
+    }
 }
 
 // Tempered SMC (vmx_smc_run): the particles, their proposals, the weights of a stage, the rows of a sweep and the stage record
@@ -1581,6 +1725,7 @@ int vmx_struct_size(int32_t which)
         case 15: return (int)sizeof(vmx_smc_options);
         case 16: return (int)sizeof(vmx_smc_stats);
         case 17: return (int)sizeof(vmx_nested_clusters);
+        case 18: return (int)sizeof(vmx_nested_set_options);
         default: return -1;
     }
 }
@@ -4859,6 +5004,207 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
     if (clustering) *clusters->next_id = info_out[2];
     R.iterations = done;
     R.rows_own_position = own;
+    R.seconds_enqueuing = enqueue_s;
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// E independent runs advanced together (vmx_nested.h "a set of runs"): per set round one launch heads the runs whose iteration
+// begins, one advances every thread of every active run, one packs the requests of all runs into the engine's rows; the host
+// waits once per round
+int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
+                        double* live_u, double* live_lnl, int64_t* iteration, int32_t* status, int32_t n_iterations,
+                        double* dead_u, double* dead_lnl, int32_t* dead_nlive, int32_t* iterations_done,
+                        const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run)
+{
+    const std::string name("vmx_nested_run_many");
+    REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration && status && iterations_done, name);
+    REQUIRE(E >= 1, name + ": at least one run");
+    REQUIRE(streams, name + ": a Philox stream for every run");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (check_box(name, e, spec, VMX_NS_MAXN, varies, inv)) return -1;
+    const int n = spec->n, P = e->n_params, nlive = spec->nlive, K = spec->K;
+    REQUIRE(nlive >= n + 2 && nlive <= VMX_NS_MAX_LIVE, name + ": n + 2 .. 4096 live points");
+    REQUIRE(K >= 1 && K <= nlive - n - 1, name + ": 1 .. nlive - n - 1 threads");
+    REQUIRE(spec->num_repeats >= 1, name + ": num_repeats >= 1");
+    REQUIRE(n_iterations >= 0, name + ": n_iterations >= 0");
+    REQUIRE(n_iterations == 0 || (dead_u && dead_lnl && dead_nlive), name + ": the dead record");
+    // sizes: the engine's rows are counted in int32, the largest array (the record, or the rows themselves) in size_t
+    REQUIRE((int64_t)E * nlive <= INT32_MAX, name + ": E nlive exceeds the engine's row count");
+    const size_t EL = (size_t)E * nlive, EK = (size_t)E * K, rec_iter = (size_t)std::max(n_iterations, 1), rec_rows = rec_iter * K;
+    const size_t per_row = (size_t)std::max(n, P) * sizeof(double);
+    REQUIRE(EL <= SIZE_MAX / per_row && EK * per_row <= SIZE_MAX / rec_iter, name + ": the record is too large");
+    const bool draw = opt && opt->draw_live != 0;
+    for (int q = 0; q < E; ++q) {
+        REQUIRE(iteration[q] >= 0, name + ": iteration >= 0");
+        REQUIRE(!draw || iteration[q] == 0, name + ": live points are drawn at iteration 0");
+        if (draw) continue;
+        for (size_t i = (size_t)q * nlive; i < (size_t)(q + 1) * nlive; ++i) {
+            REQUIRE(!std::isnan(live_lnl[i]), name + ": a live point has a NaN lnL");
+            for (int d = 0; d < n; ++d) {
+                const double v = live_u[i * n + d];
+                REQUIRE(v >= 0.0 && v <= 1.0, name + ": a live point lies outside the unit cube");
+            }
+        }
+    }
+    if (mock_row)
+        for (int q = 0; q < E; ++q)
+            for (auto* it : e->items) {
+                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
+                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
+            }
+    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    const size_t cap = EL;          // (K < nlive: the draw's rows are the most a launch writes)
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->nsws) e->nsws = new NsWorkspace();
+    NsWorkspace& S = *e->nsws;
+    if (ensure(S.live_u, EL * n) || ensure(S.live_lnl, EL) || ensure(S.rank, EL) || ensure(S.surv, EL) || ensure(S.killed, EK) ||
+        ensure(S.mean, (size_t)E * n) || ensure(S.cov, (size_t)E * n * n) || ensure(S.chol, (size_t)E * n * n) || ensure(S.lstar, E) ||
+        ensure(S.th, EK * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, EK) || ensure(S.dead_u, E * rec_rows * n) ||
+        ensure(S.dead_lnl, E * rec_rows) || ensure(S.dead_n, E * rec_rows) || ensure(S.counters, E) || ensure(S.set_ctl, (size_t)3 * E) ||
+        ensure(S.set_count, E) || ensure(S.streams, E) || ensure(S.it0, E) || (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, cap))))
+        return -2;
+    if (!S.pin_word) {
+        HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_word, S.pin_word, 0));
+    }
+    const size_t lnl_words = (size_t)E * ((size_t)nlive + K);
+    if (S.pin_lnl_n < lnl_words) {
+        if (S.pin_lnl) { (void)hipHostFree(S.pin_lnl); S.pin_lnl = nullptr; S.pin_lnl_n = 0; }
+        HIP_OK(hipHostMalloc((void**)&S.pin_lnl, lnl_words * sizeof(double), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_lnl, S.pin_lnl, 0));
+        S.pin_lnl_n = lnl_words;
+    }
+    if (S.set_runs < (size_t)E) {
+        if (S.set_host) { (void)hipHostFree(S.set_host); S.set_host = nullptr; }
+        if (S.pin_count) { (void)hipHostFree(S.pin_count); S.pin_count = nullptr; }
+        S.set_runs = 0;
+        HIP_OK(hipHostMalloc((void**)&S.set_host, (size_t)3 * E * sizeof(int32_t), hipHostMallocDefault));
+        HIP_OK(hipHostMalloc((void**)&S.pin_count, (size_t)E * sizeof(int32_t), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_count, S.pin_count, 0));
+        S.set_runs = (size_t)E;
+    }
+    hipStream_t st = e->stream;
+    if (!draw) {
+        HIP_OK(hipMemcpyAsync(S.live_u.p, live_u, EL * n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.live_lnl.p, live_lnl, EL * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemcpyAsync(S.streams.p, streams, (size_t)E * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.it0.p, iteration, (size_t)E * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (mock_row) HIP_OK(hipMemcpyAsync(S.mock_row.p, mock_row, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(S.counters.p, 0, (size_t)E * sizeof(int64_t), st));
+    NsSetDev X{};
+    NsDev& D = X.run0;
+    if (S.box.upload(cap, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
+    D.live_u = S.live_u.p; D.live_lnl = S.live_lnl.p; D.rank = S.rank.p; D.surv = S.surv.p; D.killed = S.killed.p;
+    D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.lstar = S.lstar.p;
+    D.th = (vmx_ns::Thread*)S.th.p; D.slot = S.slot.p;
+    D.dead_u = S.dead_u.p; D.dead_lnl = S.dead_lnl.p; D.dead_n = S.dead_n.p;
+    D.host_word = S.dpin_word; D.host_lnl = S.dpin_lnl; D.counters = S.counters.p;
+    D.nlive = nlive; D.K = K; D.n = n; D.P = P; D.num_repeats = spec->num_repeats;
+    D.log_norm = spec->log_norm; D.seed = spec->seed; D.stream = 0;
+    X.active = S.set_ctl.p; X.heading = S.set_ctl.p + E; X.done = S.set_ctl.p + 2 * (size_t)E;
+    X.it0 = S.it0.p; X.streams = S.streams.p;
+    X.mock_row = mock_row ? S.mock_row.p : nullptr; X.mock = mock_row ? S.mock.p : nullptr;
+    X.count = S.set_count.p; X.host_count = S.dpin_count; X.rec_rows = (int32_t)rec_iter;
+    const int32_t* d_mock = mock_row ? S.mock.p : nullptr;
+
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
+    vmx_nested_stats R{};
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
+    double enqueue_s = 0.0;
+    std::vector<int64_t> rows_of(E, 0), rounds_of(E, 0);
+    std::vector<int32_t> phase(E, vmx_ns::OUT);
+    int32_t* active = S.set_host;
+    int32_t* heading = S.set_host + E;
+    int32_t* done = S.set_host + 2 * (size_t)E;
+    for (int q = 0; q < E; ++q) { status[q] = vmx_ns::GOING; done[q] = 0; active[q] = q; }
+    int A = E, H = 0;
+    // the lists and the iterations done go up on the stream: the host changes them only after it has waited for the stream
+    auto put_lists = [&]() -> int {
+        X.A = A;
+        HIP_OK(hipMemcpyAsync(S.set_ctl.p, S.set_host, (size_t)3 * E * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        return 0;
+    };
+    auto evaluate = [&](int total, bool from_kernel) -> int {
+        const auto t0 = std::chrono::steady_clock::now();
+        const int calls = L.evaluate(S.box.theta.p, total, S.box.chi2.p, S.box.status.p, d_mock, from_kernel);
+        if (calls < 0) return -2;
+        R.engine_calls += calls;
+        R.rows += total;
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    };
+    if (draw) {
+        if (put_lists()) return -2;
+        hipLaunchKernelGGL(k_ns_set_draw_live, dim3(A), dim3(NS_THREADS), 0, st, X);
+        HIP_OK(hipGetLastError());
+        if (evaluate(E * nlive, true)) return -2;
+        hipLaunchKernelGGL(k_ns_set_live_lnl, dim3(A), dim3(NS_THREADS), 0, st, X);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st));       // (the draw's wait: whether every run has a live point with a finite lnL)
+        R.host_waits += 1;
+        for (int q = 0; q < E; ++q) { rows_of[q] += nlive; status[q] = vmx_ns::start_status(S.pin_count[q]); }
+    }
+    A = vmx_ns::first_active(status, E, n_iterations, active, phase.data());
+    while (A > 0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        H = vmx_ns::heading_list(active, A, phase.data(), heading);
+        if (put_lists()) return -2;
+        if (H > 0) hipLaunchKernelGGL(k_ns_set_head, dim3(H), dim3(NS_THREADS), 0, st, X);
+        hipLaunchKernelGGL(k_ns_set_advance, dim3(A), dim3(NS_THREADS), 0, st, X);
+        hipLaunchKernelGGL(k_ns_set_emit, dim3(A), dim3(NS_THREADS), 0, st, X);
+        HIP_OK(hipGetLastError());
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the round's only wait: the total and the runs' counts, mapped words)
+        R.host_waits += 1;
+        R.rounds += 1;
+        const int total = S.pin_word[0];
+        if (total < 0 || (size_t)total > cap) return fail(-2, name + ": a round asked for more rows than its buffers hold");
+        if (total > 0 && evaluate(total, false)) return -2;
+        for (int a = 0; a < A; ++a) {
+            const int q = active[a];
+            const int32_t cnt = S.pin_count[q];
+            rounds_of[q] += 1;
+            rows_of[q] += cnt;
+            if (!vmx_ns::iteration_ended(cnt)) { phase[q] = vmx_ns::WALK; continue; }
+            done[q] += 1;
+            const double* word = S.pin_lnl + (size_t)q * ((size_t)nlive + K);
+            std::memcpy(live_lnl + (size_t)q * nlive, word, (size_t)nlive * sizeof(double));
+            const bool stopped = opt && opt->stop && opt->stop(opt->user, q, iteration[q] + done[q], word + nlive, live_lnl + (size_t)q * nlive);
+            phase[q] = vmx_ns::after_iteration(stopped, done[q], n_iterations, &status[q]);
+        }
+        A = vmx_ns::compact_active(active, A, phase.data());
+    }
+    // the runs that were entered come back; a run without a finite live lnL leaves its arrays as they were
+    std::vector<int64_t> own(E, 0);
+    for (int q = 0; q < E; ++q) {
+        if (status[q] == vmx_ns::NO_FINITE) continue;
+        const size_t o = (size_t)q * nlive;
+        HIP_OK(hipMemcpyAsync(live_u + o * n, S.live_u.p + o * n, (size_t)nlive * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(live_lnl + o, S.live_lnl.p + o, (size_t)nlive * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (done[q] == 0) continue;
+        const size_t r = (size_t)q * rec_rows, h = (size_t)q * n_iterations * K, rows = (size_t)done[q] * K;
+        HIP_OK(hipMemcpyAsync(dead_u + h * n, S.dead_u.p + r * n, rows * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(dead_lnl + h, S.dead_lnl.p + r, rows * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(dead_nlive + h, S.dead_n.p + r, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipMemcpyAsync(own.data(), S.counters.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    R.host_waits += 1;
+    for (int q = 0; q < E; ++q) {
+        iterations_done[q] = done[q];
+        iteration[q] += done[q];
+        if (per_run) { per_run[3 * q] = rows_of[q]; per_run[3 * q + 1] = own[q]; per_run[3 * q + 2] = rounds_of[q]; }
+        R.iterations += done[q];
+        R.rows_own_position += own[q];
+    }
     R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;

@@ -51,6 +51,25 @@
 //     threads        thread k walks with the factor of its start point's cluster; its end point inherits that cluster's id.
 //     record         a death carries the id the point held when it was killed.
 //
+//   a set of runs    (vmx_nested_run_many; the functions at the end of this header, tests/helpers/nested_set_driver.cpp) E such
+//                    runs, run e under the Philox key (seed, streams[e]), advanced together.  Nothing crosses runs except the
+//                    row offsets: run e is the run above on its stream, the same functions in the same order.
+//     phases         HEAD: the run's next iteration has to be headed (kill, whiten, start); WALK: some thread is asking; OUT: it
+//                    has left the set.  The active list holds the runs not OUT in ascending run order (first_active,
+//                    compact_active), the heading list those of them in HEAD, in the same order (heading_list).
+//     status         GOING (0): the call's iterations are used up; STOPPED (1): the stop callback ended the run; NO_FINITE (2):
+//                    with draw_live no live point has a finite lnL - the run is never entered (start_status).
+//     a set round    the heading list is headed (skipped when empty); every thread of every active run takes the answer of the
+//                    engine row it asked for last round and advances, and every run counts its requests; the requests are
+//                    packed into the engine rows [0, total) in ascending (run, thread) order, run active[a] from row
+//                    offset[a] = count[0] + ... + count[a - 1] (row_offsets: a sum in list order, no atomic decides a row); a run
+//                    whose count is 0 has finished its iteration: its end points take the killed slots in the same round.  The
+//                    host waits once, evaluates the rows when there are any, and for every run whose count was 0 adds one to
+//                    its iterations done, asks its stop callback and moves it to OUT or HEAD (after_iteration); the others
+//                    stay in WALK.  Runs do not wait for each other: a run whose iteration ended in round r is headed in
+//                    round r + 1.  The iteration index of run e is iteration[e] + iterations_done[e], its record row
+//                    iterations_done[e].
+//
 // Thread is a resumable state machine: advance(state, lnL of my last request) -> next request | done.  Every expression is the
 // separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are correctly rounded.
 #pragma once
@@ -471,6 +490,62 @@ VMX_HD inline double cluster_cov_entry(int a, int b, const double* u, const int3
         acc = acc + p;
     }
     return acc / (double)(size - 1);
+}
+
+// ---- a set of runs (vmx_nested_run_many): E independent runs advanced together; nothing below crosses runs but row_offsets
+constexpr int32_t HEAD = 0, WALK = 1, OUT = 2;
+constexpr int32_t GOING = 0, STOPPED = 1, NO_FINITE = 2;
+
+// after the draw: `finite` of the nlive drawn points have a finite lnL
+VMX_HD inline int32_t start_status(int64_t finite) { return finite > 0 ? GOING : NO_FINITE; }
+
+// the runs a call begins with, in ascending order: those with status GOING when there is an iteration to do; they are in HEAD,
+// the others OUT.  Returns their number.
+VMX_HD inline int first_active(const int32_t* status, int E, int64_t n_iterations, int32_t* active, int32_t* phase)
+{
+    int A = 0;
+    for (int e = 0; e < E; ++e) {
+        phase[e] = status[e] == GOING && n_iterations > 0 ? HEAD : OUT;
+        if (phase[e] != OUT) active[A++] = e;
+    }
+    return A;
+}
+
+// the active runs whose next iteration has to be headed, in the list's order.  Returns their number.
+VMX_HD inline int heading_list(const int32_t* active, int A, const int32_t* phase, int32_t* heading)
+{
+    int H = 0;
+    for (int a = 0; a < A; ++a)
+        if (phase[active[a]] == HEAD) heading[H++] = active[a];
+    return H;
+}
+
+// the first engine row of every active run from the runs' request counts, summed in list order.  Returns the total.
+VMX_HD inline int64_t row_offsets(const int32_t* count, int A, int64_t* offset)
+{
+    int64_t total = 0;
+    for (int a = 0; a < A; ++a) { offset[a] = total; total += count[a]; }
+    return total;
+}
+
+// the phase of a run after a round in which it asked for `count` rows: 0 ends its iteration (the host decides: after_iteration)
+VMX_HD inline bool iteration_ended(int32_t count) { return count == 0; }
+
+// the phase of a run whose iteration has just ended, `done` iterations into a call of n_iterations; *status moves to STOPPED
+// when its stop callback said so
+VMX_HD inline int32_t after_iteration(bool stopped, int64_t done, int64_t n_iterations, int32_t* status)
+{
+    if (stopped) { *status = STOPPED; return OUT; }
+    return done >= n_iterations ? OUT : HEAD;
+}
+
+// drop the runs that are OUT; the rest keep their (ascending) order and move up.  Returns the new number.
+VMX_HD inline int compact_active(int32_t* active, int A, const int32_t* phase)
+{
+    int B = 0;
+    for (int a = 0; a < A; ++a)
+        if (phase[active[a]] != OUT) active[B++] = active[a];
+    return B;
 }
 
 }  // namespace vmx_ns

@@ -158,6 +158,14 @@ class NestedStats(C.Structure):
                 ('const_hint', C.c_int32), ('lanes', C.c_int32)]
 
 
+NESTED_SET_STOP = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))
+
+
+class NestedSetOptions(C.Structure):
+    _fields_ = [('const_hint', C.c_int32), ('chunk', C.c_int32), ('lanes', C.c_int32), ('draw_live', C.c_int32),
+                ('stop', NESTED_SET_STOP), ('user', C.c_void_p)]
+
+
 VMX_NS_KNN = 8
 VMX_NS_MAX_CLUSTERS = 8
 VMX_NS_CLUSTER = 1
@@ -279,6 +287,9 @@ def load_library():
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
     lib.vmx_nested_cluster_points.argtypes = [C.c_int32, dptr, C.c_int32, C.c_int32, iptr, iptr, iptr, iptr, iptr, dptr, dptr]
+    lib.vmx_nested_run_many.argtypes = [C.c_void_p, C.POINTER(NestedSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
+                                        C.POINTER(C.c_int64), iptr, C.c_int32, dptr, dptr, iptr, iptr, C.POINTER(NestedSetOptions),
+                                        C.POINTER(NestedStats), C.POINTER(C.c_int64)]
     lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
                                 iptr, C.POINTER(SmcOptions), C.POINTER(SmcStats)]
     lib.vmx_smc_run_many.argtypes = [C.c_void_p, C.POINTER(SmcSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
@@ -320,7 +331,7 @@ def load_library():
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
-                                    SmcSpec, SmcOptions, SmcStats, NestedClusters)):
+                                    SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -352,7 +363,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1193,6 +1204,60 @@ class Engine:
             raise raised[0]
         m = int(stats.iterations) * K
         return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), _stats_dict(stats)
+
+    def nested_run_many(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, streams, n_iterations, threads, num_repeats,
+                        mock_rows=None, log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):
+        """Up to ``n_iterations`` iterations of each of E independent nested-sampling runs in one device run (include/vegamx.h:
+        vmx_nested_run_many): ``live_u`` [E, nlive, n] / ``live_lnl`` [E, nlive] the runs' state and ``iteration`` int64 [E] their
+        next iterations (all updated in place; a run without a finite live lnL keeps what it had), ``streams`` [E] the Philox
+        stream of every run, ``mock_rows`` [E] the pool row every run is compared with (None: the installed data); the rest as for
+        :meth:`nested_run`.  ``stop(run, iterations, dead_lnl [K], live_lnl [nlive])`` is asked after every iteration of every
+        run; a true answer ends that run.  Returns (dead: per run (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K]) for its m
+        iterations done, status int32 [E], iterations_done int32 [E], statistics); the statistics carry ``per_run`` int64
+        [E, 3]: rows evaluated, rows that were a thread's own position, set rounds the run took part in."""
+        _in_place(np.float64, live_u=live_u, live_lnl=live_lnl)
+        _in_place(np.int64, iteration=iteration)
+        if live_u.ndim != 3 or live_lnl.shape != live_u.shape[:2]:
+            raise ValueError('live_u [E, nlive, n], live_lnl [E, nlive]')
+        E, nlive = live_u.shape[:2]
+        cols, lo, hi, theta_fixed, _ = self._sampled_box(cols, lo, hi, theta_fixed, live_u=live_u.reshape(-1, live_u.shape[-1]),
+                                                         live_lnl=live_lnl.reshape(-1))
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if iteration.shape != (E,) or (streams is not None and streams.shape != (E,)) or \
+                (mock_rows is not None and mock_rows.shape != (E,)):
+            raise ValueError('iteration [E], streams [E], mock_rows [E]')
+        K, n_iterations = int(threads), max(0, int(n_iterations))
+        rows = n_iterations * max(K, 0)
+        dead_u, dead_lnl, dead_n = np.empty((E, rows, cols.size)), np.empty((E, rows)), np.empty((E, rows), dtype=np.int32)
+        status, done, per = np.zeros(E, dtype=np.int32), np.zeros(E, dtype=np.int32), np.zeros((E, 3), dtype=np.int64)
+        spec = NestedSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), nlive, K, int(num_repeats), 0, float(log_norm),
+                          int(seed), 0, _dp(theta_fixed))
+        raised = []
+
+        def _stop(_user, run, iterations, p_dead, p_live):
+            try:
+                return 1 if stop(int(run), int(iterations), np.ctypeslib.as_array(p_dead, (K,)),
+                                 np.ctypeslib.as_array(p_live, (nlive,))) else 0
+            except BaseException as exc:        # (an exception cannot cross the C frames: end the run, raise it afterwards)
+                raised.append(exc)
+                return 1
+
+        callback = NESTED_SET_STOP(_stop) if stop is not None else NESTED_SET_STOP()
+        opt = NestedSetOptions(int(const_hint), int(chunk), int(lanes), 1 if draw_live else 0, callback, None)
+        stats = NestedStats()
+        self._check(self.lib.vmx_nested_run_many(
+            self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), _dp(live_u), _dp(live_lnl), iteration.ctypes.data_as(C.POINTER(C.c_int64)),
+            _ip(status), n_iterations, _dp(dead_u), _dp(dead_lnl), _ip(dead_n), _ip(done), C.byref(opt), C.byref(stats),
+            per.ctypes.data_as(C.POINTER(C.c_int64))))
+        if raised:
+            raise raised[0]
+        dead = [(dead_u[e, :int(done[e]) * K].copy(), dead_lnl[e, :int(done[e]) * K].copy(), dead_n[e, :int(done[e]) * K].copy())
+                for e in range(E)]
+        return dead, status, done, dict(_stats_dict(stats), per_run=per)
 
     def nested_cluster_points(self, u, prev_id, next_id):
         """:func:`cluster_points` of this engine's device."""

@@ -977,7 +977,8 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
     :class:`EnsembleSet` (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`); writes the getdist chains ``<name>_mock<m>.txt``
     with one ``<name>.paramnames`` and the summary table ``mock_posteriors.fits``.  ``[SMC] mocks = M``: the same mocks as one
     :class:`vega_amd.smc.SMCSet`; every mock's three files ``<name>_mock<m>.txt`` / ``.paramnames`` / ``.stats`` (the evidence)
-    and the table.  Returns the set."""
+    and the table.  ``[Nested] mocks = M``: the same mocks as one :class:`vega_amd.nested.NestedSet`, with the same files per mock.
+    Returns the set."""
     mc = vega.analysis
     scale = None
     if vega._use_global_cov and 'global_cov_rescale' in control:
@@ -991,6 +992,15 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
                                   sampler='smc', particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'])
         for m in range(sampler.E):
             sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')
+        mc.write_mock_posteriors(cfg['path'])
+        return sampler
+    if cfg['sampler'] == 'Nested':
+        sampler = mc.sample_mocks_nested(mocks=mocks, seed=cfg['seed'], scale=scale, sample_params=sample_params,
+                                         driver=cfg['driver'], num_live=cfg['num_live'], num_repeats=cfg['num_repeats'],
+                                         threads=cfg['threads'], precision=cfg['precision'], max_iterations=cfg['max_iterations'])
+        for m in range(sampler.E):
+            if sampler.status[m] != 2:          # (a mock without a finite live lnL has nothing to write: its row of the table says so)
+                sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')
         mc.write_mock_posteriors(cfg['path'])
         return sampler
     sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],

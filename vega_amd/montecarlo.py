@@ -489,10 +489,32 @@ class MonteCarlo:
         settings; ``walkers`` / ``steps`` / ``burn`` / ``thin`` are not read: every run ends by itself at beta = 1).  It keeps in
         ``mc_posteriors``: names, ``mean`` / ``sd`` / ``covariance`` of the N samples, ``log_z``, ``log_z_err`` (NaN for a run that
         failed), ``stages``, ``status`` (:class:`SMCSet`), ``acceptance`` and the settings; ``mc_chains`` holds the samples
-        [M, N, n] and ``mc_chain_lnl`` their lnL."""
-        from .ensemble import EnsembleSet, SampledBox
+        [M, N, n] and ``mc_chain_lnl`` their lnL.  (Nested sampling of every mock: :meth:`sample_mocks_nested`.)"""
         if sampler not in ('ensemble', 'smc'):
             raise ValueError("sample_mocks: sampler 'ensemble' or 'smc'")
+        return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
+                                  fiducial_model, sampler, particles, ess, sweeps)
+
+    def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
+                            max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
+                            fiducial_model=None):
+        """The evidence and a weighted posterior of every Monte-Carlo mock by nested sampling, M runs advanced together in one
+        device run (:class:`vega_amd.nested.NestedSet`: run m on mock m and stream m; ``num_live``, ``num_repeats``, ``threads``,
+        ``precision``, ``max_iterations`` its settings; every run ends on its own termination test).  The mocks, ``seed``,
+        ``scale``, ``sample_params`` and ``driver`` as for :meth:`sample_mocks`.  It keeps in ``mc_posteriors``: ``sampler`` =
+        'nested', names, the weighted ``mean`` / ``sd`` / ``covariance``, ``log_z``, ``log_z_err``, ``info`` (NaN for a run
+        without a finite live lnL), ``iterations``, ``status`` and the settings; with ``keep_chains`` ``mc_chains`` holds per mock
+        the tuple (points, lnL, weights) of its samples and ``mc_chain_lnl`` their lnL.  Returns the set."""
+        return self._sample_mocks(num_mocks, mocks, None, 0, None, 1, seed, scale, sample_params, driver, keep_chains, fiducial_model,
+                                  'nested', None, 0.5, None, num_live=num_live, num_repeats=num_repeats, threads=threads,
+                                  precision=precision, max_iterations=max_iterations)
+
+    def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
+                      fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
+                      max_iterations=None):
+        """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
+        kind ``sampler`` names, its run and the summaries."""
+        from .ensemble import EnsembleSet, SampledBox
         vega = self.vega
         prob = vega.problem
         if sample_params is None:
@@ -515,8 +537,8 @@ class MonteCarlo:
         if num_mocks is not None and int(num_mocks) != M:
             raise ValueError(f'sample_mocks: num_mocks = {num_mocks}, but {M} mocks were passed')
         n = SampledBox(vega, sample_params).n
-        smc = sampler == 'smc'
-        if not smc:
+        smc, nested = sampler == 'smc', sampler == 'nested'
+        if not smc and not nested:
             walkers = max(32, 2 * n) if walkers is None else int(walkers)
             steps, thin = int(steps), int(thin)
             burn = steps // 3 if burn is None else int(burn)
@@ -529,6 +551,10 @@ class MonteCarlo:
             from .smc import SMCSet
             sampler = SMCSet(vega, M, particles=1024 if particles is None else int(particles), mock_rows=np.arange(M), ess=ess,
                              sweeps=sweeps, seed=seed, driver=driver, sample_params=sample_params)
+        elif nested:
+            from .nested import NestedSet
+            sampler = NestedSet(vega, M, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
+                                mock_rows=np.arange(M), driver=driver, max_iterations=max_iterations, sample_params=sample_params)
         else:
             sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
                                   sample_params=sample_params)
@@ -538,7 +564,7 @@ class MonteCarlo:
             for name in rescaled:
                 # (marginalize-in-fit: chi2_matrix keeps the projector of the unscaled covariance, as in _fit_mocks)
                 eng.set_invcov(name, prob.items[name].chi2_matrix / scales[name])
-            if smc:
+            if smc or nested:
                 sampler.run()
             else:
                 sampler.run(steps)
@@ -558,6 +584,26 @@ class MonteCarlo:
             self.mc_chains = pts if keep_chains else None
             self.mc_chain_lnl = lnl if keep_chains else None
             return sampler
+        if nested:
+            found = sampler.samples()
+            log_z, err = sampler.log_evidence()
+            mean, sd, cov = np.full((M, n), np.nan), np.full((M, n), np.nan), np.full((M, n, n), np.nan)
+            for m, part in enumerate(found):
+                if part is None:
+                    continue
+                pts, _, w = part
+                mean[m] = w @ pts
+                dev = pts - mean[m]
+                cov[m] = (w[:, None] * dev).T @ dev / (1.0 - np.sum(w * w))         # (the unbiased estimate under reliability weights)
+                sd[m] = np.sqrt(np.diag(cov[m]))
+            self.mc_posteriors = dict(
+                sampler='nested', names=list(sampler.names), mean=mean, sd=sd, covariance=cov, log_z=log_z, log_z_err=err,
+                info=sampler.information(), iterations=sampler.iteration.copy(), status=sampler.status.copy(),
+                num_live=sampler.num_live, num_repeats=sampler.num_repeats, threads=sampler.threads, precision=sampler.precision,
+                seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+            self.mc_chains = found if keep_chains else None
+            self.mc_chain_lnl = [None if part is None else part[1] for part in found] if keep_chains else None
+            return sampler
         first = burn // thin
         post = sampler.get_chain(discard=first)
         flat = post.reshape(M, -1, n)
@@ -576,8 +622,10 @@ class MonteCarlo:
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
         ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  After
         ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
-        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED``.  Returns the
-        path."""
+        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED``; after
+        ``sample_mocks_nested`` ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``info``, ``iterations``,
+        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``NUMLIVE``, ``NREPEATS``, ``THREADS``, ``PRECISN``, ``SEED``.
+        Returns the path."""
         from pathlib import Path
         from . import fitslite
         post = getattr(self, 'mc_posteriors', None)
@@ -594,6 +642,14 @@ class MonteCarlo:
                      ('stages', 'K', np.asarray(post['stages'], dtype=np.int64)), ('status', 'K', np.asarray(post['status'], dtype=np.int64)),
                      cov_col]
             header = {'SAMPLER': 'SMC', 'PARTICLE': post['particles'], 'ESS': post['ess'], 'SWEEPS': post['sweeps'], 'SEED': post['seed']}
+        elif post.get('sampler') == 'nested':
+            for j, nm in enumerate(names):
+                cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j])]
+            cols += [('log_z', 'D', post['log_z']), ('log_z_err', 'D', post['log_z_err']), ('info', 'D', post['info']),
+                     ('iterations', 'K', np.asarray(post['iterations'], dtype=np.int64)),
+                     ('status', 'K', np.asarray(post['status'], dtype=np.int64)), cov_col]
+            header = {'SAMPLER': 'NESTED', 'NUMLIVE': post['num_live'], 'NREPEATS': post['num_repeats'], 'THREADS': post['threads'],
+                      'PRECISN': post['precision'], 'SEED': post['seed']}
         else:
             for j, nm in enumerate(names):
                 cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]

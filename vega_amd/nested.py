@@ -410,6 +410,130 @@ def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats,
     return np.concatenate(dead_u), np.concatenate(dead_lnl), np.concatenate(dead_n), iteration, st
 
 
+# ------------------------------------------------------------------ a set of runs (vmx_nested.h: "a set of runs")
+HEAD, WALK, OUT = 0, 1, 2
+GOING, STOPPED, NO_FINITE = 0, 1, 2
+
+
+def first_active(status, n_iterations):
+    """vmx_ns::first_active: (the runs a call begins with, ascending; the phase of every run)."""
+    phase = np.where((np.asarray(status) == GOING) & (n_iterations > 0), HEAD, OUT).astype(np.int32)
+    return [int(e) for e in np.flatnonzero(phase != OUT)], phase
+
+
+def heading_list(active, phase):
+    """vmx_ns::heading_list: the active runs whose next iteration has to be headed, in the list's order."""
+    return [e for e in active if phase[e] == HEAD]
+
+
+def row_offsets(count):
+    """vmx_ns::row_offsets: (the first engine row of every active run, the total) from the runs' request counts in list order."""
+    offset, total = [], 0
+    for c in count:
+        offset.append(total)
+        total += int(c)
+    return offset, total
+
+
+def after_iteration(stopped, done, n_iterations):
+    """vmx_ns::after_iteration: (the phase, the status) of a run whose iteration has just ended."""
+    if stopped:
+        return OUT, STOPPED
+    return (OUT if done >= n_iterations else HEAD), GOING
+
+
+def compact_active(active, phase):
+    """vmx_ns::compact_active: the runs not OUT keep their order and move up."""
+    return [e for e in active if phase[e] != OUT]
+
+
+def python_iterations_many(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, streams, evaluate, stop=None, draw=False,
+                           watch=None):
+    """Up to ``n_iterations`` iterations of each of E runs in NumPy (vmx_nested_run_many restated over :func:`iteration_head` and
+    :class:`Threads`): ``live_u`` [E, nlive, n], ``live_lnl`` [E, nlive], ``iteration`` int64 [E] the runs' state, updated in place
+    (a run without a finite live lnL keeps what it had at entry), ``streams`` [E].  A set round heads the runs in HEAD, advances
+    every thread of every active run by the answer of the row it asked for, packs the requests in ascending (run, thread) order
+    (:func:`row_offsets`), ends the iteration of the runs that ask for nothing and hands the rows to ``evaluate(rows_u [R, n], runs
+    [R])`` -> lnL [R] (``runs``: the run of every row; not called when R = 0); a run whose iteration ended is asked
+    ``stop(run, iterations, dead_lnl [K], live_lnl [nlive])`` and headed again in the next round.  ``draw``: the live points are
+    drawn and evaluated first.  ``watch(round, state)`` sees every round before the host's turn.  Returns (dead: per run
+    (dead_u, dead_lnl, dead_nlive) of the iterations done, status int32 [E]: 0 still going, 1 stopped, 2 no live point with a
+    finite lnL; iterations_done int32 [E]; statistics with ``per_run`` int64 [E, 3]: rows evaluated, own-position rows, set
+    rounds the run took part in)."""
+    E, nlive, n = live_u.shape
+    entry = (live_u.copy(), live_lnl.copy())
+    per = np.zeros((E, 3), dtype=np.int64)
+    status = np.zeros(E, dtype=np.int32)
+    done = np.zeros(E, dtype=np.int32)
+    dead = [([], [], []) for _ in range(E)]
+    st = dict(iterations=0, rounds=0, rows=0, rows_own_position=0)
+    if draw:
+        for e in range(E):
+            live_u[e] = draw_live(nlive, n, seed, int(streams[e]))
+        first = np.asarray(evaluate(live_u.reshape(E * nlive, n), np.repeat(np.arange(E), nlive)), dtype=np.float64).reshape(E, nlive)
+        per[:, 0] += nlive
+        st['rows'] += E * nlive
+        for e in range(E):
+            live_lnl[e] = first[e]
+            status[e] = GOING if np.any(first[e] > -np.inf) else NO_FINITE
+    active, phase = first_active(status, n_iterations)
+    heads, T, answer = {}, {}, {}
+    while active:
+        heading = heading_list(active, phase)
+        for e in heading:
+            it = int(iteration[e]) + int(done[e])
+            head = heads[e] = iteration_head(live_u[e], live_lnl[e], K, it, seed, int(streams[e]))
+            killed = head['killed']
+            dead[e][0].append(live_u[e][killed].copy())
+            dead[e][1].append(live_lnl[e][killed].copy())
+            dead[e][2].append(nlive - np.arange(K, dtype=np.int32))
+            T[e] = Threads(live_u[e][head['start']], live_lnl[e][head['start']], head['C'], head['lstar'], it, num_repeats, seed,
+                           int(streams[e]))
+            answer[e] = np.full(K, -np.inf)
+            phase[e] = WALK
+        requests, count = {}, []
+        for e in active:
+            requests[e] = T[e].requests(T[e].advance(answer[e]))
+            count.append(requests[e][0].size)
+        offset, total = row_offsets(count)
+        for e, c in zip(active, count):
+            per[e, 0] += c
+            per[e, 1] += requests[e][2]
+            per[e, 2] += 1
+            if c == 0:
+                killed = heads[e]['killed']
+                live_u[e][killed] = T[e].x
+                live_lnl[e][killed] = T[e].lnl
+        st['rounds'] += 1
+        st['rows'] += total
+        if watch is not None:
+            watch(st['rounds'] - 1, dict(active=list(active), heading=list(heading), count=list(count), offset=list(offset), total=total,
+                                         threads=T, requests=requests, phase=phase.copy()))
+        if total > 0:
+            lnl = np.asarray(evaluate(np.concatenate([requests[e][1] for e in active], axis=0),
+                                      np.repeat(np.array(active, dtype=np.int64), count)), dtype=np.float64)
+        for e, c, o in zip(active, count, offset):
+            if c > 0:
+                answer[e] = np.full(K, -np.inf)
+                answer[e][requests[e][0]] = lnl[o:o + c]
+                continue
+            done[e] += 1
+            stopped = stop is not None and bool(stop(e, int(iteration[e]) + int(done[e]), dead[e][1][-1], live_lnl[e]))
+            phase[e], status[e] = after_iteration(stopped, int(done[e]), n_iterations)
+        active = compact_active(active, phase)
+    out = []
+    for e in range(E):
+        if status[e] == NO_FINITE:
+            live_u[e], live_lnl[e] = entry[0][e], entry[1][e]
+        iteration[e] += int(done[e])
+        if done[e] == 0:
+            out.append((np.empty((0, n)), np.empty(0), np.empty(0, dtype=np.int32)))
+        else:
+            out.append(tuple(np.concatenate(part) for part in dead[e]))
+    st.update(iterations=int(done.sum()), rows_own_position=int(per[:, 1].sum()), per_run=per)
+    return out, status, done, st
+
+
 # ------------------------------------------------------------------ evidence (host, both drivers)
 def _logsumexp(a):
     a = np.asarray(a, dtype=np.float64)
@@ -668,13 +792,258 @@ class NestedSampler(E.EngineSampler, NestedRun):
                          **self._write_extra(derived, print_func, self.derived))
 
 
+class NestedRunSet:
+    """E independent nested-sampling runs over ``loglike(rows_u [R, n], runs [R]) -> lnL [R]`` (``runs``: the run every row belongs
+    to) advanced together by :func:`python_iterations_many`: run e is the :class:`NestedRun` on the Philox stream ``streams[e]``
+    (default ``range(E)``), with its own dead record, termination test and evidence (``runs[e]``).  :class:`NestedSet` puts the
+    engine behind it.  ``status`` [E]: 0 the run goes on, 1 its termination test ended it, 2 no drawn live point has a finite lnL
+    (such a run is left out; the others are not affected)."""
+
+    def __init__(self, loglike, n, runs, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, streams=None,
+                 max_iterations=None, max_batch=None, clustering=False):
+        if clustering:
+            raise ValueError('clustering is not part of a set of nested runs: run a NestedSampler(clustering=True) for each')
+        self.loglike = loglike
+        self.E = int(runs)
+        if self.E < 1:
+            raise ValueError('runs: at least one')
+        self.streams = np.arange(self.E, dtype=np.uint64) if streams is None else np.array(streams, dtype=np.uint64)
+        if self.streams.shape != (self.E,):
+            raise ValueError(f'streams: one entry for each of the {self.E} runs')
+        self.runs = [NestedRun(None, n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
+                               stream=int(st), max_iterations=max_iterations, max_batch=max_batch) for st in self.streams]
+        probe = self.runs[0]
+        self.n, self.num_live, self.num_repeats, self.threads = probe.n, probe.num_live, probe.num_repeats, probe.threads
+        self.precision, self.seed, self.max_iterations = probe.precision, probe.seed, probe.max_iterations
+        self.reset()
+
+    def reset(self):
+        for run in self.runs:
+            run.reset()
+        self.status = np.zeros(self.E, dtype=np.int32)
+        self._drawn = False
+        self.stats = dict(iterations=0, rounds=0, rows=0, rows_own_position=0, engine_calls=0, host_waits=0, seconds=0.0,
+                          seconds_enqueuing=0.0, calls=0, per_run=np.zeros((self.E, 3), dtype=np.int64))
+
+    @property
+    def iteration(self):
+        """[E]: the iterations every run has done."""
+        return np.array([run.iteration for run in self.runs], dtype=np.int64)
+
+    @property
+    def finished(self):
+        """[E]: the run's termination test (the precision criterion, or ``max_iterations``) is met."""
+        return np.array([run.terminated for run in self.runs], dtype=bool)
+
+    # ---- drivers
+    def _evaluate(self, rows_u, runs):
+        return np.asarray(self.loglike(rows_u, runs), dtype=np.float64)
+
+    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw):
+        """One call of the driver over the runs ``idx`` (their state stacked, updated in place): what
+        :func:`python_iterations_many` returns."""
+        return python_iterations_many(live_u, live_lnl, iteration, n_iterations, self.threads, self.num_repeats, self.seed,
+                                      self.streams[idx], lambda rows, runs: self._evaluate(rows, idx[runs]), stop, draw=draw)
+
+    def _advance(self, idx, n_iterations):
+        """Up to ``n_iterations`` iterations of each of the runs ``idx``, as a set of their own; returns the statistics."""
+        draw = not self._drawn
+        nlive, n = self.num_live, self.n
+        if draw:
+            live_u, live_lnl = np.zeros((idx.size, nlive, n)), np.zeros((idx.size, nlive))
+        else:
+            live_u = np.ascontiguousarray(np.stack([self.runs[e].live_u for e in idx]))
+            live_lnl = np.ascontiguousarray(np.stack([self.runs[e].live_lnl for e in idx]))
+        iteration = np.array([self.runs[e].iteration for e in idx], dtype=np.int64)
+
+        def stop(a, iterations, dead_lnl, live):
+            return self.runs[idx[a]]._stop(iterations, dead_lnl, live)
+
+        dead, status, done, st = self._drive(idx, live_u, live_lnl, iteration, n_iterations, stop, draw)
+        self._drawn = True
+        per = np.zeros((self.E, 3), dtype=np.int64)
+        per[idx] = st['per_run']
+        for a, e in enumerate(idx):
+            run = self.runs[e]
+            self.status[e] = status[a]
+            if status[a] == NO_FINITE:
+                continue
+            run.live_u, run.live_lnl, run.iteration = live_u[a].copy(), live_lnl[a].copy(), int(iteration[a])
+            if done[a] > 0:
+                run._dead_u.append(dead[a][0])
+                run._dead_lnl.append(dead[a][1])
+                run._dead_n.append(dead[a][2])
+            run.stats['iterations'] += int(done[a])
+            run.stats['rows'] += int(per[e, 0])
+            run.stats['rows_own_position'] += int(per[e, 1])
+            run.stats['rounds'] += int(per[e, 2])
+            run.stats['calls'] += 1
+        return dict(st, per_run=per)
+
+    def run(self, iterations=None):
+        """Every run to its own termination (``iterations`` None: the precision criterion or ``max_iterations``, run by run), or
+        exactly ``iterations`` more iterations of every run, whatever the criterion says (``finished`` still reports it); the set
+        does not depend on how it is cut."""
+        t0 = time.perf_counter()
+        for run in self.runs:
+            run._to_termination = iterations is None
+        per_call = max(1, 65536 // self.threads)        # (the dead record of a call is allocated up front)
+        left = None if iterations is None else int(iterations)
+        while True:
+            going = self.status != NO_FINITE
+            if iterations is None:
+                going &= ~self.finished
+                if self.max_iterations is not None:
+                    going &= self.iteration < self.max_iterations
+            idx = np.flatnonzero(going)
+            if idx.size == 0:
+                break
+            if iterations is None:
+                call = per_call if self.max_iterations is None else min(per_call, int(self.max_iterations - self.iteration[idx].min()))
+            else:
+                call = min(per_call, left)
+                left -= call
+            if call <= 0 and self._drawn:
+                break
+            st = self._advance(idx, max(call, 0))
+            for key, val in st.items():
+                if key in ('lanes', 'const_hint'):      # (what the engine ran with)
+                    self.stats[key] = val
+                elif key in self.stats and key != 'seconds':
+                    self.stats[key] = self.stats[key] + val
+            self.stats['calls'] += 1
+            if iterations is not None and left <= 0:
+                break
+        self.stats['seconds'] += time.perf_counter() - t0
+        return self
+
+    # ---- results
+    def _ran(self):
+        if not self._drawn:
+            raise ValueError('nothing has run yet')
+
+    def log_evidence(self):
+        """(log Z [E], its error sqrt(H / num_live) [E]); NaN for a run without a finite live lnL."""
+        self._ran()
+        out = np.full((2, self.E), np.nan)
+        for e, run in enumerate(self.runs):
+            if self.status[e] != NO_FINITE:
+                out[:, e] = run.log_evidence()
+        return out[0], out[1]
+
+    def information(self):
+        """H [E]; NaN for a run without a finite live lnL."""
+        self._ran()
+        return np.array([run.information() if self.status[e] != NO_FINITE else np.nan for e, run in enumerate(self.runs)])
+
+    def dead(self, e):
+        """The dead record of run ``e``: (u [N, n], lnL [N], live count [N])."""
+        return self.runs[int(e)].dead()
+
+    def to_physical(self, u):
+        return u
+
+    def samples(self):
+        """Per run (points [N_e, n], lnL [N_e], weights [N_e] summing to 1): its dead points in order of death, then its live
+        points; None for a run without a finite live lnL."""
+        self._ran()
+        out = []
+        for e, run in enumerate(self.runs):
+            if self.status[e] == NO_FINITE:
+                out.append(None)
+                continue
+            pts, lnl, w = run.samples()
+            out.append((self.to_physical(pts), lnl, w))
+        return out
+
+
+class NestedSet(E.EngineSampler, NestedRunSet):
+    """E independent nested-sampling runs of ``vega`` over its sampled parameters, advanced together: one host wait per set round
+    for all of them, the requests of all runs packed into one stream of engine rows (``'device'``: vmx_nested_run_many, one
+    work-group per run; ``'python'``: :func:`python_iterations_many` over ``chi2_batch_device``, cut into the same chunks).  Run e
+    is on the Philox stream ``streams[e]`` (default ``range(E)``) and is the run ``NestedSampler(..., seed=seed,
+    stream=streams[e])`` makes - up to the last bits of lnL where the engine's batches are shaped differently (DESIGN section
+    6h).  ``mock_rows`` [E]: the row of the installed mock pools every run is compared with - log Z and a weighted posterior per
+    Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks_nested`); None: every run reads the data the interface has
+    installed - replicas of one run (:func:`vega_amd.replicas.merge_nested`).  Every run ends on its own termination test.
+    Clustering is not part of a set.  An engine group takes ``'python'``."""
+
+    def __init__(self, vega, runs, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, streams=None, mock_rows=None,
+                 driver='device', max_iterations=None, chunk=0, lanes=0, const_hint=-1, sample_params=None, clustering=False):
+        if clustering:
+            raise ValueError('clustering is not part of a set of nested runs: run a NestedSampler(clustering=True) for each')
+        n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        NestedRunSet.__init__(self, None, n, runs, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision,
+                              seed=seed, streams=streams, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
+        self.mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
+        if self.mock_rows is not None and self.mock_rows.shape != (self.E,):
+            raise ValueError(f'mock_rows: one entry for each of the {self.E} runs')
+        if self.mock_rows is not None and np.any(self.mock_rows < 0):
+            raise ValueError('mock_rows: rows of the installed mock pools, none negative')
+
+    def to_physical(self, u):
+        return E.EngineSampler.to_physical(self, u)
+
+    def _evaluate(self, rows_u, runs):
+        rows_t = np.repeat(self._theta[None, :], rows_u.shape[0], axis=0)
+        rows_t[:, self.cols] = self.to_physical(rows_u)
+        return lnl_of(0, self._rows.chi2(rows_t, None if self.mock_rows is None else self.mock_rows[runs]), self.log_norm())
+
+    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw):
+        vega = self.vega
+        self._begin_advance(lambda: draw_live(1, self.n, self.seed, int(self.streams[0]))[0], 'nested_run_many')
+        if self.driver == 'python':
+            with self._engine_rows() as self._rows:
+                try:
+                    dead, status, done, st = NestedRunSet._drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw)
+                finally:
+                    calls, self._rows = self._rows.calls, None
+            return dead, status, done, dict(st, engine_calls=calls, host_waits=calls)
+        vega._sync_monte_carlo()
+        return vega.engine.nested_run_many(
+            self.cols, self.lo, self.hi, self._theta, live_u, live_lnl, iteration, self.streams[idx], n_iterations, self.threads,
+            self.num_repeats, mock_rows=None if self.mock_rows is None else self.mock_rows[idx], log_norm=self.log_norm(),
+            seed=self.seed, const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=stop)
+
+    def member(self, e):
+        """Run ``e`` as a sampler that has run: :class:`NestedSampler`'s result methods (``log_evidence``, ``information``,
+        ``samples``, ``dead``, ``derived``, ``write``) over copies of its part of the set's state.  Read-only: it cannot be
+        advanced."""
+        if not 0 <= int(e) < self.E:
+            raise IndexError(f'member: 0 .. {self.E - 1}')
+        e = int(e)
+        run = self.runs[e]
+        m = NestedSampler(self.vega, num_live=self.num_live, num_repeats=self.num_repeats, threads=self.threads,
+                          precision=self.precision, seed=self.seed, driver=self.driver_asked,
+                          sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))), values=self.values,
+                                             errors=self.errors),
+                          stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint,
+                          max_iterations=self.max_iterations)
+        m.driver = self.driver
+        m.run = m.reset = _read_only
+        if run.live_u is not None:
+            m.live_u, m.live_lnl = run.live_u.copy(), run.live_lnl.copy()
+        m.iteration, m.terminated = run.iteration, run.terminated
+        m._dead_u, m._dead_lnl, m._dead_n = list(run._dead_u), list(run._dead_lnl), list(run._dead_n)
+        m._log_x, m._log_z_dead = run._log_x, run._log_z_dead
+        m.stats = dict(run.stats)
+        m.status = int(self.status[e])
+        return m
+
+
+def _read_only(*args, **kwargs):
+    raise RuntimeError('a member of a NestedSet is read-only: advance the set')
+
+
 def nested_settings(main_config, sample_params):
     """The ``[Nested]`` settings of a main config with ``sampler = Nested`` (called by
     :func:`vega_amd.ensemble.sampler_settings`, which has checked ``run_sampler``): {sampler, path, name, num_live, num_repeats,
     precision, seed, threads, driver, max_iterations}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them.``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
     mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default.
     ``do_clustering`` / ``cluster_posteriors`` (the reference's keys, both False when absent and then not in the settings;
-    ``cluster_posteriors`` implies ``do_clustering`` and is refused with ``replicas > 1``)."""
+    ``cluster_posteriors`` implies ``do_clustering`` and is refused with ``replicas > 1``).  ``mocks = M``: log Z and a weighted
+    posterior for each of M Monte-Carlo mocks in one run (the conditions of ``[Ensemble] mocks``); ``together = True`` with
+    ``replicas``: a rank's replicas advance as one :class:`NestedSet`; neither combines with ``do_clustering``."""
     sec, limits, out = E.section_settings(main_config, sample_params, 'Nested', name='nested')
     n = len(limits)
     out.update(num_live=sec.getint('num_live', 25 * n), num_repeats=sec.getint('num_repeats', 5 * n),
@@ -688,6 +1057,15 @@ def nested_settings(main_config, sample_params):
         if out.get('replicas', 1) > 1:
             raise ValueError('[Nested] cluster_posteriors and replicas > 1 do not combine: the cluster ids of different replicas '
                              'are unrelated')
+    if 'mocks' in sec:
+        out['mocks'] = E._parse_mocks(sec, main_config, 'Nested', 'a nested run')
+    if 'together' in sec:
+        try:
+            out['together'] = sec.getboolean('together')
+        except ValueError:
+            raise ValueError('[Nested] together: True or False') from None
+    if out.get('do_clustering') and (out.get('mocks') or out.get('together')):
+        raise ValueError('[Nested] do_clustering does not combine with mocks or together: clustering is not part of a set of runs')
     if not n + 2 <= out['num_live'] <= MAX_LIVE:
         raise ValueError(f'[Nested] num_live: {n + 2} .. {MAX_LIVE} for {n} sampled parameters')
     if out['threads'] is not None and not 1 <= out['threads'] <= out['num_live'] - n - 1:

@@ -499,6 +499,17 @@ def run_replicas(vega, cfg, sample_params, group, print_func=print):
                                  + ('no particle has a finite log-likelihood' if both.status[k] == 2 else
                                     'the temperature ladder cannot advance: fewer than ess N particles carry weight'))
         ready = [both.member(k) for k in range(hi - lo)]
+    if cfg.get('together', False) and cfg['sampler'] == 'Nested' and hi > lo:
+        # the rank's replicas as one set: one host wait per set round for all of them, their requests packed into one stream of rows
+        from .nested import NestedSet
+        both = NestedSet(vega, hi - lo, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
+                         precision=cfg['precision'], seed=cfg['seed'], streams=range(lo, hi), driver=cfg['driver'],
+                         max_iterations=cfg['max_iterations'], sample_params=sample_params)
+        both.run()
+        for k in range(hi - lo):        # (a single run without a finite live lnL cannot be weighed: neither can the set's)
+            if both.status[k] == 2:
+                raise ValueError(f'Nested: replica {lo + k} cannot go on: no live point has a finite log-likelihood')
+        ready = [both.member(k) for k in range(hi - lo)]
     for r in range(lo, hi):
         if ready:
             sampler = ready[r - lo]
