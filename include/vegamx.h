@@ -12,7 +12,7 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_many) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_phantoms, vmx_nested_run_many) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
  * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
@@ -159,7 +159,7 @@ const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
- * 18 vmx_nested_set_options): lets a foreign binding verify its struct layout at load time. */
+ * 18 vmx_nested_set_options, 19 vmx_nested_phantoms): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -561,6 +561,40 @@ typedef struct {
 int vmx_nested_run_clustered(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                              int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
                              const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters);
+/* The same run (with or without clustering) keeping the accepted points inside the threads' walks - the reference's [Polychord]
+ * boost_posterior; the rule, pinned: vega_amd/csrc/vmx_nested.h "boost".  Every thread of an iteration makes num_repeats slice
+ * steps and only its end point joins the live points; the num_repeats - 1 accepted points before it were evaluated under the
+ * same constraint and are each a uniform draw from the contour.  k_ns_advance_phantoms / k_ns_advance_phantoms_clustered are
+ * k_ns_advance / k_ns_advance_clustered with one more step: after a thread's advance its lane asks vmx_ns::phantom_of and
+ * vmx_ns::phantom_kept, a second prefix scan gives the kept points of the round their places behind a running count (one
+ * work-group: no atomic decides a place), and the lanes write the record one column per lane.  The base run - dead record, live
+ * points, statistics, random streams - is bit for bit the one without `phantoms`; no likelihood row is added.
+ *   clusters  NULL: what vmx_nested_run runs; else as for vmx_nested_run_clustered
+ *   phantoms  fraction: every phantom point (k, t, r) is kept iff u01(word 0 of the Philox block (k, t, r, 3)) < fraction;
+ *                       0 (or phantoms NULL) runs exactly vmx_nested_run / vmx_nested_run_clustered and touches nothing in the struct
+ *             capacity: rows of the arrays below, at least n_iterations K (num_repeats - 1): what the call can keep at the most
+ *             u [capacity][n], lnl, birth [capacity], iteration (int64), thread, repeat [capacity] host: the kept points in the
+ *                       order they were accepted (round by round, threads ascending within a round: sort by the tags for the
+ *                       canonical order), their lnL, the L* they were accepted under and (iteration, thread, repeat)
+ *             cluster [capacity] host: the id of the thread's cluster, what its end point inherits; read with clustering only
+ *                       (then required), else it may be NULL
+ *             count:    out, the rows written
+ *             flags, reserved: 0
+ * The record comes back in the copy that brings the dead record: stats->host_waits is what it is without phantoms.
+ * Refused in addition (-1, the engine untouched): a fraction outside [0, 1] or NaN, a missing array, a capacity below
+ * n_iterations K (num_repeats - 1), non-zero flags. */
+typedef struct {
+    double fraction;
+    int64_t capacity;
+    double* u; double* lnl; double* birth;
+    int64_t* iteration; int32_t* thread; int32_t* repeat; int32_t* cluster;
+    int64_t count;
+    uint32_t flags, reserved;
+} vmx_nested_phantoms;
+int vmx_nested_run_phantoms(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                            int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                            const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters,
+                            vmx_nested_phantoms* phantoms);
 /* The clustering of one iteration on host arrays, the two kernels' unit-test entry: m points u[m][n] (finite) with previous ids
  * prev_id[m] (0: none; all below *next_id) on `device`.  Writes ids[m] (every point's new id), *k_used (the neighbour level 3 .. 8
  * the components were taken at), *n_clusters (1 .. VMX_NS_MAX_CLUSTERS), means [VMX_NS_MAX_CLUSTERS][n] and factors

@@ -2,7 +2,7 @@
 """Sample the posterior of a main config, one process per GPU: the reference's ``bin/run_vega_mpi.py`` with
 ``[control] run_sampler = True`` and ``sampler = Ensemble`` (settings in ``[Ensemble]``: path, name, walkers, steps, seed, a,
 thin, init, init_scale, driver) or ``sampler = Nested`` (``[Nested]``: path, name, num_live, num_repeats, precision, seed, threads,
-driver, max_iterations) or ``sampler = SMC`` (``[SMC]``: path, name, particles, ess, sweeps, seed, driver, max_stages).  Writes
+driver, max_iterations, do_clustering, cluster_posteriors, boost_posterior) or ``sampler = SMC`` (``[SMC]``: path, name, particles, ess, sweeps, seed, driver, max_stages).  Writes
 ``<path>/<name>.txt`` and ``<path>/<name>.paramnames`` (getdist's plain-text chain); a nested or SMC run also
 ``<path>/<name>.stats`` with the evidence.  ``derived = True`` in the sampler's section appends the marginalisation
 coefficients as derived parameters (``<corr>_marg_<i>``) to both files.

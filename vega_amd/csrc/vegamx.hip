@@ -322,6 +322,10 @@ struct NsWorkspace {
     DevBuf<int32_t> live_cluster, dead_cluster, nn, cslot, tslot, cl_id, cl_size, cl_info;
     DevBuf<uint8_t> lev;
     DevBuf<double> cl_mean, cl_cov, cl_chol;
+    // boost (vmx_nested_run_phantoms): the call's phantom record and its running count
+    DevBuf<double> ph_u, ph_lnl, ph_birth;
+    DevBuf<int64_t> ph_it, ph_count;
+    DevBuf<int32_t> ph_thread, ph_repeat, ph_cluster;
     int32_t info_host[4] = {0, 0, 0, 0};                             // what goes up into cl_info (it outlives the copy)
     int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr;       // mapped host memory: rows of the round
     double* pin_lnl = nullptr; double* dpin_lnl = nullptr;           // ... and, when an iteration ends, live lnL [nlive] + dead lnL [K]
@@ -368,6 +372,16 @@ struct NsDev {
 struct NsClusterRun {
     NsClusterDev cl; int32_t* dead_cluster; int32_t* tslot;
     int32_t phase;                                          // k_ns_iteration_clustered: 0 the kill, 1 (after the clustering) the starts
+};
+
+// what a run that keeps phantom points hands its advance kernel beside NsDev (vmx_nested.h "boost"): the call's record
+// [capacity] ([n]), the rows written so far, the kept fraction
+struct NsPhantomRun {
+    double* u; double* lnl; double* birth;
+    int64_t* iteration; int32_t* thread; int32_t* repeat; int32_t* cluster;     // cluster: with clustering only
+    int64_t* count;
+    int64_t capacity;
+    double fraction;
 };
 
 constexpr int NS_THREADS = 1024;
@@ -630,9 +644,12 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_iteration_clustered(NsDev D, 
 // running and emit their rows (the fixed row with the sampled columns mapped out of the cube) and the row count to the host's
 // word.  When nothing is asked for the iteration is over: the end points take the killed points' slots, and the live and the
 // newly dead lnL go to the host beside the word.  CLUSTER (k_ns_advance_clustered): every thread walks with the factor of its
-// start's cluster, and its end point inherits that cluster's id.
-template <bool CLUSTER>
-__device__ __forceinline__ int ns_advance_threads(const NsDev& D, const NsClusterRun& X, int64_t it, int32_t* s_scan, int32_t* s_row_thread)
+// start's cluster, and its end point inherits that cluster's id.  PHANTOM (k_ns_advance_phantoms, _clustered): after its advance
+// every lane asks whether the call accepted a point inside the walk and whether the thinning keeps it (*keeps: one bit per thread
+// of the lane, as `asks`); ns_record_phantoms writes them.  Without it the code is what it was.
+template <bool CLUSTER, bool PHANTOM = false>
+__device__ __forceinline__ int ns_advance_threads(const NsDev& D, const NsClusterRun& X, int64_t it, int32_t* s_scan, int32_t* s_row_thread,
+                                                  double fraction = 0.0, uint32_t* keeps = nullptr)
 {
     const int K = D.K, n = D.n;
     const int per = (K + NS_THREADS - 1) / NS_THREADS;
@@ -648,7 +665,14 @@ __device__ __forceinline__ int ns_advance_threads(const NsDev& D, const NsCluste
         const int row = D.slot[k];
         const double answer = row >= 0 ? vmx_ns::lnl_of(D.box.status[row], D.box.chi2[row], D.log_norm) : -INFINITY;
         if constexpr (CLUSTER) I.C = X.cl.chol + (size_t)X.tslot[k] * n * n;
-        if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
+        if constexpr (PHANTOM) {
+            const int32_t state_before = T.state, inside_before = T.inside;
+            if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
+            const int32_t r = vmx_ns::phantom_of(state_before, inside_before, answer, I.lstar, T, I.num_repeats);
+            if (r > 0 && vmx_ns::phantom_kept(k, it, r, fraction, D.seed, D.stream)) *keeps |= 1u << j;
+        } else {
+            if (vmx_ns::advance(T, I, k, answer)) { asks |= 1u << j; mine += 1; }
+        }
     }
     s_scan[threadIdx.x] = mine;
     __syncthreads();
@@ -693,12 +717,71 @@ __device__ __forceinline__ void ns_iteration_end(const NsDev& D, const NsCluster
     for (int i = threadIdx.x; i < D.nlive; i += blockDim.x) D.host_lnl[i] = D.live_lnl[i];
 }
 
+// The kept phantom points of the round (`keeps`: this lane's threads, bit j = thread k0 + j) behind the F.count rows the call has
+// written: a second scan over s_scan (free again after ns_advance_threads' last barrier) places them in thread order, s_list holds
+// the accepting threads, and the lanes write the record one column per lane.  A kept point's thread goes on walking: T.x is the
+// accepted point, T.lnl its lnL, T.repeat its index.  The running count goes to the host beside the row count.
 template <bool CLUSTER>
-__device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec)
+__device__ __forceinline__ void ns_record_phantoms(const NsDev& D, const NsClusterRun& X, const NsPhantomRun& F, int64_t it, uint32_t keeps,
+                                                   int32_t* s_scan, int32_t* s_list)
+{
+    const int K = D.K, n = D.n;
+    const int per = (K + NS_THREADS - 1) / NS_THREADS;
+    const int k0 = threadIdx.x * per;
+    const int mine = __popc(keeps);
+    s_scan[threadIdx.x] = mine;
+    __syncthreads();
+    for (int step = 1; step < NS_THREADS; step <<= 1) {
+        const int v = threadIdx.x >= step ? s_scan[threadIdx.x - step] : 0;
+        __syncthreads();
+        s_scan[threadIdx.x] += v;
+        __syncthreads();
+    }
+    const int total = s_scan[NS_THREADS - 1];
+    const int64_t base = *F.count;
+    int place = s_scan[threadIdx.x] - mine;
+    for (int j = 0; j < per; ++j)
+        if (keeps & (1u << j)) s_list[place++] = k0 + j;
+    __syncthreads();                    // (the list is whole, and every lane has read the count)
+    // (capacity >= iterations K (num_repeats - 1) was checked before the run: the guard never bites)
+    const int64_t left = F.capacity > base ? F.capacity - base : 0;
+    const int room = left < (int64_t)total ? (int)left : total;
+    for (int e = threadIdx.x; e < room * n; e += NS_THREADS) {
+        const int p = e / n, d = e % n;
+        F.u[(size_t)(base + p) * n + d] = D.th[s_list[p]].x[d];
+    }
+    const double lstar = *D.lstar;
+    for (int p = threadIdx.x; p < room; p += NS_THREADS) {
+        const int k = s_list[p];
+        const vmx_ns::Thread& T = D.th[k];
+        const size_t row = (size_t)(base + p);
+        F.lnl[row] = T.lnl;
+        F.birth[row] = lstar;
+        F.iteration[row] = it;
+        F.thread[row] = k;
+        F.repeat[row] = T.repeat;
+        if constexpr (CLUSTER) F.cluster[row] = X.cl.cl_id[X.tslot[k]];
+    }
+    if (threadIdx.x == 0) {
+        *F.count = base + total;
+        *(long long*)(D.host_word + 2) = (long long)(base + total);
+    }
+}
+
+template <bool CLUSTER, bool PHANTOM = false>
+__device__ __forceinline__ void ns_advance(const NsDev& D, const NsClusterRun& X, int64_t it, int64_t rec, const NsPhantomRun& F = NsPhantomRun{})
 {
     __shared__ int32_t s_scan[NS_THREADS];
     __shared__ int32_t s_row_thread[vmx_ns::MAX_LIVE];
-    const int total = ns_advance_threads<CLUSTER>(D, X, it, s_scan, s_row_thread);
+    int total;
+    if constexpr (PHANTOM) {
+        __shared__ int32_t s_phantom_thread[vmx_ns::MAX_LIVE];
+        uint32_t keeps = 0;
+        total = ns_advance_threads<CLUSTER, true>(D, X, it, s_scan, s_row_thread, F.fraction, &keeps);
+        ns_record_phantoms<CLUSTER>(D, X, F, it, keeps, s_scan, s_phantom_thread);
+    } else {
+        total = ns_advance_threads<CLUSTER>(D, X, it, s_scan, s_row_thread);
+    }
     write_cube_rows<NS_THREADS>(D.box, D.P, total, [&](int r, int d) {
         const vmx_ns::Thread& T = D.th[s_row_thread[r]];
         return T.inside ? T.y[d] : T.x[d];
@@ -715,6 +798,16 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_advance(NsDev D, int64_t it, 
 __global__ __launch_bounds__(NS_THREADS) void k_ns_advance_clustered(NsDev D, NsClusterRun X, int64_t it, int64_t rec)
 {
     ns_advance<true>(D, X, it, rec);
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_advance_phantoms(NsDev D, NsPhantomRun F, int64_t it, int64_t rec)
+{
+    ns_advance<false, true>(D, NsClusterRun{}, it, rec, F);
+}
+
+__global__ __launch_bounds__(NS_THREADS) void k_ns_advance_phantoms_clustered(NsDev D, NsClusterRun X, NsPhantomRun F, int64_t it, int64_t rec)
+{
+    ns_advance<true, true>(D, X, it, rec, F);
 }
 
 // A set of runs (vmx_nested_run_many; vmx_nested.h "a set of runs"): a work-group owns one run - the functions above over that
@@ -1726,6 +1819,7 @@ int vmx_struct_size(int32_t which)
         case 16: return (int)sizeof(vmx_smc_stats);
         case 17: return (int)sizeof(vmx_nested_clusters);
         case 18: return (int)sizeof(vmx_nested_set_options);
+        case 19: return (int)sizeof(vmx_nested_phantoms);
         default: return -1;
     }
 }
@@ -4784,7 +4878,8 @@ static int launch_clustering(const NsClusterDev& C, hipStream_t st)
 
 static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                       int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
-                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters);
+                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters,
+                      vmx_nested_phantoms* phantoms = nullptr);
 
 int vmx_nested_run(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                    int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
@@ -4802,6 +4897,20 @@ int vmx_nested_run_clustered(vmx_engine* e, const vmx_nested_spec* spec, double*
     REQUIRE((clusters->flags & ~(uint32_t)VMX_NS_CLUSTER) == 0, "vmx_nested_run_clustered: flags 0 or VMX_NS_CLUSTER");
     return nested_run("vmx_nested_run_clustered", e, spec, live_u, live_lnl, iteration, n_iterations, dead_u, dead_lnl, dead_nlive, opt,
                       stats, (clusters->flags & VMX_NS_CLUSTER) ? clusters : nullptr);
+}
+
+int vmx_nested_run_phantoms(vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
+                            int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                            const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters,
+                            vmx_nested_phantoms* phantoms)
+{
+    const std::string name("vmx_nested_run_phantoms");
+    if (clusters) REQUIRE((clusters->flags & ~(uint32_t)VMX_NS_CLUSTER) == 0, name + ": flags 0 or VMX_NS_CLUSTER");
+    const vmx_nested_clusters* cl = clusters && (clusters->flags & VMX_NS_CLUSTER) ? clusters : nullptr;
+    if (phantoms) REQUIRE(phantoms->fraction >= 0.0 && phantoms->fraction <= 1.0, name + ": the kept fraction lies in [0, 1]");
+    // (fraction 0: the run without phantoms, and nothing in the struct is touched)
+    return nested_run("vmx_nested_run_phantoms", e, spec, live_u, live_lnl, iteration, n_iterations, dead_u, dead_lnl, dead_nlive, opt,
+                      stats, cl, phantoms && phantoms->fraction > 0.0 ? phantoms : nullptr);
 }
 
 int vmx_nested_cluster_points(int32_t device, const double* u, int32_t m, int32_t n, const int32_t* prev_id, int32_t* next_id,
@@ -4842,7 +4951,8 @@ int vmx_nested_cluster_points(int32_t device, const double* u, int32_t m, int32_
 
 static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spec, double* live_u, double* live_lnl, int64_t* iteration,
                       int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive,
-                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters)
+                      const vmx_nested_options* opt, vmx_nested_stats* stats, const vmx_nested_clusters* clusters,
+                      vmx_nested_phantoms* phantoms)
 {
     const std::string name(who);
     REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration, name);
@@ -4864,6 +4974,14 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
         REQUIRE((int64_t)*clusters->next_id + (int64_t)n_iterations * VMX_NS_MAX_CLUSTERS < 0x7fffffff, name + ": next_id would overflow");
         for (int i = 0; i < nlive; ++i)
             REQUIRE(clusters->live_cluster[i] >= 0 && clusters->live_cluster[i] < *clusters->next_id, name + ": 0 <= live_cluster < next_id");
+    }
+    const bool recording = phantoms != nullptr;
+    const int64_t ph_need = (int64_t)n_iterations * K * (spec->num_repeats - 1);       // (what the call can keep at the most)
+    if (recording) {
+        REQUIRE(phantoms->flags == 0, name + ": phantoms->flags 0");
+        REQUIRE(phantoms->capacity >= ph_need, name + ": phantoms->capacity below n_iterations K (num_repeats - 1)");
+        REQUIRE(ph_need == 0 || (phantoms->u && phantoms->lnl && phantoms->birth && phantoms->iteration && phantoms->thread &&
+                                 phantoms->repeat && (!clustering || phantoms->cluster)), name + ": the phantom record");
     }
     REQUIRE(!draw || *iteration == 0, name + ": live points are drawn at iteration 0");
     if (!draw)
@@ -4892,6 +5010,11 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
          ensure(S.lev, (size_t)m * VMX_NS_KNN) || ensure(S.cslot, m) || ensure(S.tslot, K) || ensure(S.cl_id, VMX_NS_MAX_CLUSTERS) ||
          ensure(S.cl_size, VMX_NS_MAX_CLUSTERS) || ensure(S.cl_info, 4) || ensure(S.cl_mean, (size_t)VMX_NS_MAX_CLUSTERS * n) ||
          ensure(S.cl_cov, (size_t)VMX_NS_MAX_CLUSTERS * n * n) || ensure(S.cl_chol, (size_t)VMX_NS_MAX_CLUSTERS * n * n)))
+        return -2;
+    const size_t ph_rows = (size_t)std::max<int64_t>(ph_need, 1);
+    if (recording &&
+        (ensure(S.ph_u, ph_rows * n) || ensure(S.ph_lnl, ph_rows) || ensure(S.ph_birth, ph_rows) || ensure(S.ph_it, ph_rows) ||
+         ensure(S.ph_thread, ph_rows) || ensure(S.ph_repeat, ph_rows) || (clustering && ensure(S.ph_cluster, ph_rows)) || ensure(S.ph_count, 1)))
         return -2;
     if (!S.pin_word) {
         HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
@@ -4928,6 +5051,13 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
                             S.cl_mean.p, S.cl_cov.p, S.cl_chol.p, m, n};
         X.dead_cluster = S.dead_cluster.p; X.tslot = S.tslot.p;
     }
+    NsPhantomRun F{};
+    if (recording) {
+        HIP_OK(hipMemsetAsync(S.ph_count.p, 0, sizeof(int64_t), st));
+        F = NsPhantomRun{S.ph_u.p, S.ph_lnl.p, S.ph_birth.p, S.ph_it.p, S.ph_thread.p, S.ph_repeat.p, S.ph_cluster.p, S.ph_count.p,
+                         ph_need, phantoms->fraction};      // (the device record holds ph_need rows, whatever the host's capacity)
+    }
+    int64_t ph_count = 0;
 
     // the engine as the sampler's likelihood, at the table level the sampled columns allow
     LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
@@ -4966,11 +5096,15 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
             hipLaunchKernelGGL(k_ns_iteration_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
         } else hipLaunchKernelGGL(k_ns_iteration, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
         for (;;) {
-            if (clustering) hipLaunchKernelGGL(k_ns_advance_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
+            if (recording) {
+                if (clustering) hipLaunchKernelGGL(k_ns_advance_phantoms_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, F, it, (int64_t)done);
+                else hipLaunchKernelGGL(k_ns_advance_phantoms, dim3(1), dim3(NS_THREADS), 0, st, D, F, it, (int64_t)done);
+            } else if (clustering) hipLaunchKernelGGL(k_ns_advance_clustered, dim3(1), dim3(NS_THREADS), 0, st, D, X, it, (int64_t)done);
             else hipLaunchKernelGGL(k_ns_advance, dim3(1), dim3(NS_THREADS), 0, st, D, it, (int64_t)done);
             HIP_OK(hipGetLastError());
             HIP_OK(hipStreamSynchronize(st));   // (the round's only wait: the row count, one mapped word)
             R.host_waits += 1;
+            if (recording) std::memcpy(&ph_count, S.pin_word + 2, sizeof(int64_t));     // (the phantom rows so far, beside it)
             const int total = S.pin_word[0];
             if (total <= 0) break;
             if ((size_t)total > cap) return fail(-2, name + ": a round asked for more rows than its buffers hold");
@@ -4989,6 +5123,17 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
         HIP_OK(hipMemcpyAsync(dead_lnl, S.dead_lnl.p, (size_t)done * K * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(dead_nlive, S.dead_n.p, (size_t)done * K * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
+    if (recording && (ph_count < 0 || ph_count > ph_need)) return fail(-2, name + ": the phantom record overran its capacity");
+    if (recording && ph_count > 0) {
+        const size_t c = (size_t)ph_count;
+        HIP_OK(hipMemcpyAsync(phantoms->u, S.ph_u.p, c * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->lnl, S.ph_lnl.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->birth, S.ph_birth.p, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->iteration, S.ph_it.p, c * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->thread, S.ph_thread.p, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->repeat, S.ph_repeat.p, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (clustering) HIP_OK(hipMemcpyAsync(phantoms->cluster, S.ph_cluster.p, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
     int32_t info_out[4] = {0, 0, 0, 0};
     if (clustering) {
         HIP_OK(hipMemcpyAsync(clusters->live_cluster, S.live_cluster.p, (size_t)nlive * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -5002,6 +5147,7 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
     R.host_waits += 1;
     *iteration += done;
     if (clustering) *clusters->next_id = info_out[2];
+    if (recording) phantoms->count = ph_count;
     R.iterations = done;
     R.rows_own_position = own;
     R.seconds_enqueuing = enqueue_s;

@@ -3,7 +3,8 @@
 // The loop runs where the live points are (vmx_nested_run, vegamx.hip: k_ns_iteration kills, whitens and starts the threads,
 // k_ns_advance moves every thread's state machine by one likelihood answer and compacts the next requests);
 // vega_amd/nested.py restates every expression below in NumPy (the `python` driver) and tests/helpers/nested_driver.cpp compiles
-// this header with g++ so that tests/test_nested_host.py can hold the two against each other bit for bit.  No HIP type, no heap.
+// this header with g++ so that tests/test_nested_host.py can hold the two against each other bit for bit (the boost part:
+// tests/helpers/nested_boost_driver.cpp, tests/test_nested_boost_host.py).  No HIP type, no heap.
 //
 //   cube             the sampler works in u in [0, 1]^n; a physical parameter is lo + (hi - lo) u (map_cube), a uniform prior over
 //                    the limits.  lnL = log_norm - 0.5 chi2 (vmx_ens::log_lik); a failed model (!vmx_ens::model_ok) has
@@ -69,6 +70,18 @@
 //                    stay in WALK.  Runs do not wait for each other: a run whose iteration ended in round r is headed in
 //                    round r + 1.  The iteration index of run e is iteration[e] + iterations_done[e], its record row
 //                    iterations_done[e].
+//
+//   boost            (optional: vmx_nested_run_phantoms; off, everything above is what a run does) the accepted points inside a
+//                    thread's walk are kept beside the dead record instead of being thrown away - no likelihood row is spent.
+//     phantom        thread k of iteration t has the phantom point r (1 <= r < num_repeats) when advance accepts a trial in
+//                    S_SHRINK (T.inside != 0 && answer > L*) and T.repeat after the call is r < num_repeats (phantom_of, from the
+//                    state and `inside` before the call and the thread after it).  The point is T.x, its lnL T.lnl = the answer,
+//                    its birth contour the iteration's L*.  A step that gives up after MAX_SHRINK yields none, nor does the end
+//                    point (r = num_repeats).
+//     thinning       (k, t, r) is kept iff u01(word 0 of philox4x64_10(k, t, r, 3, seed, stream)) < f (phantom_kept), f in [0, 1]:
+//                    the last counter word 3 is a domain of its own (threads 1, live points 2), so the run is the same run at any f.
+//     record         per kept point u[n], lnL, birth, (iteration, thread, repeat), and with clustering the id of the thread's
+//                    cluster (what its end point inherits); the canonical order is ascending (iteration, thread, repeat).
 //
 // Thread is a resumable state machine: advance(state, lnL of my last request) -> next request | done.  Every expression is the
 // separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are correctly rounded.
@@ -309,6 +322,22 @@ VMX_HD inline bool advance(Thread& T, const Iteration& I, int64_t k, double answ
         return true;
     }
     return false;
+}
+
+// ---- boost: the accepted points inside a walk (nothing here changes advance or a thread's stream)
+// the index r of the phantom point the last call of advance produced, 0: none.  `state_before` / `inside_before`: T.state and
+// T.inside when advance was called with `answer`; T: the thread after the call.
+VMX_HD inline int32_t phantom_of(int32_t state_before, int32_t inside_before, double answer, double lstar, const Thread& T,
+                                 int32_t num_repeats)
+{
+    const bool accepted = state_before == S_SHRINK && inside_before != 0 && answer > lstar;
+    return accepted && T.repeat < num_repeats ? T.repeat : 0;
+}
+
+// whether the phantom point r of thread k at iteration t is kept at the fraction f
+VMX_HD inline bool phantom_kept(int64_t k, int64_t t, int32_t r, double f, uint64_t seed, uint64_t stream)
+{
+    return vmx_ens::u01(vmx_ens::philox4x64_10((uint64_t)k, (uint64_t)t, (uint64_t)r, 3, seed, stream).w[0]) < f;
 }
 
 // ---- clustering of the survivors (positions 0 .. m-1; `surv` maps a position to its row of u and of prev_id, nullptr: itself)

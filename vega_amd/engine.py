@@ -176,6 +176,13 @@ class NestedClusters(C.Structure):
                 ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+class NestedPhantoms(C.Structure):
+    _fields_ = [('fraction', C.c_double), ('capacity', C.c_int64), ('u', C.POINTER(C.c_double)), ('lnl', C.POINTER(C.c_double)),
+                ('birth', C.POINTER(C.c_double)), ('iteration', C.POINTER(C.c_int64)), ('thread', C.POINTER(C.c_int32)),
+                ('repeat', C.POINTER(C.c_int32)), ('cluster', C.POINTER(C.c_int32)), ('count', C.c_int64),
+                ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
 VMX_SMC_MAX_PARTICLES = 4096
 VMX_SMC_REC = 8
 
@@ -286,6 +293,7 @@ def load_library():
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
+    lib.vmx_nested_run_phantoms.argtypes = lib.vmx_nested_run_clustered.argtypes + [C.POINTER(NestedPhantoms)]
     lib.vmx_nested_cluster_points.argtypes = [C.c_int32, dptr, C.c_int32, C.c_int32, iptr, iptr, iptr, iptr, iptr, dptr, dptr]
     lib.vmx_nested_run_many.argtypes = [C.c_void_p, C.POINTER(NestedSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
                                         C.POINTER(C.c_int64), iptr, C.c_int32, dptr, dptr, iptr, iptr, C.POINTER(NestedSetOptions),
@@ -331,7 +339,7 @@ def load_library():
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
-                                    SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions)):
+                                    SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -363,7 +371,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1157,7 +1165,8 @@ class Engine:
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
-                   seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, clusters=None, cluster_flags=None):
+                   seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, clusters=None, cluster_flags=None,
+                   phantoms=None, phantom_capacity=None):
         """Up to ``n_iterations`` iterations of the nested sampler on the device (include/vegamx.h: vmx_nested_run): ``cols`` the
         sampled parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``live_u`` [nlive, n] in the unit
         cube / ``live_lnl`` [nlive] the run's state (updated in place; drawn first with ``draw_live``), ``iteration`` the global
@@ -1165,7 +1174,10 @@ class Engine:
         answer ends the call.  Returns (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K], iteration + m, statistics) for the m
         iterations done.  ``clusters`` (a :class:`vega_amd.nested.ClusterState`, updated in place, the ids of this call's dead
         appended to its ``dead``): the run with clustering (vmx_nested_run_clustered); ``cluster_flags`` overrides the flags word
-        (0: the entry runs what vmx_nested_run runs)."""
+        (0: the entry runs what vmx_nested_run runs).  ``phantoms`` (a :class:`vega_amd.nested.PhantomState`: its ``fraction`` of
+        the accepted points inside the walks is kept and this call's are appended to it, in the canonical order): the run
+        through vmx_nested_run_phantoms, with or without ``clusters``; ``phantom_capacity`` overrides the rows of the record's
+        arrays (threads (num_repeats - 1) per iteration: what the call can keep at the most)."""
         cols, lo, hi, theta_fixed, nlive = self._sampled_box(cols, lo, hi, theta_fixed, live_u=live_u, live_lnl=live_lnl)
         K, n_iterations = int(threads), max(0, int(n_iterations))
         rows = n_iterations * max(K, 0)
@@ -1185,7 +1197,34 @@ class Engine:
         opt = NestedOptions(int(const_hint), int(chunk), int(lanes), 1 if draw_live else 0, callback, None)
         stats = NestedStats()
         it = C.c_int64(int(iteration))
-        if clusters is None:
+        if phantoms is not None:
+            n = cols.size
+            cap = rows * max(0, int(num_repeats) - 1) if phantom_capacity is None else int(phantom_capacity)
+            size = max(cap, 0)
+            ph_u, ph_lnl, ph_birth = np.empty((size, n)), np.empty(size), np.empty(size)
+            ph_it, ph_k, ph_r = np.empty(size, dtype=np.int64), np.empty(size, dtype=np.int32), np.empty(size, dtype=np.int32)
+            ph_c = np.zeros(size, dtype=np.int32) if clusters is not None else None
+            ph = NestedPhantoms(float(phantoms.fraction), cap, _dp(ph_u), _dp(ph_lnl), _dp(ph_birth),
+                                ph_it.ctypes.data_as(C.POINTER(C.c_int64)), _ip(ph_k), _ip(ph_r), None if ph_c is None else _ip(ph_c),
+                                0, 0, 0)
+            cl, dead_c, next_id = None, None, None
+            if clusters is not None:
+                if clusters.live_cluster.dtype != np.int32 or clusters.live_cluster.shape != (nlive,) or \
+                        not clusters.live_cluster.flags['C_CONTIGUOUS']:
+                    raise ValueError('clusters.live_cluster: a contiguous int32 array [nlive]')
+                dead_c, next_id = np.zeros(rows, dtype=np.int32), C.c_int32(int(clusters.next_id))
+                cl = NestedClusters(_ip(clusters.live_cluster), C.pointer(next_id), _ip(dead_c),
+                                    VMX_NS_CLUSTER if cluster_flags is None else int(cluster_flags), 0)
+            self._check(self.lib.vmx_nested_run_phantoms(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
+                                                         _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats),
+                                                         None if cl is None else C.byref(cl), C.byref(ph)))
+            if clusters is not None:
+                clusters.next_id = int(next_id.value)
+                clusters.dead.append(dead_c[:int(stats.iterations) * K])
+            c = int(ph.count)
+            phantoms.append(ph_u[:c], ph_lnl[:c], ph_birth[:c], np.stack([ph_it[:c], ph_k[:c], ph_r[:c]], axis=1),
+                            None if ph_c is None else ph_c[:c])
+        elif clusters is None:
             self._check(self.lib.vmx_nested_run(self._h, C.byref(spec), _dp(live_u), _dp(live_lnl), C.byref(it), n_iterations,
                                                 _dp(dead_u), _dp(dead_lnl), _ip(dead_n), C.byref(opt), C.byref(stats)))
         else:

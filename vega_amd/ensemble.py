@@ -892,7 +892,8 @@ def build_sampler(vega, cfg, sample_params, stream=0):
         return NestedSampler(vega, num_live=cfg['num_live'], num_repeats=cfg['num_repeats'], threads=cfg['threads'],
                              precision=cfg['precision'], seed=cfg['seed'], driver=cfg['driver'],
                              max_iterations=cfg['max_iterations'], sample_params=sample_params, stream=stream,
-                             clustering=cfg.get('do_clustering', False), cluster_posteriors=cfg.get('cluster_posteriors', False))
+                             clustering=cfg.get('do_clustering', False), cluster_posteriors=cfg.get('cluster_posteriors', False),
+                             boost_posterior=cfg.get('boost_posterior', 0.0))
     if cfg['sampler'] == 'SMC':
         from .smc import SMCSampler
         return SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],

@@ -14,7 +14,11 @@ and termination are computed here, on the host, from the dead record - one code 
 neighbours, whitens each on its own and keeps persistent ids, so that separated modes get factors that fit them, local evidences
 (:meth:`NestedRun.clusters`) and chains of their own (``cluster_posteriors``).
 
-What is not here: ``boost_posterior``, resume files.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
+``boost_posterior`` (the reference's key) keeps the accepted points inside the threads' walks - each a uniform draw from its
+iteration's contour that the engine has already evaluated - as a phantom record beside the dead one and merges them into the
+weighted chain (:func:`boosted_weights`); the evidence and its error stay those of the base run.
+
+What is not here: resume files; ``boost_posterior`` for sets of runs, replica merges and per-cluster chains.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
 """
 import math
 import time
@@ -32,6 +36,14 @@ WIDTH = 2.0
 S_NEXT, S_LEFT, S_RIGHT, S_SHRINK, S_DONE = range(5)
 KNN = 8
 MAX_CLUSTERS = 8
+# boost: the phantom record of one driver call is allocated at its capacity, on the host and on the device; this many bytes at the
+# most (at n = 32 with the defaults - 384 threads, 160 repeats, 18 MB an iteration - 11 iterations a call)
+PHANTOM_BUDGET = 200 * 1000 * 1000
+
+
+def phantom_row_bytes(n):
+    """u [n], lnL, birth; iteration (int64), thread, repeat, cluster (int32)."""
+    return 8 * (n + 2) + 8 + 3 * 4
 
 
 # ------------------------------------------------------------------ the algorithm (vmx_nested.h) in NumPy
@@ -249,6 +261,52 @@ def iteration_head(live_u, live_lnl, K, t, seed, stream=0, clusters=None):
                 start=surv[choice])
 
 
+# ---- boost: the accepted points inside a walk (vmx_nested.h "boost")
+def boost_fraction(boost_posterior, num_repeats):
+    """f = min(1, b / num_repeats): one cannot boost by more than num_repeats."""
+    return min(1.0, float(boost_posterior) / float(num_repeats))
+
+
+def phantom_of(state_before, inside_before, answer, lstar, repeat_after, num_repeats):
+    """vmx_ns::phantom_of on arrays: the index r of the phantom point the last advance produced, 0: none."""
+    with np.errstate(invalid='ignore'):
+        accepted = (state_before == S_SHRINK) & inside_before & (answer > lstar)
+    return np.where(accepted & (repeat_after < num_repeats), repeat_after, 0).astype(np.int32)
+
+
+def phantom_kept(k, t, r, f, seed, stream=0):
+    """vmx_ns::phantom_kept: u01(word 0 of the Philox block (k, t, r, 3)) < f."""
+    return E.u01(_blocks(k, t, r, 3, seed, stream)[..., 0]) < f
+
+
+class PhantomState:
+    """What boost adds to a run's state: the fraction f and the kept phantom points of every call (one dict per call, in the
+    canonical order): ``u`` [N, n], ``lnl``, ``birth`` [N], ``tag`` [N, 3] int64 (iteration, thread, repeat), ``cluster`` [N]
+    int32 (a run with clustering; else None)."""
+
+    def __init__(self, fraction):
+        self.fraction = float(fraction)
+        if not 0.0 <= self.fraction <= 1.0:
+            raise ValueError('the kept fraction of the phantom points: 0 .. 1')
+        self.calls = []
+
+    def append(self, u, lnl, birth, tag, cluster=None):
+        """The points of one call, in any order: they are put into the canonical one first."""
+        tag = np.asarray(tag, dtype=np.int64).reshape(-1, 3)
+        order = np.lexsort((tag[:, 2], tag[:, 1], tag[:, 0]))
+        self.calls.append(dict(u=np.asarray(u, dtype=np.float64)[order], lnl=np.asarray(lnl, dtype=np.float64)[order],
+                               birth=np.asarray(birth, dtype=np.float64)[order], tag=tag[order],
+                               cluster=None if cluster is None else np.asarray(cluster, dtype=np.int32)[order]))
+
+    def record(self, n):
+        if not self.calls:
+            return dict(u=np.empty((0, n)), lnl=np.empty(0), birth=np.empty(0), tag=np.empty((0, 3), dtype=np.int64), cluster=None)
+        out = {key: np.concatenate([c[key] for c in self.calls]) for key in ('u', 'lnl', 'birth', 'tag')}
+        out['u'] = out['u'].reshape(-1, n)
+        out['cluster'] = None if self.calls[0]['cluster'] is None else np.concatenate([c['cluster'] for c in self.calls])
+        return out
+
+
 class Threads:
     """The K state machines of an iteration (vmx_ns::Thread as arrays); ``C`` [n, n], or [K, n, n]: a factor per thread."""
 
@@ -367,13 +425,18 @@ class Threads:
         return ks, np.where(self.inside[ks, None], self.y[ks], self.x[ks]), int((~self.inside[ks]).sum())
 
 
-def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, stream, evaluate, stop=None, clusters=None):
+def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, stream, evaluate, stop=None, clusters=None,
+                      boost=None):
     """Up to ``n_iterations`` iterations in NumPy from the state ``live_u`` [nlive, n], ``live_lnl`` [nlive] (updated in place).
     ``evaluate(rows_u)`` -> lnL [R] of rows in the cube (-inf: a failed model).  ``stop(iterations, dead_lnl, live_lnl)`` as for
     the device driver.  ``clusters``: a :class:`ClusterState` turns clustering on (updated in place; the ids of this call's dead
-    are appended to its ``dead``).  Returns (dead_u, dead_lnl, dead_nlive, iteration, stats)."""
+    are appended to its ``dead``).  ``boost``: a :class:`PhantomState` records the kept phantom points of this call (appended to
+    it; the run itself is the same run).  Returns (dead_u, dead_lnl, dead_nlive, iteration, stats)."""
     nlive, n = live_u.shape
     dead_u, dead_lnl, dead_n, dead_c = [], [], [], []
+    if boost is not None and boost.fraction == 0.0:
+        boost = None
+    ph = dict(u=[], lnl=[], birth=[], tag=[], cluster=[])
     st = dict(iterations=0, rounds=0, rows=0, rows_own_position=0)
     for _ in range(n_iterations):
         head = iteration_head(live_u, live_lnl, K, iteration, seed, stream, clusters)
@@ -394,7 +457,22 @@ def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats,
             st['rounds'] += 1
             st['rows'] += ks.size
             st['rows_own_position'] += own
-            asks = T.advance(answer)
+            if boost is None:
+                asks = T.advance(answer)
+            else:
+                was, inside = T.state.copy(), T.inside.copy()
+                asks = T.advance(answer)
+                r = phantom_of(was, inside, answer, T.lstar, T.repeat, num_repeats)
+                kp = np.flatnonzero(r > 0)
+                kp = kp[phantom_kept(kp, iteration, r[kp], boost.fraction, seed, stream)]
+                if kp.size:
+                    ph['u'].append(T.x[kp].copy())
+                    ph['lnl'].append(T.lnl[kp].copy())
+                    ph['birth'].append(np.full(kp.size, head['lstar'], dtype=np.float64))
+                    ph['tag'].append(np.stack([np.full(kp.size, iteration, dtype=np.int64), kp.astype(np.int64),
+                                               r[kp].astype(np.int64)], axis=1))
+                    if clusters is not None:
+                        ph['cluster'].append(head['cluster']['cluster_id'][head['start_slot'][kp]].astype(np.int32))
         live_u[killed] = T.x
         live_lnl[killed] = T.lnl
         if clusters is not None:
@@ -405,6 +483,12 @@ def python_iterations(live_u, live_lnl, iteration, n_iterations, K, num_repeats,
             break
     if clusters is not None:
         clusters.dead.append(np.concatenate(dead_c) if dead_c else np.empty(0, dtype=np.int32))
+    if boost is not None:
+        cat = {key: (np.concatenate(val) if val else None) for key, val in ph.items()}
+        boost.append(cat['u'] if cat['u'] is not None else np.empty((0, n)), *(cat[key] if cat[key] is not None else np.empty(0)
+                                                                                for key in ('lnl', 'birth')),
+                     cat['tag'] if cat['tag'] is not None else np.empty((0, 3), dtype=np.int64),
+                     None if clusters is None else (cat['cluster'] if cat['cluster'] is not None else np.empty(0, dtype=np.int32)))
     if not dead_u:
         return np.empty((0, n)), np.empty(0), np.empty(0, dtype=np.int32), iteration, st
     return np.concatenate(dead_u), np.concatenate(dead_lnl), np.concatenate(dead_n), iteration, st
@@ -557,6 +641,43 @@ def log_weights(dead_lnl, dead_nlive, live_lnl):
     return np.concatenate([np.asarray(dead_lnl) + log_w, np.asarray(live_lnl) + log_w_live])
 
 
+def boosted_weights(dead_lnl, dead_nlive, live_lnl, ph_lnl, ph_birth):
+    """The base run and the kept phantom points (lnL ``ph_lnl`` > birth contour ``ph_birth``, canonical order) merged as runs are
+    merged by birth contour.  L_D: the lnL of the last death.  The events are the deaths and the phantoms with lnL <= L_D, sorted
+    by (lnL, deaths before phantoms, record order); the live count of event i is m_i = b_i + a_i, b_i the death's own recorded
+    count (a phantom: that of the first death in record order with lnL >= its lnL) and a_i = #{phantoms p : birth_p < lnL_i <=
+    lnL_p}; log X_i = log X_{i-1} - 1 / m_i, w_i = X_{i-1} - X_i (the expressions of :func:`log_weights`).  The final live points
+    and the A phantoms above L_D are all uniform in the last contour: X_end / (nlive + A) each.
+
+    Returns (log(L w) in the order events, live points, late phantoms; ``index`` - row j of that order is row index[j] of the
+    deaths, the live points and the phantoms laid end to end; log Z_boost, the log-sum).  Without phantoms: :func:`log_weights`."""
+    dead_lnl, live_lnl = np.asarray(dead_lnl, dtype=np.float64), np.asarray(live_lnl, dtype=np.float64)
+    ph_lnl, ph_birth = np.asarray(ph_lnl, dtype=np.float64), np.asarray(ph_birth, dtype=np.float64)
+    dead_nlive = np.asarray(dead_nlive, dtype=np.float64)
+    D, nl, P = dead_lnl.size, live_lnl.size, ph_lnl.size
+    early = ph_lnl <= dead_lnl[-1] if D else np.zeros(P, dtype=bool)
+    ev_ph, late = np.flatnonzero(early), np.flatnonzero(~early)
+    ev_lnl = np.concatenate([dead_lnl, ph_lnl[ev_ph]])
+    is_ph = np.concatenate([np.zeros(D, dtype=np.int8), np.ones(ev_ph.size, dtype=np.int8)])
+    src = np.concatenate([np.arange(D), ev_ph])
+    order = np.lexsort((src, is_ph, ev_lnl))
+    x = ev_lnl[order]
+    # b: a phantom takes the count of the first death in record order whose lnL is not below its own
+    first = np.searchsorted(np.maximum.accumulate(dead_lnl), ph_lnl[ev_ph], side='left') if D else np.empty(0, dtype=np.int64)
+    b = np.concatenate([dead_nlive, dead_nlive[first]])[order]
+    # a: lnL_p > birth_p, so #{birth_p < x <= lnL_p} = #{birth_p < x} - #{lnL_p < x}
+    a = np.searchsorted(np.sort(ph_birth), x, side='left') - np.searchsorted(np.sort(ph_lnl), x, side='left')
+    m = b + a
+    log_x = -np.cumsum(1.0 / m)
+    log_x_before = np.concatenate([[0.0], log_x[:-1]])
+    log_w = log_x_before + np.log1p(-np.exp(-1.0 / m))
+    log_x_end = log_x[-1] if log_x.size else 0.0
+    tail = np.concatenate([live_lnl, ph_lnl[late]])
+    lw = np.concatenate([x + log_w, tail + (log_x_end - math.log(nl + late.size))])
+    index = np.concatenate([np.where(is_ph[order] == 1, D + nl + src[order], src[order]), D + np.arange(nl), D + nl + late])
+    return lw, index.astype(np.int64), _logsumexp(lw)
+
+
 def evidence(dead_lnl, dead_nlive, live_lnl):
     """(log Z, H, posterior weights p_i summing to 1) over the dead points followed by the live ones."""
     lw = log_weights(dead_lnl, dead_nlive, live_lnl)
@@ -573,11 +694,17 @@ def evidence(dead_lnl, dead_nlive, live_lnl):
 class NestedRun:
     """A nested-sampling run over ``loglike(rows_u [R, n]) -> lnL [R]`` in the unit cube (-inf: a failed model), NumPy driver: the
     live points, the dead record, termination and the evidence.  :class:`NestedSampler` puts the engine behind it.
-    ``clustering``: cluster the survivors of every iteration, whiten per cluster and keep ids (:meth:`clusters`)."""
+    ``clustering``: cluster the survivors of every iteration, whiten per cluster and keep ids (:meth:`clusters`).
+    ``boost_posterior`` = b >= 0 (the reference's key; 0: off): keep the fraction min(1, b / num_repeats) of the accepted points
+    inside the threads' walks (:meth:`phantoms`) and merge them into :meth:`samples`; the run, its evidence and its termination
+    are those of b = 0."""
 
     def __init__(self, loglike, n, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, stream=0,
-                 max_iterations=None, max_batch=None, clustering=False):
+                 max_iterations=None, max_batch=None, clustering=False, boost_posterior=0.0):
         self.loglike = loglike
+        self.boost_posterior = float(boost_posterior)
+        if not (math.isfinite(self.boost_posterior) and self.boost_posterior >= 0.0):
+            raise ValueError('boost_posterior: a finite number, at least 0')
         if not isinstance(clustering, (bool, np.bool_)):
             raise ValueError('clustering: True or False')
         self.clustering = bool(clustering)
@@ -613,6 +740,7 @@ class NestedRun:
         self._dead_u, self._dead_lnl, self._dead_n = [], [], []
         self._log_x, self._log_z_dead = 0.0, -np.inf
         self.cluster_state = ClusterState(self.num_live) if self.clustering else None
+        self.phantom_state = PhantomState(boost_fraction(self.boost_posterior, self.num_repeats)) if self.boost_posterior > 0.0 else None
         self.stats = dict(iterations=0, rounds=0, rows=0, rows_own_position=0, engine_calls=0, host_waits=0, seconds=0.0,
                           seconds_enqueuing=0.0, calls=0)
 
@@ -646,22 +774,36 @@ class NestedRun:
             self._draw()
         du, dl, dn, self.iteration, st = python_iterations(self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
                                                            self.num_repeats, self.seed, self.stream, self._evaluate, self._stop,
-                                                           clusters=self.cluster_state)
+                                                           clusters=self.cluster_state, boost=self.phantom_state)
         return du, dl, dn, st
+
+    def _per_call(self):
+        """Iterations per call of the driver: the dead record of a call is allocated up front, and with boost the phantom record
+        at its capacity threads (num_repeats - 1) rows per iteration, which stays under PHANTOM_BUDGET bytes (at least one
+        iteration)."""
+        per_call = max(1, 65536 // self.threads)
+        if self.phantom_state is not None and self.num_repeats > 1:
+            rows = self.threads * (self.num_repeats - 1)
+            per_call = min(per_call, max(1, PHANTOM_BUDGET // (rows * phantom_row_bytes(self.n))))
+        return per_call
 
     def run(self, iterations=None):
         """To termination (``iterations`` None: the precision criterion or ``max_iterations``), or exactly ``iterations`` more
         iterations, whatever the criterion says (``terminated`` still reports it); the run does not depend on how it is cut."""
         t0 = time.perf_counter()
         self._to_termination = iterations is None
-        per_call = max(1, 65536 // self.threads)        # (the dead record of a call is allocated up front)
+        per_call = self._per_call()
         if iterations is None:
             left = self.max_iterations - self.iteration if self.max_iterations is not None else per_call
             call = min(max(0, left), per_call) if not self.terminated else 0
         else:
             call = int(iterations)
+        left_asked = call
         while call > 0:
+            if iterations is not None:      # (one call, as ever; with boost cut to the phantom record's budget)
+                call = min(left_asked, per_call) if self.phantom_state is not None else left_asked
             du, dl, dn, st = self._advance(call)
+            left_asked -= call
             self._dead_u.append(du)
             self._dead_lnl.append(dl)
             self._dead_n.append(dn)
@@ -669,7 +811,11 @@ class NestedRun:
                 if key in self.stats and key != 'seconds':
                     self.stats[key] += val
             self.stats['calls'] += 1
-            if iterations is not None or self.terminated or st['iterations'] == 0:
+            if iterations is not None:
+                if left_asked <= 0 or st['iterations'] == 0:
+                    break
+                continue
+            if self.terminated or st['iterations'] == 0:
                 break
             if self.max_iterations is not None:
                 call = min(per_call, self.max_iterations - self.iteration)
@@ -700,10 +846,49 @@ class NestedRun:
     def to_physical(self, u):
         return u
 
-    def samples(self, cluster=None):
+    def phantoms(self):
+        """The kept phantom points in the canonical order (ascending iteration, thread, repeat), a dict: ``u`` [N, n] in the cube,
+        ``lnl`` [N], ``birth`` [N] (the L* they were accepted under), ``tag`` [N, 3] int64 (iteration, thread, repeat),
+        ``cluster`` [N] int32 in a run with clustering (the id the thread's end point inherits), else None."""
+        if self.phantom_state is None:
+            raise ValueError('the run keeps no phantom points (boost_posterior > 0)')
+        return self.phantom_state.record(self.n)
+
+    def _boosted(self):
+        """(log(L w), index, log Z_boost) of :func:`boosted_weights` over this run."""
+        if self.live_u is None:
+            raise ValueError('nothing has run yet')
+        _, dl, dn = self.dead()
+        ph = self.phantoms()
+        return boosted_weights(dl, dn, self.live_lnl, ph['lnl'], ph['birth'])
+
+    def boost_log_evidence(self):
+        """log Z_boost, the log-sum of the boosted chain's weights: a consistency diagnostic, never the reported evidence (the
+        phantoms of one walk are correlated: they sharpen the posterior, not the evidence error)."""
+        return self._boosted()[2]
+
+    def boost_index(self):
+        """Row j of the boosted ``samples()`` is row ``boost_index()[j]`` of the dead points, the live points and
+        :meth:`phantoms` laid end to end."""
+        return self._boosted()[1]
+
+    def samples(self, cluster=None, boost=None):
         """(points [N, n], lnL [N], weights [N] summing to 1): the dead points in order of death, then the live points;
-        ``cluster``: those of one id of :meth:`clusters` only."""
+        ``cluster``: those of one id of :meth:`clusters` only.  ``boost`` (None: on iff ``boost_posterior > 0``): the chain with
+        the phantom points merged in - the events of :func:`boosted_weights` in their order, the live points, the phantoms above
+        the last death."""
+        boost = (self.phantom_state is not None and cluster is None) if boost is None else bool(boost)
+        if boost and cluster is not None:
+            raise ValueError('the chain of one cluster is not boosted: per-cluster chains are the base run\'s')
         du, dl, _ = self.dead()
+        if boost:
+            lw, index, log_z = self._boosted()
+            ph = self.phantoms()
+            with np.errstate(invalid='ignore'):
+                p = np.exp(lw - log_z) if np.isfinite(log_z) else np.zeros(lw.size)
+            p = np.where(np.isfinite(p), p, 0.0)
+            pts = self.to_physical(np.concatenate([du, self.live_u, ph['u']])[index])
+            return pts, np.concatenate([dl, self.live_lnl, ph['lnl']])[index], p / p.sum()
         p = self._evidence()[2]
         pts, lnl = self.to_physical(np.concatenate([du, self.live_u])), np.concatenate([dl, self.live_lnl])
         if cluster is not None:
@@ -716,7 +901,7 @@ class NestedRun:
 
     # ---- clusters
     def cluster_ids(self):
-        """The id of every row of :meth:`samples`: what a dead point held when it was killed (0: never labelled), then the live
+        """The id of every row of the unboosted :meth:`samples`: what a dead point held when it was killed (0: never labelled), then the live
         points' ids."""
         if self.cluster_state is None:
             raise ValueError('the run was not asked to cluster (clustering=True)')
@@ -761,12 +946,12 @@ class NestedSampler(E.EngineSampler, NestedRun):
 
     def __init__(self, vega, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, driver='device',
                  sample_params=None, stream=0, chunk=0, lanes=0, const_hint=-1, max_iterations=None, clustering=False,
-                 cluster_posteriors=False):
+                 cluster_posteriors=False, boost_posterior=0.0):
         n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         self.cluster_posteriors = bool(cluster_posteriors)
         NestedRun.__init__(self, None, n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
                            stream=stream, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None),
-                           clustering=bool(clustering) or self.cluster_posteriors)
+                           clustering=bool(clustering) or self.cluster_posteriors, boost_posterior=boost_posterior)
 
     def _advance(self, n_iterations):
         vega = self.vega
@@ -780,13 +965,15 @@ class NestedSampler(E.EngineSampler, NestedRun):
         du, dl, dn, self.iteration, st = vega.engine.nested_run(
             self.cols, self.lo, self.hi, self._theta, self.live_u, self.live_lnl, self.iteration, n_iterations, self.threads,
             self.num_repeats, log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint,
-            chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop, clusters=self.cluster_state)
+            chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=self._stop, clusters=self.cluster_state,
+            **({} if self.phantom_state is None else dict(phantoms=self.phantom_state)))
         return du, dl, dn, st
 
     def write(self, path, name, derived=False, print_func=print):
         """getdist's weighted chain ``name.txt`` (weight / max weight, -lnL, the parameters: :func:`vega_amd.ensemble.write_getdist`),
         ``name.paramnames`` and ``name.stats``; ``derived``: with the derived parameters' columns and lines after the sampled
-        ones.  A sampler built with ``cluster_posteriors`` also writes ``name_cluster_<j>.txt``, j = 1 ... in the order of
+        ones.  With ``boost_posterior > 0`` the chain is the boosted one (PolyChord's posterior file) and ``name.stats`` also
+        carries ``phantom points`` and ``log(Z) boosted``.  A sampler built with ``cluster_posteriors`` also writes ``name_cluster_<j>.txt``, j = 1 ... in the order of
         :meth:`clusters`, and their evidences and masses into ``name.stats``."""
         return write_run(self, path, name, self.names, cluster_posteriors=self.cluster_posteriors,
                          **self._write_extra(derived, print_func, self.derived))
@@ -1041,7 +1228,9 @@ def nested_settings(main_config, sample_params):
     precision, seed, threads, driver, max_iterations}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them.``num_live``, ``num_repeats``, ``precision`` and ``seed`` mean what they
     mean in the reference's ``[Polychord]`` section, with its defaults; ``threads`` None: the sampler's own default.
     ``do_clustering`` / ``cluster_posteriors`` (the reference's keys, both False when absent and then not in the settings;
-    ``cluster_posteriors`` implies ``do_clustering`` and is refused with ``replicas > 1``).  ``mocks = M``: log Z and a weighted
+    ``cluster_posteriors`` implies ``do_clustering`` and is refused with ``replicas > 1``).  ``boost_posterior`` (the reference's
+    key, a float >= 0, in the settings only when the section states it; > 0 is refused with ``mocks``, ``together`` and
+    ``replicas > 1``).  ``mocks = M``: log Z and a weighted
     posterior for each of M Monte-Carlo mocks in one run (the conditions of ``[Ensemble] mocks``); ``together = True`` with
     ``replicas``: a rank's replicas advance as one :class:`NestedSet`; neither combines with ``do_clustering``."""
     sec, limits, out = E.section_settings(main_config, sample_params, 'Nested', name='nested')
@@ -1057,6 +1246,13 @@ def nested_settings(main_config, sample_params):
         if out.get('replicas', 1) > 1:
             raise ValueError('[Nested] cluster_posteriors and replicas > 1 do not combine: the cluster ids of different replicas '
                              'are unrelated')
+    if 'boost_posterior' in sec:                                # (the reference's key, 0.0 when absent and then not in the settings)
+        try:
+            out['boost_posterior'] = sec.getfloat('boost_posterior')
+        except ValueError:
+            raise ValueError('[Nested] boost_posterior: a number, at least 0') from None
+        if not (math.isfinite(out['boost_posterior']) and out['boost_posterior'] >= 0.0):
+            raise ValueError('[Nested] boost_posterior: a finite number, at least 0')
     if 'mocks' in sec:
         out['mocks'] = E._parse_mocks(sec, main_config, 'Nested', 'a nested run')
     if 'together' in sec:
@@ -1066,6 +1262,9 @@ def nested_settings(main_config, sample_params):
             raise ValueError('[Nested] together: True or False') from None
     if out.get('do_clustering') and (out.get('mocks') or out.get('together')):
         raise ValueError('[Nested] do_clustering does not combine with mocks or together: clustering is not part of a set of runs')
+    if out.get('boost_posterior', 0.0) > 0.0 and (out.get('mocks') or out.get('together') or out.get('replicas', 1) > 1):
+        raise ValueError('[Nested] boost_posterior does not combine with mocks, together or replicas > 1: sets of runs and replica '
+                         'merges keep no phantom points (out of scope)')
     if not n + 2 <= out['num_live'] <= MAX_LIVE:
         raise ValueError(f'[Nested] num_live: {n + 2} .. {MAX_LIVE} for {n} sampled parameters')
     if out['threads'] is not None and not 1 <= out['threads'] <= out['num_live'] - n - 1:
@@ -1084,13 +1283,22 @@ def write_run(run, path, name, names, cluster_posteriors=False, **derived):
     :func:`vega_amd.ensemble.write_getdist`.  ``cluster_posteriors`` (a run with clustering): also ``name_cluster_<j>.txt`` for
     j = 1 ... in the order of ``run.clusters()``, the weighted chain of that id alone (with its own ``.paramnames``, so that
     getdist reads it as a chain of its own), and per cluster the lines
-    ``log(Z_j)``, ``mass_j`` and ``id_j`` in ``name.stats``."""
+    ``log(Z_j)``, ``mass_j`` and ``id_j`` in ``name.stats``.  A run with ``boost_posterior > 0``: ``name.txt`` is the boosted
+    chain, the per-cluster chains stay the base run's, and ``name.stats`` ends with ``phantom points`` and ``log(Z) boosted``."""
     pts, lnl, w = run.samples()
     txt, pn = E.write_getdist(path, name, names, pts, lnl, weights=w / w.max(), **derived)
+    boosted = getattr(run, 'phantom_state', None) is not None
     found = run.clusters() if cluster_posteriors else []
     if found:
         ids = run.cluster_ids()
         block = derived.get('derived')
+        if boosted:         # (the per-cluster chains are the base run's: its rows, and their derived rows out of the boosted block)
+            pts, lnl, w = run.samples(boost=False)
+            if block is not None:
+                index = run.boost_index()
+                base = np.empty((ids.size,) + np.asarray(block).shape[1:])
+                base[index[index < ids.size]] = np.asarray(block)[index < ids.size]
+                block = base
         for j, c in enumerate(found, start=1):
             keep = ids == c['id']
             extra = dict(derived, derived=np.asarray(block)[keep]) if block is not None else derived
@@ -1106,6 +1314,8 @@ def write_run(run, path, name, names, cluster_posteriors=False, **derived):
         f.write(f'threads = {run.threads}\n')
         for j, c in enumerate(found, start=1):
             f.write(f'log(Z_{j}) = {c["log_z"]!r}\nmass_{j} = {c["mass"]!r}\nid_{j} = {c["id"]}\n')
+        if boosted:
+            f.write(f'phantom points = {run.phantoms()["lnl"].size}\nlog(Z) boosted = {run.boost_log_evidence()!r}\n')
     return txt, pn, stats
 
 
@@ -1114,6 +1324,6 @@ def read_stats(path):
     out = {}
     for line in Path(path).read_text().splitlines():
         key, _, val = line.partition(' = ')
-        real = key in ('log(Z)', 'log(Z) error', 'H') or key.startswith('log(Z_') or key.startswith('mass_')
+        real = key in ('log(Z)', 'log(Z) error', 'H', 'log(Z) boosted') or key.startswith('log(Z_') or key.startswith('mass_')
         out[key] = float(val) if real else int(val)
     return out
