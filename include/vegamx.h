@@ -12,7 +12,7 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_phantoms, vmx_nested_run_many) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_phantoms, vmx_nested_run_many, vmx_nested_run_many_phantoms) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
  * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
@@ -159,7 +159,7 @@ const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
- * 18 vmx_nested_set_options, 19 vmx_nested_phantoms): lets a foreign binding verify its struct layout at load time. */
+ * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -653,6 +653,44 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E,
                         double* dead_u, double* dead_lnl, int32_t* dead_nlive,
                         int32_t* iterations_done,
                         const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run);
+/* The same set with every run keeping the accepted points inside its threads' walks (boost_posterior for a set; the rule, pinned:
+ * vega_amd/csrc/vmx_nested.h "a set of runs", boost).  The advance launch is k_ns_set_advance_phantoms: one work-group per active
+ * run advances that run's threads, asks vmx_ns::phantom_of and vmx_ns::phantom_kept under the run's own stream, and writes the
+ * round's kept points into the run's own part of one record [E][capacity] behind the run's own running count (a prefix scan inside
+ * the work-group: nothing crosses runs, no atomic decides a place); a run whose iteration ends in that launch records first.  The
+ * base runs - dead records, live points, statuses, statistics, the engine's batches - are bit for bit those of vmx_nested_run_many;
+ * no likelihood row is added.  The arguments before `phantoms` are those of vmx_nested_run_many, with its checks.
+ *   phantoms  fraction: as for vmx_nested_run_phantoms, the same for every run; 0 (or phantoms NULL) runs exactly
+ *                       vmx_nested_run_many - its kernels, k_ns_set_advance among them - and touches nothing in the struct
+ *             capacity: rows per run of the arrays below, at least n_iterations K (num_repeats - 1)
+ *             u [E][capacity][n], lnl, birth [E][capacity], iteration (int64), thread, repeat [E][capacity] host: run e's kept
+ *                       points in rows e capacity .. e capacity + count[e] - 1, in the order the run accepted them (sort by the
+ *                       tags for the canonical order); the rows behind them, up to iterations_done[e] K (num_repeats - 1), may be
+ *                       overwritten with anything
+ *             count [E] host, out: the rows written per run (0 for a run that was never entered)
+ *             flags, reserved: 0
+ * The counts stay on the device while the set runs and come back, with the record, in the copy that brings the dead records:
+ * stats->host_waits is what it is without phantoms.
+ * Refused in addition (-1, the engine untouched): a fraction outside [0, 1] or NaN, a missing array, a capacity below
+ * n_iterations K (num_repeats - 1), non-zero flags. */
+typedef struct {
+    double fraction;
+    int64_t capacity;
+    double* u; double* lnl; double* birth;
+    int64_t* iteration; int32_t* thread; int32_t* repeat;
+    int64_t* count;
+    uint32_t flags, reserved;
+} vmx_nested_set_phantoms;
+int vmx_nested_run_many_phantoms(vmx_engine* e, const vmx_nested_spec* spec, int32_t E,
+                                 const uint64_t* streams, const int32_t* mock_row,
+                                 double* live_u, double* live_lnl,
+                                 int64_t* iteration,
+                                 int32_t* status,
+                                 int32_t n_iterations,
+                                 double* dead_u, double* dead_lnl, int32_t* dead_nlive,
+                                 int32_t* iterations_done,
+                                 const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run,
+                                 vmx_nested_set_phantoms* phantoms);
 /* Evidence and an equal-weight posterior where the particles live: tempered sequential Monte Carlo (the scheme of pocoMC, the
  * reference's second sampler in bin/run_vega_mpi.py, without its normalising flow), every decision pinned in
  * vega_amd/csrc/vmx_smc.h.  N particles walk from the prior (beta = 0) to the posterior (beta = 1); a stage picks the next beta by

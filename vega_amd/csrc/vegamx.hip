@@ -720,8 +720,9 @@ __device__ __forceinline__ void ns_iteration_end(const NsDev& D, const NsCluster
 // The kept phantom points of the round (`keeps`: this lane's threads, bit j = thread k0 + j) behind the F.count rows the call has
 // written: a second scan over s_scan (free again after ns_advance_threads' last barrier) places them in thread order, s_list holds
 // the accepting threads, and the lanes write the record one column per lane.  A kept point's thread goes on walking: T.x is the
-// accepted point, T.lnl its lnL, T.repeat its index.  The running count goes to the host beside the row count.
-template <bool CLUSTER>
+// accepted point, T.lnl its lnL, T.repeat its index.  The running count goes to the host beside the row count (HOST_COUNT; a set of
+// runs keeps every run's count in device memory: that word is the set's total).
+template <bool CLUSTER, bool HOST_COUNT = true>
 __device__ __forceinline__ void ns_record_phantoms(const NsDev& D, const NsClusterRun& X, const NsPhantomRun& F, int64_t it, uint32_t keeps,
                                                    int32_t* s_scan, int32_t* s_list)
 {
@@ -764,7 +765,7 @@ __device__ __forceinline__ void ns_record_phantoms(const NsDev& D, const NsClust
     }
     if (threadIdx.x == 0) {
         *F.count = base + total;
-        *(long long*)(D.host_word + 2) = (long long)(base + total);
+        if constexpr (HOST_COUNT) *(long long*)(D.host_word + 2) = (long long)(base + total);
     }
 }
 
@@ -887,6 +888,33 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_set_advance(NsSetDev S)
     const int run = S.active[blockIdx.x];
     const NsDev D = ns_view(S, run);
     const int total = ns_advance_threads<false>(D, NsClusterRun{}, S.it0[run] + S.done[run], s_scan, nullptr);
+    if (total == 0) ns_iteration_end<false>(D, NsClusterRun{}, (int64_t)S.done[run]);
+    if (threadIdx.x == 0) S.count[blockIdx.x] = total;
+}
+
+// run `run`'s part of the set's phantom record [E][capacity] (vmx_ns::set_phantom_row) and its own running count: F is run 0's
+__device__ __forceinline__ NsPhantomRun ns_phantom_view(const NsPhantomRun& F, int run, int n)
+{
+    NsPhantomRun G = F;
+    const size_t r = (size_t)vmx_ns::set_phantom_row(run, F.capacity, 0, 0);
+    G.u += r * (size_t)n; G.lnl += r; G.birth += r; G.iteration += r; G.thread += r; G.repeat += r;
+    G.count += run;
+    return G;
+}
+
+// k_ns_set_advance keeping the kept phantom points of the round (vmx_nested_run_many_phantoms): the advance with the PHANTOM step,
+// then the placing scan and the column writes of ns_record_phantoms on the run's own part of the record behind the run's own
+// count - nothing crosses runs, no atomic decides a place - and then the end of the iteration.  Holds 4 KB + 16 KB of LDS.
+__global__ __launch_bounds__(NS_THREADS) void k_ns_set_advance_phantoms(NsSetDev S, NsPhantomRun F)
+{
+    __shared__ int32_t s_scan[NS_THREADS];
+    __shared__ int32_t s_phantom_thread[vmx_ns::MAX_LIVE];
+    const int run = S.active[blockIdx.x];
+    const NsDev D = ns_view(S, run);
+    const int64_t it = S.it0[run] + S.done[run];
+    uint32_t keeps = 0;
+    const int total = ns_advance_threads<false, true>(D, NsClusterRun{}, it, s_scan, nullptr, F.fraction, &keeps);
+    ns_record_phantoms<false, false>(D, NsClusterRun{}, ns_phantom_view(F, run, D.n), it, keeps, s_scan, s_phantom_thread);
     if (total == 0) ns_iteration_end<false>(D, NsClusterRun{}, (int64_t)S.done[run]);
     if (threadIdx.x == 0) S.count[blockIdx.x] = total;
 }
@@ -1820,6 +1848,7 @@ int vmx_struct_size(int32_t which)
         case 17: return (int)sizeof(vmx_nested_clusters);
         case 18: return (int)sizeof(vmx_nested_set_options);
         case 19: return (int)sizeof(vmx_nested_phantoms);
+        case 20: return (int)sizeof(vmx_nested_set_phantoms);
         default: return -1;
     }
 }
@@ -5158,13 +5187,44 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
 
 // E independent runs advanced together (vmx_nested.h "a set of runs"): per set round one launch heads the runs whose iteration
 // begins, one advances every thread of every active run, one packs the requests of all runs into the engine's rows; the host
-// waits once per round
+// waits once per round.  `phantoms` (vmx_nested_run_many_phantoms): every run keeps its phantom record, the advance launch is
+// k_ns_set_advance_phantoms; nullptr: the launches are what they were.
+static int nested_run_many(const char* who, vmx_engine* e, const vmx_nested_spec* spec, int32_t E, const uint64_t* streams,
+                           const int32_t* mock_row, double* live_u, double* live_lnl, int64_t* iteration, int32_t* status,
+                           int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive, int32_t* iterations_done,
+                           const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run,
+                           vmx_nested_set_phantoms* phantoms);
+
 int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
                         double* live_u, double* live_lnl, int64_t* iteration, int32_t* status, int32_t n_iterations,
                         double* dead_u, double* dead_lnl, int32_t* dead_nlive, int32_t* iterations_done,
                         const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run)
 {
-    const std::string name("vmx_nested_run_many");
+    return nested_run_many("vmx_nested_run_many", e, spec, E, streams, mock_row, live_u, live_lnl, iteration, status, n_iterations,
+                           dead_u, dead_lnl, dead_nlive, iterations_done, opt, stats, per_run, nullptr);
+}
+
+int vmx_nested_run_many_phantoms(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
+                                 double* live_u, double* live_lnl, int64_t* iteration, int32_t* status, int32_t n_iterations,
+                                 double* dead_u, double* dead_lnl, int32_t* dead_nlive, int32_t* iterations_done,
+                                 const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run,
+                                 vmx_nested_set_phantoms* phantoms)
+{
+    const std::string name("vmx_nested_run_many_phantoms");
+    if (phantoms) REQUIRE(phantoms->fraction >= 0.0 && phantoms->fraction <= 1.0, name + ": the kept fraction lies in [0, 1]");
+    // (fraction 0: the set without phantoms, and nothing in the struct is touched)
+    return nested_run_many("vmx_nested_run_many_phantoms", e, spec, E, streams, mock_row, live_u, live_lnl, iteration, status,
+                           n_iterations, dead_u, dead_lnl, dead_nlive, iterations_done, opt, stats, per_run,
+                           phantoms && phantoms->fraction > 0.0 ? phantoms : nullptr);
+}
+
+static int nested_run_many(const char* who, vmx_engine* e, const vmx_nested_spec* spec, int32_t E, const uint64_t* streams,
+                           const int32_t* mock_row, double* live_u, double* live_lnl, int64_t* iteration, int32_t* status,
+                           int32_t n_iterations, double* dead_u, double* dead_lnl, int32_t* dead_nlive, int32_t* iterations_done,
+                           const vmx_nested_set_options* opt, vmx_nested_stats* stats, int64_t* per_run,
+                           vmx_nested_set_phantoms* phantoms)
+{
+    const std::string name(who);
     REQUIRE(e && e->finalized && spec && live_u && live_lnl && iteration && status && iterations_done, name);
     REQUIRE(E >= 1, name + ": at least one run");
     REQUIRE(streams, name + ": a Philox stream for every run");
@@ -5201,6 +5261,17 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, c
                 REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
                 REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
             }
+    const bool recording = phantoms != nullptr;
+    int64_t ph_need = 0;                // (what one run can keep in this call at the most: the rows of its part of the device record)
+    if (recording) {
+        REQUIRE(phantoms->flags == 0, name + ": phantoms->flags 0");
+        REQUIRE((double)n_iterations * K * ((double)spec->num_repeats - 1.0) * E * (8.0 * n + 36.0) < 9.0e18, name + ": the phantom record is too large");
+        ph_need = vmx_ns::set_phantom_capacity(n_iterations, K, spec->num_repeats);
+        REQUIRE(phantoms->capacity >= ph_need, name + ": phantoms->capacity below n_iterations K (num_repeats - 1)");
+        REQUIRE(phantoms->count, name + ": phantoms->count [E]");
+        REQUIRE(ph_need == 0 || (phantoms->u && phantoms->lnl && phantoms->birth && phantoms->iteration && phantoms->thread &&
+                                 phantoms->repeat), name + ": the phantom record");
+    }
     if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const size_t cap = EL;          // (K < nlive: the draw's rows are the most a launch writes)
 
@@ -5213,6 +5284,11 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, c
         ensure(S.th, EK * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, EK) || ensure(S.dead_u, E * rec_rows * n) ||
         ensure(S.dead_lnl, E * rec_rows) || ensure(S.dead_n, E * rec_rows) || ensure(S.counters, E) || ensure(S.set_ctl, (size_t)3 * E) ||
         ensure(S.set_count, E) || ensure(S.streams, E) || ensure(S.it0, E) || (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, cap))))
+        return -2;
+    const size_t ph_rows = (size_t)E * (size_t)std::max<int64_t>(ph_need, 1);
+    if (recording &&
+        (ensure(S.ph_u, ph_rows * n) || ensure(S.ph_lnl, ph_rows) || ensure(S.ph_birth, ph_rows) || ensure(S.ph_it, ph_rows) ||
+         ensure(S.ph_thread, ph_rows) || ensure(S.ph_repeat, ph_rows) || ensure(S.ph_count, E)))
         return -2;
     if (!S.pin_word) {
         HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
@@ -5258,6 +5334,12 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, c
     X.mock_row = mock_row ? S.mock_row.p : nullptr; X.mock = mock_row ? S.mock.p : nullptr;
     X.count = S.set_count.p; X.host_count = S.dpin_count; X.rec_rows = (int32_t)rec_iter;
     const int32_t* d_mock = mock_row ? S.mock.p : nullptr;
+    NsPhantomRun F{};
+    if (recording) {
+        HIP_OK(hipMemsetAsync(S.ph_count.p, 0, (size_t)E * sizeof(int64_t), st));
+        F = NsPhantomRun{S.ph_u.p, S.ph_lnl.p, S.ph_birth.p, S.ph_it.p, S.ph_thread.p, S.ph_repeat.p, nullptr, S.ph_count.p,
+                         ph_need, phantoms->fraction};      // (run e's part of the device record: the rows from e ph_need)
+    }
 
     // the engine as the sampler's likelihood, at the table level the sampled columns allow
     LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
@@ -5304,7 +5386,8 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, c
         H = vmx_ns::heading_list(active, A, phase.data(), heading);
         if (put_lists()) return -2;
         if (H > 0) hipLaunchKernelGGL(k_ns_set_head, dim3(H), dim3(NS_THREADS), 0, st, X);
-        hipLaunchKernelGGL(k_ns_set_advance, dim3(A), dim3(NS_THREADS), 0, st, X);
+        if (recording) hipLaunchKernelGGL(k_ns_set_advance_phantoms, dim3(A), dim3(NS_THREADS), 0, st, X, F);
+        else hipLaunchKernelGGL(k_ns_set_advance, dim3(A), dim3(NS_THREADS), 0, st, X);
         hipLaunchKernelGGL(k_ns_set_emit, dim3(A), dim3(NS_THREADS), 0, st, X);
         HIP_OK(hipGetLastError());
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -5340,10 +5423,29 @@ int vmx_nested_run_many(vmx_engine* e, const vmx_nested_spec* spec, int32_t E, c
         HIP_OK(hipMemcpyAsync(dead_u + h * n, S.dead_u.p + r * n, rows * n * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(dead_lnl + h, S.dead_lnl.p + r, rows * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(dead_nlive + h, S.dead_n.p + r, rows * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (!recording || ph_need == 0) continue;
+        // the run's count is on the device: the rows its done[q] iterations can have kept at the most come back in this copy
+        // (the kept ones lead them), and the counts behind them
+        const size_t c = (size_t)vmx_ns::set_phantom_capacity(done[q], K, spec->num_repeats);
+        const size_t dr = (size_t)vmx_ns::set_phantom_row(q, ph_need, 0, 0), hr = (size_t)vmx_ns::set_phantom_row(q, phantoms->capacity, 0, 0);
+        HIP_OK(hipMemcpyAsync(phantoms->u + hr * n, S.ph_u.p + dr * n, c * n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->lnl + hr, S.ph_lnl.p + dr, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->birth + hr, S.ph_birth.p + dr, c * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->iteration + hr, S.ph_it.p + dr, c * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->thread + hr, S.ph_thread.p + dr, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(phantoms->repeat + hr, S.ph_repeat.p + dr, c * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
+    std::vector<int64_t> ph_count(E, 0);
+    if (recording) HIP_OK(hipMemcpyAsync(ph_count.data(), S.ph_count.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(own.data(), S.counters.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     R.host_waits += 1;
+    if (recording)
+        for (int q = 0; q < E; ++q) {
+            if (ph_count[q] < 0 || ph_count[q] > vmx_ns::set_phantom_capacity(done[q], K, spec->num_repeats))
+                return fail(-2, name + ": a run's phantom record overran its capacity");
+            phantoms->count[q] = ph_count[q];
+        }
     for (int q = 0; q < E; ++q) {
         iterations_done[q] = done[q];
         iteration[q] += done[q];

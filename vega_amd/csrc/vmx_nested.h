@@ -4,7 +4,7 @@
 // k_ns_advance moves every thread's state machine by one likelihood answer and compacts the next requests);
 // vega_amd/nested.py restates every expression below in NumPy (the `python` driver) and tests/helpers/nested_driver.cpp compiles
 // this header with g++ so that tests/test_nested_host.py can hold the two against each other bit for bit (the boost part:
-// tests/helpers/nested_boost_driver.cpp, tests/test_nested_boost_host.py).  No HIP type, no heap.
+// tests/helpers/nested_boost_driver.cpp, tests/test_nested_boost_host.py; boost in a set: tests/helpers/nested_set_boost_driver.cpp).  No HIP type, no heap.
 //
 //   cube             the sampler works in u in [0, 1]^n; a physical parameter is lo + (hi - lo) u (map_cube), a uniform prior over
 //                    the limits.  lnL = log_norm - 0.5 chi2 (vmx_ens::log_lik); a failed model (!vmx_ens::model_ok) has
@@ -70,6 +70,10 @@
 //                    stay in WALK.  Runs do not wait for each other: a run whose iteration ended in round r is headed in
 //                    round r + 1.  The iteration index of run e is iteration[e] + iterations_done[e], its record row
 //                    iterations_done[e].
+//     boost          (vmx_nested_run_many_phantoms) every run keeps its own phantom record by the rule of "boost" below, under its
+//                    own stream: run e's kept points of a call lie in the rows [e capacity, e capacity + count[e]) of one record
+//                    [E][capacity] (set_phantom_row), in the order that run accepted them, behind that run's own running count;
+//                    a call needs capacity >= n_iterations K (num_repeats - 1) (set_phantom_capacity).  Nothing crosses runs.
 //
 //   boost            (optional: vmx_nested_run_phantoms; off, everything above is what a run does) the accepted points inside a
 //                    thread's walk are kept beside the dead record instead of being thrown away - no likelihood row is spent.
@@ -576,5 +580,14 @@ VMX_HD inline int compact_active(int32_t* active, int A, const int32_t* phase)
         if (phase[active[a]] != OUT) active[B++] = active[a];
     return B;
 }
+
+// boost in a set: the rows a call's phantom record needs per run (what one run can keep at the most) ...
+VMX_HD inline int64_t set_phantom_capacity(int64_t n_iterations, int64_t K, int64_t num_repeats)
+{
+    return n_iterations * K * (num_repeats - 1);
+}
+
+// ... and the row of the record [E][capacity] that holds the p-th point a round adds behind the `count` rows `run` has written
+VMX_HD inline int64_t set_phantom_row(int64_t run, int64_t capacity, int64_t count, int64_t p) { return run * capacity + count + p; }
 
 }  // namespace vmx_ns

@@ -183,6 +183,37 @@ class NestedPhantoms(C.Structure):
                 ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+class NestedSetPhantoms(C.Structure):
+    _fields_ = [('fraction', C.c_double), ('capacity', C.c_int64), ('u', C.POINTER(C.c_double)), ('lnl', C.POINTER(C.c_double)),
+                ('birth', C.POINTER(C.c_double)), ('iteration', C.POINTER(C.c_int64)), ('thread', C.POINTER(C.c_int32)),
+                ('repeat', C.POINTER(C.c_int32)), ('count', C.POINTER(C.c_int64)), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
+class PhantomArrays:
+    """The phantom record of one call of :meth:`Engine.nested_run_many` (include/vegamx.h: vmx_nested_set_phantoms): the kept
+    ``fraction``, ``capacity`` rows per run and the host arrays ``u`` [E, capacity, n], ``lnl``, ``birth``, ``iteration`` (int64),
+    ``thread``, ``repeat`` [E, capacity] and ``count`` int64 [E] (out: the rows every run wrote); ``flags``: 0."""
+
+    def __init__(self, runs, capacity, n, fraction, flags=0):
+        self.E, self.capacity, self.n, self.fraction, self.flags = int(runs), int(capacity), int(n), float(fraction), int(flags)
+        rows = max(self.capacity, 0)
+        self.u, self.lnl, self.birth = np.empty((self.E, rows, self.n)), np.empty((self.E, rows)), np.empty((self.E, rows))
+        self.iteration = np.empty((self.E, rows), dtype=np.int64)
+        self.thread, self.repeat = np.empty((self.E, rows), dtype=np.int32), np.empty((self.E, rows), dtype=np.int32)
+        self.count = np.zeros(self.E, dtype=np.int64)
+
+    def struct(self):
+        return NestedSetPhantoms(self.fraction, self.capacity, _dp(self.u), _dp(self.lnl), _dp(self.birth),
+                                 self.iteration.ctypes.data_as(C.POINTER(C.c_int64)), _ip(self.thread), _ip(self.repeat),
+                                 self.count.ctypes.data_as(C.POINTER(C.c_int64)), self.flags, 0)
+
+    def run(self, e):
+        """Run ``e``'s rows in the order they were written: (u [N, n], lnl [N], birth [N], tag [N, 3] int64)."""
+        c = int(self.count[e])
+        return (self.u[e, :c].copy(), self.lnl[e, :c].copy(), self.birth[e, :c].copy(),
+                np.stack([self.iteration[e, :c], self.thread[e, :c].astype(np.int64), self.repeat[e, :c].astype(np.int64)], axis=1))
+
+
 VMX_SMC_MAX_PARTICLES = 4096
 VMX_SMC_REC = 8
 
@@ -298,6 +329,7 @@ def load_library():
     lib.vmx_nested_run_many.argtypes = [C.c_void_p, C.POINTER(NestedSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
                                         C.POINTER(C.c_int64), iptr, C.c_int32, dptr, dptr, iptr, iptr, C.POINTER(NestedSetOptions),
                                         C.POINTER(NestedStats), C.POINTER(C.c_int64)]
+    lib.vmx_nested_run_many_phantoms.argtypes = lib.vmx_nested_run_many.argtypes + [C.POINTER(NestedSetPhantoms)]
     lib.vmx_smc_run.argtypes = [C.c_void_p, C.POINTER(SmcSpec), dptr, dptr, C.POINTER(C.c_int64), dptr, dptr, C.c_int32, dptr, dptr,
                                 iptr, C.POINTER(SmcOptions), C.POINTER(SmcStats)]
     lib.vmx_smc_run_many.argtypes = [C.c_void_p, C.POINTER(SmcSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
@@ -339,7 +371,8 @@ def load_library():
     lib.vmx_struct_size.argtypes = [C.c_int32]
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
-                                    SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms)):
+                                    SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms,
+                                    NestedSetPhantoms)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -371,7 +404,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1245,7 +1278,7 @@ class Engine:
         return dead_u[:m], dead_lnl[:m], dead_n[:m], int(it.value), _stats_dict(stats)
 
     def nested_run_many(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, streams, n_iterations, threads, num_repeats,
-                        mock_rows=None, log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None):
+                        mock_rows=None, log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, phantoms=None):
         """Up to ``n_iterations`` iterations of each of E independent nested-sampling runs in one device run (include/vegamx.h:
         vmx_nested_run_many): ``live_u`` [E, nlive, n] / ``live_lnl`` [E, nlive] the runs' state and ``iteration`` int64 [E] their
         next iterations (all updated in place; a run without a finite live lnL keeps what it had), ``streams`` [E] the Philox
@@ -1253,7 +1286,10 @@ class Engine:
         :meth:`nested_run`.  ``stop(run, iterations, dead_lnl [K], live_lnl [nlive])`` is asked after every iteration of every
         run; a true answer ends that run.  Returns (dead: per run (dead_u [m K, n], dead_lnl [m K], dead_nlive [m K]) for its m
         iterations done, status int32 [E], iterations_done int32 [E], statistics); the statistics carry ``per_run`` int64
-        [E, 3]: rows evaluated, rows that were a thread's own position, set rounds the run took part in."""
+        [E, 3]: rows evaluated, rows that were a thread's own position, set rounds the run took part in.  ``phantoms`` (a
+        :class:`PhantomArrays` of E runs, at least ``n_iterations threads (num_repeats - 1)`` rows each): the set through
+        vmx_nested_run_many_phantoms - every run's kept phantom points of this call are written into it (``phantoms.run(e)``); the
+        runs themselves are the same runs."""
         _in_place(np.float64, live_u=live_u, live_lnl=live_lnl)
         _in_place(np.int64, iteration=iteration)
         if live_u.ndim != 3 or live_lnl.shape != live_u.shape[:2]:
@@ -1287,11 +1323,17 @@ class Engine:
         callback = NESTED_SET_STOP(_stop) if stop is not None else NESTED_SET_STOP()
         opt = NestedSetOptions(int(const_hint), int(chunk), int(lanes), 1 if draw_live else 0, callback, None)
         stats = NestedStats()
-        self._check(self.lib.vmx_nested_run_many(
-            self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), _dp(live_u), _dp(live_lnl), iteration.ctypes.data_as(C.POINTER(C.c_int64)),
-            _ip(status), n_iterations, _dp(dead_u), _dp(dead_lnl), _ip(dead_n), _ip(done), C.byref(opt), C.byref(stats),
-            per.ctypes.data_as(C.POINTER(C.c_int64))))
+        args = (self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+                None if mock_rows is None else _ip(mock_rows), _dp(live_u), _dp(live_lnl), iteration.ctypes.data_as(C.POINTER(C.c_int64)),
+                _ip(status), n_iterations, _dp(dead_u), _dp(dead_lnl), _ip(dead_n), _ip(done), C.byref(opt), C.byref(stats),
+                per.ctypes.data_as(C.POINTER(C.c_int64)))
+        if phantoms is None:
+            self._check(self.lib.vmx_nested_run_many(*args))
+        else:
+            if not isinstance(phantoms, PhantomArrays) or phantoms.E != E or phantoms.n != cols.size:
+                raise ValueError('phantoms: a PhantomArrays of the set\'s E runs and n sampled parameters')
+            ph = phantoms.struct()
+            self._check(self.lib.vmx_nested_run_many_phantoms(*args, C.byref(ph)))
         if raised:
             raise raised[0]
         dead = [(dead_u[e, :int(done[e]) * K].copy(), dead_lnl[e, :int(done[e]) * K].copy(), dead_n[e, :int(done[e]) * K].copy())

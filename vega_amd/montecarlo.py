@@ -497,21 +497,25 @@ class MonteCarlo:
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
-                            fiducial_model=None):
+                            fiducial_model=None, boost_posterior=0.0):
         """The evidence and a weighted posterior of every Monte-Carlo mock by nested sampling, M runs advanced together in one
         device run (:class:`vega_amd.nested.NestedSet`: run m on mock m and stream m; ``num_live``, ``num_repeats``, ``threads``,
         ``precision``, ``max_iterations`` its settings; every run ends on its own termination test).  The mocks, ``seed``,
         ``scale``, ``sample_params`` and ``driver`` as for :meth:`sample_mocks`.  It keeps in ``mc_posteriors``: ``sampler`` =
         'nested', names, the weighted ``mean`` / ``sd`` / ``covariance``, ``log_z``, ``log_z_err``, ``info`` (NaN for a run
         without a finite live lnL), ``iterations``, ``status`` and the settings; with ``keep_chains`` ``mc_chains`` holds per mock
-        the tuple (points, lnL, weights) of its samples and ``mc_chain_lnl`` their lnL.  Returns the set."""
+        the tuple (points, lnL, weights) of its samples and ``mc_chain_lnl`` their lnL.  ``boost_posterior`` = b > 0
+        (:class:`NestedSet`): every run keeps the accepted points inside its walks, the samples - and with them the weighted
+        mean, sd and covariance - are the boosted chains', and ``mc_posteriors`` gains ``boost_posterior``, ``phantoms`` [M] (kept
+        points per mock), ``n_eff`` [M] (the Kish size 1 / sum w^2 of the chain used) and ``log_z_boost`` [M] (a diagnostic:
+        ``log_z`` stays the base run's); at b = 0 the dict has the keys it had.  Returns the set."""
         return self._sample_mocks(num_mocks, mocks, None, 0, None, 1, seed, scale, sample_params, driver, keep_chains, fiducial_model,
                                   'nested', None, 0.5, None, num_live=num_live, num_repeats=num_repeats, threads=threads,
-                                  precision=precision, max_iterations=max_iterations)
+                                  precision=precision, max_iterations=max_iterations, boost_posterior=boost_posterior)
 
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
-                      max_iterations=None):
+                      max_iterations=None, boost_posterior=0.0):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -554,7 +558,8 @@ class MonteCarlo:
         elif nested:
             from .nested import NestedSet
             sampler = NestedSet(vega, M, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
-                                mock_rows=np.arange(M), driver=driver, max_iterations=max_iterations, sample_params=sample_params)
+                                mock_rows=np.arange(M), driver=driver, max_iterations=max_iterations, sample_params=sample_params,
+                                **({'boost_posterior': boost_posterior} if boost_posterior else {}))
         else:
             sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
                                   sample_params=sample_params)
@@ -601,6 +606,12 @@ class MonteCarlo:
                 info=sampler.information(), iterations=sampler.iteration.copy(), status=sampler.status.copy(),
                 num_live=sampler.num_live, num_repeats=sampler.num_repeats, threads=sampler.threads, precision=sampler.precision,
                 seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+            if sampler.boost_posterior > 0.0:
+                self.mc_posteriors.update(
+                    boost_posterior=sampler.boost_posterior, log_z_boost=sampler.boost_log_evidence(),
+                    phantoms=np.array([0 if part is None else sampler.phantoms(m)['lnl'].size for m, part in enumerate(found)],
+                                      dtype=np.int64),
+                    n_eff=np.array([np.nan if part is None else 1.0 / np.sum(part[2] * part[2]) for part in found]))
             self.mc_chains = found if keep_chains else None
             self.mc_chain_lnl = [None if part is None else part[1] for part in found] if keep_chains else None
             return sampler
@@ -624,7 +635,8 @@ class MonteCarlo:
         ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
         ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED``; after
         ``sample_mocks_nested`` ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``info``, ``iterations``,
-        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``NUMLIVE``, ``NREPEATS``, ``THREADS``, ``PRECISN``, ``SEED``.
+        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``NUMLIVE``, ``NREPEATS``, ``THREADS``, ``PRECISN``, ``SEED``
+        (with ``boost_posterior > 0`` also the columns ``phantoms``, ``n_eff``, ``log_z_boost`` and the header key ``BOOST``).
         Returns the path."""
         from pathlib import Path
         from . import fitslite
@@ -650,6 +662,10 @@ class MonteCarlo:
                      ('status', 'K', np.asarray(post['status'], dtype=np.int64)), cov_col]
             header = {'SAMPLER': 'NESTED', 'NUMLIVE': post['num_live'], 'NREPEATS': post['num_repeats'], 'THREADS': post['threads'],
                       'PRECISN': post['precision'], 'SEED': post['seed']}
+            if post.get('boost_posterior', 0.0) > 0.0:
+                cols += [('phantoms', 'K', np.asarray(post['phantoms'], dtype=np.int64)), ('n_eff', 'D', post['n_eff']),
+                         ('log_z_boost', 'D', post['log_z_boost'])]
+                header['BOOST'] = post['boost_posterior']
         else:
             for j, nm in enumerate(names):
                 cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]

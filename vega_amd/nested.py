@@ -16,9 +16,12 @@ neighbours, whitens each on its own and keeps persistent ids, so that separated 
 
 ``boost_posterior`` (the reference's key) keeps the accepted points inside the threads' walks - each a uniform draw from its
 iteration's contour that the engine has already evaluated - as a phantom record beside the dead one and merges them into the
-weighted chain (:func:`boosted_weights`); the evidence and its error stay those of the base run.
+weighted chain (:func:`boosted_weights`); the evidence and its error stay those of the base run.  A set of runs
+(:class:`NestedSet`, ``boost_posterior``) keeps one phantom record per run - on the device through vmx_nested_run_many_phantoms -
+and replicas merge with their phantoms (:func:`vega_amd.replicas.merge_nested_boosted`); the ``[Nested]`` settings still refuse
+``boost_posterior > 0`` with ``mocks``, ``together`` and ``replicas > 1``: sets and merges are boosted through Python.
 
-What is not here: resume files; ``boost_posterior`` for sets of runs, replica merges and per-cluster chains.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
+What is not here: resume files; clustering in sets; ``boost_posterior`` for per-cluster chains.  The reference's other sampler, pocoMC, has its counterpart in vega_amd/smc.py.
 """
 import math
 import time
@@ -531,8 +534,18 @@ def compact_active(active, phase):
     return [e for e in active if phase[e] != OUT]
 
 
+def set_iterations_per_call(runs, K, num_repeats, n, boost):
+    """Iterations per call of a set's driver: the dead record of a call is allocated up front (65536 // K), and with ``boost``
+    the phantom records of all ``runs`` runs at their capacity K (num_repeats - 1) rows per run and iteration
+    (vmx_ns::set_phantom_capacity) stay under PHANTOM_BUDGET bytes together; 0: not even one iteration fits."""
+    per_call = max(1, 65536 // K)
+    if boost and num_repeats > 1:
+        per_call = min(per_call, PHANTOM_BUDGET // (runs * K * (num_repeats - 1) * phantom_row_bytes(n)))
+    return per_call
+
+
 def python_iterations_many(live_u, live_lnl, iteration, n_iterations, K, num_repeats, seed, streams, evaluate, stop=None, draw=False,
-                           watch=None):
+                           watch=None, boost=None):
     """Up to ``n_iterations`` iterations of each of E runs in NumPy (vmx_nested_run_many restated over :func:`iteration_head` and
     :class:`Threads`): ``live_u`` [E, nlive, n], ``live_lnl`` [E, nlive], ``iteration`` int64 [E] the runs' state, updated in place
     (a run without a finite live lnL keeps what it had at entry), ``streams`` [E].  A set round heads the runs in HEAD, advances
@@ -543,8 +556,16 @@ def python_iterations_many(live_u, live_lnl, iteration, n_iterations, K, num_rep
     drawn and evaluated first.  ``watch(round, state)`` sees every round before the host's turn.  Returns (dead: per run
     (dead_u, dead_lnl, dead_nlive) of the iterations done, status int32 [E]: 0 still going, 1 stopped, 2 no live point with a
     finite lnL; iterations_done int32 [E]; statistics with ``per_run`` int64 [E, 3]: rows evaluated, own-position rows, set
-    rounds the run took part in)."""
+    rounds the run took part in).  ``boost``: a list of E :class:`PhantomState` - run e's kept phantom points of this call are
+    appended to ``boost[e]`` as :func:`python_iterations` appends a run's (vmx_nested_run_many_phantoms; the phases, lists,
+    packing order and rows are the same with or without it)."""
     E, nlive, n = live_u.shape
+    if boost is not None:
+        if len(boost) != E:
+            raise ValueError(f'boost: one PhantomState for each of the {E} runs')
+        if all(b.fraction == 0.0 for b in boost):
+            boost = None
+    ph = [dict(u=[], lnl=[], birth=[], tag=[]) for _ in range(E)]
     entry = (live_u.copy(), live_lnl.copy())
     per = np.zeros((E, 3), dtype=np.int64)
     status = np.zeros(E, dtype=np.int32)
@@ -577,7 +598,22 @@ def python_iterations_many(live_u, live_lnl, iteration, n_iterations, K, num_rep
             phase[e] = WALK
         requests, count = {}, []
         for e in active:
-            requests[e] = T[e].requests(T[e].advance(answer[e]))
+            if boost is None or boost[e].fraction == 0.0:
+                requests[e] = T[e].requests(T[e].advance(answer[e]))
+            else:
+                t = T[e]
+                was, inside = t.state.copy(), t.inside.copy()
+                asks = t.advance(answer[e])
+                r = phantom_of(was, inside, answer[e], t.lstar, t.repeat, num_repeats)
+                kp = np.flatnonzero(r > 0)
+                kp = kp[phantom_kept(kp, t.iteration, r[kp], boost[e].fraction, seed, int(streams[e]))]
+                if kp.size:     # (before the end of the iteration, should it end in this round: T.x is the accepted point)
+                    ph[e]['u'].append(t.x[kp].copy())
+                    ph[e]['lnl'].append(t.lnl[kp].copy())
+                    ph[e]['birth'].append(np.full(kp.size, t.lstar, dtype=np.float64))
+                    ph[e]['tag'].append(np.stack([np.full(kp.size, t.iteration, dtype=np.int64), kp.astype(np.int64),
+                                                  r[kp].astype(np.int64)], axis=1))
+                requests[e] = t.requests(asks)
             count.append(requests[e][0].size)
         offset, total = row_offsets(count)
         for e, c in zip(active, count):
@@ -614,6 +650,15 @@ def python_iterations_many(live_u, live_lnl, iteration, n_iterations, K, num_rep
             out.append((np.empty((0, n)), np.empty(0), np.empty(0, dtype=np.int32)))
         else:
             out.append(tuple(np.concatenate(part) for part in dead[e]))
+    if boost is not None:
+        for e in range(E):
+            if boost[e].fraction == 0.0:
+                continue
+            got = ph[e]
+            boost[e].append(np.concatenate(got['u']) if got['u'] else np.empty((0, n)),
+                            np.concatenate(got['lnl']) if got['lnl'] else np.empty(0),
+                            np.concatenate(got['birth']) if got['birth'] else np.empty(0),
+                            np.concatenate(got['tag']) if got['tag'] else np.empty((0, 3), dtype=np.int64))
     st.update(iterations=int(done.sum()), rows_own_position=int(per[:, 1].sum()), per_run=per)
     return out, status, done, st
 
@@ -984,10 +1029,12 @@ class NestedRunSet:
     to) advanced together by :func:`python_iterations_many`: run e is the :class:`NestedRun` on the Philox stream ``streams[e]``
     (default ``range(E)``), with its own dead record, termination test and evidence (``runs[e]``).  :class:`NestedSet` puts the
     engine behind it.  ``status`` [E]: 0 the run goes on, 1 its termination test ended it, 2 no drawn live point has a finite lnL
-    (such a run is left out; the others are not affected)."""
+    (such a run is left out; the others are not affected).  ``boost_posterior`` = b >= 0 (0: off) as for :class:`NestedRun`:
+    every run keeps its own phantom record (:meth:`phantoms`) and :meth:`samples` merges it in; the runs, their evidences and
+    their termination are those of b = 0."""
 
     def __init__(self, loglike, n, runs, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, streams=None,
-                 max_iterations=None, max_batch=None, clustering=False):
+                 max_iterations=None, max_batch=None, clustering=False, boost_posterior=0.0):
         if clustering:
             raise ValueError('clustering is not part of a set of nested runs: run a NestedSampler(clustering=True) for each')
         self.loglike = loglike
@@ -998,11 +1045,21 @@ class NestedRunSet:
         if self.streams.shape != (self.E,):
             raise ValueError(f'streams: one entry for each of the {self.E} runs')
         self.runs = [NestedRun(None, n, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
-                               stream=int(st), max_iterations=max_iterations, max_batch=max_batch) for st in self.streams]
+                               stream=int(st), max_iterations=max_iterations, max_batch=max_batch, boost_posterior=boost_posterior)
+                     for st in self.streams]
         probe = self.runs[0]
         self.n, self.num_live, self.num_repeats, self.threads = probe.n, probe.num_live, probe.num_repeats, probe.threads
         self.precision, self.seed, self.max_iterations = probe.precision, probe.seed, probe.max_iterations
+        self.boost_posterior = probe.boost_posterior
+        if self._per_call() < 1:
+            raise ValueError(f'boost_posterior: one iteration of the {self.E} runs keeps up to {self.E} x {self.threads} x '
+                             f'{self.num_repeats - 1} phantom points, more than the {PHANTOM_BUDGET} bytes a call may hold: fewer '
+                             'runs in the set, fewer threads or fewer repeats')
         self.reset()
+
+    def _per_call(self):
+        """Iterations per call of the driver (:func:`set_iterations_per_call` over the whole set)."""
+        return set_iterations_per_call(self.E, self.threads, self.num_repeats, self.n, self.boost_posterior > 0.0)
 
     def reset(self):
         for run in self.runs:
@@ -1026,11 +1083,12 @@ class NestedRunSet:
     def _evaluate(self, rows_u, runs):
         return np.asarray(self.loglike(rows_u, runs), dtype=np.float64)
 
-    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw):
-        """One call of the driver over the runs ``idx`` (their state stacked, updated in place): what
-        :func:`python_iterations_many` returns."""
+    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw, boost=None):
+        """One call of the driver over the runs ``idx`` (their state stacked, updated in place; ``boost``: their
+        :class:`PhantomState` objects, this call's kept points appended): what :func:`python_iterations_many` returns."""
         return python_iterations_many(live_u, live_lnl, iteration, n_iterations, self.threads, self.num_repeats, self.seed,
-                                      self.streams[idx], lambda rows, runs: self._evaluate(rows, idx[runs]), stop, draw=draw)
+                                      self.streams[idx], lambda rows, runs: self._evaluate(rows, idx[runs]), stop, draw=draw,
+                                      boost=boost)
 
     def _advance(self, idx, n_iterations):
         """Up to ``n_iterations`` iterations of each of the runs ``idx``, as a set of their own; returns the statistics."""
@@ -1046,7 +1104,9 @@ class NestedRunSet:
         def stop(a, iterations, dead_lnl, live):
             return self.runs[idx[a]]._stop(iterations, dead_lnl, live)
 
-        dead, status, done, st = self._drive(idx, live_u, live_lnl, iteration, n_iterations, stop, draw)
+        boost = [self.runs[e].phantom_state for e in idx] if self.boost_posterior > 0.0 else None
+        dead, status, done, st = self._drive(idx, live_u, live_lnl, iteration, n_iterations, stop, draw,
+                                             **({} if boost is None else dict(boost=boost)))
         self._drawn = True
         per = np.zeros((self.E, 3), dtype=np.int64)
         per[idx] = st['per_run']
@@ -1074,7 +1134,7 @@ class NestedRunSet:
         t0 = time.perf_counter()
         for run in self.runs:
             run._to_termination = iterations is None
-        per_call = max(1, 65536 // self.threads)        # (the dead record of a call is allocated up front)
+        per_call = self._per_call()         # (the dead record of a call is allocated up front, with boost the phantom records too)
         left = None if iterations is None else int(iterations)
         while True:
             going = self.status != NO_FINITE
@@ -1130,18 +1190,35 @@ class NestedRunSet:
     def to_physical(self, u):
         return u
 
-    def samples(self):
+    def samples(self, boost=None):
         """Per run (points [N_e, n], lnL [N_e], weights [N_e] summing to 1): its dead points in order of death, then its live
-        points; None for a run without a finite live lnL."""
+        points; None for a run without a finite live lnL.  ``boost`` (None: on iff ``boost_posterior > 0``): every run's chain
+        with its phantom points merged in, as :meth:`NestedRun.samples` orders it."""
         self._ran()
         out = []
         for e, run in enumerate(self.runs):
             if self.status[e] == NO_FINITE:
                 out.append(None)
                 continue
-            pts, lnl, w = run.samples()
+            pts, lnl, w = run.samples(boost=boost)
             out.append((self.to_physical(pts), lnl, w))
         return out
+
+    def phantoms(self, e):
+        """The kept phantom points of run ``e`` in the canonical order: the dict of :meth:`NestedRun.phantoms`."""
+        return self.runs[int(e)].phantoms()
+
+    def boost_log_evidence(self):
+        """log Z_boost [E] (:meth:`NestedRun.boost_log_evidence`: a diagnostic, never the reported evidence); NaN for a run
+        without a finite live lnL."""
+        self._ran()
+        return np.array([run.boost_log_evidence() if self.status[e] != NO_FINITE else np.nan for e, run in enumerate(self.runs)])
+
+    def boost_index(self):
+        """Per run :meth:`NestedRun.boost_index` (row j of its boosted samples is row index[j] of its dead points, live points
+        and phantoms laid end to end); None for a run without a finite live lnL."""
+        self._ran()
+        return [run.boost_index() if self.status[e] != NO_FINITE else None for e, run in enumerate(self.runs)]
 
 
 class NestedSet(E.EngineSampler, NestedRunSet):
@@ -1153,15 +1230,20 @@ class NestedSet(E.EngineSampler, NestedRunSet):
     6h).  ``mock_rows`` [E]: the row of the installed mock pools every run is compared with - log Z and a weighted posterior per
     Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks_nested`); None: every run reads the data the interface has
     installed - replicas of one run (:func:`vega_amd.replicas.merge_nested`).  Every run ends on its own termination test.
-    Clustering is not part of a set.  An engine group takes ``'python'``."""
+    Clustering is not part of a set.  ``boost_posterior`` = b > 0: every run keeps the fraction min(1, b / num_repeats) of the
+    accepted points inside its walks (``'device'``: vmx_nested_run_many_phantoms) and its samples, its member's files and
+    ``sample_mocks_nested``'s summaries are the boosted chain's; the runs and their evidences are those of b = 0.  An engine group
+    takes ``'python'``."""
 
     def __init__(self, vega, runs, num_live=None, num_repeats=None, threads=None, precision=1e-3, seed=0, streams=None, mock_rows=None,
-                 driver='device', max_iterations=None, chunk=0, lanes=0, const_hint=-1, sample_params=None, clustering=False):
+                 driver='device', max_iterations=None, chunk=0, lanes=0, const_hint=-1, sample_params=None, clustering=False,
+                 boost_posterior=0.0):
         if clustering:
             raise ValueError('clustering is not part of a set of nested runs: run a NestedSampler(clustering=True) for each')
         n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         NestedRunSet.__init__(self, None, n, runs, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision,
-                              seed=seed, streams=streams, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None))
+                              seed=seed, streams=streams, max_iterations=max_iterations, max_batch=getattr(vega, 'max_batch', None),
+                              boost_posterior=boost_posterior)
         self.mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
         if self.mock_rows is not None and self.mock_rows.shape != (self.E,):
             raise ValueError(f'mock_rows: one entry for each of the {self.E} runs')
@@ -1176,26 +1258,37 @@ class NestedSet(E.EngineSampler, NestedRunSet):
         rows_t[:, self.cols] = self.to_physical(rows_u)
         return lnl_of(0, self._rows.chi2(rows_t, None if self.mock_rows is None else self.mock_rows[runs]), self.log_norm())
 
-    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw):
+    def _drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw, boost=None):
         vega = self.vega
         self._begin_advance(lambda: draw_live(1, self.n, self.seed, int(self.streams[0]))[0], 'nested_run_many')
         if self.driver == 'python':
             with self._engine_rows() as self._rows:
                 try:
-                    dead, status, done, st = NestedRunSet._drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw)
+                    dead, status, done, st = NestedRunSet._drive(self, idx, live_u, live_lnl, iteration, n_iterations, stop, draw,
+                                                                 boost=boost)
                 finally:
                     calls, self._rows = self._rows.calls, None
             return dead, status, done, dict(st, engine_calls=calls, host_waits=calls)
         vega._sync_monte_carlo()
-        return vega.engine.nested_run_many(
+        extra = {}
+        if boost is not None:       # (with boost off the call is the one of before: vmx_nested_run_many)
+            from .engine import PhantomArrays
+            extra['phantoms'] = PhantomArrays(idx.size, max(0, int(n_iterations)) * self.threads * (self.num_repeats - 1), self.n,
+                                              boost[0].fraction)
+        out = vega.engine.nested_run_many(
             self.cols, self.lo, self.hi, self._theta, live_u, live_lnl, iteration, self.streams[idx], n_iterations, self.threads,
             self.num_repeats, mock_rows=None if self.mock_rows is None else self.mock_rows[idx], log_norm=self.log_norm(),
-            seed=self.seed, const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=stop)
+            seed=self.seed, const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw_live=draw, stop=stop, **extra)
+        if boost is not None:
+            for a, state in enumerate(boost):
+                state.append(*extra['phantoms'].run(a))
+        return out
 
     def member(self, e):
         """Run ``e`` as a sampler that has run: :class:`NestedSampler`'s result methods (``log_evidence``, ``information``,
-        ``samples``, ``dead``, ``derived``, ``write``) over copies of its part of the set's state.  Read-only: it cannot be
-        advanced."""
+        ``samples``, ``dead``, ``derived``, ``write``) over copies of its part of the set's state; with ``boost_posterior > 0``
+        it carries the run's phantom record, so that these give the boosted chain as a single boosted run does.  Read-only: it
+        cannot be advanced."""
         if not 0 <= int(e) < self.E:
             raise IndexError(f'member: 0 .. {self.E - 1}')
         e = int(e)
@@ -1205,7 +1298,7 @@ class NestedSet(E.EngineSampler, NestedRunSet):
                           sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))), values=self.values,
                                              errors=self.errors),
                           stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint,
-                          max_iterations=self.max_iterations)
+                          max_iterations=self.max_iterations, boost_posterior=self.boost_posterior)
         m.driver = self.driver
         m.run = m.reset = _read_only
         if run.live_u is not None:
@@ -1214,6 +1307,8 @@ class NestedSet(E.EngineSampler, NestedRunSet):
         m._dead_u, m._dead_lnl, m._dead_n = list(run._dead_u), list(run._dead_lnl), list(run._dead_n)
         m._log_x, m._log_z_dead = run._log_x, run._log_z_dead
         m.stats = dict(run.stats)
+        if run.phantom_state is not None:
+            m.phantom_state.calls = list(run.phantom_state.calls)
         m.status = int(self.status[e])
         return m
 

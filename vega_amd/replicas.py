@@ -10,7 +10,8 @@ Ranks take contiguous shares of ``range(R)`` (:func:`vega_amd.parallel.shard_bou
 own engine; every replica leaves one record ``<name>.replica<r>.npz``; after a barrier rank 0 reads the R records back and merges:
 
 * nested runs merge exactly into one run with the summed live count (:func:`merge_nested`; Skilling 2006, the rule nestcheck and
-  dyPolyChord use); replicas that cluster (``do_clustering``) number their clusters independently, so a record carries no
+  dyPolyChord use); runs that kept phantom points (``boost_posterior``) carry them in their records and
+  :func:`merge_nested_boosted` merges them into the weighted chain, the evidence staying the base merge's; replicas that cluster (``do_clustering``) number their clusters independently, so a record carries no
   cluster ids and the merged run has none (``cluster_posteriors`` with ``replicas > 1`` is refused when the settings are read),
 * SMC evidences are unbiased, so they average (:func:`merge_smc`),
 * independent ensembles are kept apart and supply what one ensemble cannot, a between-chain convergence figure
@@ -67,10 +68,26 @@ def _common(sampler, kind, points, derived):
 
 def nested_record(run, derived=None):
     """The record of a finished :class:`vega_amd.nested.NestedRun`: the dead record, the final live points, the run's own
-    evidence; ``points`` are the physical rows of ``run.samples()`` (dead, then live)."""
+    evidence; ``points`` are the physical rows of the base run's samples (dead, then live).  A run that kept phantom points
+    (``boost_posterior > 0``) also carries ``ph_u`` (in the cube), ``ph_lnl``, ``ph_birth`` and ``ph_points`` (physical) in the
+    canonical order, and with ``derived`` (the block over its boosted ``samples()``) ``ph_derived``; a run without them writes
+    the keys it always wrote."""
     du, dl, dn = run.dead()
     log_z, err = run.log_evidence()
-    rec = _common(run, 'nested', run.samples()[0], derived)
+    boosted = getattr(run, 'phantom_state', None) is not None
+    extra = {}
+    if boosted:
+        ph = run.phantoms()
+        extra = dict(ph_u=ph['u'], ph_lnl=ph['lnl'], ph_birth=ph['birth'], ph_points=np.asarray(run.to_physical(ph['u']), dtype=np.float64))
+        if derived:         # (the block follows the boosted chain: back into the order dead, live, phantoms)
+            block = np.asarray(derived['derived'], dtype=np.float64)
+            rows = np.empty_like(block)
+            rows[run.boost_index()] = block
+            base = dl.size + run.live_lnl.size
+            derived = dict(derived, derived=rows[:base])
+            extra['ph_derived'] = rows[base:]
+    rec = _common(run, 'nested', run.samples(boost=False)[0] if boosted else run.samples()[0], derived)
+    rec.update(extra)
     rec.update(dead_u=du, dead_lnl=dl, dead_nlive=np.asarray(dn, dtype=np.int32), live_u=run.live_u.copy(),
                live_lnl=run.live_lnl.copy(), num_live=run.num_live, num_repeats=run.num_repeats, threads=run.threads,
                iteration=run.iteration, log_z=log_z, err=err, info=run.information())
@@ -217,6 +234,66 @@ def merge_nested(records):
     return out
 
 
+def merge_nested_boosted(records):
+    """:func:`merge_nested` with the records' phantom points (``ph_lnl``, ``ph_birth``, ``ph_points``; a record may have none)
+    merged into the weighted chain, as :func:`vega_amd.nested.boosted_weights` does for one run.  The events are the runs'
+    :func:`death_sequence` and all phantoms of all records, sorted by (lnL, deaths before phantoms, (replica, index)).  The
+    live count of an event at level L is ``m = sum_r n_r(L) + a(L)``: ``n_r(L)`` by :func:`merge_nested`'s rule - a run's own count
+    at its own deaths, the count at its first event with lnL >= L otherwise, 0 once it is exhausted - and
+    ``a(L) = #{phantoms p of any record : birth_p < L <= lnL_p}``, a phantom being a point that is uniform in its birth contour
+    until the level passes it.  Then ``log X_i = log X_{i-1} - 1 / m_i`` and ``w_i = X_{i-1} - X_i``.
+
+    Returns :func:`merge_nested`'s dict with ``points``, ``lnl``, ``weights``, ``nlive`` (m), ``log_x``, ``replica`` and ``index``
+    (a phantom's: its row of the record's phantoms) over the boosted events, ``phantom`` [rows] bool and ``log_z_boost`` (the
+    log-sum of the boosted weights: a diagnostic); ``log_z``, ``err`` and ``info`` are :func:`merge_nested`'s, from the base
+    records."""
+    records = _check(records, 'nested')
+    base = merge_nested(records)
+    dims = np.asarray(records[0]['points']).shape[-1]
+    seqs = [death_sequence(r) for r in records]
+    ph_lnl = [np.asarray(r['ph_lnl'], dtype=np.float64) if 'ph_lnl' in r else np.empty(0) for r in records]
+    ph_birth = [np.asarray(r['ph_birth'], dtype=np.float64) if 'ph_birth' in r else np.empty(0) for r in records]
+    ph_pts = [np.asarray(r['ph_points'], dtype=np.float64).reshape(-1, dims) if 'ph_points' in r else np.empty((0, dims)) for r in records]
+    if any(a.size != b.size or a.size != c.shape[0] for a, b, c in zip(ph_lnl, ph_birth, ph_pts)):
+        raise ValueError('a record\'s ph_lnl, ph_birth and ph_points differ in length')
+    if any(np.any(~(a > b)) for a, b in zip(ph_lnl, ph_birth)):
+        raise ValueError('a phantom point must lie above its birth contour')
+    lnl = np.concatenate([s[0] for s in seqs] + ph_lnl)
+    own = np.concatenate([s[1] for s in seqs] + [np.zeros(a.size, dtype=np.int64) for a in ph_lnl])
+    is_ph = np.concatenate([np.zeros(s[0].size, dtype=bool) for s in seqs] + [np.ones(a.size, dtype=bool) for a in ph_lnl])
+    replica = np.concatenate([np.full(s[0].size, r, dtype=np.int64) for r, s in enumerate(seqs)] +
+                             [np.full(a.size, r, dtype=np.int64) for r, a in enumerate(ph_lnl)])
+    index = np.concatenate([s[2] for s in seqs] + [np.arange(a.size, dtype=np.int64) for a in ph_lnl])
+    points = np.concatenate([np.asarray(r['points'])[s[2]] for r, s in zip(records, seqs)] + ph_pts)
+    # (the events of every kind lie replica by replica, index by index: a stable sort leaves ties in that order)
+    order = np.lexsort((is_ph, lnl))
+    lnl, own, is_ph, replica, index = lnl[order], own[order], is_ph[order], replica[order], index[order]
+    count = np.zeros(lnl.size, dtype=np.int64)
+    for r, (l_r, n_r, _) in enumerate(seqs):
+        first = np.searchsorted(l_r, lnl, side='left')
+        there = first < l_r.size
+        count += np.where((replica == r) & ~is_ph, own, np.where(there, n_r[np.minimum(first, l_r.size - 1)], 0))
+    # a: lnL_p > birth_p, so #{birth_p < L <= lnL_p} = #{birth_p < L} - #{lnL_p < L}
+    all_lnl, all_birth = np.sort(np.concatenate(ph_lnl)), np.sort(np.concatenate(ph_birth))
+    count += np.searchsorted(all_birth, lnl, side='left') - np.searchsorted(all_lnl, lnl, side='left')
+    log_x = -np.cumsum(1.0 / count)
+    lw = lnl + np.concatenate([[0.0], log_x[:-1]]) + np.log1p(-np.exp(-1.0 / count))
+    log_z_boost = NS._logsumexp(lw)
+    with np.errstate(invalid='ignore'):
+        p = np.exp(lw - log_z_boost) if np.isfinite(log_z_boost) else np.zeros(lw.size)
+    p = np.where(np.isfinite(p), p, 0.0)
+    out = dict(base, lnl=lnl, weights=p / p.sum(), nlive=count, log_x=log_x, replica=replica, index=index, points=points[order],
+               phantom=is_ph, log_z_boost=log_z_boost)
+    if 'derived' in records[0]:
+        width = np.asarray(records[0]['derived']).shape[1:]
+        if any(a.size and 'ph_derived' not in r for a, r in zip(ph_lnl, records)):
+            raise ValueError('records with derived columns and phantom points need ph_derived')
+        out['derived'] = np.concatenate([np.asarray(r['derived'])[s[2]] for r, s in zip(records, seqs)] +
+                                        [np.asarray(r['ph_derived']) if 'ph_derived' in r else np.empty((0,) + width)
+                                         for r in records])[order]
+    return out
+
+
 def merge_smc(records):
     """Independent SMC runs: every ``Z_r`` is an unbiased estimate of Z, so ``Z = mean_r Z_r``:
     ``log Z = logsumexp_r(log Z_r) - log R`` with ``err = sqrt(sum_r (Z_r err_r)^2) / sum_r Z_r`` (the runs' delta-method figures
@@ -358,6 +435,8 @@ def write_merged(path, name, records, merged=None):
             f.write(f'iterations = {sum(int(r["iteration"]) for r in records)}\nseed = {int(records[0]["seed"])}\n')
             f.write(f'num_live = {merged["num_live"]}\nnum_repeats = {int(records[0]["num_repeats"])}\n')
             f.write(f'threads = {int(records[0]["threads"])}\n')
+            if 'log_z_boost' in merged:         # (a merge by merge_nested_boosted, passed in)
+                f.write(f'phantom points = {int(np.sum(merged["phantom"]))}\nlog(Z) boosted = {merged["log_z_boost"]!r}\n')
         else:
             f.write(f'log(Z) = {merged["log_z"]!r}\nlog(Z) error = {merged["err"]!r}\n')
             f.write(f'stages = {sum(int(r["stage"]) for r in records)}\nsweeps = {int(records[0]["sweeps"])}\n')
