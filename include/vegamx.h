@@ -905,6 +905,8 @@ void* vmx_stream(vmx_engine* e);
  * nodes per wavenumber of that rule (the mean over the wavenumbers on it, where k tiles took shorter tiers), leading wavenumbers whose tiles took the rule in the last evaluation, table level of
  * the last evaluation (vmx_set_constant_nl_hint), first and last spline-coefficient row the last evaluation's bins read,
  * walkers that left the mu rule's box since vmx_finalize, form of the last evaluation (vmx_set_quadratic_form_kind)}.
+ * 5 = the assembled pre-distortion vector [B][pad32(n_model)] of item `index` as the last full-chain evaluation handed it to
+ * the distortion product (refused after a chi2-only evaluation and after a single walker's fused product, which keeps none).
  * Returns the number of doubles written (<= capacity) or a negative error. */
 int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, int64_t capacity);
 
@@ -912,7 +914,9 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
  * uses (bench / roofline measurement of the distortion-matrix step).  d_A row-major [rows][cols] with
  * cols a multiple of 32 (zero padded), d_x [B][cols], d_y [B][pad32(rows)], all device pointers (B <= 8 streams
  * the matrix once; larger B takes the MFMA path, split-K partial sums added in fixed order);
- * enqueued on the engine stream. */
+ * enqueued on the engine stream.  On the MFMA path both operands must stay below 4 GiB (the kernel addresses them with
+ * 32-bit byte offsets): larger ones are refused before anything is launched.  The same limit holds for the distortion,
+ * metal and inverse-covariance matrices of vmx_item_set_matrix and for the matrices of the quadratic form. */
 int vmx_matvec_device(vmx_engine* e, const double* d_A, int32_t rows, int32_t cols,
                       const double* d_x, int32_t B, double* d_y);
 

@@ -519,6 +519,47 @@ def dump_fits_ingest(VegaInterface):
         print('fits ingest: chi2', out['fid/chi2'], 'log_lik', out['fid/log_lik'], out['walker0/chi2'])
 
 
+def dump_small_grids(VegaInterface):
+    """Small, awkward grids (tests/helpers/small_grids.py: 63 to 5184 model bins - one row tile, one row more, odd and even
+    remainders, exact multiples, a one-tile item next to a 21-tile item, COEFMOD 2): the files written by
+    vega_amd.synthetic.grid_tables / write_data_file / write_dmat_file_case read by the unmodified reference, built like
+    dump_fits_ingest; chi2 and the per-item models at the fiducial point and three seeded walkers per case."""
+    sys.path.insert(0, str(REPO / 'tests'))
+    from helpers import small_grids as sg
+    os.chdir(REF / 'tests')
+    sg.check_claims()
+    out = {}
+    for case, (items, _) in sg.CASES.items():
+        with tempfile.TemporaryDirectory() as tmp:
+            names = [sg.ITEM_FILES[item['kind']][1] for item in items]
+            main = _ref_main(tmp, names, False)
+            for i, (item, name) in enumerate(zip(items, names)):
+                ini = Path(tmp) / f'{name}.ini'
+                ini.write_text(sg.adapt_item_ini(ini.read_text(), item, sg.write_item_files(tmp, item, f'{case}_{i}')))
+            vega = VegaInterface(main)
+            for item, name in zip(items, names):
+                data = vega.data[name]
+                assert data.has_distortion and data.cov_mat is not None
+                assert data.distortion_mat.shape == (item['n_p'] * item['n_t'], item['n_p'] * item['n_t'] * item['coef']**2)
+            pnames, walkers = make_walkers(vega.params, sg.N_WALKERS, seed=sg.WALKER_SEED)
+            points = [{n: vega.params[n] for n in pnames}] + walkers
+            chi2, models = [], {name: [] for name in names}
+            for w in points:
+                _reset_caches(vega)
+                chi2.append(vega.chi2(w))
+                _reset_caches(vega)
+                model = vega.compute_model(w, run_init=False)
+                for name in names:
+                    models[name].append(np.array(model[name]))
+            out[f'{case}/param_names'] = np.array(pnames)
+            out[f'{case}/theta'] = np.array([[w[n] for n in pnames] for w in points])
+            out[f'{case}/chi2'] = np.array(chi2)
+            for name in names:
+                out[f'{case}/model/{name}'] = np.array(models[name])
+            print('small grids:', case, out[f'{case}/chi2'])
+    np.savez_compressed(HERE / 'expected_small_grids.npz', **out)
+
+
 def dump_blinding(VegaInterface):
     """Blinding (reference vega/data.py:305-339, vega_interface.py:389-421, :853-886, utils.py:375-393): a `desi_dr3`
     data file - the DA_BLIND column replaces DA - read by the unmodified reference, first without parameter
@@ -1328,12 +1369,12 @@ def dump_pk_kat(VegaInterface):
 
 
 if __name__ == '__main__':
-    what = sys.argv[1:] or ['inputs', 'configs', 'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only']
+    what = sys.argv[1:] or ['inputs', 'configs', 'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids']
     if 'inputs' in what:
         convert_inputs()
     if 'configs' in what:
         derive_configs()
-    VI = _reference() if set(what) & {'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only'} else None
+    VI = _reference() if set(what) & {'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids'} else None
     if 'full4' in what:
         dump_full4(VI)
     if 'joint' in what:
@@ -1394,3 +1435,5 @@ if __name__ == '__main__':
         dump_components(VI)
     if 'model_only' in what:
         dump_model_only(VI)
+    if 'small_grids' in what:
+        dump_small_grids(VI)

@@ -1603,6 +1603,12 @@ static int pk_variant(const vmx_pipe_desc& d, bool paired)
     return PKV_GENERIC;
 }
 
+// k_gemm_nt44 forms its DMA source addresses as 32-bit byte offsets from the operand's base (vmx_device.h: oa / ox in setup()):
+// the last byte of an operand of `rows` rows of `ld` doubles has to lie below 4 GiB.  (The streaming kernels index with size_t.)
+static const uint64_t GEMM44_OPERAND_LIMIT = 1ull << 32;
+static bool gemm44_addressable(int64_t rows, int64_t ld) { return (uint64_t)rows * (uint64_t)ld * sizeof(double) < GEMM44_OPERAND_LIMIT; }
+#define GEMM44_LIMIT_MSG "an operand of the MFMA product kernel must stay below 4 GiB (2^32 bytes: 32-bit DMA byte offsets)"
+
 // the single-walker streaming kernel keeps x in LDS
 static bool gemv1_applies(int N, int K) { return N == 1 && K <= 5120 && (size_t)K * sizeof(double) <= 48 * 1024; }
 
@@ -2287,11 +2293,13 @@ int vmx_item_set_matrix(vmx_engine* e, int32_t item, int32_t kind, int32_t index
         REQUIRE(!e->finalized, "distortion matrix must be set before vmx_finalize");
         REQUIRE(rows == it->dev.d.n_dist && cols == it->dev.d.n_model, "distortion matrix shape");
         REQUIRE(!it->has_csr, "the item already has a CSR distortion matrix");
+        REQUIRE(gemm44_addressable(rows, it->dev.n_model_pad), "distortion matrix: " GEMM44_LIMIT_MSG);
         if (upload_padded(it->dm, dense, rows, cols, it->dev.n_model_pad)) return -2;
         it->has_dm = true;
     } else if (kind == VMX_MAT_INVCOV) {
         REQUIRE(it->has_mask, "set the mask before the inverse covariance");
         REQUIRE(rows == it->dev.n_masked && cols == rows, "inverse covariance shape");
+        REQUIRE(gemm44_addressable(rows, it->dev.n_masked_pad), "inverse covariance: " GEMM44_LIMIT_MSG);
         const std::vector<double> half = half_form(dense, rows);
         e->quad_mat_dirty = true;
         if (e->finalized) {
@@ -2310,6 +2318,7 @@ int vmx_item_set_matrix(vmx_engine* e, int32_t item, int32_t kind, int32_t index
         MetalHost* m = it->metals[index];
         REQUIRE(m->dev.d.pipeline >= 0, "a static metal correlation takes no matrix");
         REQUIRE(rows == it->dev.d.n_model && cols == e->pipes[m->dev.d.pipeline].n, "metal matrix shape");
+        REQUIRE(gemm44_addressable(rows, vmx_pad(cols)), "metal matrix: " GEMM44_LIMIT_MSG);
         if (upload_padded(m->mat, dense, rows, cols, vmx_pad(cols))) return -2;
         m->rows = rows; m->cols = cols;
         m->dev.mat_off = 0;
@@ -4076,6 +4085,9 @@ static int quad_build(vmx_engine* e)
             it->lean_pair = lean;
         }
         const int nq = d.nq, nqp = d.nq_pad;
+        // (Q' [nq][nq_pad], its factor F [n_masked][nq_pad] and the gathered rows X [nq][n_masked_pad] are operands of k_gemm_nt44)
+        REQUIRE(gemm44_addressable(nq, nqp) && gemm44_addressable(nq, nmp) && gemm44_addressable(nm, nqp),
+                "quadratic form: " GEMM44_LIMIT_MSG);
         // reference vector x0' = [vec(theta_ref) ; (1 + bao) c_j(theta_ref)]
         std::vector<double> x0((size_t)nqp, 0.0);
         HIP_OK(hipMemcpy(x0.data(), it->vec.p, (size_t)d.d.n_model * sizeof(double), hipMemcpyDeviceToHost));
@@ -6238,6 +6250,15 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (capacity >= 8) { out[7] = live[4]; return capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
         return capacity >= 7 ? 7 : capacity >= 5 ? 5 : capacity >= 4 ? 4 : 3;
     }
+    else if (what == 5) {
+        // the assembled pre-distortion vector of item `index`: the operand the last full-chain evaluation handed to the distortion
+        // product (a single walker's fused product assembles it while staging it and leaves nothing behind)
+        if (index < 0 || index >= (int)e->items.size()) { fail(-1, "invalid argument: item index"); return -1; }
+        const ItemHost* it = e->items[index];
+        const bool fused = B == 1 && it->has_dm && gemv1_applies(1, it->dev.n_model_pad) && !e->no_fuse;
+        if (!e->last_full || fused) { fail(-1, "the last evaluation (chi2 only, or a single walker's fused distortion product) did not store the pre-distortion vector"); return -1; }
+        src = it->vec.p; count = (int64_t)B * it->dev.n_model_pad;
+    }
     else { fail(-1, "invalid argument: what"); return -1; }
     if (count > capacity) { fail(-1, "invalid argument: capacity too small"); return -1; }
     if (hipMemcpy(out, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { fail(-2, "hipMemcpy"); return -2; }
@@ -6253,6 +6274,7 @@ int vmx_matvec_device(vmx_engine* e, const double* d_A, int32_t rows, int32_t co
     REQUIRE(B > 0, "vmx_matvec_device: B > 0");
     HIP_OK(hipSetDevice(e->device));
     const int ldy = vmx_pad(rows);
+    REQUIRE(B <= 8 || (gemm44_addressable(rows, cols) && gemm44_addressable(B, cols)), "vmx_matvec_device with more than 8 vectors: " GEMM44_LIMIT_MSG);
     if (B <= 8) {
         launch_product(e, KC_MATVEC, d_A, cols, 0, rows, cols, d_x, cols, 0, B, d_y, ldy, 0, 1, 0);
     } else {

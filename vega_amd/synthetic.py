@@ -301,7 +301,31 @@ def write_data_file(path, source, with_distortion=True, with_covariance=True, ex
     return path
 
 
-PICCA_COSMOLOGY_HEADER = {'OMEGAM': 0.315, 'OMEGAK': 0., 'OMEGAR': 7.9e-5, 'WL': -1.}
+def grid_tables(rp_min, rp_max, rt_max, n_p, n_t, z=2.3, z_scatter=0.0, seed=SEED):
+    """The table list of a correlation file on an arbitrary regular grid (what vega_amd.tables.read_tables returns for a
+    reference data file, and what :func:`write_data_file` takes as ``source``): HDU 1 = RP, RT, Z, DA with the grid
+    keywords, HDU 2 = the model-grid coordinates DMRP, DMRT, DMZ, equal to the data grid.  Bin centres rp-major like the
+    reference's regular grids (vega/coordinates.py:8-73); redshift ``z`` with a seeded scatter of ``z_scatter``; the data
+    vector is a seeded smooth function of (r, mu) with the size of a Lya correlation - not a model of anything, so chi2
+    against it is large."""
+    from .tables import Table
+    n_p, n_t = int(n_p), int(n_t)
+    dp, dt = (float(rp_max) - float(rp_min)) / n_p, float(rt_max) / n_t
+    rp = np.repeat(float(rp_min) + dp * (np.arange(n_p) + 0.5), n_t)
+    rt = np.tile(dt * (np.arange(n_t) + 0.5), n_p)
+    rng = np.random.default_rng(seed + 7919 * n_p + n_t)
+    zz = np.full(rp.size, float(z)) + z_scatter * rng.uniform(-1, 1, rp.size)
+    r = np.sqrt(rp**2 + rt**2)
+    mu = rp / r
+    amp, phase = rng.uniform(0.5, 1.5, 3), rng.uniform(0, 2 * np.pi, 3)
+    da = -2e-3 * amp[0] * np.exp(-r / 25.) * (1 - 2.2 * mu**2)
+    da += 4e-5 * amp[1] * np.sin(r / 17. + phase[1]) * (1 + 0.5 * mu**2) + 2e-5 * amp[2] * np.cos(rt / 29. + phase[2])
+    hdr = {'RPMIN': float(rp_min), 'RPMAX': float(rp_max), 'RTMAX': float(rt_max), 'NP': n_p, 'NT': n_t}
+    return [Table(hdr, {'RP': rp, 'RT': rt, 'Z': zz, 'DA': da}),
+            Table({}, {'DMRP': rp.copy(), 'DMRT': rt.copy(), 'DMZ': zz.copy()})]
+
+
+PICCA_COSMOLOGY_HEADER ={'OMEGAM': 0.315, 'OMEGAK': 0., 'OMEGAR': 7.9e-5, 'WL': -1.}
 
 METAL_MATRIX_SECTION = """[metal-matrix]
 rebin_factor = 2
