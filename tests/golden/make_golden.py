@@ -560,6 +560,50 @@ def dump_small_grids(VegaInterface):
     np.savez_compressed(HERE / 'expected_small_grids.npz', **out)
 
 
+def dump_small_metals(VegaInterface):
+    """The metal terms on small, awkward grids (tests/helpers/small_grids.py: METAL_CASES - 63 to 1320 bins, every remainder
+    of n_rp and n_rt mod 5, an rp-only set, a cross-correlation, two items): `new_metals = True` on the files written by
+    vega_amd.synthetic (grid_tables / write_data_file with the picca cosmology, write_stacked_deltas, write_object_catalog),
+    read by the unmodified reference as in dump_new_metals; chi2 and the per-item models at the fiducial point and three
+    seeded walkers per case."""
+    sys.path.insert(0, str(REPO / 'tests'))
+    from helpers import small_grids as sg
+    os.chdir(REF / 'tests')
+    sg.check_claims()
+    out = {}
+    for case, (items, facts) in sg.METAL_CASES.items():
+        with tempfile.TemporaryDirectory() as tmp:
+            names = [sg.METAL_ITEM_FILES[item['kind']][1] for item in items]
+            main = _ref_main(tmp, names, True)
+            for i, (item, name) in enumerate(zip(items, names)):
+                ini = Path(tmp) / f'{name}.ini'
+                ini.write_text(sg.metal_item_ini(ini.read_text(), item, tmp, f'{case}_{i}'))
+            vega = VegaInterface(main)
+            for item, fact, name in zip(items, facts, names):
+                data, metals = vega.data[name], vega.models[name].metals
+                assert data.has_distortion and data.cov_mat is not None
+                assert data.distortion_mat.shape == (fact['n_model'], fact['n_model']) and int(data.model_mask.sum()) == fact['n_masked']
+                assert metals.new_metals and metals.rp_only_metal_mats == item['rp_only']
+                assert len(metals.rp_metal_dmats) == fact['n_pairs']
+            pnames, walkers = make_walkers(vega.params, sg.N_WALKERS, seed=sg.WALKER_SEED)
+            points = [{n: vega.params[n] for n in pnames}] + walkers
+            chi2, models = [], {name: [] for name in names}
+            for w in points:
+                _reset_caches(vega)
+                chi2.append(vega.chi2(w))
+                _reset_caches(vega)
+                model = vega.compute_model(w, run_init=False)
+                for name in names:
+                    models[name].append(np.array(model[name]))
+            out[f'{case}/param_names'] = np.array(pnames)
+            out[f'{case}/theta'] = np.array([[w[n] for n in pnames] for w in points])
+            out[f'{case}/chi2'] = np.array(chi2)
+            for name in names:
+                out[f'{case}/model/{name}'] = np.array(models[name])
+            print('small metals:', case, out[f'{case}/chi2'])
+    np.savez_compressed(HERE / 'expected_small_metals.npz', **out)
+
+
 def dump_blinding(VegaInterface):
     """Blinding (reference vega/data.py:305-339, vega_interface.py:389-421, :853-886, utils.py:375-393): a `desi_dr3`
     data file - the DA_BLIND column replaces DA - read by the unmodified reference, first without parameter
@@ -1369,12 +1413,12 @@ def dump_pk_kat(VegaInterface):
 
 
 if __name__ == '__main__':
-    what = sys.argv[1:] or ['inputs', 'configs', 'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids']
+    what = sys.argv[1:] or ['inputs', 'configs', 'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids', 'small_metals']
     if 'inputs' in what:
         convert_inputs()
     if 'configs' in what:
         derive_configs()
-    VI = _reference() if set(what) & {'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids'} else None
+    VI = _reference() if set(what) & {'full4', 'joint', 'picca', 'mc', 'extras', 'fast_metals', 'mockbin', 'fits_ingest', 'marginalization', 'direct_pk', 'blinding', 'metal_decomp', 'new_metals', 'new_bias_evol', 'config1', 'marg_coeff', 'global_mc', 'model_compute', 'options2', 'fits', 'dmat_file', 'marg_mc', 'direct_pk_metals', 'mockbin_sampled', 'fht_extrap', 'fit_stats', 'sensitivity', 'components', 'model_only', 'small_grids', 'small_metals'} else None
     if 'full4' in what:
         dump_full4(VI)
     if 'joint' in what:
@@ -1437,3 +1481,5 @@ if __name__ == '__main__':
         dump_model_only(VI)
     if 'small_grids' in what:
         dump_small_grids(VI)
+    if 'small_metals' in what:
+        dump_small_metals(VI)

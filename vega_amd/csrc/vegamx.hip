@@ -1408,6 +1408,7 @@ struct vmx_engine {
     bool xi_sums = true;             // VMX_NO_XI_SUMS: one array per pipeline, as the general kernels write them
     bool sums_dirty = true;
     std::vector<XiLeanGroup> lean_groups; std::vector<XiStaticGroup> static_groups;
+    std::vector<int32_t> lean_single;                // lean pipelines that keep their own array: k_xi_bins_lean serves them, as without sums
     std::vector<int32_t> static_single;              // static-coordinate pipelines that keep their own array
     DevBuf<XiLeanGroup> d_lean_groups; DevBuf<XiStaticGroup> d_static_groups; DevBuf<ItemSums> d_item_sums;
     DevBuf<int32_t> d_static_single;
@@ -3202,12 +3203,12 @@ static bool xi_plain_args(vmx_engine* e, XiPlainArgs& A)
 
 // Which bins arrive pre-summed (ItemSums): per item, the lean per-walker pipelines in groups of four and the static-coordinate
 // pipelines in groups of sixteen, each member with the factor it enters the item's vector with.  A pipeline with a second
-// reader of its own array - another metal pair (fast_metals sharing), a metal matrix product - keeps that array (a group of
-// one, presum = 0).  A pure function of the engine's configuration; rebuilt when the static basis is.
+// reader of its own array - another metal pair (fast_metals sharing), a metal matrix product - keeps that array (lean_single:
+// k_xi_bins_lean serves it as without sums; static_single for the static-coordinate ones).  A pure function of the engine's configuration; rebuilt when the static basis is.
 static int xi_sum_plan(vmx_engine* e)
 {
     e->sums_dirty = false;
-    e->lean_groups.clear(); e->static_groups.clear(); e->static_single.clear();
+    e->lean_groups.clear(); e->static_groups.clear(); e->static_single.clear(); e->lean_single.clear();
     e->sums_any = false;
     const int np = (int)e->pipes.size();
     struct Role { int item = -1, fkind = 0, findex = 0, metal = -1, refs = 0; bool plain = true; };
@@ -3257,13 +3258,13 @@ static int xi_sum_plan(vmx_engine* e)
         XiLeanGroup G{};
         auto flush = [&]() {
             if (G.n_members == 0) return;
-            if (G.n_members == 1) G.presum = 0;        // (a sum of one: the plain array, read with its factor as before)
+            if (G.n_members == 1) e->lean_single.push_back(G.m[0].pipe);       // (a sum of one: the plain array, read with its factor as before)
             else {
                 sums[q].off[sums[q].n_arrays++] = G.out_off;
                 for (int m = 0; m < G.n_members; ++m) mark(G.m[m].pipe);
                 e->sums_any = true;
+                e->lean_groups.push_back(G);
             }
-            e->lean_groups.push_back(G);
             G = XiLeanGroup{};
         };
         for (int p : e->xi_lean_pipes) {
@@ -3278,11 +3279,11 @@ static int xi_sum_plan(vmx_engine* e)
     for (int p : e->xi_lean_pipes) {
         bool placed = false;
         for (auto& G : e->lean_groups) for (int m = 0; m < G.n_members; ++m) placed = placed || G.m[m].pipe == p;
-        if (placed) continue;
-        const PipeDev& P = e->pipes[p];
-        XiLeanGroup G{};
-        G.out_off = P.xi_off; G.n = P.n; G.n_pad = P.n_pad; G.presum = 0; G.n_members = 1; G.m[0] = member_of(p);
-        e->lean_groups.push_back(G);
+        for (int s1 : e->lean_single) placed = placed || s1 == p;
+        // a pipeline whose array has another reader (a metal matrix product, a sharing pair) is evaluated by the kernel that serves
+        // it when nothing is summed: its bins - and what a matrix makes of their last bits - do not depend on what the other
+        // pipelines of the engine do (k_xi_bins_group and k_xi_bins_lean are compiled apart and round apart)
+        if (!placed) e->lean_single.push_back(p);
     }
     // the static-coordinate pipelines (standard evolution, nothing added: what k_xi_bins_static_nw serves)
     auto static_lean = [&](int p) {
@@ -3556,6 +3557,17 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
             // (walkers per thread of the lean kernels: 1 / 2 / 4 measured the same - the stage is bound by its dependent lookups)
             const dim3 grid((max_n + 255) / 256, (unsigned)e->lean_groups.size(), (B + 1) / 2);
             hipLaunchKernelGGL((D.same_grid ? k_xi_bins_group<2, true> : k_xi_bins_group<2, false>), grid, dim3(256), 0, e->stream, D, e->d_lean_groups.p, B);
+            if (!e->lean_single.empty()) {
+                XiLeanArgs LA{};
+                for (size_t q = 0; q < e->lean_single.size(); ++q) {
+                    const PipeDev& P = e->pipes[e->lean_single[q]];
+                    XiLeanPipe& L = LA.p[q];
+                    L.coord_off = P.coord_off; L.xi_off = P.xi_off; L.n = P.n; L.n_pad = P.n_pad; L.pipe = e->lean_single[q]; L.col = P.col;
+                    L.n_ell = P.d.n_ell; L.split_evol = P.split_evol; L.radiation = P.d.is_peak ? 0 : P.d.radiation;
+                }
+                const dim3 single((max_n + 255) / 256, (unsigned)e->lean_single.size(), (B + 1) / 2);
+                hipLaunchKernelGGL((D.same_grid ? k_xi_bins_lean<2, true> : k_xi_bins_lean<2, false>), single, dim3(256), 0, e->stream, D, LA, B);
+            }
             if (!e->xi_rest_pipes.empty())
                 hipLaunchKernelGGL(k_xi_bins<false>, dim3((max_n + 255) / 256, (unsigned)e->xi_rest_pipes.size(), B), dim3(256), 0, e->stream, D, e->d_xi_rest_pipes.p);
         } else if (B > 8 && !e->direct && !e->xi_lean_pipes.empty()) {
@@ -3999,6 +4011,7 @@ static int run_chain_cached(vmx_engine* e, int B, int tab_mode, bool zero_copy =
     HIP_OK(hipGraphLaunch(it->second, e->stream));
     e->last_B = B;
     e->last_full = !quad;
+    e->last_form = quad ? (e->quad_factored ? 2 : 1) : 0;       // (a replayed graph runs no host code: run_chain set this at capture only)
     return 0;
 }
 
