@@ -12,7 +12,7 @@
  * and the Gaussian chi2 (vega/vega_interface.py:295-319).
  *
  * Beside evaluations the handle runs whole loops that consist of them where their state lives: fits (vmx_fit_migrad),
- * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_phantoms, vmx_nested_run_many, vmx_nested_run_many_phantoms) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many), both
+ * an ensemble MCMC sampler (vmx_ensemble_run), a nested sampler (vmx_nested_run, vmx_nested_run_phantoms, vmx_nested_run_many, vmx_nested_run_many_phantoms) and a tempered SMC sampler (vmx_smc_run, vmx_smc_run_many, vmx_smc_run_kept, vmx_smc_run_many_kept), both
  * with the evidence, the counterparts of
  * the reference's iminuit / PolyChord callers (vega/minimizer.py, vega/samplers/polychord.py, bin/run_vega_mpi.py).
  *
@@ -159,7 +159,7 @@ const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
- * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms): lets a foreign binding verify its struct layout at load time. */
+ * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -780,6 +780,41 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E,
                      double* rec, double* rec_lnl, int32_t* rec_anc,
                      int32_t* stages_done,
                      const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run);
+/* Kept populations and posterior rounds (vmx_smc.h: "kept populations and posterior rounds"): the calls above with a record of the
+ * positions every stage reweighted - what a weighted posterior over all stages' particles needs (vega_amd/smc.py:
+ * recycled_weights) - and with further stages at beta = 1 that only whiten and move, so that a run yields more than N points.
+ *   keep->rec_u         [n_stages][N][n] host ([E][n_stages][N][n] for the set), or NULL: row k is the particles at the entry of
+ *                       the call's stage k - the positions of rec_lnl's row k.  It lives in the workspace beside rec_lnl and comes
+ *                       back in the copy that brings the record.
+ *   keep->topups_left   [1] ([E] for the set) in/out, or NULL (no round owed): the posterior rounds the run still owes.  A run
+ *                       with beta >= 1 and rounds owed is not finished: its next stage is a posterior round (no bisection, no
+ *                       weights, no resampling; identity ancestors; record row beta_prev = beta = 1, ESS = the particles with a
+ *                       finite lnL), which pays one.  n_stages bounds ladder stages and posterior rounds together, one record row
+ *                       each; the Philox stage index keeps counting, so that a run is the same however it is cut.
+ *   keep->flags         0
+ * keep == NULL, or rec_u == NULL with no round owed, launches the kernels of vmx_smc_run / vmx_smc_run_many; otherwise the stage
+ * heads are k_smc_stage_kept / k_smc_set_stage_kept (smc_stage under its KEPT flag), the sweeps k_smc_move / k_smc_set_move as they
+ * are.  In a set, runs on the ladder and runs in posterior rounds stand side by side in one launch; a run at beta = 1 that owes
+ * rounds has status 0 and stays in the active list, and gets status 1 in the round that pays its last one.
+ *   stats     single run: a ladder stage waits on beta as before; the posterior rounds of a call need no decision of the host and
+ *             are enqueued back to back with one wait: host_waits = ladder stages + (1 if the call ran a posterior round) + 1 (the
+ *             copy back) + 1 with draw.  The set keeps one wait per round: host_waits = rounds + 1 + 1 with draw.
+ * Refused before anything runs (-1): whatever the base calls refuse; non-zero flags; a negative topups_left; rounds owed while
+ * rec_u is NULL; a record beyond size_t.  A run entered with beta = 1 and rounds owed is accepted. */
+typedef struct { double* rec_u; int32_t* topups_left; int32_t flags; } vmx_smc_keep;
+int vmx_smc_run_kept(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                     int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_keep* keep,
+                     const vmx_smc_options* opt, vmx_smc_stats* stats);
+int vmx_smc_run_many_kept(vmx_engine* e, const vmx_smc_spec* spec, int32_t E,
+                          const uint64_t* streams, const int32_t* mock_row,
+                          double* u, double* lnl,
+                          int64_t* stage, double* beta, double* scale,
+                          int32_t* status,
+                          int32_t n_stages,
+                          double* rec, double* rec_lnl, int32_t* rec_anc,
+                          int32_t* stages_done,
+                          const vmx_smc_keep* keep,
+                          const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run);
 /* The table level (vmx_set_constant_nl_hint) that batches whose rows differ only in the columns varies[n_params] != 0 allow - what
  * vmx_fit_migrad and vmx_ensemble_run derive when they are given const_hint = -1; a caller that evaluates such batches itself
  * sets it with vmx_set_constant_nl_hint. */

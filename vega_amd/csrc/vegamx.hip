@@ -956,9 +956,10 @@ __global__ __launch_bounds__(NS_THREADS) void k_ns_set_emit(NsSetDev S)
 }
 
 // Tempered SMC (vmx_smc_run): the particles, their proposals, the weights of a stage, the rows of a sweep and the stage record
+// (rec_u: the positions every stage reweighted, for vmx_smc_run_kept / vmx_smc_run_many_kept only)
 struct SmcWorkspace {
     BoxWorkspace box;
-    DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, rec, rec_lnl;
+    DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, rec, rec_lnl, rec_u;
     DevBuf<int32_t> inside, zero, rec_anc;
     DevBuf<int64_t> counters;
     double* pin = nullptr; double* dpin = nullptr;          // mapped host memory: beta, accepted, scale of the stage; the start's count
@@ -1060,17 +1061,71 @@ __device__ inline void smc_sums(double dbeta, const double (&d)[SMC_PER], int J,
     s2 = s_b[0];
 }
 
+// the particles' mean and covariance (one lane per entry) and the factor (one lane: n <= 32) into record row `rec`
+__device__ __forceinline__ void smc_precondition(const SmcDev& D, int64_t rec)
+{
+    const int N = D.N, n = D.n, tid = threadIdx.x;
+    for (int a = tid; a < n; a += SMC_THREADS) D.mean[a] = vmx_ns::mean_entry(a, D.u, D.zero, N, 0, n);
+    __syncthreads();
+    for (int q = tid; q < n * n; q += SMC_THREADS) {
+        const int a = q / n, b = q % n;
+        if (b > a) continue;
+        const double c = vmx_ns::cov_entry(a, b, D.u, D.zero, D.mean, N, 0, n);
+        D.cov[a * n + b] = c;
+        D.cov[b * n + a] = c;
+    }
+    __syncthreads();
+    if (tid == 0) D.rec[(size_t)rec * VMX_SMC_REC + 5] = vmx_ns::whiten(n, D.cov, D.chol) ? 1.0 : 0.0;
+}
+
+// The head of a posterior round (vmx_smc.h: a stage entered with beta = 1): the record row (1, 1, the particles with a finite lnL),
+// the lnL at entry, identity ancestors; the particles stay where they are and beta stays 1.
+__device__ __forceinline__ void smc_round_head(const SmcDev& D, int64_t rec)
+{
+    __shared__ int s_finite;
+    const int N = D.N, tid = threadIdx.x;
+    if (tid == 0) s_finite = 0;
+    __syncthreads();
+    int c = 0;
+    for (int i = tid; i < N; i += SMC_THREADS) {
+        const double v = D.lnl[i];
+        D.rec_lnl[(size_t)rec * N + i] = v;
+        D.rec_anc[(size_t)rec * N + i] = i;
+        c += v > -INFINITY ? 1 : 0;
+    }
+    if (c) atomicAdd(&s_finite, c);
+    __syncthreads();
+    if (tid == 0) {
+        double* r = D.rec + (size_t)rec * VMX_SMC_REC;
+        r[0] = 1.0; r[1] = 1.0; r[2] = (double)s_finite;
+        D.counters[0] = 0; D.counters[1] = 0; D.counters[2] = 0;
+    }
+}
+
 // The head of stage `stage` (record row `rec` of this call) in one work-group: the next beta by bisection on the effective sample
 // size (every sum in the fixed order of vmx_smc.h), the record, the cumulative weights, the ancestors, the gather, the particles'
 // mean and covariance (one lane per entry) and the factor (one lane: n <= 32).  beta_t goes to D.state[0]; NaN: no particle has a
 // finite lnL.
-__device__ __forceinline__ void smc_stage(const SmcDev& D, int64_t stage, int64_t rec)
+// KEPT (vmx_smc_run_kept): the particles at entry go to row `rec` of rec_u [stages][N][n] first, and a stage entered with beta = 1
+// is a posterior round: smc_round_head in place of everything up to the gather.
+template <bool KEPT = false>
+__device__ __forceinline__ void smc_stage(const SmcDev& D, int64_t stage, int64_t rec, double* rec_u = nullptr)
 {
     VMX_NO_CONTRACT
     __shared__ double s_a[SMC_THREADS], s_b[SMC_THREADS];
     const int N = D.N, n = D.n, tid = threadIdx.x;
     const int M = vmx_smc::pad_pow2(N), J = M > SMC_THREADS ? M / SMC_THREADS : 1, W = M < SMC_THREADS ? M : SMC_THREADS;
     const double beta_prev = D.state[0];
+    if constexpr (KEPT) {
+        if (rec_u)
+            for (int q = tid; q < N * n; q += SMC_THREADS) rec_u[(size_t)rec * N * n + q] = D.u[q];
+        if (vmx_smc::posterior_round(beta_prev)) {
+            smc_round_head(D, rec);
+            __syncthreads();
+            smc_precondition(D, rec);
+            return;
+        }
+    }
     double d[SMC_PER];
     double top = -INFINITY;
 #pragma unroll
@@ -1147,17 +1202,7 @@ __device__ __forceinline__ void smc_stage(const SmcDev& D, int64_t stage, int64_
     for (int i = tid; i < N; i += SMC_THREADS) D.lnl[i] = D.lnl2[i];
     __syncthreads();
 
-    for (int a = tid; a < n; a += SMC_THREADS) D.mean[a] = vmx_ns::mean_entry(a, D.u, D.zero, N, 0, n);
-    __syncthreads();
-    for (int q = tid; q < n * n; q += SMC_THREADS) {
-        const int a = q / n, b = q % n;
-        if (b > a) continue;
-        const double c = vmx_ns::cov_entry(a, b, D.u, D.zero, D.mean, N, 0, n);
-        D.cov[a * n + b] = c;
-        D.cov[b * n + a] = c;
-    }
-    __syncthreads();
-    if (tid == 0) D.rec[(size_t)rec * VMX_SMC_REC + 5] = vmx_ns::whiten(n, D.cov, D.chol) ? 1.0 : 0.0;
+    smc_precondition(D, rec);
 }
 
 // One sweep boundary in one work-group (the acceptance count steers the scale of every particle's next proposal): decide sweep
@@ -1227,6 +1272,10 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stag
 {
     smc_move(D, stage, s_dec, s_prop, rec);
 }
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage_kept(SmcDev D, int64_t stage, int64_t rec, double* rec_u)
+{
+    smc_stage<true>(D, stage, rec, rec_u);
+}
 
 // A set of runs (vmx_smc_run_many): work-group a of a launch owns run active[a] - the functions above over that run's part of
 // every array - and the engine rows a N .. (a + 1) N - 1; nothing crosses runs.  `run0` is the view of run 0 on the rows of slot
@@ -1284,6 +1333,15 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage(SmcSetDev S, int6
     int run;
     const SmcDev D = smc_view(S, run);
     smc_stage(D, S.stage0[run] + round, round);
+}
+
+// (rec_u [E][rec_rows][N][n])
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage_kept(SmcSetDev S, int64_t round, double* rec_u)
+{
+    int run;
+    const SmcDev D = smc_view(S, run);
+    if (rec_u) rec_u += (size_t)run * (size_t)S.rec_rows * (size_t)D.N * (size_t)D.n;
+    smc_stage<true>(D, S.stage0[run] + round, round, rec_u);
 }
 
 __global__ __launch_bounds__(SMC_THREADS) void k_smc_set_move(SmcSetDev S, int64_t round, int s_dec, int s_prop)
@@ -1856,6 +1914,7 @@ int vmx_struct_size(int32_t which)
         case 18: return (int)sizeof(vmx_nested_set_options);
         case 19: return (int)sizeof(vmx_nested_phantoms);
         case 20: return (int)sizeof(vmx_nested_set_phantoms);
+        case 21: return (int)sizeof(vmx_smc_keep);
         default: return -1;
     }
 }
@@ -5487,38 +5546,46 @@ static int nested_run_many(const char* who, vmx_engine* e, const vmx_nested_spec
 // ---- evidence where the particles live (vmx_smc.h)
 static_assert(VMX_SMC_MAX_PARTICLES == vmx_smc::MAX_PARTICLES && VMX_NS_MAXN == vmx_smc::MAXN, "SMC limits");
 
-int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
-                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
-                vmx_smc_stats* stats)
+// vmx_smc_run (keep = nullptr) and vmx_smc_run_kept
+static int smc_run_single(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage,
+                          double* beta, double* scale, int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc,
+                          const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats)
 {
-    REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale, "vmx_smc_run");
+    REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale, name);
+    double* const rec_u = keep ? keep->rec_u : nullptr;
+    int32_t owed = keep && keep->topups_left ? *keep->topups_left : 0;
+    REQUIRE(!keep || keep->flags == 0, name + ": keep->flags must be 0");
+    REQUIRE(owed >= 0, name + ": topups_left >= 0");
+    REQUIRE(owed == 0 || rec_u, name + ": posterior rounds are owed, but there is no rec_u");
+    const bool kept = rec_u != nullptr || owed > 0;         // (neither: the kernels of vmx_smc_run)
     std::vector<char> varies;
     std::vector<int32_t> inv;
-    if (check_box("vmx_smc_run", e, spec, VMX_NS_MAXN, varies, inv)) return -1;
+    if (check_box(name, e, spec, VMX_NS_MAXN, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params, N = spec->N, sweeps = spec->sweeps;
-    REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, "vmx_smc_run: max(2 n + 2, 8) .. 4096 particles");
-    REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, "vmx_smc_run: 0 < ess < 1");
-    REQUIRE(sweeps >= 1, "vmx_smc_run: sweeps >= 1");
-    REQUIRE(n_stages >= 0 && *stage >= 0 && *stage < ((int64_t)1 << 31), "vmx_smc_run: n_stages >= 0, 0 <= stage < 2^31");
-    REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), "vmx_smc_run: the stage record");
+    REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, name + ": max(2 n + 2, 8) .. 4096 particles");
+    REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, name + ": 0 < ess < 1");
+    REQUIRE(sweeps >= 1, name + ": sweeps >= 1");
+    REQUIRE(n_stages >= 0 && *stage >= 0 && *stage < ((int64_t)1 << 31), name + ": n_stages >= 0, 0 <= stage < 2^31");
+    REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), name + ": the stage record");
     const bool draw = opt && opt->draw != 0;
-    REQUIRE(!draw || *stage == 0, "vmx_smc_run: particles are drawn at stage 0");
+    REQUIRE(!draw || *stage == 0, name + ": particles are drawn at stage 0");
     if (!draw) {
-        REQUIRE(*beta >= 0.0 && *beta <= 1.0, "vmx_smc_run: beta in [0, 1]");
-        REQUIRE(*scale > 0.0 && std::isfinite(*scale), "vmx_smc_run: a positive scale");
+        REQUIRE(*beta >= 0.0 && *beta <= 1.0, name + ": beta in [0, 1]");
+        REQUIRE(*scale > 0.0 && std::isfinite(*scale), name + ": a positive scale");
         bool any = false;
         for (int i = 0; i < N; ++i) {
-            REQUIRE(!std::isnan(lnl[i]), "vmx_smc_run: a particle has a NaN lnL");
+            REQUIRE(!std::isnan(lnl[i]), name + ": a particle has a NaN lnL");
             any = any || lnl[i] > -INFINITY;
             for (int d = 0; d < n; ++d) {
                 const double v = u[(size_t)i * n + d];
-                REQUIRE(v >= 0.0 && v <= 1.0, "vmx_smc_run: a particle lies outside the unit cube");
+                REQUIRE(v >= 0.0 && v <= 1.0, name + ": a particle lies outside the unit cube");
             }
         }
-        REQUIRE(any, "vmx_smc_run: no particle has a finite lnL");
+        REQUIRE(any, name + ": no particle has a finite lnL");
     }
-    if (LikelihoodSession::check("vmx_smc_run", opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
     const size_t rec_rows = (size_t)std::max(n_stages, 1);
+    REQUIRE(!rec_u || (size_t)N * n * sizeof(double) <= SIZE_MAX / rec_rows, name + ": the record is too large");
 
     HIP_OK(hipSetDevice(e->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -5528,7 +5595,7 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
         ensure(S.cum, N) || ensure(S.zero, N) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) ||
         ensure(S.state, 2) || ensure(S.prop, (size_t)N * n) || ensure(S.uacc, N) || ensure(S.inside, N) ||
         ensure(S.rec, rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * N) || ensure(S.rec_anc, rec_rows * N) ||
-        ensure(S.counters, 3))
+        ensure(S.counters, 3) || (rec_u && ensure(S.rec_u, rec_rows * N * n)))
         return -2;
     if (!S.pin) {
         HIP_OK(hipHostMalloc((void**)&S.pin, 4 * sizeof(double), hipHostMallocMapped));
@@ -5578,32 +5645,52 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         HIP_OK(hipStreamSynchronize(st));       // (the start's wait: how many particles have a finite lnL)
         R.host_waits += 1;
-        if (!(S.pin[3] > 0.0)) return fail(-2, "vmx_smc_run: no start particle has a finite lnL");
+        if (!(S.pin[3] > 0.0)) return fail(-2, name + ": no start particle has a finite lnL");
         b_now = 0.0;
         scale_now = vmx_smc::start_scale(n);
     }
     int done = 0;
-    while (done < n_stages && b_now < 1.0) {
-        const int64_t t = *stage + done;
-        const auto t0 = std::chrono::steady_clock::now();
-        hipLaunchKernelGGL(k_smc_stage, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)done);
-        hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, -1, 0, (int64_t)done);
+    // a stage's kernels: its head, the first proposals, and per sweep the engine and the sweep boundary
+    auto enqueue_stage = [&](int64_t t, int row) -> int {
+        if (kept) hipLaunchKernelGGL(k_smc_stage_kept, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)row, rec_u ? S.rec_u.p : nullptr);
+        else hipLaunchKernelGGL(k_smc_stage, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)row);
+        hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, -1, 0, (int64_t)row);
         HIP_OK(hipGetLastError());
         for (int s = 0; s < sweeps; ++s) {
             if (evaluate()) return -2;
-            hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, s, s + 1 < sweeps ? s + 1 : -1, (int64_t)done);
+            hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, s, s + 1 < sweeps ? s + 1 : -1, (int64_t)row);
             HIP_OK(hipGetLastError());
         }
+        return 0;
+    };
+    while (done < n_stages && b_now < 1.0) {
+        const int64_t t = *stage + done;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (enqueue_stage(t, done)) return -2;
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         HIP_OK(hipStreamSynchronize(st));       // (the stage's only wait: beta, acceptance and scale, three mapped words)
         R.host_waits += 1;
         const double b = S.pin[0];
-        if (std::isnan(b)) return fail(-2, "vmx_smc_run: no particle has a finite lnL");
-        if (!(b > b_now)) return fail(-2, "vmx_smc_run: the temperature ladder cannot advance: fewer than ess N particles carry weight");
+        if (std::isnan(b)) return fail(-2, name + ": no particle has a finite lnL");
+        if (!(b > b_now)) return fail(-2, name + ": the temperature ladder cannot advance: fewer than ess N particles carry weight");
         b_now = b;
         scale_now = S.pin[2];
         R.accepted += (int64_t)S.pin[1];
         done += 1;
+    }
+    // the posterior rounds this call may run need no decision of the host: all of them back to back, one wait
+    const int ladder_done = done;
+    if (b_now >= 1.0 && owed > 0 && done < n_stages) {
+        const int rounds = std::min(n_stages - done, (int)owed);
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < rounds; ++k)
+            if (enqueue_stage(*stage + done + k, done + k)) return -2;
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));
+        R.host_waits += 1;
+        scale_now = S.pin[2];
+        done += rounds;
+        owed -= rounds;
     }
     std::vector<double> rec_host((size_t)std::max(done, 1) * VMX_SMC_REC);
     HIP_OK(hipMemcpyAsync(u, S.u.p, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -5612,14 +5699,17 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
         HIP_OK(hipMemcpyAsync(rec_host.data(), S.rec.p, (size_t)done * VMX_SMC_REC * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(rec_lnl, S.rec_lnl.p, (size_t)done * N * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(rec_anc, S.rec_anc.p, (size_t)done * N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (rec_u) HIP_OK(hipMemcpyAsync(rec_u, S.rec_u.p, (size_t)done * N * n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipStreamSynchronize(st));
     R.host_waits += 1;
     for (int k = 0; k < done; ++k) {
         R.rows_own_position += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 6];
         R.rejected_failed_model += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 7];
+        if (k >= ladder_done) R.accepted += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 3];
     }
     if (done > 0) std::memcpy(rec, rec_host.data(), (size_t)done * VMX_SMC_REC * sizeof(double));
+    if (keep && keep->topups_left) *keep->topups_left = owed;
     *stage += done;
     *beta = b_now;
     *scale = scale_now;
@@ -5631,16 +5721,41 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
     return 0;
 }
 
-// E independent runs advanced together (k_smc_set_*): one host round per stage for every run still going, the A N rows of a sweep
-// as one stream of chunks for the engine, every row with the mock of its run
-int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
-                     double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status, int32_t n_stages,
-                     double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_options* opt,
-                     vmx_smc_stats* stats, int64_t* per_run)
+int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
+                vmx_smc_stats* stats)
 {
-    const std::string name("vmx_smc_run_many");
+    return smc_run_single("vmx_smc_run", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, nullptr, opt, stats);
+}
+
+int vmx_smc_run_kept(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                     int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_keep* keep,
+                     const vmx_smc_options* opt, vmx_smc_stats* stats)
+{
+    return smc_run_single("vmx_smc_run_kept", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, keep, opt, stats);
+}
+
+// E independent runs advanced together (k_smc_set_*): one host round per stage for every run still going, the A N rows of a sweep
+// as one stream of chunks for the engine, every row with the mock of its run.  vmx_smc_run_many (keep = nullptr) and
+// vmx_smc_run_many_kept.
+static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams,
+                       const int32_t* mock_row, double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status,
+                       int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done,
+                       const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run)
+{
     REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale && status && stages_done, name);
     REQUIRE(E >= 1, name + ": at least one run");
+    double* const rec_u = keep ? keep->rec_u : nullptr;
+    std::vector<int32_t> owed((size_t)E, 0);
+    if (keep && keep->topups_left) owed.assign(keep->topups_left, keep->topups_left + E);
+    REQUIRE(!keep || keep->flags == 0, name + ": keep->flags must be 0");
+    bool any_owed = false;
+    for (int q = 0; q < E; ++q) {
+        REQUIRE(owed[q] >= 0, name + ": topups_left >= 0");
+        any_owed = any_owed || owed[q] > 0;
+    }
+    REQUIRE(!any_owed || rec_u, name + ": posterior rounds are owed, but there is no rec_u");
+    const bool kept = rec_u != nullptr || any_owed;         // (neither: the kernels of vmx_smc_run_many)
     REQUIRE(streams, name + ": a Philox stream for every run");
     std::vector<char> varies;
     std::vector<int32_t> inv;
@@ -5656,6 +5771,7 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
     const size_t EN = (size_t)E * N, rec_rows = (size_t)std::max(n_stages, 1);
     const size_t per_row = (size_t)std::max(std::max(n, P), VMX_SMC_REC) * sizeof(double);
     REQUIRE(EN <= SIZE_MAX / per_row && EN * per_row <= SIZE_MAX / rec_rows, name + ": the record is too large");
+    REQUIRE(!rec_u || (EN * rec_rows <= SIZE_MAX / ((size_t)n * sizeof(double))), name + ": the record is too large");
     const bool draw = opt && opt->draw != 0;
     for (int q = 0; q < E; ++q) {
         REQUIRE(stage[q] >= 0 && stage[q] < ((int64_t)1 << 31), name + ": 0 <= stage < 2^31");
@@ -5691,7 +5807,7 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
         ensure(S.state, (size_t)E * 2) || ensure(S.prop, EN * n) || ensure(S.uacc, EN) || ensure(S.inside, EN) ||
         ensure(S.rec, E * rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * EN) || ensure(S.rec_anc, rec_rows * EN) ||
         ensure(S.counters, (size_t)E * 3) || ensure(S.active, E) || ensure(S.streams, E) || ensure(S.stage0, E) ||
-        (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, EN))))
+        (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, EN))) || (rec_u && ensure(S.rec_u, rec_rows * EN * n)))
         return -2;
     if (S.set_runs < (size_t)E) {
         if (S.set_pin) { (void)hipHostFree(S.set_pin); S.set_pin = nullptr; }
@@ -5740,7 +5856,7 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
     std::vector<int32_t> done(E, 0);
     std::vector<double> b_now(beta, beta + E), scale_now(scale, scale + E);
     int32_t* active = S.set_active;
-    int A = vmx_smc::first_active(beta, E, draw, active, status);
+    int A = vmx_smc::first_active_kept(beta, owed.data(), E, draw, active, status);
     // the list goes up on the stream: the host changes it only after it has waited for the stream
     auto put_active = [&]() -> int {
         if (A > 0) HIP_OK(hipMemcpyAsync(S.active.p, active, (size_t)A * sizeof(int32_t), hipMemcpyHostToDevice, st));
@@ -5778,7 +5894,8 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
     int round = 0;
     while (round < n_stages && A > 0) {
         const auto t0 = std::chrono::steady_clock::now();
-        hipLaunchKernelGGL(k_smc_set_stage, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round);
+        if (kept) hipLaunchKernelGGL(k_smc_set_stage_kept, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, rec_u ? S.rec_u.p : nullptr);
+        else hipLaunchKernelGGL(k_smc_set_stage, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round);
         hipLaunchKernelGGL(k_smc_set_move, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, -1, 0);
         HIP_OK(hipGetLastError());
         for (int s = 0; s < sweeps; ++s) {
@@ -5792,7 +5909,7 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
         for (int a = 0; a < A; ++a) {
             const int q = active[a];
             const double* word = S.set_pin + (size_t)q * 4;
-            status[q] = vmx_smc::run_status(b_now[q], word[0]);
+            status[q] = vmx_smc::run_status_kept(b_now[q], word[0], owed[q]);
             if (status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK) continue;
             b_now[q] = word[0];
             scale_now[q] = word[2];
@@ -5814,6 +5931,8 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
         const size_t r = (size_t)q * rec_rows, h = (size_t)q * n_stages;
         HIP_OK(hipMemcpyAsync(rec_lnl + h * N, S.rec_lnl.p + r * N, (size_t)done[q] * N * sizeof(double), hipMemcpyDeviceToHost, st));
         HIP_OK(hipMemcpyAsync(rec_anc + h * N, S.rec_anc.p + r * N, (size_t)done[q] * N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        if (rec_u)
+            HIP_OK(hipMemcpyAsync(rec_u + h * N * n, S.rec_u.p + r * N * n, (size_t)done[q] * N * n * sizeof(double), hipMemcpyDeviceToHost, st));
     }
     HIP_OK(hipMemcpyAsync(rec_host.data(), S.rec.p, rec_host.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
@@ -5830,7 +5949,10 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
                         (size_t)done[q] * VMX_SMC_REC * sizeof(double));
         const bool failed = status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK;
         if (failed) accepted_of[q] = 0;
-        else { stage[q] += done[q]; beta[q] = b_now[q]; scale[q] = scale_now[q]; }
+        else {
+            stage[q] += done[q]; beta[q] = b_now[q]; scale[q] = scale_now[q];
+            if (keep && keep->topups_left) keep->topups_left[q] = owed[q];
+        }
         stages_done[q] = done[q];
         if (per_run) { per_run[4 * q] = accepted_of[q]; per_run[4 * q + 1] = own; per_run[4 * q + 2] = bad; per_run[4 * q + 3] = rows_of[q]; }
         R.accepted += accepted_of[q];
@@ -5843,6 +5965,24 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const u
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;
     return 0;
+}
+
+int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
+                     double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status, int32_t n_stages,
+                     double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_options* opt,
+                     vmx_smc_stats* stats, int64_t* per_run)
+{
+    return smc_run_set("vmx_smc_run_many", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec, rec_lnl,
+                       rec_anc, stages_done, nullptr, opt, stats, per_run);
+}
+
+int vmx_smc_run_many_kept(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
+                          double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status, int32_t n_stages,
+                          double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_keep* keep,
+                          const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run)
+{
+    return smc_run_set("vmx_smc_run_many_kept", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec,
+                       rec_lnl, rec_anc, stages_done, keep, opt, stats, per_run);
 }
 
 void* vmx_stream(vmx_engine* e) { return e ? (void*)e->stream : nullptr; }

@@ -346,4 +346,68 @@ VMX_HD inline int compact_active(int32_t* active, int A, const int32_t* status)
     return B;
 }
 
+// ---- kept populations and posterior rounds (vmx_smc_run_kept, vmx_smc_run_many_kept)
+// A weighted posterior from every population the run walked through (vega_amd/smc.py: recycled_weights) needs their positions,
+// and more points at beta = 1 need more moves there.
+//   kept population  the population a stage reweights is the particles at its entry: their lnL is the stage's rec_lnl row, their
+//                    positions go to the row of the same index of rec_u [stages][N][n].  The final particles are the last
+//                    population.
+//   posterior round  a stage entered with beta_prev = 1.  No bisection, no weights, no resampling uniform (the block (0, t, 0, 4)
+//                    of that stage is not read); the ancestors are the identity.  Record row: beta_prev = beta = 1, ESS = the
+//                    number of particles with a finite lnL; rec_lnl and rec_u the particles at entry.  Mean, covariance and
+//                    factor of the particles as they stand (mean_entry / cov_entry / whiten, fallback included), then the
+//                    stage's sweeps through the unchanged propose / accept / adapt at beta = 1.  The Philox stage index is the
+//                    run's global stage index, which keeps counting: a run is the same however it is cut, also inside the rounds.
+//   rounds owed      topups_left is state beside stage, beta and scale.  beta >= 1 and topups_left = 0: the run is finished;
+//                    beta >= 1 and topups_left > 0: the next stage is a posterior round, which pays one.  n_stages of a call bounds
+//                    ladder stages and posterior rounds together, one record row each.
+//   a set            a run at beta = 1 that owes rounds stays RUNNING and in the active list; it is FINISHED in the round that
+//                    pays the last one.  compact_active reads nothing but the statuses and serves both forms.
+VMX_HD inline bool posterior_round(double beta_prev) { return beta_prev >= 1.0; }
+
+// nothing is left to do
+VMX_HD inline bool run_finished(double beta, int32_t topups_left) { return beta >= 1.0 && topups_left <= 0; }
+
+// ESS of a posterior round's record row: the particles with a finite lnL
+VMX_HD inline double round_ess(const double* lnl, int N)
+{
+    int c = 0;
+    for (int i = 0; i < N; ++i) c += lnl[i] > -INFINITY ? 1 : 0;
+    return (double)c;
+}
+
+// the head of a posterior round over u[N][n], lnl[N] (both left as they are): row[0 .. 2] = 1, 1, ESS; anc the identity; mean[n],
+// cov[n][n], C[n][n]; zero[N] zeros.  Returns whiten's flag (row[5] of the record).
+inline bool posterior_round_head(const double* u, const double* lnl, int N, int n, const int32_t* zero, double* row, int32_t* anc,
+                                 double* mean, double* cov, double* C)
+{
+    row[0] = 1.0; row[1] = 1.0; row[2] = round_ess(lnl, N);
+    for (int i = 0; i < N; ++i) anc[i] = i;
+    for (int a = 0; a < n; ++a) mean[a] = vmx_ns::mean_entry(a, u, zero, N, 0, n);
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) cov[a * n + b] = cov[b * n + a] = vmx_ns::cov_entry(a, b, u, zero, mean, N, 0, n);
+    return vmx_ns::whiten(n, cov, C);
+}
+
+// run_status with rounds owed: topups_left is the count at the head of the stage and is paid here.  A posterior round (beta_before
+// >= 1) cannot be STUCK; beta_after NaN: no particle has a finite lnL (the count is then left as it was).
+VMX_HD inline int run_status_kept(double beta_before, double beta_after, int32_t& topups_left)
+{
+    if (beta_after != beta_after) return NO_FINITE;
+    if (posterior_round(beta_before)) topups_left -= 1;
+    else if (!(beta_after > beta_before)) return STUCK;
+    return run_finished(beta_after, topups_left) ? FINISHED : RUNNING;
+}
+
+// first_active with rounds owed (topups_left NULL: none): a run at beta = 1 that owes rounds begins the call
+VMX_HD inline int first_active_kept(const double* beta, const int32_t* topups_left, int E, bool draw, int32_t* active, int32_t* status)
+{
+    int A = 0;
+    for (int e = 0; e < E; ++e) {
+        status[e] = draw || !run_finished(beta[e], topups_left ? topups_left[e] : 0) ? RUNNING : FINISHED;
+        if (status[e] == RUNNING) active[A++] = e;
+    }
+    return A;
+}
+
 }  // namespace vmx_smc

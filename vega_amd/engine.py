@@ -228,6 +228,10 @@ class SmcOptions(C.Structure):
     _fields_ = [('const_hint', C.c_int32), ('chunk', C.c_int32), ('lanes', C.c_int32), ('draw', C.c_int32)]
 
 
+class SmcKeep(C.Structure):
+    _fields_ = [('rec_u', C.POINTER(C.c_double)), ('topups_left', C.POINTER(C.c_int32)), ('flags', C.c_int32)]
+
+
 class SmcStats(C.Structure):
     _fields_ = [('stages', C.c_int64), ('sweeps', C.c_int64), ('rows', C.c_int64), ('rows_own_position', C.c_int64),
                 ('accepted', C.c_int64), ('rejected_failed_model', C.c_int64), ('engine_calls', C.c_int64),
@@ -335,6 +339,8 @@ def load_library():
     lib.vmx_smc_run_many.argtypes = [C.c_void_p, C.POINTER(SmcSpec), C.c_int32, C.POINTER(C.c_uint64), iptr, dptr, dptr,
                                      C.POINTER(C.c_int64), dptr, dptr, iptr, C.c_int32, dptr, dptr, iptr, iptr, C.POINTER(SmcOptions),
                                      C.POINTER(SmcStats), C.POINTER(C.c_int64)]
+    lib.vmx_smc_run_kept.argtypes = lib.vmx_smc_run.argtypes[:11] + [C.POINTER(SmcKeep)] + lib.vmx_smc_run.argtypes[11:]
+    lib.vmx_smc_run_many_kept.argtypes = lib.vmx_smc_run_many.argtypes[:16] + [C.POINTER(SmcKeep)] + lib.vmx_smc_run_many.argtypes[16:]
     lib.vmx_derived_const_hint.argtypes = [C.c_void_p, iptr]
     lib.vmx_set_constant_nl_hint.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_set_direct_pk.argtypes = [C.c_void_p, dptr, C.c_int32, C.c_int32]
@@ -372,7 +378,7 @@ def load_library():
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
                                     SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms,
-                                    NestedSetPhantoms)):
+                                    NestedSetPhantoms, SmcKeep)):
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -404,7 +410,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1345,13 +1351,18 @@ class Engine:
         return cluster_points(u, prev_id, next_id, device=self.device)
 
     def smc_run(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, n_stages, ess, sweeps, log_norm=0.0, seed=0, stream=0,
-                const_hint=-1, chunk=0, lanes=0, draw=False):
+                const_hint=-1, chunk=0, lanes=0, draw=False, keep=False, topups_left=None):
         """Up to ``n_stages`` stages of the tempered SMC sampler on the device (include/vegamx.h: vmx_smc_run): ``cols`` the sampled
         parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``u`` [N, n] in the unit cube / ``lnl``
         [N] the particles (updated in place; drawn first with ``draw``), ``stage`` the global index of the next stage, ``beta`` and
         ``scale`` its inverse temperature and proposal scale.  Returns (record: one dict per stage done with beta_prev, beta, ess,
-        lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale afterwards; statistics)."""
+        lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale afterwards; statistics).
+
+        ``keep`` or ``topups_left`` (an int) go through vmx_smc_run_kept: every stage dict also carries ``u``, the particles at the
+        stage's entry, the call goes on at beta = 1 with up to ``topups_left`` posterior rounds (``n_stages`` bounds both kinds), and
+        the rounds still owed are returned after ``scale``."""
         cols, lo, hi, theta_fixed, N = self._sampled_box(cols, lo, hi, theta_fixed, u=u, lnl=lnl)
+        kept = bool(keep) or topups_left is not None
         n_stages = max(0, int(n_stages))
         rec, rec_lnl = np.zeros((n_stages, VMX_SMC_REC)), np.empty((n_stages, N))
         rec_anc = np.empty((n_stages, N), dtype=np.int32)
@@ -1360,22 +1371,37 @@ class Engine:
         opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
         stats = SmcStats()
         st, b, sc = C.c_int64(int(stage)), C.c_double(float(beta)), C.c_double(float(scale))
-        self._check(self.lib.vmx_smc_run(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc), n_stages,
-                                         _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(opt), C.byref(stats)))
+        if kept:
+            rec_u = np.empty((n_stages, N, cols.size))
+            owed = C.c_int32(int(topups_left or 0))
+            keep_arg = SmcKeep(_dp(rec_u), C.pointer(owed), 0)
+            self._check(self.lib.vmx_smc_run_kept(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc),
+                                                  n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(keep_arg), C.byref(opt),
+                                                  C.byref(stats)))
+        else:
+            self._check(self.lib.vmx_smc_run(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc), n_stages,
+                                             _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(opt), C.byref(stats)))
         record = [dict(beta_prev=float(rec[k, 0]), beta=float(rec[k, 1]), ess=float(rec[k, 2]), lnl=rec_lnl[k].copy(),
                        anc=rec_anc[k].copy(), accepted=int(rec[k, 3]), scale=float(rec[k, 4]), cholesky=bool(rec[k, 5]))
                   for k in range(int(stats.stages))]
+        if kept:
+            for k, r in enumerate(record):
+                r['u'] = rec_u[k].copy()
+            return record, int(st.value), float(b.value), float(sc.value), int(owed.value), _stats_dict(stats)
         return record, int(st.value), float(b.value), float(sc.value), _stats_dict(stats)
 
     def smc_run_many(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, streams, n_stages, ess, sweeps, mock_rows=None,
-                     log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw=False):
+                     log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw=False, keep=False, topups_left=None):
         """Up to ``n_stages`` stage rounds of E independent SMC runs in one device run (include/vegamx.h: vmx_smc_run_many): ``u``
         [E, N, n] / ``lnl`` [E, N] the particles, ``stage`` int64 [E] / ``beta`` [E] / ``scale`` [E] the runs' own state (all updated
         in place; a failed run's part is left as it was), ``streams`` [E] the Philox stream of every run, ``mock_rows`` [E] the pool
         row every run is compared with (None: the installed data); the rest as for :meth:`smc_run`.  Returns (records: for every
         run the list of stage dicts of the stages done, status int32 [E], stages_done int32 [E], statistics); the statistics
         carry ``per_run`` int64 [E, 4]: accepted, rows that were a particle's own position, rejected for a failed model, rows
-        evaluated."""
+        evaluated.
+
+        ``keep`` or ``topups_left`` (int32 [E], updated in place: the posterior rounds every run still owes) go through
+        vmx_smc_run_many_kept: every stage dict also carries ``u``, the run's particles at the stage's entry."""
         _in_place(np.float64, u=u, lnl=lnl, beta=beta, scale=scale)
         _in_place(np.int64, stage=stage)
         if u.ndim != 3 or lnl.shape != u.shape[:2]:
@@ -1397,14 +1423,28 @@ class Engine:
                        0, _dp(theta_fixed))
         opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
         stats = SmcStats()
-        self._check(self.lib.vmx_smc_run_many(
-            self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), _dp(u), _dp(lnl), stage.ctypes.data_as(C.POINTER(C.c_int64)), _dp(beta),
-            _dp(scale), _ip(status), n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), _ip(done), C.byref(opt), C.byref(stats),
-            per.ctypes.data_as(C.POINTER(C.c_int64))))
+        head = (self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+                None if mock_rows is None else _ip(mock_rows), _dp(u), _dp(lnl), stage.ctypes.data_as(C.POINTER(C.c_int64)), _dp(beta),
+                _dp(scale), _ip(status), n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), _ip(done))
+        tail = (C.byref(opt), C.byref(stats), per.ctypes.data_as(C.POINTER(C.c_int64)))
+        kept = bool(keep) or topups_left is not None
+        if kept:
+            if topups_left is not None:
+                _in_place(np.int32, topups_left=topups_left)
+                if topups_left.shape != (E,):
+                    raise ValueError('topups_left [E]')
+            rec_u = np.empty((E, n_stages, N, cols.size))
+            keep_arg = SmcKeep(_dp(rec_u), None if topups_left is None else _ip(topups_left), 0)
+            self._check(self.lib.vmx_smc_run_many_kept(*head, C.byref(keep_arg), *tail))
+        else:
+            self._check(self.lib.vmx_smc_run_many(*head, *tail))
         records = [[dict(beta_prev=float(rec[e, k, 0]), beta=float(rec[e, k, 1]), ess=float(rec[e, k, 2]), lnl=rec_lnl[e, k].copy(),
                          anc=rec_anc[e, k].copy(), accepted=int(rec[e, k, 3]), scale=float(rec[e, k, 4]),
                          cholesky=bool(rec[e, k, 5])) for k in range(int(done[e]))] for e in range(E)]
+        if kept:
+            for e in range(E):
+                for k, r in enumerate(records[e]):
+                    r['u'] = rec_u[e, k].copy()
         return records, status, done, dict(_stats_dict(stats), per_run=per)
 
     def derived_const_hint(self, cols):

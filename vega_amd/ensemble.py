@@ -897,7 +897,8 @@ def build_sampler(vega, cfg, sample_params, stream=0):
     if cfg['sampler'] == 'SMC':
         from .smc import SMCSampler
         return SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],
-                          driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params, stream=stream)
+                          driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params, stream=stream,
+                          **{key: cfg[key] for key in ('n_total', 'recycle') if key in cfg})
     return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
                            sample_params=sample_params, stream=stream)
 
@@ -990,7 +991,8 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
         mocks = mc.mc_mocks['global']
     if cfg['sampler'] == 'SMC':
         sampler = mc.sample_mocks(mocks=mocks, seed=cfg['seed'], scale=scale, sample_params=sample_params, driver=cfg['driver'],
-                                  sampler='smc', particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'])
+                                  sampler='smc', particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'],
+                                  **{key: cfg[key] for key in ('n_total', 'recycle') if key in cfg})
         for m in range(sampler.E):
             sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')
         mc.write_mock_posteriors(cfg['path'])

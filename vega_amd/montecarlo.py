@@ -470,7 +470,7 @@ class MonteCarlo:
 
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
-                     ess=0.5, sweeps=None):
+                     ess=0.5, sweeps=None, n_total=None, recycle=False):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -489,11 +489,18 @@ class MonteCarlo:
         settings; ``walkers`` / ``steps`` / ``burn`` / ``thin`` are not read: every run ends by itself at beta = 1).  It keeps in
         ``mc_posteriors``: names, ``mean`` / ``sd`` / ``covariance`` of the N samples, ``log_z``, ``log_z_err`` (NaN for a run that
         failed), ``stages``, ``status`` (:class:`SMCSet`), ``acceptance`` and the settings; ``mc_chains`` holds the samples
-        [M, N, n] and ``mc_chain_lnl`` their lnL.  (Nested sampling of every mock: :meth:`sample_mocks_nested`.)"""
+        [M, N, n] and ``mc_chain_lnl`` their lnL.  ``n_total`` / ``recycle`` (:class:`vega_amd.smc.SMCRun`: posterior rounds at beta = 1
+        until every run has ``n_total`` points; the particles of every stage reweighted into one chain): ``mean`` / ``sd`` /
+        ``covariance`` are then the weighted moments of the chain used, ``mc_posteriors`` gains ``points`` [M], ``n_eff`` [M] (Kish)
+        and ``log_z_recycled`` [M], ``n_total`` and ``recycle``, ``stages`` counts the ladder's stages alone, and ``mc_chains``
+        holds per mock the tuple (points, lnL, weights); with neither the dict has the keys it had.  (Nested sampling of every
+        mock: :meth:`sample_mocks_nested`.)"""
         if sampler not in ('ensemble', 'smc'):
             raise ValueError("sample_mocks: sampler 'ensemble' or 'smc'")
+        if sampler != 'smc' and (n_total is not None or recycle):
+            raise ValueError("sample_mocks: n_total and recycle go with sampler='smc'")
         return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
-                                  fiducial_model, sampler, particles, ess, sweeps)
+                                  fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle)
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
@@ -515,7 +522,7 @@ class MonteCarlo:
 
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
-                      max_iterations=None, boost_posterior=0.0):
+                      max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -554,7 +561,8 @@ class MonteCarlo:
         if smc:
             from .smc import SMCSet
             sampler = SMCSet(vega, M, particles=1024 if particles is None else int(particles), mock_rows=np.arange(M), ess=ess,
-                             sweeps=sweeps, seed=seed, driver=driver, sample_params=sample_params)
+                             sweeps=sweeps, seed=seed, driver=driver, sample_params=sample_params,
+                             **(dict(n_total=n_total, recycle=recycle) if n_total is not None or recycle else {}))
         elif nested:
             from .nested import NestedSet
             sampler = NestedSet(vega, M, num_live=num_live, num_repeats=num_repeats, threads=threads, precision=precision, seed=seed,
@@ -576,6 +584,26 @@ class MonteCarlo:
         finally:
             for name in rescaled:
                 eng.set_invcov(name, prob.items[name].chi2_matrix)
+        if smc and sampler.keeping:
+            found = list(zip(*sampler.samples()))
+            log_z, err = sampler.log_evidence()
+            mean, sd, cov = np.full((M, n), np.nan), np.full((M, n), np.nan), np.full((M, n, n), np.nan)
+            for m, (pts, _, w) in enumerate(found):
+                mean[m] = w @ pts
+                dev = pts - mean[m]
+                cov[m] = (w[:, None] * dev).T @ dev / (1.0 - np.sum(w * w))         # (the unbiased estimate under reliability weights)
+                sd[m] = np.sqrt(np.diag(cov[m]))
+            moved = np.maximum(sampler.stats['per_run'][:, 3] - sampler.particles, 1)       # (the rows of the sweeps)
+            self.mc_posteriors = dict(
+                sampler='smc', names=list(sampler.names), mean=mean, sd=sd, covariance=cov, log_z=log_z, log_z_err=err,
+                stages=np.array([len(r) for r in sampler.record], dtype=np.int64), status=sampler.status.copy(),
+                acceptance=sampler.stats['per_run'][:, 0] / moved, particles=sampler.particles, ess=sampler.ess, sweeps=sampler.sweeps,
+                seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats),
+                points=np.array([part[1].size for part in found], dtype=np.int64), n_eff=sampler.n_eff(),
+                log_z_recycled=sampler.recycled_log_evidence(), n_total=sampler.n_total, recycle=sampler.recycle)
+            self.mc_chains = found if keep_chains else None
+            self.mc_chain_lnl = [part[1] for part in found] if keep_chains else None
+            return sampler
         if smc:
             pts, lnl, _ = sampler.samples()
             log_z, err = sampler.log_evidence()
@@ -633,7 +661,8 @@ class MonteCarlo:
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
         ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  After
         ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
-        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED``; after
+        ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED`` (with ``n_total`` or
+        ``recycle`` also the columns ``points``, ``n_eff``, ``log_z_recycled`` and the header keys ``NTOTAL`` and ``RECYCLE``); after
         ``sample_mocks_nested`` ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``info``, ``iterations``,
         ``status``, ``covariance`` and the header keys ``SAMPLER``, ``NUMLIVE``, ``NREPEATS``, ``THREADS``, ``PRECISN``, ``SEED``
         (with ``boost_posterior > 0`` also the columns ``phantoms``, ``n_eff``, ``log_z_boost`` and the header key ``BOOST``).
@@ -654,6 +683,11 @@ class MonteCarlo:
                      ('stages', 'K', np.asarray(post['stages'], dtype=np.int64)), ('status', 'K', np.asarray(post['status'], dtype=np.int64)),
                      cov_col]
             header = {'SAMPLER': 'SMC', 'PARTICLE': post['particles'], 'ESS': post['ess'], 'SWEEPS': post['sweeps'], 'SEED': post['seed']}
+            if 'points' in post:
+                cols += [('points', 'K', np.asarray(post['points'], dtype=np.int64)), ('n_eff', 'D', post['n_eff']),
+                         ('log_z_recycled', 'D', post['log_z_recycled'])]
+                header['NTOTAL'] = 0 if post['n_total'] is None else int(post['n_total'])
+                header['RECYCLE'] = bool(post['recycle'])
         elif post.get('sampler') == 'nested':
             for j, nm in enumerate(names):
                 cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j])]

@@ -15,7 +15,12 @@ is the delta-method figure for independent particles: it ignores the correlation
 particles of a stage more alike than independent draws would be, and the seed-to-seed scatter then exceeds it; see
 :func:`evidence`).
 
-What is not here: pocoMC's flow-based preconditioning, ``dynamic`` particle counts, ``n_total`` top-ups at beta = 1, state files.
+``n_total`` and ``recycle`` (pocoMC's ``posterior()``): with ``n_total`` the run goes on at beta = 1 with posterior rounds - whiten,
+move, no reweighting, no resampling - until that many points are there; with ``recycle`` the particles of every stage are kept and
+reweighted into one weighted chain (:func:`recycled_weights`), which costs no likelihood evaluation.
+
+What is not here: pocoMC's flow-based preconditioning, ``dynamic`` particle counts, the trimming of the largest recycled weights,
+state files.
 """
 import math
 import time
@@ -249,21 +254,49 @@ def adapt(scale, accepted, N):
 _REC_KEYS = ('beta_prev', 'beta', 'ess', 'accepted', 'scale', 'cholesky')
 
 
-def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, watch=None):
+def posterior_round_head(u, lnl):
+    """vmx_smc::posterior_round_head: the head of a posterior round, a stage entered with beta = 1.  No bisection, no weights, no
+    resampling uniform; the particles stay as they are.  dict(beta = 1, ess = the particles with a finite lnL, anc the identity,
+    u, lnl, mean, cov, C, cholesky) - the keys of :func:`stage_head` that the sweeps and the record read."""
+    mean, cov = NS.mean_cov(u)
+    C, ok = NS.whiten(cov)
+    return dict(beta=1.0, ess=float(np.count_nonzero(lnl > -np.inf)), anc=np.arange(u.shape[0], dtype=np.int32), u=u, lnl=lnl,
+                mean=mean, cov=cov, C=C, cholesky=ok)
+
+
+def run_finished(beta, topups_left):
+    """vmx_smc::run_finished: at beta = 1 with no posterior round owed."""
+    return beta >= 1.0 and topups_left <= 0
+
+
+def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, watch=None, topups_left=0, keep=None):
     """Up to ``n_stages`` stages in NumPy from the state ``u`` [N, n], ``lnl`` [N] (updated in place), stopping after the stage
     that reaches beta = 1.  ``evaluate(rows_u)`` -> lnL [N] of rows in the cube (-inf: a failed model).  ``watch(stage, sweep, u,
     lnl, scale, accepted)`` is called after every sweep.  Returns (record: a list of dicts per stage with beta_prev, beta, ess,
-    lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale, stats)."""
+    lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale, stats).
+
+    ``topups_left`` posterior rounds are owed at beta = 1 (vmx_smc.h: "kept populations and posterior rounds"): the run then goes
+    on with stages headed by :func:`posterior_round_head`, one record row each (beta_prev = beta = 1), ``n_stages`` bounding both
+    kinds together.  ``keep``, a list, receives the particles at the entry of every stage done.  With either, the rounds still
+    owed are returned after ``scale``: (record, stage, beta, scale, topups_left, stats)."""
     N, n = u.shape
     record = []
+    new_form = keep is not None or bool(topups_left)
+    topups_left = int(topups_left)
     st = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0)
     for _ in range(n_stages):
-        if beta >= 1.0:
+        if run_finished(beta, topups_left):
             break
-        head = stage_head(u, lnl, beta, ess, stage, seed, stream)
+        if keep is not None:
+            keep.append(u.copy())
+        if beta >= 1.0:
+            head = posterior_round_head(u, lnl)
+            topups_left -= 1
+        else:
+            head = stage_head(u, lnl, beta, ess, stage, seed, stream)
         if math.isnan(head['beta']):
             raise ValueError('SMC: no particle has a finite log-likelihood')
-        if not head['beta'] > beta:
+        if beta < 1.0 and not head['beta'] > beta:
             raise ValueError('SMC: the temperature ladder cannot advance: fewer than ess N particles carry weight')
         rec = dict(beta_prev=beta, beta=head['beta'], ess=head['ess'], lnl=lnl.copy(), anc=head['anc'], cholesky=head['cholesky'])
         u[:], lnl[:] = head['u'], head['lnl']
@@ -290,6 +323,8 @@ def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, strea
         rec.update(accepted=acc_stage, scale=scale)
         record.append(rec)
         stage += 1
+    if new_form:
+        return record, stage, beta, scale, topups_left, st
     return record, stage, beta, scale, st
 
 
@@ -317,7 +352,27 @@ def compact_active(active, status):
     return [e for e in active if status[e] == RUNNING]
 
 
-def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, streams, evaluate, draw=False):
+def run_status_kept(beta_before, beta_after, topups_left):
+    """vmx_smc::run_status_kept: (what a stage round made of a run that owed ``topups_left`` posterior rounds at its head, the
+    rounds it owes now).  A posterior round (``beta_before`` = 1) pays one and cannot be stuck."""
+    if math.isnan(beta_after):
+        return NO_FINITE, topups_left
+    if beta_before >= 1.0:
+        topups_left -= 1
+    elif not beta_after > beta_before:
+        return STUCK, topups_left
+    return (FINISHED if run_finished(beta_after, topups_left) else RUNNING), topups_left
+
+
+def first_active_kept(beta, topups_left, draw):
+    """vmx_smc::first_active_kept: a run at beta = 1 that owes posterior rounds begins the call."""
+    going = np.array([draw or not run_finished(b, t) for b, t in zip(np.asarray(beta), np.asarray(topups_left))], dtype=bool)
+    status = np.where(going, RUNNING, FINISHED).astype(np.int32)
+    return [int(e) for e in np.flatnonzero(going)], status
+
+
+def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, streams, evaluate, draw=False, topups_left=None,
+                       keep=None):
     """Up to ``n_stages`` stage rounds of E runs in NumPy (vmx_smc_run_many restated): ``u`` [E, N, n], ``lnl`` [E, N], ``stage``
     int64 [E], ``beta`` [E], ``scale`` [E] the runs' state, updated in place (a failed run's part is left as it was at entry),
     ``streams`` [E].  A round advances every run still going by one stage (:func:`stage_head`, then ``sweeps`` times
@@ -325,12 +380,20 @@ def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, 
     rows of the A runs still going (ascending, run ``runs[a]`` owns rows a N .. (a + 1) N - 1) at once.  ``draw``: the particles are
     drawn and evaluated first.  Returns (records: per run the list of stage dicts as :func:`python_stages` makes them, status
     int32 [E]: 0 still going, 1 at beta = 1, 2 no particle with a finite lnL, 3 the ladder cannot advance; stages_done int32 [E];
-    statistics with ``per_run`` int64 [E, 4]: accepted, own-position rows, failed models, rows evaluated, and ``rounds``)."""
+    statistics with ``per_run`` int64 [E, 4]: accepted, own-position rows, failed models, rows evaluated, and ``rounds``).
+
+    ``topups_left`` int [E] (updated in place): the posterior rounds every run owes at beta = 1 (vmx_smc_run_many_kept restated) -
+    such a run stays in the list and takes :func:`posterior_round_head` beside the others' :func:`stage_head`.  ``keep``: a list
+    of E lists, run e's receives its particles at the entry of every stage it does.  With either, ``topups_left`` is returned
+    after ``stages_done``."""
     E, N, n = u.shape
+    new_form = keep is not None or topups_left is not None
+    owed = np.zeros(E, dtype=np.int64) if topups_left is None else topups_left
+    owed_entry = owed.copy()
     entry = (u.copy(), lnl.copy(), stage.copy(), beta.copy(), scale.copy())
     records = [[] for _ in range(E)]
     per = np.zeros((E, 4), dtype=np.int64)
-    active, status = first_active(beta, bool(draw))
+    active, status = first_active_kept(beta, owed, bool(draw))
     rounds = 0
 
     def rows_of(parts):
@@ -349,8 +412,14 @@ def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, 
     while rounds < n_stages and active:
         heads = {}
         for e in active:
-            head = stage_head(u[e], lnl[e], float(beta[e]), ess, int(stage[e]), seed, int(streams[e]))
+            before = u[e].copy() if keep is not None else None
+            if beta[e] >= 1.0:
+                head = posterior_round_head(u[e], lnl[e])
+            else:
+                head = stage_head(u[e], lnl[e], float(beta[e]), ess, int(stage[e]), seed, int(streams[e]))
             heads[e] = head
+            if keep is not None and not math.isnan(head['beta']):
+                keep[e].append(before)
             if math.isnan(head['beta']):
                 continue
             records[e].append(dict(beta_prev=float(beta[e]), beta=head['beta'], ess=head['ess'], lnl=lnl[e].copy(), anc=head['anc'],
@@ -379,7 +448,7 @@ def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, 
                 own[e] += int((~inside).sum())
                 bad[e] += int((inside & ~ok).sum())
         for e in active:
-            status[e] = run_status(float(beta[e]), heads[e]['beta'])
+            status[e], owed[e] = run_status_kept(float(beta[e]), heads[e]['beta'], int(owed[e]))
             if status[e] in (NO_FINITE, STUCK):
                 continue
             records[e][-1]['scale'] = float(scale[e])
@@ -394,11 +463,16 @@ def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, 
     for e in range(E):
         if status[e] in (NO_FINITE, STUCK):
             u[e], lnl[e], stage[e], beta[e], scale[e] = (arr[e] for arr in entry)
+            owed[e] = owed_entry[e]
             records[e] = []
+            if keep is not None:
+                del keep[e][:]
             per[e, :3] = 0
         done[e] = len(records[e])
     st = dict(stages=int(done.sum()), sweeps=int(done.sum()) * sweeps, rows=int(per[:, 3].sum()), rows_own_position=int(per[:, 1].sum()),
               accepted=int(per[:, 0].sum()), rejected_failed_model=int(per[:, 2].sum()), rounds=rounds, per_run=per)
+    if new_form:
+        return records, status, done, owed, st
     return records, status, done, st
 
 
@@ -419,11 +493,75 @@ def evidence(record, N):
     return log_z, math.sqrt(max(var, 0.0))
 
 
+def running_evidence(record, N):
+    """log Z at the entry of every stage of ``record`` and after the last one, [stages + 1], by :func:`evidence`'s own recursion:
+    0 first, then the sums of its terms."""
+    out = [0.0]
+    for rec in record:
+        db = rec['beta'] - rec['beta_prev']
+        with np.errstate(invalid='ignore'):
+            out.append(out[-1] + (NS._logsumexp(db * np.asarray(rec['lnl'], dtype=np.float64)) - math.log(N)))
+    return np.array(out)
+
+
+def recycled_weights(betas, log_z_running, lnl):
+    """The particles of S populations of N points each as one weighted posterior sample, by the balance heuristic: population s
+    was drawn from ``L^beta_s / Z_s`` over the prior (``betas`` [S]: 0 for the start, the ladder's values, 1 for every beta = 1
+    population; ``log_z_running`` [S]: the running evidence at that stage, 0 for the start, the final value for every beta = 1
+    population: :func:`running_evidence`), so that the S N points together are a sample of the mixture ``sum_s N L^beta_s /
+    Z_s`` and a point with ``lnL = l`` has the posterior weight
+
+        ``log w = l - logsumexp_s(log N + beta_s l - log Z_s)``.
+
+    ``lnl`` [S, N].  A point with ``l = -inf`` gets weight 0 and takes no part.  Returns (the weights [S, N], normalised to sum
+    1; ``log_z_recycled = logsumexp(log w)``: the sum of the unnormalised weights estimates Z).  float64 on the host, the same code
+    for both drivers.  pocoMC trims the largest weights of its recycled chain afterwards; that is not done here."""
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    log_z = np.asarray(log_z_running, dtype=np.float64).reshape(-1)
+    lnl = np.asarray(lnl, dtype=np.float64)
+    if lnl.ndim != 2 or betas.shape != (lnl.shape[0],) or log_z.shape != betas.shape:
+        raise ValueError('recycled_weights: betas [S], log_z_running [S], lnl [S, N]')
+    N = lnl.shape[1]
+    live = lnl > -np.inf
+    if not np.any(live):
+        return np.zeros(lnl.shape), -math.inf
+    l = lnl[live]
+    terms = math.log(N) + betas[:, None] * l[None, :] - log_z[:, None]          # [S, points]
+    top = terms.max(axis=0)
+    log_w = l - (top + np.log(np.exp(terms - top[None, :]).sum(axis=0)))
+    log_z_recycled = float(NS._logsumexp(log_w))
+    w = np.zeros(lnl.shape)
+    w[live] = np.exp(log_w - log_z_recycled)
+    return w, log_z_recycled
+
+
+KEEP_BUDGET = 1 << 30       # bytes of kept positions (stages + posterior rounds) N n 8 a run may hold
+KEEP_STAGES = 64            # the ladder stages that figure assumes where max_stages is not given
+
+
+def posterior_rounds_for(n_total, particles):
+    """R = ceil(n_total / N) - 1 posterior rounds make (R + 1) N >= n_total points at beta = 1; None: 0."""
+    if n_total is None:
+        return 0
+    if isinstance(n_total, bool) or int(n_total) != n_total or int(n_total) < particles:
+        raise ValueError(f'n_total: a whole number, at least the {particles} particles')
+    return -(-int(n_total) // particles) - 1
+
+
 class SMCRun:
     """A tempered SMC run over ``loglike(rows_u [R, n]) -> lnL [R]`` in the unit cube (-inf: a failed model), NumPy driver: the
-    particles, the stage record and the evidence.  :class:`SMCSampler` puts the engine behind it."""
+    particles, the stage record and the evidence.  :class:`SMCSampler` puts the engine behind it.
 
-    def __init__(self, loglike, n, particles=1024, ess=0.5, sweeps=None, seed=0, stream=0, max_stages=None):
+    ``n_total`` (a whole number >= ``particles``): after the ladder the run goes on with R = ceil(n_total / N) - 1 posterior rounds
+    at beta = 1, and ``samples()`` returns the (R + 1) N points of the beta = 1 populations.  It counts points, not independent
+    draws: successive rounds are ``sweeps`` sweeps apart, and a particle that no sweep moved appears again.  ``recycle``: the
+    particles of every stage are kept and ``samples()`` returns all of them with :func:`recycled_weights`.  Either option keeps
+    the positions of every population, (stages + R) N n 8 bytes; a run that would exceed ``KEEP_BUDGET`` with ``max_stages``
+    (``KEEP_STAGES`` where it is None) ladder stages is refused here.  ``log_evidence()``, ``stages``, ``record`` and
+    ``max_stages`` stay the ladder's: the rows of the posterior rounds are in ``posterior_rounds``."""
+
+    def __init__(self, loglike, n, particles=1024, ess=0.5, sweeps=None, seed=0, stream=0, max_stages=None, n_total=None,
+                 recycle=False):
         self.loglike = loglike
         self.n = int(n)
         self.particles = int(particles)
@@ -441,6 +579,14 @@ class SMCRun:
             raise ValueError('sweeps >= 1')
         if self.max_stages is not None and self.max_stages < 1:
             raise ValueError('max_stages >= 1')
+        self.rounds = posterior_rounds_for(n_total, self.particles)
+        self.n_total = None if n_total is None else int(n_total)
+        if not isinstance(recycle, (bool, np.bool_)):
+            raise ValueError('recycle: True or False')
+        self.recycle = bool(recycle)
+        self.keeping = self.recycle or n_total is not None
+        if self.keeping and ((self.max_stages or KEEP_STAGES) + self.rounds) * self.particles * self.n * 8 > KEEP_BUDGET:
+            raise ValueError(f'n_total / recycle: the kept populations would exceed {KEEP_BUDGET} bytes')
         self.reset()
 
     def reset(self):
@@ -449,12 +595,15 @@ class SMCRun:
         self.beta = 0.0
         self.scale = start_scale(self.n)
         self.record = []
+        self.topups_left = self.rounds
+        self.posterior_rounds = []
         self.stats = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0, engine_calls=0,
                           host_waits=0, seconds=0.0, seconds_enqueuing=0.0, calls=0)
 
     @property
     def finished(self):
-        return self.beta >= 1.0
+        """At beta = 1 with no posterior round owed."""
+        return run_finished(self.beta, self.topups_left)
 
     @property
     def stages(self):
@@ -483,30 +632,44 @@ class SMCRun:
         """One call of the driver: (record, statistics)."""
         if self.u is None:
             self._draw()
-        rec, self.stage, self.beta, self.scale, st = python_stages(
+        if not self.keeping:
+            rec, self.stage, self.beta, self.scale, st = python_stages(
+                self.u, self.lnl, self.stage, self.beta, self.scale, n_stages, self.ess, self.sweeps, self.seed, self.stream,
+                self._evaluate)
+            return rec, st
+        keep = []
+        rec, self.stage, self.beta, self.scale, self.topups_left, st = python_stages(
             self.u, self.lnl, self.stage, self.beta, self.scale, n_stages, self.ess, self.sweeps, self.seed, self.stream,
-            self._evaluate)
+            self._evaluate, topups_left=self.topups_left, keep=keep)
+        for r, before in zip(rec, keep):
+            r['u'] = before
         return rec, st
 
     def run(self, stages=None):
-        """To beta = 1 (``stages`` None; ``max_stages`` bounds the run), or at most ``stages`` more stages; the run does not
-        depend on how it is cut."""
+        """To beta = 1 and through the posterior rounds owed (``stages`` None; ``max_stages`` bounds the ladder), or at most
+        ``stages`` more stages, ladder stages and posterior rounds alike; the run does not depend on how it is cut."""
         t0 = time.perf_counter()
-        if stages is None:
-            call = 1 << 20 if self.max_stages is None else max(0, self.max_stages - self.stage)
-        else:
-            call = int(stages)
-            if self.max_stages is not None:
-                call = min(call, max(0, self.max_stages - self.stage))
-        if call > 0 and not self.finished:
+        budget = 1 << 20 if stages is None else int(stages)
+        while budget > 0 and not self.finished:
+            if self.beta >= 1.0:
+                call = min(budget, self.topups_left)
+            else:
+                call = budget if self.max_stages is None else min(budget, max(0, self.max_stages - len(self.record)))
+            if call <= 0:
+                break
+            at = self.stage
             rec, st = self._advance(call)
-            self.record.extend(rec)
+            for r in rec:           # (the rows of the posterior rounds stay out of the ladder's record)
+                (self.posterior_rounds if r['beta_prev'] >= 1.0 else self.record).append(r)
             for key, val in st.items():
                 if key in ('lanes', 'const_hint'):      # (what the engine ran with)
                     self.stats[key] = val
                 elif key in self.stats and key != 'seconds':
                     self.stats[key] += val
             self.stats['calls'] += 1
+            budget -= self.stage - at
+            if self.stage == at:
+                break
         self.stats['seconds'] += time.perf_counter() - t0
         return self
 
@@ -520,11 +683,56 @@ class SMCRun:
     def to_physical(self, u):
         return u
 
-    def samples(self):
-        """(points [N, n], lnL [N], weights [N] = 1 / N): the particles - the posterior sample once ``finished``."""
+    def populations(self):
+        """The kept populations in the order they were made, the particles as they stand last: (u [S, N, n] in the unit cube, lnL
+        [S, N], beta [S], the running log Z [S] of :func:`recycled_weights`).  Population s < stages is what ladder stage s
+        reweighted; then the entries of the posterior rounds, then the particles."""
         if self.u is None:
             raise ValueError('nothing has run yet')
-        return self.to_physical(self.u.copy()), self.lnl.copy(), np.full(self.particles, 1.0 / self.particles)
+        if not self.keeping:
+            raise ValueError('populations: the run keeps them with n_total or recycle')
+        rows = self.record + self.posterior_rounds
+        u = np.array([r['u'] for r in rows] + [self.u])
+        lnl = np.array([r['lnl'] for r in rows] + [self.lnl])
+        beta = np.array([r['beta_prev'] for r in rows] + [self.beta])
+        log_z = running_evidence(self.record, self.particles)
+        log_z = np.concatenate([log_z, np.full(len(self.posterior_rounds), log_z[-1])])
+        return u, lnl, beta, log_z
+
+    def _chain(self, recycle=None):
+        """(u [points, n], lnL, weights, log_z_recycled or None) of the chain ``samples(recycle)`` returns."""
+        if self.u is None:
+            raise ValueError('nothing has run yet')
+        recycle = self.recycle if recycle is None else bool(recycle)
+        N = self.particles
+        if not recycle and self.n_total is None:
+            return self.u.copy(), self.lnl.copy(), np.full(N, 1.0 / N), None
+        u, lnl, beta, log_z = self.populations()
+        if not recycle:
+            at_one = beta >= 1.0
+            if not np.any(at_one):          # (the ladder is still going: the particles as they stand)
+                at_one[-1] = True
+            u, lnl = u[at_one], lnl[at_one]
+            return u.reshape(-1, self.n), lnl.reshape(-1), np.full(lnl.size, 1.0 / lnl.size), None
+        w, log_zr = recycled_weights(beta, log_z, lnl)
+        return u.reshape(-1, self.n), lnl.reshape(-1), w.reshape(-1), log_zr
+
+    def samples(self, recycle=None):
+        """(points [N, n], lnL [N], weights [N] = 1 / N): the particles - the posterior sample once ``finished``.  ``recycle``
+        (None: the constructor's setting) off with ``n_total``: the (R + 1) N points of the beta = 1 populations, equal weights; on:
+        every kept population and the particles, [S N, n], with :func:`recycled_weights`."""
+        u, lnl, w, _ = self._chain(recycle)
+        return self.to_physical(u), lnl, w
+
+    def n_eff(self, recycle=None):
+        """Kish's sample size 1 / sum w^2 of the chain ``samples(recycle)`` returns.  It does not see the correlation between
+        populations that are ``sweeps`` sweeps apart."""
+        w = self._chain(recycle)[2]
+        return float(1.0 / np.sum(w * w))
+
+    def recycled_log_evidence(self):
+        """``log_z_recycled`` of :func:`recycled_weights` over every kept population: the evidence from all stages' particles."""
+        return self._chain(True)[3]
 
 
 # ------------------------------------------------------------------ the sampler over the engine
@@ -537,9 +745,10 @@ class SMCSampler(E.EngineSampler, SMCRun):
     ``'python'`` (the NumPy restatement over ``chi2_batch_device``); an engine group takes ``'python'``."""
 
     def __init__(self, vega, particles=1024, ess=0.5, sweeps=None, seed=0, driver='device', chunk=0, sample_params=None, stream=0,
-                 lanes=0, const_hint=-1, max_stages=None):
+                 lanes=0, const_hint=-1, max_stages=None, n_total=None, recycle=False):
         n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
-        SMCRun.__init__(self, None, n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, stream=stream, max_stages=max_stages)
+        SMCRun.__init__(self, None, n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, stream=stream, max_stages=max_stages,
+                        n_total=n_total, recycle=recycle)
 
     def _advance(self, n_stages):
         vega = self.vega
@@ -551,11 +760,15 @@ class SMCSampler(E.EngineSampler, SMCRun):
         u = np.zeros((self.particles, self.n)) if draw else self.u
         lnl = np.zeros(self.particles) if draw else self.lnl
         record, total = [], None
-        while n_stages > 0 and (draw or self.beta < 1.0):
-            rec, self.stage, self.beta, self.scale, st = vega.engine.smc_run(
+        while n_stages > 0 and (draw or not self.finished):
+            out = vega.engine.smc_run(
                 self.cols, self.lo, self.hi, self._theta, u, lnl, self.stage, self.beta, self.scale, min(n_stages, _PER_CALL),
                 self.ess, self.sweeps, log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint,
-                chunk=self.chunk, lanes=self.lanes, draw=draw)
+                chunk=self.chunk, lanes=self.lanes, draw=draw, **(dict(keep=True, topups_left=self.topups_left) if self.keeping else {}))
+            if self.keeping:
+                rec, self.stage, self.beta, self.scale, self.topups_left, st = out
+            else:
+                rec, self.stage, self.beta, self.scale, st = out
             self.u, self.lnl = u, lnl
             draw = False
             n_stages -= min(n_stages, _PER_CALL)
@@ -585,13 +798,16 @@ class SMCSet(E.EngineSampler):
     and a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`); None: every run reads the data
     the interface has installed - replicas of one run.  Every run ends on its own: at beta = 1 (``status`` 1), or because no
     particle has a finite lnL (2) or its ladder cannot advance (3); the last two do not stop the others.  An engine group takes
-    ``'python'``."""
+    ``'python'``.  ``n_total`` / ``recycle`` as for :class:`SMCRun`, the same for every run: a run that has reached beta = 1 stays
+    in the set until it has paid its R posterior rounds (vmx_smc_run_many_kept), beside the runs still on the ladder."""
 
     def __init__(self, vega, runs, particles=1024, streams=None, mock_rows=None, ess=0.5, sweeps=None, seed=0, driver='device',
-                 chunk=0, lanes=0, const_hint=-1, max_stages=None, sample_params=None):
+                 chunk=0, lanes=0, const_hint=-1, max_stages=None, sample_params=None, n_total=None, recycle=False):
         self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
-        probe = SMCRun(None, self.n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, max_stages=max_stages)   # (its checks)
+        probe = SMCRun(None, self.n, particles=particles, ess=ess, sweeps=sweeps, seed=seed, max_stages=max_stages, n_total=n_total,
+                       recycle=recycle)   # (its checks)
         self.particles, self.ess, self.sweeps, self.seed, self.max_stages = probe.particles, probe.ess, probe.sweeps, probe.seed, probe.max_stages
+        self.n_total, self.rounds, self.recycle, self.keeping = probe.n_total, probe.rounds, probe.recycle, probe.keeping
         self.E = int(runs)
         if self.E < 1:
             raise ValueError('runs: at least one')
@@ -610,27 +826,31 @@ class SMCSet(E.EngineSampler):
         self.scale = np.full(self.E, start_scale(self.n))
         self.status = np.zeros(self.E, dtype=np.int32)
         self.record = [[] for _ in range(self.E)]
+        self.topups_left = np.full(self.E, self.rounds, dtype=np.int32)
+        self.posterior_rounds = [[] for _ in range(self.E)]
         self.stats = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0, engine_calls=0,
                           host_waits=0, seconds=0.0, seconds_enqueuing=0.0, calls=0, rounds=0,
                           per_run=np.zeros((self.E, 4), dtype=np.int64))
 
     @property
     def finished(self):
-        """[E]: the run has reached beta = 1."""
-        return self.beta >= 1.0
+        """[E]: the run has reached beta = 1 and owes no posterior round."""
+        return (self.beta >= 1.0) & (self.topups_left <= 0)
 
     # ---- drivers
-    def _advance(self, n_stages):
-        """Up to ``n_stages`` rounds of the runs still going, as a set of their own (the engine's rows are those of the runs still
-        going either way); returns the statistics."""
+    def _advance(self, n_stages, rounds_only=False):
+        """Up to ``n_stages`` rounds of the runs still going (``rounds_only``: of those at beta = 1 that owe posterior rounds), as
+        a set of their own (the engine's rows are those of the runs still going either way); returns the statistics."""
         vega, N, n = self.vega, self.particles, self.n
         self._begin_advance(lambda: draw_start(1, n, self.seed, int(self.streams[0]))[0], 'smc_run_many')
         draw = self.u is None
         if draw:
             self.u, self.lnl = np.zeros((self.E, N, n)), np.zeros((self.E, N))
-        idx = np.flatnonzero(self.status == RUNNING)
+        idx = np.flatnonzero((self.status == RUNNING) & ((self.beta >= 1.0) if rounds_only else True))
         u, lnl = np.ascontiguousarray(self.u[idx]), np.ascontiguousarray(self.lnl[idx])
         stage, beta, scale = self.stage[idx].copy(), self.beta[idx].copy(), self.scale[idx].copy()
+        owed = self.topups_left[idx].copy()
+        kept = dict(keep=True, topups_left=owed) if self.keeping else {}
         streams = self.streams[idx]
         mocks = None if self.mock_rows is None else self.mock_rows[idx]
         records, total = [[] for _ in idx], None
@@ -655,8 +875,17 @@ class SMCSet(E.EngineSampler):
 
             with self._engine_rows() as self._rows:
                 try:
-                    records, status, _, st = python_stages_many(u, lnl, stage, beta, scale, n_stages, self.ess, self.sweeps, self.seed,
-                                                                streams, evaluate, draw=draw)
+                    if self.keeping:
+                        keep = [[] for _ in idx]
+                        records, status, _, _, st = python_stages_many(u, lnl, stage, beta, scale, n_stages, self.ess, self.sweeps,
+                                                                       self.seed, streams, evaluate, draw=draw, topups_left=owed,
+                                                                       keep=keep)
+                        for a in range(idx.size):
+                            for r, before in zip(records[a], keep[a]):
+                                r['u'] = before
+                    else:
+                        records, status, _, st = python_stages_many(u, lnl, stage, beta, scale, n_stages, self.ess, self.sweeps,
+                                                                    self.seed, streams, evaluate, draw=draw)
                 finally:
                     calls, self._rows = self._rows.calls, None
             add(dict(st, engine_calls=calls, host_waits=calls))
@@ -668,11 +897,15 @@ class SMCSet(E.EngineSampler):
                 if sub.size == 0 or (k == 0 and not draw):
                     break
                 su, sl, ss, sb, sc = (np.ascontiguousarray(arr[sub]) for arr in (u, lnl, stage, beta, scale))
+                if self.keeping:
+                    kept['topups_left'] = np.ascontiguousarray(owed[sub])
                 rec, stat, _, st = vega.engine.smc_run_many(
                     self.cols, self.lo, self.hi, self._theta, su, sl, ss, sb, sc, streams[sub], k, self.ess, self.sweeps,
                     mock_rows=None if mocks is None else mocks[sub], log_norm=self.log_norm(), seed=self.seed,
-                    const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw=draw)
+                    const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, draw=draw, **kept)
                 u[sub], lnl[sub], stage[sub], beta[sub], scale[sub], status[sub] = su, sl, ss, sb, sc, stat
+                if self.keeping:
+                    owed[sub] = kept['topups_left']
                 for a, e in enumerate(sub):
                     records[e].extend(rec[a])
                 per = np.zeros((idx.size, 4), dtype=np.int64)
@@ -681,8 +914,10 @@ class SMCSet(E.EngineSampler):
                 draw = False
                 n_stages -= k
         self.u[idx], self.lnl[idx], self.stage[idx], self.beta[idx], self.scale[idx], self.status[idx] = u, lnl, stage, beta, scale, status
+        self.topups_left[idx] = owed
         for a, e in enumerate(idx):
-            self.record[e].extend(records[a])
+            for r in records[a]:        # (the rows of the posterior rounds stay out of the ladder's record)
+                (self.posterior_rounds[e] if r['beta_prev'] >= 1.0 else self.record[e]).append(r)
         if total is not None:
             per = np.zeros((self.E, 4), dtype=np.int64)
             per[idx] = total['per_run']
@@ -693,22 +928,28 @@ class SMCSet(E.EngineSampler):
         """Every run to its end (``stages`` None; ``max_stages`` bounds the runs), or at most ``stages`` more rounds (0 on a new
         set: the start particles alone); the set does not depend on how it is cut."""
         t0 = time.perf_counter()
-        at = int(self.stage.max())
-        if stages is None:
-            call = 1 << 20 if self.max_stages is None else max(0, self.max_stages - at)
-        else:
-            call = int(stages)
-            if self.max_stages is not None:
-                call = min(call, max(0, self.max_stages - at))
-        going = (self.status == RUNNING) & (True if self.u is None else ~self.finished)
-        if (call > 0 or self.u is None) and np.any(going):        # (a first call of no stages draws and evaluates the start)
-            st = self._advance(max(call, 0))
+        at = max(len(r) for r in self.record)       # (max_stages bounds the ladder: posterior rounds do not count)
+        budget = 1 << 20 if stages is None else int(stages)
+        call = budget if self.max_stages is None else min(budget, max(0, self.max_stages - at))
+
+        def advance(count, rounds_only=False):
+            before = self.stats['rounds']
+            st = self._advance(count, rounds_only)
             for key, val in st.items():
                 if key in ('lanes', 'const_hint'):      # (what the engine ran with)
                     self.stats[key] = val
                 elif key in self.stats and key != 'seconds':
                     self.stats[key] = self.stats[key] + val
             self.stats['calls'] += 1
+            return self.stats['rounds'] - before
+
+        going = (self.status == RUNNING) & (True if self.u is None else ~self.finished)
+        if (call > 0 or self.u is None) and np.any(going):        # (a first call of no stages draws and evaluates the start)
+            budget -= advance(max(call, 0))
+        # the runs at beta = 1 that owe posterior rounds go on where max_stages has stopped the ladder of the others
+        owing = (self.status == RUNNING) & (self.beta >= 1.0) & (self.topups_left > 0)
+        if budget > 0 and np.any(owing):
+            advance(min(budget, int(self.topups_left[owing].max())), rounds_only=True)
         self.stats['seconds'] += time.perf_counter() - t0
         return self
 
@@ -726,11 +967,37 @@ class SMCSet(E.EngineSampler):
                 out[:, e] = evidence(self.record[e], self.particles)
         return out[0], out[1]
 
-    def samples(self):
+    def samples(self, recycle=None):
         """(points [E, N, n], lnL [E, N], weights [E, N] = 1 / N): the particles of every run - its posterior sample once finished
-        (a failed run's are what it started from)."""
+        (a failed run's are what it started from).  With ``n_total`` or ``recycle`` (None: the constructor's setting) every
+        entry is a list over the runs of what :meth:`SMCRun.samples` returns for that run: the ladders differ in length, and
+        with them the recycled chains."""
         self._ran()
-        return self.to_physical(self.u.copy()), self.lnl.copy(), np.full((self.E, self.particles), 1.0 / self.particles)
+        recycle = self.recycle if recycle is None else bool(recycle)
+        if not recycle and self.n_total is None:
+            return self.to_physical(self.u.copy()), self.lnl.copy(), np.full((self.E, self.particles), 1.0 / self.particles)
+        runs = [self._bare_member(e).samples(recycle) for e in range(self.E)]
+        return [r[0] for r in runs], [r[1] for r in runs], [r[2] for r in runs]
+
+    def n_eff(self, recycle=None):
+        """[E]: Kish's sample size of every run's chain (:meth:`SMCRun.n_eff`)."""
+        self._ran()
+        return np.array([self._bare_member(e).n_eff(recycle) for e in range(self.E)])
+
+    def recycled_log_evidence(self):
+        """[E]: :meth:`SMCRun.recycled_log_evidence` of every run; NaN for a failed run."""
+        self._ran()
+        return np.array([math.nan if self.status[e] in (NO_FINITE, STUCK) else self._bare_member(e).recycled_log_evidence()
+                         for e in range(self.E)])
+
+    def _bare_member(self, e):
+        """Run ``e``'s state in an :class:`SMCRun` in the unit cube's own terms, for its result methods."""
+        m = SMCRun(None, self.n, particles=self.particles, ess=self.ess, sweeps=self.sweeps, seed=self.seed, stream=int(self.streams[e]),
+                   max_stages=self.max_stages, n_total=self.n_total, recycle=self.recycle)
+        m.to_physical = self.to_physical
+        m.u, m.lnl, m.stage, m.beta, m.scale = self.u[e], self.lnl[e], int(self.stage[e]), float(self.beta[e]), float(self.scale[e])
+        m.record, m.posterior_rounds, m.topups_left = self.record[e], self.posterior_rounds[e], int(self.topups_left[e])
+        return m
 
     def member(self, e):
         """Run ``e`` as a sampler that has run: :class:`SMCSampler`'s result methods (``log_evidence``, ``samples``, ``stages``,
@@ -741,16 +1008,19 @@ class SMCSet(E.EngineSampler):
         m = SMCSampler(self.vega, particles=self.particles, ess=self.ess, sweeps=self.sweeps, seed=self.seed, driver=self.driver_asked,
                        chunk=self.chunk, sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))), values=self.values,
                                                             errors=self.errors),
-                       stream=int(self.streams[e]), lanes=self.lanes, const_hint=self.const_hint, max_stages=self.max_stages)
+                       stream=int(self.streams[e]), lanes=self.lanes, const_hint=self.const_hint, max_stages=self.max_stages,
+                       n_total=self.n_total, recycle=self.recycle)
         m.driver = self.driver
         m.run = m.reset = _read_only
         if self.u is not None:
             m.u, m.lnl = self.u[e].copy(), self.lnl[e].copy()
         m.stage, m.beta, m.scale = int(self.stage[e]), float(self.beta[e]), float(self.scale[e])
         m.record = list(self.record[e])
+        m.posterior_rounds, m.topups_left = list(self.posterior_rounds[e]), int(self.topups_left[e])
         took, own, bad, rows = (int(v) for v in self.stats['per_run'][e])
-        m.stats = dict({k: v for k, v in self.stats.items() if k not in ('per_run', 'rounds')}, stages=len(m.record),
-                       sweeps=len(m.record) * self.sweeps, rows=rows, rows_own_position=own, accepted=took, rejected_failed_model=bad)
+        done = len(m.record) + len(m.posterior_rounds)
+        m.stats = dict({k: v for k, v in self.stats.items() if k not in ('per_run', 'rounds')}, stages=done,
+                       sweeps=done * self.sweeps, rows=rows, rows_own_position=own, accepted=took, rejected_failed_model=bad)
         m.status = int(self.status[e])
         return m
 
@@ -763,7 +1033,10 @@ def smc_settings(main_config, sample_params):
     """The ``[SMC]`` settings of a main config with ``sampler = SMC`` (called by :func:`vega_amd.ensemble.sampler_settings`, which
     has checked ``run_sampler``): {sampler, path, name, particles, ess, sweeps, seed, driver, max_stages}, and ``derived`` / ``replicas`` (:mod:`vega_amd.replicas`) when the section states them; ``sweeps``
     None: 4 n.  ``mocks = M``: log Z and a posterior for each of M Monte-Carlo mocks in one run (the conditions of ``[Ensemble]
-    mocks``); ``together = True`` with ``replicas``: a rank's replicas advance as one :class:`SMCSet`."""
+    mocks``); ``together = True`` with ``replicas``: a rank's replicas advance as one :class:`SMCSet`.  ``n_total`` (a whole number
+    >= ``particles``) and ``recycle`` (True | False) are in the settings only when the section states them (:class:`SMCRun`); both
+    go with ``mocks`` and with ``together``, neither with ``replicas`` > 1: :func:`vega_amd.replicas.merge_smc` has no weighted
+    chains yet."""
     sec, limits, out = E.section_settings(main_config, sample_params, 'SMC', name='smc')
     n = len(limits)
     out.update(particles=sec.getint('particles', 1024), ess=sec.getfloat('ess', 0.5), sweeps=sec.getint('sweeps', None),
@@ -785,32 +1058,53 @@ def smc_settings(main_config, sample_params):
             out['together'] = sec.getboolean('together')
         except ValueError:
             raise ValueError('[SMC] together: True or False') from None
+    if 'n_total' in sec:
+        try:
+            out['n_total'] = sec.getint('n_total')
+        except ValueError:
+            raise ValueError('[SMC] n_total: a whole number, at least the particles') from None
+        if out['n_total'] < out['particles']:
+            raise ValueError('[SMC] n_total: a whole number, at least the particles')
+    if 'recycle' in sec:
+        try:
+            out['recycle'] = sec.getboolean('recycle')
+        except ValueError:
+            raise ValueError('[SMC] recycle: True or False') from None
+    if ('n_total' in out or 'recycle' in out) and out.get('replicas', 1) > 1:
+        raise ValueError('[SMC] n_total / recycle and replicas > 1 do not combine yet: the replicas\' weighted chains cannot be merged')
     return out
 
 
 def write_run(run, path, name, names, **derived):
     """The three files of an :class:`SMCRun`: (txt, paramnames, stats); ``derived``: the derived-parameter arguments of
     :func:`vega_amd.ensemble.write_getdist`."""
-    pts, lnl, _ = run.samples()
+    pts, lnl, w = run.samples()
+    keeping = getattr(run, 'keeping', False)
+    if keeping:         # (getdist's weights: the largest is 1)
+        derived = dict(derived, weights=w / w.max())
     txt, pn = E.write_getdist(path, name, names, pts, lnl, **derived)
     log_z, err = run.log_evidence()
     stats = Path(path) / f'{name}.stats'
     with open(stats, 'w') as f:
         f.write(f'log(Z) = {log_z!r}\nlog(Z) error = {err!r}\n')
-        f.write(f'stages = {run.stage}\nsweeps = {run.sweeps}\nlikelihood evaluations = {run.stats["rows"]}\n')
+        f.write(f'stages = {len(run.record) if keeping else run.stage}\nsweeps = {run.sweeps}\n')
+        f.write(f'likelihood evaluations = {run.stats["rows"]}\n')
         f.write(f'seed = {run.seed}\nparticles = {run.particles}\ness = {run.ess!r}\n')
         f.write('beta = ' + ' '.join(repr(float(r['beta'])) for r in run.record) + '\n')
+        if keeping:
+            f.write(f'posterior rounds = {len(run.posterior_rounds)}\nposterior points = {lnl.size}\nn_eff = {run.n_eff()!r}\n')
+            f.write(f'log(Z) recycled = {run.recycled_log_evidence()!r}\n')
     return txt, pn, stats
 
 
 def read_stats(path):
     """``name.stats`` back as a dict (floats for the evidence lines and ``ess``, a list of floats for ``beta``, ints for the
-    counts)."""
+    counts; ``n_eff`` and ``log(Z) recycled``, floats, where the run had ``n_total`` or ``recycle``)."""
     out = {}
     for line in Path(path).read_text().splitlines():
         key, _, val = line.partition(' = ')
         if key == 'beta':
             out[key] = [float(v) for v in val.split()]
         else:
-            out[key] = float(val) if key in ('log(Z)', 'log(Z) error', 'ess') else int(val)
+            out[key] = float(val) if key in ('log(Z)', 'log(Z) error', 'ess', 'n_eff', 'log(Z) recycled') else int(val)
     return out
