@@ -331,6 +331,10 @@ int vmx_model_size(vmx_engine* e);
  * times static factors: they carry a static coefficient basis) have none: the value is then -3 - n_columns. */
 int vmx_pipeline_column(vmx_engine* e, int32_t pipeline);
 
+/* Precondition of the QSO radiation term (vmx_pipe_desc::radiation): no bin of such a pipeline may have r_perp = 0.  The term
+ * divides by r_shift^2 = (r_par' + delta_rp)^2 + r_perp'^2 through a reciprocal square root without a guard; with r_perp = 0 a
+ * walker's delta_rp can cancel a bin centre, and that bin's model is then NaN (VMX_STATUS_NONFINITE for the walker).  Grids of
+ * bin centres have r_perp > 0 everywhere. */
 /* Evaluate B parameter points.  theta [B][n_params] host memory.
  * chi2 [B] (may be NULL), model [B][vmx_model_size] (may be NULL), status [B] (may be NULL).
  * Synchronous: outputs are valid on return. */
@@ -942,8 +946,45 @@ void* vmx_stream(vmx_engine* e);
  * walkers that left the mu rule's box since vmx_finalize, form of the last evaluation (vmx_set_quadratic_form_kind)}.
  * 5 = the assembled pre-distortion vector [B][pad32(n_model)] of item `index` as the last full-chain evaluation handed it to
  * the distortion product (refused after a chi2-only evaluation and after a single walker's fused product, which keeps none).
+ * 4 has one more entry, [9]: the bins kernels the last evaluation launched, a mask of VMX_ROUTE_* (kept with a captured chain,
+ * so it holds for a replayed graph too; VMX_ROUTE_POLY_BINS says what set-up launched).
+ * The operands of the spline-bins stage, for an oracle that starts where the kernels start (host-side copies, no kernel):
+ * 6 = the walkers' scalars [B][n_pipelines][VMX_DEBUG_NS] of the last evaluation; 7 = where the entries the bins read sit in
+ * such a row: {VMX_DEBUG_NS, then the indices in the order of VMX_DEBUG_SCALARS};
+ * 8 = the per-bin static arrays of pipeline `index` as uploaded, [8][n]: r, r_par, r_perp, z, rel z, ln rel z (std::log on the
+ * host: read it, do not recompute it), ln rel z of the second tracer, growth;
+ * 9 = the spline grid: {n_coef, ncp, same_grid, extrapolate, n_columns (pipelines with a column of per-walker coefficients), then per ell (4): x0, h, inv_h, xlast}, and of pipeline
+ * `index`: {column (-1: none), n, n_pad, split_evol, static basis (-1: none), static bins (1: PipeDev::poly_bins_off >= 0),
+ * odd_x0, odd_h, odd_ncoef};
+ * 10 = x' - x0' of item `index` after a chi2-only evaluation [B][nq_pad]; 11 = its x0' [nq_pad];
+ * 12 = the static basis on the bins of pipeline `index` [3][n_pad] (refused for a pipeline without: "none").
+ * 13 = the groups of lean pipelines whose bins arrive pre-summed: {groups, then of group `index`: members, n, n_pad, presum, per
+ * member (pipeline, factor kind 0: 1, 1: theta[factor index], 2: the metal pair's bias product, factor index)} - {groups} alone
+ * for an index outside; 14 = the pre-summed array [B][n_pad] of group `index` after an evaluation that summed on the way.
+ * 18, 19 = the same for the groups of static-coordinate pipelines; 15 = the static coefficient basis
+ * [n_ell_max][n_static][3][ncp] (a pipeline's place: the static basis of tap 9); 16 = the odd-multipole coefficient rows
+ * [4][odd_ncoef] of pipeline `index`; 17 = the metal pairs' walker factors [B][3][n_metals] (bias product x multiplicity,
+ * beta1 + beta2, beta1 beta2) of the last evaluation.
  * Returns the number of doubles written (<= capacity) or a negative error. */
 int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, int64_t capacity);
+#define VMX_DEBUG_NS 40
+#define VMX_DEBUG_SCALARS(X) X(AP) X(AT) X(DRP) X(EV1A) X(EV1B) X(EV2A) X(EV2B) X(BIAS1) X(BB1) X(BIAS2) X(BB2) \
+                             X(RAD_S) X(RAD_A) X(RAD_L) X(RAD_D) X(RAD_IL) X(RAD_ID)
+enum { VMX_ROUTE_GENERAL = 1,            /* k_xi_bins<false> */
+       VMX_ROUTE_STATIC_TAPS = 2,        /* k_xi_bins<true> */
+       VMX_ROUTE_STATIC = 4,             /* k_xi_bins_static */
+       VMX_ROUTE_STATIC_NW = 8,          /* k_xi_bins_static_nw<4> */
+       VMX_ROUTE_LEAN = 16,              /* k_xi_bins_lean<2, .> */
+       VMX_ROUTE_GROUP = 32,             /* k_xi_bins_group<2, .> */
+       VMX_ROUTE_STATIC_GROUP = 64,      /* k_xi_bins_static_group<2> */
+       VMX_ROUTE_ASSEMBLE_QUAD = 128,    /* k_xi_assemble_quad */
+       VMX_ROUTE_ASSEMBLE_QUAD_GENERAL = 256,    /* ... with an item on its general branch (not a plain pair) */
+       VMX_ROUTE_QUAD_PLAIN = 512,       /* k_xi_quad_plain<2, .> */
+       VMX_ROUTE_SAME_GRID = 1024,       /* the SAME = true instantiations (one ln r grid for every multipole) */
+       VMX_ROUTE_POLY_BINS = 2048 };     /* set-up ran k_poly_bins */
+/* The device math functions of the kernels, elementwise on host arrays (a trivial kernel of its own; for tests against
+ * extended precision): which = 0 vmx_log, 1 vmx_exp, 2 vmx_rsqrt.  x [n] -> out [n]. */
+int vmx_debug_math(vmx_engine* e, int32_t which, const double* x, int64_t n, double* out);
 
 /* Stand-alone distortion-style product y[b] = A x[b] through the same kernels the evaluation
  * uses (bench / roofline measurement of the distortion-matrix step).  d_A row-major [rows][cols] with

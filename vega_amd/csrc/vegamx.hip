@@ -1502,6 +1502,11 @@ struct vmx_engine {
     const MargReq* marg_req = nullptr;      // set while vmx_marg_coeff_device runs the chain: derived columns instead of chi2
     int marg_slab_rows = 0;          // rows of the items' mg_y (K slabs of G dx)
     int last_form = 0;               // form of the last evaluation: 0 full chain, 1 Q', 2 factored (vmx_debug_read 4 [8])
+    // bins kernels of the last evaluation (vmx_debug_read 4 [9], VMX_ROUTE_*); route_setup: those of set-up.  A replayed graph runs
+    // no host code: graph_route keeps the mask and last_taps of each captured chain.
+    int last_route = 0, route_setup = 0;
+    struct ChainFacts { int route = 0; bool taps = true; };
+    std::map<int, ChainFacts> graph_route;
     // VMX_TRACE_HOST: host-side phases of vmx_eval accumulated in nanoseconds (staging, enqueue, wait), printed at destroy
     bool trace_host = false; double host_ns[3] = {0, 0, 0}; int64_t host_calls = 0;
     EngineDev dev{};
@@ -2316,7 +2321,7 @@ int vmx_set_metal_beta_override(vmx_engine* e, int32_t enabled, double beta)
     HIP_OK(hipSetDevice(e->device));
     HIP_OK(hipStreamSynchronize(e->stream));
     for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second);
-    e->graphs.clear();
+    e->graphs.clear(); e->graph_route.clear();
     return 0;
 }
 
@@ -3205,6 +3210,7 @@ static int poly_basis_build(vmx_engine* e)
         for (int p : e->pk_static) max_n = std::max(max_n, (int)e->pipes[p].n);
         hipLaunchKernelGGL(k_poly_bins, dim3((max_n + 255) / 256, ns, 3), dim3(256), 0, e->stream, e->dev, e->d_pk_static.p,
                            e->poly_bins.p, d_ok.p);
+        e->route_setup |= VMX_ROUTE_POLY_BINS;
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(e->stream));
         HIP_OK(hipMemcpy(ok.data(), d_ok.p, ok.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -3594,16 +3600,21 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
     bool xi_fused = quad && (size_t)n_pipe == 2 * e->items.size();
     for (auto* it : e->items) if (!it->metals.empty() || it->dev.d.pipe_peak == it->dev.d.pipe_smooth) xi_fused = false;
     e->last_taps = !(xi_fused && B > 8);
+    int route = D.same_grid ? VMX_ROUTE_SAME_GRID : 0;
     if (xi_fused) {
         ScopedTimer t(e, KC_XI);
         int max_nq = 0;
         for (auto* it : e->items) max_nq = std::max(max_nq, (int)it->dev.nq_pad);
         XiPlainArgs XA{};
         // (two walkers per thread: 41 us at B = 256 against 53 with one; four measured the same as two)
-        if (B > 8 && xi_plain_args(e, XA))
+        if (B > 8 && xi_plain_args(e, XA)) {
+            route |= VMX_ROUTE_QUAD_PLAIN;
             hipLaunchKernelGGL((D.same_grid ? k_xi_quad_plain<2, true> : k_xi_quad_plain<2, false>), dim3((max_nq + 255) / 256, (B + 1) / 2, (unsigned)e->items.size()), dim3(256), 0, e->stream, D, XA, 0, B);
-        else
-        hipLaunchKernelGGL(k_xi_assemble_quad, dim3((max_nq + 255) / 256, B, (unsigned)e->items.size()), dim3(256), 0, e->stream, D, 0, B <= 8 ? 1 : 0);
+        } else {
+            route |= VMX_ROUTE_ASSEMBLE_QUAD;
+            for (auto* it : e->items) if (!it->dev.plain_pair) route |= VMX_ROUTE_ASSEMBLE_QUAD_GENERAL;
+            hipLaunchKernelGGL(k_xi_assemble_quad, dim3((max_nq + 255) / 256, B, (unsigned)e->items.size()), dim3(256), 0, e->stream, D, 0, B <= 8 ? 1 : 0);
+        }
     } else {
         ScopedTimer t(e, KC_XI);
         int max_n = 0;
@@ -3615,6 +3626,7 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
         if (sums_on && !e->lean_groups.empty()) {
             // (walkers per thread of the lean kernels: 1 / 2 / 4 measured the same - the stage is bound by its dependent lookups)
             const dim3 grid((max_n + 255) / 256, (unsigned)e->lean_groups.size(), (B + 1) / 2);
+            route |= VMX_ROUTE_GROUP;
             hipLaunchKernelGGL((D.same_grid ? k_xi_bins_group<2, true> : k_xi_bins_group<2, false>), grid, dim3(256), 0, e->stream, D, e->d_lean_groups.p, B);
             if (!e->lean_single.empty()) {
                 XiLeanArgs LA{};
@@ -3625,10 +3637,13 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
                     L.n_ell = P.d.n_ell; L.split_evol = P.split_evol; L.radiation = P.d.is_peak ? 0 : P.d.radiation;
                 }
                 const dim3 single((max_n + 255) / 256, (unsigned)e->lean_single.size(), (B + 1) / 2);
+                route |= VMX_ROUTE_LEAN;
                 hipLaunchKernelGGL((D.same_grid ? k_xi_bins_lean<2, true> : k_xi_bins_lean<2, false>), single, dim3(256), 0, e->stream, D, LA, B);
             }
-            if (!e->xi_rest_pipes.empty())
+            if (!e->xi_rest_pipes.empty()) {
+                route |= VMX_ROUTE_GENERAL;
                 hipLaunchKernelGGL(k_xi_bins<false>, dim3((max_n + 255) / 256, (unsigned)e->xi_rest_pipes.size(), B), dim3(256), 0, e->stream, D, e->d_xi_rest_pipes.p);
+            }
         } else if (B > 8 && !e->direct && !e->xi_lean_pipes.empty()) {
             XiLeanArgs LA{};
             for (size_t q = 0; q < e->xi_lean_pipes.size(); ++q) {
@@ -3638,23 +3653,33 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
                 L.n_ell = P.d.n_ell; L.split_evol = P.split_evol; L.radiation = P.d.is_peak ? 0 : P.d.radiation;
             }
             const dim3 grid((max_n + 255) / 256, (unsigned)e->xi_lean_pipes.size(), (B + 1) / 2);
+            route |= VMX_ROUTE_LEAN;
             hipLaunchKernelGGL((D.same_grid ? k_xi_bins_lean<2, true> : k_xi_bins_lean<2, false>), grid, dim3(256), 0, e->stream, D, LA, B);
-            if (!e->xi_rest_pipes.empty())
+            if (!e->xi_rest_pipes.empty()) {
+                route |= VMX_ROUTE_GENERAL;
                 hipLaunchKernelGGL(k_xi_bins<false>, dim3((max_n + 255) / 256, (unsigned)e->xi_rest_pipes.size(), B), dim3(256), 0, e->stream, D, e->d_xi_rest_pipes.p);
-        } else if (e->n_active > 0)
+            }
+        } else if (e->n_active > 0) {
+            route |= VMX_ROUTE_GENERAL;
             hipLaunchKernelGGL(k_xi_bins<false>, dim3((max_n + 255) / 256, e->n_active, B), dim3(256), 0, e->stream, D, e->d_pipe_active.p);
+        }
         if (!e->pk_static.empty())
         {
             // static-basis pipelines: tap form, and the ones already evaluated on their (static) bins
-            if (!e->xi_static_taps.empty())
+            if (!e->xi_static_taps.empty()) {
+                route |= VMX_ROUTE_STATIC_TAPS;
                 hipLaunchKernelGGL(k_xi_bins<true>, dim3((max_n + 255) / 256, (unsigned)e->xi_static_taps.size(), B), dim3(256), 0, e->stream, D, e->d_xi_static_taps.p);
+            }
             if (sums_on && !e->xi_static_bins.empty()) {
                 if (!e->static_groups.empty()) {
                     const dim3 grid((max_n + 255) / 256, (unsigned)e->static_groups.size(), (B + 1) / 2);
+                    route |= VMX_ROUTE_STATIC_GROUP;
                     hipLaunchKernelGGL(k_xi_bins_static_group<2>, grid, dim3(256), 0, e->stream, D, e->d_static_groups.p, B);
                 }
-                if (!e->static_single.empty())
+                if (!e->static_single.empty()) {
+                    route |= VMX_ROUTE_STATIC;
                     hipLaunchKernelGGL(k_xi_bins_static, dim3((max_n + 255) / 256, (unsigned)e->static_single.size(), B), dim3(256), 0, e->stream, D, e->d_static_single.p);
+                }
             } else if (!e->xi_static_bins.empty()) {
                 bool lean = e->xi_lean && B > 8 && (int)e->xi_static_bins.size() <= VMX_XI_LEAN_MAX;
                 for (int p : e->xi_static_bins) {
@@ -3673,12 +3698,16 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
                     }
                     // (four walkers per thread load the three basis values and the two per-bin factors once: 96 -> 51 us at B = 512)
                     const dim3 grid((max_n + 255) / 256, (unsigned)e->xi_static_bins.size(), (B + 3) / 4);
+                    route |= VMX_ROUTE_STATIC_NW;
                     hipLaunchKernelGGL(k_xi_bins_static_nw<4>, grid, dim3(256), 0, e->stream, D, LA, B);
-                } else
+                } else {
+                    route |= VMX_ROUTE_STATIC;
                     hipLaunchKernelGGL(k_xi_bins_static, dim3((max_n + 255) / 256, (unsigned)e->xi_static_bins.size(), B), dim3(256), 0, e->stream, D, e->d_xi_static_bins.p);
+                }
             }
         }
     }
+    e->last_route = route;
     // dense metal-matrix products of an item (no split-K: the consumer reads one slab)
     auto metal_products = [&](ItemHost* it) {
         launch_metal_kron(e, D, it, B);
@@ -4066,11 +4095,15 @@ static int run_chain_cached(vmx_engine* e, int B, int tab_mode, bool zero_copy =
             return run_chain(e, B, tab_mode, zero_copy, nullptr, nullptr, nullptr, quad);
         }
         it = e->graphs.emplace(key, exec).first;
+        e->graph_route[key].route = e->last_route;        // (of the capture: the launches the graph replays)
+        e->graph_route[key].taps = e->last_taps;
     }
     HIP_OK(hipGraphLaunch(it->second, e->stream));
     e->last_B = B;
     e->last_full = !quad;
     e->last_form = quad ? (e->quad_factored ? 2 : 1) : 0;       // (a replayed graph runs no host code: run_chain set this at capture only)
+    e->last_route = e->graph_route[key].route;
+    e->last_taps = e->graph_route[key].taps;
     return 0;
 }
 
@@ -4283,7 +4316,7 @@ static int quad_build(vmx_engine* e)
     e->last_B = 0;                  // the reference evaluation is not a caller's evaluation
     // graphs captured before hold the previous per-mock buffers (q_lin / q_c0 grow with the pool): capture again
     for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second);
-    e->graphs.clear();
+    e->graphs.clear(); e->graph_route.clear();
     return 0;
 }
 
@@ -4311,7 +4344,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
     L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->ev_rows = nullptr; L->ev_lane = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
-    L->graphs.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
+    L->graphs.clear(); L->graph_route.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
     L->pin_theta = nullptr; L->pin_chi2 = nullptr; L->pin_status = nullptr; L->pin_done = nullptr; L->pin_part = nullptr;
     L->dpin_theta = nullptr; L->dpin_chi2 = nullptr; L->dpin_status = nullptr; L->dpin_done = nullptr; L->dpin_part = nullptr;
     L->host_key_valid = false; L->pending_key.clear();
@@ -6170,7 +6203,7 @@ int vmx_set_mu_quadrature(vmx_engine* e, int32_t node_rule)
     e->mu_nodes_on = node_rule != 0 && e->n_extra > 0;
     e->dev.k_node_max = e->mu_nodes_on ? e->k_node_max : 0.0;
     for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second);      // (captured graphs hold the previous setting)
-    e->graphs.clear();
+    e->graphs.clear(); e->graph_route.clear();
     e->quad_lin_dirty = true;       // the reference point (x0', m0) is re-evaluated with the new rule; Q' and W do not depend on it
     return e->mu_nodes_on ? 1 : 0;
 }
@@ -6400,7 +6433,8 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (capacity >= 5) out[4] = e->last_tab_level;
         if (capacity >= 7) { out[5] = live[2]; out[6] = live[3]; }
         if (capacity >= 9) out[8] = e->last_form;               // 0: full chain, 1: the quadratic form Q', 2: its factored form
-        if (capacity >= 8) { out[7] = live[4]; return capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
+        if (capacity >= 10) out[9] = e->last_route | e->route_setup;        // bins kernels launched (VMX_ROUTE_*)
+        if (capacity >= 8) { out[7] = live[4]; return capacity >= 10 ? 10 : capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
         return capacity >= 7 ? 7 : capacity >= 5 ? 5 : capacity >= 4 ? 4 : 3;
     }
     else if (what == 5) {
@@ -6412,10 +6446,113 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (!e->last_full || fused) { fail(-1, "the last evaluation (chi2 only, or a single walker's fused distortion product) did not store the pre-distortion vector"); return -1; }
         src = it->vec.p; count = (int64_t)B * it->dev.n_model_pad;
     }
+    else if (what == 6) { src = e->scal.p; count = (int64_t)B * (int64_t)e->pipes.size() * VMX_NS; }
+    else if (what == 7) {
+        static_assert(VMX_DEBUG_NS == VMX_NS, "vegamx.h states the row length of the scalars");
+#define VMX_SCALAR_INDEX(name) S_##name,
+        const int idx[] = {VMX_NS, VMX_DEBUG_SCALARS(VMX_SCALAR_INDEX)};
+#undef VMX_SCALAR_INDEX
+        const int64_t n = sizeof(idx) / sizeof(idx[0]);
+        if (capacity < n) { fail(-1, "invalid argument: capacity too small"); return -1; }
+        for (int64_t i = 0; i < n; ++i) out[i] = idx[i];
+        return n;
+    }
+    else if (what == 8) {
+        if (index < 0 || index >= (int)e->pipes.size()) { fail(-1, "invalid argument: pipeline index"); return -1; }
+        const PipeDev& P = e->pipes[index];
+        const double* arr[8] = {e->cr.p, e->crp.p, e->crt.p, e->cz.p, e->crelz.p, e->clnrelz.p, e->clnrelz2.p, e->cgrowth.p};
+        if ((int64_t)8 * P.n > capacity) { fail(-1, "invalid argument: capacity too small"); return -1; }
+        for (int a = 0; a < 8; ++a)
+            if (hipMemcpy(out + (size_t)a * P.n, arr[a] + P.coord_off, (size_t)P.n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { fail(-2, "hipMemcpy"); return -2; }
+        return (int64_t)8 * P.n;
+    }
+    else if (what == 9) {
+        if (index < 0 || index >= (int)e->pipes.size()) { fail(-1, "invalid argument: pipeline index"); return -1; }
+        if (capacity < 30) { fail(-1, "invalid argument: capacity too small"); return -1; }
+        const EngineDev& D = e->dev;
+        const PipeDev& P = e->pipes[index];
+        int64_t n = 0;
+        out[n++] = D.n_coef; out[n++] = D.ncp; out[n++] = D.same_grid; out[n++] = D.extrapolate; out[n++] = e->n_active;       // (n_active: the columns of the coefficient buffer)
+        for (int l = 0; l < VMX_MAX_ELL; ++l) { out[n++] = D.x0[l]; out[n++] = D.h[l]; out[n++] = D.inv_h[l]; out[n++] = D.xlast[l]; }
+        out[n++] = P.col; out[n++] = P.n; out[n++] = P.n_pad; out[n++] = P.split_evol; out[n++] = P.poly_basis;
+        out[n++] = P.poly_bins_off >= 0 ? 1 : 0; out[n++] = P.odd_x0; out[n++] = P.odd_h; out[n++] = P.odd_ncoef;
+        return n;
+    }
+    else if (what == 10 || what == 11) {
+        if (index < 0 || index >= (int)e->items.size()) { fail(-1, "invalid argument: item index"); return -1; }
+        const ItemHost* it = e->items[index];
+        if (e->last_full || e->last_form == 0 || !it->q_x.p || !it->q_x0.p) { fail(-1, "the last evaluation was not a chi2-only evaluation of the quadratic form: no x' - x0'"); return -1; }
+        src = what == 10 ? it->q_x.p : it->q_x0.p; count = (what == 10 ? (int64_t)B : 1) * it->dev.nq_pad;
+    }
+    else if (what == 12) {
+        if (index < 0 || index >= (int)e->pipes.size()) { fail(-1, "invalid argument: pipeline index"); return -1; }
+        const PipeDev& P = e->pipes[index];
+        if (P.poly_bins_off < 0 || !e->poly_bins.p) { fail(-1, "none: the pipeline has no static basis on its bins"); return -1; }
+        src = e->poly_bins.p + P.poly_bins_off; count = (int64_t)3 * P.n_pad;
+    }
+    else if (what == 13 || what == 14 || what == 18 || what == 19) {
+        // the groups of xi_sum_plan (13, 14: lean; 18, 19: static-coordinate): 13 / 18 = {groups, then of group `index`: members, n,
+        // n_pad, presum, per member (pipeline, factor kind, factor index)}; 14 / 19 = its pre-summed array [B][n_pad] after an
+        // evaluation that summed on the way
+        const bool lean = what < 18, describe = what == 13 || what == 18;
+        const int ng = (int)(lean ? e->lean_groups.size() : e->static_groups.size());
+        if (describe && (index < 0 || index >= ng)) {
+            if (capacity < 1) { fail(-1, "invalid argument: capacity too small"); return -1; }
+            out[0] = ng;
+            return 1;
+        }
+        if (index < 0 || index >= ng) { fail(-1, "invalid argument: group index"); return -1; }
+        // (XiLeanGroup and XiStaticGroup differ in the length of their member array only)
+        auto serve = [&](const auto& G) -> int64_t {
+            if (describe) {
+                if (capacity < 5 + 3 * G.n_members) { fail(-1, "invalid argument: capacity too small"); return -1; }
+                int64_t n = 0;
+                out[n++] = ng; out[n++] = G.n_members; out[n++] = G.n; out[n++] = G.n_pad; out[n++] = G.presum;
+                for (int m = 0; m < G.n_members; ++m) { out[n++] = G.m[m].pipe; out[n++] = G.m[m].fkind; out[n++] = G.m[m].findex; }
+                return n;
+            }
+            if (!(e->last_route & (lean ? VMX_ROUTE_GROUP : VMX_ROUTE_STATIC_GROUP))) { fail(-1, "the last evaluation did not sum its bins on the way: no group array"); return -1; }
+            src = e->xi.p + G.out_off; count = (int64_t)B * G.n_pad;
+            return 0;
+        };
+        const int64_t served = lean ? serve(e->lean_groups[index]) : serve(e->static_groups[index]);
+        if (served != 0) return served;
+    }
+    else if (what == 15) { src = e->poly_coef.p; count = (int64_t)VMX_MAX_ELL * (int64_t)e->pk_static.size() * 3 * e->ncp; if (count == 0) { fail(-1, "none: no pipeline has a static coefficient basis"); return -1; } }
+    else if (what == 16) {
+        if (index < 0 || index >= (int)e->pipes.size()) { fail(-1, "invalid argument: pipeline index"); return -1; }
+        const PipeDev& P = e->pipes[index];
+        if (!P.odd_rel && !P.odd_asy) { fail(-1, "none: the pipeline has no odd-multipole terms"); return -1; }
+        src = e->odd_coef.p + P.odd_off; count = (int64_t)4 * P.odd_ncoef;
+    }
+    else if (what == 17) { src = e->metal_bias.p; count = (int64_t)B * 3 * (int64_t)e->metals.size(); if (count == 0) { fail(-1, "none: no metal terms"); return -1; } }
     else { fail(-1, "invalid argument: what"); return -1; }
     if (count > capacity) { fail(-1, "invalid argument: capacity too small"); return -1; }
     if (hipMemcpy(out, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { fail(-2, "hipMemcpy"); return -2; }
     return count;
+}
+
+// the device math functions elementwise (tests against extended precision: nothing else launches this)
+__global__ __launch_bounds__(256) void k_debug_math(int which, const double* x, double* out, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double v = x[i];
+    out[i] = which == 0 ? vmx_log(v) : which == 1 ? vmx_exp(v) : vmx_rsqrt(v);
+}
+
+int vmx_debug_math(vmx_engine* e, int32_t which, const double* x, int64_t n, double* out)
+{
+    REQUIRE(e && x && out && n > 0 && n <= ((int64_t)1 << 30) && which >= 0 && which <= 2, "vmx_debug_math");
+    wait_lane(e);
+    HIP_OK(hipSetDevice(e->device));
+    DevBuf<double> dx, dy;
+    if (dx.upload(x, (size_t)n) || dy.alloc((size_t)n, false)) return -2;
+    hipLaunchKernelGGL(k_debug_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, (int)which, dx.p, dy.p, n);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(e->stream));
+    HIP_OK(hipMemcpy(out, dy.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int vmx_matvec_device(vmx_engine* e, const double* d_A, int32_t rows, int32_t cols, const double* d_x, int32_t B,

@@ -362,6 +362,7 @@ def load_library():
     lib.vmx_set_lanes.argtypes = [C.c_void_p, C.c_int32]
     lib.vmx_debug_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dptr, C.c_int64]
     lib.vmx_debug_read.restype = C.c_int64
+    lib.vmx_debug_math.argtypes = [C.c_void_p, C.c_int32, dptr, C.c_int64, dptr]
     lib.vmx_matvec_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p]
     lib.vmx_item_set_metal_static.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dptr, C.c_int32]
@@ -410,7 +411,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -681,6 +682,10 @@ class Engine:
         self.csr_items = []
         self.metal_source = {}          # (item name, pair index) -> (global metal index, pipeline id, has matrix)
         self.low = Lowering(problem, extra_names)
+        self.pipe_descs = {}            # pipeline id -> its PipeDesc as handed to vmx_add_pipeline (the bins taps below)
+        # item name -> what vmx_item_set_additive_template / vmx_item_add_broadband were handed: {'template': (vector, slot,
+        # default) or None, 'broadband': [(position, function, slots, basis)]}
+        self.item_extras = {}
         self.names = self.low.names
         self.n_params = len(self.names)
         self.max_batch = int(max_batch)
@@ -745,6 +750,7 @@ class Engine:
             self._h, C.byref(desc), n, _dp(_f64(pipe.r)), _dp(_f64(pipe.mu)), _dp(_f64(pipe.z)),
             _dp(_f64(pipe.rel_z_evol)), _dp(_f64(pipe.xi_growth))))
         self.n_pipelines = pid + 1
+        self.pipe_descs[pid] = desc
         if getattr(pipe, 'rel_z_evol_1', None) is not None:
             # new-bias-evolution: each tracer of a cross-correlation evolves with its own redshift
             self._check(self.lib.vmx_pipeline_set_tracer_evolution(
@@ -907,8 +913,10 @@ class Engine:
                                                                 dense.shape[1], _dp(dense)))
                         entry += 1
 
+            extras = self.item_extras[name] = {'template': None, 'broadband': []}
             if item.inst_sys_table is not None:
                 vec = _f64(static_terms.instrumental_systematics_template(item))
+                extras['template'] = (vec, low.s('desi_inst_sys_amp'), static_terms.DESI_INST_SYS_DEFAULT_AMP)
                 self._check(lib.vmx_item_set_additive_template(self._h, iid, _dp(vec), vec.size,
                                                                low.s('desi_inst_sys_amp'),
                                                                static_terms.DESI_INST_SYS_DEFAULT_AMP))
@@ -939,6 +947,7 @@ class Engine:
                     func = BB_POLY
                 if slots.size > 16:
                     raise NotImplementedError('more than 16 coefficients in one broadband term')
+                extras['broadband'].append((pos, func, slots, basis))
                 self._check(lib.vmx_item_add_broadband(self._h, iid, pos, func, slots.size, _ip(slots),
                                                        _dp(basis), basis.shape[1]))
 
@@ -1551,6 +1560,111 @@ class Engine:
         (|| U r0 - F dx ||^2, 2 n_masked nq flops: model grids much finer than the data grid) - include/vegamx.h:
         vmx_set_quadratic_form_kind."""
         self._check(self.lib.vmx_set_quadratic_form_kind(self._h, self.QUADRATIC_FORM_KINDS[kind]))
+
+    # ---- operands of the spline-bins stage (include/vegamx.h: vmx_debug_read 6 ... 19, 4 [9]; vmx_debug_math)
+    ROUTE_BITS = {'general': 1, 'static_taps': 2, 'static': 4, 'static_nw': 8, 'lean': 16, 'group': 32, 'static_group': 64,
+                  'assemble_quad': 128, 'assemble_quad_general': 256, 'quad_plain': 512, 'same_grid': 1024, 'poly_bins': 2048}
+    # (the order of VMX_DEBUG_SCALARS in include/vegamx.h; tests/test_xi_bins_host.py holds the two together)
+    BINS_SCALAR_NAMES = ('AP', 'AT', 'DRP', 'EV1A', 'EV1B', 'EV2A', 'EV2B', 'BIAS1', 'BB1', 'BIAS2', 'BB2',
+                         'RAD_S', 'RAD_A', 'RAD_L', 'RAD_D', 'RAD_IL', 'RAD_ID')
+    BINS_STATIC_NAMES = ('r', 'rp', 'rt', 'z', 'relz', 'lnrelz', 'lnrelz2', 'growth')
+    MATH_FUNCTIONS = {'log': 0, 'exp': 1, 'rsqrt': 2}
+
+    def bins_route(self):
+        """The bins kernels the last evaluation launched: the set of ROUTE_BITS names (vmx_debug_read 4 [9])."""
+        mask = int(self.debug_read(4, 0, 10)[9])
+        return {name for name, bit in self.ROUTE_BITS.items() if mask & bit}
+
+    def bins_scalar_index(self):
+        """{'NS': row length, 'AP': index, ...} of a walker's scalars as the bins kernels read them (vmx_debug_read 7)."""
+        idx = self.debug_read(7, 0, 32).astype(int)
+        names = ('NS',) + self.BINS_SCALAR_NAMES
+        assert idx.size == len(names)
+        return dict(zip(names, idx.tolist()))
+
+    def bins_scalars(self, B):
+        """The walkers' scalars of the last evaluation [B, n_pipelines, NS] (vmx_debug_read 6)."""
+        ns = self.bins_scalar_index()['NS']
+        return self.debug_read(6, 0, B * self.n_pipelines * ns).reshape(B, self.n_pipelines, ns).copy()
+
+    def bins_static(self, pid):
+        """The per-bin static arrays of a pipeline as uploaded: {'r', 'rp', 'rt', 'z', 'relz', 'lnrelz', 'lnrelz2', 'growth'}."""
+        n = int(self.bins_grid(pid)['n'])
+        arr = self.debug_read(8, pid, 8 * n).reshape(8, n)
+        return {name: arr[i].copy() for i, name in enumerate(self.BINS_STATIC_NAMES)}
+
+    def bins_grid(self, pid):
+        """The spline grid and the pipeline's place on it (vmx_debug_read 9)."""
+        g = self.debug_read(9, pid, 32)
+        out = dict(n_coef=int(g[0]), ncp=int(g[1]), same_grid=bool(g[2]), extrapolate=bool(g[3]), n_columns=int(g[4]))
+        per_ell = g[5:21].reshape(4, 4)
+        out.update(x0=per_ell[:, 0].copy(), h=per_ell[:, 1].copy(), inv_h=per_ell[:, 2].copy(), xlast=per_ell[:, 3].copy())
+        out.update(column=int(g[21]), n=int(g[22]), n_pad=int(g[23]), split_evol=bool(g[24]), static_basis=int(g[25]),
+                   static_bins=bool(g[26]), odd_x0=float(g[27]), odd_h=float(g[28]), odd_ncoef=int(g[29]))
+        return out
+
+    def bins_coefficients(self, B):
+        """The spline coefficients of the last evaluation [4, n_columns, B, ncp] (vmx_debug_read 2)."""
+        g = self.bins_grid(0)
+        return self.debug_read(2, 0, 4 * B * g['n_columns'] * g['ncp']).reshape(4, g['n_columns'], B, g['ncp']).copy()
+
+    def bins_xi(self, pid, B):
+        """xi of a pipeline in the last evaluation [B, n_pad] (vmx_debug_read 1)."""
+        g = self.bins_grid(pid)
+        return self.debug_read(1, pid, B * g['n_pad']).reshape(B, g['n_pad']).copy()
+
+    def quad_vector(self, name, B):
+        """(x' - x0' [B, nq_pad], x0' [nq_pad]) of an item after a chi2-only evaluation (vmx_debug_read 10, 11)."""
+        qi = self.item_names.index(name)
+        x0 = self.debug_read(11, qi, self.prob.items[name].model_grid.size + 128).copy()      # (nq <= n_model + 64, padded to 32)
+        return self.debug_read(10, qi, B * x0.size).reshape(B, x0.size).copy(), x0
+
+    def lean_groups(self, static=False):
+        """The groups of lean (static: of static-coordinate) pipelines whose bins arrive pre-summed (vmx_debug_read 13 / 18): a
+        list of dict(n, n_pad, presum, members=[(pipeline, factor kind, factor index)])."""
+        what = 18 if static else 13
+        n_groups = int(self.debug_read(what, -1, 1)[0])
+        out = []
+        for g in range(n_groups):
+            d = self.debug_read(what, g, 64)
+            members = [tuple(int(v) for v in d[5 + 3 * m:8 + 3 * m]) for m in range(int(d[1]))]
+            out.append(dict(n=int(d[2]), n_pad=int(d[3]), presum=bool(d[4]), members=members))
+        return out
+
+    def lean_group_sum(self, g, B, static=False):
+        """The pre-summed array [B, n_pad] of group g after an evaluation that summed on the way (vmx_debug_read 14 / 19)."""
+        n_pad = self.lean_groups(static)[g]['n_pad']
+        return self.debug_read(19 if static else 14, g, B * n_pad).reshape(B, n_pad).copy()
+
+    def poly_coefficients(self):
+        """The static coefficient basis [4, n_static, 3, ncp] (vmx_debug_read 15)."""
+        g = self.bins_grid(0)
+        n_static = sum(self.bins_grid(p)['static_basis'] >= 0 for p in range(self.n_pipelines))
+        return self.debug_read(15, 0, 4 * n_static * 3 * g['ncp']).reshape(4, n_static, 3, g['ncp']).copy()
+
+    def odd_coefficients(self, pid):
+        """The odd-multipole coefficient rows [4, odd_ncoef] of a pipeline (vmx_debug_read 16)."""
+        n = self.bins_grid(pid)['odd_ncoef']
+        return self.debug_read(16, pid, 4 * n).reshape(4, n).copy()
+
+    def metal_factors(self, B):
+        """The metal pairs' walker factors [B, 3, n_metals] of the last evaluation (vmx_debug_read 17)."""
+        n = len(self.metal_source)
+        return self.debug_read(17, 0, B * 3 * n).reshape(B, 3, n).copy()
+
+    def poly_bins(self, pid):
+        """The static basis on the bins of a pipeline [3, n_pad], None for a pipeline without (vmx_debug_read 12)."""
+        g = self.bins_grid(pid)
+        if not g['static_bins']:
+            return None
+        return self.debug_read(12, pid, 3 * g['n_pad']).reshape(3, g['n_pad']).copy()
+
+    def debug_math(self, which, x):
+        """vmx_log / vmx_exp / vmx_rsqrt of the kernels, elementwise on the device ('log' | 'exp' | 'rsqrt')."""
+        x = _f64(np.ravel(x))
+        out = np.empty_like(x)
+        self._check(self.lib.vmx_debug_math(self._h, self.MATH_FUNCTIONS[which], _dp(x), x.size, _dp(out)))
+        return out
 
     def last_form(self):
         """Form the last evaluation took: 'full' (distortion + C^-1 products), 'q' or 'factored'."""
