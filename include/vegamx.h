@@ -159,7 +159,8 @@ const char* vmx_last_error(void);
 /* sizeof() of the structs as compiled (0 tracer, 1 pipe, 2 metal, 3 item, 4 vmx_fit_spec, 5 vmx_fit_options, 6 vmx_fit_result,
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
- * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep): lets a foreign binding verify its struct layout at load time. */
+ * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep,
+ * 23 vmx_ensemble_moves; 22 is vacant and answers -1, as every index that names no struct): lets a foreign binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -494,6 +495,38 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
                           double* chain, double* chain_lnL,
                           const vmx_ensemble_options* opt,
                           vmx_ensemble_stats* stats, int64_t* per_ensemble);
+/* The same run with every walker's move drawn from a mixture of the stretch move, the differential-evolution move (ter Braak
+ * 2006, emcee's DEMove) and the snooker move (ter Braak & Vrugt 2008, emcee's DESnookerMove): what an emcee user writes as
+ * moves=[(DEMove(), 0.8), (DESnookerMove(), 0.2)].  The stretch move's acceptance falls with the number of sampled parameters and
+ * one point on a line through one partner rarely crosses between separated modes; both new moves are red-blue moves like it (a
+ * walker of the active half moves using walkers of the other half alone: two distinct ones for DE, three for the snooker), so
+ * the half-step, the box rule and the decision are unchanged.  Every expression, the second Philox block (counter (k, s, h, 1):
+ * move choice and jitter) and the rule of the distinct partners are pinned in vega_amd/csrc/vmx_ensemble.h.  The half-step kernel
+ * is k_ens_half_moves, beside k_ens_half: one work-group per ensemble, the same decide / record / propose order.
+ *   moves     weights[3]: (stretch, DE, snooker), each >= 0, of positive sum (they need not add up to 1; a pure move has the
+ *             others 0); gamma0: the DE scale (emcee's default 2.38 / sqrt(2 n), computed by the caller); sigma: the relative
+ *             width of the DE jitter, gamma = gamma0 (1 + sigma g) with g triangular on (-1, 1) (default 1e-5); gamma_s: the
+ *             snooker scale (default 1.7); flags, reserved: 0.  NULL runs exactly vmx_ensemble_run_many (k_ens_half).  Weights
+ *             (1, 0, 0) give the chain of vmx_ensemble_run_many bit for bit through the other kernel.
+ *   everything else as for vmx_ensemble_run_many; the single run is E = 1 with streams = &stream.
+ * The statistics are those of vmx_ensemble_run_many: a snooker proposal that is none (the walker on its partner, a factor that is
+ * not finite) counts with the rejections outside the box.
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever vmx_ensemble_run_many refuses; a negative or
+ * non-finite weight or a zero sum of weights; a DE weight with W / 2 < 2; a snooker weight with W / 2 < 3; gamma0 or gamma_s
+ * non-positive or non-finite; sigma negative or non-finite; flags or reserved not 0. */
+typedef struct {
+    double weights[3];
+    double gamma0, sigma, gamma_s;
+    uint32_t flags, reserved;
+} vmx_ensemble_moves;
+int vmx_ensemble_run_many_moves(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W,
+                                const uint64_t* streams, const int32_t* mock_row,
+                                double* x, double* lnL, int64_t* accepted,
+                                int64_t step0, int32_t n_steps, int32_t thin,
+                                double* chain, double* chain_lnL,
+                                const vmx_ensemble_options* opt,
+                                vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                                const vmx_ensemble_moves* moves);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

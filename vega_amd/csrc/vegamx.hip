@@ -311,6 +311,94 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_de
     }
 }
 
+// The moves of vmx_ensemble_run_many_moves as the kernel reads them: the thresholds of the mixture and the moves' scales
+struct EnsMovesDev { double t0, t1, gamma0, sigma, gamma_s; };
+
+// k_ens_half with the move of every walker drawn from a mixture of the stretch, differential-evolution and snooker moves
+// (vmx_ensemble.h, "the differential-evolution and snooker moves"): the same grid, the same decide / record / propose order and
+// the same strided loops, so that the chain does not depend on the block size.  The decision does not know the move: the
+// proposal left its factor and whether it is inside.  The partners' rows - up to three distinct walkers - are read from the half
+// decided just before; the snooker move passes three times over the n columns of its four rows.
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMovesDev M, int64_t s_dec, int h_dec, int64_t s_prop,
+                                                                int h_prop)
+{
+    const int W = D.W, H = W / 2, n = D.n;
+    const size_t e = blockIdx.x;
+    const uint64_t stream = D.streams[e];
+    double* const x = D.x + e * W * n;
+    double* const lnl = D.lnl + e * W;
+    int64_t* const acc = D.acc + e * W;
+    int64_t* const n_box = D.n_box + e * W;
+    int64_t* const n_fail = D.n_fail + e * W;
+    double* const prop = D.prop + e * H * n;
+    double* const factor = D.factor + e * H;
+    int32_t* const inside_of = D.inside + e * H;
+    const double* const chi2 = D.box.chi2 + e * H;
+    const int32_t* const status = D.box.status + e * H;
+    double* const theta = D.box.theta + e * H * D.P;
+    if (s_dec >= 0) {
+        for (int k = threadIdx.x; k < H; k += blockDim.x) {
+            const int w = h_dec * H + k;
+            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, stream);
+            const double c2 = chi2[k];
+            const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
+            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
+            if (vmx_ens::accept(inside, ok, factor[k], lnl_new, lnl[w], b.w[2])) {
+                for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
+                lnl[w] = lnl_new;
+                acc[w] += 1;
+            } else if (!inside) n_box[w] += 1;
+            else if (!ok) n_fail[w] += 1;
+        }
+        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
+            __syncthreads();
+            const size_t r = e * D.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
+            if (D.chain)
+                for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
+            if (D.chain_lnl)
+                for (int q = threadIdx.x; q < W; q += blockDim.x) D.chain_lnl[r * W + q] = lnl[q];
+        }
+    }
+    if (s_prop < 0) return;
+    __syncthreads();            // (the partners of the next half are the walkers just decided)
+    const double* const other = x + (size_t)(1 - h_prop) * H * n;
+    for (int k = threadIdx.x; k < H; k += blockDim.x) {
+        const int w = h_prop * H + k;
+        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
+        const vmx_ens::Block m = vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream);
+        const int move = vmx_ens::move_choice(m.w[0], M.t0, M.t1);
+        const int64_t j1 = vmx_ens::partner(b.w[0], H);
+        const double* c1 = other + (size_t)j1 * n;
+        const double* s = x + (size_t)w * n;
+        double* y = prop + (size_t)k * n;
+        double f = 0.0;
+        bool in = true;
+        if (move == vmx_ens::MOVE_STRETCH) {
+            const double z = vmx_ens::stretch_z(D.a, b.w[1]);
+            for (int d = 0; d < n; ++d) y[d] = vmx_ens::propose(c1[d], s[d], z);
+            f = vmx_ens::log_factor(n, z);
+        } else {
+            // (the entry refuses a DE weight with H < 2 and a snooker weight with H < 3: the indices below are in range)
+            const int64_t j2 = vmx_ens::partner2(b.w[1], H, j1);
+            const double* c2 = other + (size_t)j2 * n;
+            if (move == vmx_ens::MOVE_DE) {
+                const double gamma = vmx_ens::de_gamma(M.gamma0, M.sigma, m.w[1], m.w[2]);
+                for (int d = 0; d < n; ++d) y[d] = vmx_ens::de_propose(s[d], c1[d], c2[d], gamma);
+            } else {
+                const int64_t j3 = vmx_ens::partner3(b.w[3], H, j1, j2);
+                in = vmx_ens::snooker_propose(n, s, c1, c2, other + (size_t)j3 * n, M.gamma_s, y, f);
+            }
+        }
+        for (int d = 0; d < n; ++d) in = in && y[d] >= D.box.lo[d] && y[d] <= D.box.hi[d];
+        factor[k] = f;
+        inside_of[k] = in ? 1 : 0;
+        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
+        double* row = theta + (size_t)k * D.P;
+        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
+        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
+    }
+}
+
 // Nested sampling (vmx_nested_run): live points, the threads' state machines, the rows of a round and the dead record
 struct NsWorkspace {
     BoxWorkspace box;
@@ -1920,6 +2008,7 @@ int vmx_struct_size(int32_t which)
         case 19: return (int)sizeof(vmx_nested_phantoms);
         case 20: return (int)sizeof(vmx_nested_set_phantoms);
         case 21: return (int)sizeof(vmx_smc_keep);
+        case 23: return (int)sizeof(vmx_ensemble_moves);           // (22 stays vacant: see vegamx.h)
         default: return -1;
     }
 }
@@ -4852,7 +4941,7 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
-                        vmx_ensemble_stats* stats, int64_t* per_ensemble);
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves);
 
 // One ensemble is the set of one, on the stream of its spec
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
@@ -4861,7 +4950,7 @@ int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, do
 {
     REQUIRE(spec, "vmx_ensemble_run");
     return ensemble_run("vmx_ensemble_run", e, spec, 1, W, &spec->stream, nullptr, x, lnL, accepted, step0, n_steps, thin, chain,
-                        chain_lnL, opt, stats, nullptr);
+                        chain_lnL, opt, stats, nullptr, nullptr);
 }
 
 int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
@@ -4870,7 +4959,20 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
                           vmx_ensemble_stats* stats, int64_t* per_ensemble)
 {
     return ensemble_run("vmx_ensemble_run_many", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, chain,
-                        chain_lnL, opt, stats, per_ensemble);
+                        chain_lnL, opt, stats, per_ensemble, nullptr);
+}
+
+// The same run with the walkers' moves drawn from a mixture (k_ens_half_moves); without moves it is vmx_ensemble_run_many
+int vmx_ensemble_run_many_moves(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                                const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                                int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
+                                vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves)
+{
+    if (!moves)
+        return ensemble_run("vmx_ensemble_run_many", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, chain,
+                            chain_lnL, opt, stats, per_ensemble, nullptr);
+    return ensemble_run("vmx_ensemble_run_many_moves", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin,
+                        chain, chain_lnL, opt, stats, per_ensemble, moves);
 }
 
 // E independent ensembles advanced together (k_ens_half): the E H proposal rows of a half-step as one stream of chunks for the
@@ -4878,7 +4980,7 @@ int vmx_ensemble_run_many(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t 
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
-                        vmx_ensemble_stats* stats, int64_t* per_ensemble)
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves)
 {
     const std::string name(who);
     REQUIRE(e && e->finalized && spec && x && lnL && accepted, name);
@@ -4892,6 +4994,21 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), name + ": the stretch scale a must exceed 1");
     REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, name + ": thin >= 1, n_steps >= 0, step0 >= 0");
     const int H = W / 2;
+    EnsMovesDev M{};
+    if (moves) {
+        const double* p = moves->weights;
+        REQUIRE(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && p[0] >= 0.0 && p[1] >= 0.0 && p[2] >= 0.0,
+                name + ": the moves' weights must be finite and not negative");
+        vmx_ens::move_thresholds(p, M.t0, M.t1);
+        REQUIRE((p[0] + p[1]) + p[2] > 0.0 && std::isfinite(M.t0) && std::isfinite(M.t1), name + ": the moves' weights must have a positive, finite sum");
+        REQUIRE(!(p[1] > 0.0) || H >= 2, name + ": the DE move needs two partners in the other half, W >= 4");
+        REQUIRE(!(p[2] > 0.0) || H >= 3, name + ": the snooker move needs three partners in the other half, W >= 6");
+        REQUIRE(std::isfinite(moves->gamma0) && moves->gamma0 > 0.0, name + ": gamma0 must be positive and finite");
+        REQUIRE(std::isfinite(moves->gamma_s) && moves->gamma_s > 0.0, name + ": gamma_s must be positive and finite");
+        REQUIRE(std::isfinite(moves->sigma) && moves->sigma >= 0.0, name + ": sigma must be finite and not negative");
+        REQUIRE(moves->flags == 0 && moves->reserved == 0, name + ": flags and reserved must be 0");
+        M.gamma0 = moves->gamma0; M.sigma = moves->sigma; M.gamma_s = moves->gamma_s;
+    }
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
     // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
     REQUIRE((int64_t)E * W <= INT32_MAX, name + ": E W exceeds the engine's row count");
@@ -4958,7 +5075,10 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int64_t halves = 2 * (int64_t)n_steps;
     // (every loop of the kernel strides by its block: the chain does not depend on this size)
     const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
-    if (halves > 0) hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, (int64_t)-1, 0, step0, 0);
+    if (halves > 0) {
+        if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, (int64_t)-1, 0, step0, 0);
+        else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, (int64_t)-1, 0, step0, 0);
+    }
     HIP_OK(hipGetLastError());
     for (int64_t q = 0; q < halves; ++q) {
         const int64_t s = step0 + q / 2;
@@ -4967,8 +5087,9 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         if (calls < 0) return -2;
         R.engine_calls += calls;
         const int64_t nq = q + 1;
-        hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s, h,
-                           nq < halves ? step0 + nq / 2 : (int64_t)-1, (int)(nq % 2));
+        const int64_t s_next = nq < halves ? step0 + nq / 2 : (int64_t)-1;
+        if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s, h, s_next, (int)(nq % 2));
+        else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s, h, s_next, (int)(nq % 2));
         HIP_OK(hipGetLastError());
     }
     std::vector<int64_t> acc0(accepted, accepted + EW), box(EW), failed(EW);

@@ -122,4 +122,139 @@ VMX_HD inline bool accept(bool inside, bool ok, double factor, double lnl_new, d
     return lhs > log(u01(x2));
 }
 
+// ---- the differential-evolution and snooker moves, and mixtures of the three (vmx_ensemble_run_many_moves: k_ens_half_moves)
+//
+// Both are red-blue moves like the stretch move: a walker of the active half is moved using only walkers of the other half, so
+// the half-step and the decision above stay what they are.  Only + - x / sqrt log, each rounded on its own; no Box-Muller and
+// no trigonometric function (they would end the bit-for-bit agreement of the two drivers).
+//
+//   random numbers   walker-in-half k, step s, half h has two blocks: A, counter (k, s, h, 0), the block above - w0 the first
+//                    index, w1 the second index (in the stretch move its uniform, as ever), w2 the acceptance word, w3 the third
+//                    index - and B, counter (k, s, h, 1): w0 the move choice, w1 and w2 the jitter, w3 unused.
+//   partners         distinct walkers of the other half of H: j1 = partner(A.w0, H); j2 = partner(A.w1, H - 1), plus 1 if
+//                    j2 >= j1 (H >= 2); j3 = partner(A.w3, H - 2), raised by 1 if it is at or above the smaller of j1, j2 and
+//                    the raised value by 1 again if it is at or above the larger (H >= 3).
+//   mixture          weights (p_stretch, p_de, p_snooker) >= 0 of positive sum S reach the device as the thresholds t0 = p0 / S,
+//                    t1 = (p0 + p1) / S: stretch if u(B.w0) < t0, DE if u(B.w0) < t1, else snooker.  A pure move has its weight
+//                    equal to S (x / x = 1 exactly, and u < 1) and draws from the same words.
+//   DE               ter Braak 2006, emcee's DEMove: g = (u(B.w1) + u(B.w2)) - 1; gamma = gamma0 (1 + sigma g); per column
+//                    y = s + gamma (c[j1] - c[j2]); factor = 0.  The jitter g is triangular on (-1, 1) where emcee's is normal:
+//                    it is symmetric about 0 and independent of the state, so the proposal density stays symmetric and the
+//                    move reversible.  gamma0 comes from the host as a double (default 2.38 / sqrt(2 n)); sigma defaults to 1e-5.
+//   snooker          ter Braak & Vrugt 2008, emcee's DESnookerMove: z = c[j1], z1 = c[j2], z2 = c[j3]; d = s - z;
+//                    norm = sqrt(sum d^2); u = d / norm; p = sum u z1 - sum u z2; y = s + u (gamma_s p);
+//                    factor = (n - 1) (log(sqrt(sum (y - z)^2)) - log(norm)); every sum in column order.  norm == 0 (not
+//                    greater than 0) or a factor that is not finite marks the proposal as not inside: it is rejected and counted
+//                    with the box rejections; with norm == 0 the proposal is the walker's own position and the factor 0.
+//                    gamma_s defaults to 1.7.
+//   box, decision    unchanged: a proposal outside the box evaluates the walker's own position; accept(...) above.
+enum Move { MOVE_STRETCH = 0, MOVE_DE = 1, MOVE_SNOOKER = 2 };
+
+// block B of walker-in-half i at global step s, half h
+VMX_HD inline Block move_block(int64_t i, int64_t s, int h, uint64_t seed, uint64_t stream)
+{
+    return philox4x64_10((uint64_t)i, (uint64_t)s, (uint64_t)h, 1, seed, stream);
+}
+
+// the thresholds of the weights (p_stretch, p_de, p_snooker)
+VMX_HD inline void move_thresholds(const double* p, double& t0, double& t1)
+{
+    VMX_NO_CONTRACT
+    const double p01 = p[0] + p[1];
+    const double sum = p01 + p[2];
+    t0 = p[0] / sum;
+    t1 = p01 / sum;
+}
+
+VMX_HD inline int move_choice(uint64_t w0, double t0, double t1)
+{
+    const double u = u01(w0);
+    return u < t0 ? MOVE_STRETCH : (u < t1 ? MOVE_DE : MOVE_SNOOKER);
+}
+
+// the second partner, distinct from j1 (half >= 2)
+VMX_HD inline int64_t partner2(uint64_t x1, int64_t half, int64_t j1)
+{
+    const int64_t j = partner(x1, half - 1);
+    return j >= j1 ? j + 1 : j;
+}
+
+// the third partner, distinct from j1 and j2 (half >= 3)
+VMX_HD inline int64_t partner3(uint64_t x3, int64_t half, int64_t j1, int64_t j2)
+{
+    const int64_t small = j1 < j2 ? j1 : j2, large = j1 < j2 ? j2 : j1;
+    int64_t j = partner(x3, half - 2);
+    if (j >= small) j += 1;
+    if (j >= large) j += 1;
+    return j;
+}
+
+VMX_HD inline double de_gamma(double gamma0, double sigma, uint64_t w1, uint64_t w2)
+{
+    VMX_NO_CONTRACT
+    double g = u01(w1) + u01(w2);
+    g = g - 1.0;
+    double t = sigma * g;
+    t = 1.0 + t;
+    return gamma0 * t;
+}
+
+// one sampled column of the DE proposal: s the walker's own position, c1 and c2 the two partners'
+VMX_HD inline double de_propose(double s, double c1, double c2, double gamma)
+{
+    VMX_NO_CONTRACT
+    const double d = c1 - c2;
+    const double t = gamma * d;
+    return s + t;
+}
+
+VMX_HD inline bool is_finite(double v) { return v - v == 0.0; }
+
+// the snooker proposal y[n] of the walker at s[n] along its line through z[n], with the projections of z1[n] and z2[n] on that
+// line; false: not a proposal (norm == 0, or a factor that is not finite).  y must not overlap the inputs.
+VMX_HD inline bool snooker_propose(int n, const double* s, const double* z, const double* z1, const double* z2, double gamma_s,
+                                   double* y, double& factor)
+{
+    VMX_NO_CONTRACT
+    double ss = 0.0;
+    for (int d = 0; d < n; ++d) {
+        const double e = s[d] - z[d];
+        const double q = e * e;
+        ss = ss + q;
+    }
+    const double norm = sqrt(ss);
+    if (!(norm > 0.0)) {
+        for (int d = 0; d < n; ++d) y[d] = s[d];
+        factor = 0.0;
+        return false;
+    }
+    double p1 = 0.0, p2 = 0.0;
+    for (int d = 0; d < n; ++d) {
+        const double e = s[d] - z[d];
+        const double u = e / norm;
+        const double q1 = u * z1[d];
+        p1 = p1 + q1;
+        const double q2 = u * z2[d];
+        p2 = p2 + q2;
+    }
+    const double p = p1 - p2;
+    const double gp = gamma_s * p;
+    double tt = 0.0;
+    for (int d = 0; d < n; ++d) {
+        const double e = s[d] - z[d];
+        const double u = e / norm;
+        const double m = u * gp;
+        const double v = s[d] + m;
+        y[d] = v;
+        const double r = v - z[d];
+        const double q = r * r;
+        tt = tt + q;
+    }
+    const double l_new = log(sqrt(tt));
+    const double l_old = log(norm);
+    const double dl = l_new - l_old;
+    factor = (double)(n - 1) * dl;
+    return is_finite(factor);
+}
+
 }  // namespace vmx_ens

@@ -135,6 +135,11 @@ class EnsembleStats(C.Structure):
                 ('lanes', C.c_int32)]
 
 
+class EnsembleMoves(C.Structure):
+    _fields_ = [('weights', C.c_double * 3), ('gamma0', C.c_double), ('sigma', C.c_double), ('gamma_s', C.c_double),
+                ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
 VMX_NS_MAXN = 32
 VMX_NS_MAX_LIVE = 4096
 NESTED_STOP = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -325,6 +330,7 @@ def load_library():
     lib.vmx_ensemble_run_many.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, C.c_int32, C.POINTER(C.c_uint64), iptr, dptr,
                                           dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, dptr, dptr,
                                           C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64)]
+    lib.vmx_ensemble_run_many_moves.argtypes = lib.vmx_ensemble_run_many.argtypes + [C.POINTER(EnsembleMoves)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -379,7 +385,9 @@ def load_library():
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
                                     SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms,
-                                    NestedSetPhantoms, SmcKeep)):
+                                    NestedSetPhantoms, SmcKeep, None, EnsembleMoves)):
+        if struct is None:          # (an index that names no struct)
+            continue
         if lib.vmx_struct_size(which) != C.sizeof(struct):
             raise EngineError(f'ABI mismatch: {struct.__name__} is {C.sizeof(struct)} bytes here, '
                               f'{lib.vmx_struct_size(which)} in libvegamx.so')
@@ -411,7 +419,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1178,11 +1186,22 @@ class Engine:
         return spec, args, chain, chain_lnl, EnsembleStats(), (cols, lo, hi, theta_fixed, opt)
 
     def ensemble_run(self, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin=1, a=2.0, log_norm=0.0, seed=0,
-                     stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
+                     stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):
         """``n_steps`` steps of the ensemble sampler on the device (include/vegamx.h: vmx_ensemble_run): ``cols`` the sampled
         parameter columns with their box [lo, hi], ``theta_fixed`` the row of the others, ``x`` [W, n] / ``lnl`` [W] / ``accepted``
         int64 [W] the walkers' state (updated in place), ``step0`` the global index of the first step.  Returns (chain [rows, W, n],
-        chain_lnl [rows, W], statistics), rows = (step0 + n_steps) // thin - step0 // thin."""
+        chain_lnl [rows, W], statistics), rows = (step0 + n_steps) // thin - step0 // thin.  ``moves`` (None: the stretch move
+        through vmx_ensemble_run): the mixture of :meth:`ensemble_run_many`, run as the set of one."""
+        if moves is not None:
+            _in_place(np.float64, x=x, lnl=lnl)
+            _in_place(np.int64, accepted=accepted)
+            if x.ndim != 2:
+                raise ValueError('x [W, n], lnl [W], accepted [W]')
+            chain, chain_lnl, st = self.ensemble_run_many(
+                cols, lo, hi, theta_fixed, x[None], lnl[None], accepted[None], [stream], step0, n_steps, thin=thin, a=a,
+                log_norm=log_norm, seed=seed, const_hint=const_hint, chunk=chunk, lanes=lanes, keep_chain=keep_chain, moves=moves)
+            st.pop('per_ensemble')
+            return (chain[0], chain_lnl[0], st) if keep_chain else (None, None, st)
         spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
             2, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=a, log_norm=log_norm, seed=seed,
             stream=stream, const_hint=const_hint, chunk=chunk, lanes=lanes)
@@ -1190,12 +1209,15 @@ class Engine:
         return chain, chain_lnl, _stats_dict(stats)
 
     def ensemble_run_many(self, cols, lo, hi, theta_fixed, x, lnl, accepted, streams, step0, n_steps, mock_rows=None, thin=1, a=2.0,
-                          log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True):
+                          log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):
         """``n_steps`` steps of E independent ensembles in one device run (include/vegamx.h: vmx_ensemble_run_many): ``x`` [E, W, n]
         / ``lnl`` [E, W] / ``accepted`` int64 [E, W] the walkers' state (updated in place), ``streams`` [E] the Philox stream of every
         ensemble, ``mock_rows`` [E] the pool row every ensemble is compared with (None: the installed data); the rest as for
         :meth:`ensemble_run`.  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], statistics); the statistics carry
-        ``per_ensemble`` int64 [E, 3]: accepted, rejected outside the box, rejected for a failed model."""
+        ``per_ensemble`` int64 [E, 3]: accepted, rejected outside the box, rejected for a failed model.  ``moves`` (None:
+        vmx_ensemble_run_many, the stretch move): a mapping with ``weights`` (stretch, DE, snooker), ``gamma0``, ``sigma``,
+        ``gamma_s`` and optionally ``flags`` - the mixture of vmx_ensemble_run_many_moves
+        (:func:`vega_amd.ensemble.resolve_moves` makes one)."""
         spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
             3, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=a, log_norm=log_norm, seed=seed,
             stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
@@ -1207,9 +1229,14 @@ class Engine:
         if (streams is not None and streams.shape != (E,)) or (mock_rows is not None and mock_rows.shape != (E,)):
             raise ValueError('streams [E], mock_rows [E]')
         per = np.zeros((E, 3), dtype=np.int64)
-        self._check(self.lib.vmx_ensemble_run_many(
-            self._h, C.byref(spec), E, W, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), *args, C.byref(stats), per.ctypes.data_as(C.POINTER(C.c_int64))))
+        head = (self._h, C.byref(spec), E, W, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+                None if mock_rows is None else _ip(mock_rows), *args, C.byref(stats), per.ctypes.data_as(C.POINTER(C.c_int64)))
+        if moves is None:
+            self._check(self.lib.vmx_ensemble_run_many(*head))
+        else:
+            mv = EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']), float(moves['sigma']),
+                               float(moves['gamma_s']), int(moves.get('flags', 0)), 0)
+            self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,

@@ -1,5 +1,6 @@
 """Posterior sampling: the affine-invariant ensemble sampler (Goodman & Weare 2010, emcee's stretch move with
-randomize_split=False), run where the walkers are.
+randomize_split=False; on request the differential-evolution and snooker moves and mixtures of the three), run where the walkers
+are.
 
 The reference samples through PolyChord / pocoMC (bin/run_vega_mpi.py: ``[control] run_sampler = True``), which call
 ``log_lik`` one point at a time.  Here W walkers advance half an ensemble at a time: the ``device`` driver runs the whole walker
@@ -11,6 +12,7 @@ same chain bit for bit.  The random stream is NumPy's Philox4x64-10 (one block p
 import configparser
 import math
 import os
+from collections.abc import Mapping
 from pathlib import Path
 
 import numpy as np
@@ -102,28 +104,195 @@ def accept(inside, ok, factor, lnl_new, lnl_old, x2):
         return np.asarray(inside, dtype=bool) & np.asarray(ok, dtype=bool) & (lhs > _log(u01(x2)))
 
 
-def half_step_proposals(x, h, step, a, seed, stream, lo, hi):
-    """Proposals of half ``h`` at ``step`` for the walkers ``x`` [W, n]: (y [W/2, n], inside [W/2], factor [W/2], blocks)."""
+# ---- the differential-evolution and snooker moves, and mixtures (vmx_ensemble.h, the second part)
+MOVE_NAMES = ('stretch', 'de', 'snooker')
+MOVE_STRETCH, MOVE_DE, MOVE_SNOOKER = 0, 1, 2
+
+
+def move_blocks(half, step, h, seed, stream=0):
+    """Block B of walkers-in-half 0 .. half-1 at global step ``step``, half ``h`` (counter (k, step, h, 1)): [half, 4] uint64."""
+    ctr = np.zeros((half, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(half, dtype=np.uint64)
+    ctr[:, 1] = np.uint64(step)
+    ctr[:, 2] = np.uint64(h)
+    ctr[:, 3] = np.uint64(1)
+    return philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def move_thresholds(p):
+    """(t0, t1) of the weights (p_stretch, p_de, p_snooker)."""
+    p01 = float(p[0]) + float(p[1])
+    total = p01 + float(p[2])
+    return float(p[0]) / total, p01 / total
+
+
+def move_choice(w0, t0, t1):
+    u = u01(w0)
+    return np.where(u < t0, MOVE_STRETCH, np.where(u < t1, MOVE_DE, MOVE_SNOOKER))
+
+
+def partner2(x1, half, j1):
+    """The second partner, distinct from ``j1`` (half >= 2)."""
+    j = partner(x1, half - 1).astype(np.int64)
+    return j + (j >= j1)
+
+
+def partner3(x3, half, j1, j2):
+    """The third partner, distinct from ``j1`` and ``j2`` (half >= 3)."""
+    j = partner(x3, half - 2).astype(np.int64)
+    j = j + (j >= np.minimum(j1, j2))
+    return j + (j >= np.maximum(j1, j2))
+
+
+def de_gamma(gamma0, sigma, w1, w2):
+    g = u01(w1) + u01(w2)
+    g = g - 1.0
+    t = sigma * g
+    t = 1.0 + t
+    return gamma0 * t
+
+
+def de_propose(s, c1, c2, gamma):
+    """Rows of the DE proposal: s the walkers' own positions [k, n], c1 and c2 the two partners' [k, n], gamma [k]."""
+    d = c1 - c2
+    t = gamma[:, None] * d
+    return s + t
+
+
+def _column_sum(terms):
+    total = np.zeros(terms.shape[0])
+    for d in range(terms.shape[1]):         # (in column order, as the header adds them)
+        total = total + terms[:, d]
+    return total
+
+
+def snooker_propose(s, z, z1, z2, gamma_s):
+    """Rows of the snooker proposal: s the walkers' own positions [k, n], z, z1, z2 the three partners' [k, n].  Returns
+    (y [k, n], factor [k], ok [k]); not ok: no proposal (norm == 0 - then y is s and the factor 0 - or a factor not finite)."""
+    n = s.shape[1]
+    e = s - z
+    norm = np.sqrt(_column_sum(e * e))
+    some = norm > 0.0
+    with np.errstate(all='ignore'):
+        u = e / norm[:, None]
+        p = _column_sum(u * z1) - _column_sum(u * z2)
+        gp = gamma_s * p
+        y = s + u * gp[:, None]
+        r = y - z
+        dl = _log(np.sqrt(_column_sum(r * r))) - _log(norm)
+        factor = float(n - 1) * dl
+    y = np.where(some[:, None], y, s)
+    factor = np.where(some, factor, 0.0)
+    return y, factor, some & np.isfinite(factor)
+
+
+def resolve_moves(moves, n, walkers, gamma0=None, sigma=None, gamma_s=None):
+    """The mixture a sampler of ``walkers`` walkers over ``n`` parameters runs with: None for ``moves`` None (the stretch move as
+    ever), else dict(weights (stretch, DE, snooker), gamma0, sigma, gamma_s) - what vmx_ensemble_run_many_moves takes.
+    ``moves``: ``'stretch'``, ``'de'`` or ``'snooker'``, a list of (name, weight), or such a dict.  Defaults: gamma0 =
+    2.38 / sqrt(2 n), sigma = 1e-5, gamma_s = 1.7.  Refused as the library refuses them: an unknown name, a negative or
+    non-finite weight, a zero sum, DE with fewer than 4 walkers, the snooker with fewer than 6, a scale that is not positive."""
+    if moves is None:
+        if gamma0 is not None or sigma is not None or gamma_s is not None:
+            raise ValueError('gamma0, sigma and gamma_s belong to moves: name the moves')
+        return None
+    if isinstance(moves, dict):
+        weights = [float(w) for w in moves['weights']]
+        gamma0 = moves.get('gamma0') if gamma0 is None else gamma0
+        sigma = moves.get('sigma') if sigma is None else sigma
+        gamma_s = moves.get('gamma_s') if gamma_s is None else gamma_s
+        if len(weights) != 3:
+            raise ValueError('moves: three weights (stretch, de, snooker)')
+    else:
+        pairs = [(moves, 1.0)] if isinstance(moves, str) else list(moves)
+        weights = [0.0, 0.0, 0.0]
+        for pair in pairs:
+            name, w = (pair, 1.0) if isinstance(pair, str) else pair
+            if name not in MOVE_NAMES:
+                raise ValueError(f"moves: unknown move {name!r}; one of 'stretch', 'de', 'snooker'")
+            weights[MOVE_NAMES.index(name)] += float(w)
+            if not float(w) >= 0.0:
+                raise ValueError('moves: a weight must be finite and not negative')
+    if not all(math.isfinite(w) and w >= 0.0 for w in weights):
+        raise ValueError('moves: a weight must be finite and not negative')
+    if not 0.0 < (weights[0] + weights[1]) + weights[2] < math.inf:
+        raise ValueError('moves: the weights must have a positive sum')
+    if weights[1] > 0.0 and walkers < 4:
+        raise ValueError("moves: 'de' needs two partners in the other half, at least 4 walkers")
+    if weights[2] > 0.0 and walkers < 6:
+        raise ValueError("moves: 'snooker' needs three partners in the other half, at least 6 walkers")
+    out = dict(weights=tuple(weights), gamma0=2.38 / math.sqrt(2.0 * n) if gamma0 is None else float(gamma0),
+               sigma=1e-5 if sigma is None else float(sigma), gamma_s=1.7 if gamma_s is None else float(gamma_s))
+    if not (math.isfinite(out['gamma0']) and out['gamma0'] > 0.0 and math.isfinite(out['gamma_s']) and out['gamma_s'] > 0.0):
+        raise ValueError('moves: gamma0 and gamma_s must be positive and finite')
+    if not (math.isfinite(out['sigma']) and out['sigma'] >= 0.0):
+        raise ValueError('moves: sigma must be finite and not negative')
+    return out
+
+
+def half_step_moves(H, h, step, seed, stream, moves):
+    """The move of every walker of half ``h`` at ``step``: [H] of MOVE_STRETCH / MOVE_DE / MOVE_SNOOKER."""
+    return move_choice(move_blocks(H, step, h, seed, stream)[:, 0], *move_thresholds(moves['weights']))
+
+
+def steps_moves(H, step0, n_steps, seed, stream, moves):
+    """The move of every walker at the steps ``step0`` .. ``step0 + n_steps - 1``: [n_steps, 2 H] (walker h H + k: half h), the
+    :func:`half_step_moves` of every half-step.  The walkers of a half-step are consecutive counters, so NumPy's own Philox
+    draws their blocks B in one call (the generator :func:`philox4x64_10` restates; it increments before it encrypts)."""
+    key = np.array([int(seed), int(stream)], dtype=np.uint64)
+    words = np.empty((n_steps, 2, H), dtype=np.uint64)
+    for i in range(n_steps):
+        for h in (0, 1):
+            counter = ((step0 + i) << 64) | (h << 128) | (1 << 192)
+            words[i, h] = np.random.Philox(key=key, counter=counter - 1).random_raw(4 * H)[0::4]
+    return move_choice(words, *move_thresholds(moves['weights'])).reshape(n_steps, 2 * H)
+
+
+def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None):
+    """Proposals of half ``h`` at ``step`` for the walkers ``x`` [W, n]: (y [W/2, n], inside [W/2], factor [W/2], blocks).
+    ``moves`` (:func:`resolve_moves`; None: the stretch move): every walker's move is drawn from the mixture."""
     W, n = x.shape
     H = W // 2
     b = step_blocks(H, step, h, seed, stream)
     j = partner(b[:, 0], H).astype(np.int64)
-    c = x[(1 - h) * H + j]
+    other = x[(1 - h) * H:(2 - h) * H]
+    c = other[j]
     s = x[h * H:(h + 1) * H]
-    z = stretch_z(a, b[:, 1])
-    y = propose(c, s, z)
+    if moves is None:
+        z = stretch_z(a, b[:, 1])
+        y = propose(c, s, z)
+        factor = log_factor(n, z)
+        some = True
+    else:
+        m = move_blocks(H, step, h, seed, stream)
+        move = move_choice(m[:, 0], *move_thresholds(moves['weights']))
+        y, factor, some = np.empty((H, n)), np.zeros(H), np.ones(H, dtype=bool)
+        k = np.flatnonzero(move == MOVE_STRETCH)
+        if k.size:
+            z = stretch_z(a, b[k, 1])
+            y[k], factor[k] = propose(c[k], s[k], z), log_factor(n, z)
+        k = np.flatnonzero(move == MOVE_DE)
+        if k.size:
+            j2 = partner2(b[k, 1], H, j[k])
+            y[k] = de_propose(s[k], c[k], other[j2], de_gamma(moves['gamma0'], moves['sigma'], m[k, 1], m[k, 2]))
+        k = np.flatnonzero(move == MOVE_SNOOKER)
+        if k.size:
+            j2 = partner2(b[k, 1], H, j[k])
+            j3 = partner3(b[k, 3], H, j[k], j2)
+            y[k], factor[k], some[k] = snooker_propose(s[k], c[k], other[j2], other[j3], moves['gamma_s'])
     with np.errstate(invalid='ignore'):
-        inside = np.all((y >= lo) & (y <= hi), axis=1)
-    return y, inside, log_factor(n, z), b
+        inside = some & np.all((y >= lo) & (y <= hi), axis=1)
+    return y, inside, factor, b
 
 
-def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate):
+def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate, moves=None):
     """``n_steps`` steps of E independent ensembles advanced together, in NumPy: the state ``x`` [E, W, n], ``lnl`` [E, W],
     ``accepted`` [E, W] (updated in place), ensemble e on the Philox stream ``streams[e]``.  Every half-step is decided ensemble by
     ensemble; only the likelihood is joined: ``evaluate(rows, h)`` -> (chi2 [E W/2], status [E W/2]) for the E W/2 rows
     [E W/2, n] of the half, ensemble e's at [e W/2, (e + 1) W/2) - the rows the device driver hands the engine (a proposal outside
     the box is replaced by the walker's own position).  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats,
-    per_ensemble [E, 3]: accepted, rejected outside the box, rejected for a failed model)."""
+    per_ensemble [E, 3]: accepted, rejected outside the box, rejected for a failed model).  ``moves`` (:func:`resolve_moves`; None:
+    the stretch move): the mixture every walker's move is drawn from."""
     E, W, n = x.shape
     H = W // 2
     rows = (step0 + n_steps) // thin - step0 // thin
@@ -132,7 +301,7 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     for s in range(step0, step0 + n_steps):
         for h in (0, 1):
             mine = slice(h * H, (h + 1) * H)
-            props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi) for e in range(E)]
+            props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi, moves) for e in range(E)]
             chi2, status = evaluate(np.concatenate([np.where(inside[:, None], y, x[e, mine])
                                                     for e, (y, inside, _, _) in enumerate(props)]), h)
             for e, (y, inside, factor, b) in enumerate(props):
@@ -152,12 +321,12 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     return chain, chain_lnl, st, per
 
 
-def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate):
+def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate, moves=None):
     """``n_steps`` steps of one ensemble in NumPy - :func:`python_steps_many` with E = 1 - from the state ``x`` [W, n], ``lnl`` [W],
     ``accepted`` [W] (updated in place); ``evaluate(rows, h)`` -> (chi2 [W/2], status [W/2]) for the half's rows [W/2, n].
     Returns (chain [rows, W, n], chain_lnl [rows, W], stats)."""
     chain, chain_lnl, st, _ = python_steps_many(x[None], lnl[None], accepted[None], step0, n_steps, thin, a, seed, [stream], lo, hi,
-                                                log_norm, evaluate)
+                                                log_norm, evaluate, moves)
     return chain[0], chain_lnl[0], st
 
 
@@ -460,6 +629,43 @@ class EngineSampler:
 
 
 # ------------------------------------------------------------------ the sampler
+class MoveCounts(Mapping):
+    """``stats['moves']`` of a sampler that runs a mixture of moves: {move: {proposals, accepted}} over the steps run so far,
+    computed when it is read (:meth:`StretchSampler.move_counts`) and kept until the sampler advances; ``accepted`` is None
+    with thin > 1.  ``unseen``: the accepted proposals no move could be credited with (None with thin > 1)."""
+
+    def __init__(self, sampler):
+        self._sampler, self._step, self._counts, self._unseen = sampler, -1, None, None
+
+    def _read(self):
+        s = self._sampler
+        if self._step != s.step:
+            total = s.move_counts().reshape(-1, 3, 2).sum(axis=0)
+            known = s.thin == 1
+            self._counts = {name: dict(proposals=int(total[m, 0]), accepted=int(total[m, 1]) if known else None)
+                            for m, name in enumerate(MOVE_NAMES)}
+            self._unseen = int(np.sum(s.accepted)) - int(total[:, 1].sum()) if known else None
+            self._step = s.step
+        return self._counts
+
+    @property
+    def unseen(self):
+        self._read()
+        return self._unseen
+
+    def __getitem__(self, name):
+        return self._read()[name]
+
+    def __iter__(self):
+        return iter(MOVE_NAMES)
+
+    def __len__(self):
+        return len(MOVE_NAMES)
+
+    def __repr__(self):
+        return repr(self._read())
+
+
 class StretchSampler(EngineSampler):
     """What :class:`EnsembleSampler` and :class:`EnsembleSet` do alike: the settings of the stretch move, the statistics, the loop
     over segments and the python driver's engine.  ``_lead`` is the shape in front of the walkers: () or (E,).  A class supplies
@@ -467,7 +673,8 @@ class StretchSampler(EngineSampler):
     per-ensemble counters."""
     _lead = ()
 
-    def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint):
+    def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves=None,
+                       gamma0=None, sigma=None, gamma_s=None):
         self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         self.W = int(walkers)
         if self.W % 2 or self.W < 2 * self.n:
@@ -479,6 +686,9 @@ class StretchSampler(EngineSampler):
         if self.thin < 1:
             raise ValueError('thin >= 1')
         self.segment = max(1, int(segment))
+        # the mixture of moves (None: the stretch move alone, the run of ever) and what asked for it, for a set's members
+        self.moves = resolve_moves(moves, self.n, self.W, gamma0, sigma, gamma_s)
+        self._moves_kw = {} if moves is None else dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s)
 
     def reset(self):
         self.x = self.lnl = None
@@ -487,6 +697,34 @@ class StretchSampler(EngineSampler):
         self._chain, self._chain_lnl = [], []
         self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
                           seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
+        if self.moves is not None:
+            self._start = None          # (the walkers ahead of the first step: what the first recorded row is compared with)
+            self.stats['moves'] = MoveCounts(self)
+
+    def move_counts(self):
+        """Per move the proposals and the accepted ones of the steps run so far, int64 [(E,) 3, 2] in the order of
+        ``MOVE_NAMES``: counted on the host, and only when asked for (``stats['moves']`` reads it), from the words the drivers
+        drew the moves from (block B of every walker) and the recorded rows - a run does not pay for it.  With a row for every
+        step (thin = 1) a proposal counts as accepted when the walker's recorded position or lnL changed; an accepted proposal
+        that lands on the walker's own position bit for bit (DE between two partners at one point, a snooker projection of
+        exactly 0) is not seen: ``stats['moves'].unseen`` counts those.  With thin > 1 the accepted column is 0 and unknown."""
+        H = self.W // 2
+        lead = int(np.prod(self._lead, dtype=np.int64))
+        streams = self.streams if self._lead else [self.stream]
+        counts = np.zeros((lead, 3, 2), dtype=np.int64)
+        if self.step > 0:
+            axis = len(self._lead)
+            rows = np.concatenate(self._chain, axis=axis).reshape(lead, -1, self.W, self.n)
+            rows_lnl = np.concatenate(self._chain_lnl, axis=axis).reshape(lead, -1, self.W)
+            start, start_lnl = (a.reshape((lead, 1) + a.shape[axis:]) for a in self._start)
+            for e in range(lead):
+                move = steps_moves(H, 0, self.step, self.seed, int(streams[e]), self.moves)         # [steps, W]
+                counts[e, :, 0] = np.bincount(move.reshape(-1), minlength=3)
+                if self.thin == 1:
+                    moved = np.any(np.diff(np.concatenate([start[e], rows[e]]), axis=0) != 0.0, axis=2)
+                    moved |= np.diff(np.concatenate([start_lnl[e], rows_lnl[e]]), axis=0) != 0.0
+                    counts[e, :, 1] = np.bincount(move[moved], minlength=3)
+        return counts.reshape(self._lead + (3, 2))
 
     def run(self, n_steps, start='ball', init_scale=1.0):
         """Advance by ``n_steps`` steps.  The first call draws the start, as the class's ``_start_positions`` says: ``'ball'``,
@@ -496,6 +734,8 @@ class StretchSampler(EngineSampler):
         while done < n_steps:
             k = min(self.segment, n_steps - done)
             segment = self._segment_device if self.driver == 'device' else self._segment_python
+            if self.moves is not None and self._start is None:
+                self._start = (self.x.copy(), self.lnl.copy())
             chain, chain_lnl, st, *per = segment(theta, k)
             self._chain.append(chain)
             self._chain_lnl.append(chain_lnl)
@@ -528,6 +768,10 @@ class StretchSampler(EngineSampler):
         st['seconds'] = time.perf_counter() - t0
         return out
 
+    def _moves_arg(self):
+        # (without moves the engine's methods are called as ever: a stand-in engine need not know the argument)
+        return {} if self.moves is None else dict(moves=self.moves)
+
     @property
     def acceptance_fraction(self):
         return self.accepted / max(self.step, 1)
@@ -539,11 +783,20 @@ class EnsembleSampler(StretchSampler):
 
     ``driver``: ``'device'`` (vmx_ensemble_run) or ``'python'`` (the NumPy restatement over ``chi2_batch_device``); an engine
     group (one engine per transform setting, no single C handle) takes ``'python'``.  The choice is made when ``run`` knows the
-    engine - ``freeze_metals`` may replace it.  ``segment``: steps per call of the driver (the chain does not depend on it)."""
+    engine - ``freeze_metals`` may replace it.  ``segment``: steps per call of the driver (the chain does not depend on it).
+
+    ``moves`` (emcee's ``moves=``): None - the stretch move, the run of ever - or ``'stretch'``, ``'de'`` (emcee's DEMove),
+    ``'snooker'`` (DESnookerMove) or a list of (name, weight), e.g. ``[('de', 0.8), ('snooker', 0.2)]``: every walker's move is
+    drawn from the mixture at every step (vmx_ensemble_run_many_moves; the ``python`` driver runs the same rule).  ``gamma0``
+    (default 2.38 / sqrt(2 n)) and ``sigma`` (1e-5) are the DE move's scale and jitter, ``gamma_s`` (1.7) the snooker's scale;
+    DE needs 4 walkers, the snooker 6.  ``stats['moves']`` then counts per move the proposals and - with a row for every step
+    (thin = 1) - the accepted ones, on the host from the words the moves were drawn from, when it is read
+    (:class:`MoveCounts`: the run itself does not pay for it)."""
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
-                 chunk=0, lanes=0, const_hint=-1):
-        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint)
+                 chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None):
+        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
+                            sigma, gamma_s)
         self.stream = int(stream)
         self.reset()
 
@@ -601,12 +854,12 @@ class EnsembleSampler(StretchSampler):
         chain, chain_lnl, st = self.vega.engine.ensemble_run(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.step, k, thin=self.thin, a=self.a,
             log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint, chunk=self.chunk,
-            lanes=self.lanes)
+            lanes=self.lanes, **self._moves_arg())
         return chain, chain_lnl, st
 
     def _python_steps(self, k, chi2):
         return python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.stream, self.lo,
-                            self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x))
+                            self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x), self.moves)
 
     # ---- results
     def _stack(self, parts, discard, thin, flat):
@@ -653,11 +906,13 @@ class EnsembleSet(StretchSampler):
     ``EnsembleSampler(..., seed=seed, stream=streams[e])`` draws, and is the chain that sampler makes - up to the last bits of lnL
     where the engine's batches are shaped differently.  ``mock_rows`` [E]: the row of the installed mock
     pools every ensemble is compared with - a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`);
-    None: every ensemble reads the data the interface has installed - replicas of one run.  An engine group takes ``'python'``."""
+    None: every ensemble reads the data the interface has installed - replicas of one run.  An engine group takes ``'python'``.
+    ``moves``, ``gamma0``, ``sigma``, ``gamma_s``: the mixture of moves of every ensemble, as for :class:`EnsembleSampler`."""
 
     def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
-                 sample_params=None, chunk=0, lanes=0, const_hint=-1):
-        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint)
+                 sample_params=None, chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None):
+        self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
+                            sigma, gamma_s)
         self.E = int(ensembles)
         if self.E < 1:
             raise ValueError('ensembles: at least one')
@@ -680,7 +935,8 @@ class EnsembleSet(StretchSampler):
         return EnsembleSampler(self.vega, self.W, a=self.a, seed=self.seed, thin=self.thin, driver=self.driver_asked,
                                segment=self.segment, sample_params=dict(limits=dict(zip(self.names, zip(self.lo, self.hi))),
                                                                          values=self.values, errors=self.errors),
-                               stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint)
+                               stream=int(self.streams[e]), chunk=self.chunk, lanes=self.lanes, const_hint=self.const_hint,
+                               **self._moves_kw)
 
     def _start_positions(self, start, init_scale):
         """The starts of ``run``'s first call: ``'ball'``, ``'prior'`` - ensemble e as ``EnsembleSampler(seed, stream=streams[e])``
@@ -730,13 +986,13 @@ class EnsembleSet(StretchSampler):
         chain, chain_lnl, st = self.vega.engine.ensemble_run_many(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.step, k,
             mock_rows=self.mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(), seed=self.seed,
-            const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes)
+            const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, **self._moves_arg())
         return chain, chain_lnl, st, st.pop('per_ensemble')
 
     def _python_steps(self, k, chi2):
         row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, self.W // 2)
         return python_steps_many(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.streams, self.lo,
-                                 self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x, row_mock))
+                                 self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x, row_mock), self.moves)
 
     # ---- results
     def _stack(self, parts, tail, discard, thin, flat):
@@ -774,6 +1030,9 @@ class EnsembleSet(StretchSampler):
         m._chain_lnl[:] = [part[e] for part in self._chain_lnl]
         took, out, bad = (int(v) for v in self.per_ensemble[e])
         m.stats = dict(self.stats, proposals=self.step * self.W, accepted=took, rejected_outside_box=out, rejected_failed_model=bad)
+        if self.moves is not None:
+            m._start = None if self._start is None else (self._start[0][e].copy(), self._start[1][e].copy())
+            m.stats['moves'] = MoveCounts(m)
         return m
 
 
@@ -819,10 +1078,11 @@ def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
     parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver} and, when the section states it,
-    ``derived`` (True | False; absent means False: the chain files are what they were) and ``replicas`` (R >= 1 independent
-    copies on Philox streams 0 .. R - 1, merged afterwards: :mod:`vega_amd.replicas`); with ``sampler = Nested`` the
-    ``[Nested]`` settings instead (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones
-    (:func:`vega_amd.smc.smc_settings`)."""
+    ``moves`` with ``gamma0`` / ``de_sigma`` / ``snooker_gamma`` (:func:`_parse_moves`: a mixture of the stretch, DE and snooker
+    moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
+    they were) and ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
+    :mod:`vega_amd.replicas`); with ``sampler = Nested`` the ``[Nested]`` settings instead
+    (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
     run = control.getboolean('run_sampler', False) if hasattr(control, 'getboolean') else False
     if not run:
@@ -856,6 +1116,7 @@ def sampler_settings(main_config, sample_params):
         raise ValueError('[Ensemble] steps and thin must be positive')
     if not out['a'] > 1.0:
         raise ValueError('[Ensemble] a: the stretch scale must exceed 1')
+    _parse_moves(sec, out, len(limits))
     if 'mocks' in sec:
         out['mocks'] = _parse_mocks(sec, main_config)
     if 'together' in sec:
@@ -864,6 +1125,55 @@ def sampler_settings(main_config, sample_params):
         except ValueError:
             raise ValueError('[Ensemble] together: True or False') from None
     return out
+
+
+_MOVE_KEYS = (('gamma0', 'gamma0'), ('de_sigma', 'sigma'), ('snooker_gamma', 'gamma_s'))
+
+
+def _parse_moves(sec, out, n):
+    """``moves = de 0.8 snooker 0.2`` of ``[Ensemble]``: move names (stretch, de, snooker), each with its weight after it - a
+    bare name weighs 1, so that ``moves = de`` is the pure move - into ``out['moves']`` as a list of (name, weight); ``gamma0``,
+    ``de_sigma`` and ``snooker_gamma`` into the keys of the same names when stated.  Without ``moves`` nothing is added.  The
+    mixture is checked against the walkers as :func:`resolve_moves` checks it."""
+    scales = {}
+    for key, _ in _MOVE_KEYS:
+        if key in sec:
+            try:
+                scales[key] = sec.getfloat(key)
+            except ValueError:
+                raise ValueError(f'[Ensemble] {key}: a number') from None
+    if 'moves' not in sec:
+        if scales:
+            raise ValueError(f'[Ensemble] {", ".join(scales)}: the scales of moves, but no moves are named')
+        return
+    pairs = []
+    for tok in sec.get('moves').replace(',', ' ').split():
+        try:
+            w = float(tok)
+        except ValueError:
+            if tok not in MOVE_NAMES:
+                raise ValueError(f"[Ensemble] moves: unknown move {tok!r}; one of 'stretch', 'de', 'snooker'") from None
+            pairs.append([tok, None])
+            continue
+        if not pairs or pairs[-1][1] is not None:
+            raise ValueError('[Ensemble] moves: a weight follows the name of its move')
+        pairs[-1][1] = w
+    if not pairs:
+        raise ValueError('[Ensemble] moves: name at least one move')
+    out['moves'] = [(name, 1.0 if w is None else w) for name, w in pairs]
+    out.update(scales)
+    try:
+        resolve_moves(**moves_arguments(out), n=n, walkers=out['walkers'])
+    except ValueError as err:
+        raise ValueError(f'[Ensemble] {err}') from None
+
+
+def moves_arguments(cfg):
+    """The ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s`` arguments of the sampler classes the settings ``cfg`` ask for: empty
+    without ``moves``, so that a run without them is constructed as ever."""
+    if 'moves' not in cfg:
+        return {}
+    return dict(moves=cfg['moves'], **{arg: cfg[key] for key, arg in _MOVE_KEYS if key in cfg})
 
 
 def _parse_mocks(sec, main_config, section='Ensemble', own='an ensemble'):
@@ -900,7 +1210,7 @@ def build_sampler(vega, cfg, sample_params, stream=0):
                           driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params, stream=stream,
                           **{key: cfg[key] for key in ('n_total', 'recycle') if key in cfg})
     return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
-                           sample_params=sample_params, stream=stream)
+                           sample_params=sample_params, stream=stream, **moves_arguments(cfg))
 
 
 def advance_sampler(sampler, cfg):
@@ -1007,7 +1317,7 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
         mc.write_mock_posteriors(cfg['path'])
         return sampler
     sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],
-                              scale=scale, sample_params=sample_params, driver=cfg['driver'])
+                              scale=scale, sample_params=sample_params, driver=cfg['driver'], **moves_arguments(cfg))
     chain, lnl = sampler.get_chain(), sampler.get_log_lik()
     for m in range(sampler.E):
         table, lines = getdist_table(sampler.names, chain[m], lnl[m])

@@ -470,7 +470,7 @@ class MonteCarlo:
 
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
-                     ess=0.5, sweeps=None, n_total=None, recycle=False):
+                     ess=0.5, sweeps=None, n_total=None, recycle=False, moves=None, gamma0=None, sigma=None, gamma_s=None):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -481,7 +481,8 @@ class MonteCarlo:
 
         Keeps ``mc_posteriors``: names, per mock ``mean`` / ``sd`` [M, n] and ``covariance`` [M, n, n] of the rows after ``burn``,
         ``tau`` [M, n] (integrated autocorrelation times in recorded rows), ``acceptance`` [M], ``n_eff`` [M] (rows after burn x
-        walkers / the largest tau) and the run's settings; with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
+        walkers / the largest tau) and the run's settings; ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s``: the ensembles' mixture
+        of moves (:class:`vega_amd.ensemble.EnsembleSet`; None: the stretch move); with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
         ``mc_chain_lnl``.  Returns the set.
 
         ``sampler='smc'``: the evidence and an equal-weight posterior of every mock instead, M tempered SMC runs advanced together
@@ -499,8 +500,11 @@ class MonteCarlo:
             raise ValueError("sample_mocks: sampler 'ensemble' or 'smc'")
         if sampler != 'smc' and (n_total is not None or recycle):
             raise ValueError("sample_mocks: n_total and recycle go with sampler='smc'")
+        moves_kw = {key: v for key, v in dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s).items() if v is not None}
+        if sampler != 'ensemble' and moves_kw:
+            raise ValueError("sample_mocks: moves go with sampler='ensemble'")
         return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
-                                  fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle)
+                                  fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle, moves_kw=moves_kw)
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
@@ -522,7 +526,7 @@ class MonteCarlo:
 
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
-                      max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False):
+                      max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False, moves_kw=None):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -570,7 +574,7 @@ class MonteCarlo:
                                 **({'boost_posterior': boost_posterior} if boost_posterior else {}))
         else:
             sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
-                                  sample_params=sample_params)
+                                  sample_params=sample_params, **(moves_kw or {}))
         try:
             for name, pool in mocks.items():
                 eng.set_mock_pool(name, pool)
@@ -652,6 +656,8 @@ class MonteCarlo:
             covariance=np.array([np.atleast_2d(np.cov(rows.T)) for rows in flat]), tau=tau,
             acceptance=sampler.acceptance_fraction.mean(axis=1), n_eff=flat.shape[1] / tau.max(axis=1),
             steps=steps, burn=burn, thin=thin, walkers=walkers, seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+        if sampler.moves is not None:       # (without moves the dict has the keys it had)
+            self.mc_posteriors['moves'] = dict(sampler.moves)
         self.mc_chains = sampler.get_chain() if keep_chains else None
         self.mc_chain_lnl = sampler.get_log_lik() if keep_chains else None
         return sampler

@@ -59,6 +59,9 @@ def _common(sampler, kind, points, derived):
                names=np.array([str(nm) for nm in getattr(sampler, 'names', [f'p{i}' for i in range(sampler.n)])]),
                driver=str(getattr(sampler, 'driver', None) or 'python'))
     for key, val in sampler.stats.items():
+        if key == 'moves':          # (the ensemble's per-move counts: one number per move and count; an unknown count is left out)
+            rec.update({f'stats_moves_{move}_{what}': v for move, counts in val.items() for what, v in counts.items() if v is not None})
+            continue
         rec[f'stats_{key}'] = val
     if derived:
         rec.update(derived=np.asarray(derived['derived'], dtype=np.float64), derived_names=np.array(list(derived['derived_names'])),
@@ -563,7 +566,7 @@ def run_replicas(vega, cfg, sample_params, group, print_func=print):
     if cfg.get('together', False) and cfg['sampler'] == 'Ensemble' and hi > lo:
         # the rank's replicas as one set: their half-steps decided together, their rows one stream of full batches for the engine
         both = E.EnsembleSet(vega, hi - lo, cfg['walkers'], streams=range(lo, hi), a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'],
-                             driver=cfg['driver'], sample_params=sample_params)
+                             driver=cfg['driver'], sample_params=sample_params, **E.moves_arguments(cfg))
         both.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
         ready = [both.member(k) for k in range(hi - lo)]
     if cfg.get('together', False) and cfg['sampler'] == 'SMC' and hi > lo:
