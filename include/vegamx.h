@@ -527,6 +527,42 @@ int vmx_ensemble_run_many_moves(vmx_engine* e, const vmx_ensemble_spec* spec, in
                                 const vmx_ensemble_options* opt,
                                 vmx_ensemble_stats* stats, int64_t* per_ensemble,
                                 const vmx_ensemble_moves* moves);
+/* Parallel tempering (Swendsen & Wang 1986; ptemcee): G ladders of T ensembles each, the rungs of a ladder differing only in the
+ * beta that multiplies lnL in the Metropolis decision, with swaps of walkers between adjacent rungs - what lets the cold rung
+ * cross between separated modes, and what gives the evidence from the rungs' lnL records (stepping stones or thermodynamic
+ * integration, on the host: vega_amd/ensemble.py).  The run is vmx_ensemble_run_many_moves over the G T ensembles (ladder g owns
+ * g T .. g T + T - 1, rung 0 cold) through the half-step kernel k_ens_half_pt; after every swap_every-th step one more small
+ * kernel, k_ens_swap (one work-group per ladder), exchanges walkers from the hottest pair of rungs down, between the deciding
+ * half-step and the next proposal.  It needs no likelihood row - lnL is stored untempered - and no host wait: the call keeps its
+ * single synchronisation.  The tempered decision, the rotation that pairs the walkers, the swap rule and their two Philox blocks
+ * (counters (k, s, t, 2) and (0, s, t, 3), key (seed, stream of the ladder's rung 0)) are pinned in vega_amd/csrc/vmx_ensemble.h.
+ *   G, T, W   ladders (>= 1) of T rungs (1 <= T <= VMX_PT_MAXT) of W walkers each, W even and >= 2 n
+ *   betas     [T]: betas[0] = 1 > betas[1] > ... > betas[T - 1] >= 0, shared by the ladders.  With beta = 1 a rung's decisions are
+ *             those of vmx_ensemble_run_many_moves bit for bit; with beta = 0 a rung samples the box (a proposal outside it, or
+ *             with a failed model, is still rejected)
+ *   streams   [G T] the Philox stream of every rung
+ *   mock_row  [G] the row of the items' mock pools ladder g is compared with; NULL: the installed data
+ *   x, lnL, accepted   [G T][W][n], [G T][W], [G T][W] host: the state, read at entry and written back at exit; lnL is
+ *             log_norm - 0.5 chi2 on every rung.  A swap exchanges positions and lnL; accepted stays with the slot
+ *   step0, n_steps, thin   as for vmx_ensemble_run_many
+ *   swap_every  a sweep after every global step s with (s + 1) % swap_every == 0, before that step's chain row (a run cut into
+ *             calls swaps at the same steps); 0: no swaps - every rung is then the plain ensemble at its beta
+ *   chain, chain_lnL       [G T][rows][W][n], [G T][rows][W] (host, NULL: not kept): the records of all rungs
+ *   stats, per_ensemble [G T][3]   as for vmx_ensemble_run_many
+ *   moves     as for vmx_ensemble_run_many_moves; NULL: the stretch move
+ *   swaps     [G][T - 1][2] (NULL: not wanted): per pair of rungs (t, t + 1) the swaps proposed and accepted in this call
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever vmx_ensemble_run_many_moves refuses; G < 1;
+ * T < 1 or T > VMX_PT_MAXT; betas NULL, betas[0] != 1, a beta that is not finite, negative or not below the one before it;
+ * swap_every < 0; G T W beyond the engine's int32 row count. */
+#define VMX_PT_MAXT 64
+int vmx_ensemble_run_pt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G, int32_t T, int32_t W,
+                        const double* betas, const uint64_t* streams, const int32_t* mock_row,
+                        double* x, double* lnL, int64_t* accepted,
+                        int64_t step0, int32_t n_steps, int32_t thin, int32_t swap_every,
+                        double* chain, double* chain_lnL,
+                        const vmx_ensemble_options* opt,
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                        const vmx_ensemble_moves* moves, int64_t* swaps);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

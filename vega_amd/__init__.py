@@ -3,6 +3,7 @@ from .interface import VegaInterface  # noqa: F401
 from .setup import Grid as Coordinates  # noqa: F401  (reference vega/coordinates.py: the grids a caller hands to a model-only correlation)
 from .errors import VegaModelError, VegaBoundsError, VegaArinyoError  # noqa: F401
 from .ensemble import EnsembleSampler, EnsembleSet, run_vega_sampler  # noqa: F401  (posterior sampling: bin/run_vega_mpi.py for one process)
+from .ensemble import TemperedEnsemble  # noqa: F401  (parallel tempering: separated modes, and an evidence from the ladder)
 from .nested import NestedSampler, NestedSet  # noqa: F401  (evidence and a weighted posterior: sampler = Nested)
 from .smc import SMCRun, SMCSampler, SMCSet  # noqa: F401  (evidence and an equal-weight posterior by tempered SMC: sampler = SMC)
 from .replicas import gelman_rubin, merge_ensemble, merge_nested, merge_smc  # noqa: F401  (replicas = R: one process per GPU)

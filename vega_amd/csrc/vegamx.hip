@@ -225,6 +225,8 @@ struct EnsWorkspace {
     DevBuf<int32_t> inside, col;
     DevBuf<int32_t> mock;               // the mock row of every engine row [E H], written once per call that names mocks
     DevBuf<uint64_t> streams;           // the ensembles' Philox streams [E]
+    DevBuf<double> beta;                // parallel tempering: the ladder [T] ...
+    DevBuf<int64_t> swaps;              // ... and the call's swap counters [G][T - 1][2]
 };
 
 struct EnsDev {
@@ -396,6 +398,140 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMov
         double* row = theta + (size_t)k * D.P;
         for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
         for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
+    }
+}
+
+// Parallel tempering (vmx_ensemble_run_pt; vmx_ensemble.h, "parallel tempering"): G ladders of T rungs are G T ensembles, ensemble
+// g T + t on the rung of beta[t].  What the kernels read beside EnsDev: the ladder and the call's swap counters.
+struct EnsPtDev {
+    const double* beta;                 // [T]
+    int64_t* swaps;                     // [G][T - 1][2]: proposed, accepted
+    int32_t T;
+};
+enum { ENS_PT_DECIDE = 1, ENS_PT_RECORD = 2, ENS_PT_PROPOSE = 4 };
+
+// k_ens_half_moves with the rung's beta in the decision (accept_tempered): the same grid - one work-group per ensemble - the same
+// decide / record / propose order and the same strided loops, so that the chain does not depend on the block size.  `what` names
+// the parts to run: all three between two half-steps without a sweep; with a sweep due, ENS_PT_DECIDE alone, then k_ens_swap, then
+// ENS_PT_RECORD | ENS_PT_PROPOSE, so that the row of step s_dec and the next proposals see the walkers after the swaps.  A run
+// without moves comes with the thresholds of the pure stretch move (t0 = t1 = 1: the chain of k_ens_half).
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesDev M, EnsPtDev Pt, int64_t s_dec, int h_dec,
+                                                             int64_t s_prop, int h_prop, int what)
+{
+    const int W = D.W, H = W / 2, n = D.n;
+    const size_t e = blockIdx.x;
+    const uint64_t stream = D.streams[e];
+    const double beta = Pt.beta[e % (size_t)Pt.T];
+    double* const x = D.x + e * W * n;
+    double* const lnl = D.lnl + e * W;
+    int64_t* const acc = D.acc + e * W;
+    int64_t* const n_box = D.n_box + e * W;
+    int64_t* const n_fail = D.n_fail + e * W;
+    double* const prop = D.prop + e * H * n;
+    double* const factor = D.factor + e * H;
+    int32_t* const inside_of = D.inside + e * H;
+    const double* const chi2 = D.box.chi2 + e * H;
+    const int32_t* const status = D.box.status + e * H;
+    double* const theta = D.box.theta + e * H * D.P;
+    if (s_dec >= 0) {
+        if (what & ENS_PT_DECIDE)
+            for (int k = threadIdx.x; k < H; k += blockDim.x) {
+                const int w = h_dec * H + k;
+                const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, stream);
+                const double c2 = chi2[k];
+                const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
+                const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
+                if (vmx_ens::accept_tempered(inside, ok, factor[k], beta, lnl_new, lnl[w], b.w[2])) {
+                    for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
+                    lnl[w] = lnl_new;
+                    acc[w] += 1;
+                } else if (!inside) n_box[w] += 1;
+                else if (!ok) n_fail[w] += 1;
+            }
+        if ((what & ENS_PT_RECORD) && h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
+            __syncthreads();
+            const size_t r = e * D.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
+            if (D.chain)
+                for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
+            if (D.chain_lnl)
+                for (int q = threadIdx.x; q < W; q += blockDim.x) D.chain_lnl[r * W + q] = lnl[q];
+        }
+    }
+    if (s_prop < 0 || !(what & ENS_PT_PROPOSE)) return;
+    __syncthreads();            // (the partners of the next half are the walkers just decided)
+    const double* const other = x + (size_t)(1 - h_prop) * H * n;
+    for (int k = threadIdx.x; k < H; k += blockDim.x) {
+        const int w = h_prop * H + k;
+        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
+        const vmx_ens::Block m = vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream);
+        const int move = vmx_ens::move_choice(m.w[0], M.t0, M.t1);
+        const int64_t j1 = vmx_ens::partner(b.w[0], H);
+        const double* c1 = other + (size_t)j1 * n;
+        const double* s = x + (size_t)w * n;
+        double* y = prop + (size_t)k * n;
+        double f = 0.0;
+        bool in = true;
+        if (move == vmx_ens::MOVE_STRETCH) {
+            const double z = vmx_ens::stretch_z(D.a, b.w[1]);
+            for (int d = 0; d < n; ++d) y[d] = vmx_ens::propose(c1[d], s[d], z);
+            f = vmx_ens::log_factor(n, z);
+        } else {
+            // (the entry refuses a DE weight with H < 2 and a snooker weight with H < 3: the indices below are in range)
+            const int64_t j2 = vmx_ens::partner2(b.w[1], H, j1);
+            const double* c2 = other + (size_t)j2 * n;
+            if (move == vmx_ens::MOVE_DE) {
+                const double gamma = vmx_ens::de_gamma(M.gamma0, M.sigma, m.w[1], m.w[2]);
+                for (int d = 0; d < n; ++d) y[d] = vmx_ens::de_propose(s[d], c1[d], c2[d], gamma);
+            } else {
+                const int64_t j3 = vmx_ens::partner3(b.w[3], H, j1, j2);
+                in = vmx_ens::snooker_propose(n, s, c1, c2, other + (size_t)j3 * n, M.gamma_s, y, f);
+            }
+        }
+        for (int d = 0; d < n; ++d) in = in && y[d] >= D.box.lo[d] && y[d] <= D.box.hi[d];
+        factor[k] = f;
+        inside_of[k] = in ? 1 : 0;
+        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
+        double* row = theta + (size_t)k * D.P;
+        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
+        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
+    }
+}
+
+// The swap sweep after global step s: one work-group per ladder (nothing crosses ladders, so __syncthreads() between the T - 1
+// pairs of rungs is the only barrier), the pairs of rungs from the hottest down.  The threads stride over the W pairs of walkers
+// of a pair of rungs; the rotation makes them disjoint, so a thread reads and writes its own two rows alone.  No likelihood row:
+// lnL is stored untempered.  Every expression: vmx_ensemble.h.
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_swap(EnsDev D, EnsPtDev Pt, int64_t s)
+{
+    const int W = D.W, n = D.n, T = Pt.T;
+    const size_t g = blockIdx.x;
+    const uint64_t stream = D.streams[g * T];
+    int64_t* const swaps = Pt.swaps + g * (size_t)(T - 1) * 2;
+    for (int t = T - 1; t >= 1; --t) {
+        const size_t cold = g * T + (size_t)(t - 1), hot = cold + 1;
+        double* const xc = D.x + cold * W * n;
+        double* const xh = D.x + hot * W * n;
+        double* const lc = D.lnl + cold * W;
+        double* const lh = D.lnl + hot * W;
+        const double bc = Pt.beta[t - 1], bh = Pt.beta[t];
+        const int64_t r = vmx_ens::swap_shift(vmx_ens::shift_block(s, t, D.seed, stream).w[0], W);
+        unsigned long long took = 0;
+        for (int k = threadIdx.x; k < W; k += blockDim.x) {
+            const int64_t j = vmx_ens::swap_partner(k, r, W);
+            const vmx_ens::Block b = vmx_ens::swap_block(k, s, t, D.seed, stream);
+            const double l_cold = lc[k], l_hot = lh[j];
+            if (vmx_ens::swap_accept(bc, bh, l_cold, l_hot, b.w[0])) {
+                double* pc = xc + (size_t)k * n;
+                double* ph = xh + (size_t)j * n;
+                for (int d = 0; d < n; ++d) { const double v = pc[d]; pc[d] = ph[d]; ph[d] = v; }
+                lc[k] = l_hot;
+                lh[j] = l_cold;
+                took += 1;
+            }
+        }
+        if (took) atomicAdd((unsigned long long*)&swaps[2 * (t - 1) + 1], took);
+        if (threadIdx.x == 0) swaps[2 * (t - 1)] += W;
+        __syncthreads();        // (rung t - 1 is the hot rung of the next pair)
     }
 }
 
@@ -4938,10 +5074,13 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
 }
 
 // ---- posterior sampling where the walkers live (vmx_ensemble.h)
+// what makes a run of E = G T ensembles G ladders of T rungs (vmx_ensemble_run_pt): the ladder, the sweeps, where the counts go
+struct EnsPtRun { int32_t G, T; const double* betas; int32_t swap_every; int64_t* swaps; };
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
-                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves);
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves,
+                        const EnsPtRun* pt = nullptr);
 
 // One ensemble is the set of one, on the stream of its spec
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
@@ -4975,12 +5114,38 @@ int vmx_ensemble_run_many_moves(vmx_engine* e, const vmx_ensemble_spec* spec, in
                         chain, chain_lnL, opt, stats, per_ensemble, moves);
 }
 
+// G ladders of T rungs: the run of G T ensembles with the rung's beta in every decision (k_ens_half_pt) and a swap sweep between
+// the rungs of a ladder after every swap_every-th step (k_ens_swap), on the main stream between the deciding half-step and the
+// next proposal - no host wait, no likelihood row
+static_assert(VMX_PT_MAXT == vmx_ens::PT_MAXT, "parallel tempering limits");
+int vmx_ensemble_run_pt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G, int32_t T, int32_t W, const double* betas,
+                        const uint64_t* streams, const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0,
+                        int32_t n_steps, int32_t thin, int32_t swap_every, double* chain, double* chain_lnL,
+                        const vmx_ensemble_options* opt, vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                        const vmx_ensemble_moves* moves, int64_t* swaps)
+{
+    const std::string name("vmx_ensemble_run_pt");
+    REQUIRE(G >= 1, name + ": at least one ladder");
+    REQUIRE(T >= 1 && T <= VMX_PT_MAXT, name + ": 1 <= T <= VMX_PT_MAXT rungs");
+    REQUIRE(betas && vmx_ens::ladder_ok(betas, T), name + ": the ladder must start at 1, be finite, strictly decreasing and not negative");
+    REQUIRE(swap_every >= 0, name + ": swap_every >= 0");
+    REQUIRE(W >= 1 && (int64_t)G * T <= INT32_MAX && (int64_t)G * T * W <= INT32_MAX, name + ": G T W exceeds the engine's row count");
+    std::vector<int32_t> rung_mock;         // (every rung of a ladder reads the ladder's mock)
+    if (mock_row) {
+        rung_mock.resize((size_t)G * T);
+        for (int g = 0; g < G; ++g) std::fill(rung_mock.begin() + (size_t)g * T, rung_mock.begin() + (size_t)(g + 1) * T, mock_row[g]);
+    }
+    const EnsPtRun pt{G, T, betas, swap_every, swaps};
+    return ensemble_run("vmx_ensemble_run_pt", e, spec, G * T, W, streams, mock_row ? rung_mock.data() : nullptr, x, lnL, accepted, step0,
+                        n_steps, thin, chain, chain_lnL, opt, stats, per_ensemble, moves, &pt);
+}
+
 // E independent ensembles advanced together (k_ens_half): the E H proposal rows of a half-step as one stream of chunks for the
 // engine, every row with the mock of its ensemble
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
-                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves)
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves, const EnsPtRun* pt)
 {
     const std::string name(who);
     REQUIRE(e && e->finalized && spec && x && lnL && accepted, name);
@@ -5008,6 +5173,8 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         REQUIRE(std::isfinite(moves->sigma) && moves->sigma >= 0.0, name + ": sigma must be finite and not negative");
         REQUIRE(moves->flags == 0 && moves->reserved == 0, name + ": flags and reserved must be 0");
         M.gamma0 = moves->gamma0; M.sigma = moves->sigma; M.gamma_s = moves->gamma_s;
+    } else if (pt) {
+        M.t0 = M.t1 = 1.0;      // (the pure stretch move of k_ens_half_pt: u < 1 always)
     }
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
     // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
@@ -5038,6 +5205,8 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         ensure(S.prop, (size_t)EH * n) || ensure(S.factor, EH) || ensure(S.inside, EH) || ensure(S.col, n) || ensure(S.streams, E) ||
         (mock_row && ensure(S.mock, EH)))
         return -2;
+    const size_t n_swaps = pt ? (size_t)pt->G * (size_t)(pt->T - 1) * 2 : 0;
+    if (pt && (ensure(S.beta, pt->T) || (n_swaps && ensure(S.swaps, n_swaps)))) return -2;
     if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
     if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
     hipStream_t st = e->stream;
@@ -5075,8 +5244,27 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int64_t halves = 2 * (int64_t)n_steps;
     // (every loop of the kernel strides by its block: the chain does not depend on this size)
     const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
+    // a ladder's half-step: with a sweep due after step s_dec, the swaps come between the decisions and the row and proposals
+    EnsPtDev Pt{};
+    if (pt) {
+        HIP_OK(hipMemcpyAsync(S.beta.p, pt->betas, (size_t)pt->T * sizeof(double), hipMemcpyHostToDevice, st));
+        if (n_swaps) HIP_OK(hipMemsetAsync(S.swaps.p, 0, n_swaps * sizeof(int64_t), st));
+        Pt.beta = S.beta.p; Pt.swaps = n_swaps ? S.swaps.p : nullptr; Pt.T = pt->T;
+    }
+    const dim3 grid_swap(pt ? pt->G : 1), block_swap(std::min(ENS_THREADS, std::max(64, (W + 63) / 64 * 64)));
+    const int pt_all = ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE;
+    auto half_pt = [&](int64_t s_dec, int h_dec, int64_t s_prop, int h_prop) {
+        if (s_dec >= 0 && h_dec == 1 && pt->T > 1 && vmx_ens::swap_due(s_dec, pt->swap_every)) {
+            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, (int)ENS_PT_DECIDE);
+            hipLaunchKernelGGL(k_ens_swap, grid_swap, block_swap, 0, st, D, Pt, s_dec);
+            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, ENS_PT_RECORD | ENS_PT_PROPOSE);
+        } else {
+            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, pt_all);
+        }
+    };
     if (halves > 0) {
-        if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, (int64_t)-1, 0, step0, 0);
+        if (pt) half_pt((int64_t)-1, 0, step0, 0);
+        else if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, (int64_t)-1, 0, step0, 0);
         else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, (int64_t)-1, 0, step0, 0);
     }
     HIP_OK(hipGetLastError());
@@ -5088,11 +5276,16 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         R.engine_calls += calls;
         const int64_t nq = q + 1;
         const int64_t s_next = nq < halves ? step0 + nq / 2 : (int64_t)-1;
-        if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s, h, s_next, (int)(nq % 2));
+        if (pt) half_pt(s, h, s_next, (int)(nq % 2));
+        else if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s, h, s_next, (int)(nq % 2));
         else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s, h, s_next, (int)(nq % 2));
         HIP_OK(hipGetLastError());
     }
     std::vector<int64_t> acc0(accepted, accepted + EW), box(EW), failed(EW);
+    if (pt && pt->swaps && n_swaps) {
+        if (halves > 0) HIP_OK(hipMemcpyAsync(pt->swaps, S.swaps.p, n_swaps * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        else std::fill(pt->swaps, pt->swaps + n_swaps, (int64_t)0);
+    }
     HIP_OK(hipMemcpyAsync(x, S.x.p, EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, EW * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));

@@ -257,4 +257,84 @@ VMX_HD inline bool snooker_propose(int n, const double* s, const double* z, cons
     return is_finite(factor);
 }
 
+// ---- parallel tempering: ladders of ensembles and the swaps between their rungs (vmx_ensemble_run_pt: k_ens_half_pt, k_ens_swap)
+//
+//   ladder           beta[0] = 1 > beta[1] > ... > beta[T - 1] >= 0, T <= PT_MAXT.  A run holds G ladders; ladder g owns the
+//                    ensembles g T .. g T + T - 1, rung 0 the cold one.  Every rung is an ensemble as above, on its own stream.
+//   decision         rung t accepts iff inside, model ok and (factor + beta lnL_new) - beta lnL_old > log(u(w2)): the products
+//                    a = beta lnL_new and b = beta lnL_old first, each rounded, then accept(inside, ok, factor, a, b, w2).  With
+//                    beta = 1 the products are exact and the decision is the one above bit for bit; with beta = 0 a proposal
+//                    outside the box or with a failed model is still rejected.  The stored lnL is untempered, always.
+//   swap sweep       after step s when swap_every > 0 and (s + 1) % swap_every == 0 (s the global step: a run cut into calls swaps
+//                    at the same steps), once half 1 of step s is decided and before the chain row of step s is recorded.  Pairs
+//                    of rungs from the hottest down, one after the other: t = T - 1, ..., 1, rung t - 1 against rung t, so that a
+//                    walker may travel several rungs in one sweep.
+//   pairing          a random rotation: r = swap_shift(w0, W) = partner(w0, W), w0 the first word of the block with counter
+//                    (0, s, t, 3); walker k of rung t - 1 is paired with walker (k + r) mod W of rung t - disjoint pairs, chosen
+//                    independently of the state.
+//   swap rule        pair k draws word 0 of the block with counter (k, s, t, 2); db = beta[t - 1] - beta[t];
+//                    dl = lnL_hot - lnL_cold; lhs = db dl; swap iff lhs > log(u(word)).  A swap exchanges the n positions and the
+//                    lnL; the accepted / box / failed counters stay with the slot.
+//   key              both blocks: (seed, the stream of the ladder's rung 0).  The last counter words 2 and 3 keep them apart from
+//                    the blocks of the moves (0 and 1).
+constexpr int PT_MAXT = 64;
+
+// a ladder the sampler takes: beta[0] == 1, finite, strictly decreasing, none negative
+VMX_HD inline bool ladder_ok(const double* beta, int T)
+{
+    if (T < 1 || T > PT_MAXT || !(beta[0] == 1.0)) return false;
+    for (int t = 0; t < T; ++t) {
+        if (!is_finite(beta[t]) || !(beta[t] >= 0.0)) return false;
+        if (t > 0 && !(beta[t] < beta[t - 1])) return false;
+    }
+    return true;
+}
+
+// a rung's view of a log-likelihood: what its Metropolis decision compares
+VMX_HD inline double tempered(double beta, double lnl)
+{
+    VMX_NO_CONTRACT
+    return beta * lnl;
+}
+
+// the decision of a proposal on the rung of beta
+VMX_HD inline bool accept_tempered(bool inside, bool ok, double factor, double beta, double lnl_new, double lnl_old, uint64_t x2)
+{
+    const double a = tempered(beta, lnl_new), b = tempered(beta, lnl_old);
+    return accept(inside, ok, factor, a, b, x2);
+}
+
+// the block of the rotation of the pair (rung t - 1, rung t) at global step s
+VMX_HD inline Block shift_block(int64_t s, int t, uint64_t seed, uint64_t stream)
+{
+    return philox4x64_10(0, (uint64_t)s, (uint64_t)t, 3, seed, stream);
+}
+
+// the block of pair k of (rung t - 1, rung t) at global step s: w0 the acceptance word
+VMX_HD inline Block swap_block(int64_t k, int64_t s, int t, uint64_t seed, uint64_t stream)
+{
+    return philox4x64_10((uint64_t)k, (uint64_t)s, (uint64_t)t, 2, seed, stream);
+}
+
+// the rotation r in [0, W): walker k of the colder rung meets walker (k + r) mod W of the hotter one
+VMX_HD inline int64_t swap_shift(uint64_t w0, int64_t W) { return partner(w0, W); }
+
+VMX_HD inline int64_t swap_partner(int64_t k, int64_t r, int64_t W)
+{
+    const int64_t j = k + r;
+    return j >= W ? j - W : j;
+}
+
+VMX_HD inline bool swap_accept(double beta_cold, double beta_hot, double lnl_cold, double lnl_hot, uint64_t word)
+{
+    VMX_NO_CONTRACT
+    const double db = beta_cold - beta_hot;
+    const double dl = lnl_hot - lnl_cold;
+    const double lhs = db * dl;
+    return lhs > log(u01(word));
+}
+
+// a sweep is due after global step s
+VMX_HD inline bool swap_due(int64_t s, int32_t swap_every) { return swap_every > 0 && (s + 1) % swap_every == 0; }
+
 }  // namespace vmx_ens

@@ -331,6 +331,10 @@ def load_library():
                                           dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, dptr, dptr,
                                           C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64)]
     lib.vmx_ensemble_run_many_moves.argtypes = lib.vmx_ensemble_run_many.argtypes + [C.POINTER(EnsembleMoves)]
+    lib.vmx_ensemble_run_pt.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, C.c_int32, C.c_int32, dptr, C.POINTER(C.c_uint64),
+                                        iptr, dptr, dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, C.c_int32, dptr, dptr,
+                                        C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64),
+                                        C.POINTER(EnsembleMoves), C.POINTER(C.c_int64)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -419,7 +423,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1238,6 +1242,43 @@ class Engine:
                                float(moves['gamma_s']), int(moves.get('flags', 0)), 0)
             self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
+
+    def ensemble_run_pt(self, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, step0, n_steps, swap_every=1, mock_rows=None,
+                        thin=1, a=2.0, log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):
+        """``n_steps`` steps of G temperature ladders of T rungs in one device run (include/vegamx.h: vmx_ensemble_run_pt): ``x``
+        [G, T, W, n] / ``lnl`` [G, T, W] / ``accepted`` int64 [G, T, W] the walkers' state (updated in place; lnl untempered),
+        ``betas`` [T] the ladder, ``streams`` [G, T] the Philox stream of every rung, ``mock_rows`` [G] the pool row of every ladder
+        (None: the installed data), ``swap_every`` the steps between swap sweeps (0: none); the rest as for
+        :meth:`ensemble_run_many`.  Returns (chain [G, T, rows, W, n], chain_lnl [G, T, rows, W], statistics); the statistics
+        carry ``per_ensemble`` int64 [G, T, 3] and ``swaps`` int64 [G, T - 1, 2]: proposed and accepted per pair of rungs."""
+        _in_place(np.float64, x=x, lnl=lnl)
+        _in_place(np.int64, accepted=accepted)
+        if x.ndim != 4:
+            raise ValueError('x [G, T, W, n], lnl [G, T, W], accepted [G, T, W]')
+        G, T, W, n = x.shape
+        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
+            3, cols, lo, hi, theta_fixed, x.reshape(G * T, W, n), lnl.reshape(G * T, W), accepted.reshape(G * T, W), step0, n_steps,
+            thin, keep_chain, a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
+        betas = np.ascontiguousarray(betas, dtype=np.float64)
+        streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if betas.shape != (T,) or streams.shape != (G, T) or (mock_rows is not None and mock_rows.shape != (G,)):
+            raise ValueError('betas [T], streams [G, T], mock_rows [G]')
+        per = np.zeros((G, T, 3), dtype=np.int64)
+        swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
+        mv = None
+        if moves is not None:
+            mv = C.byref(EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']),
+                                       float(moves['sigma']), float(moves['gamma_s']), int(moves.get('flags', 0)), 0))
+        i64 = C.POINTER(C.c_int64)
+        self._check(self.lib.vmx_ensemble_run_pt(
+            self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), *args[:6], int(swap_every), *args[6:], C.byref(stats),
+            per.ctypes.data_as(i64), mv, swaps.ctypes.data_as(i64)))
+        if keep_chain:
+            chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
+        return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, swaps=swaps)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
                    seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, clusters=None, cluster_flags=None,

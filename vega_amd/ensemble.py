@@ -38,8 +38,9 @@ def philox4x64_10(counter, key):
     c = np.array(counter, dtype=np.uint64)
     c0, c1, c2, c3 = (c[..., i].copy() for i in range(4))
     shape = c0.shape
-    k0 = np.full(shape, key[0], dtype=np.uint64)
-    k1 = np.full(shape, key[1], dtype=np.uint64)
+    # (a key word may be an array that broadcasts against the counters' shape: the blocks of many streams in one pass)
+    k0 = np.broadcast_to(np.asarray(key[0], dtype=np.uint64), shape).copy()
+    k1 = np.broadcast_to(np.asarray(key[1], dtype=np.uint64), shape).copy()
     with np.errstate(over='ignore'):
         for r in range(10):
             if r > 0:
@@ -248,12 +249,25 @@ def steps_moves(H, step0, n_steps, seed, stream, moves):
     return move_choice(words, *move_thresholds(moves['weights'])).reshape(n_steps, 2 * H)
 
 
-def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None):
+def half_step_blocks(H, step, h, seed, streams, last=0):
+    """The blocks of the walkers-in-half 0 .. H-1 of every stream of ``streams`` [E] at ``step``, half ``h``, in one pass:
+    [E, H, 4] uint64, entry e :func:`step_blocks` (``last`` 0) or :func:`move_blocks` (``last`` 1) of ``streams[e]``."""
+    streams = np.asarray(streams, dtype=np.uint64).reshape(-1)
+    ctr = np.zeros((streams.size, H, 4), dtype=np.uint64)
+    ctr[:, :, 0] = np.arange(H, dtype=np.uint64)
+    ctr[:, :, 1] = np.uint64(step)
+    ctr[:, :, 2] = np.uint64(h)
+    ctr[:, :, 3] = np.uint64(last)
+    return philox4x64_10(ctr, (int(seed), streams[:, None]))
+
+
+def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None, blocks=None):
     """Proposals of half ``h`` at ``step`` for the walkers ``x`` [W, n]: (y [W/2, n], inside [W/2], factor [W/2], blocks).
-    ``moves`` (:func:`resolve_moves`; None: the stretch move): every walker's move is drawn from the mixture."""
+    ``moves`` (:func:`resolve_moves`; None: the stretch move): every walker's move is drawn from the mixture.  ``blocks``
+    (None: drawn here): the half's (:func:`step_blocks`, :func:`move_blocks` or None) when the caller has them already."""
     W, n = x.shape
     H = W // 2
-    b = step_blocks(H, step, h, seed, stream)
+    b = step_blocks(H, step, h, seed, stream) if blocks is None else blocks[0]
     j = partner(b[:, 0], H).astype(np.int64)
     other = x[(1 - h) * H:(2 - h) * H]
     c = other[j]
@@ -264,7 +278,7 @@ def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None):
         factor = log_factor(n, z)
         some = True
     else:
-        m = move_blocks(H, step, h, seed, stream)
+        m = move_blocks(H, step, h, seed, stream) if blocks is None else blocks[1]
         move = move_choice(m[:, 0], *move_thresholds(moves['weights']))
         y, factor, some = np.empty((H, n)), np.zeros(H), np.ones(H, dtype=bool)
         k = np.flatnonzero(move == MOVE_STRETCH)
@@ -285,14 +299,157 @@ def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None):
     return y, inside, factor, b
 
 
-def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate, moves=None):
+# ---- parallel tempering: ladders and swaps (vmx_ensemble.h, the third part)
+PT_MAXT = 64
+
+
+def ladder_ok(betas):
+    """A ladder the sampler takes: betas[0] == 1, finite, strictly decreasing, none negative, at most PT_MAXT rungs."""
+    b = np.asarray(betas, dtype=np.float64)
+    if b.ndim != 1 or not 1 <= b.size <= PT_MAXT or b[0] != 1.0:
+        return False
+    return bool(np.all(np.isfinite(b)) and np.all(b >= 0.0) and np.all(np.diff(b) < 0.0))
+
+
+def default_ladder(ntemps, beta_min=None):
+    """The ladder of ``ntemps`` = T >= 2 rungs: geometric from 1 to ``beta_min`` (default 2**-(T - 2)) over the first T - 1 rungs,
+    then 0 - the rung that samples the box, which the stepping-stone evidence needs.  T = 2: (1, 0)."""
+    T = int(ntemps)
+    if not 2 <= T <= PT_MAXT:
+        raise ValueError(f'ntemps: 2 .. {PT_MAXT} rungs')
+    if T == 2:
+        return np.array([1.0, 0.0])
+    if beta_min is None:        # (the powers of two themselves, not their roots)
+        return np.append(2.0 ** -np.arange(T - 1, dtype=np.float64), 0.0)
+    beta_min = float(beta_min)
+    if not 0.0 < beta_min < 1.0:
+        raise ValueError('beta_min: between 0 and 1')
+    betas = np.append(beta_min ** (np.arange(T - 1) / (T - 2.0)), 0.0)
+    betas[0], betas[T - 2] = 1.0, beta_min
+    if not ladder_ok(betas):
+        raise ValueError('beta_min: the ladder must decrease strictly')
+    return betas
+
+
+def tempered(beta, lnl):
+    """A rung's view of a log-likelihood: what its Metropolis decision compares."""
+    return beta * np.asarray(lnl, dtype=np.float64)
+
+
+def accept_tempered(inside, ok, factor, beta, lnl_new, lnl_old, x2):
+    return accept(inside, ok, factor, tempered(beta, lnl_new), tempered(beta, lnl_old), x2)
+
+
+def shift_block(step, t, seed, stream=0):
+    """The block of the rotation of the pair (rung t - 1, rung t) at global step ``step`` (counter (0, step, t, 3)): [4] uint64."""
+    ctr = np.array([0, step, t, 3], dtype=np.uint64)
+    return philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def swap_blocks(W, step, t, seed, stream=0):
+    """The blocks of the pairs 0 .. W-1 of (rung t - 1, rung t) at global step ``step`` (counter (k, step, t, 2)): [W, 4] uint64."""
+    ctr = np.zeros((W, 4), dtype=np.uint64)
+    ctr[:, 0] = np.arange(W, dtype=np.uint64)
+    ctr[:, 1] = np.uint64(step)
+    ctr[:, 2] = np.uint64(t)
+    ctr[:, 3] = np.uint64(2)
+    return philox4x64_10(ctr, (int(seed), int(stream)))
+
+
+def swap_shift(w0, W):
+    """The rotation r in [0, W): walker k of the colder rung meets walker (k + r) mod W of the hotter one."""
+    return partner(w0, W)
+
+
+def swap_partner(k, r, W):
+    j = np.asarray(k, dtype=np.int64) + int(r)
+    return np.where(j >= W, j - W, j)
+
+
+def swap_accept(beta_cold, beta_hot, lnl_cold, lnl_hot, word):
+    db = beta_cold - beta_hot
+    dl = np.asarray(lnl_hot, dtype=np.float64) - np.asarray(lnl_cold, dtype=np.float64)
+    lhs = db * dl
+    return lhs > _log(u01(word))
+
+
+def swap_due(step, swap_every):
+    return swap_every > 0 and (step + 1) % swap_every == 0
+
+
+def swap_sweep(x, lnl, betas, step, seed, stream, swaps):
+    """The swap sweep of one ladder after global step ``step``: ``x`` [T, W, n] and ``lnl`` [T, W] (updated in place), pairs of
+    rungs from the hottest down, under the key (seed, ``stream``: the stream of rung 0); ``swaps`` [T - 1, 2] += (proposed,
+    accepted)."""
+    T, W = lnl.shape
+    k = np.arange(W)
+    # the blocks of all pairs of rungs in one pass: counters (k, step, t, 2) and (0, step, t, 3), t = 1 .. T - 1
+    ctr = np.zeros((T - 1, W + 1, 4), dtype=np.uint64)
+    ctr[:, :W, 0] = np.arange(W, dtype=np.uint64)
+    ctr[:, :, 1] = np.uint64(step)
+    ctr[:, :, 2] = np.arange(1, T, dtype=np.uint64)[:, None]
+    ctr[:, :W, 3], ctr[:, W, 3] = np.uint64(2), np.uint64(3)
+    words = philox4x64_10(ctr, (int(seed), int(stream)))[:, :, 0]
+    for t in range(T - 1, 0, -1):
+        r = int(swap_shift(words[t - 1, W], W))
+        j = swap_partner(k, r, W)
+        word = words[t - 1, :W]
+        take = swap_accept(betas[t - 1], betas[t], lnl[t - 1], lnl[t, j], word)
+        kk, jj = k[take], j[take]
+        x[t - 1, kk], x[t, jj] = x[t, jj].copy(), x[t - 1, kk].copy()
+        lnl[t - 1, kk], lnl[t, jj] = lnl[t, jj].copy(), lnl[t - 1, kk].copy()
+        swaps[t - 1] += (W, int(take.sum()))
+
+
+def python_steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm, evaluate,
+                    moves=None):
+    """``n_steps`` steps of G temperature ladders of T rungs in NumPy - what vmx_ensemble_run_pt runs: the state ``x``
+    [G, T, W, n], ``lnl`` [G, T, W] (untempered), ``accepted`` [G, T, W] (updated in place), ``betas`` [T], ``streams`` [G, T].
+    The steps are :func:`python_steps_many`'s over the G T ensembles with the rung's beta in the decision, run up to every step
+    after which a sweep is due (:func:`swap_due`: the global step counts); the sweep (:func:`swap_sweep`) comes before that step's
+    chain row.  ``evaluate(rows, h)`` as there, for the G T W/2 rows of a half.  Returns (chain [G, T, rows, W, n], chain_lnl
+    [G, T, rows, W], stats, per_ensemble [G, T, 3], swaps [G, T - 1, 2])."""
+    G, T, W, n = x.shape
+    E = G * T
+    xe, le, ae = x.reshape(E, W, n), lnl.reshape(E, W), accepted.reshape(E, W)
+    betas = np.asarray(betas, dtype=np.float64)
+    flat_streams = np.asarray(streams, dtype=np.uint64).reshape(E)
+    rung_beta = np.tile(betas, G)
+    rows = (step0 + n_steps) // thin - step0 // thin
+    chain, chain_lnl = np.empty((E, rows, W, n)), np.empty((E, rows, W))
+    per = np.zeros((E, 3), dtype=np.int64)
+    swaps = np.zeros((G, T - 1, 2), dtype=np.int64)
+    s, end = step0, step0 + n_steps
+    while s < end:
+        # up to and with the next step a sweep follows (or the end); every step's row, of which the thinning picks
+        stop = end if swap_every <= 0 or T < 2 else min(end, (s // swap_every + 1) * swap_every)
+        part, part_lnl, _, p = python_steps_many(xe, le, ae, s, stop - s, 1, a, seed, flat_streams, lo, hi, log_norm, evaluate, moves,
+                                                 betas=rung_beta)
+        per += p
+        if T > 1 and swap_due(stop - 1, swap_every):
+            for g in range(G):
+                swap_sweep(x[g], lnl[g], betas, stop - 1, seed, int(flat_streams[g * T]), swaps[g])
+            part[:, -1], part_lnl[:, -1] = xe, le
+        for q in range(s, stop):
+            if (q + 1) % thin == 0:
+                r = (q + 1) // thin - step0 // thin - 1
+                chain[:, r], chain_lnl[:, r] = part[:, q - s], part_lnl[:, q - s]
+        s = stop
+    st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
+              rejected_failed_model=int(per[:, 2].sum()), swaps_proposed=int(swaps[:, :, 0].sum()),
+              swaps_accepted=int(swaps[:, :, 1].sum()))
+    return (chain.reshape(G, T, rows, W, n), chain_lnl.reshape(G, T, rows, W), st, per.reshape(G, T, 3), swaps)
+
+
+def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate, moves=None, betas=None):
     """``n_steps`` steps of E independent ensembles advanced together, in NumPy: the state ``x`` [E, W, n], ``lnl`` [E, W],
     ``accepted`` [E, W] (updated in place), ensemble e on the Philox stream ``streams[e]``.  Every half-step is decided ensemble by
     ensemble; only the likelihood is joined: ``evaluate(rows, h)`` -> (chi2 [E W/2], status [E W/2]) for the E W/2 rows
     [E W/2, n] of the half, ensemble e's at [e W/2, (e + 1) W/2) - the rows the device driver hands the engine (a proposal outside
     the box is replaced by the walker's own position).  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats,
     per_ensemble [E, 3]: accepted, rejected outside the box, rejected for a failed model).  ``moves`` (:func:`resolve_moves`; None:
-    the stretch move): the mixture every walker's move is drawn from."""
+    the stretch move): the mixture every walker's move is drawn from.  ``betas`` [E] (None: 1, the run of ever): ensemble e decides
+    at the inverse temperature ``betas[e]`` (:func:`accept_tempered`; the stored lnl stays untempered)."""
     E, W, n = x.shape
     H = W // 2
     rows = (step0 + n_steps) // thin - step0 // thin
@@ -301,14 +458,20 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     for s in range(step0, step0 + n_steps):
         for h in (0, 1):
             mine = slice(h * H, (h + 1) * H)
-            props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi, moves) for e in range(E)]
+            b_all = half_step_blocks(H, s, h, seed, streams)          # (the Philox blocks of all ensembles in one pass)
+            m_all = None if moves is None else half_step_blocks(H, s, h, seed, streams, last=1)
+            props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi, moves,
+                                         blocks=(b_all[e], None if m_all is None else m_all[e])) for e in range(E)]
             chi2, status = evaluate(np.concatenate([np.where(inside[:, None], y, x[e, mine])
                                                     for e, (y, inside, _, _) in enumerate(props)]), h)
             for e, (y, inside, factor, b) in enumerate(props):
                 c2, st_e = chi2[e * H:(e + 1) * H], status[e * H:(e + 1) * H]
                 ok = model_ok(st_e, c2)
                 lnl_new = log_lik(log_norm, c2)
-                acc = accept(inside, ok, factor, lnl_new, lnl[e, mine], b[:, 2])
+                if betas is None:
+                    acc = accept(inside, ok, factor, lnl_new, lnl[e, mine], b[:, 2])
+                else:
+                    acc = accept_tempered(inside, ok, factor, float(betas[e]), lnl_new, lnl[e, mine], b[:, 2])
                 x[e, mine][acc] = y[acc]
                 lnl[e, mine][acc] = lnl_new[acc]
                 accepted[e, mine] += acc
@@ -1040,6 +1203,240 @@ def _read_only(*args, **kwargs):
     raise RuntimeError('a member of an EnsembleSet is read-only: advance the set')
 
 
+# ------------------------------------------------------------------ parallel tempering: ladders of ensembles, and the evidence
+def _ends_at_zero(betas):
+    if not (len(betas) >= 2 and betas[-1] == 0.0):
+        raise ValueError('the evidence needs a ladder whose last beta is 0 (the rung that samples the box)')
+
+
+def stepping_stone_evidence(betas, lnl):
+    """The stepping-stone estimator (Xie et al. 2011) of log Z over a uniform prior on the box: log Z = sum over t >= 1 of
+    log <exp((beta[t-1] - beta[t]) lnL)> over the rows of rung t, each mean with a max-shift.  ``lnl`` [T, rows, W]: the
+    untempered lnL records of the rungs.  Returns (log Z, err): per rung the variance of the ratio over an effective sample size
+    N / tau, tau the :func:`integrated_time` of the ratio's walker series (at least 1), the rungs added in quadrature.  Raises
+    ValueError unless the last beta is 0."""
+    betas = np.asarray(betas, dtype=np.float64)
+    _ends_at_zero(betas)
+    lnl = np.asarray(lnl, dtype=np.float64)
+    if lnl.ndim != 3 or lnl.shape[0] != betas.size or lnl.shape[1] < 2:
+        raise ValueError('lnl [T, rows, W] with at least two rows')
+    log_z, var = 0.0, 0.0
+    for t in range(1, betas.size):
+        e = (betas[t - 1] - betas[t]) * lnl[t]
+        top = e.max()
+        ratio = np.exp(e - top)
+        mean = ratio.mean()
+        log_z += top + math.log(mean)
+        tau = max(1.0, float(integrated_time(ratio)[0])) if np.ptp(ratio) > 0.0 else 1.0
+        var += ratio.var(ddof=1) / mean**2 * tau / ratio.size
+    return float(log_z), math.sqrt(var)
+
+
+def _trapezoid(b, y):
+    # (the ladder descends: the integral from beta = 0 up to 1)
+    return float(-np.sum(np.diff(b) * 0.5 * (y[1:] + y[:-1])))
+
+
+def thermodynamic_integration(betas, mean_lnl):
+    """Thermodynamic integration: log Z = the integral of <lnL>_beta from 0 to 1 by the trapezoid rule over the ladder,
+    ``mean_lnl`` [T] the rungs' means.  Returns (log Z, err) with ptemcee's error: the difference to the same rule on every
+    second rung (rungs 0, 2, 4, ... and the last one) - the discretisation, not the sampling noise.  Raises ValueError unless the
+    last beta is 0."""
+    betas = np.asarray(betas, dtype=np.float64)
+    _ends_at_zero(betas)
+    y = np.asarray(mean_lnl, dtype=np.float64)
+    if y.shape != betas.shape:
+        raise ValueError('mean_lnl [T]')
+    keep = np.unique(np.append(np.arange(0, betas.size, 2), betas.size - 1))
+    log_z = _trapezoid(betas, y)
+    return log_z, abs(log_z - _trapezoid(betas[keep], y[keep]))
+
+
+class TemperedEnsemble(EnsembleSet):
+    """Parallel tempering (ptemcee's answer to separated modes, and an evidence): ``ladders`` = G temperature ladders of T rungs
+    each, a rung an ensemble of ``walkers`` walkers that decides at its beta (``betas`` [T]: 1 > ... >= 0, or ``ntemps`` = T with
+    ``beta_min``: :func:`default_ladder`), with a swap sweep between adjacent rungs after every ``swap_every``-th step (0: none).
+    An :class:`EnsembleSet` of G T ensembles - ladder g owns g T .. g T + T - 1, rung 0 the cold one - advanced in one device run
+    (``'device'``: vmx_ensemble_run_pt; ``'python'``: :func:`python_steps_pt`, the same chain bit for bit).  ``streams`` [G]
+    (default ``range(G)``): ladder stream sigma puts rung t on the Philox stream 64 sigma + t; [G, T]: every rung's own.
+    ``mock_rows`` [G]: the mock every ladder is compared with.  The other arguments are :class:`EnsembleSet`'s.  With swaps a
+    walker's recorded position also changes when it is exchanged, so ``stats['moves']`` is not kept.
+
+    ``get_chain`` / ``get_log_lik`` read one rung (default the cold one, which ``write`` puts into the getdist chain);
+    ``swap_fraction`` [G, T - 1] is the accepted fraction of the swaps between rungs t and t + 1; ``log_evidence`` is the
+    stepping-stone or thermodynamic-integration evidence over the box, with the ``log_norm`` of the other samplers."""
+
+    def __init__(self, vega, walkers, ntemps=None, betas=None, swap_every=1, ladders=1, streams=None, mock_rows=None, beta_min=None,
+                 a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, chunk=0, lanes=0, const_hint=-1,
+                 moves=None, gamma0=None, sigma=None, gamma_s=None):
+        if (ntemps is None) == (betas is None):
+            raise ValueError('ntemps or betas: one of the two')
+        if betas is None:
+            self.betas = default_ladder(ntemps, beta_min)
+        else:
+            if beta_min is not None:
+                raise ValueError('beta_min belongs to ntemps: betas are given')
+            self.betas = np.array(betas, dtype=np.float64)
+            if not ladder_ok(self.betas):
+                raise ValueError(f'betas: from 1, strictly decreasing, none negative, at most {PT_MAXT}')
+        self.T, self.G = int(self.betas.size), int(ladders)
+        self.swap_every = int(swap_every)
+        if self.G < 1 or self.swap_every < 0:
+            raise ValueError('ladders: at least one; swap_every: 0 (no swaps) or more')
+        if streams is None:
+            streams = np.arange(self.G)
+        streams = np.array(streams, dtype=np.uint64)
+        if streams.shape == (self.G,):
+            streams = np.uint64(64) * streams[:, None] + np.arange(self.T, dtype=np.uint64)[None, :]
+        if streams.shape != (self.G, self.T):
+            raise ValueError(f'streams: one for each of the {self.G} ladders, or [{self.G}, {self.T}]')
+        self.ladder_mock_rows = None if mock_rows is None else np.array(mock_rows, dtype=np.int32)
+        if self.ladder_mock_rows is not None and self.ladder_mock_rows.shape != (self.G,):
+            raise ValueError(f'mock_rows: one entry for each of the {self.G} ladders')
+        super().__init__(vega, self.G * self.T, walkers, streams=streams.reshape(-1),
+                         mock_rows=None if mock_rows is None else np.repeat(self.ladder_mock_rows, self.T), a=a, seed=seed, thin=thin,
+                         driver=driver, segment=segment, sample_params=sample_params, chunk=chunk, lanes=lanes, const_hint=const_hint,
+                         moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s)
+
+    def reset(self):
+        super().reset()
+        self.swaps = np.zeros((self.G, self.T - 1, 2), dtype=np.int64)
+        self.stats.update(swaps_proposed=0, swaps_accepted=0)
+        if self.swap_every > 0:
+            self.stats.pop('moves', None)
+
+    def _prepare(self, start, init_scale):
+        theta = super()._prepare(start, init_scale)
+        if self.driver == 'device' and not hasattr(self.vega.engine, 'ensemble_run_pt'):
+            self.driver = 'python'
+        return theta
+
+    # ---- run
+    def _shaped(self):
+        lead = (self.G, self.T, self.W)
+        return self.x.reshape(lead + (self.n,)), self.lnl.reshape(lead), self.accepted.reshape(lead)
+
+    def _took(self, chain, chain_lnl, st, per, swaps):
+        self.swaps += swaps
+        st = dict(st, swaps_proposed=int(swaps[:, :, 0].sum()), swaps_accepted=int(swaps[:, :, 1].sum()))
+        return chain.reshape((self.E,) + chain.shape[2:]), chain_lnl.reshape((self.E,) + chain_lnl.shape[2:]), st, per.reshape(self.E, 3)
+
+    def _segment_device(self, theta, k):
+        self.vega._sync_monte_carlo()
+        x, lnl, accepted = self._shaped()
+        chain, chain_lnl, st = self.vega.engine.ensemble_run_pt(
+            self.cols, self.lo, self.hi, theta, x, lnl, accepted, self.betas, self.streams.reshape(self.G, self.T), self.step, k,
+            swap_every=self.swap_every, mock_rows=self.ladder_mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(),
+            seed=self.seed, const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, **self._moves_arg())
+        return self._took(chain, chain_lnl, st, st.pop('per_ensemble'), st.pop('swaps'))
+
+    def _python_steps(self, k, chi2):
+        row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, self.W // 2)
+        x, lnl, accepted = self._shaped()
+        return self._took(*python_steps_pt(x, lnl, accepted, self.step, k, self.thin, self.swap_every, self.a, self.seed, self.betas,
+                                           self.streams.reshape(self.G, self.T), self.lo, self.hi, self.log_norm(),
+                                           lambda rows_x, h: chi2(rows_x, row_mock), self.moves))
+
+    # ---- results
+    def _index(self, rung, ladder):
+        if not (0 <= int(rung) < self.T and 0 <= int(ladder) < self.G):
+            raise IndexError(f'rung 0 .. {self.T - 1} of ladder 0 .. {self.G - 1}')
+        return int(ladder) * self.T + int(rung)
+
+    def _rungs(self, arr, rung, ladder):
+        if rung is None:
+            arr = arr.reshape((self.G, self.T) + arr.shape[1:])
+            return arr
+        return arr[self._index(rung, ladder)]
+
+    def get_chain(self, discard=0, thin=1, flat=False, *, rung=0, ladder=0):
+        """Recorded positions of rung ``rung`` (0: the cold one) of ladder ``ladder``, [rows, W, n] (``flat``: [rows W, n]);
+        ``rung=None``: of every rung, [G, T, rows, W, n]."""
+        return self._rungs(super().get_chain(discard=discard, thin=thin, flat=flat), rung, ladder)
+
+    def get_log_lik(self, discard=0, thin=1, flat=False, *, rung=0, ladder=0):
+        """The untempered lnL of :meth:`get_chain`'s rows."""
+        return self._rungs(super().get_log_lik(discard=discard, thin=thin, flat=flat), rung, ladder)
+
+    def get_autocorr_time(self, discard=0, thin=1, c=5, *, rung=0, ladder=0):
+        return integrated_time(self.get_chain(discard=discard, thin=thin, rung=rung, ladder=ladder), c=c)
+
+    def rung(self, t, ladder=0):
+        """Rung ``t`` of ladder ``ladder`` as a sampler that has run, read-only like :meth:`EnsembleSet.member`."""
+        m = self.member(self._index(t, ladder))
+        if self.swap_every > 0:
+            m.stats.pop('moves', None)
+        m.beta = float(self.betas[int(t)])
+        return m
+
+    @property
+    def recorded_rows(self):
+        return sum(part.shape[1] for part in self._chain_lnl)
+
+    @property
+    def swap_fraction(self):
+        """The accepted fraction of the swaps proposed between the rungs t and t + 1, [G, T - 1] (nan before the first sweep)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self.swaps[:, :, 1] / self.swaps[:, :, 0]
+
+    def log_evidence(self, method='ss', discard=None, ladder=0):
+        """(log Z, err) over the uniform prior on the box, from the rungs' lnL records past the first ``discard`` recorded rows
+        (None: a quarter of them): ``'ss'`` - :func:`stepping_stone_evidence` - or ``'ti'`` - :func:`thermodynamic_integration`.
+        ValueError unless the ladder ends at beta = 0."""
+        _ends_at_zero(self.betas)
+        rows = super().get_log_lik().shape[1]
+        discard = rows // 4 if discard is None else int(discard)
+        lnl = self.get_log_lik(discard=discard, rung=None)[int(ladder)]
+        if method == 'ss':
+            return stepping_stone_evidence(self.betas, lnl)
+        if method == 'ti':
+            return thermodynamic_integration(self.betas, lnl.mean(axis=(1, 2)))
+        raise ValueError("method: 'ss' (stepping stones) or 'ti' (thermodynamic integration)")
+
+    def write(self, path, name, derived=False, print_func=print):
+        """getdist's plain-text chain of the cold rung - ``name.txt`` and ``name.paramnames`` (``name_ladder<g>`` with several
+        ladders) - and, with a ladder that ends at beta = 0 and at least two recorded rows, ``name.stats`` with the evidence, as the
+        nested and SMC runs write it."""
+        out = []
+        for g in range(self.G):
+            nm = name if self.G == 1 else f'{name}_ladder{g}'
+            files = tuple(self.rung(0, g).write(path, nm, derived=derived, print_func=print_func))
+            if self.betas[-1] == 0.0 and self.T >= 2 and self.recorded_rows >= 2:
+                files += (write_pt_stats(self, path, nm, g),)
+            elif self.betas[-1] == 0.0 and g == 0:
+                print_func('fewer than two recorded rows: no evidence, no ' + f'{nm}.stats')
+            out.append(files)
+        return out[0] if self.G == 1 else out
+
+
+def write_pt_stats(run, path, name, ladder=0):
+    """``name.stats`` of a :class:`TemperedEnsemble`'s ladder: both evidences, the ladder and its swap fractions."""
+    log_z, err = run.log_evidence('ss', ladder=ladder)
+    ti, ti_err = run.log_evidence('ti', ladder=ladder)
+    stats = Path(path) / f'{name}.stats'
+    with open(stats, 'w') as f:
+        f.write(f'log(Z) = {log_z!r}\nlog(Z) error = {err!r}\n')
+        f.write(f'log(Z) thermodynamic = {ti!r}\nlog(Z) thermodynamic error = {ti_err!r}\n')
+        f.write(f'steps = {run.step}\nwalkers = {run.W}\nswap_every = {run.swap_every}\nseed = {run.seed}\n')
+        f.write(f'likelihood evaluations = {run.step * run.W * run.T}\n')
+        f.write('beta = ' + ' '.join(repr(float(b)) for b in run.betas) + '\n')
+        f.write('swap fraction = ' + ' '.join(repr(float(v)) for v in run.swap_fraction[ladder]) + '\n')
+    return stats
+
+
+def read_pt_stats(path):
+    """``name.stats`` of :func:`write_pt_stats` back as a dict (floats for the evidence lines, lists of floats for ``beta`` and
+    ``swap fraction``, ints for the counts)."""
+    out = {}
+    for line in Path(path).read_text().splitlines():
+        key, _, val = line.partition(' = ')
+        if key in ('beta', 'swap fraction'):
+            out[key] = [float(v) for v in val.split()]
+        else:
+            out[key] = float(val) if key.startswith('log(Z)') else int(val)
+    return out
+
+
 # ------------------------------------------------------------------ the config switch (bin/run_vega_mpi.py for one process)
 _ENSEMBLE_DEFAULTS = dict(sampler='Ensemble', name='ensemble', walkers=None, steps=1000, seed=0, a=2.0, thin=1, init='ball', init_scale=1.0,
                           driver='device')
@@ -1080,8 +1477,9 @@ def sampler_settings(main_config, sample_params):
     parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver} and, when the section states it,
     ``moves`` with ``gamma0`` / ``de_sigma`` / ``snooker_gamma`` (:func:`_parse_moves`: a mixture of the stretch, DE and snooker
     moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
-    they were) and ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
-    :mod:`vega_amd.replicas`); with ``sampler = Nested`` the ``[Nested]`` settings instead
+    they were), ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
+    :mod:`vega_amd.replicas`) and ``ntemps`` with ``beta_min`` / ``swap_every`` (:func:`_parse_tempering`: parallel tempering);
+    with ``sampler = Nested`` the ``[Nested]`` settings instead
     (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
     run = control.getboolean('run_sampler', False) if hasattr(control, 'getboolean') else False
@@ -1124,7 +1522,39 @@ def sampler_settings(main_config, sample_params):
             out['together'] = sec.getboolean('together')
         except ValueError:
             raise ValueError('[Ensemble] together: True or False') from None
+    _parse_tempering(sec, out)
     return out
+
+
+def _parse_tempering(sec, out):
+    """``ntemps = T`` of ``[Ensemble]`` (T >= 2 rungs: parallel tempering, :class:`TemperedEnsemble` on
+    :func:`default_ladder`), with ``beta_min`` and ``swap_every`` (default 1) when stated, into the keys of the same names.
+    Without ``ntemps`` nothing is added.  Not combined with ``mocks``, ``together`` or ``replicas > 1``."""
+    if 'ntemps' not in sec:
+        stray = [key for key in ('beta_min', 'swap_every') if key in sec]
+        if stray:
+            raise ValueError(f'[Ensemble] {", ".join(stray)}: settings of a temperature ladder, but no ntemps')
+        return
+    try:
+        out['ntemps'] = sec.getint('ntemps')
+        if 'beta_min' in sec:
+            out['beta_min'] = sec.getfloat('beta_min')
+        out['swap_every'] = sec.getint('swap_every', 1)
+    except ValueError:
+        raise ValueError('[Ensemble] ntemps, swap_every: whole numbers; beta_min: a number') from None
+    try:
+        default_ladder(out['ntemps'], out.get('beta_min'))
+    except ValueError as err:
+        raise ValueError(f'[Ensemble] {err}') from None
+    if out['swap_every'] < 0:
+        raise ValueError('[Ensemble] swap_every: 0 (no swaps) or more')
+    if out['steps'] // out['thin'] < 2:
+        raise ValueError('[Ensemble] ntemps: the evidence needs at least two recorded rows, steps // thin >= 2')
+    for key in ('mocks', 'together'):
+        if key in out:
+            raise ValueError(f'[Ensemble] ntemps and {key} do not combine yet')
+    if out.get('replicas', 1) > 1:
+        raise ValueError('[Ensemble] ntemps and replicas > 1 do not combine yet')
 
 
 _MOVE_KEYS = (('gamma0', 'gamma0'), ('de_sigma', 'sigma'), ('snooker_gamma', 'gamma_s'))
@@ -1209,6 +1639,10 @@ def build_sampler(vega, cfg, sample_params, stream=0):
         return SMCSampler(vega, particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'], seed=cfg['seed'],
                           driver=cfg['driver'], max_stages=cfg['max_stages'], sample_params=sample_params, stream=stream,
                           **{key: cfg[key] for key in ('n_total', 'recycle') if key in cfg})
+    if 'ntemps' in cfg:
+        return TemperedEnsemble(vega, cfg['walkers'], ntemps=cfg['ntemps'], beta_min=cfg.get('beta_min'), swap_every=cfg['swap_every'],
+                                streams=[stream], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
+                                sample_params=sample_params, **moves_arguments(cfg))
     return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
                            sample_params=sample_params, stream=stream, **moves_arguments(cfg))
 
