@@ -160,7 +160,8 @@ const char* vmx_last_error(void);
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
  * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep,
- * 23 vmx_ensemble_moves; 22 is vacant and answers -1, as every index that names no struct): lets a foreign binding verify its struct layout at load time. */
+ * 23 vmx_ensemble_moves, 24 vmx_ensemble_adapt; 22 is vacant and answers -1, as every index that names no struct): lets a foreign
+ * binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
 int vmx_create(vmx_engine** out, int device);
@@ -563,6 +564,42 @@ int vmx_ensemble_run_pt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G,
                         const vmx_ensemble_options* opt,
                         vmx_ensemble_stats* stats, int64_t* per_ensemble,
                         const vmx_ensemble_moves* moves, int64_t* swaps);
+/* Adaptive ladders (Vousden, Farr & Mandel 2016; ptemcee's adaptation_lag / adaptation_time): the run above with a ladder of its
+ * own for every one of the G ladders, whose intermediate betas move after every swap sweep so that all adjacent pairs of rungs come
+ * to swap at the same rate; the adjustment decays, so that the chain becomes a proper one.  The swap kernel is k_ens_swap_adapt
+ * beside k_ens_swap - the same grid, pairs, rotation, swap rule and counters: it gathers the sweep's accepted swaps per pair of
+ * rungs in LDS, and behind the last pair one thread moves the ladder (at most T - 2 exponentials, the pinned pexp) before the
+ * half-step kernel that follows on the stream reads it.  No host wait and no likelihood row.  The rule and its guard are pinned in
+ * vega_amd/csrc/vmx_ensemble.h, the fourth part:
+ *     A_t = accepted_t / W of this sweep for the pair (t, t + 1); time = (s + 1) / swap_every - 1, the sweeps before this one;
+ *     kappa = (lag / (time + lag)) / adapt->time; for i = 0 .. T - 3: the gap 1 / beta[i + 1] - 1 / beta[i] of the old ladder is
+ *     multiplied by pexp(kappa (A_i - A_{i+1})) and the new 1 / beta[i + 1] is 1 / beta[0] plus the gaps so far.
+ * betas[.][0] = 1 and betas[.][T - 1] never move.  A new ladder that is not one the sampler takes (not finite, not strictly
+ * decreasing - a positive last beta can be crossed) is dropped: the old one stays for that sweep and adapt_skipped[g] counts it.
+ *   betas     [G][T], in and out: every ladder as vmx_ensemble_run_pt takes one; at exit the ladders after the call's last sweep
+ *   adapt     lag, time: ptemcee's adaptation_lag and adaptation_time, in sweeps, finite and positive (its defaults 10000, 100);
+ *             adapt_until: the sweep after global step s adapts iff s < adapt_until (negative: always; 0: never - the chain
+ *             of vmx_ensemble_run_pt for equal ladders); flags, reserved: 0
+ *   beta_hist [sweeps][G][T] (NULL: not kept), sweeps = (step0 + n_steps) / swap_every - step0 / swap_every: the ladders after
+ *             every sweep of this call, adapting or not
+ *   adapt_skipped  [G] (NULL: not wanted): the sweeps of this call whose adjustment the guard dropped
+ *   everything else as for vmx_ensemble_run_pt.  time depends on the global step alone: a run cut into calls adapts identically.
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever vmx_ensemble_run_pt refuses; T < 3;
+ * swap_every < 1; adapt NULL; lag or time not finite and positive; flags or reserved not 0; any of the G ladders not in order. */
+typedef struct {
+    double lag, time;
+    int64_t adapt_until;
+    uint32_t flags, reserved;
+} vmx_ensemble_adapt;
+int vmx_ensemble_run_pt_adapt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G, int32_t T, int32_t W,
+                              double* betas, const uint64_t* streams, const int32_t* mock_row,
+                              double* x, double* lnL, int64_t* accepted,
+                              int64_t step0, int32_t n_steps, int32_t thin, int32_t swap_every,
+                              double* chain, double* chain_lnL,
+                              const vmx_ensemble_options* opt,
+                              vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                              const vmx_ensemble_moves* moves, int64_t* swaps,
+                              const vmx_ensemble_adapt* adapt, double* beta_hist, int64_t* adapt_skipped);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

@@ -225,8 +225,10 @@ struct EnsWorkspace {
     DevBuf<int32_t> inside, col;
     DevBuf<int32_t> mock;               // the mock row of every engine row [E H], written once per call that names mocks
     DevBuf<uint64_t> streams;           // the ensembles' Philox streams [E]
-    DevBuf<double> beta;                // parallel tempering: the ladder [T] ...
+    DevBuf<double> beta;                // parallel tempering: the ladder [T] (adaptive ladders: [G][T]) ...
     DevBuf<int64_t> swaps;              // ... and the call's swap counters [G][T - 1][2]
+    DevBuf<double> beta_hist;           // adaptive ladders: the ladders after every sweep of the call [sweeps][G][T] ...
+    DevBuf<int64_t> adapt_skipped;      // ... and the sweeps whose adjustment the guard dropped [G]
 };
 
 struct EnsDev {
@@ -404,9 +406,10 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMov
 // Parallel tempering (vmx_ensemble_run_pt; vmx_ensemble.h, "parallel tempering"): G ladders of T rungs are G T ensembles, ensemble
 // g T + t on the rung of beta[t].  What the kernels read beside EnsDev: the ladder and the call's swap counters.
 struct EnsPtDev {
-    const double* beta;                 // [T]
+    const double* beta;                 // [T], or [G][T] with the ladder stride T
     int64_t* swaps;                     // [G][T - 1][2]: proposed, accepted
     int32_t T;
+    int32_t stride;                     // ladder g reads beta + g stride: 0, the ladder all share; T, a ladder of its own
 };
 enum { ENS_PT_DECIDE = 1, ENS_PT_RECORD = 2, ENS_PT_PROPOSE = 4 };
 
@@ -421,7 +424,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesD
     const int W = D.W, H = W / 2, n = D.n;
     const size_t e = blockIdx.x;
     const uint64_t stream = D.streams[e];
-    const double beta = Pt.beta[e % (size_t)Pt.T];
+    const double beta = Pt.beta[(e / (size_t)Pt.T) * (size_t)Pt.stride + e % (size_t)Pt.T];
     double* const x = D.x + e * W * n;
     double* const lnl = D.lnl + e * W;
     int64_t* const acc = D.acc + e * W;
@@ -532,6 +535,74 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_swap(EnsDev D, EnsPtDev Pt,
         if (took) atomicAdd((unsigned long long*)&swaps[2 * (t - 1) + 1], took);
         if (threadIdx.x == 0) swaps[2 * (t - 1)] += W;
         __syncthreads();        // (rung t - 1 is the hot rung of the next pair)
+    }
+}
+
+// Adaptive ladders (vmx_ensemble_run_pt_adapt; vmx_ensemble.h, the fourth part): what k_ens_swap_adapt reads beside EnsPtDev
+struct EnsAdaptDev {
+    double* beta;                       // [G][T]: the ladders, which the kernel moves (Pt.beta reads the same array)
+    double* hist;                       // [sweeps of the call][G][T]: the ladders after every sweep (nullptr: not kept)
+    int64_t* skipped;                   // [G]: the sweeps whose adjustment the guard dropped
+    double lag, tau;
+    int64_t sweep0;                     // the sweeps before the call's first step
+    int32_t swap_every, G;
+};
+
+// k_ens_swap over ladders of their own that move: the same grid - one work-group per ladder - the same pairs, rotation, swap rule
+// and counters.  The ladder is read into LDS once, so that every pair of the sweep decides with the old ladder; the sweep's accepted
+// swaps per pair of rungs are gathered in LDS by integer atomics (order-independent; W may exceed the block).  After the barrier
+// behind the last pair one thread runs ladder_adjust - at most T - 2 = 62 exponentials - and writes the ladder, the history row and
+// the guard's count; the k_ens_half_pt(record | propose) that follows on the stream decides with the new betas.  `adapt` 0: a
+// sweep past adapt_until, which moves nothing.
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_swap_adapt(EnsDev D, EnsPtDev Pt, EnsAdaptDev A, int64_t s, int adapt)
+{
+    __shared__ double beta[vmx_ens::PT_MAXT];
+    __shared__ unsigned int took_of[vmx_ens::PT_MAXT];
+    const int W = D.W, n = D.n, T = Pt.T;
+    const size_t g = blockIdx.x;
+    const uint64_t stream = D.streams[g * T];
+    int64_t* const swaps = Pt.swaps + g * (size_t)(T - 1) * 2;
+    double* const ladder = A.beta + g * (size_t)T;
+    for (int t = threadIdx.x; t < T; t += blockDim.x) { beta[t] = ladder[t]; took_of[t] = 0u; }
+    __syncthreads();
+    for (int t = T - 1; t >= 1; --t) {
+        const size_t cold = g * T + (size_t)(t - 1), hot = cold + 1;
+        double* const xc = D.x + cold * W * n;
+        double* const xh = D.x + hot * W * n;
+        double* const lc = D.lnl + cold * W;
+        double* const lh = D.lnl + hot * W;
+        const double bc = beta[t - 1], bh = beta[t];
+        const int64_t r = vmx_ens::swap_shift(vmx_ens::shift_block(s, t, D.seed, stream).w[0], W);
+        unsigned int took = 0;
+        for (int k = threadIdx.x; k < W; k += blockDim.x) {
+            const int64_t j = vmx_ens::swap_partner(k, r, W);
+            const vmx_ens::Block b = vmx_ens::swap_block(k, s, t, D.seed, stream);
+            const double l_cold = lc[k], l_hot = lh[j];
+            if (vmx_ens::swap_accept(bc, bh, l_cold, l_hot, b.w[0])) {
+                double* pc = xc + (size_t)k * n;
+                double* ph = xh + (size_t)j * n;
+                for (int d = 0; d < n; ++d) { const double v = pc[d]; pc[d] = ph[d]; ph[d] = v; }
+                lc[k] = l_hot;
+                lh[j] = l_cold;
+                took += 1;
+            }
+        }
+        if (took) atomicAdd(&took_of[t - 1], took);
+        __syncthreads();        // (rung t - 1 is the hot rung of the next pair; the pair's count is whole)
+        if (threadIdx.x == 0) {
+            swaps[2 * (t - 1)] += W;
+            swaps[2 * (t - 1) + 1] += (int64_t)took_of[t - 1];
+        }
+    }
+    if (threadIdx.x != 0) return;
+    const int64_t time = vmx_ens::sweep_time(s, A.swap_every);
+    if (adapt) {
+        if (!vmx_ens::ladder_adjust(beta, took_of, T, (int64_t)W, time, A.lag, A.tau)) A.skipped[g] += 1;
+        for (int t = 1; t + 1 < T; ++t) ladder[t] = beta[t];
+    }
+    if (A.hist) {
+        double* const row = A.hist + ((size_t)(time - A.sweep0) * (size_t)A.G + g) * (size_t)T;
+        for (int t = 0; t < T; ++t) row[t] = beta[t];
     }
 }
 
@@ -2145,6 +2216,7 @@ int vmx_struct_size(int32_t which)
         case 20: return (int)sizeof(vmx_nested_set_phantoms);
         case 21: return (int)sizeof(vmx_smc_keep);
         case 23: return (int)sizeof(vmx_ensemble_moves);           // (22 stays vacant: see vegamx.h)
+        case 24: return (int)sizeof(vmx_ensemble_adapt);
         default: return -1;
     }
 }
@@ -5075,7 +5147,12 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
 
 // ---- posterior sampling where the walkers live (vmx_ensemble.h)
 // what makes a run of E = G T ensembles G ladders of T rungs (vmx_ensemble_run_pt): the ladder, the sweeps, where the counts go
-struct EnsPtRun { int32_t G, T; const double* betas; int32_t swap_every; int64_t* swaps; };
+// (betas [T]; with `adapt`, vmx_ensemble_run_pt_adapt: betas [G][T], written back through betas_out with the call's history and
+// the guard's counts)
+struct EnsPtRun {
+    int32_t G, T; const double* betas; int32_t swap_every; int64_t* swaps;
+    const vmx_ensemble_adapt* adapt = nullptr; double* betas_out = nullptr; double* beta_hist = nullptr; int64_t* adapt_skipped = nullptr;
+};
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
@@ -5138,6 +5215,38 @@ int vmx_ensemble_run_pt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G,
     const EnsPtRun pt{G, T, betas, swap_every, swaps};
     return ensemble_run("vmx_ensemble_run_pt", e, spec, G * T, W, streams, mock_row ? rung_mock.data() : nullptr, x, lnL, accepted, step0,
                         n_steps, thin, chain, chain_lnL, opt, stats, per_ensemble, moves, &pt);
+}
+
+// The ladders of vmx_ensemble_run_pt, each with betas of its own that k_ens_swap_adapt moves after every sweep (vmx_ensemble.h, the
+// fourth part): the same run, the same stream order - the k_ens_half_pt(record | propose) behind the sweep reads the new betas -
+// and the same single host wait
+int vmx_ensemble_run_pt_adapt(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t G, int32_t T, int32_t W, double* betas,
+                              const uint64_t* streams, const int32_t* mock_row, double* x, double* lnL, int64_t* accepted,
+                              int64_t step0, int32_t n_steps, int32_t thin, int32_t swap_every, double* chain, double* chain_lnL,
+                              const vmx_ensemble_options* opt, vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                              const vmx_ensemble_moves* moves, int64_t* swaps, const vmx_ensemble_adapt* adapt, double* beta_hist,
+                              int64_t* adapt_skipped)
+{
+    const std::string name("vmx_ensemble_run_pt_adapt");
+    REQUIRE(G >= 1, name + ": at least one ladder");
+    REQUIRE(T >= 3 && T <= VMX_PT_MAXT, name + ": 3 <= T <= VMX_PT_MAXT rungs (an adaptive ladder moves the rungs between the first and the last)");
+    REQUIRE(swap_every >= 1, name + ": swap_every >= 1 (the ladder adapts after a sweep)");
+    REQUIRE(adapt, name + ": the adaptation settings");
+    REQUIRE(vmx_ens::adapt_ok(T, swap_every, adapt->lag, adapt->time), name + ": lag and time must be finite and positive");
+    REQUIRE(adapt->flags == 0 && adapt->reserved == 0, name + ": flags and reserved must be 0");
+    REQUIRE(betas, name + ": the ladders");
+    for (int g = 0; g < G; ++g)
+        REQUIRE(vmx_ens::ladder_ok(betas + (size_t)g * T, T), name + ": every ladder must start at 1, be finite, strictly decreasing and not negative");
+    REQUIRE(W >= 1 && (int64_t)G * T <= INT32_MAX && (int64_t)G * T * W <= INT32_MAX, name + ": G T W exceeds the engine's row count");
+    std::vector<int32_t> rung_mock;         // (every rung of a ladder reads the ladder's mock)
+    if (mock_row) {
+        rung_mock.resize((size_t)G * T);
+        for (int g = 0; g < G; ++g) std::fill(rung_mock.begin() + (size_t)g * T, rung_mock.begin() + (size_t)(g + 1) * T, mock_row[g]);
+    }
+    EnsPtRun pt{G, T, betas, swap_every, swaps};
+    pt.adapt = adapt; pt.betas_out = betas; pt.beta_hist = beta_hist; pt.adapt_skipped = adapt_skipped;
+    return ensemble_run("vmx_ensemble_run_pt_adapt", e, spec, G * T, W, streams, mock_row ? rung_mock.data() : nullptr, x, lnL, accepted,
+                        step0, n_steps, thin, chain, chain_lnL, opt, stats, per_ensemble, moves, &pt);
 }
 
 // E independent ensembles advanced together (k_ens_half): the E H proposal rows of a half-step as one stream of chunks for the
@@ -5206,7 +5315,13 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         (mock_row && ensure(S.mock, EH)))
         return -2;
     const size_t n_swaps = pt ? (size_t)pt->G * (size_t)(pt->T - 1) * 2 : 0;
-    if (pt && (ensure(S.beta, pt->T) || (n_swaps && ensure(S.swaps, n_swaps)))) return -2;
+    const vmx_ensemble_adapt* const ad = pt ? pt->adapt : nullptr;
+    const size_t n_beta = pt ? (ad ? (size_t)pt->G * pt->T : (size_t)pt->T) : 0;
+    // (the sweeps of this call: after the steps s in [step0, step0 + n_steps) with (s + 1) % swap_every == 0)
+    const int64_t sweep0 = ad ? step0 / pt->swap_every : 0;
+    const size_t n_hist = ad && pt->beta_hist ? (size_t)((step0 + n_steps) / pt->swap_every - sweep0) * n_beta : 0;
+    if (pt && (ensure(S.beta, n_beta) || (n_swaps && ensure(S.swaps, n_swaps)))) return -2;
+    if (ad && (ensure(S.adapt_skipped, pt->G) || (n_hist && ensure(S.beta_hist, n_hist)))) return -2;
     if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
     if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
     hipStream_t st = e->stream;
@@ -5247,16 +5362,26 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     // a ladder's half-step: with a sweep due after step s_dec, the swaps come between the decisions and the row and proposals
     EnsPtDev Pt{};
     if (pt) {
-        HIP_OK(hipMemcpyAsync(S.beta.p, pt->betas, (size_t)pt->T * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(S.beta.p, pt->betas, n_beta * sizeof(double), hipMemcpyHostToDevice, st));
         if (n_swaps) HIP_OK(hipMemsetAsync(S.swaps.p, 0, n_swaps * sizeof(int64_t), st));
-        Pt.beta = S.beta.p; Pt.swaps = n_swaps ? S.swaps.p : nullptr; Pt.T = pt->T;
+        Pt.beta = S.beta.p; Pt.swaps = n_swaps ? S.swaps.p : nullptr; Pt.T = pt->T; Pt.stride = ad ? pt->T : 0;
+    }
+    EnsAdaptDev Ad{};
+    if (ad) {
+        HIP_OK(hipMemsetAsync(S.adapt_skipped.p, 0, (size_t)pt->G * sizeof(int64_t), st));
+        Ad.beta = S.beta.p; Ad.hist = n_hist ? S.beta_hist.p : nullptr; Ad.skipped = S.adapt_skipped.p;
+        Ad.lag = ad->lag; Ad.tau = ad->time; Ad.sweep0 = sweep0; Ad.swap_every = pt->swap_every; Ad.G = pt->G;
     }
     const dim3 grid_swap(pt ? pt->G : 1), block_swap(std::min(ENS_THREADS, std::max(64, (W + 63) / 64 * 64)));
     const int pt_all = ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE;
     auto half_pt = [&](int64_t s_dec, int h_dec, int64_t s_prop, int h_prop) {
         if (s_dec >= 0 && h_dec == 1 && pt->T > 1 && vmx_ens::swap_due(s_dec, pt->swap_every)) {
             hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, (int)ENS_PT_DECIDE);
-            hipLaunchKernelGGL(k_ens_swap, grid_swap, block_swap, 0, st, D, Pt, s_dec);
+            if (ad)
+                hipLaunchKernelGGL(k_ens_swap_adapt, grid_swap, block_swap, 0, st, D, Pt, Ad, s_dec,
+                                   vmx_ens::adapt_due(s_dec, ad->adapt_until) ? 1 : 0);
+            else
+                hipLaunchKernelGGL(k_ens_swap, grid_swap, block_swap, 0, st, D, Pt, s_dec);
             hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, ENS_PT_RECORD | ENS_PT_PROPOSE);
         } else {
             hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, pt_all);
@@ -5285,6 +5410,14 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     if (pt && pt->swaps && n_swaps) {
         if (halves > 0) HIP_OK(hipMemcpyAsync(pt->swaps, S.swaps.p, n_swaps * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         else std::fill(pt->swaps, pt->swaps + n_swaps, (int64_t)0);
+    }
+    if (ad && halves > 0) {
+        HIP_OK(hipMemcpyAsync(pt->betas_out, S.beta.p, n_beta * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (n_hist) HIP_OK(hipMemcpyAsync(pt->beta_hist, S.beta_hist.p, n_hist * sizeof(double), hipMemcpyDeviceToHost, st));
+        if (pt->adapt_skipped)
+            HIP_OK(hipMemcpyAsync(pt->adapt_skipped, S.adapt_skipped.p, (size_t)pt->G * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    } else if (ad && pt->adapt_skipped) {
+        std::fill(pt->adapt_skipped, pt->adapt_skipped + pt->G, (int64_t)0);
     }
     HIP_OK(hipMemcpyAsync(x, S.x.p, EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, EW * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -37,6 +37,8 @@
 #define VMX_NO_CONTRACT
 #endif
 
+#include "vmx_pexp.h"
+
 namespace vmx_ens {
 
 struct Block { uint64_t w[4]; };
@@ -336,5 +338,69 @@ VMX_HD inline bool swap_accept(double beta_cold, double beta_hot, double lnl_col
 
 // a sweep is due after global step s
 VMX_HD inline bool swap_due(int64_t s, int32_t swap_every) { return swap_every > 0 && (s + 1) % swap_every == 0; }
+
+}  // namespace vmx_ens
+
+// ---- adaptive ladders (vmx_ensemble_run_pt_adapt: k_ens_swap_adapt), the fourth part
+//
+// Vousden, Farr & Mandel 2016, ptemcee's _get_ladder_adjustment: after a whole swap sweep the intermediate betas of a ladder move
+// so that all adjacent pairs of rungs come to swap at the same rate; the adjustment decays, so that the chain becomes a proper one.
+//
+//   ratios           A_t = (double)accepted_t / (double)W for the pair (rung t, rung t + 1), t = 0 .. T - 2: the accepted swaps of
+//                    this sweep alone, every pair of which was decided with the old ladder.
+//   time             the number of sweeps before this one: (s + 1) / swap_every - 1 for the sweep after global step s, a function
+//                    of the global step only (a run cut into calls adapts identically).
+//   strength         decay = lag / (time + lag); kappa = decay / tau (ptemcee's adaptation_lag and adaptation_time, in sweeps).
+//   rule             sum = 1 / beta[0]; for i = 0 .. T - 3 in order: dS = kappa (A_i - A_{i+1});
+//                    gap = (1 / beta[i + 1] - 1 / beta[i]) pexp(dS); sum = sum + gap; beta'[i + 1] = 1 / sum - every operation
+//                    rounded on its own, the betas on the right the old ones, pexp the pinned exponential of vmx_smc.h.
+//                    beta[0] = 1 and beta[T - 1] (0 or positive) never move.
+//   guard            a new ladder that is not ladder_ok (finite, strictly decreasing, the fixed last rung included - a positive
+//                    last beta can be crossed) is dropped: the old one stays for this sweep and the ladder's adapt_skipped count
+//                    goes up by one.
+//   when             the sweep after global step s adapts iff adapt_until < 0 or s < adapt_until.
+namespace vmx_ens {
+
+// what the adaptive run takes beside a ladder: T >= 3 rungs, sweeps, lag and tau finite and positive
+VMX_HD inline bool adapt_ok(int T, int32_t swap_every, double lag, double tau)
+{
+    return T >= 3 && T <= PT_MAXT && swap_every > 0 && is_finite(lag) && lag > 0.0 && is_finite(tau) && tau > 0.0;
+}
+
+// the number of sweeps before the one after global step s
+VMX_HD inline int64_t sweep_time(int64_t s, int32_t swap_every) { return (s + 1) / swap_every - 1; }
+
+VMX_HD inline bool adapt_due(int64_t s, int64_t adapt_until) { return adapt_until < 0 || s < adapt_until; }
+
+// one ladder after one sweep: beta[T] in and out, accepted[T - 1] the sweep's accepted swaps per pair of rungs (any integer type);
+// false: the guard held and beta is what it was
+template <class Count>
+VMX_HD inline bool ladder_adjust(double* beta, const Count* accepted, int T, int64_t W, int64_t time, double lag, double tau)
+{
+    VMX_NO_CONTRACT
+    if (T < 3 || T > PT_MAXT) return true;          // (nothing between the two fixed rungs)
+    const double tl = (double)time + lag;
+    const double decay = lag / tl;
+    const double kappa = decay / tau;
+    double fresh[PT_MAXT];
+    fresh[0] = beta[0];
+    fresh[T - 1] = beta[T - 1];
+    double sum = 1.0 / beta[0];
+    for (int i = 0; i + 2 < T; ++i) {
+        const double a0 = (double)accepted[i] / (double)W;
+        const double a1 = (double)accepted[i + 1] / (double)W;
+        const double da = a0 - a1;
+        const double dS = kappa * da;
+        const double inv_hot = 1.0 / beta[i + 1];
+        const double inv_cold = 1.0 / beta[i];
+        const double dT = inv_hot - inv_cold;
+        const double gap = dT * vmx_smc::pexp(dS);
+        sum = sum + gap;
+        fresh[i + 1] = 1.0 / sum;
+    }
+    if (!ladder_ok(fresh, T)) return false;
+    for (int t = 1; t + 1 < T; ++t) beta[t] = fresh[t];
+    return true;
+}
 
 }  // namespace vmx_ens

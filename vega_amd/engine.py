@@ -140,6 +140,10 @@ class EnsembleMoves(C.Structure):
                 ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+class EnsembleAdapt(C.Structure):
+    _fields_ = [('lag', C.c_double), ('time', C.c_double), ('adapt_until', C.c_int64), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
 VMX_NS_MAXN = 32
 VMX_NS_MAX_LIVE = 4096
 NESTED_STOP = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -335,6 +339,7 @@ def load_library():
                                         iptr, dptr, dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, C.c_int32, dptr, dptr,
                                         C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64),
                                         C.POINTER(EnsembleMoves), C.POINTER(C.c_int64)]
+    lib.vmx_ensemble_run_pt_adapt.argtypes = lib.vmx_ensemble_run_pt.argtypes + [C.POINTER(EnsembleAdapt), dptr, C.POINTER(C.c_int64)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -389,7 +394,7 @@ def load_library():
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
                                     SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms,
-                                    NestedSetPhantoms, SmcKeep, None, EnsembleMoves)):
+                                    NestedSetPhantoms, SmcKeep, None, EnsembleMoves, EnsembleAdapt)):
         if struct is None:          # (an index that names no struct)
             continue
         if lib.vmx_struct_size(which) != C.sizeof(struct):
@@ -423,7 +428,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1279,6 +1284,48 @@ class Engine:
         if keep_chain:
             chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, swaps=swaps)
+
+    def ensemble_run_pt_adapt(self, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, step0, n_steps, swap_every=1,
+                              adaptation_lag=10000.0, adaptation_time=100.0, adapt_until=-1, mock_rows=None, thin=1, a=2.0,
+                              log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):
+        """:meth:`ensemble_run_pt` with a ladder of its own for every one of the G ladders, moved on the device after every swap
+        sweep (include/vegamx.h: vmx_ensemble_run_pt_adapt): ``betas`` float64 [G, T] (updated in place), ``adaptation_lag`` /
+        ``adaptation_time`` ptemcee's, in sweeps; the sweep after global step s adapts iff ``adapt_until`` < 0 or s <
+        ``adapt_until``.  The statistics carry, beside ``per_ensemble`` and ``swaps``, ``beta_hist`` [sweeps, G, T] - the ladders
+        after every sweep of the call - and ``adapt_skipped`` int64 [G], the sweeps whose new ladder the guard dropped."""
+        _in_place(np.float64, x=x, lnl=lnl, betas=betas)
+        _in_place(np.int64, accepted=accepted)
+        if x.ndim != 4:
+            raise ValueError('x [G, T, W, n], lnl [G, T, W], accepted [G, T, W]')
+        G, T, W, n = x.shape
+        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
+            3, cols, lo, hi, theta_fixed, x.reshape(G * T, W, n), lnl.reshape(G * T, W), accepted.reshape(G * T, W), step0, n_steps,
+            thin, keep_chain, a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
+        streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if betas.shape != (G, T) or streams.shape != (G, T) or (mock_rows is not None and mock_rows.shape != (G,)):
+            raise ValueError('betas [G, T], streams [G, T], mock_rows [G]')
+        step0, n_steps, swap_every = int(step0), int(n_steps), int(swap_every)
+        sweeps = max(0, (step0 + n_steps) // swap_every - step0 // swap_every) if swap_every > 0 and n_steps >= 0 and step0 >= 0 else 0
+        per = np.zeros((G, T, 3), dtype=np.int64)
+        swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
+        hist = np.zeros((sweeps, G, T))
+        skipped = np.zeros(G, dtype=np.int64)
+        mv = None
+        if moves is not None:
+            mv = C.byref(EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']),
+                                       float(moves['sigma']), float(moves['gamma_s']), int(moves.get('flags', 0)), 0))
+        ad = EnsembleAdapt(float(adaptation_lag), float(adaptation_time), int(adapt_until), 0, 0)
+        i64 = C.POINTER(C.c_int64)
+        self._check(self.lib.vmx_ensemble_run_pt_adapt(
+            self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), *args[:6], swap_every, *args[6:], C.byref(stats),
+            per.ctypes.data_as(i64), mv, swaps.ctypes.data_as(i64), C.byref(ad), _dp(hist) if sweeps else None,
+            skipped.ctypes.data_as(i64)))
+        if keep_chain:
+            chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
+        return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, swaps=swaps, beta_hist=hist, adapt_skipped=skipped)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
                    seed=0, stream=0, const_hint=-1, chunk=0, lanes=0, draw_live=False, stop=None, clusters=None, cluster_flags=None,

@@ -401,34 +401,81 @@ def swap_sweep(x, lnl, betas, step, seed, stream, swaps):
         swaps[t - 1] += (W, int(take.sum()))
 
 
-def python_steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm, evaluate,
-                    moves=None):
-    """``n_steps`` steps of G temperature ladders of T rungs in NumPy - what vmx_ensemble_run_pt runs: the state ``x``
-    [G, T, W, n], ``lnl`` [G, T, W] (untempered), ``accepted`` [G, T, W] (updated in place), ``betas`` [T], ``streams`` [G, T].
-    The steps are :func:`python_steps_many`'s over the G T ensembles with the rung's beta in the decision, run up to every step
-    after which a sweep is due (:func:`swap_due`: the global step counts); the sweep (:func:`swap_sweep`) comes before that step's
-    chain row.  ``evaluate(rows, h)`` as there, for the G T W/2 rows of a half.  Returns (chain [G, T, rows, W, n], chain_lnl
-    [G, T, rows, W], stats, per_ensemble [G, T, 3], swaps [G, T - 1, 2])."""
+# ---- adaptive ladders (vmx_ensemble.h, the fourth part)
+def adapt_ok(T, swap_every, lag, tau):
+    """What the adaptive run takes beside a ladder: 3 <= T <= PT_MAXT rungs, sweeps, ``lag`` and ``tau`` finite and positive."""
+    lag, tau = float(lag), float(tau)
+    return bool(3 <= T <= PT_MAXT and swap_every > 0 and math.isfinite(lag) and lag > 0.0 and math.isfinite(tau) and tau > 0.0)
+
+
+def sweep_time(step, swap_every):
+    """The number of sweeps before the one after global step ``step``."""
+    return (step + 1) // swap_every - 1
+
+
+def adapt_due(step, adapt_until):
+    return adapt_until < 0 or step < adapt_until
+
+
+def ladder_adjust(betas, accepted, W, time, lag, tau):
+    """vmx_ens::ladder_adjust, ptemcee's ``_get_ladder_adjustment`` with every operation rounded on its own: one ladder ``betas``
+    [T] after one sweep whose pairs (t, t + 1) accepted ``accepted`` [T - 1] of ``W`` swaps, ``time`` sweeps before it.  Returns
+    (the new ladder, 0) or, when the new ladder is not :func:`ladder_ok` (a positive last beta can be crossed), (the old one, 1).
+    The first and the last beta never move."""
+    from .smc import pexp
+    old = np.array(betas, dtype=np.float64)
+    T = old.size
+    if T < 3:
+        return old, 0
+    with np.errstate(all='ignore'):
+        ratio = np.asarray(accepted, dtype=np.int64).astype(np.float64) / np.float64(W)
+        tl = np.float64(time) + np.float64(lag)
+        decay = np.float64(lag) / tl
+        kappa = decay / np.float64(tau)
+        da = ratio[:-1] - ratio[1:]
+        dS = kappa * da
+        inv = 1.0 / old[:-1]
+        dT = inv[1:] - inv[:-1]
+        gap = dT * pexp(dS)
+        new = old.copy()
+        total = np.float64(1.0) / old[0]
+        for i in range(T - 2):          # (in order: a cumulative sum that starts from 1 / beta[0])
+            total = total + gap[i]
+            new[i + 1] = np.float64(1.0) / total
+    if not ladder_ok(new):
+        return old, 1
+    return new, 0
+
+
+def _steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm, evaluate, moves, adapt):
+    """The steps of :func:`python_steps_pt` over ladders of their own, ``betas`` [G, T] (updated in place when ``adapt`` - (lag,
+    tau, adapt_until) - is given: :func:`ladder_adjust` after every sweep that is due to adapt).  Returns python_steps_pt's tuple
+    and (the ladders after every sweep of the call [sweeps, G, T], the guard's counts [G])."""
     G, T, W, n = x.shape
     E = G * T
     xe, le, ae = x.reshape(E, W, n), lnl.reshape(E, W), accepted.reshape(E, W)
-    betas = np.asarray(betas, dtype=np.float64)
     flat_streams = np.asarray(streams, dtype=np.uint64).reshape(E)
-    rung_beta = np.tile(betas, G)
     rows = (step0 + n_steps) // thin - step0 // thin
     chain, chain_lnl = np.empty((E, rows, W, n)), np.empty((E, rows, W))
     per = np.zeros((E, 3), dtype=np.int64)
     swaps = np.zeros((G, T - 1, 2), dtype=np.int64)
+    hist, skipped = [], np.zeros(G, dtype=np.int64)
     s, end = step0, step0 + n_steps
     while s < end:
         # up to and with the next step a sweep follows (or the end); every step's row, of which the thinning picks
         stop = end if swap_every <= 0 or T < 2 else min(end, (s // swap_every + 1) * swap_every)
         part, part_lnl, _, p = python_steps_many(xe, le, ae, s, stop - s, 1, a, seed, flat_streams, lo, hi, log_norm, evaluate, moves,
-                                                 betas=rung_beta)
+                                                 betas=betas.reshape(E))
         per += p
         if T > 1 and swap_due(stop - 1, swap_every):
             for g in range(G):
-                swap_sweep(x[g], lnl[g], betas, stop - 1, seed, int(flat_streams[g * T]), swaps[g])
+                before = swaps[g, :, 1].copy()
+                swap_sweep(x[g], lnl[g], betas[g], stop - 1, seed, int(flat_streams[g * T]), swaps[g])
+                if adapt is not None and adapt_due(stop - 1, adapt[2]):
+                    betas[g], skip = ladder_adjust(betas[g], swaps[g, :, 1] - before, W, sweep_time(stop - 1, swap_every), adapt[0],
+                                                   adapt[1])
+                    skipped[g] += skip
+            hist.append(betas.copy())
             part[:, -1], part_lnl[:, -1] = xe, le
         for q in range(s, stop):
             if (q + 1) % thin == 0:
@@ -438,7 +485,41 @@ def python_steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed,
     st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
               rejected_failed_model=int(per[:, 2].sum()), swaps_proposed=int(swaps[:, :, 0].sum()),
               swaps_accepted=int(swaps[:, :, 1].sum()))
-    return (chain.reshape(G, T, rows, W, n), chain_lnl.reshape(G, T, rows, W), st, per.reshape(G, T, 3), swaps)
+    hist = np.array(hist).reshape(len(hist), G, T)
+    return (chain.reshape(G, T, rows, W, n), chain_lnl.reshape(G, T, rows, W), st, per.reshape(G, T, 3), swaps), (hist, skipped)
+
+
+def python_steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm, evaluate,
+                    moves=None):
+    """``n_steps`` steps of G temperature ladders of T rungs in NumPy - what vmx_ensemble_run_pt runs: the state ``x``
+    [G, T, W, n], ``lnl`` [G, T, W] (untempered), ``accepted`` [G, T, W] (updated in place), ``betas`` [T], ``streams`` [G, T].
+    The steps are :func:`python_steps_many`'s over the G T ensembles with the rung's beta in the decision, run up to every step
+    after which a sweep is due (:func:`swap_due`: the global step counts); the sweep (:func:`swap_sweep`) comes before that step's
+    chain row.  ``evaluate(rows, h)`` as there, for the G T W/2 rows of a half.  Returns (chain [G, T, rows, W, n], chain_lnl
+    [G, T, rows, W], stats, per_ensemble [G, T, 3], swaps [G, T - 1, 2])."""
+    ladders = np.tile(np.asarray(betas, dtype=np.float64), (x.shape[0], 1))
+    return _steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, ladders, streams, lo, hi, log_norm, evaluate, moves,
+                     None)[0]
+
+
+def python_steps_pt_adapt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm, evaluate,
+                          moves=None, adaptation_lag=10000.0, adaptation_time=100.0, adapt_until=-1):
+    """:func:`python_steps_pt` over ladders of their own that adapt - what vmx_ensemble_run_pt_adapt runs: ``betas`` float64 [G, T]
+    (updated in place); after every sweep that follows a global step s with ``adapt_until`` < 0 or s < ``adapt_until``, every
+    ladder moves by :func:`ladder_adjust` with its own accepted swaps of that sweep and ``time`` = :func:`sweep_time` (the global
+    step alone: a run cut into calls adapts identically); the row of step s and the next proposals see the new ladder.  Returns
+    python_steps_pt's five, then ``betas``, the ladders after every sweep of the call [sweeps, G, T] and the sweeps whose new ladder
+    the guard dropped, int64 [G]."""
+    G, T = x.shape[:2]
+    if not (isinstance(betas, np.ndarray) and betas.dtype == np.float64 and betas.shape == (G, T)):
+        raise ValueError('betas: a float64 array [G, T] (updated in place)')
+    if not adapt_ok(T, swap_every, adaptation_lag, adaptation_time):
+        raise ValueError('adaptive ladders: T >= 3 rungs, swap_every >= 1, adaptation_lag and adaptation_time finite and positive')
+    if not all(ladder_ok(b) for b in betas):
+        raise ValueError(f'betas: every ladder from 1, strictly decreasing, none negative, at most {PT_MAXT}')
+    out, (hist, skipped) = _steps_pt(x, lnl, accepted, step0, n_steps, thin, swap_every, a, seed, betas, streams, lo, hi, log_norm,
+                                     evaluate, moves, (float(adaptation_lag), float(adaptation_time), int(adapt_until)))
+    return out + (betas, hist, skipped)
 
 
 def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, lo, hi, log_norm, evaluate, moves=None, betas=None):
@@ -1264,11 +1345,22 @@ class TemperedEnsemble(EnsembleSet):
 
     ``get_chain`` / ``get_log_lik`` read one rung (default the cold one, which ``write`` puts into the getdist chain);
     ``swap_fraction`` [G, T - 1] is the accepted fraction of the swaps between rungs t and t + 1; ``log_evidence`` is the
-    stepping-stone or thermodynamic-integration evidence over the box, with the ``log_norm`` of the other samplers."""
+    stepping-stone or thermodynamic-integration evidence over the box, with the ``log_norm`` of the other samplers.
+
+    ``adapt=True`` (ptemcee's adaptive ladder, Vousden et al. 2016; T >= 3 and swaps required): every ladder starts from ``betas``
+    and moves its intermediate betas after every swap sweep so that all pairs of rungs come to swap at the same rate
+    (:func:`ladder_adjust` with ptemcee's ``adaptation_lag`` and ``adaptation_time``, in sweeps), on the device
+    (vmx_ensemble_run_pt_adapt) or in :func:`python_steps_pt_adapt`, the same chain bit for bit.  The sweeps after the global
+    steps below ``adapt_steps`` adapt (None: all of them, as in ptemcee); ``run`` cuts its calls there, and the chain does not
+    depend on any cut.  ``current_betas`` [G, T] are the ladders as they stand (a fixed run tiles its ladder), ``beta_history``
+    [sweeps, G, T] the ladders after every adapting sweep, ``stats['adapt_skipped']`` [G] the sweeps whose new ladder was dropped
+    because it was not in order, ``frozen_swap_fraction`` [G, T - 1] the swap fractions of the sweeps after the ladder froze.  The
+    evidence of an adaptive run reads only the rows recorded after ``adapt_steps``, with the ladder's final betas."""
 
     def __init__(self, vega, walkers, ntemps=None, betas=None, swap_every=1, ladders=1, streams=None, mock_rows=None, beta_min=None,
                  a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, chunk=0, lanes=0, const_hint=-1,
-                 moves=None, gamma0=None, sigma=None, gamma_s=None):
+                 moves=None, gamma0=None, sigma=None, gamma_s=None, adapt=False, adapt_steps=None, adaptation_lag=10000,
+                 adaptation_time=100):
         if (ntemps is None) == (betas is None):
             raise ValueError('ntemps or betas: one of the two')
         if betas is None:
@@ -1283,6 +1375,13 @@ class TemperedEnsemble(EnsembleSet):
         self.swap_every = int(swap_every)
         if self.G < 1 or self.swap_every < 0:
             raise ValueError('ladders: at least one; swap_every: 0 (no swaps) or more')
+        self.adapt = bool(adapt)
+        self.adapt_steps = None if adapt_steps is None else int(adapt_steps)
+        self.adaptation_lag, self.adaptation_time = float(adaptation_lag), float(adaptation_time)
+        if self.adapt and not adapt_ok(self.T, self.swap_every, self.adaptation_lag, self.adaptation_time):
+            raise ValueError('adapt: at least 3 rungs, swap_every >= 1, adaptation_lag and adaptation_time finite and positive')
+        if self.adapt and self.adapt_steps is not None and self.adapt_steps < 0:
+            raise ValueError('adapt_steps: 0 or more steps, or None (adapt to the end)')
         if streams is None:
             streams = np.arange(self.G)
         streams = np.array(streams, dtype=np.uint64)
@@ -1304,26 +1403,62 @@ class TemperedEnsemble(EnsembleSet):
         self.stats.update(swaps_proposed=0, swaps_accepted=0)
         if self.swap_every > 0:
             self.stats.pop('moves', None)
+        self.current_betas = np.tile(self.betas, (self.G, 1))
+        self._frozen_swaps = np.zeros((self.G, self.T - 1, 2), dtype=np.int64)
+        self._beta_hist = []
+        if self.adapt:
+            self.stats['adapt_skipped'] = np.zeros(self.G, dtype=np.int64)
 
     def _prepare(self, start, init_scale):
         theta = super()._prepare(start, init_scale)
-        if self.driver == 'device' and not hasattr(self.vega.engine, 'ensemble_run_pt'):
+        entry = 'ensemble_run_pt_adapt' if self.adapt else 'ensemble_run_pt'
+        if self.driver == 'device' and not hasattr(self.vega.engine, entry):
             self.driver = 'python'
         return theta
+
+    def run(self, n_steps, start='ball', init_scale=1.0):
+        """:meth:`StretchSampler.run`; an adaptive run cuts its calls at ``adapt_steps``, so that every call is all adapting or all
+        frozen."""
+        if self.adapt and self.adapt_steps is not None and self.step < self.adapt_steps < self.step + n_steps:
+            first = self.adapt_steps - self.step
+            super().run(first, start=start, init_scale=init_scale)
+            return super().run(n_steps - first)
+        return super().run(n_steps, start=start, init_scale=init_scale)
 
     # ---- run
     def _shaped(self):
         lead = (self.G, self.T, self.W)
         return self.x.reshape(lead + (self.n,)), self.lnl.reshape(lead), self.accepted.reshape(lead)
 
-    def _took(self, chain, chain_lnl, st, per, swaps):
+    def _adapting(self):
+        """Whether the call that starts at the current step adapts (``run`` cuts the calls at ``adapt_steps``)."""
+        return self.adapt and (self.adapt_steps is None or self.step < self.adapt_steps)
+
+    def _adapt_arg(self):
+        return dict(adaptation_lag=self.adaptation_lag, adaptation_time=self.adaptation_time,
+                    adapt_until=-1 if self.adapt_steps is None else self.adapt_steps)
+
+    def _took(self, chain, chain_lnl, st, per, swaps, betas=None, hist=None, skipped=None):
         self.swaps += swaps
+        if self._adapting():
+            self._beta_hist.append(hist)
+            self.stats['adapt_skipped'] += skipped
+        else:
+            self._frozen_swaps += swaps
         st = dict(st, swaps_proposed=int(swaps[:, :, 0].sum()), swaps_accepted=int(swaps[:, :, 1].sum()))
         return chain.reshape((self.E,) + chain.shape[2:]), chain_lnl.reshape((self.E,) + chain_lnl.shape[2:]), st, per.reshape(self.E, 3)
 
     def _segment_device(self, theta, k):
         self.vega._sync_monte_carlo()
         x, lnl, accepted = self._shaped()
+        if self.adapt:
+            chain, chain_lnl, st = self.vega.engine.ensemble_run_pt_adapt(
+                self.cols, self.lo, self.hi, theta, x, lnl, accepted, self.current_betas, self.streams.reshape(self.G, self.T),
+                self.step, k, swap_every=self.swap_every, mock_rows=self.ladder_mock_rows, thin=self.thin, a=self.a,
+                log_norm=self.log_norm(), seed=self.seed, const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes,
+                **self._adapt_arg(), **self._moves_arg())
+            return self._took(chain, chain_lnl, st, st.pop('per_ensemble'), st.pop('swaps'), self.current_betas, st.pop('beta_hist'),
+                              st.pop('adapt_skipped'))
         chain, chain_lnl, st = self.vega.engine.ensemble_run_pt(
             self.cols, self.lo, self.hi, theta, x, lnl, accepted, self.betas, self.streams.reshape(self.G, self.T), self.step, k,
             swap_every=self.swap_every, mock_rows=self.ladder_mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(),
@@ -1333,6 +1468,11 @@ class TemperedEnsemble(EnsembleSet):
     def _python_steps(self, k, chi2):
         row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, self.W // 2)
         x, lnl, accepted = self._shaped()
+        if self.adapt:
+            return self._took(*python_steps_pt_adapt(
+                x, lnl, accepted, self.step, k, self.thin, self.swap_every, self.a, self.seed, self.current_betas,
+                self.streams.reshape(self.G, self.T), self.lo, self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x, row_mock),
+                self.moves, **self._adapt_arg()))
         return self._took(*python_steps_pt(x, lnl, accepted, self.step, k, self.thin, self.swap_every, self.a, self.seed, self.betas,
                                            self.streams.reshape(self.G, self.T), self.lo, self.hi, self.log_norm(),
                                            lambda rows_x, h: chi2(rows_x, row_mock), self.moves))
@@ -1366,7 +1506,7 @@ class TemperedEnsemble(EnsembleSet):
         m = self.member(self._index(t, ladder))
         if self.swap_every > 0:
             m.stats.pop('moves', None)
-        m.beta = float(self.betas[int(t)])
+        m.beta = float(self.current_betas[int(ladder), int(t)])
         return m
 
     @property
@@ -1379,18 +1519,47 @@ class TemperedEnsemble(EnsembleSet):
         with np.errstate(invalid='ignore', divide='ignore'):
             return self.swaps[:, :, 1] / self.swaps[:, :, 0]
 
+    @property
+    def beta_history(self):
+        """The ladders after every adapting sweep so far, [sweeps, G, T] (a fixed run: no row)."""
+        return np.concatenate(self._beta_hist + [np.empty((0, self.G, self.T))])
+
+    @property
+    def frozen_swap_fraction(self):
+        """:attr:`swap_fraction` over the sweeps after the ladder froze alone, [G, T - 1] (a fixed ladder: all sweeps; nan where
+        there was none)."""
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return self._frozen_swaps[:, :, 1] / self._frozen_swaps[:, :, 0]
+
+    @property
+    def frozen_rows(self):
+        """(the first recorded row after the ladder last moved, the number of such rows): (0, all rows) for a fixed ladder; the
+        rows of the steps from ``adapt_steps`` on for an adaptive one - none while it adapts."""
+        rows = self.recorded_rows
+        if not self.adapt:
+            return 0, rows
+        first = rows if self.adapt_steps is None else min(rows, self.adapt_steps // self.thin)
+        return first, rows - first
+
     def log_evidence(self, method='ss', discard=None, ladder=0):
         """(log Z, err) over the uniform prior on the box, from the rungs' lnL records past the first ``discard`` recorded rows
         (None: a quarter of them): ``'ss'`` - :func:`stepping_stone_evidence` - or ``'ti'`` - :func:`thermodynamic_integration`.
-        ValueError unless the ladder ends at beta = 0."""
+        ValueError unless the ladder ends at beta = 0.  Both need one beta per rung: an adaptive run reads only the rows recorded
+        after the ladder last moved (:attr:`frozen_rows`; ``discard`` counts from the first of them), with the ladder's final
+        betas, and raises ValueError while fewer than two such rows exist - always with ``adapt_steps=None``."""
         _ends_at_zero(self.betas)
-        rows = super().get_log_lik().shape[1]
+        first, rows = self.frozen_rows
+        if self.adapt and rows < 2:
+            raise ValueError('the evidence of an adaptive ladder needs at least two rows recorded after the ladder froze: set '
+                             'adapt_steps below the number of steps' + (' (adapt_steps=None adapts to the end)'
+                                                                        if self.adapt_steps is None else ''))
+        betas = self.current_betas[int(ladder)]
         discard = rows // 4 if discard is None else int(discard)
-        lnl = self.get_log_lik(discard=discard, rung=None)[int(ladder)]
+        lnl = self.get_log_lik(discard=first + discard, rung=None)[int(ladder)]
         if method == 'ss':
-            return stepping_stone_evidence(self.betas, lnl)
+            return stepping_stone_evidence(betas, lnl)
         if method == 'ti':
-            return thermodynamic_integration(self.betas, lnl.mean(axis=(1, 2)))
+            return thermodynamic_integration(betas, lnl.mean(axis=(1, 2)))
         raise ValueError("method: 'ss' (stepping stones) or 'ti' (thermodynamic integration)")
 
     def write(self, path, name, derived=False, print_func=print):
@@ -1401,10 +1570,11 @@ class TemperedEnsemble(EnsembleSet):
         for g in range(self.G):
             nm = name if self.G == 1 else f'{name}_ladder{g}'
             files = tuple(self.rung(0, g).write(path, nm, derived=derived, print_func=print_func))
-            if self.betas[-1] == 0.0 and self.T >= 2 and self.recorded_rows >= 2:
+            if self.betas[-1] == 0.0 and self.T >= 2 and self.frozen_rows[1] >= 2:
                 files += (write_pt_stats(self, path, nm, g),)
             elif self.betas[-1] == 0.0 and g == 0:
-                print_func('fewer than two recorded rows: no evidence, no ' + f'{nm}.stats')
+                print_func('fewer than two recorded rows' + (' after the ladder froze' if self.adapt else '') +
+                           ': no evidence, no ' + f'{nm}.stats')
             out.append(files)
         return out[0] if self.G == 1 else out
 
@@ -1419,21 +1589,26 @@ def write_pt_stats(run, path, name, ladder=0):
         f.write(f'log(Z) thermodynamic = {ti!r}\nlog(Z) thermodynamic error = {ti_err!r}\n')
         f.write(f'steps = {run.step}\nwalkers = {run.W}\nswap_every = {run.swap_every}\nseed = {run.seed}\n')
         f.write(f'likelihood evaluations = {run.step * run.W * run.T}\n')
-        f.write('beta = ' + ' '.join(repr(float(b)) for b in run.betas) + '\n')
+        f.write('beta = ' + ' '.join(repr(float(b)) for b in run.current_betas[ladder]) + '\n')
         f.write('swap fraction = ' + ' '.join(repr(float(v)) for v in run.swap_fraction[ladder]) + '\n')
+        if run.adapt:       # (the final ladder above; a fixed run's file is what it was)
+            f.write(f'adapt_steps = {run.adapt_steps}\nadaptation_lag = {run.adaptation_lag!r}\n')
+            f.write(f'adaptation_time = {run.adaptation_time!r}\nadapt skipped = {int(run.stats["adapt_skipped"][ladder])}\n')
+            f.write('frozen swap fraction = ' + ' '.join(repr(float(v)) for v in run.frozen_swap_fraction[ladder]) + '\n')
     return stats
 
 
 def read_pt_stats(path):
     """``name.stats`` of :func:`write_pt_stats` back as a dict (floats for the evidence lines, lists of floats for ``beta`` and
-    ``swap fraction``, ints for the counts)."""
+    ``swap fraction``, ints for the counts; of an adaptive run also ``adapt_steps``, ``adaptation_lag``, ``adaptation_time``,
+    ``adapt skipped`` and the list ``frozen swap fraction``, ``beta`` then being the final ladder)."""
     out = {}
     for line in Path(path).read_text().splitlines():
         key, _, val = line.partition(' = ')
-        if key in ('beta', 'swap fraction'):
+        if key in ('beta', 'swap fraction', 'frozen swap fraction'):
             out[key] = [float(v) for v in val.split()]
         else:
-            out[key] = float(val) if key.startswith('log(Z)') else int(val)
+            out[key] = float(val) if key.startswith('log(Z)') or key in ('adaptation_lag', 'adaptation_time') else int(val)
     return out
 
 
@@ -1478,7 +1653,8 @@ def sampler_settings(main_config, sample_params):
     ``moves`` with ``gamma0`` / ``de_sigma`` / ``snooker_gamma`` (:func:`_parse_moves`: a mixture of the stretch, DE and snooker
     moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
     they were), ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
-    :mod:`vega_amd.replicas`) and ``ntemps`` with ``beta_min`` / ``swap_every`` (:func:`_parse_tempering`: parallel tempering);
+    :mod:`vega_amd.replicas`) and ``ntemps`` with ``beta_min`` / ``swap_every`` and ``adapt`` with ``adapt_steps`` / ``adaptation_lag`` / ``adaptation_time``
+    (:func:`_parse_tempering`: parallel tempering, and its adaptive ladder);
     with ``sampler = Nested`` the ``[Nested]`` settings instead
     (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
@@ -1529,9 +1705,12 @@ def sampler_settings(main_config, sample_params):
 def _parse_tempering(sec, out):
     """``ntemps = T`` of ``[Ensemble]`` (T >= 2 rungs: parallel tempering, :class:`TemperedEnsemble` on
     :func:`default_ladder`), with ``beta_min`` and ``swap_every`` (default 1) when stated, into the keys of the same names.
-    Without ``ntemps`` nothing is added.  Not combined with ``mocks``, ``together`` or ``replicas > 1``."""
+    Without ``ntemps`` nothing is added.  Not combined with ``mocks``, ``together`` or ``replicas > 1``.  ``adapt = True``: the
+    adaptive ladder of :class:`TemperedEnsemble` (``ntemps >= 3``, ``swap_every >= 1``), with ``adapt_steps`` (default
+    ``steps // 2``, so that rows remain for the evidence) and, when stated, ``adaptation_lag`` and ``adaptation_time``; these keys
+    too are added only when the section states ``adapt``."""
     if 'ntemps' not in sec:
-        stray = [key for key in ('beta_min', 'swap_every') if key in sec]
+        stray = [key for key in ('beta_min', 'swap_every') + _ADAPT_KEYS if key in sec]
         if stray:
             raise ValueError(f'[Ensemble] {", ".join(stray)}: settings of a temperature ladder, but no ntemps')
         return
@@ -1555,6 +1734,44 @@ def _parse_tempering(sec, out):
             raise ValueError(f'[Ensemble] ntemps and {key} do not combine yet')
     if out.get('replicas', 1) > 1:
         raise ValueError('[Ensemble] ntemps and replicas > 1 do not combine yet')
+    _parse_adapt(sec, out)
+
+
+_ADAPT_KEYS = ('adapt', 'adapt_steps', 'adaptation_lag', 'adaptation_time')
+
+
+def _parse_adapt(sec, out):
+    """The adaptive-ladder keys of a section that has ``ntemps`` (:func:`_parse_tempering`)."""
+    stated = [key for key in _ADAPT_KEYS if key in sec]
+    if not stated:
+        return
+    try:
+        adapt = sec.getboolean('adapt', False)
+    except ValueError:
+        raise ValueError('[Ensemble] adapt: True or False') from None
+    if not adapt:
+        stray = [key for key in stated if key != 'adapt']
+        if stray:
+            raise ValueError(f'[Ensemble] {", ".join(stray)}: settings of an adaptive ladder, but adapt is not True')
+        out['adapt'] = False
+        return
+    out['adapt'] = True
+    try:
+        out['adapt_steps'] = sec.getint('adapt_steps', out['steps'] // 2)
+        for key in ('adaptation_lag', 'adaptation_time'):
+            if key in sec:
+                out[key] = sec.getfloat(key)
+    except ValueError:
+        raise ValueError('[Ensemble] adapt_steps: a whole number; adaptation_lag, adaptation_time: numbers') from None
+    if out['ntemps'] < 3 or out['swap_every'] == 0:
+        raise ValueError('[Ensemble] adapt: an adaptive ladder needs ntemps >= 3 and swap_every >= 1')
+    if not adapt_ok(out['ntemps'], out['swap_every'], out.get('adaptation_lag', 1.0), out.get('adaptation_time', 1.0)):
+        raise ValueError('[Ensemble] adaptation_lag, adaptation_time: finite and positive')
+    if not 0 <= out['adapt_steps'] <= out['steps']:
+        raise ValueError(f'[Ensemble] adapt_steps: 0 .. steps = {out["steps"]}')
+    if out['steps'] // out['thin'] - out['adapt_steps'] // out['thin'] < 2:
+        raise ValueError('[Ensemble] adapt_steps: the evidence needs at least two rows recorded after the ladder froze, '
+                         'steps // thin - adapt_steps // thin >= 2')
 
 
 _MOVE_KEYS = (('gamma0', 'gamma0'), ('de_sigma', 'sigma'), ('snooker_gamma', 'gamma_s'))
@@ -1642,7 +1859,8 @@ def build_sampler(vega, cfg, sample_params, stream=0):
     if 'ntemps' in cfg:
         return TemperedEnsemble(vega, cfg['walkers'], ntemps=cfg['ntemps'], beta_min=cfg.get('beta_min'), swap_every=cfg['swap_every'],
                                 streams=[stream], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
-                                sample_params=sample_params, **moves_arguments(cfg))
+                                sample_params=sample_params, **moves_arguments(cfg),
+                                **{key: cfg[key] for key in _ADAPT_KEYS if key in cfg})
     return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
                            sample_params=sample_params, stream=stream, **moves_arguments(cfg))
 
