@@ -805,8 +805,8 @@ int vmx_nested_run_many_phantoms(vmx_engine* e, const vmx_nested_spec* spec, int
  * reference's second sampler in bin/run_vega_mpi.py, without its normalising flow), every decision pinned in
  * vega_amd/csrc/vmx_smc.h.  N particles walk from the prior (beta = 0) to the posterior (beta = 1); a stage picks the next beta by
  * bisection on the effective sample size of the importance weights, resamples systematically, whitens with the particles'
- * covariance (k_smc_stage: one work-group, once per stage) and moves all particles by `sweeps` Metropolis sweeps under L^beta:
- * k_smc_move decides the sweep just evaluated, adapts the proposal scale and writes the N rows of the next one, then the
+ * covariance (k_smc_stage: one work-group per run, once per stage) and moves all particles by `sweeps` Metropolis sweeps under
+ * L^beta: k_smc_move decides the sweep just evaluated, adapts the proposal scale and writes the N rows of the next one, then the
  * engine's chain runs over them in chunks of `chunk` (two lanes alternate when the quadratic form serves them).  A whole stage is
  * enqueued at once; the host waits once per stage, on a mapped word that carries beta.
  *   spec      n_params = the engine's; n sampled columns col[n] with their box [lo, hi] (finite, lo < hi: the uniform prior);
@@ -850,12 +850,12 @@ int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl,
                 vmx_smc_stats* stats);
 /* E independent SMC runs advanced together: log Z and an equal-weight posterior for every Monte-Carlo mock, or the replicas of one
  * run, as one device run.  A run of N = 256 - 512 particles hands the engine one batch per sweep and stops the host once per
- * stage; here every kernel of the single run is launched with one work-group per run still going (k_smc_set_start,
- * k_smc_set_start_lnl, k_smc_set_stage, k_smc_set_move: work-group a owns run active[a], the same device functions as the single
- * run's kernels, nothing crosses runs), the A N rows of a sweep go through the engine as one stream of chunks of `chunk` on two
- * lanes, and the host waits once per stage round for the whole set.  Run e is by construction the run vmx_smc_run makes with
- * spec->stream = streams[e] on the data of mock_row[e]; its chi2 is evaluated in batches of another shape, so that its lnL may
- * differ from the single run's in the last bits (E = 1 has the single run's batches and gives it bit for bit).
+ * stage; here the same kernels are launched with one work-group per run still going (work-group a owns run active[a], nothing
+ * crosses runs: the single run is the set of one, through one host body), the A N rows of a sweep go through the engine as one
+ * stream of chunks of `chunk` on two lanes, and the host waits once per stage round for the whole set.  Run e is by construction
+ * the run vmx_smc_run makes with spec->stream = streams[e] on the data of mock_row[e]; its chi2 is evaluated in batches of another
+ * shape, so that its lnL may differ from the single run's in the last bits (E = 1 has the single run's batches and gives it bit
+ * for bit).
  *   spec      as for the single run; spec->stream is not read
  *   E         runs (>= 1) of spec->N particles each
  *   streams   [E] the Philox stream of every run (repeats allowed: equal streams on equal data give equal runs)
@@ -903,9 +903,10 @@ int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E,
  *                       each; the Philox stage index keeps counting, so that a run is the same however it is cut.
  *   keep->flags         0
  * keep == NULL, or rec_u == NULL with no round owed, launches the kernels of vmx_smc_run / vmx_smc_run_many; otherwise the stage
- * heads are k_smc_stage_kept / k_smc_set_stage_kept (smc_stage under its KEPT flag), the sweeps k_smc_move / k_smc_set_move as they
- * are.  In a set, runs on the ladder and runs in posterior rounds stand side by side in one launch; a run at beta = 1 that owes
- * rounds has status 0 and stays in the active list, and gets status 1 in the round that pays its last one.
+ * heads are k_smc_stage_kept (smc_stage under its KEPT flag), the sweeps k_smc_move as they are - the same kernels with one
+ * work-group per run still going.  In a set, runs on the ladder and runs in posterior rounds stand side by side in one launch; a
+ * run at beta = 1 that owes rounds has status 0 and stays in the active list, and gets status 1 in the round that pays its last
+ * one.
  *   stats     single run: a ladder stage waits on beta as before; the posterior rounds of a call need no decision of the host and
  *             are enqueued back to back with one wait: host_waits = ladder stages + (1 if the call ran a posterior round) + 1 (the
  *             copy back) + 1 with draw.  The set keeps one wait per round: host_waits = rounds + 1 + 1 with draw.

@@ -25,8 +25,7 @@ for p in (REPO, REPO / 'tests'):
         sys.path.insert(0, str(p))
 
 SAMPLED = ['ap', 'at', 'bias_eta_LYA', 'beta_LYA', 'beta_QSO', 'bias_hcd']
-KERNELS = ('k_smc_set_stage', 'k_smc_set_move', 'k_smc_set_start_lnl', 'k_smc_set_start', 'k_smc_stage', 'k_smc_move',
-           'k_smc_start_lnl', 'k_smc_start')
+KERNELS = ('k_smc_stage', 'k_smc_move', 'k_smc_start_lnl', 'k_smc_start')       # (k_smc_stage: k_smc_stage_kept too)
 
 
 def kernel_stats(folder):

@@ -3,6 +3,7 @@ vega_amd/smc.py) on real engines: the same particles and ancestors bit for bit, 
 calls or chunks, the exact evidence and posterior of parameters the model is linear in, the evidence of the nested sampler on the
 physical parameters, refused arguments that leave the engine as it was, engine groups, and the config switch end to end."""
 import configparser
+import ctypes as C
 import math
 
 import numpy as np
@@ -109,6 +110,17 @@ def test_the_run_does_not_depend_on_the_cut_or_the_chunks(auto_vega):
     assert cut.stats['host_waits'] == 4 + 4 + 1       # (a wait per stage, a copy back per call, the start)
 
 
+@pytest.mark.parametrize('N', [24, 1056])
+def test_drivers_agree_at_awkward_sizes(auto_vega, N):
+    """N = 24: fewer than a wavefront, padded to 32; N = 1056: more than one particle per lane and a segment length of 2.  Stream
+    2, two stages of two sweeps on the linear coefficients."""
+    sp = _linear_box(auto_vega)[0]
+    dev, py = _pair(auto_vega, sp, 2, particles=N, sweeps=2, seed=3, stream=2)
+    _assert_same(dev, py)
+    assert dev.stage == 2 and 0.0 < dev.beta < 1.0 and dev.stats['rows'] == N * (1 + 2 * 2)
+    assert dev.stats['host_waits'] == dev.stats['stages'] + 2
+
+
 def test_linear_parameters_give_the_exact_evidence(auto_vega):
     """chi2 = chi2_min + (b - b*)^T F (b - b*) exactly, so over the box b* +- 10 sd: log Z = lnL(b*) + 1/2 log|2 pi cov| -
     sum log(20 sd) (tests/test_nested_gpu.py).  N = 1024 equal-weight particles: ESS = N in that test's bounds."""
@@ -185,6 +197,44 @@ def test_refused_arguments_leave_the_engine_as_it_was(auto_vega):
     for case in cases:
         _refused(eng, **case)
         np.testing.assert_array_equal(auto_vega.chi2_batch(theta), before)
+
+
+def test_a_ladder_that_cannot_advance_fails_the_call_and_nothing_else(auto_vega):
+    """N = 8 particles of which one has a finite lnL: ESS = 1 at every beta, below ess N = 4, so that the head hands back beta_t =
+    beta_{t-1}.  vmx_smc_run answers -2; u, lnl and the stage are the caller's, and the next run is the run it was before."""
+    from vega_amd import engine as G
+    from vega_amd.smc import draw_start
+    eng = auto_vega.engine
+    box = dict(cols=[eng.names.index('bias_eta_LYA'), eng.names.index('beta_LYA')], lo=[-0.5, 0.5], hi=[0.0, 3.0],
+               theta_fixed=eng.low.theta0.copy())
+
+    def ordinary():
+        u, lnl = np.zeros((16, 2)), np.zeros(16)
+        rec, stage, beta, scale, st = eng.smc_run(u=u, lnl=lnl, stage=0, beta=0.0, scale=1.0, n_stages=1, ess=0.5, sweeps=3, seed=6,
+                                                  stream=1, draw=True, **box)
+        return u, lnl, rec[0]['lnl'], rec[0]['anc'], np.array([stage, beta, scale, rec[0]['accepted'], st['rows']])
+
+    before = ordinary()
+    u = np.ascontiguousarray(draw_start(8, 2, 1, 0))
+    lnl = np.array([-np.inf] * 7 + [0.0])
+    u0, lnl0 = u.copy(), lnl.copy()
+    with pytest.raises(G.EngineError, match='cannot advance'):
+        eng.smc_run(u=u, lnl=lnl, stage=0, beta=0.0, scale=1.0, n_stages=2, ess=0.5, sweeps=3, **box)
+    assert np.array_equal(u, u0) and np.array_equal(lnl, lnl0)
+    # the raw entry: the stage, beta, scale and statistics words are the caller's too
+    cols, lo, hi, theta, _ = eng._sampled_box(box['cols'], box['lo'], box['hi'], box['theta_fixed'], u=u, lnl=lnl)
+    rec, rec_lnl, rec_anc = np.full((2, G.VMX_SMC_REC), 7.0), np.full((2, 8), 7.0), np.full((2, 8), 7, dtype=np.int32)
+    spec = G.SmcSpec(eng.n_params, 2, G._ip(cols), G._dp(lo), G._dp(hi), 8, 3, 0.5, 0.0, 0, 0, G._dp(theta))
+    opt, stats = G.SmcOptions(-1, 0, 0, 0), G.SmcStats()
+    stats.stages, stats.rows = -5, -5
+    st, b, sc = C.c_int64(4), C.c_double(0.25), C.c_double(0.5)
+    assert eng.lib.vmx_smc_run(eng._h, C.byref(spec), G._dp(u), G._dp(lnl), C.byref(st), C.byref(b), C.byref(sc), 2, G._dp(rec),
+                               G._dp(rec_lnl), G._ip(rec_anc), C.byref(opt), C.byref(stats)) == -2
+    assert b'cannot advance' in eng.lib.vmx_last_error() and (st.value, b.value, sc.value) == (4, 0.25, 0.5)
+    assert np.array_equal(u, u0) and np.array_equal(lnl, lnl0) and (stats.stages, stats.rows) == (-5, -5)
+    assert np.all(rec == 7.0) and np.all(rec_lnl == 7.0) and np.all(rec_anc == 7)
+    for a, b in zip(ordinary(), before):
+        assert np.array_equal(a, b)
 
 
 def test_an_engine_group_takes_the_python_driver():

@@ -188,6 +188,51 @@ def test_a_set_of_one_is_the_single_kept_run(auto_vega, linear_box):
     assert member.log_evidence() == one.log_evidence() and member.finished
 
 
+@pytest.mark.parametrize('kept', [False, True])
+def test_the_exported_entries_side_by_side(auto_vega, linear_box, kept):
+    """``Engine.smc_run`` (vmx_smc_run, vmx_smc_run_kept) beside ``Engine.smc_run_many`` with E = 1 (vmx_smc_run_many,
+    vmx_smc_run_many_kept) at N = 24 on stream 2: a call of two stages from the draw, then a call entered at stage 2 that ends
+    the run - with ``kept``, through the two posterior rounds owed.  Every array and every statistic is equal but the seconds and
+    ``host_waits``, which follows each entry's own rule (include/vegamx.h)."""
+    from vega_amd import SMCSampler
+    N, n, sweeps = 24, 4, 2
+    s = SMCSampler(auto_vega, particles=N, sweeps=sweeps, seed=3, stream=2, sample_params=linear_box)
+    eng = auto_vega.engine
+    kw = dict(log_norm=s.log_norm(), seed=3)
+    u1, l1 = np.zeros((N, n)), np.zeros(N)
+    uE, lE = np.zeros((1, N, n)), np.zeros((1, N))
+    stage, beta, scale = np.zeros(1, dtype=np.int64), np.zeros(1), np.ones(1)
+    left = np.full(1, 2, dtype=np.int32)
+    one = (0, 0.0, 1.0, 2)
+    for call, n_stages in enumerate((2, 40)):
+        draw = call == 0
+        out = eng.smc_run(s.cols, s.lo, s.hi, s._fixed_row(), u1, l1, one[0], one[1], one[2], n_stages, 0.5, sweeps, stream=2, draw=draw,
+                          **(dict(keep=True, topups_left=one[3]) if kept else {}), **kw)
+        rec1, st1 = out[0], out[-1]
+        one = out[1:4] + ((out[4],) if kept else (0,))
+        recE, status, done, stE = eng.smc_run_many(s.cols, s.lo, s.hi, s._fixed_row(), uE, lE, stage, beta, scale, [2], n_stages, 0.5, sweeps,
+                                                   draw=draw, **(dict(keep=True, topups_left=left) if kept else {}), **kw)
+        assert np.array_equal(uE[0], u1) and np.array_equal(lE[0], l1)
+        assert (int(stage[0]), float(beta[0]), float(scale[0])) == one[:3] and done[0] == len(rec1) == len(recE[0]) == st1['stages']
+        assert not kept or int(left[0]) == one[3]
+        for a, b in zip(rec1, recE[0]):
+            assert set(a) == set(b) and ('u' in a) == kept
+            for key in a:
+                assert np.array_equal(a[key], b[key]), key
+        for key in st1:
+            if not key.startswith('seconds') and key != 'host_waits':
+                assert st1[key] == stE[key], key
+        assert stE['per_run'].tolist() == [[st1['accepted'], st1['rows_own_position'], st1['rejected_failed_model'], st1['rows']]]
+        ladder = sum(1 for r in rec1 if r['beta_prev'] < 1.0)
+        rounds = len(rec1) - ladder
+        assert st1['host_waits'] == ladder + (1 if rounds else 0) + 1 + (1 if draw else 0)
+        assert stE['host_waits'] == len(rec1) + 1 + (1 if draw else 0)
+        if call == 0:
+            assert one[0] == 2 and 0.0 < one[1] < 1.0 and status[0] == 0
+    assert one[1] == 1.0 and status[0] == 1 and rounds == (2 if kept else 0) and ladder >= 1 and one[0] == 2 + ladder + rounds < 42
+    assert one[3] == 0
+
+
 def test_runs_that_owe_different_rounds(mock_vega):  # noqa: F811
     """E = 3 x N = 64 through the engine's call with topups_left = (2, 0, 1), streams (0, 1, 1) and mock rows (2, 0, 0), round by
     round and whole, against ``python_stages_many`` (the python driver of SMCSet): the statuses after every round, the active

@@ -498,6 +498,156 @@ def test_recycled_chain_keeps_the_masses_of_two_modes():
     assert abs(p_rec - p_last) <= 0.02
 
 
+# ------------------------------------------------------------------ the single run is the set of one
+from vega_amd.smc import accept, adapt, posterior_round_head, propose, run_finished, stage_head  # noqa: E402  (the names the body below reads)
+
+
+def _reference_python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, watch=None, topups_left=0, keep=None):
+    """Up to ``n_stages`` stages in NumPy from the state ``u`` [N, n], ``lnl`` [N] (updated in place), stopping after the stage
+    that reaches beta = 1.  ``evaluate(rows_u)`` -> lnL [N] of rows in the cube (-inf: a failed model).  ``watch(stage, sweep, u,
+    lnl, scale, accepted)`` is called after every sweep.  Returns (record: a list of dicts per stage with beta_prev, beta, ess,
+    lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale, stats).
+
+    ``topups_left`` posterior rounds are owed at beta = 1 (vmx_smc.h: "kept populations and posterior rounds"): the run then goes
+    on with stages headed by :func:`posterior_round_head`, one record row each (beta_prev = beta = 1), ``n_stages`` bounding both
+    kinds together.  ``keep``, a list, receives the particles at the entry of every stage done.  With either, the rounds still
+    owed are returned after ``scale``: (record, stage, beta, scale, topups_left, stats)."""
+    N, n = u.shape
+    record = []
+    new_form = keep is not None or bool(topups_left)
+    topups_left = int(topups_left)
+    st = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0)
+    for _ in range(n_stages):
+        if run_finished(beta, topups_left):
+            break
+        if keep is not None:
+            keep.append(u.copy())
+        if beta >= 1.0:
+            head = posterior_round_head(u, lnl)
+            topups_left -= 1
+        else:
+            head = stage_head(u, lnl, beta, ess, stage, seed, stream)
+        if math.isnan(head['beta']):
+            raise ValueError('SMC: no particle has a finite log-likelihood')
+        if beta < 1.0 and not head['beta'] > beta:
+            raise ValueError('SMC: the temperature ladder cannot advance: fewer than ess N particles carry weight')
+        rec = dict(beta_prev=beta, beta=head['beta'], ess=head['ess'], lnl=lnl.copy(), anc=head['anc'], cholesky=head['cholesky'])
+        u[:], lnl[:] = head['u'], head['lnl']
+        beta = head['beta']
+        acc_stage = 0
+        for s in range(sweeps):
+            y, inside, ua = propose(u, head['C'], scale, stage, s, seed, stream)
+            lnl_new = np.asarray(evaluate(np.where(inside[:, None], y, u)), dtype=np.float64)
+            ok = lnl_new > -np.inf
+            acc = accept(inside, ok, beta, lnl_new, lnl, ua)
+            u[acc] = y[acc]
+            lnl[acc] = lnl_new[acc]
+            k = int(acc.sum())
+            scale = adapt(scale, k, N)
+            acc_stage += k
+            st['rows'] += N
+            st['rows_own_position'] += int((~inside).sum())
+            st['rejected_failed_model'] += int((inside & ~ok).sum())
+            if watch is not None:
+                watch(stage, s, u, lnl, scale, k)
+        st['sweeps'] += sweeps
+        st['accepted'] += acc_stage
+        st['stages'] += 1
+        rec.update(accepted=acc_stage, scale=scale)
+        record.append(rec)
+        stage += 1
+    if new_form:
+        return record, stage, beta, scale, topups_left, st
+    return record, stage, beta, scale, st
+
+
+def _both(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, loglike, **kw):
+    """``python_stages`` and the body it had before it became the set of one (above, verbatim), each on its own copy of the state:
+    everything they hand back and leave behind is equal, bit for bit.  Returns what the reference returned, its u and lnl."""
+    out = []
+    for run in (_reference_python_stages, S.python_stages):
+        own = dict(kw, keep=[]) if 'keep' in kw else dict(kw)
+        uu, ll = u.copy(), lnl.copy()
+        out.append((run(uu, ll, stage, beta, scale, n_stages, ess, sweeps, seed, stream, loglike, **own), uu, ll, own.get('keep')))
+    (ref, ru, rl, rk), (got, gu, gl, gk) = out
+    assert np.array_equal(ru, gu) and np.array_equal(rl, gl) and len(ref) == len(got) and len(ref[0]) == len(got[0])
+    for a, b in zip(ref[0], got[0]):
+        assert set(a) == set(b) == {'beta_prev', 'beta', 'ess', 'lnl', 'anc', 'accepted', 'scale', 'cholesky'}
+        for key in a:
+            assert np.array_equal(a[key], b[key]) and type(a[key]) is type(b[key]), key
+    assert ref[1:-1] == got[1:-1] and [type(v) for v in ref[1:-1]] == [type(v) for v in got[1:-1]]     # stage, beta, scale(, topups_left)
+    assert ref[-1] == got[-1] and list(ref[-1]) == list(got[-1])
+    assert (rk is None) == (gk is None)
+    if rk is not None:
+        assert len(rk) == len(gk) == len(ref[0]) and all(np.array_equal(a, b) for a, b in zip(rk, gk))
+    return ref, ru, rl
+
+
+def _drawn(N, n, seed, stream, loglike):
+    u = np.ascontiguousarray(S.draw_start(N, n, seed, stream))
+    return u, loglike(u)
+
+
+def test_one_run_from_a_fresh_draw_and_entered_on_the_ladder():
+    """(a) from the start particles of stream 5; (b) entered at stage 3 with beta inside (0, 1), two more stages."""
+    N, n, loglike = 64, 2, _gauss_loglike(2, sigma=0.01)
+    u, lnl = _drawn(N, n, 9, 5, loglike)
+    ref, u3, lnl3 = _both(u, lnl, 0, 0.0, S.start_scale(n), 3, 0.5, 4, 9, 5, loglike)
+    rec, stage, beta, scale, st = ref
+    assert stage == 3 and 0.0 < beta < 1.0 and st['stages'] == 3 and st['rows'] == 3 * 4 * N
+    ref = _both(u3, lnl3, stage, beta, scale, 2, 0.5, 4, 9, 5, loglike)[0]
+    assert ref[1] == 5 and ref[0][0]['beta_prev'] == beta and ref[-1]['stages'] == 2
+
+
+def test_one_run_cut_inside_its_posterior_rounds():
+    """(c) two rounds owed and a list for the kept populations; ``n_stages`` ends the call after the first round."""
+    N, n, loglike = 64, 2, _gauss_loglike(2)
+    u, lnl = _drawn(N, n, 4, 0, loglike)
+    ladder = len(_reference_python_stages(u.copy(), lnl.copy(), 0, 0.0, S.start_scale(n), 64, 0.5, 4, 4, 0, loglike)[0])
+    assert 3 <= ladder < 64
+    ref, u1, lnl1 = _both(u, lnl, 0, 0.0, S.start_scale(n), ladder + 1, 0.5, 4, 4, 0, loglike, topups_left=2, keep=[])
+    rec, stage, beta, scale, left, st = ref
+    assert (stage, beta, left) == (ladder + 1, 1.0, 1) and rec[-1]['beta_prev'] == 1.0 and rec[-2]['beta_prev'] < 1.0
+    ref = _both(u1, lnl1, stage, beta, scale, 5, 0.5, 4, 4, 0, loglike, topups_left=left, keep=[])[0]      # (entered at beta = 1)
+    assert (ref[1], ref[4], len(ref[0])) == (ladder + 2, 0, 1)
+    assert len(_both(u1, lnl1, ref[1], 1.0, ref[3], 5, 0.5, 4, 4, 0, loglike, topups_left=0, keep=[])[0][0]) == 0       # (nothing is left)
+
+
+@pytest.mark.parametrize('N', [24, 1056])
+def test_one_run_at_awkward_sizes(N):
+    """(d) N = 24: not a power of two, fewer than a wavefront; N = 1056: beyond LANES, two particles per segment."""
+    n, loglike = 2, _gauss_loglike(2)
+    u, lnl = _drawn(N, n, 2, 1, loglike)
+    assert N < 64 or (N > S.LANES and -(-N // S.LANES) == 2)
+    ref = _both(u, lnl, 0, 0.0, S.start_scale(n), 2, 0.5, 3, 2, 1, loglike)[0]
+    assert ref[1] == 2 and ref[-1]['rows'] == 2 * 3 * N
+    _both(u, lnl, 0, 0.0, S.start_scale(n), 2, 0.5, 3, 2, 1, loglike, keep=[])
+
+
+@pytest.mark.parametrize('case, match', [('none finite', 'no particle has a finite log-likelihood'), ('one finite', 'cannot advance')])
+def test_one_run_that_cannot_go_on(case, match):
+    """(e) no particle with a finite lnL at the head; (f) one among -inf: ESS = 1 at every beta, below ess N.  The exception has the
+    reference's text, and ``u`` / ``lnl`` are left as the reference left them - it raised before it touched them, the set's
+    body puts a failed run's entry state back.  (The reference had appended the entry particles to ``keep`` by then; the list is
+    now left as it was.)"""
+    N, n, loglike = 16, 2, _gauss_loglike(2)
+    u = np.ascontiguousarray(S.draw_start(N, n, 1, 0))
+    lnl = np.full(N, -np.inf)
+    if case == 'one finite':
+        lnl[-1] = 0.0
+    left, texts = [], []
+    for run in (_reference_python_stages, S.python_stages):
+        uu, ll, keep = u.copy(), lnl.copy(), ['before']
+        with pytest.raises(ValueError, match=match) as err:
+            run(uu, ll, 0, 0.0, S.start_scale(n), 3, 0.5, 3, 1, 0, loglike, keep=keep)
+        left.append((uu, ll, keep))
+        texts.append(str(err.value))
+    assert texts[0] == texts[1]
+    assert np.array_equal(left[0][0], left[1][0]) and np.array_equal(left[0][1], left[1][1])
+    assert np.array_equal(left[1][0], u) and np.array_equal(left[1][1], lnl)
+    assert len(left[0][2]) == 2 and left[1][2] == ['before']
+
+
 # ------------------------------------------------------------------ config, writer, struct
 def _config(text):
     cfg = configparser.ConfigParser()

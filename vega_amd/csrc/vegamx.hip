@@ -1257,17 +1257,16 @@ struct SmcWorkspace {
     DevBuf<double> u, lnl, u2, lnl2, w, cum, mean, cov, chol, state, prop, uacc, rec, rec_lnl, rec_u;
     DevBuf<int32_t> inside, zero, rec_anc;
     DevBuf<int64_t> counters;
-    double* pin = nullptr; double* dpin = nullptr;          // mapped host memory: beta, accepted, scale of the stage; the start's count
-    // a set of runs (vmx_smc_run_many): the words [E][4] and the active list (pinned), the list, streams, stages and mocks on the device
-    double* set_pin = nullptr; double* set_dpin = nullptr; int32_t* set_active = nullptr; size_t set_runs = 0;
+    // mapped host memory [runs][4]: beta, accepted, scale of the stage, the start's count; the active list (pinned)
+    double* pin = nullptr; double* dpin = nullptr; int32_t* pin_active = nullptr; size_t runs = 0;
+    // the list, streams, stages and mocks of the runs on the device
     DevBuf<int32_t> active, mock_row, mock;
     DevBuf<uint64_t> streams;
     DevBuf<int64_t> stage0;
     ~SmcWorkspace()
     {
         if (pin) (void)hipHostFree(pin);
-        if (set_pin) (void)hipHostFree(set_pin);
-        if (set_active) (void)hipHostFree(set_active);
+        if (pin_active) (void)hipHostFree(pin_active);
     }
 };
 
@@ -1559,22 +1558,10 @@ __device__ __forceinline__ void smc_move(const SmcDev& D, int64_t stage, int s_d
     smc_write_rows(D, true);
 }
 
-// the single run (vmx_smc_run): one work-group
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcDev D) { smc_start(D); }
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcDev D) { smc_start_lnl(D); }
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcDev D, int64_t stage, int64_t rec) { smc_stage(D, stage, rec); }
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcDev D, int64_t stage, int s_dec, int s_prop, int64_t rec)
-{
-    smc_move(D, stage, s_dec, s_prop, rec);
-}
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage_kept(SmcDev D, int64_t stage, int64_t rec, double* rec_u)
-{
-    smc_stage<true>(D, stage, rec, rec_u);
-}
-
-// A set of runs (vmx_smc_run_many): work-group a of a launch owns run active[a] - the functions above over that run's part of
-// every array - and the engine rows a N .. (a + 1) N - 1; nothing crosses runs.  `run0` is the view of run 0 on the rows of slot
-// 0.  Every active run is at record row `round` of the call and at stage stage0[run] + round of its own count.
+// The kernels, for a set of runs (vmx_smc_run_many; vmx_smc_run is the set of one): work-group a of a launch owns run active[a] -
+// the functions above over that run's part of every array - and the engine rows a N .. (a + 1) N - 1; nothing crosses runs.
+// `run0` is the view of run 0 on the rows of slot 0.  Every active run is at record row `round` of the call and at stage
+// stage0[run] + round of its own count.
 struct SmcSetDev {
     SmcDev run0;
     const int32_t* active;              // [A] the runs still going, ascending
@@ -1608,7 +1595,7 @@ __device__ __forceinline__ void smc_write_mock(const SmcSetDev& S, int run)
     for (int i = threadIdx.x; i < N; i += SMC_THREADS) S.mock[(size_t)blockIdx.x * N + i] = m;
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_start(SmcSetDev S)
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start(SmcSetDev S)
 {
     int run;
     const SmcDev D = smc_view(S, run);
@@ -1616,14 +1603,14 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_set_start(SmcSetDev S)
     smc_start(D);
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_start_lnl(SmcSetDev S)
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_start_lnl(SmcSetDev S)
 {
     int run;
     const SmcDev D = smc_view(S, run);
     smc_start_lnl(D);
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage(SmcSetDev S, int64_t round)
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage(SmcSetDev S, int64_t round)
 {
     int run;
     const SmcDev D = smc_view(S, run);
@@ -1631,7 +1618,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage(SmcSetDev S, int6
 }
 
 // (rec_u [E][rec_rows][N][n])
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage_kept(SmcSetDev S, int64_t round, double* rec_u)
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_stage_kept(SmcSetDev S, int64_t round, double* rec_u)
 {
     int run;
     const SmcDev D = smc_view(S, run);
@@ -1639,7 +1626,7 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_set_stage_kept(SmcSetDev S,
     smc_stage<true>(D, S.stage0[run] + round, round, rec_u);
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void k_smc_set_move(SmcSetDev S, int64_t round, int s_dec, int s_prop)
+__global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcSetDev S, int64_t round, int s_dec, int s_prop)
 {
     int run;
     const SmcDev D = smc_view(S, run);
@@ -6026,202 +6013,16 @@ static int nested_run_many(const char* who, vmx_engine* e, const vmx_nested_spec
 // ---- evidence where the particles live (vmx_smc.h)
 static_assert(VMX_SMC_MAX_PARTICLES == vmx_smc::MAX_PARTICLES && VMX_NS_MAXN == vmx_smc::MAXN, "SMC limits");
 
-// vmx_smc_run (keep = nullptr) and vmx_smc_run_kept
-static int smc_run_single(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage,
-                          double* beta, double* scale, int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc,
-                          const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats)
-{
-    REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale, name);
-    double* const rec_u = keep ? keep->rec_u : nullptr;
-    int32_t owed = keep && keep->topups_left ? *keep->topups_left : 0;
-    REQUIRE(!keep || keep->flags == 0, name + ": keep->flags must be 0");
-    REQUIRE(owed >= 0, name + ": topups_left >= 0");
-    REQUIRE(owed == 0 || rec_u, name + ": posterior rounds are owed, but there is no rec_u");
-    const bool kept = rec_u != nullptr || owed > 0;         // (neither: the kernels of vmx_smc_run)
-    std::vector<char> varies;
-    std::vector<int32_t> inv;
-    if (check_box(name, e, spec, VMX_NS_MAXN, varies, inv)) return -1;
-    const int n = spec->n, P = e->n_params, N = spec->N, sweeps = spec->sweeps;
-    REQUIRE(N >= std::max(2 * n + 2, 8) && N <= VMX_SMC_MAX_PARTICLES, name + ": max(2 n + 2, 8) .. 4096 particles");
-    REQUIRE(spec->ess > 0.0 && spec->ess < 1.0, name + ": 0 < ess < 1");
-    REQUIRE(sweeps >= 1, name + ": sweeps >= 1");
-    REQUIRE(n_stages >= 0 && *stage >= 0 && *stage < ((int64_t)1 << 31), name + ": n_stages >= 0, 0 <= stage < 2^31");
-    REQUIRE(n_stages == 0 || (rec && rec_lnl && rec_anc), name + ": the stage record");
-    const bool draw = opt && opt->draw != 0;
-    REQUIRE(!draw || *stage == 0, name + ": particles are drawn at stage 0");
-    if (!draw) {
-        REQUIRE(*beta >= 0.0 && *beta <= 1.0, name + ": beta in [0, 1]");
-        REQUIRE(*scale > 0.0 && std::isfinite(*scale), name + ": a positive scale");
-        bool any = false;
-        for (int i = 0; i < N; ++i) {
-            REQUIRE(!std::isnan(lnl[i]), name + ": a particle has a NaN lnL");
-            any = any || lnl[i] > -INFINITY;
-            for (int d = 0; d < n; ++d) {
-                const double v = u[(size_t)i * n + d];
-                REQUIRE(v >= 0.0 && v <= 1.0, name + ": a particle lies outside the unit cube");
-            }
-        }
-        REQUIRE(any, name + ": no particle has a finite lnL");
-    }
-    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
-    const size_t rec_rows = (size_t)std::max(n_stages, 1);
-    REQUIRE(!rec_u || (size_t)N * n * sizeof(double) <= SIZE_MAX / rec_rows, name + ": the record is too large");
-
-    HIP_OK(hipSetDevice(e->device));
-    const auto t_begin = std::chrono::steady_clock::now();
-    if (!e->smcws) e->smcws = new SmcWorkspace();
-    SmcWorkspace& S = *e->smcws;
-    if (ensure(S.u, (size_t)N * n) || ensure(S.lnl, N) || ensure(S.u2, (size_t)N * n) || ensure(S.lnl2, N) || ensure(S.w, N) ||
-        ensure(S.cum, N) || ensure(S.zero, N) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) ||
-        ensure(S.state, 2) || ensure(S.prop, (size_t)N * n) || ensure(S.uacc, N) || ensure(S.inside, N) ||
-        ensure(S.rec, rec_rows * VMX_SMC_REC) || ensure(S.rec_lnl, rec_rows * N) || ensure(S.rec_anc, rec_rows * N) ||
-        ensure(S.counters, 3) || (rec_u && ensure(S.rec_u, rec_rows * N * n)))
-        return -2;
-    if (!S.pin) {
-        HIP_OK(hipHostMalloc((void**)&S.pin, 4 * sizeof(double), hipHostMallocMapped));
-        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin, S.pin, 0));
-    }
-    hipStream_t st = e->stream;
-    const double state0[2] = {*beta, *scale};
-    if (!draw) {
-        HIP_OK(hipMemcpyAsync(S.u.p, u, (size_t)N * n * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(S.lnl.p, lnl, (size_t)N * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_OK(hipMemcpyAsync(S.state.p, state0, sizeof state0, hipMemcpyHostToDevice, st));
-    }
-    HIP_OK(hipMemsetAsync(S.zero.p, 0, (size_t)N * sizeof(int32_t), st));
-    HIP_OK(hipMemsetAsync(S.counters.p, 0, 3 * sizeof(int64_t), st));
-    HIP_OK(hipMemsetAsync(S.rec.p, 0, rec_rows * VMX_SMC_REC * sizeof(double), st));
-    SmcDev D{};
-    if (S.box.upload(N, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
-    D.u = S.u.p; D.lnl = S.lnl.p; D.u2 = S.u2.p; D.lnl2 = S.lnl2.p; D.w = S.w.p; D.cum = S.cum.p; D.zero = S.zero.p;
-    D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.state = S.state.p;
-    D.prop = S.prop.p; D.uacc = S.uacc.p; D.inside = S.inside.p;
-    D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.dpin;
-    D.N = N; D.n = n; D.P = P; D.sweeps = sweeps; D.ess = spec->ess; D.log_norm = spec->log_norm;
-    D.seed = spec->seed; D.stream = spec->stream;
-
-    // the engine as the sampler's likelihood, at the table level the sampled columns allow
-    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
-    vmx_smc_stats R{};
-    R.const_hint = L.hint;
-    R.lanes = L.lanes;
-    double enqueue_s = 0.0;
-    // the N rows a kernel has just written
-    auto evaluate = [&]() -> int {
-        const int calls = L.evaluate(S.box.theta.p, N, S.box.chi2.p, S.box.status.p, nullptr, true);
-        if (calls < 0) return -2;
-        R.engine_calls += calls;
-        R.rows += N;
-        return 0;
-    };
-    double b_now = *beta, scale_now = *scale;
-    if (draw) {
-        const auto t0 = std::chrono::steady_clock::now();
-        hipLaunchKernelGGL(k_smc_start, dim3(1), dim3(SMC_THREADS), 0, st, D);
-        HIP_OK(hipGetLastError());
-        if (evaluate()) return -2;
-        hipLaunchKernelGGL(k_smc_start_lnl, dim3(1), dim3(SMC_THREADS), 0, st, D);
-        HIP_OK(hipGetLastError());
-        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        HIP_OK(hipStreamSynchronize(st));       // (the start's wait: how many particles have a finite lnL)
-        R.host_waits += 1;
-        if (!(S.pin[3] > 0.0)) return fail(-2, name + ": no start particle has a finite lnL");
-        b_now = 0.0;
-        scale_now = vmx_smc::start_scale(n);
-    }
-    int done = 0;
-    // a stage's kernels: its head, the first proposals, and per sweep the engine and the sweep boundary
-    auto enqueue_stage = [&](int64_t t, int row) -> int {
-        if (kept) hipLaunchKernelGGL(k_smc_stage_kept, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)row, rec_u ? S.rec_u.p : nullptr);
-        else hipLaunchKernelGGL(k_smc_stage, dim3(1), dim3(SMC_THREADS), 0, st, D, t, (int64_t)row);
-        hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, -1, 0, (int64_t)row);
-        HIP_OK(hipGetLastError());
-        for (int s = 0; s < sweeps; ++s) {
-            if (evaluate()) return -2;
-            hipLaunchKernelGGL(k_smc_move, dim3(1), dim3(SMC_THREADS), 0, st, D, t, s, s + 1 < sweeps ? s + 1 : -1, (int64_t)row);
-            HIP_OK(hipGetLastError());
-        }
-        return 0;
-    };
-    while (done < n_stages && b_now < 1.0) {
-        const int64_t t = *stage + done;
-        const auto t0 = std::chrono::steady_clock::now();
-        if (enqueue_stage(t, done)) return -2;
-        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        HIP_OK(hipStreamSynchronize(st));       // (the stage's only wait: beta, acceptance and scale, three mapped words)
-        R.host_waits += 1;
-        const double b = S.pin[0];
-        if (std::isnan(b)) return fail(-2, name + ": no particle has a finite lnL");
-        if (!(b > b_now)) return fail(-2, name + ": the temperature ladder cannot advance: fewer than ess N particles carry weight");
-        b_now = b;
-        scale_now = S.pin[2];
-        R.accepted += (int64_t)S.pin[1];
-        done += 1;
-    }
-    // the posterior rounds this call may run need no decision of the host: all of them back to back, one wait
-    const int ladder_done = done;
-    if (b_now >= 1.0 && owed > 0 && done < n_stages) {
-        const int rounds = std::min(n_stages - done, (int)owed);
-        const auto t0 = std::chrono::steady_clock::now();
-        for (int k = 0; k < rounds; ++k)
-            if (enqueue_stage(*stage + done + k, done + k)) return -2;
-        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        HIP_OK(hipStreamSynchronize(st));
-        R.host_waits += 1;
-        scale_now = S.pin[2];
-        done += rounds;
-        owed -= rounds;
-    }
-    std::vector<double> rec_host((size_t)std::max(done, 1) * VMX_SMC_REC);
-    HIP_OK(hipMemcpyAsync(u, S.u.p, (size_t)N * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIP_OK(hipMemcpyAsync(lnl, S.lnl.p, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (done > 0) {
-        HIP_OK(hipMemcpyAsync(rec_host.data(), S.rec.p, (size_t)done * VMX_SMC_REC * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(rec_lnl, S.rec_lnl.p, (size_t)done * N * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(rec_anc, S.rec_anc.p, (size_t)done * N * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        if (rec_u) HIP_OK(hipMemcpyAsync(rec_u, S.rec_u.p, (size_t)done * N * n * sizeof(double), hipMemcpyDeviceToHost, st));
-    }
-    HIP_OK(hipStreamSynchronize(st));
-    R.host_waits += 1;
-    for (int k = 0; k < done; ++k) {
-        R.rows_own_position += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 6];
-        R.rejected_failed_model += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 7];
-        if (k >= ladder_done) R.accepted += (int64_t)rec_host[(size_t)k * VMX_SMC_REC + 3];
-    }
-    if (done > 0) std::memcpy(rec, rec_host.data(), (size_t)done * VMX_SMC_REC * sizeof(double));
-    if (keep && keep->topups_left) *keep->topups_left = owed;
-    *stage += done;
-    *beta = b_now;
-    *scale = scale_now;
-    R.stages = done;
-    R.sweeps = (int64_t)done * sweeps;
-    R.seconds_enqueuing = enqueue_s;
-    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-    if (stats) *stats = R;
-    return 0;
-}
-
-int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
-                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
-                vmx_smc_stats* stats)
-{
-    return smc_run_single("vmx_smc_run", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, nullptr, opt, stats);
-}
-
-int vmx_smc_run_kept(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
-                     int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_keep* keep,
-                     const vmx_smc_options* opt, vmx_smc_stats* stats)
-{
-    return smc_run_single("vmx_smc_run_kept", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, keep, opt, stats);
-}
-
-// E independent runs advanced together (k_smc_set_*): one host round per stage for every run still going, the A N rows of a sweep
-// as one stream of chunks for the engine, every row with the mock of its run.  vmx_smc_run_many (keep = nullptr) and
-// vmx_smc_run_many_kept.
-static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams,
-                       const int32_t* mock_row, double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status,
-                       int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done,
-                       const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run)
+// E independent runs advanced together (k_smc_*): one host round per stage for every run still going, the A N rows of a sweep
+// as one stream of chunks for the engine, every row with the mock of its run.  The one body of the four entries: `name` is the
+// entry that was called, keep = nullptr the calls without kept populations, E = 1 the single run (smc_run_one).
+// rounds_back_to_back (the single run): while every run still going is at beta = 1 and owes posterior rounds, as many of them as
+// the call may run are enqueued with one wait; otherwise the host waits once per round.
+static int smc_run(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams,
+                   const int32_t* mock_row, double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status,
+                   int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done,
+                   const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run,
+                   bool rounds_back_to_back)
 {
     REQUIRE(e && e->finalized && spec && u && lnl && stage && beta && scale && status && stages_done, name);
     REQUIRE(E >= 1, name + ": at least one run");
@@ -6289,14 +6090,14 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
         ensure(S.counters, (size_t)E * 3) || ensure(S.active, E) || ensure(S.streams, E) || ensure(S.stage0, E) ||
         (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, EN))) || (rec_u && ensure(S.rec_u, rec_rows * EN * n)))
         return -2;
-    if (S.set_runs < (size_t)E) {
-        if (S.set_pin) { (void)hipHostFree(S.set_pin); S.set_pin = nullptr; }
-        if (S.set_active) { (void)hipHostFree(S.set_active); S.set_active = nullptr; }
-        S.set_runs = 0;
-        HIP_OK(hipHostMalloc((void**)&S.set_pin, (size_t)E * 4 * sizeof(double), hipHostMallocMapped));
-        HIP_OK(hipHostGetDevicePointer((void**)&S.set_dpin, S.set_pin, 0));
-        HIP_OK(hipHostMalloc((void**)&S.set_active, (size_t)E * sizeof(int32_t), hipHostMallocDefault));
-        S.set_runs = (size_t)E;
+    if (S.runs < (size_t)E) {
+        if (S.pin) { (void)hipHostFree(S.pin); S.pin = nullptr; }
+        if (S.pin_active) { (void)hipHostFree(S.pin_active); S.pin_active = nullptr; }
+        S.runs = 0;
+        HIP_OK(hipHostMalloc((void**)&S.pin, (size_t)E * 4 * sizeof(double), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin, S.pin, 0));
+        HIP_OK(hipHostMalloc((void**)&S.pin_active, (size_t)E * sizeof(int32_t), hipHostMallocDefault));
+        S.runs = (size_t)E;
     }
     hipStream_t st = e->stream;
     std::vector<double> state0((size_t)E * 2);
@@ -6318,7 +6119,7 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
     D.u = S.u.p; D.lnl = S.lnl.p; D.u2 = S.u2.p; D.lnl2 = S.lnl2.p; D.w = S.w.p; D.cum = S.cum.p; D.zero = S.zero.p;
     D.mean = S.mean.p; D.cov = S.cov.p; D.chol = S.chol.p; D.state = S.state.p;
     D.prop = S.prop.p; D.uacc = S.uacc.p; D.inside = S.inside.p;
-    D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.set_dpin;
+    D.rec = S.rec.p; D.rec_lnl = S.rec_lnl.p; D.rec_anc = S.rec_anc.p; D.counters = S.counters.p; D.host = S.dpin;
     D.N = N; D.n = n; D.P = P; D.sweeps = sweeps; D.ess = spec->ess; D.log_norm = spec->log_norm;
     D.seed = spec->seed; D.stream = 0;
     X.active = S.active.p; X.streams = S.streams.p; X.stage0 = S.stage0.p;
@@ -6332,10 +6133,10 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
     R.const_hint = L.hint;
     R.lanes = L.lanes;
     double enqueue_s = 0.0;
-    std::vector<int64_t> rows_of(E, 0), accepted_of(E, 0);
+    std::vector<int64_t> rows_of(E, 0);
     std::vector<int32_t> done(E, 0);
     std::vector<double> b_now(beta, beta + E), scale_now(scale, scale + E);
-    int32_t* active = S.set_active;
+    int32_t* active = S.pin_active;
     int A = vmx_smc::first_active_kept(beta, owed.data(), E, draw, active, status);
     // the list goes up on the stream: the host changes it only after it has waited for the stream
     auto put_active = [&]() -> int {
@@ -6354,50 +6155,61 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
     if (put_active()) return -2;
     if (draw) {
         const auto t0 = std::chrono::steady_clock::now();
-        hipLaunchKernelGGL(k_smc_set_start, dim3(A), dim3(SMC_THREADS), 0, st, X);
+        hipLaunchKernelGGL(k_smc_start, dim3(A), dim3(SMC_THREADS), 0, st, X);
         HIP_OK(hipGetLastError());
         if (evaluate()) return -2;
-        hipLaunchKernelGGL(k_smc_set_start_lnl, dim3(A), dim3(SMC_THREADS), 0, st, X);
+        hipLaunchKernelGGL(k_smc_start_lnl, dim3(A), dim3(SMC_THREADS), 0, st, X);
         HIP_OK(hipGetLastError());
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         HIP_OK(hipStreamSynchronize(st));       // (the start's wait: how many particles of every run have a finite lnL)
         R.host_waits += 1;
         for (int a = 0; a < A; ++a) {
             const int q = active[a];
-            status[q] = vmx_smc::start_status(S.set_pin[(size_t)q * 4 + 3]);
+            status[q] = vmx_smc::start_status(S.pin[(size_t)q * 4 + 3]);
             b_now[q] = 0.0;
             scale_now[q] = vmx_smc::start_scale(n);
         }
         const int B = vmx_smc::compact_active(active, A, status);
         if (B != A) { A = B; if (put_active()) return -2; }
     }
-    int round = 0;
-    while (round < n_stages && A > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (kept) hipLaunchKernelGGL(k_smc_set_stage_kept, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, rec_u ? S.rec_u.p : nullptr);
-        else hipLaunchKernelGGL(k_smc_set_stage, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round);
-        hipLaunchKernelGGL(k_smc_set_move, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, -1, 0);
+    // a round's kernels: the heads, the first proposals, and per sweep the engine and the sweep boundary
+    auto enqueue_round = [&](int64_t k) -> int {
+        if (kept) hipLaunchKernelGGL(k_smc_stage_kept, dim3(A), dim3(SMC_THREADS), 0, st, X, k, rec_u ? S.rec_u.p : nullptr);
+        else hipLaunchKernelGGL(k_smc_stage, dim3(A), dim3(SMC_THREADS), 0, st, X, k);
+        hipLaunchKernelGGL(k_smc_move, dim3(A), dim3(SMC_THREADS), 0, st, X, k, -1, 0);
         HIP_OK(hipGetLastError());
         for (int s = 0; s < sweeps; ++s) {
             if (evaluate()) return -2;
-            hipLaunchKernelGGL(k_smc_set_move, dim3(A), dim3(SMC_THREADS), 0, st, X, (int64_t)round, s, s + 1 < sweeps ? s + 1 : -1);
+            hipLaunchKernelGGL(k_smc_move, dim3(A), dim3(SMC_THREADS), 0, st, X, k, s, s + 1 < sweeps ? s + 1 : -1);
             HIP_OK(hipGetLastError());
         }
+        return 0;
+    };
+    int round = 0;
+    while (round < n_stages && A > 0) {
+        // posterior rounds need no decision of the host: back to back, as many as the call may run and every run still going owes
+        int burst = 1;
+        if (rounds_back_to_back) {
+            burst = n_stages - round;
+            for (int a = 0; a < A; ++a) burst = std::min(burst, b_now[active[a]] >= 1.0 ? owed[active[a]] : 1);
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        for (int k = 0; k < burst; ++k)
+            if (enqueue_round(round + k)) return -2;
         enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        HIP_OK(hipStreamSynchronize(st));       // (the round's only wait: beta, acceptance and scale of every run, mapped words)
+        HIP_OK(hipStreamSynchronize(st));       // (the only wait: beta and scale of every run after the last round, mapped words)
         R.host_waits += 1;
         for (int a = 0; a < A; ++a) {
             const int q = active[a];
-            const double* word = S.set_pin + (size_t)q * 4;
-            status[q] = vmx_smc::run_status_kept(b_now[q], word[0], owed[q]);
+            const double* word = S.pin + (size_t)q * 4;
+            for (int k = 0; k < burst; ++k) status[q] = vmx_smc::run_status_kept(b_now[q], word[0], owed[q]);
             if (status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK) continue;
             b_now[q] = word[0];
             scale_now[q] = word[2];
-            accepted_of[q] += (int64_t)word[1];
-            done[q] += 1;
+            done[q] += burst;
         }
         const int B = vmx_smc::compact_active(active, A, status);
-        round += 1;
+        round += burst;
         if (B != A) { A = B; if (put_active()) return -2; }
     }
     // the runs that ended by themselves or are still going come back; a failed run's arrays stay as they were at entry
@@ -6418,24 +6230,23 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
     HIP_OK(hipStreamSynchronize(st));
     R.host_waits += 1;
     for (int q = 0; q < E; ++q) {
-        int64_t own = 0, bad = 0;
+        int64_t took = 0, own = 0, bad = 0;     // (a failed run: done = 0)
         for (int k = 0; k < done[q]; ++k) {
             const double* r = rec_host.data() + ((size_t)q * rec_rows + k) * VMX_SMC_REC;
+            took += (int64_t)r[3];
             own += (int64_t)r[6];
             bad += (int64_t)r[7];
         }
         if (done[q] > 0)
             std::memcpy(rec + (size_t)q * n_stages * VMX_SMC_REC, rec_host.data() + (size_t)q * rec_rows * VMX_SMC_REC,
                         (size_t)done[q] * VMX_SMC_REC * sizeof(double));
-        const bool failed = status[q] == vmx_smc::NO_FINITE || status[q] == vmx_smc::STUCK;
-        if (failed) accepted_of[q] = 0;
-        else {
+        if (status[q] != vmx_smc::NO_FINITE && status[q] != vmx_smc::STUCK) {
             stage[q] += done[q]; beta[q] = b_now[q]; scale[q] = scale_now[q];
             if (keep && keep->topups_left) keep->topups_left[q] = owed[q];
         }
         stages_done[q] = done[q];
-        if (per_run) { per_run[4 * q] = accepted_of[q]; per_run[4 * q + 1] = own; per_run[4 * q + 2] = bad; per_run[4 * q + 3] = rows_of[q]; }
-        R.accepted += accepted_of[q];
+        if (per_run) { per_run[4 * q] = took; per_run[4 * q + 1] = own; per_run[4 * q + 2] = bad; per_run[4 * q + 3] = rows_of[q]; }
+        R.accepted += took;
         R.rows_own_position += own;
         R.rejected_failed_model += bad;
         R.stages += done[q];
@@ -6447,13 +6258,46 @@ static int smc_run_set(const std::string& name, vmx_engine* e, const vmx_smc_spe
     return 0;
 }
 
+// vmx_smc_run (keep = nullptr) and vmx_smc_run_kept: the set of one on spec->stream, the installed data and the caller's own words.
+// A run that cannot go on fails the call (-2); nothing of the caller's has been written then, *stats neither.
+static int smc_run_one(const std::string& name, vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage,
+                       double* beta, double* scale, int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc,
+                       const vmx_smc_keep* keep, const vmx_smc_options* opt, vmx_smc_stats* stats)
+{
+    int32_t status = 0, stages_done = 0;
+    vmx_smc_stats R{};
+    const int rc = smc_run(name, e, spec, 1, spec ? &spec->stream : nullptr, nullptr, u, lnl, stage, beta, scale, &status, n_stages, rec,
+                           rec_lnl, rec_anc, &stages_done, keep, opt, &R, nullptr, true);
+    if (rc) return rc;
+    if (status == vmx_smc::STUCK)
+        return fail(-2, name + ": the temperature ladder cannot advance: fewer than ess N particles carry weight");
+    if (status == vmx_smc::NO_FINITE)           // (after a draw with the start's rows alone evaluated: the start found none)
+        return fail(-2, name + (opt && opt->draw && R.rows == spec->N ? ": no start particle has a finite lnL" : ": no particle has a finite lnL"));
+    if (stats) *stats = R;
+    return 0;
+}
+
+int vmx_smc_run(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_options* opt,
+                vmx_smc_stats* stats)
+{
+    return smc_run_one("vmx_smc_run", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, nullptr, opt, stats);
+}
+
+int vmx_smc_run_kept(vmx_engine* e, const vmx_smc_spec* spec, double* u, double* lnl, int64_t* stage, double* beta, double* scale,
+                     int32_t n_stages, double* rec, double* rec_lnl, int32_t* rec_anc, const vmx_smc_keep* keep,
+                     const vmx_smc_options* opt, vmx_smc_stats* stats)
+{
+    return smc_run_one("vmx_smc_run_kept", e, spec, u, lnl, stage, beta, scale, n_stages, rec, rec_lnl, rec_anc, keep, opt, stats);
+}
+
 int vmx_smc_run_many(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
                      double* u, double* lnl, int64_t* stage, double* beta, double* scale, int32_t* status, int32_t n_stages,
                      double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_options* opt,
                      vmx_smc_stats* stats, int64_t* per_run)
 {
-    return smc_run_set("vmx_smc_run_many", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec, rec_lnl,
-                       rec_anc, stages_done, nullptr, opt, stats, per_run);
+    return smc_run("vmx_smc_run_many", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec, rec_lnl,
+                   rec_anc, stages_done, nullptr, opt, stats, per_run, false);
 }
 
 int vmx_smc_run_many_kept(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, const uint64_t* streams, const int32_t* mock_row,
@@ -6461,8 +6305,8 @@ int vmx_smc_run_many_kept(vmx_engine* e, const vmx_smc_spec* spec, int32_t E, co
                           double* rec, double* rec_lnl, int32_t* rec_anc, int32_t* stages_done, const vmx_smc_keep* keep,
                           const vmx_smc_options* opt, vmx_smc_stats* stats, int64_t* per_run)
 {
-    return smc_run_set("vmx_smc_run_many_kept", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec,
-                       rec_lnl, rec_anc, stages_done, keep, opt, stats, per_run);
+    return smc_run("vmx_smc_run_many_kept", e, spec, E, streams, mock_row, u, lnl, stage, beta, scale, status, n_stages, rec,
+                   rec_lnl, rec_anc, stages_done, keep, opt, stats, per_run, false);
 }
 
 void* vmx_stream(vmx_engine* e) { return e ? (void*)e->stream : nullptr; }

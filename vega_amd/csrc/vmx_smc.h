@@ -3,7 +3,7 @@
 // N particles walk from the prior (beta = 0) to the posterior (beta = 1) along a ladder of inverse temperatures chosen by the
 // effective sample size; every stage reweights, resamples, whitens and moves all particles by `sweeps` Metropolis sweeps under
 // L^beta.  The loop runs where the particles are (vmx_smc_run, vegamx.hip: k_smc_stage once per stage, k_smc_move once per
-// sweep); vega_amd/smc.py restates every expression below in NumPy (the `python` driver) and tests/helpers/smc_driver.cpp compiles
+// sweep, one work-group per run); vega_amd/smc.py restates every expression below in NumPy (the `python` driver) and tests/helpers/smc_driver.cpp compiles
 // this header with g++ so that tests/test_smc_host.py can hold the two against each other bit for bit.  No HIP type, no heap.
 //
 //   cube             particles live in u in [0, 1]^n (vmx_ns::map_cube: a uniform prior over the limits); lnL = log_norm - 0.5 chi2,
@@ -39,8 +39,9 @@
 //   start            beta = 0, scale = 2.38 sqrt(3 / n); the scale carries over from stage to stage.  After the sweeps of the stage
 //                    with beta_t = 1 the particles are the posterior sample, weight 1 / N each.
 //
-//   a set of runs   vmx_smc_run_many advances E such runs a stage per host round, one work-group per run; the status of a run and
-//                    the list of the runs still going are decided at the end of this header (tests/helpers/smc_set_driver.cpp).
+//   a set of runs   vmx_smc_run_many advances E such runs a stage per host round, one work-group per run (vmx_smc_run is the set
+//                    of one, by the same host body and kernels); the status of a run and the list of the runs still going are
+//                    decided at the end of this header (tests/helpers/smc_set_driver.cpp).
 //
 // Every expression is the separately rounded IEEE operations written below (contraction off, as in vmx_ensemble.h); sqrt and / are
 // correctly rounded.  The evidence is computed from the stage record by host Python (vega_amd/smc.py: evidence).

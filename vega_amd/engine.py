@@ -1474,6 +1474,39 @@ class Engine:
         """:func:`cluster_points` of this engine's device."""
         return cluster_points(u, prev_id, next_id, device=self.device)
 
+    def _smc_arrays(self, ndim, cols, lo, hi, theta_fixed, u, lnl, n_stages, kept, topups, *, ess, sweeps, log_norm, seed, stream,
+                    const_hint, chunk, lanes, draw):
+        """What :meth:`smc_run` (``ndim`` 2: u [N, n]) and :meth:`smc_run_many` (3: u [E, N, n]) hand the library alike: the box and
+        the particles checked as :meth:`_sampled_box` checks them; the spec; the call's arguments from ``n_stages`` to the record;
+        its last arguments - with ``kept`` the SmcKeep of the positions' record and ``topups`` (a pointer to the rounds owed, or
+        None), then the options and the statistics; ``stages(done, *run)``: the stage dicts of the first ``done`` record rows (of
+        run ``run``); the statistics; last, what the pointers borrow."""
+        _in_place(np.float64, u=u, lnl=lnl)
+        if u.ndim != ndim or lnl.shape != u.shape[:-1]:
+            raise ValueError('u [rows, n], lnl [rows]' if ndim == 2 else 'u [E, N, n], lnl [E, N]')
+        cols, lo, hi, theta_fixed, _ = self._sampled_box(cols, lo, hi, theta_fixed, u=u.reshape(-1, u.shape[-1]), lnl=lnl.reshape(-1))
+        n_stages, N = max(0, int(n_stages)), u.shape[-2]
+        lead = u.shape[:-2] + (n_stages,)
+        rec, rec_lnl, rec_anc = np.zeros(lead + (VMX_SMC_REC,)), np.empty(lead + (N,)), np.empty(lead + (N,), dtype=np.int32)
+        rec_u = np.empty(lead + (N, cols.size)) if kept else None
+        spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
+                       int(stream), _dp(theta_fixed))
+        opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
+        keep_arg = SmcKeep(_dp(rec_u), topups, 0) if kept else None
+        stats = SmcStats()
+
+        def stages(done, *run):
+            r, r_lnl, r_anc = rec[run], rec_lnl[run], rec_anc[run]
+            out = [dict(beta_prev=float(r[k, 0]), beta=float(r[k, 1]), ess=float(r[k, 2]), lnl=r_lnl[k].copy(), anc=r_anc[k].copy(),
+                        accepted=int(r[k, 3]), scale=float(r[k, 4]), cholesky=bool(r[k, 5])) for k in range(int(done))]
+            if kept:
+                for k, row in enumerate(out):
+                    row['u'] = rec_u[run][k].copy()
+            return out
+
+        tail = ((C.byref(keep_arg),) if kept else ()) + (C.byref(opt), C.byref(stats))
+        return spec, (n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc)), tail, stages, stats, (cols, lo, hi, theta_fixed, opt, keep_arg)
+
     def smc_run(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, n_stages, ess, sweeps, log_norm=0.0, seed=0, stream=0,
                 const_hint=-1, chunk=0, lanes=0, draw=False, keep=False, topups_left=None):
         """Up to ``n_stages`` stages of the tempered SMC sampler on the device (include/vegamx.h: vmx_smc_run): ``cols`` the sampled
@@ -1485,34 +1518,16 @@ class Engine:
         ``keep`` or ``topups_left`` (an int) go through vmx_smc_run_kept: every stage dict also carries ``u``, the particles at the
         stage's entry, the call goes on at beta = 1 with up to ``topups_left`` posterior rounds (``n_stages`` bounds both kinds), and
         the rounds still owed are returned after ``scale``."""
-        cols, lo, hi, theta_fixed, N = self._sampled_box(cols, lo, hi, theta_fixed, u=u, lnl=lnl)
         kept = bool(keep) or topups_left is not None
-        n_stages = max(0, int(n_stages))
-        rec, rec_lnl = np.zeros((n_stages, VMX_SMC_REC)), np.empty((n_stages, N))
-        rec_anc = np.empty((n_stages, N), dtype=np.int32)
-        spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
-                       int(stream), _dp(theta_fixed))
-        opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
-        stats = SmcStats()
+        owed = C.c_int32(int(topups_left or 0))
+        spec, recs, tail, stages, stats, _held = self._smc_arrays(
+            2, cols, lo, hi, theta_fixed, u, lnl, n_stages, kept, C.pointer(owed), ess=ess, sweeps=sweeps, log_norm=log_norm,
+            seed=seed, stream=stream, const_hint=const_hint, chunk=chunk, lanes=lanes, draw=draw)
         st, b, sc = C.c_int64(int(stage)), C.c_double(float(beta)), C.c_double(float(scale))
-        if kept:
-            rec_u = np.empty((n_stages, N, cols.size))
-            owed = C.c_int32(int(topups_left or 0))
-            keep_arg = SmcKeep(_dp(rec_u), C.pointer(owed), 0)
-            self._check(self.lib.vmx_smc_run_kept(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc),
-                                                  n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(keep_arg), C.byref(opt),
-                                                  C.byref(stats)))
-        else:
-            self._check(self.lib.vmx_smc_run(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc), n_stages,
-                                             _dp(rec), _dp(rec_lnl), _ip(rec_anc), C.byref(opt), C.byref(stats)))
-        record = [dict(beta_prev=float(rec[k, 0]), beta=float(rec[k, 1]), ess=float(rec[k, 2]), lnl=rec_lnl[k].copy(),
-                       anc=rec_anc[k].copy(), accepted=int(rec[k, 3]), scale=float(rec[k, 4]), cholesky=bool(rec[k, 5]))
-                  for k in range(int(stats.stages))]
-        if kept:
-            for k, r in enumerate(record):
-                r['u'] = rec_u[k].copy()
-            return record, int(st.value), float(b.value), float(sc.value), int(owed.value), _stats_dict(stats)
-        return record, int(st.value), float(b.value), float(sc.value), _stats_dict(stats)
+        run = self.lib.vmx_smc_run_kept if kept else self.lib.vmx_smc_run
+        self._check(run(self._h, C.byref(spec), _dp(u), _dp(lnl), C.byref(st), C.byref(b), C.byref(sc), *recs, *tail))
+        out = (stages(stats.stages), int(st.value), float(b.value), float(sc.value))
+        return out + ((int(owed.value),) if kept else ()) + (_stats_dict(stats),)
 
     def smc_run_many(self, cols, lo, hi, theta_fixed, u, lnl, stage, beta, scale, streams, n_stages, ess, sweeps, mock_rows=None,
                      log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, draw=False, keep=False, topups_left=None):
@@ -1526,12 +1541,15 @@ class Engine:
 
         ``keep`` or ``topups_left`` (int32 [E], updated in place: the posterior rounds every run still owes) go through
         vmx_smc_run_many_kept: every stage dict also carries ``u``, the run's particles at the stage's entry."""
-        _in_place(np.float64, u=u, lnl=lnl, beta=beta, scale=scale)
+        _in_place(np.float64, beta=beta, scale=scale)
         _in_place(np.int64, stage=stage)
-        if u.ndim != 3 or lnl.shape != u.shape[:2]:
-            raise ValueError('u [E, N, n], lnl [E, N]')
-        E, N = u.shape[:2]
-        cols, lo, hi, theta_fixed, _ = self._sampled_box(cols, lo, hi, theta_fixed, u=u.reshape(-1, u.shape[-1]), lnl=lnl.reshape(-1))
+        kept = bool(keep) or topups_left is not None
+        if topups_left is not None:
+            _in_place(np.int32, topups_left=topups_left)
+        spec, recs, tail, stages, stats, _held = self._smc_arrays(
+            3, cols, lo, hi, theta_fixed, u, lnl, n_stages, kept, None if topups_left is None else _ip(topups_left), ess=ess,
+            sweeps=sweeps, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes, draw=draw)
+        E = u.shape[0]
         if streams is not None:
             streams = np.ascontiguousarray(streams, dtype=np.uint64)
         if mock_rows is not None:
@@ -1539,37 +1557,14 @@ class Engine:
         if stage.shape != (E,) or beta.shape != (E,) or scale.shape != (E,) or (streams is not None and streams.shape != (E,)) or \
                 (mock_rows is not None and mock_rows.shape != (E,)):
             raise ValueError('stage [E], beta [E], scale [E], streams [E], mock_rows [E]')
-        n_stages = max(0, int(n_stages))
-        rec, rec_lnl = np.zeros((E, n_stages, VMX_SMC_REC)), np.empty((E, n_stages, N))
-        rec_anc = np.empty((E, n_stages, N), dtype=np.int32)
+        if topups_left is not None and topups_left.shape != (E,):
+            raise ValueError('topups_left [E]')
         status, done, per = np.zeros(E, dtype=np.int32), np.zeros(E, dtype=np.int32), np.zeros((E, 4), dtype=np.int64)
-        spec = SmcSpec(self.n_params, cols.size, _ip(cols), _dp(lo), _dp(hi), N, int(sweeps), float(ess), float(log_norm), int(seed),
-                       0, _dp(theta_fixed))
-        opt = SmcOptions(int(const_hint), int(chunk), int(lanes), 1 if draw else 0)
-        stats = SmcStats()
-        head = (self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-                None if mock_rows is None else _ip(mock_rows), _dp(u), _dp(lnl), stage.ctypes.data_as(C.POINTER(C.c_int64)), _dp(beta),
-                _dp(scale), _ip(status), n_stages, _dp(rec), _dp(rec_lnl), _ip(rec_anc), _ip(done))
-        tail = (C.byref(opt), C.byref(stats), per.ctypes.data_as(C.POINTER(C.c_int64)))
-        kept = bool(keep) or topups_left is not None
-        if kept:
-            if topups_left is not None:
-                _in_place(np.int32, topups_left=topups_left)
-                if topups_left.shape != (E,):
-                    raise ValueError('topups_left [E]')
-            rec_u = np.empty((E, n_stages, N, cols.size))
-            keep_arg = SmcKeep(_dp(rec_u), None if topups_left is None else _ip(topups_left), 0)
-            self._check(self.lib.vmx_smc_run_many_kept(*head, C.byref(keep_arg), *tail))
-        else:
-            self._check(self.lib.vmx_smc_run_many(*head, *tail))
-        records = [[dict(beta_prev=float(rec[e, k, 0]), beta=float(rec[e, k, 1]), ess=float(rec[e, k, 2]), lnl=rec_lnl[e, k].copy(),
-                         anc=rec_anc[e, k].copy(), accepted=int(rec[e, k, 3]), scale=float(rec[e, k, 4]),
-                         cholesky=bool(rec[e, k, 5])) for k in range(int(done[e]))] for e in range(E)]
-        if kept:
-            for e in range(E):
-                for k, r in enumerate(records[e]):
-                    r['u'] = rec_u[e, k].copy()
-        return records, status, done, dict(_stats_dict(stats), per_run=per)
+        run = self.lib.vmx_smc_run_many_kept if kept else self.lib.vmx_smc_run_many
+        self._check(run(self._h, C.byref(spec), E, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+                        None if mock_rows is None else _ip(mock_rows), _dp(u), _dp(lnl), stage.ctypes.data_as(C.POINTER(C.c_int64)),
+                        _dp(beta), _dp(scale), _ip(status), *recs, _ip(done), *tail, per.ctypes.data_as(C.POINTER(C.c_int64))))
+        return [stages(done[e], e) for e in range(E)], status, done, dict(_stats_dict(stats), per_run=per)
 
     def derived_const_hint(self, cols):
         """The table level that batches whose rows differ only in the columns ``cols`` allow (include/vegamx.h:

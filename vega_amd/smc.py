@@ -269,65 +269,6 @@ def run_finished(beta, topups_left):
     return beta >= 1.0 and topups_left <= 0
 
 
-def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, watch=None, topups_left=0, keep=None):
-    """Up to ``n_stages`` stages in NumPy from the state ``u`` [N, n], ``lnl`` [N] (updated in place), stopping after the stage
-    that reaches beta = 1.  ``evaluate(rows_u)`` -> lnL [N] of rows in the cube (-inf: a failed model).  ``watch(stage, sweep, u,
-    lnl, scale, accepted)`` is called after every sweep.  Returns (record: a list of dicts per stage with beta_prev, beta, ess,
-    lnl (before reweighting), anc, accepted, scale, cholesky; stage, beta, scale, stats).
-
-    ``topups_left`` posterior rounds are owed at beta = 1 (vmx_smc.h: "kept populations and posterior rounds"): the run then goes
-    on with stages headed by :func:`posterior_round_head`, one record row each (beta_prev = beta = 1), ``n_stages`` bounding both
-    kinds together.  ``keep``, a list, receives the particles at the entry of every stage done.  With either, the rounds still
-    owed are returned after ``scale``: (record, stage, beta, scale, topups_left, stats)."""
-    N, n = u.shape
-    record = []
-    new_form = keep is not None or bool(topups_left)
-    topups_left = int(topups_left)
-    st = dict(stages=0, sweeps=0, rows=0, rows_own_position=0, accepted=0, rejected_failed_model=0)
-    for _ in range(n_stages):
-        if run_finished(beta, topups_left):
-            break
-        if keep is not None:
-            keep.append(u.copy())
-        if beta >= 1.0:
-            head = posterior_round_head(u, lnl)
-            topups_left -= 1
-        else:
-            head = stage_head(u, lnl, beta, ess, stage, seed, stream)
-        if math.isnan(head['beta']):
-            raise ValueError('SMC: no particle has a finite log-likelihood')
-        if beta < 1.0 and not head['beta'] > beta:
-            raise ValueError('SMC: the temperature ladder cannot advance: fewer than ess N particles carry weight')
-        rec = dict(beta_prev=beta, beta=head['beta'], ess=head['ess'], lnl=lnl.copy(), anc=head['anc'], cholesky=head['cholesky'])
-        u[:], lnl[:] = head['u'], head['lnl']
-        beta = head['beta']
-        acc_stage = 0
-        for s in range(sweeps):
-            y, inside, ua = propose(u, head['C'], scale, stage, s, seed, stream)
-            lnl_new = np.asarray(evaluate(np.where(inside[:, None], y, u)), dtype=np.float64)
-            ok = lnl_new > -np.inf
-            acc = accept(inside, ok, beta, lnl_new, lnl, ua)
-            u[acc] = y[acc]
-            lnl[acc] = lnl_new[acc]
-            k = int(acc.sum())
-            scale = adapt(scale, k, N)
-            acc_stage += k
-            st['rows'] += N
-            st['rows_own_position'] += int((~inside).sum())
-            st['rejected_failed_model'] += int((inside & ~ok).sum())
-            if watch is not None:
-                watch(stage, s, u, lnl, scale, k)
-        st['sweeps'] += sweeps
-        st['accepted'] += acc_stage
-        st['stages'] += 1
-        rec.update(accepted=acc_stage, scale=scale)
-        record.append(rec)
-        stage += 1
-    if new_form:
-        return record, stage, beta, scale, topups_left, st
-    return record, stage, beta, scale, st
-
-
 # ------------------------------------------------------------------ a set of runs (vmx_smc.h: "a set of runs")
 RUNNING, FINISHED, NO_FINITE, STUCK = 0, 1, 2, 3
 
@@ -474,6 +415,35 @@ def python_stages_many(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, 
     if new_form:
         return records, status, done, owed, st
     return records, status, done, st
+
+
+def python_stages(u, lnl, stage, beta, scale, n_stages, ess, sweeps, seed, stream, evaluate, topups_left=0, keep=None):
+    """Up to ``n_stages`` stages of one run in NumPy: the set of one of :func:`python_stages_many`, from the state ``u`` [N, n],
+    ``lnl`` [N] (updated in place), stopping after the stage that reaches beta = 1.  ``evaluate(rows_u)`` -> lnL [N] of rows in the
+    cube (-inf: a failed model).  Returns (record: a list of dicts per stage with beta_prev, beta, ess, lnl (before reweighting),
+    anc, accepted, scale, cholesky; stage, beta, scale, stats).  A run that cannot go on raises ValueError and leaves ``u``,
+    ``lnl`` and ``keep`` as they were at entry.  (There is no ``watch`` hook any more: nothing called it.)
+
+    ``topups_left`` posterior rounds are owed at beta = 1 (vmx_smc.h: "kept populations and posterior rounds"): the run then goes
+    on with stages headed by :func:`posterior_round_head`, one record row each (beta_prev = beta = 1), ``n_stages`` bounding both
+    kinds together.  ``keep``, a list, receives the particles at the entry of every stage done.  With either, the rounds still
+    owed are returned after ``scale``: (record, stage, beta, scale, topups_left, stats)."""
+    new_form = keep is not None or bool(topups_left)
+    stage, beta, scale = np.array([stage], dtype=np.int64), np.array([beta], dtype=np.float64), np.array([scale], dtype=np.float64)
+    kept = [[]] if keep is not None else None
+    records, status, _, owed, st = python_stages_many(
+        u[None], lnl[None], stage, beta, scale, n_stages, ess, sweeps, seed, [stream], lambda rows_u, runs: evaluate(rows_u),
+        topups_left=np.array([int(topups_left)], dtype=np.int64), keep=kept)
+    if status[0] == NO_FINITE:
+        raise ValueError('SMC: no particle has a finite log-likelihood')
+    if status[0] == STUCK:
+        raise ValueError('SMC: the temperature ladder cannot advance: fewer than ess N particles carry weight')
+    if keep is not None:
+        keep.extend(kept[0])
+    st = {key: val for key, val in st.items() if key not in ('rounds', 'per_run')}
+    if new_form:
+        return records[0], int(stage[0]), float(beta[0]), float(scale[0]), int(owed[0]), st
+    return records[0], int(stage[0]), float(beta[0]), float(scale[0]), st
 
 
 # ------------------------------------------------------------------ evidence (host, both drivers)
