@@ -245,163 +245,8 @@ struct EnsDev {
     int64_t step0;
 };
 
-// One half-step of the sampler, a grid of E work-groups: work-group e owns ensemble e (partners read the half decided just before,
-// a dependency across the whole ensemble; nothing crosses ensembles, so __syncthreads() is the only barrier) under the Philox
-// stream streams[e].  Decide the proposals of half h_dec at step s_dec (s_dec < 0: none), record the chain row when step s_dec is
-// complete and due, then propose half h_prop at step s_prop (s_prop < 0: none) and write the engine's rows, so that the E H
-// proposal rows of a half-step are one stream of chunks for the engine.  Every expression: vmx_ensemble.h.
-constexpr int ENS_THREADS = 1024;
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
-{
-    const int W = D.W, H = W / 2, n = D.n;
-    const size_t e = blockIdx.x;
-    const uint64_t stream = D.streams[e];
-    double* const x = D.x + e * W * n;
-    double* const lnl = D.lnl + e * W;
-    int64_t* const acc = D.acc + e * W;
-    int64_t* const n_box = D.n_box + e * W;
-    int64_t* const n_fail = D.n_fail + e * W;
-    double* const prop = D.prop + e * H * n;
-    double* const factor = D.factor + e * H;
-    int32_t* const inside_of = D.inside + e * H;
-    const double* const chi2 = D.box.chi2 + e * H;
-    const int32_t* const status = D.box.status + e * H;
-    double* const theta = D.box.theta + e * H * D.P;
-    if (s_dec >= 0) {
-        for (int k = threadIdx.x; k < H; k += blockDim.x) {
-            const int w = h_dec * H + k;
-            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, stream);
-            const double c2 = chi2[k];
-            const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
-            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
-            if (vmx_ens::accept(inside, ok, factor[k], lnl_new, lnl[w], b.w[2])) {
-                for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
-                lnl[w] = lnl_new;
-                acc[w] += 1;
-            } else if (!inside) n_box[w] += 1;
-            else if (!ok) n_fail[w] += 1;
-        }
-        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
-            __syncthreads();
-            const size_t r = e * D.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
-            if (D.chain)
-                for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
-            if (D.chain_lnl)
-                for (int q = threadIdx.x; q < W; q += blockDim.x) D.chain_lnl[r * W + q] = lnl[q];
-        }
-    }
-    if (s_prop < 0) return;
-    __syncthreads();            // (the partners of the next half are the walkers just decided)
-    for (int k = threadIdx.x; k < H; k += blockDim.x) {
-        const int w = h_prop * H + k;
-        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
-        const int64_t j = vmx_ens::partner(b.w[0], H);
-        const double* c = x + (size_t)((1 - h_prop) * H + j) * n;
-        const double* s = x + (size_t)w * n;
-        const double z = vmx_ens::stretch_z(D.a, b.w[1]);
-        double* y = prop + (size_t)k * n;
-        bool in = true;
-        for (int d = 0; d < n; ++d) {
-            const double v = vmx_ens::propose(c[d], s[d], z);
-            y[d] = v;
-            in = in && v >= D.box.lo[d] && v <= D.box.hi[d];
-        }
-        factor[k] = vmx_ens::log_factor(n, z);
-        inside_of[k] = in ? 1 : 0;
-        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
-        double* row = theta + (size_t)k * D.P;
-        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
-        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
-    }
-}
-
 // The moves of vmx_ensemble_run_many_moves as the kernel reads them: the thresholds of the mixture and the moves' scales
 struct EnsMovesDev { double t0, t1, gamma0, sigma, gamma_s; };
-
-// k_ens_half with the move of every walker drawn from a mixture of the stretch, differential-evolution and snooker moves
-// (vmx_ensemble.h, "the differential-evolution and snooker moves"): the same grid, the same decide / record / propose order and
-// the same strided loops, so that the chain does not depend on the block size.  The decision does not know the move: the
-// proposal left its factor and whether it is inside.  The partners' rows - up to three distinct walkers - are read from the half
-// decided just before; the snooker move passes three times over the n columns of its four rows.
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMovesDev M, int64_t s_dec, int h_dec, int64_t s_prop,
-                                                                int h_prop)
-{
-    const int W = D.W, H = W / 2, n = D.n;
-    const size_t e = blockIdx.x;
-    const uint64_t stream = D.streams[e];
-    double* const x = D.x + e * W * n;
-    double* const lnl = D.lnl + e * W;
-    int64_t* const acc = D.acc + e * W;
-    int64_t* const n_box = D.n_box + e * W;
-    int64_t* const n_fail = D.n_fail + e * W;
-    double* const prop = D.prop + e * H * n;
-    double* const factor = D.factor + e * H;
-    int32_t* const inside_of = D.inside + e * H;
-    const double* const chi2 = D.box.chi2 + e * H;
-    const int32_t* const status = D.box.status + e * H;
-    double* const theta = D.box.theta + e * H * D.P;
-    if (s_dec >= 0) {
-        for (int k = threadIdx.x; k < H; k += blockDim.x) {
-            const int w = h_dec * H + k;
-            const vmx_ens::Block b = vmx_ens::step_block(k, s_dec, h_dec, D.seed, stream);
-            const double c2 = chi2[k];
-            const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
-            const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
-            if (vmx_ens::accept(inside, ok, factor[k], lnl_new, lnl[w], b.w[2])) {
-                for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
-                lnl[w] = lnl_new;
-                acc[w] += 1;
-            } else if (!inside) n_box[w] += 1;
-            else if (!ok) n_fail[w] += 1;
-        }
-        if (h_dec == 1 && (s_dec + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
-            __syncthreads();
-            const size_t r = e * D.rows + (size_t)((s_dec + 1) / D.thin - D.step0 / D.thin - 1);
-            if (D.chain)
-                for (int q = threadIdx.x; q < W * n; q += blockDim.x) D.chain[r * W * n + q] = x[q];
-            if (D.chain_lnl)
-                for (int q = threadIdx.x; q < W; q += blockDim.x) D.chain_lnl[r * W + q] = lnl[q];
-        }
-    }
-    if (s_prop < 0) return;
-    __syncthreads();            // (the partners of the next half are the walkers just decided)
-    const double* const other = x + (size_t)(1 - h_prop) * H * n;
-    for (int k = threadIdx.x; k < H; k += blockDim.x) {
-        const int w = h_prop * H + k;
-        const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
-        const vmx_ens::Block m = vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream);
-        const int move = vmx_ens::move_choice(m.w[0], M.t0, M.t1);
-        const int64_t j1 = vmx_ens::partner(b.w[0], H);
-        const double* c1 = other + (size_t)j1 * n;
-        const double* s = x + (size_t)w * n;
-        double* y = prop + (size_t)k * n;
-        double f = 0.0;
-        bool in = true;
-        if (move == vmx_ens::MOVE_STRETCH) {
-            const double z = vmx_ens::stretch_z(D.a, b.w[1]);
-            for (int d = 0; d < n; ++d) y[d] = vmx_ens::propose(c1[d], s[d], z);
-            f = vmx_ens::log_factor(n, z);
-        } else {
-            // (the entry refuses a DE weight with H < 2 and a snooker weight with H < 3: the indices below are in range)
-            const int64_t j2 = vmx_ens::partner2(b.w[1], H, j1);
-            const double* c2 = other + (size_t)j2 * n;
-            if (move == vmx_ens::MOVE_DE) {
-                const double gamma = vmx_ens::de_gamma(M.gamma0, M.sigma, m.w[1], m.w[2]);
-                for (int d = 0; d < n; ++d) y[d] = vmx_ens::de_propose(s[d], c1[d], c2[d], gamma);
-            } else {
-                const int64_t j3 = vmx_ens::partner3(b.w[3], H, j1, j2);
-                in = vmx_ens::snooker_propose(n, s, c1, c2, other + (size_t)j3 * n, M.gamma_s, y, f);
-            }
-        }
-        for (int d = 0; d < n; ++d) in = in && y[d] >= D.box.lo[d] && y[d] <= D.box.hi[d];
-        factor[k] = f;
-        inside_of[k] = in ? 1 : 0;
-        // (a proposal outside the box is rejected whatever the model says: the engine evaluates the walker's own position)
-        double* row = theta + (size_t)k * D.P;
-        for (int p = 0; p < D.P; ++p) row[p] = D.box.fixed[p];
-        for (int d = 0; d < n; ++d) row[D.col[d]] = in ? y[d] : s[d];
-    }
-}
 
 // Parallel tempering (vmx_ensemble_run_pt; vmx_ensemble.h, "parallel tempering"): G ladders of T rungs are G T ensembles, ensemble
 // g T + t on the rung of beta[t].  What the kernels read beside EnsDev: the ladder and the call's swap counters.
@@ -413,18 +258,30 @@ struct EnsPtDev {
 };
 enum { ENS_PT_DECIDE = 1, ENS_PT_RECORD = 2, ENS_PT_PROPOSE = 4 };
 
-// k_ens_half_moves with the rung's beta in the decision (accept_tempered): the same grid - one work-group per ensemble - the same
-// decide / record / propose order and the same strided loops, so that the chain does not depend on the block size.  `what` names
-// the parts to run: all three between two half-steps without a sweep; with a sweep due, ENS_PT_DECIDE alone, then k_ens_swap, then
-// ENS_PT_RECORD | ENS_PT_PROPOSE, so that the row of step s_dec and the next proposals see the walkers after the swaps.  A run
-// without moves comes with the thresholds of the pure stretch move (t0 = t1 = 1: the chain of k_ens_half).
-__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesDev M, EnsPtDev Pt, int64_t s_dec, int h_dec,
-                                                             int64_t s_prop, int h_prop, int what)
+// One half-step of the sampler, the body of the three kernels below.  A grid of E work-groups: work-group e owns ensemble e
+// (partners read the half decided just before, a dependency across the whole ensemble; nothing crosses ensembles, so
+// __syncthreads() is the only barrier) under the Philox stream streams[e].  Decide the proposals of half h_dec at step s_dec
+// (s_dec < 0: none), record the chain row when step s_dec is complete and due, then propose half h_prop at step s_prop
+// (s_prop < 0: none) and write the engine's rows, so that the E H proposal rows of a half-step are one stream of chunks for the
+// engine.  Every loop strides by the block, so that the chain does not depend on the block size.  Every expression: vmx_ensemble.h.
+//   MOVES: the move of every walker is drawn from a mixture of the stretch, differential-evolution and snooker moves
+// (vmx_ensemble.h, "the differential-evolution and snooker moves") with a Philox block of its own; without, no block is drawn and
+// the move is the stretch move.  The decision does not know the move: the proposal left its factor and whether it is inside.  The
+// partners' rows - up to three distinct walkers - are read from the half decided just before; the snooker move passes three times
+// over the n columns of its four rows.
+//   PT: the rung's beta is in the decision (accept_tempered); without, no beta is read.
+//   `what` names the parts to run: all three between two half-steps without a sweep; with a sweep due, ENS_PT_DECIDE alone, then
+// k_ens_swap, then ENS_PT_RECORD | ENS_PT_PROPOSE, so that the row of step s_dec and the next proposals see the walkers after the
+// swaps.
+constexpr int ENS_THREADS = 1024;
+template <bool MOVES, bool PT>
+__device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, const EnsPtDev& Pt, int64_t s_dec, int h_dec,
+                                         int64_t s_prop, int h_prop, int what)
 {
     const int W = D.W, H = W / 2, n = D.n;
     const size_t e = blockIdx.x;
     const uint64_t stream = D.streams[e];
-    const double beta = Pt.beta[(e / (size_t)Pt.T) * (size_t)Pt.stride + e % (size_t)Pt.T];
+    const double beta = PT ? Pt.beta[(e / (size_t)Pt.T) * (size_t)Pt.stride + e % (size_t)Pt.T] : 1.0;
     double* const x = D.x + e * W * n;
     double* const lnl = D.lnl + e * W;
     int64_t* const acc = D.acc + e * W;
@@ -444,7 +301,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesD
                 const double c2 = chi2[k];
                 const bool inside = inside_of[k] != 0, ok = vmx_ens::model_ok(status[k], c2);
                 const double lnl_new = vmx_ens::log_lik(D.log_norm, c2);
-                if (vmx_ens::accept_tempered(inside, ok, factor[k], beta, lnl_new, lnl[w], b.w[2])) {
+                if (PT ? vmx_ens::accept_tempered(inside, ok, factor[k], beta, lnl_new, lnl[w], b.w[2])
+                       : vmx_ens::accept(inside, ok, factor[k], lnl_new, lnl[w], b.w[2])) {
                     for (int d = 0; d < n; ++d) x[(size_t)w * n + d] = prop[(size_t)k * n + d];
                     lnl[w] = lnl_new;
                     acc[w] += 1;
@@ -466,8 +324,8 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesD
     for (int k = threadIdx.x; k < H; k += blockDim.x) {
         const int w = h_prop * H + k;
         const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
-        const vmx_ens::Block m = vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream);
-        const int move = vmx_ens::move_choice(m.w[0], M.t0, M.t1);
+        const vmx_ens::Block m = MOVES ? vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream) : vmx_ens::Block{};
+        const int move = MOVES ? vmx_ens::move_choice(m.w[0], M.t0, M.t1) : (int)vmx_ens::MOVE_STRETCH;
         const int64_t j1 = vmx_ens::partner(b.w[0], H);
         const double* c1 = other + (size_t)j1 * n;
         const double* s = x + (size_t)w * n;
@@ -500,38 +358,68 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesD
     }
 }
 
+// The default path (vmx_ensemble_run, vmx_ensemble_run_many): the stretch move, the untempered decision, all three parts
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
+{
+    ens_half<false, false>(D, EnsMovesDev{}, EnsPtDev{}, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
+}
+
+// The mixture of moves (vmx_ensemble_run_many_moves), the untempered decision, all three parts
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMovesDev M, int64_t s_dec, int h_dec, int64_t s_prop,
+                                                                int h_prop)
+{
+    ens_half<true, false>(D, M, EnsPtDev{}, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
+}
+
+// A ladder's half-step (vmx_ensemble_run_pt, vmx_ensemble_run_pt_adapt): the parts that `what` names.  A run without moves comes
+// with the thresholds of the pure stretch move (t0 = t1 = 1: the chain of k_ens_half).
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesDev M, EnsPtDev Pt, int64_t s_dec, int h_dec,
+                                                             int64_t s_prop, int h_prop, int what)
+{
+    ens_half<true, true>(D, M, Pt, s_dec, h_dec, s_prop, h_prop, what);
+}
+
 // The swap sweep after global step s: one work-group per ladder (nothing crosses ladders, so __syncthreads() between the T - 1
 // pairs of rungs is the only barrier), the pairs of rungs from the hottest down.  The threads stride over the W pairs of walkers
 // of a pair of rungs; the rotation makes them disjoint, so a thread reads and writes its own two rows alone.  No likelihood row:
 // lnL is stored untempered.  Every expression: vmx_ensemble.h.
+//   ens_swap_pairs: the pairs of (rung t - 1, rung t) of ladder g that the calling thread owns, decided with the betas bc (cold)
+// and bh (hot) and exchanged, rows and lnL; returns how many it swapped.  The callers keep the barriers and the counts.
+__device__ __forceinline__ unsigned int ens_swap_pairs(const EnsDev& D, size_t g, int T, int t, double bc, double bh, int64_t s,
+                                                       uint64_t stream)
+{
+    const int W = D.W, n = D.n;
+    const size_t cold = g * T + (size_t)(t - 1), hot = cold + 1;
+    double* const xc = D.x + cold * W * n;
+    double* const xh = D.x + hot * W * n;
+    double* const lc = D.lnl + cold * W;
+    double* const lh = D.lnl + hot * W;
+    const int64_t r = vmx_ens::swap_shift(vmx_ens::shift_block(s, t, D.seed, stream).w[0], W);
+    unsigned int took = 0;
+    for (int k = threadIdx.x; k < W; k += blockDim.x) {
+        const int64_t j = vmx_ens::swap_partner(k, r, W);
+        const vmx_ens::Block b = vmx_ens::swap_block(k, s, t, D.seed, stream);
+        const double l_cold = lc[k], l_hot = lh[j];
+        if (vmx_ens::swap_accept(bc, bh, l_cold, l_hot, b.w[0])) {
+            double* pc = xc + (size_t)k * n;
+            double* ph = xh + (size_t)j * n;
+            for (int d = 0; d < n; ++d) { const double v = pc[d]; pc[d] = ph[d]; ph[d] = v; }
+            lc[k] = l_hot;
+            lh[j] = l_cold;
+            took += 1;
+        }
+    }
+    return took;
+}
+
 __global__ __launch_bounds__(ENS_THREADS) void k_ens_swap(EnsDev D, EnsPtDev Pt, int64_t s)
 {
-    const int W = D.W, n = D.n, T = Pt.T;
+    const int W = D.W, T = Pt.T;
     const size_t g = blockIdx.x;
     const uint64_t stream = D.streams[g * T];
     int64_t* const swaps = Pt.swaps + g * (size_t)(T - 1) * 2;
     for (int t = T - 1; t >= 1; --t) {
-        const size_t cold = g * T + (size_t)(t - 1), hot = cold + 1;
-        double* const xc = D.x + cold * W * n;
-        double* const xh = D.x + hot * W * n;
-        double* const lc = D.lnl + cold * W;
-        double* const lh = D.lnl + hot * W;
-        const double bc = Pt.beta[t - 1], bh = Pt.beta[t];
-        const int64_t r = vmx_ens::swap_shift(vmx_ens::shift_block(s, t, D.seed, stream).w[0], W);
-        unsigned long long took = 0;
-        for (int k = threadIdx.x; k < W; k += blockDim.x) {
-            const int64_t j = vmx_ens::swap_partner(k, r, W);
-            const vmx_ens::Block b = vmx_ens::swap_block(k, s, t, D.seed, stream);
-            const double l_cold = lc[k], l_hot = lh[j];
-            if (vmx_ens::swap_accept(bc, bh, l_cold, l_hot, b.w[0])) {
-                double* pc = xc + (size_t)k * n;
-                double* ph = xh + (size_t)j * n;
-                for (int d = 0; d < n; ++d) { const double v = pc[d]; pc[d] = ph[d]; ph[d] = v; }
-                lc[k] = l_hot;
-                lh[j] = l_cold;
-                took += 1;
-            }
-        }
+        const unsigned long long took = ens_swap_pairs(D, g, T, t, Pt.beta[t - 1], Pt.beta[t], s, stream);
         if (took) atomicAdd((unsigned long long*)&swaps[2 * (t - 1) + 1], took);
         if (threadIdx.x == 0) swaps[2 * (t - 1)] += W;
         __syncthreads();        // (rung t - 1 is the hot rung of the next pair)
@@ -558,7 +446,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_swap_adapt(EnsDev D, EnsPtD
 {
     __shared__ double beta[vmx_ens::PT_MAXT];
     __shared__ unsigned int took_of[vmx_ens::PT_MAXT];
-    const int W = D.W, n = D.n, T = Pt.T;
+    const int W = D.W, T = Pt.T;
     const size_t g = blockIdx.x;
     const uint64_t stream = D.streams[g * T];
     int64_t* const swaps = Pt.swaps + g * (size_t)(T - 1) * 2;
@@ -566,27 +454,7 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_swap_adapt(EnsDev D, EnsPtD
     for (int t = threadIdx.x; t < T; t += blockDim.x) { beta[t] = ladder[t]; took_of[t] = 0u; }
     __syncthreads();
     for (int t = T - 1; t >= 1; --t) {
-        const size_t cold = g * T + (size_t)(t - 1), hot = cold + 1;
-        double* const xc = D.x + cold * W * n;
-        double* const xh = D.x + hot * W * n;
-        double* const lc = D.lnl + cold * W;
-        double* const lh = D.lnl + hot * W;
-        const double bc = beta[t - 1], bh = beta[t];
-        const int64_t r = vmx_ens::swap_shift(vmx_ens::shift_block(s, t, D.seed, stream).w[0], W);
-        unsigned int took = 0;
-        for (int k = threadIdx.x; k < W; k += blockDim.x) {
-            const int64_t j = vmx_ens::swap_partner(k, r, W);
-            const vmx_ens::Block b = vmx_ens::swap_block(k, s, t, D.seed, stream);
-            const double l_cold = lc[k], l_hot = lh[j];
-            if (vmx_ens::swap_accept(bc, bh, l_cold, l_hot, b.w[0])) {
-                double* pc = xc + (size_t)k * n;
-                double* ph = xh + (size_t)j * n;
-                for (int d = 0; d < n; ++d) { const double v = pc[d]; pc[d] = ph[d]; ph[d] = v; }
-                lc[k] = l_hot;
-                lh[j] = l_cold;
-                took += 1;
-            }
-        }
+        const unsigned int took = ens_swap_pairs(D, g, T, t, beta[t - 1], beta[t], s, stream);
         if (took) atomicAdd(&took_of[t - 1], took);
         __syncthreads();        // (rung t - 1 is the hot rung of the next pair; the pair's count is whole)
         if (threadIdx.x == 0) {
@@ -5346,7 +5214,6 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int64_t halves = 2 * (int64_t)n_steps;
     // (every loop of the kernel strides by its block: the chain does not depend on this size)
     const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
-    // a ladder's half-step: with a sweep due after step s_dec, the swaps come between the decisions and the row and proposals
     EnsPtDev Pt{};
     if (pt) {
         HIP_OK(hipMemcpyAsync(S.beta.p, pt->betas, n_beta * sizeof(double), hipMemcpyHostToDevice, st));
@@ -5360,25 +5227,27 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         Ad.lag = ad->lag; Ad.tau = ad->time; Ad.sweep0 = sweep0; Ad.swap_every = pt->swap_every; Ad.G = pt->G;
     }
     const dim3 grid_swap(pt ? pt->G : 1), block_swap(std::min(ENS_THREADS, std::max(64, (W + 63) / 64 * 64)));
-    const int pt_all = ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE;
-    auto half_pt = [&](int64_t s_dec, int h_dec, int64_t s_prop, int h_prop) {
-        if (s_dec >= 0 && h_dec == 1 && pt->T > 1 && vmx_ens::swap_due(s_dec, pt->swap_every)) {
-            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, (int)ENS_PT_DECIDE);
+    // one half-step with the wrapper that pt / moves choose.  A ladder's, with a sweep due after step s_dec: the swaps come between
+    // the decisions and the row and proposals
+    auto half = [&](int64_t s_dec, int h_dec, int64_t s_prop, int h_prop) {
+        auto half_pt = [&](int what) { hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, what); };
+        if (!pt && !moves) {
+            hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s_dec, h_dec, s_prop, h_prop);
+        } else if (!pt) {
+            hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s_dec, h_dec, s_prop, h_prop);
+        } else if (s_dec >= 0 && h_dec == 1 && pt->T > 1 && vmx_ens::swap_due(s_dec, pt->swap_every)) {
+            half_pt(ENS_PT_DECIDE);
             if (ad)
                 hipLaunchKernelGGL(k_ens_swap_adapt, grid_swap, block_swap, 0, st, D, Pt, Ad, s_dec,
                                    vmx_ens::adapt_due(s_dec, ad->adapt_until) ? 1 : 0);
             else
                 hipLaunchKernelGGL(k_ens_swap, grid_swap, block_swap, 0, st, D, Pt, s_dec);
-            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, ENS_PT_RECORD | ENS_PT_PROPOSE);
+            half_pt(ENS_PT_RECORD | ENS_PT_PROPOSE);
         } else {
-            hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, pt_all);
+            half_pt(ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
         }
     };
-    if (halves > 0) {
-        if (pt) half_pt((int64_t)-1, 0, step0, 0);
-        else if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, (int64_t)-1, 0, step0, 0);
-        else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, (int64_t)-1, 0, step0, 0);
-    }
+    if (halves > 0) half((int64_t)-1, 0, step0, 0);
     HIP_OK(hipGetLastError());
     for (int64_t q = 0; q < halves; ++q) {
         const int64_t s = step0 + q / 2;
@@ -5388,9 +5257,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         R.engine_calls += calls;
         const int64_t nq = q + 1;
         const int64_t s_next = nq < halves ? step0 + nq / 2 : (int64_t)-1;
-        if (pt) half_pt(s, h, s_next, (int)(nq % 2));
-        else if (moves) hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s, h, s_next, (int)(nq % 2));
-        else hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s, h, s_next, (int)(nq % 2));
+        half(s, h, s_next, (int)(nq % 2));
         HIP_OK(hipGetLastError());
     }
     std::vector<int64_t> acc0(accepted, accepted + EW), box(EW), failed(EW);

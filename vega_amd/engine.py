@@ -270,6 +270,14 @@ def _in_place(dtype, **arrays):
             raise ValueError(f'{name}: a C-contiguous {np.dtype(dtype).name} array (updated in place)')
 
 
+def _ensemble_moves(moves):
+    """The mapping ``moves`` of the ensemble entries as the library reads it (None: none)."""
+    if moves is None:
+        return None
+    return EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']), float(moves['sigma']),
+                         float(moves['gamma_s']), int(moves.get('flags', 0)), 0)
+
+
 def _stats_dict(stats):
     return {name: getattr(stats, name) for name, _ in stats._fields_}
 
@@ -1194,6 +1202,39 @@ class Engine:
                 _dp(chain) if keep_chain else None, _dp(chain_lnl) if keep_chain else None, C.byref(opt))
         return spec, args, chain, chain_lnl, EnsembleStats(), (cols, lo, hi, theta_fixed, opt)
 
+    def _ensemble_ladders(self, own, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, mock_rows, moves, step0, n_steps,
+                          thin, keep_chain, **spec_kw):
+        """What :meth:`ensemble_run_pt` (``own`` False: betas [T]) and :meth:`ensemble_run_pt_adapt` (True: betas [G, T], updated
+        in place) hand the library alike: x [G, T, W, n] checked and passed on to :meth:`_ensemble_arrays` as G T ensembles, the
+        ladder, streams and mocks checked.  Returns (G, T), the call's arguments before and after ``swap_every``, the chain
+        [G, T, rows, W, n] with its lnL (None: not kept), the statistics with ``per_ensemble`` [G, T, 3] and ``swaps``
+        [G, T - 1, 2]; last, what the pointers borrow."""
+        _in_place(np.float64, x=x, lnl=lnl, **({'betas': betas} if own else {}))
+        _in_place(np.int64, accepted=accepted)
+        if x.ndim != 4:
+            raise ValueError('x [G, T, W, n], lnl [G, T, W], accepted [G, T, W]')
+        G, T, W, n = x.shape
+        spec, args, chain, chain_lnl, stats, held = self._ensemble_arrays(
+            3, cols, lo, hi, theta_fixed, x.reshape(G * T, W, n), lnl.reshape(G * T, W), accepted.reshape(G * T, W), step0, n_steps,
+            thin, keep_chain, **spec_kw)
+        if not own:
+            betas = np.ascontiguousarray(betas, dtype=np.float64)
+        streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if betas.shape != ((G, T) if own else (T,)) or streams.shape != (G, T) or (mock_rows is not None and mock_rows.shape != (G,)):
+            raise ValueError(f"betas [{'G, T' if own else 'T'}], streams [G, T], mock_rows [G]")
+        per = np.zeros((G, T, 3), dtype=np.int64)
+        swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
+        mv = _ensemble_moves(moves)
+        i64 = C.POINTER(C.c_int64)
+        head = (self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+                None if mock_rows is None else _ip(mock_rows), *args[:6])
+        tail = (*args[6:], C.byref(stats), per.ctypes.data_as(i64), None if mv is None else C.byref(mv), swaps.ctypes.data_as(i64))
+        if keep_chain:      # (views of what the library fills)
+            chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
+        return (G, T), head, tail, chain, chain_lnl, stats, per, swaps, (held, spec, betas, streams, mock_rows, mv)
+
     def ensemble_run(self, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin=1, a=2.0, log_norm=0.0, seed=0,
                      stream=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):
         """``n_steps`` steps of the ensemble sampler on the device (include/vegamx.h: vmx_ensemble_run): ``cols`` the sampled
@@ -1243,8 +1284,7 @@ class Engine:
         if moves is None:
             self._check(self.lib.vmx_ensemble_run_many(*head))
         else:
-            mv = EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']), float(moves['sigma']),
-                               float(moves['gamma_s']), int(moves.get('flags', 0)), 0)
+            mv = _ensemble_moves(moves)
             self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
 
@@ -1256,33 +1296,10 @@ class Engine:
         (None: the installed data), ``swap_every`` the steps between swap sweeps (0: none); the rest as for
         :meth:`ensemble_run_many`.  Returns (chain [G, T, rows, W, n], chain_lnl [G, T, rows, W], statistics); the statistics
         carry ``per_ensemble`` int64 [G, T, 3] and ``swaps`` int64 [G, T - 1, 2]: proposed and accepted per pair of rungs."""
-        _in_place(np.float64, x=x, lnl=lnl)
-        _in_place(np.int64, accepted=accepted)
-        if x.ndim != 4:
-            raise ValueError('x [G, T, W, n], lnl [G, T, W], accepted [G, T, W]')
-        G, T, W, n = x.shape
-        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
-            3, cols, lo, hi, theta_fixed, x.reshape(G * T, W, n), lnl.reshape(G * T, W), accepted.reshape(G * T, W), step0, n_steps,
-            thin, keep_chain, a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
-        betas = np.ascontiguousarray(betas, dtype=np.float64)
-        streams = np.ascontiguousarray(streams, dtype=np.uint64)
-        if mock_rows is not None:
-            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
-        if betas.shape != (T,) or streams.shape != (G, T) or (mock_rows is not None and mock_rows.shape != (G,)):
-            raise ValueError('betas [T], streams [G, T], mock_rows [G]')
-        per = np.zeros((G, T, 3), dtype=np.int64)
-        swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
-        mv = None
-        if moves is not None:
-            mv = C.byref(EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']),
-                                       float(moves['sigma']), float(moves['gamma_s']), int(moves.get('flags', 0)), 0))
-        i64 = C.POINTER(C.c_int64)
-        self._check(self.lib.vmx_ensemble_run_pt(
-            self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), *args[:6], int(swap_every), *args[6:], C.byref(stats),
-            per.ctypes.data_as(i64), mv, swaps.ctypes.data_as(i64)))
-        if keep_chain:
-            chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
+        _shape, head, tail, chain, chain_lnl, stats, per, swaps, _held = self._ensemble_ladders(
+            False, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, mock_rows, moves, step0, n_steps, thin, keep_chain,
+            a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
+        self._check(self.lib.vmx_ensemble_run_pt(*head, int(swap_every), *tail))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, swaps=swaps)
 
     def ensemble_run_pt_adapt(self, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, step0, n_steps, swap_every=1,
@@ -1293,38 +1310,16 @@ class Engine:
         ``adaptation_time`` ptemcee's, in sweeps; the sweep after global step s adapts iff ``adapt_until`` < 0 or s <
         ``adapt_until``.  The statistics carry, beside ``per_ensemble`` and ``swaps``, ``beta_hist`` [sweeps, G, T] - the ladders
         after every sweep of the call - and ``adapt_skipped`` int64 [G], the sweeps whose new ladder the guard dropped."""
-        _in_place(np.float64, x=x, lnl=lnl, betas=betas)
-        _in_place(np.int64, accepted=accepted)
-        if x.ndim != 4:
-            raise ValueError('x [G, T, W, n], lnl [G, T, W], accepted [G, T, W]')
-        G, T, W, n = x.shape
-        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
-            3, cols, lo, hi, theta_fixed, x.reshape(G * T, W, n), lnl.reshape(G * T, W), accepted.reshape(G * T, W), step0, n_steps,
-            thin, keep_chain, a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
-        streams = np.ascontiguousarray(streams, dtype=np.uint64)
-        if mock_rows is not None:
-            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
-        if betas.shape != (G, T) or streams.shape != (G, T) or (mock_rows is not None and mock_rows.shape != (G,)):
-            raise ValueError('betas [G, T], streams [G, T], mock_rows [G]')
+        (G, T), head, tail, chain, chain_lnl, stats, per, swaps, _held = self._ensemble_ladders(
+            True, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, mock_rows, moves, step0, n_steps, thin, keep_chain,
+            a=a, log_norm=log_norm, seed=seed, stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
         step0, n_steps, swap_every = int(step0), int(n_steps), int(swap_every)
         sweeps = max(0, (step0 + n_steps) // swap_every - step0 // swap_every) if swap_every > 0 and n_steps >= 0 and step0 >= 0 else 0
-        per = np.zeros((G, T, 3), dtype=np.int64)
-        swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
         hist = np.zeros((sweeps, G, T))
         skipped = np.zeros(G, dtype=np.int64)
-        mv = None
-        if moves is not None:
-            mv = C.byref(EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']),
-                                       float(moves['sigma']), float(moves['gamma_s']), int(moves.get('flags', 0)), 0))
         ad = EnsembleAdapt(float(adaptation_lag), float(adaptation_time), int(adapt_until), 0, 0)
-        i64 = C.POINTER(C.c_int64)
-        self._check(self.lib.vmx_ensemble_run_pt_adapt(
-            self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
-            None if mock_rows is None else _ip(mock_rows), *args[:6], swap_every, *args[6:], C.byref(stats),
-            per.ctypes.data_as(i64), mv, swaps.ctypes.data_as(i64), C.byref(ad), _dp(hist) if sweeps else None,
-            skipped.ctypes.data_as(i64)))
-        if keep_chain:
-            chain, chain_lnl = chain.reshape((G, T) + chain.shape[1:]), chain_lnl.reshape((G, T) + chain_lnl.shape[1:])
+        self._check(self.lib.vmx_ensemble_run_pt_adapt(*head, swap_every, *tail, C.byref(ad), _dp(hist) if sweeps else None,
+                                                       skipped.ctypes.data_as(C.POINTER(C.c_int64))))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, swaps=swaps, beta_hist=hist, adapt_skipped=skipped)
 
     def nested_run(self, cols, lo, hi, theta_fixed, live_u, live_lnl, iteration, n_iterations, threads, num_repeats, log_norm=0.0,
