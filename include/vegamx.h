@@ -160,7 +160,7 @@ const char* vmx_last_error(void);
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
  * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep,
- * 23 vmx_ensemble_moves, 24 vmx_ensemble_adapt; 22 is vacant and answers -1, as every index that names no struct): lets a foreign
+ * 23 vmx_ensemble_moves, 24 vmx_ensemble_adapt, 25 vmx_ensemble_slice; 22 is vacant and answers -1, as every index that names no struct): lets a foreign
  * binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
@@ -600,6 +600,36 @@ int vmx_ensemble_run_pt_adapt(vmx_engine* e, const vmx_ensemble_spec* spec, int3
                               vmx_ensemble_stats* stats, int64_t* per_ensemble,
                               const vmx_ensemble_moves* moves, int64_t* swaps,
                               const vmx_ensemble_adapt* adapt, double* beta_hist, int64_t* adapt_skipped);
+/* Ensemble slice sampling (Karamanis & Beutler 2021, zeus's differential move) for the E ensembles of vmx_ensemble_run_many: a
+ * walker's update takes its direction from two walkers of the other half and its step from a slice-sampling bracket along it, so
+ * no update is rejected, and the scale of the direction tunes itself.  A trial point outside the box is answered by the walker's
+ * machine itself: every engine row is a real evaluation, none a walker's own position.  The counters, the machine, the tuning
+ * rule and the packing of a round are pinned in vega_amd/csrc/vmx_ensemble.h, the fifth part.  The run goes in rounds
+ * (k_ens_slice_advance: one work-group per running ensemble, one lane per walker; k_ens_slice_emit: the requests of all ensembles
+ * behind each other); the host reads one integer per round and hands the engine that many rows in chunks of `chunk`.
+ *   slice     mu0: the scale a caller starts mu from (default 1; the library reads mu, not mu0, but refuses a bad mu0);
+ *             tune_steps: the steps with global index s < tune_steps tune mu (their rows are no stationary chain: discard them);
+ *             max_expansions (<= 32, per side) and max_contractions (<= 64): the caps of one update; flags: 0
+ *   mu        [E], in and out: the scale of every ensemble, positive and finite
+ *   slice_counts   [E][8] (NULL: not wanted), of this call: updates, updates that moved the walker, engine rows, expansions,
+ *             contractions, box answers, failed-model answers, updates that ended capped or had a null direction
+ *   stats     proposals = updates, accepted = moved; host_synchronisations = rounds + 1
+ *   accepted  counts, per walker, the updates that moved it
+ *   everything else as for vmx_ensemble_run_many; spec->a is not read.  The single run is E = 1.
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever vmx_ensemble_run_many refuses; W < 4 (two
+ * partners in the other half); mu0 or an entry of mu not positive and finite; tune_steps < 0; a cap < 1 or beyond 32 / 64;
+ * flags != 0; slice or mu NULL. */
+#define VMX_SLICE_COUNTS 8
+#define VMX_SLICE_MAX_EXPANSIONS 32
+#define VMX_SLICE_MAX_CONTRACTIONS 64
+typedef struct { double mu0; int32_t tune_steps, max_expansions, max_contractions, flags; } vmx_ensemble_slice;
+int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W,
+                           const uint64_t* streams, const int32_t* mock_row,
+                           double* x, double* lnL, int64_t* accepted,
+                           int64_t step0, int32_t n_steps, int32_t thin,
+                           double* chain, double* chain_lnL,
+                           const vmx_ensemble_options* opt, vmx_ensemble_stats* stats,
+                           const vmx_ensemble_slice* slice, double* mu, int64_t* slice_counts);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

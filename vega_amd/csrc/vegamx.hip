@@ -229,6 +229,21 @@ struct EnsWorkspace {
     DevBuf<int64_t> swaps;              // ... and the call's swap counters [G][T - 1][2]
     DevBuf<double> beta_hist;           // adaptive ladders: the ladders after every sweep of the call [sweeps][G][T] ...
     DevBuf<int64_t> adapt_skipped;      // ... and the sweeps whose adjustment the guard dropped [G]
+    // ensemble slice sampling (vmx_ensemble_run_slice), sized once per (E, W, n): the active half's machines [E][H] and directions
+    // [E][H][n], the walkers' rows and the rows' walkers [E][H], the scales [E], the counts [E][8] and the open step's expansions
+    // and contractions [E][2], the half-steps done [E], whether a half is open [E], the running list and its counts [E]
+    DevBuf<vmx_ens::SliceWalker> sl_wk;
+    DevBuf<double> sl_eta, sl_mu;
+    DevBuf<int32_t> sl_slot, sl_row, sl_open, sl_active, sl_count, sl_mock_row;
+    DevBuf<int64_t> sl_counts, sl_step, sl_q;
+    // mapped host memory: the round's total; per ensemble its requests of the round; the running list (pinned)
+    int32_t* pin_word = nullptr; int32_t* dpin_word = nullptr; int32_t* pin_count = nullptr; int32_t* dpin_count = nullptr;
+    int32_t* pin_active = nullptr; size_t pin_runs = 0;
+    ~EnsWorkspace() {
+        if (pin_word) (void)hipHostFree(pin_word);
+        if (pin_count) (void)hipHostFree(pin_count);
+        if (pin_active) (void)hipHostFree(pin_active);
+    }
 };
 
 struct EnsDev {
@@ -471,6 +486,200 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_swap_adapt(EnsDev D, EnsPtD
     if (A.hist) {
         double* const row = A.hist + ((size_t)(time - A.sweep0) * (size_t)A.G + g) * (size_t)T;
         for (int t = 0; t < T; ++t) row[t] = beta[t];
+    }
+}
+
+// Ensemble slice sampling (vmx_ensemble_run_slice; vmx_ensemble.h, the fifth part): what the two kernels of a round read beside
+// EnsDev (its prop / factor / inside / n_box / n_fail are not used).  Ensemble e's parts of the per-walker arrays start at e H.
+struct EnsSliceDev {
+    vmx_ens::SliceWalker* wk;           // [E][H] the machines of the active half
+    double* eta;                        // [E][H][n] their directions
+    int32_t* slot;                      // [E][H] the engine row of a walker's request (k_ens_slice_emit makes it global)
+    int32_t* row_walker;                // [E][H] the walker of an ensemble's r-th request
+    double* mu;                         // [E] the scales, in and out
+    int64_t* counts;                    // [E][SLICE_COUNTS]
+    int64_t* step_counts;               // [E][2] expansions and contractions of the step that is open
+    int64_t* q;                         // [E] half-steps done in this call
+    int32_t* open;                      // [E] a half is open: its machines hold requests
+    const int32_t* active;              // [A] the ensembles still running, ascending
+    int32_t* count;                     // [A] the requests of ensemble active[a] in this round
+    int32_t* host_count;                // [E] mapped: the same per ensemble
+    int32_t* host_word;                 // mapped: the round's total
+    const int32_t* mock_row;            // [E] the pool row of every ensemble, or nullptr
+    int32_t* mock;                      // the mock row of every engine row
+    int32_t A, n_steps, tune_steps, max_e, max_c;
+};
+
+// One pass over the walkers of the active half h of step s of ensemble e: OPEN, every walker opens its update; else every walker
+// with a request out takes the answer of its row.  Either way the machines settle and the requesting walkers are numbered in
+// walker order (a ballot per wave, the waves' counts through LDS; the lanes stride beyond the block): slot[k] the walker's place
+// among the ensemble's requests, row_walker the inverse.  Returns the ensemble's requests.  Every expression: vmx_ensemble.h.
+template <bool OPEN>
+__device__ __forceinline__ int ens_slice_pass(const EnsDev& D, const EnsSliceDev& S, size_t e, int64_t s, int h, double mu, int32_t* s_wave)
+{
+    const int W = D.W, H = W / 2, n = D.n;
+    const uint64_t stream = D.streams[e];
+    const double* const x = D.x + e * W * n + (size_t)h * H * n;
+    const double* const lnl = D.lnl + e * W + (size_t)h * H;
+    const double* const other = D.x + e * W * n + (size_t)(1 - h) * H * n;
+    vmx_ens::SliceWalker* const wk = S.wk + e * H;
+    double* const eta = S.eta + e * H * n;
+    int32_t* const slot = S.slot + e * H;
+    int32_t* const row_walker = S.row_walker + e * H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (blockDim.x + 63) >> 6;
+    int total = 0;
+    for (int base = 0; base < H; base += blockDim.x) {
+        const int k = base + threadIdx.x;
+        int asks = 0;
+        if (k < H) {
+            vmx_ens::SliceWalker w;
+            if (OPEN) {
+                vmx_ens::slice_open(w, eta + (size_t)k * n, n, x + (size_t)k * n, lnl[k], other, H, mu, D.box.lo, D.box.hi, S.max_e,
+                                    S.max_c, k, s, h, D.seed, stream);
+                wk[k] = w;
+            } else {
+                w = wk[k];
+                if (w.asks) {
+                    const int row = slot[k];
+                    vmx_ens::slice_advance(w, n, x + (size_t)k * n, eta + (size_t)k * n, D.box.lo, D.box.hi, D.log_norm,
+                                           D.box.status[row], D.box.chi2[row], S.max_e, S.max_c, k, s, h, D.seed, stream);
+                    wk[k] = w;
+                }
+            }
+            asks = w.asks;
+        }
+        const unsigned long long m = __ballot(asks);
+        if (lane == 0) s_wave[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int i = 0; i < waves; ++i) { const int c = s_wave[i]; before += i < wave ? c : 0; all += c; }
+        if (asks) {
+            const int local = total + before + __popcll(m & ((1ull << lane) - 1ull));
+            slot[k] = local;
+            row_walker[local] = k;
+        }
+        total += all;
+        __syncthreads();        // (the waves' counts are rewritten by the next stride)
+    }
+    return total;
+}
+
+// a wave's sum of `mine` into the LDS word (integers: the order does not matter)
+__device__ __forceinline__ void ens_slice_add(unsigned long long* word, unsigned long long mine)
+{
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(word, mine);
+}
+
+// A round of the set, first kernel: one work-group per running ensemble, one lane per walker of the active half.  Every walker
+// with a request out takes its answer and the machines settle.  While the ensemble asks for nothing its half is over: the half is
+// committed - positions, lnL, the moved counter, the counts (integer sums through LDS: the order does not matter) - at a step's
+// end the scale is tuned while the step is below tune_steps and the chain row written when due, and unless the call's steps are
+// done the next half opens.  Nothing crosses ensembles; __syncthreads() is the only barrier.  Holds 144 B of LDS.
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_slice_advance(EnsDev D, EnsSliceDev S)
+{
+    __shared__ int32_t s_wave[ENS_THREADS / 64];
+    __shared__ unsigned long long s_cnt[vmx_ens::SLICE_COUNTS];
+    __shared__ double s_mu;
+    const int a = blockIdx.x, W = D.W, H = W / 2, n = D.n;
+    const size_t e = (size_t)S.active[a];
+    int64_t q = S.q[e];
+    bool open = S.open[e] != 0;
+    if (threadIdx.x == 0) s_mu = S.mu[e];
+    __syncthreads();
+    int total = 0;
+    if (open) total = ens_slice_pass<false>(D, S, e, vmx_ens::slice_step(D.step0, q), vmx_ens::slice_half(q), s_mu, s_wave);
+    while (total == 0) {
+        if (open) {
+            const int64_t s = vmx_ens::slice_step(D.step0, q);
+            const int h = vmx_ens::slice_half(q);
+            double* const x = D.x + e * W * n + (size_t)h * H * n;
+            double* const lnl = D.lnl + e * W + (size_t)h * H;
+            int64_t* const acc = D.acc + e * W + (size_t)h * H;
+            if (threadIdx.x < vmx_ens::SLICE_COUNTS) s_cnt[threadIdx.x] = 0ull;
+            __syncthreads();
+            unsigned long long mine[vmx_ens::SLICE_COUNTS] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+            for (int k = threadIdx.x; k < H; k += blockDim.x)
+                acc[k] += vmx_ens::slice_commit(S.wk[e * H + k], n, x + (size_t)k * n, S.eta + (e * H + k) * n, lnl + k, mine);
+            // (every index a constant, so that the lane's counts stay in registers; a wave adds its lanes' first)
+            ens_slice_add(&s_cnt[0], mine[0]); ens_slice_add(&s_cnt[1], mine[1]); ens_slice_add(&s_cnt[2], mine[2]);
+            ens_slice_add(&s_cnt[3], mine[3]); ens_slice_add(&s_cnt[4], mine[4]); ens_slice_add(&s_cnt[5], mine[5]);
+            ens_slice_add(&s_cnt[6], mine[6]); ens_slice_add(&s_cnt[7], mine[7]);
+            __syncthreads();        // (the half is committed: the next half's partners, the chain row)
+            if (threadIdx.x == 0) {
+                int64_t* const counts = S.counts + e * vmx_ens::SLICE_COUNTS;
+                for (int i = 0; i < vmx_ens::SLICE_COUNTS; ++i) counts[i] += (int64_t)s_cnt[i];
+                int64_t* const step = S.step_counts + e * 2;
+                step[0] += (int64_t)s_cnt[vmx_ens::SC_EXPANSIONS];
+                step[1] += (int64_t)s_cnt[vmx_ens::SC_CONTRACTIONS];
+                if (h == 1) {
+                    if (vmx_ens::slice_tune_due(s, S.tune_steps)) s_mu = vmx_ens::slice_tune(s_mu, step[0], step[1]);
+                    step[0] = step[1] = 0;
+                }
+            }
+            if (h == 1 && (s + 1) % D.thin == 0 && (D.chain || D.chain_lnl)) {
+                const size_t r = e * D.rows + (size_t)((s + 1) / D.thin - D.step0 / D.thin - 1);
+                const double* const xe = D.x + e * W * n;
+                const double* const le = D.lnl + e * W;
+                if (D.chain)
+                    for (int i = threadIdx.x; i < W * n; i += blockDim.x) D.chain[r * W * n + i] = xe[i];
+                if (D.chain_lnl)
+                    for (int i = threadIdx.x; i < W; i += blockDim.x) D.chain_lnl[r * W + i] = le[i];
+            }
+            __syncthreads();        // (the scale of the next half; s_cnt is zeroed again)
+            q += 1;
+            open = false;
+        }
+        if (q >= 2 * (int64_t)S.n_steps) break;
+        total = ens_slice_pass<true>(D, S, e, vmx_ens::slice_step(D.step0, q), vmx_ens::slice_half(q), s_mu, s_wave);
+        open = true;
+    }
+    if (threadIdx.x == 0) {
+        S.q[e] = q;
+        S.open[e] = open ? 1 : 0;
+        S.mu[e] = s_mu;
+        S.count[a] = total;
+    }
+}
+
+// ... second kernel, the packing: ensemble active[a] owns the engine's rows offset .. offset + count[a] - 1, offset the sum of the
+// counts before it in list order (vmx_ens::slice_offsets), its requests in walker order.  Every slot becomes a global row; the
+// rows are written one column per lane - the fixed row with the sampled columns at the trial point, the row's walker, trial and
+// direction read once per row by the lanes of a wave; the rows' mocks, the ensemble's count and (work-group 0) the total go out.
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_slice_emit(EnsDev D, EnsSliceDev S)
+{
+    const int a = blockIdx.x, W = D.W, H = W / 2, n = D.n, P = D.P;
+    const size_t e = (size_t)S.active[a];
+    int offset = 0;
+    for (int b = 0; b < a; ++b) offset += S.count[b];
+    const int cnt = S.count[a];
+    const int h = vmx_ens::slice_half(S.q[e]);
+    const int32_t* const row_walker = S.row_walker + e * H;
+    const vmx_ens::SliceWalker* const wk = S.wk + e * H;
+    const double* const eta = S.eta + e * H * n;
+    const double* const x = D.x + e * W * n + (size_t)h * H * n;
+    for (int r = threadIdx.x; r < cnt; r += blockDim.x) S.slot[e * H + row_walker[r]] = offset + r;
+    for (int p = threadIdx.x % 64; p < P; p += 64) {
+        const int d = D.box.inv[p];
+        const double fixed = D.box.fixed[p];
+        for (int r = threadIdx.x / 64; r < cnt; r += blockDim.x / 64) {
+            const int k = row_walker[r];
+            double v = fixed;
+            if (d >= 0) v = vmx_ens::slice_point(x[(size_t)k * n + d], wk[k].t, eta[(size_t)k * n + d]);
+            D.box.theta[((size_t)offset + r) * P + p] = v;
+        }
+    }
+    if (S.mock_row) {
+        const int m = S.mock_row[e];
+        for (int i = threadIdx.x; i < cnt; i += blockDim.x) S.mock[offset + i] = m;
+    }
+    if (threadIdx.x == 0) {
+        S.host_count[e] = cnt;
+        if (a == 0) {
+            int total = 0;
+            for (int b = 0; b < S.A; ++b) total += S.count[b];
+            *S.host_word = total;
+        }
     }
 }
 
@@ -2072,6 +2281,7 @@ int vmx_struct_size(int32_t which)
         case 21: return (int)sizeof(vmx_smc_keep);
         case 23: return (int)sizeof(vmx_ensemble_moves);           // (22 stays vacant: see vegamx.h)
         case 24: return (int)sizeof(vmx_ensemble_adapt);
+        case 25: return (int)sizeof(vmx_ensemble_slice);
         default: return -1;
     }
 }
@@ -5104,6 +5314,42 @@ int vmx_ensemble_run_pt_adapt(vmx_engine* e, const vmx_ensemble_spec* spec, int3
                         step0, n_steps, thin, chain, chain_lnL, opt, stats, per_ensemble, moves, &pt);
 }
 
+// What every ensemble run refuses before anything runs: the box, the walkers, the steps, the sizes, the start and the mocks of E
+// ensembles of W walkers, and the options of the engine's calls.  stretch: the run reads the stretch scale spec->a.
+static int ensemble_check(const std::string& name, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                          const int32_t* mock_row, const double* x, const double* lnL, const int64_t* accepted, int64_t step0,
+                          int32_t n_steps, int32_t thin, const vmx_ensemble_options* opt, bool stretch, std::vector<char>& varies,
+                          std::vector<int32_t>& inv)
+{
+    REQUIRE(e && e->finalized && spec && x && lnL && accepted, name);
+    REQUIRE(E >= 1, name + ": at least one ensemble");
+    REQUIRE(streams, name + ": a Philox stream for every ensemble");
+    if (check_box(name, e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
+    const int n = spec->n, P = e->n_params;
+    REQUIRE(W >= 2 * n && W % 2 == 0, name + ": an even number of walkers, at least twice the sampled columns");
+    REQUIRE(!stretch || (spec->a > 1.0 && std::isfinite(spec->a)), name + ": the stretch scale a must exceed 1");
+    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, name + ": thin >= 1, n_steps >= 0, step0 >= 0");
+    const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
+    // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
+    REQUIRE((int64_t)E * W <= INT32_MAX, name + ": E W exceeds the engine's row count");
+    const size_t EW = (size_t)E * W, per_row = (size_t)std::max(n, P) * sizeof(double);
+    REQUIRE(EW <= SIZE_MAX / per_row && (rows <= 0 || EW * per_row <= SIZE_MAX / (size_t)rows), name + ": the chain is too large");
+    for (size_t w = 0; w < EW; ++w) {
+        REQUIRE(std::isfinite(lnL[w]), name + ": a start walker has a non-finite lnL");
+        for (int i = 0; i < n; ++i) {
+            const double v = x[w * n + i];
+            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], name + ": a start walker lies outside the box");
+        }
+    }
+    if (mock_row)
+        for (int q = 0; q < E; ++q)
+            for (auto* it : e->items) {
+                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
+                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
+            }
+    return LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true);
+}
+
 // E independent ensembles advanced together (k_ens_half): the E H proposal rows of a half-step as one stream of chunks for the
 // engine, every row with the mock of its ensemble
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
@@ -5112,16 +5358,10 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
                         vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves, const EnsPtRun* pt)
 {
     const std::string name(who);
-    REQUIRE(e && e->finalized && spec && x && lnL && accepted, name);
-    REQUIRE(E >= 1, name + ": at least one ensemble");
-    REQUIRE(streams, name + ": a Philox stream for every ensemble");
     std::vector<char> varies;
     std::vector<int32_t> inv;
-    if (check_box(name, e, spec, VMX_ENS_MAXN, varies, inv)) return -1;
+    if (ensemble_check(name, e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, opt, true, varies, inv)) return -1;
     const int n = spec->n, P = e->n_params;
-    REQUIRE(W >= 2 * n && W % 2 == 0, name + ": an even number of walkers, at least twice the sampled columns");
-    REQUIRE(spec->a > 1.0 && std::isfinite(spec->a), name + ": the stretch scale a must exceed 1");
-    REQUIRE(thin >= 1 && n_steps >= 0 && step0 >= 0, name + ": thin >= 1, n_steps >= 0, step0 >= 0");
     const int H = W / 2;
     EnsMovesDev M{};
     if (moves) {
@@ -5141,24 +5381,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         M.t0 = M.t1 = 1.0;      // (the pure stretch move of k_ens_half_pt: u < 1 always)
     }
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
-    // sizes: the engine's rows are counted in int32, the largest array (the chain, or the rows themselves) in size_t
-    REQUIRE((int64_t)E * W <= INT32_MAX, name + ": E W exceeds the engine's row count");
-    const size_t EW = (size_t)E * W, per_row = (size_t)std::max(n, P) * sizeof(double);
-    REQUIRE(EW <= SIZE_MAX / per_row && (rows <= 0 || EW * per_row <= SIZE_MAX / (size_t)rows), name + ": the chain is too large");
-    for (size_t w = 0; w < EW; ++w) {
-        REQUIRE(std::isfinite(lnL[w]), name + ": a start walker has a non-finite lnL");
-        for (int i = 0; i < n; ++i) {
-            const double v = x[w * n + i];
-            REQUIRE(v >= spec->lo[i] && v <= spec->hi[i], name + ": a start walker lies outside the box");
-        }
-    }
-    if (mock_row)
-        for (int q = 0; q < E; ++q)
-            for (auto* it : e->items) {
-                REQUIRE(it->n_mocks > 0 && it->dev.mock_pool, name + ": mock rows, but an item has no mock pool");
-                REQUIRE(mock_row[q] >= 0 && mock_row[q] < it->n_mocks, name + ": mock row outside the pool");
-            }
-    if (LikelihoodSession::check(name, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, true)) return -1;
+    const size_t EW = (size_t)E * W;
     const int EH = E * H;
 
     HIP_OK(hipSetDevice(e->device));
@@ -5297,6 +5520,146 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         R.rejected_outside_box += out;
         R.rejected_failed_model += bad;
     }
+    R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = R;
+    return 0;
+}
+
+// Ensemble slice sampling (vmx_ensemble.h, the fifth part): E ensembles in rounds.  A round is k_ens_slice_advance - answers,
+// machines, and whatever of commit, tuning, chain row and the next half's opening an ensemble without requests is due -
+// k_ens_slice_emit - the rows of all ensembles behind each other - one wait for the mapped total, and the engine's chain over
+// those rows; the host has waited, so no event guards the rows.  An ensemble that asks for nothing has done its steps and leaves
+// the list.  host_synchronisations = rounds + 1: the last wait brings the state back.
+static_assert(VMX_SLICE_COUNTS == vmx_ens::SLICE_COUNTS && vmx_ens::SLICE_COUNTS == 8 && VMX_SLICE_MAX_EXPANSIONS == vmx_ens::SLICE_MAX_EXPANSIONS &&
+              VMX_SLICE_MAX_CONTRACTIONS == vmx_ens::SLICE_MAX_CONTRACTIONS, "slice sampling limits");
+int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                           const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                           int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt, vmx_ensemble_stats* stats,
+                           const vmx_ensemble_slice* slice, double* mu, int64_t* slice_counts)
+{
+    const std::string name("vmx_ensemble_run_slice");
+    std::vector<char> varies;
+    std::vector<int32_t> inv;
+    if (ensemble_check(name, e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, opt, false, varies, inv)) return -1;
+    REQUIRE(slice && mu, name + ": the slice settings and the scales mu [E]");
+    REQUIRE(W >= 4, name + ": two partners in the other half, W >= 4");
+    REQUIRE(vmx_ens::slice_ok(W / 2, slice->mu0, slice->tune_steps, slice->max_expansions, slice->max_contractions, slice->flags),
+            name + ": mu0 positive and finite, tune_steps >= 0, 1 <= max_expansions <= 32, 1 <= max_contractions <= 64, flags 0");
+    for (int q = 0; q < E; ++q) REQUIRE(std::isfinite(mu[q]) && mu[q] > 0.0, name + ": every scale mu must be positive and finite");
+    const int n = spec->n, P = e->n_params, H = W / 2;
+    const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
+    const size_t EW = (size_t)E * W, EH = (size_t)E * H;
+
+    HIP_OK(hipSetDevice(e->device));
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (!e->ensws) e->ensws = new EnsWorkspace();
+    EnsWorkspace& S = *e->ensws;
+    if (ensure(S.x, EW * n) || ensure(S.lnl, EW) || ensure(S.acc, EW) || ensure(S.col, n) || ensure(S.streams, E) ||
+        ensure(S.sl_wk, EH) || ensure(S.sl_eta, EH * n) || ensure(S.sl_slot, EH) || ensure(S.sl_row, EH) || ensure(S.sl_mu, E) ||
+        ensure(S.sl_counts, (size_t)E * vmx_ens::SLICE_COUNTS) || ensure(S.sl_step, (size_t)E * 2) || ensure(S.sl_q, E) ||
+        ensure(S.sl_open, E) || ensure(S.sl_active, E) || ensure(S.sl_count, E) ||
+        (mock_row && (ensure(S.sl_mock_row, E) || ensure(S.mock, EH))))
+        return -2;
+    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
+    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
+    if (!S.pin_word) {
+        HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_word, S.pin_word, 0));
+    }
+    if (S.pin_runs < (size_t)E) {
+        if (S.pin_count) { (void)hipHostFree(S.pin_count); S.pin_count = nullptr; }
+        if (S.pin_active) { (void)hipHostFree(S.pin_active); S.pin_active = nullptr; }
+        S.pin_runs = 0;
+        HIP_OK(hipHostMalloc((void**)&S.pin_count, (size_t)E * sizeof(int32_t), hipHostMallocMapped));
+        HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_count, S.pin_count, 0));
+        HIP_OK(hipHostMalloc((void**)&S.pin_active, (size_t)E * sizeof(int32_t), hipHostMallocDefault));
+        S.pin_runs = (size_t)E;
+    }
+    hipStream_t st = e->stream;
+    EnsDev D{};
+    if (S.box.upload(EH, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
+    HIP_OK(hipMemcpyAsync(S.x.p, x, EW * n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.lnl.p, lnL, EW * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.acc.p, accepted, EW * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.col.p, spec->col, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.streams.p, streams, (size_t)E * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemcpyAsync(S.sl_mu.p, mu, (size_t)E * sizeof(double), hipMemcpyHostToDevice, st));
+    if (mock_row) HIP_OK(hipMemcpyAsync(S.sl_mock_row.p, mock_row, (size_t)E * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipMemsetAsync(S.sl_counts.p, 0, (size_t)E * vmx_ens::SLICE_COUNTS * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.sl_step.p, 0, (size_t)E * 2 * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.sl_q.p, 0, (size_t)E * sizeof(int64_t), st));
+    HIP_OK(hipMemsetAsync(S.sl_open.p, 0, (size_t)E * sizeof(int32_t), st));
+    const int32_t* d_mock = mock_row ? S.mock.p : nullptr;
+
+    D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p;
+    D.col = S.col.p;
+    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.streams = S.streams.p; D.rows = rows;
+    D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = 0.0; D.log_norm = spec->log_norm;
+    D.seed = spec->seed; D.step0 = step0;
+    EnsSliceDev X{};
+    X.wk = S.sl_wk.p; X.eta = S.sl_eta.p; X.slot = S.sl_slot.p; X.row_walker = S.sl_row.p; X.mu = S.sl_mu.p;
+    X.counts = S.sl_counts.p; X.step_counts = S.sl_step.p; X.q = S.sl_q.p; X.open = S.sl_open.p;
+    X.active = S.sl_active.p; X.count = S.sl_count.p; X.host_count = S.dpin_count; X.host_word = S.dpin_word;
+    X.mock_row = mock_row ? S.sl_mock_row.p : nullptr; X.mock = mock_row ? S.mock.p : nullptr;
+    X.n_steps = n_steps; X.tune_steps = slice->tune_steps; X.max_e = slice->max_expansions; X.max_c = slice->max_contractions;
+
+    // the engine as the sampler's likelihood, at the table level the sampled columns allow
+    LikelihoodSession L(e, opt ? opt->const_hint : -1, opt ? opt->chunk : 0, opt ? opt->lanes : 0, e->max_batch, varies);
+    vmx_ensemble_stats R{};
+    R.const_hint = L.hint;
+    R.lanes = L.lanes;
+    double enqueue_s = 0.0;
+    // (every loop of the kernels strides by its block: the chain does not depend on this size)
+    const dim3 block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
+    int32_t* const active = S.pin_active;
+    for (int q = 0; q < E; ++q) active[q] = q;
+    int A = n_steps > 0 ? E : 0;
+    int64_t rounds = 0, rows_asked = 0;
+    while (A > 0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        // (the list goes up on the stream: the host changes it only after it has waited for the stream)
+        X.A = A;
+        HIP_OK(hipMemcpyAsync(S.sl_active.p, active, (size_t)A * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ens_slice_advance, dim3(A), block, 0, st, D, X);
+        hipLaunchKernelGGL(k_ens_slice_emit, dim3(A), block, 0, st, D, X);
+        HIP_OK(hipGetLastError());
+        enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        HIP_OK(hipStreamSynchronize(st));       // (the round's only wait: the total and the ensembles' counts, mapped words)
+        rounds += 1;
+        const int total = S.pin_word[0];
+        if (total < 0 || (size_t)total > EH) return fail(-2, name + ": a round asked for more rows than its buffers hold");
+        if (total > 0) {
+            const auto t1 = std::chrono::steady_clock::now();
+            const int calls = L.evaluate(S.box.theta.p, total, S.box.chi2.p, S.box.status.p, d_mock, false);
+            if (calls < 0) return -2;
+            R.engine_calls += calls;
+            rows_asked += total;
+            enqueue_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+        }
+        A = vmx_ens::slice_compact(active, A, S.pin_count);
+    }
+    std::vector<int64_t> counts((size_t)E * vmx_ens::SLICE_COUNTS, 0);
+    HIP_OK(hipMemcpyAsync(x, S.x.p, EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, EW * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(mu, S.sl_mu.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(counts.data(), S.sl_counts.p, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * EW * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    R.host_synchronisations = rounds + 1;
+    R.steps = n_steps;
+    int64_t rows_counted = 0;           // (the machines' own count of their requests: the rows the engine was given, no other)
+    for (int q = 0; q < E; ++q) rows_counted += counts[(size_t)q * vmx_ens::SLICE_COUNTS + vmx_ens::SC_ROWS];
+    if (rows_counted != rows_asked) return fail(-2, name + ": the engine's rows are not the walkers' requests");
+    for (int q = 0; q < E; ++q) {
+        const int64_t* c = counts.data() + (size_t)q * vmx_ens::SLICE_COUNTS;
+        if (slice_counts) std::memcpy(slice_counts + (size_t)q * vmx_ens::SLICE_COUNTS, c, vmx_ens::SLICE_COUNTS * sizeof(int64_t));
+        R.proposals += c[vmx_ens::SC_UPDATES];
+        R.accepted += c[vmx_ens::SC_MOVED];
+    }
+    R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;
     return 0;

@@ -403,4 +403,259 @@ VMX_HD inline bool ladder_adjust(double* beta, const Count* accepted, int T, int
     return true;
 }
 
+// ---- ensemble slice sampling (vmx_ensemble_run_slice: k_ens_slice_advance, k_ens_slice_emit), the fifth part
+//
+// Karamanis & Beutler 2021 (zeus's differential move): the direction of a walker's update comes from two walkers of the other
+// half, so the move is affine-invariant like the ones above; the step along it is a slice-sampling bracket (Neal 2003: stepping
+// out, then shrinkage), so no update is rejected; the length scale mu tunes itself from the counts of expansions and
+// contractions.  One step is two halves, as ever: in half h of global step s walker-in-half k of the active half (H = W / 2)
+// makes one update against the other half c, which is fixed for the whole half-step.  Only + - x / log, each rounded on its own.
+//
+//   random numbers   walker k reads the blocks with counter (k, s, 2 j + h, 6) under the key (seed, stream), j = 0, 1, ... its own
+//                    block index within this update (the parts above use the last words 0 - 3, the nested and SMC samplers 1 - 5
+//                    under their own rules: 6 is free).  Block 0: w0 -> j1 = partner(w0, H); w1 -> j2 = partner2(w1, H, j1);
+//                    w2 -> the slice height lnY = lnL_k + log(u01(w2)); w3 -> the bracket, r = u01(w3), L = -r, R = L + 1.
+//                    Every shrink draw takes the next unused word (w0 of block 1, w1 of block 1, ...: word index `draw` of the
+//                    walker, block draw / 4, word draw % 4); stepping out draws nothing.  A walker's stream depends on (k, s, h)
+//                    and its own history alone: the run is the same however rows are cut into chunks, lanes or calls.
+//   direction        eta_q = mu (c[j1]_q - c[j2]_q) per column, the difference first.  Every eta_q exactly 0: no update, the
+//                    walker stays (END_NULL).  A trial point is y_q = x_q + t eta_q, the product first.
+//   answer           of the trial point at t: outside the box in any column -inf, given by the machine itself without an engine
+//                    row (counted as box); inside, a request goes to the engine and the answer is log_lik(log_norm, chi2), or
+//                    -inf when model_ok fails (counted as failed).  In the slice iff answer > lnY, strictly.
+//   machine          LEFT: the trial is t = L; in the slice: L = L - 1, one expansion, and LEFT again unless that was the
+//                    max_expansions-th of this side; else RIGHT.  RIGHT: likewise with t = R, R = R + 1; then SHRINK with
+//                    t = L + (R - L) u01(next word) (the difference, the product, the sum).  SHRINK: in the slice: the walker
+//                    moves to t and takes that lnL (END_MOVED); else L = t if t < 0, else R = t, one contraction, and after
+//                    max_contractions of them the update ends where it began (END_CAPPED); else the next t.  The machine keeps
+//                    answering itself (slice_settle) until it holds a request inside the box or is done: a round carries real
+//                    evaluations only, and no row is ever a walker's own position.
+//   scale            after both halves of a step with global index s < tune_steps: Ne = max(1, expansions), Nc = contractions of
+//                    the step over all W walkers; mu <- mu (2 Ne / (Ne + Nc)) (zeus's rule; the sums in integers, one division,
+//                    one product); a product that is not a positive normal number leaves mu as it was.  The rule reads the
+//                    global step alone: a run cut into calls tunes identically.
+//   the set round    every ensemble still running gives each of its walkers the answer of the row it asked for, advances the
+//                    machines and counts its requests; at 0 the half is over: it is committed (slice_commit), at a step's end mu
+//                    is tuned, the counters are added and the chain row written when due, and unless its steps are done the next
+//                    half opens - so it has requests again (or the next half is over at once, and so on).  Ensembles do not wait
+//                    for each other.  Rows are packed in ascending (ensemble, walker) order: a walker's place among its
+//                    ensemble's requests is the number of requesting walkers before it, the ensemble's offset the sum of the
+//                    counts of the running ensembles before it (slice_offsets).  No atomic decides a row.
+constexpr int SLICE_MAX_EXPANSIONS = 32, SLICE_MAX_CONTRACTIONS = 64;
+enum SlicePhase { SLICE_LEFT = 0, SLICE_RIGHT = 1, SLICE_SHRINK = 2, SLICE_DONE = 3 };
+enum SliceEnd { END_NONE = 0, END_MOVED = 1, END_CAPPED = 2, END_NULL = 3 };
+// the counts of a run, per ensemble: [SLICE_COUNTS]
+enum SliceCount { SC_UPDATES = 0, SC_MOVED, SC_ROWS, SC_EXPANSIONS, SC_CONTRACTIONS, SC_BOX, SC_FAILED, SC_CAPPED_NULL, SLICE_COUNTS };
+
+// a walker's update: the bracket, the trial, the height, the lnL it moved to; where the machine is, the next unused word, and
+// the update's own counts (left, right: the expansions of either side); asks: a request is out, its answer is due
+struct SliceWalker {
+    double L, R, t, lnY, lnl;
+    int32_t phase, draw, left, right, contractions, rows, box, failed, end, asks;
+};
+
+VMX_HD inline Block slice_block(int64_t k, int64_t s, int h, int64_t j, uint64_t seed, uint64_t stream)
+{
+    return philox4x64_10((uint64_t)k, (uint64_t)s, 2 * (uint64_t)j + (uint64_t)h, 6, seed, stream);
+}
+
+// the walker's next unused word
+VMX_HD inline uint64_t slice_word(SliceWalker& w, int64_t k, int64_t s, int h, uint64_t seed, uint64_t stream)
+{
+    const int32_t i = w.draw;
+    w.draw = i + 1;
+    const Block b = slice_block(k, s, h, i / 4, seed, stream);
+    const int r = i % 4;        // (selected, not indexed: a lane's array indexed at run time would live in scratch memory)
+    return r == 0 ? b.w[0] : (r == 1 ? b.w[1] : (r == 2 ? b.w[2] : b.w[3]));
+}
+
+VMX_HD inline double slice_eta(double mu, double c1, double c2)
+{
+    VMX_NO_CONTRACT
+    const double d = c1 - c2;
+    return mu * d;
+}
+
+// one column of the trial point at t
+VMX_HD inline double slice_point(double x, double t, double eta)
+{
+    VMX_NO_CONTRACT
+    const double p = t * eta;
+    return x + p;
+}
+
+VMX_HD inline double slice_height(double lnl, uint64_t w2)
+{
+    VMX_NO_CONTRACT
+    return lnl + log(u01(w2));
+}
+
+VMX_HD inline double slice_shrink(double L, double R, uint64_t word)
+{
+    VMX_NO_CONTRACT
+    const double d = R - L;
+    const double m = d * u01(word);
+    return L + m;
+}
+
+// the trial point at t lies in the box (a NaN lies outside)
+VMX_HD inline bool slice_inside(int n, const double* x, double t, const double* eta, const double* lo, const double* hi)
+{
+    bool in = true;
+    for (int q = 0; q < n; ++q) {
+        const double y = slice_point(x[q], t, eta[q]);
+        in = in && y >= lo[q] && y <= hi[q];
+    }
+    return in;
+}
+
+// the engine's answer of a request; *failed goes up when the model failed
+VMX_HD inline double slice_answer(double log_norm, int32_t status, double chi2, int32_t* failed)
+{
+    if (model_ok(status, chi2)) return log_lik(log_norm, chi2);
+    *failed += 1;
+    return -INFINITY;
+}
+
+// the machine takes the answer of its trial
+VMX_HD inline void slice_take(SliceWalker& w, double answer, int max_e, int max_c, int64_t k, int64_t s, int h, uint64_t seed,
+                              uint64_t stream)
+{
+    VMX_NO_CONTRACT
+    const bool in = answer > w.lnY;
+    if (w.phase == SLICE_LEFT) {
+        if (in) { w.L = w.L - 1.0; w.left += 1; }
+        if (in && w.left < max_e) { w.t = w.L; return; }
+        w.phase = SLICE_RIGHT;
+        w.t = w.R;
+        return;
+    }
+    if (w.phase == SLICE_RIGHT) {
+        if (in) { w.R = w.R + 1.0; w.right += 1; }
+        if (in && w.right < max_e) { w.t = w.R; return; }
+        w.phase = SLICE_SHRINK;
+        w.t = slice_shrink(w.L, w.R, slice_word(w, k, s, h, seed, stream));
+        return;
+    }
+    if (w.phase != SLICE_SHRINK) return;
+    if (in) { w.lnl = answer; w.end = END_MOVED; w.phase = SLICE_DONE; return; }
+    if (w.t < 0.0) w.L = w.t; else w.R = w.t;
+    w.contractions += 1;
+    if (w.contractions >= max_c) { w.end = END_CAPPED; w.phase = SLICE_DONE; return; }
+    w.t = slice_shrink(w.L, w.R, slice_word(w, k, s, h, seed, stream));
+}
+
+// the machine answers itself until it holds a request inside the box (asks = 1) or is done
+VMX_HD inline void slice_settle(SliceWalker& w, int n, const double* x, const double* eta, const double* lo, const double* hi, int max_e,
+                                int max_c, int64_t k, int64_t s, int h, uint64_t seed, uint64_t stream)
+{
+    w.asks = 0;
+    while (w.phase != SLICE_DONE) {
+        if (slice_inside(n, x, w.t, eta, lo, hi)) { w.asks = 1; w.rows += 1; return; }
+        w.box += 1;
+        slice_take(w, -INFINITY, max_e, max_c, k, s, h, seed, stream);
+    }
+}
+
+// a walker's update opens: block 0, the direction eta[n] from the other half `other` [H][n], the height and the bracket; then the
+// machine settles on its first request
+VMX_HD inline void slice_open(SliceWalker& w, double* eta, int n, const double* x, double lnl, const double* other, int64_t H, double mu,
+                              const double* lo, const double* hi, int max_e, int max_c, int64_t k, int64_t s, int h, uint64_t seed,
+                              uint64_t stream)
+{
+    VMX_NO_CONTRACT
+    const Block b = slice_block(k, s, h, 0, seed, stream);
+    const int64_t j1 = partner(b.w[0], H), j2 = partner2(b.w[1], H, j1);
+    bool null = true;
+    for (int q = 0; q < n; ++q) {
+        eta[q] = slice_eta(mu, other[j1 * n + q], other[j2 * n + q]);
+        null = null && eta[q] == 0.0;
+    }
+    w.lnY = slice_height(lnl, b.w[2]);
+    const double r = u01(b.w[3]);
+    w.L = -r;
+    w.R = w.L + 1.0;
+    w.t = w.L;
+    w.lnl = lnl;
+    w.phase = null ? SLICE_DONE : SLICE_LEFT;
+    w.end = null ? END_NULL : END_NONE;
+    w.draw = 4;
+    w.left = w.right = w.contractions = w.rows = w.box = w.failed = 0;
+    slice_settle(w, n, x, eta, lo, hi, max_e, max_c, k, s, h, seed, stream);
+}
+
+// the answer of the walker's request has come: (status, chi2) of its engine row
+VMX_HD inline void slice_advance(SliceWalker& w, int n, const double* x, const double* eta, const double* lo, const double* hi,
+                                 double log_norm, int32_t status, double chi2, int max_e, int max_c, int64_t k, int64_t s, int h,
+                                 uint64_t seed, uint64_t stream)
+{
+    const double answer = slice_answer(log_norm, status, chi2, &w.failed);
+    slice_take(w, answer, max_e, max_c, k, s, h, seed, stream);
+    slice_settle(w, n, x, eta, lo, hi, max_e, max_c, k, s, h, seed, stream);
+}
+
+// the half is over: a walker that moved goes to its trial point - the row the engine evaluated, bit for bit - and takes its lnL;
+// the update's counts go to counts[SLICE_COUNTS] (any integer type).  Returns 1 if the walker moved.
+template <class Count>
+VMX_HD inline int slice_commit(const SliceWalker& w, int n, double* x, const double* eta, double* lnl, Count* counts)
+{
+    const int moved = w.end == END_MOVED ? 1 : 0;
+    if (moved) {
+        for (int q = 0; q < n; ++q) x[q] = slice_point(x[q], w.t, eta[q]);
+        *lnl = w.lnl;
+    }
+    counts[SC_UPDATES] += 1;
+    counts[SC_MOVED] += moved;
+    counts[SC_ROWS] += w.rows;
+    counts[SC_EXPANSIONS] += w.left + w.right;
+    counts[SC_CONTRACTIONS] += w.contractions;
+    counts[SC_BOX] += w.box;
+    counts[SC_FAILED] += w.failed;
+    counts[SC_CAPPED_NULL] += w.end == END_CAPPED || w.end == END_NULL ? 1 : 0;
+    return moved;
+}
+
+// a step with global index s tunes the scale
+VMX_HD inline bool slice_tune_due(int64_t s, int32_t tune_steps) { return s < (int64_t)tune_steps; }
+
+// zeus's rule from the step's expansions and contractions over all walkers
+VMX_HD inline double slice_tune(double mu, int64_t expansions, int64_t contractions)
+{
+    VMX_NO_CONTRACT
+    const int64_t ne = expansions < 1 ? 1 : expansions;
+    const double num = 2.0 * (double)ne;
+    const double den = (double)(ne + contractions);
+    const double f = num / den;
+    const double m = mu * f;
+    return m >= 0x1.0p-1022 && m <= 0x1.fffffffffffffp+1023 ? m : mu;
+}
+
+// what the run takes beside what vmx_ensemble_run_many takes
+VMX_HD inline bool slice_ok(int64_t H, double mu0, int32_t tune_steps, int32_t max_e, int32_t max_c, int32_t flags)
+{
+    return H >= 2 && is_finite(mu0) && mu0 > 0.0 && tune_steps >= 0 && max_e >= 1 && max_e <= SLICE_MAX_EXPANSIONS && max_c >= 1 &&
+           max_c <= SLICE_MAX_CONTRACTIONS && flags == 0;
+}
+
+// the half-step q of a call that starts at global step step0: its step and half
+VMX_HD inline int64_t slice_step(int64_t step0, int64_t q) { return step0 + q / 2; }
+VMX_HD inline int slice_half(int64_t q) { return (int)(q % 2); }
+
+// the packing of a round: offset[a] of the a-th running ensemble is the sum of the counts before it in list order; the total
+VMX_HD inline int32_t slice_offsets(const int32_t* count, int A, int32_t* offset)
+{
+    int32_t total = 0;
+    for (int a = 0; a < A; ++a) { if (offset) offset[a] = total; total += count[a]; }
+    return total;
+}
+
+// the running list after a round: an ensemble that asked for nothing has done its steps and leaves, the order stays
+VMX_HD inline int slice_compact(int32_t* active, int A, const int32_t* count_of)
+{
+    int B = 0;
+    for (int a = 0; a < A; ++a)
+        if (count_of[active[a]] > 0) active[B++] = active[a];
+    return B;
+}
+
 }  // namespace vmx_ens

@@ -144,6 +144,15 @@ class EnsembleAdapt(C.Structure):
     _fields_ = [('lag', C.c_double), ('time', C.c_double), ('adapt_until', C.c_int64), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+VMX_SLICE_COUNTS = 8
+SLICE_COUNT_NAMES = ('updates', 'moved', 'rows', 'expansions', 'contractions', 'box', 'failed', 'capped')
+
+
+class EnsembleSlice(C.Structure):
+    _fields_ = [('mu0', C.c_double), ('tune_steps', C.c_int32), ('max_expansions', C.c_int32), ('max_contractions', C.c_int32),
+                ('flags', C.c_int32)]
+
+
 VMX_NS_MAXN = 32
 VMX_NS_MAX_LIVE = 4096
 NESTED_STOP = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_double), C.POINTER(C.c_double))
@@ -348,6 +357,7 @@ def load_library():
                                         C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64),
                                         C.POINTER(EnsembleMoves), C.POINTER(C.c_int64)]
     lib.vmx_ensemble_run_pt_adapt.argtypes = lib.vmx_ensemble_run_pt.argtypes + [C.POINTER(EnsembleAdapt), dptr, C.POINTER(C.c_int64)]
+    lib.vmx_ensemble_run_slice.argtypes = lib.vmx_ensemble_run_many.argtypes[:-1] + [C.POINTER(EnsembleSlice), dptr, C.POINTER(C.c_int64)]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -402,7 +412,7 @@ def load_library():
     for which, struct in enumerate((Tracer, PipeDesc, MetalDesc, ItemDesc, FitSpec, FitOptions, FitResultArrays, FitStats,
                                     EnsembleSpec, EnsembleOptions, EnsembleStats, NestedSpec, NestedOptions, NestedStats,
                                     SmcSpec, SmcOptions, SmcStats, NestedClusters, NestedSetOptions, NestedPhantoms,
-                                    NestedSetPhantoms, SmcKeep, None, EnsembleMoves, EnsembleAdapt)):
+                                    NestedSetPhantoms, SmcKeep, None, EnsembleMoves, EnsembleAdapt, EnsembleSlice)):
         if struct is None:          # (an index that names no struct)
             continue
         if lib.vmx_struct_size(which) != C.sizeof(struct):
@@ -436,7 +446,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1287,6 +1297,33 @@ class Engine:
             mv = _ensemble_moves(moves)
             self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
+
+    def ensemble_run_slice(self, cols, lo, hi, theta_fixed, x, lnl, accepted, streams, mu, step0, n_steps, mock_rows=None, thin=1,
+                           log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, mu0=1.0, tune_steps=100,
+                           max_expansions=32, max_contractions=64, flags=0):
+        """``n_steps`` steps of ensemble slice sampling for E independent ensembles in one device run (include/vegamx.h:
+        vmx_ensemble_run_slice): the state as for :meth:`ensemble_run_many`, ``mu`` float64 [E] the scales (updated in place).
+        Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], statistics); the statistics carry ``slice_counts`` int64 [E, 8] in
+        the order of ``SLICE_COUNT_NAMES`` and ``rounds``.  The steps with global index below ``tune_steps`` tune ``mu``."""
+        spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
+            3, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=2.0, log_norm=log_norm, seed=seed,
+            stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
+        _in_place(np.float64, mu=mu)
+        E, W = x.shape[:2]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+        if mock_rows is not None:
+            mock_rows = np.ascontiguousarray(mock_rows, dtype=np.int32)
+        if (streams is not None and streams.shape != (E,)) or (mock_rows is not None and mock_rows.shape != (E,)) or mu.shape != (E,):
+            raise ValueError('streams [E], mock_rows [E], mu [E]')
+        counts = np.zeros((E, VMX_SLICE_COUNTS), dtype=np.int64)
+        sl = EnsembleSlice(float(mu0), int(tune_steps), int(max_expansions), int(max_contractions), int(flags))
+        self._check(self.lib.vmx_ensemble_run_slice(
+            self._h, C.byref(spec), E, W, None if streams is None else streams.ctypes.data_as(C.POINTER(C.c_uint64)),
+            None if mock_rows is None else _ip(mock_rows), *args, C.byref(stats), C.byref(sl), _dp(mu),
+            counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        st = _stats_dict(stats)
+        return chain, chain_lnl, dict(st, slice_counts=counts, rounds=st['host_synchronisations'] - 1)
 
     def ensemble_run_pt(self, cols, lo, hi, theta_fixed, x, lnl, accepted, betas, streams, step0, n_steps, swap_every=1, mock_rows=None,
                         thin=1, a=2.0, log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, moves=None):

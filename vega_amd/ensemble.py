@@ -231,6 +231,38 @@ def resolve_moves(moves, n, walkers, gamma0=None, sigma=None, gamma_s=None):
     return out
 
 
+def _names_slice(moves):
+    if isinstance(moves, str):
+        return moves == 'slice'
+    if moves is None or isinstance(moves, dict):
+        return False
+    return any((pair if isinstance(pair, str) else pair[0]) == 'slice' for pair in moves)
+
+
+def resolve_slice(moves, walkers, mu=None, tune_steps=None, gamma0=None, sigma=None, gamma_s=None):
+    """``moves='slice'`` - ensemble slice sampling (vmx_ensemble.h, the fifth part) - as dict(mu0, tune_steps), defaults 1.0 and 100;
+    None when ``moves`` does not name it.  Refused: ``'slice'`` inside a mixture, ``mu`` / ``tune_steps`` without it, the scales
+    of the other moves with it, fewer than 4 walkers, a ``mu`` that is not positive and finite, negative ``tune_steps``."""
+    if not _names_slice(moves):
+        if mu is not None or tune_steps is not None:
+            raise ValueError("mu and tune_steps belong to moves='slice'")
+        return None
+    if not isinstance(moves, str):
+        pairs = [(pair, 1.0) if isinstance(pair, str) else tuple(pair) for pair in moves]
+        if len(pairs) != 1 or not float(pairs[0][1]) > 0.0:
+            raise ValueError("moves: 'slice' is a sampler of its own, not a member of a mixture: moves='slice'")
+    if gamma0 is not None or sigma is not None or gamma_s is not None:
+        raise ValueError("gamma0, sigma and gamma_s are scales of the stretch / DE / snooker moves, not of 'slice'")
+    out = dict(mu0=1.0 if mu is None else float(mu), tune_steps=100 if tune_steps is None else int(tune_steps))
+    if walkers < 4:
+        raise ValueError("moves: 'slice' needs two partners in the other half, at least 4 walkers")
+    if not (math.isfinite(out['mu0']) and out['mu0'] > 0.0):
+        raise ValueError('mu: the scale of the slice directions must be positive and finite')
+    if out['tune_steps'] < 0:
+        raise ValueError('tune_steps: 0 or more steps')
+    return out
+
+
 def half_step_moves(H, h, step, seed, stream, moves):
     """The move of every walker of half ``h`` at ``step``: [H] of MOVE_STRETCH / MOVE_DE / MOVE_SNOOKER."""
     return move_choice(move_blocks(H, step, h, seed, stream)[:, 0], *move_thresholds(moves['weights']))
@@ -563,6 +595,346 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
               rejected_failed_model=int(per[:, 2].sum()))
     return chain, chain_lnl, st, per
+
+
+# ---- ensemble slice sampling (vmx_ensemble.h, the fifth part): scalar functions over Python floats and integers, one per function
+# of the header - a Python float is an IEEE double and every operation below is rounded on its own
+SLICE_MAX_EXPANSIONS, SLICE_MAX_CONTRACTIONS = 32, 64
+SLICE_LEFT, SLICE_RIGHT, SLICE_SHRINK, SLICE_DONE = 0, 1, 2, 3
+END_NONE, END_MOVED, END_CAPPED, END_NULL = 0, 1, 2, 3
+SLICE_COUNT_NAMES = ('updates', 'moved', 'rows', 'expansions', 'contractions', 'box', 'failed', 'capped')
+SC_UPDATES, SC_MOVED, SC_ROWS, SC_EXPANSIONS, SC_CONTRACTIONS, SC_BOX, SC_FAILED, SC_CAPPED_NULL = range(8)
+_M64 = (1 << 64) - 1
+_INF = math.inf
+
+
+def philox_block(c0, c1, c2, c3, k0, k1):
+    """:func:`philox4x64_10` of one counter in Python integers: the four words."""
+    m0, m1, w0, w1 = (int(v) for v in _PHILOX_M + _PHILOX_W)
+    for r in range(10):
+        if r > 0:
+            k0, k1 = (k0 + w0) & _M64, (k1 + w1) & _M64
+        p0, p1 = m0 * c0, m1 * c2
+        c0, c1, c2, c3 = (p1 >> 64) ^ c1 ^ k0, p1 & _M64, (p0 >> 64) ^ c3 ^ k1, p0 & _M64
+    return c0, c1, c2, c3
+
+
+def slice_block(k, s, h, j, seed, stream):
+    return philox_block(int(k), int(s), 2 * int(j) + int(h), 6, int(seed) & _M64, int(stream) & _M64)
+
+
+def _u01(word):
+    return float(word >> 11) * 2.0**-53
+
+
+def _log1(v):
+    return math.log(v) if v > 0.0 else -_INF
+
+
+class SliceWalker:
+    """A walker's update (the header's struct of the same name)."""
+    FIELDS = ('L', 'R', 't', 'lnY', 'lnl', 'phase', 'draw', 'left', 'right', 'contractions', 'rows', 'box', 'failed', 'end', 'asks')
+    __slots__ = FIELDS
+
+    def fields(self):
+        return tuple(getattr(self, f) for f in self.FIELDS)
+
+
+def slice_word(w, k, s, h, seed, stream):
+    i = w.draw
+    w.draw = i + 1
+    return slice_block(k, s, h, i // 4, seed, stream)[i % 4]
+
+
+def slice_eta(mu, c1, c2):
+    d = c1 - c2
+    return mu * d
+
+
+def slice_point(x, t, eta):
+    p = t * eta
+    return x + p
+
+
+def slice_height(lnl, w2):
+    return lnl + _log1(_u01(w2))
+
+
+def slice_shrink(L, R, word):
+    d = R - L
+    m = d * _u01(word)
+    return L + m
+
+
+def slice_inside(x, t, eta, lo, hi):
+    for xq, eq, l, h in zip(x, eta, lo, hi):
+        y = slice_point(xq, t, eq)
+        if not (l <= y <= h):
+            return False
+    return True
+
+
+def slice_answer(w, log_norm, status, chi2):
+    if status == 0 and chi2 < 1e99:
+        return log_norm - 0.5 * chi2
+    w.failed += 1
+    return -_INF
+
+
+def slice_take(w, answer, max_e, max_c, k, s, h, seed, stream):
+    inside = answer > w.lnY
+    if w.phase == SLICE_LEFT:
+        if inside:
+            w.L = w.L - 1.0
+            w.left += 1
+        if inside and w.left < max_e:
+            w.t = w.L
+            return
+        w.phase, w.t = SLICE_RIGHT, w.R
+        return
+    if w.phase == SLICE_RIGHT:
+        if inside:
+            w.R = w.R + 1.0
+            w.right += 1
+        if inside and w.right < max_e:
+            w.t = w.R
+            return
+        w.phase = SLICE_SHRINK
+        w.t = slice_shrink(w.L, w.R, slice_word(w, k, s, h, seed, stream))
+        return
+    if w.phase != SLICE_SHRINK:
+        return
+    if inside:
+        w.lnl, w.end, w.phase = answer, END_MOVED, SLICE_DONE
+        return
+    if w.t < 0.0:
+        w.L = w.t
+    else:
+        w.R = w.t
+    w.contractions += 1
+    if w.contractions >= max_c:
+        w.end, w.phase = END_CAPPED, SLICE_DONE
+        return
+    w.t = slice_shrink(w.L, w.R, slice_word(w, k, s, h, seed, stream))
+
+
+def slice_settle(w, x, eta, lo, hi, max_e, max_c, k, s, h, seed, stream):
+    w.asks = 0
+    while w.phase != SLICE_DONE:
+        if slice_inside(x, w.t, eta, lo, hi):
+            w.asks = 1
+            w.rows += 1
+            return
+        w.box += 1
+        slice_take(w, -_INF, max_e, max_c, k, s, h, seed, stream)
+
+
+def slice_open(x, lnl, other, mu, lo, hi, max_e, max_c, k, s, h, seed, stream):
+    """The update of walker-in-half ``k`` at ``x`` (a list) opens against the other half ``other`` (a list of lists): (the walker,
+    its direction)."""
+    H = len(other)
+    b = slice_block(k, s, h, 0, seed, stream)
+    j1 = ((b[0] >> 32) * H) >> 32
+    j2 = ((b[1] >> 32) * (H - 1)) >> 32
+    j2 += j2 >= j1
+    eta = [slice_eta(mu, c1, c2) for c1, c2 in zip(other[j1], other[j2])]
+    null = all(v == 0.0 for v in eta)
+    w = SliceWalker()
+    w.lnY = slice_height(lnl, b[2])
+    w.L = -_u01(b[3])
+    w.R = w.L + 1.0
+    w.t, w.lnl = w.L, lnl
+    w.phase, w.end = (SLICE_DONE, END_NULL) if null else (SLICE_LEFT, END_NONE)
+    w.draw = 4
+    w.left = w.right = w.contractions = w.rows = w.box = w.failed = 0
+    slice_settle(w, x, eta, lo, hi, max_e, max_c, k, s, h, seed, stream)
+    return w, eta
+
+
+def slice_advance(w, x, eta, lo, hi, log_norm, status, chi2, max_e, max_c, k, s, h, seed, stream):
+    answer = slice_answer(w, log_norm, status, chi2)
+    slice_take(w, answer, max_e, max_c, k, s, h, seed, stream)
+    slice_settle(w, x, eta, lo, hi, max_e, max_c, k, s, h, seed, stream)
+
+
+def slice_commit(w, x, eta, lnl, counts):
+    """(the walker's position, its lnL, whether it moved) after the half; the update's counts are added to ``counts`` [8]."""
+    moved = w.end == END_MOVED
+    if moved:
+        x, lnl = [slice_point(xq, w.t, eq) for xq, eq in zip(x, eta)], w.lnl
+    counts += (1, int(moved), w.rows, w.left + w.right, w.contractions, w.box, w.failed, int(w.end in (END_CAPPED, END_NULL)))
+    return x, lnl, moved
+
+
+def slice_tune_due(s, tune_steps):
+    return s < tune_steps
+
+
+def slice_tune(mu, expansions, contractions):
+    ne = max(1, int(expansions))
+    num = 2.0 * float(ne)
+    den = float(ne + int(contractions))
+    f = num / den
+    m = mu * f
+    return m if 2.0**-1022 <= m <= 1.7976931348623157e308 else mu
+
+
+def slice_ok(H, mu0, tune_steps, max_e, max_c, flags=0):
+    return (H >= 2 and math.isfinite(mu0) and mu0 > 0.0 and tune_steps >= 0 and 1 <= max_e <= SLICE_MAX_EXPANSIONS
+            and 1 <= max_c <= SLICE_MAX_CONTRACTIONS and flags == 0)
+
+
+def slice_offsets(count):
+    """(offsets, total) of the counts of the running ensembles, in list order."""
+    offsets, total = [], 0
+    for c in count:
+        offsets.append(total)
+        total += c
+    return offsets, total
+
+
+def slice_compact(active, count_of):
+    return [e for e in active if count_of[e] > 0]
+
+
+class SliceRounds:
+    """The set round of ensemble slice sampling, round by round, as the device driver runs it: the state ``x`` [E, W, n], ``lnl``
+    [E, W], ``accepted`` [E, W], ``mu`` [E] (all updated in place).  :meth:`round` takes the answers (chi2, status) of the rows the
+    round before asked for and returns the next rows (rows [R, n], the ensemble of every row [R]) - in ascending (ensemble,
+    walker) order - until the running list ``active`` is empty.  ``wk`` / ``eta`` / ``slot`` hold the machines, directions and
+    engine rows of every ensemble's active half, ``q`` the half-steps done, ``counts`` [E, 8] the counts, ``count_of`` [E] the
+    requests of the last round."""
+
+    def __init__(self, x, lnl, accepted, mu, step0, n_steps, thin, seed, streams, lo, hi, log_norm, tune_steps=100,
+                 max_expansions=SLICE_MAX_EXPANSIONS, max_contractions=SLICE_MAX_CONTRACTIONS):
+        self.x, self.lnl, self.accepted, self.mu = x, lnl, accepted, mu
+        self.E, self.W, self.n = x.shape
+        self.H = self.W // 2
+        if not all(slice_ok(self.H, float(m), tune_steps, max_expansions, max_contractions) for m in mu):
+            raise ValueError('slice: W >= 4, mu positive and finite, tune_steps >= 0, 1 <= max_expansions <= 32, '
+                             '1 <= max_contractions <= 64')
+        self.step0, self.n_steps, self.thin, self.seed = int(step0), int(n_steps), int(thin), int(seed)
+        self.streams = [int(v) for v in streams]
+        self.lo, self.hi, self.log_norm = [float(v) for v in lo], [float(v) for v in hi], float(log_norm)
+        self.tune_steps, self.max_e, self.max_c = int(tune_steps), int(max_expansions), int(max_contractions)
+        E, H = self.E, self.H
+        rows = (self.step0 + self.n_steps) // self.thin - self.step0 // self.thin
+        self.chain, self.chain_lnl = np.empty((E, rows, self.W, self.n)), np.empty((E, rows, self.W))
+        self.q, self.open = [0] * E, [False] * E
+        self.wk, self.eta = [[None] * H for _ in range(E)], [[None] * H for _ in range(E)]
+        self.slot, self.row_walker = [[-1] * H for _ in range(E)], [[] for _ in range(E)]
+        self.counts, self.step_counts = np.zeros((E, 8), dtype=np.int64), np.zeros((E, 2), dtype=np.int64)
+        self.count_of = [0] * E
+        self.active = list(range(E)) if self.n_steps > 0 else []
+        self.rounds = self.rows = 0
+
+    def _half(self, e):
+        return self.step0 + self.q[e] // 2, self.q[e] % 2
+
+    def _pass(self, e, opening, chi2, status):
+        s, h = self._half(e)
+        H, stream = self.H, self.streams[e]
+        mine = self.x[e, h * H:(h + 1) * H].tolist()
+        tail = (self.max_e, self.max_c)
+        if opening:
+            other = self.x[e, (1 - h) * H:(2 - h) * H].tolist()
+            mu = float(self.mu[e])
+        self.row_walker[e] = order = []
+        for k in range(H):
+            if opening:
+                self.wk[e][k], self.eta[e][k] = slice_open(mine[k], float(self.lnl[e, h * H + k]), other, mu, self.lo, self.hi, *tail,
+                                                           k, s, h, self.seed, stream)
+            elif self.wk[e][k].asks:
+                row = self.slot[e][k]
+                slice_advance(self.wk[e][k], mine[k], self.eta[e][k], self.lo, self.hi, self.log_norm, int(status[row]),
+                              float(chi2[row]), *tail, k, s, h, self.seed, stream)
+            if self.wk[e][k].asks:
+                self.slot[e][k] = len(order)
+                order.append(k)
+        return len(order)
+
+    def _commit(self, e):
+        s, h = self._half(e)
+        H = self.H
+        took = np.zeros(8, dtype=np.int64)
+        for k in range(H):
+            w = h * H + k
+            xk, lk, moved = slice_commit(self.wk[e][k], self.x[e, w].tolist(), self.eta[e][k], float(self.lnl[e, w]), took)
+            if moved:
+                self.x[e, w], self.lnl[e, w] = xk, lk
+                self.accepted[e, w] += 1
+        self.counts[e] += took
+        self.step_counts[e] += (took[SC_EXPANSIONS], took[SC_CONTRACTIONS])
+        if h == 1:
+            if slice_tune_due(s, self.tune_steps):
+                self.mu[e] = slice_tune(float(self.mu[e]), *self.step_counts[e])
+            self.step_counts[e] = 0
+            if (s + 1) % self.thin == 0:
+                r = (s + 1) // self.thin - self.step0 // self.thin - 1
+                self.chain[e, r], self.chain_lnl[e, r] = self.x[e], self.lnl[e]
+
+    def round(self, chi2=None, status=None):
+        counts = []
+        for e in self.active:
+            total = self._pass(e, False, chi2, status) if self.open[e] else 0
+            while total == 0:
+                if self.open[e]:
+                    self._commit(e)
+                    self.q[e] += 1
+                    self.open[e] = False
+                if self.q[e] >= 2 * self.n_steps:
+                    break
+                total = self._pass(e, True, None, None)
+                self.open[e] = True
+            counts.append(total)
+        offsets, total = slice_offsets(counts)
+        self.listing = list(zip(self.active, counts, offsets))         # (the round's list: ensemble, requests, offset)
+        rows, ens = np.empty((total, self.n)), np.empty(total, dtype=np.int64)
+        for a, e in enumerate(self.active):
+            h = self.q[e] % 2
+            for r, k in enumerate(self.row_walker[e][:counts[a]]):
+                self.slot[e][k] = offsets[a] + r
+                t = self.wk[e][k].t
+                rows[offsets[a] + r] = [slice_point(xq, t, eq) for xq, eq in zip(self.x[e, h * self.H + k].tolist(), self.eta[e][k])]
+                ens[offsets[a] + r] = e
+            self.count_of[e] = counts[a]
+        self.active = slice_compact(self.active, self.count_of)
+        self.rounds += 1
+        self.rows += total
+        return rows, ens
+
+
+def slice_stats(counts, mu):
+    """``stats['slice']`` of the counts [E, 8] and scales [E] of a run: every count summed, ``per_ensemble`` [E, 8] in the order of
+    ``SLICE_COUNT_NAMES``, ``rows_per_update`` and ``mu``."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1, 8)
+    total = counts.sum(axis=0)
+    out = {name: int(v) for name, v in zip(SLICE_COUNT_NAMES, total)}
+    out.update(per_ensemble=counts.copy(), rows_per_update=float(total[SC_ROWS]) / max(int(total[SC_UPDATES]), 1),
+               mu=np.array(mu, dtype=np.float64).copy())
+    return out
+
+
+def python_steps_slice_many(x, lnl, accepted, mu, step0, n_steps, thin, seed, streams, lo, hi, log_norm, evaluate, tune_steps=100,
+                            max_expansions=SLICE_MAX_EXPANSIONS, max_contractions=SLICE_MAX_CONTRACTIONS):
+    """``n_steps`` steps of ensemble slice sampling for E independent ensembles advanced together, in NumPy: the state ``x``
+    [E, W, n], ``lnl`` [E, W], ``accepted`` [E, W] and the scales ``mu`` [E] (all updated in place), ensemble e on the Philox stream
+    ``streams[e]``.  The rounds of :class:`SliceRounds` - the phases, the packing order and hence the chunks of the device driver;
+    ``evaluate(rows [R, n], ens [R])`` -> (chi2 [R], status [R]) is the likelihood of a round's rows, ``ens`` the ensemble of every
+    row.  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats with ``slice_counts`` [E, 8] and ``rounds``).  The rows of
+    the steps below ``tune_steps`` are not a stationary chain: discard them."""
+    run = SliceRounds(x, lnl, accepted, mu, step0, n_steps, thin, seed, streams, lo, hi, log_norm, tune_steps, max_expansions,
+                      max_contractions)
+    chi2 = status = None
+    while run.active:
+        rows, ens = run.round(chi2, status)
+        if rows.shape[0]:
+            chi2, status = evaluate(rows, ens)
+    st = dict(steps=n_steps, proposals=int(run.counts[:, SC_UPDATES].sum()), accepted=int(run.counts[:, SC_MOVED].sum()),
+              rejected_outside_box=0, rejected_failed_model=0, slice_counts=run.counts, rounds=run.rounds)
+    if run.rows != int(run.counts[:, SC_ROWS].sum()):
+        raise RuntimeError("slice: the engine's rows are not the walkers' requests")
+    return run.chain, run.chain_lnl, st
 
 
 def python_steps(x, lnl, accepted, step0, n_steps, thin, a, seed, stream, lo, hi, log_norm, evaluate, moves=None):
@@ -918,7 +1290,7 @@ class StretchSampler(EngineSampler):
     _lead = ()
 
     def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves=None,
-                       gamma0=None, sigma=None, gamma_s=None):
+                       gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None):
         self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         self.W = int(walkers)
         if self.W % 2 or self.W < 2 * self.n:
@@ -930,6 +1302,11 @@ class StretchSampler(EngineSampler):
         if self.thin < 1:
             raise ValueError('thin >= 1')
         self.segment = max(1, int(segment))
+        # ensemble slice sampling (None: not asked for): mu0 and tune_steps; it is no member of a mixture
+        self.slice = resolve_slice(moves, self.W, mu, tune_steps, gamma0, sigma, gamma_s)
+        if self.slice is not None:
+            self.moves, self._moves_kw = None, dict(moves='slice', mu=self.slice['mu0'], tune_steps=self.slice['tune_steps'])
+            return
         # the mixture of moves (None: the stretch move alone, the run of ever) and what asked for it, for a set's members
         self.moves = resolve_moves(moves, self.n, self.W, gamma0, sigma, gamma_s)
         self._moves_kw = {} if moves is None else dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s)
@@ -944,6 +1321,24 @@ class StretchSampler(EngineSampler):
         if self.moves is not None:
             self._start = None          # (the walkers ahead of the first step: what the first recorded row is compared with)
             self.stats['moves'] = MoveCounts(self)
+        if self.slice is not None:
+            lead = int(np.prod(self._lead, dtype=np.int64))
+            self.mu = np.full(lead, self.slice['mu0'])
+            self.slice_counts = np.zeros((lead, 8), dtype=np.int64)
+            self.stats['rounds'] = 0
+            self._slice_took()
+
+    def _slice_took(self, st=None):
+        """The counts of a segment join the run's: ``stats['slice']``, ``stats['mu']`` and ``stats['moves']`` as the drivers'
+        counters have them."""
+        if st is not None:
+            self.slice_counts += st['slice_counts']
+        self.stats['slice'] = slice_stats(self.slice_counts, self.mu)
+        self.stats['mu'] = self.mu.copy() if self._lead else float(self.mu[0])
+        self.stats['moves'] = {'slice': dict(proposals=self.stats['slice']['updates'], accepted=self.stats['slice']['moved'])}
+
+    def _slice_arg(self):
+        return dict(tune_steps=self.slice['tune_steps'], max_expansions=SLICE_MAX_EXPANSIONS, max_contractions=SLICE_MAX_CONTRACTIONS)
 
     def move_counts(self):
         """Per move the proposals and the accepted ones of the steps run so far, int64 [(E,) 3, 2] in the order of
@@ -988,6 +1383,8 @@ class StretchSampler(EngineSampler):
             for key in st:
                 if key in self.stats:
                     self.stats[key] += st[key]
+            if self.slice is not None:
+                self._slice_took(st)
             self.stats['calls'] += 1
             self.step += k
             done += k
@@ -1035,12 +1432,21 @@ class EnsembleSampler(StretchSampler):
     (default 2.38 / sqrt(2 n)) and ``sigma`` (1e-5) are the DE move's scale and jitter, ``gamma_s`` (1.7) the snooker's scale;
     DE needs 4 walkers, the snooker 6.  ``stats['moves']`` then counts per move the proposals and - with a row for every step
     (thin = 1) - the accepted ones, on the host from the words the moves were drawn from, when it is read
-    (:class:`MoveCounts`: the run itself does not pay for it)."""
+    (:class:`MoveCounts`: the run itself does not pay for it).
+
+    ``moves='slice'``: ensemble slice sampling (Karamanis & Beutler 2021, zeus's differential move; vmx_ensemble_run_slice, and
+    :func:`python_steps_slice_many` the same run bit for bit) instead of a proposal and a decision - a sampler of its own, not a
+    member of a mixture.  Every update moves its walker along the difference of two walkers of the other half, scaled by ``mu``
+    (default 1.0), to a point drawn by a slice-sampling bracket; a trial point outside the box costs no likelihood row.  ``mu``
+    tunes itself after every step with global index below ``tune_steps`` (default 100): discard those rows.  ``a`` is not read.
+    ``stats['slice']`` holds the counts of ``SLICE_COUNT_NAMES`` (summed, and ``per_ensemble``) with ``rows_per_update``,
+    ``stats['mu']`` the scale as it stands, ``stats['moves']`` is ``{'slice': {proposals: updates, accepted: moved}}``,
+    ``stats['rounds']`` the rounds of the run, and ``accepted`` counts per walker the updates that moved it."""
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
-                 chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None):
+                 chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s)
+                            sigma, gamma_s, mu, tune_steps)
         self.stream = int(stream)
         self.reset()
 
@@ -1095,6 +1501,12 @@ class EnsembleSampler(StretchSampler):
     # ---- run
     def _segment_device(self, theta, k):
         self.vega._sync_monte_carlo()
+        if self.slice is not None:      # (the single run is the set of one)
+            chain, chain_lnl, st = self.vega.engine.ensemble_run_slice(
+                self.cols, self.lo, self.hi, theta, self.x[None], self.lnl[None], self.accepted[None], [self.stream], self.mu,
+                self.step, k, thin=self.thin, log_norm=self.log_norm(), seed=self.seed, const_hint=self.const_hint,
+                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg())
+            return chain[0], chain_lnl[0], st
         chain, chain_lnl, st = self.vega.engine.ensemble_run(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.step, k, thin=self.thin, a=self.a,
             log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint, chunk=self.chunk,
@@ -1102,6 +1514,11 @@ class EnsembleSampler(StretchSampler):
         return chain, chain_lnl, st
 
     def _python_steps(self, k, chi2):
+        if self.slice is not None:
+            chain, chain_lnl, st = python_steps_slice_many(
+                self.x[None], self.lnl[None], self.accepted[None], self.mu, self.step, k, self.thin, self.seed, [self.stream],
+                self.lo, self.hi, self.log_norm(), lambda rows_x, ens: chi2(rows_x), **self._slice_arg())
+            return chain[0], chain_lnl[0], st
         return python_steps(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.stream, self.lo,
                             self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x), self.moves)
 
@@ -1116,7 +1533,8 @@ class EnsembleSampler(StretchSampler):
 
     def get_chain(self, discard=0, thin=1, flat=False):
         """Recorded positions [rows, W, n] (rows = steps / thin of the sampler), ``discard`` / ``thin`` in recorded rows;
-        ``flat``: [rows W, n]."""
+        ``flat``: [rows W, n].  With ``moves='slice'`` the rows of the steps below ``tune_steps`` - while the scale is tuned - are
+        not a stationary chain: discard them."""
         return self._stack(self._chain, discard, thin, flat)
 
     def get_log_lik(self, discard=0, thin=1, flat=False):
@@ -1151,12 +1569,15 @@ class EnsembleSet(StretchSampler):
     where the engine's batches are shaped differently.  ``mock_rows`` [E]: the row of the installed mock
     pools every ensemble is compared with - a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`);
     None: every ensemble reads the data the interface has installed - replicas of one run.  An engine group takes ``'python'``.
-    ``moves``, ``gamma0``, ``sigma``, ``gamma_s``: the mixture of moves of every ensemble, as for :class:`EnsembleSampler`."""
+    ``moves``, ``gamma0``, ``sigma``, ``gamma_s``: the mixture of moves of every ensemble, as for :class:`EnsembleSampler`;
+    ``moves='slice'`` with ``mu`` / ``tune_steps``: ensemble slice sampling, every ensemble with a scale of its own
+    (vmx_ensemble_run_slice: the ensembles' requests of a round packed behind each other)."""
 
     def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
-                 sample_params=None, chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None):
+                 sample_params=None, chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
+                 tune_steps=None):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s)
+                            sigma, gamma_s, mu, tune_steps)
         self.E = int(ensembles)
         if self.E < 1:
             raise ValueError('ensembles: at least one')
@@ -1227,13 +1648,32 @@ class EnsembleSet(StretchSampler):
     # ---- run
     def _segment_device(self, theta, k):
         self.vega._sync_monte_carlo()
+        if self.slice is not None:
+            chain, chain_lnl, st = self.vega.engine.ensemble_run_slice(
+                self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.mu, self.step, k,
+                mock_rows=self.mock_rows, thin=self.thin, log_norm=self.log_norm(), seed=self.seed, const_hint=self.const_hint,
+                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg())
+            return chain, chain_lnl, st, self._slice_per(st)
         chain, chain_lnl, st = self.vega.engine.ensemble_run_many(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.step, k,
             mock_rows=self.mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(), seed=self.seed,
             const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, **self._moves_arg())
         return chain, chain_lnl, st, st.pop('per_ensemble')
 
+    @staticmethod
+    def _slice_per(st):
+        """``per_ensemble`` [E, 3] of a slice segment: moved; nothing is rejected."""
+        per = np.zeros((st['slice_counts'].shape[0], 3), dtype=np.int64)
+        per[:, 0] = st['slice_counts'][:, SC_MOVED]
+        return per
+
     def _python_steps(self, k, chi2):
+        if self.slice is not None:
+            mocks = self.mock_rows
+            chain, chain_lnl, st = python_steps_slice_many(
+                self.x, self.lnl, self.accepted, self.mu, self.step, k, self.thin, self.seed, self.streams, self.lo, self.hi,
+                self.log_norm(), lambda rows_x, ens: chi2(rows_x, None if mocks is None else mocks[ens]), **self._slice_arg())
+            return chain, chain_lnl, st, self._slice_per(st)
         row_mock = None if self.mock_rows is None else np.repeat(self.mock_rows, self.W // 2)
         return python_steps_many(self.x, self.lnl, self.accepted, self.step, k, self.thin, self.a, self.seed, self.streams, self.lo,
                                  self.hi, self.log_norm(), lambda rows_x, h: chi2(rows_x, row_mock), self.moves)
@@ -1246,7 +1686,8 @@ class EnsembleSet(StretchSampler):
 
     def get_chain(self, discard=0, thin=1, flat=False):
         """Recorded positions [E, rows, W, n] (rows = steps / thin of the set), ``discard`` / ``thin`` in recorded rows; ``flat``:
-        [E, rows W, n]."""
+        [E, rows W, n].  With ``moves='slice'`` the rows of the steps below ``tune_steps`` - while the scale is tuned - are not a
+        stationary chain: discard them."""
         return self._stack(self._chain, (self.n,), discard, thin, flat)
 
     def get_log_lik(self, discard=0, thin=1, flat=False):
@@ -1277,6 +1718,10 @@ class EnsembleSet(StretchSampler):
         if self.moves is not None:
             m._start = None if self._start is None else (self._start[0][e].copy(), self._start[1][e].copy())
             m.stats['moves'] = MoveCounts(m)
+        if self.slice is not None:
+            m.mu, m.slice_counts = self.mu[e:e + 1].copy(), self.slice_counts[e:e + 1].copy()
+            m.stats['proposals'] = int(m.slice_counts[0, SC_UPDATES])
+            m._slice_took()
         return m
 
 
@@ -1361,6 +1806,8 @@ class TemperedEnsemble(EnsembleSet):
                  a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, chunk=0, lanes=0, const_hint=-1,
                  moves=None, gamma0=None, sigma=None, gamma_s=None, adapt=False, adapt_steps=None, adaptation_lag=10000,
                  adaptation_time=100):
+        if _names_slice(moves):
+            raise ValueError("moves: 'slice' does not combine with parallel tempering (ntemps / betas)")
         if (ntemps is None) == (betas is None):
             raise ValueError('ntemps or betas: one of the two')
         if betas is None:
@@ -1709,6 +2156,8 @@ def _parse_tempering(sec, out):
     adaptive ladder of :class:`TemperedEnsemble` (``ntemps >= 3``, ``swap_every >= 1``), with ``adapt_steps`` (default
     ``steps // 2``, so that rows remain for the evidence) and, when stated, ``adaptation_lag`` and ``adaptation_time``; these keys
     too are added only when the section states ``adapt``."""
+    if 'ntemps' in sec and out.get('moves') == 'slice':
+        raise ValueError('[Ensemble] moves = slice does not combine with ntemps (parallel tempering)')
     if 'ntemps' not in sec:
         stray = [key for key in ('beta_min', 'swap_every') + _ADAPT_KEYS if key in sec]
         if stray:
@@ -1789,6 +2238,13 @@ def _parse_moves(sec, out, n):
                 scales[key] = sec.getfloat(key)
             except ValueError:
                 raise ValueError(f'[Ensemble] {key}: a number') from None
+    tokens = sec.get('moves', '').replace(',', ' ').split()
+    slice_keys = [key for key, _ in _SLICE_KEYS if key in sec]
+    if 'slice' in tokens:
+        _parse_slice(sec, out, tokens, scales)
+        return
+    if slice_keys:
+        raise ValueError(f'[Ensemble] {", ".join(slice_keys)}: settings of ensemble slice sampling, but moves is not slice')
     if 'moves' not in sec:
         if scales:
             raise ValueError(f'[Ensemble] {", ".join(scales)}: the scales of moves, but no moves are named')
@@ -1815,11 +2271,38 @@ def _parse_moves(sec, out, n):
         raise ValueError(f'[Ensemble] {err}') from None
 
 
+_SLICE_KEYS = (('slice_mu', 'mu'), ('slice_tune_steps', 'tune_steps'))
+
+
+def _parse_slice(sec, out, tokens, scales):
+    """``moves = slice`` of ``[Ensemble]``: ensemble slice sampling, ``out['moves'] = 'slice'``; ``slice_mu`` and
+    ``slice_tune_steps`` into the keys of the same names when stated."""
+    if tokens != ['slice']:
+        raise ValueError("[Ensemble] moves: 'slice' is a sampler of its own, not a member of a mixture: moves = slice")
+    if scales:
+        raise ValueError(f'[Ensemble] {", ".join(scales)}: scales of the stretch / DE / snooker moves, not of slice')
+    out['moves'] = 'slice'
+    try:
+        if 'slice_mu' in sec:
+            out['slice_mu'] = sec.getfloat('slice_mu')
+        if 'slice_tune_steps' in sec:
+            out['slice_tune_steps'] = sec.getint('slice_tune_steps')
+    except ValueError:
+        raise ValueError('[Ensemble] slice_mu: a number; slice_tune_steps: a whole number') from None
+    try:
+        resolve_slice(**moves_arguments(out), walkers=out['walkers'])
+    except ValueError as err:
+        raise ValueError(f'[Ensemble] {err}') from None
+
+
 def moves_arguments(cfg):
-    """The ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s`` arguments of the sampler classes the settings ``cfg`` ask for: empty
-    without ``moves``, so that a run without them is constructed as ever."""
+    """The ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s`` arguments of the sampler classes the settings ``cfg`` ask for (with
+    ``moves = slice``: ``moves`` / ``mu`` / ``tune_steps``): empty without ``moves``, so that a run without them is constructed as
+    ever."""
     if 'moves' not in cfg:
         return {}
+    if cfg['moves'] == 'slice':
+        return dict(moves='slice', **{arg: cfg[key] for key, arg in _SLICE_KEYS if key in cfg})
     return dict(moves=cfg['moves'], **{arg: cfg[key] for key, arg in _MOVE_KEYS if key in cfg})
 
 
