@@ -1085,6 +1085,10 @@ void* vmx_stream(vmx_engine* e);
  * the distortion product (refused after a chi2-only evaluation and after a single walker's fused product, which keeps none).
  * 4 has one more entry, [9]: the bins kernels the last evaluation launched, a mask of VMX_ROUTE_* (kept with a captured chain,
  * so it holds for a replayed graph too; VMX_ROUTE_POLY_BINS says what set-up launched).
+ * And [10]: the form the FFTLog o spline product (coefficients = operator x P_ell) of the last evaluation took, a mask of
+ * VMX_FFT_* with the streaming kernel's columns per pass above VMX_FFT_NB_SHIFT (kept with a captured chain like [9]; 0: the
+ * evaluation had no such product).  The table level and the nodes per wavenumber ([4], [2]) are those of the evaluation itself
+ * as well, replayed graph or not.
  * The operands of the spline-bins stage, for an oracle that starts where the kernels start (host-side copies, no kernel):
  * 6 = the walkers' scalars [B][n_pipelines][VMX_DEBUG_NS] of the last evaluation; 7 = where the entries the bins read sit in
  * such a row: {VMX_DEBUG_NS, then the indices in the order of VMX_DEBUG_SCALARS};
@@ -1119,6 +1123,15 @@ enum { VMX_ROUTE_GENERAL = 1,            /* k_xi_bins<false> */
        VMX_ROUTE_QUAD_PLAIN = 512,       /* k_xi_quad_plain<2, .> */
        VMX_ROUTE_SAME_GRID = 1024,       /* the SAME = true instantiations (one ln r grid for every multipole) */
        VMX_ROUTE_POLY_BINS = 2048 };     /* set-up ran k_poly_bins */
+enum { VMX_FFT_GEMV1 = 1,               /* k_gemv1: a single column, x in LDS */
+       VMX_FFT_GEMV = 2,                /* k_gemv<NB>: at most 8 columns, NB = (mask >> VMX_FFT_NB_SHIFT) of them per pass */
+       VMX_FFT_MFMA64 = 4,              /* k_gemm_nt44<KC_FFTLOG>: 64 x 64 tiles, two buffers */
+       VMX_FFT_MFMA32 = 8,              /* k_gemm_nt44<KC_FFTLOG, 2, 32>: 64 x 32 tiles */
+       VMX_FFT_RING = 16,               /* k_gemm_nt44<KC_FFTLOG, 4>: 64 x 64 tiles, four-buffer ring */
+       VMX_FFT_BATCH_X = 32,            /* MFMA forms: the multipoles folded into grid.x ... */
+       VMX_FFT_BATCH_Y = 64,            /* ... or in grid.y (the streaming kernels keep them in grid.z: neither bit) */
+       VMX_FFT_K_LIMIT = 128,           /* the kernel was handed the device column limit (live wavenumbers, tap 4 [0]) */
+       VMX_FFT_NB_SHIFT = 8 };
 /* The device math functions of the kernels, elementwise on host arrays (a trivial kernel of its own; for tests against
  * extended precision): which = 0 vmx_log, 1 vmx_exp, 2 vmx_rsqrt.  x [n] -> out [n]. */
 int vmx_debug_math(vmx_engine* e, int32_t which, const double* x, int64_t n, double* out);

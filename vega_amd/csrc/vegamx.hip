@@ -1864,7 +1864,9 @@ struct vmx_engine {
     // bins kernels of the last evaluation (vmx_debug_read 4 [9], VMX_ROUTE_*); route_setup: those of set-up.  A replayed graph runs
     // no host code: graph_route keeps the mask and last_taps of each captured chain.
     int last_route = 0, route_setup = 0;
-    struct ChainFacts { int route = 0; bool taps = true; };
+    // form of the FFTLog o spline product of the last evaluation (vmx_debug_read 4 [10], VMX_FFT_*): set where it is launched
+    int last_fft_form = 0;
+    struct ChainFacts { int route = 0; bool taps = true; int fft_form = 0; int tab2_kt = 0; };
     std::map<int, ChainFacts> graph_route;
     // VMX_TRACE_HOST: host-side phases of vmx_eval accumulated in nanoseconds (staging, enqueue, wait), printed at destroy
     bool trace_host = false; double host_ns[3] = {0, 0, 0}; int64_t host_calls = 0;
@@ -2119,6 +2121,7 @@ static void launch_gemm_group(vmx_engine* e, int kc, const GemmGroup& G, int per
             case KC_DISTORTION: hipLaunchKernelGGL((k_gemm_nt44<KC_DISTORTION>), grid, block, 0, e->cur, G); break;
             case KC_METAL: hipLaunchKernelGGL((k_gemm_nt44<KC_METAL>), grid, block, 0, e->cur, G); break;
             case KC_FFTLOG:
+                e->last_fft_form = G.p[0].k_limit ? VMX_FFT_K_LIMIT : 0;
                 if (getenv("VMX_GEMM_TRACE")) {
                     e->gemm_trace_blocks = (size_t)2 * grid.x * grid.y;       // (the 64 x 32 tiling has up to twice the blocks)
                     if (e->gemm_trace.n < 4 * e->gemm_trace_blocks) (void)e->gemm_trace.alloc(4 * e->gemm_trace_blocks, true);
@@ -2142,25 +2145,29 @@ static void launch_gemm_group(vmx_engine* e, int kc, const GemmGroup& G, int per
                         // (+ 24 KB of unused dynamic LDS: 72 KB per block = two per CU.  With its own 48 KB the dispatcher packs three
                         // blocks on a CU before it moves on and leaves a third of the CUs empty.)
                         const size_t pad = 24 * 1024;
+                        e->last_fft_form |= VMX_FFT_MFMA32 | (G2.batch_in_x ? VMX_FFT_BATCH_X : VMX_FFT_BATCH_Y);
                         hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG, 2, 32>), grid2, block, pad, e->cur, G2);
                         break;
                     }
                 }
+                e->last_fft_form |= Gx.batch_in_x ? VMX_FFT_BATCH_X : VMX_FFT_BATCH_Y;
                 if (e->fft_ring && e->ring_allowed && G.n == 1 && G.p[0].m_window) {
                     const int64_t est = (int64_t)G.p[0].tn * nbatch * ((G.p[0].tm * 3 + 9) / 10);
-                    if (est < 160 || est > 320) { hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG>), gridx, block, 0, e->cur, Gx); break; }
+                    if (est < 160 || est > 320) { e->last_fft_form |= VMX_FFT_MFMA64; hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG>), gridx, block, 0, e->cur, Gx); break; }
                     constexpr size_t ring_bytes = (size_t)4 * (GEMM_BM + GEMM_BN) * GEMM_BK * sizeof(double);
                     if (!e->fft_ring_attr) {
                         if (hipFuncSetAttribute((const void*)k_gemm_nt44<KC_FFTLOG, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_bytes) != hipSuccess) {
                             (void)hipGetLastError();
                             e->fft_ring = false;
+                            e->last_fft_form |= VMX_FFT_MFMA64;
                             hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG>), gridx, block, 0, e->cur, Gx);
                             break;
                         }
                         e->fft_ring_attr = true;
                     }
+                    e->last_fft_form |= VMX_FFT_RING;
                     hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG, 4>), gridx, block, ring_bytes, e->cur, Gx);
-                } else hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG>), gridx, block, 0, e->cur, Gx);
+                } else { e->last_fft_form |= VMX_FFT_MFMA64; hipLaunchKernelGGL((k_gemm_nt44<KC_FFTLOG>), gridx, block, 0, e->cur, Gx); }
                 break;
             default: hipLaunchKernelGGL((k_gemm_nt44<KC_OTHER>), grid, block, 0, e->cur, G); break;
         }
@@ -2187,6 +2194,7 @@ static int launch_product(vmx_engine* e, int kc, const double* A, int lda, int64
         const int blocks = gemv1_blocks(M);
         dim3 grid(blocks, 1, nbatch), block(256);
         const size_t shmem = (size_t)K * sizeof(double);
+        if (kc == KC_FFTLOG) e->last_fft_form = VMX_FFT_GEMV1;
         if (fused_item >= 0) {
             if (K <= 2560) hipLaunchKernelGGL((k_gemv1<5, 1>), grid, block, shmem, e->cur, g, e->dev, fused_item);
             else hipLaunchKernelGGL((k_gemv1<10, 1>), grid, block, shmem, e->cur, g, e->dev, fused_item);
@@ -2199,6 +2207,8 @@ static int launch_product(vmx_engine* e, int kc, const double* A, int lda, int64
     if (N <= 8) {
         g.nsplit = 1; g.klen = K; g.d_slab = 0;
         dim3 grid((M + 3) / 4, 1, nbatch), block(256);
+        // (the streaming kernels read whole rows: no column limit; their batch is grid.z)
+        if (kc == KC_FFTLOG) e->last_fft_form = VMX_FFT_GEMV | ((N == 1 ? 1 : N == 2 ? 2 : N <= 4 ? 4 : 8) << VMX_FFT_NB_SHIFT);
         switch (N) {
             case 1: hipLaunchKernelGGL(k_gemv<1>, grid, block, 0, e->cur, g); break;
             case 2: hipLaunchKernelGGL(k_gemv<2>, grid, block, 0, e->cur, g); break;
@@ -3948,6 +3958,7 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
     {
         const int64_t ncols = (int64_t)B * e->n_active;
         const bool pads = e->pad_l + e->pad_r > 0;
+        e->last_fft_form = 0;
         if (ncols > 0 && pads) {
             // fht_extrap: the power-law pads of every (multipole, pipeline, walker) row, behind its samples
             ScopedTimer t(e, KC_FFTLOG);
@@ -4457,15 +4468,22 @@ static int run_chain_cached(vmx_engine* e, int B, int tab_mode, bool zero_copy =
             return run_chain(e, B, tab_mode, zero_copy, nullptr, nullptr, nullptr, quad);
         }
         it = e->graphs.emplace(key, exec).first;
-        e->graph_route[key].route = e->last_route;        // (of the capture: the launches the graph replays)
-        e->graph_route[key].taps = e->last_taps;
+        vmx_engine::ChainFacts& captured = e->graph_route[key];       // (of the capture: the launches the graph replays)
+        captured.route = e->last_route;
+        captured.taps = e->last_taps;
+        captured.fft_form = e->last_fft_form;
+        captured.tab2_kt = e->last_tab2_kt;
     }
     HIP_OK(hipGraphLaunch(it->second, e->stream));
     e->last_B = B;
     e->last_full = !quad;
     e->last_form = quad ? (e->quad_factored ? 2 : 1) : 0;       // (a replayed graph runs no host code: run_chain set this at capture only)
-    e->last_route = e->graph_route[key].route;
-    e->last_taps = e->graph_route[key].taps;
+    const vmx_engine::ChainFacts& facts = e->graph_route[key];
+    e->last_route = facts.route;
+    e->last_taps = facts.taps;
+    e->last_fft_form = facts.fft_form;
+    e->last_tab_level = tab_mode;          // (vmx_debug_read 4 [4], [2]: of this chain, not of the last one captured)
+    e->last_tab2_kt = facts.tab2_kt;
     return 0;
 }
 
@@ -6955,7 +6973,8 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (capacity >= 7) { out[5] = live[2]; out[6] = live[3]; }
         if (capacity >= 9) out[8] = e->last_form;               // 0: full chain, 1: the quadratic form Q', 2: its factored form
         if (capacity >= 10) out[9] = e->last_route | e->route_setup;        // bins kernels launched (VMX_ROUTE_*)
-        if (capacity >= 8) { out[7] = live[4]; return capacity >= 10 ? 10 : capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
+        if (capacity >= 11) out[10] = e->last_fft_form;         // form of the FFTLog o spline product (VMX_FFT_*)
+        if (capacity >= 8) { out[7] = live[4]; return capacity >= 11 ? 11 : capacity >= 10 ? 10 : capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
         return capacity >= 7 ? 7 : capacity >= 5 ? 5 : capacity >= 4 ? 4 : 3;
     }
     else if (what == 5) {

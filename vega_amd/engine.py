@@ -1717,6 +1717,17 @@ class Engine:
         mask = int(self.debug_read(4, 0, 10)[9])
         return {name for name, bit in self.ROUTE_BITS.items() if mask & bit}
 
+    FFTLOG_FORM_BITS = {'gemv1': 1, 'gemv': 2, 'mfma64': 4, 'mfma32': 8, 'ring': 16, 'batch_x': 32, 'batch_y': 64, 'k_limit': 128}
+
+    def fftlog_form(self):
+        """The form the FFTLog o spline product of the last evaluation took: the set of FFTLOG_FORM_BITS names, with 'nb2' / 'nb4'
+        / 'nb8' for the streaming kernel's columns per pass (vmx_debug_read 4 [10]; empty: no such product ran)."""
+        mask = int(self.debug_read(4, 0, 11)[10])
+        form = {name for name, bit in self.FFTLOG_FORM_BITS.items() if mask & bit}
+        if mask >> 8:
+            form.add(f'nb{mask >> 8}')
+        return form
+
     def bins_scalar_index(self):
         """{'NS': row length, 'AP': index, ...} of a walker's scalars as the bins kernels read them (vmx_debug_read 7)."""
         idx = self.debug_read(7, 0, 32).astype(int)
