@@ -160,7 +160,8 @@ const char* vmx_last_error(void);
  * 7 vmx_fit_stats, 8 vmx_ensemble_spec, 9 vmx_ensemble_options, 10 vmx_ensemble_stats, 11 vmx_nested_spec, 12 vmx_nested_options,
  * 13 vmx_nested_stats, 14 vmx_smc_spec, 15 vmx_smc_options, 16 vmx_smc_stats, 17 vmx_nested_clusters,
  * 18 vmx_nested_set_options, 19 vmx_nested_phantoms, 20 vmx_nested_set_phantoms, 21 vmx_smc_keep,
- * 23 vmx_ensemble_moves, 24 vmx_ensemble_adapt, 25 vmx_ensemble_slice; 22 is vacant and answers -1, as every index that names no struct): lets a foreign
+ * 23 vmx_ensemble_moves, 24 vmx_ensemble_adapt, 25 vmx_ensemble_slice, 27 vmx_ensemble_cov; 22 and 26 are vacant and answer -1, as every index
+ * that names no struct): lets a foreign
  * binding verify its struct layout at load time. */
 int vmx_struct_size(int32_t which);
 
@@ -630,6 +631,39 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
                            double* chain, double* chain_lnL,
                            const vmx_ensemble_options* opt, vmx_ensemble_stats* stats,
                            const vmx_ensemble_slice* slice, double* mu, int64_t* slice_counts);
+/* The covariance move: vmx_ensemble_run_many_moves with a fourth member in the mixture, a Metropolis step whose increment has the
+ * covariance of the complementary half scaled by gamma_c - emcee's WalkMove taken over the whole other half, with the
+ * Roberts-Gelman-Gilks scale 2.38 / sqrt(n).  The stretch, DE and snooker moves take their direction from one, two or three
+ * partners; this one uses what the other half knows about the posterior's shape.  It is a red-blue move like them: the factor
+ * depends on the other half alone, so the half-step, the box rule and the decision are unchanged.  The mean, the covariance, its
+ * lower Cholesky factor C (the operation order of vmx_ns::cholesky; a pivot that is not positive: diag(sqrt(cov_aa)), counted as a
+ * fallback), the variate z of a 64-bit word (the centred sum of its four 16-bit fields: unit variance, symmetric, not normal), the
+ * further Philox blocks (counter (k, s, h, 2 + b / 4)) and the proposal y = s + gamma_c (C z) are pinned in
+ * vega_amd/csrc/vmx_ensemble.h, the sixth part.  The half-step kernel is k_ens_half_cov: between the decision and the proposals
+ * the ensemble's work-group computes the factor in LDS, every entry by one thread with the pinned serial expression, so that the
+ * factor is the serial one bit for bit.
+ *   cov       weight: the move's weight beside moves->weights (stretch, DE, snooker), >= 0 - the four need a positive sum, and
+ *             moves must not be NULL when the weight is positive; scale: gamma_c (default 2.38 / sqrt(n), computed by the caller);
+ *             flags, reserved: 0.  NULL, or weight 0, runs exactly vmx_ensemble_run_many_moves.
+ *   fallbacks [E] (NULL: not wanted), of this call: the half-steps whose factor fell back to the diagonal
+ *   everything else as for vmx_ensemble_run_many_moves; the single run is E = 1.
+ * Refused before anything runs (-1, vmx_last_error, the engine untouched): whatever vmx_ensemble_run_many_moves refuses; a
+ * negative or non-finite cov weight; a zero sum over the four weights; a cov weight with W / 2 < 2; a scale that is not positive
+ * and finite; flags or reserved not 0.
+ * vmx_ensemble_cov_factor runs the factor stage alone, for tests and diagnostics: the halves x [E][H][n] (2 <= H, 1 <= n <=
+ * VMX_ENS_MAXN, n <= H not required) give mean [E][n], factor [E][n][n] (lower, the strict upper triangle 0) and flag [E] (1: the
+ * Cholesky factor, 0: the diagonal fallback).  The engine gives the device and the stream; nothing of it is read or changed. */
+typedef struct { double weight, scale; uint32_t flags, reserved; } vmx_ensemble_cov;
+int vmx_ensemble_run_many_cov(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W,
+                              const uint64_t* streams, const int32_t* mock_row,
+                              double* x, double* lnL, int64_t* accepted,
+                              int64_t step0, int32_t n_steps, int32_t thin,
+                              double* chain, double* chain_lnL,
+                              const vmx_ensemble_options* opt,
+                              vmx_ensemble_stats* stats, int64_t* per_ensemble,
+                              const vmx_ensemble_moves* moves, const vmx_ensemble_cov* cov, int64_t* fallbacks);
+int vmx_ensemble_cov_factor(vmx_engine* e, int32_t E, int32_t H, int32_t n, const double* x, double* mean, double* factor,
+                            int32_t* flag);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

@@ -229,6 +229,7 @@ struct EnsWorkspace {
     DevBuf<int64_t> swaps;              // ... and the call's swap counters [G][T - 1][2]
     DevBuf<double> beta_hist;           // adaptive ladders: the ladders after every sweep of the call [sweeps][G][T] ...
     DevBuf<int64_t> adapt_skipped;      // ... and the sweeps whose adjustment the guard dropped [G]
+    DevBuf<int64_t> cov_fallbacks;      // the covariance move: the half-steps of the call whose factor fell back to the diagonal [E]
     // ensemble slice sampling (vmx_ensemble_run_slice), sized once per (E, W, n): the active half's machines [E][H] and directions
     // [E][H][n], the walkers' rows and the rows' walkers [E][H], the scales [E], the counts [E][8] and the open step's expansions
     // and contractions [E][2], the half-steps done [E], whether a half is open [E], the running list and its counts [E]
@@ -273,6 +274,63 @@ struct EnsPtDev {
 };
 enum { ENS_PT_DECIDE = 1, ENS_PT_RECORD = 2, ENS_PT_PROPOSE = 4 };
 
+// The covariance move (vmx_ensemble_run_many_cov; vmx_ensemble.h, the sixth part) as k_ens_half_cov reads it beside EnsMovesDev:
+// the third threshold, the scale gamma_c and the call's fallback counters
+struct EnsCovDev { double t2, scale; int64_t* fallbacks; };     // fallbacks [E]
+
+// The factor of a half in LDS: C [n][ld], ld = n | 1 - an odd row stride, so that the threads of a Cholesky column, which read
+// rows i, i + 1, ... at the same k, fall on different banks (with ld = 64 all of them would fall on one) - the mean, the
+// covariance's diagonal for the fallback, and whether every pivot was positive.  n^2 + 3 n doubles at most: 34.3 KB at n = 64.
+struct EnsCovLds {
+    double C[VMX_ENS_MAXN * (VMX_ENS_MAXN + 1)];
+    double mean[VMX_ENS_MAXN], diag[VMX_ENS_MAXN];
+    int good;
+};
+__device__ __forceinline__ int ens_cov_ld(int n) { return n | 1; }
+
+// The factor stage: the work-group computes vmx_ens::half_factor of the half c[H][n] into L, every entry by exactly one thread
+// with the pinned function of that entry, so that the result is the serial one bit for bit.  Means: a thread per column.
+// Covariance: a thread per entry of the lower triangle, strided by the block.  Cholesky: column by column in place; thread 0 takes
+// the pivot, the entries below it go to different threads; a barrier after the pivot, one after the column.  A pivot that is not
+// positive is written to LDS and read by all threads after the barrier: they leave the loop together, and write the diagonal
+// fallback.  Returns whether the factor is the Cholesky factor; L is complete and visible to the block on return.
+__device__ __forceinline__ bool ens_factor_stage(EnsCovLds& L, const double* c, int H, int n)
+{
+    const int ld = ens_cov_ld(n), entries = n * (n + 1) / 2;
+    for (int a = threadIdx.x; a < n; a += blockDim.x) L.mean[a] = vmx_ens::half_mean_entry(a, c, H, n);
+    if (threadIdx.x == 0) L.good = 1;
+    __syncthreads();
+    for (int q = threadIdx.x; q < entries; q += blockDim.x) {
+        int a, b;
+        vmx_ens::tri_entry(q, a, b);
+        const double v = vmx_ens::half_cov_entry(a, b, c, L.mean, H, n);
+        L.C[a * ld + b] = v;
+        if (a == b) L.diag[a] = v;
+    }
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+        if (threadIdx.x == 0) {
+            const double s = vmx_ens::chol_pivot(j, L.C, ld);
+            if (s > 0.0) L.C[j * ld + j] = sqrt(s);
+            else L.good = 0;
+        }
+        __syncthreads();
+        if (!L.good) break;         // (the same word for every thread, written before the barrier and not again)
+        const double piv = L.C[j * ld + j];
+        for (int i = j + 1 + threadIdx.x; i < n; i += blockDim.x) L.C[i * ld + j] = vmx_ens::chol_entry(i, j, L.C, ld, piv);
+        __syncthreads();
+    }
+    const bool good = L.good != 0;
+    if (!good)
+        for (int q = threadIdx.x; q < entries; q += blockDim.x) {
+            int a, b;
+            vmx_ens::tri_entry(q, a, b);
+            L.C[a * ld + b] = a == b ? vmx_ens::fallback_entry(L.diag[a]) : 0.0;
+        }
+    __syncthreads();
+    return good;
+}
+
 // One half-step of the sampler, the body of the three kernels below.  A grid of E work-groups: work-group e owns ensemble e
 // (partners read the half decided just before, a dependency across the whole ensemble; nothing crosses ensembles, so
 // __syncthreads() is the only barrier) under the Philox stream streams[e].  Decide the proposals of half h_dec at step s_dec
@@ -288,11 +346,15 @@ enum { ENS_PT_DECIDE = 1, ENS_PT_RECORD = 2, ENS_PT_PROPOSE = 4 };
 //   `what` names the parts to run: all three between two half-steps without a sweep; with a sweep due, ENS_PT_DECIDE alone, then
 // k_ens_swap, then ENS_PT_RECORD | ENS_PT_PROPOSE, so that the row of step s_dec and the next proposals see the walkers after the
 // swaps.
+//   COV (with MOVES): the mixture has the covariance move as its fourth member.  Between the barrier that follows the decision
+// and the propose loop the work-group computes the factor of the other half into Lc (ens_factor_stage), and thread 0 counts a
+// fallback; a walker that draws the move writes its variates into its proposal row and multiplies them by the factor in place.
 constexpr int ENS_THREADS = 1024;
-template <bool MOVES, bool PT>
-__device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, const EnsPtDev& Pt, int64_t s_dec, int h_dec,
-                                         int64_t s_prop, int h_prop, int what)
+template <bool MOVES, bool PT, bool COV>
+__device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, const EnsPtDev& Pt, const EnsCovDev& Cv,
+                                         EnsCovLds* Lc, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop, int what)
 {
+    static_assert(!COV || (MOVES && !PT), "the covariance move: a member of the mixture, untempered");
     const int W = D.W, H = W / 2, n = D.n;
     const size_t e = blockIdx.x;
     const uint64_t stream = D.streams[e];
@@ -336,11 +398,17 @@ __device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, 
     if (s_prop < 0 || !(what & ENS_PT_PROPOSE)) return;
     __syncthreads();            // (the partners of the next half are the walkers just decided)
     const double* const other = x + (size_t)(1 - h_prop) * H * n;
+    if (COV) {
+        // (the entry refuses a cov weight with H < 2)
+        const bool good = ens_factor_stage(*Lc, other, H, n);
+        if (threadIdx.x == 0 && !good) Cv.fallbacks[e] += 1;
+    }
     for (int k = threadIdx.x; k < H; k += blockDim.x) {
         const int w = h_prop * H + k;
         const vmx_ens::Block b = vmx_ens::step_block(k, s_prop, h_prop, D.seed, stream);
         const vmx_ens::Block m = MOVES ? vmx_ens::move_block(k, s_prop, h_prop, D.seed, stream) : vmx_ens::Block{};
-        const int move = MOVES ? vmx_ens::move_choice(m.w[0], M.t0, M.t1) : (int)vmx_ens::MOVE_STRETCH;
+        const int move = COV ? vmx_ens::move_choice4(m.w[0], M.t0, M.t1, Cv.t2)
+                             : (MOVES ? vmx_ens::move_choice(m.w[0], M.t0, M.t1) : (int)vmx_ens::MOVE_STRETCH);
         const int64_t j1 = vmx_ens::partner(b.w[0], H);
         const double* c1 = other + (size_t)j1 * n;
         const double* s = x + (size_t)w * n;
@@ -351,6 +419,9 @@ __device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, 
             const double z = vmx_ens::stretch_z(D.a, b.w[1]);
             for (int d = 0; d < n; ++d) y[d] = vmx_ens::propose(c1[d], s[d], z);
             f = vmx_ens::log_factor(n, z);
+        } else if (COV && move == vmx_ens::MOVE_COV) {
+            vmx_ens::cov_variates(n, k, s_prop, h_prop, D.seed, stream, y);
+            vmx_ens::cov_propose(n, s, Lc->C, ens_cov_ld(n), Cv.scale, y);
         } else {
             // (the entry refuses a DE weight with H < 2 and a snooker weight with H < 3: the indices below are in range)
             const int64_t j2 = vmx_ens::partner2(b.w[1], H, j1);
@@ -376,14 +447,14 @@ __device__ __forceinline__ void ens_half(const EnsDev& D, const EnsMovesDev& M, 
 // The default path (vmx_ensemble_run, vmx_ensemble_run_many): the stretch move, the untempered decision, all three parts
 __global__ __launch_bounds__(ENS_THREADS) void k_ens_half(EnsDev D, int64_t s_dec, int h_dec, int64_t s_prop, int h_prop)
 {
-    ens_half<false, false>(D, EnsMovesDev{}, EnsPtDev{}, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
+    ens_half<false, false, false>(D, EnsMovesDev{}, EnsPtDev{}, EnsCovDev{}, nullptr, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
 }
 
 // The mixture of moves (vmx_ensemble_run_many_moves), the untempered decision, all three parts
 __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMovesDev M, int64_t s_dec, int h_dec, int64_t s_prop,
                                                                 int h_prop)
 {
-    ens_half<true, false>(D, M, EnsPtDev{}, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
+    ens_half<true, false, false>(D, M, EnsPtDev{}, EnsCovDev{}, nullptr, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
 }
 
 // A ladder's half-step (vmx_ensemble_run_pt, vmx_ensemble_run_pt_adapt): the parts that `what` names.  A run without moves comes
@@ -391,7 +462,31 @@ __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_moves(EnsDev D, EnsMov
 __global__ __launch_bounds__(ENS_THREADS) void k_ens_half_pt(EnsDev D, EnsMovesDev M, EnsPtDev Pt, int64_t s_dec, int h_dec,
                                                              int64_t s_prop, int h_prop, int what)
 {
-    ens_half<true, true>(D, M, Pt, s_dec, h_dec, s_prop, h_prop, what);
+    ens_half<true, true, false>(D, M, Pt, EnsCovDev{}, nullptr, s_dec, h_dec, s_prop, h_prop, what);
+}
+
+// The mixture with the covariance move (vmx_ensemble_run_many_cov), the untempered decision, all three parts
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_half_cov(EnsDev D, EnsMovesDev M, EnsCovDev Cv, int64_t s_dec, int h_dec,
+                                                              int64_t s_prop, int h_prop)
+{
+    __shared__ EnsCovLds L;
+    ens_half<true, false, true>(D, M, EnsPtDev{}, Cv, &L, s_dec, h_dec, s_prop, h_prop, ENS_PT_DECIDE | ENS_PT_RECORD | ENS_PT_PROPOSE);
+}
+
+// The factor stage alone (vmx_ensemble_cov_factor): work-group e factors the half x[e][H][n] and writes mean[e][n], the factor
+// [e][n][n] with its strict upper triangle 0, and flag[e] - 1 the Cholesky factor, 0 the diagonal fallback
+__global__ __launch_bounds__(ENS_THREADS) void k_ens_cov_factor(const double* x, int H, int n, double* mean, double* factor, int32_t* flag)
+{
+    __shared__ EnsCovLds L;
+    const size_t e = blockIdx.x;
+    const bool good = ens_factor_stage(L, x + e * H * n, H, n);
+    const int ld = ens_cov_ld(n);
+    for (int a = threadIdx.x; a < n; a += blockDim.x) mean[e * n + a] = L.mean[a];
+    for (int q = threadIdx.x; q < n * n; q += blockDim.x) {
+        const int a = q / n, b = q % n;
+        factor[e * n * n + q] = b <= a ? L.C[a * ld + b] : 0.0;
+    }
+    if (threadIdx.x == 0) flag[e] = good ? 1 : 0;
 }
 
 // The swap sweep after global step s: one work-group per ladder (nothing crosses ladders, so __syncthreads() between the T - 1
@@ -2292,6 +2387,7 @@ int vmx_struct_size(int32_t which)
         case 23: return (int)sizeof(vmx_ensemble_moves);           // (22 stays vacant: see vegamx.h)
         case 24: return (int)sizeof(vmx_ensemble_adapt);
         case 25: return (int)sizeof(vmx_ensemble_slice);
+        case 27: return (int)sizeof(vmx_ensemble_cov);             // (26 stays vacant: see vegamx.h)
         default: return -1;
     }
 }
@@ -5240,7 +5336,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
                         vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves,
-                        const EnsPtRun* pt = nullptr);
+                        const EnsPtRun* pt = nullptr, const vmx_ensemble_cov* cov = nullptr, int64_t* fallbacks = nullptr);
 
 // One ensemble is the set of one, on the stream of its spec
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
@@ -5272,6 +5368,55 @@ int vmx_ensemble_run_many_moves(vmx_engine* e, const vmx_ensemble_spec* spec, in
                             chain_lnL, opt, stats, per_ensemble, nullptr);
     return ensemble_run("vmx_ensemble_run_many_moves", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin,
                         chain, chain_lnL, opt, stats, per_ensemble, moves);
+}
+
+// The same run with the covariance move as the mixture's fourth member (k_ens_half_cov); without it, vmx_ensemble_run_many_moves
+int vmx_ensemble_run_many_cov(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
+                              const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
+                              int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
+                              vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves,
+                              const vmx_ensemble_cov* cov, int64_t* fallbacks)
+{
+    const std::string name("vmx_ensemble_run_many_cov");
+    if (cov) {
+        REQUIRE(std::isfinite(cov->weight) && cov->weight >= 0.0, name + ": the cov weight must be finite and not negative");
+        REQUIRE(std::isfinite(cov->scale) && cov->scale > 0.0, name + ": the cov scale must be positive and finite");
+        REQUIRE(cov->flags == 0 && cov->reserved == 0, name + ": flags and reserved must be 0");
+    }
+    if (!cov || !(cov->weight > 0.0)) {
+        const int rc = vmx_ensemble_run_many_moves(e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin, chain,
+                                                   chain_lnL, opt, stats, per_ensemble, moves);
+        if (rc == 0 && fallbacks) std::fill(fallbacks, fallbacks + E, (int64_t)0);
+        return rc;
+    }
+    REQUIRE(moves, name + ": a cov weight comes beside the weights of the other moves");
+    return ensemble_run("vmx_ensemble_run_many_cov", e, spec, E, W, streams, mock_row, x, lnL, accepted, step0, n_steps, thin,
+                        chain, chain_lnL, opt, stats, per_ensemble, moves, nullptr, cov, fallbacks);
+}
+
+// The factor stage of k_ens_half_cov alone, on halves the caller gives
+int vmx_ensemble_cov_factor(vmx_engine* e, int32_t E, int32_t H, int32_t n, const double* x, double* mean, double* factor, int32_t* flag)
+{
+    const std::string name("vmx_ensemble_cov_factor");
+    REQUIRE(e && x && mean && factor && flag, name);
+    REQUIRE(E >= 1 && H >= 2 && n >= 1 && n <= VMX_ENS_MAXN, name + ": E >= 1, H >= 2, 1 <= n <= VMX_ENS_MAXN");
+    REQUIRE((int64_t)E * H * n <= INT32_MAX, name + ": E H n is too large");
+    HIP_OK(hipSetDevice(e->device));
+    const size_t Ex = (size_t)E;
+    DevBuf<double> dx, dmean, dfactor;
+    DevBuf<int32_t> dflag;
+    if (dx.alloc(Ex * H * n, false) || dmean.alloc(Ex * n, false) || dfactor.alloc(Ex * n * n, false) || dflag.alloc(Ex, false)) return -2;
+    hipStream_t st = e->stream;
+    HIP_OK(hipMemcpyAsync(dx.p, x, Ex * H * n * sizeof(double), hipMemcpyHostToDevice, st));
+    // (the block of a run with this half)
+    const dim3 grid(E), block(std::min(ENS_THREADS, std::max(64, (H + 63) / 64 * 64)));
+    hipLaunchKernelGGL(k_ens_cov_factor, grid, block, 0, st, dx.p, H, n, dmean.p, dfactor.p, dflag.p);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(mean, dmean.p, Ex * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(factor, dfactor.p, Ex * n * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(flag, dflag.p, Ex * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
 }
 
 // G ladders of T rungs: the run of G T ensembles with the rung's beta in every decision (k_ens_half_pt) and a swap sweep between
@@ -5373,7 +5518,8 @@ static int ensemble_check(const std::string& name, vmx_engine* e, const vmx_ense
 static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec* spec, int32_t E, int32_t W, const uint64_t* streams,
                         const int32_t* mock_row, double* x, double* lnL, int64_t* accepted, int64_t step0, int32_t n_steps,
                         int32_t thin, double* chain, double* chain_lnL, const vmx_ensemble_options* opt,
-                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves, const EnsPtRun* pt)
+                        vmx_ensemble_stats* stats, int64_t* per_ensemble, const vmx_ensemble_moves* moves, const EnsPtRun* pt,
+                        const vmx_ensemble_cov* cov, int64_t* fallbacks)
 {
     const std::string name(who);
     std::vector<char> varies;
@@ -5382,12 +5528,23 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int n = spec->n, P = e->n_params;
     const int H = W / 2;
     EnsMovesDev M{};
+    EnsCovDev Cv{};
+    REQUIRE(!cov || (moves && !pt), name + ": the cov move comes with the moves' weights and without a ladder");
     if (moves) {
         const double* p = moves->weights;
+        const double pc = cov ? cov->weight : 0.0;      // (the caller has checked the cov struct; + 0.0 changes no sum)
         REQUIRE(std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]) && p[0] >= 0.0 && p[1] >= 0.0 && p[2] >= 0.0,
                 name + ": the moves' weights must be finite and not negative");
-        vmx_ens::move_thresholds(p, M.t0, M.t1);
-        REQUIRE((p[0] + p[1]) + p[2] > 0.0 && std::isfinite(M.t0) && std::isfinite(M.t1), name + ": the moves' weights must have a positive, finite sum");
+        if (cov) {
+            const double p4[4] = {p[0], p[1], p[2], pc};
+            vmx_ens::move_thresholds4(p4, M.t0, M.t1, Cv.t2);
+            REQUIRE(std::isfinite(Cv.t2), name + ": the moves' weights must have a positive, finite sum");
+            REQUIRE(H >= 2, name + ": the cov move needs two walkers in the other half, W >= 4");
+            Cv.scale = cov->scale;
+        } else {
+            vmx_ens::move_thresholds(p, M.t0, M.t1);
+        }
+        REQUIRE(((p[0] + p[1]) + p[2]) + pc > 0.0 && std::isfinite(M.t0) && std::isfinite(M.t1), name + ": the moves' weights must have a positive, finite sum");
         REQUIRE(!(p[1] > 0.0) || H >= 2, name + ": the DE move needs two partners in the other half, W >= 4");
         REQUIRE(!(p[2] > 0.0) || H >= 3, name + ": the snooker move needs three partners in the other half, W >= 6");
         REQUIRE(std::isfinite(moves->gamma0) && moves->gamma0 > 0.0, name + ": gamma0 must be positive and finite");
@@ -5417,6 +5574,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int64_t sweep0 = ad ? step0 / pt->swap_every : 0;
     const size_t n_hist = ad && pt->beta_hist ? (size_t)((step0 + n_steps) / pt->swap_every - sweep0) * n_beta : 0;
     if (pt && (ensure(S.beta, n_beta) || (n_swaps && ensure(S.swaps, n_swaps)))) return -2;
+    if (cov && ensure(S.cov_fallbacks, E)) return -2;
     if (ad && (ensure(S.adapt_skipped, pt->G) || (n_hist && ensure(S.beta_hist, n_hist)))) return -2;
     if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
     if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
@@ -5467,6 +5625,10 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         Ad.beta = S.beta.p; Ad.hist = n_hist ? S.beta_hist.p : nullptr; Ad.skipped = S.adapt_skipped.p;
         Ad.lag = ad->lag; Ad.tau = ad->time; Ad.sweep0 = sweep0; Ad.swap_every = pt->swap_every; Ad.G = pt->G;
     }
+    if (cov) {
+        HIP_OK(hipMemsetAsync(S.cov_fallbacks.p, 0, (size_t)E * sizeof(int64_t), st));
+        Cv.fallbacks = S.cov_fallbacks.p;
+    }
     const dim3 grid_swap(pt ? pt->G : 1), block_swap(std::min(ENS_THREADS, std::max(64, (W + 63) / 64 * 64)));
     // one half-step with the wrapper that pt / moves choose.  A ladder's, with a sweep due after step s_dec: the swaps come between
     // the decisions and the row and proposals
@@ -5474,6 +5636,8 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
         auto half_pt = [&](int what) { hipLaunchKernelGGL(k_ens_half_pt, grid, block, 0, st, D, M, Pt, s_dec, h_dec, s_prop, h_prop, what); };
         if (!pt && !moves) {
             hipLaunchKernelGGL(k_ens_half, grid, block, 0, st, D, s_dec, h_dec, s_prop, h_prop);
+        } else if (cov) {
+            hipLaunchKernelGGL(k_ens_half_cov, grid, block, 0, st, D, M, Cv, s_dec, h_dec, s_prop, h_prop);
         } else if (!pt) {
             hipLaunchKernelGGL(k_ens_half_moves, grid, block, 0, st, D, M, s_dec, h_dec, s_prop, h_prop);
         } else if (s_dec >= 0 && h_dec == 1 && pt->T > 1 && vmx_ens::swap_due(s_dec, pt->swap_every)) {
@@ -5514,6 +5678,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     } else if (ad && pt->adapt_skipped) {
         std::fill(pt->adapt_skipped, pt->adapt_skipped + pt->G, (int64_t)0);
     }
+    if (cov && fallbacks) HIP_OK(hipMemcpyAsync(fallbacks, S.cov_fallbacks.p, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(x, S.x.p, EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(lnL, S.lnl.p, EW * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));

@@ -638,8 +638,7 @@ VMX_HD inline bool slice_ok(int64_t H, double mu0, int32_t tune_steps, int32_t m
 }
 
 // the half-step q of a call that starts at global step step0: its step and half
-VMX_HD inline int64_t slice_step(int64_t step0, int64_t q) { return step0 + q / 2; }
-VMX_HD inline int slice_half(int64_t q) { return (int)(q % 2); }
+VMX_HD inline int64_t slice_step(int64_t step0, int64_t q) { return step0 + q / 2; }VMX_HD inline int slice_half(int64_t q) { return (int)(q % 2); }
 
 // the packing of a round: offset[a] of the a-th running ensemble is the sum of the counts before it in list order; the total
 VMX_HD inline int32_t slice_offsets(const int32_t* count, int A, int32_t* offset)
@@ -656,6 +655,207 @@ VMX_HD inline int slice_compact(int32_t* active, int A, const int32_t* count_of)
     for (int a = 0; a < A; ++a)
         if (count_of[active[a]] > 0) active[B++] = active[a];
     return B;
+}
+
+}  // namespace vmx_ens
+
+// ---- the covariance move (vmx_ensemble_run_many_cov: k_ens_half_cov), the sixth part
+//
+// A Metropolis step whose increment has the covariance of the complementary half: emcee's WalkMove taken over the whole other
+// half, with the Roberts-Gelman-Gilks scale.  A red-blue move like the others: the factor below depends on the other half alone,
+// which is fixed for the whole half-step, so the move is reversible by the same argument.  Only + - x / sqrt, each rounded on its
+// own.  (tests/helpers/ensemble_cov_driver.cpp compiles this part for tests/test_ensemble_cov_host.py.)
+//
+//   the factor       for the half-step that proposes half h the other half c[H][n] is fixed: mean_a = (sum_i c_ia) / H and
+//                    cov_ab = (sum_i (c_ia - mean_a)(c_ib - mean_b)) / (H - 1), both summed in walker order with one accumulator
+//                    from 0.0 (half_mean_entry, half_cov_entry: the order of vmx_ns::mean_entry and cov_entry).  C is the lower
+//                    Cholesky factor in the operation order of vmx_ns::cholesky - column by column, the inner sums in k order
+//                    (chol_pivot, chol_entry; in place: the lower triangle of cov goes in, C comes out).  A pivot that is not
+//                    positive: C = diag(sqrt(cov_aa)), 0 where cov_aa is not positive (vmx_ns::whiten's fallback), and the
+//                    half-step counts as a fallback.  Every entry is a function of its inputs alone: a work-group that gives
+//                    every entry to one thread computes the factor of half_factor bit for bit.
+//   the variate      one 64-bit word w gives z = ((double)(a0 + a1 + a2 + a3) - 131070) kappa, a0 .. a3 the four 16-bit fields
+//                    of w, kappa = sqrt(3 / 4294967295): symmetric about 0, of unit variance, |z| <= 2 sqrt(3), exact in integers
+//                    up to the last product.  It is not normal (the sum of four uniforms): like the triangular DE jitter it is
+//                    symmetric and independent of the state, which is all reversibility needs.
+//   the words        column b of walker-in-half k at step s, half h takes word b % 4 of the block with counter
+//                    (k, s, h, 2 + b / 4); blocks 0 and 1 stay what they are (the move is refused with tempering and with
+//                    slice sampling, whose blocks carry the last words 2, 3 and 6).
+//   the proposal     y_a = s_a + gamma_c (sum_{b <= a} C_ab z_b): the sum in b order from 0.0, the product by gamma_c a rounding
+//                    of its own; factor = 0.  gamma_c comes from the host as a double (default 2.38 / sqrt(n)).
+//   the mixture      weights (p_stretch, p_de, p_snooker, p_cov): t0 and t1 as above but over the sum of all four,
+//                    t2 = (p0 + p1 + p2) / sum; the move is cov when u(B.w0) >= t2, else move_choice.  With p_cov = 0 the sum,
+//                    t0 and t1 are those of three weights.  A pure cov run draws from the same words.
+//   box, decision    unchanged.
+namespace vmx_ens {
+
+constexpr int MOVE_COV = 3;
+
+// the thresholds of the weights (p_stretch, p_de, p_snooker, p_cov)
+VMX_HD inline void move_thresholds4(const double* p, double& t0, double& t1, double& t2)
+{
+    VMX_NO_CONTRACT
+    const double p01 = p[0] + p[1];
+    const double p012 = p01 + p[2];
+    const double sum = p012 + p[3];
+    t0 = p[0] / sum;
+    t1 = p01 / sum;
+    t2 = p012 / sum;
+}
+
+VMX_HD inline int move_choice4(uint64_t w0, double t0, double t1, double t2)
+{
+    return u01(w0) >= t2 ? MOVE_COV : move_choice(w0, t0, t1);
+}
+
+// what the run takes beside what the moves entry takes
+VMX_HD inline bool cov_ok(double weight, double scale, uint32_t flags, uint32_t reserved)
+{
+    return is_finite(weight) && weight >= 0.0 && is_finite(scale) && scale > 0.0 && flags == 0 && reserved == 0;
+}
+
+// the mean of column a over the half c[H][n].  (The rows are read HALF_BATCH at a time ahead of the sum, so that a device thread
+// has that many loads in flight instead of one per addition; the additions are the same ones in the same order.)
+constexpr int HALF_BATCH = 8;
+VMX_HD inline double half_mean_entry(int a, const double* c, int64_t H, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    int64_t i = 0;
+    for (; i + HALF_BATCH <= H; i += HALF_BATCH) {
+        double v[HALF_BATCH];
+        for (int u = 0; u < HALF_BATCH; ++u) v[u] = c[(size_t)(i + u) * n + a];
+        for (int u = 0; u < HALF_BATCH; ++u) acc = acc + v[u];
+    }
+    for (; i < H; ++i) acc = acc + c[(size_t)i * n + a];
+    return acc / (double)H;
+}
+
+VMX_HD inline double half_cov_entry(int a, int b, const double* c, const double* mean, int64_t H, int n)
+{
+    VMX_NO_CONTRACT
+    double acc = 0.0;
+    const double ma = mean[a], mb = mean[b];
+    int64_t i = 0;
+    for (; i + HALF_BATCH <= H; i += HALF_BATCH) {
+        double va[HALF_BATCH], vb[HALF_BATCH];
+        for (int u = 0; u < HALF_BATCH; ++u) { va[u] = c[(size_t)(i + u) * n + a]; vb[u] = c[(size_t)(i + u) * n + b]; }
+        for (int u = 0; u < HALF_BATCH; ++u) {
+            const double da = va[u] - ma;
+            const double db = vb[u] - mb;
+            const double p = da * db;
+            acc = acc + p;
+        }
+    }
+    for (; i < H; ++i) {
+        const double da = c[(size_t)i * n + a] - ma;
+        const double db = c[(size_t)i * n + b] - mb;
+        const double p = da * db;
+        acc = acc + p;
+    }
+    return acc / (double)(H - 1);
+}
+
+// entry q = a (a + 1) / 2 + b of the lower triangle, b <= a
+VMX_HD inline void tri_entry(int q, int& a, int& b)
+{
+    a = 0;
+    while ((a + 1) * (a + 2) / 2 <= q) ++a;
+    b = q - a * (a + 1) / 2;
+}
+
+// The factor in place, C[n][ld] (ld >= n the row stride): columns k < j hold the factor, column j the covariance.
+// What is under the root of pivot j; the pivot is its sqrt when it is positive
+VMX_HD inline double chol_pivot(int j, const double* C, int ld)
+{
+    VMX_NO_CONTRACT
+    double s = C[j * ld + j];
+    for (int k = 0; k < j; ++k) {
+        const double p = C[j * ld + k] * C[j * ld + k];
+        s = s - p;
+    }
+    return s;
+}
+
+// entry (i, j), i > j, of the factor, given pivot j
+VMX_HD inline double chol_entry(int i, int j, const double* C, int ld, double piv)
+{
+    VMX_NO_CONTRACT
+    double t = C[i * ld + j];
+    for (int k = 0; k < j; ++k) {
+        const double p = C[i * ld + k] * C[j * ld + k];
+        t = t - p;
+    }
+    return t / piv;
+}
+
+VMX_HD inline double fallback_entry(double cov_aa) { return cov_aa > 0.0 ? sqrt(cov_aa) : 0.0; }
+
+// The factor of the half c[H][n] (H >= 2), one entry after the other: mean[n], C[n][ld] (the strict upper triangle 0), diag[n] the
+// covariance's diagonal.  true: the Cholesky factor; false: the diagonal fallback
+VMX_HD inline bool half_factor(int n, int64_t H, const double* c, double* mean, double* C, int ld, double* diag)
+{
+    for (int a = 0; a < n; ++a) mean[a] = half_mean_entry(a, c, H, n);
+    for (int a = 0; a < n; ++a) {
+        for (int b = 0; b <= a; ++b) C[a * ld + b] = half_cov_entry(a, b, c, mean, H, n);
+        for (int b = a + 1; b < n; ++b) C[a * ld + b] = 0.0;
+        diag[a] = C[a * ld + a];
+    }
+    bool good = true;
+    for (int j = 0; j < n && good; ++j) {
+        const double s = chol_pivot(j, C, ld);
+        if (!(s > 0.0)) { good = false; break; }
+        const double piv = sqrt(s);
+        C[j * ld + j] = piv;
+        for (int i = j + 1; i < n; ++i) C[i * ld + j] = chol_entry(i, j, C, ld, piv);
+    }
+    if (good) return true;
+    for (int a = 0; a < n; ++a)
+        for (int b = 0; b <= a; ++b) C[a * ld + b] = a == b ? fallback_entry(diag[a]) : 0.0;
+    return false;
+}
+
+VMX_HD inline double cov_z(uint64_t w)
+{
+    VMX_NO_CONTRACT
+    const double kappa = sqrt(3.0 / 4294967295.0);
+    const uint64_t a = (w & 0xFFFFull) + ((w >> 16) & 0xFFFFull) + ((w >> 32) & 0xFFFFull) + (w >> 48);
+    const double d = (double)a - 131070.0;
+    return d * kappa;
+}
+
+// block j of the variates of walker-in-half i at global step s, half h: the columns 4 j .. 4 j + 3
+VMX_HD inline Block cov_block(int64_t i, int64_t s, int h, int j, uint64_t seed, uint64_t stream)
+{
+    return philox4x64_10((uint64_t)i, (uint64_t)s, (uint64_t)h, 2 + (uint64_t)j, seed, stream);
+}
+
+// the variates z[n] of walker-in-half i
+VMX_HD inline void cov_variates(int n, int64_t i, int64_t s, int h, uint64_t seed, uint64_t stream, double* z)
+{
+    for (int b = 0; b < n; b += 4) {
+        const Block blk = cov_block(i, s, h, b / 4, seed, stream);
+        z[b] = cov_z(blk.w[0]);
+        if (b + 1 < n) z[b + 1] = cov_z(blk.w[1]);
+        if (b + 2 < n) z[b + 2] = cov_z(blk.w[2]);
+        if (b + 3 < n) z[b + 3] = cov_z(blk.w[3]);
+    }
+}
+
+// The proposal of the walker at s[n], in place: y[n] holds the variates and takes the proposal (from the last column down: y_a
+// reads the variates b <= a alone).  y must not overlap s.
+VMX_HD inline void cov_propose(int n, const double* s, const double* C, int ld, double gamma_c, double* y)
+{
+    VMX_NO_CONTRACT
+    for (int a = n - 1; a >= 0; --a) {
+        double acc = 0.0;
+        for (int b = 0; b <= a; ++b) {
+            const double p = C[a * ld + b] * y[b];
+            acc = acc + p;
+        }
+        const double t = gamma_c * acc;
+        y[a] = s[a] + t;
+    }
 }
 
 }  // namespace vmx_ens

@@ -140,6 +140,10 @@ class EnsembleMoves(C.Structure):
                 ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
 
+class EnsembleCov(C.Structure):
+    _fields_ = [('weight', C.c_double), ('scale', C.c_double), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
+
+
 class EnsembleAdapt(C.Structure):
     _fields_ = [('lag', C.c_double), ('time', C.c_double), ('adapt_until', C.c_int64), ('flags', C.c_uint32), ('reserved', C.c_uint32)]
 
@@ -283,8 +287,16 @@ def _ensemble_moves(moves):
     """The mapping ``moves`` of the ensemble entries as the library reads it (None: none)."""
     if moves is None:
         return None
-    return EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'])), float(moves['gamma0']), float(moves['sigma']),
+    return EnsembleMoves((C.c_double * 3)(*(float(w) for w in moves['weights'][:3])), float(moves['gamma0']), float(moves['sigma']),
                          float(moves['gamma_s']), int(moves.get('flags', 0)), 0)
+
+
+def _ensemble_cov(moves):
+    """The covariance move of the mapping ``moves`` - a fourth weight and ``cov_scale`` - as vmx_ensemble_run_many_cov reads it
+    (None: the mapping has three weights)."""
+    if moves is None or len(moves['weights']) < 4:
+        return None
+    return EnsembleCov(float(moves['weights'][3]), float(moves['cov_scale']), int(moves.get('cov_flags', 0)), 0)
 
 
 def _stats_dict(stats):
@@ -352,6 +364,8 @@ def load_library():
                                           dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, dptr, dptr,
                                           C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64)]
     lib.vmx_ensemble_run_many_moves.argtypes = lib.vmx_ensemble_run_many.argtypes + [C.POINTER(EnsembleMoves)]
+    lib.vmx_ensemble_run_many_cov.argtypes = lib.vmx_ensemble_run_many_moves.argtypes + [C.POINTER(EnsembleCov), C.POINTER(C.c_int64)]
+    lib.vmx_ensemble_cov_factor.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, dptr, dptr, dptr, iptr]
     lib.vmx_ensemble_run_pt.argtypes = [C.c_void_p, C.POINTER(EnsembleSpec), C.c_int32, C.c_int32, C.c_int32, dptr, C.POINTER(C.c_uint64),
                                         iptr, dptr, dptr, C.POINTER(C.c_int64), C.c_int64, C.c_int32, C.c_int32, C.c_int32, dptr, dptr,
                                         C.POINTER(EnsembleOptions), C.POINTER(EnsembleStats), C.POINTER(C.c_int64),
@@ -446,7 +460,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -1236,6 +1250,8 @@ class Engine:
             raise ValueError(f"betas [{'G, T' if own else 'T'}], streams [G, T], mock_rows [G]")
         per = np.zeros((G, T, 3), dtype=np.int64)
         swaps = np.zeros((G, max(T - 1, 0), 2), dtype=np.int64)
+        if _ensemble_cov(moves) is not None:
+            raise ValueError("moves: 'cov' does not run on a temperature ladder")
         mv = _ensemble_moves(moves)
         i64 = C.POINTER(C.c_int64)
         head = (self._h, C.byref(spec), G, T, W, _dp(betas), streams.ctypes.data_as(C.POINTER(C.c_uint64)),
@@ -1277,7 +1293,9 @@ class Engine:
         ``per_ensemble`` int64 [E, 3]: accepted, rejected outside the box, rejected for a failed model.  ``moves`` (None:
         vmx_ensemble_run_many, the stretch move): a mapping with ``weights`` (stretch, DE, snooker), ``gamma0``, ``sigma``,
         ``gamma_s`` and optionally ``flags`` - the mixture of vmx_ensemble_run_many_moves
-        (:func:`vega_amd.ensemble.resolve_moves` makes one)."""
+        (:func:`vega_amd.ensemble.resolve_moves` makes one).  With a fourth weight - the covariance move - and ``cov_scale`` the run
+        is vmx_ensemble_run_many_cov, and the statistics carry ``cov_fallbacks`` int64 [E]: the half-steps whose factor fell back
+        to the diagonal."""
         spec, args, chain, chain_lnl, stats, _held = self._ensemble_arrays(
             3, cols, lo, hi, theta_fixed, x, lnl, accepted, step0, n_steps, thin, keep_chain, a=a, log_norm=log_norm, seed=seed,
             stream=0, const_hint=const_hint, chunk=chunk, lanes=lanes)
@@ -1294,9 +1312,25 @@ class Engine:
         if moves is None:
             self._check(self.lib.vmx_ensemble_run_many(*head))
         else:
-            mv = _ensemble_moves(moves)
-            self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
+            mv, cv = _ensemble_moves(moves), _ensemble_cov(moves)
+            if cv is None:
+                self._check(self.lib.vmx_ensemble_run_many_moves(*head, C.byref(mv)))
+            else:
+                fallbacks = np.zeros(E, dtype=np.int64)
+                self._check(self.lib.vmx_ensemble_run_many_cov(*head, C.byref(mv), C.byref(cv), fallbacks.ctypes.data_as(C.POINTER(C.c_int64))))
+                return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, cov_fallbacks=fallbacks)
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
+
+    def ensemble_cov_factor(self, x):
+        """The factor stage of the covariance move alone (include/vegamx.h: vmx_ensemble_cov_factor): the halves ``x`` [E, H, n] give
+        (mean [E, n], factor [E, n, n] lower, flag int32 [E]: 1 the Cholesky factor, 0 the diagonal fallback)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 3:
+            raise ValueError('x [E, H, n]')
+        E, H, n = x.shape
+        mean, factor, flag = np.zeros((E, n)), np.zeros((E, n, n)), np.zeros(E, dtype=np.int32)
+        self._check(self.lib.vmx_ensemble_cov_factor(self._h, E, H, n, _dp(x), _dp(mean), _dp(factor), _ip(flag)))
+        return mean, factor, flag
 
     def ensemble_run_slice(self, cols, lo, hi, theta_fixed, x, lnl, accepted, streams, mu, step0, n_steps, mock_rows=None, thin=1,
                            log_norm=0.0, seed=0, const_hint=-1, chunk=0, lanes=0, keep_chain=True, mu0=1.0, tune_steps=100,

@@ -1,6 +1,6 @@
 """Posterior sampling: the affine-invariant ensemble sampler (Goodman & Weare 2010, emcee's stretch move with
-randomize_split=False; on request the differential-evolution and snooker moves and mixtures of the three), run where the walkers
-are.
+randomize_split=False; on request the differential-evolution, snooker and covariance moves and mixtures of them), run where the
+walkers are.
 
 The reference samples through PolyChord / pocoMC (bin/run_vega_mpi.py: ``[control] run_sampler = True``), which call
 ``log_lik`` one point at a time.  Here W walkers advance half an ensemble at a time: the ``device`` driver runs the whole walker
@@ -132,6 +132,81 @@ def move_choice(w0, t0, t1):
     return np.where(u < t0, MOVE_STRETCH, np.where(u < t1, MOVE_DE, MOVE_SNOOKER))
 
 
+# ---- the covariance move (vmx_ensemble.h, the sixth part)
+MOVE_COV = 3
+COV_MOVE_NAMES = MOVE_NAMES + ('cov',)
+_COV_KAPPA = float(np.sqrt(np.float64(3.0) / np.float64(4294967295.0)))
+
+
+def move_thresholds4(p):
+    """(t0, t1, t2) of the weights (p_stretch, p_de, p_snooker, p_cov)."""
+    p01 = float(p[0]) + float(p[1])
+    p012 = p01 + float(p[2])
+    total = p012 + float(p[3])
+    return float(p[0]) / total, p01 / total, p012 / total
+
+
+def move_choice4(w0, t0, t1, t2):
+    return np.where(u01(w0) >= t2, MOVE_COV, move_choice(w0, t0, t1))
+
+
+def has_cov(moves):
+    """The mixture ``moves`` (:func:`resolve_moves`) has the covariance move as its fourth member."""
+    return moves is not None and len(moves['weights']) == 4
+
+
+def choose_moves(w0, moves):
+    """The move of every word ``w0`` (word 0 of block B) under the mixture ``moves``, of three weights or four."""
+    if has_cov(moves):
+        return move_choice4(w0, *move_thresholds4(moves['weights']))
+    return move_choice(w0, *move_thresholds(moves['weights']))
+
+
+def cov_z(words):
+    """The variate of every 64-bit word: the centred sum of its four 16-bit fields times kappa = sqrt(3 / 4294967295) - symmetric,
+    of unit variance, |z| <= 2 sqrt(3); not normal."""
+    w = np.asarray(words, dtype=np.uint64)
+    m = np.uint64(0xFFFF)
+    total = (w & m) + ((w >> np.uint64(16)) & m) + ((w >> np.uint64(32)) & m) + (w >> np.uint64(48))
+    d = total.astype(np.float64) - 131070.0
+    return d * _COV_KAPPA
+
+
+def cov_variates(walkers, n, step, h, seed, stream=0):
+    """The variates z [len(walkers), n] of the walkers-in-half ``walkers`` at ``step``, half ``h``: column b from word b % 4 of
+    the block with counter (k, step, h, 2 + b // 4)."""
+    walkers = np.asarray(walkers, dtype=np.uint64)
+    nb = (n + 3) // 4
+    ctr = np.zeros((walkers.size, nb, 4), dtype=np.uint64)
+    ctr[:, :, 0] = walkers[:, None]
+    ctr[:, :, 1] = np.uint64(step)
+    ctr[:, :, 2] = np.uint64(h)
+    ctr[:, :, 3] = np.uint64(2) + np.arange(nb, dtype=np.uint64)[None, :]
+    return cov_z(philox4x64_10(ctr, (int(seed), int(stream))).reshape(walkers.size, 4 * nb)[:, :n])
+
+
+def half_factor(other):
+    """The factor of the half ``other`` [H, n] (H >= 2): (mean [n], C [n, n] lower, good) - the mean and covariance in walker
+    order, the Cholesky factor in the order of vmx_ns::cholesky, or with a pivot that is not positive (good False) the diagonal
+    of standard deviations: :func:`vega_amd.nested.mean_cov` and :func:`vega_amd.nested.whiten`, whose order is the header's."""
+    from .nested import mean_cov, whiten
+    mean, cov = mean_cov(np.asarray(other, dtype=np.float64))
+    C, good = whiten(cov)
+    return mean, C, bool(good)
+
+
+def cov_propose(s, C, gamma_c, z):
+    """Rows of the covariance proposal: s the walkers' own positions [k, n], z their variates [k, n]: y_a = s_a + gamma_c (sum over
+    b <= a of C_ab z_b), the sum in b order from 0.0."""
+    y = np.empty_like(s)
+    for a in range(s.shape[1]):
+        acc = np.zeros(s.shape[0])
+        for b in range(a + 1):
+            acc = acc + C[a, b] * z[:, b]
+        y[:, a] = s[:, a] + gamma_c * acc
+    return y
+
+
 def partner2(x1, half, j1):
     """The second partner, distinct from ``j1`` (half >= 2)."""
     j = partner(x1, half - 1).astype(np.int64)
@@ -187,37 +262,50 @@ def snooker_propose(s, z, z1, z2, gamma_s):
     return y, factor, some & np.isfinite(factor)
 
 
-def resolve_moves(moves, n, walkers, gamma0=None, sigma=None, gamma_s=None):
+def resolve_moves(moves, n, walkers, gamma0=None, sigma=None, gamma_s=None, cov_scale=None):
     """The mixture a sampler of ``walkers`` walkers over ``n`` parameters runs with: None for ``moves`` None (the stretch move as
     ever), else dict(weights (stretch, DE, snooker), gamma0, sigma, gamma_s) - what vmx_ensemble_run_many_moves takes.
     ``moves``: ``'stretch'``, ``'de'`` or ``'snooker'``, a list of (name, weight), or such a dict.  Defaults: gamma0 =
     2.38 / sqrt(2 n), sigma = 1e-5, gamma_s = 1.7.  Refused as the library refuses them: an unknown name, a negative or
-    non-finite weight, a zero sum, DE with fewer than 4 walkers, the snooker with fewer than 6, a scale that is not positive."""
+    non-finite weight, a zero sum, DE with fewer than 4 walkers, the snooker with fewer than 6, a scale that is not positive.
+    ``'cov'`` - the covariance move (vmx_ensemble.h, the sixth part), alone or in the list; a dict may carry a fourth weight and
+    ``cov_scale``: with a positive cov weight the result has four weights (stretch, DE, snooker, cov) and ``cov_scale`` (default
+    2.38 / sqrt(n)) - what vmx_ensemble_run_many_cov takes; without one it is the dict of three weights.  Refused beside the above:
+    ``cov_scale`` without a cov weight, cov with fewer than 4 walkers, a ``cov_scale`` that is not positive and finite."""
     if moves is None:
         if gamma0 is not None or sigma is not None or gamma_s is not None:
             raise ValueError('gamma0, sigma and gamma_s belong to moves: name the moves')
+        if cov_scale is not None:
+            raise ValueError("cov_scale belongs to the 'cov' move: name the moves")
         return None
     if isinstance(moves, dict):
         weights = [float(w) for w in moves['weights']]
         gamma0 = moves.get('gamma0') if gamma0 is None else gamma0
         sigma = moves.get('sigma') if sigma is None else sigma
         gamma_s = moves.get('gamma_s') if gamma_s is None else gamma_s
-        if len(weights) != 3:
-            raise ValueError('moves: three weights (stretch, de, snooker)')
+        cov_scale = moves.get('cov_scale') if cov_scale is None else cov_scale
+        if len(weights) not in (3, 4):
+            raise ValueError('moves: three weights (stretch, de, snooker), or four with cov')
+        weights += [0.0] * (4 - len(weights))
     else:
         pairs = [(moves, 1.0)] if isinstance(moves, str) else list(moves)
-        weights = [0.0, 0.0, 0.0]
+        weights = [0.0, 0.0, 0.0, 0.0]
         for pair in pairs:
             name, w = (pair, 1.0) if isinstance(pair, str) else pair
-            if name not in MOVE_NAMES:
-                raise ValueError(f"moves: unknown move {name!r}; one of 'stretch', 'de', 'snooker'")
-            weights[MOVE_NAMES.index(name)] += float(w)
+            if name not in COV_MOVE_NAMES:
+                raise ValueError(f"moves: unknown move {name!r}; one of 'stretch', 'de', 'snooker', 'cov'")
+            weights[COV_MOVE_NAMES.index(name)] += float(w)
             if not float(w) >= 0.0:
                 raise ValueError('moves: a weight must be finite and not negative')
     if not all(math.isfinite(w) and w >= 0.0 for w in weights):
         raise ValueError('moves: a weight must be finite and not negative')
-    if not 0.0 < (weights[0] + weights[1]) + weights[2] < math.inf:
+    if not 0.0 < ((weights[0] + weights[1]) + weights[2]) + weights[3] < math.inf:
         raise ValueError('moves: the weights must have a positive sum')
+    cov_weight = weights.pop()
+    if not cov_weight > 0.0 and cov_scale is not None:
+        raise ValueError("cov_scale belongs to the 'cov' move, which the moves do not name")
+    if cov_weight > 0.0 and walkers < 4:
+        raise ValueError("moves: 'cov' needs two walkers in the other half, at least 4 walkers")
     if weights[1] > 0.0 and walkers < 4:
         raise ValueError("moves: 'de' needs two partners in the other half, at least 4 walkers")
     if weights[2] > 0.0 and walkers < 6:
@@ -228,7 +316,23 @@ def resolve_moves(moves, n, walkers, gamma0=None, sigma=None, gamma_s=None):
         raise ValueError('moves: gamma0 and gamma_s must be positive and finite')
     if not (math.isfinite(out['sigma']) and out['sigma'] >= 0.0):
         raise ValueError('moves: sigma must be finite and not negative')
+    if cov_weight > 0.0:
+        out['weights'] = out['weights'] + (cov_weight,)
+        out['cov_scale'] = 2.38 / math.sqrt(float(n)) if cov_scale is None else float(cov_scale)
+        if not (math.isfinite(out['cov_scale']) and out['cov_scale'] > 0.0):
+            raise ValueError('moves: cov_scale must be positive and finite')
     return out
+
+
+def names_cov(moves):
+    """``moves`` as a caller writes it names the covariance move with a positive weight."""
+    if isinstance(moves, str):
+        return moves == 'cov'
+    if moves is None:
+        return False
+    if isinstance(moves, dict):
+        return len(moves['weights']) == 4 and float(moves['weights'][3]) > 0.0
+    return any(pair == 'cov' if isinstance(pair, str) else (pair[0] == 'cov' and float(pair[1]) > 0.0) for pair in moves)
 
 
 def _names_slice(moves):
@@ -265,7 +369,7 @@ def resolve_slice(moves, walkers, mu=None, tune_steps=None, gamma0=None, sigma=N
 
 def half_step_moves(H, h, step, seed, stream, moves):
     """The move of every walker of half ``h`` at ``step``: [H] of MOVE_STRETCH / MOVE_DE / MOVE_SNOOKER."""
-    return move_choice(move_blocks(H, step, h, seed, stream)[:, 0], *move_thresholds(moves['weights']))
+    return choose_moves(move_blocks(H, step, h, seed, stream)[:, 0], moves)
 
 
 def steps_moves(H, step0, n_steps, seed, stream, moves):
@@ -278,7 +382,7 @@ def steps_moves(H, step0, n_steps, seed, stream, moves):
         for h in (0, 1):
             counter = ((step0 + i) << 64) | (h << 128) | (1 << 192)
             words[i, h] = np.random.Philox(key=key, counter=counter - 1).random_raw(4 * H)[0::4]
-    return move_choice(words, *move_thresholds(moves['weights'])).reshape(n_steps, 2 * H)
+    return choose_moves(words, moves).reshape(n_steps, 2 * H)
 
 
 def half_step_blocks(H, step, h, seed, streams, last=0):
@@ -293,10 +397,11 @@ def half_step_blocks(H, step, h, seed, streams, last=0):
     return philox4x64_10(ctr, (int(seed), streams[:, None]))
 
 
-def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None, blocks=None):
+def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None, blocks=None, factor_of_half=None):
     """Proposals of half ``h`` at ``step`` for the walkers ``x`` [W, n]: (y [W/2, n], inside [W/2], factor [W/2], blocks).
     ``moves`` (:func:`resolve_moves`; None: the stretch move): every walker's move is drawn from the mixture.  ``blocks``
-    (None: drawn here): the half's (:func:`step_blocks`, :func:`move_blocks` or None) when the caller has them already."""
+    (None: drawn here): the half's (:func:`step_blocks`, :func:`move_blocks` or None) when the caller has them already.
+    ``factor_of_half`` (None: computed here when the mixture has the covariance move): :func:`half_factor` of the other half."""
     W, n = x.shape
     H = W // 2
     b = step_blocks(H, step, h, seed, stream) if blocks is None else blocks[0]
@@ -311,8 +416,12 @@ def half_step_proposals(x, h, step, a, seed, stream, lo, hi, moves=None, blocks=
         some = True
     else:
         m = move_blocks(H, step, h, seed, stream) if blocks is None else blocks[1]
-        move = move_choice(m[:, 0], *move_thresholds(moves['weights']))
+        move = choose_moves(m[:, 0], moves)
         y, factor, some = np.empty((H, n)), np.zeros(H), np.ones(H, dtype=bool)
+        k = np.flatnonzero(move == MOVE_COV)
+        if k.size:
+            _, C, _ = half_factor(other) if factor_of_half is None else factor_of_half
+            y[k] = cov_propose(s[k], C, moves['cov_scale'], cov_variates(k, n, step, h, seed, stream))
         k = np.flatnonzero(move == MOVE_STRETCH)
         if k.size:
             z = stretch_z(a, b[k, 1])
@@ -562,19 +671,27 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
     the box is replaced by the walker's own position).  Returns (chain [E, rows, W, n], chain_lnl [E, rows, W], stats,
     per_ensemble [E, 3]: accepted, rejected outside the box, rejected for a failed model).  ``moves`` (:func:`resolve_moves`; None:
     the stretch move): the mixture every walker's move is drawn from.  ``betas`` [E] (None: 1, the run of ever): ensemble e decides
-    at the inverse temperature ``betas[e]`` (:func:`accept_tempered`; the stored lnl stays untempered)."""
+    at the inverse temperature ``betas[e]`` (:func:`accept_tempered`; the stored lnl stays untempered).  With the covariance
+    move in the mixture the factor of every half-step is computed once per ensemble, and ``stats['cov_fallbacks']`` int64 [E]
+    counts the half-steps whose factor fell back to the diagonal."""
     E, W, n = x.shape
     H = W // 2
     rows = (step0 + n_steps) // thin - step0 // thin
     chain, chain_lnl = np.empty((E, rows, W, n)), np.empty((E, rows, W))
     per = np.zeros((E, 3), dtype=np.int64)
+    cov = has_cov(moves)
+    fallbacks = np.zeros(E, dtype=np.int64)
     for s in range(step0, step0 + n_steps):
         for h in (0, 1):
             mine = slice(h * H, (h + 1) * H)
             b_all = half_step_blocks(H, s, h, seed, streams)          # (the Philox blocks of all ensembles in one pass)
             m_all = None if moves is None else half_step_blocks(H, s, h, seed, streams, last=1)
+            factors = [half_factor(x[e, (1 - h) * H:(2 - h) * H]) if cov else None for e in range(E)]
+            if cov:
+                fallbacks += [0 if f[2] else 1 for f in factors]
             props = [half_step_proposals(x[e], h, s, a, seed, streams[e], lo, hi, moves,
-                                         blocks=(b_all[e], None if m_all is None else m_all[e])) for e in range(E)]
+                                         blocks=(b_all[e], None if m_all is None else m_all[e]), factor_of_half=factors[e])
+                     for e in range(E)]
             chi2, status = evaluate(np.concatenate([np.where(inside[:, None], y, x[e, mine])
                                                     for e, (y, inside, _, _) in enumerate(props)]), h)
             for e, (y, inside, factor, b) in enumerate(props):
@@ -594,6 +711,8 @@ def python_steps_many(x, lnl, accepted, step0, n_steps, thin, a, seed, streams, 
             chain[:, r], chain_lnl[:, r] = x, lnl
     st = dict(steps=n_steps, proposals=n_steps * W * E, accepted=int(per[:, 0].sum()), rejected_outside_box=int(per[:, 1].sum()),
               rejected_failed_model=int(per[:, 2].sum()))
+    if cov:
+        st['cov_fallbacks'] = fallbacks
     return chain, chain_lnl, st, per
 
 
@@ -1248,18 +1367,20 @@ class EngineSampler:
 class MoveCounts(Mapping):
     """``stats['moves']`` of a sampler that runs a mixture of moves: {move: {proposals, accepted}} over the steps run so far,
     computed when it is read (:meth:`StretchSampler.move_counts`) and kept until the sampler advances; ``accepted`` is None
-    with thin > 1.  ``unseen``: the accepted proposals no move could be credited with (None with thin > 1)."""
+    with thin > 1.  ``unseen``: the accepted proposals no move could be credited with (None with thin > 1).  The moves are the
+    three of ``MOVE_NAMES``, and ``cov`` when the mixture has it."""
 
     def __init__(self, sampler):
         self._sampler, self._step, self._counts, self._unseen = sampler, -1, None, None
+        self._names = COV_MOVE_NAMES if has_cov(sampler.moves) else MOVE_NAMES
 
     def _read(self):
         s = self._sampler
         if self._step != s.step:
-            total = s.move_counts().reshape(-1, 3, 2).sum(axis=0)
+            total = s.move_counts().reshape(-1, len(self._names), 2).sum(axis=0)
             known = s.thin == 1
             self._counts = {name: dict(proposals=int(total[m, 0]), accepted=int(total[m, 1]) if known else None)
-                            for m, name in enumerate(MOVE_NAMES)}
+                            for m, name in enumerate(self._names)}
             self._unseen = int(np.sum(s.accepted)) - int(total[:, 1].sum()) if known else None
             self._step = s.step
         return self._counts
@@ -1273,10 +1394,10 @@ class MoveCounts(Mapping):
         return self._read()[name]
 
     def __iter__(self):
-        return iter(MOVE_NAMES)
+        return iter(self._names)
 
     def __len__(self):
-        return len(MOVE_NAMES)
+        return len(self._names)
 
     def __repr__(self):
         return repr(self._read())
@@ -1290,7 +1411,7 @@ class StretchSampler(EngineSampler):
     _lead = ()
 
     def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves=None,
-                       gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None):
+                       gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None, cov_scale=None):
         self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
         self.W = int(walkers)
         if self.W % 2 or self.W < 2 * self.n:
@@ -1305,11 +1426,15 @@ class StretchSampler(EngineSampler):
         # ensemble slice sampling (None: not asked for): mu0 and tune_steps; it is no member of a mixture
         self.slice = resolve_slice(moves, self.W, mu, tune_steps, gamma0, sigma, gamma_s)
         if self.slice is not None:
+            if cov_scale is not None:
+                raise ValueError("cov_scale is the scale of the 'cov' move, not of 'slice'")
             self.moves, self._moves_kw = None, dict(moves='slice', mu=self.slice['mu0'], tune_steps=self.slice['tune_steps'])
             return
         # the mixture of moves (None: the stretch move alone, the run of ever) and what asked for it, for a set's members
-        self.moves = resolve_moves(moves, self.n, self.W, gamma0, sigma, gamma_s)
+        self.moves = resolve_moves(moves, self.n, self.W, gamma0, sigma, gamma_s, cov_scale)
         self._moves_kw = {} if moves is None else dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s)
+        if cov_scale is not None:
+            self._moves_kw['cov_scale'] = cov_scale
 
     def reset(self):
         self.x = self.lnl = None
@@ -1321,6 +1446,10 @@ class StretchSampler(EngineSampler):
         if self.moves is not None:
             self._start = None          # (the walkers ahead of the first step: what the first recorded row is compared with)
             self.stats['moves'] = MoveCounts(self)
+        if has_cov(self.moves):
+            # the half-steps whose factor fell back to the diagonal, per ensemble; stats['cov'] carries their sum
+            self.cov_fallbacks = np.zeros(int(np.prod(self._lead, dtype=np.int64)), dtype=np.int64)
+            self.stats['cov'] = dict(scale=self.moves['cov_scale'], factor_fallbacks=0)
         if self.slice is not None:
             lead = int(np.prod(self._lead, dtype=np.int64))
             self.mu = np.full(lead, self.slice['mu0'])
@@ -1342,7 +1471,7 @@ class StretchSampler(EngineSampler):
 
     def move_counts(self):
         """Per move the proposals and the accepted ones of the steps run so far, int64 [(E,) 3, 2] in the order of
-        ``MOVE_NAMES``: counted on the host, and only when asked for (``stats['moves']`` reads it), from the words the drivers
+        ``MOVE_NAMES`` ([(E,) 4, 2], ``COV_MOVE_NAMES``, when the mixture has the covariance move): counted on the host, and only when asked for (``stats['moves']`` reads it), from the words the drivers
         drew the moves from (block B of every walker) and the recorded rows - a run does not pay for it.  With a row for every
         step (thin = 1) a proposal counts as accepted when the walker's recorded position or lnL changed; an accepted proposal
         that lands on the walker's own position bit for bit (DE between two partners at one point, a snooker projection of
@@ -1350,7 +1479,8 @@ class StretchSampler(EngineSampler):
         H = self.W // 2
         lead = int(np.prod(self._lead, dtype=np.int64))
         streams = self.streams if self._lead else [self.stream]
-        counts = np.zeros((lead, 3, 2), dtype=np.int64)
+        nm = 4 if has_cov(self.moves) else 3
+        counts = np.zeros((lead, nm, 2), dtype=np.int64)
         if self.step > 0:
             axis = len(self._lead)
             rows = np.concatenate(self._chain, axis=axis).reshape(lead, -1, self.W, self.n)
@@ -1358,12 +1488,12 @@ class StretchSampler(EngineSampler):
             start, start_lnl = (a.reshape((lead, 1) + a.shape[axis:]) for a in self._start)
             for e in range(lead):
                 move = steps_moves(H, 0, self.step, self.seed, int(streams[e]), self.moves)         # [steps, W]
-                counts[e, :, 0] = np.bincount(move.reshape(-1), minlength=3)
+                counts[e, :, 0] = np.bincount(move.reshape(-1), minlength=nm)
                 if self.thin == 1:
                     moved = np.any(np.diff(np.concatenate([start[e], rows[e]]), axis=0) != 0.0, axis=2)
                     moved |= np.diff(np.concatenate([start_lnl[e], rows_lnl[e]]), axis=0) != 0.0
-                    counts[e, :, 1] = np.bincount(move[moved], minlength=3)
-        return counts.reshape(self._lead + (3, 2))
+                    counts[e, :, 1] = np.bincount(move[moved], minlength=nm)
+        return counts.reshape(self._lead + (nm, 2))
 
     def run(self, n_steps, start='ball', init_scale=1.0):
         """Advance by ``n_steps`` steps.  The first call draws the start, as the class's ``_start_positions`` says: ``'ball'``,
@@ -1385,6 +1515,9 @@ class StretchSampler(EngineSampler):
                     self.stats[key] += st[key]
             if self.slice is not None:
                 self._slice_took(st)
+            if has_cov(self.moves):
+                self.cov_fallbacks += st['cov_fallbacks']
+                self.stats['cov']['factor_fallbacks'] = int(self.cov_fallbacks.sum())
             self.stats['calls'] += 1
             self.step += k
             done += k
@@ -1432,6 +1565,11 @@ class EnsembleSampler(StretchSampler):
     (default 2.38 / sqrt(2 n)) and ``sigma`` (1e-5) are the DE move's scale and jitter, ``gamma_s`` (1.7) the snooker's scale;
     DE needs 4 walkers, the snooker 6.  ``stats['moves']`` then counts per move the proposals and - with a row for every step
     (thin = 1) - the accepted ones, on the host from the words the moves were drawn from, when it is read
+    ``moves='cov'``, or ``('cov', w)`` in the list: the covariance move (emcee's WalkMove over the whole other half, with the
+    Roberts-Gelman-Gilks scale; vmx_ensemble_run_many_cov) - a Metropolis step whose increment has the covariance of the other half
+    times ``cov_scale`` (default 2.38 / sqrt(n)), the factor computed on the device at every half-step.  It needs 4 walkers;
+    ``stats['moves']`` then has a ``cov`` entry and ``stats['cov']`` is ``dict(scale, factor_fallbacks)`` - the half-steps whose
+    covariance had no Cholesky factor and fell back to its diagonal.  It does not combine with tempering or ``'slice'`` yet.
     (:class:`MoveCounts`: the run itself does not pay for it).
 
     ``moves='slice'``: ensemble slice sampling (Karamanis & Beutler 2021, zeus's differential move; vmx_ensemble_run_slice, and
@@ -1444,9 +1582,10 @@ class EnsembleSampler(StretchSampler):
     ``stats['rounds']`` the rounds of the run, and ``accepted`` counts per walker the updates that moved it."""
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
-                 chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None):
+                 chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None,
+                 cov_scale=None):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s, mu, tune_steps)
+                            sigma, gamma_s, mu, tune_steps, cov_scale)
         self.stream = int(stream)
         self.reset()
 
@@ -1569,15 +1708,16 @@ class EnsembleSet(StretchSampler):
     where the engine's batches are shaped differently.  ``mock_rows`` [E]: the row of the installed mock
     pools every ensemble is compared with - a posterior per Monte-Carlo mock (:meth:`vega_amd.montecarlo.MonteCarlo.sample_mocks`);
     None: every ensemble reads the data the interface has installed - replicas of one run.  An engine group takes ``'python'``.
-    ``moves``, ``gamma0``, ``sigma``, ``gamma_s``: the mixture of moves of every ensemble, as for :class:`EnsembleSampler`;
+    ``moves``, ``gamma0``, ``sigma``, ``gamma_s``, ``cov_scale``: the mixture of moves of every ensemble, as for
+    :class:`EnsembleSampler` (with ``'cov'``, ``cov_fallbacks`` [E] counts every ensemble's factor fallbacks);
     ``moves='slice'`` with ``mu`` / ``tune_steps``: ensemble slice sampling, every ensemble with a scale of its own
     (vmx_ensemble_run_slice: the ensembles' requests of a round packed behind each other)."""
 
     def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
                  sample_params=None, chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                 tune_steps=None):
+                 tune_steps=None, cov_scale=None):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s, mu, tune_steps)
+                            sigma, gamma_s, mu, tune_steps, cov_scale)
         self.E = int(ensembles)
         if self.E < 1:
             raise ValueError('ensembles: at least one')
@@ -1718,6 +1858,9 @@ class EnsembleSet(StretchSampler):
         if self.moves is not None:
             m._start = None if self._start is None else (self._start[0][e].copy(), self._start[1][e].copy())
             m.stats['moves'] = MoveCounts(m)
+        if has_cov(self.moves):
+            m.cov_fallbacks = self.cov_fallbacks[e:e + 1].copy()
+            m.stats['cov'] = dict(scale=self.moves['cov_scale'], factor_fallbacks=int(m.cov_fallbacks[0]))
         if self.slice is not None:
             m.mu, m.slice_counts = self.mu[e:e + 1].copy(), self.slice_counts[e:e + 1].copy()
             m.stats['proposals'] = int(m.slice_counts[0, SC_UPDATES])
@@ -1808,6 +1951,8 @@ class TemperedEnsemble(EnsembleSet):
                  adaptation_time=100):
         if _names_slice(moves):
             raise ValueError("moves: 'slice' does not combine with parallel tempering (ntemps / betas)")
+        if names_cov(moves):
+            raise ValueError("moves: 'cov' does not combine with parallel tempering (ntemps / betas) yet")
         if (ntemps is None) == (betas is None):
             raise ValueError('ntemps or betas: one of the two')
         if betas is None:
@@ -2097,8 +2242,8 @@ def sampler_settings(main_config, sample_params):
     """The ``[Ensemble]`` settings of a main config that asks for the sampler, checked as the reference checks its samplers
     (vega_interface.py:186-195, samplers/sampler_interface.py:43-57).  A plain function of the parsed config and the sampled
     parameters: {sampler, path, name, walkers, steps, seed, a, thin, init, init_scale, driver} and, when the section states it,
-    ``moves`` with ``gamma0`` / ``de_sigma`` / ``snooker_gamma`` (:func:`_parse_moves`: a mixture of the stretch, DE and snooker
-    moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
+    ``moves`` with ``gamma0`` / ``de_sigma`` / ``snooker_gamma`` / ``cov_scale`` (:func:`_parse_moves`: a mixture of the stretch,
+    DE, snooker and cov moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
     they were), ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
     :mod:`vega_amd.replicas`) and ``ntemps`` with ``beta_min`` / ``swap_every`` and ``adapt`` with ``adapt_steps`` / ``adaptation_lag`` / ``adaptation_time``
     (:func:`_parse_tempering`: parallel tempering, and its adaptive ladder);
@@ -2158,6 +2303,8 @@ def _parse_tempering(sec, out):
     too are added only when the section states ``adapt``."""
     if 'ntemps' in sec and out.get('moves') == 'slice':
         raise ValueError('[Ensemble] moves = slice does not combine with ntemps (parallel tempering)')
+    if 'ntemps' in sec and out.get('moves') != 'slice' and names_cov(out.get('moves')):
+        raise ValueError("[Ensemble] moves: 'cov' does not combine with ntemps (parallel tempering) yet")
     if 'ntemps' not in sec:
         stray = [key for key in ('beta_min', 'swap_every') + _ADAPT_KEYS if key in sec]
         if stray:
@@ -2223,13 +2370,13 @@ def _parse_adapt(sec, out):
                          'steps // thin - adapt_steps // thin >= 2')
 
 
-_MOVE_KEYS = (('gamma0', 'gamma0'), ('de_sigma', 'sigma'), ('snooker_gamma', 'gamma_s'))
+_MOVE_KEYS = (('gamma0', 'gamma0'), ('de_sigma', 'sigma'), ('snooker_gamma', 'gamma_s'), ('cov_scale', 'cov_scale'))
 
 
 def _parse_moves(sec, out, n):
-    """``moves = de 0.8 snooker 0.2`` of ``[Ensemble]``: move names (stretch, de, snooker), each with its weight after it - a
+    """``moves = de 0.8 snooker 0.2`` of ``[Ensemble]``: move names (stretch, de, snooker, cov), each with its weight after it - a
     bare name weighs 1, so that ``moves = de`` is the pure move - into ``out['moves']`` as a list of (name, weight); ``gamma0``,
-    ``de_sigma`` and ``snooker_gamma`` into the keys of the same names when stated.  Without ``moves`` nothing is added.  The
+    ``de_sigma``, ``snooker_gamma`` and ``cov_scale`` into the keys of the same names when stated.  Without ``moves`` nothing is added.  The
     mixture is checked against the walkers as :func:`resolve_moves` checks it."""
     scales = {}
     for key, _ in _MOVE_KEYS:
@@ -2254,8 +2401,8 @@ def _parse_moves(sec, out, n):
         try:
             w = float(tok)
         except ValueError:
-            if tok not in MOVE_NAMES:
-                raise ValueError(f"[Ensemble] moves: unknown move {tok!r}; one of 'stretch', 'de', 'snooker'") from None
+            if tok not in COV_MOVE_NAMES:
+                raise ValueError(f"[Ensemble] moves: unknown move {tok!r}; one of 'stretch', 'de', 'snooker', 'cov'") from None
             pairs.append([tok, None])
             continue
         if not pairs or pairs[-1][1] is not None:

@@ -471,7 +471,7 @@ class MonteCarlo:
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
                      ess=0.5, sweeps=None, n_total=None, recycle=False, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                     tune_steps=None):
+                     tune_steps=None, cov_scale=None):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -482,8 +482,9 @@ class MonteCarlo:
 
         Keeps ``mc_posteriors``: names, per mock ``mean`` / ``sd`` [M, n] and ``covariance`` [M, n, n] of the rows after ``burn``,
         ``tau`` [M, n] (integrated autocorrelation times in recorded rows), ``acceptance`` [M], ``n_eff`` [M] (rows after burn x
-        walkers / the largest tau) and the run's settings; ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s``: the ensembles' mixture
-        of moves (:class:`vega_amd.ensemble.EnsembleSet`; None: the stretch move; ``moves='slice'`` with ``mu`` / ``tune_steps``: ensemble
+        walkers / the largest tau) and the run's settings; ``moves`` / ``gamma0`` / ``sigma`` / ``gamma_s`` / ``cov_scale``: the ensembles' mixture
+        of moves (:class:`vega_amd.ensemble.EnsembleSet`; None: the stretch move; with ``'cov'`` ``mc_posteriors`` gains
+        ``cov_fallbacks`` [M], every mock's factor fallbacks, and the table a column of that name; ``moves='slice'`` with ``mu`` / ``tune_steps``: ensemble
         slice sampling, whose ``burn`` should cover ``tune_steps``); with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
         ``mc_chain_lnl``.  Returns the set.
 
@@ -502,7 +503,8 @@ class MonteCarlo:
             raise ValueError("sample_mocks: sampler 'ensemble' or 'smc'")
         if sampler != 'smc' and (n_total is not None or recycle):
             raise ValueError("sample_mocks: n_total and recycle go with sampler='smc'")
-        moves_kw = {key: v for key, v in dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s, mu=mu, tune_steps=tune_steps).items()
+        moves_kw = {key: v for key, v in dict(moves=moves, gamma0=gamma0, sigma=sigma, gamma_s=gamma_s, mu=mu, tune_steps=tune_steps,
+                                                      cov_scale=cov_scale).items()
                     if v is not None}
         if sampler != 'ensemble' and moves_kw:
             raise ValueError("sample_mocks: moves go with sampler='ensemble'")
@@ -661,6 +663,8 @@ class MonteCarlo:
             steps=steps, burn=burn, thin=thin, walkers=walkers, seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
         if sampler.moves is not None:       # (without moves the dict has the keys it had)
             self.mc_posteriors['moves'] = dict(sampler.moves)
+            if len(sampler.moves['weights']) == 4:      # (the covariance move: every mock's factor fallbacks)
+                self.mc_posteriors['cov_fallbacks'] = sampler.cov_fallbacks.copy()
         if sampler.slice is not None:
             self.mc_posteriors.update(moves='slice', mu=sampler.mu.copy(), tune_steps=sampler.slice['tune_steps'])
         self.mc_chains = sampler.get_chain() if keep_chains else None
@@ -715,6 +719,8 @@ class MonteCarlo:
             for j, nm in enumerate(names):
                 cols += [(f'{nm}_mean', 'D', post['mean'][:, j]), (f'{nm}_sd', 'D', post['sd'][:, j]), (f'{nm}_tau', 'D', post['tau'][:, j])]
             cols += [('acceptance', 'D', post['acceptance']), ('n_eff', 'D', post['n_eff']), cov_col]
+            if 'cov_fallbacks' in post:
+                cols += [('cov_fallbacks', 'K', np.asarray(post['cov_fallbacks'], dtype=np.int64))]
             header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)

@@ -62,6 +62,9 @@ def _common(sampler, kind, points, derived):
         if key == 'moves':          # (the ensemble's per-move counts: one number per move and count; an unknown count is left out)
             rec.update({f'stats_moves_{move}_{what}': v for move, counts in val.items() for what, v in counts.items() if v is not None})
             continue
+        if key == 'cov':            # (the covariance move: its scale and the factor fallbacks, one entry each)
+            rec.update({f'stats_cov_{name}': v for name, v in val.items()})
+            continue
         if key == 'slice':          # (ensemble slice sampling: its counts and scale, one entry each)
             rec.update({f'stats_slice_{name}': v for name, v in val.items()})
             continue
