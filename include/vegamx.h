@@ -664,6 +664,39 @@ int vmx_ensemble_run_many_cov(vmx_engine* e, const vmx_ensemble_spec* spec, int3
                               const vmx_ensemble_moves* moves, const vmx_ensemble_cov* cov, int64_t* fallbacks);
 int vmx_ensemble_cov_factor(vmx_engine* e, int32_t E, int32_t H, int32_t n, const double* x, double* mean, double* factor,
                             int32_t* flag);
+/* A chain store: the recorded rows of E ensembles of W walkers over n columns kept on the device, positions [E][capacity][W][n]
+ * and lnL [E][capacity][W], and reduced there (vega_amd/csrc/vmx_chain.h pins every sum).  A store belongs to the engine it was
+ * created on and is destroyed with it at the latest.
+ *   create    E >= 1, 2 <= W <= 1024, 1 <= n <= VMX_ENS_MAXN, capacity_rows >= 0.  A failed allocation returns -2 and leaves the
+ *             engine usable.
+ *   reserve   grows the capacity to capacity_rows (never shrinks); the stored rows are kept.
+ *   rows      the rows stored, per ensemble.
+ *   append    uploads `rows` rows of every ensemble from the host, chain [E][rows][W][n] and chain_lnl [E][rows][W], behind the
+ *             stored ones (the `python` driver's rows, synthetic chains).
+ *   fetch     the rows [row0, row0 + rows) as chain [E][rows][W][n] and chain_lnl [E][rows][W] - the layout the run entries write;
+ *             either pointer may be NULL.
+ *   vmx_ensemble_set_chain_store   while a store is attached (NULL: detached) every ensemble run - vmx_ensemble_run and all the
+ *             vmx_ensemble_run_* entries - appends the rows it records device to device, one pitched copy per array on the engine's
+ *             stream behind the half-step kernels.  The call's host `chain` / `chain_lnL` may then be NULL: nothing of the chain
+ *             is copied to the host, and the call's single wait stays single.  A run of G ladders of T rungs needs E = G T.
+ *   summary   over the rows [first_row, rows) of every ensemble, with Sokal's window constant c (emcee: 5): count [E] (= (rows -
+ *             first_row) W), mean [E][n], covariance [E][n][n] (two passes, ddof 1 over rows x walkers), tau [E][n] and window
+ *             [E][n] (emcee's integrated autocorrelation time by direct lag sums up to the window).  Any output may be NULL; tau
+ *             and window both NULL skip the autocorrelation, mean and covariance both NULL the moments' second pass.
+ * Refused before anything runs (-1, vmx_last_error, engine and store untouched): a NULL engine or store; sizes outside the ranges
+ * above, or whose product overflows; an attached store whose (E, W, n) is not the run's, or without room for the run's rows; rows
+ * beyond the capacity (append); row0 + rows beyond the rows stored (fetch); first_row outside [0, rows) or a c that is not positive
+ * and finite (summary). */
+typedef struct vmx_chain_store vmx_chain_store;
+int vmx_chain_store_create(vmx_engine* e, int32_t E, int32_t W, int32_t n, int64_t capacity_rows, vmx_chain_store** out);
+int vmx_chain_store_destroy(vmx_chain_store* store);
+int vmx_chain_store_reserve(vmx_chain_store* store, int64_t capacity_rows);
+int vmx_chain_store_rows(vmx_chain_store* store, int64_t* rows);
+int vmx_chain_store_append(vmx_chain_store* store, int64_t rows, const double* chain, const double* chain_lnl);
+int vmx_chain_store_fetch(vmx_chain_store* store, int64_t row0, int64_t rows, double* chain, double* chain_lnl);
+int vmx_chain_store_summary(vmx_chain_store* store, int64_t first_row, double c, int64_t* count, double* mean, double* covariance,
+                            double* tau, int64_t* window);
+int vmx_ensemble_set_chain_store(vmx_engine* e, vmx_chain_store* store);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

@@ -9,6 +9,7 @@
 #include "vmx_ensemble.h"
 #include "vmx_nested.h"
 #include "vmx_smc.h"
+#include "vmx_chain.h"
 
 #include <atomic>
 #include <cmath>
@@ -1808,6 +1809,17 @@ __global__ __launch_bounds__(SMC_THREADS) void k_smc_move(SmcSetDev S, int64_t r
 
 }  // namespace
 
+// A chain store (vmx_chain_store_*; vmx_chain.h): the recorded rows of E ensembles on the device and the scratch of their summary
+struct vmx_chain_store {
+    vmx_engine* engine = nullptr;
+    int E = 0, W = 0, n = 0;
+    int64_t capacity = 0, rows = 0;
+    DevBuf<double> x, lnl;              // [E][capacity][W][n], [E][capacity][W]
+    // the summary's scratch, grown on demand: series sums and means [E][W][n] each, the centred series [E][n][T][W], the results
+    DevBuf<double> sums, centred, out;
+    DevBuf<int64_t> window;
+};
+
 struct vmx_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1826,6 +1838,8 @@ struct vmx_engine {
     const int32_t* call_mock = nullptr;     // per-call mock rows of the walkers (device pointer; vmx_eval_device_mocks, vmx_fit_migrad)
     FitWorkspace* fitws = nullptr;
     EnsWorkspace* ensws = nullptr;
+    std::vector<vmx_chain_store*> chain_stores;    // every store created on this engine and not yet destroyed
+    vmx_chain_store* chain_store = nullptr;        // the one the ensemble runs append to (vmx_ensemble_set_chain_store)
     NsWorkspace* nsws = nullptr;
     SmcWorkspace* smcws = nullptr;
     // a likelihood session (vmx_fit_migrad and the three samplers): lane_wait, when set, is the event at which the rows of the second
@@ -2002,6 +2016,7 @@ struct vmx_engine {
         for (void* p : host_allocs) (void)hipHostFree(p);
         delete fitws;
         delete ensws;
+        for (auto* c : chain_stores) delete c;
         delete nsws;
         delete smcws;
         if (pin_theta) (void)hipHostFree(pin_theta);
@@ -4818,6 +4833,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
+    L->chain_stores.clear(); L->chain_store = nullptr;      // (the stores belong to the engine they were created on, not to its lanes)
     L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->ev_rows = nullptr; L->ev_lane = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
     L->graphs.clear(); L->graph_route.clear(); L->quad_lists.clear(); L->cinv_lists.clear(); L->host_allocs.clear(); L->spans.clear(); L->span_used = 0; L->profiling = false;
@@ -5339,6 +5355,9 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
                         const EnsPtRun* pt = nullptr, const vmx_ensemble_cov* cov = nullptr, int64_t* fallbacks = nullptr);
 
 // One ensemble is the set of one, on the stream of its spec
+static int chain_store_check(const std::string& name, const vmx_chain_store* s, int32_t E, int32_t W, int32_t n, int64_t rows);
+static int chain_store_take(vmx_chain_store* s, const double* chain, const double* chain_lnl, int64_t rows, hipStream_t st);
+
 int vmx_ensemble_run(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t W, double* x, double* lnL, int64_t* accepted,
                      int64_t step0, int32_t n_steps, int32_t thin, double* chain, double* chain_lnL,
                      const vmx_ensemble_options* opt, vmx_ensemble_stats* stats)
@@ -5558,6 +5577,10 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
     const size_t EW = (size_t)E * W;
     const int EH = E * H;
+    // (an attached chain store takes the recorded rows where they are: the kernels record whether or not the host wants them)
+    vmx_chain_store* const store = e->chain_store;
+    if (chain_store_check(name, store, E, W, n, rows)) return -1;
+    const bool keep_x = chain || store, keep_lnl = chain_lnL || store;
 
     HIP_OK(hipSetDevice(e->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -5576,8 +5599,8 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     if (pt && (ensure(S.beta, n_beta) || (n_swaps && ensure(S.swaps, n_swaps)))) return -2;
     if (cov && ensure(S.cov_fallbacks, E)) return -2;
     if (ad && (ensure(S.adapt_skipped, pt->G) || (n_hist && ensure(S.beta_hist, n_hist)))) return -2;
-    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
-    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
+    if (keep_x && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
+    if (keep_lnl && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
     hipStream_t st = e->stream;
     EnsDev D{};
     if (S.box.upload(EH, P, n, spec->theta_fixed, spec->lo, spec->hi, inv, st, D.box)) return -2;
@@ -5599,7 +5622,7 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p; D.n_box = S.n_box.p; D.n_fail = S.n_fail.p;
     D.prop = S.prop.p; D.factor = S.factor.p; D.inside = S.inside.p;
     D.col = S.col.p;
-    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.chain = keep_x && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = keep_lnl && rows > 0 ? S.chain_lnl.p : nullptr;
     D.streams = S.streams.p; D.rows = rows;
     D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = spec->a; D.log_norm = spec->log_norm;
     D.seed = spec->seed; D.step0 = step0;
@@ -5684,10 +5707,12 @@ static int ensemble_run(const char* who, vmx_engine* e, const vmx_ensemble_spec*
     HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(box.data(), S.n_box.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(failed.data(), S.n_fail.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (chain_store_take(store, S.chain.p, S.chain_lnl.p, rows, st)) return -2;
     if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * EW * sizeof(double), hipMemcpyDeviceToHost, st));
     R.seconds_enqueuing = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_loop).count();
     HIP_OK(hipStreamSynchronize(st));       // (the call's only wait: the segment is enqueued as a whole)
+    if (store) store->rows += rows;
     R.host_synchronisations = 1;
     R.steps = n_steps;
     R.proposals = (int64_t)n_steps * (int64_t)EW;
@@ -5732,6 +5757,9 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
     const int n = spec->n, P = e->n_params, H = W / 2;
     const int64_t rows = (step0 + n_steps) / thin - step0 / thin;
     const size_t EW = (size_t)E * W, EH = (size_t)E * H;
+    vmx_chain_store* const store = e->chain_store;          // (as in ensemble_run)
+    if (chain_store_check(name, store, E, W, n, rows)) return -1;
+    const bool keep_x = chain || store, keep_lnl = chain_lnL || store;
 
     HIP_OK(hipSetDevice(e->device));
     const auto t_begin = std::chrono::steady_clock::now();
@@ -5743,8 +5771,8 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
         ensure(S.sl_open, E) || ensure(S.sl_active, E) || ensure(S.sl_count, E) ||
         (mock_row && (ensure(S.sl_mock_row, E) || ensure(S.mock, EH))))
         return -2;
-    if (chain && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
-    if (chain_lnL && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
+    if (keep_x && rows > 0 && ensure(S.chain, (size_t)rows * EW * n)) return -2;
+    if (keep_lnl && rows > 0 && ensure(S.chain_lnl, (size_t)rows * EW)) return -2;
     if (!S.pin_word) {
         HIP_OK(hipHostMalloc((void**)&S.pin_word, 16 * sizeof(int32_t), hipHostMallocMapped));
         HIP_OK(hipHostGetDevicePointer((void**)&S.dpin_word, S.pin_word, 0));
@@ -5776,7 +5804,7 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
 
     D.x = S.x.p; D.lnl = S.lnl.p; D.acc = S.acc.p;
     D.col = S.col.p;
-    D.chain = chain && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = chain_lnL && rows > 0 ? S.chain_lnl.p : nullptr;
+    D.chain = keep_x && rows > 0 ? S.chain.p : nullptr; D.chain_lnl = keep_lnl && rows > 0 ? S.chain_lnl.p : nullptr;
     D.streams = S.streams.p; D.rows = rows;
     D.W = W; D.n = n; D.P = P; D.thin = thin; D.a = 0.0; D.log_norm = spec->log_norm;
     D.seed = spec->seed; D.step0 = step0;
@@ -5828,9 +5856,11 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
     HIP_OK(hipMemcpyAsync(accepted, S.acc.p, EW * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(mu, S.sl_mu.p, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipMemcpyAsync(counts.data(), S.sl_counts.p, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (chain_store_take(store, S.chain.p, S.chain_lnl.p, rows, st)) return -2;
     if (chain && rows > 0) HIP_OK(hipMemcpyAsync(chain, S.chain.p, (size_t)rows * EW * n * sizeof(double), hipMemcpyDeviceToHost, st));
     if (chain_lnL && rows > 0) HIP_OK(hipMemcpyAsync(chain_lnL, S.chain_lnl.p, (size_t)rows * EW * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (store) store->rows += rows;
     R.host_synchronisations = rounds + 1;
     R.steps = n_steps;
     int64_t rows_counted = 0;           // (the machines' own count of their requests: the rows the engine was given, no other)
@@ -5845,6 +5875,312 @@ int vmx_ensemble_run_slice(vmx_engine* e, const vmx_ensemble_spec* spec, int32_t
     R.seconds_enqueuing = enqueue_s;
     R.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
     if (stats) *stats = R;
+    return 0;
+}
+
+// ---- the chain where it is recorded (vmx_chain.h): the store, and its summary
+static_assert(vmx_chain::MAXW * (int)sizeof(double) + vmx_chain::TILE * (int)sizeof(double) <= 48 * 1024, "the summary's LDS");
+
+namespace {
+
+constexpr int CHAIN_THREADS = 256;
+
+// What the three kernels of the summary read: the store's rows [first, first + T) of every ensemble and the scratch
+struct ChainDev {
+    const double* x;                    // [E][capacity][W][n]
+    double* sums;                       // [2][E][W][n]: the series sums, then the series' own means
+    double* centred;                    // [E][n][T][W]
+    double* mean; double* cov;          // [E][n], [E][n][n] (cov nullptr: not wanted)
+    double* tau; int64_t* window;       // [E][n] each
+    int64_t capacity, first, T;
+    int32_t E, W, n;
+    double c;
+};
+
+// pair p of the lower triangle, rows first: (0,0) (1,0) (1,1) (2,0) ...
+__device__ inline void chain_pair(int p, int& i, int& j)
+{
+    i = 0;
+    while ((i + 1) * (i + 2) / 2 <= p) ++i;
+    j = p - i * (i + 1) / 2;
+}
+
+// One work-group per ensemble: the series sums and means (a lane per (walker, column), sequential in t), the mean (a lane per
+// column, sequential in w), then the covariance in chunks of pairs that fill the tile: a lane per (pair, walker), sequential in t,
+// then a lane per pair, sequential in w.  Every loop strides by the block: no sum depends on its size.
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_moments(ChainDev C)
+{
+    __shared__ double tile[vmx_chain::TILE];
+    const int e = blockIdx.x, W = C.W, n = C.n;
+    const int64_t Wn = (int64_t)W * n, T = C.T, count = T * W;
+    const double* x = C.x + ((int64_t)e * C.capacity + C.first) * Wn;
+    double* S = C.sums + (int64_t)e * Wn;
+    double* m = C.sums + ((int64_t)C.E + e) * Wn;
+    for (int64_t q = threadIdx.x; q < Wn; q += blockDim.x) {
+        const double s = vmx_chain::seq_sum(x + q, T, Wn);
+        S[q] = s;
+        m[q] = vmx_chain::quotient(s, T);
+    }
+    __syncthreads();
+    double* mean = C.mean + (int64_t)e * n;
+    for (int d = threadIdx.x; d < n; d += blockDim.x) mean[d] = vmx_chain::quotient(vmx_chain::seq_sum(S + d, W, n), count);
+    __syncthreads();
+    if (!C.cov) return;
+    double* cov = C.cov + (int64_t)e * n * n;
+    const int pairs = n * (n + 1) / 2, chunk = vmx_chain::per_tile(W, pairs);
+    for (int p0 = 0; p0 < pairs; p0 += chunk) {
+        const int pc = min(chunk, pairs - p0);
+        for (int q = threadIdx.x; q < pc * W; q += blockDim.x) {
+            const int k = q / W, w = q % W;
+            int i, j;
+            chain_pair(p0 + k, i, j);
+            tile[q] = vmx_chain::product_sum(x + (int64_t)w * n + i, x + (int64_t)w * n + j, mean[i], mean[j], T, Wn);
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < pc; k += blockDim.x) {
+            int i, j;
+            chain_pair(p0 + k, i, j);
+            const double v = vmx_chain::quotient(vmx_chain::seq_sum(tile + (int64_t)k * W, W, 1), count - 1);
+            cov[i * n + j] = v;
+            cov[j * n + i] = v;
+        }
+        __syncthreads();
+    }
+}
+
+// The centred series, x[e][first + t][w][d] - m[e][w][d] -> centred[e][d][t][w]: W fastest, so that the lanes of k_chain_acf,
+// (walker, lag), read contiguous rows instead of every n-th double of the chain
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_centre(ChainDev C)
+{
+    const int64_t Wn = (int64_t)C.W * C.n, per = C.T * Wn, total = (int64_t)C.E * per;
+    const double* m = C.sums + (int64_t)C.E * Wn;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = g / per, q = g % per, t = q / Wn, r = q % Wn;
+        const int w = (int)(r / C.n), d = (int)(r % C.n);
+        const double v = C.x[(e * C.capacity + C.first) * Wn + q];
+        C.centred[((e * C.n + d) * C.T + t) * C.W + w] = vmx_chain::centred(v, m[e * Wn + r]);
+    }
+}
+
+// One work-group per (ensemble, column): the lags in blocks of `lags`, a lane per (lag, walker) with w fastest and sequential in
+// t, rho into the tile, then a lane per lag for f (sequential in w) and thread 0 walks the block's lags in order
+// (vmx_chain::window_take); the group leaves at the block in which the window closes.  The series streams from L2: one
+// parameter's is T W doubles, more than the LDS at the sizes that matter.
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_acf(ChainDev C)
+{
+    __shared__ double tile[vmx_chain::TILE];
+    __shared__ double acov0[vmx_chain::MAXW];
+    __shared__ double f[vmx_chain::LAG_BLOCK];
+    __shared__ int closed;
+    const int d = blockIdx.x % C.n, W = C.W;
+    const int64_t e = blockIdx.x / C.n, T = C.T;
+    const double* cen = C.centred + ((e * C.n + d) * T) * W;
+    const int LB = vmx_chain::per_tile(W, vmx_chain::LAG_BLOCK);
+    vmx_chain::Window win;              // (thread 0's is the one that walks)
+    if (threadIdx.x == 0) closed = 0;
+    for (int w = threadIdx.x; w < W; w += blockDim.x) acov0[w] = vmx_chain::lag_sum(cen + w, T, 0, W);
+    __syncthreads();
+    for (int64_t l0 = 0; l0 < T; l0 += LB) {
+        const int lags = (int)min((int64_t)LB, T - l0);
+        for (int q = threadIdx.x; q < lags * W; q += blockDim.x) {
+            const int k = q / W, w = q % W;
+            const int64_t l = l0 + k;
+            const double a = l == 0 ? acov0[w] : vmx_chain::lag_sum(cen + w, T, l, W);
+            tile[q] = vmx_chain::rho(a, acov0[w]);
+        }
+        __syncthreads();
+        for (int k = threadIdx.x; k < lags; k += blockDim.x) f[k] = vmx_chain::quotient(vmx_chain::seq_sum(tile + (int64_t)k * W, W, 1), W);
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int k = 0; k < lags; ++k)
+                if (vmx_chain::window_take(win, f[k], T, C.c)) {
+                    C.tau[e * C.n + d] = win.tau;
+                    C.window[e * C.n + d] = win.window;
+                    closed = 1;
+                    break;
+                }
+        __syncthreads();
+        if (closed) return;
+    }
+}
+
+// bytes of `rows` rows of every ensemble must fit size_t: E capacity W n doubles
+static bool chain_fits(int64_t E, int64_t W, int64_t n, int64_t rows)
+{
+    const size_t per = (size_t)E * (size_t)W * (size_t)n * sizeof(double);        // (E <= 2^31, W <= 2^10, n <= 2^6: no overflow)
+    return rows == 0 || (size_t)rows <= SIZE_MAX / per;
+}
+
+// rows of E blocks between two layouts [E][rows_a][per] and [E][rows_b][per]: one pitched copy
+static hipError_t chain_copy(void* dst, int64_t dst_rows, const void* src, int64_t src_rows, int64_t rows, int64_t per, int E,
+                             hipMemcpyKind kind, hipStream_t st)
+{
+    return hipMemcpy2DAsync(dst, (size_t)dst_rows * per * sizeof(double), src, (size_t)src_rows * per * sizeof(double),
+                            (size_t)rows * per * sizeof(double), (size_t)E, kind, st);
+}
+
+// `count` entries in a fresh allocation (what `b` held is gone); a failure leaves the runtime without a pending error
+static int chain_alloc(DevBuf<double>& b, size_t count)
+{
+    if (b.alloc(count, false)) { (void)hipGetLastError(); return -2; }
+    return 0;
+}
+
+}  // namespace
+
+int vmx_chain_store_create(vmx_engine* e, int32_t E, int32_t W, int32_t n, int64_t capacity_rows, vmx_chain_store** out)
+{
+    const std::string name("vmx_chain_store_create");
+    REQUIRE(e && out, name);
+    REQUIRE(E >= 1 && W >= 2 && W <= vmx_chain::MAXW && n >= 1 && n <= VMX_ENS_MAXN && capacity_rows >= 0,
+            name + ": E >= 1, 2 <= W <= 1024, 1 <= n <= VMX_ENS_MAXN, capacity_rows >= 0");
+    REQUIRE(chain_fits(E, W, n, capacity_rows), name + ": the store is too large");
+    HIP_OK(hipSetDevice(e->device));
+    vmx_chain_store* s = new vmx_chain_store();
+    s->engine = e; s->E = E; s->W = W; s->n = n; s->capacity = capacity_rows;
+    const size_t slots = (size_t)E * (size_t)capacity_rows * (size_t)W;
+    if (chain_alloc(s->x, slots * n) || chain_alloc(s->lnl, slots)) { delete s; return -2; }
+    e->chain_stores.push_back(s);
+    *out = s;
+    return 0;
+}
+
+int vmx_chain_store_destroy(vmx_chain_store* s)
+{
+    REQUIRE(s, "vmx_chain_store_destroy");
+    vmx_engine* e = s->engine;
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+    if (e->chain_store == s) e->chain_store = nullptr;
+    e->chain_stores.erase(std::remove(e->chain_stores.begin(), e->chain_stores.end(), s), e->chain_stores.end());
+    delete s;
+    return 0;
+}
+
+int vmx_chain_store_reserve(vmx_chain_store* s, int64_t capacity_rows)
+{
+    const std::string name("vmx_chain_store_reserve");
+    REQUIRE(s && capacity_rows >= 0, name);
+    if (capacity_rows <= s->capacity) return 0;
+    REQUIRE(chain_fits(s->E, s->W, s->n, capacity_rows), name + ": the store is too large");
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const size_t slots = (size_t)s->E * (size_t)capacity_rows * (size_t)s->W;
+    DevBuf<double> x, lnl;
+    if (chain_alloc(x, slots * s->n) || chain_alloc(lnl, slots)) return -2;
+    if (s->rows > 0) {
+        HIP_OK(chain_copy(x.p, capacity_rows, s->x.p, s->capacity, s->rows, (int64_t)s->W * s->n, s->E, hipMemcpyDeviceToDevice, e->stream));
+        HIP_OK(chain_copy(lnl.p, capacity_rows, s->lnl.p, s->capacity, s->rows, s->W, s->E, hipMemcpyDeviceToDevice, e->stream));
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    std::swap(s->x.p, x.p); std::swap(s->x.n, x.n);
+    std::swap(s->lnl.p, lnl.p); std::swap(s->lnl.n, lnl.n);
+    s->capacity = capacity_rows;
+    return 0;
+}
+
+int vmx_chain_store_rows(vmx_chain_store* s, int64_t* rows)
+{
+    REQUIRE(s && rows, "vmx_chain_store_rows");
+    *rows = s->rows;
+    return 0;
+}
+
+int vmx_chain_store_append(vmx_chain_store* s, int64_t rows, const double* chain, const double* chain_lnl)
+{
+    const std::string name("vmx_chain_store_append");
+    REQUIRE(s && rows >= 0 && (rows == 0 || (chain && chain_lnl)), name);
+    REQUIRE(rows <= s->capacity - s->rows, name + ": rows beyond the store's capacity");
+    if (rows == 0) return 0;
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const int64_t Wn = (int64_t)s->W * s->n;
+    HIP_OK(chain_copy(s->x.p + s->rows * Wn, s->capacity, chain, rows, rows, Wn, s->E, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(chain_copy(s->lnl.p + s->rows * s->W, s->capacity, chain_lnl, rows, rows, s->W, s->E, hipMemcpyHostToDevice, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    s->rows += rows;
+    return 0;
+}
+
+int vmx_chain_store_fetch(vmx_chain_store* s, int64_t row0, int64_t rows, double* chain, double* chain_lnl)
+{
+    const std::string name("vmx_chain_store_fetch");
+    REQUIRE(s && row0 >= 0 && rows >= 0, name);
+    REQUIRE(row0 <= s->rows && rows <= s->rows - row0, name + ": row0 + rows beyond the rows stored");
+    if (rows == 0 || (!chain && !chain_lnl)) return 0;
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const int64_t Wn = (int64_t)s->W * s->n;
+    if (chain) HIP_OK(chain_copy(chain, rows, s->x.p + row0 * Wn, s->capacity, rows, Wn, s->E, hipMemcpyDeviceToHost, e->stream));
+    if (chain_lnl) HIP_OK(chain_copy(chain_lnl, rows, s->lnl.p + row0 * s->W, s->capacity, rows, s->W, s->E, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int vmx_ensemble_set_chain_store(vmx_engine* e, vmx_chain_store* s)
+{
+    REQUIRE(e, "vmx_ensemble_set_chain_store");
+    REQUIRE(!s || s->engine == e, "vmx_ensemble_set_chain_store: the store belongs to another engine");
+    e->chain_store = s;
+    return 0;
+}
+
+// What an ensemble run refuses of the attached store before anything runs
+static int chain_store_check(const std::string& name, const vmx_chain_store* s, int32_t E, int32_t W, int32_t n, int64_t rows)
+{
+    if (!s) return 0;
+    REQUIRE(s->E == E && s->W == W && s->n == n, name + ": the attached chain store has another (E, W, n)");
+    REQUIRE(rows <= s->capacity - s->rows, name + ": the run's rows exceed the attached chain store's capacity");
+    return 0;
+}
+
+// The call's block [E][rows][W][n] (and its lnL) behind the store's rows, on the stream behind the half-step kernels; the caller
+// counts the rows in once the stream has been waited for
+static int chain_store_take(vmx_chain_store* s, const double* chain, const double* chain_lnl, int64_t rows, hipStream_t st)
+{
+    if (!s || rows <= 0) return 0;
+    const int64_t Wn = (int64_t)s->W * s->n;
+    HIP_OK(chain_copy(s->x.p + s->rows * Wn, s->capacity, chain, rows, rows, Wn, s->E, hipMemcpyDeviceToDevice, st));
+    HIP_OK(chain_copy(s->lnl.p + s->rows * s->W, s->capacity, chain_lnl, rows, rows, s->W, s->E, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int vmx_chain_store_summary(vmx_chain_store* s, int64_t first_row, double c, int64_t* count, double* mean, double* covariance,
+                            double* tau, int64_t* window)
+{
+    const std::string name("vmx_chain_store_summary");
+    REQUIRE(s, name);
+    REQUIRE(first_row >= 0 && first_row < s->rows, name + ": first_row must be a stored row (the summary needs at least one)");
+    REQUIRE(c > 0.0 && std::isfinite(c), name + ": c must be positive and finite");
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const int E = s->E, W = s->W, n = s->n;
+    const int64_t T = s->rows - first_row, Wn = (int64_t)W * n;
+    const bool acf = tau || window, second = mean || covariance;
+    const size_t En = (size_t)E * n;
+    if ((s->sums.n < 2 * (size_t)E * Wn && chain_alloc(s->sums, 2 * (size_t)E * Wn)) ||
+        (s->out.n < En * (2 + n) && chain_alloc(s->out, En * (2 + n))) || (s->window.n < En && s->window.alloc(En, false) && ((void)hipGetLastError(), true)) ||
+        (acf && s->centred.n < En * (size_t)T * W && chain_alloc(s->centred, En * (size_t)T * W)))
+        return -2;
+    ChainDev C{};
+    C.x = s->x.p; C.sums = s->sums.p; C.centred = s->centred.p;
+    C.mean = s->out.p; C.cov = second ? s->out.p + En : nullptr; C.tau = s->out.p + En * (1 + n); C.window = s->window.p;
+    C.capacity = s->capacity; C.first = first_row; C.T = T; C.E = E; C.W = W; C.n = n; C.c = c;
+    hipStream_t st = e->stream;
+    hipLaunchKernelGGL(k_chain_moments, dim3(E), dim3(CHAIN_THREADS), 0, st, C);
+    if (acf) {
+        const int64_t total = (int64_t)E * T * Wn;
+        const int blocks = (int)std::min<int64_t>((total + CHAIN_THREADS - 1) / CHAIN_THREADS, 65536);
+        hipLaunchKernelGGL(k_chain_centre, dim3(blocks), dim3(CHAIN_THREADS), 0, st, C);
+        hipLaunchKernelGGL(k_chain_acf, dim3((unsigned)En), dim3(CHAIN_THREADS), 0, st, C);
+    }
+    HIP_OK(hipGetLastError());
+    if (mean) HIP_OK(hipMemcpyAsync(mean, C.mean, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (covariance) HIP_OK(hipMemcpyAsync(covariance, C.cov, En * n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (tau) HIP_OK(hipMemcpyAsync(tau, C.tau, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (window) HIP_OK(hipMemcpyAsync(window, C.window, En * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (count) std::fill(count, count + E, T * W);
     return 0;
 }
 

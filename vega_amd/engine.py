@@ -372,6 +372,15 @@ def load_library():
                                         C.POINTER(EnsembleMoves), C.POINTER(C.c_int64)]
     lib.vmx_ensemble_run_pt_adapt.argtypes = lib.vmx_ensemble_run_pt.argtypes + [C.POINTER(EnsembleAdapt), dptr, C.POINTER(C.c_int64)]
     lib.vmx_ensemble_run_slice.argtypes = lib.vmx_ensemble_run_many.argtypes[:-1] + [C.POINTER(EnsembleSlice), dptr, C.POINTER(C.c_int64)]
+    i64p = C.POINTER(C.c_int64)
+    lib.vmx_chain_store_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.vmx_chain_store_destroy.argtypes = [C.c_void_p]
+    lib.vmx_chain_store_reserve.argtypes = [C.c_void_p, C.c_int64]
+    lib.vmx_chain_store_rows.argtypes = [C.c_void_p, i64p]
+    lib.vmx_chain_store_append.argtypes = [C.c_void_p, C.c_int64, dptr, dptr]
+    lib.vmx_chain_store_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dptr, dptr]
+    lib.vmx_chain_store_summary.argtypes = [C.c_void_p, C.c_int64, C.c_double, i64p, dptr, dptr, dptr, i64p]
+    lib.vmx_ensemble_set_chain_store.argtypes = [C.c_void_p, C.c_void_p]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -460,7 +469,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -709,6 +718,87 @@ class Lowering:
         return d
 
 
+class ChainStore:
+    """The recorded rows of E ensembles of W walkers over n columns kept on the device (include/vegamx.h: vmx_chain_store_*),
+    made by :meth:`Engine.chain_store`.  While it is attached (:meth:`Engine.attach_chain_store`) every ensemble run of the engine
+    appends the rows it records, device to device."""
+
+    def __init__(self, engine, E, W, n, capacity):
+        self.engine, self.E, self.W, self.n, self.capacity = engine, int(E), int(W), int(n), int(capacity)
+        self._h = None
+        handle = C.c_void_p()
+        engine._check(engine.lib.vmx_chain_store_create(engine._h, self.E, self.W, self.n, self.capacity, C.byref(handle)))
+        self._h = handle
+
+    def _handle(self):
+        if not self._h or not self.engine._h:
+            raise EngineError('the chain store is closed')
+        return self._h
+
+    @property
+    def rows(self):
+        """The rows stored, per ensemble."""
+        rows = C.c_int64()
+        self.engine._check(self.engine.lib.vmx_chain_store_rows(self._handle(), C.byref(rows)))
+        return int(rows.value)
+
+    def reserve(self, capacity):
+        """Room for ``capacity`` rows per ensemble (it never shrinks); the stored rows are kept."""
+        self.engine._check(self.engine.lib.vmx_chain_store_reserve(self._handle(), int(capacity)))
+        self.capacity = max(self.capacity, int(capacity))
+
+    def append(self, chain, chain_lnl):
+        """Upload the host rows ``chain`` [E, rows, W, n] with ``chain_lnl`` [E, rows, W] behind the stored ones."""
+        chain, chain_lnl = _f64(chain), _f64(chain_lnl)
+        if chain.ndim != 4 or chain.shape[0::2] != (self.E, self.W) or chain.shape[3] != self.n or chain_lnl.shape != chain.shape[:3]:
+            raise ValueError(f'chain [{self.E}, rows, {self.W}, {self.n}], chain_lnl [{self.E}, rows, {self.W}]')
+        self.engine._check(self.engine.lib.vmx_chain_store_append(self._handle(), chain.shape[1], _dp(chain), _dp(chain_lnl)))
+
+    def fetch(self, row0=0, rows=None, lnl=True):
+        """The rows [row0, row0 + rows) (None: to the end) as (chain [E, rows, W, n], chain_lnl [E, rows, W]; None without
+        ``lnl``) - the arrays the run entries return."""
+        row0 = int(row0)
+        rows = self.rows - row0 if rows is None else int(rows)
+        chain = np.empty((self.E, max(rows, 0), self.W, self.n))
+        chain_lnl = np.empty(chain.shape[:3]) if lnl else None
+        self.engine._check(self.engine.lib.vmx_chain_store_fetch(self._handle(), row0, rows, _dp(chain), _dp(chain_lnl) if lnl else None))
+        return chain, chain_lnl
+
+    def summary(self, first=0, c=5, moments=True, tau=True):
+        """The summary of the rows from ``first`` on, computed where they are (vega_amd/csrc/vmx_chain.h;
+        :func:`vega_amd.ensemble.chain_summary` is the same numbers bit for bit): ``dict(count [E], mean [E, n], sd [E, n],
+        covariance [E, n, n], tau [E, n], window [E, n], n_eff [E])``.  Without ``moments`` only count, tau, window and n_eff
+        cross to the host, without ``tau`` only count, mean, sd and covariance."""
+        E, n = self.E, self.n
+        count = np.zeros(E, dtype=np.int64)
+        out = dict(count=count)
+        mean, cov = (np.empty((E, n)), np.empty((E, n, n))) if moments else (None, None)
+        t, window = (np.empty((E, n)), np.zeros((E, n), dtype=np.int64)) if tau else (None, None)
+        i64p = C.POINTER(C.c_int64)
+        self.engine._check(self.engine.lib.vmx_chain_store_summary(
+            self._handle(), int(first), float(c), count.ctypes.data_as(i64p), None if mean is None else _dp(mean),
+            None if cov is None else _dp(cov), None if t is None else _dp(t), None if window is None else window.ctypes.data_as(i64p)))
+        if moments:
+            out.update(mean=mean, sd=np.sqrt(np.diagonal(cov, axis1=1, axis2=2)), covariance=cov)
+        if tau:
+            with np.errstate(divide='ignore', invalid='ignore'):
+                out.update(tau=t, window=window, n_eff=count.astype(np.float64) / np.max(t, axis=1))
+        return out
+
+    def close(self):
+        if self._h and self.engine._h:
+            if self.engine._attached is self:
+                self.engine.attach_chain_store(None)
+            self.engine.lib.vmx_chain_store_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Engine:
     """One vegamx engine handle on one GPU, built from a Problem."""
 
@@ -742,6 +832,7 @@ class Engine:
         self.lanes = 1
         self.nl_hint = 0                # (the level of set_constant_nl_hint, 0 until it is called)
         self._h = C.c_void_p()
+        self._attached = None           # the chain store the ensemble runs append to (attach_chain_store)
         self._gk = {}
         self.device = int(device)
         self._check(self.lib.vmx_create(C.byref(self._h), int(device)))
@@ -783,8 +874,9 @@ class Engine:
 
     def close(self):
         if self._h:
-            self.lib.vmx_destroy(self._h)
+            self.lib.vmx_destroy(self._h)       # (its chain stores go with it)
             self._h = C.c_void_p()
+            self._attached = None
 
     def __del__(self):
         try:
@@ -1320,6 +1412,18 @@ class Engine:
                 self._check(self.lib.vmx_ensemble_run_many_cov(*head, C.byref(mv), C.byref(cv), fallbacks.ctypes.data_as(C.POINTER(C.c_int64))))
                 return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per, cov_fallbacks=fallbacks)
         return chain, chain_lnl, dict(_stats_dict(stats), per_ensemble=per)
+
+    def chain_store(self, E, W, n, capacity):
+        """A :class:`ChainStore` on this engine's device: ``capacity`` rows of E ensembles of W walkers over n columns."""
+        return ChainStore(self, E, W, n, capacity)
+
+    def attach_chain_store(self, store=None):
+        """While ``store`` is attached, every ``ensemble_run*`` call appends the rows it records to it on the device (include/vegamx.h:
+        vmx_ensemble_set_chain_store) - with ``keep_chain=False`` nothing of the chain crosses to the host.  None detaches."""
+        if store is not None and store.engine is not self:
+            raise ValueError('the chain store belongs to another engine')
+        self._check(self.lib.vmx_ensemble_set_chain_store(self._h, None if store is None else store._handle()))
+        self._attached = store
 
     def ensemble_cov_factor(self, x):
         """The factor stage of the covariance move alone (include/vegamx.h: vmx_ensemble_cov_factor): the halves ``x`` [E, H, n] give

@@ -1186,6 +1186,77 @@ def integrated_time(chain, c=5):
     return tau
 
 
+# ------------------------------------------------------------------ the summary of a chain (vmx_chain.h, restated)
+CHAIN_MAX_WALKERS = 1024
+CHAIN_LAG_BLOCK = 32
+SUMMARY_KEYS = ('count', 'mean', 'sd', 'covariance', 'tau', 'window', 'n_eff')
+
+
+def _seq_sum(a):
+    """The sum over the first axis in index order, one rounded addition per term (vmx_chain::seq_sum)."""
+    return np.add.accumulate(a, axis=0)[-1]
+
+
+def _chain_summary_one(x, c, lag_block, moments=True):
+    T, W, n = x.shape
+    count = T * W
+    S = _seq_sum(x)                                                 # [W, n] the series sums
+    m = S / float(T)                                                # the series' own means
+    if moments:
+        mean = _seq_sum(S) / float(count)
+        y = x - mean
+        cov = np.empty((n, n))
+        for i in range(n):
+            cov[i] = _seq_sum(_seq_sum(y[:, :, i, None] * y)) / np.float64(count - 1)
+    tau, window = np.empty(n), np.empty(n, dtype=np.int64)
+    cen = np.ascontiguousarray(np.moveaxis(x - m, 2, 0))            # [n, T, W] the centred series
+    for d in range(n):
+        s = cen[d]
+        acov0 = _seq_sum(s * s)                                      # [W]
+        flat = acov0 == 0.0
+        cumulative, lag, closed = 0.0, 0, False
+        while not closed:
+            for l in range(lag, min(lag + lag_block, T)):
+                acov = acov0 if l == 0 else _seq_sum(s[:T - l] * s[l:])
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    rho = np.where(flat, acov, acov / acov0)
+                f = _seq_sum(rho) / float(W)
+                cumulative = f if l == 0 else cumulative + f
+                taus = 2.0 * cumulative - 1.0
+                if not (float(l) < c * taus) or l == T - 1:
+                    tau[d], window[d], closed = taus, l, True
+                    break
+            lag += lag_block
+    with np.errstate(divide='ignore', invalid='ignore'):
+        n_eff = np.float64(count) / np.max(tau)
+    if not moments:
+        return dict(count=count, tau=tau, window=window, n_eff=n_eff)
+    return dict(count=count, mean=mean, sd=np.sqrt(np.diagonal(cov)), covariance=cov, tau=tau, window=window, n_eff=n_eff)
+
+
+def chain_summary(chain, first=0, c=5, lag_block=CHAIN_LAG_BLOCK, moments=True):
+    """The summary of a recorded chain [rows, W, n] (or [E, rows, W, n]: every ensemble's, stacked) over the rows from ``first``
+    on, as vmx_chain_store_summary computes it where the chain is recorded - vega_amd/csrc/vmx_chain.h restated, bit for bit:
+    ``dict(count, mean [n], sd [n], covariance [n, n], tau [n], window [n], n_eff)``.  mean / covariance: two passes, ddof = 1
+    over rows x walkers (``np.cov``); tau / window: emcee's estimator (:func:`integrated_time`) with direct lag sums up to Sokal's
+    window M >= c tau, every sum sequential in its index; sd = sqrt(diag covariance), n_eff = count / max tau.  ``lag_block``
+    (the lags computed at a time) changes no bit; without ``moments`` mean, sd and covariance are neither computed nor
+    returned.  W >= 2 makes count - 1 >= 1 even for a single row (then tau = -1 and window = 0, as ``integrated_time`` gives)."""
+    x = np.asarray(chain, dtype=np.float64)
+    if x.ndim not in (3, 4) or x.shape[-1] < 1 or x.shape[-2] < 2:
+        raise ValueError('chain [rows, W, n] or [E, rows, W, n], W >= 2')
+    first, c, lag_block = int(first), float(c), int(lag_block)
+    rows = x.shape[-3]
+    if not 0 <= first < rows:
+        raise ValueError(f'first: a recorded row, 0 .. {rows - 1} (the summary needs at least one row)')
+    if not (c > 0.0 and np.isfinite(c)) or lag_block < 1:
+        raise ValueError('c positive and finite, lag_block >= 1')
+    if x.ndim == 3:
+        return _chain_summary_one(x[first:], c, lag_block, moments)
+    parts = [_chain_summary_one(xe[first:], c, lag_block, moments) for xe in x]
+    return {key: np.array([p[key] for p in parts]) for key in parts[0]}
+
+
 # ------------------------------------------------------------------ what every sampler here sets up the same way
 _NO_LIMITS = ('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
               ' just say par_name = True to use defaults.')
@@ -1411,9 +1482,14 @@ class StretchSampler(EngineSampler):
     _lead = ()
 
     def _setup_walkers(self, vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves=None,
-                       gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None, cov_scale=None):
+                       gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None, cov_scale=None, chain='host'):
         self.n = self._setup_engine(vega, sample_params, driver, chunk, lanes, const_hint)
+        if chain not in ('host', 'device'):
+            raise ValueError("chain: 'host' or 'device'")
+        self.chain_mode, self._store, self.convergence, self._fetched = chain, None, None, {}
         self.W = int(walkers)
+        if chain == 'device' and self.W > CHAIN_MAX_WALKERS:
+            raise ValueError(f"chain='device': at most {CHAIN_MAX_WALKERS} walkers")
         if self.W % 2 or self.W < 2 * self.n:
             raise ValueError(f'walkers: an even number, at least twice the {self.n} sampled parameters')
         self.a, self.seed = float(a), int(seed)
@@ -1441,6 +1517,8 @@ class StretchSampler(EngineSampler):
         self.accepted = np.zeros(self._lead + (self.W,), dtype=np.int64)
         self.step = 0
         self._chain, self._chain_lnl = [], []
+        self._drop_store()
+        self.convergence = None
         self.stats = dict(steps=0, proposals=0, accepted=0, rejected_outside_box=0, rejected_failed_model=0, engine_calls=0,
                           seconds=0.0, seconds_enqueuing=0.0, host_synchronisations=0, calls=0)
         if self.moves is not None:
@@ -1483,8 +1561,8 @@ class StretchSampler(EngineSampler):
         counts = np.zeros((lead, nm, 2), dtype=np.int64)
         if self.step > 0:
             axis = len(self._lead)
-            rows = np.concatenate(self._chain, axis=axis).reshape(lead, -1, self.W, self.n)
-            rows_lnl = np.concatenate(self._chain_lnl, axis=axis).reshape(lead, -1, self.W)
+            rows = np.concatenate(self._recorded(), axis=axis).reshape(lead, -1, self.W, self.n)
+            rows_lnl = np.concatenate(self._recorded(lnl=True), axis=axis).reshape(lead, -1, self.W)
             start, start_lnl = (a.reshape((lead, 1) + a.shape[axis:]) for a in self._start)
             for e in range(lead):
                 move = steps_moves(H, 0, self.step, self.seed, int(streams[e]), self.moves)         # [steps, W]
@@ -1499,15 +1577,167 @@ class StretchSampler(EngineSampler):
         """Advance by ``n_steps`` steps.  The first call draws the start, as the class's ``_start_positions`` says: ``'ball'``,
         ``'prior'`` or an array; later calls continue the chain."""
         theta = self._prepare(start, init_scale)
+        try:
+            self._open_store(int(n_steps))
+            self._advance(theta, int(n_steps))
+        finally:
+            if self._store is not None:
+                self.vega.engine.attach_chain_store(None)
+        return self
+
+    # ---- the recorded rows: a list of host blocks, or - chain='device' with the device driver - a store on the device
+    def _rows_in_store(self):
+        return self.chain_mode == 'device' and self.driver == 'device'
+
+    def _open_store(self, n_steps):
+        """Ahead of a run of ``n_steps`` steps with the rows on the device: the store, with room for the rows the run adds (sized from
+        the first run's steps, grown by ``reserve`` on later calls), attached to the engine for the run."""
+        if not self._rows_in_store():
+            return
+        eng = self.vega.engine
+        need = (self.step + n_steps) // self.thin
+        if self._store is not None and self._store.engine is not eng:
+            raise RuntimeError("chain='device': the engine was replaced after rows were recorded on it")
+        if self._store is None:
+            self._store = eng.chain_store(int(np.prod(self._lead, dtype=np.int64)), self.W, self.n, need)
+        else:
+            self._store.reserve(need)
+        self._fetched = {}
+        eng.attach_chain_store(self._store)
+
+    def _drop_store(self):
+        store, self._store = getattr(self, '_store', None), None
+        self._fetched = {}
+        if store is not None:
+            store.close()
+
+    def close(self):
+        """Release the chain store of ``chain='device'``: a sampler that has run owns its recorded rows on the device (with
+        ``sample_mocks(summaries='device')`` the whole chain of every mock) until it is closed, reset or collected.  The rows are
+        brought to the host first, so ``get_chain``, ``summary`` and the moves' counters keep answering - from the host rows,
+        the same numbers; ``keep=False`` drops the rows instead (then those raise or return nothing)."""
+        return self._close(True)
+
+    def _close(self, keep):
+        if self._store is not None:
+            if keep and self._store.rows > 0:
+                chain, chain_lnl = self._store.fetch()
+                self._chain, self._chain_lnl = ([chain], [chain_lnl]) if self._lead else ([chain[0]], [chain_lnl[0]])
+            self._drop_store()
+        return self
+
+    def discard_chain(self):
+        """Release the chain store without bringing its rows to the host: the summaries already taken are all that is kept."""
+        return self._close(False)
+
+    def _recorded(self, lnl=False):
+        """The recorded blocks, positions or lnL: the host list, or the store's rows fetched as one block."""
+        if self._store is None or self._store.rows == 0:
+            return self._chain_lnl if lnl else self._chain
+        # (fetched once per state of the store: the members of a set slice one copy instead of fetching the whole store each)
+        rows = self._store.rows
+        held = self._fetched.get(lnl)
+        if held is None or held[0] != rows:
+            arr = self._store.fetch(lnl=True)[1] if lnl else self._store.fetch(lnl=False)[0]
+            held = self._fetched[lnl] = (rows, arr if self._lead else arr[0])
+        return [held[1]]
+
+    def _recorded_count(self):
+        """Rows recorded so far, per ensemble."""
+        if self._store is not None:
+            return self._store.rows
+        return sum(part.shape[len(self._lead)] for part in self._chain_lnl)
+
+    def summary(self, discard=0, c=5):
+        """``dict(count, mean, sd, covariance, tau, window, n_eff)`` of the recorded rows from ``discard`` on (per ensemble for a
+        set: arrays with a leading E): mean and covariance (ddof 1) over rows x walkers, emcee's integrated autocorrelation time
+        with its window, n_eff = count / max tau.  With the rows on the device (``chain='device'``, device driver) it is computed
+        there (vmx_chain_store_summary) and a few numbers per ensemble cross to the host; otherwise it is
+        :func:`chain_summary` over the host rows - the same numbers bit for bit."""
+        if self._store is not None:
+            out = self._store.summary(int(discard), c)
+            return out if self._lead else {key: (val[0].item() if val[0].ndim == 0 else val[0]) for key, val in out.items()}
+        axis = len(self._lead)
+        parts = self._chain
+        if not parts:
+            raise ValueError('summary: no recorded rows')
+        out = chain_summary(np.concatenate(parts, axis=axis), int(discard), c)
+        if not self._lead:
+            out['n_eff'] = float(out['n_eff'])
+        return out
+
+    def _tau_now(self, discard, c):
+        """tau [(E,) n] and the rows used of the check of :meth:`run_until`: E n doubles from the device."""
+        if self._store is not None:
+            tau = self._store.summary(int(discard), c, moments=False)['tau']
+            return tau if self._lead else tau[0]
+        axis = len(self._lead)         # (the rows behind the burn-in alone are stacked, and the moments are skipped)
+        done, parts = 0, []
+        for part in self._chain:
+            rows = part.shape[axis]
+            if done + rows > discard:
+                parts.append(part[(slice(None),) * axis + (slice(max(discard - done, 0), None),)])
+            done += rows
+        return chain_summary(np.concatenate(parts, axis=axis), 0, c, moments=False)['tau']
+
+    def run_until(self, max_steps, tau_factor=50, tau_rtol=0.01, check_every=100, burn=1.0 / 3.0, c=5, start='ball', init_scale=1.0):
+        """Advance until the chain is long enough by its own integrated autocorrelation time (emcee's recipe), at most
+        ``max_steps`` steps: after every ``check_every`` steps tau is estimated over the recorded rows behind the first
+        floor(``burn`` rows); an ensemble is converged at a check when rows_used >= ``tau_factor`` max_d tau and max_d |tau -
+        tau_previous| / tau <= ``tau_rtol``.  The run ends at the first check at which every ensemble is converged (all
+        ensembles advance together until then), or at ``max_steps``.  ``convergence`` keeps ``dict(steps [checks], tau [checks,
+        (E,) n], rows_used [checks], converged [(E,)], converged_at [(E,)]: the step of the first check at which the ensemble
+        held, -1 if never)``.  The decision is host arithmetic over numbers both drivers produce bit for bit: both stop at the
+        same step."""
+        max_steps, check_every = int(max_steps), int(check_every)
+        tau_factor, tau_rtol, burn = float(tau_factor), float(tau_rtol), float(burn)
+        if max_steps < 1 or check_every < 1:
+            raise ValueError('run_until: max_steps >= 1, check_every >= 1')
+        if not (tau_factor > 0.0 and np.isfinite(tau_factor)) or not (tau_rtol >= 0.0 and np.isfinite(tau_rtol)):
+            raise ValueError('run_until: tau_factor positive, tau_rtol not negative, both finite')
+        if not 0.0 <= burn < 1.0:
+            raise ValueError('run_until: burn in [0, 1)')
+        lead = self._lead
+        steps, taus, used = [], [], []
+        converged, at = np.zeros(lead, dtype=bool), np.full(lead, -1, dtype=np.int64)
+        previous, done = None, 0
+        while done < max_steps:
+            k = min(check_every, max_steps - done)
+            self.run(k, start=start, init_scale=init_scale)
+            done += k
+            rows = self._recorded_count()
+            if rows < 1:
+                continue
+            discard = int(np.floor(burn * rows))
+            tau = np.asarray(self._tau_now(discard, c), dtype=np.float64)
+            steps.append(self.step), taus.append(tau), used.append(rows - discard)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                worst = np.max(tau, axis=-1)
+                long_enough = (rows - discard) >= tau_factor * worst
+                settled = np.max(np.abs(tau - previous) / tau, axis=-1) <= tau_rtol if previous is not None else np.zeros(lead, dtype=bool)
+            converged = np.asarray(long_enough & settled & np.all(np.isfinite(tau) & (tau > 0.0), axis=-1))
+            at = np.where((at < 0) & converged, self.step, at)
+            previous = tau
+            if np.all(converged):
+                break
+        self.convergence = dict(steps=np.array(steps, dtype=np.int64), tau=np.array(taus).reshape((len(taus),) + lead + (self.n,)),
+                                rows_used=np.array(used, dtype=np.int64), converged=converged if lead else bool(converged),
+                                converged_at=at if lead else int(at), max_steps=max_steps, tau_factor=tau_factor, tau_rtol=tau_rtol,
+                                check_every=check_every, burn=burn)
+        return self
+
+    def _advance(self, theta, n_steps):
         done = 0
+        on_device = self._store is not None
         while done < n_steps:
             k = min(self.segment, n_steps - done)
             segment = self._segment_device if self.driver == 'device' else self._segment_python
             if self.moves is not None and self._start is None:
                 self._start = (self.x.copy(), self.lnl.copy())
             chain, chain_lnl, st, *per = segment(theta, k)
-            self._chain.append(chain)
-            self._chain_lnl.append(chain_lnl)
+            if not on_device:
+                self._chain.append(chain)
+                self._chain_lnl.append(chain_lnl)
             if per:             # (a set's segment: the counters of every ensemble)
                 self.per_ensemble += per[0]
             for key in st:
@@ -1521,7 +1751,10 @@ class StretchSampler(EngineSampler):
             self.stats['calls'] += 1
             self.step += k
             done += k
-        return self
+
+    def _keep_arg(self):
+        # (with the rows in a store the library is asked for no host chain; otherwise the methods are called as ever)
+        return dict(keep_chain=False) if self._store is not None else {}
 
     def _segment_python(self, theta, k):
         """The readable restatement: proposals and decisions in NumPy (``_python_steps``), chi2 of a half's rows through
@@ -1583,9 +1816,9 @@ class EnsembleSampler(StretchSampler):
 
     def __init__(self, vega, walkers, a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, stream=0,
                  chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None, tune_steps=None,
-                 cov_scale=None):
+                 cov_scale=None, chain='host'):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s, mu, tune_steps, cov_scale)
+                            sigma, gamma_s, mu, tune_steps, cov_scale, chain)
         self.stream = int(stream)
         self.reset()
 
@@ -1644,12 +1877,12 @@ class EnsembleSampler(StretchSampler):
             chain, chain_lnl, st = self.vega.engine.ensemble_run_slice(
                 self.cols, self.lo, self.hi, theta, self.x[None], self.lnl[None], self.accepted[None], [self.stream], self.mu,
                 self.step, k, thin=self.thin, log_norm=self.log_norm(), seed=self.seed, const_hint=self.const_hint,
-                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg())
-            return chain[0], chain_lnl[0], st
+                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg(), **self._keep_arg())
+            return (None, None, st) if chain is None else (chain[0], chain_lnl[0], st)
         chain, chain_lnl, st = self.vega.engine.ensemble_run(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.step, k, thin=self.thin, a=self.a,
             log_norm=self.log_norm(), seed=self.seed, stream=self.stream, const_hint=self.const_hint, chunk=self.chunk,
-            lanes=self.lanes, **self._moves_arg())
+            lanes=self.lanes, **self._moves_arg(), **self._keep_arg())
         return chain, chain_lnl, st
 
     def _python_steps(self, k, chi2):
@@ -1663,10 +1896,12 @@ class EnsembleSampler(StretchSampler):
 
     # ---- results
     def _stack(self, parts, discard, thin, flat):
+        lnl = parts is self._chain_lnl
+        parts = self._recorded(lnl)
         if parts:
             arr = np.concatenate(parts)
         else:
-            arr = np.empty((0, self.W) + ((self.n,) if parts is self._chain else ()))
+            arr = np.empty((0, self.W) + (() if lnl else (self.n,)))
         arr = arr[int(discard)::int(thin)]
         return arr.reshape((-1,) + arr.shape[2:]) if flat else arr
 
@@ -1715,9 +1950,9 @@ class EnsembleSet(StretchSampler):
 
     def __init__(self, vega, ensembles, walkers, streams=None, mock_rows=None, a=2.0, seed=0, thin=1, driver='device', segment=1000,
                  sample_params=None, chunk=0, lanes=0, const_hint=-1, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                 tune_steps=None, cov_scale=None):
+                 tune_steps=None, cov_scale=None, chain='host'):
         self._setup_walkers(vega, walkers, a, seed, thin, driver, segment, sample_params, chunk, lanes, const_hint, moves, gamma0,
-                            sigma, gamma_s, mu, tune_steps, cov_scale)
+                            sigma, gamma_s, mu, tune_steps, cov_scale, chain)
         self.E = int(ensembles)
         if self.E < 1:
             raise ValueError('ensembles: at least one')
@@ -1792,12 +2027,12 @@ class EnsembleSet(StretchSampler):
             chain, chain_lnl, st = self.vega.engine.ensemble_run_slice(
                 self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.mu, self.step, k,
                 mock_rows=self.mock_rows, thin=self.thin, log_norm=self.log_norm(), seed=self.seed, const_hint=self.const_hint,
-                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg())
+                chunk=self.chunk, lanes=self.lanes, mu0=self.slice['mu0'], **self._slice_arg(), **self._keep_arg())
             return chain, chain_lnl, st, self._slice_per(st)
         chain, chain_lnl, st = self.vega.engine.ensemble_run_many(
             self.cols, self.lo, self.hi, theta, self.x, self.lnl, self.accepted, self.streams, self.step, k,
             mock_rows=self.mock_rows, thin=self.thin, a=self.a, log_norm=self.log_norm(), seed=self.seed,
-            const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, **self._moves_arg())
+            const_hint=self.const_hint, chunk=self.chunk, lanes=self.lanes, **self._moves_arg(), **self._keep_arg())
         return chain, chain_lnl, st, st.pop('per_ensemble')
 
     @staticmethod
@@ -1820,6 +2055,7 @@ class EnsembleSet(StretchSampler):
 
     # ---- results
     def _stack(self, parts, tail, discard, thin, flat):
+        parts = self._recorded(lnl=parts is self._chain_lnl)
         arr = np.concatenate(parts, axis=1) if parts else np.empty((self.E, 0, self.W) + tail)
         arr = arr[:, int(discard)::int(thin)]
         return arr.reshape((self.E, -1) + arr.shape[3:]) if flat else arr
@@ -1851,8 +2087,8 @@ class EnsembleSet(StretchSampler):
         if self.x is not None:
             m.x, m.lnl = self.x[e].copy(), self.lnl[e].copy()
         m.accepted, m.step = self.accepted[e].copy(), self.step
-        m._chain[:] = [part[e] for part in self._chain]
-        m._chain_lnl[:] = [part[e] for part in self._chain_lnl]
+        m._chain[:] = [part[e] for part in self._recorded()]
+        m._chain_lnl[:] = [part[e] for part in self._recorded(lnl=True)]
         took, out, bad = (int(v) for v in self.per_ensemble[e])
         m.stats = dict(self.stats, proposals=self.step * self.W, accepted=took, rejected_outside_box=out, rejected_failed_model=bad)
         if self.moves is not None:
@@ -1948,7 +2184,9 @@ class TemperedEnsemble(EnsembleSet):
     def __init__(self, vega, walkers, ntemps=None, betas=None, swap_every=1, ladders=1, streams=None, mock_rows=None, beta_min=None,
                  a=2.0, seed=0, thin=1, driver='device', segment=1000, sample_params=None, chunk=0, lanes=0, const_hint=-1,
                  moves=None, gamma0=None, sigma=None, gamma_s=None, adapt=False, adapt_steps=None, adaptation_lag=10000,
-                 adaptation_time=100):
+                 adaptation_time=100, chain='host'):
+        if chain != 'host':
+            raise ValueError("chain: a temperature ladder keeps its rows on the host (chain='host'); the store is for the untempered runs")
         if _names_slice(moves):
             raise ValueError("moves: 'slice' does not combine with parallel tempering (ntemps / betas)")
         if names_cov(moves):
@@ -2104,6 +2342,12 @@ class TemperedEnsemble(EnsembleSet):
     @property
     def recorded_rows(self):
         return sum(part.shape[1] for part in self._chain_lnl)
+
+    def run_until(self, *args, **kwargs):
+        raise ValueError('run_until: the convergence stop is for the untempered runs; a temperature ladder runs its steps')
+
+    def summary(self, *args, **kwargs):
+        raise ValueError('summary: per rung, chain_summary(run.get_chain(rung=...))')
 
     @property
     def swap_fraction(self):
@@ -2291,6 +2535,61 @@ def sampler_settings(main_config, sample_params):
         except ValueError:
             raise ValueError('[Ensemble] together: True or False') from None
     _parse_tempering(sec, out)
+    _parse_converge(sec, out)
+    return out
+
+
+_CONVERGE_KEYS = ('tau_factor', 'tau_rtol', 'check_every')
+
+
+def _parse_converge(sec, out):
+    """``converge = True`` of ``[Ensemble]``: the run stops by its own integrated autocorrelation times
+    (:meth:`StretchSampler.run_until`, ``steps`` the maximum), with ``tau_factor``, ``tau_rtol`` and ``check_every`` when stated,
+    into ``out['converge']`` - a dict of the stated ones.  Without ``converge`` nothing is added.  Not combined with ``ntemps``;
+    ``replicas > 1`` need ``together = True`` (the set stops as one)."""
+    stated = [key for key in _CONVERGE_KEYS if key in sec]
+    if 'converge' not in sec:
+        if stated:
+            raise ValueError(f'[Ensemble] {", ".join(stated)}: settings of the convergence stop, but no converge')
+        return
+    try:
+        on = sec.getboolean('converge')
+    except ValueError:
+        raise ValueError('[Ensemble] converge: True or False') from None
+    if not on:
+        if stated:
+            raise ValueError(f'[Ensemble] {", ".join(stated)}: settings of the convergence stop, but converge is not True')
+        return
+    if 'ntemps' in sec:
+        raise ValueError('[Ensemble] converge and ntemps do not combine yet')
+    if out.get('replicas', 1) > 1 and not out.get('together', False):
+        raise ValueError('[Ensemble] converge with replicas > 1 needs together = True: the set stops as one')
+    conv = {}
+    try:
+        for key in ('tau_factor', 'tau_rtol'):
+            if key in sec:
+                conv[key] = sec.getfloat(key)
+        if 'check_every' in sec:
+            conv['check_every'] = sec.getint('check_every')
+    except ValueError:
+        raise ValueError('[Ensemble] tau_factor, tau_rtol: numbers; check_every: a whole number') from None
+    for key, value in conv.items():
+        if not (value > 0 and np.isfinite(value)):
+            raise ValueError(f'[Ensemble] {key} must be positive')
+    out['converge'] = conv
+
+
+def write_convergence(sampler, path, name):
+    """``name.convergence`` beside the chain files: one line per check of :meth:`StretchSampler.run_until` - the step, then tau
+    per sampled parameter (a set: the worst member's) - and a last line ``converged = True|False``.  Returns the path."""
+    conv = sampler.convergence
+    lines = ['# step ' + ' '.join(sampler.names)]
+    for step, tau in zip(conv['steps'], conv['tau']):
+        worst = np.max(tau.reshape(-1, tau.shape[-1]), axis=0)
+        lines.append(f'{int(step)} ' + ' '.join(f'{v:.17g}' for v in worst))
+    lines.append(f'converged = {bool(np.all(conv["converged"]))}')
+    out = Path(path) / f'{name}.convergence'
+    out.write_text('\n'.join(lines) + '\n')
     return out
 
 
@@ -2472,6 +2771,12 @@ def _parse_mocks(sec, main_config, section='Ensemble', own='an ensemble'):
     return M
 
 
+def chain_arguments(cfg):
+    """``chain='device'`` for the settings that stop by convergence - the checks then read a few numbers per ensemble instead of
+    the chain; empty otherwise, so that a run without ``converge`` is constructed as ever."""
+    return dict(chain='device') if 'converge' in cfg else {}
+
+
 def build_sampler(vega, cfg, sample_params, stream=0):
     """The sampler the settings ``cfg`` (:func:`sampler_settings`) ask for, on the Philox stream ``stream``."""
     if cfg['sampler'] == 'Nested':
@@ -2492,13 +2797,15 @@ def build_sampler(vega, cfg, sample_params, stream=0):
                                 sample_params=sample_params, **moves_arguments(cfg),
                                 **{key: cfg[key] for key in _ADAPT_KEYS if key in cfg})
     return EnsembleSampler(vega, cfg['walkers'], a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'], driver=cfg['driver'],
-                           sample_params=sample_params, stream=stream, **moves_arguments(cfg))
+                           sample_params=sample_params, stream=stream, **moves_arguments(cfg), **chain_arguments(cfg))
 
 
 def advance_sampler(sampler, cfg):
     """Run a sampler of :func:`build_sampler` as its settings say: the ensemble its steps, the others to their end."""
     if cfg['sampler'] in ('Nested', 'SMC'):
         return sampler.run()
+    if 'converge' in cfg:
+        return sampler.run_until(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'], **cfg['converge'])
     return sampler.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
 
 
@@ -2561,6 +2868,8 @@ def run_vega_sampler(config_path, search_dirs=(), print_func=print, rank=None, w
             log_z, err = sampler.log_evidence()
             print_func(f'log(Z) = {log_z} +- {err}')
         sampler.write(cfg['path'], cfg['name'], derived=cfg.get('derived', False), print_func=print_func)
+        if 'converge' in cfg:
+            write_convergence(sampler, cfg['path'], cfg['name'])
     group.barrier()
     print_func('Finished running sampler')
     return sampler
@@ -2599,7 +2908,10 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
         mc.write_mock_posteriors(cfg['path'])
         return sampler
     sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],
-                              scale=scale, sample_params=sample_params, driver=cfg['driver'], **moves_arguments(cfg))
+                              scale=scale, sample_params=sample_params, driver=cfg['driver'], **moves_arguments(cfg),
+                              **(dict(summaries='device', converge=cfg['converge']) if 'converge' in cfg else {}))
+    if 'converge' in cfg:
+        write_convergence(sampler, cfg['path'], cfg['name'])
     chain, lnl = sampler.get_chain(), sampler.get_log_lik()
     for m in range(sampler.E):
         table, lines = getdist_table(sampler.names, chain[m], lnl[m])

@@ -471,7 +471,7 @@ class MonteCarlo:
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
                      ess=0.5, sweeps=None, n_total=None, recycle=False, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                     tune_steps=None, cov_scale=None):
+                     tune_steps=None, cov_scale=None, summaries='host', converge=None):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -487,6 +487,15 @@ class MonteCarlo:
         ``cov_fallbacks`` [M], every mock's factor fallbacks, and the table a column of that name; ``moves='slice'`` with ``mu`` / ``tune_steps``: ensemble
         slice sampling, whose ``burn`` should cover ``tune_steps``); with ``keep_chains`` also ``mc_chains`` [M, rows, W, n] and
         ``mc_chain_lnl``.  Returns the set.
+
+        ``summaries='device'``: the set runs with ``chain='device'`` - the recorded rows stay in a chain store on the device and
+        ``mean`` / ``sd`` / ``covariance`` / ``tau`` / ``n_eff`` come from its summary (vmx_chain_store_summary;
+        :func:`vega_amd.ensemble.chain_summary` is the same numbers), a few hundred bytes per mock; with ``keep_chains=False`` no
+        chain is ever copied to the host.  ``'host'`` (default): the summaries of ever, NumPy over the whole chain.
+        ``converge=dict(tau_factor=, tau_rtol=, check_every=)`` (any subset): the set stops by its own autocorrelation times
+        (:meth:`vega_amd.ensemble.StretchSampler.run_until`) with ``steps`` as the maximum; ``mc_posteriors`` gains ``converged``
+        and ``converged_at`` [M] and the table two columns of those names, ``steps`` is the steps run, and a ``burn`` left to
+        the default is a third of them.
 
         ``sampler='smc'``: the evidence and an equal-weight posterior of every mock instead, M tempered SMC runs advanced together
         (:class:`vega_amd.smc.SMCSet`: run m on mock m and stream m, ``particles`` - default 1024 - ``ess`` and ``sweeps`` its
@@ -508,8 +517,15 @@ class MonteCarlo:
                     if v is not None}
         if sampler != 'ensemble' and moves_kw:
             raise ValueError("sample_mocks: moves go with sampler='ensemble'")
+        if summaries not in ('host', 'device'):
+            raise ValueError("sample_mocks: summaries 'host' or 'device'")
+        if sampler != 'ensemble' and (summaries != 'host' or converge is not None):
+            raise ValueError("sample_mocks: summaries and converge go with sampler='ensemble'")
+        if converge is not None and set(converge) - {'tau_factor', 'tau_rtol', 'check_every'}:
+            raise ValueError('sample_mocks: converge takes tau_factor, tau_rtol and check_every')
         return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
-                                  fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle, moves_kw=moves_kw)
+                                  fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle, moves_kw=moves_kw,
+                                  summaries=summaries, converge=converge)
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
@@ -531,7 +547,8 @@ class MonteCarlo:
 
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
-                      max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False, moves_kw=None):
+                      max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False, moves_kw=None, summaries='host',
+                      converge=None):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -561,6 +578,7 @@ class MonteCarlo:
         if not smc and not nested:
             walkers = max(32, 2 * n) if walkers is None else int(walkers)
             steps, thin = int(steps), int(thin)
+            burn_given = burn is not None
             burn = steps // 3 if burn is None else int(burn)
             if not 0 <= burn < steps:
                 raise ValueError('sample_mocks: 0 <= burn < steps')
@@ -579,7 +597,8 @@ class MonteCarlo:
                                 **({'boost_posterior': boost_posterior} if boost_posterior else {}))
         else:
             sampler = EnsembleSet(vega, M, walkers, mock_rows=np.arange(M), seed=seed, thin=thin, driver=driver,
-                                  sample_params=sample_params, **(moves_kw or {}))
+                                  sample_params=sample_params, **(moves_kw or {}),
+                                  **(dict(chain='device') if summaries == 'device' else {}))
         try:
             for name, pool in mocks.items():
                 eng.set_mock_pool(name, pool)
@@ -588,6 +607,8 @@ class MonteCarlo:
                 eng.set_invcov(name, prob.items[name].chi2_matrix / scales[name])
             if smc or nested:
                 sampler.run()
+            elif converge is not None:
+                sampler.run_until(steps, **converge)
             else:
                 sampler.run(steps)
         finally:
@@ -652,15 +673,27 @@ class MonteCarlo:
             self.mc_chains = found if keep_chains else None
             self.mc_chain_lnl = [None if part is None else part[1] for part in found] if keep_chains else None
             return sampler
+        if converge is not None:            # (the run may have stopped early: the steps run, and the burn-in that goes with them)
+            steps = sampler.step
+            burn = min(burn, steps - 1) if burn_given else steps // 3
         first = burn // thin
-        post = sampler.get_chain(discard=first)
-        flat = post.reshape(M, -1, n)
-        tau = sampler.get_autocorr_time(discard=first)
+        if summaries == 'device':
+            summ = sampler.summary(discard=first)
+            moments = dict(mean=summ['mean'], sd=summ['sd'], covariance=summ['covariance'], tau=summ['tau'], n_eff=summ['n_eff'])
+        else:
+            post = sampler.get_chain(discard=first)
+            flat = post.reshape(M, -1, n)
+            tau = sampler.get_autocorr_time(discard=first)
+            moments = dict(mean=flat.mean(axis=1), sd=flat.std(axis=1, ddof=1),
+                           covariance=np.array([np.atleast_2d(np.cov(rows.T)) for rows in flat]), tau=tau,
+                           n_eff=flat.shape[1] / tau.max(axis=1))
         self.mc_posteriors = dict(
-            names=list(sampler.names), mean=flat.mean(axis=1), sd=flat.std(axis=1, ddof=1),
-            covariance=np.array([np.atleast_2d(np.cov(rows.T)) for rows in flat]), tau=tau,
-            acceptance=sampler.acceptance_fraction.mean(axis=1), n_eff=flat.shape[1] / tau.max(axis=1),
+            names=list(sampler.names), mean=moments['mean'], sd=moments['sd'], covariance=moments['covariance'], tau=moments['tau'],
+            acceptance=sampler.acceptance_fraction.mean(axis=1), n_eff=moments['n_eff'],
             steps=steps, burn=burn, thin=thin, walkers=walkers, seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+        if converge is not None:
+            self.mc_posteriors.update(converged=np.asarray(sampler.convergence['converged']).copy(),
+                                      converged_at=np.asarray(sampler.convergence['converged_at']).copy())
         if sampler.moves is not None:       # (without moves the dict has the keys it had)
             self.mc_posteriors['moves'] = dict(sampler.moves)
             if len(sampler.moves['weights']) == 4:      # (the covariance move: every mock's factor fallbacks)
@@ -674,7 +707,8 @@ class MonteCarlo:
     def write_mock_posteriors(self, directory, cpu_id=None, overwrite=True):
         """`mock_posteriors[_<cpu_id>].fits` under ``directory``: one table ``POSTERIORS`` with one row per mock of
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
-        ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header.  After
+        ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header (after
+        ``sample_mocks(converge=...)`` also the columns ``converged`` and ``converged_at``).  After
         ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
         ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED`` (with ``n_total`` or
         ``recycle`` also the columns ``points``, ``n_eff``, ``log_z_recycled`` and the header keys ``NTOTAL`` and ``RECYCLE``); after
@@ -721,6 +755,9 @@ class MonteCarlo:
             cols += [('acceptance', 'D', post['acceptance']), ('n_eff', 'D', post['n_eff']), cov_col]
             if 'cov_fallbacks' in post:
                 cols += [('cov_fallbacks', 'K', np.asarray(post['cov_fallbacks'], dtype=np.int64))]
+            if 'converged' in post:
+                cols += [('converged', 'K', np.asarray(post['converged'], dtype=np.int64)),
+                         ('converged_at', 'K', np.asarray(post['converged_at'], dtype=np.int64))]
             header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)

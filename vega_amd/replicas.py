@@ -572,8 +572,10 @@ def run_replicas(vega, cfg, sample_params, group, print_func=print):
     if cfg.get('together', False) and cfg['sampler'] == 'Ensemble' and hi > lo:
         # the rank's replicas as one set: their half-steps decided together, their rows one stream of full batches for the engine
         both = E.EnsembleSet(vega, hi - lo, cfg['walkers'], streams=range(lo, hi), a=cfg['a'], seed=cfg['seed'], thin=cfg['thin'],
-                             driver=cfg['driver'], sample_params=sample_params, **E.moves_arguments(cfg))
-        both.run(cfg['steps'], start=cfg['init'], init_scale=cfg['init_scale'])
+                             driver=cfg['driver'], sample_params=sample_params, **E.moves_arguments(cfg), **E.chain_arguments(cfg))
+        E.advance_sampler(both, cfg)
+        if 'converge' in cfg:       # (the rank's set stops as one: its record beside the chain files)
+            E.write_convergence(both, cfg['path'], cfg['name'] if group.world == 1 else f'{cfg["name"]}_rank{group.rank}')
         ready = [both.member(k) for k in range(hi - lo)]
     if cfg.get('together', False) and cfg['sampler'] == 'SMC' and hi > lo:
         # the rank's replicas as one set: one host round per stage for all of them, their rows one stream of full batches
