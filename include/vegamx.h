@@ -1123,7 +1123,10 @@ int vmx_set_quadratic_form(vmx_engine* e, const double* theta_ref);
  * data grid (2500 / 5000 bins against 1590 / 3180 fitted ones), the factored form when the model grid is much finer (a
  * `distortion-file` with COEFMOD >= 2, reference vega/data.py:441-473: nq = 10 000 against 1590); 1: Q'; 2: the factored form.
  * The two agree to rounding (the sum of squares has no cancellation at all); vmx_debug_read(what = 4)[8] reports the form the last
- * evaluation took (0: full chain, 1: Q', 2: factored).  After vmx_finalize; the tensors are rebuilt at the next chi2-only call. */
+ * evaluation took (0: full chain, 1: Q', 2: factored).  After vmx_finalize; the tensors are rebuilt at the next chi2-only call.
+ * Within the Q' form, batches of more than 8 walkers may take the quadratic term alone as || L dx ||^2 from a lower-trapezoidal
+ * root L [n_masked][nq] of Q' (Householder reflectors on F, built at set-up when n_masked < nq makes it the cheaper product);
+ * linear term, constants and the reported form stay those of Q'.  VMX_NO_QUAD_ROOT=1 keeps the half-triangle contraction. */
 int vmx_set_quadratic_form_kind(vmx_engine* e, int32_t kind);
 
 /* Samplers usually keep the Arinyo non-linear parameters fixed.  When they are identical for every walker of a
@@ -1173,6 +1176,9 @@ void* vmx_stream(vmx_engine* e);
  * [n_ell_max][n_static][3][ncp] (a pipeline's place: the static basis of tap 9); 16 = the odd-multipole coefficient rows
  * [4][odd_ncoef] of pipeline `index`; 17 = the metal pairs' walker factors [B][3][n_metals] (bias product x multiplicity,
  * beta1 + beta2, beta1 beta2) of the last evaluation.
+ * 4 [11] = 1 when the last Q' evaluation took its quadratic term from the trapezoidal root of Q' (below), 0 otherwise.
+ * 20 = that root of item `index`, L [n_masked][nq_pad] with L^T L = Q' and L[i][j] = 0 for j > i + nq - n_masked; 21 = Q' itself in
+ * half form [nq][nq_pad] (below the diagonal, half the diagonal on it) - "none" for an engine that holds no such tensor.
  * Returns the number of doubles written (<= capacity) or a negative error. */
 int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, int64_t capacity);
 #define VMX_DEBUG_NS 40

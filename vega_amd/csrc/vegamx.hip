@@ -131,6 +131,7 @@ struct ItemHost {
     // ... in its factored form (vmx_set_quadratic_form_kind): U with C^-1 = U^T U [n_masked][n_masked_pad], F = U S DM'
     // [n_masked][nq_pad], u0 = U r0 per data vector / mock [rows][n_masked_pad], slabs of F dx [slab_rows][n_masked_pad]
     DevBuf<double> q_u, q_f, q_u0, q_y;
+    DevBuf<double> q_root;      // [n_masked][nq_pad]: lower-trapezoidal L with L^T L = Q' (quad_build), when n_masked < nq
     // marginalisation coefficients folded into that form (vmx_marg_coeff_device): G = M S DM' [n_templates][nq_pad] (static),
     // c0 = M r0 per data vector / mock [rows][pad(n_templates)], slabs of G dx (or of M . residual) [mg_rows][pad(n_templates)]
     DevBuf<double> mg_g, mg_c0, mg_y;
@@ -1820,6 +1821,9 @@ struct vmx_chain_store {
     DevBuf<int64_t> window;
 };
 
+// Whether the quadratic term of the Q' form may run over the trapezoidal root of Q' (quad_build).  false: only with VMX_QUAD_ROOT=1.
+constexpr bool QUAD_ROOT_DEFAULT = true;
+
 struct vmx_engine {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -1921,7 +1925,13 @@ struct vmx_engine {
     int fact_slab_rows = 0;          // rows of the factored form's slabs of F dx (small rows: up to 4 K splits of a full batch)
     std::map<int, std::vector<int>> group_splits;     // K splits of the grouped launches per (stage, batch size)
     // tapes of the quadratic-form launches per number of walker tiles: the blocks' entries, their queues, the partial-sum slots
-    struct QuadList { DevBuf<GemmWork> work; DevBuf<int32_t> queue, nt_off; DevBuf<double> part; int n_blocks = 0; int n_entries = 0; };
+    // (root = true: the tape runs over the items' trapezoidal roots and stores partial tiles - ypart holds, item after item,
+    // max_segs slabs of [64 tn walkers][n_masked_pad]; segs the segment counts per (item's row tile, walker tile); y_off / seg_off
+    // where an item's share of the two begins)
+    struct QuadList {
+        DevBuf<GemmWork> work; DevBuf<int32_t> queue, nt_off; DevBuf<double> part; int n_blocks = 0; int n_entries = 0;
+        bool root = false; DevBuf<double> ypart; DevBuf<int32_t> segs; std::vector<int64_t> y_off; std::vector<int32_t> seg_off; int max_segs = 0;
+    };
     std::map<int, QuadList*> quad_lists;     // by number of walker tiles
     std::vector<void*> host_allocs;          // vmx_host_alloc: pinned host buffers handed to the caller, freed with the engine at the latest
     std::map<int, QuadList*> cinv_lists;     // the same tape over the inverse covariances (chi2 of the full chain), by walker tiles
@@ -1966,6 +1976,10 @@ struct vmx_engine {
     bool static_poly = true;         // vmx_set_static_poly
     int quad_kind = 0;               // vmx_set_quadratic_form_kind: 0 = the cheaper form, 1 = Q', 2 = factored
     bool quad_factored = false;      // the form the tensors were built for
+    bool quad_root = false;          // every item holds the trapezoidal root of its Q' (quad_build): tapes may run over it
+    bool no_quad_root = false;       // VMX_NO_QUAD_ROOT: the quadratic term stays the half-triangle contraction
+    bool force_quad_root = false;    // VMX_QUAD_ROOT=force: the root wherever it can be built, whatever the tapes' prices (tests)
+    bool last_root = false;          // the last Q' evaluation ran the tape over the roots (vmx_debug_read 4 [11])
     struct MargReq { double* out; int64_t ld_out; int32_t* status; };
     const MargReq* marg_req = nullptr;      // set while vmx_marg_coeff_device runs the chain: derived columns instead of chi2
     int marg_slab_rows = 0;          // rows of the items' mg_y (K slabs of G dx)
@@ -3094,6 +3108,8 @@ int vmx_finalize(vmx_engine* e, int32_t n_params, int32_t max_batch)
     }
     if (getenv("VMX_NO_TAB2")) e->no_tab2 = true;
     if (getenv("VMX_NO_CINV_TAPE")) e->no_cinv_tape = true;
+    if (getenv("VMX_NO_QUAD_ROOT") || (!QUAD_ROOT_DEFAULT && !getenv("VMX_QUAD_ROOT"))) e->no_quad_root = true;
+    if (getenv("VMX_QUAD_ROOT") && !std::strcmp(getenv("VMX_QUAD_ROOT"), "force")) e->force_quad_root = !e->no_quad_root;
     if (getenv("VMX_NO_PK_W")) e->no_pk_w = true;
     if (getenv("VMX_NO_HOST_REDUCE")) e->no_host_reduce = true;
     if (getenv("VMX_NO_XI_LEAN")) e->xi_lean = false;
@@ -3553,6 +3569,10 @@ int vmx_pipeline_column(vmx_engine* e, int32_t pipeline)
 // + 9.8), and the share of a piece moved from the blocks dispatched second to those dispatched first (B = 256: 145.1 us at 0,
 // 142.6 at 0.12 - 0.16, 144.0 at 0.2, 149.6 at 0.4)
 constexpr double QUAD_ENTRY_STAGES = 4.0, QUAD_SKEW = 0.12;
+// The tape over the trapezoidal roots (vmx_plan::TapeProblem::k_off > 0): its entries end with the plain store of their partial
+// tile - no E tile to wait for, no row sums - so an entry is charged less than a contraction's; a K stage at 1.98 us and the
+// reducer's reads of the partial tiles at ~3 TB/s (+ 2 stages for what it costs beyond k_chi2_parts) price it against the triangle.
+constexpr double QUAD_ROOT_ENTRY_STAGES = 2.5, QUAD_STAGE_US = 1.98, QUAD_ROOT_BYTES_PER_US = 3.0e6, QUAD_ROOT_REDUCER_STAGES = 2.0;
 // The equal-cost pieces of the tape are dealt to the XCDs by their place in K (the heavy and the light ones separately, so that
 // the skew keeps its meaning): same pieces, same slots, the same sums bit for bit - 12 % fewer L2 misses of the walker operand
 // (493 -> 435 MB per launch at B = 256), the same launch time with one batch in flight and ~1 % less with two (round 4).
@@ -3567,6 +3587,30 @@ static vmx_engine::QuadList* quad_build_tape(vmx_engine* e, int B)
     // B = 256 - and nothing off its time: 151.4 us either way, round 4; the sums are the same bit for bit)
     vmx_plan::Tape T = vmx_plan::plan_quad_tape(probs, tn, e->quad_blocks, QUAD_ENTRY_STAGES, QUAD_SKEW, GEMM_BM, GEMM_BK, QUAD_K_BANDS);
     auto* ql = new vmx_engine::QuadList();
+    if (e->quad_root && !e->no_quad_root) {
+        // The same launch over the items' trapezoidal roots (|| L dx ||^2 instead of 2 dx^T (L' dx)): fewer K stages when n_masked <
+        // nq, but its entries store partial tiles that k_chi2_root reads back.  Both tapes are priced in K stages - a piece's
+        // capacity is the launch's length - and the root pays for the reducer's traffic on top.
+        std::vector<vmx_plan::TapeProblem> roots;
+        for (auto* it : e->items) roots.push_back({it->dev.n_masked, it->dev.nq_pad, it->dev.nq - it->dev.n_masked});
+        vmx_plan::Tape R = vmx_plan::plan_quad_tape(roots, tn, e->quad_blocks, QUAD_ROOT_ENTRY_STAGES, QUAD_SKEW, GEMM_BM, GEMM_BK, QUAD_K_BANDS, true);
+        double bytes = 0.0;
+        for (size_t q = 0; q < roots.size(); ++q)
+            for (int t = R.tile_off[q]; t < R.tile_off[q + 1]; ++t)
+                for (int nt = 0; nt < tn; ++nt) bytes += 8.0 * GEMM_BM * GEMM_BN * R.seg_count[(size_t)t * tn + nt];
+        const double reducer_stages = bytes / QUAD_ROOT_BYTES_PER_US / QUAD_STAGE_US + QUAD_ROOT_REDUCER_STAGES;
+        if ((R.capacity + reducer_stages < T.capacity || e->force_quad_root) && !R.work.empty()) {
+            ql->root = true;
+            ql->max_segs = R.max_segs;
+            int64_t y = 0;
+            for (size_t q = 0; q < roots.size(); ++q) {
+                ql->y_off.push_back(y); ql->seg_off.push_back(R.tile_off[q] * tn);
+                y += (int64_t)R.max_segs * tn * GEMM_BN * e->items[q]->dev.n_masked_pad;
+            }
+            if (ql->ypart.alloc((size_t)y, true) || ql->segs.upload(R.seg_count.data(), R.seg_count.size())) { delete ql; return nullptr; }
+            T = std::move(R);
+        }
+    }
     ql->n_blocks = T.n_blocks;
     ql->n_entries = (int)T.n_slots;
     if (T.work.empty()) T.work.push_back(GemmWork{-1, 0, 0, 0, 0, 0, 0, 0});
@@ -3590,6 +3634,13 @@ static void quad_launch_list(vmx_engine* e, vmx_engine::QuadList* ql, int B)
         g.tm = (d.nq + GEMM_BM - 1) / GEMM_BM; g.tn = (B + GEMM_BN - 1) / GEMM_BN;
         g.part = ql->part.p; g.lin = it->q_lin.p; g.lin_row = e->call_mock ? e->call_mock : e->mock_index.p; g.lin_pool = d.mock_pool ? 1 : 0;
         g.row0 = vmx_plan::tape_row0(d.nq, GEMM_BM);       // (the tape's K ranges are those of this tiling)
+        if (ql->root) {
+            // the trapezoidal root in place of the half form: n_masked rows, the partial tile of K segment s stored to slab s
+            g.A = it->q_root.p; g.M = d.n_masked; g.tri = 0; g.part = nullptr;
+            g.D = ql->ypart.p + ql->y_off[q]; g.ldd = d.n_masked_pad; g.d_slab = (int64_t)g.tn * GEMM_BN * d.n_masked_pad;
+            g.tm = (d.n_masked + GEMM_BM - 1) / GEMM_BM;
+            g.row0 = vmx_plan::tape_row0(d.n_masked, GEMM_BM);
+        }
         G.p[G.n++] = g;
     }
     G.work = ql->work.p;
@@ -4281,6 +4332,7 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
             return 0;
         }
         e->last_form = 1;
+        e->last_root = false;
         if (B > 8 && e->items.size() <= VMX_MAX_GROUP) {
             // the persistent tape: every block the same work to a stage, contraction partials in the tape's slots
             vmx_engine::QuadList* ql = quad_work_list(e, B);
@@ -4288,6 +4340,23 @@ static int run_chain(vmx_engine* e, int B, int tab_mode, bool zero_copy = false,
             {
                 ScopedTimer t(e, KC_QUAD);
                 quad_launch_list(e, ql, B);
+            }
+            e->last_root = ql->root;
+            if (ql->root) {
+                // the launch left partial tiles of L dx: the reducer squares and adds them, and the linear term with them
+                RootArgs R{};
+                for (size_t q = 0; q < e->items.size(); ++q) {
+                    const ItemDev& d = e->items[q]->dev;
+                    const int tn = (B + GEMM_BN - 1) / GEMM_BN;
+                    R.p[q] = {ql->ypart.p + ql->y_off[q], (int64_t)tn * GEMM_BN * d.n_masked_pad, ql->segs.p + ql->seg_off[q],
+                              (int32_t)d.n_masked_pad, (int32_t)d.n_masked, vmx_plan::tape_row0(d.n_masked, GEMM_BM), tn};
+                }
+                ScopedTimer t(e, KC_CHI2);
+                hipLaunchKernelGGL(k_chi2_root, dim3(B), dim3(CHI2_ROOT_THREADS), 0, e->stream, D, B, R);
+                HIP_OK(hipGetLastError());
+                e->last_B = B;
+                e->last_full = false;
+                return 0;
             }
             // the launch left contraction partials instead of the product: a small kernel adds them up
             ScopedTimer t(e, KC_CHI2);
@@ -4651,6 +4720,23 @@ static int quad_build(vmx_engine* e)
         const bool fact = e->quad_kind == 2 || (e->quad_kind == 0 && cost_f < 0.75 * cost_q);
         if (fact != e->quad_factored) { e->quad_factored = fact; e->quad_mat_dirty = true; }
     }
+    // The Q' form's quadratic term over a root of Q': Q' = F^T F with F = U S DM' [n_masked][nq] has rank <= n_masked, and an
+    // orthogonal Qt turns F into a lower-trapezoidal L = Qt^T F - dx^T Q' dx = || L dx ||^2 exactly, for n_masked nq - n_masked^2 / 2
+    // multiply-adds per walker instead of the half triangle's nq^2 / 2.  Built when that is the smaller number for the items together
+    // (which tape a batch size takes is priced in quad_build_tape); the linear and constant terms stay those of Q'.
+    bool want_root = !e->quad_factored && !e->no_quad_root && e->items.size() <= VMX_MAX_GROUP;
+    {
+        double tri = 0.0, trap = 0.0;
+        for (auto* it : e->items) {
+            int na = 0;
+            for (int q = 0; q < it->dev.n_bb[VMX_BB_POST_ADD]; ++q) na += it->dev.bb[VMX_BB_POST_ADD][q].n_coef;
+            const double nq = it->dev.d.n_model + na, nm = it->dev.n_masked;
+            if (nm > nq) want_root = false;
+            tri += 0.5 * nq * nq; trap += nm * nq - 0.5 * nm * nm;
+        }
+        if (!e->force_quad_root && !(trap < tri)) want_root = false;
+    }
+    bool root_ok = want_root, rebuilt = false;
     for (auto* it : e->items) {
         ItemDev& d = it->dev;
         const int nm = d.n_masked, nmp = d.n_masked_pad;
@@ -4758,6 +4844,43 @@ static int quad_build(vmx_engine* e)
             if (it->q_mat.p == nullptr && it->q_mat.alloc((size_t)nq * nqp, true)) return -2;
             hipLaunchKernelGGL(k_half_from_full, dim3((nqp + 255) / 256, nq), dim3(256), 0, e->stream, it->q_mat.p, qfull.p, nq, nqp);
             if (marg_fold_matrix(e, it, X.p)) return -2;
+            rebuilt = true;
+            DevBuf<double> U, qr_part, qr_v, qr_row;
+            std::vector<double> hu;
+            if (root_ok) {
+                // F = U X^T with C^-1 = U^T U, by the factored form's own steps (the Cholesky factor on the host, vmx_plan.h) ...
+                hu.assign((size_t)nm * nmp, 0.0);
+                if (it->has_cinv) {
+                    std::vector<double> hc((size_t)nm * nmp);
+                    HIP_OK(hipStreamSynchronize(e->stream));
+                    HIP_OK(hipMemcpy(hc.data(), cfull.p, hc.size() * sizeof(double), hipMemcpyDeviceToHost));
+                    if (!vmx_plan::cholesky_lower(hc.data(), nm, nmp)) {
+                        std::fprintf(stderr, "[vegamx] the inverse covariance of an item is not positive definite: chi2 keeps the Q' form\n");
+                        root_ok = false;
+                    }
+                    for (int i = 0; i < nm && root_ok; ++i)
+                        for (int m = 0; m <= i; ++m) hu[(size_t)m * nmp + i] = hc[(size_t)i * nmp + m];       // U = L^T
+                } else
+                    for (int i = 0; i < nm; ++i) hu[(size_t)i * nmp + i] = 1.0;
+            }
+            if (root_ok) {
+                if (U.upload(hu.data(), hu.size())) return -2;
+                // (allocated once: captured graphs and lanes hold the pointer)
+                if (it->q_root.p == nullptr && it->q_root.alloc((size_t)nm * nqp, true)) return -2;
+                launch_product(e, KC_OTHER, X.p, nmp, 0, nq, nmp, U.p, nmp, 0, nm, it->q_root.p, nqp, 0, 1, nm);
+                // ... and F -> L in place by Householder reflectors from the last column on (k_qr_dot / k_qr_apply, vmx_device.h):
+                // backward stable whatever the condition of F, no atomics, fixed orders - L is the same bit for bit on every rebuild
+                const int chunks_max = (nm + QR_CH - 1) / QR_CH;
+                if (qr_part.alloc((size_t)chunks_max * nqp, true) || qr_v.alloc((size_t)nmp, true) || qr_row.alloc((size_t)nqp, true)) return -2;
+                for (int t = 0; t + 1 < nm; ++t) {
+                    const int r = nm - 1 - t, j = nq - 1 - t, chunks = r / QR_CH + 1;
+                    const dim3 grid((unsigned)(j / 256 + 1), (unsigned)chunks);
+                    hipLaunchKernelGGL(k_qr_dot, grid, dim3(256), 0, e->stream, (const double*)it->q_root.p, nqp, r, j, qr_part.p, qr_v.p, qr_row.p);
+                    hipLaunchKernelGGL(k_qr_apply, grid, dim3(256), 0, e->stream, it->q_root.p, nqp, r, j, chunks, (const double*)qr_part.p,
+                                       (const double*)qr_v.p, (const double*)qr_row.p);
+                }
+                HIP_OK(hipGetLastError());
+            }
             HIP_OK(hipStreamSynchronize(e->stream));        // X / qfull are released here
         }
         // linear terms for the data vector and every mock of the pool
@@ -4802,6 +4925,15 @@ static int quad_build(vmx_engine* e)
     std::vector<ItemDev> items;
     for (auto* it : e->items) items.push_back(it->dev);
     HIP_OK(hipMemcpy(e->d_items.p, items.data(), items.size() * sizeof(ItemDev), hipMemcpyHostToDevice));
+    if (rebuilt || e->quad_factored) {
+        // (tapes were planned with or without the roots: plan them again when that changed - the graphs are dropped below anyway)
+        const bool have = root_ok && !e->quad_factored;
+        if (have != e->quad_root) {
+            for (auto& q : e->quad_lists) delete q.second;
+            e->quad_lists.clear();
+        }
+        e->quad_root = have;
+    }
     e->quad_mat_dirty = false;
     e->quad_lin_dirty = false;
     e->last_B = 0;                  // the reference evaluation is not a caller's evaluation
@@ -7475,7 +7607,8 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         if (capacity >= 9) out[8] = e->last_form;               // 0: full chain, 1: the quadratic form Q', 2: its factored form
         if (capacity >= 10) out[9] = e->last_route | e->route_setup;        // bins kernels launched (VMX_ROUTE_*)
         if (capacity >= 11) out[10] = e->last_fft_form;         // form of the FFTLog o spline product (VMX_FFT_*)
-        if (capacity >= 8) { out[7] = live[4]; return capacity >= 11 ? 11 : capacity >= 10 ? 10 : capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
+        if (capacity >= 12) out[11] = e->last_form == 1 && e->last_root ? 1 : 0;      // the Q' form's quadratic term ran over the trapezoidal root
+        if (capacity >= 8) { out[7] = live[4]; return capacity >= 12 ? 12 : capacity >= 11 ? 11 : capacity >= 10 ? 10 : capacity >= 9 ? 9 : 8; }       // walkers that left the mu rule's box since vmx_finalize
         return capacity >= 7 ? 7 : capacity >= 5 ? 5 : capacity >= 4 ? 4 : 3;
     }
     else if (what == 5) {
@@ -7567,6 +7700,13 @@ int64_t vmx_debug_read(vmx_engine* e, int32_t what, int32_t index, double* out, 
         src = e->odd_coef.p + P.odd_off; count = (int64_t)4 * P.odd_ncoef;
     }
     else if (what == 17) { src = e->metal_bias.p; count = (int64_t)B * 3 * (int64_t)e->metals.size(); if (count == 0) { fail(-1, "none: no metal terms"); return -1; } }
+    else if (what == 20 || what == 21) {
+        // static tensors of the Q' form of item `index`: 20 = the trapezoidal root L [n_masked][nq_pad], 21 = Q' in half form [nq][nq_pad]
+        if (index < 0 || index >= (int)e->items.size()) { fail(-1, "invalid argument: item index"); return -1; }
+        const ItemHost* it = e->items[index];
+        if (e->quad_factored || !it->q_mat.p || (what == 20 && (!e->quad_root || !it->q_root.p))) { fail(-1, "none: the engine holds no such tensor of the Q' form"); return -1; }
+        src = what == 20 ? it->q_root.p : it->q_mat.p; count = (int64_t)(what == 20 ? it->dev.n_masked : it->dev.nq) * it->dev.nq_pad;
+    }
     else { fail(-1, "invalid argument: what"); return -1; }
     if (count > capacity) { fail(-1, "invalid argument: capacity too small"); return -1; }
     if (hipMemcpy(out, src, (size_t)count * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) { fail(-2, "hipMemcpy"); return -2; }

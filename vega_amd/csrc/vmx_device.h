@@ -2383,6 +2383,137 @@ __global__ __launch_bounds__(256) void k_chi2_parts(EngineDev D, int B, const do
     }
 }
 
+// chi2 from the partial tiles of the root tape (the quadratic term as || L dx ||^2 with the lower-trapezoidal root L of Q',
+// quad_build): the launch left y_s[b][m] = sum over K segment s of L[m][k] dx[b][k] in slab s of the item's partial buffer.
+// One block of 16 waves per walker: wave w takes the row tiles w, w + 16, .. of every item, lane l row l of the tile - the
+// segments of a row added in index order (the tile's count is wave-uniform: the loads of up to four segments go out together),
+// then squared - and thread t the columns t, t + 1024, .. of -2 lin . dx with the walker's own row of the linear term; the
+// block's sum goes lane by lane, wave by wave in a fixed order.  Constants, priors, sentinel and status as in k_chi2_parts;
+// what the last additions need is requested first, as there.
+struct RootItem { const double* y; int64_t slab; const int32_t* segs; int32_t ldy, rows, row0, tn; };
+struct RootArgs { RootItem p[VMX_MAX_GROUP]; };
+#define CHI2_ROOT_THREADS 1024
+
+__global__ __launch_bounds__(CHI2_ROOT_THREADS) void k_chi2_root(EngineDev D, int B, RootArgs R)
+{
+    constexpr int NWV = CHI2_ROOT_THREADS / 64;
+    const int b = blockIdx.x;
+    if (b >= B) return;
+    __shared__ double red[NWV];
+    const int nt = b >> 6, lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int mock = D.mock_index[b];
+    int st = D.status[b];
+    double tail = 0.0;          // constants, then priors: every thread asks (uniform addresses), thread 0 uses them
+    for (int q = 0; q < D.n_items; ++q) {
+        const ItemDev& it = D.items[q];
+        tail += it.q_c0[(mock >= 0 && it.mock_pool) ? 1 + mock : 0];
+    }
+    {
+        const double* t = D.theta + (size_t)b * D.n_params;
+        for (int q = 0; q < D.n_priors; ++q) {
+            const double dlt = t[D.prior_slot[q]] - D.prior_mean[q];
+            tail += dlt * dlt / (D.prior_sigma[q] * D.prior_sigma[q]);
+        }
+    }
+    double acc = 0.0;
+    for (int q = 0; q < D.n_items; ++q) {
+        const ItemDev& it = D.items[q];
+        const RootItem& r = R.p[q];
+        const double* y = r.y + (size_t)b * r.ldy + lane;
+        const int tm = (r.rows + 63) / 64;
+#pragma unroll 2
+        for (int mt = wave; mt < tm; mt += NWV) {
+            const int m0 = r.row0 > 0 ? (mt == 0 ? 0 : r.row0 + (mt - 1) * 64) : mt * 64;
+            const int mend = (r.row0 > 0 && mt == 0) ? r.row0 : min(m0 + 64, r.rows);
+            const int ns = r.segs[mt * r.tn + nt];
+            if (m0 + lane < mend) {
+                const double* ym = y + m0;
+                const double y0 = ym[0];
+                const double y1 = ns > 1 ? ym[r.slab] : 0.0;
+                const double y2 = ns > 2 ? ym[2 * r.slab] : 0.0;
+                const double y3 = ns > 3 ? ym[3 * r.slab] : 0.0;
+                double v = ((y0 + y1) + y2) + y3;
+                for (int s = 4; s < ns; ++s) v += ym[(size_t)s * r.slab];
+                acc = fma(v, v, acc);
+            }
+        }
+        const double* lin = it.q_lin + (size_t)((mock >= 0 && it.mock_pool) ? 1 + mock : 0) * it.nq_pad;
+        const double* x = it.q_x + (size_t)b * it.nq_pad;
+#pragma unroll 4
+        for (int j = threadIdx.x; j < it.nq; j += CHI2_ROOT_THREADS) acc = fma(-2.0 * lin[j], x[j], acc);
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) red[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double c = 0.0;
+    for (int w = 0; w < NWV; ++w) c += red[w];
+    c += tail;
+    if (!(c == c) || c > 1e300 || c < -1e300) { st |= VMX_STATUS_NONFINITE; D.status[b] = st; }
+    D.chi2[b] = st ? 1e100 : c;
+    if (D.chi2_host) D.chi2_host[b] = st ? 1e100 : c;
+    if (D.status_host) D.status_host[b] = st;
+    if (b == 0) {
+        D.k_live[2] = D.coef_win[0]; D.k_live[3] = D.coef_win[1]; D.coef_win[0] = 0x7fffffff; D.coef_win[1] = -1;
+        xtab_key_store(D);
+    }
+}
+
+// The root of Q' by Householder reflectors (quad_build): F [rows][ld] = U S DM' is turned in place into L = Qt^T F, lower
+// trapezoidal - L[i][j] = 0 for j > i + (cols - rows).  Reflector t works on column j = cols - 1 - t over the rows 0 .. r =
+// rows - 1 - t: it maps that column to alpha e_r and is applied to the columns to its left (those to its right are zero in these
+// rows already).  Two kernels per reflector, both tiled (256 columns) x (QR_CH rows), no atomics, every sum in a fixed order:
+//   k_qr_dot    part[chunk][c] = sum over the chunk's rows of F[i][j] F[i][c], c <= j (c = j: the column's own square), and
+//               copies of what the second kernel must read unchanged while F is rewritten: the column (v) and the row r (rowr)
+//   k_qr_apply  adds the chunks' partial sums in chunk order, forms alpha = -sign(x_r) |x|, v = x - alpha e_r, tau = 2 / v^T v, and
+//               F[i][c] -= tau v_i (v^T F[:, c]);  column j itself becomes alpha e_r
+#define QR_CH 128
+__global__ __launch_bounds__(256) void k_qr_dot(const double* F, int ld, int r, int j, double* part, double* v, double* rowr)
+{
+    __shared__ double sx[QR_CH];
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int i0 = blockIdx.y * QR_CH, i1 = min(i0 + QR_CH, r + 1);
+    if (threadIdx.x < i1 - i0) {
+        const double x = F[(size_t)(i0 + threadIdx.x) * ld + j];
+        sx[threadIdx.x] = x;
+        if (blockIdx.x == 0) v[i0 + threadIdx.x] = x;
+    }
+    __syncthreads();
+    if (c > j) return;
+    if (blockIdx.y == 0) rowr[c] = F[(size_t)r * ld + c];
+    const double* col = F + (size_t)i0 * ld + c;
+    double s = 0.0;
+#pragma unroll 8
+    for (int i = 0; i < i1 - i0; ++i) s = fma(sx[i], col[(size_t)i * ld], s);
+    part[(size_t)blockIdx.y * ld + c] = s;
+}
+
+__global__ __launch_bounds__(256) void k_qr_apply(double* F, int ld, int r, int j, int chunks, const double* part, const double* v,
+                                                  const double* rowr)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int i0 = blockIdx.y * QR_CH, i1 = min(i0 + QR_CH, r + 1);
+    if (c > j) return;
+    double sigma = 0.0, d = 0.0;
+    for (int ch = 0; ch < chunks; ++ch) { sigma += part[(size_t)ch * ld + j]; d += part[(size_t)ch * ld + c]; }
+    if (!(sigma > 0.0)) return;            // (a zero column is reduced already)
+    const double xr = v[r];
+    const double alpha = xr >= 0.0 ? -sqrt(sigma) : sqrt(sigma);
+    const double tau = 1.0 / (sigma - alpha * xr);          // 2 / v^T v, v^T v = 2 (sigma - alpha x_r)
+    const double w = -tau * (d - alpha * rowr[c]);          // -tau v^T F[:, c]
+    double* col = F + (size_t)i0 * ld + c;
+    if (c == j) {
+        for (int i = i0; i < i1; ++i) col[(size_t)(i - i0) * ld] = i == r ? alpha : 0.0;
+        return;
+    }
+#pragma unroll 4
+    for (int i = i0; i < i1; ++i) {
+        const double vi = i == r ? xr - alpha : v[i];
+        col[(size_t)(i - i0) * ld] = fma(w, vi, col[(size_t)(i - i0) * ld]);
+    }
+}
+
 // Marginalisation coefficients as derived columns (vmx_marg_coeff_device).  The coefficients are the static map M of the residual,
 // and the residual is linear in the dx the quadratic form contracts: coeff = M (d - S DM' x') = c0 - G dx with G = M S DM'
 // [n_templates][nq_pad] and c0 = M r0 per data vector / mock, both folded at set-up (quad_build).  The product kernel leaves
@@ -2884,6 +3015,9 @@ __global__ __launch_bounds__(GEMM44_THREADS, NBUF == 2 ? GEMM44_THREADS / 128 : 
     int p_M = g.M, p_N = g.N, p_lda = g.lda, p_ldx = g.ldx, p_lin_pool = g.lin_pool, p_row0 = g.row0;
     int p_mend = g.M;           // one past the last row of the current tile that counts (a ragged first tile: row0)
     double* p_part = g.part;
+    // (a tape without `part` stores its partial tiles: K segment wk.slab of a tile goes to slab wk.slab of the entry's problem)
+    double* p_D = Dp;
+    int p_ldd = g.ldd;
     const double* p_lin = g.lin;
     const int32_t* p_lin_row = g.lin_row;
 
@@ -2915,6 +3049,7 @@ __global__ __launch_bounds__(GEMM44_THREADS, NBUF == 2 ? GEMM44_THREADS / 128 : 
             A = (const char*)q.A; X = (const char*)q.X;
             p_M = q.M; p_N = q.N; p_lda = q.lda; p_ldx = q.ldx; p_lin_pool = q.lin_pool; p_row0 = q.row0;
             p_part = q.part; p_lin = q.lin; p_lin_row = q.lin_row;
+            p_D = q.D + (int64_t)__builtin_amdgcn_readfirstlane(wk.slab) * q.d_slab; p_ldd = q.ldd;
             n0 = wk.nt * BN;
             slot = wk.slot;
         }
@@ -2967,6 +3102,8 @@ __global__ __launch_bounds__(GEMM44_THREADS, NBUF == 2 ? GEMM44_THREADS / 128 : 
     const int c_m0 = m0, kbeg_c = kbeg, kend_c = kend, c_n0 = n0, c_slot = slot, c_first = first_buf;
     const int c_M = p_mend, c_N = p_N, c_ldx = p_ldx, c_lin_pool = p_lin_pool;
     double* const c_part = p_part;
+    double* const c_D = p_D;
+    const int c_ldd = p_ldd;
     const double* const c_lin = p_lin;
     const int32_t* const c_lin_row = p_lin_row;
     const bool c_skip = skip;
@@ -3154,9 +3291,11 @@ __global__ __launch_bounds__(GEMM44_THREADS, NBUF == 2 ? GEMM44_THREADS / 128 : 
                 tot[u] = sum_k_quarters(v);
             }
             const double out = fb == 0 ? tot[0] : fb == 1 ? tot[1] : fb == 2 ? tot[2] : tot[3];
-            const int n = n0 + wn + 4 * i + (lane >> 4);
+            // (the c_ copies: a persistent block's next entry has moved n0 and the problem on already; c_M is the ragged first
+            // tile's end on a tape, the problem's rows otherwise)
+            const int n = c_n0 + wn + 4 * i + (lane >> 4);
             const int m = c_m0 + wm + 16 * jg + (lane & 15);
-            if (n < g.N && m < g.M) Dp[(size_t)n * g.ldd + m] = out;
+            if (n < c_N && m < c_M) c_D[(size_t)n * c_ldd + m] = out;
         }
   }
     if (G.trace && threadIdx.x == 0 && !skip) {

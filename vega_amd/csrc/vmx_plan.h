@@ -21,7 +21,10 @@ struct GemmWork { int32_t prob, mt, nt, kbeg, kend, slab, slot, pad; };
 
 namespace vmx_plan {
 
-struct TapeProblem { int nq, nq_pad; };       // rows of the half-form matrix and its padded leading dimension (multiple of bk)
+// Rows of the matrix and its padded leading dimension (multiple of bk).  k_off = 0: the half form of a symmetric matrix (lower
+// triangle, row i reads k <= i).  k_off > 0: a lower-trapezoidal root L [nq rows][k_off + nq columns] of the quadratic form,
+// L[i][j] = 0 for j > i + k_off - row i reads k <= i + k_off.
+struct TapeProblem { int nq, nq_pad; int k_off = 0; };
 
 // Row tiling of a half-form (lower-triangular) problem.  nq is rarely a multiple of the 64-row tile, and a tile costs its K
 // range whatever its live rows: with the ragged tile at the BOTTOM of the triangle it is the longest row of all (5000 rows: 8
@@ -35,7 +38,7 @@ inline int tape_tile_hi(int nq, int mt, int bm)            // one past the last 
     const int row0 = tape_row0(nq, bm);
     return row0 > 0 ? row0 + mt * bm : (mt + 1) * bm;
 }
-inline int tape_tile_stages(const TapeProblem& p, int mt, int bm, int bk) { return std::min((tape_tile_hi(p.nq, mt, bm) + bk - 1) / bk, p.nq_pad / bk); }
+inline int tape_tile_stages(const TapeProblem& p, int mt, int bm, int bk) { return std::min((p.k_off + tape_tile_hi(p.nq, mt, bm) + bk - 1) / bk, p.nq_pad / bk); }
 
 struct Tape {
     std::vector<GemmWork> work;     // every block's entries, block after block
@@ -45,6 +48,11 @@ struct Tape {
     int n_blocks = 0, group_size = 1, n_pieces = 0;
     int64_t n_slots = 0;
     double capacity = 0.0;          // cost bound of a piece (K stages + entry charges) the bisection ended on
+    // `segments` tapes only (the entries store their partial tiles, one slab per K segment): GemmWork::slab is the index of the
+    // entry's segment within its K range (ascending in K), seg_count[(tile_off[prob] + mt) * tn + nt] the number of segments
+    // of that range, max_segs the largest of them (the slabs the partial buffer needs)
+    std::vector<int32_t> seg_count, tile_off;
+    int max_segs = 0;
 };
 
 // The quadratic-form launch as a persistent tape ("stream-K"): every (row tile, walker tile) K range of every item's
@@ -60,7 +68,7 @@ struct Tape {
 // operand at the same time and find it in their L2.  The pieces themselves, their cost and the slot numbering are the same
 // either way: which block computes an entry changes, the sums do not (bit for bit).
 inline Tape plan_quad_tape(const std::vector<TapeProblem>& probs, int tn, int blocks, double entry_stages, double skew,
-                           int bm = 64, int bk = 32, bool k_bands = false)
+                           int bm = 64, int bk = 32, bool k_bands = false, bool segments = false)
 {
     Tape T;
     const int P = std::max(blocks / 8 * 8, 8);
@@ -102,14 +110,15 @@ inline Tape plan_quad_tape(const std::vector<TapeProblem>& probs, int tn, int bl
         double cur = 0.0, cap = cap0 * weight(0);
         for (auto& r : ranges)
             for (int grp = 0; grp < n_groups; ++grp) {
-                int k = 0, left = r.stages;
+                int k = 0, left = r.stages, seg = 0;
                 while (left > 0) {
                     const double avail = cap - cur - ovh;
                     if (cur > 0.0 && avail < (double)std::min(left, MIN_SEG)) { ++pc; cur = 0.0; cap = cap0 * weight(std::min(pc, n_pieces - 1)); continue; }
                     int take = std::min(left, std::max(MIN_SEG, (int)std::floor(avail + 1e-9)));
                     const int rem = left - take;
                     if (rem > 0 && rem < MIN_SEG) take = (take - (MIN_SEG - rem) >= MIN_SEG) ? take - (MIN_SEG - rem) : left;     // no sliver behind the cut
-                    if (keep) entries.push_back({GemmWork{r.prob, r.mt, grp * gs, k * bk, (k + take) * bk, 0, 0, 0}, std::min(pc, n_pieces - 1)});
+                    if (keep) entries.push_back({GemmWork{r.prob, r.mt, grp * gs, k * bk, (k + take) * bk, segments ? seg : 0, 0, 0}, std::min(pc, n_pieces - 1)});
+                    ++seg;
                     cur += take + ovh;
                     k += take; left -= take;
                 }
@@ -166,6 +175,17 @@ inline Tape plan_quad_tape(const std::vector<TapeProblem>& probs, int tn, int bl
             for (int j = 0; j < per_xcd_pieces; ++j)
                 piece_at[x * per_xcd_pieces + j] = j < half ? heavy[(size_t)x * half + j] : light[(size_t)x * (per_xcd_pieces - half) + (j - half)];
     }
+    if (segments) {
+        T.tile_off.assign(probs.size() + 1, 0);
+        for (size_t q = 0; q < probs.size(); ++q) T.tile_off[q + 1] = T.tile_off[q] + (probs[q].nq + bm - 1) / bm;
+        T.seg_count.assign((size_t)T.tile_off[probs.size()] * tn, 0);
+        for (auto& en : entries)
+            for (int m = 0; m < gs; ++m) {
+                int32_t& n = T.seg_count[(size_t)(T.tile_off[en.w.prob] + en.w.mt) * tn + en.w.nt + m];
+                n = std::max(n, en.w.slab + 1);
+                T.max_segs = std::max(T.max_segs, (int)n);
+            }
+    }
     T.work.reserve(entries.size() * gs);
     for (int p = 0; p < P; ++p) {
         const int xcd = p % 8, i = p / 8, per_xcd = P / 8 / gs;
@@ -200,8 +220,14 @@ inline std::string check_quad_tape(const Tape& T, const std::vector<TapeProblem>
     if (T.queue[0] != 0 || T.queue[T.n_blocks] != (int32_t)T.work.size()) return "queue ends";
     for (int p = 0; p < T.n_blocks; ++p) if (T.queue[p + 1] < T.queue[p]) return "queue not monotone";
     // (i) coverage
-    std::vector<std::vector<std::vector<std::pair<int, int>>>> seg(probs.size());
-    for (size_t q = 0; q < probs.size(); ++q) seg[q].resize((size_t)((probs[q].nq + bm - 1) / bm) * tn);
+    std::vector<std::vector<std::vector<std::pair<int, int>>>> seg(probs.size()), seg_slab(probs.size());
+    for (size_t q = 0; q < probs.size(); ++q) { seg[q].resize((size_t)((probs[q].nq + bm - 1) / bm) * tn); seg_slab[q].resize(seg[q].size()); }
+    const bool segments = !T.seg_count.empty();
+    if (segments) {
+        if (T.tile_off.size() != probs.size() + 1 || T.tile_off[0] != 0) return "tile_off size";
+        for (size_t q = 0; q < probs.size(); ++q) if (T.tile_off[q + 1] - T.tile_off[q] != (probs[q].nq + bm - 1) / bm) return "tile_off steps";
+        if (T.seg_count.size() != (size_t)T.tile_off[probs.size()] * tn) return "seg_count size";
+    }
     std::vector<char> slot_used((size_t)T.n_slots, 0);
     for (auto& w : T.work) {
         if (w.prob < 0 || w.prob >= (int)probs.size()) return "problem index";
@@ -211,6 +237,8 @@ inline std::string check_quad_tape(const Tape& T, const std::vector<TapeProblem>
         if (w.slot < T.nt_off[w.nt] || w.slot >= T.nt_off[w.nt + 1]) return "slot outside its walker tile's range";
         if (slot_used[w.slot]++) return "slot written twice";
         seg[w.prob][(size_t)w.mt * tn + w.nt].push_back({w.kbeg, w.kend});
+        seg_slab[w.prob][(size_t)w.mt * tn + w.nt].push_back({w.kbeg, w.slab});
+        if (!segments && w.slab != 0) return "a slab index on a tape without segments";
     }
     for (auto u : slot_used) if (!u) return "slot never written";
     for (size_t q = 0; q < probs.size(); ++q) {
@@ -223,6 +251,14 @@ inline std::string check_quad_tape(const Tape& T, const std::vector<TapeProblem>
                 int at = 0;
                 for (auto& s : v) { if (s.first != at) return "K range has a gap or an overlap"; at = s.second; }
                 if (at != want) return "K range not covered to its end";
+                if (segments) {
+                    // the segment indices of a range: 0, 1, .. in K order, as many as seg_count says, none beyond max_segs
+                    auto u = seg_slab[q][(size_t)mt * tn + nt];
+                    std::sort(u.begin(), u.end());
+                    for (size_t j = 0; j < u.size(); ++j) if (u[j].second != (int)j) return "segment indices of a K range not dense in K order";
+                    if (T.seg_count[(size_t)(T.tile_off[q] + mt) * tn + nt] != (int32_t)u.size()) return "seg_count differs from the range's entries";
+                    if ((int)u.size() > T.max_segs) return "a range has more segments than max_segs";
+                }
             }
     }
     // (ii) slots of a walker tile in tape order: sort its entries by slot; (stages desc, prob, mt) must not increase in length
