@@ -1208,6 +1208,12 @@ enum { VMX_FFT_GEMV1 = 1,               /* k_gemv1: a single column, x in LDS */
 /* The device math functions of the kernels, elementwise on host arrays (a trivial kernel of its own; for tests against
  * extended precision): which = 0 vmx_log, 1 vmx_exp, 2 vmx_rsqrt.  x [n] -> out [n]. */
 int vmx_debug_math(vmx_engine* e, int32_t which, const double* x, int64_t n, double* out);
+/* A process-wide debug switch (tests): while on != 0, device scratch of plain doubles that a call takes without clearing it is
+ * filled with 0xFF bytes - NaN doubles - when it is allocated and at every call that finds it large enough from an earlier one,
+ * so that a read of what no writer of the call covered shows as NaN in the call's outputs.  Buffers that are uploaded whole,
+ * hold integers or carry structs are left alone.  Off (the default) nothing is filled and no call differs.  Returns the
+ * switch as it was. */
+int vmx_debug_poison_scratch(int on);
 
 /* Stand-alone distortion-style product y[b] = A x[b] through the same kernels the evaluation
  * uses (bench / roofline measurement of the distortion-matrix step).  d_A row-major [rows][cols] with

@@ -38,6 +38,7 @@ pytestmark = pytest.mark.gpu
 CHI2_RTOL = 1e-6
 BATCHES = (1, 5, 9, 70)
 U = 2.0**-53
+QUAD_DATA_BAR, QUAD_MOCK_BAR = 1e-11, 1e-10         # (d): of S, with the case's data vector and with a mock
 LD = np.longdouble
 ALL_CASES = list(sg.CASES)
 NO_BROADBAND = [c for c in ALL_CASES if not any(item['broadband'] for item in sg.CASES[c][0])]
@@ -296,7 +297,7 @@ def test_quadratic_forms_against_extended_precision(run, form):
             if not with_bb:
                 tw = run.evaluate('twin', B)
                 twin = run.vega('twin').engine
-            for data, tol in ((None, 1e-11), (mocks, 1e-10)):
+            for data, tol in ((None, QUAD_DATA_BAR), (mocks, QUAD_MOCK_BAR)):
                 eng.set_mock_index(None if data is None else np.zeros(B, dtype=np.int32))
                 got = eng.eval(theta)[0]
                 assert eng.last_form() == form

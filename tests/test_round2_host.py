@@ -149,6 +149,29 @@ def test_mock_scale_resolution_and_unmasked_cholesky():
             item.__dict__.pop('_cholesky', None)
 
 
+def test_a_new_covariance_drops_the_cached_mock_factor():
+    """`set_covariance` resets what was derived from the covariance before, the Cholesky factors `create_mocks` keeps per
+    (scale, masked) among it: the same seed after a covariance scaled by 4 draws exactly twice the noise (a power of two
+    scales every step of the factorisation and of the product exactly), not the old factor's noise again."""
+    from conftest import load_problem
+    from vega_amd import synthetic
+    from vega_amd.montecarlo import create_mocks
+    prob = load_problem('auto')
+    (name, item), = prob.items.items()
+    cov = synthetic.covariance(item.data_grid.rp, item.data_grid.rt)
+    fid = {name: np.zeros(item.data_vec.size)}         # (a zero fiducial: the mocks are their noise)
+    try:
+        item.set_covariance(cov)
+        first = create_mocks(prob, fid, 3, seed=11)[name]
+        assert '_cholesky' in item.__dict__ and np.abs(first).min() > 0
+        item.set_covariance(4.0 * cov)
+        assert '_cholesky' not in item.__dict__
+        second = create_mocks(prob, fid, 3, seed=11)[name]
+        np.testing.assert_array_equal(second, 2.0 * first)
+    finally:
+        item.set_covariance(None)
+
+
 def test_monte_carlo_tables_follow_the_reference_layout(tmp_path):
     """reference vega/output.py:442-520 + vega/data.py:749-753 + vega/analysis.py:279-297: mocks on the full data grid
     with NaN outside the mask; a failed fit has no Bestfit row and chisq = NaN."""

@@ -60,6 +60,27 @@ const char* kKernelNames[VMX_N_KERNELS] = {
     "assemble", "distortion_product", "post", "invcov_product", "chi2", "matvec_api", "other",
     "quadratic_form_product"};
 
+// vmx_debug_poison_scratch: with the switch on, device scratch of plain doubles that is taken without being cleared - alloc(count,
+// false) and every ensure() - is filled with 0xFF bytes (NaN doubles), so that a read of what no writer of the call covered shows
+// in the call's outputs.  Off (the default): no fill, no launch, nothing else differs.
+static std::atomic<int> g_poison_scratch{0};
+
+// The fill of the whole buffer, ordered by two device-wide waits: the first ends whatever an earlier call may still have in
+// flight on any stream (every driver ends in a host wait already, so it finds nothing), the second ends the fill before the
+// caller enqueues the call's first use on whichever stream it takes.  Integer buffers are never filled: a poisoned index would
+// be an address.
+template <typename T>
+static int poison_fill(T*, size_t) { return 0; }
+static int poison_fill(double* p, size_t count)
+{
+    if (!g_poison_scratch.load(std::memory_order_relaxed) || !p) return 0;
+    hipError_t err = hipDeviceSynchronize();
+    if (err == hipSuccess) err = hipMemset(p, 0xFF, count * sizeof(double));
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    if (err != hipSuccess) return fail(-2, std::string("poison fill: ") + hipGetErrorString(err));
+    return 0;
+}
+
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
@@ -69,20 +90,26 @@ struct DevBuf {
     DevBuf(const DevBuf& o) : p(o.p), n(o.n), borrowed(true) {}
     DevBuf& operator=(const DevBuf& o) { if (this != &o) { release(); p = o.p; n = o.n; borrowed = true; } return *this; }
     void forget() { if (borrowed) { p = nullptr; n = 0; borrowed = false; } }
-    int alloc(size_t count, bool zero = true) {
+    // room for `count` elements as hipMalloc hands it out (never poisoned: for buffers that are overwritten whole, or carry structs)
+    int alloc_raw(size_t count) {
         release();
         if (count == 0) count = 1;
         hipError_t err = hipMalloc((void**)&p, count * sizeof(T));
         if (err != hipSuccess) return fail(-2, std::string("hipMalloc: ") + hipGetErrorString(err));
         n = count;
-        if (zero) {
-            err = hipMemset(p, 0, count * sizeof(T));
-            if (err != hipSuccess) return fail(-2, std::string("hipMemset: ") + hipGetErrorString(err));
-        }
         return 0;
     }
+    int alloc(size_t count, bool zero = true) {
+        if (alloc_raw(count)) return -2;
+        if (zero) {
+            hipError_t err = hipMemset(p, 0, n * sizeof(T));
+            if (err != hipSuccess) return fail(-2, std::string("hipMemset: ") + hipGetErrorString(err));
+            return 0;
+        }
+        return poison_fill(p, n);
+    }
     int upload(const T* host, size_t count) {
-        if (alloc(count, false)) return -2;
+        if (alloc_raw(count)) return -2;        // (exempt from poison: the copy overwrites the whole buffer)
         hipError_t err = hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
         if (err != hipSuccess) return fail(-2, std::string("hipMemcpy: ") + hipGetErrorString(err));
         return 0;
@@ -169,8 +196,11 @@ struct FitWorkspace {
         for (auto& ev : ev_gap) (void)hipEventDestroy(ev);
     }
 };
+// (under vmx_debug_poison_scratch a buffer that is still large enough is filled too: the stale contents of an earlier, larger call)
 template <typename T>
-static int ensure(DevBuf<T>& b, size_t count) { return b.n >= count && b.p ? 0 : b.alloc(count, false); }
+static int ensure(DevBuf<T>& b, size_t count) { return b.n >= count && b.p ? poison_fill(b.p, b.n) : b.alloc(count, false); }
+// ensure() for a double buffer that carries structs (indices and counts among the doubles): exempt from poison
+static int ensure_structs(DevBuf<double>& b, size_t count) { return b.n >= count && b.p ? 0 : b.alloc_raw(count); }
 
 // What the three samplers share: the engine's rows and its answers, the fixed row and the sampled box, grown on demand
 struct BoxDev {
@@ -5307,6 +5337,9 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
             const size_t rows = (size_t)wave * it->dev.n_masked_pad;
             if (ensure(it->mc_z, rows) || ensure(it->mc_noise, rows) || ensure(it->mc_r0, rows) || ensure(it->mc_t, rows)) return -2;
             HIP_OK(hipMemset(it->mc_z.p, 0, rows * sizeof(double)));       // (the pad columns of the draws stay zero)
+            // (... and those of the residual rows: k_mock_rows writes the columns below n_masked, the products and row dots of a
+            // wave read all n_masked_pad, and 0 . NaN is no zero; mc_noise and mc_t are read below n_masked only)
+            HIP_OK(hipMemset(it->mc_r0.p, 0, rows * sizeof(double)));
         }
         own_rows.resize(n_fits);
         for (int f = 0; f < n_fits; ++f) own_rows[f] = f;
@@ -5316,7 +5349,8 @@ int vmx_fit_migrad(vmx_engine* e, const vmx_fit_spec* spec, int32_t n_fits, cons
     FitWorkspace& W = *e->fitws;
     const int fit_cap = n_max <= 4 ? 4 : n_max <= 8 ? 8 : n_max <= 16 ? 16 : 32;
     const size_t state_bytes = fit_state_bytes(fit_cap);
-    if (ensure(W.state, (size_t)F * state_bytes / sizeof(double)) || ensure(W.done, F) || ensure(W.spec, 1) || ensure(W.base, (size_t)F * P) || ensure(W.theta, cap * P) || ensure(W.chi2, cap) ||
+    // (W.state carries structs - phases, counts - among its doubles: exempt from poison, and cleared whole below)
+    if (ensure_structs(W.state, (size_t)F * state_bytes / sizeof(double)) || ensure(W.done, F) || ensure(W.spec, 1) || ensure(W.base, (size_t)F * P) || ensure(W.theta, cap * P) || ensure(W.chi2, cap) ||
         ensure(W.mock_row, F) || ensure(W.count, F) || ensure(W.offset, (size_t)F + 1) || ensure(W.mock, cap) || ensure(W.status, cap)) return -2;
     for (int s = 0; s < spec->n_stages; ++s) {
         const size_t n = spec->stage[s].n;
@@ -6462,7 +6496,8 @@ static int nested_run(const char* who, vmx_engine* e, const vmx_nested_spec* spe
     NsWorkspace& S = *e->nsws;
     if (ensure(S.live_u, (size_t)nlive * n) || ensure(S.live_lnl, nlive) || ensure(S.rank, nlive) || ensure(S.surv, nlive) ||
         ensure(S.killed, K) || ensure(S.mean, n) || ensure(S.cov, (size_t)n * n) || ensure(S.chol, (size_t)n * n) || ensure(S.lstar, 1) ||
-        ensure(S.th, (size_t)K * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, K) || ensure(S.dead_u, rec_rows * n) ||
+        ensure_structs(S.th, (size_t)K * sizeof(vmx_ns::Thread) / sizeof(double)) ||        // (vmx_ns::Thread: states and counts; exempt from poison)
+        ensure(S.slot, K) || ensure(S.dead_u, rec_rows * n) ||
         ensure(S.dead_lnl, rec_rows) || ensure(S.dead_n, rec_rows) || ensure(S.counters, 1))
         return -2;
     const int m = nlive - K;
@@ -6713,7 +6748,8 @@ static int nested_run_many(const char* who, vmx_engine* e, const vmx_nested_spec
     NsWorkspace& S = *e->nsws;
     if (ensure(S.live_u, EL * n) || ensure(S.live_lnl, EL) || ensure(S.rank, EL) || ensure(S.surv, EL) || ensure(S.killed, EK) ||
         ensure(S.mean, (size_t)E * n) || ensure(S.cov, (size_t)E * n * n) || ensure(S.chol, (size_t)E * n * n) || ensure(S.lstar, E) ||
-        ensure(S.th, EK * sizeof(vmx_ns::Thread) / sizeof(double)) || ensure(S.slot, EK) || ensure(S.dead_u, E * rec_rows * n) ||
+        ensure_structs(S.th, EK * sizeof(vmx_ns::Thread) / sizeof(double)) ||       // (vmx_ns::Thread: states and counts; exempt from poison)
+        ensure(S.slot, EK) || ensure(S.dead_u, E * rec_rows * n) ||
         ensure(S.dead_lnl, E * rec_rows) || ensure(S.dead_n, E * rec_rows) || ensure(S.counters, E) || ensure(S.set_ctl, (size_t)3 * E) ||
         ensure(S.set_count, E) || ensure(S.streams, E) || ensure(S.it0, E) || (mock_row && (ensure(S.mock_row, E) || ensure(S.mock, cap))))
         return -2;
@@ -7736,6 +7772,8 @@ int vmx_debug_math(vmx_engine* e, int32_t which, const double* x, int64_t n, dou
     return 0;
 }
 
+int vmx_debug_poison_scratch(int on) { return g_poison_scratch.exchange(on ? 1 : 0); }
+
 int vmx_matvec_device(vmx_engine* e, const double* d_A, int32_t rows, int32_t cols, const double* d_x, int32_t B,
                       double* d_y)
 {
@@ -7750,10 +7788,8 @@ int vmx_matvec_device(vmx_engine* e, const double* d_A, int32_t rows, int32_t co
         launch_product(e, KC_MATVEC, d_A, cols, 0, rows, cols, d_x, cols, 0, B, d_y, ldy, 0, 1, 0);
     } else {
         const size_t need = (size_t)8 * B * ldy;
-        if (e->mv_part.n < need) {
-            HIP_OK(hipStreamSynchronize(e->stream));
-            if (e->mv_part.alloc(need, false)) return -2;
-        }
+        if (e->mv_part.n < need) HIP_OK(hipStreamSynchronize(e->stream));
+        if (ensure(e->mv_part, need)) return -2;
         const int ns = launch_product(e, KC_MATVEC, d_A, cols, 0, rows, cols, d_x, cols, 0, B, e->mv_part.p, ldy, 0, 1, 8 * B);
         const int64_t count = (int64_t)B * ldy;
         hipLaunchKernelGGL(k_sum_slabs, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, e->cur, e->mv_part.p, d_y, count, ns);

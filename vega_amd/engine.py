@@ -4,6 +4,7 @@ This is the reference-side binding INTEGRATION.md describes: plain ``ctypes`` ag
 ``include/vegamx.h``.  There is no CPU fallback: if the library (or a GPU) is missing the engine
 fails loudly.
 """
+import contextlib
 import ctypes as C
 import os
 from pathlib import Path
@@ -419,6 +420,8 @@ def load_library():
     lib.vmx_debug_read.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dptr, C.c_int64]
     lib.vmx_debug_read.restype = C.c_int64
     lib.vmx_debug_math.argtypes = [C.c_void_p, C.c_int32, dptr, C.c_int64, dptr]
+    lib.vmx_debug_poison_scratch.argtypes = [C.c_int]
+    lib.vmx_debug_poison_scratch.restype = C.c_int
     lib.vmx_matvec_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                       C.c_void_p]
     lib.vmx_item_set_metal_static.argtypes = [C.c_void_p, C.c_int32, C.c_int32, dptr, C.c_int32]
@@ -445,6 +448,18 @@ def load_library():
     return lib
 
 
+@contextlib.contextmanager
+def poison_scratch(on=True):
+    """While the block runs, device scratch of plain doubles that a call takes without clearing it reads as NaN (include/vegamx.h:
+    vmx_debug_poison_scratch; process-wide, for tests).  The switch is put back on the way out."""
+    lib = load_library()
+    before = lib.vmx_debug_poison_scratch(1 if on else 0)
+    try:
+        yield
+    finally:
+        lib.vmx_debug_poison_scratch(before)
+
+
 def cluster_points(u, prev_id, next_id, device=0):
     """The clustering of one nested-sampling iteration on the device (include/vegamx.h: vmx_nested_cluster_points): ``u`` [m, n],
     ``prev_id`` [m].  dict(ids [m], k, n_clusters, next_id, mean [n_clusters, n], C [n_clusters, n, n]) - the entries of the same
@@ -469,7 +484,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_debug_poison_scratch', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 

@@ -368,6 +368,7 @@ class CorrItem:
         self._inv_masked_cov = inv_masked_cov
         self._log_cov_det = None
         self._chi2_matrix = None
+        self.__dict__.pop('_cholesky', None)        # (the mocks' factors of the covariance before: vega_amd/montecarlo.py)
 
 
 @dataclass
