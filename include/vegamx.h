@@ -686,7 +686,20 @@ int vmx_ensemble_cov_factor(vmx_engine* e, int32_t E, int32_t H, int32_t n, cons
  * Refused before anything runs (-1, vmx_last_error, engine and store untouched): a NULL engine or store; sizes outside the ranges
  * above, or whose product overflows; an attached store whose (E, W, n) is not the run's, or without room for the run's rows; rows
  * beyond the capacity (append); row0 + rows beyond the rows stored (fetch); first_row outside [0, rows) or a c that is not positive
- * and finite (summary). */
+ * and finite (summary).
+ *   order_stats   exact order statistics of every (ensemble, column) over the rows [first_row, rows) (vega_amd/csrc/
+ *             vmx_chain_select.h pins the order): with N = (rows - first_row) W values per column, values[e][d][r] is the
+ *             ranks[r]-th smallest of them (0 <= ranks[r] < N) in the total order -inf < ... < -0 < +0 < ... < +inf < NaN - a stored
+ *             value's own bits, or the canonical NaN.  The ranks may come in any order and may repeat; the answer does not depend
+ *             on the other ranks asked.  A radix select on the device, no floating-point operation: bitwise reproducible.
+ *   best      the largest lnL of every ensemble over the rows [first_row, rows) x walkers: lnl_max [E], its row [E] (counted from
+ *             row 0 of the store) and walker [E], and the position [E][n] there (position may be NULL).  A NaN never wins, -inf
+ *             may; among equal values the lowest (row, walker) wins.  An ensemble without a candidate (all NaN): row -1, walker
+ *             -1, lnl_max and position NaN.
+ * Both take one host wait, on the engine's stream, like summary.  Refused before anything runs (-1, vmx_last_error, engine and store
+ * untouched): a NULL store or a NULL output (position alone may be NULL); first_row outside [0, rows); n_ranks outside [1,
+ * VMX_CHAIN_MAX_RANKS]; a rank outside [0, N); N >= 2^31 (order_stats).  A failed allocation returns -2 and leaves the engine usable. */
+#define VMX_CHAIN_MAX_RANKS 32
 typedef struct vmx_chain_store vmx_chain_store;
 int vmx_chain_store_create(vmx_engine* e, int32_t E, int32_t W, int32_t n, int64_t capacity_rows, vmx_chain_store** out);
 int vmx_chain_store_destroy(vmx_chain_store* store);
@@ -696,6 +709,10 @@ int vmx_chain_store_append(vmx_chain_store* store, int64_t rows, const double* c
 int vmx_chain_store_fetch(vmx_chain_store* store, int64_t row0, int64_t rows, double* chain, double* chain_lnl);
 int vmx_chain_store_summary(vmx_chain_store* store, int64_t first_row, double c, int64_t* count, double* mean, double* covariance,
                             double* tau, int64_t* window);
+int vmx_chain_store_order_stats(vmx_chain_store* store, int64_t first_row, int32_t n_ranks, const int64_t* ranks,
+                                double* values /* [E][n][n_ranks] */);
+int vmx_chain_store_best(vmx_chain_store* store, int64_t first_row, double* lnl_max /* [E] */,
+                         int64_t* row /* [E], counted from row 0 of the store */, int32_t* walker /* [E] */, double* position /* [E][n] */);
 int vmx_ensemble_set_chain_store(vmx_engine* e, vmx_chain_store* store);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration

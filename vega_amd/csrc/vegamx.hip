@@ -10,6 +10,7 @@
 #include "vmx_nested.h"
 #include "vmx_smc.h"
 #include "vmx_chain.h"
+#include "vmx_chain_select.h"
 
 #include <atomic>
 #include <cmath>
@@ -1849,6 +1850,11 @@ struct vmx_chain_store {
     // the summary's scratch, grown on demand: series sums and means [E][W][n] each, the centred series [E][n][T][W], the results
     DevBuf<double> sums, centred, out;
     DevBuf<int64_t> window;
+    // the scratch of the order statistics and the best row (vmx_chain_select.h): the keys [E][n][T W] (64-bit keys held in a buffer
+    // of doubles, so that the poison mode reaches them: its fill is the NaN key), the values [E][n][ranks] or lnL [E] + position
+    // [E][n], and the best index [E]
+    DevBuf<double> sel_keys, sel_out;
+    DevBuf<int64_t> sel_index;
 };
 
 // Whether the quadratic term of the Q' form may run over the trapezoidal root of Q' (quad_build).  false: only with VMX_QUAD_ROOT=1.
@@ -6170,6 +6176,123 @@ __global__ __launch_bounds__(CHAIN_THREADS) void k_chain_acf(ChainDev C)
     }
 }
 
+// ---- order statistics and the best row of the store's rows (vmx_chain_select.h)
+static_assert(VMX_CHAIN_MAX_RANKS == vmx_select::MAX_RANKS, "ranks of an order-statistics call");
+static_assert(vmx_select::MAX_RANKS <= CHAIN_THREADS && vmx_select::MAX_RANKS * vmx_select::BINS * (int)sizeof(uint32_t) <= 32 * 1024,
+              "the select's histograms");
+
+struct SelectDev {
+    const double* x; const double* lnl; // [E][capacity][W][n], [E][capacity][W]
+    uint64_t* keys;                     // [E][n][T W]: the keys of a column, contiguous
+    uint64_t* values;                   // [E][n][U]: the bits of the order statistics
+    double* best_lnl; double* best_x;   // [E], [E][n] (best_x nullptr: not wanted)
+    int64_t* best_index;                // [E]: row W + walker from row 0 of the store, -1 for none
+    int64_t capacity, first, T;
+    int32_t E, W, n, U;
+    uint32_t ranks[vmx_select::MAX_RANKS];      // the U ranks asked, ascending and distinct
+};
+
+// The keys of the rows from `first` on, x[e][first + t][w][d] -> keys[e][d][t][w]: the twin of k_chain_centre, so that a
+// work-group of k_chain_select streams one contiguous column
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_keys(SelectDev C)
+{
+    const int64_t Wn = (int64_t)C.W * C.n, per = C.T * Wn, total = (int64_t)C.E * per;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = g / per, q = g % per, t = q / Wn, r = q % Wn;
+        const int w = (int)(r / C.n), d = (int)(r % C.n);
+        C.keys[((e * C.n + d) * C.T + t) * C.W + w] = vmx_select::key(C.x[(e * C.capacity + C.first) * Wn + q]);
+    }
+}
+
+// One work-group per (ensemble, column): eight passes of 8-bit digits, most significant first.  A pass counts the next digit of
+// every key whose leading bits are a prefix still alive among the ranks, one 256-bin histogram in LDS per distinct prefix (integer
+// atomics: the counts do not depend on their order; a wave whose keys all fall into one bin adds its count once), then a lane per
+// rank walks its histogram to the next digit and lane 0 regroups the prefixes.  The keys stream from L2 eight times.
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_select(SelectDev C)
+{
+    using namespace vmx_select;
+    __shared__ uint32_t hist[MAX_RANKS * BINS];
+    __shared__ uint64_t prefix[MAX_RANKS], group_prefix[MAX_RANKS];
+    __shared__ uint32_t left[MAX_RANKS];
+    __shared__ int group[MAX_RANKS];
+    __shared__ int groups;
+    const int tid = threadIdx.x, lane = tid & 63, U = C.U;
+    const int64_t N = C.T * C.W;
+    const uint64_t* keys = C.keys + (int64_t)blockIdx.x * N;
+    if (tid < U) { prefix[tid] = 0; left[tid] = C.ranks[tid]; }
+    __syncthreads();
+    if (tid == 0) groups = regroup(prefix, U, group, group_prefix);
+    __syncthreads();
+    for (int p = 0; p < PASSES; ++p) {
+        const int G = groups;
+        for (int q = tid; q < G * BINS; q += blockDim.x) hist[q] = 0;
+        __syncthreads();
+        for (int64_t base = 0; base < N; base += blockDim.x) {          // (every lane of a wave takes every turn: the ballots below)
+            const int64_t i = base + tid;
+            int slot = -1;
+            if (i < N) {
+                const uint64_t k = keys[i];
+                const int at = find_group(group_prefix, G, leading(k, p));
+                if (at >= 0) slot = at * BINS + digit(k, p);
+            }
+            const unsigned long long active = __ballot(slot >= 0);
+            if (active) {
+                const int leader = __ffsll(active) - 1;
+                const int slot0 = __shfl(slot, leader);
+                const unsigned long long same = __ballot(slot == slot0);
+                if (same == active) {
+                    if (lane == leader) atomicAdd(&hist[slot0], (uint32_t)__popcll(same));
+                } else if (slot >= 0) {
+                    atomicAdd(&hist[slot], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < U) prefix[tid] = (prefix[tid] << 8) | (uint64_t)walk(hist + group[tid] * BINS, left[tid]);
+        __syncthreads();
+        if (tid == 0) groups = regroup(prefix, U, group, group_prefix);
+        __syncthreads();
+    }
+    if (tid < U) C.values[(int64_t)blockIdx.x * U + tid] = unkey(prefix[tid]);
+}
+
+// One work-group per ensemble: the lanes stride over (row, walker) of lnl[e] from `first` on and keep their best candidate, an LDS
+// tree reduces them with vmx_select::wins (associative and commutative: the tree's shape does not matter), then the group copies
+// the winning position row
+__global__ __launch_bounds__(CHAIN_THREADS) void k_chain_best(SelectDev C)
+{
+    using namespace vmx_select;
+    __shared__ double value[CHAIN_THREADS];
+    __shared__ int64_t index[CHAIN_THREADS];
+    const int tid = threadIdx.x, e = blockIdx.x, W = C.W, n = C.n;
+    const double* lnl = C.lnl + (int64_t)e * C.capacity * W;
+    double best = 0.0;
+    int64_t at = -1;
+    for (int64_t q = C.first * W + tid; q < (C.first + C.T) * W; q += CHAIN_THREADS) {
+        const double v = lnl[q];
+        const int64_t i = v != v ? -1 : q;          // (vmx_select::candidate: a NaN is none)
+        if (wins(v, i, best, at)) { best = v; at = i; }
+    }
+    value[tid] = best;
+    index[tid] = at;
+    __syncthreads();
+    for (int s = CHAIN_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s && wins(value[tid + s], index[tid + s], value[tid], index[tid])) {
+            value[tid] = value[tid + s];
+            index[tid] = index[tid + s];
+        }
+        __syncthreads();
+    }
+    const int64_t won = index[0];
+    if (tid == 0) {
+        C.best_index[e] = won;
+        C.best_lnl[e] = won < 0 ? double_of(CANONICAL_NAN) : value[0];
+    }
+    if (C.best_x)
+        for (int d = tid; d < n; d += CHAIN_THREADS)
+            C.best_x[(int64_t)e * n + d] = won < 0 ? double_of(CANONICAL_NAN) : C.x[((int64_t)e * C.capacity * W + won) * n + d];
+}
+
 // bytes of `rows` rows of every ensemble must fit size_t: E capacity W n doubles
 static bool chain_fits(int64_t E, int64_t W, int64_t n, int64_t rows)
 {
@@ -6347,6 +6470,83 @@ int vmx_chain_store_summary(vmx_chain_store* s, int64_t first_row, double c, int
     if (window) HIP_OK(hipMemcpyAsync(window, C.window, En * sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     if (count) std::fill(count, count + E, T * W);
+    return 0;
+}
+
+// Scratch of the select through the helpers of the summary's: a fresh allocation when the buffer is too small, and under
+// vmx_debug_poison_scratch the fill of a buffer kept from an earlier, larger call too
+static int chain_scratch(DevBuf<double>& b, size_t count)
+{
+    if (b.p && b.n >= count) return poison_fill(b.p, b.n) ? -2 : 0;
+    return chain_alloc(b, count);
+}
+
+int vmx_chain_store_order_stats(vmx_chain_store* s, int64_t first_row, int32_t n_ranks, const int64_t* ranks, double* values)
+{
+    const std::string name("vmx_chain_store_order_stats");
+    REQUIRE(s && ranks && values, name + ": a store, ranks and values");
+    REQUIRE(first_row >= 0 && first_row < s->rows, name + ": first_row must be a stored row");
+    REQUIRE(n_ranks >= 1 && n_ranks <= VMX_CHAIN_MAX_RANKS, name + ": 1 <= n_ranks <= VMX_CHAIN_MAX_RANKS");
+    const int E = s->E, W = s->W, n = s->n;
+    const int64_t T = s->rows - first_row, N = T * W;
+    REQUIRE(vmx_select::count_fits(T, W), name + ": (rows - first_row) W must stay below 2^31");
+    for (int r = 0; r < n_ranks; ++r) REQUIRE(ranks[r] >= 0 && ranks[r] < N, name + ": a rank outside [0, (rows - first_row) W)");
+    int64_t sorted[vmx_select::MAX_RANKS];
+    const int U = vmx_select::distinct_ranks(ranks, n_ranks, sorted);
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const size_t En = (size_t)E * n;
+    if (chain_scratch(s->sel_keys, En * (size_t)N) || chain_scratch(s->sel_out, En * (size_t)U)) return -2;
+    SelectDev C{};
+    C.x = s->x.p; C.lnl = s->lnl.p;
+    C.keys = reinterpret_cast<uint64_t*>(s->sel_keys.p); C.values = reinterpret_cast<uint64_t*>(s->sel_out.p);
+    C.capacity = s->capacity; C.first = first_row; C.T = T; C.E = E; C.W = W; C.n = n; C.U = U;
+    for (int r = 0; r < U; ++r) C.ranks[r] = (uint32_t)sorted[r];
+    hipStream_t st = e->stream;
+    const int64_t total = (int64_t)En * N;
+    const int blocks = (int)std::min<int64_t>((total + CHAIN_THREADS - 1) / CHAIN_THREADS, 65536);
+    hipLaunchKernelGGL(k_chain_keys, dim3(blocks), dim3(CHAIN_THREADS), 0, st, C);
+    hipLaunchKernelGGL(k_chain_select, dim3((unsigned)En), dim3(CHAIN_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    std::vector<double> found(En * (size_t)U);
+    HIP_OK(hipMemcpyAsync(found.data(), s->sel_out.p, found.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    // the caller's order and repeats (bytes are copied: a value's bits stay its own)
+    int at[vmx_select::MAX_RANKS];
+    for (int r = 0; r < n_ranks; ++r) at[r] = (int)(std::lower_bound(sorted, sorted + U, ranks[r]) - sorted);
+    for (size_t q = 0; q < En; ++q)
+        for (int r = 0; r < n_ranks; ++r) std::memcpy(values + q * n_ranks + r, found.data() + q * U + at[r], sizeof(double));
+    return 0;
+}
+
+int vmx_chain_store_best(vmx_chain_store* s, int64_t first_row, double* lnl_max, int64_t* row, int32_t* walker, double* position)
+{
+    const std::string name("vmx_chain_store_best");
+    REQUIRE(s && lnl_max && row && walker, name + ": a store, lnl_max, row and walker");
+    REQUIRE(first_row >= 0 && first_row < s->rows, name + ": first_row must be a stored row");
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const int E = s->E, W = s->W, n = s->n;
+    const size_t En = (size_t)E * n;
+    if (chain_scratch(s->sel_out, (size_t)E + En) ||
+        (s->sel_index.n < (size_t)E && s->sel_index.alloc((size_t)E, false) && ((void)hipGetLastError(), true)))
+        return -2;
+    SelectDev C{};
+    C.x = s->x.p; C.lnl = s->lnl.p;
+    C.best_lnl = s->sel_out.p; C.best_x = position ? s->sel_out.p + E : nullptr; C.best_index = s->sel_index.p;
+    C.capacity = s->capacity; C.first = first_row; C.T = s->rows - first_row; C.E = E; C.W = W; C.n = n;
+    hipStream_t st = e->stream;
+    hipLaunchKernelGGL(k_chain_best, dim3(E), dim3(CHAIN_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    std::vector<int64_t> index((size_t)E);
+    HIP_OK(hipMemcpyAsync(lnl_max, C.best_lnl, (size_t)E * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(index.data(), C.best_index, (size_t)E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (position) HIP_OK(hipMemcpyAsync(position, C.best_x, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (int k = 0; k < E; ++k) {
+        row[k] = index[k] < 0 ? -1 : index[k] / W;
+        walker[k] = index[k] < 0 ? -1 : (int32_t)(index[k] % W);
+    }
     return 0;
 }
 

@@ -381,6 +381,8 @@ def load_library():
     lib.vmx_chain_store_append.argtypes = [C.c_void_p, C.c_int64, dptr, dptr]
     lib.vmx_chain_store_fetch.argtypes = [C.c_void_p, C.c_int64, C.c_int64, dptr, dptr]
     lib.vmx_chain_store_summary.argtypes = [C.c_void_p, C.c_int64, C.c_double, i64p, dptr, dptr, dptr, i64p]
+    lib.vmx_chain_store_order_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, i64p, dptr]
+    lib.vmx_chain_store_best.argtypes = [C.c_void_p, C.c_int64, dptr, i64p, C.POINTER(C.c_int32), dptr]
     lib.vmx_ensemble_set_chain_store.argtypes = [C.c_void_p, C.c_void_p]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
@@ -484,7 +486,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_debug_poison_scratch', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_chain_store_order_stats', 'vmx_chain_store_best', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_debug_poison_scratch', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -798,6 +800,32 @@ class ChainStore:
         if tau:
             with np.errstate(divide='ignore', invalid='ignore'):
                 out.update(tau=t, window=window, n_eff=count.astype(np.float64) / np.max(t, axis=1))
+        return out
+
+    def order_statistics(self, ranks, first=0):
+        """Exact order statistics of every (ensemble, column) over the rows from ``first`` on, found where they are
+        (vmx_chain_store_order_stats, vega_amd/csrc/vmx_chain_select.h; :func:`vega_amd.ensemble.chain_order_statistics` is the
+        same bits): [E, n, R], entry r the ``ranks[r]``-th smallest of the (rows - first) W values - 1 .. 32 ranks in any order,
+        repeats allowed."""
+        ranks = np.ascontiguousarray(np.atleast_1d(ranks), dtype=np.int64)
+        if ranks.ndim != 1:
+            raise ValueError('ranks: a list of whole numbers')
+        values = np.empty((self.E, self.n, max(ranks.size, 1)))
+        self.engine._check(self.engine.lib.vmx_chain_store_order_stats(
+            self._handle(), int(first), ranks.size, ranks.ctypes.data_as(C.POINTER(C.c_int64)), _dp(values)))
+        return values
+
+    def best(self, first=0, position=True):
+        """The best row of every ensemble over the rows from ``first`` on (vmx_chain_store_best;
+        :func:`vega_amd.ensemble.chain_best` is the same numbers): ``dict(lnl_max [E], best [E, n], best_row [E] (from row 0 of
+        the store), best_walker [E])``; without ``position`` no ``best``."""
+        top, row, walker = np.empty(self.E), np.zeros(self.E, dtype=np.int64), np.zeros(self.E, dtype=np.int32)
+        at = np.empty((self.E, self.n)) if position else None
+        self.engine._check(self.engine.lib.vmx_chain_store_best(
+            self._handle(), int(first), _dp(top), row.ctypes.data_as(C.POINTER(C.c_int64)), _ip(walker), None if at is None else _dp(at)))
+        out = dict(lnl_max=top, best_row=row, best_walker=walker)
+        if position:
+            out['best'] = at
         return out
 
     def close(self):

@@ -1257,6 +1257,123 @@ def chain_summary(chain, first=0, c=5, lag_block=CHAIN_LAG_BLOCK, moments=True):
     return {key: np.array([p[key] for p in parts]) for key in parts[0]}
 
 
+# ------------------------------------------------------------------ order statistics and the best row (vmx_chain_select.h, restated)
+CHAIN_MAX_RANKS = 32
+CHAIN_MAX_QUANTILES = 16
+SELECT_KEYS = ('q', 'quantiles', 'lnl_max', 'best', 'best_row', 'best_walker')
+_SIGN, _NAN_KEY, _CANONICAL_NAN = np.uint64(1 << 63), np.uint64(2**64 - 1), np.uint64(0x7ff8000000000000)
+
+
+def chain_keys(x):
+    """The order-preserving 64-bit keys of doubles (vmx_select::key): all ones for every NaN of either sign, else ``~b`` if the
+    sign bit of the bits ``b`` is set, else ``b | 1 << 63``.  Unsigned order of the keys: -inf < ... < -0 < +0 < ... < +inf < NaN."""
+    b = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    k = np.where((b & _SIGN) != 0, ~b, b | _SIGN)
+    return np.where((b & ~_SIGN) > np.uint64(0x7ff0000000000000), _NAN_KEY, k)
+
+
+def chain_unkeys(k):
+    """The doubles of keys (vmx_select::unkey): a value's own bits, the canonical NaN for the NaN key."""
+    k = np.ascontiguousarray(k, dtype=np.uint64)
+    return np.where(k == _NAN_KEY, _CANONICAL_NAN, np.where((k & _SIGN) != 0, k ^ _SIGN, ~k)).view(np.float64)
+
+
+def _select_rows(chain, first, min_walkers=1):
+    x = np.asarray(chain, dtype=np.float64)
+    if x.ndim not in (3, 4) or x.shape[-1] < 1 or x.shape[-2] < min_walkers:
+        raise ValueError('chain [rows, W, n] or [E, rows, W, n]')
+    first = int(first)
+    if not 0 <= first < x.shape[-3]:
+        raise ValueError(f'first: a recorded row, 0 .. {x.shape[-3] - 1}')
+    return (x[None] if x.ndim == 3 else x), first, x.ndim == 3
+
+
+def chain_order_statistics(chain, ranks, first=0):
+    """Exact order statistics of every column of a recorded chain [rows, W, n] (or [E, rows, W, n]) over the rows from ``first``
+    on, as vmx_chain_store_order_stats computes them where the chain is recorded - vega_amd/csrc/vmx_chain_select.h restated, bit
+    for bit: with N = (rows - first) W values per (ensemble, column), entry r is the ``ranks[r]``-th smallest (0 <= rank < N) in
+    the total order of :func:`chain_keys` - NaNs last as in ``np.sort``, -0 before +0 - as that value's own bits, or the
+    canonical NaN.  The keys are sorted, not the doubles.  ``ranks``: 1 .. 32 of them, in any order, repeats allowed.
+    Returns [n, R] (or [E, n, R])."""
+    x, first, single = _select_rows(chain, first)
+    ranks = np.atleast_1d(np.asarray(ranks, dtype=np.int64))
+    E, rows, W, n = x.shape
+    N = (rows - first) * W
+    if ranks.ndim != 1 or not 1 <= ranks.size <= CHAIN_MAX_RANKS:
+        raise ValueError(f'ranks: 1 .. {CHAIN_MAX_RANKS} of them')
+    if np.any(ranks < 0) or np.any(ranks >= N):
+        raise ValueError(f'ranks: 0 .. {N - 1}')
+    keys = np.moveaxis(chain_keys(x[:, first:]), 3, 1).reshape(E, n, N)
+    out = chain_unkeys(np.sort(keys, axis=-1)[:, :, ranks])
+    return out[0] if single else out
+
+
+def chain_best(chain, chain_lnl, first=0):
+    """The best recorded row of a chain [rows, W, n] with lnL [rows, W] (or [E, rows, W, n] and [E, rows, W]) over the rows from
+    ``first`` on, as vmx_chain_store_best finds it (vega_amd/csrc/vmx_chain_select.h): ``dict(lnl_max, best [n], best_row,
+    best_walker)``, per ensemble with a leading E.  A NaN lnL never wins, -inf may; among equal values the lowest (row, walker)
+    wins; ``best_row`` counts from row 0 of the chain.  Without a candidate (all NaN): row -1, walker -1, lnL and position NaN."""
+    x, first, single = _select_rows(chain, first)
+    lnl = np.asarray(chain_lnl, dtype=np.float64)
+    lnl = lnl[None] if single else lnl
+    if lnl.shape != x.shape[:3]:
+        raise ValueError('chain_lnl [rows, W] (or [E, rows, W]) of the chain')
+    E, rows, W, n = x.shape
+    top, at = np.full(E, np.nan), np.full((E, n), np.nan)
+    row, walker = np.full(E, -1, dtype=np.int64), np.full(E, -1, dtype=np.int32)
+    for e in range(E):
+        flat = lnl[e, first:].reshape(-1)
+        valid = ~np.isnan(flat)
+        if not np.any(valid):
+            continue
+        index = int(np.argmax(valid & (flat == flat[valid].max()))) + first * W        # (the first of the equal ones)
+        row[e], walker[e] = index // W, index % W
+        top[e], at[e] = lnl[e, row[e], walker[e]], x[e, row[e], walker[e]]
+    out = dict(lnl_max=top, best=at, best_row=row, best_walker=walker)
+    return {key: (val[0].item() if val[0].ndim == 0 else val[0]) for key, val in out.items()} if single else out
+
+
+def check_quantiles(q):
+    """``q`` as a float array: 1 .. 16 values in [0, 1] (ValueError otherwise)."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if q.ndim != 1 or not 1 <= q.size <= CHAIN_MAX_QUANTILES or not np.all((q >= 0.0) & (q <= 1.0)):
+        raise ValueError(f'quantiles: 1 .. {CHAIN_MAX_QUANTILES} values in [0, 1]')
+    return q
+
+
+def quantile_ranks(q, N):
+    """What the quantiles ``q`` of N values read: ``(ranks, lo, hi, g)`` with ``h = q (N - 1)`` in double, ``floor(h)`` and
+    ``min(floor(h) + 1, N - 1)`` as places ``lo`` / ``hi`` in the sorted, distinct ``ranks`` (at most 2 Q <= 32 of them), and the
+    fraction ``g = h - floor(h)``."""
+    q = check_quantiles(q)
+    h = q * np.float64(N - 1)
+    low = np.floor(h)
+    g = h - low
+    low = low.astype(np.int64)
+    high = np.minimum(low + 1, N - 1)
+    ranks = np.unique(np.concatenate([low, high]))
+    return ranks, np.searchsorted(ranks, low), np.searchsorted(ranks, high), g
+
+
+def quantiles_of_order_statistics(stats, lo, hi, g):
+    """``x_lo + g (x_hi - x_lo)`` over order statistics [..., R]: every operation a separately rounded IEEE one."""
+    x_lo, x_hi = stats[..., lo], stats[..., hi]
+    with np.errstate(invalid='ignore', over='ignore'):
+        return x_lo + g * (x_hi - x_lo)
+
+
+def chain_quantiles(chain, q, first=0):
+    """The quantiles ``q`` (1 .. 16 values in [0, 1]) of every column of a recorded chain over the rows from ``first`` on,
+    [n, Q] (or [E, n, Q]): host arithmetic over exact order statistics (:func:`chain_order_statistics`), so the device and the
+    ``python`` driver give the same bits.  With N = (rows - first) W values: ``h = q (N - 1)`` in double, ``lo = floor(h)``,
+    ``hi = min(lo + 1, N - 1)``, ``g = h - lo`` and the value ``x_lo + g (x_hi - x_lo)`` - ``np.quantile(method='linear')`` up
+    to the rounding of the two fractional ranks."""
+    x, first, single = _select_rows(chain, first)
+    ranks, lo, hi, g = quantile_ranks(q, (x.shape[1] - first) * x.shape[2])
+    out = quantiles_of_order_statistics(chain_order_statistics(x, ranks, first), lo, hi, g)
+    return out[0] if single else out
+
+
 # ------------------------------------------------------------------ what every sampler here sets up the same way
 _NO_LIMITS = ('Sampler needs well defined prior limits. You passed a None. Please give numbers, or'
               ' just say par_name = True to use defaults.')
@@ -1648,23 +1765,62 @@ class StretchSampler(EngineSampler):
             return self._store.rows
         return sum(part.shape[len(self._lead)] for part in self._chain_lnl)
 
-    def summary(self, discard=0, c=5):
+    def summary(self, discard=0, c=5, quantiles=None):
         """``dict(count, mean, sd, covariance, tau, window, n_eff)`` of the recorded rows from ``discard`` on (per ensemble for a
         set: arrays with a leading E): mean and covariance (ddof 1) over rows x walkers, emcee's integrated autocorrelation time
         with its window, n_eff = count / max tau.  With the rows on the device (``chain='device'``, device driver) it is computed
         there (vmx_chain_store_summary) and a few numbers per ensemble cross to the host; otherwise it is
-        :func:`chain_summary` over the host rows - the same numbers bit for bit."""
+        :func:`chain_summary` over the host rows - the same numbers bit for bit.  ``quantiles=q`` adds the keys ``q``,
+        ``quantiles`` [(E,) n, Q] (:meth:`quantiles`) and ``lnl_max``, ``best``, ``best_row``, ``best_walker`` (:meth:`best`);
+        without it the dict is what it was."""
+        if quantiles is not None:
+            quantiles = check_quantiles(quantiles)
         if self._store is not None:
             out = self._store.summary(int(discard), c)
-            return out if self._lead else {key: (val[0].item() if val[0].ndim == 0 else val[0]) for key, val in out.items()}
-        axis = len(self._lead)
-        parts = self._chain
-        if not parts:
-            raise ValueError('summary: no recorded rows')
-        out = chain_summary(np.concatenate(parts, axis=axis), int(discard), c)
-        if not self._lead:
-            out['n_eff'] = float(out['n_eff'])
+            out = out if self._lead else {key: (val[0].item() if val[0].ndim == 0 else val[0]) for key, val in out.items()}
+        else:
+            axis = len(self._lead)
+            parts = self._chain
+            if not parts:
+                raise ValueError('summary: no recorded rows')
+            out = chain_summary(np.concatenate(parts, axis=axis), int(discard), c)
+            if not self._lead:
+                out['n_eff'] = float(out['n_eff'])
+        if quantiles is not None:
+            out.update(q=quantiles, quantiles=self.quantiles(quantiles, discard), **self.best(discard))
         return out
+
+    def _host_rows(self, what):
+        """The recorded rows on the host as one block each, positions and lnL, for the restatements."""
+        if not self._chain:
+            raise ValueError(f'{what}: no recorded rows')
+        axis = len(self._lead)
+        return np.concatenate(self._chain, axis=axis), np.concatenate(self._chain_lnl, axis=axis)
+
+    def quantiles(self, q, discard=0):
+        """The quantiles ``q`` (1 .. 16 values in [0, 1]) of every sampled parameter over the recorded rows from ``discard`` on,
+        [n, Q] (a set: [E, n, Q]), as :func:`chain_quantiles` defines them: linear interpolation between exact order statistics.
+        With the rows on the device (``chain='device'``, device driver) the order statistics are found there
+        (vmx_chain_store_order_stats) and at most 2 Q numbers per ensemble and parameter cross to the host; otherwise they come
+        from the host rows - the same bits, since the interpolation is the same host arithmetic."""
+        q, discard = check_quantiles(q), int(discard)
+        if self._store is None:
+            return chain_quantiles(self._host_rows('quantiles')[0], q, discard)
+        rows = self._store.rows
+        if not 0 <= discard < rows:
+            raise ValueError(f'discard: a recorded row, 0 .. {rows - 1}')
+        ranks, lo, hi, g = quantile_ranks(q, (rows - discard) * self.W)
+        out = quantiles_of_order_statistics(self._store.order_statistics(ranks, discard), lo, hi, g)
+        return out if self._lead else out[0]
+
+    def best(self, discard=0):
+        """``dict(lnl_max, best [n], best_row, best_walker)`` of the recorded rows from ``discard`` on (a set: arrays with a
+        leading E): the largest recorded lnL and where it was - the lowest (row, walker) among equal ones, ``best_row`` counted
+        from the first recorded row.  On the device with the rows there (vmx_chain_store_best), else :func:`chain_best`."""
+        if self._store is None:
+            return chain_best(*self._host_rows('best'), int(discard))
+        out = self._store.best(int(discard))
+        return out if self._lead else {key: (val[0].item() if val[0].ndim == 0 else val[0]) for key, val in out.items()}
 
     def _tau_now(self, discard, c):
         """tau [(E,) n] and the rows used of the check of :meth:`run_until`: E n doubles from the device."""
@@ -2349,6 +2505,12 @@ class TemperedEnsemble(EnsembleSet):
     def summary(self, *args, **kwargs):
         raise ValueError('summary: per rung, chain_summary(run.get_chain(rung=...))')
 
+    def quantiles(self, *args, **kwargs):
+        raise ValueError('quantiles: per rung, chain_quantiles(run.get_chain(rung=...), q)')
+
+    def best(self, *args, **kwargs):
+        raise ValueError('best: per rung, chain_best(run.get_chain(rung=...), run.get_log_lik(rung=...))')
+
     @property
     def swap_fraction(self):
         """The accepted fraction of the swaps proposed between the rungs t and t + 1, [G, T - 1] (nan before the first sweep)."""
@@ -2490,7 +2652,8 @@ def sampler_settings(main_config, sample_params):
     DE, snooker and cov moves; absent: the stretch move, and no such key), ``derived`` (True | False; absent means False: the chain files are what
     they were), ``replicas`` (R >= 1 independent copies on Philox streams 0 .. R - 1, merged afterwards:
     :mod:`vega_amd.replicas`) and ``ntemps`` with ``beta_min`` / ``swap_every`` and ``adapt`` with ``adapt_steps`` / ``adaptation_lag`` / ``adaptation_time``
-    (:func:`_parse_tempering`: parallel tempering, and its adaptive ladder);
+    (:func:`_parse_tempering`: parallel tempering, and its adaptive ladder) and ``quantiles`` (:func:`_parse_quantiles`: with
+    ``mocks``, every parameter's quantiles and best point per mock, found on the device);
     with ``sampler = Nested`` the ``[Nested]`` settings instead
     (:func:`vega_amd.nested.nested_settings`), with ``sampler = SMC`` the ``[SMC]`` ones (:func:`vega_amd.smc.smc_settings`)."""
     control = main_config['control'] if 'control' in main_config else {}
@@ -2536,7 +2699,30 @@ def sampler_settings(main_config, sample_params):
             raise ValueError('[Ensemble] together: True or False') from None
     _parse_tempering(sec, out)
     _parse_converge(sec, out)
+    _parse_quantiles(sec, out)
     return out
+
+
+def _parse_quantiles(sec, out):
+    """``quantiles = q0 q1 ...`` of ``[Ensemble]`` (1 .. 16 values in [0, 1], e.g. ``0.025 0.16 0.5 0.84 0.975``) into
+    ``out['quantiles']``: with ``mocks = M`` the run keeps its chains on the device (``summaries='device'``) and the table
+    ``mock_posteriors.fits`` gains every parameter's quantiles and best point.  Without the key nothing is added.  Refused without
+    ``mocks`` (a single run's chain file is there for getdist) and with ``ntemps``."""
+    if 'quantiles' not in sec:
+        return
+    try:
+        q = [float(v) for v in sec.get('quantiles').replace(',', ' ').split()]
+    except ValueError:
+        raise ValueError('[Ensemble] quantiles: numbers in [0, 1]') from None
+    try:
+        q = check_quantiles(q) if q else check_quantiles(np.empty(0))
+    except ValueError as err:
+        raise ValueError(f'[Ensemble] {err}') from None
+    if 'ntemps' in out:
+        raise ValueError('[Ensemble] quantiles and ntemps do not combine')
+    if 'mocks' not in out:
+        raise ValueError('[Ensemble] quantiles go with mocks = M: a single run writes its chain for getdist')
+    out['quantiles'] = [float(v) for v in q]
 
 
 _CONVERGE_KEYS = ('tau_factor', 'tau_rtol', 'check_every')
@@ -2909,7 +3095,8 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
         return sampler
     sampler = mc.sample_mocks(mocks=mocks, walkers=cfg['walkers'], steps=cfg['steps'], thin=cfg['thin'], seed=cfg['seed'],
                               scale=scale, sample_params=sample_params, driver=cfg['driver'], **moves_arguments(cfg),
-                              **(dict(summaries='device', converge=cfg['converge']) if 'converge' in cfg else {}))
+                              **(dict(summaries='device') if 'converge' in cfg or 'quantiles' in cfg else {}),
+                              **{key: cfg[key] for key in ('converge', 'quantiles') if key in cfg})
     if 'converge' in cfg:
         write_convergence(sampler, cfg['path'], cfg['name'])
     chain, lnl = sampler.get_chain(), sampler.get_log_lik()

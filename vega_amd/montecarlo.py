@@ -471,7 +471,7 @@ class MonteCarlo:
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
                      ess=0.5, sweeps=None, n_total=None, recycle=False, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                     tune_steps=None, cov_scale=None, summaries='host', converge=None):
+                     tune_steps=None, cov_scale=None, summaries='host', converge=None, quantiles=None):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -496,6 +496,11 @@ class MonteCarlo:
         (:meth:`vega_amd.ensemble.StretchSampler.run_until`) with ``steps`` as the maximum; ``mc_posteriors`` gains ``converged``
         and ``converged_at`` [M] and the table two columns of those names, ``steps`` is the steps run, and a ``burn`` left to
         the default is a third of them.
+        ``quantiles=q`` (1 .. 16 values in [0, 1]; with either ``summaries``): ``mc_posteriors`` gains ``quantiles`` (the q),
+        ``quantile_values`` [M, n, Q] (:meth:`vega_amd.ensemble.StretchSampler.quantiles` of the rows after ``burn``), ``lnl_max``
+        [M] and ``best`` [M, n] (the best recorded point of every mock) and the table their columns; with ``summaries='device'``
+        they are found in the chain store (vmx_chain_store_order_stats, vmx_chain_store_best), so that with ``keep_chains=False``
+        still no chain crosses to the host - the same bits as the host rows give.
 
         ``sampler='smc'``: the evidence and an equal-weight posterior of every mock instead, M tempered SMC runs advanced together
         (:class:`vega_amd.smc.SMCSet`: run m on mock m and stream m, ``particles`` - default 1024 - ``ess`` and ``sweeps`` its
@@ -523,9 +528,14 @@ class MonteCarlo:
             raise ValueError("sample_mocks: summaries and converge go with sampler='ensemble'")
         if converge is not None and set(converge) - {'tau_factor', 'tau_rtol', 'check_every'}:
             raise ValueError('sample_mocks: converge takes tau_factor, tau_rtol and check_every')
+        if quantiles is not None:
+            if sampler != 'ensemble':
+                raise ValueError("sample_mocks: quantiles go with sampler='ensemble'")
+            from .ensemble import check_quantiles
+            quantiles = check_quantiles(quantiles)
         return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                                   fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle, moves_kw=moves_kw,
-                                  summaries=summaries, converge=converge)
+                                  summaries=summaries, converge=converge, quantiles=quantiles)
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
@@ -548,7 +558,7 @@ class MonteCarlo:
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                       max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False, moves_kw=None, summaries='host',
-                      converge=None):
+                      converge=None, quantiles=None):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -691,6 +701,10 @@ class MonteCarlo:
             names=list(sampler.names), mean=moments['mean'], sd=moments['sd'], covariance=moments['covariance'], tau=moments['tau'],
             acceptance=sampler.acceptance_fraction.mean(axis=1), n_eff=moments['n_eff'],
             steps=steps, burn=burn, thin=thin, walkers=walkers, seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats))
+        if quantiles is not None:       # (on the device when the rows are there, from the host rows otherwise: the same bits)
+            top = sampler.best(discard=first)
+            self.mc_posteriors.update(quantiles=quantiles.copy(), quantile_values=sampler.quantiles(quantiles, discard=first),
+                                      lnl_max=top['lnl_max'], best=top['best'])
         if converge is not None:
             self.mc_posteriors.update(converged=np.asarray(sampler.convergence['converged']).copy(),
                                       converged_at=np.asarray(sampler.convergence['converged_at']).copy())
@@ -708,7 +722,9 @@ class MonteCarlo:
         """`mock_posteriors[_<cpu_id>].fits` under ``directory``: one table ``POSTERIORS`` with one row per mock of
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
         ``n_eff``, and the vector column ``covariance`` (n x n, row-major) - the run's settings in the header (after
-        ``sample_mocks(converge=...)`` also the columns ``converged`` and ``converged_at``).  After
+        ``sample_mocks(converge=...)`` also the columns ``converged`` and ``converged_at``; after ``sample_mocks(quantiles=q)`` also
+        ``<par>_q<k>`` for k = 0 .. Q - 1 and ``<par>_best`` per parameter, ``lnl_max``, and the header keys ``NQUANT`` and
+        ``QUANT<k>``).  After
         ``sample_mocks(sampler='smc')`` the columns are ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``stages``,
         ``status``, ``covariance`` and the header keys ``SAMPLER``, ``PARTICLE``, ``ESS``, ``SWEEPS``, ``SEED`` (with ``n_total`` or
         ``recycle`` also the columns ``points``, ``n_eff``, ``log_z_recycled`` and the header keys ``NTOTAL`` and ``RECYCLE``); after
@@ -759,6 +775,14 @@ class MonteCarlo:
                 cols += [('converged', 'K', np.asarray(post['converged'], dtype=np.int64)),
                          ('converged_at', 'K', np.asarray(post['converged_at'], dtype=np.int64))]
             header = {'STEPS': post['steps'], 'BURN': post['burn'], 'THIN': post['thin'], 'WALKERS': post['walkers'], 'SEED': post['seed']}
+            if 'quantiles' in post:
+                q = np.asarray(post['quantiles'], dtype=np.float64)
+                for j, nm in enumerate(names):
+                    cols += [(f'{nm}_q{k}', 'D', np.ascontiguousarray(post['quantile_values'][:, j, k])) for k in range(q.size)]
+                    cols += [(f'{nm}_best', 'D', np.ascontiguousarray(post['best'][:, j]))]
+                cols += [('lnl_max', 'D', post['lnl_max'])]
+                header['NQUANT'] = int(q.size)
+                header.update({f'QUANT{k}': float(v) for k, v in enumerate(q)})
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)
         path = directory / ('mock_posteriors.fits' if cpu_id is None else f'mock_posteriors_{cpu_id}.fits')
