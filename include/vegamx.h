@@ -714,6 +714,44 @@ int vmx_chain_store_order_stats(vmx_chain_store* store, int64_t first_row, int32
 int vmx_chain_store_best(vmx_chain_store* store, int64_t first_row, double* lnl_max /* [E] */,
                          int64_t* row /* [E], counted from row 0 of the store */, int32_t* walker /* [E] */, double* position /* [E][n] */);
 int vmx_ensemble_set_chain_store(vmx_engine* e, vmx_chain_store* store);
+/* A sample store: E weighted, ragged sample sets over n columns kept on the device - the posterior samples of nested or SMC runs -
+ * positions [E][capacity][n], lnL [E][capacity] and weights [E][capacity], and reduced there (vega_amd/csrc/vmx_chain_weighted.h
+ * pins every sum and the order statistic).  Set e has count[e] rows, 0 <= count[e] <= capacity; nothing behind them is ever read.
+ * A store belongs to the engine it was created on and is destroyed with it at the latest.
+ *   create    E >= 1, 1 <= n <= VMX_ENS_MAXN, 0 <= capacity_rows < 2^31; every set starts empty.
+ *   put       replaces set `set` by `count` rows from the host, x [count][n], lnl [count] and w [count]; count 0 empties it.  The
+ *             weights need not sum to 1; each must be finite and >= 0 (they are scanned here, where the rows are).
+ *   counts    the rows of every set [E].
+ *   fetch     the rows of set `set`, x [count][n], lnl [count] and w [count]; any pointer may be NULL.
+ *   summary   per set: S [E] (the sum of the weights), n_eff [E] (Kish: 1 / sum p^2 with p = w / S), mean [E][n], covariance
+ *             [E][n][n] (two passes, sum p dx dx^T / (1 - sum p^2)), total [E] (M, the sum of the integer weights m = floor(w /
+ *             w_max 2^32)) and w_max [E].  Every sum of doubles is a stride-halving tree whose shape depends on count alone.  NaN,
+ *             not an error, where a set cannot say: count = 0 or S = 0 (mean, covariance, n_eff); one row with all the weight
+ *             (covariance).
+ *   order_stats   weighted order statistics of every (set, column): values[e][d][r] is the smallest stored value v of column d, in
+ *             the total order -inf < ... < -0 < +0 < ... < +inf < NaN, with sum_{x <= v} m >= targets[e][r] - a stored value's own
+ *             bits, or the canonical NaN - for 1 <= targets[e][r] <= M_e, in any order, repeats allowed.  The inverted-CDF quantile
+ *             q of set e is the value at max(1, ceil(q M_e)).  A radix select over integer sums: no floating-point operation once
+ *             the integer weights are made, bitwise reproducible.  A set with M = 0 ignores its targets and answers NaN.
+ *   best      the largest lnL of every set: lnl_max [E], its row index [E] and the position [E][n] there (position may be NULL).  A
+ *             NaN never wins, ties go to the lowest row; a set without a candidate: index -1, lnl_max and position NaN.
+ * summary, order_stats and best take one host wait each, on the engine's stream.  Refused before anything runs (-1, vmx_last_error,
+ * engine and store untouched): a NULL engine, store or output (position and the pointers of fetch may be NULL); sizes outside the
+ * ranges above; a set outside [0, E); count beyond the capacity; a weight that is negative, NaN or infinite; n_targets outside [1,
+ * VMX_SAMPLE_MAX_TARGETS]; a target of 0 or above M_e for a set with M_e > 0.  A failed allocation returns -2 and leaves the engine
+ * usable. */
+#define VMX_SAMPLE_MAX_TARGETS 16
+typedef struct vmx_sample_store vmx_sample_store;
+int vmx_sample_store_create(vmx_engine* e, int32_t E, int32_t n, int64_t capacity_rows, vmx_sample_store** out);
+int vmx_sample_store_destroy(vmx_sample_store* store);
+int vmx_sample_store_put(vmx_sample_store* store, int32_t set, int64_t count, const double* x, const double* lnl, const double* w);
+int vmx_sample_store_counts(vmx_sample_store* store, int64_t* counts /* [E] */);
+int vmx_sample_store_fetch(vmx_sample_store* store, int32_t set, double* x, double* lnl, double* w);
+int vmx_sample_store_summary(vmx_sample_store* store, double* S, double* n_eff, double* mean, double* covariance, uint64_t* total,
+                             double* w_max);
+int vmx_sample_store_order_stats(vmx_sample_store* store, int32_t n_targets, const uint64_t* targets /* [E][n_targets] */,
+                                 double* values /* [E][n][n_targets] */);
+int vmx_sample_store_best(vmx_sample_store* store, double* lnl_max /* [E] */, int64_t* index /* [E] */, double* position /* [E][n] */);
 /* Evidence where the live points live: nested sampling (Skilling 2006) by slice sampling in the whitened unit cube (the scheme of
  * PolyChord, which the reference runs in bin/run_vega_mpi.py), every decision pinned in vega_amd/csrc/vmx_nested.h.  An iteration
  * kills the K live points of lowest lnL, whitens with the survivors' covariance and lets K threads each walk num_repeats slice

@@ -11,6 +11,7 @@
 #include "vmx_smc.h"
 #include "vmx_chain.h"
 #include "vmx_chain_select.h"
+#include "vmx_chain_weighted.h"
 
 #include <atomic>
 #include <cmath>
@@ -1857,6 +1858,25 @@ struct vmx_chain_store {
     DevBuf<int64_t> sel_index;
 };
 
+// A sample store (vmx_sample_store_*; vmx_chain_weighted.h): E weighted, ragged sample sets on the device and the scratch of their
+// reductions
+struct vmx_sample_store {
+    vmx_engine* engine = nullptr;
+    int E = 0, n = 0;
+    int64_t capacity = 0;
+    DevBuf<double> x, lnl, w;           // [E][capacity][n], [E][capacity], [E][capacity]
+    DevBuf<int64_t> counts;             // [E]: the rows of every set, where the kernels read them
+    std::vector<int64_t> h_counts;      // ... and where the entries check them
+    std::vector<uint64_t> h_total;      // [E]: M of every set as put computed it on the host (the bound of a target)
+    // scratch, grown on demand (64-bit integers held in buffers of doubles, so that the poison mode reaches them): the integer
+    // weights [E][capacity], the trees' terms [E][padded(capacity) / 2], w_max / S / s2 / M / mean / covariance [E][4 + n + n n],
+    // the keys [E][n][capacity], the targets [E][U], the values [E][n][U] or lnL [E] + position [E][n], the best index [E] (the one
+    // buffer outside those helpers: an int64 buffer like the chain store's sel_index - integers are never poisoned, and
+    // k_wchain_best writes every entry)
+    DevBuf<double> m, tree, stats, keys, targets, out;
+    DevBuf<int64_t> index;
+};
+
 // Whether the quadratic term of the Q' form may run over the trapezoidal root of Q' (quad_build).  false: only with VMX_QUAD_ROOT=1.
 constexpr bool QUAD_ROOT_DEFAULT = true;
 
@@ -1880,6 +1900,7 @@ struct vmx_engine {
     EnsWorkspace* ensws = nullptr;
     std::vector<vmx_chain_store*> chain_stores;    // every store created on this engine and not yet destroyed
     vmx_chain_store* chain_store = nullptr;        // the one the ensemble runs append to (vmx_ensemble_set_chain_store)
+    std::vector<vmx_sample_store*> sample_stores;  // every sample store created on this engine and not yet destroyed
     NsWorkspace* nsws = nullptr;
     SmcWorkspace* smcws = nullptr;
     // a likelihood session (vmx_fit_migrad and the three samplers): lane_wait, when set, is the event at which the rows of the second
@@ -2067,6 +2088,7 @@ struct vmx_engine {
         delete fitws;
         delete ensws;
         for (auto* c : chain_stores) delete c;
+        for (auto* c : sample_stores) delete c;
         delete nsws;
         delete smcws;
         if (pin_theta) (void)hipHostFree(pin_theta);
@@ -5001,6 +5023,7 @@ static vmx_engine* clone_lane(vmx_engine* e)
     auto* L = new vmx_engine(*e);
     // what the copy must not share (or free)
     L->lanes.clear(); L->n_lanes = 1; L->lane_calls = 0;
+    L->sample_stores.clear();
     L->chain_stores.clear(); L->chain_store = nullptr;      // (the stores belong to the engine they were created on, not to its lanes)
     L->fitws = nullptr; L->ensws = nullptr; L->nsws = nullptr; L->smcws = nullptr; L->lane_wait = nullptr; L->ev_rows = nullptr; L->ev_lane = nullptr; L->call_mock = nullptr;
     L->stream = nullptr; L->cur = nullptr; L->aux.clear(); L->ev_join.clear(); L->ev_fork = nullptr;
@@ -6547,6 +6570,449 @@ int vmx_chain_store_best(vmx_chain_store* s, int64_t first_row, double* lnl_max,
         row[k] = index[k] < 0 ? -1 : index[k] / W;
         walker[k] = index[k] < 0 ? -1 : (int32_t)(index[k] % W);
     }
+    return 0;
+}
+
+// ---- weighted, ragged sample sets (vmx_chain_weighted.h): the store, its summary, order statistics and best point
+static_assert(VMX_SAMPLE_MAX_TARGETS == vmx_wchain::MAX_TARGETS, "targets of an order-statistics call");
+static_assert(vmx_wchain::MAX_TARGETS <= CHAIN_THREADS && vmx_wchain::MAX_TARGETS * vmx_select::BINS * (int)sizeof(uint64_t) <= 32 * 1024,
+              "the weighted select's histograms");
+
+namespace {
+
+constexpr int WCHAIN_TILE = 4096;       // doubles of LDS for a tree's terms: sets of up to 8192 rows never leave it
+constexpr int WCHAIN_STATS = 4;         // w_max, S, s2, M in front of a set's mean and covariance
+
+struct WchainDev {
+    const double* x; const double* lnl; const double* w;    // [E][capacity][n], [E][capacity], [E][capacity]
+    const int64_t* counts;              // [E]
+    uint64_t* m;                        // [E][capacity]: the integer weights
+    double* tree;                       // [E][half]: the terms of a tree too long for the LDS
+    double* stats;                      // [E][WCHAIN_STATS + n + n n]
+    uint64_t* keys;                     // [E][n][capacity]: the keys of a column, contiguous
+    const uint64_t* targets;            // [E][U]: non-decreasing per set
+    uint64_t* values;                   // [E][n][U]: the bits of the order statistics
+    double* best_lnl; double* best_x;   // [E], [E][n] (best_x nullptr: not wanted)
+    int64_t* best_index;                // [E]: -1 for none
+    int64_t capacity, half;
+    int32_t E, n, U;
+};
+
+__device__ inline int64_t wchain_stride(int n) { return WCHAIN_STATS + n + (int64_t)n * n; }
+
+// The stride-halving tree (vmx_chain_weighted.h) of term(0) ... term(count - 1), count >= 1, by the whole work-group: the first
+// level is formed from the terms themselves, the others in place in buf [padded(count) / 2].  Every thread gets the sum; the
+// loops stride by the block, so no sum depends on its size.
+extern "C++" template <class F>         // (this stretch of the file has C linkage)
+__device__ inline double wchain_tree(F term, int64_t count, double* buf)
+{
+    const int64_t h = vmx_wchain::padded(count) / 2;
+    for (int64_t i = threadIdx.x; i < h; i += blockDim.x) {
+        const double a = i < count ? term(i) : 0.0, b = i + h < count ? term(i + h) : 0.0;
+        buf[i] = vmx_wchain::add(a, b);
+    }
+    __syncthreads();
+    for (int64_t s = h / 2; s >= 1; s /= 2) {
+        for (int64_t i = threadIdx.x; i < s; i += blockDim.x) buf[i] = vmx_wchain::add(buf[i], buf[i + s]);
+        __syncthreads();
+    }
+    const double r = buf[0];
+    __syncthreads();
+    return r;
+}
+
+// One work-group per set: w_max (any order), S and s2 (trees), the integer weights and their sum M (an integer sum: LDS atomics)
+__global__ __launch_bounds__(CHAIN_THREADS) void k_wchain_scale(WchainDev C)
+{
+    __shared__ double tile[WCHAIN_TILE];
+    __shared__ double top[CHAIN_THREADS];
+    __shared__ unsigned long long total;
+    const int tid = threadIdx.x, e = blockIdx.x;
+    const int64_t count = C.counts[e];
+    const double* w = C.w + (int64_t)e * C.capacity;
+    double* st = C.stats + (int64_t)e * wchain_stride(C.n);
+    if (count < 1) {
+        if (tid == 0) {
+            st[0] = 0.0; st[1] = 0.0; st[2] = vmx_wchain::canonical_nan();
+            reinterpret_cast<uint64_t*>(st)[3] = 0;
+        }
+        return;
+    }
+    double mine = 0.0;
+    for (int64_t i = tid; i < count; i += CHAIN_THREADS) mine = vmx_wchain::larger(mine, w[i]);
+    top[tid] = mine;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    for (int s = CHAIN_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) top[tid] = vmx_wchain::larger(top[tid], top[tid + s]);
+        __syncthreads();
+    }
+    const double w_max = top[0];
+    double* buf = vmx_wchain::padded(count) / 2 <= WCHAIN_TILE ? tile : C.tree + (int64_t)e * C.half;
+    const double S = wchain_tree([=](int64_t i) { return w[i]; }, count, buf);
+    const double s2 = wchain_tree([=](int64_t i) { return vmx_wchain::square_term(w[i], S); }, count, buf);
+    uint64_t* m = C.m + (int64_t)e * C.capacity;
+    unsigned long long part = 0;
+    for (int64_t i = tid; i < count; i += CHAIN_THREADS) {
+        const uint64_t mi = vmx_wchain::integer_weight(w[i], w_max);
+        m[i] = mi;
+        part += mi;
+    }
+    atomicAdd(&total, part);
+    __syncthreads();
+    if (tid == 0) {
+        st[0] = w_max; st[1] = S; st[2] = s2;
+        reinterpret_cast<uint64_t*>(st)[3] = total;
+    }
+}
+
+// One work-group per set, behind k_wchain_scale: the means, a tree per column, then the covariance, a tree per pair i >= j in the
+// order of k_chain_moments' pairs, and n_eff into the slot of s2
+__global__ __launch_bounds__(CHAIN_THREADS) void k_wchain_moments(WchainDev C)
+{
+    __shared__ double tile[WCHAIN_TILE];
+    __shared__ double mean[VMX_ENS_MAXN];
+    const int tid = threadIdx.x, e = blockIdx.x, n = C.n;
+    const int64_t count = C.counts[e];
+    const double* w = C.w + (int64_t)e * C.capacity;
+    const double* x = C.x + (int64_t)e * C.capacity * n;
+    double* st = C.stats + (int64_t)e * wchain_stride(n);
+    double* out_mean = st + WCHAIN_STATS;
+    double* cov = out_mean + n;
+    if (count < 1) {
+        for (int q = tid; q < n + n * n; q += CHAIN_THREADS) out_mean[q] = vmx_wchain::canonical_nan();
+        return;
+    }
+    const double S = st[1], s2 = st[2];
+    __syncthreads();                    // (s2 is read by every thread before thread 0 puts n_eff in its place)
+    double* buf = vmx_wchain::padded(count) / 2 <= WCHAIN_TILE ? tile : C.tree + (int64_t)e * C.half;
+    for (int d = 0; d < n; ++d) {
+        const double sum = wchain_tree([=](int64_t i) { return vmx_wchain::mean_term(w[i], S, x[i * n + d]); }, count, buf);
+        if (tid == 0) {
+            const double v = vmx_wchain::mean_of(S, sum);
+            mean[d] = v;
+            out_mean[d] = v;
+        }
+    }
+    __syncthreads();
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j <= i; ++j) {
+            const double mi = mean[i], mj = mean[j];
+            const double sum = wchain_tree([=](int64_t k) { return vmx_wchain::cov_term(w[k], S, x[k * n + i], mi, x[k * n + j], mj); }, count, buf);
+            if (tid == 0) {
+                const double v = vmx_wchain::covariance_of(S, s2, sum);
+                cov[i * n + j] = v;
+                cov[j * n + i] = v;
+            }
+        }
+    if (tid == 0) st[2] = vmx_wchain::n_eff_of(S, s2);
+}
+
+// The keys of every set's rows, x[e][i][d] -> keys[e][d][i] for i < count[e]: the twin of k_chain_keys
+__global__ __launch_bounds__(CHAIN_THREADS) void k_wchain_keys(WchainDev C)
+{
+    const int64_t per = C.capacity * C.n, total = (int64_t)C.E * per;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t e = g / per, q = g % per, i = q / C.n;
+        const int d = (int)(q % C.n);
+        if (i < C.counts[e]) C.keys[(e * C.n + d) * C.capacity + i] = vmx_select::key(C.x[g]);
+    }
+}
+
+// One work-group per (set, column), behind k_wchain_scale and k_wchain_keys: k_chain_select with sums of the integer weights in
+// the histograms (64-bit integer LDS atomics: the sums do not depend on their order; a wave whose keys all fall into one bin adds
+// its weights across the wave by shuffles and adds once) and the walk of vmx_chain_weighted.h.  A set without rows or without
+// weight answers the canonical NaN.
+__global__ __launch_bounds__(CHAIN_THREADS) void k_wchain_select(WchainDev C)
+{
+    using namespace vmx_select;
+    __shared__ unsigned long long hist[vmx_wchain::MAX_TARGETS * BINS];
+    __shared__ uint64_t prefix[vmx_wchain::MAX_TARGETS], group_prefix[vmx_wchain::MAX_TARGETS], left[vmx_wchain::MAX_TARGETS];
+    __shared__ int group[vmx_wchain::MAX_TARGETS];
+    __shared__ int groups;
+    const int tid = threadIdx.x, lane = tid & 63, U = C.U;
+    const int64_t e = blockIdx.x / C.n, N = C.counts[e];
+    const uint64_t M = reinterpret_cast<const uint64_t*>(C.stats + e * wchain_stride(C.n))[3];
+    if (N < 1 || M == 0) {
+        if (tid < U) C.values[(int64_t)blockIdx.x * U + tid] = CANONICAL_NAN;
+        return;
+    }
+    const uint64_t* keys = C.keys + (int64_t)blockIdx.x * C.capacity;
+    const uint64_t* m = C.m + e * C.capacity;
+    if (tid < U) { prefix[tid] = 0; left[tid] = C.targets[e * U + tid]; }
+    __syncthreads();
+    if (tid == 0) groups = regroup(prefix, U, group, group_prefix);
+    __syncthreads();
+    for (int p = 0; p < PASSES; ++p) {
+        const int G = groups;
+        for (int q = tid; q < G * BINS; q += blockDim.x) hist[q] = 0;
+        __syncthreads();
+        for (int64_t base = 0; base < N; base += blockDim.x) {          // (every lane of a wave takes every turn: the ballots below)
+            const int64_t i = base + tid;
+            int slot = -1;
+            unsigned long long mine = 0;
+            if (i < N) {
+                const uint64_t k = keys[i];
+                const int at = find_group(group_prefix, G, leading(k, p));
+                if (at >= 0) { slot = at * BINS + digit(k, p); mine = m[i]; }
+            }
+            const unsigned long long active = __ballot(slot >= 0);
+            if (active) {
+                const int leader = __ffsll(active) - 1;
+                const int slot0 = __shfl(slot, leader);
+                const unsigned long long same = __ballot(slot == slot0);
+                if (same == active) {
+                    unsigned long long sum = mine;                      // (0 in the lanes without a key)
+                    for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
+                    if (lane == leader) atomicAdd(&hist[slot0], sum);
+                } else if (slot >= 0) {
+                    atomicAdd(&hist[slot], mine);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid < U) {
+            uint64_t l = left[tid];
+            prefix[tid] = (prefix[tid] << 8) | (uint64_t)vmx_wchain::walk(reinterpret_cast<const uint64_t*>(hist) + group[tid] * BINS, l);
+            left[tid] = l;
+        }
+        __syncthreads();
+        if (tid == 0) groups = regroup(prefix, U, group, group_prefix);
+        __syncthreads();
+    }
+    if (tid < U) C.values[(int64_t)blockIdx.x * U + tid] = unkey(prefix[tid]);
+}
+
+// One work-group per set: k_chain_best over the rows [0, count[e])
+__global__ __launch_bounds__(CHAIN_THREADS) void k_wchain_best(WchainDev C)
+{
+    using namespace vmx_select;
+    __shared__ double value[CHAIN_THREADS];
+    __shared__ int64_t index[CHAIN_THREADS];
+    const int tid = threadIdx.x, e = blockIdx.x, n = C.n;
+    const int64_t count = C.counts[e];
+    const double* lnl = C.lnl + (int64_t)e * C.capacity;
+    double best = 0.0;
+    int64_t at = -1;
+    for (int64_t q = tid; q < count; q += CHAIN_THREADS) {
+        const double v = lnl[q];
+        const int64_t i = v != v ? -1 : q;          // (vmx_select::candidate: a NaN is none)
+        if (wins(v, i, best, at)) { best = v; at = i; }
+    }
+    value[tid] = best;
+    index[tid] = at;
+    __syncthreads();
+    for (int s = CHAIN_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s && wins(value[tid + s], index[tid + s], value[tid], index[tid])) {
+            value[tid] = value[tid + s];
+            index[tid] = index[tid + s];
+        }
+        __syncthreads();
+    }
+    const int64_t won = index[0];
+    if (tid == 0) {
+        C.best_index[e] = won;
+        C.best_lnl[e] = won < 0 ? double_of(CANONICAL_NAN) : value[0];
+    }
+    if (C.best_x)
+        for (int d = tid; d < n; d += CHAIN_THREADS)
+            C.best_x[(int64_t)e * n + d] = won < 0 ? double_of(CANONICAL_NAN) : C.x[((int64_t)e * C.capacity + won) * n + d];
+}
+
+// what every reduction of a sample store reads
+static WchainDev wchain_dev(const vmx_sample_store* s)
+{
+    WchainDev C{};
+    C.x = s->x.p; C.lnl = s->lnl.p; C.w = s->w.p; C.counts = s->counts.p;
+    C.capacity = s->capacity; C.half = vmx_wchain::padded(s->capacity) / 2; C.E = s->E; C.n = s->n;
+    return C;
+}
+
+// the scratch of k_wchain_scale, and the kernel on `st`
+static int wchain_scale(vmx_sample_store* s, WchainDev& C, hipStream_t st)
+{
+    const size_t E = (size_t)s->E, n = (size_t)s->n;
+    if (chain_scratch(s->m, E * (size_t)s->capacity) || chain_scratch(s->tree, E * (size_t)C.half) ||
+        chain_scratch(s->stats, E * (WCHAIN_STATS + n + n * n)))
+        return -2;
+    C.m = reinterpret_cast<uint64_t*>(s->m.p); C.tree = s->tree.p; C.stats = s->stats.p;
+    hipLaunchKernelGGL(k_wchain_scale, dim3(s->E), dim3(CHAIN_THREADS), 0, st, C);
+    return 0;
+}
+
+}  // namespace
+
+int vmx_sample_store_create(vmx_engine* e, int32_t E, int32_t n, int64_t capacity_rows, vmx_sample_store** out)
+{
+    const std::string name("vmx_sample_store_create");
+    REQUIRE(e && out, name);
+    REQUIRE(E >= 1 && n >= 1 && n <= VMX_ENS_MAXN && capacity_rows >= 0 && capacity_rows <= vmx_wchain::MAX_COUNT,
+            name + ": E >= 1, 1 <= n <= VMX_ENS_MAXN, 0 <= capacity_rows < 2^31");
+    REQUIRE(chain_fits(E, 1, n, capacity_rows), name + ": the store is too large");
+    HIP_OK(hipSetDevice(e->device));
+    vmx_sample_store* s = new vmx_sample_store();
+    s->engine = e; s->E = E; s->n = n; s->capacity = capacity_rows;
+    const size_t slots = (size_t)E * (size_t)capacity_rows;
+    if (chain_alloc(s->x, slots * n) || chain_alloc(s->lnl, slots) || chain_alloc(s->w, slots) ||
+        (s->counts.alloc((size_t)E, true) && ((void)hipGetLastError(), true))) {
+        delete s;
+        return -2;
+    }
+    s->h_counts.assign((size_t)E, 0);
+    s->h_total.assign((size_t)E, 0);
+    e->sample_stores.push_back(s);
+    *out = s;
+    return 0;
+}
+
+int vmx_sample_store_destroy(vmx_sample_store* s)
+{
+    REQUIRE(s, "vmx_sample_store_destroy");
+    vmx_engine* e = s->engine;
+    (void)hipSetDevice(e->device);
+    (void)hipStreamSynchronize(e->stream);
+    e->sample_stores.erase(std::remove(e->sample_stores.begin(), e->sample_stores.end(), s), e->sample_stores.end());
+    delete s;
+    return 0;
+}
+
+int vmx_sample_store_put(vmx_sample_store* s, int32_t set, int64_t count, const double* x, const double* lnl, const double* w)
+{
+    const std::string name("vmx_sample_store_put");
+    REQUIRE(s && count >= 0 && (count == 0 || (x && lnl && w)), name);
+    REQUIRE(set >= 0 && set < s->E, name + ": the set must be one of the store's");
+    REQUIRE(count <= s->capacity, name + ": rows beyond the store's capacity");
+    double w_max = 0.0;
+    for (int64_t i = 0; i < count; ++i) {
+        REQUIRE(vmx_wchain::weight_ok(w[i]), name + ": every weight must be finite and >= 0");
+        w_max = vmx_wchain::larger(w_max, w[i]);
+    }
+    uint64_t total = 0;
+    for (int64_t i = 0; i < count; ++i) total += vmx_wchain::integer_weight(w[i], w_max);
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    const int64_t at = (int64_t)set * s->capacity;
+    if (count > 0) {
+        HIP_OK(hipMemcpyAsync(s->x.p + at * s->n, x, (size_t)count * s->n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s->lnl.p + at, lnl, (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(s->w.p + at, w, (size_t)count * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    HIP_OK(hipMemcpyAsync(s->counts.p + set, &count, sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_OK(hipStreamSynchronize(st));
+    s->h_counts[(size_t)set] = count;
+    s->h_total[(size_t)set] = total;
+    return 0;
+}
+
+int vmx_sample_store_counts(vmx_sample_store* s, int64_t* counts)
+{
+    REQUIRE(s && counts, "vmx_sample_store_counts");
+    std::copy(s->h_counts.begin(), s->h_counts.end(), counts);
+    return 0;
+}
+
+int vmx_sample_store_fetch(vmx_sample_store* s, int32_t set, double* x, double* lnl, double* w)
+{
+    const std::string name("vmx_sample_store_fetch");
+    REQUIRE(s, name);
+    REQUIRE(set >= 0 && set < s->E, name + ": the set must be one of the store's");
+    const int64_t count = s->h_counts[(size_t)set], at = (int64_t)set * s->capacity;
+    if (count == 0 || (!x && !lnl && !w)) return 0;
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    if (x) HIP_OK(hipMemcpyAsync(x, s->x.p + at * s->n, (size_t)count * s->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (lnl) HIP_OK(hipMemcpyAsync(lnl, s->lnl.p + at, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (w) HIP_OK(hipMemcpyAsync(w, s->w.p + at, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+int vmx_sample_store_summary(vmx_sample_store* s, double* S, double* n_eff, double* mean, double* covariance, uint64_t* total, double* w_max)
+{
+    const std::string name("vmx_sample_store_summary");
+    REQUIRE(s && S && n_eff && mean && covariance && total && w_max, name + ": a store and every output");
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    WchainDev C = wchain_dev(s);
+    if (wchain_scale(s, C, st)) return -2;
+    hipLaunchKernelGGL(k_wchain_moments, dim3(s->E), dim3(CHAIN_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    const size_t E = (size_t)s->E, n = (size_t)s->n, stride = WCHAIN_STATS + n + n * n;
+    std::vector<double> got(E * stride);
+    HIP_OK(hipMemcpyAsync(got.data(), s->stats.p, got.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    for (size_t k = 0; k < E; ++k) {
+        const double* g = got.data() + k * stride;
+        w_max[k] = g[0]; S[k] = g[1]; n_eff[k] = g[2];
+        std::memcpy(total + k, g + 3, sizeof(uint64_t));
+        std::memcpy(mean + k * n, g + WCHAIN_STATS, n * sizeof(double));
+        std::memcpy(covariance + k * n * n, g + WCHAIN_STATS + n, n * n * sizeof(double));
+    }
+    return 0;
+}
+
+int vmx_sample_store_order_stats(vmx_sample_store* s, int32_t n_targets, const uint64_t* targets, double* values)
+{
+    const std::string name("vmx_sample_store_order_stats");
+    REQUIRE(s && targets && values, name + ": a store, targets and values");
+    REQUIRE(n_targets >= 1 && n_targets <= VMX_SAMPLE_MAX_TARGETS, name + ": 1 <= n_targets <= VMX_SAMPLE_MAX_TARGETS");
+    const size_t E = (size_t)s->E, n = (size_t)s->n, U = (size_t)n_targets;
+    std::vector<uint64_t> sorted(E * U, 1);
+    std::vector<int> place(E * U, 0);
+    for (size_t k = 0; k < E; ++k) {
+        if (s->h_total[k] == 0) {       // (a set without weight ignores its targets)
+            for (size_t r = 0; r < U; ++r) place[k * U + r] = (int)r;
+            continue;
+        }
+        for (size_t r = 0; r < U; ++r)
+            REQUIRE(targets[k * U + r] >= 1 && targets[k * U + r] <= s->h_total[k], name + ": a target outside [1, M] of its set");
+        vmx_wchain::sort_targets(targets + k * U, n_targets, sorted.data() + k * U, place.data() + k * U);
+    }
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    WchainDev C = wchain_dev(s);
+    if (chain_scratch(s->keys, E * n * (size_t)s->capacity) || chain_scratch(s->targets, E * U) || chain_scratch(s->out, E * n * U)) return -2;
+    C.keys = reinterpret_cast<uint64_t*>(s->keys.p); C.targets = reinterpret_cast<const uint64_t*>(s->targets.p);
+    C.values = reinterpret_cast<uint64_t*>(s->out.p); C.U = n_targets;
+    HIP_OK(hipMemcpyAsync(s->targets.p, sorted.data(), E * U * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (wchain_scale(s, C, st)) return -2;
+    const int64_t total = (int64_t)E * s->capacity * s->n;
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((total + CHAIN_THREADS - 1) / CHAIN_THREADS, 65536));
+    hipLaunchKernelGGL(k_wchain_keys, dim3(blocks), dim3(CHAIN_THREADS), 0, st, C);
+    hipLaunchKernelGGL(k_wchain_select, dim3((unsigned)(E * n)), dim3(CHAIN_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    std::vector<double> found(E * n * U);
+    HIP_OK(hipMemcpyAsync(found.data(), s->out.p, found.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    // the caller's order and repeats (bytes are copied: a value's bits stay its own)
+    for (size_t k = 0; k < E; ++k)
+        for (size_t d = 0; d < n; ++d)
+            for (size_t r = 0; r < U; ++r)
+                std::memcpy(values + (k * n + d) * U + r, found.data() + (k * n + d) * U + place[k * U + r], sizeof(double));
+    return 0;
+}
+
+int vmx_sample_store_best(vmx_sample_store* s, double* lnl_max, int64_t* index, double* position)
+{
+    const std::string name("vmx_sample_store_best");
+    REQUIRE(s && lnl_max && index, name + ": a store, lnl_max and index");
+    vmx_engine* e = s->engine;
+    HIP_OK(hipSetDevice(e->device));
+    const size_t E = (size_t)s->E, En = E * (size_t)s->n;
+    if (chain_scratch(s->out, E + En) || (s->index.n < E && s->index.alloc(E, false) && ((void)hipGetLastError(), true))) return -2;
+    WchainDev C = wchain_dev(s);
+    C.best_lnl = s->out.p; C.best_x = position ? s->out.p + E : nullptr; C.best_index = s->index.p;
+    hipStream_t st = e->stream;
+    hipLaunchKernelGGL(k_wchain_best, dim3(s->E), dim3(CHAIN_THREADS), 0, st, C);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(lnl_max, C.best_lnl, E * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(index, C.best_index, E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (position) HIP_OK(hipMemcpyAsync(position, C.best_x, En * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -384,6 +384,15 @@ def load_library():
     lib.vmx_chain_store_order_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, i64p, dptr]
     lib.vmx_chain_store_best.argtypes = [C.c_void_p, C.c_int64, dptr, i64p, C.POINTER(C.c_int32), dptr]
     lib.vmx_ensemble_set_chain_store.argtypes = [C.c_void_p, C.c_void_p]
+    u64p = C.POINTER(C.c_uint64)
+    lib.vmx_sample_store_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+    lib.vmx_sample_store_destroy.argtypes = [C.c_void_p]
+    lib.vmx_sample_store_put.argtypes = [C.c_void_p, C.c_int32, C.c_int64, dptr, dptr, dptr]
+    lib.vmx_sample_store_counts.argtypes = [C.c_void_p, i64p]
+    lib.vmx_sample_store_fetch.argtypes = [C.c_void_p, C.c_int32, dptr, dptr, dptr]
+    lib.vmx_sample_store_summary.argtypes = [C.c_void_p, dptr, dptr, dptr, dptr, u64p, dptr]
+    lib.vmx_sample_store_order_stats.argtypes = [C.c_void_p, C.c_int32, u64p, dptr]
+    lib.vmx_sample_store_best.argtypes = [C.c_void_p, dptr, i64p, dptr]
     lib.vmx_nested_run.argtypes = [C.c_void_p, C.POINTER(NestedSpec), dptr, dptr, C.POINTER(C.c_int64), C.c_int32, dptr, dptr, iptr,
                                    C.POINTER(NestedOptions), C.POINTER(NestedStats)]
     lib.vmx_nested_run_clustered.argtypes = lib.vmx_nested_run.argtypes + [C.POINTER(NestedClusters)]
@@ -486,7 +495,7 @@ EXPORTED_SYMBOLS = [
     'vmx_add_pipeline', 'vmx_pipeline_set_tracer_evolution', 'vmx_pipeline_set_odd_terms', 'vmx_pipeline_set_odd_operator', 'vmx_set_shotnoise_table',
     'vmx_item_set_additive_template', 'vmx_add_item', 'vmx_item_add_metal', 'vmx_item_set_metal_static', 'vmx_item_set_metal_basis', 'vmx_item_set_metal_kron', 'vmx_set_metal_beta_override', 'vmx_item_add_broadband', 'vmx_item_set_matrix', 'vmx_item_set_matrix_csr',
     'vmx_item_set_mask', 'vmx_item_set_data', 'vmx_item_set_mock_pool', 'vmx_set_mock_index', 'vmx_item_set_mock_factor', 'vmx_item_get_mock_pool', 'vmx_host_alloc', 'vmx_host_free', 'vmx_set_global_invcov', 'vmx_add_prior', 'vmx_finalize',
-    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_chain_store_order_stats', 'vmx_chain_store_best', 'vmx_ensemble_set_chain_store', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_debug_poison_scratch', 'vmx_matvec_device', 'vmx_matmul_host',
+    'vmx_model_size', 'vmx_pipeline_column', 'vmx_eval', 'vmx_eval_device', 'vmx_eval_device_mocks', 'vmx_fit_migrad', 'vmx_ensemble_run', 'vmx_ensemble_run_many', 'vmx_ensemble_run_many_moves', 'vmx_ensemble_run_many_cov', 'vmx_ensemble_cov_factor', 'vmx_ensemble_run_pt', 'vmx_ensemble_run_pt_adapt', 'vmx_ensemble_run_slice', 'vmx_chain_store_create', 'vmx_chain_store_destroy', 'vmx_chain_store_reserve', 'vmx_chain_store_rows', 'vmx_chain_store_append', 'vmx_chain_store_fetch', 'vmx_chain_store_summary', 'vmx_chain_store_order_stats', 'vmx_chain_store_best', 'vmx_ensemble_set_chain_store', 'vmx_sample_store_create', 'vmx_sample_store_destroy', 'vmx_sample_store_put', 'vmx_sample_store_counts', 'vmx_sample_store_fetch', 'vmx_sample_store_summary', 'vmx_sample_store_order_stats', 'vmx_sample_store_best', 'vmx_nested_run', 'vmx_nested_run_clustered', 'vmx_nested_run_phantoms', 'vmx_nested_cluster_points', 'vmx_nested_run_many', 'vmx_nested_run_many_phantoms', 'vmx_smc_run', 'vmx_smc_run_many', 'vmx_smc_run_kept', 'vmx_smc_run_many_kept', 'vmx_derived_const_hint', 'vmx_sync', 'vmx_set_constant_nl_hint', 'vmx_set_direct_pk', 'vmx_set_linear_spectra', 'vmx_item_set_marg_matrix', 'vmx_marg_coeff', 'vmx_marg_coeff_device', 'vmx_marg_layout', 'vmx_set_quadratic_form', 'vmx_set_quadratic_form_kind', 'vmx_set_static_poly', 'vmx_set_mu_quadrature', 'vmx_set_mu_rule_box', 'vmx_get_mu_nodes', 'vmx_set_parameter_transform', 'vmx_stream', 'vmx_last_stream', 'vmx_set_lanes', 'vmx_debug_read', 'vmx_debug_math', 'vmx_debug_poison_scratch', 'vmx_matvec_device', 'vmx_matmul_host',
     'vmx_set_profiling', 'vmx_set_profiling_mask', 'vmx_get_timings', 'vmx_kernel_name']
 
 
@@ -833,6 +842,111 @@ class ChainStore:
             if self.engine._attached is self:
                 self.engine.attach_chain_store(None)
             self.engine.lib.vmx_chain_store_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SampleStore:
+    """E weighted, ragged sample sets over n columns kept on the device (include/vegamx.h: vmx_sample_store_*), made by
+    :meth:`Engine.sample_store`: the posterior samples of nested or SMC runs, reduced where they are.  vega_amd/weighted.py is the
+    same numbers on the host, bit for bit."""
+
+    def __init__(self, engine, E, n, capacity):
+        self.engine, self.E, self.n, self.capacity = engine, int(E), int(n), int(capacity)
+        self._h = None
+        handle = C.c_void_p()
+        engine._check(engine.lib.vmx_sample_store_create(engine._h, self.E, self.n, self.capacity, C.byref(handle)))
+        self._h = handle
+
+    def _handle(self):
+        if not self._h or not self.engine._h:
+            raise EngineError('the sample store is closed')
+        return self._h
+
+    def put(self, e, x, lnl, w):
+        """Replace set ``e`` by the rows ``x`` [count, n], ``lnl`` [count] and weights ``w`` [count] (finite, >= 0; they need not
+        sum to 1); count 0 empties it."""
+        x, lnl, w = _f64(x), _f64(lnl), _f64(w)
+        if x.ndim != 2 or x.shape[1] != self.n or lnl.shape != x.shape[:1] or w.shape != x.shape[:1]:
+            raise ValueError(f'x [count, {self.n}], lnl [count], w [count]')
+        self.engine._check(self.engine.lib.vmx_sample_store_put(self._handle(), int(e), x.shape[0], _dp(x), _dp(lnl), _dp(w)))
+
+    def counts(self):
+        """The rows of every set [E]."""
+        counts = np.zeros(self.E, dtype=np.int64)
+        self.engine._check(self.engine.lib.vmx_sample_store_counts(self._handle(), counts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return counts
+
+    def fetch(self, e):
+        """Set ``e`` as (x [count, n], lnl [count], w [count])."""
+        e = int(e)
+        if not 0 <= e < self.E:
+            raise ValueError(f'set: 0 .. {self.E - 1}')
+        count = int(self.counts()[e])
+        x, lnl, w = np.empty((count, self.n)), np.empty(count), np.empty(count)
+        self.engine._check(self.engine.lib.vmx_sample_store_fetch(self._handle(), e, _dp(x), _dp(lnl), _dp(w)))
+        return x, lnl, w
+
+    def summary(self):
+        """``dict(count [E], S [E], n_eff [E], mean [E, n], sd [E, n], covariance [E, n, n], total [E] (Python integers), w_max
+        [E])`` of every set, computed where the rows are (vmx_sample_store_summary;
+        :func:`vega_amd.weighted.weighted_summary` per set is the same bits)."""
+        E, n = self.E, self.n
+        S, n_eff, w_max, mean, cov = np.empty(E), np.empty(E), np.empty(E), np.empty((E, n)), np.empty((E, n, n))
+        total = np.zeros(E, dtype=np.uint64)
+        self.engine._check(self.engine.lib.vmx_sample_store_summary(
+            self._handle(), _dp(S), _dp(n_eff), _dp(mean), _dp(cov), total.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(w_max)))
+        with np.errstate(invalid='ignore'):
+            sd = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+        return dict(count=self.counts(), S=S, n_eff=n_eff, mean=mean, sd=sd, covariance=cov, total=[int(v) for v in total.tolist()],
+                    w_max=w_max)
+
+    def order_statistics(self, targets):
+        """Weighted order statistics of every (set, column), found where the rows are (vmx_sample_store_order_stats;
+        :func:`vega_amd.weighted.weighted_order_statistics` is the same bits): [E, n, R] for ``targets`` [E, R] (or [R], the same for
+        every set) of whole numbers in [1, M_e], 1 .. 16 per set in any order, repeats allowed."""
+        given = list(targets)
+        rows = [list(r) for r in given] if given and np.ndim(given[0]) else [given] * self.E
+        if len(rows) != self.E or any(len(r) != len(rows[0]) for r in rows):
+            raise ValueError(f'targets [{self.E}, R] or [R]')
+        if any(int(t) < 0 or int(t) >= 2**64 for r in rows for t in r):
+            raise ValueError('targets: whole numbers in [1, M]')
+        t = np.array([[int(v) for v in r] for r in rows], dtype=np.uint64).reshape(self.E, -1)
+        values = np.empty((self.E, self.n, max(t.shape[1], 1)))
+        self.engine._check(self.engine.lib.vmx_sample_store_order_stats(
+            self._handle(), t.shape[1], t.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(values)))
+        return values
+
+    def weighted_quantiles(self, q, total=None):
+        """The inverted-CDF quantiles ``q`` (1 .. 16 values in [0, 1]) of every (set, column), [E, n, Q]: the order statistics at
+        ``max(1, ceil(q M_e))``, the targets computed exactly on the host (:func:`vega_amd.weighted.weighted_targets`).  ``total``:
+        the M of every set when a summary has handed them out already."""
+        from .weighted import weighted_targets
+        from .ensemble import check_quantiles
+        q = check_quantiles(q)
+        total = self.summary()['total'] if total is None else total
+        return self.order_statistics([weighted_targets(q, M) if M > 0 else [1] * q.size for M in total])
+
+    def best(self, position=True):
+        """The row of the largest lnL of every set (vmx_sample_store_best; :func:`vega_amd.weighted.weighted_best`):
+        ``dict(lnl_max [E], index [E], best [E, n])``; without ``position`` no ``best``."""
+        top, index = np.empty(self.E), np.zeros(self.E, dtype=np.int64)
+        at = np.empty((self.E, self.n)) if position else None
+        self.engine._check(self.engine.lib.vmx_sample_store_best(
+            self._handle(), _dp(top), index.ctypes.data_as(C.POINTER(C.c_int64)), None if at is None else _dp(at)))
+        out = dict(lnl_max=top, index=index)
+        if position:
+            out['best'] = at
+        return out
+
+    def close(self):
+        if self._h and self.engine._h:
+            self.engine.lib.vmx_sample_store_destroy(self._h)
         self._h = None
 
     def __del__(self):
@@ -1459,6 +1573,10 @@ class Engine:
     def chain_store(self, E, W, n, capacity):
         """A :class:`ChainStore` on this engine's device: ``capacity`` rows of E ensembles of W walkers over n columns."""
         return ChainStore(self, E, W, n, capacity)
+
+    def sample_store(self, E, n, capacity):
+        """A :class:`SampleStore` on this engine's device: E weighted sample sets of up to ``capacity`` rows over n columns."""
+        return SampleStore(self, E, n, capacity)
 
     def attach_chain_store(self, store=None):
         """While ``store`` is attached, every ``ensemble_run*`` call appends the rows it records to it on the device (include/vegamx.h:

@@ -3079,7 +3079,7 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
     if cfg['sampler'] == 'SMC':
         sampler = mc.sample_mocks(mocks=mocks, seed=cfg['seed'], scale=scale, sample_params=sample_params, driver=cfg['driver'],
                                   sampler='smc', particles=cfg['particles'], ess=cfg['ess'], sweeps=cfg['sweeps'],
-                                  **{key: cfg[key] for key in ('n_total', 'recycle') if key in cfg})
+                                  **{key: cfg[key] for key in ('n_total', 'recycle', 'weighted_quantiles') if key in cfg})
         for m in range(sampler.E):
             sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')
         mc.write_mock_posteriors(cfg['path'])
@@ -3087,7 +3087,8 @@ def _sample_config_mocks(vega, cfg, sample_params, control):
     if cfg['sampler'] == 'Nested':
         sampler = mc.sample_mocks_nested(mocks=mocks, seed=cfg['seed'], scale=scale, sample_params=sample_params,
                                          driver=cfg['driver'], num_live=cfg['num_live'], num_repeats=cfg['num_repeats'],
-                                         threads=cfg['threads'], precision=cfg['precision'], max_iterations=cfg['max_iterations'])
+                                         threads=cfg['threads'], precision=cfg['precision'], max_iterations=cfg['max_iterations'],
+                                         **{key: cfg[key] for key in ('weighted_quantiles',) if key in cfg})
         for m in range(sampler.E):
             if sampler.status[m] != 2:          # (a mock without a finite live lnL has nothing to write: its row of the table says so)
                 sampler.member(m).write(cfg['path'], f'{cfg["name"]}_mock{m}')

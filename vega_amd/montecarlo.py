@@ -471,7 +471,8 @@ class MonteCarlo:
     def sample_mocks(self, num_mocks=None, mocks=None, walkers=None, steps=1000, burn=None, thin=1, seed=0, scale=None,
                      sample_params=None, driver='device', keep_chains=True, fiducial_model=None, sampler='ensemble', particles=None,
                      ess=0.5, sweeps=None, n_total=None, recycle=False, moves=None, gamma0=None, sigma=None, gamma_s=None, mu=None,
-                     tune_steps=None, cov_scale=None, summaries='host', converge=None, quantiles=None):
+                     tune_steps=None, cov_scale=None, summaries='host', converge=None, quantiles=None, weighted_quantiles=None,
+                     weighted_summaries='host'):
         """A posterior for every Monte-Carlo mock, all in one device run: M ensembles advanced together
         (:class:`vega_amd.ensemble.EnsembleSet`), ensemble m compared with mock m and on the Philox stream m.  The reference can
         only do this as one sampler job per mock.  The mocks are drawn as ``run_monte_carlo`` draws them (``num_mocks`` around
@@ -528,6 +529,14 @@ class MonteCarlo:
             raise ValueError("sample_mocks: summaries and converge go with sampler='ensemble'")
         if converge is not None and set(converge) - {'tau_factor', 'tau_rtol', 'check_every'}:
             raise ValueError('sample_mocks: converge takes tau_factor, tau_rtol and check_every')
+        # weighted_summaries='device' (sampler='smc'): mean, sd and covariance come from a sample store on the GPU
+        # (vega_amd.smc.SMCSet.summary); weighted_quantiles=q (1 .. 16 values in [0, 1], with either): mc_posteriors gains
+        # weighted_quantiles, quantile_values [M, n, Q] (the inverted CDF of the weighted chain), lnl_max and best
+        if weighted_quantiles is not None and sampler != 'smc':
+            raise ValueError("sample_mocks: weighted_quantiles go with sampler='smc' (and sample_mocks_nested); the ensemble "
+                             "sampler's chains are unweighted: quantiles")
+        if weighted_summaries not in ('host', 'device'):
+            raise ValueError("sample_mocks: weighted_summaries 'host' or 'device'")
         if quantiles is not None:
             if sampler != 'ensemble':
                 raise ValueError("sample_mocks: quantiles go with sampler='ensemble'")
@@ -535,11 +544,12 @@ class MonteCarlo:
             quantiles = check_quantiles(quantiles)
         return self._sample_mocks(num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                                   fiducial_model, sampler, particles, ess, sweeps, n_total=n_total, recycle=recycle, moves_kw=moves_kw,
-                                  summaries=summaries, converge=converge, quantiles=quantiles)
+                                  summaries=summaries, converge=converge, quantiles=quantiles,
+                                  weighted=(weighted_summaries, weighted_quantiles))
 
     def sample_mocks_nested(self, num_mocks=None, mocks=None, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                             max_iterations=None, seed=0, scale=None, sample_params=None, driver='device', keep_chains=True,
-                            fiducial_model=None, boost_posterior=0.0):
+                            fiducial_model=None, boost_posterior=0.0, summaries='host', weighted_quantiles=None):
         """The evidence and a weighted posterior of every Monte-Carlo mock by nested sampling, M runs advanced together in one
         device run (:class:`vega_amd.nested.NestedSet`: run m on mock m and stream m; ``num_live``, ``num_repeats``, ``threads``,
         ``precision``, ``max_iterations`` its settings; every run ends on its own termination test).  The mocks, ``seed``,
@@ -550,15 +560,22 @@ class MonteCarlo:
         (:class:`NestedSet`): every run keeps the accepted points inside its walks, the samples - and with them the weighted
         mean, sd and covariance - are the boosted chains', and ``mc_posteriors`` gains ``boost_posterior``, ``phantoms`` [M] (kept
         points per mock), ``n_eff`` [M] (the Kish size 1 / sum w^2 of the chain used) and ``log_z_boost`` [M] (a diagnostic:
-        ``log_z`` stays the base run's); at b = 0 the dict has the keys it had.  Returns the set."""
+        ``log_z`` stays the base run's); at b = 0 the dict has the keys it had.  ``summaries='device'``: mean, sd, covariance and
+        ``n_eff`` come from a sample store on the GPU (:meth:`vega_amd.nested.NestedSet.summary`; the default keeps the host
+        expressions and their bits).  ``weighted_quantiles=q`` (1 .. 16 values in [0, 1], with either ``summaries``):
+        ``mc_posteriors`` gains ``weighted_quantiles`` (the q), ``quantile_values`` [M, n, Q] (the inverted CDF of the weighted
+        chain), ``lnl_max`` [M] and ``best`` [M, n].  Returns the set."""
+        if summaries not in ('host', 'device'):
+            raise ValueError("sample_mocks_nested: summaries 'host' or 'device'")
         return self._sample_mocks(num_mocks, mocks, None, 0, None, 1, seed, scale, sample_params, driver, keep_chains, fiducial_model,
                                   'nested', None, 0.5, None, num_live=num_live, num_repeats=num_repeats, threads=threads,
-                                  precision=precision, max_iterations=max_iterations, boost_posterior=boost_posterior)
+                                  precision=precision, max_iterations=max_iterations, boost_posterior=boost_posterior,
+                                  weighted=(summaries, weighted_quantiles))
 
     def _sample_mocks(self, num_mocks, mocks, walkers, steps, burn, thin, seed, scale, sample_params, driver, keep_chains,
                       fiducial_model, sampler, particles, ess, sweeps, num_live=None, num_repeats=None, threads=None, precision=1e-3,
                       max_iterations=None, boost_posterior=0.0, n_total=None, recycle=False, moves_kw=None, summaries='host',
-                      converge=None, quantiles=None):
+                      converge=None, quantiles=None, weighted=('host', None)):
         """What :meth:`sample_mocks` and :meth:`sample_mocks_nested` do alike: the mocks, their pools on the engine, the set of the
         kind ``sampler`` names, its run and the summaries."""
         from .ensemble import EnsembleSet, SampledBox
@@ -585,6 +602,9 @@ class MonteCarlo:
             raise ValueError(f'sample_mocks: num_mocks = {num_mocks}, but {M} mocks were passed')
         n = SampledBox(vega, sample_params).n
         smc, nested = sampler == 'smc', sampler == 'nested'
+        if weighted[1] is not None:
+            from .ensemble import check_quantiles
+            weighted = (weighted[0], check_quantiles(weighted[1]))
         if not smc and not nested:
             walkers = max(32, 2 * n) if walkers is None else int(walkers)
             steps, thin = int(steps), int(thin)
@@ -641,6 +661,7 @@ class MonteCarlo:
                 seed=int(seed), driver=sampler.driver, stats=dict(sampler.stats),
                 points=np.array([part[1].size for part in found], dtype=np.int64), n_eff=sampler.n_eff(),
                 log_z_recycled=sampler.recycled_log_evidence(), n_total=sampler.n_total, recycle=sampler.recycle)
+            self._weighted_posteriors(sampler, weighted)
             self.mc_chains = found if keep_chains else None
             self.mc_chain_lnl = [part[1] for part in found] if keep_chains else None
             return sampler
@@ -654,6 +675,7 @@ class MonteCarlo:
                 stages=sampler.stage.copy(), status=sampler.status.copy(), acceptance=sampler.stats['per_run'][:, 0] / moved,
                 particles=sampler.particles, ess=sampler.ess, sweeps=sampler.sweeps, seed=int(seed), driver=sampler.driver,
                 stats=dict(sampler.stats))
+            self._weighted_posteriors(sampler, weighted)
             self.mc_chains = pts if keep_chains else None
             self.mc_chain_lnl = lnl if keep_chains else None
             return sampler
@@ -680,6 +702,7 @@ class MonteCarlo:
                     phantoms=np.array([0 if part is None else sampler.phantoms(m)['lnl'].size for m, part in enumerate(found)],
                                       dtype=np.int64),
                     n_eff=np.array([np.nan if part is None else 1.0 / np.sum(part[2] * part[2]) for part in found]))
+            self._weighted_posteriors(sampler, weighted, n_eff=True)
             self.mc_chains = found if keep_chains else None
             self.mc_chain_lnl = [None if part is None else part[1] for part in found] if keep_chains else None
             return sampler
@@ -718,6 +741,20 @@ class MonteCarlo:
         self.mc_chain_lnl = sampler.get_log_lik() if keep_chains else None
         return sampler
 
+    def _weighted_posteriors(self, sampler, weighted, n_eff=False):
+        """``summaries='device'`` / ``weighted_quantiles`` of the nested and SMC sets: with neither, ``mc_posteriors`` stays what
+        the host expressions made it, key for key and bit for bit."""
+        where, q = weighted
+        if where != 'device' and q is None:
+            return
+        summ = sampler.summary(weighted_quantiles=q, where=where)
+        if where == 'device':
+            self.mc_posteriors.update(mean=summ['mean'], sd=summ['sd'], covariance=summ['covariance'])
+            if n_eff:
+                self.mc_posteriors['n_eff'] = summ['n_eff']
+        if q is not None:
+            self.mc_posteriors.update({key: summ[key] for key in ('weighted_quantiles', 'quantile_values', 'lnl_max', 'best')})
+
     def write_mock_posteriors(self, directory, cpu_id=None, overwrite=True):
         """`mock_posteriors[_<cpu_id>].fits` under ``directory``: one table ``POSTERIORS`` with one row per mock of
         :meth:`sample_mocks` - the scalar columns ``<par>_mean``, ``<par>_sd``, ``<par>_tau`` per sampled parameter, ``acceptance``,
@@ -731,7 +768,8 @@ class MonteCarlo:
         ``sample_mocks_nested`` ``<par>_mean``, ``<par>_sd``, ``log_z``, ``log_z_err``, ``info``, ``iterations``,
         ``status``, ``covariance`` and the header keys ``SAMPLER``, ``NUMLIVE``, ``NREPEATS``, ``THREADS``, ``PRECISN``, ``SEED``
         (with ``boost_posterior > 0`` also the columns ``phantoms``, ``n_eff``, ``log_z_boost`` and the header key ``BOOST``).
-        Returns the path."""
+        After ``weighted_quantiles=q`` of either also ``<par>_q<k>``, ``<par>_best``, ``lnl_max`` and the header keys ``NQUANT``,
+        ``QUANT<k>`` and ``QMETHOD = 'inverted_cdf'``.  Returns the path."""
         from pathlib import Path
         from . import fitslite
         post = getattr(self, 'mc_posteriors', None)
@@ -783,6 +821,15 @@ class MonteCarlo:
                 cols += [('lnl_max', 'D', post['lnl_max'])]
                 header['NQUANT'] = int(q.size)
                 header.update({f'QUANT{k}': float(v) for k, v in enumerate(q)})
+        if 'weighted_quantiles' in post:        # (nested and SMC sets, when asked: the inverted CDF of the weighted chain)
+            q = np.asarray(post['weighted_quantiles'], dtype=np.float64)
+            for j, nm in enumerate(names):
+                cols += [(f'{nm}_q{k}', 'D', np.ascontiguousarray(post['quantile_values'][:, j, k])) for k in range(q.size)]
+                cols += [(f'{nm}_best', 'D', np.ascontiguousarray(post['best'][:, j]))]
+            cols += [('lnl_max', 'D', post['lnl_max'])]
+            header['NQUANT'] = int(q.size)
+            header.update({f'QUANT{k}': float(v) for k, v in enumerate(q)})
+            header['QMETHOD'] = 'inverted_cdf'
         directory = Path(directory)
         directory.mkdir(parents=True, exist_ok=True)
         path = directory / ('mock_posteriors.fits' if cpu_id is None else f'mock_posteriors_{cpu_id}.fits')

@@ -1208,6 +1208,16 @@ class NestedRunSet:
         """The kept phantom points of run ``e`` in the canonical order: the dict of :meth:`NestedRun.phantoms`."""
         return self.runs[int(e)].phantoms()
 
+    def summary(self, weighted_quantiles=None, boost=None, where='device'):
+        """The weighted summary of every run's :meth:`samples` (``boost`` as there): ``dict(count [E], n_eff [E] (Kish), mean
+        [E, n], sd [E, n], covariance [E, n, n])``, and with ``weighted_quantiles=q`` (1 .. 16 values in [0, 1]) also
+        ``weighted_quantiles`` (the q), ``quantile_values`` [E, n, Q] (the inverted CDF), ``lnl_max`` [E] and ``best`` [E, n].
+        ``where='device'`` reduces the samples in a sample store on the GPU (vega_amd/csrc/vmx_chain_weighted.h), ``'host'``, the
+        ``python`` driver and an engine group with :mod:`vega_amd.weighted`: the same bits.  A run without a finite live lnL is a
+        set without rows: count 0 and NaNs."""
+        from .weighted import summarise_runs
+        return summarise_runs(self, self.samples(boost=boost), weighted_quantiles, where)
+
     def boost_log_evidence(self):
         """log Z_boost [E] (:meth:`NestedRun.boost_log_evidence`: a diagnostic, never the reported evidence); NaN for a run
         without a finite live lnL."""
@@ -1350,6 +1360,8 @@ def nested_settings(main_config, sample_params):
             raise ValueError('[Nested] boost_posterior: a finite number, at least 0')
     if 'mocks' in sec:
         out['mocks'] = E._parse_mocks(sec, main_config, 'Nested', 'a nested run')
+    from .weighted import parse_weighted_quantiles
+    parse_weighted_quantiles(sec, out, 'Nested')
     if 'together' in sec:
         try:
             out['together'] = sec.getboolean('together')

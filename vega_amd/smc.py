@@ -949,6 +949,15 @@ class SMCSet(E.EngineSampler):
         runs = [self._bare_member(e).samples(recycle) for e in range(self.E)]
         return [r[0] for r in runs], [r[1] for r in runs], [r[2] for r in runs]
 
+    def summary(self, weighted_quantiles=None, recycle=None, where='device'):
+        """The weighted summary of every run's :meth:`samples` (``recycle`` as there): ``dict(count [E], n_eff [E] (Kish), mean
+        [E, n], sd [E, n], covariance [E, n, n])``, and with ``weighted_quantiles=q`` (1 .. 16 values in [0, 1]) also
+        ``weighted_quantiles`` (the q), ``quantile_values`` [E, n, Q] (the inverted CDF), ``lnl_max`` [E] and ``best`` [E, n].
+        ``where='device'`` reduces the samples in a sample store on the GPU (vega_amd/csrc/vmx_chain_weighted.h), ``'host'``, the
+        ``python`` driver and an engine group with :mod:`vega_amd.weighted`: the same bits."""
+        from .weighted import summarise_runs
+        return summarise_runs(self, list(zip(*self.samples(recycle))), weighted_quantiles, where)
+
     def n_eff(self, recycle=None):
         """[E]: Kish's sample size of every run's chain (:meth:`SMCRun.n_eff`)."""
         self._ran()
@@ -1023,6 +1032,8 @@ def smc_settings(main_config, sample_params):
         raise ValueError('[SMC] max_stages must be positive')
     if 'mocks' in sec:
         out['mocks'] = E._parse_mocks(sec, main_config, 'SMC', 'an SMC run')
+    from .weighted import parse_weighted_quantiles
+    parse_weighted_quantiles(sec, out, 'SMC')
     if 'together' in sec:
         try:
             out['together'] = sec.getboolean('together')
